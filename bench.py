@@ -5,6 +5,8 @@ N_mc = 256, batch 512 PER GPU) -- BASELINE.json configs[2] at 1 GPU, configs[3]
 at 8 GPUs (weak scaling, 512 rows per rank).
 
     python bench.py --gpus 1 --steps 3 --warmup 1
+    python bench.py --gpus 1 --steps 3 --warmup 1 --full                  # + roofline, cpu_baseline, parity_check
+    python bench.py --gpus 1 --steps 3 --warmup 1 --dump-outputs DIR      # + DIR/<name>.npy of the last timed step
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 \
         --master-port P bench.py --gpus N --steps K --warmup W
 
@@ -12,9 +14,16 @@ One "step" = one whole sampling call: sharded MC pre-phase + ratio estimator +
 all_gather of the MC set + the guided Euler loop + the gather of the outputs,
 on noise that is already resident in HBM.  Synthetic parameters
 (ratio_guided_multimodal_fm_amd/synth.py, no trained checkpoint exists) and
-CPU-generator noise seeded 42 (the reference CLI's default seed).
+CPU-generator noise seeded 42 (the reference CLI's default seed): the inputs are
+the same in every run with the same arguments.
 
-Rank 0 prints ONE JSON line with the driver's contract fields plus
+A plain run sets up, warms up, times --steps calls and prints ONE JSON line (rank 0) with the
+headline fields (metric, value, unit, higher_is_better, dtype, ms_per_step, ...).
+--dump-outputs DIR writes the samples the LAST timed call returned, as float32 DIR/x_mnist32.npy
+[B, 1, 32, 32] and DIR/y_svhn.npy [B, 3, 32, 32] (a fixed, seeded sample of rows if the pair would pass
+64 MB), so that two builds can be compared output for output.
+
+--full adds to the line (each also switchable off with its --no-* option):
   roofline     : the conv kernel class (the dominant kernels, matrix-core-bound), hipEvent-timed on the
                  launch streams inside the timed region (librgfm_hip's rgfm_profile_*).  Default arithmetic
                  (RGFM_CONV unset / hx2): fp32 operands as two scaled fp16 planes, three f16-MFMA products per
@@ -68,6 +77,11 @@ def parse():
     p.add_argument("--mc", type=int, default=256)
     p.add_argument("--euler-steps", type=int, default=100)
     p.add_argument("--gamma", type=float, default=0.5)
+    p.add_argument("--full", action="store_true",
+                   help="also measure and check what the headline figure does not need: kernel-class timers and "
+                        "roofline, CPU baseline, exact-fp32 mode, arithmetic check, oracle parity gate")
+    p.add_argument("--dump-outputs", metavar="DIR",
+                   help="write the outputs of the last timed step as DIR/<name>.npy (float32)")
     p.add_argument("--no-cpu-baseline", action="store_true")
     p.add_argument("--no-kernel-timers", action="store_true",
                    help="skip the hipEvent kernel-class timers (use under rocprofv3)")
@@ -78,7 +92,31 @@ def parse():
     p.add_argument("--no-arith-check", action="store_true",
                    help="skip the small float64 error check after the timed region (use under rocprofv3: the trace "
                         "then ends with the guided main loop)")
-    return p.parse_args()
+    args = p.parse_args()
+    if args.steps < 1:
+        raise SystemExit("--steps must be >= 1")
+    if not args.full:  # a plain run: the timed steps and the headline line only
+        args.no_cpu_baseline = args.no_kernel_timers = args.no_alt_mode = True
+        args.no_parity_check = args.no_arith_check = True
+    return args
+
+
+DUMP_LIMIT_BYTES = 64 * 10**6
+
+
+def dump_outputs(out, dirname):
+    """The samples the last timed call returned, float32, one .npy per array; a fixed, seeded row sample above 64 MB."""
+    import numpy as np
+    os.makedirs(dirname, exist_ok=True)
+    arrays = {"x_mnist32": out[0], "y_svhn": out[1]}
+    B = out[0].shape[0]
+    row_bytes = sum(4 * t[0].numel() for t in arrays.values())
+    rows = None
+    if B * row_bytes > DUMP_LIMIT_BYTES:
+        rows = np.sort(np.random.default_rng(0).choice(B, DUMP_LIMIT_BYTES // row_bytes, replace=False))
+    for name, t in arrays.items():
+        a = t.detach().float().cpu().numpy()
+        np.save(os.path.join(dirname, name + ".npy"), a if rows is None else a[rows])
 
 
 def cpu_baseline(fm, fs, rr, euler_steps, B_full, N_full):
@@ -231,6 +269,8 @@ def main():
         t = torch.tensor([elapsed], device=dev, dtype=torch.float64)
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         elapsed = float(t.item())
+    if rank == 0 and args.dump_outputs:
+        dump_outputs(out, args.dump_outputs)
     parity = None
     if rank == 0 and not args.no_parity_check:
         # the number is reported only with the outputs of the timed run inside the tolerance

@@ -503,7 +503,7 @@ def test_bench_under_the_distributed_launcher(dev):
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "1", "--master-addr",
            "127.0.0.1", "--master-port", "29578", os.path.join(root, "bench.py"), "--gpus", "1", "--steps", "1",
-           "--warmup", "1", "--batch-per-gpu", "24", "--mc", "16", "--euler-steps", "6", "--no-cpu-baseline",
+           "--warmup", "1", "--batch-per-gpu", "24", "--mc", "16", "--euler-steps", "6", "--full", "--no-cpu-baseline",
            "--no-alt-mode", "--no-arith-check"]
     p = subprocess.run(cmd, capture_output=True, text=True, timeout=900, cwd=root)
     assert p.returncode == 0, p.stdout[-2000:] + p.stderr[-2000:]
@@ -513,6 +513,40 @@ def test_bench_under_the_distributed_launcher(dev):
     assert line["n_gpus"] == 1 and line["value"] > 0 and line["steps"] == 1
     assert line["ranks"] == [{"rank": 0, "world_size_seen": 1, "device": 0, "seconds": line["ranks"][0]["seconds"]}]
     assert line["parity_check"]["rows"] == 8 and line["parity_check"]["max_abs"] <= line["parity_check"]["tolerance"] == 1e-4
+
+
+def test_bench_plain_run_dumps_the_last_timed_step(dev, tmp_path):
+    """A plain `bench.py` run (no --full): the headline fields only, --steps timed calls, and --dump-outputs writes the
+    samples of the last timed call -- float32, the sampler's shapes, equal to the same call made here on the same
+    seeded inputs (synth weights 0 / 1 / 2, noise seed 42)."""
+    import subprocess
+    import sys
+    from ratio_guided_multimodal_fm_amd import models as M
+    from ratio_guided_multimodal_fm_amd.distributed import sharded_paired_sampler
+    from ratio_guided_multimodal_fm_amd.synth import load_synth
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    B, N, S = 20, 12, 5
+    cmd = [sys.executable, os.path.join(root, "bench.py"), "--gpus", "1", "--steps", "2", "--warmup", "1",
+           "--batch-per-gpu", str(B), "--mc", str(N), "--euler-steps", str(S), "--dump-outputs", str(tmp_path)]
+    env = {k: v for k, v in os.environ.items() if k not in ("RANK", "WORLD_SIZE", "LOCAL_RANK", "MASTER_PORT")}
+    p = subprocess.run(cmd, capture_output=True, text=True, timeout=600, cwd=root, env=env)
+    assert p.returncode == 0, p.stdout[-2000:] + p.stderr[-2000:]
+    lines = [ln for ln in p.stdout.splitlines() if ln.startswith("{")]
+    assert len(lines) == 1
+    line = json.loads(lines[0])
+    assert line["steps"] == 2 and line["warmup"] == 1 and line["value"] > 0 and line["higher_is_better"] is True
+    assert line["unit"] == "paired images/sec" and line["dtype"] == "f32"
+    assert abs(line["ms_per_step"] - 1e3 * B / line["value"]) <= 1e-6 * line["ms_per_step"]
+    assert not {"roofline", "cpu_baseline", "parity_check"} & set(line)
+    assert sorted(os.listdir(tmp_path)) == ["x_mnist32.npy", "y_svhn.npy"]
+    xs, ys = np.load(tmp_path / "x_mnist32.npy"), np.load(tmp_path / "y_svhn.npy")
+    assert xs.dtype == ys.dtype == np.float32 and xs.shape == (B, 1, 32, 32) and ys.shape == (B, 3, 32, 32)
+    fm = load_synth(M.FlowMatchingUNetMNIST(32), 0).eval().to(dev)
+    fs = load_synth(M.FlowMatchingUNetSVHN(), 1).eval().to(dev)
+    rr = load_synth(M.RatioEstimatorMNISTSVHN(), 2).eval().to(dev)
+    noise = tuple(t.to(dev) for t in paired_noise(42, B, N, (1, 32, 32), (3, 32, 32)))
+    x, y = sharded_paired_sampler(fm, fs, rr, "mc_feng", 0.5, S, noise, dev, gather="rank0")
+    assert maxdiff(xs, x.cpu().numpy()) <= 1e-5 and maxdiff(ys, y.cpu().numpy()) <= 1e-5
 
 
 def test_cli_sample28_from_checkpoint_files(dev, tmp_path, monkeypatch):

@@ -11,8 +11,8 @@ mkdir -p $O
 cd /tmp && export TMPDIR=/tmp
 B="--no-cpu-baseline --no-alt-mode --no-arith-check --no-parity-check"
 
-# 1. the official line (default flags: cpu_baseline, alternative mode, arithmetic check all on)
-( cd $R && timeout -k 10 900 python3 bench.py > $O/${TAG}_bench_line.json 2> $O/${TAG}_bench_err.txt ) || exit 1
+# 1. the official line with everything (--full: cpu_baseline, roofline, alternative mode, arithmetic check, parity gate)
+( cd $R && timeout -k 10 900 python3 bench.py --full > $O/${TAG}_bench_line.json 2> $O/${TAG}_bench_err.txt ) || exit 1
 echo "bench line done"
 
 # 2. kernel stats of one call, two streams (per-launch durations include overlap with the other net)

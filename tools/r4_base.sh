@@ -5,7 +5,7 @@ cd $GRAFT_REPO_ROOT
 O=gpurun_out; mkdir -p $O
 timeout -k 10 900 python -m pytest tests -m gpu -x -q > $O/r4_t1.log 2>&1; echo "pytest rc $?" | tee -a $O/r4_t1.log
 tail -5 $O/r4_t1.log
-timeout -k 10 600 python bench.py > $O/r4_bench1.json 2> $O/r4_bench1.err; echo "bench rc $?"
+timeout -k 10 600 python bench.py --full > $O/r4_bench1.json 2> $O/r4_bench1.err; echo "bench rc $?"
 tail -c 600 $O/r4_bench1.json
 export REPS=1000
 K=tools/kbench/conv_bench

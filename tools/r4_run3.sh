@@ -13,8 +13,8 @@ done; done ) > $O/r4_kbench_d3.txt 2>&1
 cat $O/r4_kbench_d3.txt | sed 's/check vs f32 kernel: //' | cut -c1-230
 timeout -k 10 1100 python -m pytest tests -m gpu -q -x > $O/r4_t3.log 2>&1; echo "pytest rc $?" | tee -a $O/r4_t3.log
 tail -8 $O/r4_t3.log
-timeout -k 10 600 python bench.py --no-cpu-baseline --no-alt-mode > $O/r4_bench3.json 2> $O/r4_bench3.err; echo "bench rc $?"
-RGFM_HX2D=0 timeout -k 10 600 python bench.py --no-cpu-baseline --no-alt-mode > $O/r4_bench3_off.json 2> $O/r4_bench3_off.err; echo "bench rc $?"
+timeout -k 10 600 python bench.py --full --no-cpu-baseline --no-alt-mode > $O/r4_bench3.json 2> $O/r4_bench3.err; echo "bench rc $?"
+RGFM_HX2D=0 timeout -k 10 600 python bench.py --full --no-cpu-baseline --no-alt-mode > $O/r4_bench3_off.json 2> $O/r4_bench3_off.err; echo "bench rc $?"
 python - <<'PY'
 import json
 for f in ("gpurun_out/r4_bench3.json","gpurun_out/r4_bench3_off.json"):

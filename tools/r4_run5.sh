@@ -5,7 +5,7 @@ O=gpurun_out; mkdir -p $O
 timeout -k 10 1100 python -m pytest tests -m gpu -q -x > $O/r4_t5.log 2>&1; echo "pytest rc $?" | tee -a $O/r4_t5.log
 tail -5 $O/r4_t5.log
 for i in 1 2; do
-timeout -k 10 600 python bench.py --no-cpu-baseline --no-alt-mode --no-arith-check > $O/r4_bench5_$i.json 2> $O/r4_bench5.err; echo "bench rc $?"
+timeout -k 10 600 python bench.py --full --no-cpu-baseline --no-alt-mode --no-arith-check > $O/r4_bench5_$i.json 2> $O/r4_bench5.err; echo "bench rc $?"
 done
 python - <<'PY'
 import json
