@@ -119,6 +119,40 @@ int rgfm_unet_read_activation(rgfm_unet* h, int index, int batch, const void* ws
                               rgfm_stream_t stream);
 
 /* ------------------------------------------------------------------------
+ * Training pass of the U-Net (replaces the reference's autograd through FlexibleUNet.forward in
+ * train_flow_matching_epoch, src/utils/flow_utils.py:103-156).  Exact fp32 arithmetic (v_mfma_f32_32x32x2_f32 for
+ * every conv, whatever the handle's conv mode), NCHW boundary tensors, stream-ordered, no synchronisation.
+ *
+ * rgfm_unet_forward_train evaluates v_out = model(x, t) in TRAINING mode and leaves in `ws` (at least
+ * rgfm_unet_train_workspace_bytes(h, batch) bytes, owned by the caller) everything rgfm_unet_backward needs; one ws
+ * per forward that is still to be differentiated.  Dropout (every ResBlock, on conv2's input, unet_flexible.py:77-79):
+ * element i of the NCHW tensor [batch][cout][H][W] in front of conv2 of ResBlock `block` (ResBlocks counted in the
+ * order the forward runs them: encoder, middle, decoder, from 0) is kept, and scaled by 1 / (1 - p_drop), iff
+ *     z = seed + 0x9E3779B97F4A7C15 * (((uint64)block << 32 | i) + 1)         (mod 2^64)
+ *     z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9;  z = (z ^ (z >> 27)) * 0x94D049BB133111EB;  z ^= z >> 31
+ *     (float)(z >> 40) * 2^-24 >= p_drop
+ * (the splitmix64 finaliser); p_drop = 0 applies none.  The backward regenerates the mask instead of storing it.
+ *
+ * rgfm_unet_backward: given dv = dL/dv_out, writes dL/dx to dx_out (optional, may be null) and dL/dparams to
+ * dparams_out -- one blob in the parameter blob's state_dict order, overwritten (not accumulated).  Every reduction
+ * has a fixed order: two calls on the same inputs give bitwise-identical results.  The handle's parameters must be
+ * those of the forward.
+ *
+ * rgfm_unet_dropout_mask writes the keep decisions (1.0 / 0.0) of ResBlock `block` for `batch` rows,
+ * out[batch][cout][H][W], on the null stream (test hook).
+ *
+ * rgfm_unet_update_params copies a new state_dict-order blob into the handle and repacks every derived weight image
+ * in place (fp32-packed, two-plane, split-bf16, Upsample parity-class, Winograd), without reallocating: what an
+ * optimizer step needs before the next eval-mode forward / sample call.  Synchronises `stream` once (as create). */
+int rgfm_unet_train_workspace_bytes(const rgfm_unet* h, int batch, size_t* bytes);
+int rgfm_unet_forward_train(rgfm_unet* h, const float* x, const float* t_dev, int t_count, float* v_out, int batch,
+                            float p_drop, uint64_t seed, void* ws, size_t ws_bytes, rgfm_stream_t stream);
+int rgfm_unet_backward(rgfm_unet* h, const float* dv, float* dx_out, float* dparams_out, int batch, void* ws,
+                       size_t ws_bytes, rgfm_stream_t stream);
+int rgfm_unet_dropout_mask(rgfm_unet* h, int block, uint64_t seed, float p_drop, int batch, float* out);
+int rgfm_unet_update_params(rgfm_unet* h, const float* params_dev, size_t n_floats, rgfm_stream_t stream);
+
+/* ------------------------------------------------------------------------
  * Density-ratio estimators.  Replaces RatioEstimatorMNISTSVHN
  * (src/models/ratio_flexible.py:305-385) and RatioEstimator
  * (src/models/ratio_estimator.py:96-191), eval mode.

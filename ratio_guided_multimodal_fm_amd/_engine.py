@@ -166,10 +166,16 @@ class _EngineBase:
                 "semantics only (Dropout = identity, BatchNorm = running statistics). Call .eval().")
 
 
+def _same_tensors(key, old):
+    """Two _state_key tuples that differ at most in the tensors' version counters."""
+    return old is not None and [(k, p, d) for k, p, _, d in key] == [(k, p, d) for k, p, _, d in old]
+
+
 class _VelocityEngine(_EngineBase):
     """Shared handle cache / forward of the velocity nets; subclasses name the ABI family."""
     PREFIX = None          # rgfm_<family>_{param_floats,create,destroy,workspace_bytes,forward}
     SINGLE = SINGLE_WS = PAIR = PAIR_WS = None
+    UPDATE = False         # the family has rgfm_<family>_update_params (in-place repack of the same handle)
 
     def desc(self):
         raise NotImplementedError
@@ -185,6 +191,13 @@ class _VelocityEngine(_EngineBase):
         sd = m.state_dict()
         key = self._state_key(sd)
         if self._handle is not None and key == self._key:
+            return self._handle
+        if self._handle is not None and self.UPDATE and _same_tensors(key, self._key):
+            # only the values moved (an optimizer step, an in-place edit): repack the same handle
+            blob = self._blob_from(sd, device)
+            with torch.cuda.device(device):
+                _lib.check(self._fn("update_params")(self._handle, _ptr(blob), blob.numel(), _stream(device)))
+            self._key, self._blob = key, blob
             return self._handle
         if self._handle is not None:
             self._destroy()
@@ -268,6 +281,36 @@ class UNetEngine(_VelocityEngine):
     PREFIX = "rgfm_unet"
     SINGLE, SINGLE_WS = "rgfm_sample_single", "rgfm_sample_single_workspace_bytes"
     PAIR, PAIR_WS = "rgfm_sample_pair", "rgfm_sample_pair_workspace_bytes"
+    UPDATE = True
+
+    def _check_eval(self, module):
+        if module.training:
+            raise _lib.RgfmError(
+                f"{type(module).__name__} is in training mode; model(x, t) implements eval-mode semantics only "
+                "(Dropout = identity). Train through model.forward_train(x, t) (HIP backward, dropout), or call "
+                ".eval() to evaluate / sample.")
+
+    # ---- training -----------------------------------------------------
+    def forward_train(self, x, t):
+        """v = model(x, t) in training semantics, differentiable w.r.t. x and the parameters (_UNetTrainFn)."""
+        m = self._module()
+        _require_hip(x, t)
+        self._check_input(m, x)
+        t = t.reshape(-1)
+        if t.numel() not in (1, x.shape[0]):
+            raise _lib.RgfmError(f"t must have 1 or {x.shape[0]} elements, got {t.numel()}")
+        p = m.dropout_p() if m.training else 0.0
+        return _UNetTrainFn.apply(self, x, t, float(p), *m.parameters())
+
+    def dropout_mask(self, block, seed, p, batch, device):
+        """Keep decisions (1 / 0) of ResBlock `block` for `batch` rows: [batch, cout, H, W] (rgfm_unet_dropout_mask)."""
+        m = self._module()
+        S, C = m.resblock_geometry()[block]
+        out = torch.empty(batch, C, S, S, device=device)
+        with torch.cuda.device(device):
+            _lib.check(_lib.lib().rgfm_unet_dropout_mask(self.handle(device), int(block), int(seed), float(p),
+                                                         int(batch), _ptr(out)))
+        return out
 
     def _check_input(self, m, x):
         if x.dim() != 4 or x.shape[1] != m.in_channels or x.shape[2] != m.img_size or x.shape[3] != m.img_size:
@@ -322,6 +365,56 @@ class UNetEngine(_VelocityEngine):
             finally:
                 _lib.check(L.rgfm_unet_set_trace(h, 0))
         return out, acts
+
+
+class _UNetTrainFn(torch.autograd.Function):
+    """Training forward / backward of FlexibleUNet through rgfm_unet_forward_train / rgfm_unet_backward.
+
+    Inputs: the engine, x, t, p_drop and the module's parameters (state_dict order), so that autograd hands back
+    dL/dx and every dL/dparam.  Each call owns its saved-state buffer; the dropout seed is drawn from the device's
+    torch generator."""
+
+    @staticmethod
+    def forward(ctx, engine, x, t, p_drop, *params):
+        dev = x.device
+        x, t = x.contiguous(), t.contiguous()
+        B = x.shape[0]
+        out = torch.empty_like(x)
+        ctx.engine, ctx.B, ctx.ws, ctx.nbytes = engine, B, None, 0
+        ctx.save_for_backward(*params)
+        if B == 0:
+            return out
+        seed = int(torch.randint(0, 2 ** 62, (1,), device=dev).item()) if p_drop > 0 else 0
+        L = _lib.lib()
+        with torch.cuda.device(dev):
+            h = engine.handle(dev)
+            n = ctypes.c_size_t()
+            _lib.check(L.rgfm_unet_train_workspace_bytes(h, B, ctypes.byref(n)))
+            ws = torch.empty(n.value, dtype=torch.uint8, device=dev)
+            _lib.check(L.rgfm_unet_forward_train(h, _ptr(x), _ptr(t), t.numel(), _ptr(out), B, p_drop, seed, _ptr(ws),
+                                                 n.value, _stream(dev)))
+        ctx.ws, ctx.nbytes = ws, n.value
+        ctx.x_shape = x.shape
+        return out
+
+    @staticmethod
+    def backward(ctx, dv):
+        params = ctx.saved_tensors
+        dev = dv.device
+        grads = [torch.zeros_like(q) for q in params]
+        if ctx.B == 0:
+            return (None, torch.zeros(0, *dv.shape[1:], device=dev) if ctx.needs_input_grad[1] else None, None, None,
+                    *grads)
+        dv = dv.to(torch.float32).contiguous()
+        dparams = torch.empty(sum(q.numel() for q in params), device=dev)
+        dx = torch.empty(ctx.x_shape, device=dev) if ctx.needs_input_grad[1] else None
+        with torch.cuda.device(dev):
+            h = ctx.engine.handle(dev)
+            _lib.check(_lib.lib().rgfm_unet_backward(h, _ptr(dv), _ptr(dx), _ptr(dparams), ctx.B, _ptr(ctx.ws),
+                                                     ctx.nbytes, _stream(dev)))
+        ctx.ws = None
+        grads = [g.view(q.shape) for g, q in zip(torch.split(dparams, [q.numel() for q in params]), params)]
+        return (None, dx, None, None, *grads)
 
 
 class RatioEngine(_EngineBase):

@@ -14,7 +14,7 @@ ABI_VERSION = 3
 _lib = None
 
 c_void_p, c_int, c_size_t, c_double = ctypes.c_void_p, ctypes.c_int, ctypes.c_size_t, ctypes.c_double
-c_int32, c_int64 = ctypes.c_int32, ctypes.c_int64
+c_int32, c_int64, c_uint64, c_float = ctypes.c_int32, ctypes.c_int64, ctypes.c_uint64, ctypes.c_float
 P = ctypes.POINTER
 
 
@@ -47,6 +47,12 @@ SIGNATURES = {
     "rgfm_unet_num_activations": (c_int, [c_void_p, P(c_int)]),
     "rgfm_unet_activation_shape": (c_int, [c_void_p, c_int, P(c_int), P(c_int), P(c_int)]),
     "rgfm_unet_read_activation": (c_int, [c_void_p, c_int, c_int, c_void_p, c_void_p, c_void_p]),
+    "rgfm_unet_train_workspace_bytes": (c_int, [c_void_p, c_int, P(c_size_t)]),
+    "rgfm_unet_forward_train": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_void_p, c_int, c_float, c_uint64,
+                                        c_void_p, c_size_t, c_void_p]),
+    "rgfm_unet_backward": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_void_p, c_size_t, c_void_p]),
+    "rgfm_unet_dropout_mask": (c_int, [c_void_p, c_int, c_uint64, c_float, c_int, c_void_p]),
+    "rgfm_unet_update_params": (c_int, [c_void_p, c_void_p, c_size_t, c_void_p]),
     "rgfm_ratio_param_floats": (c_int, [P(RatioDesc), P(c_size_t)]),
     "rgfm_ratio_create": (c_int, [P(RatioDesc), c_void_p, c_size_t, c_void_p, P(c_void_p)]),
     "rgfm_ratio_destroy": (None, [c_void_p]),

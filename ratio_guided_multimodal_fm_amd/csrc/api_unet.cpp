@@ -9,6 +9,68 @@ extern "C" int rgfm_unet_param_floats(const rgfm_unet_desc* desc, size_t* n_floa
   return RGFM_OK;
 }
 
+// Every derived weight image of the handle from h->params: the fp32-packed, two-plane and bf16 images, the stride-2
+// phase order, the Upsample parity-class sums, the Winograd images and the output conv's layout; then which convs may
+// run on the fp16 path (synchronises once).  Used by rgfm_unet_create and, in place, by rgfm_unet_update_params.
+static int pack_weights(rgfm_unet* h, hipStream_t s) {
+  std::vector<ConvW*> all;
+  for (auto* v : {&h->enc, &h->mid, &h->dec})
+    for (ResW& r : *v) {
+      all.push_back(&r.c1), all.push_back(&r.c2);
+      if (r.has_skip) all.push_back(&r.sk);
+    }
+  for (ConvW* w : all) pack_one(h, *w, CONV_S1, s);
+  for (ConvW& w : h->down) pack_one(h, w, CONV_S2, s), all.push_back(&w);  // stride-2 convs: phase-ordered weights
+  for (ConvW& w : h->down)  // ... and once more in plain tap order (same scale record: same weights)
+    launch_pack_conv_hx2(h->params + w.w_raw, h->packedh + (w.w_hx9 - 1), h->hq + 4 * w.hq, w.cout, w.cin, 9, CONV_S1, s);
+  for (ConvW& w : h->up) pack_one(h, w, CONV_S1, s), all.push_back(&w);
+  // the Upsample convs once more as ConvTranspose2d(4, 2, 1) weights (summed taps), packed in parity-class order; the
+  // ResBlock convs once more as Winograd images (one scratch array serves both)
+  std::vector<ConvW> t2rec(h->up.size());
+  std::vector<ConvW*> wino;
+  for (auto* v : {&h->enc, &h->mid, &h->dec})
+    for (ResW& r : *v) {
+      if (r.c1.w_w) wino.push_back(&r.c1);
+      if (r.c2.w_w) wino.push_back(&r.c2);
+    }
+  std::vector<ConvW> wrec(wino.size());
+  float* t2tmp = h->wtmp;
+  {
+    for (size_t i = 0; i < h->up.size(); ++i) {
+      const ConvW& w = h->up[i];
+      launch_up2_as_deconv(h->params + w.w_raw, t2tmp, w.cout, w.cin, s);
+      launch_pack_conv_hx2(t2tmp, h->packedh + (w.w_t2 - 1), h->hq + 4 * w.hq_t2, w.cout, w.cin, 16, CONV_T2, s);
+      t2rec[i].hq = w.hq_t2;
+      all.push_back(&t2rec[i]);
+    }
+    for (size_t i = 0; i < wino.size(); ++i) {
+      const ConvW& w = *wino[i];
+      launch_pack_conv_hx2w(h->params + w.w_raw, h->packedh + (w.w_w - 1), h->hq + 4 * w.hq_w, t2tmp, w.cout, w.cin, s);
+      wrec[i].hq = w.hq_w;
+      all.push_back(&wrec[i]);
+    }
+  }
+  const int rc_flags = read_hx_flags(h->hq, h->n_hq, all, s);  // (synchronises: the temporary is free)
+  if (rc_flags != RGFM_OK) return fail(RGFM_EHIP, "reading the fp16 scale records failed");
+  for (size_t i = 0; i < h->up.size(); ++i) h->up[i].t2_ok = t2rec[i].hx_ok;
+  for (size_t i = 0; i < wino.size(); ++i) wino[i]->w_ok = wrec[i].hx_ok;
+  {
+    // (norm_params_ok: convs behind a GroupNorm with out-of-window parameters leave the fp16 path here)
+    std::vector<float> host(h->n_params);
+    if (hipMemcpyAsync(host.data(), h->params, h->n_params * sizeof(float), hipMemcpyDeviceToHost, s) != hipSuccess ||
+        hipStreamSynchronize(s) != hipSuccess)
+      return fail(RGFM_EHIP, "reading the parameters back failed");
+    auto norm_ok = [&](size_t gw, size_t gb, int C) { return norm_params_ok(host, gw, gb, C); };
+    for (auto* v : {&h->enc, &h->mid, &h->dec})
+      for (ResW& r : *v) {
+        if (!norm_ok(r.n1w, r.n1b, r.cin)) r.c1.hx_ok = false;
+        if (!norm_ok(r.n2w, r.n2b, r.cout)) r.c2.hx_ok = false;
+      }
+  }
+  launch_pack_conv_out(h->params + h->ocw, h->packed + h->ocw_pk, h->d.in_channels, h->final_ch, s);
+  return RGFM_OK;
+}
+
 extern "C" int rgfm_unet_create(const rgfm_unet_desc* desc, const float* params_dev, size_t n_floats,
                                 rgfm_stream_t stream, rgfm_unet** out) {
   int rc = check_desc(desc);
@@ -43,66 +105,17 @@ extern "C" int rgfm_unet_create(const rgfm_unet_desc* desc, const float* params_
   if (hipMalloc(&h->packed3, (h->n_packed3 + 8) * sizeof(unsigned short)) != hipSuccess) return bail(RGFM_ENOMEM, "hipMalloc(packed3)");
   if (hipMemcpyAsync(h->params, params_dev, n_floats * sizeof(float), hipMemcpyDeviceToDevice, s) != hipSuccess)
     return bail(RGFM_EHIP, "hipMemcpyAsync(params)");
-  std::vector<ConvW*> all;
-  for (auto* v : {&h->enc, &h->mid, &h->dec})
-    for (ResW& r : *v) {
-      all.push_back(&r.c1), all.push_back(&r.c2);
-      if (r.has_skip) all.push_back(&r.sk);
-    }
-  for (ConvW* w : all) pack_one(h, *w, CONV_S1, s);
-  for (ConvW& w : h->down) pack_one(h, w, CONV_S2, s), all.push_back(&w);  // stride-2 convs: phase-ordered weights
-  for (ConvW& w : h->down)  // ... and once more in plain tap order (same scale record: same weights)
-    launch_pack_conv_hx2(h->params + w.w_raw, h->packedh + (w.w_hx9 - 1), h->hq + 4 * w.hq, w.cout, w.cin, 9, CONV_S1, s);
-  for (ConvW& w : h->up) pack_one(h, w, CONV_S1, s), all.push_back(&w);
-  // the Upsample convs once more as ConvTranspose2d(4, 2, 1) weights (summed taps), packed in parity-class order; the
-  // ResBlock convs once more as Winograd images (one scratch array serves both)
-  std::vector<ConvW> t2rec(h->up.size());
-  std::vector<ConvW*> wino;
-  for (auto* v : {&h->enc, &h->mid, &h->dec})
-    for (ResW& r : *v) {
-      if (r.c1.w_w) wino.push_back(&r.c1);
-      if (r.c2.w_w) wino.push_back(&r.c2);
-    }
-  std::vector<ConvW> wrec(wino.size());
-  float* t2tmp = nullptr;
   {
     size_t mx = 0;
     for (const ConvW& w : h->up) mx = std::max(mx, (size_t)w.cin * w.cout * 16);
-    for (const ConvW* w : wino) mx = std::max(mx, (size_t)w->cin * w->cout * 16);
-    if (mx && hipMalloc(&t2tmp, mx * sizeof(float)) != hipSuccess) return bail(RGFM_ENOMEM, "hipMalloc(upsample weights)");
-    for (size_t i = 0; i < h->up.size(); ++i) {
-      const ConvW& w = h->up[i];
-      launch_up2_as_deconv(h->params + w.w_raw, t2tmp, w.cout, w.cin, s);
-      launch_pack_conv_hx2(t2tmp, h->packedh + (w.w_t2 - 1), h->hq + 4 * w.hq_t2, w.cout, w.cin, 16, CONV_T2, s);
-      t2rec[i].hq = w.hq_t2;
-      all.push_back(&t2rec[i]);
-    }
-    for (size_t i = 0; i < wino.size(); ++i) {
-      const ConvW& w = *wino[i];
-      launch_pack_conv_hx2w(h->params + w.w_raw, h->packedh + (w.w_w - 1), h->hq + 4 * w.hq_w, t2tmp, w.cout, w.cin, s);
-      wrec[i].hq = w.hq_w;
-      all.push_back(&wrec[i]);
-    }
-  }
-  const int rc_flags = read_hx_flags(h->hq, h->n_hq, all, s);  // (synchronises: the temporary is free)
-  if (t2tmp) (void)hipFree(t2tmp);
-  if (rc_flags != RGFM_OK) return bail(RGFM_EHIP, "reading the fp16 scale records failed");
-  for (size_t i = 0; i < h->up.size(); ++i) h->up[i].t2_ok = t2rec[i].hx_ok;
-  for (size_t i = 0; i < wino.size(); ++i) wino[i]->w_ok = wrec[i].hx_ok;
-  {
-    // (norm_params_ok: convs behind a GroupNorm with out-of-window parameters leave the fp16 path here)
-    std::vector<float> host(n_floats);
-    if (hipMemcpyAsync(host.data(), h->params, n_floats * sizeof(float), hipMemcpyDeviceToHost, s) != hipSuccess ||
-        hipStreamSynchronize(s) != hipSuccess)
-      return bail(RGFM_EHIP, "reading the parameters back failed");
-    auto norm_ok = [&](size_t gw, size_t gb, int C) { return norm_params_ok(host, gw, gb, C); };
-    for (auto* v : {&h->enc, &h->mid, &h->dec})
-      for (ResW& r : *v) {
-        if (!norm_ok(r.n1w, r.n1b, r.cin)) r.c1.hx_ok = false;
-        if (!norm_ok(r.n2w, r.n2b, r.cout)) r.c2.hx_ok = false;
+    for (const auto* v : {&h->enc, &h->mid, &h->dec})
+      for (const ResW& r : *v) {
+        if (r.c1.w_w) mx = std::max(mx, (size_t)r.c1.cin * r.c1.cout * 16);
+        if (r.c2.w_w) mx = std::max(mx, (size_t)r.c2.cin * r.c2.cout * 16);
       }
+    if (mx && hipMalloc(&h->wtmp, mx * sizeof(float)) != hipSuccess) return bail(RGFM_ENOMEM, "hipMalloc(upsample weights)");
   }
-  launch_pack_conv_out(h->params + h->ocw, h->packed + h->ocw_pk, desc->in_channels, h->final_ch, s);
+  if ((rc = pack_weights(h, s))) return bail(rc, "packing the weights failed");
   // frequency table exp(-ln(1e4) * i / half) in fp32, as torch evaluates it (unet_flexible.py:28-31)
   const int half = h->mc / 2;
   std::vector<float> fr(half);
@@ -130,8 +143,17 @@ extern "C" void rgfm_unet_destroy(rgfm_unet* h) {
   if (h->packed3) (void)hipFree(h->packed3);
   if (h->freqs) (void)hipFree(h->freqs);
   if (h->lin_dev) (void)hipFree(h->lin_dev);
+  if (h->wtmp) (void)hipFree(h->wtmp);
   if (h->range_flag) (void)hipFree(h->range_flag);
   delete h;
+}
+
+extern "C" int rgfm_unet_update_params(rgfm_unet* h, const float* params_dev, size_t n_floats, rgfm_stream_t stream) {
+  if (!h || !params_dev) return fail(RGFM_EINVAL, "null argument");
+  if (n_floats != h->n_params) return fail(RGFM_EINVAL, "parameter blob has %zu floats, the handle has %zu", n_floats, h->n_params);
+  hipStream_t s = (hipStream_t)stream;
+  HIP_TRY(hipMemcpyAsync(h->params, params_dev, n_floats * sizeof(float), hipMemcpyDeviceToDevice, s));
+  return pack_weights(h, s);
 }
 
 extern "C" int rgfm_unet_set_conv_mode(rgfm_unet* h, int mode) {

@@ -415,6 +415,7 @@ struct rgfm_unet {
   size_t n_packed3 = 0;
   float* freqs = nullptr;
   TimeLinear* lin_dev = nullptr;
+  float* wtmp = nullptr;  // scratch of the Upsample / Winograd weight images (kept for rgfm_unet_update_params)
   size_t n_params = 0, n_packed = 0;
   int mc = 0, temb = 0, nlin = 0, temb_total = 0;
   size_t te0w, te0b, te2w, te2b, icw, icb, onw, onb, ocw, ocb;

@@ -375,4 +375,60 @@ void launch_euler(float* x, const float* v, size_t n, float dt, hipStream_t s);
 void launch_step_inc(int* step, hipStream_t s);  // *step += 1
 void launch_guid_schedule(float* sched, int step_begin, int ns, int num_steps, hipStream_t s);  // [ns][4] = {tf, s2, cden, 0}
 
+// ---- training pass of the U-Net (unet_grad.hip; all tensors NCHW fp32)
+// One conv for ug_igemm_kernel.  op 0: out = conv(x) + bias (+ temb[b][co]) (+ res), op 1: data gradient of the conv's
+// input (conv-input raster Hc x Wc) from dy, routed by channel to out ([B][C0]) / out1 ([B][Cin - C0]), each added to
+// (acc0 / acc1) or overwritten; op 2: weight gradient partials part[split][Cout][Cin * taps] from dy and x.
+// The conv input raster is Hc x Wc; with `up` it is the nearest-x2 image of the Hs x Ws source, else Hs = Hc.
+struct UgConv {
+  const float* x;   // input [B][Cin][Hs][Ws]
+  const float* w;   // [Cout][Cin][taps]
+  const float* dy;  // output gradient [B][Cout][Ho][Wo]
+  const float* bias;
+  const float* temb;  // [B][Cout] or null
+  const float* res;   // [B][Cout][Ho][Wo] or null (may alias out)
+  float* out;
+  float* out1;
+  float* part;
+  int C0, acc0, acc1;
+  int B, Cin, Cout, taps, stride, up;
+  int Hs, Ws, Hc, Wc, Ho, Wo;
+  int splits, kps;  // op 2: K split into `splits` ranges of kps (multiple of 16); else splits = 1, kps = K
+};
+// out = cat(s0, s1) [B][C0 + C1][HW]; with mr: silu(gamma (v - mean) rstd + beta) per group, then (drop_hdr set and
+// its p > 0) dropout with the keep decisions of ResBlock `block`
+struct UgAct {
+  const float* s0;
+  const float* s1;
+  int C0, C1, B, HW, groups;
+  const float* mr;  // [B][groups][2] (mean, rstd) or null
+  const float* gamma;
+  const float* beta;
+  const unsigned* drop_hdr;  // {p_drop bits, seed lo, seed hi} on the device, or null
+  int block;
+  float* out;
+};
+void launch_ug_conv(const UgConv& c, int op, hipStream_t s);
+void launch_ug_reduce(const float* part, int splits, size_t n, float* out, hipStream_t s);
+void launch_ug_bias_grad(const float* dy, int B, int C, int HW, float* db, hipStream_t s);
+void launch_ug_gn_stats(const float* s0, const float* s1, int C0, int C1, int B, int HW, int groups, float* mr,
+                        hipStream_t s);
+void launch_ug_gn_act(const UgAct& a, hipStream_t s);
+void launch_ug_gn_act_bwd(const UgAct& a, const float* dout, float* d0, float* d1, int acc0, int acc1, float* pg,
+                          float* pb, hipStream_t s);
+void launch_ug_colsum(const float* in, int rows, int cols, float* out, hipStream_t s);
+void launch_ug_rowsum(const float* in, int rows, int n, float* out, hipStream_t s);
+void launch_ug_linear(const float* x, const float* w, const float* b, float* y, int rows, int in, int out, int silu_in,
+                      hipStream_t s);
+void launch_ug_linear_wgrad(const float* dy, const float* x, int rows, int in, int out, int silu_in, float* dw,
+                            float* db, hipStream_t s);
+void launch_ug_linear_dgrad(const float* dy, const float* w, int rows, int in, int out, float* dx, int acc,
+                            hipStream_t s);
+void launch_ug_dsilu(float* g, const float* x, int n, hipStream_t s);
+void launch_ug_sincos(const float* t, int t_count, const float* freqs, int B, int mc, float* emb, hipStream_t s);
+void launch_ug_pool2_add(const float* du, float* dx, int BC, int H, int W, hipStream_t s);
+void launch_ug_split_add(const float* src, float* d0, float* d1, int B, int C0, int C1, int HW, hipStream_t s);
+void launch_ug_mask(float* out, size_t n, uint64_t seed, int block, float p, hipStream_t s);
+void launch_ug_header(unsigned* hdr, float p, uint64_t seed, hipStream_t s);
+
 }  // namespace rgfm

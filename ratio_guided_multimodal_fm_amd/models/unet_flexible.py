@@ -113,8 +113,45 @@ class FlexibleUNet(nn.Module):
 
 
     def forward(self, x, t):
-        """x: [B,C,H,W] fp32 on a HIP device, t: [B] (or [1]) -> velocity [B,C,H,W]."""
+        """x: [B,C,H,W] fp32 on a HIP device, t: [B] (or [1]) -> velocity [B,C,H,W] (eval mode only)."""
         return self._engine.forward(x, t)
+
+    def forward_train(self, x, t):
+        """Differentiable forward for training: ``loss.backward()`` fills ``p.grad`` and ``x.grad`` through the
+        HIP backward (rgfm_unet_forward_train / rgfm_unet_backward).  Dropout applies while ``self.training``."""
+        return self._engine.forward_train(x, t)
+
+    def _resblocks(self):
+        return list(self.encoder_blocks) + [self.middle_block1, self.middle_block2] + list(self.decoder_blocks)
+
+    def dropout_p(self):
+        """The ResBlocks' dropout probability (one value for the whole net, as every constructor sets it)."""
+        ps = {b.dropout.p for b in self._resblocks()}
+        if len(ps) != 1:
+            raise ValueError(f"the ResBlocks have different dropout probabilities {sorted(ps)}")
+        return float(ps.pop())
+
+    def resblock_geometry(self):
+        """[(size, out_channels)] of every ResBlock in the order the forward runs them (the dropout mask's block ids)."""
+        out, S = [], self.img_size
+        n, last = self.num_res_blocks, len(self.channel_mult) - 1
+        blocks = self._resblocks()
+        i = 0
+        for level in range(last + 1):
+            for _ in range(n):
+                out.append((S, blocks[i].out_channels))
+                i += 1
+            if level < last:
+                S //= 2
+        out += [(S, self.middle_block1.out_channels), (S, self.middle_block2.out_channels)]
+        i += 2
+        for level in range(last, -1, -1):
+            for _ in range(n + 1):
+                out.append((S, blocks[i].out_channels))
+                i += 1
+            if level > 0:
+                S *= 2
+        return out
 
 
 class FlowMatchingUNetMNIST(FlexibleUNet):

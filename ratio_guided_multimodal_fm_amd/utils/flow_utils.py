@@ -1,11 +1,14 @@
-"""Samplers of the 28x28 experiments (reference ``src/utils/flow_utils.py``).
+"""Samplers of the 28x28 experiments and CFM training (reference ``src/utils/flow_utils.py``).
 
 ``CFMSchedule.sample`` (``:69-100``) and ``sample_bimodal_guided``
 (``:178-375``) keep the reference signatures and return values; the Euler
 loops, the U-Net evaluations, the ratio estimator and the MC guidance all run
-inside librgfm_hip.so (one C-ABI call per phase).
+inside librgfm_hip.so (one C-ABI call per phase).  ``CFMSchedule.add_noise``
+(``:40-67``) and ``train_flow_matching_epoch`` (``:103-156``) train a
+``FlexibleUNet`` through its HIP backward (``FlexibleUNet.forward_train``).
 """
 import torch
+import torch.nn.functional as F
 
 from .. import _engine
 
@@ -34,12 +37,48 @@ class CFMSchedule:
     def compute_sigma_t(self, t):
         return self.sigma
 
+    def add_noise(self, x_1, t):
+        """(x_t, u_t): x_0 ~ N(0, I) like x_1, x_t = (1 - t) x_0 + t x_1, u_t = x_1 - x_0 (reference :40-67)."""
+        x_0 = torch.randn_like(x_1)
+        t = t.view(x_1.shape[0], *([1] * (x_1.dim() - 1)))
+        return (1 - t) * x_0 + t * x_1, x_1 - x_0
+
     def sample(self, model, num_samples, num_steps=100, device='cuda'):
         """x0 ~ N(0, I) [n,1,28,28]; num_steps explicit Euler steps (reference :69-100)."""
         model.eval()
         dev = _device(device)
         x_t = torch.randn(num_samples, 1, 28, 28, device=dev)
         return _engine.sample_single(model, x_t, num_steps)
+
+
+def _velocity_train(model, x_t, t):
+    """model(x_t, t) with training semantics: FlexibleUNet trains through its HIP backward."""
+    fwd = getattr(model, 'forward_train', None)
+    if fwd is None:
+        raise TypeError(f"{type(model).__name__} has no HIP training path (FlexibleUNet and its presets have one)")
+    return fwd(x_t, t)
+
+
+def train_flow_matching_epoch(model, dataloader, optimizer, schedule, device, modality='x'):
+    """One CFM epoch (reference :103-156): per batch t ~ U(0, 1), (x_t, u_t) = schedule.add_noise(x_1, t),
+    MSE(model(x_t, t), u_t), backward, optimizer step.  Batches are dicts (``batch[modality]``) as the reference's
+    loaders yield, or plain tensors.  Returns the mean batch loss."""
+    model.train()
+    dev = _device(device)
+    total_loss = 0.0
+    num_batches = 0
+    for batch in dataloader:
+        x_1 = (batch[modality] if isinstance(batch, dict) else batch).to(dev)
+        t = torch.rand(x_1.shape[0], device=dev)
+        x_t, u_t_target = schedule.add_noise(x_1, t)
+        v_t = _velocity_train(model, x_t, t)
+        loss = F.mse_loss(v_t, u_t_target)
+        optimizer.zero_grad()
+        loss.backward()
+        optimizer.step()
+        total_loss += loss.item()
+        num_batches += 1
+    return total_loss / num_batches
 
 
 def paired_sampler(fm_x, fm_y, ratio_estimator, guidance_method, guidance_strength, num_samples,
