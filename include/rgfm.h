@@ -114,6 +114,22 @@ int rgfm_unet_p_handovers(const rgfm_unet* h, int* blocks);
 /* Debug / test hook: how many convs of the handle's LATEST network walk were described for the Winograd F(2x2, 3x3) kernel
  * (conv_mfma_hx2w.hip; opt-in: RGFM_WINO=1). */
 int rgfm_unet_wino_convs(const rgfm_unet* h, int* convs);
+/* Debug / test hook: conv launches of the handle's LATEST network walk per kernel route (the dispatch of
+ * launch_conv, csrc/rgfm_host.h), plus the launches that ran as the four parity classes of an Upsample (CONV_T2,
+ * whichever route took them).  counts[i] for i < min(n, RGFM_ROUTE_SLOTS); the input / output convs are not counted. */
+#define RGFM_ROUTE_HX2D 0   /* conv_mfma_hx2d.hip: P-format input                       */
+#define RGFM_ROUTE_HX2W 1   /* conv_mfma_hx2w.hip: Winograd F(2x2, 3x3) (RGFM_WINO=1)   */
+#define RGFM_ROUTE_HX2S 2   /* conv_mfma_hx2s.hip: stride-2 Downsample                  */
+#define RGFM_ROUTE_HX2C 3   /* conv_mfma_hx2c.hip: the 8x8 level                        */
+#define RGFM_ROUTE_HX2Q 4   /* conv_mfma_hx2q.hip: four waves per SIMD                  */
+#define RGFM_ROUTE_HX2P 5   /* conv_mfma_hx2p.hip: pipelined fp16                       */
+#define RGFM_ROUTE_HX2 6    /* conv_mfma_hx2.hip                                        */
+#define RGFM_ROUTE_BX3 7    /* conv_mfma_bx3.hip: three bf16 planes                     */
+#define RGFM_ROUTE_F32 8    /* conv_mfma.hip: exact fp32 MFMA                           */
+#define RGFM_ROUTE_COUNT 9
+#define RGFM_ROUTE_T2 9     /* (not a route) launches in the Upsample parity-class form */
+#define RGFM_ROUTE_SLOTS 10
+int rgfm_unet_conv_routes(const rgfm_unet* h, int* counts, int n);
 int rgfm_unet_activation_shape(const rgfm_unet* h, int index, int* channels, int* height, int* width);
 int rgfm_unet_read_activation(rgfm_unet* h, int index, int batch, const void* ws, float* out_dev,
                               rgfm_stream_t stream);

@@ -9,6 +9,7 @@
 #include "rgfm_oracle.h"
 
 #include <math.h>
+#include <stdio.h>
 #include <stdlib.h>
 #include <string.h>
 #ifdef _OPENMP
@@ -177,11 +178,15 @@ static void rb_take(cursor* c, resblock* r, int cin, int cout, int temb) {
   }
 }
 
-#define MAXB 32
+/* the library's descriptor limits (check_desc): 1..4 levels, 1..8 ResBlocks per level; the decoder runs one more per level */
+#define MAXL 4
+#define MAXNRB 8
+#define MAXENC (MAXL * MAXNRB)
+#define MAXDEC (MAXL * (MAXNRB + 1))
 typedef struct {
   int mc, temb, nenc, ndec, ndown, nup;
   const float *te0w, *te0b, *te2w, *te2b, *icw, *icb, *onw, *onb, *ocw, *ocb;
-  resblock enc[MAXB], mid[2], dec[MAXB];
+  resblock enc[MAXENC], mid[2], dec[MAXDEC];
   const float *dw[4], *db[4], *uw[4], *ub[4];
   int dch[4], uch[4];
   size_t total;
@@ -189,6 +194,15 @@ typedef struct {
 
 /* Parameter registration order of FlexibleUNet.__init__ (src/models/unet_flexible.py:146-201);
  * UNetMNIST (src/models/unet.py:155-214) is identical. */
+/* Descriptors the plan's fixed arrays hold (and the sizes the walk's buffers assume); anything else is refused. */
+static int desc_ok(const ro_unet_desc* d) {
+  if (d->num_levels < 1 || d->num_levels > MAXL || d->num_res_blocks < 1 || d->num_res_blocks > MAXNRB) return 0;
+  if (d->in_channels < 1 || d->model_channels < 1 || d->model_channels > 256 || d->img_size < 1) return 0;
+  for (int l = 0; l < d->num_levels; ++l)
+    if (d->channel_mult[l] < 1 || d->model_channels * d->channel_mult[l] > 256) return 0;
+  return 1;
+}
+
 static void plan_unet(const ro_unet_desc* d, const float* params, unet_plan* P) {
   cursor c = {params};
   const int mc = d->model_channels, temb = 4 * mc;
@@ -247,6 +261,7 @@ static void plan_unet(const ro_unet_desc* d, const float* params, unet_plan* P) 
 }
 
 size_t ro_unet_param_floats(const ro_unet_desc* d) {
+  if (!desc_ok(d)) return 0; /* refused: no network has 0 parameters */
   unet_plan P;
   plan_unet(d, NULL, &P);
   return P.total;
@@ -298,10 +313,12 @@ static int act_table(const ro_unet_desc* d, int* ch_out, int* sz_out) {
   return n;
 }
 
-int ro_unet_num_activations(const ro_unet_desc* d) { return act_table(d, NULL, NULL); }
+int ro_unet_num_activations(const ro_unet_desc* d) { return desc_ok(d) ? act_table(d, NULL, NULL) : 0; }
 
 void ro_unet_activation_shape(const ro_unet_desc* d, int idx, int* c, int* h, int* w) {
-  int ch[256], sz[256];
+  int ch[256], sz[256]; /* >= 1 + 2 * MAXENC + 2 * (MAXL - 1) + 4 + 2 * MAXDEC + 1 = 148 */
+  *c = *h = *w = 0;
+  if (!desc_ok(d) || idx < 0 || idx >= act_table(d, NULL, NULL)) return;
   act_table(d, ch, sz);
   *c = ch[idx];
   *h = *w = sz[idx];
@@ -437,6 +454,10 @@ static void unet_one(const ro_unet_desc* d, const unet_plan* P, const float* x, 
 
 void ro_unet_forward(const ro_unet_desc* d, const float* params, const float* x, const float* t,
                      int t_count, float* out, int B, float** acts) {
+  if (!desc_ok(d)) {
+    fprintf(stderr, "ro_unet_forward: descriptor outside the library's limits refused\n");
+    return;
+  }
   unet_plan P;
   plan_unet(d, params, &P);
   const size_t n = (size_t)d->in_channels * d->img_size * d->img_size;

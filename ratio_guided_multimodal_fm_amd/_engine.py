@@ -341,6 +341,12 @@ class UNetEngine(_VelocityEngine):
             _lib.check(_lib.lib().rgfm_unet_time_embedding(h, _ptr(t), t.numel(), _ptr(out), _ptr(ws), nb, _stream(dev)))
         return out
 
+    def conv_routes(self, device):
+        """{route name: conv launches} of the handle's latest walk (rgfm_unet_conv_routes); key "t2": CONV_T2 launches."""
+        counts = (ctypes.c_int * (_lib.ROUTE_T2 + 1))()
+        _lib.check(_lib.lib().rgfm_unet_conv_routes(self.handle(device), counts, len(counts)))
+        return dict(zip(_lib.ROUTES + ("t2",), counts))
+
     def forward_trace(self, x, t):
         """Forward in trace mode; returns (out, [activation tensors, NCHW])."""
         dev = x.device

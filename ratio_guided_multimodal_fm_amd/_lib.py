@@ -43,6 +43,7 @@ SIGNATURES = {
     "rgfm_unet_set_trace": (c_int, [c_void_p, c_int]),
     "rgfm_unet_p_handovers": (c_int, [c_void_p, P(c_int)]),
     "rgfm_unet_wino_convs": (c_int, [c_void_p, P(c_int)]),
+    "rgfm_unet_conv_routes": (c_int, [c_void_p, P(c_int), c_int]),
     "rgfm_unet_time_embedding": (c_int, [c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_size_t, c_void_p]),
     "rgfm_unet_num_activations": (c_int, [c_void_p, P(c_int)]),
     "rgfm_unet_activation_shape": (c_int, [c_void_p, c_int, P(c_int), P(c_int), P(c_int)]),
@@ -101,6 +102,11 @@ SIGNATURES = {
     "rgfm_abi_version": (c_int, []),
     "rgfm_last_error": (ctypes.c_char_p, []),
 }
+
+
+# RGFM_ROUTE_* of include/rgfm.h, in index order (rgfm_unet_conv_routes); slot ROUTE_T2 counts the CONV_T2 launches
+ROUTES = ("hx2d", "hx2w", "hx2s", "hx2c", "hx2q", "hx2p", "hx2", "bx3", "f32")
+ROUTE_T2 = len(ROUTES)
 
 
 class RgfmError(RuntimeError):

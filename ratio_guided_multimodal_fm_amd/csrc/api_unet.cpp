@@ -261,6 +261,11 @@ extern "C" int rgfm_unet_wino_convs(const rgfm_unet* h, int* convs) {
   *convs = h->wino_convs;
   return RGFM_OK;
 }
+extern "C" int rgfm_unet_conv_routes(const rgfm_unet* h, int* counts, int n) {
+  if (!h || !counts || n < 0) return fail(RGFM_EINVAL, "null argument or negative count");
+  for (int i = 0; i < n && i < RGFM_ROUTE_SLOTS; ++i) counts[i] = h->routes[i];
+  return RGFM_OK;
+}
 
 extern "C" int rgfm_unet_num_activations(const rgfm_unet* h, int* n) {
   if (!h || !n) return fail(RGFM_EINVAL, "null argument");

@@ -350,22 +350,42 @@ inline bool hx2w_pays(const ConvArgs& c) {
   return c.wpkw != nullptr && c.C0 + c.C1 >= 128 && (!w32_only || c.g.W == 32);
 }
 
-inline void launch_conv(const ConvArgs& c, int mode, hipStream_t s) {
-  if (c.pin0) {  // (P-format input: only conv_mfma_hx2d_kernel reads it; the walk has checked conv_hx2d_supported)
-    launch_conv_hx2d(c, s);
-    return;
+// Which kernel launch_conv sends this launch to (RGFM_ROUTE_*): the one place the predicate chain is written.
+inline int conv_route(const ConvArgs& c, int mode) {
+  if (c.pin0) return RGFM_ROUTE_HX2D;  // (P-format input: only conv_mfma_hx2d_kernel reads it; the walk has checked conv_hx2d_supported)
+  const bool hx2 = g_modes.conv == CONV_ARITH_HX2, pipe = hx2 && g_modes.pipelined;
+  if (pipe && g_modes.wino && hx2w_pays(c) && conv_hx2w_supported(c, mode)) return RGFM_ROUTE_HX2W;
+  if (pipe && g_modes.s2 && conv_hx2s_supported(c, mode)) return RGFM_ROUTE_HX2S;
+  if (pipe && g_modes.c8 && conv_hx2c_supported(c, mode)) return RGFM_ROUTE_HX2C;
+  if (pipe && g_modes.quad && conv_hx2q_supported(c, mode)) return RGFM_ROUTE_HX2Q;
+  if (pipe && conv_hx2p_supported(c, mode)) return RGFM_ROUTE_HX2P;
+  if (hx2 && conv_hx2_supported(c, mode)) return RGFM_ROUTE_HX2;
+  if (g_modes.conv != CONV_ARITH_F32 && conv_bx3_supported(c, mode)) return RGFM_ROUTE_BX3;
+  return RGFM_ROUTE_F32;
+}
+
+inline void launch_conv_on(int route, const ConvArgs& c, int mode, hipStream_t s) {
+  switch (route) {
+    case RGFM_ROUTE_HX2D: launch_conv_hx2d(c, s); break;
+    case RGFM_ROUTE_HX2W: launch_conv_hx2w(c, s); break;
+    case RGFM_ROUTE_HX2S: launch_conv_hx2s(c, s); break;
+    case RGFM_ROUTE_HX2C: launch_conv_hx2c(c, s); break;
+    case RGFM_ROUTE_HX2Q: launch_conv_hx2q(c, mode, s); break;
+    case RGFM_ROUTE_HX2P: launch_conv_hx2p(c, mode, s); break;
+    case RGFM_ROUTE_HX2: launch_conv_hx2(c, mode, s); break;
+    case RGFM_ROUTE_BX3: launch_conv_bx3(c, mode, s); break;
+    default: launch_conv_mfma(c, mode, s); break;
   }
-  if (g_modes.conv == CONV_ARITH_HX2 && g_modes.pipelined && g_modes.wino && hx2w_pays(c) && conv_hx2w_supported(c, mode)) {
-    launch_conv_hx2w(c, s);
-    return;
+}
+
+// routes: the handle's per-route launch counts (RGFM_ROUTE_SLOTS entries), or null
+inline void launch_conv(const ConvArgs& c, int mode, hipStream_t s, int* routes = nullptr) {
+  const int route = conv_route(c, mode);
+  if (routes) {
+    routes[route] += 1;
+    if (mode == CONV_T2) routes[RGFM_ROUTE_T2] += 1;
   }
-  if (g_modes.conv == CONV_ARITH_HX2 && g_modes.pipelined && g_modes.s2 && conv_hx2s_supported(c, mode)) launch_conv_hx2s(c, s);
-  else if (g_modes.conv == CONV_ARITH_HX2 && g_modes.pipelined && g_modes.c8 && conv_hx2c_supported(c, mode)) launch_conv_hx2c(c, s);
-  else if (g_modes.conv == CONV_ARITH_HX2 && g_modes.pipelined && g_modes.quad && conv_hx2q_supported(c, mode)) launch_conv_hx2q(c, mode, s);
-  else if (g_modes.conv == CONV_ARITH_HX2 && g_modes.pipelined && conv_hx2p_supported(c, mode)) launch_conv_hx2p(c, mode, s);
-  else if (g_modes.conv == CONV_ARITH_HX2 && conv_hx2_supported(c, mode)) launch_conv_hx2(c, mode, s);
-  else if (g_modes.conv != CONV_ARITH_F32 && conv_bx3_supported(c, mode)) launch_conv_bx3(c, mode, s);
-  else launch_conv_mfma(c, mode, s);
+  launch_conv_on(route, c, mode, s);
 }
 
 
@@ -426,6 +446,7 @@ struct rgfm_unet {
   bool trace = false;
   int wino_convs = 0;   // convs of the latest walk described for the Winograd kernel (rgfm_unet_wino_convs)
   int p_handovers = 0;  // ResBlocks of the latest walk whose conv1 -> conv2 hand-over took the P format (rgfm_unet_p_handovers)
+  int routes[RGFM_ROUTE_SLOTS] = {};  // conv launches of the latest walk per route, + CONV_T2 launches (rgfm_unet_conv_routes)
   struct Act {
     float* data;
     int C, S;
@@ -610,11 +631,11 @@ struct PendingConv {
   double flops = 0.0;
 };
 
-inline void flush_conv(PendingConv& p, hipStream_t s) {
+inline void flush_conv(PendingConv& p, hipStream_t s, int* routes = nullptr) {
   if (!p.valid) return;
   p.valid = false;
   ProfScope ps(RGFM_KCLASS_CONV_MFMA, p.flops, s);
-  launch_conv(p.c, p.mode, s);
+  launch_conv(p.c, p.mode, s, routes);
 }
 
 // true when `p` can take the finalize of cat(its output, partner) itself
@@ -677,7 +698,7 @@ struct UNetRun {
     if (dry) return ab;
     const bool fused = try_fuse_finalize(pend, a.data, b ? b->stats : nullptr, b ? b->C : 0, h->params + gamma,
                                          h->params + beta, ab, fin_counter);
-    flush_conv(pend, s);
+    flush_conv(pend, s, h->routes);
     if (fused) return ab;
     GnFinalizeArgs f{};
     f.stats0 = a.stats, f.stats1 = b ? b->stats : nullptr;
@@ -752,7 +773,7 @@ struct UNetRun {
                            h->params + norm->beta))
         c.ab = finalize(a, b, norm->gamma, norm->beta, ab_buf);  // (may attach itself to the pending producer)
     }
-    flush_conv(pend, s);
+    flush_conv(pend, s, h->routes);
     if (g_modes.conv == CONV_ARITH_HX2 && g_modes.pipelined && g_modes.wino && hx2w_pays(c) && conv_hx2w_supported(c, mode)) h->wino_convs += 1;
     pend.valid = true, pend.c = c, pend.mode = mode;
     pend.flops = conv_flops(B, So * So, w.cout, kprod);
@@ -791,7 +812,7 @@ struct UNetRun {
     const rgfm_unet_desc& d = h->d;
     ModeScope mode_scope(h->conv_mode);
     if (!dry && h->trace) h->acts.clear();
-    if (!dry) h->p_handovers = 0, h->wino_convs = 0;
+    if (!dry) h->p_handovers = 0, h->wino_convs = 0, std::fill(h->routes, h->routes + RGFM_ROUTE_SLOTS, 0);
     int S = d.img_size;
     Tensor cur = new_tensor(h->mc, S);
     if (!dry) {
@@ -835,7 +856,7 @@ struct UNetRun {
     }
     float* ab = finalize(cur, nullptr, h->onw, h->onb);
     if (!dry) {
-      flush_conv(pend, s);
+      flush_conv(pend, s, h->routes);
       ConvOutArgs co{};
       co.in = cur.data, co.ab = ab, co.w = h->packed + h->ocw_pk, co.bias = h->params + h->ocb;
       co.v_out = v_out, co.x_state = x_state, co.dt = dt, co.B = B, co.Cin = cur.C;

@@ -96,3 +96,46 @@ def make_generic_unet(tag, device=None):
                     generator=torch.Generator().manual_seed(300 + i))
     t = torch.tensor([0.0, 0.2, 0.5, 0.8, 0.99])
     return (m.to(device) if device is not None else m), x, t
+
+
+# FlexibleUNet descriptors chosen to reach the shape-dependent branches of the conv dispatch (launch_conv's routes,
+# NT = 1 / 2 channel blocks, P-format hand-over, parity-class Upsample, fused / separate GroupNorm finalize) that the
+# presets and GENERIC_UNETS leave out.  Fixed: nothing is drawn at run time.
+ARCH_SWEEP = {
+    # Cout 96 (NT = 1 over three 32-channel blocks) and 192 (NT = 2, no PAIRN); concat 384 and 288 (> 256: separate
+    # gn_finalize + table path); 20 -> 10
+    "a96": dict(in_channels=1, img_size=20, model_channels=96, channel_mult=(1, 2), num_res_blocks=2),
+    # one level: no Downsample, no Upsample; Cout 160; concat 320; one 144-pixel tile per sample
+    "a160": dict(in_channels=3, img_size=12, model_channels=160, channel_mult=(1,), num_res_blocks=2),
+    # Cout 96 and 224; 10 -> 5 (odd 5x5 bottom, four samples per tile); Upsample 5 -> 10
+    "a224": dict(in_channels=1, img_size=10, model_channels=32, channel_mult=(3, 7), num_res_blocks=2),
+    # time MLP width 1024 (time_embed_kernel's LDS exactly full); concat 512 (gn_finalize's s_mean[512] exactly full)
+    "a256": dict(in_channels=3, img_size=8, model_channels=256, channel_mult=(1,), num_res_blocks=1),
+    # 64x64: 64 statistics parts (no producer-side finalize), 64 -> 32 -> 16 -> 8, Upsample 32 -> 64 in the nine-tap
+    # form (up_parts_match(32) is false) while 8 -> 16 and 16 -> 32 take the parity classes
+    "a64": dict(in_channels=3, img_size=64, model_channels=32, channel_mult=(1, 2, 4, 8), num_res_blocks=1),
+    # 48x48 (tiles of 5 rows, 40 parts) and 24x24
+    "a48": dict(in_channels=1, img_size=48, model_channels=64, channel_mult=(1, 2), num_res_blocks=2),
+    # 56 -> 28 -> 14 -> 7: an odd bottom map reached by three Downsamples
+    "a56": dict(in_channels=1, img_size=56, model_channels=32, channel_mult=(1, 1, 2, 2), num_res_blocks=1),
+    # 12 -> 6 -> 3 (3x3 bottom, 9-pixel samples); Cout 192 at 3x3
+    "a12": dict(in_channels=3, img_size=12, model_channels=64, channel_mult=(1, 2, 3), num_res_blocks=1),
+    # the minimum image: 4 -> 2
+    "a4": dict(in_channels=1, img_size=4, model_channels=32, channel_mult=(1, 2), num_res_blocks=1),
+    # 36x36 (24 parts); Cout 96 and 192 at 36 and 18
+    "a36": dict(in_channels=3, img_size=36, model_channels=96, channel_mult=(1, 2), num_res_blocks=1),
+    # num_res_blocks at its maximum: 4 x 9 = 36 decoder blocks
+    "deep": dict(in_channels=1, img_size=16, model_channels=32, channel_mult=(1, 1, 1, 1), num_res_blocks=8),
+}
+
+
+def make_sweep_unet(tag, batch, device=None):
+    """(module, x, t) of ARCH_SWEEP[tag]: synthetic weights under the entry's own seed, `batch` rows of N(0, 1) input
+    and t spread over [0, 0.99] (both ends included once batch >= 2)."""
+    i = list(ARCH_SWEEP).index(tag)
+    cfg = ARCH_SWEEP[tag]
+    m = load_synth(M.FlexibleUNet(**cfg), 80 + i).eval()
+    x = torch.randn(batch, cfg["in_channels"], cfg["img_size"], cfg["img_size"],
+                    generator=torch.Generator().manual_seed(400 + i))
+    t = torch.linspace(0.0, 0.99, batch) if batch > 1 else torch.tensor([0.99])
+    return (m.to(device) if device is not None else m), x, t

@@ -37,28 +37,36 @@ def params64(module, requires_grad=True):
             for k, v in module.state_dict().items()}
 
 
-def forward64(cfg, sd, x, t, masks=None, p_drop=0.0):
-    """v = FlexibleUNet(**cfg)(x, t) in float64; masks: list of keep masks (1 / 0) per ResBlock, or None."""
+def forward64(cfg, sd, x, t, masks=None, p_drop=0.0, trace=False):
+    """v = FlexibleUNet(**cfg)(x, t) in float64; masks: list of keep masks (1 / 0) per ResBlock, or None.
+    trace=True: (v, activations) with the activations in the order and shapes of UNetEngine.forward_trace and
+    oracle.unet_forward(..., trace=True): input_conv, then per ResBlock conv1 + time term (before norm2) and the block's
+    output, each Downsample / Upsample output, and v last."""
     x = x.to(torch.float64)
     t = t.to(torch.float64).reshape(-1)
     if t.numel() == 1:
         t = t.expand(x.shape[0])
     mc, mult, nrb = cfg["model_channels"], tuple(cfg["channel_mult"]), cfg["num_res_blocks"]
     blk = [0]
+    acts = []
 
     def res(h, name, emb):
         a = _conv(F.silu(_gn(h, sd, name + ".norm1")), sd, name + ".conv1")
         a = a + _linear(F.silu(emb), sd, name + ".time_mlp.1")[:, :, None, None]
+        acts.append(a)
         a = F.silu(_gn(a, sd, name + ".norm2"))
         if masks is not None:
             a = a * masks[blk[0]].to(torch.float64) / (1.0 - p_drop)
         blk[0] += 1
         a = _conv(a, sd, name + ".conv2")
-        return a + (_conv(h, sd, name + ".skip") if name + ".skip.weight" in sd else h)
+        a = a + (_conv(h, sd, name + ".skip") if name + ".skip.weight" in sd else h)
+        acts.append(a)
+        return a
 
     emb = timestep_embedding64(t, mc)
     emb = _linear(F.silu(_linear(emb, sd, "time_embed.0")), sd, "time_embed.2")
     h = _conv(x, sd, "input_conv")
+    acts.append(h)
     hs = [h]
     bi = 0
     for level in range(len(mult)):
@@ -68,6 +76,7 @@ def forward64(cfg, sd, x, t, masks=None, p_drop=0.0):
             bi += 1
         if level < len(mult) - 1:
             h = _conv(h, sd, f"downsamplers.{level}.conv", stride=2)
+            acts.append(h)
             hs.append(h)
     h = res(h, "middle_block1", emb)
     h = res(h, "middle_block2", emb)
@@ -78,8 +87,10 @@ def forward64(cfg, sd, x, t, masks=None, p_drop=0.0):
             bi += 1
         if level > 0:
             h = _conv(F.interpolate(h, scale_factor=2, mode="nearest"), sd, f"upsamplers.{ui}.conv")
+            acts.append(h)
             ui += 1
-    return _conv(F.silu(_gn(h, sd, "out_norm")), sd, "out_conv")
+    v = _conv(F.silu(_gn(h, sd, "out_norm")), sd, "out_conv")
+    return (v, acts + [v]) if trace else v
 
 
 def cfg_of(module):
