@@ -3,18 +3,7 @@
 
 // ================================================================== FlowMatchingModel ("--model original")
 // Encoder-decoder velocity net of src/models/flow_matching.py:34-173, 1x28x28 images.
-struct rgfm_fmnet {
-  rgfm_fmnet_desc d;
-  float* params = nullptr;
-  float* packed = nullptr;  // packed conv / deconv weights + re-indexed Linear weights
-  unsigned short* packed3 = nullptr;  // 3-plane bf16 conv / deconv weights (conv_mfma_bx3.hip)
-  unsigned short* packedh = nullptr;  // 2-plane scaled fp16 conv / deconv weights + scale records (conv_mfma_hx2.hip)
-  float* hq = nullptr;
-  unsigned* range_flag = nullptr;  // this handle's range-flag word
-  int conv_mode = -1;              // rgfm_fmnet_set_conv_mode: -1 = RGFM_CONV from the environment
-  float* freqs = nullptr;
-  size_t n_params = 0, n_packed = 0, n_packed3 = 0, n_packedh = 0;
-  int n_hq = 0;
+struct FmPlan {  // what plan_fmnet produces: blob / packed offsets of every layer
   size_t c1w = 0, c1b = 0;           // encoder.conv1 (reference layout, conv_in kernel)
   size_t egw[4], egb[4];             // encoder.gn1..4
   ConvW ec[3];                       // encoder.conv2..4
@@ -25,6 +14,10 @@ struct rgfm_fmnet {
   ConvW c3;                          // decoder.conv3
   size_t cow = 0, cob = 0, cow_pk = 0;  // decoder.conv_out (raw; re-laid out for conv_out_kernel in `packed`)
 };
+struct rgfm_fmnet : WeightStore, FmPlan {  // (`packed` also holds the re-indexed Linear weights)
+  rgfm_fmnet_desc d;
+  float* freqs = nullptr;
+};
 
 namespace {
 
@@ -33,49 +26,33 @@ constexpr int FM_FC_SPLITS = 14;                  // 12544/16 = 784 K-chunks = 1
 
 // state_dict order of FlowMatchingModel (flow_matching.py:43-54, :88-98, :147-151)
 size_t plan_fmnet(const rgfm_fmnet_desc& d, rgfm_fmnet* h) {
-  Cursor c, pk, p3, ph;
-  int nhq = 0;
-  rgfm_fmnet t;
+  Planner P;
+  Cursor &c = P.raw, &pk = P.pk;
+  FmPlan t;
   const int F = d.feature_dim, T = d.time_emb_dim;
-  auto conv = [&](int cin, int cout, int taps) {
-    ConvW w;
-    w.cin = cin, w.cout = cout, w.taps = taps;
-    w.w_raw = c.take((size_t)cout * cin * taps);
-    w.b = c.take(cout);
-    w.w_pk = pk.take((size_t)cout * cin * taps);
-    w.w_bx3 = p3.take((size_t)cout * cin * taps * 3);
-    w.w_hx2 = ph.take((size_t)cout * cin * taps * 2);
-    w.hq = nhq++;
-    return w;
-  };
   t.c1w = c.take((size_t)32 * d.img_channels * 9), t.c1b = c.take(32);
   t.egw[0] = c.take(32), t.egb[0] = c.take(32);
   const int ech[4] = {32, 64, 128, 256};
   for (int i = 1; i < 4; ++i) {
-    t.ec[i - 1] = conv(ech[i - 1], ech[i], 9);
+    t.ec[i - 1] = P.conv(ech[i - 1], ech[i], 9);
     t.egw[i] = c.take(ech[i]), t.egb[i] = c.take(ech[i]);
   }
   t.fcw = c.take((size_t)F * FM_CF * FM_P), t.fcb = c.take(F);
   t.fc_pk = pk.take((size_t)F * FM_CF * FM_P);
   t.f1w = c.take((size_t)FM_CF * FM_P * (F + T)), t.f1b = c.take((size_t)FM_CF * FM_P);
   t.f1w_pk = pk.take((size_t)FM_CF * FM_P * (F + T)), t.f1b_pk = pk.take((size_t)FM_CF * FM_P);
-  t.d1 = conv(256, 128, 16);
+  t.d1 = P.conv(256, 128, 16);
   t.dgw[0] = c.take(128), t.dgb[0] = c.take(128);
-  t.d2 = conv(128, 64, 16);
+  t.d2 = P.conv(128, 64, 16);
   t.dgw[1] = c.take(64), t.dgb[1] = c.take(64);
-  t.c3 = conv(64, 32, 9);
+  t.c3 = P.conv(64, 32, 9);
   t.dgw[2] = c.take(32), t.dgb[2] = c.take(32);
   t.cow = c.take((size_t)d.img_channels * 32 * 9), t.cob = c.take(d.img_channels);
   t.cow_pk = pk.take((size_t)d.img_channels * 32 * 9);
   if (h) {
-    float *pa = h->params, *pp = h->packed, *fr = h->freqs, *hqp = h->hq;
-    unsigned short *p3p = h->packed3, *php = h->packedh;
-    unsigned* rf = h->range_flag;
-    const int cm = h->conv_mode;
-    *h = t;
-    h->d = d, h->params = pa, h->packed = pp, h->freqs = fr, h->packed3 = p3p, h->packedh = php, h->hq = hqp, h->range_flag = rf;
-    h->conv_mode = cm;
-    h->n_packed = pk.off, h->n_packed3 = p3.off, h->n_packedh = ph.off, h->n_hq = nhq;
+    h->d = d;
+    static_cast<FmPlan&>(*h) = t;
+    static_cast<WeightLayout&>(*h) = P.layout();
   }
   return c.off;
 }
@@ -138,7 +115,7 @@ struct FmRun {
     ConvArgs c{};
     c.in0 = a.data, c.C0 = a.C, c.Hin = c.Win = a.S, c.ab = nullptr;
     c.wpk = h->packed + w.w_pk, c.wpk3 = h->packed3 + w.w_bx3, c.bias = h->params + w.b;
-    fill_hx2(c, h->packedh, h->hq, h->range_flag, w, nullptr);
+    fill_hx2(c, *h, w, nullptr);
     c.out = o.data, c.stats_out = o.stats, c.B = B, c.Cout = w.cout;
     const int sg = mode == CONV_T2 ? a.S : So;  // raster the tiles walk
     c.g = make_geom(sg, sg);
@@ -189,7 +166,7 @@ struct FmRun {
                          FM_P * FM_CF, s);
       // deconv1 stages this map RAW (no norm in front, flow_matching.py:113-116): the low side of the two-plane
       // representation is checked here, as a producing conv's epilogue would (ConvArgs::small_check)
-      if (g_modes.conv == CONV_ARITH_HX2 && h->d1.hx_ok) launch_range_low_check(d0, B, FM_P, FM_CF, h->range_flag, s);
+      if (g_modes.conv == CONV_ARITH_HX2 && h->d1.hx.ok) launch_range_low_check(d0, B, FM_P, FM_CF, h->range_flag, s);
     }
     Map m0;
     m0.data = d0, m0.C = FM_CF, m0.S = 7;
@@ -237,8 +214,7 @@ extern "C" int rgfm_fmnet_create(const rgfm_fmnet_desc* desc, const float* param
   if ((rc = ensure_init())) return rc;
   hipStream_t s = (hipStream_t)stream;
   rgfm_fmnet* h = new rgfm_fmnet();
-  h->n_params = plan_fmnet(*desc, h);
-  if (h->n_params != n_floats) {
+  if (plan_fmnet(*desc, h) != n_floats) {
     const size_t want = h->n_params;
     delete h;
     return fail(RGFM_EINVAL, "parameter blob has %zu floats, architecture needs %zu", n_floats, want);
@@ -248,33 +224,21 @@ extern "C" int rgfm_fmnet_create(const rgfm_fmnet_desc* desc, const float* param
     return fail(code, "%s", what);
   };
   const int F = desc->feature_dim, T = desc->time_emb_dim, half = T / 2;
-  if (hipMalloc(&h->params, n_floats * sizeof(float)) != hipSuccess) return bail(RGFM_ENOMEM, "hipMalloc(params)");
-  if (hipMalloc(&h->packed, (h->n_packed + 4) * sizeof(float)) != hipSuccess) return bail(RGFM_ENOMEM, "hipMalloc(packed)");
+  if ((rc = h->alloc(params_dev, true, s))) return rgfm_fmnet_destroy(h), rc;
   if (hipMalloc(&h->freqs, half * sizeof(float)) != hipSuccess) return bail(RGFM_ENOMEM, "hipMalloc(freqs)");
-  if (hipMalloc(&h->packed3, (h->n_packed3 + 8) * sizeof(unsigned short)) != hipSuccess) return bail(RGFM_ENOMEM, "hipMalloc(packed3)");
-  if (hipMalloc(&h->packedh, (h->n_packedh + 8) * sizeof(unsigned short)) != hipSuccess) return bail(RGFM_ENOMEM, "hipMalloc(packedh)");
-  if (hipMalloc(&h->hq, ((size_t)h->n_hq * 4 + 4) * sizeof(float)) != hipSuccess) return bail(RGFM_ENOMEM, "hipMalloc(hq)");
-  if (alloc_flag_word(&h->range_flag) != RGFM_OK) return bail(RGFM_ENOMEM, "hipMalloc(range flag)");
-  if (hipMemcpyAsync(h->params, params_dev, n_floats * sizeof(float), hipMemcpyDeviceToDevice, s) != hipSuccess)
-    return bail(RGFM_EHIP, "hipMemcpyAsync(params)");
   {
     auto packh = [&](const ConvW& w, int mode) {
-      launch_pack_conv_hx2(h->params + w.w_raw, h->packedh + w.w_hx2, h->hq + 4 * w.hq, w.cout, w.cin, w.taps, mode, s);
+      launch_pack_conv_hx2(h->params + w.w_raw, h->packedh + w.hx.off, h->hq + 4 * w.hx.hq, w.cout, w.cin, w.taps, mode, s);
     };
     packh(h->ec[0], CONV_S2), packh(h->ec[1], CONV_S2), packh(h->ec[2], CONV_S1), packh(h->c3, CONV_S1);
     packh(h->d1, CONV_T2), packh(h->d2, CONV_T2);
-    std::vector<ConvW*> all{&h->ec[0], &h->ec[1], &h->ec[2], &h->c3, &h->d1, &h->d2};
-    if (read_hx_flags(h->hq, h->n_hq, all, s) != RGFM_OK) return bail(RGFM_EHIP, "reading the fp16 scale records failed");
+    if ((rc = read_hx_flags(*h, {&h->ec[0].hx, &h->ec[1].hx, &h->ec[2].hx, &h->c3.hx, &h->d1.hx, &h->d2.hx}, s)))
+      return rgfm_fmnet_destroy(h), rc;
     // (as rgfm_unet_create: a conv behind a GroupNorm with out-of-window parameters leaves the fp16 path)
-    std::vector<float> host(n_floats);
-    if (hipMemcpyAsync(host.data(), h->params, n_floats * sizeof(float), hipMemcpyDeviceToHost, s) != hipSuccess ||
-        hipStreamSynchronize(s) != hipSuccess)
-      return bail(RGFM_EHIP, "reading the parameters back failed");
+    std::vector<NormGate> gates{{h->dgw[0], h->dgb[0], 128, &h->d2.hx}, {h->dgw[1], h->dgb[1], 64, &h->c3.hx}};
     const int ech[3] = {32, 64, 128};
-    for (int i = 0; i < 3; ++i)
-      if (!norm_params_ok(host, h->egw[i], h->egb[i], ech[i])) h->ec[i].hx_ok = false;
-    if (!norm_params_ok(host, h->dgw[0], h->dgb[0], 128)) h->d2.hx_ok = false;
-    if (!norm_params_ok(host, h->dgw[1], h->dgb[1], 64)) h->c3.hx_ok = false;
+    for (int i = 0; i < 3; ++i) gates.push_back({h->egw[i], h->egb[i], ech[i], &h->ec[i].hx});
+    if ((rc = demote_by_norms(*h, gates, s))) return rgfm_fmnet_destroy(h), rc;
   }
   for (int i = 0; i < 3; ++i) {  // encoder conv2 / conv3 are stride 2 (phase-ordered weights), conv4 stride 1
     const ConvW& w = h->ec[i];
@@ -303,13 +267,8 @@ extern "C" int rgfm_fmnet_create(const rgfm_fmnet_desc* desc, const float* param
 
 extern "C" void rgfm_fmnet_destroy(rgfm_fmnet* h) {
   if (!h) return;
-  if (h->params) (void)hipFree(h->params);
-  if (h->packed) (void)hipFree(h->packed);
-  if (h->packed3) (void)hipFree(h->packed3);
-  if (h->packedh) (void)hipFree(h->packedh);
-  if (h->hq) (void)hipFree(h->hq);
+  h->free();
   if (h->freqs) (void)hipFree(h->freqs);
-  if (h->range_flag) (void)hipFree(h->range_flag);
   delete h;
 }
 

@@ -2,26 +2,20 @@
 #include "rgfm_host.h"
 
 // ================================================================== ratio estimators
-struct rgfm_ratio {
+// (packedh / hq: the encoders' 3x3 convs once more as two scaled fp16 planes (conv_mfma_hx2*.hip) -- the forward half of
+// the gradient-guided sampler's per-step ratio pass runs on the default arithmetic of the U-Nets it guides; no bf16 image,
+// no range flag of its own)
+struct rgfm_ratio : WeightStore {
   rgfm_ratio_desc d;
-  float* params = nullptr;
-  float* packed = nullptr;
   float* bn = nullptr;  // folded BatchNorm scale/shift pairs
   // gradient path (kind RGFM_RATIO_MNIST_SVHN): transposed weights, built at create time
   float* gradw = nullptr;  // [packed W^T of every conv after the first | fc W^T | dense W^T | zeros]
-  size_t n_gradw = 0, g_zeros = 0;
-  // the encoders' 3x3 convs once more as two scaled fp16 planes (conv_mfma_hx2*.hip): the forward half of the
-  // gradient-guided sampler's per-step ratio pass runs on the default arithmetic of the U-Nets it guides
-  unsigned short* packedh = nullptr;
-  float* hq = nullptr;
-  size_t n_packedh = 0;
-  int n_hq = 0;
-  size_t n_params = 0, n_packed = 0, n_bn = 0;
+  size_t n_gradw = 0, g_zeros = 0, n_bn = 0;
   struct Conv {
     size_t wt_pk = 0;  // packed transposed weights (offset into gradw), convs after the first
-    ConvW wt_h;        // the same transposed weights as two scaled fp16 planes (offsets into packedh / hq): the reverse pass
-                       // inside the gradient-guided sampler runs on the U-Nets' default arithmetic (round 4)
-    ConvW w;
+    HxImage wt_h;      // the same transposed weights as two scaled fp16 planes: the reverse pass inside the
+                       // gradient-guided sampler runs on the U-Nets' default arithmetic (round 4)
+    ConvW w;           // (no bf16 image; the first conv of an encoder has no packed images at all)
     size_t nw = 0, nb = 0;                 // GroupNorm weight/bias (mnist28) or BatchNorm w/b
     size_t rm = 0, rv = 0;                 // BatchNorm running stats
     size_t bn_scale = 0, bn_shift = 0;     // offsets into `bn`
@@ -50,7 +44,8 @@ namespace {
 // Parameter order of RatioEstimatorMNISTSVHN (src/models/ratio_flexible.py:191-208,
 // :241-269, :327-345) and RatioEstimator (src/models/ratio_estimator.py:43-65, :121-135).
 size_t plan_ratio(const rgfm_ratio_desc& d, rgfm_ratio* h) {
-  Cursor c, pk, bn, gw;
+  Planner P;
+  Cursor &c = P.raw, &pk = P.pk, bn, gw;
   const int F = d.feature_dim, Hd = d.hidden_dim;
   auto encoder = [&](int in_ch, int size, const std::vector<int>& chans, const std::vector<int>& pools, bool batchnorm) {
     rgfm_ratio::Encoder e;
@@ -61,12 +56,11 @@ size_t plan_ratio(const rgfm_ratio_desc& d, rgfm_ratio* h) {
       cv.w.cin = ci, cv.w.cout = chans[i], cv.w.taps = 9;
       cv.w.w_raw = c.take((size_t)chans[i] * ci * 9);
       cv.w.b = c.take(chans[i]);
-      if (i > 0) cv.w.w_pk = pk.take((size_t)chans[i] * ci * 9);
-      if (i > 0) cv.wt_pk = gw.take((size_t)chans[i] * ci * 9);
-      if (i > 0 && h) cv.w.w_hx2 = h->n_packedh, h->n_packedh += (size_t)chans[i] * ci * 9 * 2, cv.w.hq = h->n_hq++;
-      if (i > 0 && h) {
-        cv.wt_h.cin = chans[i], cv.wt_h.cout = ci, cv.wt_h.taps = 9;
-        cv.wt_h.w_hx2 = h->n_packedh, h->n_packedh += (size_t)chans[i] * ci * 9 * 2, cv.wt_h.hq = h->n_hq++;
+      if (i > 0) {
+        cv.w.w_pk = pk.take((size_t)chans[i] * ci * 9);
+        cv.wt_pk = gw.take((size_t)chans[i] * ci * 9);
+        cv.w.hx = P.image((size_t)chans[i] * ci * 9 * 2);
+        cv.wt_h = P.image((size_t)chans[i] * ci * 9 * 2);
       }
       cv.nw = c.take(chans[i]);
       cv.nb = c.take(chans[i]);
@@ -110,7 +104,8 @@ size_t plan_ratio(const rgfm_ratio_desc& d, rgfm_ratio* h) {
   const size_t headw = c.take(dims.back()), headb = c.take(1);
   if (h) {
     h->ex = ex, h->ey = ey, h->hidden = hidden, h->headw = headw, h->headb = headb, h->head_in = dims.back();
-    h->n_packed = pk.off, h->n_bn = bn.off;
+    static_cast<WeightLayout&>(*h) = P.layout();
+    h->n_bn = bn.off;
     h->g_zeros = gw.take(1024);
     h->n_gradw = gw.off;
   }
@@ -241,8 +236,7 @@ extern "C" int rgfm_ratio_create(const rgfm_ratio_desc* desc, const float* param
   hipStream_t s = (hipStream_t)stream;
   rgfm_ratio* h = new rgfm_ratio();
   h->d = *desc;
-  h->n_params = plan_ratio(*desc, h);
-  if (h->n_params != n_floats) {
+  if (plan_ratio(*desc, h) != n_floats) {
     const size_t want = h->n_params;
     delete h;
     return fail(RGFM_EINVAL, "parameter blob has %zu floats, architecture needs %zu", n_floats, want);
@@ -251,11 +245,8 @@ extern "C" int rgfm_ratio_create(const rgfm_ratio_desc* desc, const float* param
     rgfm_ratio_destroy(h);
     return fail(code, "%s", what);
   };
-  if (hipMalloc(&h->params, n_floats * sizeof(float)) != hipSuccess) return bail(RGFM_ENOMEM, "hipMalloc(params)");
-  if (hipMalloc(&h->packed, (h->n_packed + 4) * sizeof(float)) != hipSuccess) return bail(RGFM_ENOMEM, "hipMalloc(packed)");
+  if ((rc = h->alloc(params_dev, false, s))) return rgfm_ratio_destroy(h), rc;
   if (hipMalloc(&h->bn, (h->n_bn + 4) * sizeof(float)) != hipSuccess) return bail(RGFM_ENOMEM, "hipMalloc(bn)");
-  if (hipMemcpyAsync(h->params, params_dev, n_floats * sizeof(float), hipMemcpyDeviceToDevice, s) != hipSuccess)
-    return bail(RGFM_EHIP, "hipMemcpyAsync(params)");
   for (const auto* e : {&h->ex, &h->ey})
     for (size_t i = 0; i < e->convs.size(); ++i) {
       const auto& cv = e->convs[i];
@@ -268,8 +259,6 @@ extern "C" int rgfm_ratio_create(const rgfm_ratio_desc* desc, const float* param
     // gradient path (rgfm_ratio_grad_log_ratio): dL/d(in) of a 3x3 conv is the conv of dL/d(out) with the weights
     // transposed and the taps flipped; of a Linear, the Linear with W^T
     if (hipMalloc(&h->gradw, (h->n_gradw + 4) * sizeof(float)) != hipSuccess) return bail(RGFM_ENOMEM, "hipMalloc(gradw)");
-    if (hipMalloc(&h->packedh, (h->n_packedh + 8) * sizeof(unsigned short)) != hipSuccess) return bail(RGFM_ENOMEM, "hipMalloc(packedh)");
-    if (hipMalloc(&h->hq, ((size_t)h->n_hq * 4 + 4) * sizeof(float)) != hipSuccess) return bail(RGFM_ENOMEM, "hipMalloc(hq)");
     float* tmp = nullptr;
     if (hipMalloc(&tmp, (size_t)256 * 256 * 9 * sizeof(float)) != hipSuccess) return bail(RGFM_ENOMEM, "hipMalloc(tmp)");
     for (const auto* e : {&h->ex, &h->ey}) {
@@ -277,7 +266,7 @@ extern "C" int rgfm_ratio_create(const rgfm_ratio_desc* desc, const float* param
         const auto& cv = e->convs[i];
         launch_conv_weight_transpose(h->params + cv.w.w_raw, tmp, cv.w.cout, cv.w.cin, s);
         launch_pack_conv(tmp, h->gradw + cv.wt_pk, cv.w.cin, cv.w.cout, 9, nt32_of(cv.w.cin), s);
-        launch_pack_conv_hx2(tmp, h->packedh + cv.wt_h.w_hx2, h->hq + 4 * cv.wt_h.hq, cv.w.cin, cv.w.cout, 9, CONV_S1, s);
+        launch_pack_conv_hx2(tmp, h->packedh + cv.wt_h.off, h->hq + 4 * cv.wt_h.hq, cv.w.cin, cv.w.cout, 9, CONV_S1, s);
       }
       launch_transpose2d(h->params + e->fcw, h->gradw + e->fcw_t, desc->feature_dim, e->fc_in, s);
     }
@@ -288,15 +277,15 @@ extern "C" int rgfm_ratio_create(const rgfm_ratio_desc* desc, const float* param
       return bail(RGFM_EHIP, "building the transposed weights failed");
     }
     (void)hipFree(tmp);
-    std::vector<ConvW*> all;
+    std::vector<HxImage*> images;
     for (auto* e : {&h->ex, &h->ey})
       for (size_t i = 1; i < e->convs.size(); ++i) {
         ConvW& w = e->convs[i].w;
-        launch_pack_conv_hx2(h->params + w.w_raw, h->packedh + w.w_hx2, h->hq + 4 * w.hq, w.cout, w.cin, 9, CONV_S1, s);
-        all.push_back(&w);
-        all.push_back(&e->convs[i].wt_h);
+        launch_pack_conv_hx2(h->params + w.w_raw, h->packedh + w.hx.off, h->hq + 4 * w.hx.hq, w.cout, w.cin, 9, CONV_S1, s);
+        images.push_back(&w.hx);
+        images.push_back(&e->convs[i].wt_h);
       }
-    if (read_hx_flags(h->hq, h->n_hq, all, s) != RGFM_OK) return bail(RGFM_EHIP, "reading the fp16 scale records failed");
+    if ((rc = read_hx_flags(*h, images, s))) return rgfm_ratio_destroy(h), rc;
   }
   *out = h;
   return RGFM_OK;
@@ -304,11 +293,8 @@ extern "C" int rgfm_ratio_create(const rgfm_ratio_desc* desc, const float* param
 
 extern "C" void rgfm_ratio_destroy(rgfm_ratio* h) {
   if (!h) return;
-  if (h->params) (void)hipFree(h->params);
-  if (h->packed) (void)hipFree(h->packed);
+  h->free();
   if (h->bn) (void)hipFree(h->bn);
-  if (h->packedh) (void)hipFree(h->packedh);
-  if (h->hq) (void)hipFree(h->hq);
   if (h->gradw) (void)hipFree(h->gradw);
   delete h;
 }
@@ -447,8 +433,8 @@ struct RatioGradRun {
           c.ep_scale = h->bn + cv.bn_scale, c.ep_shift = h->bn + cv.bn_shift, c.ep_nosilu = 1;
           c.out = z, c.stats_out = nullptr, c.B = n, c.Cout = cv.w.cout, c.g = g;
           c.halo_px = g.spt * (g.th + 2) * (g.W + 2);
-          if (flag && g_modes.conv == CONV_ARITH_HX2 && cv.w.hx_ok) {
-            c.wpkh = h->packedh + cv.w.w_hx2, c.hq = h->hq + 4 * cv.w.hq, c.range_flag = flag;
+          if (flag && g_modes.conv == CONV_ARITH_HX2 && cv.w.hx.ok) {
+            c.wpkh = h->packedh + cv.w.hx.off, c.hq = h->hq + 4 * cv.w.hx.hq, c.range_flag = flag;
             launch_conv(c, CONV_S1, s);  // (fp16 two-plane conv with the BatchNorm epilogue; fp32 MFMA when unsupported)
           } else {
             launch_conv_mfma(c, CONV_S1, s);
@@ -495,7 +481,7 @@ struct RatioGradRun {
           launch_gn_bwd(gz, k.z, h->params + cv.nw, k.mr, n, k.S * k.S, k.C, 8, s);
         } else {
           // (inside the sampler the next conv runs on the two-plane arithmetic: it needs the tensor's magnitude)
-          am = (flag && i > 0 && amax && g_modes.conv == CONV_ARITH_HX2 && g_modes.rev_hx2 && cv.wt_h.hx_ok) ? amax + amax_used++ : nullptr;
+          am = (flag && i > 0 && amax && g_modes.conv == CONV_ARITH_HX2 && g_modes.rev_hx2 && cv.wt_h.ok) ? amax + amax_used++ : nullptr;
           launch_grad_act(g, k.z, h->bn + cv.bn_scale, gz, n, k.S, k.C, mode, s, am);
         }
       }
@@ -517,7 +503,7 @@ struct RatioGradRun {
           // weights outside the fp16 window): the exact fp32 matrix-core conv.
           bool hx = false;
           if (am) {
-            c.wpkh = h->packedh + cv.wt_h.w_hx2, c.hq = h->hq + 4 * cv.wt_h.hq, c.range_flag = flag, c.in_amax = am;
+            c.wpkh = h->packedh + cv.wt_h.off, c.hq = h->hq + 4 * cv.wt_h.hq, c.range_flag = flag, c.in_amax = am;
             hx = conv_hx2_supported(c, CONV_S1);
           }
           if (hx) launch_conv_hx2(c, CONV_S1, s);

@@ -13,62 +13,37 @@ extern "C" int rgfm_unet_param_floats(const rgfm_unet_desc* desc, size_t* n_floa
 // phase order, the Upsample parity-class sums, the Winograd images and the output conv's layout; then which convs may
 // run on the fp16 path (synchronises once).  Used by rgfm_unet_create and, in place, by rgfm_unet_update_params.
 static int pack_weights(rgfm_unet* h, hipStream_t s) {
-  std::vector<ConvW*> all;
+  std::vector<HxImage*> images;
+  std::vector<NormGate> gates;
+  std::vector<ConvW*> res_convs;
   for (auto* v : {&h->enc, &h->mid, &h->dec})
     for (ResW& r : *v) {
-      all.push_back(&r.c1), all.push_back(&r.c2);
-      if (r.has_skip) all.push_back(&r.sk);
+      res_convs.push_back(&r.c1), res_convs.push_back(&r.c2);
+      if (r.has_skip) res_convs.push_back(&r.sk);
+      gates.push_back({r.n1w, r.n1b, r.cin, &r.c1.hx}), gates.push_back({r.n2w, r.n2b, r.cout, &r.c2.hx});
     }
-  for (ConvW* w : all) pack_one(h, *w, CONV_S1, s);
-  for (ConvW& w : h->down) pack_one(h, w, CONV_S2, s), all.push_back(&w);  // stride-2 convs: phase-ordered weights
-  for (ConvW& w : h->down)  // ... and once more in plain tap order (same scale record: same weights)
-    launch_pack_conv_hx2(h->params + w.w_raw, h->packedh + (w.w_hx9 - 1), h->hq + 4 * w.hq, w.cout, w.cin, 9, CONV_S1, s);
-  for (ConvW& w : h->up) pack_one(h, w, CONV_S1, s), all.push_back(&w);
+  for (ConvW* w : res_convs) pack_one(h, *w, CONV_S1, s), images.push_back(&w->hx);
+  for (ConvW& w : h->down) {  // stride-2 convs: phase-ordered weights, and once more in plain tap order
+    pack_one(h, w, CONV_S2, s), images.push_back(&w.hx);
+    launch_pack_conv_hx2(h->params + w.w_raw, h->packedh + w.hx9.off, h->hq + 4 * w.hx9.hq, w.cout, w.cin, 9, CONV_S1, s);
+    images.push_back(&w.hx9);
+  }
   // the Upsample convs once more as ConvTranspose2d(4, 2, 1) weights (summed taps), packed in parity-class order; the
   // ResBlock convs once more as Winograd images (one scratch array serves both)
-  std::vector<ConvW> t2rec(h->up.size());
-  std::vector<ConvW*> wino;
-  for (auto* v : {&h->enc, &h->mid, &h->dec})
-    for (ResW& r : *v) {
-      if (r.c1.w_w) wino.push_back(&r.c1);
-      if (r.c2.w_w) wino.push_back(&r.c2);
-    }
-  std::vector<ConvW> wrec(wino.size());
-  float* t2tmp = h->wtmp;
-  {
-    for (size_t i = 0; i < h->up.size(); ++i) {
-      const ConvW& w = h->up[i];
-      launch_up2_as_deconv(h->params + w.w_raw, t2tmp, w.cout, w.cin, s);
-      launch_pack_conv_hx2(t2tmp, h->packedh + (w.w_t2 - 1), h->hq + 4 * w.hq_t2, w.cout, w.cin, 16, CONV_T2, s);
-      t2rec[i].hq = w.hq_t2;
-      all.push_back(&t2rec[i]);
-    }
-    for (size_t i = 0; i < wino.size(); ++i) {
-      const ConvW& w = *wino[i];
-      launch_pack_conv_hx2w(h->params + w.w_raw, h->packedh + (w.w_w - 1), h->hq + 4 * w.hq_w, t2tmp, w.cout, w.cin, s);
-      wrec[i].hq = w.hq_w;
-      all.push_back(&wrec[i]);
-    }
+  for (ConvW& w : h->up) {
+    pack_one(h, w, CONV_S1, s), images.push_back(&w.hx);
+    launch_up2_as_deconv(h->params + w.w_raw, h->wtmp, w.cout, w.cin, s);
+    launch_pack_conv_hx2(h->wtmp, h->packedh + w.t2.off, h->hq + 4 * w.t2.hq, w.cout, w.cin, 16, CONV_T2, s);
+    images.push_back(&w.t2);
   }
-  const int rc_flags = read_hx_flags(h->hq, h->n_hq, all, s);  // (synchronises: the temporary is free)
-  if (rc_flags != RGFM_OK) return fail(RGFM_EHIP, "reading the fp16 scale records failed");
-  for (size_t i = 0; i < h->up.size(); ++i) h->up[i].t2_ok = t2rec[i].hx_ok;
-  for (size_t i = 0; i < wino.size(); ++i) wino[i]->w_ok = wrec[i].hx_ok;
-  {
-    // (norm_params_ok: convs behind a GroupNorm with out-of-window parameters leave the fp16 path here)
-    std::vector<float> host(h->n_params);
-    if (hipMemcpyAsync(host.data(), h->params, h->n_params * sizeof(float), hipMemcpyDeviceToHost, s) != hipSuccess ||
-        hipStreamSynchronize(s) != hipSuccess)
-      return fail(RGFM_EHIP, "reading the parameters back failed");
-    auto norm_ok = [&](size_t gw, size_t gb, int C) { return norm_params_ok(host, gw, gb, C); };
-    for (auto* v : {&h->enc, &h->mid, &h->dec})
-      for (ResW& r : *v) {
-        if (!norm_ok(r.n1w, r.n1b, r.cin)) r.c1.hx_ok = false;
-        if (!norm_ok(r.n2w, r.n2b, r.cout)) r.c2.hx_ok = false;
-      }
-  }
+  for (ConvW* w : res_convs)
+    if (w->wino.present) {
+      launch_pack_conv_hx2w(h->params + w->w_raw, h->packedh + w->wino.off, h->hq + 4 * w->wino.hq, h->wtmp, w->cout, w->cin, s);
+      images.push_back(&w->wino);
+    }
   launch_pack_conv_out(h->params + h->ocw, h->packed + h->ocw_pk, h->d.in_channels, h->final_ch, s);
-  return RGFM_OK;
+  if (int rc = read_hx_flags(*h, images, s)) return rc;
+  return demote_by_norms(*h, gates, s);
 }
 
 extern "C" int rgfm_unet_create(const rgfm_unet_desc* desc, const float* params_dev, size_t n_floats,
@@ -80,8 +55,7 @@ extern "C" int rgfm_unet_create(const rgfm_unet_desc* desc, const float* params_
   hipStream_t s = (hipStream_t)stream;
   rgfm_unet* h = new rgfm_unet();
   h->d = *desc;
-  h->n_params = plan_unet(*desc, h);
-  if (h->n_params != n_floats) {
+  if (plan_unet(*desc, h) != n_floats) {
     const size_t want = h->n_params;
     delete h;
     return fail(RGFM_EINVAL, "parameter blob has %zu floats, architecture needs %zu", n_floats, want);
@@ -97,21 +71,14 @@ extern "C" int rgfm_unet_create(const rgfm_unet_desc* desc, const float* params_
     rgfm_unet_destroy(h);
     return fail(code, "%s", what);
   };
-  if (hipMalloc(&h->params, n_floats * sizeof(float)) != hipSuccess) return bail(RGFM_ENOMEM, "hipMalloc(params)");
-  if (hipMalloc(&h->packed, (h->n_packed + 4) * sizeof(float)) != hipSuccess) return bail(RGFM_ENOMEM, "hipMalloc(packed)");
-  if (hipMalloc(&h->packedh, (h->n_packedh + 8) * sizeof(unsigned short)) != hipSuccess) return bail(RGFM_ENOMEM, "hipMalloc(packedh)");
-  if (hipMalloc(&h->hq, ((size_t)h->n_hq * 4 + 4) * sizeof(float)) != hipSuccess) return bail(RGFM_ENOMEM, "hipMalloc(hq)");
-  if (alloc_flag_word(&h->range_flag) != RGFM_OK) return bail(RGFM_ENOMEM, "hipMalloc(range flag)");
-  if (hipMalloc(&h->packed3, (h->n_packed3 + 8) * sizeof(unsigned short)) != hipSuccess) return bail(RGFM_ENOMEM, "hipMalloc(packed3)");
-  if (hipMemcpyAsync(h->params, params_dev, n_floats * sizeof(float), hipMemcpyDeviceToDevice, s) != hipSuccess)
-    return bail(RGFM_EHIP, "hipMemcpyAsync(params)");
+  if ((rc = h->alloc(params_dev, true, s))) return rgfm_unet_destroy(h), rc;
   {
     size_t mx = 0;
     for (const ConvW& w : h->up) mx = std::max(mx, (size_t)w.cin * w.cout * 16);
     for (const auto* v : {&h->enc, &h->mid, &h->dec})
       for (const ResW& r : *v) {
-        if (r.c1.w_w) mx = std::max(mx, (size_t)r.c1.cin * r.c1.cout * 16);
-        if (r.c2.w_w) mx = std::max(mx, (size_t)r.c2.cin * r.c2.cout * 16);
+        if (r.c1.wino.present) mx = std::max(mx, (size_t)r.c1.cin * r.c1.cout * 16);
+        if (r.c2.wino.present) mx = std::max(mx, (size_t)r.c2.cin * r.c2.cout * 16);
       }
     if (mx && hipMalloc(&h->wtmp, mx * sizeof(float)) != hipSuccess) return bail(RGFM_ENOMEM, "hipMalloc(upsample weights)");
   }
@@ -136,15 +103,10 @@ extern "C" int rgfm_unet_create(const rgfm_unet_desc* desc, const float* params_
 
 extern "C" void rgfm_unet_destroy(rgfm_unet* h) {
   if (!h) return;
-  if (h->params) (void)hipFree(h->params);
-  if (h->packed) (void)hipFree(h->packed);
-  if (h->packedh) (void)hipFree(h->packedh);
-  if (h->hq) (void)hipFree(h->hq);
-  if (h->packed3) (void)hipFree(h->packed3);
+  h->free();
   if (h->freqs) (void)hipFree(h->freqs);
   if (h->lin_dev) (void)hipFree(h->lin_dev);
   if (h->wtmp) (void)hipFree(h->wtmp);
-  if (h->range_flag) (void)hipFree(h->range_flag);
   delete h;
 }
 
@@ -200,11 +162,8 @@ extern "C" int rgfm_unet_time_embedding(rgfm_unet* h, const float* t_dev, int t_
                                         size_t ws_bytes, rgfm_stream_t stream) {
   if (!h || !t_dev || !emb_out || !ws || t_count < 1) return fail(RGFM_EINVAL, "bad argument");
   if (table_bytes(h, t_count) > ws_bytes) return fail(RGFM_ENOMEM, "workspace too small");
-  TimeEmbedArgs a{};
-  a.params = h->params, a.freqs = h->freqs, a.mc = h->mc, a.temb = h->temb;
-  a.te0w = (int)h->te0w, a.te0b = (int)h->te0b, a.te2w = (int)h->te2w, a.te2b = (int)h->te2b;
-  a.lin = h->lin_dev, a.nlin = h->nlin, a.total = h->temb_total;
-  a.t_dev = t_dev, a.num_steps = 1, a.step_begin = 0, a.table = reinterpret_cast<float*>(ws), a.emb_out = emb_out;
+  TimeEmbedArgs a = time_embed_args(h, t_dev, 1, 0, reinterpret_cast<float*>(ws));
+  a.emb_out = emb_out;
   launch_time_embed(a, t_count, (hipStream_t)stream);
   HIP_TRY(hipGetLastError());
   return RGFM_OK;

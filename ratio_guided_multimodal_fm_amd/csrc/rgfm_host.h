@@ -166,24 +166,55 @@ struct Cursor {
   }
 };
 
+// One two-plane fp16 weight image (conv_mfma_hx2*.hip) of a conv.
+struct HxImage {
+  size_t off = 0;        // offset (fp16 elements) into the packedh buffer
+  int hq = 0;            // index of its scale record {q, 1/q, s_w, eligible} in the hq array
+  bool present = false;  // the plan carved it
+  bool ok = false;       // weights inside the fp16 path's range (read_hx_flags, after packing)
+  bool usable() const { return present && ok; }
+};
+
 struct ConvW {  // one packed conv
   size_t w_raw = 0, b = 0;  // offsets into the params blob
   size_t w_pk = 0;          // offset into the packed buffer
   size_t w_bx3 = 0;         // offset (bf16 elements) into the 3-plane bf16 buffer of conv_mfma_bx3.hip
-  size_t w_hx2 = 0;         // offset (fp16 elements) into the 2-plane fp16 buffer of conv_mfma_hx2.hip
-  size_t w_hx9 = 0;         // stride-2 convs: offset of the plain nine-tap fp16 image (conv_mfma_hx2s.hip), + 1 (0: none)
-  int hq = 0;               // index of the conv's scale record {q, 1/q, s_w, eligible} in the handle's hq array
-  bool hx_ok = false;       // weights inside the fp16 path's range (set after packing)
   int cin = 0, cout = 0, taps = 9;
-  // Upsample convs (nearest x 2, then 3x3: unet_flexible.py:107-108) a second time as the EQUIVALENT ConvTranspose2d(4, 2, 1)
+  HxImage hx;    // the image every conv has, in the order of its mode (stride-2 convs: phase-major)
+  HxImage hx9;   // stride-2 convs once more in plain nine-tap order (conv_mfma_hx2s.hip): same weights, hx's scale record
+  HxImage wino;  // ResBlock convs with Cout % 64 == 0 once more as Winograd F(2x2, 3x3) images (conv_mfma_hx2w.hip)
+  // Upsample convs (nearest x 2, then 3x3: unet_flexible.py:107-108) once more as the EQUIVALENT ConvTranspose2d(4, 2, 1)
   // -- four 2x2-tap parity classes over the INPUT raster, 16 instead of 36 tap products per input pixel (launch_up2_as_deconv)
-  // ResBlock convs with Cout % 64 == 0 a second time as Winograd F(2x2, 3x3) images (conv_mfma_hx2w.hip)
-  size_t w_w = 0;           // offset (fp16 elements) of the transformed two-plane image, + 1 (0: none)
-  int hq_w = 0;             // its scale record
-  bool w_ok = false;        // ... inside the fp16 path's range
-  size_t w_t2 = 0;          // offset of its packed two-plane image, + 1 (0: none)
-  int hq_t2 = 0;            // its scale record
-  bool t2_ok = false;       // ... inside the fp16 path's range
+  HxImage t2;
+};
+
+// What a plan hands to the weight store: element counts of the buffers every handle owns.
+struct WeightLayout {
+  size_t n_params = 0, n_packed = 0, n_packed3 = 0, n_packedh = 0;
+  int n_hq = 0;
+};
+
+// The cursors of one plan: the state_dict-order blob, the fp32-packed, bf16 and fp16 buffers and the scale records.
+struct Planner {
+  Cursor raw, pk, p3, ph;
+  int nhq = 0;
+  // a two-plane image of n_fp16 elements; `same_scale`: an image of the same weights, whose scale record this one shares
+  HxImage image(size_t n_fp16, const HxImage* same_scale = nullptr) {
+    HxImage i;
+    i.off = ph.take(n_fp16), i.hq = same_scale ? same_scale->hq : nhq++, i.present = true;
+    return i;
+  }
+  ConvW conv(int cin, int cout, int taps) {
+    ConvW w;
+    w.cin = cin, w.cout = cout, w.taps = taps;
+    w.w_raw = raw.take((size_t)cout * cin * taps);
+    w.b = raw.take(cout);
+    w.w_pk = pk.take((size_t)cout * cin * taps);
+    w.w_bx3 = p3.take((size_t)cout * cin * taps * 3);
+    w.hx = image((size_t)cout * cin * taps * 2);
+    return w;
+  }
+  WeightLayout layout() const { return {raw.off, pk.off, p3.off, ph.off, nhq}; }
 };
 
 struct ResW {
@@ -329,19 +360,6 @@ inline int ensure_init() {
   return RGFM_OK;
 }
 
-// Would launch_conv send this launch to a kernel that can write ConvArgs::pout (the P-format hand-over)?
-inline bool p_producer_ok(const ConvArgs& c, int mode) {
-  if (g_modes.conv != CONV_ARITH_HX2 || !g_modes.pipelined || !g_modes.pfmt) return false;
-  if (g_modes.s2 && conv_hx2s_supported(c, mode)) return false;
-  if (g_modes.c8 && conv_hx2c_supported(c, mode)) return true;
-  if (g_modes.quad && conv_hx2q_supported(c, mode)) return false;
-  // conv_mfma_hx2p_kernel: 16x16 rasters (a tile = one whole sample), whole power-of-two groups per 32-channel wave block
-  if (mode == CONV_S1 && c.g.W == 16 && c.g.H == 16 && c.g.spt == 1 && c.g.tps == 1 && (c.Cout == 64 || c.Cout == 128 || c.Cout == 256) &&
-      !c.ep_scale && !c.fin_ab && conv_hx2p_supported(c, mode))
-    return true;
-  return false;
-}
-
 // Where the Winograd form is the faster kernel (tools/kbench, B = 512, profiles/r04_kbench/hx2w_vs_direct.txt): its K loop
 // costs less per chunk than the direct kernels', its epilogue (the output transform through LDS) more -- so the long-K
 // layers: 128 or more input channels.  By layer shape only, never by batch.
@@ -362,6 +380,17 @@ inline int conv_route(const ConvArgs& c, int mode) {
   if (hx2 && conv_hx2_supported(c, mode)) return RGFM_ROUTE_HX2;
   if (g_modes.conv != CONV_ARITH_F32 && conv_bx3_supported(c, mode)) return RGFM_ROUTE_BX3;
   return RGFM_ROUTE_F32;
+}
+
+// Would launch_conv send this launch to a kernel that can write ConvArgs::pout (the P-format hand-over)?  Asked with
+// pout already set, which conv_hx2w_supported rejects: the Winograd line of conv_route cannot fire here.
+inline bool p_producer_ok(const ConvArgs& c, int mode) {
+  if (!g_modes.pfmt) return false;
+  const int route = conv_route(c, mode);
+  if (route == RGFM_ROUTE_HX2C) return true;
+  // conv_mfma_hx2p_kernel: 16x16 rasters (a tile = one whole sample), whole power-of-two groups per 32-channel wave block
+  return route == RGFM_ROUTE_HX2P && mode == CONV_S1 && c.g.W == 16 && c.g.H == 16 && c.g.spt == 1 && c.g.tps == 1 &&
+         (c.Cout == 64 || c.Cout == 128 || c.Cout == 256) && !c.ep_scale && !c.fin_ab;
 }
 
 inline void launch_conv_on(int route, const ConvArgs& c, int mode, hipStream_t s) {
@@ -420,23 +449,82 @@ inline int check_conv_mode(int mode) {
 }
 
 
-// ================================================================== U-Net
-struct rgfm_unet {
-  rgfm_unet_desc d;
-  float* params = nullptr;  // device copy of the state_dict-order blob
-  float* packed = nullptr;  // packed conv weights
+// ------------------------------------------------------------------ weight store
+// The device buffers every handle owns, sized by its plan's WeightLayout.
+struct WeightStore : WeightLayout {
+  float* params = nullptr;            // device copy of the state_dict-order blob
+  float* packed = nullptr;            // packed fp32 conv weights (+ whatever else the handle re-lays out)
+  unsigned short* packed3 = nullptr;  // 3-plane bf16 weights (conv_mfma_bx3.hip); null when the plan has none
   unsigned short* packedh = nullptr;  // 2-plane scaled fp16 weights (conv_mfma_hx2.hip)
-  size_t n_packedh = 0;
-  float* hq = nullptr;      // [n_hq][4] scale records of packedh
-  int n_hq = 0;
-  unsigned* range_flag = nullptr;  // this handle's range-flag word
-  int conv_mode = -1;              // rgfm_unet_set_conv_mode: -1 = RGFM_CONV from the environment
-  unsigned short* packed3 = nullptr;  // 3-plane bf16 weights (conv_mfma_bx3.hip)
-  size_t n_packed3 = 0;
+  float* hq = nullptr;                // [n_hq][4] scale records of packedh
+  unsigned* range_flag = nullptr;     // this handle's range-flag word (the velocity nets)
+  int conv_mode = -1;                 // rgfm_*_set_conv_mode: -1 = RGFM_CONV from the environment
+
+  // allocates the buffers of the layout and copies the caller's blob in (stream-ordered)
+  int alloc(const float* params_dev, bool with_range_flag, hipStream_t s) {
+    if (hipMalloc(&params, n_params * sizeof(float)) != hipSuccess) return fail(RGFM_ENOMEM, "hipMalloc(params)");
+    if (hipMalloc(&packed, (n_packed + 4) * sizeof(float)) != hipSuccess) return fail(RGFM_ENOMEM, "hipMalloc(packed)");
+    if (hipMalloc(&packedh, (n_packedh + 8) * sizeof(unsigned short)) != hipSuccess) return fail(RGFM_ENOMEM, "hipMalloc(packedh)");
+    if (hipMalloc(&hq, ((size_t)n_hq * 4 + 4) * sizeof(float)) != hipSuccess) return fail(RGFM_ENOMEM, "hipMalloc(hq)");
+    if (with_range_flag && alloc_flag_word(&range_flag) != RGFM_OK) return fail(RGFM_ENOMEM, "hipMalloc(range flag)");
+    if (n_packed3 && hipMalloc(&packed3, (n_packed3 + 8) * sizeof(unsigned short)) != hipSuccess)
+      return fail(RGFM_ENOMEM, "hipMalloc(packed3)");
+    if (hipMemcpyAsync(params, params_dev, n_params * sizeof(float), hipMemcpyDeviceToDevice, s) != hipSuccess)
+      return fail(RGFM_EHIP, "hipMemcpyAsync(params)");
+    return RGFM_OK;
+  }
+  void free() {
+    for (void* p : {(void*)params, (void*)packed, (void*)packed3, (void*)packedh, (void*)hq, (void*)range_flag})
+      if (p) (void)hipFree(p);
+  }
+};
+
+// after the pack launches: which images may run on the fp16 path, from their scale records (one synchronising copy)
+inline int read_hx_flags(const WeightStore& st, const std::vector<HxImage*>& images, hipStream_t s) {
+  std::vector<float> host((size_t)st.n_hq * 4);
+  if (hipMemcpyAsync(host.data(), st.hq, host.size() * sizeof(float), hipMemcpyDeviceToHost, s) != hipSuccess ||
+      hipStreamSynchronize(s) != hipSuccess)
+    return fail(RGFM_EHIP, "reading the fp16 scale records failed");
+  for (HxImage* i : images) i->ok = host[(size_t)i->hq * 4 + 3] != 0.f;
+  return RGFM_OK;
+}
+
+// The normalised inputs of the fp16 path are S_A silu(gamma xhat + beta): in range for every trained net the reference
+// can produce, but a conv whose norm parameters are tiny (the activation would sit in the fp16 subnormals) or huge is
+// routed to the split-bf16 kernel, like a conv with out-of-window weights.  `host` = the parameter blob.
+inline bool norm_params_ok(const std::vector<float>& host, size_t gw, size_t gb, int C) {
+  float mg = 0.f, mb = 0.f;
+  for (int i = 0; i < C; ++i) mg = std::max(mg, std::fabs(host[gw + i])), mb = std::max(mb, std::fabs(host[gb + i]));
+  if (!(mg <= 3.0e38f) || !(mb <= 3.0e38f)) return false;
+  const float hi = 8.f * mg + mb, lo = std::max(mg, mb);  // |gamma xhat + beta| for |xhat| <= 8; the activation's scale
+  return hi < 1024.f && lo >= 0.015625f;
+}
+
+struct NormGate {  // a GroupNorm (blob offsets, channels) in front of the conv that owns `image`
+  size_t gamma, beta;
+  int C;
+  HxImage* image;
+};
+
+// after read_hx_flags (which recomputes every verdict): convs behind a GroupNorm with out-of-window parameters leave
+// the fp16 path (one synchronising read of the blob)
+inline int demote_by_norms(const WeightStore& st, const std::vector<NormGate>& gates, hipStream_t s) {
+  std::vector<float> host(st.n_params);
+  if (hipMemcpyAsync(host.data(), st.params, host.size() * sizeof(float), hipMemcpyDeviceToHost, s) != hipSuccess ||
+      hipStreamSynchronize(s) != hipSuccess)
+    return fail(RGFM_EHIP, "reading the parameters back failed");
+  for (const NormGate& g : gates)
+    if (!norm_params_ok(host, g.gamma, g.beta, g.C)) g.image->ok = false;
+  return RGFM_OK;
+}
+
+
+// ================================================================== U-Net
+struct rgfm_unet : WeightStore {
+  rgfm_unet_desc d;
   float* freqs = nullptr;
   TimeLinear* lin_dev = nullptr;
   float* wtmp = nullptr;  // scratch of the Upsample / Winograd weight images (kept for rgfm_unet_update_params)
-  size_t n_params = 0, n_packed = 0;
   int mc = 0, temb = 0, nlin = 0, temb_total = 0;
   size_t te0w, te0b, te2w, te2b, icw, icb, onw, onb, ocw, ocb;
   size_t ocw_pk = 0;  // out_conv weights re-laid out for conv_out_kernel (offset into `packed`)
@@ -460,38 +548,26 @@ struct rgfm_unet {
 // (reference src/models/unet_flexible.py:146-201; UNetMNIST, src/models/unet.py:155-214,
 // is identical) and records blob offsets.  Returns the total float count.
 inline size_t plan_unet(const rgfm_unet_desc& d, rgfm_unet* h) {
-  Cursor c;
-  Cursor pk, p3, ph;
-  int nhq = 0;
+  Planner P;
+  Cursor& c = P.raw;
   const int mc = d.model_channels, temb = 4 * mc;
   std::vector<ResW> enc, mid, dec;
   std::vector<ConvW> down, up;
   int temb_off = 0;
-  auto conv = [&](int cin, int cout, int taps) {
-    ConvW w;
-    w.cin = cin, w.cout = cout, w.taps = taps;
-    w.w_raw = c.take((size_t)cout * cin * taps);
-    w.b = c.take(cout);
-    w.w_pk = pk.take((size_t)cout * cin * taps);
-    w.w_bx3 = p3.take((size_t)cout * cin * taps * 3);
-    w.w_hx2 = ph.take((size_t)cout * cin * taps * 2);
-    w.hq = nhq++;
-    return w;
-  };
   auto res = [&](int cin, int cout) {
     ResW r;
     r.cin = cin, r.cout = cout;
     r.n1w = c.take(cin), r.n1b = c.take(cin);
-    r.c1 = conv(cin, cout, 9);
+    r.c1 = P.conv(cin, cout, 9);
     r.tw = c.take((size_t)cout * temb), r.tb = c.take(cout);
     r.n2w = c.take(cout), r.n2b = c.take(cout);
-    r.c2 = conv(cout, cout, 9);
+    r.c2 = P.conv(cout, cout, 9);
     if (cout % 64 == 0 && cin % KC == 0) {  // the Winograd images (16 positions instead of 9 taps)
-      r.c1.w_w = ph.take((size_t)cout * cin * 16 * 2) + 1, r.c1.hq_w = nhq++;
-      r.c2.w_w = ph.take((size_t)cout * cout * 16 * 2) + 1, r.c2.hq_w = nhq++;
+      r.c1.wino = P.image((size_t)cout * cin * 16 * 2);
+      r.c2.wino = P.image((size_t)cout * cout * 16 * 2);
     }
     r.has_skip = cin != cout;
-    if (r.has_skip) r.sk = conv(cin, cout, 1);
+    if (r.has_skip) r.sk = P.conv(cin, cout, 1);
     r.temb_off = temb_off;
     temb_off += cout;
     return r;
@@ -514,8 +590,8 @@ inline size_t plan_unet(const rgfm_unet_desc& d, rgfm_unet* h) {
     }
   }
   for (int dc : down_ch) {
-    ConvW w = conv(dc, dc, 9);
-    w.w_hx9 = ph.take((size_t)dc * dc * 9 * 2) + 1;  // (the Downsample convs twice: phase-major and plain)
+    ConvW w = P.conv(dc, dc, 9);
+    w.hx9 = P.image((size_t)dc * dc * 9 * 2, &w.hx);  // (the Downsample convs twice: phase-major and plain)
     down.push_back(w);
   }
   mid.push_back(res(ch, ch));
@@ -530,14 +606,13 @@ inline size_t plan_unet(const rgfm_unet_desc& d, rgfm_unet* h) {
     if (l > 0) up_ch.push_back(ch);
   }
   for (int uc : up_ch) {
-    ConvW w = conv(uc, uc, 9);
-    w.w_t2 = ph.take((size_t)uc * uc * 16 * 2) + 1;  // (the Upsample convs twice: nine taps, and the parity-class form)
-    w.hq_t2 = nhq++;
+    ConvW w = P.conv(uc, uc, 9);
+    w.t2 = P.image((size_t)uc * uc * 16 * 2);  // (the Upsample convs twice: nine taps, and the parity-class form)
     up.push_back(w);
   }
   const size_t onw = c.take(ch), onb = c.take(ch);
   const size_t ocw = c.take((size_t)d.in_channels * ch * 9), ocb = c.take(d.in_channels);
-  const size_t ocw_pk = pk.take((size_t)d.in_channels * ch * 9);
+  const size_t ocw_pk = P.pk.take((size_t)d.in_channels * ch * 9);
   if (h) {
     h->mc = mc, h->temb = temb;
     h->te0w = te0w, h->te0b = te0b, h->te2w = te2w, h->te2b = te2b;
@@ -545,9 +620,7 @@ inline size_t plan_unet(const rgfm_unet_desc& d, rgfm_unet* h) {
     h->enc = enc, h->mid = mid, h->dec = dec, h->down = down, h->up = up;
     h->final_ch = ch;
     h->temb_total = temb_off;
-    h->n_packed = pk.off;
-    h->n_packedh = ph.off, h->n_hq = nhq;
-    h->n_packed3 = p3.off;
+    static_cast<WeightLayout&>(*h) = P.layout();
   }
   return c.off;
 }
@@ -575,36 +648,16 @@ inline void pack_one(const rgfm_unet* h, const ConvW& w, int mode, hipStream_t s
   launch_pack_conv(h->params + w.w_raw, h->packed + w.w_pk, w.cout, w.cin, w.taps, nt32_of(w.cout), s);
   if (mode == CONV_S2) launch_pack_conv_bx3_s2(h->params + w.w_raw, h->packed3 + w.w_bx3, w.cout, w.cin, s);
   else launch_pack_conv_bx3(h->params + w.w_raw, h->packed3 + w.w_bx3, w.cout, w.cin, w.taps, s);
-  launch_pack_conv_hx2(h->params + w.w_raw, h->packedh + w.w_hx2, h->hq + 4 * w.hq, w.cout, w.cin, w.taps, mode, s);
-}
-
-// after the pack launches: which convs may run on the fp16 path (one synchronising copy at create time)
-inline int read_hx_flags(const float* hq_dev, int n, std::vector<ConvW*>& convs, hipStream_t s) {
-  std::vector<float> host((size_t)n * 4);
-  HIP_TRY(hipMemcpyAsync(host.data(), hq_dev, host.size() * sizeof(float), hipMemcpyDeviceToHost, s));
-  HIP_TRY(hipStreamSynchronize(s));
-  for (ConvW* w : convs) w->hx_ok = host[(size_t)w->hq * 4 + 3] != 0.f;
-  return RGFM_OK;
+  launch_pack_conv_hx2(h->params + w.w_raw, h->packedh + w.hx.off, h->hq + 4 * w.hx.hq, w.cout, w.cin, w.taps, mode, s);
 }
 
 // fills the fp16-path fields of a conv launch (main conv `w`, optional fused 1x1 skip `sk`)
-inline void fill_hx2(ConvArgs& c, const unsigned short* packedh, const float* hq, unsigned* flag, const ConvW& w, const ConvW* sk) {
-  if (!w.hx_ok || (sk && !sk->hx_ok)) return;
-  c.wpkh = packedh + w.w_hx2, c.hq = hq + 4 * w.hq, c.range_flag = flag;
-  if (w.w_hx9) c.wpkh9 = packedh + (w.w_hx9 - 1);
-  if (w.w_w && w.w_ok && !sk) c.wpkw = packedh + (w.w_w - 1), c.hqw = hq + 4 * w.hq_w;
-  if (sk) c.wskiph = packedh + sk->w_hx2, c.hq_skip = hq + 4 * sk->hq;
-}
-
-// The normalised inputs of the fp16 path are S_A silu(gamma xhat + beta): in range for every trained net the reference
-// can produce, but a conv whose norm parameters are tiny (the activation would sit in the fp16 subnormals) or huge is
-// routed to the split-bf16 kernel once, at create, like a conv with out-of-window weights.  `host` = the parameter blob.
-inline bool norm_params_ok(const std::vector<float>& host, size_t gw, size_t gb, int C) {
-  float mg = 0.f, mb = 0.f;
-  for (int i = 0; i < C; ++i) mg = std::max(mg, std::fabs(host[gw + i])), mb = std::max(mb, std::fabs(host[gb + i]));
-  if (!(mg <= 3.0e38f) || !(mb <= 3.0e38f)) return false;
-  const float hi = 8.f * mg + mb, lo = std::max(mg, mb);  // |gamma xhat + beta| for |xhat| <= 8; the activation's scale
-  return hi < 1024.f && lo >= 0.015625f;
+inline void fill_hx2(ConvArgs& c, const WeightStore& st, const ConvW& w, const ConvW* sk) {
+  if (!w.hx.usable() || (sk && !sk->hx.usable())) return;
+  c.wpkh = st.packedh + w.hx.off, c.hq = st.hq + 4 * w.hx.hq, c.range_flag = st.range_flag;
+  if (w.hx9.usable()) c.wpkh9 = st.packedh + w.hx9.off;
+  if (w.wino.usable() && !sk) c.wpkw = st.packedh + w.wino.off, c.hqw = st.hq + 4 * w.wino.hq;
+  if (sk) c.wskiph = st.packedh + sk->hx.off, c.hq_skip = st.hq + 4 * sk->hx.hq;
 }
 
 inline double conv_flops(int B, int HW, int cout, int kprod) { return 2.0 * B * HW * (double)cout * kprod; }
@@ -740,16 +793,16 @@ struct UNetRun {
     c.g = make_geom(So, So);
     c.halo_px = mode == CONV_S2 ? c.g.spt * (2 * c.g.th + 1) * (2 * c.g.W + 1) : c.g.spt * (c.g.th + 2) * (c.g.W + 2);
     const int kprod = 9 * w.cin + (res_mode == 2 ? sk->cin : 0);
-    fill_hx2(c, h->packedh, h->hq, h->range_flag, w, res_mode == 2 ? sk : nullptr);
+    fill_hx2(c, *h, w, res_mode == 2 ? sk : nullptr);
     if (g_modes.conv == CONV_ARITH_HX2) c.range_flag = h->range_flag, c.small_check = raw_consumed ? 1 : 0;
-    if (mode == CONV_UP2 && g_modes.conv == CONV_ARITH_HX2 && g_modes.up_t2 && w.w_t2 && w.t2_ok && up_parts_match(a.S)) {
+    if (mode == CONV_UP2 && g_modes.conv == CONV_ARITH_HX2 && g_modes.up_t2 && w.t2.usable() && up_parts_match(a.S)) {
       // nearest x 2 + 3x3 == ConvTranspose2d(4, 2, 1) with summed taps: the parity-class form over the INPUT raster
       // (4 / 9 of the matrix work, a quarter of the halo per output).  Its statistics parts -- four classes x the input
       // raster's parts -- have the sizes of the output raster's parts (up_parts_match), so readers see a plain map.
       ConvArgs ct = c;
       ct.g = make_geom(a.S, a.S);
       ct.halo_px = ct.g.spt * (ct.g.th + 2) * (ct.g.W + 2);
-      ct.wpkh = h->packedh + (w.w_t2 - 1), ct.hq = h->hq + 4 * w.hq_t2;
+      ct.wpkh = h->packedh + w.t2.off, ct.hq = h->hq + 4 * w.t2.hq;
       if (conv_hx2_supported(ct, CONV_T2)) c = ct, mode = CONV_T2;
     }
     bool p_in = false;
@@ -774,7 +827,7 @@ struct UNetRun {
         c.ab = finalize(a, b, norm->gamma, norm->beta, ab_buf);  // (may attach itself to the pending producer)
     }
     flush_conv(pend, s, h->routes);
-    if (g_modes.conv == CONV_ARITH_HX2 && g_modes.pipelined && g_modes.wino && hx2w_pays(c) && conv_hx2w_supported(c, mode)) h->wino_convs += 1;
+    if (conv_route(c, mode) == RGFM_ROUTE_HX2W) h->wino_convs += 1;  // (as described: a finalize or pout attached later moves it)
     pend.valid = true, pend.c = c, pend.mode = mode;
     pend.flops = conv_flops(B, So * So, w.cout, kprod);
     return o;
@@ -793,7 +846,7 @@ struct UNetRun {
     // the 8x8 level and 64-channel 16x16 layers; 128-channel 16x16 layers keep the fp32 hand-over.
     if ((a.S == 8 || (a.S == 16 && r.cout == 64)) && r.cout % 64 == 0) {
       h1.p = ws->f((size_t)B * a.S * a.S * r.cout);
-      if (!dry && pend.valid && pend.c.out == h1.data && r.c1.hx_ok && r.c2.hx_ok && (!r.has_skip || r.sk.hx_ok)) {
+      if (!dry && pend.valid && pend.c.out == h1.data && r.c1.hx.ok && r.c2.hx.ok && (!r.has_skip || r.sk.hx.ok)) {
         pend.c.pout = h1.p, pend.c.pn_gamma = h->params + r.n2w, pend.c.pn_beta = h->params + r.n2b;
         if (p_producer_ok(pend.c, pend.mode)) h1.p_valid = true;
         else pend.c.pout = nullptr;
@@ -882,19 +935,21 @@ inline size_t unet_eval_bytes(rgfm_unet* h, int B) {
   return b.off;
 }
 
-inline int launch_time_table(rgfm_unet* h, const float* t_dev, int num_steps, int step_begin, int nt, float* table,
-                      hipStream_t s) {
+inline TimeEmbedArgs time_embed_args(const rgfm_unet* h, const float* t_dev, int num_steps, int step_begin, float* table) {
   TimeEmbedArgs a{};
   a.params = h->params, a.freqs = h->freqs, a.mc = h->mc, a.temb = h->temb;
   a.te0w = (int)h->te0w, a.te0b = (int)h->te0b, a.te2w = (int)h->te2w, a.te2b = (int)h->te2b;
   a.lin = h->lin_dev, a.nlin = h->nlin, a.total = h->temb_total;
   a.t_dev = t_dev, a.num_steps = num_steps, a.step_begin = step_begin, a.table = table;
-  ProfScope p(RGFM_KCLASS_OTHER, 0, s);
-  launch_time_embed(a, nt, s);
-  return RGFM_OK;
+  return a;
 }
 
-
+inline int launch_time_table(rgfm_unet* h, const float* t_dev, int num_steps, int step_begin, int nt, float* table,
+                      hipStream_t s) {
+  ProfScope p(RGFM_KCLASS_OTHER, 0, s);
+  launch_time_embed(time_embed_args(h, t_dev, num_steps, step_begin, table), nt, s);
+  return RGFM_OK;
+}
 
 inline size_t table_bytes(const rgfm_unet* h, int rows) {
   return (((size_t)rows * h->temb_total * sizeof(float)) + 255) & ~(size_t)255;
