@@ -212,6 +212,38 @@ int rgfm_ratio_grad_workspace_bytes(const rgfm_ratio* h, int n, size_t* bytes);
 int rgfm_ratio_grad_log_ratio(rgfm_ratio* h, const float* x, const float* y, float* gx, float* gy,
                               float* log_ratio_out, int n, void* ws, size_t ws_bytes, rgfm_stream_t stream);
 
+/* Training pass of the ratio estimators (exact fp32 arithmetic on v_mfma_f32_32x32x2_f32, NCHW fp32 tensors,
+ * stream-ordered, caller-owned workspace, nothing allocated or synchronised inside a call; both kinds).
+ *
+ * rgfm_ratio_forward_train writes score_out[n] = forward(x, y) and leaves in `ws` what rgfm_ratio_backward needs; `ws`
+ * (rgfm_ratio_train_workspace_bytes(h, n)) must stay untouched between the two calls.
+ *   training != 0: BatchNorm normalises with the batch mean and the biased batch variance (eps 1e-5), and Dropout is
+ *     applied behind the SiLU of the score MLP where the reference has a Dropout layer (the first two hidden layers
+ *     of either estimator): element i of [n][width] of Dropout layer `block` (counted from 0) is kept by the counter
+ *     hash documented for rgfm_unet_dropout_mask, kept values are scaled by 1 / (1 - p_drop), and the backward
+ *     regenerates the mask.  bn_stats_out (may be null; ignored for RGFM_RATIO_MNIST28) receives per BatchNorm layer,
+ *     in state_dict order, [C][2] = (batch mean, UNBIASED batch variance): what the running-statistics update needs.
+ *   training == 0: running statistics, no dropout, still differentiable.
+ * rgfm_ratio_backward: given dscore = dL/dscore_out, writes dL/dx and dL/dy (each optional) and dL/dparams -- one blob
+ * in state_dict order, overwritten; the slots of running_mean, running_var and num_batches_tracked are zero.  Every
+ * reduction has a fixed order: two calls on the same inputs give bitwise-identical results.
+ * rgfm_ratio_pool_choice (test hook, null stream): for max-pool `pool` of encoder `encoder` (0 = x, 1 = y), the
+ * window element (0..3, row-major) that the forward which filled `ws` chose and the backward routes to, as
+ * out[n][C][Ho][Wo] floats; ties go to the first element in row-major order, as in PyTorch.
+ * rgfm_ratio_dropout_mask (test hook, null stream): keep decisions (1.0 / 0.0) of Dropout layer `block`, out[n][width].
+ * rgfm_ratio_update_params copies a new state_dict-order blob into the handle and repacks every derived image in
+ * place (fp32-packed and two-plane conv weights, the transposed weights of rgfm_ratio_grad_log_ratio, the folded
+ * BatchNorm scale/shift).  Synchronises `stream` once (as create). */
+int rgfm_ratio_train_workspace_bytes(const rgfm_ratio* h, int n, size_t* bytes);
+int rgfm_ratio_forward_train(rgfm_ratio* h, const float* x, const float* y, float* score_out, int n, int training,
+                             float p_drop, uint64_t seed, float* bn_stats_out, void* ws, size_t ws_bytes,
+                             rgfm_stream_t stream);
+int rgfm_ratio_backward(rgfm_ratio* h, const float* dscore, float* dx_out, float* dy_out, float* dparams_out, int n,
+                        void* ws, size_t ws_bytes, rgfm_stream_t stream);
+int rgfm_ratio_pool_choice(rgfm_ratio* h, const void* ws, int encoder, int pool, int n, float* out);
+int rgfm_ratio_dropout_mask(rgfm_ratio* h, int block, uint64_t seed, float p_drop, int n, float* out);
+int rgfm_ratio_update_params(rgfm_ratio* h, const float* params_dev, size_t n_floats, rgfm_stream_t stream);
+
 /* ------------------------------------------------------------------------
  * Samplers (the Euler/ODE loops).
  * ---------------------------------------------------------------------- */

@@ -436,6 +436,13 @@ class RatioEngine(_EngineBase):
         d.loss_type = _LOSS.get(m.loss_type, 0)
         return d
 
+    def _check_eval(self, module):
+        if module.training:
+            raise _lib.RgfmError(
+                f"{type(module).__name__} is in training mode; model(x, y), log_ratio and grad_log_ratio implement "
+                "eval-mode semantics only (Dropout = identity, BatchNorm = running statistics). Train through "
+                "model.forward_train(x, y) (HIP backward, batch statistics, dropout), or call .eval().")
+
     def handle(self, device):
         m = self._module()
         sd = m.state_dict()
@@ -443,6 +450,13 @@ class RatioEngine(_EngineBase):
         if self._handle is not None and key == self._key:
             return self._handle
         L = _lib.lib()
+        if self._handle is not None and key[-1] == self._key[-1] and _same_tensors(key[:-1], self._key[:-1]):
+            # only the values moved (an optimizer step, the running statistics): repack the same handle
+            blob = self._blob_from(sd, device)
+            with torch.cuda.device(device):
+                _lib.check(L.rgfm_ratio_update_params(self._handle, _ptr(blob), blob.numel(), _stream(device)))
+            self._key, self._blob = key, blob
+            return self._handle
         if self._handle is not None:
             self._destroy()
         d = self.desc()
@@ -461,6 +475,58 @@ class RatioEngine(_EngineBase):
     def _destroy(self):
         _lib.lib().rgfm_ratio_destroy(self._handle)
         self._handle = None
+
+    # ---- training -----------------------------------------------------
+    def image_shapes(self):
+        return ((1, 32, 32), (3, 32, 32)) if self.kind == "mnist_svhn" else ((1, 28, 28), (1, 28, 28))
+
+    def pool_geometry(self):
+        """Per encoder (x, y), per max-pool in forward order: (channels, output size)."""
+        if self.kind == "mnist_svhn":
+            return [(32, 16), (64, 8), (128, 4)], [(64, 16), (128, 8), (256, 4), (256, 2)]
+        return [(32, 14), (64, 7), (128, 3)], [(32, 14), (64, 7), (128, 3)]
+
+    def _check_pair(self, x, y):
+        _require_hip(x, y)
+        sx, sy = self.image_shapes()
+        if x.dim() != 4 or y.dim() != 4 or tuple(x.shape[1:]) != sx or tuple(y.shape[1:]) != sy or x.shape[0] != y.shape[0]:
+            raise _lib.RgfmError(f"expected x of shape [B,{sx[0]},{sx[1]},{sx[2]}] and y of shape [B,{sy[0]},{sy[1]},{sy[2]}], got "
+                                 f"{tuple(x.shape)} and {tuple(y.shape)}")
+
+    def forward_train(self, x, y):
+        """scores = model(x, y) in the module's current mode, differentiable w.r.t. x, y and the parameters
+        (_RatioTrainFn).  In training mode: batch statistics, dropout, and the BatchNorm buffers are updated."""
+        m = self._module()
+        self._check_pair(x, y)
+        p = m.dropout_p() if m.training else 0.0
+        return _RatioTrainFn.apply(self, x, y, float(p), *m.parameters())
+
+    def dropout_mask(self, block, seed, p, batch, device):
+        """Keep decisions (1 / 0) of Dropout layer `block` of the score MLP: [batch, width] (rgfm_ratio_dropout_mask)."""
+        m = self._module()
+        width = [l.out_features for l in m.score_net if isinstance(l, torch.nn.Linear)][block]
+        out = torch.empty(batch, width, device=device)
+        with torch.cuda.device(device):
+            _lib.check(_lib.lib().rgfm_ratio_dropout_mask(self.handle(device), int(block), int(seed), float(p),
+                                                          int(batch), _ptr(out)))
+        return out
+
+    def pool_choices(self):
+        """The window elements (0..3, row-major) the max-pools of the latest forward_train chose, per encoder (x, y) a
+        list of [B, C, Ho, Wo] tensors (rgfm_ratio_pool_choice).  Valid until that call's backward has run."""
+        ws, n = (self._last_train[0](), self._last_train[1]) if getattr(self, "_last_train", None) else (None, 0)
+        if ws is None:
+            raise _lib.RgfmError("no saved state: call pool_choices() between forward_train and its backward")
+        dev = ws.device
+        out = []
+        with torch.cuda.device(dev):
+            for e, geo in enumerate(self.pool_geometry()):
+                out.append([])
+                for i, (C, S) in enumerate(geo):
+                    t = torch.empty(n, C, S, S, device=dev)
+                    _lib.check(_lib.lib().rgfm_ratio_pool_choice(self._handle, _ptr(ws), e, i, n, _ptr(t)))
+                    out[-1].append(t)
+        return out
 
     def eval(self, x, y, what):
         m = self._module()
@@ -512,6 +578,76 @@ class RatioEngine(_EngineBase):
             _lib.check(L.rgfm_ratio_grad_log_ratio(h, _ptr(x), _ptr(y), _ptr(gx), _ptr(gy), _ptr(lr), n, _ptr(ws),
                                                    nb.value, _stream(dev)))
         return gx, gy, lr
+
+
+class _RatioTrainFn(torch.autograd.Function):
+    """Training forward / backward of the ratio estimators through rgfm_ratio_forward_train / rgfm_ratio_backward.
+
+    Inputs: the engine, x, y, p_drop and the module's parameters, so that autograd hands back dL/dx, dL/dy and every
+    dL/dparam.  Each call owns its saved-state buffer; the dropout seed is drawn from the device's torch generator.
+    While the module trains, the BatchNorm buffers are updated from the batch statistics the library reports."""
+
+    @staticmethod
+    def forward(ctx, engine, x, y, p_drop, *params):
+        m = engine._module()
+        dev = x.device
+        x, y = x.contiguous(), y.contiguous()
+        n = x.shape[0]
+        out = torch.empty(n, device=dev)
+        ctx.engine, ctx.n, ctx.ws, ctx.nbytes, ctx.h = engine, n, None, 0, None
+        ctx.save_for_backward(*params)
+        ctx.shapes = (x.shape, y.shape)
+        if n == 0:
+            return out
+        training = bool(m.training)
+        seed = int(torch.randint(0, 2 ** 62, (1,), device=dev).item()) if p_drop > 0 else 0
+        bns = [b for b in m.modules() if isinstance(b, torch.nn.BatchNorm2d)] if training else []
+        stats = torch.empty(2 * sum(b.num_features for b in bns), device=dev) if bns else None
+        named = {id(q) for q in m.parameters()}
+        ctx.layout = [(v.numel(), id(v) in named) for v in m.state_dict(keep_vars=True).values()]
+        L = _lib.lib()
+        with torch.cuda.device(dev):
+            h = engine.handle(dev)
+            nb = ctypes.c_size_t()
+            _lib.check(L.rgfm_ratio_train_workspace_bytes(h, n, ctypes.byref(nb)))
+            ws = torch.empty(nb.value, dtype=torch.uint8, device=dev)
+            _lib.check(L.rgfm_ratio_forward_train(h, _ptr(x), _ptr(y), _ptr(out), n, 1 if training else 0, p_drop, seed,
+                                                  _ptr(stats), _ptr(ws), nb.value, _stream(dev)))
+        off = 0
+        for b in bns:  # nn.BatchNorm2d's update: momentum 0.1, unbiased batch variance
+            st = stats[off:off + 2 * b.num_features].view(-1, 2)
+            off += 2 * b.num_features
+            mom = b.momentum
+            b.running_mean.mul_(1 - mom).add_(st[:, 0], alpha=mom)
+            b.running_var.mul_(1 - mom).add_(st[:, 1], alpha=mom)
+            b.num_batches_tracked.add_(1)
+        ctx.ws, ctx.nbytes, ctx.h = ws, nb.value, h
+        engine._last_train = (weakref.ref(ws), n)
+        return out
+
+    @staticmethod
+    def backward(ctx, dscore):
+        params = ctx.saved_tensors
+        dev = dscore.device
+        need_x, need_y = ctx.needs_input_grad[1], ctx.needs_input_grad[2]
+        if ctx.n == 0:
+            return (None, torch.zeros(ctx.shapes[0], device=dev) if need_x else None,
+                    torch.zeros(ctx.shapes[1], device=dev) if need_y else None, None, *[torch.zeros_like(q) for q in params])
+        if ctx.ws is None:
+            raise _lib.RgfmError("the saved state of this forward_train call is gone (backward ran twice?)")
+        if ctx.engine._handle is not ctx.h:
+            raise _lib.RgfmError("the module's handle was re-created between forward_train and backward")
+        dscore = dscore.to(torch.float32).contiguous()
+        dparams = torch.empty(sum(k for k, _ in ctx.layout), device=dev)
+        dx = torch.empty(ctx.shapes[0], device=dev) if need_x else None
+        dy = torch.empty(ctx.shapes[1], device=dev) if need_y else None
+        with torch.cuda.device(dev):
+            _lib.check(_lib.lib().rgfm_ratio_backward(ctx.h, _ptr(dscore), _ptr(dx), _ptr(dy), _ptr(dparams), ctx.n,
+                                                      _ptr(ctx.ws), ctx.nbytes, _stream(dev)))
+        ctx.ws = None
+        chunks = torch.split(dparams, [k for k, _ in ctx.layout])
+        grads = [g.view(q.shape) for g, q in zip([c for c, (_, is_p) in zip(chunks, ctx.layout) if is_p], params)]
+        return (None, dx, dy, None, *grads)
 
 
 # ---- sampler entry points ------------------------------------------------

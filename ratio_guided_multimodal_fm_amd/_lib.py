@@ -63,6 +63,14 @@ SIGNATURES = {
     "rgfm_ratio_grad_workspace_bytes": (c_int, [c_void_p, c_int, P(c_size_t)]),
     "rgfm_ratio_grad_log_ratio": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int,
                                           c_void_p, c_size_t, c_void_p]),
+    "rgfm_ratio_train_workspace_bytes": (c_int, [c_void_p, c_int, P(c_size_t)]),
+    "rgfm_ratio_forward_train": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_float, c_uint64,
+                                         c_void_p, c_void_p, c_size_t, c_void_p]),
+    "rgfm_ratio_backward": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_void_p, c_size_t,
+                                    c_void_p]),
+    "rgfm_ratio_pool_choice": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_void_p]),
+    "rgfm_ratio_dropout_mask": (c_int, [c_void_p, c_int, c_uint64, c_float, c_int, c_void_p]),
+    "rgfm_ratio_update_params": (c_int, [c_void_p, c_void_p, c_size_t, c_void_p]),
     "rgfm_sample_pair_grad_workspace_bytes": (c_int, [c_void_p, c_void_p, c_void_p, c_int, P(c_size_t)]),
     "rgfm_sample_pair_grad": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_double,
                                       c_int, c_int, c_void_p, c_size_t, c_void_p]),

@@ -1,44 +1,6 @@
 // api_ratio.cpp -- ratio estimators: evaluation, gradient of log r, and the gradient-guided paired sampler (C ABI: include/rgfm.h).
 #include "rgfm_host.h"
 
-// ================================================================== ratio estimators
-// (packedh / hq: the encoders' 3x3 convs once more as two scaled fp16 planes (conv_mfma_hx2*.hip) -- the forward half of
-// the gradient-guided sampler's per-step ratio pass runs on the default arithmetic of the U-Nets it guides; no bf16 image,
-// no range flag of its own)
-struct rgfm_ratio : WeightStore {
-  rgfm_ratio_desc d;
-  float* bn = nullptr;  // folded BatchNorm scale/shift pairs
-  // gradient path (kind RGFM_RATIO_MNIST_SVHN): transposed weights, built at create time
-  float* gradw = nullptr;  // [packed W^T of every conv after the first | fc W^T | dense W^T | zeros]
-  size_t n_gradw = 0, g_zeros = 0, n_bn = 0;
-  struct Conv {
-    size_t wt_pk = 0;  // packed transposed weights (offset into gradw), convs after the first
-    HxImage wt_h;      // the same transposed weights as two scaled fp16 planes: the reverse pass inside the
-                       // gradient-guided sampler runs on the U-Nets' default arithmetic (round 4)
-    ConvW w;           // (no bf16 image; the first conv of an encoder has no packed images at all)
-    size_t nw = 0, nb = 0;                 // GroupNorm weight/bias (mnist28) or BatchNorm w/b
-    size_t rm = 0, rv = 0;                 // BatchNorm running stats
-    size_t bn_scale = 0, bn_shift = 0;     // offsets into `bn`
-    bool pool_after = false;
-  };
-  struct Encoder {
-    int in_ch = 1, size = 32;
-    std::vector<Conv> convs;
-    size_t fcw = 0, fcb = 0;
-    size_t fcw_t = 0;  // fc weight transposed [fc_in][F] (offset into gradw)
-    int fc_in = 0;
-  };
-  Encoder ex, ey;
-  struct Dense {
-    size_t w, b, lw, lb;
-    size_t w_t = 0;  // weight transposed [in][out] (offset into gradw)
-    int in, out;
-  };
-  std::vector<Dense> hidden;
-  size_t headw = 0, headb = 0;
-  int head_in = 0;
-};
-
 namespace {
 
 // Parameter order of RatioEstimatorMNISTSVHN (src/models/ratio_flexible.py:191-208,
@@ -119,6 +81,41 @@ int check_ratio_desc(const rgfm_ratio_desc* d) {
     return fail(RGFM_EINVAL, "feature_dim must be a multiple of 64 (<=512), hidden_dim of 128 (<=1024)");
   if (d->loss_type != RGFM_LOSS_DISC && d->loss_type != RGFM_LOSS_RULSIF) return fail(RGFM_EINVAL, "unknown loss_type");
   return RGFM_OK;
+}
+
+// Every derived image of the handle from h->params: the fp32-packed and two-plane conv weights, the folded BatchNorm
+// scale/shift, and the transposed weights of the gradient path (dL/d(in) of a 3x3 conv is the conv of dL/d(out) with
+// the weights transposed and the taps flipped; of a Linear, the Linear with W^T); then which convs may run on the fp16
+// path (synchronises once).  Used by rgfm_ratio_create and, in place, by rgfm_ratio_update_params.
+int pack_ratio(rgfm_ratio* h, hipStream_t s) {
+  for (const auto* e : {&h->ex, &h->ey})
+    for (size_t i = 0; i < e->convs.size(); ++i) {
+      const auto& cv = e->convs[i];
+      if (i > 0) launch_pack_conv(h->params + cv.w.w_raw, h->packed + cv.w.w_pk, cv.w.cout, cv.w.cin, 9, nt32_of(cv.w.cout), s);
+      if (h->d.kind == RGFM_RATIO_MNIST_SVHN)
+        launch_bn_fold(h->params + cv.nw, h->params + cv.nb, h->params + cv.rm, h->params + cv.rv,
+                       h->bn + cv.bn_scale, h->bn + cv.bn_shift, cv.w.cout, s);
+    }
+  for (const auto* e : {&h->ex, &h->ey}) {
+    for (size_t i = 1; i < e->convs.size(); ++i) {
+      const auto& cv = e->convs[i];
+      launch_conv_weight_transpose(h->params + cv.w.w_raw, h->wtmp, cv.w.cout, cv.w.cin, s);
+      launch_pack_conv(h->wtmp, h->gradw + cv.wt_pk, cv.w.cin, cv.w.cout, 9, nt32_of(cv.w.cin), s);
+      launch_pack_conv_hx2(h->wtmp, h->packedh + cv.wt_h.off, h->hq + 4 * cv.wt_h.hq, cv.w.cin, cv.w.cout, 9, CONV_S1, s);
+    }
+    launch_transpose2d(h->params + e->fcw, h->gradw + e->fcw_t, h->d.feature_dim, e->fc_in, s);
+  }
+  for (const auto& dn : h->hidden) launch_transpose2d(h->params + dn.w, h->gradw + dn.w_t, dn.out, dn.in, s);
+  launch_fill(h->gradw + h->g_zeros, 0.f, 1024, s);
+  std::vector<HxImage*> images;
+  for (auto* e : {&h->ex, &h->ey})
+    for (size_t i = 1; i < e->convs.size(); ++i) {
+      ConvW& w = e->convs[i].w;
+      launch_pack_conv_hx2(h->params + w.w_raw, h->packedh + w.hx.off, h->hq + 4 * w.hx.hq, w.cout, w.cin, 9, CONV_S1, s);
+      images.push_back(&w.hx);
+      images.push_back(&e->convs[i].wt_h);
+    }
+  return read_hx_flags(*h, images, s);
 }
 
 struct RatioRun {
@@ -247,46 +244,9 @@ extern "C" int rgfm_ratio_create(const rgfm_ratio_desc* desc, const float* param
   };
   if ((rc = h->alloc(params_dev, false, s))) return rgfm_ratio_destroy(h), rc;
   if (hipMalloc(&h->bn, (h->n_bn + 4) * sizeof(float)) != hipSuccess) return bail(RGFM_ENOMEM, "hipMalloc(bn)");
-  for (const auto* e : {&h->ex, &h->ey})
-    for (size_t i = 0; i < e->convs.size(); ++i) {
-      const auto& cv = e->convs[i];
-      if (i > 0) launch_pack_conv(h->params + cv.w.w_raw, h->packed + cv.w.w_pk, cv.w.cout, cv.w.cin, 9, nt32_of(cv.w.cout), s);
-      if (desc->kind == RGFM_RATIO_MNIST_SVHN)
-        launch_bn_fold(h->params + cv.nw, h->params + cv.nb, h->params + cv.rm, h->params + cv.rv,
-                       h->bn + cv.bn_scale, h->bn + cv.bn_shift, cv.w.cout, s);
-    }
-  {
-    // gradient path (rgfm_ratio_grad_log_ratio): dL/d(in) of a 3x3 conv is the conv of dL/d(out) with the weights
-    // transposed and the taps flipped; of a Linear, the Linear with W^T
-    if (hipMalloc(&h->gradw, (h->n_gradw + 4) * sizeof(float)) != hipSuccess) return bail(RGFM_ENOMEM, "hipMalloc(gradw)");
-    float* tmp = nullptr;
-    if (hipMalloc(&tmp, (size_t)256 * 256 * 9 * sizeof(float)) != hipSuccess) return bail(RGFM_ENOMEM, "hipMalloc(tmp)");
-    for (const auto* e : {&h->ex, &h->ey}) {
-      for (size_t i = 1; i < e->convs.size(); ++i) {
-        const auto& cv = e->convs[i];
-        launch_conv_weight_transpose(h->params + cv.w.w_raw, tmp, cv.w.cout, cv.w.cin, s);
-        launch_pack_conv(tmp, h->gradw + cv.wt_pk, cv.w.cin, cv.w.cout, 9, nt32_of(cv.w.cin), s);
-        launch_pack_conv_hx2(tmp, h->packedh + cv.wt_h.off, h->hq + 4 * cv.wt_h.hq, cv.w.cin, cv.w.cout, 9, CONV_S1, s);
-      }
-      launch_transpose2d(h->params + e->fcw, h->gradw + e->fcw_t, desc->feature_dim, e->fc_in, s);
-    }
-    for (const auto& dn : h->hidden) launch_transpose2d(h->params + dn.w, h->gradw + dn.w_t, dn.out, dn.in, s);
-    launch_fill(h->gradw + h->g_zeros, 0.f, 1024, s);
-    if (hipStreamSynchronize(s) != hipSuccess) {
-      (void)hipFree(tmp);
-      return bail(RGFM_EHIP, "building the transposed weights failed");
-    }
-    (void)hipFree(tmp);
-    std::vector<HxImage*> images;
-    for (auto* e : {&h->ex, &h->ey})
-      for (size_t i = 1; i < e->convs.size(); ++i) {
-        ConvW& w = e->convs[i].w;
-        launch_pack_conv_hx2(h->params + w.w_raw, h->packedh + w.hx.off, h->hq + 4 * w.hx.hq, w.cout, w.cin, 9, CONV_S1, s);
-        images.push_back(&w.hx);
-        images.push_back(&e->convs[i].wt_h);
-      }
-    if ((rc = read_hx_flags(*h, images, s))) return rgfm_ratio_destroy(h), rc;
-  }
+  if (hipMalloc(&h->gradw, (h->n_gradw + 4) * sizeof(float)) != hipSuccess) return bail(RGFM_ENOMEM, "hipMalloc(gradw)");
+  if (hipMalloc(&h->wtmp, (size_t)256 * 256 * 9 * sizeof(float)) != hipSuccess) return bail(RGFM_ENOMEM, "hipMalloc(tmp)");
+  if ((rc = pack_ratio(h, s))) return rgfm_ratio_destroy(h), rc;
   *out = h;
   return RGFM_OK;
 }
@@ -296,7 +256,16 @@ extern "C" void rgfm_ratio_destroy(rgfm_ratio* h) {
   h->free();
   if (h->bn) (void)hipFree(h->bn);
   if (h->gradw) (void)hipFree(h->gradw);
+  if (h->wtmp) (void)hipFree(h->wtmp);
   delete h;
+}
+
+extern "C" int rgfm_ratio_update_params(rgfm_ratio* h, const float* params_dev, size_t n_floats, rgfm_stream_t stream) {
+  if (!h || !params_dev) return fail(RGFM_EINVAL, "null argument");
+  if (n_floats != h->n_params) return fail(RGFM_EINVAL, "parameter blob has %zu floats, the handle has %zu", n_floats, h->n_params);
+  hipStream_t s = (hipStream_t)stream;
+  HIP_TRY(hipMemcpyAsync(h->params, params_dev, n_floats * sizeof(float), hipMemcpyDeviceToDevice, s));
+  return pack_ratio(h, s);
 }
 
 extern "C" int rgfm_ratio_workspace_bytes(const rgfm_ratio* h, int n, size_t* bytes) {

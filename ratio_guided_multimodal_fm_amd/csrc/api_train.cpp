@@ -39,15 +39,6 @@ struct TrainPlan {
 
 int groups_of(int C) { return std::min(8, C); }
 
-void wgrad_split(UgConv& c) {
-  const int M = c.Cout, N = c.Cin * c.taps, K = c.B * c.Ho * c.Wo;
-  const int base = ((M + 63) / 64) * ((N + 63) / 64);
-  int splits = std::max(1, std::min((1024 + base - 1) / base, (K + 255) / 256));
-  const int kps = ((K + splits - 1) / splits + 15) / 16 * 16;
-  c.splits = (K + kps - 1) / kps;
-  c.kps = kps;
-}
-
 TrainPlan plan_train(const rgfm_unet* h, int B) {
   TrainPlan p;
   Cursor c;
@@ -159,23 +150,6 @@ UgConv conv_of(const rgfm_unet* h, const ConvW& w, int B, int S, int mode) {
   c.C0 = w.cin;
   c.splits = 1;
   return c;
-}
-
-void run_fwd(UgConv c, const float* x, float* out, const float* temb, const float* res, hipStream_t s) {
-  c.x = x, c.out = out, c.temb = temb, c.res = res, c.kps = c.Cin * c.taps;
-  launch_ug_conv(c, 0, s);
-}
-// input gradient of the conv input raster Hc x Wc into d0 (+ d1 beyond channel C0); acc: add instead of overwrite
-void run_dgrad(UgConv c, const float* dy, float* d0, float* d1, int C0, int acc, hipStream_t s) {
-  c.dy = dy, c.out = d0, c.out1 = d1, c.C0 = C0, c.acc0 = c.acc1 = acc, c.kps = c.Cout * c.taps;
-  launch_ug_conv(c, 1, s);
-}
-void run_wgrad(UgConv c, const float* dy, const float* x, float* part, float* dw, float* db, hipStream_t s) {
-  c.dy = dy, c.x = x, c.part = part;
-  wgrad_split(c);
-  launch_ug_conv(c, 2, s);
-  launch_ug_reduce(part, c.splits, (size_t)c.Cout * c.Cin * c.taps, dw, s);
-  launch_ug_bias_grad(dy, c.B, c.Cout, c.Ho * c.Wo, db, s);
 }
 
 UgAct act_of(const float* s0, const float* s1, int C0, int C1, int B, int HW, const float* mr, const float* gamma,

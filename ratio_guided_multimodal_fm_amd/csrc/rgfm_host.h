@@ -8,6 +8,8 @@
 //   api_unet.cpp     rgfm_unet_*            (create / forward / trace hooks)
 //   api_sampler.cpp  rgfm_sample_single, rgfm_guidance_*, rgfm_sample_pair
 //   api_ratio.cpp    rgfm_ratio_*, gradient of log r, rgfm_sample_pair_grad
+//   api_train.cpp    rgfm_unet_forward_train / _backward (U-Net training pass)
+//   api_ratio_train.cpp  rgfm_ratio_forward_train / _backward (ratio estimators' training pass)
 //   api_fmnet.cpp    rgfm_fmnet_*           (FlowMatchingModel)
 //
 // No PyTorch types, no allocation and no synchronisation inside forward / sample calls (everything is carved from the
@@ -1144,3 +1146,71 @@ int pair_loop(EvalX&& eval_x, EvalY&& eval_y, float* x_inout, float* y_inout, co
   return RGFM_OK;
 }
 
+
+// ================================================================== ratio estimators
+// (packedh / hq: the encoders' 3x3 convs once more as two scaled fp16 planes (conv_mfma_hx2*.hip) -- the forward half of
+// the gradient-guided sampler's per-step ratio pass runs on the default arithmetic of the U-Nets it guides; no bf16 image,
+// no range flag of its own)
+struct rgfm_ratio : WeightStore {
+  rgfm_ratio_desc d;
+  float* bn = nullptr;  // folded BatchNorm scale/shift pairs
+  // gradient path (kind RGFM_RATIO_MNIST_SVHN): transposed weights, built at create time
+  float* gradw = nullptr;  // [packed W^T of every conv after the first | fc W^T | dense W^T | zeros]
+  size_t n_gradw = 0, g_zeros = 0, n_bn = 0;
+  float* wtmp = nullptr;  // scratch of the transposed conv weights (kept for rgfm_ratio_update_params)
+  struct Conv {
+    size_t wt_pk = 0;  // packed transposed weights (offset into gradw), convs after the first
+    HxImage wt_h;      // the same transposed weights as two scaled fp16 planes: the reverse pass inside the
+                       // gradient-guided sampler runs on the U-Nets' default arithmetic (round 4)
+    ConvW w;           // (no bf16 image; the first conv of an encoder has no packed images at all)
+    size_t nw = 0, nb = 0;                 // GroupNorm weight/bias (mnist28) or BatchNorm w/b
+    size_t rm = 0, rv = 0;                 // BatchNorm running stats
+    size_t bn_scale = 0, bn_shift = 0;     // offsets into `bn`
+    bool pool_after = false;
+  };
+  struct Encoder {
+    int in_ch = 1, size = 32;
+    std::vector<Conv> convs;
+    size_t fcw = 0, fcb = 0;
+    size_t fcw_t = 0;  // fc weight transposed [fc_in][F] (offset into gradw)
+    int fc_in = 0;
+  };
+  Encoder ex, ey;
+  struct Dense {
+    size_t w, b, lw, lb;
+    size_t w_t = 0;  // weight transposed [in][out] (offset into gradw)
+    int in, out;
+  };
+  std::vector<Dense> hidden;
+  size_t headw = 0, headb = 0;
+  int head_in = 0;
+};
+
+
+// ================================================================== training passes (api_train.cpp, api_ratio_train.cpp)
+// One conv on ug_igemm_kernel (unet_grad.hip): forward, data gradient, weight gradient with its ordered split-K reduce.
+inline void wgrad_split(UgConv& c) {
+  const int M = c.Cout, N = c.Cin * c.taps, K = c.B * c.Ho * c.Wo;
+  const int base = ((M + 63) / 64) * ((N + 63) / 64);
+  int splits = std::max(1, std::min((1024 + base - 1) / base, (K + 255) / 256));
+  const int kps = ((K + splits - 1) / splits + 15) / 16 * 16;
+  c.splits = (K + kps - 1) / kps;
+  c.kps = kps;
+}
+
+inline void run_fwd(UgConv c, const float* x, float* out, const float* temb, const float* res, hipStream_t s) {
+  c.x = x, c.out = out, c.temb = temb, c.res = res, c.kps = c.Cin * c.taps;
+  launch_ug_conv(c, 0, s);
+}
+// input gradient of the conv input raster Hc x Wc into d0 (+ d1 beyond channel C0); acc: add instead of overwrite
+inline void run_dgrad(UgConv c, const float* dy, float* d0, float* d1, int C0, int acc, hipStream_t s) {
+  c.dy = dy, c.out = d0, c.out1 = d1, c.C0 = C0, c.acc0 = c.acc1 = acc, c.kps = c.Cout * c.taps;
+  launch_ug_conv(c, 1, s);
+}
+inline void run_wgrad(UgConv c, const float* dy, const float* x, float* part, float* dw, float* db, hipStream_t s) {
+  c.dy = dy, c.x = x, c.part = part;
+  wgrad_split(c);
+  launch_ug_conv(c, 2, s);
+  launch_ug_reduce(part, c.splits, (size_t)c.Cout * c.Cin * c.taps, dw, s);
+  launch_ug_bias_grad(dy, c.B, c.Cout, c.Ho * c.Wo, db, s);
+}

@@ -431,4 +431,34 @@ void launch_ug_split_add(const float* src, float* d0, float* d1, int B, int C0, 
 void launch_ug_mask(float* out, size_t n, uint64_t seed, int block, float p, hipStream_t s);
 void launch_ug_header(unsigned* hdr, float p, uint64_t seed, hipStream_t s);
 
+// ---- training pass of the ratio estimators (ratio_train.hip; NCHW fp32)
+// A norm in front of a SiLU: z [B][C][H][W] and its (mean, rstd) pairs -- groups == 0: BatchNorm, mr[C][2];
+// groups > 0: GroupNorm, mr[B][groups][2].
+struct RtNorm {
+  const float* z;
+  const float* mr;
+  const float* gamma;
+  const float* beta;
+  int B, C, H, W, groups;
+};
+constexpr int RT_BN_SLICES = 16;  // batch slices of a per-channel BatchNorm reduction (partials per channel)
+// part: [C][RT_BN_SLICES][3] floats; stats (optional): [C][2] = (batch mean, unbiased batch variance)
+void launch_rt_bn_stats(const float* z, int B, int C, int HW, float* part, float* mr, float* stats, hipStream_t s);
+void launch_rt_bn_running(const float* rm, const float* rv, int C, float* mr, hipStream_t s);
+void launch_rt_norm_act(const RtNorm& a, float* out, hipStream_t s);
+void launch_rt_norm_act_pool(const RtNorm& a, float* out, unsigned char* choice, hipStream_t s);
+void launch_rt_unpool(const float* g, const unsigned char* choice, float* full, int BC, int H, int W, hipStream_t s);
+void launch_rt_choice(const unsigned char* choice, size_t n, float* out, hipStream_t s);
+// dout (gradient of silu(norm(z)), full raster) is replaced by dz; part: [C][RT_BN_SLICES][2], m12: [C][2]; training: a
+// device word, non-zero = batch statistics (their dependence on z is differentiated), zero = constants
+void launch_rt_bn_bwd(const RtNorm& a, float* dout, const unsigned* training, float* part, float* m12, float* dgamma, float* dbeta,
+                      hipStream_t s);
+void launch_rt_avgpool(const float* in, int rows, int n, float* out, hipStream_t s);
+void launch_rt_avgpool_bwd(const float* g, int rows, int n, float* din, hipStream_t s);
+void launch_rt_ln_act(const float* u, const float* gamma, const float* beta, int rows, int width, const unsigned* hdr,
+                      int block, float* mr, float* out, hipStream_t s);
+void launch_rt_ln_act_bwd(const float* u, const float* g, const float* gamma, const float* beta, int rows, int width,
+                          const unsigned* hdr, int block, const float* mr, float* du, float* pg, float* pb,
+                          hipStream_t s);
+
 }  // namespace rgfm

@@ -18,25 +18,9 @@
 #include <cstring>
 
 #include "rgfm_device.h"
+#include "train_device.h"
 
 namespace rgfm {
-
-__device__ __forceinline__ float ug_sigmoid(float v) { return 1.0f / (1.0f + expf(-v)); }
-__device__ __forceinline__ float ug_silu(float v) { return v / (1.0f + expf(-v)); }
-__device__ __forceinline__ float ug_dsilu(float v) {
-  const float s = ug_sigmoid(v);
-  return s * (1.0f + v * (1.0f - s));
-}
-
-// Dropout keep decision of element `idx` of ResBlock `block` (rgfm.h: rgfm_unet_dropout_mask).
-__host__ __device__ inline bool ug_keep(uint64_t seed, int block, uint32_t idx, float p) {
-  uint64_t z = seed + 0x9E3779B97F4A7C15ull * ((((uint64_t)(uint32_t)block) << 32 | idx) + 1ull);
-  z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9ull;
-  z = (z ^ (z >> 27)) * 0x94D049BB133111EBull;
-  z ^= z >> 31;
-  const float u = (float)(uint32_t)(z >> 40) * (1.0f / 16777216.0f);
-  return u >= p;
-}
 
 // ------------------------------------------------------------------ implicit GEMM
 // Block tile 64 (M) x 64 (N), K staged 16 at a time; four waves, one 32x32 accumulator each (same LDS layout and k
@@ -206,19 +190,6 @@ void launch_ug_reduce(const float* part, int splits, size_t n, float* out, hipSt
                      splits, n, out);
 }
 
-// 256-thread LDS tree (fixed order)
-__device__ __forceinline__ float ug_block_sum(float v, float* red) {
-  const int t = threadIdx.x;
-  __syncthreads();
-  red[t] = v;
-  __syncthreads();
-  for (int o = 128; o > 0; o >>= 1) {
-    if (t < o) red[t] += red[t + o];
-    __syncthreads();
-  }
-  return red[0];
-}
-
 // db[c] = sum over (b, pixel) of dy[b][c][pixel]; one workgroup per channel
 __global__ __launch_bounds__(256) void ug_bias_grad_kernel(const float* dy, int B, int C, int HW, float* db) {
   __shared__ float red[256];
@@ -261,11 +232,6 @@ void launch_ug_gn_stats(const float* s0, const float* s1, int C0, int C1, int B,
 }
 
 // out[b][c][p] = cat(s0, s1), optionally normalised (mr != null), SiLU'd and dropped (drop_p > 0)
-__device__ __forceinline__ void ug_drop_params(const unsigned* hdr, float& p, uint64_t& seed) {
-  p = 0.f, seed = 0;
-  if (hdr) p = __uint_as_float(hdr[0]), seed = (uint64_t)hdr[1] | ((uint64_t)hdr[2] << 32);
-}
-
 __global__ void ug_gn_act_kernel(UgAct a) {
   const int C = a.C0 + a.C1, cg = C / max(a.groups, 1);
   const size_t total = (size_t)a.B * C * a.HW;

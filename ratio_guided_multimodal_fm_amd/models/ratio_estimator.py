@@ -41,6 +41,19 @@ class RatioEstimator(nn.Module):
     def forward(self, x, y):
         return self._engine.eval(x, y, "score")
 
+    def forward_train(self, x, y):
+        """Scores [B] in the module's current mode with autograd through the HIP backward: ``loss.backward()`` fills
+        ``p.grad`` of every parameter (and ``x.grad`` / ``y.grad`` if requested).  While ``self.training``: batch
+        statistics (BatchNorm buffers updated with momentum 0.1), dropout seeded from the CUDA generator."""
+        return self._engine.forward_train(x, y)
+
+    def dropout_p(self):
+        """The one dropout probability of the score MLP (the device pass takes one p)."""
+        ps = {l.p for l in self.score_net if isinstance(l, nn.Dropout)}
+        if len(ps) != 1:
+            raise ValueError(f"the Dropout layers of score_net must share one p, got {sorted(ps)}")
+        return ps.pop()
+
     def log_ratio(self, x, y):
         if self.loss_type not in ("disc", "rulsif"):
             raise ValueError(f"Unknown loss_type: {self.loss_type}")

@@ -58,6 +58,19 @@ class RatioEstimatorMNISTSVHN(nn.Module):
         """Scores T(x, y): x [B,1,32,32], y [B,3,32,32] -> [B]."""
         return self._engine.eval(x, y, "score")
 
+    def forward_train(self, x, y):
+        """Scores [B] in the module's current mode with autograd through the HIP backward: ``loss.backward()`` fills
+        ``p.grad`` of every parameter (and ``x.grad`` / ``y.grad`` if requested).  While ``self.training``: batch
+        statistics (BatchNorm buffers updated with momentum 0.1), dropout seeded from the CUDA generator."""
+        return self._engine.forward_train(x, y)
+
+    def dropout_p(self):
+        """The one dropout probability of the score MLP (the device pass takes one p)."""
+        ps = {l.p for l in self.score_net if isinstance(l, nn.Dropout)}
+        if len(ps) != 1:
+            raise ValueError(f"the Dropout layers of score_net must share one p, got {sorted(ps)}")
+        return ps.pop()
+
     def log_ratio(self, x, y):
         """log r(x, y); raises ValueError for an unknown loss_type (reference :384-385)."""
         if self.loss_type not in ("disc", "rulsif"):
