@@ -597,11 +597,9 @@ size_t conv_mfma_lds_bytes(const ConvArgs& a) {
 
 template <int NT, int MODE>
 static int raise_lds() {
-  int rc = (int)hipFuncSetAttribute(reinterpret_cast<const void*>(&conv_mfma_kernel<NT, MODE>),
-                                    hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
+  int rc = raise_lds_limit(&conv_mfma_kernel<NT, MODE>, 160 * 1024);
   if (MODE != CONV_S2)
-    rc |= (int)hipFuncSetAttribute(reinterpret_cast<const void*>(&conv_mfma_pf_kernel<NT, MODE == CONV_S2 ? CONV_S1 : MODE>),
-                                   hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
+    rc |= raise_lds_limit(&conv_mfma_pf_kernel<NT, MODE == CONV_S2 ? CONV_S1 : MODE>, 160 * 1024);
   return rc;
 }
 
@@ -613,10 +611,8 @@ int conv_mfma_init() {
   rc |= raise_lds<2, CONV_S1>();
   rc |= raise_lds<2, CONV_S2>();
   rc |= raise_lds<2, CONV_UP2>();
-  rc |= (int)hipFuncSetAttribute(reinterpret_cast<const void*>(&conv_mfma_pf_kernel<1, CONV_T2>),
-                                 hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-  rc |= (int)hipFuncSetAttribute(reinterpret_cast<const void*>(&conv_mfma_pf_kernel<2, CONV_T2>),
-                                 hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
+  rc |= raise_lds_limit(&conv_mfma_pf_kernel<1, CONV_T2>, 160 * 1024);
+  rc |= raise_lds_limit(&conv_mfma_pf_kernel<2, CONV_T2>, 160 * 1024);
   return rc;
 }
 

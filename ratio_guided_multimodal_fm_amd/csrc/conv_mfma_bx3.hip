@@ -163,7 +163,7 @@ __global__ __launch_bounds__(512, 2) void conv_mfma_bx3w_kernel(const ConvArgs a
       for (int mt = 0; mt < 2; ++mt)
 #pragma unroll
         for (int r = 0; r < 16; ++r) {
-          const int pl = 32 * mt + (r & 3) + 8 * (r >> 2) + 4 * hp_;
+          const int pl = hx_acc_pixel(mt, r, hp_);
           const int p = 64 * seg + pl;
           const bool valid = (g.spt == 1) ? (sample_ok && p < nvalid) : (sample_ok && pl < HW);
           const unsigned pix = valid ? (unsigned)pix0 + (unsigned)((g.spt == 1) ? p : pl) : 0u;
@@ -356,60 +356,11 @@ __global__ __launch_bounds__(512, 2) void conv_mfma_bx3w_kernel(const ConvArgs a
   if (a.gn_stats0) {
     // ---- consumer-side GroupNorm: scale/shift of this block's sample(s) from the producers' partial statistics,
     // before chunk 0's prefetch registers come alive (with them the partials would spill).  Wave w owns table row
-    // w (= ga * spt + s, the slot of smask); lane = group * 8 + sub, sub strides over the group's channels; all of a
-    // lane's <= 4 x 16 partials are fetched in one round trip, reduced in fp64 without divisions in the loop:
-    //   N = sum n_p, S1 = sum n_p mean_p, S2 = sum [M2_p + n_p mean_p^2]  ->  mean = S1 / N, var = S2 / N - mean^2
+    // w (= ga * spt + s, the slot of smask), one wave per row (rgfm_device.h: gn_table_row)
     if (wave < NA * g.spt) {
       const int ga = (g.spt == 1) ? wave : (wave >> 2), sl = (g.spt == 1) ? 0 : (wave & 3);
       const int b = (ga ? tb0_[1] : tb0_[0]) + sl;
-      const TileGeom gg = a.gn_g;
-      const int cpg = cin >> 3, gi = lane >> 3, sub = lane & 7;
-      float gam[4], bet[4];
-      const bool bok = b < a.B;
-      double n = 0.0, s1 = 0.0, s2 = 0.0;
-      const int kmax = (cpg + 7) >> 3;  // channels per lane (wave-uniform)
-#pragma unroll 1
-      for (int k = 0; k < kmax; ++k) {  // one channel (16 partials) per round trip: more at once spills
-        const int c = gi * cpg + sub + 8 * k;
-        const bool have = bok && sub + 8 * k < cpg;
-        const bool first = !have || c < a.C0;  // (no k-th channel: entry 0 of the first source, never used)
-        const float* st = first ? a.gn_stats0 : a.gn_stats1;
-        const int cs = first ? a.C0 : a.C1, cc = have ? (first ? c : c - a.C0) : 0;
-        const int npt = first ? a.gn_nparts0 : gg.nparts;
-        const size_t bb = bok ? (size_t)b : 0;
-        float2 v[16];
-#pragma unroll
-        for (int p = 0; p < 16; ++p)
-          v[p] = *reinterpret_cast<const float2*>(st + ((bb * npt + (p < npt ? p : 0)) * cs + cc) * 2);
-        const float gv = a.gn_gamma[have ? c : 0], bv = a.gn_beta[have ? c : 0];
-        if (k == 0) gam[0] = gv, bet[0] = bv;
-        else if (k == 1) gam[1] = gv, bet[1] = bv;
-        else if (k == 2) gam[2] = gv, bet[2] = bv;
-        else gam[3] = gv, bet[3] = bv;
-#pragma unroll
-        for (int p = 0; p < 16; ++p) {
-          const double np = (have && p < npt) ? (double)geom_part_count(gg, p % gg.nparts) : 0.0;
-          const double mp = (double)v[p].x;
-          n += np;
-          s1 += np * mp;
-          s2 += np > 0.0 ? (double)v[p].y + np * mp * mp : 0.0;
-        }
-      }
-      n = sub_sum(n), s1 = sub_sum(s1), s2 = sub_sum(s2);
-      const double mean = n > 0.0 ? s1 / n : 0.0;
-      const double var = n > 0.0 ? s2 / n - mean * mean : 0.0;
-      const float gm = (float)mean;
-      const float rstd = (float)(1.0 / sqrt((var > 0.0 ? var : 0.0) + 1e-5));
-#pragma unroll
-      for (int k = 0; k < 4; ++k) {
-        if (sub + 8 * k < cpg) {
-          const float sc = rstd * gam[k];
-          float2 o;
-          o.x = sc;
-          o.y = bet[k] - gm * sc;
-          *reinterpret_cast<float2*>(sTab + ((size_t)wave * cin + gi * cpg + sub + 8 * k) * 2) = o;
-        }
-      }
+      gn_table_row(a, GnLane(wave, lane, 0, cin >> 3), b, b < a.B, sTab + (size_t)wave * cin * 2, 1.f);
     }
     // (visible to every wave after the barrier that opens commit(0))
   }
@@ -477,7 +428,7 @@ __global__ __launch_bounds__(512, 2) void conv_mfma_bx3w_kernel(const ConvArgs a
     for (int mt = 0; mt < 2; ++mt)
 #pragma unroll
       for (int r = 0; r < 16; ++r) {
-        const int pl = 32 * mt + (r & 3) + 8 * (r >> 2) + 4 * h;
+        const int pl = hx_acc_pixel(mt, r, h);
         const int p = 64 * seg + pl;
         const bool valid = FULL || ((g.spt == 1) ? (sample_ok && p < nvalid) : (sample_ok && pl < HW));
         if (!FULL && valid) vmask[mt] |= 1u << r;
@@ -571,7 +522,7 @@ __device__ __forceinline__ void split1(float v, unsigned short& h, unsigned shor
 }
 
 // [Cout][Cin][taps] fp32 -> [Cout/nb][Cin/16][taps][nb][3][16] bf16, nb = channels of one workgroup
-// (bx3_block_channels): each [taps][nb] slab is the byte image of the kernel's LDS weight tile
+// (conv_block_channels): each [taps][nb] slab is the byte image of the kernel's LDS weight tile
 __global__ void pack_conv_bx3_kernel(const float* w, unsigned short* out, int Cout, int Cin, int taps, int nb) {
   const size_t total = (size_t)Cout * Cin * taps;
   for (size_t i = blockIdx.x * (size_t)blockDim.x + threadIdx.x; i < total; i += (size_t)gridDim.x * blockDim.x) {
@@ -654,25 +605,18 @@ __global__ void pack_conv_bx3_s2_kernel(const float* w, unsigned short* out, int
   }
 }
 
-// channels one workgroup covers: 128 when Cout % 128 == 0 (two 64-channel groups), else 64 or 32
-int bx3_block_channels(int Cout) { return Cout % 128 == 0 ? 128 : (Cout % 64 == 0 ? 64 : 32); }
-
 void launch_pack_conv_bx3(const float* w, void* out, int Cout, int Cin, int taps, hipStream_t s) {
   hipLaunchKernelGGL(pack_conv_bx3_kernel, dim3(256), dim3(256), 0, s, w, (unsigned short*)out, Cout, Cin, taps,
-                     bx3_block_channels(Cout));
+                     conv_block_channels(Cout));
 }
 void launch_pack_conv_bx3_s2(const float* w, void* out, int Cout, int Cin, hipStream_t s) {
   hipLaunchKernelGGL(pack_conv_bx3_s2_kernel, dim3(256), dim3(256), 0, s, w, (unsigned short*)out, Cout, Cin,
-                     bx3_block_channels(Cout));
+                     conv_block_channels(Cout));
 }
 void launch_pack_deconv_bx3(const float* w, void* out, int Cin, int Cout, hipStream_t s) {
   hipLaunchKernelGGL(pack_deconv_bx3_kernel, dim3(256), dim3(256), 0, s, w, (unsigned short*)out, Cin, Cout,
-                     bx3_block_channels(Cout));
+                     conv_block_channels(Cout));
 }
-
-// halo of one tile in this kernel: (th + 2) x (W + 2) plane pixels per sample in every mode (ConvArgs::halo_px is
-// the fp32 kernel's, which differs for stride 2)
-static int bx3_halo(const ConvArgs& a) { return a.g.spt * (a.g.th + 2) * (a.g.W + 2); }
 
 static bool bx3_pairn(const ConvArgs& a) {
   const int nt = (a.Cout % 64 == 0) ? 2 : 1;
@@ -682,7 +626,7 @@ static size_t bx3w_lds_bytes(const ConvArgs& a, int mode) {
   const int nt = (a.Cout % 64 == 0) ? 2 : 1;
   const int ntaps = (mode == CONV_T2 || mode == CONV_S2) ? 4 : 9;
   const bool pn = bx3_pairn(a);
-  size_t bytes = (size_t)((pn ? 1 : 2) * bx3_halo(a) + ntaps * 32 * nt * (pn ? 2 : 1)) * RW + (256 + 128) * sizeof(float);
+  size_t bytes = (size_t)((pn ? 1 : 2) * conv_halo_px(a) + ntaps * 32 * nt * (pn ? 2 : 1)) * RW + (256 + 128) * sizeof(float);
   if (a.gn_stats0) bytes += (size_t)(pn ? 1 : 2) * a.g.spt * (a.C0 + a.C1) * 2 * sizeof(float);  // scale/shift table
   return bytes;
 }
@@ -695,7 +639,7 @@ bool conv_bx3_supported(const ConvArgs& a, int mode) {
   if (px_in >= (1u << 24) || px_out >= (1u << 24) || (px_in > px_out ? px_in : px_out) * cmax >= (1ull << 32)) return false;
   if (mode == CONV_S2 && getenv("RGFM_S2_F32")) return false;  // A/B switch: stride-2 convs on the fp32 kernel
   if (mode == CONV_S2 && (a.Hin != 2 * a.g.H || a.Win != 2 * a.g.W || a.C1 != 0 || a.res_mode != 0)) return false;
-  return bx3_halo(a) <= 448 && bx3w_lds_bytes(a, mode) <= 160 * 1024;
+  return conv_halo_px(a) <= 448 && bx3w_lds_bytes(a, mode) <= 160 * 1024;
 }
 
 bool conv_bx3_gn_supported(const ConvArgs& a, int mode) {
@@ -712,8 +656,7 @@ int conv_fin_expected(const ConvArgs& a, int mode) {
 
 int conv_bx3_init() {
   int rc = 0;
-#define RAISEW(NTV, M, P) rc |= (int)hipFuncSetAttribute(reinterpret_cast<const void*>(&conv_mfma_bx3w_kernel<NTV, M, P>), \
-                                                        hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024)
+#define RAISEW(NTV, M, P) rc |= raise_lds_limit(&conv_mfma_bx3w_kernel<NTV, M, P>, 160 * 1024)
   RAISEW(1, CONV_S1, false); RAISEW(1, CONV_UP2, false); RAISEW(1, CONV_T2, false);
   RAISEW(2, CONV_S1, false); RAISEW(2, CONV_UP2, false); RAISEW(2, CONV_T2, false);
   RAISEW(2, CONV_S1, true); RAISEW(2, CONV_UP2, true); RAISEW(2, CONV_T2, true);
@@ -724,7 +667,7 @@ int conv_bx3_init() {
 
 void launch_conv_bx3(const ConvArgs& a_in, int mode, hipStream_t s) {
   ConvArgs a = a_in;
-  a.halo_px = bx3_halo(a_in);
+  a.halo_px = conv_halo_px(a_in);
   const int nt = (a.Cout % 64 == 0) ? 2 : 1;
   {
     const int tiles = geom_num_tiles(a.g, a.B);

@@ -48,89 +48,15 @@ __global__ __launch_bounds__(512, 1) void conv_mfma_hx2c_kernel(const ConvArgs a
   const int b0 = tile * SPT;
 
   // ---- consumer-side GroupNorm: scale/shift of the tile's four samples from the producers' partial statistics
-  // (as conv_mfma_hx2q_kernel: rows side by side on the waves, two waves per row)
-  {
-    const int gn_cpg = cin >> 3;
-    int gn_wsh = 1;  // log2 (waves per row): 8 waves / 4 rows
-    {
-      const int need = gn_cpg <= 8 ? 0 : (gn_cpg <= 16 ? 1 : 2);
-      gn_wsh = gn_wsh < need ? gn_wsh : need;
-    }
-    const int gn_row = wave >> gn_wsh, gn_part = wave & ((1 << gn_wsh) - 1);
-    const int gn_b = b0 + gn_row;
-    if (gn_row < SPT && gn_b < a.B) {
-      const int gn_lpg = 8 << gn_wsh;
-      const int gn_gl = lane >> (3 + gn_wsh), gn_sub = lane & (gn_lpg - 1);
-      const int gn_gi = gn_part * (8 >> gn_wsh) + gn_gl;
-      const int gn_kmax = (gn_cpg + gn_lpg - 1) / gn_lpg;
-      float gam[4], bet[4];
-      double n = 0.0, s1 = 0.0, s2 = 0.0;
-#pragma unroll 1
-      for (int k = 0; k < gn_kmax; ++k) {
-        const int c = gn_gi * gn_cpg + gn_sub + gn_lpg * k;
-        const bool have = gn_sub + gn_lpg * k < gn_cpg;
-        const bool first = !have || c < a.C0;
-        const float* st = first ? a.gn_stats0 : a.gn_stats1;
-        const int cs = first ? a.C0 : a.C1, cc = have ? (first ? c : c - a.C0) : 0;
-        const int npt = first ? a.gn_nparts0 : a.gn_g.nparts;
-        float2 gn_v[16];
-#pragma unroll
-        for (int p = 0; p < 16; ++p)
-          gn_v[p] = *reinterpret_cast<const float2*>(st + (((size_t)gn_b * npt + (p < npt ? p : 0)) * cs + cc) * 2);
-        const float gv = a.gn_gamma[have ? c : 0], bv = a.gn_beta[have ? c : 0];
-        if (k == 0) gam[0] = gv, bet[0] = bv;
-        else if (k == 1) gam[1] = gv, bet[1] = bv;
-        else if (k == 2) gam[2] = gv, bet[2] = bv;
-        else gam[3] = gv, bet[3] = bv;
-#pragma unroll
-        for (int p = 0; p < 16; ++p) {
-          const double np = (have && p < npt) ? (double)geom_part_count(a.gn_g, p % a.gn_g.nparts) : 0.0;
-          const double mp = (double)gn_v[p].x;
-          n += np;
-          s1 += np * mp;
-          s2 += np > 0.0 ? (double)gn_v[p].y + np * mp * mp : 0.0;
-        }
-      }
-      for (int o = 1; o < gn_lpg; o <<= 1) n += __shfl_xor(n, o), s1 += __shfl_xor(s1, o), s2 += __shfl_xor(s2, o);
-      const double mean = n > 0.0 ? s1 / n : 0.0;
-      const double var = n > 0.0 ? s2 / n - mean * mean : 0.0;
-      const float gm = (float)mean;
-      const float rstd = (float)(1.0 / sqrt((var > 0.0 ? var : 0.0) + 1e-5));
-#pragma unroll
-      for (int k = 0; k < 4; ++k) {
-        if (gn_sub + gn_lpg * k < gn_cpg) {
-          const float sc = rstd * gam[k];
-          float2 o;
-          o.x = HX_SA * sc;
-          o.y = HX_SA * (bet[k] - gm * sc);
-          *reinterpret_cast<float2*>(sTab + ((size_t)gn_row * cin + gn_gi * gn_cpg + gn_sub + gn_lpg * k) * 2) = o;
-        }
-      }
-    }
-    for (int i = tid; i < 2 * cin; i += NTHR) sTab[SPT * cin * 2 + i] = 0.f;  // the all-zero row of the padding items
-    // (rows of samples past the batch are never read: their items are invalid and take the zero row)
-  }
+  // (rows side by side on the waves, two waves per row: 8 waves / 4 rows)
+  hx_gn_table_rows(a, SPT, 1, b0, sTab, cin);
+  hx_tab_zero_row(sTab, SPT, cin, NTHR);
 
   const int nmain = cin / KC;
   const int nskip = SKIP ? (a.R0 + a.R1) / KC : 0;
   const int ntot = nmain + nskip;
-  typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
-  if (tid < ntot) {  // chunk descriptors: which tensor a chunk comes from (input / concat partner / 1x1-skip sources)
-    const bool skip = tid >= nmain;
-    const int c = (skip ? tid - nmain : tid) * KC;
-    const float* src;
-    int cs, cc;
-    if (!skip) {
-      if (c < a.C0) src = a.in0, cs = a.C0, cc = c;
-      else src = a.in1, cs = a.C1, cc = c - a.C0;
-    } else {
-      if (c < a.R0) src = a.res0, cs = a.R0, cc = c;
-      else src = a.res1, cs = a.R1, cc = c - a.R0;
-    }
-    const unsigned long long pv = reinterpret_cast<unsigned long long>(src + cc);
-    const u32x4 d = {(unsigned)pv, (unsigned)(pv >> 32), (unsigned)cs, 0u};
-    *reinterpret_cast<u32x4*>(sDesc + tid * 16) = d;
-  }
+  typedef hx_u32x4 u32x4;
+  hx_store_chunk_desc(a, sDesc, nmain, ntot);
 
   // ---- per-item decode, once: source PIXEL index, LDS destination, table row (the sample inside the tile; SPT: invalid)
   const int q4 = tid & 3;
@@ -254,56 +180,16 @@ __global__ __launch_bounds__(512, 1) void conv_mfma_hx2c_kernel(const ConvArgs a
   const float qmain = a.hq[0];
   const int sample = b0 + seg;  // this wave's sample
   const int ch0 = cb * CB + grp * 32 + l31;
-  f32x16 acc[2];
-  {
-    float v = a.bias[ch0];
-    if (SKIP) v += a.skip_bias[ch0];
-    if (a.temb) v += a.temb[((size_t)(a.temb_per_row ? (sample < a.B ? sample : 0) : 0) + (a.step_ptr ? (size_t)*a.step_ptr : 0)) * a.temb_stride + ch0];
-    const float add0 = v * qmain;
-    if (!SKIP && a.res_mode == 1) {
-      const size_t pixr = (size_t)(sample < a.B ? sample : 0) * (W * W);
-#pragma unroll
-      for (int mt = 0; mt < 2; ++mt)
-#pragma unroll
-        for (int r = 0; r < 16; ++r) {
-          const int p = 32 * mt + (r & 3) + 8 * (r >> 2) + 4 * hp;
-          acc[mt][r] = a.res0[(pixr + p) * a.Cout + ch0];
-        }
-#pragma unroll
-      for (int mt = 0; mt < 2; ++mt)
-#pragma unroll
-        for (int r = 0; r < 16; ++r) acc[mt][r] = fmaf(acc[mt][r], qmain, add0);
-    } else {
-#pragma unroll
-      for (int mt = 0; mt < 2; ++mt)
-#pragma unroll
-        for (int r = 0; r < 16; ++r) acc[mt][r] = add0;
-    }
-  }
+  f32x16 acc[2][1];
+  hx_acc_init<SKIP>(acc, a, sample, (size_t)(sample < a.B ? sample : 0) * (W * W), ch0, hp, qmain);
 
   // one tap: 6 fragment reads, 6 MFMAs (a_l w_h, a_h w_l, a_h w_h per tile).  The reads of tap t + 1 are issued BEFORE the
   // MFMAs of tap t (two fragment sets, pinned with sched_barrier): left to itself hipcc emits read x 6, wait, MFMA x 6
   // per tap, and every tap of a wave then waits out an LDS round trip in front of its MFMAs (with two waves per SIMD
   // that was half of a chunk's time: 3.0 us per chunk against 1.45 us of matrix work)
-  struct Frag {
-    f16x8 a[2][2], b[2];
-  };
-  auto ldf = [&](Frag& f, const char* sArow, const char* sBt, int o0) {
-    const int o1 = o0 ^ 32;
-    f.a[0][0] = *reinterpret_cast<const f16x8*>(sArow + o0);
-    f.a[0][1] = *reinterpret_cast<const f16x8*>(sArow + o1);
-    f.a[1][0] = *reinterpret_cast<const f16x8*>(sArow + o0 + MT_OFF);
-    f.a[1][1] = *reinterpret_cast<const f16x8*>(sArow + o1 + MT_OFF);
-    f.b[0] = *reinterpret_cast<const f16x8*>(sBt + bofs);
-    f.b[1] = *reinterpret_cast<const f16x8*>(sBt + (bofs ^ 32));
-  };
-  auto mma = [&](const Frag& f) {
-    constexpr int PA[3] = {1, 0, 0}, PB[3] = {0, 1, 0};
-#pragma unroll
-    for (int q = 0; q < 3; ++q)
-#pragma unroll
-      for (int mt = 0; mt < 2; ++mt) acc[mt] = __builtin_amdgcn_mfma_f32_32x32x16_f16(f.a[mt][PA[q]], f.b[PB[q]], acc[mt], 0, 0, 0);
-  };
+  typedef HxFrag<> Frag;
+  auto ldf = [&](Frag& f, const char* sArow, const char* sBt, int o0) { f.load(sArow, o0, MT_OFF, sBt, bofs); };
+  auto mma = [&](const Frag& f) { f.mma(acc); };
 
   // ---- K loop: one barrier per position.  Behind it the next position is transformed + stored (the other halo buffer),
   // its weights requested (the other weight buffer), the position after that fetched, and this position multiplied
@@ -355,7 +241,7 @@ __global__ __launch_bounds__(512, 1) void conv_mfma_hx2c_kernel(const ConvArgs a
         if (SKIP && c == nmain - 1) {  // the 1x1 skip weights carry their own scale: q_main -> q_skip
           const float rs = a.hq_skip[0] * a.hq[1];
 #pragma unroll
-          for (int mt = 0; mt < 2; ++mt) acc[mt] = acc[mt] * rs;
+          for (int mt = 0; mt < 2; ++mt) acc[mt][0] = acc[mt][0] * rs;
         }
       } else {
         Frag f;
@@ -384,44 +270,22 @@ __global__ __launch_bounds__(512, 1) void conv_mfma_hx2c_kernel(const ConvArgs a
   {
     const float qinv = SKIP ? a.hq_skip[1] : a.hq[1];
 #pragma unroll
-    for (int mt = 0; mt < 2; ++mt) acc[mt] = acc[mt] * qinv;
+    for (int mt = 0; mt < 2; ++mt) acc[mt][0] = acc[mt][0] * qinv;
   }
   if (sample >= a.B) return;  // (wave-uniform; no barrier follows)
-  if (a.small_check && a.range_flag) {  // (ConvArgs::small_check: the output's low range)
-    float m = 0.f;
-#pragma unroll
-    for (int mt = 0; mt < 2; ++mt)
-#pragma unroll
-      for (int r = 0; r < 16; r += 2) m = hx_absmax3(acc[mt][r], acc[mt][r + 1], m);
-    hx_small_flag(a.range_flag, m);
-  }
+  if (a.small_check && a.range_flag) hx_small_scan(a.range_flag, acc);  // (ConvArgs::small_check: the output's low range)
   const size_t pix0 = (size_t)sample * (W * W);
   if (a.out) {
 #pragma unroll
     for (int mt = 0; mt < 2; ++mt)
 #pragma unroll
       for (int r = 0; r < 16; ++r) {
-        const int p = 32 * mt + (r & 3) + 8 * (r >> 2) + 4 * hp;
-        a.out[(pix0 + p) * a.Cout + ch0] = acc[mt][r];
+        a.out[(pix0 + hx_acc_pixel(mt, r, hp)) * a.Cout + ch0] = acc[mt][0][r];
       }
   }
   if (a.stats_out || a.pout) {
-    float s = 0.f;
-#pragma unroll
-    for (int mt = 0; mt < 2; ++mt)
-#pragma unroll
-      for (int r = 0; r < 16; ++r) s += acc[mt][r];
-    s += __shfl_xor(s, 32);
-    const float mean = s / 64.f;
-    float m2 = 0.f;
-#pragma unroll
-    for (int mt = 0; mt < 2; ++mt)
-#pragma unroll
-      for (int r = 0; r < 16; ++r) {
-        const float d = acc[mt][r] - mean;
-        m2 += d * d;
-      }
-    m2 += __shfl_xor(m2, 32);
+    float mean, m2;
+    hx_stats64(acc, 0, mean, m2);
     if (a.stats_out && hp == 0) store_stats(a, a.stats_out + ((size_t)sample * a.g.nparts * a.Cout + ch0) * 2, mean, m2);
     if (a.pout) {
       // P format for the norm that consumes this output (ConvArgs::pout): a wave holds a whole sample x 32 channels, i.e.
@@ -430,7 +294,7 @@ __global__ __launch_bounds__(512, 1) void conv_mfma_hx2c_kernel(const ConvArgs a
       hx_group_affine(mean, m2, 64.f, a.Cout >> 3, a.pn_gamma[ch0], a.pn_beta[ch0], sc, sh);
       const unsigned pstride = (unsigned)a.Cout * 4u;
       char* const rec0 = reinterpret_cast<char*>(a.pout) + pix0 * pstride + (size_t)(ch0 >> 4) * 64;
-      const float pm = hx_p_emit(acc[0], acc[1], sc, sh, rec0, pstride, l31, hp);
+      const float pm = hx_p_emit(acc[0][0], acc[1][0], sc, sh, rec0, pstride, l31, hp);
       if (!(pm < HX_BIG)) atomicOr(a.range_flag, 1u);
     }
   }
@@ -467,8 +331,8 @@ bool conv_hx2c_supported(const ConvArgs& a, int mode) {
 
 int conv_hx2c_init() {
   int rc = 0;
-  rc |= (int)hipFuncSetAttribute(reinterpret_cast<const void*>(&conv_mfma_hx2c_kernel<false>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-  rc |= (int)hipFuncSetAttribute(reinterpret_cast<const void*>(&conv_mfma_hx2c_kernel<true>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
+  rc |= raise_lds_limit(&conv_mfma_hx2c_kernel<false>, 160 * 1024);
+  rc |= raise_lds_limit(&conv_mfma_hx2c_kernel<true>, 160 * 1024);
   return rc;
 }
 

@@ -186,52 +186,12 @@ __global__ __launch_bounds__(512, 1) void conv_mfma_hx2d_kernel(const ConvArgs a
   const int part = SPT == 4 ? 0 : seg;             // ... and its statistics part / 64-pixel segment of the sample
   const int ch0 = cb * CB + grp * 32 + l31;
   const size_t pix0 = (size_t)sample * (H * W) + (SPT == 4 ? 0 : seg * 64);
-  f32x16 acc[2];
-  {
-    float v = a.bias[ch0];
-    if (SKIP) v += a.skip_bias[ch0];
-    if (a.temb) v += a.temb[((size_t)(a.temb_per_row ? (sample < a.B ? sample : 0) : 0) + (a.step_ptr ? (size_t)*a.step_ptr : 0)) * a.temb_stride + ch0];
-    const float add0 = v * qmain;
-    if (!SKIP && a.res_mode == 1) {
-      const size_t pixr = sample < a.B ? pix0 : 0;
-#pragma unroll
-      for (int mt = 0; mt < 2; ++mt)
-#pragma unroll
-        for (int r = 0; r < 16; ++r) {
-          const int p = 32 * mt + (r & 3) + 8 * (r >> 2) + 4 * hp;
-          acc[mt][r] = a.res0[(pixr + p) * a.Cout + ch0];
-        }
-#pragma unroll
-      for (int mt = 0; mt < 2; ++mt)
-#pragma unroll
-        for (int r = 0; r < 16; ++r) acc[mt][r] = fmaf(acc[mt][r], qmain, add0);
-    } else {
-#pragma unroll
-      for (int mt = 0; mt < 2; ++mt)
-#pragma unroll
-        for (int r = 0; r < 16; ++r) acc[mt][r] = add0;
-    }
-  }
+  f32x16 acc[2][1];
+  hx_acc_init<SKIP>(acc, a, sample, sample < a.B ? pix0 : 0, ch0, hp, qmain);
 
-  struct Frag {
-    f16x8 a[2][2], b[2];
-  };
-  auto ldf = [&](Frag& f, const char* sArow, const char* sBt, int o0) {
-    const int o1 = o0 ^ 32;
-    f.a[0][0] = *reinterpret_cast<const f16x8*>(sArow + o0);
-    f.a[0][1] = *reinterpret_cast<const f16x8*>(sArow + o1);
-    f.a[1][0] = *reinterpret_cast<const f16x8*>(sArow + o0 + MT_OFF);
-    f.a[1][1] = *reinterpret_cast<const f16x8*>(sArow + o1 + MT_OFF);
-    f.b[0] = *reinterpret_cast<const f16x8*>(sBt + bofs);
-    f.b[1] = *reinterpret_cast<const f16x8*>(sBt + (bofs ^ 32));
-  };
-  auto mma = [&](const Frag& f) {
-    constexpr int PA[3] = {1, 0, 0}, PB[3] = {0, 1, 0};
-#pragma unroll
-    for (int q = 0; q < 3; ++q)
-#pragma unroll
-      for (int mt = 0; mt < 2; ++mt) acc[mt] = __builtin_amdgcn_mfma_f32_32x32x16_f16(f.a[mt][PA[q]], f.b[PB[q]], acc[mt], 0, 0, 0);
-  };
+  typedef HxFrag<> Frag;
+  auto ldf = [&](Frag& f, const char* sArow, const char* sBt, int o0) { f.load(sArow, o0, MT_OFF, sBt, bofs); };
+  auto mma = [&](const Frag& f) { f.mma(acc); };
 
   // ---- K loop: one barrier per position.  Every DMA this wave has in flight at the top of iteration c belongs to
   // position c (issued one iteration earlier), so the wait is vmcnt(0) (SKIP: the register fetches of later skip chunks,
@@ -283,7 +243,7 @@ __global__ __launch_bounds__(512, 1) void conv_mfma_hx2d_kernel(const ConvArgs a
       if (SKIP && c == nmain - 1) {  // the 1x1 skip weights carry their own scale: q_main -> q_skip
         const float rs = a.hq_skip[0] * a.hq[1];
 #pragma unroll
-        for (int mt = 0; mt < 2; ++mt) acc[mt] = acc[mt] * rs;
+        for (int mt = 0; mt < 2; ++mt) acc[mt][0] = acc[mt][0] * rs;
       }
     } else {
       if (nxt) wdma(c + 1);
@@ -312,45 +272,23 @@ __global__ __launch_bounds__(512, 1) void conv_mfma_hx2d_kernel(const ConvArgs a
   }
   if (SKIP && !(hmax < HX_BIG)) atomicOr(a.range_flag, 1u);  // (rare) plane h of a raw skip source would be >= 32768 (or inf)
 
-  // ---- epilogue (conv_mfma_hx2c_kernel's): a wave's 64 pixels are one whole sample (W = 8) or four rows of one (W = 16)
+  // ---- epilogue (conv_hx2_common.h: hx_small_scan, hx_stats64): a wave's 64 pixels are one whole sample (W = 8) or four rows of one (W = 16)
   {
     const float qinv = SKIP ? a.hq_skip[1] : a.hq[1];
 #pragma unroll
-    for (int mt = 0; mt < 2; ++mt) acc[mt] = acc[mt] * qinv;
+    for (int mt = 0; mt < 2; ++mt) acc[mt][0] = acc[mt][0] * qinv;
   }
   if (sample >= a.B) return;  // (wave-uniform; no barrier follows)
-  if (a.small_check && a.range_flag) {
-    float m = 0.f;
-#pragma unroll
-    for (int mt = 0; mt < 2; ++mt)
-#pragma unroll
-      for (int r = 0; r < 16; r += 2) m = hx_absmax3(acc[mt][r], acc[mt][r + 1], m);
-    hx_small_flag(a.range_flag, m);
-  }
+  if (a.small_check && a.range_flag) hx_small_scan(a.range_flag, acc);
 #pragma unroll
   for (int mt = 0; mt < 2; ++mt)
 #pragma unroll
     for (int r = 0; r < 16; ++r) {
-      const int p = 32 * mt + (r & 3) + 8 * (r >> 2) + 4 * hp;
-      a.out[(pix0 + p) * a.Cout + ch0] = acc[mt][r];
+      a.out[(pix0 + hx_acc_pixel(mt, r, hp)) * a.Cout + ch0] = acc[mt][0][r];
     }
   if (a.stats_out) {
-    float s = 0.f;
-#pragma unroll
-    for (int mt = 0; mt < 2; ++mt)
-#pragma unroll
-      for (int r = 0; r < 16; ++r) s += acc[mt][r];
-    s += __shfl_xor(s, 32);
-    const float mean = s / 64.f;
-    float m2 = 0.f;
-#pragma unroll
-    for (int mt = 0; mt < 2; ++mt)
-#pragma unroll
-      for (int r = 0; r < 16; ++r) {
-        const float d = acc[mt][r] - mean;
-        m2 += d * d;
-      }
-    m2 += __shfl_xor(m2, 32);
+    float mean, m2;
+    hx_stats64(acc, 0, mean, m2);
     if (hp == 0) store_stats(a, a.stats_out + (((size_t)sample * a.g.nparts + part) * a.Cout + ch0) * 2, mean, m2);
   }
 }
@@ -525,59 +463,11 @@ __global__ __launch_bounds__(256, 2) void conv_mfma_hx2d4_kernel(const ConvArgs 
   const int ch0 = cb * CB + l31;  // (+ 32 nt)
   const size_t pix0 = (size_t)sample * (H * W) + (SPT == 4 ? 0 : seg * 64);
   f32x16 acc[2][2];
-#pragma unroll
-  for (int nt = 0; nt < 2; ++nt) {
-    const int ch = ch0 + 32 * nt;
-    float v = a.bias[ch];
-    if (SKIP) v += a.skip_bias[ch];
-    if (a.temb) v += a.temb[((size_t)(a.temb_per_row ? (sample < a.B ? sample : 0) : 0) + (a.step_ptr ? (size_t)*a.step_ptr : 0)) * a.temb_stride + ch];
-    const float add0 = v * qmain;
-    if (!SKIP && a.res_mode == 1) {
-      const size_t pixr = sample < a.B ? pix0 : 0;
-#pragma unroll
-      for (int mt = 0; mt < 2; ++mt)
-#pragma unroll
-        for (int r = 0; r < 16; ++r) {
-          const int p = 32 * mt + (r & 3) + 8 * (r >> 2) + 4 * hp;
-          acc[mt][nt][r] = a.res0[(pixr + p) * a.Cout + ch];
-        }
-#pragma unroll
-      for (int mt = 0; mt < 2; ++mt)
-#pragma unroll
-        for (int r = 0; r < 16; ++r) acc[mt][nt][r] = fmaf(acc[mt][nt][r], qmain, add0);
-    } else {
-#pragma unroll
-      for (int mt = 0; mt < 2; ++mt)
-#pragma unroll
-        for (int r = 0; r < 16; ++r) acc[mt][nt][r] = add0;
-    }
-  }
+  hx_acc_init<SKIP>(acc, a, sample, sample < a.B ? pix0 : 0, ch0, hp, qmain);
 
-  struct Frag {
-    f16x8 a[2][2], b[2][2];
-  };
-  auto ldf = [&](Frag& f, const char* sArow, const char* sBt, int o0) {
-    const int o1 = o0 ^ 32;
-    f.a[0][0] = *reinterpret_cast<const f16x8*>(sArow + o0);
-    f.a[0][1] = *reinterpret_cast<const f16x8*>(sArow + o1);
-    f.a[1][0] = *reinterpret_cast<const f16x8*>(sArow + o0 + MT_OFF);
-    f.a[1][1] = *reinterpret_cast<const f16x8*>(sArow + o1 + MT_OFF);
-#pragma unroll
-    for (int nt = 0; nt < 2; ++nt) {
-      f.b[nt][0] = *reinterpret_cast<const f16x8*>(sBt + bofs[nt]);
-      f.b[nt][1] = *reinterpret_cast<const f16x8*>(sBt + (bofs[nt] ^ 32));
-    }
-  };
-  auto mma = [&](const Frag& f) {  // (a_l w_h, a_h w_l, a_h w_h per accumulator: the other kernels' product order)
-    constexpr int PA[3] = {1, 0, 0}, PB[3] = {0, 1, 0};
-#pragma unroll
-    for (int q = 0; q < 3; ++q)
-#pragma unroll
-      for (int mt = 0; mt < 2; ++mt)
-#pragma unroll
-        for (int nt = 0; nt < 2; ++nt)
-          acc[mt][nt] = __builtin_amdgcn_mfma_f32_32x32x16_f16(f.a[mt][PA[q]], f.b[nt][PB[q]], acc[mt][nt], 0, 0, 0);
-  };
+  typedef HxFrag<2> Frag;
+  auto ldf = [&](Frag& f, const char* sArow, const char* sBt, int o0) { f.load(sArow, o0, MT_OFF, sBt, bofs); };
+  auto mma = [&](const Frag& f) { f.mma(acc); };
 
   // ---- K loop: one barrier per unit.  At the top of unit g every DMA this wave has in flight was issued during unit
   // g - 1 (unit g's weights; a share of the next chunk's halo), so the wait is vmcnt(0).  Behind the barrier: the weights
@@ -665,44 +555,20 @@ __global__ __launch_bounds__(256, 2) void conv_mfma_hx2d4_kernel(const ConvArgs 
       for (int nt = 0; nt < 2; ++nt) acc[mt][nt] = acc[mt][nt] * qinv;
   }
   if (sample >= a.B) return;  // (wave-uniform; no barrier follows)
-  if (a.small_check && a.range_flag) {
-    float m = 0.f;
-#pragma unroll
-    for (int mt = 0; mt < 2; ++mt)
-#pragma unroll
-      for (int nt = 0; nt < 2; ++nt)
-#pragma unroll
-        for (int r = 0; r < 16; r += 2) m = hx_absmax3(acc[mt][nt][r], acc[mt][nt][r + 1], m);
-    hx_small_flag(a.range_flag, m);
-  }
+  if (a.small_check && a.range_flag) hx_small_scan(a.range_flag, acc);
 #pragma unroll
   for (int mt = 0; mt < 2; ++mt)
 #pragma unroll
     for (int r = 0; r < 16; ++r) {
-      const int p = 32 * mt + (r & 3) + 8 * (r >> 2) + 4 * hp;
-      float* op = a.out + (pix0 + p) * a.Cout + ch0;
+      float* op = a.out + (pix0 + hx_acc_pixel(mt, r, hp)) * a.Cout + ch0;
       op[0] = acc[mt][0][r];
       op[32] = acc[mt][1][r];
     }
   if (a.stats_out) {
 #pragma unroll
     for (int nt = 0; nt < 2; ++nt) {
-      float s = 0.f;
-#pragma unroll
-      for (int mt = 0; mt < 2; ++mt)
-#pragma unroll
-        for (int r = 0; r < 16; ++r) s += acc[mt][nt][r];
-      s += __shfl_xor(s, 32);
-      const float mean = s / 64.f;
-      float m2 = 0.f;
-#pragma unroll
-      for (int mt = 0; mt < 2; ++mt)
-#pragma unroll
-        for (int r = 0; r < 16; ++r) {
-          const float d = acc[mt][nt][r] - mean;
-          m2 += d * d;
-        }
-      m2 += __shfl_xor(m2, 32);
+      float mean, m2;
+      hx_stats64(acc, nt, mean, m2);
       if (hp == 0) store_stats(a, a.stats_out + (((size_t)sample * a.g.nparts + part) * a.Cout + ch0 + 32 * nt) * 2, mean, m2);
     }
   }
@@ -743,14 +609,14 @@ bool conv_hx2d_supported(const ConvArgs& a, int mode) {
 
 int conv_hx2d_init() {
   int rc = 0;
-  rc |= (int)hipFuncSetAttribute(reinterpret_cast<const void*>(&conv_mfma_hx2d_kernel<8, false>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-  rc |= (int)hipFuncSetAttribute(reinterpret_cast<const void*>(&conv_mfma_hx2d_kernel<8, true>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-  rc |= (int)hipFuncSetAttribute(reinterpret_cast<const void*>(&conv_mfma_hx2d_kernel<16, false>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-  rc |= (int)hipFuncSetAttribute(reinterpret_cast<const void*>(&conv_mfma_hx2d_kernel<16, true>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-  rc |= (int)hipFuncSetAttribute(reinterpret_cast<const void*>(&conv_mfma_hx2d4_kernel<8, false>), hipFuncAttributeMaxDynamicSharedMemorySize, 80 * 1024);
-  rc |= (int)hipFuncSetAttribute(reinterpret_cast<const void*>(&conv_mfma_hx2d4_kernel<8, true>), hipFuncAttributeMaxDynamicSharedMemorySize, 80 * 1024);
-  rc |= (int)hipFuncSetAttribute(reinterpret_cast<const void*>(&conv_mfma_hx2d4_kernel<16, false>), hipFuncAttributeMaxDynamicSharedMemorySize, 80 * 1024);
-  rc |= (int)hipFuncSetAttribute(reinterpret_cast<const void*>(&conv_mfma_hx2d4_kernel<16, true>), hipFuncAttributeMaxDynamicSharedMemorySize, 80 * 1024);
+  rc |= raise_lds_limit(&conv_mfma_hx2d_kernel<8, false>, 160 * 1024);
+  rc |= raise_lds_limit(&conv_mfma_hx2d_kernel<8, true>, 160 * 1024);
+  rc |= raise_lds_limit(&conv_mfma_hx2d_kernel<16, false>, 160 * 1024);
+  rc |= raise_lds_limit(&conv_mfma_hx2d_kernel<16, true>, 160 * 1024);
+  rc |= raise_lds_limit(&conv_mfma_hx2d4_kernel<8, false>, 80 * 1024);
+  rc |= raise_lds_limit(&conv_mfma_hx2d4_kernel<8, true>, 80 * 1024);
+  rc |= raise_lds_limit(&conv_mfma_hx2d4_kernel<16, false>, 80 * 1024);
+  rc |= raise_lds_limit(&conv_mfma_hx2d4_kernel<16, true>, 80 * 1024);
   return rc;
 }
 

@@ -163,46 +163,27 @@ __global__ __launch_bounds__(CFG == HX2P_FOUR_WAVES ? 256 : 512, 2) void conv_mf
   const bool sample_ok = bw < a.B;
   const size_t pix0 = (g.spt == 1) ? (size_t)b0 * HW + (size_t)row0 * W : (size_t)bw * HW;
   const float qmain = a.hq[0];
-  // ---- GroupNorm prologue, part 1: which (row, group, channel) this lane reduces, and the request for the first
-  // channel's partials -- they fly during the accumulator set-up and the item decode (part 2 is further down)
+  // ---- consumer-side GroupNorm: which (table row, group, channels) this lane reduces (rgfm_device.h: GnLane).  Up to
+  // all waves take part: the block's R = NA * spt table rows (one per sample slot) are split over the NW waves.
+  // Worked out HERE and not beside gn_table_row further down: there, the four-wave 64-channel cut doubles the scratch
+  // accesses around its prologue (tools/isa_census.py)
   constexpr int NW = NTHR / 64;
   const int gn_cin = a.C0 + a.C1;
   const int gn_rows = NA * g.spt;                       // 1, 2, 4 or 8 (<= NW)
-  const int gn_cpg = gn_cin >> 3;
   // log2 of the waves per row (all powers of two): as many as it takes to give every lane ONE channel (a round trip
   // per channel is what the time goes into), never more -- measured: with 8-channel groups the one-wave-per-row
   // form is 3-5 % faster per layer (fewer waves fetching and reducing in fp64), at 32-channel groups four waves
   // per row are 3 % faster
   int gn_wsh = (31 - __builtin_clz(NW)) - (31 - __builtin_clz(gn_rows));
   {
-    const int need = gn_cpg <= 8 ? 0 : (gn_cpg <= 16 ? 1 : (gn_cpg <= 32 ? 2 : 3));
+    const int need = gn_waves_log2(gn_cin >> 3);
     gn_wsh = gn_wsh < need ? gn_wsh : need;
   }
-  const int gn_row = wave >> gn_wsh, gn_part = wave & ((1 << gn_wsh) - 1);
+  const GnLane gn_lane(wave, lane, gn_wsh, gn_cin >> 3);
+  const int gn_row = gn_lane.row;
   const bool gn_active = gn_row < gn_rows;  // (wave-uniform: the waves past the last row sit this out)
-  const int gn_lpg = 8 << gn_wsh;                       // lanes per group = 64 / (8 / WPR)
-  const int gn_gl = lane >> (3 + gn_wsh), gn_sub = lane & (gn_lpg - 1);
-  const int gn_gi = gn_part * (8 >> gn_wsh) + gn_gl;    // group of this lane
-  const int gn_kmax = (gn_cpg + gn_lpg - 1) / gn_lpg;   // channels per lane (wave-uniform, <= 4)
   const int gn_b = ((g.spt == 1 ? gn_row : (gn_row >> 2)) ? tb0_[1] : tb0_[0]) + (g.spt == 1 ? 0 : (gn_row & 3));
   const bool gn_bok = gn_active && gn_b < a.B;
-  float2 gn_v[16];
-  float gn_gv = 0.f, gn_bv = 0.f;
-  int gn_npt = 0;
-  auto gn_fetch = [&](int k) {
-    const int c = gn_gi * gn_cpg + gn_sub + gn_lpg * k;
-    const bool have = gn_bok && gn_sub + gn_lpg * k < gn_cpg;
-    const bool first = !have || c < a.C0;  // (no k-th channel: entry 0 of the first source, never used)
-    const float* st = first ? a.gn_stats0 : a.gn_stats1;
-    const int cs = first ? a.C0 : a.C1, cc = have ? (first ? c : c - a.C0) : 0;
-    const int npt = first ? a.gn_nparts0 : a.gn_g.nparts;
-    const size_t bb = gn_bok ? (size_t)gn_b : 0;
-#pragma unroll
-    for (int p = 0; p < 16; ++p)
-      gn_v[p] = *reinterpret_cast<const float2*>(st + ((bb * npt + (p < npt ? p : 0)) * cs + cc) * 2);
-    gn_gv = a.gn_gamma[have ? c : 0], gn_bv = a.gn_beta[have ? c : 0];
-    gn_npt = npt;
-  };
   f32x16 acc[2][NT];
   // bias (+ skip bias + time embedding) and, for an identity residual, the RAW residual values go into the
   // accumulators here; they are scaled by q only after the pipeline fill (finish_acc below), so that the 64 residual
@@ -223,7 +204,7 @@ __global__ __launch_bounds__(CFG == HX2P_FOUR_WAVES ? 256 : 512, 2) void conv_mf
       for (int mt = 0; mt < 2; ++mt)
 #pragma unroll
         for (int r = 0; r < 16; ++r) {
-          const int pl = 32 * mt + (r & 3) + 8 * (r >> 2) + 4 * hp_;
+          const int pl = hx_acc_pixel(mt, r, hp_);
           const int p = 64 * seg + pl;
           const bool valid = (g.spt == 1) ? (sample_ok && p < nvalid) : (sample_ok && pl < HW);
           const unsigned pix = valid ? (unsigned)pix0 + (unsigned)((g.spt == 1) ? p : pl) : 0u;
@@ -333,7 +314,6 @@ __global__ __launch_bounds__(CFG == HX2P_FOUR_WAVES ? 256 : 512, 2) void conv_mf
   const int nitems = (NA * nA + NTHR - 1) / NTHR;  // items that exist for at least one thread (block-uniform)
 
   // raw fp32 fetch of item j of a chunk whose descriptor is d (chunk_desc)
-  typedef unsigned hx_u32x4 __attribute__((ext_vector_type(4)));
   auto chunk_desc = [&](int ch) { return *reinterpret_cast<const hx_u32x4*>(sDesc + ch * 16); };
   auto issue_a = [&](const hx_u32x4& d, int j) {
     const float* src = reinterpret_cast<const float*>(((unsigned long long)d.y << 32) | (unsigned long long)d.x);
@@ -403,51 +383,9 @@ __global__ __launch_bounds__(CFG == HX2P_FOUR_WAVES ? 256 : 512, 2) void conv_mf
     issue_b(0);
   }
 
-  if (a.gn_stats0 && gn_active) {
-    // ---- consumer-side GroupNorm: scale/shift of this block's sample(s) from the producers' partial statistics.
-    // Up to all waves take part: the block's R = NA * spt table rows (one per sample slot) are split over the NW waves,
-    // WPR = NW / R waves per row, each wave GPW = 8 / WPR of the row's 8 groups, LPG = 64 / GPW lanes per group; a lane
-    // strides over its group's channels (sub, sub + LPG, ...), fetches the <= 16 partials of a channel in one
-    // round trip (the first channel's were requested at the top of the kernel: gn_fetch(0)) and reduces
-    //   N = sum n_p, S1 = sum n_p mean_p, S2 = sum [M2_p + n_p mean_p^2]  ->  mean = S1 / N, var = S2 / N - mean^2
-    // in fp64 without divisions in the loop; an LPG-lane butterfly gives the group's sums.
-    float gam[4], bet[4];
-    double n = 0.0, s1 = 0.0, s2 = 0.0;
-#pragma unroll 1
-    for (int k = 0; k < gn_kmax; ++k) {
-      gn_fetch(k);
-      if (k == 0) gam[0] = gn_gv, bet[0] = gn_bv;
-      else if (k == 1) gam[1] = gn_gv, bet[1] = gn_bv;
-      else if (k == 2) gam[2] = gn_gv, bet[2] = gn_bv;
-      else gam[3] = gn_gv, bet[3] = gn_bv;
-      const bool have = gn_bok && gn_sub + gn_lpg * k < gn_cpg;
-      const int npt = gn_npt;
-#pragma unroll
-      for (int p = 0; p < 16; ++p) {
-        const double np = (have && p < npt) ? (double)geom_part_count(a.gn_g, p % a.gn_g.nparts) : 0.0;
-        const double mp = (double)gn_v[p].x;
-        n += np;
-        s1 += np * mp;
-        s2 += np > 0.0 ? (double)gn_v[p].y + np * mp * mp : 0.0;
-      }
-    }
-    for (int o = 1; o < gn_lpg; o <<= 1) n += __shfl_xor(n, o), s1 += __shfl_xor(s1, o), s2 += __shfl_xor(s2, o);
-    const double mean = n > 0.0 ? s1 / n : 0.0;
-    const double var = n > 0.0 ? s2 / n - mean * mean : 0.0;
-    const float gm = (float)mean;
-    const float rstd = (float)(1.0 / sqrt((var > 0.0 ? var : 0.0) + 1e-5));
-#pragma unroll
-    for (int k = 0; k < 4; ++k) {
-      if (gn_sub + gn_lpg * k < gn_cpg) {
-        const float sc = rstd * gam[k];
-        float2 o;
-        o.x = HX_SA * sc;
-        o.y = HX_SA * (bet[k] - gm * sc);
-        *reinterpret_cast<float2*>(sTab + ((size_t)gn_row * cin + gn_gi * gn_cpg + gn_sub + gn_lpg * k) * 2) = o;
-      }
-    }
-    // (visible to every wave after the barrier that opens commit(0))
-  }
+  // ---- consumer-side GroupNorm: scale/shift of this block's sample(s) from the producers' partial statistics, this
+  // wave's share of its table row (visible to every wave after the barrier below)
+  if (a.gn_stats0 && gn_active) gn_table_row(a, gn_lane, gn_b, gn_bok, sTab + (size_t)gn_row * gn_cin * 2, HX_SA);
 
   if (!a.gn_stats0 && a.ab) {
     // external scale/shift array ab[B][cin][2] (RGFM_GN=table; the ratio encoders' "SiLU on load" identity pairs):
@@ -464,24 +402,8 @@ __global__ __launch_bounds__(CFG == HX2P_FOUR_WAVES ? 256 : 512, 2) void conv_mf
       *reinterpret_cast<float2*>(sTab + (size_t)i * 2) = o;
     }
   }
-  if (has_tab)  // the all-zero row of the padding items
-    for (int i = tid; i < 2 * (a.C0 + a.C1); i += NTHR) sTab[nrows_tab * (a.C0 + a.C1) * 2 + i] = 0.f;
-  if (tid < ntot) {  // chunk descriptors: which tensor a chunk comes from (input / concat partner / 1x1-skip sources)
-    const bool skip = tid >= nmain;
-    const int c = (skip ? tid - nmain : tid) * KC;
-    const float* src;
-    int cs, cc;
-    if (!skip) {
-      if (c < a.C0) src = a.in0, cs = a.C0, cc = c;
-      else src = a.in1, cs = a.C1, cc = c - a.C0;
-    } else {
-      if (c < a.R0) src = a.res0, cs = a.R0, cc = c;
-      else src = a.res1, cs = a.R1, cc = c - a.R0;
-    }
-    const unsigned long long pv = reinterpret_cast<unsigned long long>(src + cc);
-    const hx_u32x4 d = {(unsigned)pv, (unsigned)(pv >> 32), (unsigned)cs, 0u};
-    *reinterpret_cast<hx_u32x4*>(sDesc + tid * 16) = d;
-  }
+  if (has_tab) hx_tab_zero_row(sTab, nrows_tab, a.C0 + a.C1, NTHR);
+  hx_store_chunk_desc(a, sDesc, nmain, ntot);
   __syncthreads();  // the scale/shift table and the chunk descriptors are complete
   const bool gn_on = has_tab;
   // ---- pipeline fill, part 2: halo of chunk 0 and weights of unit 0 into LDS, raw halo of chunk 1 and weights of unit 1 in registers
@@ -529,14 +451,7 @@ __global__ __launch_bounds__(CFG == HX2P_FOUR_WAVES ? 256 : 512, 2) void conv_mf
       bf[nt][1] = *reinterpret_cast<const f16x8*>(sBt + bsw[nt]);
     }
     }
-    constexpr int PA[3] = {1, 0, 0}, PB[3] = {0, 1, 0};  // a_l w_h, a_h w_l, a_h w_h
-#pragma unroll
-    for (int q = 0; q < 3; ++q)
-#pragma unroll
-      for (int mt = 0; mt < 2; ++mt)
-#pragma unroll
-        for (int nt = 0; nt < NT; ++nt)
-          acc[mt][nt] = __builtin_amdgcn_mfma_f32_32x32x16_f16(af[mt][PA[q]], bf[nt][PB[q]], acc[mt][nt], 0, 0, 0);
+    hx_mma3<NT>(acc, af, bf);
   };
   using K0 = std::integral_constant<int, 0>;
   using K1 = std::integral_constant<int, 1>;
@@ -611,14 +526,7 @@ __global__ __launch_bounds__(CFG == HX2P_FOUR_WAVES ? 256 : 512, 2) void conv_mf
     }
   };
   auto mfma_tap = [&](const f16x8 (&af)[2][2], const f16x8 (&bf)[NT][2]) {
-    constexpr int PA[3] = {1, 0, 0}, PB[3] = {0, 1, 0};  // a_l w_h, a_h w_l, a_h w_h
-#pragma unroll
-    for (int q = 0; q < 3; ++q)
-#pragma unroll
-      for (int mt = 0; mt < 2; ++mt)
-#pragma unroll
-        for (int nt = 0; nt < NT; ++nt)
-          acc[mt][nt] = __builtin_amdgcn_mfma_f32_32x32x16_f16(af[mt][PA[q]], bf[nt][PB[q]], acc[mt][nt], 0, 0, 0);
+    hx_mma3<NT>(acc, af, bf);
   };
 #define HX2P_SEG() __builtin_amdgcn_sched_barrier(0x0002 | 0x0004 | 0x0010 | 0x0400)  // VALU, SALU, VMEM, transcendentals may cross
   auto unit_fast = [&](int c, auto u_tag) {
@@ -773,21 +681,12 @@ __global__ __launch_bounds__(CFG == HX2P_FOUR_WAVES ? 256 : 512, 2) void conv_mf
     unsigned vmask[2] = {0u, 0u};
     // ConvArgs::small_check: the output's low range.  For full segments HERE, while nothing but the accumulators is live
     // (behind the stores and the statistics it costs registers: conv_mfma_hx2q.hip)
-    if (FULL && a.small_check && a.range_flag) {
-      float m = 0.f;
-#pragma unroll
-      for (int mt = 0; mt < 2; ++mt)
-#pragma unroll
-        for (int nt = 0; nt < NT; ++nt)
-#pragma unroll
-          for (int r = 0; r < 16; r += 2) m = hx_absmax3(acc[mt][nt][r], acc[mt][nt][r + 1], m);
-      hx_small_flag(a.range_flag, m);
-    }
+    if (FULL && a.small_check && a.range_flag) hx_small_scan(a.range_flag, acc);
 #pragma unroll
     for (int mt = 0; mt < 2; ++mt)
 #pragma unroll
       for (int r = 0; r < 16; ++r) {
-        const int pl = 32 * mt + (r & 3) + 8 * (r >> 2) + 4 * h;
+        const int pl = hx_acc_pixel(mt, r, h);
         const int p = 64 * seg + pl;
         const bool valid = FULL || ((g.spt == 1) ? (sample_ok && p < nvalid) : (sample_ok && pl < HW));
         if (!FULL && valid) vmask[mt] |= 1u << r;
@@ -874,22 +773,8 @@ __global__ __launch_bounds__(CFG == HX2P_FOUR_WAVES ? 256 : 512, 2) void conv_mf
       for (int nt = 0; nt < NT; ++nt) {
         const int c = n0 + nt * 32 + l31;
         gam[nt] = a.pn_gamma[c], bet[nt] = a.pn_beta[c];
-        float sm = 0.f;
-#pragma unroll
-        for (int mt = 0; mt < 2; ++mt)
-#pragma unroll
-          for (int r = 0; r < 16; ++r) sm += acc[mt][nt][r];
-        sm += __shfl_xor(sm, 32);
-        const float mean = sm / 64.f;
-        float m2 = 0.f;
-#pragma unroll
-        for (int mt = 0; mt < 2; ++mt)
-#pragma unroll
-          for (int r = 0; r < 16; ++r) {
-            const float d = acc[mt][nt][r] - mean;
-            m2 += d * d;
-          }
-        m2 += __shfl_xor(m2, 32);
+        float mean, m2;
+        hx_stats64(acc, nt, mean, m2);
         if (h == 0) {
           float2 v;
           v.x = mean, v.y = m2;
@@ -923,13 +808,12 @@ __global__ __launch_bounds__(CFG == HX2P_FOUR_WAVES ? 256 : 512, 2) void conv_mf
 }
 
 // ---------------------------------------------------------------- host side
-static int hx2p_halo(const ConvArgs& a) { return a.g.spt * (a.g.th + 2) * (a.g.W + 2); }
 static size_t hx2p_lds_bytes(const ConvArgs& a, int cfg, int mode) {
   const bool halfc = cfg == HX2P_PAIRN_HALF;
   const int nt = halfc ? 1 : ((a.Cout % 64 == 0) ? 2 : 1);
   const int na = cfg == HX2P_TWO_TILES ? 2 : 1, nbt = 32 * nt * ((cfg == HX2P_PAIRN || halfc) ? 2 : 1);
   const int tpu = mode == CONV_T2 ? 2 : 3;
-  size_t bytes = (size_t)2 * (na * hx2p_halo(a) + 1) * HRW + (size_t)2 * tpu * nbt * HRW;  // two halo buffers (+ pad record) + two weight units
+  size_t bytes = (size_t)2 * (na * conv_halo_px(a) + 1) * HRW + (size_t)2 * tpu * nbt * HRW;  // two halo buffers (+ pad record) + two weight units
   if (a.gn_stats0 || a.ab) bytes += (size_t)(na * a.g.spt + 1) * (a.C0 + a.C1) * 2 * sizeof(float);  // scale/shift table + the zero row
   bytes += (size_t)(a.C0 + a.C1 + (a.res_mode == 2 ? a.R0 + a.R1 : 0));                    // 16 bytes per 16-channel chunk: descriptors
   return bytes;
@@ -967,13 +851,12 @@ bool conv_hx2p_supported(const ConvArgs& a, int mode) {
   if (mode == CONV_T2 && (a.res_mode != 0 || a.pout)) return false;
   if (!conv_hx2_supported(a, mode)) return false;
   if (a.gn_stats0 && !conv_hx2_gn_supported(a, mode)) return false;
-  return hx2p_halo(a) <= 448 && hx2p_lds_bytes(a, hx2p_cfg(a, mode), mode) <= 160 * 1024;
+  return conv_halo_px(a) <= 448 && hx2p_lds_bytes(a, hx2p_cfg(a, mode), mode) <= 160 * 1024;
 }
 
 int conv_hx2p_init() {
   int rc = 0;
-#define RAISEP(NTV, M, P) rc |= (int)hipFuncSetAttribute(reinterpret_cast<const void*>(&conv_mfma_hx2p_kernel<NTV, M, P>), \
-                                                        hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024)
+#define RAISEP(NTV, M, P) rc |= raise_lds_limit(&conv_mfma_hx2p_kernel<NTV, M, P>, 160 * 1024)
   RAISEP(1, CONV_S1, HX2P_TWO_TILES); RAISEP(1, CONV_UP2, HX2P_TWO_TILES); RAISEP(1, CONV_T2, HX2P_TWO_TILES);
   RAISEP(2, CONV_S1, HX2P_TWO_TILES); RAISEP(2, CONV_UP2, HX2P_TWO_TILES); RAISEP(2, CONV_T2, HX2P_TWO_TILES);
   RAISEP(2, CONV_S1, HX2P_PAIRN); RAISEP(2, CONV_UP2, HX2P_PAIRN); RAISEP(2, CONV_T2, HX2P_PAIRN);
@@ -981,8 +864,7 @@ int conv_hx2p_init() {
   RAISEP(1, CONV_S1, HX2P_FOUR_WAVES); RAISEP(1, CONV_UP2, HX2P_FOUR_WAVES); RAISEP(1, CONV_T2, HX2P_FOUR_WAVES);
   RAISEP(2, CONV_S1, HX2P_FOUR_WAVES); RAISEP(2, CONV_UP2, HX2P_FOUR_WAVES); RAISEP(2, CONV_T2, HX2P_FOUR_WAVES);
 #undef RAISEP
-#define RAISEPP(NTV, P) rc |= (int)hipFuncSetAttribute(reinterpret_cast<const void*>(&conv_mfma_hx2p_kernel<NTV, CONV_S1, P, true>), \
-                                                      hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024)
+#define RAISEPP(NTV, P) rc |= raise_lds_limit(&conv_mfma_hx2p_kernel<NTV, CONV_S1, P, true>, 160 * 1024)
   RAISEPP(2, HX2P_PAIRN); RAISEPP(1, HX2P_PAIRN_HALF); RAISEPP(2, HX2P_TWO_TILES); RAISEPP(2, HX2P_FOUR_WAVES);
 #undef RAISEPP
   return rc;
@@ -990,7 +872,7 @@ int conv_hx2p_init() {
 
 void launch_conv_hx2p(const ConvArgs& a_in, int mode, hipStream_t s) {
   ConvArgs a = a_in;
-  a.halo_px = hx2p_halo(a_in);
+  a.halo_px = conv_halo_px(a_in);
   const int nt = (a.Cout % 64 == 0) ? 2 : 1;
   const int tiles = geom_num_tiles(a.g, a.B);
   const int cfg = hx2p_cfg(a, mode);

@@ -63,90 +63,20 @@ __global__ __launch_bounds__(256 * NG, (NG == 2 && NT == 1) ? 4 : 2) void conv_m
   const int bfirst = tile0 / tps, rfirst = tile0 - bfirst * tps;
 
   // ---- consumer-side GroupNorm: scale/shift of this workgroup's sample(s) from the producers' partial statistics
-  // (as conv_mfma_hx2p_kernel: one table row per sample; as many waves per row as it takes to give every lane one
-  // channel, rows side by side on the waves)
+  // (one table row per sample, rows side by side on the waves; nrows is 1, 2 or 4, and a row takes at most four waves:
+  // cin <= 256)
   {
-    const int gn_cpg = cin >> 3;
-    int gn_wsh = (NG + 1) - (31 - __builtin_clz(nrows));  // log2 (waves / rows): nrows is 1, 2 or 4
-    {
-      const int need = gn_cpg <= 8 ? 0 : (gn_cpg <= 16 ? 1 : 2);  // (cin <= 256)
-      gn_wsh = gn_wsh < need ? gn_wsh : need;
-    }
-    const int gn_row = wave >> gn_wsh, gn_part = wave & ((1 << gn_wsh) - 1);
-    const int gn_b = bfirst + gn_row;
-    if (gn_row < nrows && gn_b < a.B) {
-      const int gn_lpg = 8 << gn_wsh;
-      const int gn_gl = lane >> (3 + gn_wsh), gn_sub = lane & (gn_lpg - 1);
-      const int gn_gi = gn_part * (8 >> gn_wsh) + gn_gl;
-      const int gn_kmax = (gn_cpg + gn_lpg - 1) / gn_lpg;
-      float gam[4], bet[4];
-      double n = 0.0, s1 = 0.0, s2 = 0.0;
-#pragma unroll 1
-      for (int k = 0; k < gn_kmax; ++k) {
-        const int c = gn_gi * gn_cpg + gn_sub + gn_lpg * k;
-        const bool have = gn_sub + gn_lpg * k < gn_cpg;
-        const bool first = !have || c < a.C0;
-        const float* st = first ? a.gn_stats0 : a.gn_stats1;
-        const int cs = first ? a.C0 : a.C1, cc = have ? (first ? c : c - a.C0) : 0;
-        const int npt = first ? a.gn_nparts0 : a.gn_g.nparts;
-        float2 gn_v[16];
-#pragma unroll
-        for (int p = 0; p < 16; ++p)
-          gn_v[p] = *reinterpret_cast<const float2*>(st + (((size_t)gn_b * npt + (p < npt ? p : 0)) * cs + cc) * 2);
-        const float gv = a.gn_gamma[have ? c : 0], bv = a.gn_beta[have ? c : 0];
-        if (k == 0) gam[0] = gv, bet[0] = bv;
-        else if (k == 1) gam[1] = gv, bet[1] = bv;
-        else if (k == 2) gam[2] = gv, bet[2] = bv;
-        else gam[3] = gv, bet[3] = bv;
-#pragma unroll
-        for (int p = 0; p < 16; ++p) {
-          const double np = (have && p < npt) ? (double)geom_part_count(a.gn_g, p % a.gn_g.nparts) : 0.0;
-          const double mp = (double)gn_v[p].x;
-          n += np;
-          s1 += np * mp;
-          s2 += np > 0.0 ? (double)gn_v[p].y + np * mp * mp : 0.0;
-        }
-      }
-      for (int o = 1; o < gn_lpg; o <<= 1) n += __shfl_xor(n, o), s1 += __shfl_xor(s1, o), s2 += __shfl_xor(s2, o);
-      const double mean = n > 0.0 ? s1 / n : 0.0;
-      const double var = n > 0.0 ? s2 / n - mean * mean : 0.0;
-      const float gm = (float)mean;
-      const float rstd = (float)(1.0 / sqrt((var > 0.0 ? var : 0.0) + 1e-5));
-#pragma unroll
-      for (int k = 0; k < 4; ++k) {
-        if (gn_sub + gn_lpg * k < gn_cpg) {
-          const float sc = rstd * gam[k];
-          float2 o;
-          o.x = HX_SA * sc;
-          o.y = HX_SA * (bet[k] - gm * sc);
-          *reinterpret_cast<float2*>(sTab + ((size_t)gn_row * cin + gn_gi * gn_cpg + gn_sub + gn_lpg * k) * 2) = o;
-        }
-      }
-    }
-    for (int i = tid; i < 2 * cin; i += NTHR) sTab[nrows * cin * 2 + i] = 0.f;  // the all-zero row of the padding items
+    const int wpr = (NG + 1) - (31 - __builtin_clz(nrows));  // log2 (waves / rows)
+    hx_gn_table_rows(a, nrows, wpr < 2 ? wpr : 2, bfirst, sTab, cin);
+    hx_tab_zero_row(sTab, nrows, cin, NTHR);
   }
 
   const int nmain = cin / KC;
   const int nskip = SKIP ? (a.R0 + a.R1) / KC : 0;
   const int ntot = nmain + nskip;
   const int G = 3 * nmain + nskip;
-  typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
-  if (tid < ntot) {  // chunk descriptors: which tensor a chunk comes from (input / concat partner / 1x1-skip sources)
-    const bool skip = tid >= nmain;
-    const int c = (skip ? tid - nmain : tid) * KC;
-    const float* src;
-    int cs, cc;
-    if (!skip) {
-      if (c < a.C0) src = a.in0, cs = a.C0, cc = c;
-      else src = a.in1, cs = a.C1, cc = c - a.C0;
-    } else {
-      if (c < a.R0) src = a.res0, cs = a.R0, cc = c;
-      else src = a.res1, cs = a.R1, cc = c - a.R0;
-    }
-    const unsigned long long pv = reinterpret_cast<unsigned long long>(src + cc);
-    const u32x4 d = {(unsigned)pv, (unsigned)(pv >> 32), (unsigned)cs, 0u};
-    *reinterpret_cast<u32x4*>(sDesc + tid * 16) = d;
-  }
+  typedef hx_u32x4 u32x4;
+  hx_store_chunk_desc(a, sDesc, nmain, ntot);
 
   // ---- fragment offsets.  A: this lane's pixel 64 seg + l31 (+ 32: MT_OFF) at tap column kx, planes h / l; the four
   // 16-byte slots of a halo record are swizzled with its halo column (conv_mfma_hx2p.hip)
@@ -187,7 +117,7 @@ __global__ __launch_bounds__(256 * NG, (NG == 2 && NT == 1) ? 4 : 2) void conv_m
   }
 
   // packed weights: [channel block][chunk][tap] slabs; a workgroup of a 128-channel block takes its 64-channel half
-  // (the weights are packed in blocks of 128 / 64 / 32 channels -- hx2_block_channels; conv_hx2q_supported lets a
+  // (the weights are packed in blocks of 128 / 64 / 32 channels -- conv_block_channels; conv_hx2q_supported lets a
   // workgroup cover a whole block, or half of a 128-channel one)
   const bool nb128 = CB == 64 && (a.Cout & 127) == 0;
   const int TAPS = nb128 ? 2 * TAPB : TAPB;
@@ -342,14 +272,7 @@ __global__ __launch_bounds__(256 * NG, (NG == 2 && NT == 1) ? 4 : 2) void conv_m
       bf[nt][1] = *reinterpret_cast<const f16x8*>(sBt + (bofs ^ 32) + nt * 32 * HRW);
     }
     }
-    constexpr int PA[3] = {1, 0, 0}, PB[3] = {0, 1, 0};
-#pragma unroll
-    for (int q = 0; q < 3; ++q)
-#pragma unroll
-      for (int mt = 0; mt < 2; ++mt)
-#pragma unroll
-        for (int nt = 0; nt < NT; ++nt)
-          acc[mt][nt] = __builtin_amdgcn_mfma_f32_32x32x16_f16(af[mt][PA[q]], bf[nt][PB[q]], acc[mt][nt], 0, 0, 0);
+    hx_mma3<NT>(acc, af, bf);
   };
   auto taps3 = [&](int U) {
     const char* sArow = smq + (gc & 1) * ABYTES + U * WR * HRW;
@@ -407,7 +330,7 @@ __global__ __launch_bounds__(256 * NG, (NG == 2 && NT == 1) ? 4 : 2) void conv_m
         for (int mt = 0; mt < 2; ++mt)
 #pragma unroll
           for (int r = 0; r < 16; ++r) {
-            const int p = 64 * seg_b + 32 * mt + (r & 3) + 8 * (r >> 2) + 4 * hp_b;
+            const int p = 64 * seg_b + hx_acc_pixel(mt, r, hp_b);
             const float* rp = ka.res0 + (size_t)(__umul24((unsigned)pix0 + (unsigned)p, (unsigned)ka.Cout) + (unsigned)ch_b);
 #pragma unroll
             for (int nt = 0; nt < NT; ++nt) acc[mt][nt][r] = rp[nt * 32];
@@ -528,22 +451,13 @@ __global__ __launch_bounds__(256 * NG, (NG == 2 && NT == 1) ? 4 : 2) void conv_m
     }
     // (ConvArgs::small_check: the output's low range.  HERE, while nothing but the accumulators is live: behind the stores
     // and the statistics it cost the 128-register cut 33 more spilled registers)
-    if (ke.small_check && ke.range_flag) {
-      float m = 0.f;
-#pragma unroll
-      for (int mt = 0; mt < 2; ++mt)
-#pragma unroll
-        for (int nt = 0; nt < NT; ++nt)
-#pragma unroll
-          for (int r = 0; r < 16; r += 2) m = hx_absmax3(acc[mt][nt][r], acc[mt][nt][r + 1], m);
-      hx_small_flag(ke.range_flag, m);
-    }
+    if (ke.small_check && ke.range_flag) hx_small_scan(ke.range_flag, acc);
     // ---------------------------------------------------------------- epilogue: every pixel of the tile is valid
 #pragma unroll
     for (int mt = 0; mt < 2; ++mt)
 #pragma unroll
       for (int r = 0; r < 16; ++r) {
-        const int p = 64 * seg_e + 32 * mt + (r & 3) + 8 * (r >> 2) + 4 * hp_e;
+        const int p = 64 * seg_e + hx_acc_pixel(mt, r, hp_e);
         float* op = ke.out + (size_t)(__umul24((unsigned)pix0 + (unsigned)p, (unsigned)ke.Cout) + (unsigned)ch_e);
 #pragma unroll
         for (int nt = 0; nt < NT; ++nt) op[nt * 32] = acc[mt][nt][r];
@@ -553,22 +467,8 @@ __global__ __launch_bounds__(256 * NG, (NG == 2 && NT == 1) ? 4 : 2) void conv_m
       const int part = tr * 4 + seg_e;
 #pragma unroll
       for (int nt = 0; nt < NT; ++nt) {
-        float s = 0.f;
-#pragma unroll
-        for (int mt = 0; mt < 2; ++mt)
-#pragma unroll
-          for (int r = 0; r < 16; ++r) s += acc[mt][nt][r];
-        s += __shfl_xor(s, 32);
-        const float mean = s / 64.f;
-        float m2 = 0.f;
-#pragma unroll
-        for (int mt = 0; mt < 2; ++mt)
-#pragma unroll
-          for (int r = 0; r < 16; ++r) {
-            const float d = acc[mt][nt][r] - mean;
-            m2 += d * d;
-          }
-        m2 += __shfl_xor(m2, 32);
+        float mean, m2;
+        hx_stats64(acc, nt, mean, m2);
         if (hp_e == 0) store_stats(ke, ke.stats_out + (((size_t)tb * nparts + part) * ke.Cout + ch_e + nt * 32) * 2, mean, m2);
       }
       if (ke.fin_ab) fin_arrive(ke, tb, lane_e, nparts, false);
@@ -639,8 +539,8 @@ bool conv_hx2q_supported(const ConvArgs& a, int mode) {
   if (a.res_mode == 2 && (a.R0 + a.R1) % KC != 0) return false;
   const Hx2qCut c = hx2q_cut(a);
   if (c.nt != 1) return false;
-  // a workgroup covers one packed weight block (128 / 64 / 32 channels: hx2_block_channels) or half of a 128-channel one
-  const int nb = a.Cout % 128 == 0 ? 128 : (a.Cout % 64 == 0 ? 64 : 32);
+  // a workgroup covers one packed weight block (128 / 64 / 32 channels: conv_block_channels) or half of a 128-channel one
+  const int nb = conv_block_channels(a.Cout);
   if (a.Cout % c.cb() != 0 || !(c.cb() == nb || (c.cb() == 64 && nb == 128))) return false;
   const int tpw = hx2q_tiles_per_wg(a);
   if (hx2q_lds_bytes(a, tpw) > ((c.ng == 2 && c.nt == 2) ? 160 : 80) * 1024) return false;
@@ -671,9 +571,7 @@ bool conv_hx2q_supported(const ConvArgs& a, int mode) {
 
 int conv_hx2q_init() {
   int rc = 0;
-#define RAISEQ(WL, SK, G, T)                                                                               \
-  rc |= (int)hipFuncSetAttribute(reinterpret_cast<const void*>(&conv_mfma_hx2q_kernel<WL, SK, G, T>),     \
-                                 hipFuncAttributeMaxDynamicSharedMemorySize, ((G) == 2 && (T) == 2 ? 160 : 80) * 1024);
+#define RAISEQ(WL, SK, G, T) rc |= raise_lds_limit(&conv_mfma_hx2q_kernel<WL, SK, G, T>, ((G) == 2 && (T) == 2 ? 160 : 80) * 1024);
   HX2Q_FOR_ALL(RAISEQ)
 #undef RAISEQ
   return rc;

@@ -136,13 +136,13 @@ __global__ __launch_bounds__(256 * NG, 1) void conv_mfma_hx2s_kernel(const ConvA
   // ---- accumulators: bias, scaled by q (they hold q x the true sums)
   const float qmain = a.hq[0];
   const int ch0 = cb * CB + grp * 32 + l31;  // this lane's output channel
-  f32x16 acc[2];
+  f32x16 acc[2][1];
   {
     const float add0 = a.bias[ch0] * qmain;
 #pragma unroll
     for (int mt = 0; mt < 2; ++mt)
 #pragma unroll
-      for (int r = 0; r < 16; ++r) acc[mt][r] = add0;
+      for (int r = 0; r < 16; ++r) acc[mt][0][r] = add0;
   }
 
   // one tap: kernel row KY, column KX -> plane (KY != 1, KX != 1) at plane row r + (KY != 0), column x + (KX != 0)
@@ -151,19 +151,9 @@ __global__ __launch_bounds__(256 * NG, 1) void conv_mfma_hx2s_kernel(const ConvA
     constexpr int P = (KY != 1 ? 2 : 0) + (KX != 1 ? 1 : 0), DR = KY != 0 ? 1 : 0, DC = KX != 0 ? 1 : 0;
     const char* sAp = sA + (P * SPT * PREC + DR * PW) * HRW;
     const char* sBt = sBc + (KY * 3 + KX) * TAPB;
-    const int o0 = aofs[DC], o1 = o0 ^ 32;
-    f16x8 af[2][2], bf[2];
-    af[0][0] = *reinterpret_cast<const f16x8*>(sAp + o0);
-    af[0][1] = *reinterpret_cast<const f16x8*>(sAp + o1);
-    af[1][0] = *reinterpret_cast<const f16x8*>(sAp + o0 + MT_OFF);
-    af[1][1] = *reinterpret_cast<const f16x8*>(sAp + o1 + MT_OFF);
-    bf[0] = *reinterpret_cast<const f16x8*>(sBt + bofs);
-    bf[1] = *reinterpret_cast<const f16x8*>(sBt + (bofs ^ 32));
-    constexpr int PA[3] = {1, 0, 0}, PB[3] = {0, 1, 0};  // a_l w_h, a_h w_l, a_h w_h
-#pragma unroll
-    for (int q = 0; q < 3; ++q)
-#pragma unroll
-      for (int mt = 0; mt < 2; ++mt) acc[mt] = __builtin_amdgcn_mfma_f32_32x32x16_f16(af[mt][PA[q]], bf[PB[q]], acc[mt], 0, 0, 0);
+    HxFrag<> f;
+    f.load(sAp, aofs[DC], MT_OFF, sBt, bofs);
+    f.mma(acc);
   };
   using I0 = std::integral_constant<int, 0>;
   using I1 = std::integral_constant<int, 1>;
@@ -193,44 +183,22 @@ __global__ __launch_bounds__(256 * NG, 1) void conv_mfma_hx2s_kernel(const ConvA
   {
     const float qinv = a.hq[1];
 #pragma unroll
-    for (int mt = 0; mt < 2; ++mt) acc[mt] = acc[mt] * qinv;
+    for (int mt = 0; mt < 2; ++mt) acc[mt][0] = acc[mt][0] * qinv;
   }
   const int sample = SPT == 1 ? tile : b0 + seg;
   if (sample >= a.B) return;  // (wave-uniform)
-  if (a.small_check && a.range_flag) {  // (ConvArgs::small_check: the output's low range)
-    float m = 0.f;
-#pragma unroll
-    for (int mt = 0; mt < 2; ++mt)
-#pragma unroll
-      for (int r = 0; r < 16; r += 2) m = hx_absmax3(acc[mt][r], acc[mt][r + 1], m);
-    hx_small_flag(a.range_flag, m);
-  }
+  if (a.small_check && a.range_flag) hx_small_scan(a.range_flag, acc);  // (ConvArgs::small_check: the output's low range)
   const size_t pix0 = (size_t)tile * 256 + 64 * seg;  // (whole samples: the tile's pixels are consecutive in the output)
 #pragma unroll
   for (int mt = 0; mt < 2; ++mt)
 #pragma unroll
     for (int r = 0; r < 16; ++r) {
-      const int pl = 32 * mt + (r & 3) + 8 * (r >> 2) + 4 * hp;
-      a.out[(pix0 + pl) * a.Cout + ch0] = acc[mt][r];
+      a.out[(pix0 + hx_acc_pixel(mt, r, hp)) * a.Cout + ch0] = acc[mt][0][r];
     }
   if (a.stats_out) {
     const int part = SPT == 1 ? seg : 0;
-    float s = 0.f;
-#pragma unroll
-    for (int mt = 0; mt < 2; ++mt)
-#pragma unroll
-      for (int r = 0; r < 16; ++r) s += acc[mt][r];
-    s += __shfl_xor(s, 32);
-    const float mean = s / 64.f;
-    float m2 = 0.f;
-#pragma unroll
-    for (int mt = 0; mt < 2; ++mt)
-#pragma unroll
-      for (int r = 0; r < 16; ++r) {
-        const float d = acc[mt][r] - mean;
-        m2 += d * d;
-      }
-    m2 += __shfl_xor(m2, 32);
+    float mean, m2;
+    hx_stats64(acc, 0, mean, m2);
     if (hp == 0) store_stats(a, a.stats_out + (((size_t)sample * a.g.nparts + part) * a.Cout + ch0) * 2, mean, m2);
   }
 }
@@ -260,8 +228,7 @@ bool conv_hx2s_supported(const ConvArgs& a, int mode) {
 
 int conv_hx2s_init() {
   int rc = 0;
-#define RAISES(WL, G) rc |= (int)hipFuncSetAttribute(reinterpret_cast<const void*>(&conv_mfma_hx2s_kernel<WL, G>), \
-                                                    hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024)
+#define RAISES(WL, G) rc |= raise_lds_limit(&conv_mfma_hx2s_kernel<WL, G>, 160 * 1024)
   RAISES(4, 1); RAISES(4, 2); RAISES(3, 1); RAISES(3, 2);
 #undef RAISES
   return rc;

@@ -142,57 +142,12 @@ __global__ __launch_bounds__(512, 2) void conv_mfma_hx2w_kernel(const ConvArgs a
   };
   issue_a(0);  // (ahead of the table: its round trip runs under the table's)
 
-  // ---- scale / shift table of this tile's sample: from the producers' partial statistics (consumer-side GroupNorm, as
-  // conv_mfma_hx2p_kernel's prologue: as many waves as it takes to give every lane ONE channel, fp64 sums, a butterfly
-  // over the group's lanes), or copied from an external array (ConvArgs::ab)
+  // ---- scale / shift table of this tile's sample: from the producers' partial statistics (consumer-side GroupNorm:
+  // gn_table_row, ONE row over as many of the eight waves as it takes to give every lane one channel), or copied from an
+  // external array (ConvArgs::ab)
   if (a.gn_stats0) {
-    const int gn_cpg = cin >> 3;
-    const int gn_wsh = gn_cpg <= 8 ? 0 : (gn_cpg <= 16 ? 1 : (gn_cpg <= 32 ? 2 : 3));  // log2 of the waves that take part
-    if (wave < (1 << gn_wsh)) {
-      const int gn_lpg = 8 << gn_wsh;  // lanes per group
-      const int gn_gi = wave * (8 >> gn_wsh) + (lane >> (3 + gn_wsh)), gn_sub = lane & (gn_lpg - 1);
-      const int gn_kmax = (gn_cpg + gn_lpg - 1) / gn_lpg;
-      float gam[4], bet[4];
-      double n = 0.0, s1 = 0.0, s2 = 0.0;
-#pragma unroll 1
-      for (int k = 0; k < gn_kmax; ++k) {
-        const int c = gn_gi * gn_cpg + gn_sub + gn_lpg * k;
-        const bool have = gn_sub + gn_lpg * k < gn_cpg;
-        const bool first = !have || c < a.C0;
-        const float* st = first ? a.gn_stats0 : a.gn_stats1;
-        const int cs = first ? a.C0 : a.C1, cc = have ? (first ? c : c - a.C0) : 0;
-        const int npt = first ? a.gn_nparts0 : a.gn_g.nparts;
-        float2 gv[16];
-#pragma unroll
-        for (int p = 0; p < 16; ++p) gv[p] = *reinterpret_cast<const float2*>(st + (((size_t)b0 * npt + (p < npt ? p : 0)) * cs + cc) * 2);
-        const float g_ = a.gn_gamma[have ? c : 0], b_ = a.gn_beta[have ? c : 0];
-        if (k == 0) gam[0] = g_, bet[0] = b_;
-        else if (k == 1) gam[1] = g_, bet[1] = b_;
-        else if (k == 2) gam[2] = g_, bet[2] = b_;
-        else gam[3] = g_, bet[3] = b_;
-#pragma unroll
-        for (int p = 0; p < 16; ++p) {
-          const double np = (have && p < npt) ? (double)geom_part_count(a.gn_g, p % a.gn_g.nparts) : 0.0;
-          const double mp = (double)gv[p].x;
-          n += np;
-          s1 += np * mp;
-          s2 += np > 0.0 ? (double)gv[p].y + np * mp * mp : 0.0;
-        }
-      }
-      for (int o = 1; o < gn_lpg; o <<= 1) n += __shfl_xor(n, o), s1 += __shfl_xor(s1, o), s2 += __shfl_xor(s2, o);
-      const double mean = n > 0.0 ? s1 / n : 0.0;
-      const double var = n > 0.0 ? s2 / n - mean * mean : 0.0;
-      const float gm = (float)mean;
-      const float rstd = (float)(1.0 / sqrt((var > 0.0 ? var : 0.0) + 1e-5));
-#pragma unroll
-      for (int k = 0; k < 4; ++k)
-        if (gn_sub + gn_lpg * k < gn_cpg) {
-          const float sc = rstd * gam[k];
-          float2 o;
-          o.x = HX_SA * sc, o.y = HX_SA * (bet[k] - gm * sc);
-          *reinterpret_cast<float2*>(sTab + (gn_gi * gn_cpg + gn_sub + gn_lpg * k) * 2) = o;
-        }
-    }
+    const GnLane gn_lane(wave, lane, gn_waves_log2(cin >> 3), cin >> 3);
+    if (gn_lane.row == 0) gn_table_row(a, gn_lane, b0, true, sTab, HX_SA);
   } else {
     for (int c = tid; c < cin; c += 512) {
       const float2 e = *reinterpret_cast<const float2*>(a.ab + ((size_t)b0 * cin + c) * 2);
@@ -318,14 +273,7 @@ __global__ __launch_bounds__(512, 2) void conv_mfma_hx2w_kernel(const ConvArgs a
       for (int mt = 0; mt < 2; ++mt)
 #pragma unroll
         for (int pl = 0; pl < 2; ++pl) af[mt][pl] = *reinterpret_cast<const f16x8*>(vp + aofs[mt][pl]);
-      constexpr int PA[3] = {1, 0, 0}, PB[3] = {0, 1, 0};  // a_l w_h, a_h w_l, a_h w_h
-#pragma unroll
-      for (int q = 0; q < 3; ++q)
-#pragma unroll
-        for (int mt = 0; mt < 2; ++mt)
-#pragma unroll
-          for (int nt = 0; nt < 2; ++nt)
-            acc[pi][mt][nt] = __builtin_amdgcn_mfma_f32_32x32x16_f16(af[mt][PA[q]], bfr[pi][nt][PB[q]], acc[pi][mt][nt], 0, 0, 0);
+      hx_mma3<2>(acc[pi], af, bfr[pi]);
     }
   };
 
@@ -468,8 +416,8 @@ bool conv_hx2w_supported(const ConvArgs& a, int mode) {
 int conv_hx2w_init() {
   int rc = 0;
 
-  rc |= (int)hipFuncSetAttribute(reinterpret_cast<const void*>(&conv_mfma_hx2w_kernel<4>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-  rc |= (int)hipFuncSetAttribute(reinterpret_cast<const void*>(&conv_mfma_hx2w_kernel<5>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
+  rc |= raise_lds_limit(&conv_mfma_hx2w_kernel<4>, 160 * 1024);
+  rc |= raise_lds_limit(&conv_mfma_hx2w_kernel<5>, 160 * 1024);
   return rc;
 }
 

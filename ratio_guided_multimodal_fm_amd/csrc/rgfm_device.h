@@ -126,6 +126,98 @@ __device__ __forceinline__ void hx_small_flag(unsigned* flag, float m) {  // m: 
   if (m > 0.f && m < HX_SMALL && (threadIdx.x & 63) == 0) atomicOr(flag, 2u);
 }
 
+// Accumulator layout of a wave tile (the 32x32 MFMAs' output, all conv kernels): channel = lane & 31 (+ 32 nt),
+// acc[mt][nt][r] = pixel hx_acc_pixel(mt, r, hp) of the wave's 64-pixel segment, hp = lane >> 5.
+__device__ __forceinline__ constexpr int hx_acc_pixel(int mt, int r, int hp) { return 32 * mt + (r & 3) + 8 * (r >> 2) + 4 * hp; }
+
+// ---- consumer-side GroupNorm (ConvArgs::gn_stats0): a conv workgroup derives the scale/shift table of its own sample(s)
+// from the producers' partial statistics in its prologue.  One table row per sample; a row is reduced by 1, 2, 4 or 8
+// waves, so that a group's channels are spread over LPG = 8, 16, 32 or 64 consecutive lanes; a lane strides over its
+// group's channels (sub, sub + LPG, ...: at most four), fetches the <= 16 (mean, M2) partials of a channel in one
+// round trip and reduces
+//   N = sum n_p,  S1 = sum n_p mean_p,  S2 = sum [M2_p + n_p mean_p^2]  ->  mean = S1 / N,  var = S2 / N - mean^2
+// in fp64 without divisions in the loop; an LPG-lane butterfly gives the group's sums.  EVERY kernel builds its table
+// from the pieces below, so two kernels that cut a row over the same number of waves write bit-identical tables.
+struct GnLane {  // which (table row, group, channels) a lane reduces when 2^wsh waves share a row
+  int row, gi, sub, lpg, kmax, cpg;
+  __device__ __forceinline__ GnLane(int wave, int lane, int wsh, int cpg_) {
+    cpg = cpg_;
+    row = wave >> wsh;
+    lpg = 8 << wsh;  // lanes per group
+    sub = lane & (lpg - 1);
+    gi = (wave & ((1 << wsh) - 1)) * (8 >> wsh) + (lane >> (3 + wsh));
+    kmax = (cpg + lpg - 1) / lpg;  // channels per lane (wave-uniform, <= 4)
+  }
+};
+// log2 of the waves a row of cpg-channel groups wants: as many as it takes to give every lane ONE channel
+__device__ __forceinline__ int gn_waves_log2(int cpg) { return cpg <= 8 ? 0 : (cpg <= 16 ? 1 : (cpg <= 32 ? 2 : 3)); }
+
+struct GnPartials {  // one channel's partials and affine parameters, fetched before any is used (one memory round trip)
+  float2 v[16];
+  float gamma, beta;
+  int npt;
+  // concat channel c of sample b; !have: entry 0 of the first source, never used
+  __device__ __forceinline__ void fetch(const ConvArgs& a, size_t b, int c, bool have) {
+    const bool first = !have || c < a.C0;
+    const float* st = first ? a.gn_stats0 : a.gn_stats1;
+    const int cs = first ? a.C0 : a.C1, cc = have ? (first ? c : c - a.C0) : 0;
+    npt = first ? a.gn_nparts0 : a.gn_g.nparts;
+#pragma unroll
+    for (int p = 0; p < 16; ++p)
+      v[p] = *reinterpret_cast<const float2*>(st + ((b * npt + (p < npt ? p : 0)) * cs + cc) * 2);
+    gamma = a.gn_gamma[have ? c : 0], beta = a.gn_beta[have ? c : 0];
+  }
+  __device__ __forceinline__ void accumulate(const TileGeom& gg, bool have, double& n, double& s1, double& s2) const {
+#pragma unroll
+    for (int p = 0; p < 16; ++p) {
+      const double np = (have && p < npt) ? (double)geom_part_count(gg, p % gg.nparts) : 0.0;
+      const double mp = (double)v[p].x;
+      n += np;
+      s1 += np * mp;
+      s2 += np > 0.0 ? (double)v[p].y + np * mp * mp : 0.0;
+    }
+  }
+};
+// the group's sums over its lpg lanes -> mean, rstd
+__device__ __forceinline__ void gn_finish(double n, double s1, double s2, int lpg, float& gm, float& rstd) {
+  for (int o = 1; o < lpg; o <<= 1) n += __shfl_xor(n, o), s1 += __shfl_xor(s1, o), s2 += __shfl_xor(s2, o);
+  const double mean = n > 0.0 ? s1 / n : 0.0;
+  const double var = n > 0.0 ? s2 / n - mean * mean : 0.0;
+  gm = (float)mean;
+  rstd = (float)(1.0 / sqrt((var > 0.0 ? var : 0.0) + 1e-5));
+}
+// This lane's share of the table row of sample b (bok: b is inside the batch -- otherwise nothing is read and the row
+// gets the pairs of an empty group, which no item uses): tab_row[c] = scale x (rstd gamma, beta - mean rstd gamma).
+// scale: S_A for the two-plane fp16 kernels, 1 for the split-bf16 kernel.  Wave-uniform call.
+__device__ __forceinline__ void gn_table_row(const ConvArgs& a, const GnLane& L, int b, bool bok, float* tab_row, float scale) {
+  float gam[4], bet[4];
+  double n = 0.0, s1 = 0.0, s2 = 0.0;
+#pragma unroll 1
+  for (int k = 0; k < L.kmax; ++k) {  // one channel (16 partials) per round trip: more at once spills
+    const int c = L.gi * L.cpg + L.sub + L.lpg * k;
+    const bool have = bok && L.sub + L.lpg * k < L.cpg;
+    GnPartials f;
+    f.fetch(a, bok ? (size_t)b : 0, c, have);
+    if (k == 0) gam[0] = f.gamma, bet[0] = f.beta;
+    else if (k == 1) gam[1] = f.gamma, bet[1] = f.beta;
+    else if (k == 2) gam[2] = f.gamma, bet[2] = f.beta;
+    else gam[3] = f.gamma, bet[3] = f.beta;
+    f.accumulate(a.gn_g, have, n, s1, s2);
+  }
+  float gm, rstd;
+  gn_finish(n, s1, s2, L.lpg, gm, rstd);
+#pragma unroll
+  for (int k = 0; k < 4; ++k) {
+    if (L.sub + L.lpg * k < L.cpg) {
+      const float sc = rstd * gam[k];
+      float2 o;
+      o.x = scale * sc;
+      o.y = scale * (bet[k] - gm * sc);
+      *reinterpret_cast<float2*>(tab_row + (L.gi * L.cpg + L.sub + L.lpg * k) * 2) = o;
+    }
+  }
+}
+
 // Stage the input halo tile of channel chunk `c` (16 channels starting at concat
 // channel c) into sA[halo_px][LDP].  Shared with conv_out.
 template <int MODE>

@@ -157,6 +157,19 @@ struct ConvArgs {
   int halo_px;       // pixels of the staged input tile
 };
 
+// ---- host-side helpers shared by the conv kernels' launch code
+// pixels of the staged input tile of the split-plane kernels (they set ConvArgs::halo_px to it): (th + 2) x (W + 2)
+// plane pixels per sample of the tile in every mode (the fp32 kernel's own halo differs for stride 2)
+inline int conv_halo_px(const ConvArgs& a) { return a.g.spt * (a.g.th + 2) * (a.g.W + 2); }
+// output channels per block of the packed split-plane weight images (bf16x3 and two-plane fp16 alike) = channels one
+// workgroup covers: 128 when Cout % 128 == 0 (two 64-channel groups), else 64 or 32
+inline int conv_block_channels(int Cout) { return Cout % 128 == 0 ? 128 : (Cout % 64 == 0 ? 64 : 32); }
+// raises a kernel's dynamic-LDS limit (the default is 64 KB); returns the hipError_t as an int, 0 = success
+template <class Kernel>
+inline int raise_lds_limit(Kernel* kernel, int bytes) {
+  return (int)hipFuncSetAttribute(reinterpret_cast<const void*>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize, bytes);
+}
+
 struct ConvInArgs {  // first conv of a net: NCHW image -> NHWC features
   const float* x;    // [B][CIN][H][W]
   const float* w;    // [C0][CIN][3][3] (reference layout)
