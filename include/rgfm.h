@@ -325,6 +325,35 @@ int rgfm_fmnet_sample_pair(rgfm_fmnet* hx, rgfm_fmnet* hy, float* x_inout, float
                            int batch, int num_steps, double gamma, int step_begin, int step_end,
                            void* ws, size_t ws_bytes, rgfm_stream_t stream);
 
+/* Training pass of FlowMatchingModel (replaces the reference's autograd through FlowMatchingModel.forward in
+ * src/train_flow.py --model original).  Same conventions as the U-Net's training pass: exact fp32 arithmetic on
+ * v_mfma_f32_32x32x2_f32 whatever the handle's conv mode, NCHW fp32 boundary tensors, stream-ordered, caller-owned
+ * workspace, nothing allocated or synchronised inside forward_train / backward.  The net has no Dropout and no batch
+ * statistics, so training and eval semantics coincide.
+ *
+ * rgfm_fmnet_forward_train writes v_out[batch,1,28,28] = model(x, t) (t_count = 1: one t for every row, or batch) and
+ * leaves in `ws` (at least rgfm_fmnet_train_workspace_bytes(h, batch) bytes) what rgfm_fmnet_backward needs: x, every
+ * layer's raw output, the (mean, rstd) pairs of the seven GroupNorms and the [features | t_emb] concat.  One ws per
+ * forward that is still to be differentiated; it must stay untouched between the two calls.
+ *
+ * rgfm_fmnet_backward: given dv = dL/dv_out, writes dL/dx to dx_out (optional, may be null) and dL/dparams to
+ * dparams_out -- one blob in the parameter blob's state_dict order, overwritten (not accumulated); t gets no
+ * gradient.  Both ConvTranspose2d(4, 2, 1) layers and both Linears (12544 -> feature_dim, feature_dim + time_emb_dim
+ * -> 12544) run on the fp32 MFMA in all three roles.  Every reduction has a fixed order (split-K partial slices added
+ * in split order, no float atomics): two calls on the same inputs give bitwise-identical results.  The handle's
+ * parameters must be those of the forward.
+ *
+ * rgfm_fmnet_update_params copies a new state_dict-order blob into the handle and repacks every derived image in
+ * place -- everything rgfm_fmnet_create packs: the fp32-packed, two-plane and split-bf16 conv and transposed-conv
+ * images, the Linear weights and bias re-indexed to NHWC, conv_out's layout -- without reallocating: what an optimizer
+ * step needs before the next forward / sample call.  Synchronises `stream` (as create). */
+int rgfm_fmnet_train_workspace_bytes(const rgfm_fmnet* h, int batch, size_t* bytes);
+int rgfm_fmnet_forward_train(rgfm_fmnet* h, const float* x, const float* t_dev, int t_count, float* v_out,
+                             int batch, void* ws, size_t ws_bytes, rgfm_stream_t stream);
+int rgfm_fmnet_backward(rgfm_fmnet* h, const float* dv, float* dx_out, float* dparams_out, int batch, void* ws,
+                        size_t ws_bytes, rgfm_stream_t stream);
+int rgfm_fmnet_update_params(rgfm_fmnet* h, const float* params_dev, size_t n_floats, rgfm_stream_t stream);
+
 /* One guidance evaluation on its own (parity hook for sample_mnist_svhn.py:124-171):
  * vx/vy are overwritten with (1-gamma)*v + gamma*g at time t; weights_out[B,N]
  * (optional, may be null) receives the normalised importance weights. */

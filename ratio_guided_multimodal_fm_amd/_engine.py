@@ -265,6 +265,25 @@ class FmNetEngine(_VelocityEngine):
     PREFIX = "rgfm_fmnet"
     SINGLE, SINGLE_WS = "rgfm_fmnet_sample_single", "rgfm_fmnet_workspace_bytes"
     PAIR, PAIR_WS = "rgfm_fmnet_sample_pair", "rgfm_fmnet_sample_pair_workspace_bytes"
+    UPDATE = True
+
+    def _check_eval(self, module):
+        if module.training:
+            raise _lib.RgfmError(
+                f"{type(module).__name__} is in training mode; model(x, t) and the samplers are the eval path. Train "
+                "through model.forward_train(x, t) (HIP backward), or call .eval() to evaluate / sample.")
+
+    # ---- training -----------------------------------------------------
+    def forward_train(self, x, t):
+        """v = model(x, t) on the exact-fp32 training path, differentiable w.r.t. x and the parameters
+        (_FmNetTrainFn).  The net has no Dropout and no batch statistics: the module's mode does not matter."""
+        m = self._module()
+        _require_hip(x, t)
+        self._check_input(m, x)
+        t = t.reshape(-1)
+        if t.numel() not in (1, x.shape[0]):
+            raise _lib.RgfmError(f"t must have 1 or {x.shape[0]} elements, got {t.numel()}")
+        return _FmNetTrainFn.apply(self, x, t, *m.parameters())
 
     def desc(self):
         m = self._module()
@@ -421,6 +440,57 @@ class _UNetTrainFn(torch.autograd.Function):
         ctx.ws = None
         grads = [g.view(q.shape) for g, q in zip(torch.split(dparams, [q.numel() for q in params]), params)]
         return (None, dx, None, None, *grads)
+
+
+class _FmNetTrainFn(torch.autograd.Function):
+    """Training forward / backward of FlowMatchingModel through rgfm_fmnet_forward_train / rgfm_fmnet_backward.
+
+    Inputs: the engine, x, t and the module's parameters (state_dict order), so that autograd hands back dL/dx and
+    every dL/dparam.  Each call owns its saved-state buffer; dL/dx is computed only when x requires it."""
+
+    @staticmethod
+    def forward(ctx, engine, x, t, *params):
+        dev = x.device
+        x, t = x.contiguous(), t.contiguous()
+        B = x.shape[0]
+        out = torch.empty_like(x)
+        ctx.engine, ctx.B, ctx.ws, ctx.nbytes, ctx.h = engine, B, None, 0, None
+        ctx.save_for_backward(*params)
+        ctx.x_shape = x.shape
+        if B == 0:
+            return out
+        L = _lib.lib()
+        with torch.cuda.device(dev):
+            h = engine.handle(dev)
+            n = ctypes.c_size_t()
+            _lib.check(L.rgfm_fmnet_train_workspace_bytes(h, B, ctypes.byref(n)))
+            ws = torch.empty(n.value, dtype=torch.uint8, device=dev)
+            _lib.check(L.rgfm_fmnet_forward_train(h, _ptr(x), _ptr(t), t.numel(), _ptr(out), B, _ptr(ws), n.value,
+                                                  _stream(dev)))
+        ctx.ws, ctx.nbytes, ctx.h = ws, n.value, h
+        return out
+
+    @staticmethod
+    def backward(ctx, dv):
+        params = ctx.saved_tensors
+        dev = dv.device
+        need_x = ctx.needs_input_grad[1]
+        if ctx.B == 0:
+            return (None, torch.zeros(ctx.x_shape, device=dev) if need_x else None, None,
+                    *[torch.zeros_like(q) for q in params])
+        if ctx.ws is None:
+            raise _lib.RgfmError("the saved state of this forward_train call is gone (backward ran twice?)")
+        if ctx.engine._handle is not ctx.h:
+            raise _lib.RgfmError("the module's handle was re-created between forward_train and backward")
+        dv = dv.to(torch.float32).contiguous()
+        dparams = torch.empty(sum(q.numel() for q in params), device=dev)
+        dx = torch.empty(ctx.x_shape, device=dev) if need_x else None
+        with torch.cuda.device(dev):
+            _lib.check(_lib.lib().rgfm_fmnet_backward(ctx.h, _ptr(dv), _ptr(dx), _ptr(dparams), ctx.B, _ptr(ctx.ws),
+                                                      ctx.nbytes, _stream(dev)))
+        ctx.ws = None
+        grads = [g.view(q.shape) for g, q in zip(torch.split(dparams, [q.numel() for q in params]), params)]
+        return (None, dx, None, *grads)
 
 
 class RatioEngine(_EngineBase):

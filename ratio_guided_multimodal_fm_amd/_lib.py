@@ -102,6 +102,11 @@ SIGNATURES = {
     "rgfm_profile_read": (c_int, [c_int, P(c_double), P(c_double), P(c_int64), P(c_double)]),
     "rgfm_profile_reserve": (c_int, [c_int64]),
     "rgfm_ubench_mfma_f16": (c_int, [P(c_double)]),
+    "rgfm_fmnet_train_workspace_bytes": (c_int, [c_void_p, c_int, P(c_size_t)]),
+    "rgfm_fmnet_forward_train": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_void_p, c_int, c_void_p, c_size_t,
+                                         c_void_p]),
+    "rgfm_fmnet_backward": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_void_p, c_size_t, c_void_p]),
+    "rgfm_fmnet_update_params": (c_int, [c_void_p, c_void_p, c_size_t, c_void_p]),
     "rgfm_ubench_hbm_copy": (c_int, [c_size_t, P(c_double)]),
     "rgfm_unet_set_conv_mode": (c_int, [c_void_p, c_int]),
     "rgfm_fmnet_set_conv_mode": (c_int, [c_void_p, c_int]),

@@ -1,28 +1,13 @@
-// api_fmnet.cpp -- FlowMatchingModel ("--model original"): handle, forward, samplers (C ABI: include/rgfm.h).
+// api_fmnet.cpp -- FlowMatchingModel ("--model original"): handle, weight packing, forward, samplers (C ABI:
+// include/rgfm.h).  The training pass: api_fmnet_train.cpp.
 #include "rgfm_host.h"
 
 // ================================================================== FlowMatchingModel ("--model original")
 // Encoder-decoder velocity net of src/models/flow_matching.py:34-173, 1x28x28 images.
-struct FmPlan {  // what plan_fmnet produces: blob / packed offsets of every layer
-  size_t c1w = 0, c1b = 0;           // encoder.conv1 (reference layout, conv_in kernel)
-  size_t egw[4], egb[4];             // encoder.gn1..4
-  ConvW ec[3];                       // encoder.conv2..4
-  size_t fcw = 0, fcb = 0, fc_pk = 0;
-  size_t f1w = 0, f1b = 0, f1w_pk = 0, f1b_pk = 0;
-  ConvW d1, d2;                      // decoder.deconv1/2 (taps = 16 raw, packed per parity)
-  size_t dgw[3], dgb[3];             // decoder.gn1..3
-  ConvW c3;                          // decoder.conv3
-  size_t cow = 0, cob = 0, cow_pk = 0;  // decoder.conv_out (raw; re-laid out for conv_out_kernel in `packed`)
-};
-struct rgfm_fmnet : WeightStore, FmPlan {  // (`packed` also holds the re-indexed Linear weights)
-  rgfm_fmnet_desc d;
-  float* freqs = nullptr;
-};
-
+// (the handle itself: rgfm_host.h, shared with api_fmnet_train.cpp)
 namespace {
 
-constexpr int FM_S = 28, FM_P = 49, FM_CF = 256;  // image size; 7x7 bottleneck pixels x 256 channels
-constexpr int FM_FC_SPLITS = 14;                  // 12544/16 = 784 K-chunks = 14 x 56
+constexpr int FM_FC_SPLITS = 14;  // 12544/16 = 784 K-chunks = 14 x 56
 
 // state_dict order of FlowMatchingModel (flow_matching.py:43-54, :88-98, :147-151)
 size_t plan_fmnet(const rgfm_fmnet_desc& d, rgfm_fmnet* h) {
@@ -206,6 +191,44 @@ extern "C" int rgfm_fmnet_param_floats(const rgfm_fmnet_desc* desc, size_t* n_fl
   return RGFM_OK;
 }
 
+// Every derived image of the handle from h->params: the two-plane, split-bf16 and fp32-packed conv and deconv images,
+// the Linear weights and bias re-indexed to NHWC, conv_out's layout; then which convs may run on the fp16 path
+// (synchronises as rgfm_unet_create's packing does).  Used by rgfm_fmnet_create and, in place, by rgfm_fmnet_update_params.
+int fm_pack_weights(rgfm_fmnet* h, hipStream_t s) {
+  const int F = h->d.feature_dim, T = h->d.time_emb_dim;
+  int rc;
+  {
+    auto packh = [&](const ConvW& w, int mode) {
+      launch_pack_conv_hx2(h->params + w.w_raw, h->packedh + w.hx.off, h->hq + 4 * w.hx.hq, w.cout, w.cin, w.taps, mode, s);
+    };
+    packh(h->ec[0], CONV_S2), packh(h->ec[1], CONV_S2), packh(h->ec[2], CONV_S1), packh(h->c3, CONV_S1);
+    packh(h->d1, CONV_T2), packh(h->d2, CONV_T2);
+    if ((rc = read_hx_flags(*h, {&h->ec[0].hx, &h->ec[1].hx, &h->ec[2].hx, &h->c3.hx, &h->d1.hx, &h->d2.hx}, s))) return rc;
+    // (as rgfm_unet_create: a conv behind a GroupNorm with out-of-window parameters leaves the fp16 path)
+    std::vector<NormGate> gates{{h->dgw[0], h->dgb[0], 128, &h->d2.hx}, {h->dgw[1], h->dgb[1], 64, &h->c3.hx}};
+    const int ech[3] = {32, 64, 128};
+    for (int i = 0; i < 3; ++i) gates.push_back({h->egw[i], h->egb[i], ech[i], &h->ec[i].hx});
+    if ((rc = demote_by_norms(*h, gates, s))) return rc;
+  }
+  for (int i = 0; i < 3; ++i) {  // encoder conv2 / conv3 are stride 2 (phase-ordered weights), conv4 stride 1
+    const ConvW& w = h->ec[i];
+    if (i < 2) launch_pack_conv_bx3_s2(h->params + w.w_raw, h->packed3 + w.w_bx3, w.cout, w.cin, s);
+    else launch_pack_conv_bx3(h->params + w.w_raw, h->packed3 + w.w_bx3, w.cout, w.cin, 9, s);
+  }
+  launch_pack_conv_bx3(h->params + h->c3.w_raw, h->packed3 + h->c3.w_bx3, 32, 64, 9, s);
+  launch_pack_deconv_bx3(h->params + h->d1.w_raw, h->packed3 + h->d1.w_bx3, 256, 128, s);
+  launch_pack_deconv_bx3(h->params + h->d2.w_raw, h->packed3 + h->d2.w_bx3, 128, 64, s);
+  for (const ConvW& w : h->ec) launch_pack_conv(h->params + w.w_raw, h->packed + w.w_pk, w.cout, w.cin, 9, nt32_of(w.cout), s);
+  launch_pack_conv(h->params + h->c3.w_raw, h->packed + h->c3.w_pk, 32, 64, 9, 1, s);
+  launch_pack_deconv(h->params + h->d1.w_raw, h->packed + h->d1.w_pk, 256, 128, nt32_of(128), s);
+  launch_pack_deconv(h->params + h->d2.w_raw, h->packed + h->d2.w_pk, 128, 64, nt32_of(64), s);
+  launch_pack_conv_out(h->params + h->cow, h->packed + h->cow_pk, h->d.img_channels, 32, s);
+  launch_permute_cols(h->params + h->fcw, h->packed + h->fc_pk, F, FM_CF, FM_P, s);
+  launch_permute_rows(h->params + h->f1w, h->params + h->f1b, h->packed + h->f1w_pk, h->packed + h->f1b_pk, FM_CF, FM_P,
+                      F + T, s);
+  return RGFM_OK;
+}
+
 extern "C" int rgfm_fmnet_create(const rgfm_fmnet_desc* desc, const float* params_dev, size_t n_floats,
                                  rgfm_stream_t stream, rgfm_fmnet** out) {
   int rc = check_fm_desc(desc);
@@ -223,39 +246,10 @@ extern "C" int rgfm_fmnet_create(const rgfm_fmnet_desc* desc, const float* param
     rgfm_fmnet_destroy(h);
     return fail(code, "%s", what);
   };
-  const int F = desc->feature_dim, T = desc->time_emb_dim, half = T / 2;
+  const int half = desc->time_emb_dim / 2;
   if ((rc = h->alloc(params_dev, true, s))) return rgfm_fmnet_destroy(h), rc;
   if (hipMalloc(&h->freqs, half * sizeof(float)) != hipSuccess) return bail(RGFM_ENOMEM, "hipMalloc(freqs)");
-  {
-    auto packh = [&](const ConvW& w, int mode) {
-      launch_pack_conv_hx2(h->params + w.w_raw, h->packedh + w.hx.off, h->hq + 4 * w.hx.hq, w.cout, w.cin, w.taps, mode, s);
-    };
-    packh(h->ec[0], CONV_S2), packh(h->ec[1], CONV_S2), packh(h->ec[2], CONV_S1), packh(h->c3, CONV_S1);
-    packh(h->d1, CONV_T2), packh(h->d2, CONV_T2);
-    if ((rc = read_hx_flags(*h, {&h->ec[0].hx, &h->ec[1].hx, &h->ec[2].hx, &h->c3.hx, &h->d1.hx, &h->d2.hx}, s)))
-      return rgfm_fmnet_destroy(h), rc;
-    // (as rgfm_unet_create: a conv behind a GroupNorm with out-of-window parameters leaves the fp16 path)
-    std::vector<NormGate> gates{{h->dgw[0], h->dgb[0], 128, &h->d2.hx}, {h->dgw[1], h->dgb[1], 64, &h->c3.hx}};
-    const int ech[3] = {32, 64, 128};
-    for (int i = 0; i < 3; ++i) gates.push_back({h->egw[i], h->egb[i], ech[i], &h->ec[i].hx});
-    if ((rc = demote_by_norms(*h, gates, s))) return rgfm_fmnet_destroy(h), rc;
-  }
-  for (int i = 0; i < 3; ++i) {  // encoder conv2 / conv3 are stride 2 (phase-ordered weights), conv4 stride 1
-    const ConvW& w = h->ec[i];
-    if (i < 2) launch_pack_conv_bx3_s2(h->params + w.w_raw, h->packed3 + w.w_bx3, w.cout, w.cin, s);
-    else launch_pack_conv_bx3(h->params + w.w_raw, h->packed3 + w.w_bx3, w.cout, w.cin, 9, s);
-  }
-  launch_pack_conv_bx3(h->params + h->c3.w_raw, h->packed3 + h->c3.w_bx3, 32, 64, 9, s);
-  launch_pack_deconv_bx3(h->params + h->d1.w_raw, h->packed3 + h->d1.w_bx3, 256, 128, s);
-  launch_pack_deconv_bx3(h->params + h->d2.w_raw, h->packed3 + h->d2.w_bx3, 128, 64, s);
-  for (const ConvW& w : h->ec) launch_pack_conv(h->params + w.w_raw, h->packed + w.w_pk, w.cout, w.cin, 9, nt32_of(w.cout), s);
-  launch_pack_conv(h->params + h->c3.w_raw, h->packed + h->c3.w_pk, 32, 64, 9, 1, s);
-  launch_pack_deconv(h->params + h->d1.w_raw, h->packed + h->d1.w_pk, 256, 128, nt32_of(128), s);
-  launch_pack_deconv(h->params + h->d2.w_raw, h->packed + h->d2.w_pk, 128, 64, nt32_of(64), s);
-  launch_pack_conv_out(h->params + h->cow, h->packed + h->cow_pk, desc->img_channels, 32, s);
-  launch_permute_cols(h->params + h->fcw, h->packed + h->fc_pk, F, FM_CF, FM_P, s);
-  launch_permute_rows(h->params + h->f1w, h->params + h->f1b, h->packed + h->f1w_pk, h->packed + h->f1b_pk, FM_CF, FM_P,
-                      F + T, s);
+  if ((rc = fm_pack_weights(h, s))) return rgfm_fmnet_destroy(h), rc;
   // exp(arange(half) * -(ln(1e4) / (half - 1))) in fp32, as torch evaluates it (flow_matching.py:25-27)
   std::vector<float> fr(half);
   const float neg = (float)(-(std::log(10000.0) / (double)(half - 1)));

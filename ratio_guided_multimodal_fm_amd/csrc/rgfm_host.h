@@ -11,6 +11,7 @@
 //   api_train.cpp    rgfm_unet_forward_train / _backward (U-Net training pass)
 //   api_ratio_train.cpp  rgfm_ratio_forward_train / _backward (ratio estimators' training pass)
 //   api_fmnet.cpp    rgfm_fmnet_*           (FlowMatchingModel)
+//   api_fmnet_train.cpp  rgfm_fmnet_forward_train / _backward / _update_params (FlowMatchingModel's training pass)
 //
 // No PyTorch types, no allocation and no synchronisation inside forward / sample calls (everything is carved from the
 // caller's workspace, stream-ordered).
@@ -1187,7 +1188,28 @@ struct rgfm_ratio : WeightStore {
 };
 
 
-// ================================================================== training passes (api_train.cpp, api_ratio_train.cpp)
+// ================================================================== FlowMatchingModel ("--model original")
+constexpr int FM_S = 28, FM_P = 49, FM_CF = 256;  // image size; 7x7 bottleneck pixels x 256 channels
+struct FmPlan {  // what plan_fmnet produces: blob / packed offsets of every layer
+  size_t c1w = 0, c1b = 0;           // encoder.conv1 (reference layout, conv_in kernel)
+  size_t egw[4], egb[4];             // encoder.gn1..4
+  ConvW ec[3];                       // encoder.conv2..4
+  size_t fcw = 0, fcb = 0, fc_pk = 0;
+  size_t f1w = 0, f1b = 0, f1w_pk = 0, f1b_pk = 0;
+  ConvW d1, d2;                      // decoder.deconv1/2 (taps = 16 raw, packed per parity)
+  size_t dgw[3], dgb[3];             // decoder.gn1..3
+  ConvW c3;                          // decoder.conv3
+  size_t cow = 0, cob = 0, cow_pk = 0;  // decoder.conv_out (raw; re-laid out for conv_out_kernel in `packed`)
+};
+struct rgfm_fmnet : WeightStore, FmPlan {  // (`packed` also holds the re-indexed Linear weights)
+  rgfm_fmnet_desc d;
+  float* freqs = nullptr;
+};
+// every derived weight image of the handle from h->params (api_fmnet.cpp; create and update_params)
+int fm_pack_weights(rgfm_fmnet* h, hipStream_t s);
+
+
+// ================================================================== training passes (api_train.cpp, api_ratio_train.cpp, api_fmnet_train.cpp)
 // One conv on ug_igemm_kernel (unet_grad.hip): forward, data gradient, weight gradient with its ordered split-K reduce.
 inline void wgrad_split(UgConv& c) {
   const int M = c.Cout, N = c.Cin * c.taps, K = c.B * c.Ho * c.Wo;
@@ -1213,4 +1235,14 @@ inline void run_wgrad(UgConv c, const float* dy, const float* x, float* part, fl
   launch_ug_conv(c, 2, s);
   launch_ug_reduce(part, c.splits, (size_t)c.Cout * c.Cin * c.taps, dw, s);
   launch_ug_bias_grad(dy, c.B, c.Cout, c.Ho * c.Wo, db, s);
+}
+
+// One dense layer on fg_gemm_kernel (fmnet_grad.hip): K split into ranges of kps (a multiple of 16) over gridDim.z when
+// the output tile grid alone would leave the device idle (K = 12544 against a [batch][F] output); by shape only, so
+// the reduction order -- partial slices added in split order -- is the same on every call.
+inline void fg_split(FgGemm& g) {
+  const int tiles = ((g.M + 63) / 64) * ((g.N + 63) / 64);
+  const int want = std::max(1, std::min((512 + tiles - 1) / tiles, (g.K + 255) / 256));
+  g.kps = ((g.K + want - 1) / want + 15) / 16 * 16;
+  g.splits = (g.K + g.kps - 1) / g.kps;
 }

@@ -395,9 +395,9 @@ void launch_guid_schedule(float* sched, int step_begin, int ns, int num_steps, h
 // The conv input raster is Hc x Wc; with `up` it is the nearest-x2 image of the Hs x Ws source, else Hs = Hc.
 struct UgConv {
   const float* x;   // input [B][Cin][Hs][Ws]
-  const float* w;   // [Cout][Cin][taps]
+  const float* w;   // [Cout][Cin][taps]; taps 1, 9 (3x3, pad 1) or 16 (4x4, pad 1)
   const float* dy;  // output gradient [B][Cout][Ho][Wo]
-  const float* bias;
+  const float* bias;  // op 0: [Cout] or null
   const float* temb;  // [B][Cout] or null
   const float* res;   // [B][Cout][Ho][Wo] or null (may alias out)
   float* out;
@@ -407,6 +407,7 @@ struct UgConv {
   int B, Cin, Cout, taps, stride, up;
   int Hs, Ws, Hc, Wc, Ho, Wo;
   int splits, kps;  // op 2: K split into `splits` ranges of kps (multiple of 16); else splits = 1, kps = K
+  const float* dbias;  // op 1: added per row m of the result (a transposed conv's bias), or null
 };
 // out = cat(s0, s1) [B][C0 + C1][HW]; with mr: silu(gamma (v - mean) rstd + beta) per group, then (drop_hdr set and
 // its p > 0) dropout with the keep decisions of ResBlock `block`
@@ -473,5 +474,21 @@ void launch_rt_ln_act(const float* u, const float* gamma, const float* beta, int
 void launch_rt_ln_act_bwd(const float* u, const float* g, const float* gamma, const float* beta, int rows, int width,
                           const unsigned* hdr, int block, const float* mr, float* du, float* pg, float* pb,
                           hipStream_t s);
+
+// ---- training pass of FlowMatchingModel (fmnet_grad.hip): the wide Linears as fp32-MFMA GEMMs
+// C[m][n] = bias[n] + sum_k A(m, k) B(n, k).  An operand is ROW-major (element (r, k) at p[r * ld + k]) or K-major
+// (p[k * ld + r]): which one is the launch's a_kmajor / b_kmajor.  splits > 1: workgroup z covers k in
+// [z kps, (z + 1) kps) and writes part[z][M][N]; launch_fg_gemm then adds the slices in split order (+ bias).
+struct FgGemm {
+  const float* a;
+  const float* b;
+  const float* bias;  // [N] or null
+  float* c;           // [M][ldc]
+  float* part;        // [splits][M][N] (splits > 1)
+  int M, N, K, lda, ldb, ldc;
+  int splits, kps;    // kps: a multiple of 16 (splits == 1: kps >= K)
+  int veca, vecb;     // a row-major operand may be read 16 bytes at a time (set by launch_fg_gemm)
+};
+void launch_fg_gemm(FgGemm g, bool a_kmajor, bool b_kmajor, hipStream_t s);
 
 }  // namespace rgfm

@@ -1,4 +1,4 @@
-// train_device.h -- device helpers shared by the training kernels (unet_grad.hip, ratio_train.hip).
+// train_device.h -- device helpers shared by the training kernels (unet_grad.hip, ratio_train.hip, fmnet_grad.hip).
 #pragma once
 #include <cstdint>
 
@@ -12,6 +12,33 @@ __device__ __forceinline__ float ug_dsilu(float v) {
   const float s = ug_sigmoid(v);
   return s * (1.0f + v * (1.0f - s));
 }
+
+// The GEMM core of every training kernel: one staged K-chunk (KC = 16) of a 64 (M) x 64 (N) block tile.  Every thread
+// hands over 4 consecutive k -- quarter qa / qb -- of ONE row of A and ONE row (column) of B; the four waves then take
+// eight v_mfma_f32_32x32x2_f32 steps on their 32 x 32 accumulator (same LDS layout and k permutation as
+// linear_mfma_kernel).  sA / sB: 64 * LDP floats each.
+__device__ __forceinline__ void ug_mfma_chunk(float* sA, float* sB, int rowa, int qa, const float (&va)[4], int rowb,
+                                              int qb, const float (&vb)[4], int wm, int wn, int l31, int h,
+                                              f32x16& acc) {
+  __syncthreads();
+  *reinterpret_cast<f32x4*>(sA + rowa * LDP + qa * 4) = f32x4{va[0], va[1], va[2], va[3]};
+  *reinterpret_cast<f32x4*>(sB + rowb * LDP + qb * 4) = f32x4{vb[0], vb[1], vb[2], vb[3]};
+  __syncthreads();
+  const float* ap = sA + (wm * 32 + l31) * LDP + h * 8;
+  const float* bp = sB + (wn * 32 + l31) * LDP + h * 8;
+  const f32x4 a0 = *reinterpret_cast<const f32x4*>(ap), a1 = *reinterpret_cast<const f32x4*>(ap + 4);
+  const f32x4 b0 = *reinterpret_cast<const f32x4*>(bp), b1 = *reinterpret_cast<const f32x4*>(bp + 4);
+  acc = __builtin_amdgcn_mfma_f32_32x32x2f32(a0.x, b0.x, acc, 0, 0, 0);
+  acc = __builtin_amdgcn_mfma_f32_32x32x2f32(a0.y, b0.y, acc, 0, 0, 0);
+  acc = __builtin_amdgcn_mfma_f32_32x32x2f32(a0.z, b0.z, acc, 0, 0, 0);
+  acc = __builtin_amdgcn_mfma_f32_32x32x2f32(a0.w, b0.w, acc, 0, 0, 0);
+  acc = __builtin_amdgcn_mfma_f32_32x32x2f32(a1.x, b1.x, acc, 0, 0, 0);
+  acc = __builtin_amdgcn_mfma_f32_32x32x2f32(a1.y, b1.y, acc, 0, 0, 0);
+  acc = __builtin_amdgcn_mfma_f32_32x32x2f32(a1.z, b1.z, acc, 0, 0, 0);
+  acc = __builtin_amdgcn_mfma_f32_32x32x2f32(a1.w, b1.w, acc, 0, 0, 0);
+}
+// row of the accumulator's element r (C/D layout of the 32x32 MFMA: column = lane & 31, h = lane >> 5)
+__device__ __forceinline__ int ug_acc_row(int r, int h) { return (r & 3) + 8 * (r >> 2) + 4 * h; }
 
 // Dropout keep decision of element `idx` of ResBlock `block` (rgfm.h: rgfm_unet_dropout_mask).
 __host__ __device__ inline bool ug_keep(uint64_t seed, int block, uint32_t idx, float p) {

@@ -11,6 +11,8 @@
 // The weight gradient's K axis (B*H*W, up to 131 072) is split across workgroups: each writes its own partial slice and
 // ug_reduce_kernel adds the slices in split order, so no float atomics and bitwise-reproducible gradients.  Every
 // other reduction (GroupNorm statistics, dgamma / dbeta, bias, time path) is a fixed-order loop or LDS tree as well.
+// The same kernel knows 4x4 taps (stride 2, pad 1): FlowMatchingModel's ConvTranspose2d(4, 2, 1) layers are the data
+// gradient / forward / weight gradient of that conv with the roles of x and dy exchanged (api_fmnet_train.cpp).
 //
 // GroupNorm + SiLU (+ dropout) of a conv's input is applied by ug_gn_act_kernel into a transient buffer right before
 // the conv that consumes it (and again in the backward): the saved state holds only the pre-norm tensors and the
@@ -23,8 +25,14 @@
 namespace rgfm {
 
 // ------------------------------------------------------------------ implicit GEMM
-// Block tile 64 (M) x 64 (N), K staged 16 at a time; four waves, one 32x32 accumulator each (same LDS layout and k
-// permutation as linear_mfma_kernel).  Each thread stages 4 consecutive k of ONE row of A and ONE row (column) of B.
+// Block tile 64 (M) x 64 (N), K staged 16 at a time; four waves, one 32x32 accumulator each (ug_mfma_chunk,
+// train_device.h).  Each thread stages 4 consecutive k of ONE row of A and ONE row (column) of B.
+// (ky, kx) of tap tp: 1 tap (pad 0), 3 x 3 or 4 x 4 (pad 1)
+__device__ __forceinline__ void ug_tap(int taps, int tp, int& ky, int& kx) {
+  if (taps == 16) ky = tp >> 2, kx = tp & 3;
+  else if (taps == 9) ky = tp / 3, kx = tp - 3 * (tp / 3);
+  else ky = kx = 0;
+}
 __device__ __forceinline__ void ug_pix(int n, int HW, int W, int& b, int& y, int& x) {
   b = n / HW;
   const int p = n - b * HW;
@@ -41,7 +49,7 @@ __global__ __launch_bounds__(256) void ug_igemm_kernel(UgConv a) {
   const int wm = wave & 1, wn = wave >> 1;
   const int m0 = blockIdx.y * 64, n0 = blockIdx.x * 64;
   const int row = tid >> 2, q = tid & 3;
-  const int taps = a.taps, pad = taps == 9 ? 1 : 0;
+  const int taps = a.taps, pad = taps == 1 ? 0 : 1;
   const int HWo = a.Ho * a.Wo, HWc = a.Hc * a.Wc, HWs = a.Hs * a.Ws;
   int M, N, K;
   if (OP == 0) M = a.Cout, N = a.B * HWo, K = a.Cin * taps;
@@ -58,8 +66,7 @@ __global__ __launch_bounds__(256) void ug_igemm_kernel(UgConv a) {
   if (OP == 2 && bn < N) {
     wci = bn / taps;
     const int tp = bn - wci * taps;
-    wky = tp / 3, wkx = tp - 3 * (tp / 3);
-    if (taps == 1) wky = wkx = 0;
+    ug_tap(taps, tp, wky, wkx);
   }
   f32x16 acc;
 #pragma unroll
@@ -75,8 +82,8 @@ __global__ __launch_bounds__(256) void ug_igemm_kernel(UgConv a) {
           if (am < M) x = a.w[(size_t)am * K + k];
           if (bn < N) {
             const int ci = k / taps, tp = k - ci * taps;
-            int ky = tp / 3, kx = tp - 3 * (tp / 3);
-            if (taps == 1) ky = kx = 0;
+            int ky, kx;
+            ug_tap(taps, tp, ky, kx);
             const int cy = py * a.stride - pad + ky, cx = px * a.stride - pad + kx;
             if (cy >= 0 && cy < a.Hc && cx >= 0 && cx < a.Wc) {
               const int sy = a.up ? cy >> 1 : cy, sx = a.up ? cx >> 1 : cx;
@@ -87,8 +94,8 @@ __global__ __launch_bounds__(256) void ug_igemm_kernel(UgConv a) {
           const int co = k / taps, tp = k - co * taps;
           if (am < M) x = a.w[((size_t)co * a.Cin + am) * taps + tp];
           if (bn < N) {
-            int ky = tp / 3, kx = tp - 3 * (tp / 3);
-            if (taps == 1) ky = kx = 0;
+            int ky, kx;
+            ug_tap(taps, tp, ky, kx);
             const int ny = py + pad - ky, nx = px + pad - kx;  // = oy * stride
             if (ny >= 0 && nx >= 0) {
               const int oy = ny / a.stride, ox = nx / a.stride;
@@ -111,22 +118,7 @@ __global__ __launch_bounds__(256) void ug_igemm_kernel(UgConv a) {
       }
       va[j] = x, vb[j] = y;
     }
-    __syncthreads();
-    *reinterpret_cast<f32x4*>(sA + row * LDP + q * 4) = f32x4{va[0], va[1], va[2], va[3]};
-    *reinterpret_cast<f32x4*>(sB + row * LDP + q * 4) = f32x4{vb[0], vb[1], vb[2], vb[3]};
-    __syncthreads();
-    const float* ap = sA + (wm * 32 + l31) * LDP + h * 8;
-    const float* bp = sB + (wn * 32 + l31) * LDP + h * 8;
-    const f32x4 a0 = *reinterpret_cast<const f32x4*>(ap), a1 = *reinterpret_cast<const f32x4*>(ap + 4);
-    const f32x4 b0 = *reinterpret_cast<const f32x4*>(bp), b1 = *reinterpret_cast<const f32x4*>(bp + 4);
-    acc = __builtin_amdgcn_mfma_f32_32x32x2f32(a0.x, b0.x, acc, 0, 0, 0);
-    acc = __builtin_amdgcn_mfma_f32_32x32x2f32(a0.y, b0.y, acc, 0, 0, 0);
-    acc = __builtin_amdgcn_mfma_f32_32x32x2f32(a0.z, b0.z, acc, 0, 0, 0);
-    acc = __builtin_amdgcn_mfma_f32_32x32x2f32(a0.w, b0.w, acc, 0, 0, 0);
-    acc = __builtin_amdgcn_mfma_f32_32x32x2f32(a1.x, b1.x, acc, 0, 0, 0);
-    acc = __builtin_amdgcn_mfma_f32_32x32x2f32(a1.y, b1.y, acc, 0, 0, 0);
-    acc = __builtin_amdgcn_mfma_f32_32x32x2f32(a1.z, b1.z, acc, 0, 0, 0);
-    acc = __builtin_amdgcn_mfma_f32_32x32x2f32(a1.w, b1.w, acc, 0, 0, 0);
+    ug_mfma_chunk(sA, sB, row, q, va, row, q, vb, wm, wn, l31, h, acc);
   }
   // C/D: column n = lane & 31 (consecutive lanes -> consecutive pixels), row m = (r & 3) + 8 (r >> 2) + 4 h
   const int n = n0 + wn * 32 + l31;
@@ -150,7 +142,8 @@ __global__ __launch_bounds__(256) void ug_igemm_kernel(UgConv a) {
     if (m >= M) continue;
     if (OP == 0) {
       const size_t o = ((size_t)b * a.Cout + m) * HWo + pix;
-      float v = acc[r] + a.bias[m];
+      float v = acc[r];
+      if (a.bias) v += a.bias[m];
       if (a.temb) v += a.temb[(size_t)b * a.Cout + m];
       if (a.res) v += a.res[o];
       a.out[o] = v;
@@ -161,7 +154,8 @@ __global__ __launch_bounds__(256) void ug_igemm_kernel(UgConv a) {
       int accum;
       if (m < a.C0) dst = a.out, o = ((size_t)b * a.C0 + m) * HWc + pix, accum = a.acc0;
       else dst = a.out1, o = ((size_t)b * (a.Cin - a.C0) + (m - a.C0)) * HWc + pix, accum = a.acc1;
-      dst[o] = accum ? dst[o] + acc[r] : acc[r];
+      const float v = a.dbias ? acc[r] + a.dbias[m] : acc[r];
+      dst[o] = accum ? dst[o] + v : v;
     }
   }
 }

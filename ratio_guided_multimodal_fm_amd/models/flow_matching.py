@@ -5,7 +5,9 @@ Parameter container with the reference's constructor arguments, ``state_dict`` k
 reference checkpoints load); ``forward`` and the samplers run in librgfm_hip.so (``rgfm_fmnet_*``):
 the stride-2 convs and both ConvTranspose2d(k4,s2,p1) on the MFMA implicit-GEMM conv kernel (the
 transposed convs as four 2x2-tap output-parity classes), the 12544<->256/384 Linears on the MFMA
-linear kernels with their weights re-indexed to NHWC once at handle creation.  No PyTorch compute path.
+linear kernels with their weights re-indexed to NHWC once at handle creation.  ``forward_train`` is the
+differentiable forward for training: exact fp32 on the matrix cores with a hand-written HIP backward
+(``rgfm_fmnet_forward_train`` / ``rgfm_fmnet_backward``).  No PyTorch compute path.
 """
 import torch.nn as nn
 
@@ -56,3 +58,8 @@ class FlowMatchingModel(nn.Module):
     def forward(self, x_t, t):
         """v_t [B,1,28,28] = model(x_t [B,1,28,28], t [B] or [1])  (reference :153-173)."""
         return self._engine.forward(x_t, t)
+
+    def forward_train(self, x_t, t):
+        """v_t = model(x_t, t), differentiable w.r.t. x_t and the parameters through the HIP backward
+        (rgfm_fmnet_forward_train / rgfm_fmnet_backward).  The net has no Dropout: any module mode."""
+        return self._engine.forward_train(x_t, t)

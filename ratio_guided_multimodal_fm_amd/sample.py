@@ -56,9 +56,11 @@ def main(argv=None):
     fm_x, fm_y = build_flow_models(args.model, device)
     path_x = get_checkpoint_path('flow', 'x', None, 'best')
     path_y = get_checkpoint_path('flow', 'y', args.transform_type, 'best')
-    for path in (path_x, path_y):
+    preset = 'original' if args.model == 'original' else 'unet28'
+    for path, flags in ((path_x, '--modality x'), (path_y, f'--modality y --transform_type {args.transform_type}')):
         if not os.path.exists(path):
-            print(f"ERROR: FM checkpoint not found: {path} (train it with the reference: python src/train_flow.py)")
+            print(f"ERROR: FM checkpoint not found: {path} (train it: python -m ratio_guided_multimodal_fm_amd.train_flow "
+                  f"--preset {preset} {flags} --data <images.npy>)")
             return 1
     load_checkpoint(fm_x, path_x, device)
     load_checkpoint(fm_y, path_y, device)

@@ -1,11 +1,17 @@
-"""Train a velocity U-Net with conditional flow matching on the HIP backward.
+"""Train a velocity net with conditional flow matching on the HIP backward.
 
     python -m ratio_guided_multimodal_fm_amd.train_flow --preset svhn --data svhn_train.npy
+    python -m ratio_guided_multimodal_fm_amd.train_flow --preset original --modality x --data mnist_x.npy
 
 Mirrors the reference trainers (src/train_flow_svhn.py, src/train_flow_mnist32.py, src/train_flow.py): same
 arguments and defaults, Adam, best / every-N checkpoints {'epoch', 'model_state_dict', 'optimizer_state_dict',
 'best_loss'} under the reference's names, early stopping.  The data is one tensor [N, C, H, W] in a .npy or .pt
 file, already in the reference's value range (no dataset download here).
+
+The 28x28 presets (``original``: FlowMatchingModel, the reference's ``--model original``; ``unet28``) take the
+reference's ``--modality {x,y}`` and ``--transform_type``: they only select the checkpoint stem, as the reference's
+``get_checkpoint_path('flow', modality, transform, ...)`` does -- ``flow_x_*`` / ``flow_y_<transform>_*``, the names
+sample.py and evaluate.py load.  ``original`` requires ``--modality``; without it ``unet28`` writes ``flow_unet28_*``.
 """
 import argparse
 import os
@@ -13,7 +19,7 @@ import os
 import numpy as np
 import torch
 
-from .models import FlowMatchingUNet, FlowMatchingUNetMNIST, FlowMatchingUNetSVHN
+from .models import FlowMatchingModel, FlowMatchingUNet, FlowMatchingUNetMNIST, FlowMatchingUNetSVHN
 from .utils import set_seed
 from .utils.flow_utils import CFMSchedule, train_flow_matching_epoch
 
@@ -22,7 +28,17 @@ PRESETS = {
     'mnist32': (lambda: FlowMatchingUNetMNIST(32), (1, 32, 32), 'flow_mnist32'),
     'svhn': (FlowMatchingUNetSVHN, (3, 32, 32), 'flow_svhn'),
     'unet28': (FlowMatchingUNet, (1, 28, 28), 'flow_unet28'),
+    'original': (FlowMatchingModel, (1, 28, 28), None),  # (stem from --modality: checkpoint_stem)
 }
+MODALITY_PRESETS = ('original', 'unet28')
+
+
+def checkpoint_stem(preset, modality=None, transform_type='rotate90'):
+    """Checkpoint stem of a run: the preset's own, or -- 28x28 presets with --modality -- the reference's
+    get_checkpoint_path('flow', modality, transform): 'flow_x' / 'flow_y_<transform>'."""
+    if modality is None:
+        return PRESETS[preset][2]
+    return 'flow_x' if modality == 'x' else f'flow_y_{transform_type}'
 
 
 def parse_args(argv=None):
@@ -38,7 +54,16 @@ def parse_args(argv=None):
     p.add_argument('--seed', type=int, default=42)
     p.add_argument('--resume', type=str, default=None, help='checkpoint to resume from')
     p.add_argument('--out_dir', type=str, default='checkpoints')
-    return p.parse_args(argv)
+    p.add_argument('--modality', type=str, default=None, choices=['x', 'y'],
+                   help='28x28 presets: which modality the data is (selects the checkpoint name)')
+    p.add_argument('--transform_type', type=str, default='rotate90', help='names the y checkpoint')
+    args = p.parse_args(argv)
+    if args.modality is not None and args.preset not in MODALITY_PRESETS:
+        p.error(f"--modality applies to the presets {', '.join(MODALITY_PRESETS)}")
+    if args.preset == 'original' and args.modality is None:
+        p.error("--preset original requires --modality {x,y}")
+    args.stem = checkpoint_stem(args.preset, args.modality, args.transform_type)
+    return args
 
 
 def load_data(path, shape):
@@ -64,7 +89,8 @@ def checkpoint(epoch, model, optimizer, best_loss):
 def main(argv=None):
     args = parse_args(argv)
     set_seed(args.seed)
-    ctor, shape, stem = PRESETS[args.preset]
+    ctor, shape, _ = PRESETS[args.preset]
+    stem = args.stem
     device = torch.device(args.device)
     data = load_data(args.data, shape)
     model = ctor().to(device)
