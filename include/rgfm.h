@@ -170,11 +170,22 @@ int rgfm_unet_update_params(rgfm_unet* h, const float* params_dev, size_t n_floa
 
 /* ------------------------------------------------------------------------
  * Density-ratio estimators.  Replaces RatioEstimatorMNISTSVHN
- * (src/models/ratio_flexible.py:305-385) and RatioEstimator
- * (src/models/ratio_estimator.py:96-191), eval mode.
+ * (src/models/ratio_flexible.py:305-385), RatioEstimator
+ * (src/models/ratio_estimator.py:96-191) and FlexibleRatioEstimator
+ * (src/models/ratio_flexible.py:69-154), eval mode.
  * ---------------------------------------------------------------------- */
 #define RGFM_RATIO_MNIST_SVHN 0 /* x[N,1,32,32], y[N,3,32,32], BatchNorm encoders */
 #define RGFM_RATIO_MNIST28 1    /* x[N,1,28,28], y[N,1,28,28], GroupNorm encoders */
+/* FlexibleRatioEstimator (rgfm_ratio_flex_desc / rgfm_ratio_flex_create): x[N,x_channels,x_size,x_size],
+ * y[N,y_channels,y_size,y_size].  Two GroupNorm ImageEncoders
+ * (ratio_flexible.py:13-66: convs of 32, 64, 128, 128 channels, a floor 2x2 max-pool behind the first three, a global
+ * average pool, Linear(128, feature_dim)) and the two-hidden-layer score MLP; parameter blob in the order of
+ * ratio_flexible.py:22-40 and :100-114.  The module itself is size-agnostic; a handle is built for ONE pair of sizes
+ * (the rasters, tilings and workspaces follow from them) -- keep one handle per pair of sizes in use.  Channels 1..4;
+ * sizes 8..64 (below 8 the third pool would produce an empty map; 64 is the largest raster the conv kernels tile).
+ * The two sizes are independent, the images square.  Every rgfm_ratio_* entry point works on such a handle as on
+ * the other kinds. */
+#define RGFM_RATIO_FLEXIBLE 2
 
 #define RGFM_LOSS_DISC 0
 #define RGFM_LOSS_RULSIF 1
@@ -190,6 +201,18 @@ typedef struct rgfm_ratio_desc {
   int32_t loss_type;   /* RGFM_LOSS_*       */
 } rgfm_ratio_desc;
 
+/* Descriptor of kind RGFM_RATIO_FLEXIBLE; rgfm_ratio_flex_create returns the same rgfm_ratio* as rgfm_ratio_create
+ * (which rejects that kind: its descriptor has no geometry).  Added functions only: the ABI version is unchanged. */
+typedef struct rgfm_ratio_flex_desc {
+  int32_t feature_dim; /* multiple of 64, <= 512  */
+  int32_t hidden_dim;  /* multiple of 128, <= 1024 */
+  int32_t loss_type;   /* RGFM_LOSS_*       */
+  int32_t x_channels;  /* 1..4              */
+  int32_t y_channels;  /* 1..4              */
+  int32_t x_size;      /* 8..64             */
+  int32_t y_size;      /* 8..64             */
+} rgfm_ratio_flex_desc;
+
 typedef struct rgfm_ratio rgfm_ratio;
 
 int rgfm_ratio_param_floats(const rgfm_ratio_desc* desc, size_t* n_floats);
@@ -197,6 +220,9 @@ int rgfm_ratio_param_floats(const rgfm_ratio_desc* desc, size_t* n_floats);
  * carried as one fp32 each (value ignored) so that offsets follow the keys. */
 int rgfm_ratio_create(const rgfm_ratio_desc* desc, const float* params_dev, size_t n_floats,
                       rgfm_stream_t stream, rgfm_ratio** out);
+int rgfm_ratio_flex_param_floats(const rgfm_ratio_flex_desc* desc, size_t* n_floats);
+int rgfm_ratio_flex_create(const rgfm_ratio_flex_desc* desc, const float* params_dev, size_t n_floats,
+                           rgfm_stream_t stream, rgfm_ratio** out);
 void rgfm_ratio_destroy(rgfm_ratio* h);
 int rgfm_ratio_workspace_bytes(const rgfm_ratio* h, int n, size_t* bytes);
 /* out[n] per `what` (RGFM_RATIO_OUT_*): forward ratio_flexible.py:347-364,
@@ -207,13 +233,14 @@ int rgfm_ratio_eval(rgfm_ratio* h, const float* x, const float* y, float* out, i
 /* Gradient of the log-ratio, d log_ratio(x, y) / d(x, y): what torch.autograd.grad(model.log_ratio(x, y).sum(),
  * (x, y)) returns for the reference module in eval mode (ratio_flexible.py:347-385, ratio_estimator.py:137-191;
  * hand-written reverse pass).  RGFM_RATIO_MNIST_SVHN: gx[n,1,32,32], gy[n,3,32,32]; RGFM_RATIO_MNIST28: gx, gy
- * [n,1,28,28]; log_ratio_out (optional) [n]. */
+ * [n,1,28,28]; RGFM_RATIO_FLEXIBLE: gx[n,x_channels,x_size,x_size], gy[n,y_channels,y_size,y_size]; log_ratio_out
+ * (optional) [n]. */
 int rgfm_ratio_grad_workspace_bytes(const rgfm_ratio* h, int n, size_t* bytes);
 int rgfm_ratio_grad_log_ratio(rgfm_ratio* h, const float* x, const float* y, float* gx, float* gy,
                               float* log_ratio_out, int n, void* ws, size_t ws_bytes, rgfm_stream_t stream);
 
 /* Training pass of the ratio estimators (exact fp32 arithmetic on v_mfma_f32_32x32x2_f32, NCHW fp32 tensors,
- * stream-ordered, caller-owned workspace, nothing allocated or synchronised inside a call; both kinds).
+ * stream-ordered, caller-owned workspace, nothing allocated or synchronised inside a call; every kind).
  *
  * rgfm_ratio_forward_train writes score_out[n] = forward(x, y) and leaves in `ws` what rgfm_ratio_backward needs; `ws`
  * (rgfm_ratio_train_workspace_bytes(h, n)) must stay untouched between the two calls.
@@ -282,7 +309,8 @@ int rgfm_sample_pair(rgfm_unet* hx, rgfm_unet* hy, float* x_inout, float* y_inou
  * (reference README.md:159-164, "v_guided = v_ind + gamma * grad log r(x_t, y_t)").  The reference ships no code
  * for this mode, so the composition above is this library's reading of that line; the gradient itself is the
  * autograd gradient of the reference module (rgfm_ratio_grad_log_ratio).  The pair must be the estimator's:
- * 1x32x32 + 3x32x32 (RGFM_RATIO_MNIST_SVHN) or 1x28x28 + 1x28x28 (RGFM_RATIO_MNIST28). */
+ * 1x32x32 + 3x32x32 (RGFM_RATIO_MNIST_SVHN), 1x28x28 + 1x28x28 (RGFM_RATIO_MNIST28), or the descriptor's
+ * (x_channels, x_size) + (y_channels, y_size) (RGFM_RATIO_FLEXIBLE). */
 int rgfm_sample_pair_grad_workspace_bytes(const rgfm_unet* hx, const rgfm_unet* hy, const rgfm_ratio* hr,
                                           int batch, size_t* bytes);
 int rgfm_sample_pair_grad(rgfm_unet* hx, rgfm_unet* hy, rgfm_ratio* hr, float* x_inout, float* y_inout,

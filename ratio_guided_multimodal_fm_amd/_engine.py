@@ -13,7 +13,7 @@ import torch
 from . import _lib
 
 _LOSS = {"disc": 0, "rulsif": 1}
-_RATIO_KIND = {"mnist_svhn": 0, "mnist28": 1}
+_RATIO_KIND = {"mnist_svhn": 0, "mnist28": 1, "flexible": 2}
 _RATIO_OUT = {"score": 0, "log_ratio": 1, "ratio": 2}
 
 
@@ -494,6 +494,8 @@ class _FmNetTrainFn(torch.autograd.Function):
 
 
 class RatioEngine(_EngineBase):
+    PARAM_FLOATS, CREATE = "rgfm_ratio_param_floats", "rgfm_ratio_create"
+
     def __init__(self, module, kind):
         super().__init__(module)
         self.kind = kind
@@ -531,20 +533,27 @@ class RatioEngine(_EngineBase):
             self._destroy()
         d = self.desc()
         n = ctypes.c_size_t()
-        _lib.check(L.rgfm_ratio_param_floats(ctypes.byref(d), ctypes.byref(n)))
+        _lib.check(getattr(L, self.PARAM_FLOATS)(ctypes.byref(d), ctypes.byref(n)))
         blob = self._blob_from(sd, device)
         if blob.numel() != n.value:
             raise _lib.RgfmError(f"parameter blob has {blob.numel()} floats, library expects {n.value}")
         h = ctypes.c_void_p()
         with torch.cuda.device(device):
-            _lib.check(L.rgfm_ratio_create(ctypes.byref(d), _ptr(blob), blob.numel(), _stream(device),
-                                           ctypes.byref(h)))
+            _lib.check(getattr(L, self.CREATE)(ctypes.byref(d), _ptr(blob), blob.numel(), _stream(device),
+                                               ctypes.byref(h)))
         self._handle, self._key, self._blob = h, key, blob
         return h
 
     def _destroy(self):
         _lib.lib().rgfm_ratio_destroy(self._handle)
         self._handle = None
+
+    def bind(self, x, y):
+        """Select the handle that serves this pair of inputs (one geometry per fixed kind: nothing to select)."""
+
+    def owns(self, handle):
+        """Is `handle` (as handle() returned it) still alive in this engine?"""
+        return self._handle is handle
 
     # ---- training -----------------------------------------------------
     def image_shapes(self):
@@ -558,6 +567,7 @@ class RatioEngine(_EngineBase):
 
     def _check_pair(self, x, y):
         _require_hip(x, y)
+        self.bind(x, y)
         sx, sy = self.image_shapes()
         if x.dim() != 4 or y.dim() != 4 or tuple(x.shape[1:]) != sx or tuple(y.shape[1:]) != sy or x.shape[0] != y.shape[0]:
             raise _lib.RgfmError(f"expected x of shape [B,{sx[0]},{sx[1]},{sx[2]}] and y of shape [B,{sy[0]},{sy[1]},{sy[2]}], got "
@@ -587,14 +597,17 @@ class RatioEngine(_EngineBase):
         ws, n = (self._last_train[0](), self._last_train[1]) if getattr(self, "_last_train", None) else (None, 0)
         if ws is None:
             raise _lib.RgfmError("no saved state: call pool_choices() between forward_train and its backward")
+        h, geometry = self._last_train[2], self._last_train[3]
+        if not self.owns(h):
+            raise _lib.RgfmError("the module's handle was re-created since that forward_train")
         dev = ws.device
         out = []
         with torch.cuda.device(dev):
-            for e, geo in enumerate(self.pool_geometry()):
+            for e, geo in enumerate(geometry):
                 out.append([])
                 for i, (C, S) in enumerate(geo):
                     t = torch.empty(n, C, S, S, device=dev)
-                    _lib.check(_lib.lib().rgfm_ratio_pool_choice(self._handle, _ptr(ws), e, i, n, _ptr(t)))
+                    _lib.check(_lib.lib().rgfm_ratio_pool_choice(h, _ptr(ws), e, i, n, _ptr(t)))
                     out[-1].append(t)
         return out
 
@@ -604,6 +617,7 @@ class RatioEngine(_EngineBase):
         _require_hip(x, y)
         if x.shape[0] != y.shape[0]:
             raise _lib.RgfmError("x and y must have the same batch size")
+        self.bind(x, y)
         n = x.shape[0]
         x, y = x.contiguous(), y.contiguous()
         out = torch.empty(n, device=x.device, dtype=torch.float32)
@@ -628,7 +642,8 @@ class RatioEngine(_EngineBase):
         _require_hip(x, y)
         if x.shape[0] != y.shape[0]:
             raise _lib.RgfmError("x and y must have the same batch size")
-        sx, sy = ((1, 32, 32), (3, 32, 32)) if self.kind == "mnist_svhn" else ((1, 28, 28), (1, 28, 28))
+        self.bind(x, y)
+        sx, sy = self.image_shapes()
         if x.dim() != 4 or y.dim() != 4 or tuple(x.shape[1:]) != sx or tuple(y.shape[1:]) != sy:
             raise _lib.RgfmError(f"expected x of shape [B,{sx[0]},{sx[1]},{sx[2]}] and y of shape [B,{sy[0]},{sy[1]},{sy[2]}], got "
                                  f"{tuple(x.shape)} and {tuple(y.shape)}")
@@ -648,6 +663,68 @@ class RatioEngine(_EngineBase):
             _lib.check(L.rgfm_ratio_grad_log_ratio(h, _ptr(x), _ptr(y), _ptr(gx), _ptr(gy), _ptr(lr), n, _ptr(ws),
                                                    nb.value, _stream(dev)))
         return gx, gy, lr
+
+
+class FlexibleRatioEngine(RatioEngine):
+    """RatioEngine of FlexibleRatioEstimator.  The module is size-agnostic, a device handle is not (its rasters, tilings
+    and workspaces follow from the image sizes): bind() reads (x_size, y_size) from the inputs of a call and handle()
+    serves the handle of the bound pair, keeping one per pair seen -- alternating between sizes re-creates nothing."""
+    PARAM_FLOATS, CREATE = "rgfm_ratio_flex_param_floats", "rgfm_ratio_flex_create"
+
+    def __init__(self, module):
+        super().__init__(module, "flexible")
+        self._sizes = None
+        self._cache = {}  # (x_size, y_size) -> (handle, key, blob) of every pair but the bound one
+
+    def bind(self, x, y):
+        m = self._module()
+        for name, t, c in (("x", x, m.x_channels), ("y", y, m.y_channels)):
+            if t.dim() != 4 or t.shape[1] != c or t.shape[2] != t.shape[3]:
+                raise _lib.RgfmError(f"expected {name} of shape [B,{c},S,S] (square images), got {tuple(t.shape)}")
+        sizes = (int(x.shape[2]), int(y.shape[2]))
+        if sizes != self._sizes:
+            if self._sizes is not None and self._handle is not None:
+                self._cache[self._sizes] = (self._handle, self._key, self._blob)
+            self._handle, self._key, self._blob = self._cache.pop(sizes, (None, None, None))
+            self._sizes = sizes
+        return sizes
+
+    def desc(self):
+        if self._sizes is None:
+            raise _lib.RgfmError("FlexibleRatioEstimator: no image sizes yet (they are read from the inputs of a call)")
+        m = self._module()
+        d = _lib.RatioFlexDesc()
+        d.feature_dim, d.hidden_dim, d.loss_type = m.feature_dim, m.hidden_dim, _LOSS.get(m.loss_type, 0)
+        d.x_channels, d.y_channels = m.x_channels, m.y_channels
+        d.x_size, d.y_size = self._sizes
+        return d
+
+    def owns(self, handle):
+        return self._handle is handle or any(h is handle for h, _, _ in self._cache.values())
+
+    def _destroy(self):
+        # (called for the bound handle when the module's tensors were replaced: the other sizes' handles are as stale)
+        handles = [self._handle] + [h for h, _, _ in self._cache.values()]
+        self._cache = {}
+        self._handle = None
+        for h in handles:
+            if h is not None:
+                _lib.lib().rgfm_ratio_destroy(h)
+
+    def __del__(self):
+        try:
+            self._destroy()
+        except Exception:
+            pass
+
+    def image_shapes(self):
+        m = self._module()
+        sx, sy = self._sizes
+        return (m.x_channels, sx, sx), (m.y_channels, sy, sy)
+
+    def pool_geometry(self):
+        sx, sy = self._sizes
+        return tuple([(32, s // 2), (64, s // 4), (128, s // 8)] for s in (sx, sy))
 
 
 class _RatioTrainFn(torch.autograd.Function):
@@ -692,7 +769,7 @@ class _RatioTrainFn(torch.autograd.Function):
             b.running_var.mul_(1 - mom).add_(st[:, 1], alpha=mom)
             b.num_batches_tracked.add_(1)
         ctx.ws, ctx.nbytes, ctx.h = ws, nb.value, h
-        engine._last_train = (weakref.ref(ws), n)
+        engine._last_train = (weakref.ref(ws), n, h, engine.pool_geometry())
         return out
 
     @staticmethod
@@ -705,7 +782,7 @@ class _RatioTrainFn(torch.autograd.Function):
                     torch.zeros(ctx.shapes[1], device=dev) if need_y else None, None, *[torch.zeros_like(q) for q in params])
         if ctx.ws is None:
             raise _lib.RgfmError("the saved state of this forward_train call is gone (backward ran twice?)")
-        if ctx.engine._handle is not ctx.h:
+        if not ctx.engine.owns(ctx.h):
             raise _lib.RgfmError("the module's handle was re-created between forward_train and backward")
         dscore = dscore.to(torch.float32).contiguous()
         dparams = torch.empty(sum(k for k, _ in ctx.layout), device=dev)
@@ -829,6 +906,7 @@ def sample_pair_grad(fm_x, fm_y, ratio_estimator, x, y, num_steps, gamma, step_b
     if not (isinstance(fm_x._engine, UNetEngine) and isinstance(fm_y._engine, UNetEngine)):
         raise _lib.RgfmError("gradient log-ratio guidance needs two U-Net velocity nets")
     _require_hip(x, y)
+    ratio_estimator._engine.bind(x, y)
     if not (x.is_contiguous() and y.is_contiguous()):
         raise _lib.RgfmError("x and y must be contiguous (they are updated in place)")
     if step_end is None:

@@ -28,6 +28,11 @@ class RatioDesc(ctypes.Structure):
                 ("loss_type", c_int32)]
 
 
+class RatioFlexDesc(ctypes.Structure):
+    _fields_ = [("feature_dim", c_int32), ("hidden_dim", c_int32), ("loss_type", c_int32),
+                ("x_channels", c_int32), ("y_channels", c_int32), ("x_size", c_int32), ("y_size", c_int32)]
+
+
 class FmNetDesc(ctypes.Structure):
     _fields_ = [("img_channels", c_int32), ("feature_dim", c_int32), ("time_emb_dim", c_int32)]
 
@@ -56,6 +61,8 @@ SIGNATURES = {
     "rgfm_unet_update_params": (c_int, [c_void_p, c_void_p, c_size_t, c_void_p]),
     "rgfm_ratio_param_floats": (c_int, [P(RatioDesc), P(c_size_t)]),
     "rgfm_ratio_create": (c_int, [P(RatioDesc), c_void_p, c_size_t, c_void_p, P(c_void_p)]),
+    "rgfm_ratio_flex_param_floats": (c_int, [P(RatioFlexDesc), P(c_size_t)]),
+    "rgfm_ratio_flex_create": (c_int, [P(RatioFlexDesc), c_void_p, c_size_t, c_void_p, P(c_void_p)]),
     "rgfm_ratio_destroy": (None, [c_void_p]),
     "rgfm_ratio_workspace_bytes": (c_int, [c_void_p, c_int, P(c_size_t)]),
     "rgfm_ratio_eval": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_void_p,

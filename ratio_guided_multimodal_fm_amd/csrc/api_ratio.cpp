@@ -4,8 +4,9 @@
 namespace {
 
 // Parameter order of RatioEstimatorMNISTSVHN (src/models/ratio_flexible.py:191-208,
-// :241-269, :327-345) and RatioEstimator (src/models/ratio_estimator.py:43-65, :121-135).
-size_t plan_ratio(const rgfm_ratio_desc& d, rgfm_ratio* h) {
+// :241-269, :327-345), RatioEstimator (src/models/ratio_estimator.py:43-65, :121-135) and FlexibleRatioEstimator
+// (src/models/ratio_flexible.py:22-40, :100-114; `geom` gives its channels and sizes, unused by the other kinds).
+size_t plan_ratio(const rgfm_ratio_desc& d, const rgfm_ratio_flex_desc& geom, rgfm_ratio* h) {
   Planner P;
   Cursor &c = P.raw, &pk = P.pk, bn, gw;
   const int F = d.feature_dim, Hd = d.hidden_dim;
@@ -49,6 +50,10 @@ size_t plan_ratio(const rgfm_ratio_desc& d, rgfm_ratio* h) {
     ex = encoder(1, 32, {32, 64, 128, 128}, {1, 1, 1, 0}, true);
     ey = encoder(3, 32, {64, 64, 128, 128, 256, 256, 256, 256}, {0, 1, 0, 1, 0, 1, 0, 1}, true);
     dims = {2 * F, Hd, Hd, Hd / 2};
+  } else if (d.kind == RGFM_RATIO_FLEXIBLE) {
+    ex = encoder(geom.x_channels, geom.x_size, {32, 64, 128, 128}, {1, 1, 1, 0}, false);
+    ey = encoder(geom.y_channels, geom.y_size, {32, 64, 128, 128}, {1, 1, 1, 0}, false);
+    dims = {2 * F, Hd, Hd / 2};
   } else {
     ex = encoder(1, 28, {32, 64, 128, 128}, {1, 1, 1, 0}, false);
     ey = encoder(1, 28, {32, 64, 128, 128}, {1, 1, 1, 0}, false);
@@ -70,16 +75,52 @@ size_t plan_ratio(const rgfm_ratio_desc& d, rgfm_ratio* h) {
     h->n_bn = bn.off;
     h->g_zeros = gw.take(1024);
     h->n_gradw = gw.off;
+    h->max_c = 0, h->n_wtmp = 1;
+    for (const auto* e : {&h->ex, &h->ey})
+      for (size_t i = 0; i < e->convs.size(); ++i) {
+        const ConvW& w = e->convs[i].w;
+        h->max_c = std::max(h->max_c, w.cout);
+        if (i > 0) h->n_wtmp = std::max(h->n_wtmp, (size_t)w.cout * w.cin * 9);
+      }
   }
   return c.off;
 }
 
-int check_ratio_desc(const rgfm_ratio_desc* d) {
-  if (!d) return fail(RGFM_EINVAL, "null descriptor");
-  if (d->kind != RGFM_RATIO_MNIST_SVHN && d->kind != RGFM_RATIO_MNIST28) return fail(RGFM_EINVAL, "unknown ratio kind");
+int check_ratio_dims(const rgfm_ratio_desc* d) {
   if (d->feature_dim % 64 || d->hidden_dim % 128 || d->feature_dim > 512 || d->hidden_dim > 1024)
     return fail(RGFM_EINVAL, "feature_dim must be a multiple of 64 (<=512), hidden_dim of 128 (<=1024)");
   if (d->loss_type != RGFM_LOSS_DISC && d->loss_type != RGFM_LOSS_RULSIF) return fail(RGFM_EINVAL, "unknown loss_type");
+  return RGFM_OK;
+}
+
+int check_ratio_desc(const rgfm_ratio_desc* d) {
+  if (!d) return fail(RGFM_EINVAL, "null descriptor");
+  if (d->kind == RGFM_RATIO_FLEXIBLE)
+    return fail(RGFM_EINVAL, "RGFM_RATIO_FLEXIBLE takes its geometry from rgfm_ratio_flex_desc: use rgfm_ratio_flex_create");
+  if (d->kind != RGFM_RATIO_MNIST_SVHN && d->kind != RGFM_RATIO_MNIST28) return fail(RGFM_EINVAL, "unknown ratio kind");
+  return check_ratio_dims(d);
+}
+
+// Geometry rules of the flexible kind.  Channels 1..4: conv_in stages one float4 per pixel.  Size >= 8: three floor
+// 2x2 max-pools must leave a pixel for conv4.  Size <= 64: every raster S, S/2, S/4, S/8 must tile -- make_geom cuts a
+// raster into 256-pixel tiles of whole rows, and the convs hold a tile's zero-padded halo (at most 448 pixels) in LDS.
+int check_ratio_flex_desc(const rgfm_ratio_flex_desc* f, rgfm_ratio_desc* d) {
+  if (!f) return fail(RGFM_EINVAL, "null descriptor");
+  d->kind = RGFM_RATIO_FLEXIBLE, d->feature_dim = f->feature_dim, d->hidden_dim = f->hidden_dim, d->loss_type = f->loss_type;
+  if (int rc = check_ratio_dims(d)) return rc;
+  const int chans[2] = {f->x_channels, f->y_channels}, sizes[2] = {f->x_size, f->y_size};
+  const char* cn[2] = {"x_channels", "y_channels"};
+  const char* sn[2] = {"x_size", "y_size"};
+  for (int k = 0; k < 2; ++k) {
+    if (chans[k] < 1 || chans[k] > 4) return fail(RGFM_EINVAL, "%s must be in 1..4, got %d", cn[k], chans[k]);
+    if (sizes[k] < 8) return fail(RGFM_EINVAL, "%s must be at least 8 (three 2x2 max-pools), got %d", sn[k], sizes[k]);
+    if (sizes[k] > 64) return fail(RGFM_EINVAL, "%s = %d cannot be tiled: at most 64", sn[k], sizes[k]);
+    for (int S = sizes[k], l = 0; l < 4; ++l, S /= 2) {
+      const TileGeom g = make_geom(S, S);
+      if (g.spt * (g.th + 2) * (g.W + 2) > 448)
+        return fail(RGFM_EINVAL, "%s = %d cannot be tiled: the %dx%d raster's halo exceeds a tile", sn[k], sizes[k], S, S);
+    }
+  }
   return RGFM_OK;
 }
 
@@ -92,7 +133,7 @@ int pack_ratio(rgfm_ratio* h, hipStream_t s) {
     for (size_t i = 0; i < e->convs.size(); ++i) {
       const auto& cv = e->convs[i];
       if (i > 0) launch_pack_conv(h->params + cv.w.w_raw, h->packed + cv.w.w_pk, cv.w.cout, cv.w.cin, 9, nt32_of(cv.w.cout), s);
-      if (h->d.kind == RGFM_RATIO_MNIST_SVHN)
+      if (!h->gn_encoders())
         launch_bn_fold(h->params + cv.nw, h->params + cv.nb, h->params + cv.rm, h->params + cv.rv,
                        h->bn + cv.bn_scale, h->bn + cv.bn_shift, cv.w.cout, s);
     }
@@ -127,7 +168,7 @@ struct RatioRun {
 
   // one encoder: image NCHW -> features written at feat[:, col0 : col0+F] (row stride 2F)
   void encode(const rgfm_ratio::Encoder& e, const float* img, float* feat, int col0) {
-    const bool gn = h->d.kind == RGFM_RATIO_MNIST28;
+    const bool gn = h->gn_encoders();
     const int F = h->d.feature_dim;
     int S = e.size;
     Tensor cur;
@@ -220,20 +261,29 @@ extern "C" int rgfm_ratio_param_floats(const rgfm_ratio_desc* desc, size_t* n_fl
   int rc = check_ratio_desc(desc);
   if (rc) return rc;
   if (!n_floats) return fail(RGFM_EINVAL, "null output");
-  *n_floats = plan_ratio(*desc, nullptr);
+  *n_floats = plan_ratio(*desc, rgfm_ratio_flex_desc{}, nullptr);
   return RGFM_OK;
 }
 
-extern "C" int rgfm_ratio_create(const rgfm_ratio_desc* desc, const float* params_dev, size_t n_floats,
-                                 rgfm_stream_t stream, rgfm_ratio** out) {
-  int rc = check_ratio_desc(desc);
+extern "C" int rgfm_ratio_flex_param_floats(const rgfm_ratio_flex_desc* desc, size_t* n_floats) {
+  rgfm_ratio_desc d{};
+  int rc = check_ratio_flex_desc(desc, &d);
   if (rc) return rc;
+  if (!n_floats) return fail(RGFM_EINVAL, "null output");
+  *n_floats = plan_ratio(d, *desc, nullptr);
+  return RGFM_OK;
+}
+
+namespace {
+int create_ratio(const rgfm_ratio_desc& d, const rgfm_ratio_flex_desc& geom, const float* params_dev, size_t n_floats,
+                 rgfm_stream_t stream, rgfm_ratio** out) {
+  int rc;
   if (!params_dev || !out) return fail(RGFM_EINVAL, "null argument");
   if ((rc = ensure_init())) return rc;
   hipStream_t s = (hipStream_t)stream;
   rgfm_ratio* h = new rgfm_ratio();
-  h->d = *desc;
-  if (plan_ratio(*desc, h) != n_floats) {
+  h->d = d, h->geom = geom;
+  if (plan_ratio(d, geom, h) != n_floats) {
     const size_t want = h->n_params;
     delete h;
     return fail(RGFM_EINVAL, "parameter blob has %zu floats, architecture needs %zu", n_floats, want);
@@ -245,10 +295,24 @@ extern "C" int rgfm_ratio_create(const rgfm_ratio_desc* desc, const float* param
   if ((rc = h->alloc(params_dev, false, s))) return rgfm_ratio_destroy(h), rc;
   if (hipMalloc(&h->bn, (h->n_bn + 4) * sizeof(float)) != hipSuccess) return bail(RGFM_ENOMEM, "hipMalloc(bn)");
   if (hipMalloc(&h->gradw, (h->n_gradw + 4) * sizeof(float)) != hipSuccess) return bail(RGFM_ENOMEM, "hipMalloc(gradw)");
-  if (hipMalloc(&h->wtmp, (size_t)256 * 256 * 9 * sizeof(float)) != hipSuccess) return bail(RGFM_ENOMEM, "hipMalloc(tmp)");
+  if (hipMalloc(&h->wtmp, h->n_wtmp * sizeof(float)) != hipSuccess) return bail(RGFM_ENOMEM, "hipMalloc(tmp)");
   if ((rc = pack_ratio(h, s))) return rgfm_ratio_destroy(h), rc;
   *out = h;
   return RGFM_OK;
+}
+}  // namespace
+
+extern "C" int rgfm_ratio_create(const rgfm_ratio_desc* desc, const float* params_dev, size_t n_floats,
+                                 rgfm_stream_t stream, rgfm_ratio** out) {
+  if (int rc = check_ratio_desc(desc)) return rc;
+  return create_ratio(*desc, rgfm_ratio_flex_desc{}, params_dev, n_floats, stream, out);
+}
+
+extern "C" int rgfm_ratio_flex_create(const rgfm_ratio_flex_desc* desc, const float* params_dev, size_t n_floats,
+                                      rgfm_stream_t stream, rgfm_ratio** out) {
+  rgfm_ratio_desc d{};
+  if (int rc = check_ratio_flex_desc(desc, &d)) return rc;
+  return create_ratio(d, *desc, params_dev, n_floats, stream, out);
 }
 
 extern "C" void rgfm_ratio_destroy(rgfm_ratio* h) {
@@ -311,7 +375,7 @@ struct RatioGradRun {
   // exact fp32 convs).  With it the encoders' forward convs follow that handle's conv arithmetic (g_modes, set by the
   // caller's ModeScope) and raise ITS flag, so that the sampler's range guard and fallback cover them.
   unsigned* flag = nullptr;
-  float* ab1 = nullptr;  // [n][256][2] identity scale/shift: "SiLU on load"
+  float* ab1 = nullptr;  // [n][max_c][2] identity scale/shift: "SiLU on load"
   unsigned* amax = nullptr;  // one word per reverse conv: bits of max |gradient| of its input (ConvArgs::in_amax); zeroed per call
   int amax_used = 0;
 
@@ -323,7 +387,8 @@ struct RatioGradRun {
     float* mr = nullptr;  // ... and (mean, rstd) of every group [n][8][2]
   };
 
-  // RatioEstimator's ImageEncoder (ratio_estimator.py:67-93) with the conv outputs and their norms' statistics kept
+  // The GroupNorm ImageEncoder (ratio_estimator.py:67-93, ratio_flexible.py:42-66) with the conv outputs and their
+  // norms' statistics kept
   void encode_gn(const rgfm_ratio::Encoder& e, const float* img, float* feat, int col0, std::vector<Kept>& kept) {
     const int F = h->d.feature_dim;
     int S = e.size;
@@ -485,16 +550,16 @@ struct RatioGradRun {
 
   void run(const float* x, const float* y, float* gx, float* gy, float* log_ratio) {
     const int F = h->d.feature_dim;
-    ab1 = ws->f((size_t)n * 256 * 2);
+    ab1 = ws->f((size_t)n * h->max_c * 2);
     amax = reinterpret_cast<unsigned*>(ws->f(64));
     amax_used = 0;
     if (!dry) {
-      launch_fill_ab_identity(ab1, (size_t)n * 256, s);
+      launch_fill_ab_identity(ab1, (size_t)n * h->max_c, s);
       (void)hipMemsetAsync(amax, 0, 64 * sizeof(unsigned), s);
     }
     float* feat = ws->f((size_t)n * 2 * F);
     std::vector<Kept> kx, ky;
-    if (h->d.kind == RGFM_RATIO_MNIST28) {
+    if (h->gn_encoders()) {
       encode_gn(h->ex, x, feat, 0, kx);
       encode_gn(h->ey, y, feat, F, ky);
     } else {
@@ -567,14 +632,33 @@ extern "C" int rgfm_ratio_grad_log_ratio(rgfm_ratio* h, const float* x, const fl
   return RGFM_OK;
 }
 
+// the U-Net pair must be the one the estimator handle was built for
+static int check_grad_pair(const rgfm_unet* hx, const rgfm_unet* hy, const rgfm_ratio* hr) {
+  if (hr->d.kind == RGFM_RATIO_FLEXIBLE) {
+    const rgfm_ratio_flex_desc& f = hr->geom;
+    if (hx->d.in_channels != f.x_channels || hx->d.img_size != f.x_size || hy->d.in_channels != f.y_channels ||
+        hy->d.img_size != f.y_size)
+      return fail(RGFM_EINVAL, "gradient guidance: the FlexibleRatioEstimator handle is built for %dx%dx%d + %dx%dx%d, the U-Nets are %dx%dx%d + %dx%dx%d",
+                  f.x_channels, f.x_size, f.x_size, f.y_channels, f.y_size, f.y_size, hx->d.in_channels, hx->d.img_size,
+                  hx->d.img_size, hy->d.in_channels, hy->d.img_size, hy->d.img_size);
+  } else if (hr->d.kind == RGFM_RATIO_MNIST_SVHN) {
+    if (hx->d.in_channels != 1 || hx->d.img_size != 32 || hy->d.in_channels != 3 || hy->d.img_size != 32)
+      return fail(RGFM_EINVAL, "gradient guidance with RatioEstimatorMNISTSVHN needs the 1x32x32 + 3x32x32 pair");
+  } else if (hx->d.in_channels != 1 || hx->d.img_size != 28 || hy->d.in_channels != 1 || hy->d.img_size != 28) {
+    return fail(RGFM_EINVAL, "gradient guidance with RatioEstimator needs the 1x28x28 + 1x28x28 pair");
+  }
+  return RGFM_OK;
+}
+
 // Paired Euler loop with gradient log-ratio guidance (reference README.md:159-164: v_guided = v_ind + gamma *
 // grad log r(x_t, y_t); the reference ships no code for it): x <- x + (v_x + gamma dlogr/dx) dt, every step.
 extern "C" int rgfm_sample_pair_grad_workspace_bytes(const rgfm_unet* hx, const rgfm_unet* hy, const rgfm_ratio* hr, int batch,
                                                      size_t* bytes) {
   if (!hx || !hy || !hr || !bytes || batch < 1) return fail(RGFM_EINVAL, "bad argument");
   size_t base = 0, rg = 0;
-  int rc = rgfm_sample_pair_workspace_bytes(hx, hy, batch, 0, &base);
+  int rc = hr->d.kind == RGFM_RATIO_FLEXIBLE ? check_grad_pair(hx, hy, hr) : RGFM_OK;  // (the fixed kinds: checked by the sampler call)
   if (rc) return rc;
+  if ((rc = rgfm_sample_pair_workspace_bytes(hx, hy, batch, 0, &base))) return rc;
   if ((rc = rgfm_ratio_grad_workspace_bytes(hr, batch, &rg))) return rc;
   const size_t dx = (size_t)hx->d.in_channels * hx->d.img_size * hx->d.img_size;
   const size_t dy = (size_t)hy->d.in_channels * hy->d.img_size * hy->d.img_size;
@@ -587,12 +671,7 @@ extern "C" int rgfm_sample_pair_grad(rgfm_unet* hx, rgfm_unet* hy, rgfm_ratio* h
                                      rgfm_stream_t stream) {
   refresh_modes();
   if (!hx || !hy || !hr || !x_inout || !y_inout || !ws) return fail(RGFM_EINVAL, "null argument");
-  if (hr->d.kind == RGFM_RATIO_MNIST_SVHN) {
-    if (hx->d.in_channels != 1 || hx->d.img_size != 32 || hy->d.in_channels != 3 || hy->d.img_size != 32)
-      return fail(RGFM_EINVAL, "gradient guidance with RatioEstimatorMNISTSVHN needs the 1x32x32 + 3x32x32 pair");
-  } else if (hx->d.in_channels != 1 || hx->d.img_size != 28 || hy->d.in_channels != 1 || hy->d.img_size != 28) {
-    return fail(RGFM_EINVAL, "gradient guidance with RatioEstimator needs the 1x28x28 + 1x28x28 pair");
-  }
+  if (int rc = check_grad_pair(hx, hy, hr)) return rc;
   if (batch < 1 || num_steps < 1 || step_begin < 0 || step_end > num_steps || step_begin > step_end)
     return fail(RGFM_EINVAL, "bad step range [%d,%d) of %d", step_begin, step_end, num_steps);
   const int ns = step_end - step_begin;

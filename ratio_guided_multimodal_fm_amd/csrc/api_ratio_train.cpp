@@ -2,8 +2,9 @@
 // (BatchNorm on batch statistics, dropout in the score MLP), the backward to both images and to every parameter, and
 // the two test hooks (C ABI: include/rgfm.h; kernels: ratio_train.hip and the conv / Linear kernels of unet_grad.hip).
 //
-// The walk is the reference RatioEstimatorMNISTSVHN.forward (src/models/ratio_flexible.py:211-364) or
-// RatioEstimator.forward (src/models/ratio_estimator.py:67-135) over NCHW tensors in the caller's workspace, laid out
+// The walk is the reference RatioEstimatorMNISTSVHN.forward (src/models/ratio_flexible.py:211-364),
+// RatioEstimator.forward (src/models/ratio_estimator.py:67-135) or FlexibleRatioEstimator.forward
+// (src/models/ratio_flexible.py:42-66, :116-133; the rasters follow the handle's sizes) over NCHW tensors in the caller's workspace, laid out
 // by plan_rt: first the SAVED state (header, both images, per conv its input, its output z, the norm's (mean, rstd)
 // pairs, the activated (and pooled) map with the pool's choices, the score MLP's pre-norm tensors and row statistics),
 // then the backward's SCRATCH.
@@ -36,7 +37,7 @@ struct RPlan {
   size_t total;  // floats
 };
 
-bool is_bn(const rgfm_ratio* h) { return h->d.kind == RGFM_RATIO_MNIST_SVHN; }
+bool is_bn(const rgfm_ratio* h) { return !h->gn_encoders(); }
 
 UgConv conv_of(const rgfm_ratio* h, const RConv& r, int n) {
   UgConv c{};

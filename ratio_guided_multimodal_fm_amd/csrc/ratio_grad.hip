@@ -287,7 +287,9 @@ void launch_conv_bwd_img(const float* gz, const float* w, float* gimg, int B, in
   const unsigned blocks = (unsigned)(((size_t)B * S * S + 255) / 256);
   const size_t lds = (size_t)9 * Co * 4 * sizeof(float);
   if (cimg == 1) hipLaunchKernelGGL(conv_bwd_img_kernel<1>, dim3(blocks), dim3(256), lds, s, gz, w, gimg, B, S, Co);
-  else hipLaunchKernelGGL(conv_bwd_img_kernel<3>, dim3(blocks), dim3(256), lds, s, gz, w, gimg, B, S, Co);
+  else if (cimg == 2) hipLaunchKernelGGL(conv_bwd_img_kernel<2>, dim3(blocks), dim3(256), lds, s, gz, w, gimg, B, S, Co);
+  else if (cimg == 3) hipLaunchKernelGGL(conv_bwd_img_kernel<3>, dim3(blocks), dim3(256), lds, s, gz, w, gimg, B, S, Co);
+  else hipLaunchKernelGGL(conv_bwd_img_kernel<4>, dim3(blocks), dim3(256), lds, s, gz, w, gimg, B, S, Co);
 }
 
 __device__ __forceinline__ float wsum_g(float v) {

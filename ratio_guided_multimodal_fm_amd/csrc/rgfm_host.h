@@ -1154,6 +1154,11 @@ int pair_loop(EvalX&& eval_x, EvalY&& eval_y, float* x_inout, float* y_inout, co
 // no range flag of its own)
 struct rgfm_ratio : WeightStore {
   rgfm_ratio_desc d;
+  rgfm_ratio_flex_desc geom{};  // kind RGFM_RATIO_FLEXIBLE: the descriptor the handle was built from
+  // GroupNorm(8) encoders (per-sample statistics, gn_finalize, gn_bwd) rather than folded BatchNorm ones
+  bool gn_encoders() const { return d.kind != RGFM_RATIO_MNIST_SVHN; }
+  int max_c = 0;       // widest conv output of either encoder (sizes the identity scale/shift scratch)
+  size_t n_wtmp = 0;   // floats of `wtmp`: the largest conv weight after an encoder's first
   float* bn = nullptr;  // folded BatchNorm scale/shift pairs
   // gradient path (kind RGFM_RATIO_MNIST_SVHN): transposed weights, built at create time
   float* gradw = nullptr;  // [packed W^T of every conv after the first | fc W^T | dense W^T | zeros]

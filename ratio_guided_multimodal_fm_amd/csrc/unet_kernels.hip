@@ -48,6 +48,7 @@ __global__ __launch_bounds__(256) void conv_in_pk_kernel(const ConvInArgs a) {
       v.x = p[0];
       if (CIN > 1) v.y = p[(size_t)HW];
       if (CIN > 2) v.z = p[(size_t)2 * HW];
+      if (CIN > 3) v.w = p[(size_t)3 * HW];
     }
     *reinterpret_cast<f32x4*>(smem + 4 * it) = v;
   }
@@ -88,6 +89,7 @@ __global__ __launch_bounds__(256) void conv_in_pk_kernel(const ConvInArgs a) {
           acc = __builtin_elementwise_fma(ci_f32x2{t.x, t.x}, wr[ky * 3 + kx], acc);
           if (CIN > 1) acc = __builtin_elementwise_fma(ci_f32x2{t.y, t.y}, wr[9 + ky * 3 + kx], acc);
           if (CIN > 2) acc = __builtin_elementwise_fma(ci_f32x2{t.z, t.z}, wr[18 + ky * 3 + kx], acc);
+          if (CIN > 3) acc = __builtin_elementwise_fma(ci_f32x2{t.w, t.w}, wr[27 + ky * 3 + kx], acc);
         }
       float* op = a.out + (pix0 + k) * a.C0 + c;
       op[0] = acc.x, op[32] = acc.y;
@@ -157,6 +159,7 @@ __global__ __launch_bounds__(256) void conv_in_kernel(const ConvInArgs a) {
       v.x = p[0];
       if (CIN > 1) v.y = p[(size_t)HW];
       if (CIN > 2) v.z = p[(size_t)2 * HW];
+      if (CIN > 3) v.w = p[(size_t)3 * HW];
     }
     *reinterpret_cast<f32x4*>(smem + 4 * it) = v;
   }
@@ -203,6 +206,7 @@ __global__ __launch_bounds__(256) void conv_in_kernel(const ConvInArgs a) {
           acc += wr[ky * 3 + kx] * t.x;
           if (CIN > 1) acc += wr[9 + ky * 3 + kx] * t.y;
           if (CIN > 2) acc += wr[18 + ky * 3 + kx] * t.z;
+          if (CIN > 3) acc += wr[27 + ky * 3 + kx] * t.w;
         }
       if (a.ep_scale) acc = a.ep_nosilu ? acc * es + eh : silu_f(acc * es + eh);
       a.out[(pix0 + k) * a.C0 + c] = acc;
@@ -265,17 +269,22 @@ void launch_up2_as_deconv(const float* w, float* k, int Cout, int Cin, hipStream
   hipLaunchKernelGGL(up2_as_deconv_kernel, dim3(256), dim3(256), 0, s, w, k, Cout, Cin);
 }
 
+// cin 1..4 (the staged float4 holds a pixel's channels; the U-Nets use 1 and 3, the flexible ratio encoders any)
 void launch_conv_in(const ConvInArgs& a, int cin, hipStream_t s) {
   const int per = (a.g.th + 2) * (a.g.W + 2);
   dim3 grid(geom_num_tiles(a.g, a.B));
   const size_t lds4 = (size_t)a.g.spt * per * 4 * sizeof(float);
   if (a.C0 % 64 == 0 && !a.ep_scale) {  // (the U-Nets' 64-channel input convs: two channels per lane)
     if (cin == 1) hipLaunchKernelGGL(conv_in_pk_kernel<1>, grid, dim3(256), lds4, s, a);
-    else hipLaunchKernelGGL(conv_in_pk_kernel<3>, grid, dim3(256), lds4, s, a);
+    else if (cin == 2) hipLaunchKernelGGL(conv_in_pk_kernel<2>, grid, dim3(256), lds4, s, a);
+    else if (cin == 3) hipLaunchKernelGGL(conv_in_pk_kernel<3>, grid, dim3(256), lds4, s, a);
+    else hipLaunchKernelGGL(conv_in_pk_kernel<4>, grid, dim3(256), lds4, s, a);
     return;
   }
   if (cin == 1) hipLaunchKernelGGL(conv_in_kernel<1>, grid, dim3(256), lds4, s, a);
-  else hipLaunchKernelGGL(conv_in_kernel<3>, grid, dim3(256), lds4, s, a);
+  else if (cin == 2) hipLaunchKernelGGL(conv_in_kernel<2>, grid, dim3(256), lds4, s, a);
+  else if (cin == 3) hipLaunchKernelGGL(conv_in_kernel<3>, grid, dim3(256), lds4, s, a);
+  else hipLaunchKernelGGL(conv_in_kernel<4>, grid, dim3(256), lds4, s, a);
 }
 
 // ------------------------------------------------------------------ conv_out

@@ -1,14 +1,60 @@
-"""MNIST-SVHN density-ratio estimator, host side.
+"""Density-ratio estimators of the reference's ``src/models/ratio_flexible.py``, host side.
 
-API mirror of ``RatioEstimatorMNISTSVHN`` (reference
-``src/models/ratio_flexible.py:305-385``; encoders ``:185-302``): parameter
-containers with the reference's ``state_dict`` keys; ``forward`` /
-``log_ratio`` run in the HIP library (eval-mode semantics: BatchNorm uses
-running statistics, Dropout is the identity).
+API mirrors of ``FlexibleRatioEstimator`` with its presets (reference ``:69-182``; GroupNorm ``ImageEncoder``
+``:13-66``) and of ``RatioEstimatorMNISTSVHN`` (``:305-385``; BatchNorm encoders ``:185-302``): parameter
+containers with the reference's ``state_dict`` keys; ``forward`` / ``log_ratio`` run in the HIP library
+(eval-mode semantics: BatchNorm uses running statistics, Dropout is the identity).
 """
 import torch.nn as nn
 
-from .._engine import RatioEngine, engine_property
+from .._engine import FlexibleRatioEngine, RatioEngine, engine_property
+from .ratio_estimator import ImageEncoder, RatioEstimator
+
+
+class FlexibleRatioEstimator(nn.Module):
+    """Ratio estimator for any pair of square images: x [B, x_channels, Sx, Sx], y [B, y_channels, Sy, Sy] with 1..4
+    channels and sizes 8..64 (reference ``:69-154``).  The parameters do not depend on the image sizes (the encoders
+    end in a global average pool); the sizes are read from the inputs of each call and the engine keeps one device
+    handle per (Sx, Sy) pair seen.  ``forward`` / ``forward_train`` / ``log_ratio`` / ``grad_log_ratio`` /
+    ``dropout_p`` as for ``RatioEstimator``, whose architecture at 1x28x28 + 1x28x28 this is."""
+    _engine = engine_property(lambda m: FlexibleRatioEngine(m))
+
+    def __init__(self, x_channels=1, y_channels=1, feature_dim=256, hidden_dim=512, loss_type='disc'):
+        super().__init__()
+        self.x_channels = x_channels
+        self.y_channels = y_channels
+        self.feature_dim = feature_dim
+        self.hidden_dim = hidden_dim
+        self.loss_type = loss_type
+        self.encoder_x = ImageEncoder(in_channels=x_channels, feature_dim=feature_dim)
+        self.encoder_y = ImageEncoder(in_channels=y_channels, feature_dim=feature_dim)
+        h = hidden_dim
+        self.score_net = nn.Sequential(
+            nn.Linear(feature_dim * 2, h), nn.LayerNorm(h), nn.SiLU(), nn.Dropout(0.1),
+            nn.Linear(h, h // 2), nn.LayerNorm(h // 2), nn.SiLU(), nn.Dropout(0.1),
+            nn.Linear(h // 2, 1))
+
+    # the same surface as RatioEstimator (the engine is what differs)
+    forward = RatioEstimator.forward
+    forward_train = RatioEstimator.forward_train
+    dropout_p = RatioEstimator.dropout_p
+    log_ratio = RatioEstimator.log_ratio
+    grad_log_ratio = RatioEstimator.grad_log_ratio
+
+
+class RatioEstimatorMNIST(FlexibleRatioEstimator):
+    """Ratio estimator for MNIST transforms (both x and y are 1x28x28; reference ``:159-169``)."""
+
+    def __init__(self, loss_type='disc'):
+        super().__init__(x_channels=1, y_channels=1, feature_dim=256, hidden_dim=512, loss_type=loss_type)
+
+
+class RatioEstimatorMNISTSVHN_old(FlexibleRatioEstimator):
+    """Ratio estimator for MNIST-SVHN (x 1x32x32, y 3x32x32), the reference's old ~944K-parameter version
+    (``:172-182``)."""
+
+    def __init__(self, loss_type='disc'):
+        super().__init__(x_channels=1, y_channels=3, feature_dim=256, hidden_dim=512, loss_type=loss_type)
 
 
 class _BNEncoderParams(nn.Module):

@@ -1,12 +1,19 @@
 """Train a density-ratio estimator r(x, y) = q(x, y) / p_ind(x, y) on the HIP backward.
 
     python -m ratio_guided_multimodal_fm_amd.train_ratio --kind mnist_svhn --data pairs.npz
+    python -m ratio_guided_multimodal_fm_amd.train_ratio --kind flexible --x_channels 3 --y_channels 3 --data pairs.npz
 
 Mirrors the reference trainers (src/train_ratio_mnist_svhn.py for --kind mnist_svhn, src/train_ratio.py for --kind
 mnist28): same arguments and defaults, Adam, plain state_dict checkpoints under the reference's names (best / every 10
 epochs), early stopping with patience 5.  The data is one .npz / .pt with `x` [N, ...], `y` [N, ...] and `label` [N],
 already in the reference's value range (no dataset download here): a real pair takes y from an item of the same
 label, a fake pair from another label, drawn per item with probability real_fake_ratio.
+
+--kind flexible trains a FlexibleRatioEstimator (the reference has no trainer for it; the mnist28 trainer's epoch is
+used): the channel counts come from --x_channels / --y_channels, the (square) image sizes from the data file.  Its
+checkpoints, checkpoints/ratio_<loss>_flexible_<tag>.pth, are the dict format load_checkpoint reads --
+{'model_state_dict', 'epoch', 'best_loss'} -- with the constructor arguments beside them ('x_channels', 'y_channels',
+'feature_dim', 'hidden_dim', 'loss_type'), since unlike the fixed kinds the file name does not determine the module.
 """
 import argparse
 import os
@@ -16,7 +23,7 @@ import torch
 import torch.nn.functional as F
 
 from .models.ratio_estimator import RatioEstimator
-from .models.ratio_flexible import RatioEstimatorMNISTSVHN
+from .models.ratio_flexible import FlexibleRatioEstimator, RatioEstimatorMNISTSVHN
 from .utils import set_seed
 from .utils.losses import get_ratio_loss
 from .utils.path_utils import get_checkpoint_path
@@ -26,6 +33,7 @@ KINDS = {
     # kind: (constructor, x shape, y shape)
     'mnist_svhn': (RatioEstimatorMNISTSVHN, (1, 32, 32), (3, 32, 32)),
     'mnist28': (RatioEstimator, (1, 28, 28), (1, 28, 28)),
+    'flexible': (FlexibleRatioEstimator, None, None),  # (channels from the arguments, sizes from the data)
 }
 PATIENCE, SAVE_EVERY = 5, 10
 
@@ -36,6 +44,8 @@ def parse_args(argv=None):
     p.add_argument('--data', required=True, help=".npz / .pt with 'x' [N,...], 'y' [N,...], 'label' [N]")
     p.add_argument('--loss_type', type=str, default='disc', choices=['disc', 'rulsif'])
     p.add_argument('--transform_type', type=str, default='rotate90', help='names the mnist28 checkpoint')
+    p.add_argument('--x_channels', type=int, default=1, help='--kind flexible: channels of x (1..4)')
+    p.add_argument('--y_channels', type=int, default=1, help='--kind flexible: channels of y (1..4)')
     p.add_argument('--epochs', type=int, default=30)
     p.add_argument('--batch_size', type=int, default=128)
     p.add_argument('--lr', type=float, default=1e-4)
@@ -48,12 +58,17 @@ def parse_args(argv=None):
 
 
 def load_pairs(path, shape_x, shape_y):
-    """(x, y, label) tensors of the data file."""
+    """(x, y, label) tensors of the data file.  A shape's size entries may be None (--kind flexible): any square
+    image of that many channels."""
     d = torch.load(path, map_location='cpu') if path.endswith('.pt') else np.load(path)
     x = torch.as_tensor(np.asarray(d['x']), dtype=torch.float32).contiguous()
     y = torch.as_tensor(np.asarray(d['y']), dtype=torch.float32).contiguous()
     label = torch.as_tensor(np.asarray(d['label'])).long().reshape(-1)
-    if tuple(x.shape[1:]) != shape_x or tuple(y.shape[1:]) != shape_y:
+    def fits(t, shape):
+        if shape[1] is None:
+            return t.dim() == 4 and t.shape[1] == shape[0] and t.shape[2] == t.shape[3]
+        return tuple(t.shape[1:]) == shape
+    if not fits(x, shape_x) or not fits(y, shape_y):
         raise ValueError(f"{path}: expected x [N, {shape_x}] and y [N, {shape_y}], got {tuple(x.shape)} and {tuple(y.shape)}")
     if not (x.shape[0] == y.shape[0] == label.shape[0]):
         raise ValueError(f"{path}: x, y and label must have the same length")
@@ -117,7 +132,20 @@ def checkpoint_path(args, tag):
     if args.kind == 'mnist_svhn':
         os.makedirs('checkpoints', exist_ok=True)
         return f'checkpoints/ratio_{args.loss_type}_mnist_svhn_{tag}.pth'
+    if args.kind == 'flexible':
+        os.makedirs('checkpoints', exist_ok=True)
+        return f'checkpoints/ratio_{args.loss_type}_flexible_{tag}.pth'
     return get_checkpoint_path('ratio', args.loss_type, args.transform_type, tag)
+
+
+def save_checkpoint(model, args, path, epoch, best_loss):
+    """Plain state_dict for the fixed kinds (as the reference trainers write); the flexible kind adds what rebuilds it."""
+    if args.kind != 'flexible':
+        torch.save(model.state_dict(), path)
+        return
+    torch.save({'model_state_dict': model.state_dict(), 'epoch': epoch, 'best_loss': best_loss,
+                'x_channels': model.x_channels, 'y_channels': model.y_channels, 'feature_dim': model.feature_dim,
+                'hidden_dim': model.hidden_dim, 'loss_type': model.loss_type}, path)
 
 
 def main(argv=None):
@@ -125,8 +153,14 @@ def main(argv=None):
     set_seed(args.seed)
     ctor, shape_x, shape_y = KINDS[args.kind]
     device = torch.device(args.device)
+    if args.kind == 'flexible':
+        shape_x, shape_y = (args.x_channels, None, None), (args.y_channels, None, None)
     x, y, label = load_pairs(args.data, shape_x, shape_y)
-    model = ctor(loss_type=args.loss_type).to(device)
+    if args.kind == 'flexible':
+        print(f"x: {tuple(x.shape[1:])}, y: {tuple(y.shape[1:])}")
+        model = ctor(x_channels=args.x_channels, y_channels=args.y_channels, loss_type=args.loss_type).to(device)
+    else:
+        model = ctor(loss_type=args.loss_type).to(device)
     print(f"Model parameters: {sum(p.numel() for p in model.parameters()):,}")
     if args.kind == 'mnist_svhn':
         loss_fn = get_ratio_loss(loss_type=args.loss_type)
@@ -146,13 +180,13 @@ def main(argv=None):
         if metrics['loss'] < best_loss:
             best_loss, patience_counter = metrics['loss'], 0
             path = checkpoint_path(args, 'best')
-            torch.save(model.state_dict(), path)
+            save_checkpoint(model, args, path, epoch + 1, best_loss)
             print(f"  -> Saved best model: {path}")
         else:
             patience_counter += 1
         if (epoch + 1) % SAVE_EVERY == 0:
             path = checkpoint_path(args, f'epoch{epoch + 1}')
-            torch.save(model.state_dict(), path)
+            save_checkpoint(model, args, path, epoch + 1, best_loss)
             print(f"  -> Saved checkpoint: {path}")
         if patience_counter >= PATIENCE:
             print(f"\nEarly stopping after {epoch + 1} epochs (patience={PATIENCE})")

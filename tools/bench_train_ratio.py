@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """Training throughput of the ratio estimators: one optimizer step (forward, loss, backward, Adam) at batch 128.
 
-    python tools/bench_train_ratio.py [--kinds mnist_svhn mnist28] [--batch 128] [--steps 20] [--warmup 5]
+    python tools/bench_train_ratio.py [--kinds mnist_svhn mnist28 flexible] [--batch 128] [--steps 20] [--warmup 5]
 
 For each kind it times (a) the HIP step (forward_train + the library's backward) and (b) the same step on a plain
 torch.nn build of the same architecture on the same GPU (MIOpen convs, PyTorch autograd), both in training mode with
@@ -29,6 +29,9 @@ KINDS = {
                     (3, [(64, 0), (64, 1), (128, 0), (128, 1), (256, 0), (256, 1), (256, 0), (256, 1)])), True, (512, 512, 256)),
     "mnist28": (M.RatioEstimator, (1, 28, 28), (1, 28, 28),
                 ((1, [(32, 1), (64, 1), (128, 1), (128, 0)]), (1, [(32, 1), (64, 1), (128, 1), (128, 0)])), False, (512, 256)),
+    # FlexibleRatioEstimator at the MNIST-SVHN shapes (the reference's RatioEstimatorMNISTSVHN_old preset)
+    "flexible": (M.RatioEstimatorMNISTSVHN_old, (1, 32, 32), (3, 32, 32),
+                 ((1, [(32, 1), (64, 1), (128, 1), (128, 0)]), (3, [(32, 1), (64, 1), (128, 1), (128, 0)])), False, (512, 256)),
 }
 
 
