@@ -587,56 +587,38 @@ __global__ __launch_bounds__(256, 2) void conv_mfma_pf_kernel(const ConvArgs a) 
   }
 }
 
-// debug switch (RGFM_CONV_SIMPLE=1): route every conv through the non-prefetching kernel
-static const bool g_conv_force_simple = getenv("RGFM_CONV_SIMPLE") != nullptr;
-
 size_t conv_mfma_lds_bytes(const ConvArgs& a) {
   const int nt = (a.Cout % 64 == 0) ? 2 : 1;  // (sized for 9 taps; CONV_T2 uses the first 4)
   return (size_t)(a.halo_px + 9 * 32 * nt) * LDP * sizeof(float) + 128 * sizeof(float);
 }
 
-template <int NT, int MODE>
-static int raise_lds() {
-  int rc = raise_lds_limit(&conv_mfma_kernel<NT, MODE>, 160 * 1024);
-  if (MODE != CONV_S2)
-    rc |= raise_lds_limit(&conv_mfma_pf_kernel<NT, MODE == CONV_S2 ? CONV_S1 : MODE>, 160 * 1024);
-  return rc;
-}
+// Every instantiation: X(kernel, prefetching, NT, MODE).  conv_mfma_init and launch_conv_mfma both expand this list.
+#define CONV_F32_FOR_ALL(X)                                                                                         \
+  X(conv_mfma_kernel, false, 1, CONV_S1) X(conv_mfma_kernel, false, 1, CONV_S2) X(conv_mfma_kernel, false, 1, CONV_UP2) \
+  X(conv_mfma_kernel, false, 2, CONV_S1) X(conv_mfma_kernel, false, 2, CONV_S2) X(conv_mfma_kernel, false, 2, CONV_UP2) \
+  X(conv_mfma_pf_kernel, true, 1, CONV_S1) X(conv_mfma_pf_kernel, true, 1, CONV_UP2) X(conv_mfma_pf_kernel, true, 1, CONV_T2) \
+  X(conv_mfma_pf_kernel, true, 2, CONV_S1) X(conv_mfma_pf_kernel, true, 2, CONV_UP2) X(conv_mfma_pf_kernel, true, 2, CONV_T2)
 
 int conv_mfma_init() {
   int rc = 0;
-  rc |= raise_lds<1, CONV_S1>();
-  rc |= raise_lds<1, CONV_S2>();
-  rc |= raise_lds<1, CONV_UP2>();
-  rc |= raise_lds<2, CONV_S1>();
-  rc |= raise_lds<2, CONV_S2>();
-  rc |= raise_lds<2, CONV_UP2>();
-  rc |= raise_lds_limit(&conv_mfma_pf_kernel<1, CONV_T2>, 160 * 1024);
-  rc |= raise_lds_limit(&conv_mfma_pf_kernel<2, CONV_T2>, 160 * 1024);
+#define RAISEF(K, PF, NTV, M) rc |= raise_lds_limit(&K<NTV, M>, 160 * 1024);
+  CONV_F32_FOR_ALL(RAISEF)
+#undef RAISEF
   return rc;
 }
 
-void launch_conv_mfma(const ConvArgs& a, int mode, hipStream_t s) {
+bool launch_conv_mfma(const ConvArgs& a, int mode, hipStream_t s) {
   const int nt = (a.Cout % 64 == 0) ? 2 : 1;
   dim3 grid(geom_num_tiles(a.g, a.B), a.Cout / (32 * nt), mode == CONV_T2 ? 4 : 1);
   const size_t lds = conv_mfma_lds_bytes(a);
-#define LAUNCH(NTV, M) hipLaunchKernelGGL((conv_mfma_kernel<NTV, M>), grid, dim3(256), lds, s, a)
-#define LAUNCH_PF(NTV, M) hipLaunchKernelGGL((conv_mfma_pf_kernel<NTV, M>), grid, dim3(256), lds, s, a)
-  const bool pf = mode != CONV_S2 && a.halo_px * 4 <= MAXIT * 256 && !g_conv_force_simple;
-  if (mode == CONV_T2) {  // prefetching kernel only (halo_px * 4 <= MAXIT * 256 is checked by the caller)
-    if (nt == 2) LAUNCH_PF(2, CONV_T2);
-    else LAUNCH_PF(1, CONV_T2);
-  } else if (nt == 2) {
-    if (mode == CONV_S2) LAUNCH(2, CONV_S2);
-    else if (mode == CONV_S1) { if (pf) LAUNCH_PF(2, CONV_S1); else LAUNCH(2, CONV_S1); }
-    else { if (pf) LAUNCH_PF(2, CONV_UP2); else LAUNCH(2, CONV_UP2); }
-  } else {
-    if (mode == CONV_S2) LAUNCH(1, CONV_S2);
-    else if (mode == CONV_S1) { if (pf) LAUNCH_PF(1, CONV_S1); else LAUNCH(1, CONV_S1); }
-    else { if (pf) LAUNCH_PF(1, CONV_UP2); else LAUNCH(1, CONV_UP2); }
-  }
-#undef LAUNCH
-#undef LAUNCH_PF
+  // CONV_T2: the prefetching kernel only (halo_px * 4 <= MAXIT * 256 is checked by the caller); CONV_S2: never
+  const bool pf = mode == CONV_T2 || (mode != CONV_S2 && a.halo_px * 4 <= MAXIT * 256 && !g_conv_tuning.f32_simple);
+#define LAUNCHF(K, PF, NTV, M) \
+  if (pf == (PF) && nt == (NTV) && mode == (M)) { hipLaunchKernelGGL((K<NTV, M>), grid, dim3(256), lds, s, a); return true; }
+  CONV_F32_FOR_ALL(LAUNCHF)
+#undef LAUNCHF
+  return false;
 }
+#undef CONV_F32_FOR_ALL
 
 }  // namespace rgfm

@@ -637,7 +637,7 @@ bool conv_bx3_supported(const ConvArgs& a, int mode) {
   const size_t px_in = (size_t)a.B * a.Hin * a.Win, px_out = (size_t)a.B * a.g.HW * (mode == CONV_T2 ? 4 : 1);
   const size_t cmax = (size_t)(a.C0 > a.C1 ? a.C0 : a.C1) > (size_t)a.Cout ? (size_t)(a.C0 > a.C1 ? a.C0 : a.C1) : (size_t)a.Cout;
   if (px_in >= (1u << 24) || px_out >= (1u << 24) || (px_in > px_out ? px_in : px_out) * cmax >= (1ull << 32)) return false;
-  if (mode == CONV_S2 && getenv("RGFM_S2_F32")) return false;  // A/B switch: stride-2 convs on the fp32 kernel
+  if (mode == CONV_S2 && g_conv_tuning.s2_f32) return false;  // (RGFM_S2_F32, A/B switch: stride-2 convs on the fp32 kernel)
   if (mode == CONV_S2 && (a.Hin != 2 * a.g.H || a.Win != 2 * a.g.W || a.C1 != 0 || a.res_mode != 0)) return false;
   return conv_halo_px(a) <= 448 && bx3w_lds_bytes(a, mode) <= 160 * 1024;
 }
@@ -654,45 +654,34 @@ int conv_fin_expected(const ConvArgs& a, int mode) {
   return (a.g.spt == 1 ? 4 * a.g.tps : 1) * groups * (mode == CONV_T2 ? 4 : 1);
 }
 
+// Every instantiation: X(NT, MODE, PAIRN).  conv_bx3_init and launch_conv_bx3 both expand this list.
+#define BX3_FOR_ALL(X)                                                                       \
+  X(1, CONV_S1, false) X(1, CONV_UP2, false) X(1, CONV_T2, false) X(1, CONV_S2, false) \
+  X(2, CONV_S1, false) X(2, CONV_UP2, false) X(2, CONV_T2, false) X(2, CONV_S2, false) \
+  X(2, CONV_S1, true) X(2, CONV_UP2, true) X(2, CONV_T2, true) X(2, CONV_S2, true)
+
 int conv_bx3_init() {
   int rc = 0;
-#define RAISEW(NTV, M, P) rc |= raise_lds_limit(&conv_mfma_bx3w_kernel<NTV, M, P>, 160 * 1024)
-  RAISEW(1, CONV_S1, false); RAISEW(1, CONV_UP2, false); RAISEW(1, CONV_T2, false);
-  RAISEW(2, CONV_S1, false); RAISEW(2, CONV_UP2, false); RAISEW(2, CONV_T2, false);
-  RAISEW(2, CONV_S1, true); RAISEW(2, CONV_UP2, true); RAISEW(2, CONV_T2, true);
-  RAISEW(1, CONV_S2, false); RAISEW(2, CONV_S2, false); RAISEW(2, CONV_S2, true);
+#define RAISEW(NTV, M, P) rc |= raise_lds_limit(&conv_mfma_bx3w_kernel<NTV, M, P>, 160 * 1024);
+  BX3_FOR_ALL(RAISEW)
 #undef RAISEW
   return rc;
 }
 
-void launch_conv_bx3(const ConvArgs& a_in, int mode, hipStream_t s) {
+bool launch_conv_bx3(const ConvArgs& a_in, int mode, hipStream_t s) {
   ConvArgs a = a_in;
   a.halo_px = conv_halo_px(a_in);
   const int nt = (a.Cout % 64 == 0) ? 2 : 1;
-  {
-    const int tiles = geom_num_tiles(a.g, a.B);
-    const bool pn = bx3_pairn(a);  // nt == 2 and Cout % 128 == 0
-    dim3 grid(pn ? tiles : (tiles + 1) / 2, pn ? a.Cout / 128 : a.Cout / (32 * nt), mode == CONV_T2 ? 4 : 1);
-    const size_t lds = bx3w_lds_bytes(a, mode);
-#define LAUNCHW(NTV, M, P) hipLaunchKernelGGL((conv_mfma_bx3w_kernel<NTV, M, P>), grid, dim3(512), lds, s, a, tiles)
-    if (pn) {
-      if (mode == CONV_S1) LAUNCHW(2, CONV_S1, true);
-      else if (mode == CONV_UP2) LAUNCHW(2, CONV_UP2, true);
-      else if (mode == CONV_S2) LAUNCHW(2, CONV_S2, true);
-      else LAUNCHW(2, CONV_T2, true);
-    } else if (nt == 2) {
-      if (mode == CONV_S1) LAUNCHW(2, CONV_S1, false);
-      else if (mode == CONV_UP2) LAUNCHW(2, CONV_UP2, false);
-      else if (mode == CONV_S2) LAUNCHW(2, CONV_S2, false);
-      else LAUNCHW(2, CONV_T2, false);
-    } else {
-      if (mode == CONV_S1) LAUNCHW(1, CONV_S1, false);
-      else if (mode == CONV_UP2) LAUNCHW(1, CONV_UP2, false);
-      else if (mode == CONV_S2) LAUNCHW(1, CONV_S2, false);
-      else LAUNCHW(1, CONV_T2, false);
-    }
+  const int tiles = geom_num_tiles(a.g, a.B);
+  const bool pn = bx3_pairn(a);  // nt == 2 and Cout % 128 == 0
+  dim3 grid(pn ? tiles : (tiles + 1) / 2, pn ? a.Cout / 128 : a.Cout / (32 * nt), mode == CONV_T2 ? 4 : 1);
+  const size_t lds = bx3w_lds_bytes(a, mode);
+#define LAUNCHW(NTV, M, P) \
+  if (nt == (NTV) && mode == (M) && pn == (P)) { hipLaunchKernelGGL((conv_mfma_bx3w_kernel<NTV, M, P>), grid, dim3(512), lds, s, a, tiles); return true; }
+  BX3_FOR_ALL(LAUNCHW)
 #undef LAUNCHW
-  }
+  return false;
 }
+#undef BX3_FOR_ALL
 
 }  // namespace rgfm

@@ -718,45 +718,34 @@ bool conv_hx2_gn_supported(const ConvArgs& a, int mode) {
   return conv_hx2_supported(a, mode);                         // (its LDS check includes the table)
 }
 
+// Every instantiation: X(NT, MODE, PAIRN).  conv_hx2_init and launch_conv_hx2 both expand this list.
+#define HX2_FOR_ALL(X)                                                                       \
+  X(1, CONV_S1, false) X(1, CONV_UP2, false) X(1, CONV_T2, false) X(1, CONV_S2, false) \
+  X(2, CONV_S1, false) X(2, CONV_UP2, false) X(2, CONV_T2, false) X(2, CONV_S2, false) \
+  X(2, CONV_S1, true) X(2, CONV_UP2, true) X(2, CONV_T2, true) X(2, CONV_S2, true)
+
 int conv_hx2_init() {
   int rc = 0;
-#define RAISEW(NTV, M, P) rc |= raise_lds_limit(&conv_mfma_hx2_kernel<NTV, M, P>, 160 * 1024)
-  RAISEW(1, CONV_S1, false); RAISEW(1, CONV_UP2, false); RAISEW(1, CONV_T2, false);
-  RAISEW(2, CONV_S1, false); RAISEW(2, CONV_UP2, false); RAISEW(2, CONV_T2, false);
-  RAISEW(2, CONV_S1, true); RAISEW(2, CONV_UP2, true); RAISEW(2, CONV_T2, true);
-  RAISEW(1, CONV_S2, false); RAISEW(2, CONV_S2, false); RAISEW(2, CONV_S2, true);
+#define RAISEW(NTV, M, P) rc |= raise_lds_limit(&conv_mfma_hx2_kernel<NTV, M, P>, 160 * 1024);
+  HX2_FOR_ALL(RAISEW)
 #undef RAISEW
   return rc;
 }
 
-void launch_conv_hx2(const ConvArgs& a_in, int mode, hipStream_t s) {
+bool launch_conv_hx2(const ConvArgs& a_in, int mode, hipStream_t s) {
   ConvArgs a = a_in;
   a.halo_px = conv_halo_px(a_in);
   const int nt = (a.Cout % 64 == 0) ? 2 : 1;
-  {
-    const int tiles = geom_num_tiles(a.g, a.B);
-    const bool pn = hx2_pairn(a);  // nt == 2 and Cout % 128 == 0
-    dim3 grid(pn ? tiles : (tiles + 1) / 2, pn ? a.Cout / 128 : a.Cout / (32 * nt), mode == CONV_T2 ? 4 : 1);
-    const size_t lds = hx2_lds_bytes(a, mode);
-#define LAUNCHW(NTV, M, P) hipLaunchKernelGGL((conv_mfma_hx2_kernel<NTV, M, P>), grid, dim3(512), lds, s, a, tiles)
-    if (pn) {
-      if (mode == CONV_S1) LAUNCHW(2, CONV_S1, true);
-      else if (mode == CONV_UP2) LAUNCHW(2, CONV_UP2, true);
-      else if (mode == CONV_S2) LAUNCHW(2, CONV_S2, true);
-      else LAUNCHW(2, CONV_T2, true);
-    } else if (nt == 2) {
-      if (mode == CONV_S1) LAUNCHW(2, CONV_S1, false);
-      else if (mode == CONV_UP2) LAUNCHW(2, CONV_UP2, false);
-      else if (mode == CONV_S2) LAUNCHW(2, CONV_S2, false);
-      else LAUNCHW(2, CONV_T2, false);
-    } else {
-      if (mode == CONV_S1) LAUNCHW(1, CONV_S1, false);
-      else if (mode == CONV_UP2) LAUNCHW(1, CONV_UP2, false);
-      else if (mode == CONV_S2) LAUNCHW(1, CONV_S2, false);
-      else LAUNCHW(1, CONV_T2, false);
-    }
+  const int tiles = geom_num_tiles(a.g, a.B);
+  const bool pn = hx2_pairn(a);  // nt == 2 and Cout % 128 == 0
+  dim3 grid(pn ? tiles : (tiles + 1) / 2, pn ? a.Cout / 128 : a.Cout / (32 * nt), mode == CONV_T2 ? 4 : 1);
+  const size_t lds = hx2_lds_bytes(a, mode);
+#define LAUNCHW(NTV, M, P) \
+  if (nt == (NTV) && mode == (M) && pn == (P)) { hipLaunchKernelGGL((conv_mfma_hx2_kernel<NTV, M, P>), grid, dim3(512), lds, s, a, tiles); return true; }
+  HX2_FOR_ALL(LAUNCHW)
 #undef LAUNCHW
-  }
+  return false;
 }
+#undef HX2_FOR_ALL
 
 }  // namespace rgfm

@@ -301,18 +301,13 @@ __global__ __launch_bounds__(512, 1) void conv_mfma_hx2c_kernel(const ConvArgs a
 }
 
 // ---------------------------------------------------------------- host side
-static int g_hx2c_on = 1;
-void conv_hx2c_set(int v) { g_hx2c_on = v; }
-static int g_hx2c_all = 0;  // tools/kbench: every supported shape
-void conv_hx2c_set_all(int v) { g_hx2c_all = v; }
-
 static size_t hx2c_lds_bytes(const ConvArgs& a) {
   const int cin = a.C0 + a.C1, nch = cin / KC + (a.res_mode == 2 ? (a.R0 + a.R1) / KC : 0);
   return (size_t)2 * (4 * 100 + 1) * HRW + (size_t)2 * 9 * 64 * HRW + (size_t)5 * cin * 8 + (size_t)nch * 16;
 }
 
 bool conv_hx2c_supported(const ConvArgs& a, int mode) {
-  if (!g_hx2c_on || mode != CONV_S1) return false;
+  if (!g_conv_tuning.hx2c_on || mode != CONV_S1) return false;
   if (!a.gn_stats0 || a.ab) return false;  // convs of raw inputs stay on conv_mfma_hx2p_kernel
   if (!conv_hx2_supported(a, mode) || !conv_hx2_gn_supported(a, mode)) return false;
   const TileGeom& g = a.g;
@@ -325,23 +320,33 @@ bool conv_hx2c_supported(const ConvArgs& a, int mode) {
   if (hx2c_lds_bytes(a) > 160 * 1024) return false;
   // Where it pays (tools/kbench/scripts/q23.sh, q24.sh): 128 -> 128 and 256 -> 128 without a fused skip -3 ... -8 % against
   // conv_mfma_hx2p_kernel at 32 ... 512 rows; with the 1x1 skip (16 one-tap chunks, each behind a whole chunk of staging)
-  // +7 %: those stay on hx2p.  g_hx2c_all (kbench) lifts the restriction.
-  return g_hx2c_all || a.res_mode != 2;
+  // +7 %: those stay on hx2p.  ConvTuning::hx2c_all (kbench) lifts the restriction.
+  return g_conv_tuning.hx2c_all || a.res_mode != 2;
 }
+
+// Every instantiation: X(fused 1x1 skip).  conv_hx2c_init and launch_conv_hx2c both expand this list.
+#define HX2C_FOR_ALL(X) X(false) X(true)
 
 int conv_hx2c_init() {
   int rc = 0;
-  rc |= raise_lds_limit(&conv_mfma_hx2c_kernel<false>, 160 * 1024);
-  rc |= raise_lds_limit(&conv_mfma_hx2c_kernel<true>, 160 * 1024);
+#define RAISEC(SK) rc |= raise_lds_limit(&conv_mfma_hx2c_kernel<SK>, 160 * 1024);
+  HX2C_FOR_ALL(RAISEC)
+#undef RAISEC
   return rc;
 }
 
-void launch_conv_hx2c(const ConvArgs& a, hipStream_t s) {
+bool launch_conv_hx2c(const ConvArgs& a, int mode, hipStream_t s) {
+  if (mode != CONV_S1) return false;
   const int tiles = geom_num_tiles(a.g, a.B);
   const dim3 grid(tiles, a.Cout / 64);
   const size_t lds = hx2c_lds_bytes(a);
-  if (a.res_mode == 2) hipLaunchKernelGGL(conv_mfma_hx2c_kernel<true>, grid, dim3(512), lds, s, a, tiles);
-  else hipLaunchKernelGGL(conv_mfma_hx2c_kernel<false>, grid, dim3(512), lds, s, a, tiles);
+  const bool skip = a.res_mode == 2;
+#define LAUNCHC(SK) \
+  if (skip == (SK)) { hipLaunchKernelGGL(conv_mfma_hx2c_kernel<SK>, grid, dim3(512), lds, s, a, tiles); return true; }
+  HX2C_FOR_ALL(LAUNCHC)
+#undef LAUNCHC
+  return false;
 }
+#undef HX2C_FOR_ALL
 
 }  // namespace rgfm

@@ -575,14 +575,11 @@ __global__ __launch_bounds__(256, 2) void conv_mfma_hx2d4_kernel(const ConvArgs 
 }
 
 // ---------------------------------------------------------------- host side
-// 0: off; 1: the eight-wave kernel everywhere; 2: the four-wave kernel everywhere (tools/kbench A/B); 3 (default): by
+// ConvTuning::hx2d_cut -- 0: off; 1: the eight-wave kernel everywhere; 2: the four-wave kernel everywhere (A/B); 3 (default): by
 // layer shape -- never by batch, so a row's result cannot depend on its launch; the two cuts add the same products in the
 // same order anyway.  Measured at B = 512 / 32 (tools/kbench, profiles/r04_kbench/hx2d_cuts.txt): with a fused 1x1 skip the
 // four-wave cut wins everywhere (16x16, 128 channels, 256-channel skip: 149 vs 204 us); without one the eight-wave cut
 // wins at 8x8 (28.9 vs 30.8 us; 19.4 vs 22.6 at 32 rows) and the four-wave cut at 16x16 (103.6 vs 107.2).
-static int g_hx2d_on = 3;
-void conv_hx2d_set(int v) { g_hx2d_on = v; }
-
 static size_t hx2d4_lds_bytes(const ConvArgs& a) {
   const int npc = a.g.W == 8 ? 25 : 21;
   return (size_t)2 * npc * 1024 + (size_t)2 * 3 * 64 * HRW;
@@ -594,7 +591,7 @@ static size_t hx2d_lds_bytes(const ConvArgs& a) {
 }
 
 bool conv_hx2d_supported(const ConvArgs& a, int mode) {
-  if (!g_hx2d_on || mode != CONV_S1) return false;
+  if (!g_conv_tuning.hx2d_cut || mode != CONV_S1) return false;
   if (!a.pin0 || !a.zeros || a.C1 != 0) return false;
   if (!a.wpkh || !a.hq || !a.range_flag) return false;
   const TileGeom& g = a.g;
@@ -607,43 +604,37 @@ bool conv_hx2d_supported(const ConvArgs& a, int mode) {
   return true;
 }
 
+// Every instantiation: X(kernel, four-wave cut, raster width, fused 1x1 skip).  conv_hx2d_init and launch_conv_hx2d both
+// expand this list.  The four-wave cut runs two workgroups per CU: half the LDS, half the threads.
+#define HX2D_FOR_ALL(X)                                                                                   \
+  X(conv_mfma_hx2d_kernel, false, 8, false) X(conv_mfma_hx2d_kernel, false, 8, true)                       \
+  X(conv_mfma_hx2d_kernel, false, 16, false) X(conv_mfma_hx2d_kernel, false, 16, true)                     \
+  X(conv_mfma_hx2d4_kernel, true, 8, false) X(conv_mfma_hx2d4_kernel, true, 8, true)                       \
+  X(conv_mfma_hx2d4_kernel, true, 16, false) X(conv_mfma_hx2d4_kernel, true, 16, true)
+
 int conv_hx2d_init() {
   int rc = 0;
-  rc |= raise_lds_limit(&conv_mfma_hx2d_kernel<8, false>, 160 * 1024);
-  rc |= raise_lds_limit(&conv_mfma_hx2d_kernel<8, true>, 160 * 1024);
-  rc |= raise_lds_limit(&conv_mfma_hx2d_kernel<16, false>, 160 * 1024);
-  rc |= raise_lds_limit(&conv_mfma_hx2d_kernel<16, true>, 160 * 1024);
-  rc |= raise_lds_limit(&conv_mfma_hx2d4_kernel<8, false>, 80 * 1024);
-  rc |= raise_lds_limit(&conv_mfma_hx2d4_kernel<8, true>, 80 * 1024);
-  rc |= raise_lds_limit(&conv_mfma_hx2d4_kernel<16, false>, 80 * 1024);
-  rc |= raise_lds_limit(&conv_mfma_hx2d4_kernel<16, true>, 80 * 1024);
+#define RAISED(K, W4, WV, SK) rc |= raise_lds_limit(&K<WV, SK>, ((W4) ? 80 : 160) * 1024);
+  HX2D_FOR_ALL(RAISED)
+#undef RAISED
   return rc;
 }
 
-void launch_conv_hx2d(const ConvArgs& a, hipStream_t s) {
+bool launch_conv_hx2d(const ConvArgs& a, int mode, hipStream_t s) {
+  if (mode != CONV_S1) return false;
   const int tiles = geom_num_tiles(a.g, a.B);
   const dim3 grid(tiles, a.Cout / 64);
-  const size_t lds = hx2d_lds_bytes(a);
   const bool skip = a.res_mode == 2;
-  if (g_hx2d_on == 2 || (g_hx2d_on == 3 && (skip || a.g.W == 16))) {
-    const size_t lds4 = hx2d4_lds_bytes(a);
-    if (a.g.W == 8) {
-      if (skip) hipLaunchKernelGGL((conv_mfma_hx2d4_kernel<8, true>), grid, dim3(256), lds4, s, a, tiles);
-      else hipLaunchKernelGGL((conv_mfma_hx2d4_kernel<8, false>), grid, dim3(256), lds4, s, a, tiles);
-    } else {
-      if (skip) hipLaunchKernelGGL((conv_mfma_hx2d4_kernel<16, true>), grid, dim3(256), lds4, s, a, tiles);
-      else hipLaunchKernelGGL((conv_mfma_hx2d4_kernel<16, false>), grid, dim3(256), lds4, s, a, tiles);
-    }
-    return;
-  }
-  if (a.g.W == 8) {
-    if (skip) hipLaunchKernelGGL((conv_mfma_hx2d_kernel<8, true>), grid, dim3(512), lds, s, a, tiles);
-    else hipLaunchKernelGGL((conv_mfma_hx2d_kernel<8, false>), grid, dim3(512), lds, s, a, tiles);
-  } else {
-    if (skip) hipLaunchKernelGGL((conv_mfma_hx2d_kernel<16, true>), grid, dim3(512), lds, s, a, tiles);
-    else hipLaunchKernelGGL((conv_mfma_hx2d_kernel<16, false>), grid, dim3(512), lds, s, a, tiles);
-  }
+  const int cut = g_conv_tuning.hx2d_cut, w = a.g.W == 8 ? 8 : 16;
+  const bool w4 = cut == 2 || (cut == 3 && (skip || a.g.W == 16));
+  const size_t lds = w4 ? hx2d4_lds_bytes(a) : hx2d_lds_bytes(a);
+#define LAUNCHD(K, W4, WV, SK) \
+  if (w4 == (W4) && w == (WV) && skip == (SK)) { hipLaunchKernelGGL((K<WV, SK>), grid, dim3((W4) ? 256 : 512), lds, s, a, tiles); return true; }
+  HX2D_FOR_ALL(LAUNCHD)
+#undef LAUNCHD
+  return false;
 }
+#undef HX2D_FOR_ALL
 
 // ---------------------------------------------------------------- P format from an fp32 map (tools/kbench, tests, and the
 // producers that cannot emit it themselves): out[pixel][chunk] = split(S_A silu(scale x + shift)) with the per-(sample,

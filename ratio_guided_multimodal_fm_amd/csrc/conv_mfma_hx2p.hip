@@ -823,25 +823,20 @@ static size_t hx2p_lds_bytes(const ConvArgs& a, int cfg, int mode) {
 // into two four-wave ones (HX2P_FOUR_WAVES) -- a workgroup's time is set by its serial chain of round trips, not by
 // its MFMA count, so twice the workgroups on idle CUs is up to twice the rate (measured -15..-34 % per launch).
 // On FULL launches both are slower (four-wave workgroups: a four-wave workgroup takes as long as an eight-wave one
-// co-resident or not, whole bench 438 vs 450 img/s; 64-channel workgroups: +20 % time), so only below g_hx2p_half.
-// tools/kbench: RGFM_HX2P_W4 = 1 / 2 forces four-wave workgroups (layers with Cout % 128 != 0 / every layer whose
-// LDS need allows two workgroups per CU), RGFM_HX2P_HALF sets the threshold.
-static int g_hx2p_w4 = 0;
-void conv_hx2p_set_w4(int v) { g_hx2p_w4 = v; }
-// launches with fewer workgroups than this are cut finer (0: never); the CU count
-static int g_hx2p_half = 256;
-void conv_hx2p_set_half(int v) { g_hx2p_half = v; }
+// co-resident or not, whole bench 438 vs 450 img/s; 64-channel workgroups: +20 % time), so only below
+// ConvTuning::hx2p_half; ConvTuning::hx2p_w4 (tools/kbench) forces four-wave workgroups.
 static int hx2p_cfg(const ConvArgs& a, int mode) {
+  const int w4 = g_conv_tuning.hx2p_w4, half = g_conv_tuning.hx2p_half;
   const bool fits = hx2p_lds_bytes(a, HX2P_FOUR_WAVES, mode) <= 80 * 1024;  // two workgroups per CU
-  if (g_hx2p_w4 == 2 && fits) return HX2P_FOUR_WAVES;
-  if (g_hx2p_w4 == 1 && fits && a.Cout % 128 != 0) return HX2P_FOUR_WAVES;
+  if (w4 == 2 && fits) return HX2P_FOUR_WAVES;
+  if (w4 == 1 && fits && a.Cout % 128 != 0) return HX2P_FOUR_WAVES;
   const int tiles = geom_num_tiles(a.g, a.B) * (mode == CONV_T2 ? 4 : 1);  // (workgroups: a parity class each)
   if (a.Cout % 128 != 0) {
     const int wgs = ((tiles + 1) / 2) * (a.Cout / (32 * ((a.Cout % 64 == 0) ? 2 : 1)));
-    return (g_hx2p_half && wgs < g_hx2p_half) ? HX2P_FOUR_WAVES : HX2P_TWO_TILES;
+    return (half && wgs < half) ? HX2P_FOUR_WAVES : HX2P_TWO_TILES;
   }
   const int wgs = tiles * (a.Cout / 128);
-  if (!(g_hx2p_half && wgs < g_hx2p_half)) return HX2P_PAIRN;
+  if (!(half && wgs < half)) return HX2P_PAIRN;
   return HX2P_PAIRN_HALF;
 }
 
@@ -854,23 +849,25 @@ bool conv_hx2p_supported(const ConvArgs& a, int mode) {
   return conv_halo_px(a) <= 448 && hx2p_lds_bytes(a, hx2p_cfg(a, mode), mode) <= 160 * 1024;
 }
 
+// Every instantiation: X(NT, MODE, cut, POUT).  conv_hx2p_init and launch_conv_hx2p both expand this list.  The 128-channel
+// cut has NT = 2 and its 64-channel halves NT = 1 by construction; the P-format producers (POUT) are stride-1 convs with
+// 64 / 128 / 256 output channels (p_producer_ok), so NT = 2 unless halved.
+#define HX2P_MODES(X, NTV, P) X(NTV, CONV_S1, P, false) X(NTV, CONV_UP2, P, false) X(NTV, CONV_T2, P, false)
+#define HX2P_FOR_ALL(X)                                                                                  \
+  HX2P_MODES(X, 1, HX2P_TWO_TILES) HX2P_MODES(X, 2, HX2P_TWO_TILES) HX2P_MODES(X, 2, HX2P_PAIRN)           \
+  HX2P_MODES(X, 1, HX2P_PAIRN_HALF) HX2P_MODES(X, 1, HX2P_FOUR_WAVES) HX2P_MODES(X, 2, HX2P_FOUR_WAVES)    \
+  X(2, CONV_S1, HX2P_PAIRN, true) X(1, CONV_S1, HX2P_PAIRN_HALF, true) X(2, CONV_S1, HX2P_TWO_TILES, true) \
+  X(2, CONV_S1, HX2P_FOUR_WAVES, true)
+
 int conv_hx2p_init() {
   int rc = 0;
-#define RAISEP(NTV, M, P) rc |= raise_lds_limit(&conv_mfma_hx2p_kernel<NTV, M, P>, 160 * 1024)
-  RAISEP(1, CONV_S1, HX2P_TWO_TILES); RAISEP(1, CONV_UP2, HX2P_TWO_TILES); RAISEP(1, CONV_T2, HX2P_TWO_TILES);
-  RAISEP(2, CONV_S1, HX2P_TWO_TILES); RAISEP(2, CONV_UP2, HX2P_TWO_TILES); RAISEP(2, CONV_T2, HX2P_TWO_TILES);
-  RAISEP(2, CONV_S1, HX2P_PAIRN); RAISEP(2, CONV_UP2, HX2P_PAIRN); RAISEP(2, CONV_T2, HX2P_PAIRN);
-  RAISEP(1, CONV_S1, HX2P_PAIRN_HALF); RAISEP(1, CONV_UP2, HX2P_PAIRN_HALF); RAISEP(1, CONV_T2, HX2P_PAIRN_HALF);
-  RAISEP(1, CONV_S1, HX2P_FOUR_WAVES); RAISEP(1, CONV_UP2, HX2P_FOUR_WAVES); RAISEP(1, CONV_T2, HX2P_FOUR_WAVES);
-  RAISEP(2, CONV_S1, HX2P_FOUR_WAVES); RAISEP(2, CONV_UP2, HX2P_FOUR_WAVES); RAISEP(2, CONV_T2, HX2P_FOUR_WAVES);
+#define RAISEP(NTV, M, P, PO) rc |= raise_lds_limit(&conv_mfma_hx2p_kernel<NTV, M, P, PO>, 160 * 1024);
+  HX2P_FOR_ALL(RAISEP)
 #undef RAISEP
-#define RAISEPP(NTV, P) rc |= raise_lds_limit(&conv_mfma_hx2p_kernel<NTV, CONV_S1, P, true>, 160 * 1024)
-  RAISEPP(2, HX2P_PAIRN); RAISEPP(1, HX2P_PAIRN_HALF); RAISEPP(2, HX2P_TWO_TILES); RAISEPP(2, HX2P_FOUR_WAVES);
-#undef RAISEPP
   return rc;
 }
 
-void launch_conv_hx2p(const ConvArgs& a_in, int mode, hipStream_t s) {
+bool launch_conv_hx2p(const ConvArgs& a_in, int mode, hipStream_t s) {
   ConvArgs a = a_in;
   a.halo_px = conv_halo_px(a_in);
   const int nt = (a.Cout % 64 == 0) ? 2 : 1;
@@ -880,34 +877,17 @@ void launch_conv_hx2p(const ConvArgs& a_in, int mode, hipStream_t s) {
   dim3 grid(cfg == HX2P_TWO_TILES ? (tiles + 1) / 2 : tiles,
             cfg == HX2P_PAIRN ? a.Cout / 128 : (cfg == HX2P_PAIRN_HALF ? a.Cout / 64 : a.Cout / (32 * nt)), mode == CONV_T2 ? 4 : 1);
   const size_t lds = hx2p_lds_bytes(a, cfg, mode);
-#define LAUNCHP(NTV, M, P) hipLaunchKernelGGL((conv_mfma_hx2p_kernel<NTV, M, P>), grid, dim3(P == HX2P_FOUR_WAVES ? 256 : 512), lds, s, a, tiles)
-  if (a.pout) {  // (the walk has checked hx2p_pout_supported: 16x16 stride-1, 64 / 128 / 256 output channels)
-#define LAUNCHPP(NTV, P) hipLaunchKernelGGL((conv_mfma_hx2p_kernel<NTV, CONV_S1, P, true>), grid, dim3(P == HX2P_FOUR_WAVES ? 256 : 512), lds, s, a, tiles)
-    if (cfg == HX2P_PAIRN) LAUNCHPP(2, HX2P_PAIRN);
-    else if (cfg == HX2P_PAIRN_HALF) LAUNCHPP(1, HX2P_PAIRN_HALF);
-    else if (cfg == HX2P_FOUR_WAVES) LAUNCHPP(2, HX2P_FOUR_WAVES);
-    else LAUNCHPP(2, HX2P_TWO_TILES);
-#undef LAUNCHPP
-    return;
-  }
-#define LAUNCHM(NTV, P)                           \
-  do {                                            \
-    if (mode == CONV_S1) LAUNCHP(NTV, CONV_S1, P); \
-    else if (mode == CONV_T2) LAUNCHP(NTV, CONV_T2, P); \
-    else LAUNCHP(NTV, CONV_UP2, P);               \
-  } while (0)
-  if (cfg == HX2P_PAIRN) LAUNCHM(2, HX2P_PAIRN);
-  else if (cfg == HX2P_PAIRN_HALF) LAUNCHM(1, HX2P_PAIRN_HALF);
-  else if (cfg == HX2P_FOUR_WAVES) {
-    if (nt == 2) LAUNCHM(2, HX2P_FOUR_WAVES);
-    else LAUNCHM(1, HX2P_FOUR_WAVES);
-  }
-  else {
-    if (nt == 2) LAUNCHM(2, HX2P_TWO_TILES);
-    else LAUNCHM(1, HX2P_TWO_TILES);
-  }
-#undef LAUNCHM
+  const int ntk = cfg == HX2P_PAIRN_HALF ? 1 : nt;  // (a wave of a 64-channel half holds one accumulator column)
+  const bool pout = a.pout != nullptr;              // (the walk has checked p_producer_ok: 16x16 stride-1, 64 / 128 / 256 output channels)
+  const dim3 block(cfg == HX2P_FOUR_WAVES ? 256 : 512);
+#define LAUNCHP(NTV, M, P, PO)                                     \
+  if (ntk == (NTV) && mode == (M) && cfg == (P) && pout == (PO)) { \
+    hipLaunchKernelGGL((conv_mfma_hx2p_kernel<NTV, M, P, PO>), grid, block, lds, s, a, tiles); return true; }
+  HX2P_FOR_ALL(LAUNCHP)
 #undef LAUNCHP
+  return false;
 }
+#undef HX2P_FOR_ALL
+#undef HX2P_MODES
 
 }  // namespace rgfm

@@ -481,19 +481,6 @@ __global__ __launch_bounds__(256 * NG, (NG == 2 && NT == 1) ? 4 : 2) void conv_m
 }
 
 // ---------------------------------------------------------------- host side
-// launches with fewer (tile, channel block) pairs than this stay on conv_mfma_hx2p_kernel (0: this kernel never runs):
-// at two workgroups per CU the stream needs >= 2 tiles per workgroup to pay (tools/kbench: B = 128 rows lose)
-static int g_hx2q_min = 1024;
-void conv_hx2q_set_min(int v) { g_hx2q_min = v; }
-static int g_hx2q_target = 512;  // workgroups a launch is cut into when it has the tiles: two per CU
-void conv_hx2q_set_target(int v) { g_hx2q_target = v > 0 ? v : 1; }
-static int g_hx2q_all = 0;       // tools/kbench: every supported shape, not only those where this kernel is the faster one
-void conv_hx2q_set_all(int v) { g_hx2q_all = v; }
-static int g_hx2q_tpw = 0;       // tools/kbench: force the tiles per workgroup (0: hx2q_tiles_per_wg)
-void conv_hx2q_set_tpw(int v) { g_hx2q_tpw = v; }
-static int g_hx2q_cut = 0;       // tools/kbench: force the workgroup cut, 10 NG + NT (0: hx2q_cut)
-void conv_hx2q_set_cut(int v) { g_hx2q_cut = v; }
-
 // The workgroup cut {NG 32 NT-channel groups, NT accumulator columns per wave} -> channels per workgroup 32 NG NT:
 //   {1,1} 32 ch, 4 waves, two workgroups per CU (LDS)      {2,1} 64 ch, 8 waves x 128 VGPRs, two workgroups per CU
 //   {1,2} 64 ch, 4 waves x 256 VGPRs, two workgroups per CU  {2,2} 128 ch, 8 waves x 256 VGPRs, one workgroup per CU
@@ -502,7 +489,7 @@ struct Hx2qCut {
   int cb() const { return 32 * ng * nt; }
 };
 static Hx2qCut hx2q_cut(const ConvArgs& a) {
-  if (g_hx2q_cut) return {g_hx2q_cut / 10, g_hx2q_cut % 10};
+  if (g_conv_tuning.hx2q_cut) return {g_conv_tuning.hx2q_cut / 10, g_conv_tuning.hx2q_cut % 10};
   if (a.Cout % 64 != 0) return {1, 1};
   return {2, 1};
 }
@@ -511,8 +498,8 @@ static Hx2qCut hx2q_cut(const ConvArgs& a) {
 static int hx2q_tiles_per_wg(const ConvArgs& a) {
   const Hx2qCut c = hx2q_cut(a);
   const int tiles = geom_num_tiles(a.g, a.B), ncb = a.Cout / c.cb(), tps = a.g.tps;
-  if (g_hx2q_tpw) return g_hx2q_tpw;
-  const int target = (c.ng == 2 && c.nt == 2) ? g_hx2q_target / 2 : g_hx2q_target;
+  if (g_conv_tuning.hx2q_tpw) return g_conv_tuning.hx2q_tpw;
+  const int target = (c.ng == 2 && c.nt == 2) ? g_conv_tuning.hx2q_target / 2 : g_conv_tuning.hx2q_target;
   int tpw = 1;
   while (tpw * 2 <= 4 && (tiles / (tpw * 2)) * ncb >= target && ((tpw * 2) % tps == 0 || tps % (tpw * 2) == 0)) tpw *= 2;
   return tpw;
@@ -528,7 +515,7 @@ static size_t hx2q_lds_bytes(const ConvArgs& a, int tpw) {
 }
 
 bool conv_hx2q_supported(const ConvArgs& a, int mode) {
-  if (!g_hx2q_min) return false;
+  if (!g_conv_tuning.hx2q_min) return false;
   if (mode != CONV_S1) return false;
   if (!a.gn_stats0) return false;  // convs of raw inputs (the upsamplers) stay on conv_mfma_hx2p_kernel
   if (!conv_hx2_supported(a, mode) || !conv_hx2_gn_supported(a, mode)) return false;
@@ -544,7 +531,7 @@ bool conv_hx2q_supported(const ConvArgs& a, int mode) {
   if (a.Cout % c.cb() != 0 || !(c.cb() == nb || (c.cb() == 64 && nb == 128))) return false;
   const int tpw = hx2q_tiles_per_wg(a);
   if (hx2q_lds_bytes(a, tpw) > ((c.ng == 2 && c.nt == 2) ? 160 : 80) * 1024) return false;
-  if (geom_num_tiles(g, a.B) * (a.Cout / c.cb()) < g_hx2q_min) return false;
+  if (geom_num_tiles(g, a.B) * (a.Cout / c.cb()) < g_conv_tuning.hx2q_min) return false;
   {  // the GroupNorm prologue must cut a row over the same number of waves as conv_mfma_hx2p_kernel (bit-identical tables)
     const int rows = hx2q_rows(a, tpw), cpg = (a.C0 + a.C1) / 8;
     const int need = cpg <= 8 ? 1 : (cpg <= 16 ? 2 : 4);
@@ -552,15 +539,16 @@ bool conv_hx2q_supported(const ConvArgs& a, int mode) {
   }
   // Where it pays (tools/kbench, same box, B = 512): 64 -> 64 at 32x32 +9..10 %, 128 -> 64 +1 %; with a fused 1x1 skip
   // (192 -> 64: -1.5 %), at 16x16 (-3 %) and with Cout = 128 (two workgroups per tile transform the halo twice:
-  // -3..-8 %) conv_mfma_hx2p_kernel is faster.  g_hx2q_all (kbench) lifts the restriction.
-  if (g_hx2q_all) return true;
+  // -3..-8 %) conv_mfma_hx2p_kernel is faster.  ConvTuning::hx2q_all (kbench) lifts the restriction.
+  if (g_conv_tuning.hx2q_all) return true;
   // Cout = 32 (the MNIST net's 32x32 level, where a tile has 6-18 units and the per-tile fixed costs dominate):
   // 32 -> 32 +25..30 %, 64 -> 32 +16 %, 96 -> 32 +2.5 % at B = 512; +10 % / 0 at B = 256
   if (a.Cout % 64 != 0) return g.W == 32;
   return g.W == 32 && a.Cout == 64 && a.C0 + a.C1 <= 128 && a.res_mode != 2;
 }
 
-// The cuts with 64-channel wave tiles are built for tools/kbench only (-DRGFM_HX2Q_ALL_CUTS): measured against
+// Every instantiation: X(log2 of the raster width, fused 1x1 skip, NG, NT).  conv_hx2q_init and launch_conv_hx2q both expand
+// this list.  The cuts with 64-channel wave tiles (NT = 2) are not instantiated: measured against
 // conv_mfma_hx2p_kernel over every layer shape of the two U-Nets at B = 512 (tools/kbench/scripts/q11.sh), {1,2} is
 // 2..25 % slower everywhere and {2,2} -- conv_mfma_hx2p's own tile behind the tile stream -- within +-2 %: the stream
 // pays where a tile's K loop is short (Cout <= 64 at 32x32), not where hx2p's interleaved units already hide the
@@ -577,8 +565,8 @@ int conv_hx2q_init() {
   return rc;
 }
 
-void launch_conv_hx2q(const ConvArgs& a_in, int mode, hipStream_t s) {
-  (void)mode;
+bool launch_conv_hx2q(const ConvArgs& a_in, int mode, hipStream_t s) {
+  if (mode != CONV_S1) return false;
   ConvArgs a = a_in;
   const int tiles = geom_num_tiles(a.g, a.B);
   const Hx2qCut c = hx2q_cut(a);
@@ -588,11 +576,12 @@ void launch_conv_hx2q(const ConvArgs& a_in, int mode, hipStream_t s) {
   const size_t lds = hx2q_lds_bytes(a, tpw);
   const int wl = a.g.W == 32 ? 5 : 4;
   const bool sk = a.res_mode == 2;
-#define LAUNCHQ(WL, SK, G, T)                                                                                         \
-  if (wl == (WL) && sk == (SK) && c.ng == (G) && c.nt == (T))                                                         \
-    hipLaunchKernelGGL((conv_mfma_hx2q_kernel<WL, SK, G, T>), grid, dim3(256 * (G)), lds, s, a, tiles, tpw, nrows);
+#define LAUNCHQ(WL, SK, G, T)                                   \
+  if (wl == (WL) && sk == (SK) && c.ng == (G) && c.nt == (T)) { \
+    hipLaunchKernelGGL((conv_mfma_hx2q_kernel<WL, SK, G, T>), grid, dim3(256 * (G)), lds, s, a, tiles, tpw, nrows); return true; }
   HX2Q_FOR_ALL(LAUNCHQ)
 #undef LAUNCHQ
+  return false;
 }
 #undef HX2Q_FOR_ALL
 

@@ -204,9 +204,6 @@ __global__ __launch_bounds__(256 * NG, 1) void conv_mfma_hx2s_kernel(const ConvA
 }
 
 // ---------------------------------------------------------------- host side
-static int g_hx2s_on = 1;
-void conv_hx2s_set(int v) { g_hx2s_on = v; }
-
 static int hx2s_ng(const ConvArgs& a) { return a.Cout % 64 == 0 ? 2 : 1; }
 static size_t hx2s_lds_bytes(const ConvArgs& a) {
   const int W = a.g.W, spt = W == 16 ? 1 : 4;
@@ -214,7 +211,7 @@ static size_t hx2s_lds_bytes(const ConvArgs& a) {
 }
 
 bool conv_hx2s_supported(const ConvArgs& a, int mode) {
-  if (!g_hx2s_on || mode != CONV_S2) return false;
+  if (!g_conv_tuning.hx2s_on || mode != CONV_S2) return false;
   if (!a.wpkh9 || !a.hq || !a.range_flag) return false;
   if (a.C1 != 0 || a.ab || a.gn_stats0 || a.res_mode != 0 || a.temb || a.ep_scale || a.fin_ab) return false;
   const TileGeom& g = a.g;
@@ -226,27 +223,29 @@ bool conv_hx2s_supported(const ConvArgs& a, int mode) {
   return hx2s_lds_bytes(a) <= 160 * 1024;
 }
 
+// Every instantiation: X(log2 of the output width, 32-channel groups).  conv_hx2s_init and launch_conv_hx2s both expand this list.
+#define HX2S_FOR_ALL(X) X(4, 1) X(4, 2) X(3, 1) X(3, 2)
+
 int conv_hx2s_init() {
   int rc = 0;
-#define RAISES(WL, G) rc |= raise_lds_limit(&conv_mfma_hx2s_kernel<WL, G>, 160 * 1024)
-  RAISES(4, 1); RAISES(4, 2); RAISES(3, 1); RAISES(3, 2);
+#define RAISES(WL, G) rc |= raise_lds_limit(&conv_mfma_hx2s_kernel<WL, G>, 160 * 1024);
+  HX2S_FOR_ALL(RAISES)
 #undef RAISES
   return rc;
 }
 
-void launch_conv_hx2s(const ConvArgs& a, hipStream_t s) {
+bool launch_conv_hx2s(const ConvArgs& a, int mode, hipStream_t s) {
+  if (mode != CONV_S2) return false;
   const int ng = hx2s_ng(a), tiles = geom_num_tiles(a.g, a.B);
   const dim3 grid(tiles, a.Cout / (32 * ng));
   const size_t lds = hx2s_lds_bytes(a);
-#define LAUNCHS(WL, G) hipLaunchKernelGGL((conv_mfma_hx2s_kernel<WL, G>), grid, dim3(256 * (G)), lds, s, a, tiles)
-  if (a.g.W == 16) {
-    if (ng == 2) LAUNCHS(4, 2);
-    else LAUNCHS(4, 1);
-  } else {
-    if (ng == 2) LAUNCHS(3, 2);
-    else LAUNCHS(3, 1);
-  }
+  const int wl = a.g.W == 16 ? 4 : 3;
+#define LAUNCHS(WL, G) \
+  if (wl == (WL) && ng == (G)) { hipLaunchKernelGGL((conv_mfma_hx2s_kernel<WL, G>), grid, dim3(256 * (G)), lds, s, a, tiles); return true; }
+  HX2S_FOR_ALL(LAUNCHS)
 #undef LAUNCHS
+  return false;
 }
+#undef HX2S_FOR_ALL
 
 }  // namespace rgfm

@@ -413,20 +413,29 @@ bool conv_hx2w_supported(const ConvArgs& a, int mode) {
   return hx2w_lds_bytes(a) <= 160 * 1024;
 }
 
+// Every instantiation: X(log2 of the raster width).  conv_hx2w_init and launch_conv_hx2w both expand this list.
+#define HX2W_FOR_ALL(X) X(4) X(5)
+
 int conv_hx2w_init() {
   int rc = 0;
-
-  rc |= raise_lds_limit(&conv_mfma_hx2w_kernel<4>, 160 * 1024);
-  rc |= raise_lds_limit(&conv_mfma_hx2w_kernel<5>, 160 * 1024);
+#define RAISEWN(WL) rc |= raise_lds_limit(&conv_mfma_hx2w_kernel<WL>, 160 * 1024);
+  HX2W_FOR_ALL(RAISEWN)
+#undef RAISEWN
   return rc;
 }
 
-void launch_conv_hx2w(const ConvArgs& a, hipStream_t s) {
+bool launch_conv_hx2w(const ConvArgs& a, int mode, hipStream_t s) {
+  if (mode != CONV_S1) return false;
   const int tiles = geom_num_tiles(a.g, a.B);
   const dim3 grid(tiles, a.Cout / 64);
   const size_t lds = hx2w_lds_bytes(a);
-  if (a.g.W == 16) hipLaunchKernelGGL((conv_mfma_hx2w_kernel<4>), grid, dim3(512), lds, s, a, tiles);
-  else hipLaunchKernelGGL((conv_mfma_hx2w_kernel<5>), grid, dim3(512), lds, s, a, tiles);
+  const int wl = a.g.W == 16 ? 4 : 5;
+#define LAUNCHWN(WL) \
+  if (wl == (WL)) { hipLaunchKernelGGL((conv_mfma_hx2w_kernel<WL>), grid, dim3(512), lds, s, a, tiles); return true; }
+  HX2W_FOR_ALL(LAUNCHWN)
+#undef LAUNCHWN
+  return false;
 }
+#undef HX2W_FOR_ALL
 
 }  // namespace rgfm

@@ -1,5 +1,6 @@
 // rgfm_host.h -- host-side internals shared by the translation units of the C ABI (api_*.cpp): error text, the
-// hipEvent kernel-class timers, workspace carving, the per-thread run-time switches, per-device state, conv dispatch,
+// hipEvent kernel-class timers, workspace carving, the per-thread run-time switches (Modes; with the process-wide
+// ConvTuning of rgfm_kernels.h the only two places that can change conv routing), per-device state, conv dispatch,
 // the U-Net handle and its network walk (used by the samplers and the gradient-guided loop too), the guidance launch and
 // the shared paired Euler loop.  Not part of the public ABI (that is include/rgfm.h); everything here is `inline` /
 // C++17 inline variables, so every unit sees ONE definition.
@@ -238,7 +239,11 @@ inline bool on_gfx950() {
   return strncmp(p.gcnArchName, "gfx950", 6) == 0;
 }
 
-// Run-time switches, read from the environment ONCE per API call (refresh_modes), never on the launch path:
+// Run-time switches, read from the environment ONCE per API call (refresh_modes), never on the launch path.  What can
+// change conv routing is described in exactly two places: Modes (per host thread: which kernels are eligible) and
+// ConvTuning (rgfm_kernels.h; process-wide: thresholds and cuts inside the kernels' own supported() / launch code).
+// refresh_modes fills both -- ConvTuning's RGFM_HX2D cut, RGFM_WINO_W32, RGFM_S2_F32 and RGFM_CONV_SIMPLE -- except
+// RGFM_HX2P_HALF, which belongs to the device's CU count and is read with it (ensure_init).
 //   RGFM_CONV = hx2 (default: conv_mfma_hx2.hip, fp32 operands as two scaled fp16 planes, three f16-MFMA products
 //               per fp32 product) | bx3 (conv_mfma_bx3.hip: three exact bf16 planes, six products; fp32 range)
 //               | f32 (conv_mfma.hip: v_mfma_f32_32x32x2_f32 everywhere);
@@ -286,7 +291,7 @@ inline void refresh_modes() {
   m.c8 = !(e && e[0] == '0');
   e = getenv("RGFM_HX2D");
   m.pfmt = !(e && e[0] == '0');
-  conv_hx2d_set(e && e[0] == '1' ? 1 : (e && e[0] == '2' ? 2 : 3));  // (1 / 2: one cut of conv_mfma_hx2d.hip everywhere -- A/B; process-wide, tools only)
+  g_conv_tuning.hx2d_cut = e && e[0] == '1' ? 1 : (e && e[0] == '2' ? 2 : 3);
   e = getenv("RGFM_WINO");
   m.wino = e && e[0] == '1';
   e = getenv("RGFM_UP_T2");
@@ -296,6 +301,10 @@ inline void refresh_modes() {
   e = getenv("RGFM_GRAPH");
   m.graph = e && e[0] == '1';
   g_modes = m;
+  e = getenv("RGFM_WINO_W32");
+  g_conv_tuning.wino_w32 = e ? atoi(e) : 0;
+  g_conv_tuning.s2_f32 = getenv("RGFM_S2_F32") != nullptr;
+  g_conv_tuning.f32_simple = getenv("RGFM_CONV_SIMPLE") != nullptr;
 }
 
 // A handle's own conv arithmetic (rgfm_unet_set_conv_mode / rgfm_fmnet_set_conv_mode; -1: the environment's) for the
@@ -342,13 +351,13 @@ inline int ensure_init() {
   if (dev < 0 || dev >= MAX_DEVICES) return fail(RGFM_EINVAL, "device ordinal %d out of range (max %d)", dev, MAX_DEVICES - 1);
   DevState& d = g_dev[dev];
   if (!d.init) {
-    if (conv_mfma_init() != 0 || conv_bx3_init() != 0 || conv_hx2_init() != 0 || conv_hx2p_init() != 0 || conv_hx2q_init() != 0 ||
-        conv_hx2s_init() != 0 || conv_hx2c_init() != 0 || conv_hx2d_init() != 0 || conv_hx2w_init() != 0 || guid_apply_init() != 0)
-      return fail(RGFM_EHIP, "hipFuncSetAttribute(MaxDynamicSharedMemorySize) failed");
+    int rc = guid_apply_init();
+    for (const ConvKernel& k : CONV_KERNELS) rc |= k.init();
+    if (rc != 0) return fail(RGFM_EHIP, "hipFuncSetAttribute(MaxDynamicSharedMemorySize) failed");
     hipDeviceProp_t p;
     if (hipGetDeviceProperties(&p, dev) == hipSuccess) d.num_cus = p.multiProcessorCount;
-    conv_hx2p_set_half(d.num_cus);  // launches with fewer 128-channel workgroups than CUs take 64-channel workgroups
-    if (const char* e = getenv("RGFM_HX2P_HALF")) conv_hx2p_set_half(atoi(e));  // (A/B of that threshold; every cut gives the same bits)
+    const char* e = getenv("RGFM_HX2P_HALF");
+    g_conv_tuning.hx2p_half = e ? atoi(e) : d.num_cus;  // launches with fewer 128-channel workgroups than CUs take 64-channel workgroups
     HIP_TRY(hipStreamCreateWithFlags(&d.side, hipStreamNonBlocking));
     HIP_TRY(hipMalloc(&d.zeros, 256));
     HIP_TRY(hipMemset(d.zeros, 0, 256));
@@ -367,8 +376,7 @@ inline int ensure_init() {
 // costs less per chunk than the direct kernels', its epilogue (the output transform through LDS) more -- so the long-K
 // layers: 128 or more input channels.  By layer shape only, never by batch.
 inline bool hx2w_pays(const ConvArgs& c) {
-  static const int w32_only = getenv("RGFM_WINO_W32") ? atoi(getenv("RGFM_WINO_W32")) : 0;  // (A/B: the 32x32 layers only)
-  return c.wpkw != nullptr && c.C0 + c.C1 >= 128 && (!w32_only || c.g.W == 32);
+  return c.wpkw != nullptr && c.C0 + c.C1 >= 128 && (!g_conv_tuning.wino_w32 || c.g.W == 32);
 }
 
 // Which kernel launch_conv sends this launch to (RGFM_ROUTE_*): the one place the predicate chain is written.
@@ -396,18 +404,12 @@ inline bool p_producer_ok(const ConvArgs& c, int mode) {
          (c.Cout == 64 || c.Cout == 128 || c.Cout == 256) && !c.ep_scale && !c.fin_ab;
 }
 
-inline void launch_conv_on(int route, const ConvArgs& c, int mode, hipStream_t s) {
-  switch (route) {
-    case RGFM_ROUTE_HX2D: launch_conv_hx2d(c, s); break;
-    case RGFM_ROUTE_HX2W: launch_conv_hx2w(c, s); break;
-    case RGFM_ROUTE_HX2S: launch_conv_hx2s(c, s); break;
-    case RGFM_ROUTE_HX2C: launch_conv_hx2c(c, s); break;
-    case RGFM_ROUTE_HX2Q: launch_conv_hx2q(c, mode, s); break;
-    case RGFM_ROUTE_HX2P: launch_conv_hx2p(c, mode, s); break;
-    case RGFM_ROUTE_HX2: launch_conv_hx2(c, mode, s); break;
-    case RGFM_ROUTE_BX3: launch_conv_bx3(c, mode, s); break;
-    default: launch_conv_mfma(c, mode, s); break;
-  }
+// A launch whose key matches no instantiation of its kernel launches nothing: the error text says so (rgfm_last_error).
+inline bool launch_conv_on(int route, const ConvArgs& c, int mode, hipStream_t s) {
+  const ConvKernel& k = CONV_KERNELS[route];
+  if (k.launch(c, mode, s)) return true;
+  fail(RGFM_EINVAL, "no %s instantiation for mode %d, Cout %d, %d x %d raster, res_mode %d", k.name, mode, c.Cout, c.g.H, c.g.W, c.res_mode);
+  return false;
 }
 
 // routes: the handle's per-route launch counts (RGFM_ROUTE_SLOTS entries), or null

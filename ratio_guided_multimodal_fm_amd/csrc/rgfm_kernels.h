@@ -16,6 +16,8 @@
 #include <stddef.h>
 #include <stdint.h>
 
+#include "../../include/rgfm.h"  // RGFM_ROUTE_*
+
 namespace rgfm {
 
 constexpr int KC = 16;   // input channels per K-chunk of the MFMA conv
@@ -230,73 +232,122 @@ struct TimeEmbedArgs {
   float* emb_out;          // optional [nt][mc]: the sinusoidal embedding itself (parity hook)
 };
 
-void launch_conv_mfma(const ConvArgs& a, int mode, hipStream_t s);
-size_t conv_mfma_lds_bytes(const ConvArgs& a);
-int conv_mfma_init();  // raises the dynamic-LDS limit of every instantiation
+// ---- the conv kernels (conv_mfma*.hip), one group per kernel.  Each file lists its instantiations ONCE (*_FOR_ALL):
+// conv_*_init() expands the list to raise every instantiation's dynamic-LDS limit (0 = success), launch_conv_*() to launch
+// the one whose key matches (ConvArgs, mode, ConvTuning) -- false, and no launch, when none does.  conv_*_supported() is
+// the kernel's line of the predicate chain conv_route (the fp32 kernel takes everything).
 
-// fp32 conv with operands split into three bf16 planes, on the bf16 matrix cores (conv_mfma_bx3.hip)
+// Process-wide tuning of the conv kernels' host side: with Modes (rgfm_host.h), everything that can change which kernel
+// -- or which cut of one -- a launch takes.  The library writes hx2p_half (ensure_init: per device, the last one wins)
+// and the four environment fields (refresh_modes: once per API call); the rest keep their defaults unless tools/kbench
+// sets them.  Not thread_local: whoever sets a field sets it for every thread that launches.  Every cut of a kernel
+// gives the same bits, so none of these changes a result.
+struct ConvTuning {
+  int hx2p_half = 256;     // conv_mfma_hx2p.hip: launches with fewer workgroups than this are cut finer -- 64-channel halves,
+                           // four-wave workgroups (0: never).  The device's CU count, or RGFM_HX2P_HALF=n (A/B of the threshold)
+  int hx2p_w4 = 0;         // kbench: 1 = four-wave workgroups forced where Cout % 128 != 0, 2 = wherever two fit on a CU
+  int hx2q_min = 1024;     // conv_mfma_hx2q.hip: launches with fewer (tile, channel block) pairs stay on hx2p (0: never runs) -- at
+                           // two workgroups per CU the stream needs >= 2 tiles per workgroup to pay (kbench: B = 128 rows lose)
+  int hx2q_target = 512;   // workgroups a launch is cut into when it has the tiles: two per CU (> 0)
+  int hx2q_tpw = 0;        // kbench: force the tiles per workgroup (0: hx2q_tiles_per_wg)
+  int hx2q_cut = 0;        // kbench: force the workgroup cut, 10 NG + NT (0: hx2q_cut)
+  int hx2q_all = 0;        // kbench: 1 = every supported shape, not only those where it is the faster kernel
+  int hx2s_on = 1;         // conv_mfma_hx2s.hip: 0 = never (Modes::s2 is the per-call switch)
+  int hx2c_on = 1;         // conv_mfma_hx2c.hip: 0 = never (Modes::c8 is the per-call switch)
+  int hx2c_all = 0;        // kbench: 1 = every supported shape, also the fused-skip layers where hx2p is faster
+  int hx2d_cut = 3;        // conv_mfma_hx2d.hip: 0 off, 1 the eight-wave kernel everywhere, 2 the four-wave kernel everywhere,
+                           // 3 by layer shape.  RGFM_HX2D=1|2 (A/B; RGFM_HX2D=0 is Modes::pfmt)
+  int wino_w32 = 0;        // RGFM_WINO_W32=1: with RGFM_WINO=1, the Winograd form for the 32x32 layers only (A/B)
+  bool s2_f32 = false;     // RGFM_S2_F32 set: stride-2 convs off conv_mfma_bx3.hip, i.e. on the fp32 kernel (A/B)
+  bool f32_simple = false; // RGFM_CONV_SIMPLE set: conv_mfma.hip's non-prefetching kernel wherever it exists (debug)
+};
+inline ConvTuning g_conv_tuning;
+
+int conv_fin_expected(const ConvArgs& a, int mode);  // arrivals per sample for ConvArgs::fin_expected (all conv_mfma* kernels)
+
+// conv_mfma.hip: exact fp32 MFMA, every shape
+int conv_mfma_init();
+bool launch_conv_mfma(const ConvArgs& a, int mode, hipStream_t s);
+size_t conv_mfma_lds_bytes(const ConvArgs& a);
+
+// conv_mfma_bx3.hip: fp32 conv with operands split into three bf16 planes, on the bf16 matrix cores
 bool conv_bx3_supported(const ConvArgs& a, int mode);
 bool conv_bx3_gn_supported(const ConvArgs& a, int mode);  // a.gn_* filled: can the kernel take the norm itself?
-int conv_fin_expected(const ConvArgs& a, int mode);  // arrivals per sample for ConvArgs::fin_expected (all conv_mfma* kernels)
 int conv_bx3_init();
-void launch_conv_bx3(const ConvArgs& a, int mode, hipStream_t s);
+bool launch_conv_bx3(const ConvArgs& a, int mode, hipStream_t s);
 void launch_pack_conv_bx3(const float* w, void* out, int Cout, int Cin, int taps, hipStream_t s);
 void launch_pack_deconv_bx3(const float* w, void* out, int Cin, int Cout, hipStream_t s);
 void launch_pack_conv_bx3_s2(const float* w, void* out, int Cout, int Cin, hipStream_t s);  // weights of a stride-2 3x3 conv
 
-// fp32 conv with operands split into two scaled fp16 planes, on the f16 matrix cores (conv_mfma_hx2.hip)
+// conv_mfma_hx2.hip: fp32 conv with operands split into two scaled fp16 planes, on the f16 matrix cores
 bool conv_hx2_supported(const ConvArgs& a, int mode);
 bool conv_hx2_gn_supported(const ConvArgs& a, int mode);
 int conv_hx2_init();
-void launch_conv_hx2(const ConvArgs& a, int mode, hipStream_t s);
-// producer / consumer pipelined version for CONV_S1 / CONV_UP2 (conv_mfma_hx2p.hip); same arguments
+bool launch_conv_hx2(const ConvArgs& a, int mode, hipStream_t s);
+// packs w (mode CONV_S1: [Cout][Cin][taps]; CONV_S2: the phase-major stride-2 order; CONV_T2: a ConvTranspose2d
+// weight [Cin][Cout][4][4], taps ignored) and writes the scale record hq[4] (device)
+void launch_pack_conv_hx2(const float* w, void* out, float* hq, int Cout, int Cin, int taps, int mode, hipStream_t s);
+// w [Cout][Cin][3][3] of "nearest-upsample x 2, then 3x3 conv" -> the ConvTranspose2d(4, 2, 1) weight K [Cin][Cout][4][4] of
+// the same linear map: K[ky][kx] = sum of w[i][j] over i in A(ky), j in A(kx), A = {2}, {1, 2}, {0, 1}, {0} (unet_kernels.hip)
+void launch_up2_as_deconv(const float* w, float* k, int Cout, int Cin, hipStream_t s);
+
+// conv_mfma_hx2p.hip: producer / consumer pipelined version for CONV_S1 / CONV_UP2 / CONV_T2; same arguments
 bool conv_hx2p_supported(const ConvArgs& a, int mode);
 int conv_hx2p_init();
-void conv_hx2p_set_half(int v);  // launches with fewer workgroups than this are cut finer (0: never; the CU count)
-void conv_hx2p_set_w4(int v);  // tools/kbench A/B: 1 / 2 = four-wave workgroups forced, see conv_mfma_hx2p.hip
-void launch_conv_hx2p(const ConvArgs& a, int mode, hipStream_t s);
-// four-waves-per-SIMD version (conv_mfma_hx2q.hip: one tile x 64 channels at a time, two workgroups per CU, several
+bool launch_conv_hx2p(const ConvArgs& a, int mode, hipStream_t s);
+
+// conv_mfma_hx2q.hip: four-waves-per-SIMD version (one tile x 64 channels at a time, two workgroups per CU, several
 // tiles per workgroup behind one continuous staging stream) for full stride-1 launches over 16- / 32-pixel-wide
 // rasters with Cout % 64 == 0 and a consumer-side input norm; bit-identical results
 bool conv_hx2q_supported(const ConvArgs& a, int mode);
 int conv_hx2q_init();
+bool launch_conv_hx2q(const ConvArgs& a, int mode, hipStream_t s);
+
 // conv_mfma_hx2s.hip: the Downsample convs (stride 2, raw input) with a chunk's four parity planes staged together
 bool conv_hx2s_supported(const ConvArgs& a, int mode);
 int conv_hx2s_init();
-void conv_hx2s_set(int on);
-void launch_conv_hx2s(const ConvArgs& a, hipStream_t s);
+bool launch_conv_hx2s(const ConvArgs& a, int mode, hipStream_t s);
+
 // conv_mfma_hx2c.hip: the stride-1 convs of the 8x8 level, one barrier per chunk (cut for the workgroup's serial chain)
 bool conv_hx2c_supported(const ConvArgs& a, int mode);
 int conv_hx2c_init();
-void conv_hx2c_set(int on);
-void conv_hx2c_set_all(int on);
-void launch_conv_hx2c(const ConvArgs& a, hipStream_t s);
+bool launch_conv_hx2c(const ConvArgs& a, int mode, hipStream_t s);
+
 // conv_mfma_hx2d.hip: stride-1 convs of the 16x16 / 8x8 levels over a P-format input (ConvArgs::pin0), staged by LDS-DMA only
 bool conv_hx2d_supported(const ConvArgs& a, int mode);
 int conv_hx2d_init();
-void conv_hx2d_set(int on);
-void launch_conv_hx2d(const ConvArgs& a, hipStream_t s);
+bool launch_conv_hx2d(const ConvArgs& a, int mode, hipStream_t s);
 // P format of silu(scale x + shift) from an fp32 NHWC map and per-(sample, channel) pairs ab[B][C][2]
 void launch_hx_presplit(const float* in, const float* ab, void* pout, int B, int HW, int C, hipStream_t s);
-void conv_hx2q_set_min(int v);  // launches with fewer workgroups than this stay on conv_mfma_hx2p_kernel (0: never used)
-void conv_hx2q_set_target(int v);  // workgroups a launch is cut into when it has the tiles (two per CU)
-void conv_hx2q_set_tpw(int v);     // tools/kbench: force the tiles per workgroup
-void conv_hx2q_set_cut(int v);     // tools/kbench: force the workgroup cut (10 NG + NT: 11, 21, 12, 22)
-void conv_hx2q_set_all(int v);     // tools/kbench: 1 = every supported shape, not only those where it is the faster kernel
-void launch_conv_hx2q(const ConvArgs& a, int mode, hipStream_t s);
-// w [Cout][Cin][3][3] of "nearest-upsample x 2, then 3x3 conv" -> the ConvTranspose2d(4, 2, 1) weight K [Cin][Cout][4][4] of
-// the same linear map: K[ky][kx] = sum of w[i][j] over i in A(ky), j in A(kx), A = {2}, {1, 2}, {0, 1}, {0} (unet_kernels.hip)
-void launch_up2_as_deconv(const float* w, float* k, int Cout, int Cin, hipStream_t s);
-// packs w (mode CONV_S1: [Cout][Cin][taps]; CONV_S2: the phase-major stride-2 order; CONV_T2: a ConvTranspose2d
-// weight [Cin][Cout][4][4], taps ignored) and writes the scale record hq[4] (device)
-void launch_pack_conv_hx2(const float* w, void* out, float* hq, int Cout, int Cin, int taps, int mode, hipStream_t s);
 
-// Winograd F(2x2, 3x3) form of the stride-1 3x3 conv on the two-plane arithmetic (conv_mfma_hx2w.hip); its own packed weights
-void hx2_scale_launch(const float* w, size_t n, float* hq, hipStream_t s);
-void launch_pack_conv_hx2w(const float* w, void* out, float* hq, float* tmp, int Cout, int Cin, hipStream_t s);
+// conv_mfma_hx2w.hip: Winograd F(2x2, 3x3) form of the stride-1 3x3 conv on the two-plane arithmetic; its own packed weights
 bool conv_hx2w_supported(const ConvArgs& a, int mode);
 int conv_hx2w_init();
-void launch_conv_hx2w(const ConvArgs& a, hipStream_t s);
+bool launch_conv_hx2w(const ConvArgs& a, int mode, hipStream_t s);
+void hx2_scale_launch(const float* w, size_t n, float* hq, hipStream_t s);
+void launch_pack_conv_hx2w(const float* w, void* out, float* hq, float* tmp, int Cout, int Cin, hipStream_t s);
+
+// The conv kernels by route (RGFM_ROUTE_* of include/rgfm.h, whose names these are: _lib.ROUTES spells them the same).
+// ensure_init loops over it, launch_conv_on indexes it; WHICH route a launch takes is conv_route's chain (rgfm_host.h).
+struct ConvKernel {
+  const char* name;
+  int (*init)();
+  bool (*launch)(const ConvArgs& a, int mode, hipStream_t s);
+};
+inline constexpr ConvKernel CONV_KERNELS[RGFM_ROUTE_COUNT] = {
+    {"hx2d", conv_hx2d_init, launch_conv_hx2d},  // RGFM_ROUTE_HX2D
+    {"hx2w", conv_hx2w_init, launch_conv_hx2w},  // RGFM_ROUTE_HX2W
+    {"hx2s", conv_hx2s_init, launch_conv_hx2s},  // RGFM_ROUTE_HX2S
+    {"hx2c", conv_hx2c_init, launch_conv_hx2c},  // RGFM_ROUTE_HX2C
+    {"hx2q", conv_hx2q_init, launch_conv_hx2q},  // RGFM_ROUTE_HX2Q
+    {"hx2p", conv_hx2p_init, launch_conv_hx2p},  // RGFM_ROUTE_HX2P
+    {"hx2", conv_hx2_init, launch_conv_hx2},     // RGFM_ROUTE_HX2
+    {"bx3", conv_bx3_init, launch_conv_bx3},     // RGFM_ROUTE_BX3
+    {"f32", conv_mfma_init, launch_conv_mfma},   // RGFM_ROUTE_F32
+};
+static_assert(RGFM_ROUTE_HX2D == 0 && RGFM_ROUTE_HX2W == 1 && RGFM_ROUTE_HX2S == 2 && RGFM_ROUTE_HX2C == 3 && RGFM_ROUTE_HX2Q == 4 &&
+                  RGFM_ROUTE_HX2P == 5 && RGFM_ROUTE_HX2 == 6 && RGFM_ROUTE_BX3 == 7 && RGFM_ROUTE_F32 == 8,
+              "CONV_KERNELS is written in RGFM_ROUTE_* order");
 
 void launch_conv_in(const ConvInArgs& a, int cin, hipStream_t s);
 void launch_conv_out(const ConvOutArgs& a, int cimg, hipStream_t s);

@@ -139,3 +139,31 @@ def make_sweep_unet(tag, batch, device=None):
                     generator=torch.Generator().manual_seed(400 + i))
     t = torch.linspace(0.0, 0.99, batch) if batch > 1 else torch.tensor([0.99])
     return (m.to(device) if device is not None else m), x, t
+
+
+# ------------------------------------------------------------------ conv routing fixture (tests/golden/conv_routes.json)
+# Small descriptors whose per-route conv launch counts (rgfm_unet_conv_routes) are recorded by
+# tests/golden/make_conv_routes.py on the commit BEFORE a change of the conv dispatch and compared by
+# tests/test_gpu_configs.py after it.  Batch 1 and 4: under-filled launches (four-wave workgroups, 64-channel halves of
+# a 128-channel block); 4: exactly one tile of the rasters that put four samples into a tile; 130: a tile count that is
+# no multiple of the two-tile cut (and 32.5 four-sample tiles).
+def conv_route_cases():
+    """(key, FlexibleUNet kwargs, weight seed, batches) per descriptor of the grid."""
+    i = 0
+    for mc in (32, 64):
+        for size in (8, 16, 32):
+            for mult in ((1,), (1, 2), (1, 2, 2)):
+                cfg = dict(in_channels=1, img_size=size, model_channels=mc, channel_mult=mult, num_res_blocks=1)
+                yield f"mc{mc}_s{size}_m{'-'.join(map(str, mult))}", cfg, 300 + i, (1, 4, 130)
+                i += 1
+
+
+def conv_route_run(m, cfg, batch, device):
+    """One eval forward of `m` on seeded input: (output, {route: launches}, x, t)."""
+    g = torch.Generator().manual_seed(700 + batch)
+    x = torch.randn(batch, cfg["in_channels"], cfg["img_size"], cfg["img_size"], generator=g).to(device)
+    t = torch.rand(batch, generator=g).to(device)
+    with torch.no_grad():
+        out = m(x, t)
+    torch.cuda.synchronize()
+    return out, m._engine.conv_routes(device), x, t

@@ -22,6 +22,20 @@ def test_header_and_binding_agree():
     assert declared == set(_lib.SIGNATURES)
 
 
+def test_conv_kernel_table_follows_the_route_numbers():
+    """CONV_KERNELS (csrc/rgfm_kernels.h) is indexed by RGFM_ROUTE_*: its names are include/rgfm.h's route names in
+    index order -- the strings of _lib.ROUTES -- and every route has its own init and launch function."""
+    hdr = open(os.path.join(ROOT, "include", "rgfm.h")).read()
+    routes = sorted((int(i), n.lower()) for n, i in re.findall(r"#define RGFM_ROUTE_(\w+) (\d+)", hdr) if n not in ("COUNT", "T2", "SLOTS"))
+    assert tuple(n for _, n in routes) == _lib.ROUTES and [i for i, _ in routes] == list(range(len(_lib.ROUTES)))
+    src = open(os.path.join(ROOT, "ratio_guided_multimodal_fm_amd", "csrc", "rgfm_kernels.h")).read()
+    table = src[src.index("CONV_KERNELS[RGFM_ROUTE_COUNT] = {"):]
+    rows = re.findall(r'\{"(\w+)", (conv_\w+_init), (launch_conv_\w+)\},\s*// RGFM_ROUTE_(\w+)', table[:table.index("};")])
+    assert tuple(r[0] for r in rows) == _lib.ROUTES
+    assert all(r[0] == r[3].lower() for r in rows)
+    assert len({r[1] for r in rows}) == len({r[2] for r in rows}) == len(_lib.ROUTES)
+
+
 def test_library_exports_every_symbol():
     L = _lib.lib()
     for name in _lib.SIGNATURES:

@@ -18,7 +18,7 @@ import pytest
 import torch
 
 from oracle import oracle as O
-from helpers import golden, make_module, maxdiff, oracle_net, paired_noise
+from helpers import GOLDEN, conv_route_cases, conv_route_run, golden, make_module, maxdiff, oracle_net, paired_noise
 from ratio_guided_multimodal_fm_amd import _engine, _lib
 
 pytestmark = pytest.mark.gpu
@@ -619,3 +619,30 @@ def test_rows_do_not_depend_on_the_launch_shape(dev, tag):
     for lo, hi in ((0, 8), (250, 263), (500, 512)):
         part = m(x[lo:hi].contiguous(), t[lo:hi].contiguous())
         assert torch.equal(part, full[lo:hi]), (tag, lo, hi, float((part - full[lo:hi]).abs().max()))
+
+
+def test_conv_routes_of_small_descriptors_match_the_recorded_table(dev):
+    """Which conv kernel each launch of one eval forward goes to (rgfm_unet_conv_routes), for model_channels 32 / 64 x
+    img_size 8 / 16 / 32 x channel_mult (1,) / (1, 2) / (1, 2, 2) x batch 1 / 4 / 130 (helpers.conv_route_cases), against
+    tests/golden/conv_routes.json -- recorded by tests/golden/make_conv_routes.py with the library of the commit before
+    the host side of the conv kernels was rewritten.  And per case: a second forward of the same handle gives the same
+    bits -- a launch that silently did not happen would leave its output to whatever the workspace held."""
+    from ratio_guided_multimodal_fm_amd import models as M
+    from ratio_guided_multimodal_fm_amd.synth import load_synth
+    with open(os.path.join(GOLDEN, "conv_routes.json")) as f:
+        want = json.load(f)["cases"]
+    seen, wrong = set(), []
+    for key, cfg, seed, batches in conv_route_cases():
+        m = load_synth(M.FlexibleUNet(**cfg), seed).eval().to(dev)
+        for b in batches:
+            before = _engine.range_fallbacks
+            out, routes, x, t = conv_route_run(m, cfg, b, dev)
+            with torch.no_grad():
+                again = m(x, t)
+            assert _engine.range_fallbacks == before, (key, b)
+            assert torch.isfinite(out).all() and torch.equal(out, again), (key, b)
+            seen.add(f"{key}_b{b}")
+            if routes != want[f"{key}_b{b}"]:
+                wrong.append((f"{key}_b{b}", routes, want[f"{key}_b{b}"]))
+    assert seen == set(want) and len(seen) == 54
+    assert not wrong, wrong

@@ -79,22 +79,18 @@ int main(int argc, char** argv) {
   const int Sin = mode == CONV_UP2 ? S / 2 : (mode == CONV_S2 ? 2 * S : S);
   const int nt = Cout % 64 == 0 ? 2 : 1;
   CK(hipSetDevice(0));
-  conv_mfma_init();
-  conv_bx3_init();
-  conv_hx2_init();
-  conv_hx2p_init();
-  conv_hx2q_init();
-  conv_hx2s_init();
-  conv_hx2c_init();
-  conv_hx2d_init();
-  if (getenv("RGFM_HX2D")) conv_hx2d_set(atoi(getenv("RGFM_HX2D")));  // 1: eight waves, 2: four waves x two workgroups per CU
-  conv_hx2c_set_all(1);
-  if (getenv("RGFM_HX2Q_MIN")) conv_hx2q_set_min(atoi(getenv("RGFM_HX2Q_MIN")));
-  if (getenv("RGFM_HX2Q_TPW")) conv_hx2q_set_tpw(atoi(getenv("RGFM_HX2Q_TPW")));
-  conv_hx2q_set_all(1);
-  if (getenv("RGFM_HX2Q_CUT")) conv_hx2q_set_cut(atoi(getenv("RGFM_HX2Q_CUT")));
-  if (getenv("RGFM_HX2P_W4")) conv_hx2p_set_w4(atoi(getenv("RGFM_HX2P_W4")));
-  if (getenv("RGFM_HX2P_HALF")) conv_hx2p_set_half(atoi(getenv("RGFM_HX2P_HALF")));
+  for (const ConvKernel& k : CONV_KERNELS)
+    if (k.init() != 0) { printf("%s: raising the LDS limit failed\n", k.name); return 1; }
+  ConvTuning& tune = g_conv_tuning;  // (the library's defaults, then this tool's environment)
+  if (getenv("RGFM_HX2D")) tune.hx2d_cut = atoi(getenv("RGFM_HX2D"));  // 1: eight waves, 2: four waves x two workgroups per CU
+  tune.hx2c_all = 1;
+  if (getenv("RGFM_HX2Q_MIN")) tune.hx2q_min = atoi(getenv("RGFM_HX2Q_MIN"));
+  if (getenv("RGFM_HX2Q_TPW")) tune.hx2q_tpw = atoi(getenv("RGFM_HX2Q_TPW"));
+  tune.hx2q_all = 1;
+  if (getenv("RGFM_HX2Q_CUT")) tune.hx2q_cut = atoi(getenv("RGFM_HX2Q_CUT"));
+  if (getenv("RGFM_HX2P_W4")) tune.hx2p_w4 = atoi(getenv("RGFM_HX2P_W4"));
+  if (getenv("RGFM_HX2P_HALF")) tune.hx2p_half = atoi(getenv("RGFM_HX2P_HALF"));
+  tune.f32_simple = getenv("RGFM_CONV_SIMPLE") != nullptr;
 #ifdef RGFM_KB_SCAFFOLD
   if (getenv("RGFM_HX2P_CHUNK")) conv_hx2p_set_chunk(atoi(getenv("RGFM_HX2P_CHUNK")));
 #if RGFM_HX2P_QEXP
@@ -220,7 +216,7 @@ int main(int argc, char** argv) {
     aw.wpkw = whw, aw.hqw = hqw;
     if (getenv("RGFM_KB_GN")) aw = ap, aw.wpkw = whw, aw.hqw = hqw;  // the consumer-side norm (statistics) instead of the array
     CK(hipDeviceSynchronize());
-    if (conv_hx2w_init() != 0 || !conv_hx2w_supported(aw, mode)) { printf("hx2w: unsupported shape\n"); return 1; }
+    if (!conv_hx2w_supported(aw, mode)) { printf("hx2w: unsupported shape\n"); return 1; }
 #ifdef RGFM_KB_HX2W4
     conv_hx2w4_init();
 #endif
@@ -230,18 +226,20 @@ int main(int argc, char** argv) {
   if (hx2s && !conv_hx2s_supported(a, mode)) { printf("hx2s: unsupported shape\n"); return 1; }
   if (hx2c && !conv_hx2c_supported(ap, mode)) { printf("hx2c: unsupported shape\n"); return 1; }
   auto launch = [&]() {
-    if (f32) launch_conv_mfma(a, mode, 0);
-    else if (hx2) launch_conv_hx2(a, mode, 0);
-    else if (hx2p) launch_conv_hx2p(ap, mode, 0);
-    else if (hx2q) launch_conv_hx2q(ap, mode, 0);
-    else if (hx2s) launch_conv_hx2s(a, 0);
-    else if (hx2c) launch_conv_hx2c(ap, 0);
-    else if (hx2d) launch_conv_hx2d(ad, 0);
+    bool ok;
+    if (f32) ok = launch_conv_mfma(a, mode, 0);
+    else if (hx2) ok = launch_conv_hx2(a, mode, 0);
+    else if (hx2p) ok = launch_conv_hx2p(ap, mode, 0);
+    else if (hx2q) ok = launch_conv_hx2q(ap, mode, 0);
+    else if (hx2s) ok = launch_conv_hx2s(a, mode, 0);
+    else if (hx2c) ok = launch_conv_hx2c(ap, mode, 0);
+    else if (hx2d) ok = launch_conv_hx2d(ad, mode, 0);
 #ifdef RGFM_KB_HX2W4
-    else if (hx2w && getenv("RGFM_HX2W_CUT") && atoi(getenv("RGFM_HX2W_CUT")) == 2) launch_conv_hx2w4(aw, 0);
+    else if (hx2w && getenv("RGFM_HX2W_CUT") && atoi(getenv("RGFM_HX2W_CUT")) == 2) launch_conv_hx2w4(aw, 0), ok = true;
 #endif
-    else if (hx2w) launch_conv_hx2w(aw, 0);
-    else launch_conv_bx3(a, mode, 0);
+    else if (hx2w) ok = launch_conv_hx2w(aw, mode, 0);
+    else ok = launch_conv_bx3(a, mode, 0);
+    if (!ok) printf("no instantiation of the selected kernel for this shape / mode / cut: nothing was launched\n"), exit(1);
   };
   {  // reference: the exact-fp32 MFMA kernel on the same data
     const size_t no = (size_t)B * S * S * Cout, ns = (size_t)B * a.g.nparts * Cout * 2;
