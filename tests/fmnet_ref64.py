@@ -1,7 +1,13 @@
 """float64 torch.nn.functional restatement of FlowMatchingModel, written from the parameter layout of
 ratio_guided_multimodal_fm_amd/models/flow_matching.py: the yardstick of the training-pass tests
-(tests/test_gpu_fmnet_train.py), pinned to the reference's autograd by tests/test_fmnet_train_cpu.py.  Takes the
-module's state_dict (any dtype / device); evaluated in float64 on the CPU."""
+(tests/test_gpu_fmnet_train.py), pinned to the reference's autograd by tests/test_fmnet_train_cpu.py, and of the
+eval and sampler tests (tests/test_gpu_fmnet_eval.py), pinned by tests/test_fmnet_eval_cpu.py.  Takes the module's
+state_dict (any dtype / device); evaluated in float64 on the CPU.
+
+forward64 follows the dtype of the parameters it is given: over params_of(module, torch.float32) it is torch's own
+fp32 CPU evaluation of the same statements (t * freqs, sin, cos and the frequency table in fp32 as well), which is
+how the fp32 error of the architecture is measured against the float64 yardstick."""
+import functools
 import math
 
 import torch
@@ -10,16 +16,21 @@ import torch.nn.functional as F
 ENCODER_STRIDES = (1, 2, 2, 1)  # encoder.conv1..4: 28 -> 28 -> 14 -> 7 -> 7
 
 
-def params64(module, requires_grad=True):
-    """{name: float64 CPU leaf tensor} of the module's state_dict."""
-    return {k: v.detach().to("cpu", torch.float64).clone().requires_grad_(requires_grad)
+def params_of(module, dtype, requires_grad=False):
+    """{name: CPU leaf tensor of `dtype`} of the module's state_dict."""
+    return {k: v.detach().to("cpu", dtype).clone().requires_grad_(requires_grad)
             for k, v in module.state_dict().items()}
 
 
+def params64(module, requires_grad=True):
+    """{name: float64 CPU leaf tensor} of the module's state_dict."""
+    return params_of(module, torch.float64, requires_grad)
+
+
 def time_embedding64(t, dim):
-    """SinusoidalPositionEmbeddings: sin half first, divisor half - 1."""
+    """SinusoidalPositionEmbeddings: sin half first, divisor half - 1 (in t's dtype)."""
     half = dim // 2
-    freqs = torch.exp(torch.arange(half, dtype=torch.float64) * -(math.log(10000) / (half - 1)))
+    freqs = torch.exp(torch.arange(half, dtype=t.dtype) * -(math.log(10000) / (half - 1)))
     args = t[:, None] * freqs[None, :]
     return torch.cat([args.sin(), args.cos()], dim=-1)
 
@@ -28,11 +39,13 @@ def _gn_silu(h, sd, name):
     return F.silu(F.group_norm(h, 8, sd[name + ".weight"], sd[name + ".bias"], eps=1e-5))
 
 
-def forward64(sd, x, t):
-    """v = FlowMatchingModel(x, t) in float64 over the state_dict `sd`; feature_dim and time_emb_dim are read off the
-    Linear shapes."""
-    x = x.to(torch.float64)
-    t = t.to(torch.float64).reshape(-1)
+def forward64(sd, x, t, embed=time_embedding64):
+    """v = FlowMatchingModel(x, t) over the state_dict `sd`, in sd's dtype (float64 for params64); feature_dim and
+    time_emb_dim are read off the Linear shapes.  `embed(t [B], time_emb_dim)` -> the [B, time_emb_dim] columns that
+    are concatenated behind the features (the CPU tests put deliberately wrong embeddings here)."""
+    dtype = sd["encoder.fc.weight"].dtype
+    x = x.to(dtype)
+    t = torch.as_tensor(t).to(dtype).reshape(-1)
     if t.numel() == 1:
         t = t.expand(x.shape[0])
     F_dim = sd["encoder.fc.weight"].shape[0]
@@ -42,10 +55,198 @@ def forward64(sd, x, t):
         h = F.conv2d(h, sd[f"encoder.conv{i}.weight"], sd[f"encoder.conv{i}.bias"], stride=stride, padding=1)
         h = _gn_silu(h, sd, f"encoder.gn{i}")
     feat = F.linear(h.reshape(h.shape[0], -1), sd["encoder.fc.weight"], sd["encoder.fc.bias"])
-    comb = torch.cat([feat, time_embedding64(t, T_dim)], dim=1)
+    comb = torch.cat([feat, embed(t, T_dim)], dim=1)
     h = F.linear(comb, sd["decoder.fc1.weight"], sd["decoder.fc1.bias"]).reshape(-1, 256, 7, 7)
     for i in (1, 2):
         h = F.conv_transpose2d(h, sd[f"decoder.deconv{i}.weight"], sd[f"decoder.deconv{i}.bias"], stride=2, padding=1)
         h = _gn_silu(h, sd, f"decoder.gn{i}")
     h = _gn_silu(F.conv2d(h, sd["decoder.conv3.weight"], sd["decoder.conv3.bias"], padding=1), sd, "decoder.gn3")
     return F.conv2d(h, sd["decoder.conv_out.weight"], sd["decoder.conv_out.bias"], padding=1)
+
+
+def euler64(sd, x, num_steps, step_begin=0, step_end=None):
+    """The unguided Euler loop in float64: x <- x + forward64(x, t) dt for the steps [step_begin, step_end), with
+    dt = 1 / num_steps and t = step dt as Python doubles."""
+    dt = 1.0 / num_steps
+    x = x.to(torch.float64)
+    for step in range(step_begin, num_steps if step_end is None else step_end):
+        x = x + forward64(sd, x, torch.tensor([step * dt], dtype=torch.float64)) * dt
+    return x
+
+
+def pair64(sdx, sdy, x, y, mx, my, r, num_steps, gamma, step_begin=0, step_end=None, threshold=1e-3):
+    """The paired Euler loop in float64 with the MC guidance block of tests/guidance_ref64.py: both velocities at
+    t = step dt, guided where an MC set is given and t > threshold (the reference's `t > eps`, eps = 1e-3), then
+    x <- x + vx dt, y <- y + vy dt.  mx / my / r None: unguided.  Returns (x, y) as float64 tensors."""
+    from guidance_ref64 import guidance64
+    dt = 1.0 / num_steps
+    x, y = x.to(torch.float64), y.to(torch.float64)
+    for step in range(step_begin, num_steps if step_end is None else step_end):
+        t = step * dt
+        tt = torch.tensor([t], dtype=torch.float64)
+        vx, vy = forward64(sdx, x, tt), forward64(sdy, y, tt)
+        if mx is not None and t > threshold:
+            gx, gy, _, _ = guidance64(x.numpy(), y.numpy(), vx.numpy(), vy.numpy(), mx.numpy(), my.numpy(), r.numpy(), t,
+                                      gamma)
+            vx, vy = torch.from_numpy(gx).reshape(x.shape), torch.from_numpy(gy).reshape(y.shape)
+        x, y = x + vx * dt, y + vy * dt
+    return x, y
+
+
+# ------------------------------------------------------------------ the inputs of the eval tests
+# Shared by tests/test_fmnet_eval_cpu.py and tests/test_gpu_fmnet_eval.py; every float64 answer is computed once per
+# process and handed out read-only.
+SEED_W = 19  # tests/test_gpu_fmnet_train.py:module_of
+T_LATE = 1.0 - 1.0 / 1000
+
+# (feature_dim, time_emb_dim, batch, one shared t)
+EVAL_CASES = [
+    (256, 128, 37, False),   # the preset; pixel counts 37 * 784 / 196 / 49, none a multiple of 64
+    (64, 16, 5, True),       # the smallest descriptor: one 64-column block in the first Linear, T below one K chunk
+    (320, 48, 1, False),     # F + T = 368, no multiple of 64; one row
+    (1024, 1024, 3, False),  # the largest descriptor: the longest K of the second Linear, the widest concat
+    (128, 1008, 2, True),    # T >> F: the time columns dominate the concat
+    (256, 128, 70, False),   # partial four-sample tiles at 7x7, partial 64-row tiles in the Linears
+]
+EMBED_DIMS = [(64, 16), (320, 48), (128, 1008)]
+# the pairs the embedding test is asked to run, and one across the whole range: the early pair moves every column by
+# <= 1e-3, which the decoder of some descriptors carries into less than ten tolerances of output
+EMBED_PAIRS = [(0.0, 1e-3), (0.5, 0.5 + 2.0 ** -10), (0.999, 1.0), (0.0, 1.0)]
+
+
+@functools.lru_cache(maxsize=None)
+def module_cpu(F_dim, T_dim, seed=SEED_W):
+    """FlowMatchingModel(1, F, T) with the synthetic parameters of `seed`, on the CPU.  Shared: do not move or edit."""
+    from ratio_guided_multimodal_fm_amd import models as M
+    from ratio_guided_multimodal_fm_amd.synth import load_synth
+    return load_synth(M.FlowMatchingModel(1, F_dim, T_dim), seed).eval()
+
+
+@functools.lru_cache(maxsize=4)
+def sd64(F_dim, T_dim, seed=SEED_W):
+    return params64(module_cpu(F_dim, T_dim, seed), requires_grad=False)
+
+
+def eval_inputs(ci):
+    """(x [B,1,28,28], t [B] or [1]) of EVAL_CASES[ci], fp32.  Per-row t: t[0] = 0, t[-1] = 1 - 1/1000, uniform draws
+    between; one row or one shared t: the late end (where the embedding's arguments are largest) except for the
+    smallest descriptor, which takes t = 0."""
+    F_dim, T_dim, B, shared = EVAL_CASES[ci]
+    g = torch.Generator().manual_seed(1700 + ci)
+    x = torch.randn(B, 1, 28, 28, generator=g)
+    t = torch.rand(B, generator=g)
+    if shared or B == 1:
+        t = torch.tensor([0.0 if (F_dim, T_dim) == (64, 16) else T_LATE])
+    else:
+        t[0], t[-1] = 0.0, T_LATE
+    return x, t
+
+
+@functools.lru_cache(maxsize=None)
+def eval_ref(ci):
+    """float64 v of EVAL_CASES[ci] as a read-only numpy array."""
+    F_dim, T_dim, _, _ = EVAL_CASES[ci]
+    x, t = eval_inputs(ci)
+    with torch.no_grad():
+        v = forward64(sd64(F_dim, T_dim), x, t).numpy()
+    v.setflags(write=False)
+    return v
+
+
+def eval_scale(ci):
+    """What the output tolerance of EVAL_CASES[ci] is multiplied by: max(1, max |v64|), as the U-Net sweep scales its
+    activations, for the descriptors above the dims any fp32-oracle test runs (F or T > 320); 1 for the others, whose
+    bound stays the absolute one of test_fmnet_forward."""
+    F_dim, T_dim, _, _ = EVAL_CASES[ci]
+    return max(1.0, float(abs(eval_ref(ci)).max())) if max(F_dim, T_dim) > 320 else 1.0
+
+
+def embed_inputs(F_dim, T_dim):
+    """(x [2,1,28,28], ta [P], tb [P]) of the embedding test, fp32; row p of either launch is x[p % 2] at ta[p] / tb[p]."""
+    g = torch.Generator().manual_seed(1800 + F_dim + T_dim)
+    x = torch.randn(2, 1, 28, 28, generator=g)
+    ta = torch.tensor([a for a, _ in EMBED_PAIRS], dtype=torch.float32)
+    tb = torch.tensor([b for _, b in EMBED_PAIRS], dtype=torch.float32)
+    return x, ta, tb
+
+
+def embed_diff64(F_dim, T_dim, embed=time_embedding64):
+    """float64 v(x, ta) - v(x, tb): [len(EMBED_PAIRS), 2, 784], numpy."""
+    x, ta, tb = embed_inputs(F_dim, T_dim)
+    sd = sd64(F_dim, T_dim)
+    out = []
+    with torch.no_grad():
+        for a, b in zip(ta, tb):
+            out.append((forward64(sd, x, a.reshape(1), embed) - forward64(sd, x, b.reshape(1), embed)).reshape(2, -1))
+    return torch.stack(out).numpy()
+
+
+@functools.lru_cache(maxsize=None)
+def embed_ref(F_dim, T_dim):
+    d = embed_diff64(F_dim, T_dim)
+    d.setflags(write=False)
+    return d
+
+
+def embedding_divided_by_half(t, dim):
+    """The U-Net's frequency table (divisor half) where this net has half - 1."""
+    half = dim // 2
+    freqs = torch.exp(torch.arange(half, dtype=t.dtype) * -(math.log(10000) / half))
+    args = t[:, None] * freqs[None, :]
+    return torch.cat([args.sin(), args.cos()], dim=-1)
+
+
+def embedding_shifted_one_column(t, dim):
+    """The embedding written one column to the right of its place in the concat (the last column lost, a zero first)."""
+    e = time_embedding64(t, dim)
+    return torch.cat([torch.zeros_like(e[:, :1]), e[:, :-1]], dim=1)
+
+
+SAMPLER_B = 5
+SINGLE_DIMS = [(64, 16), (320, 48)]
+PAIR_DIMS = ((256, 128), (64, 16))  # the x net and the y net of the paired loop
+PAIR_SEED_Y = 20
+# (n_mc, gamma, num_steps, step_begin, step_end): the first four steps of 1000 -- step 1 has t = 0.001 exactly, which
+# `t > 1e-3` leaves unguided, step 2 is the first guided one -- and six steps over the whole range
+PAIR_CASES = [(n_mc, gamma, ns, 0, end) for n_mc in (9, 0) for gamma in (0.5, 2.0) for ns, end in ((1000, 4), (6, 6))]
+
+
+def single_inputs(F_dim, T_dim):
+    return torch.randn(SAMPLER_B, 1, 28, 28, generator=torch.Generator().manual_seed(1900 + F_dim + T_dim))
+
+
+@functools.lru_cache(maxsize=None)
+def single_ref(F_dim, T_dim, num_steps):
+    with torch.no_grad():
+        x = euler64(sd64(F_dim, T_dim), single_inputs(F_dim, T_dim), num_steps).numpy()
+    x.setflags(write=False)
+    return x
+
+
+def pair_inputs(n_mc):
+    """(x0, y0, mc_x1, mc_y1, mc_ratios), fp32; the MC entries None when n_mc == 0.  Independent N(0, 1) images and
+    ratios exp(0.5 N(0, 1)): early in the integration every MC sample carries weight ~ r_i / sum r."""
+    g = torch.Generator().manual_seed(2000)
+    x = torch.randn(SAMPLER_B, 1, 28, 28, generator=g)
+    y = torch.randn(SAMPLER_B, 1, 28, 28, generator=g)
+    if not n_mc:
+        return x, y, None, None, None
+    mx = torch.randn(n_mc, 1, 28, 28, generator=g)
+    my = torch.randn(n_mc, 1, 28, 28, generator=g)
+    r = torch.exp(0.5 * torch.randn(n_mc, generator=g))
+    return x, y, mx, my, r
+
+
+def pair_sds():
+    (fx, tx), (fy, ty) = PAIR_DIMS
+    return sd64(fx, tx), sd64(fy, ty, PAIR_SEED_Y)
+
+
+@functools.lru_cache(maxsize=None)
+def pair_ref(n_mc, gamma, num_steps, step_begin, step_end, threshold=1e-3):
+    sdx, sdy = pair_sds()
+    with torch.no_grad():
+        x, y = pair64(sdx, sdy, *pair_inputs(n_mc), num_steps, gamma, step_begin, step_end, threshold)
+    x, y = x.numpy(), y.numpy()
+    x.setflags(write=False), y.setflags(write=False)
+    return x, y
