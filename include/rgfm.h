@@ -230,6 +230,19 @@ int rgfm_ratio_workspace_bytes(const rgfm_ratio* h, int n, size_t* bytes);
 int rgfm_ratio_eval(rgfm_ratio* h, const float* x, const float* y, float* out, int n, int what,
                     void* ws, size_t ws_bytes, rgfm_stream_t stream);
 
+/* Cross evaluation: out[nx][ny], row-major, is `what` (RGFM_RATIO_OUT_*) of EVERY pair (x_i, y_j) -- the matrix that
+ * conditional sampling needs (each condition image against each Monte-Carlo sample), which rgfm_ratio_eval gives only
+ * for the nx * ny explicitly tiled pairs.  Every kind.  Each encoder runs once (nx and ny images); the first score
+ * Linear acts on the concatenation [f_x | f_y], so W [f_x | f_y] + b = W[:, :F] f_x + W[:, F:] f_y + b is two small
+ * products per image and a sum per pair; the rest of the MLP runs over the pairs in chunks of a fixed number of pair
+ * indices (a library constant, independent of nx and ny: the workspace is bounded by the encoders and one chunk; a
+ * chunk may begin and end inside a matrix row).  RGFM_CROSS_ROWS=<pairs per chunk> overrides the constant (test hook,
+ * read on entry of both functions; results do not depend on it).  nx, ny >= 1.  Results agree with rgfm_ratio_eval on
+ * the tiled pairs to fp32 rounding (another summation order in the first Linear), not bitwise. */
+int rgfm_ratio_cross_workspace_bytes(const rgfm_ratio* h, int nx, int ny, size_t* bytes);
+int rgfm_ratio_eval_cross(rgfm_ratio* h, const float* x, int nx, const float* y, int ny, float* out, int what,
+                          void* ws, size_t ws_bytes, rgfm_stream_t stream);
+
 /* Gradient of the log-ratio, d log_ratio(x, y) / d(x, y): what torch.autograd.grad(model.log_ratio(x, y).sum(),
  * (x, y)) returns for the reference module in eval mode (ratio_flexible.py:347-385, ratio_estimator.py:137-191;
  * hand-written reverse pass).  RGFM_RATIO_MNIST_SVHN: gx[n,1,32,32], gy[n,3,32,32]; RGFM_RATIO_MNIST28: gx, gy
@@ -303,6 +316,24 @@ int rgfm_sample_pair(rgfm_unet* hx, rgfm_unet* hy, float* x_inout, float* y_inou
                      const float* mc_x1, const float* mc_y1, const float* mc_ratios, int n_mc,
                      int batch, int num_steps, double gamma, int step_begin, int step_end, void* ws,
                      size_t ws_bytes, rgfm_stream_t stream);
+
+/* Conditional sampling: one modality given images of the other.  Euler loop of ONE net, in place on
+ * s_inout[B,C,H,W], guided by the MC block of sample_mnist_svhn.py:124-171 with one side observed:
+ *   mc_set[N,C,H,W]: the target net's own unguided samples (the pre-phase of :89-104);
+ *   ratios[B][N]:    r(c_b, m_j) = exp(log_ratio) of condition image c_b against MC sample m_j (rgfm_ratio_eval_cross
+ *                    with RGFM_RATIO_OUT_RATIO; transposed when the condition is the estimator's y argument).
+ * Each step with t = step/num_steps > 1e-3: logp[b][j] = -0.5 |s_b - t m_j|^2 / sigma^2, p = exp(logp - max_j),
+ * w = (R / mean_j(R p)) (p / mean_j p) row-normalised, g = sum_j w[b][j] (m_j - s_b) / (1 - t + eps),
+ * v = (1 - gamma) v + gamma g, s += v dt -- the epsilons and scalar roundings of the paired block.  This IS the paired
+ * block with the observed side's Gaussian factor dropped (it does not depend on j, so it cancels in the normalised
+ * weights) and the shared ratio vector replaced by a ratio row per sample; the same kernels run it.
+ * Conventions of rgfm_sample_pair: in place, stream-ordered, nothing allocated or synchronised, 1 <= n_mc <= 4096, at
+ * most 4096 steps per call.  Steps with t <= 1e-3 use the fused Euler epilogue as rgfm_sample_single does.  Every
+ * launch goes to `stream`: one net has nothing to overlap, so there is no side stream and no graph replay. */
+int rgfm_sample_cond_workspace_bytes(const rgfm_unet* h, int batch, int n_mc, size_t* bytes);
+int rgfm_sample_cond(rgfm_unet* h, float* s_inout, const float* mc_set, const float* ratios, int n_mc, int batch,
+                     int num_steps, double gamma, int step_begin, int step_end, void* ws, size_t ws_bytes,
+                     rgfm_stream_t stream);
 
 /* Paired Euler loop with GRADIENT LOG-RATIO guidance, in place: every step
  *     x <- x + (v_x(x, t) + gamma * d log r(x, y)/dx) dt,   y likewise
@@ -390,6 +421,13 @@ int rgfm_guidance_apply(const float* x, const float* y, float* vx, float* vy, co
                         const float* mc_y1, const float* mc_ratios, int batch, int n_mc, int dim_x,
                         int dim_y, double t, double gamma, float* weights_out, void* ws,
                         size_t ws_bytes, rgfm_stream_t stream);
+
+/* One evaluation of the one-sided block of rgfm_sample_cond on its own (parity hook): v[B,dim] is overwritten with
+ * (1-gamma)*v + gamma*g at time t for the state s[B,dim], the MC set mc_set[N,dim] and ratios[batch][n_mc];
+ * weights_out[B,N] (optional, may be null); ws as rgfm_guidance_workspace_bytes(batch, n_mc). */
+int rgfm_guidance_apply_cond(const float* s, float* v, const float* mc_set, const float* ratios, int batch,
+                             int n_mc, int dim, double t, double gamma, float* weights_out, void* ws,
+                             size_t ws_bytes, rgfm_stream_t stream);
 
 /* ------------------------------------------------------------------------
  * Bench support: per-kernel-class device time measured with hipEvents on the

@@ -634,6 +634,31 @@ class RatioEngine(_EngineBase):
                                          _ptr(ws), nb.value, _stream(dev)))
         return out
 
+    def eval_cross(self, x, y, what):
+        """[nx, ny]: `what` of every pair (x_i, y_j) (rgfm_ratio_eval_cross): each encoder runs once per image."""
+        m = self._module()
+        self._check_eval(m)
+        _require_hip(x, y)
+        self.bind(x, y)
+        sx, sy = self.image_shapes()
+        if x.dim() != 4 or y.dim() != 4 or tuple(x.shape[1:]) != sx or tuple(y.shape[1:]) != sy:
+            raise _lib.RgfmError(f"expected x of shape [nx,{sx[0]},{sx[1]},{sx[2]}] and y of shape [ny,{sy[0]},{sy[1]},{sy[2]}], got "
+                                 f"{tuple(x.shape)} and {tuple(y.shape)}")
+        nx, ny = x.shape[0], y.shape[0]
+        x, y = x.contiguous(), y.contiguous()
+        out = torch.empty(nx, ny, device=x.device, dtype=torch.float32)
+        if nx == 0 or ny == 0:
+            return out
+        dev = x.device
+        L = _lib.lib()
+        with torch.cuda.device(dev):
+            h = self.handle(dev)
+            nb = ctypes.c_size_t()
+            _lib.check(L.rgfm_ratio_cross_workspace_bytes(h, nx, ny, ctypes.byref(nb)))
+            ws = self._ws.get(nb.value, dev)
+            _lib.check(L.rgfm_ratio_eval_cross(h, _ptr(x), nx, _ptr(y), ny, _ptr(out), _RATIO_OUT[what], _ptr(ws),
+                                               nb.value, _stream(dev)))
+        return out
 
     def grad_log_ratio(self, x, y):
         """(d log_ratio/dx, d log_ratio/dy, log_ratio): rgfm_ratio_grad_log_ratio (either estimator)."""
@@ -943,6 +968,57 @@ def guidance_apply(x, y, vx, vy, mc_x1, mc_y1, mc_ratios, t, gamma, want_weights
                                          _ptr(mc_x1.contiguous()), _ptr(mc_y1.contiguous()),
                                          _ptr(mc_ratios.contiguous()), B, N, dx, dy, float(t),
                                          float(gamma), _ptr(w), _ptr(ws), nb.value, _stream(dev)))
+    return w
+
+
+def sample_cond(model, s, mc_set, ratios, num_steps, gamma, step_begin=0, step_end=None):
+    """In-place Euler loop of one U-Net with one-sided MC guidance (rgfm_sample_cond): s [B, C, H, W], mc_set
+    [N, C, H, W], ratios [B, N]."""
+    eng = model._engine
+    eng._check_eval(model)
+    if not isinstance(eng, UNetEngine):
+        raise _lib.RgfmError(f"conditional sampling needs a U-Net target (FlexibleUNet and its presets), got "
+                             f"{type(model).__name__}")
+    _require_hip(s, mc_set, ratios)
+    if not s.is_contiguous():
+        raise _lib.RgfmError("s must be contiguous (it is updated in place)")
+    eng._check_input(model, s)
+    eng._check_input(model, mc_set)
+    B, N, dev = s.shape[0], mc_set.shape[0], s.device
+    if tuple(ratios.shape) != (B, N):
+        raise _lib.RgfmError(f"expected ratios of shape [{B},{N}] (a row per sample), got {tuple(ratios.shape)}")
+    if step_end is None:
+        step_end = num_steps
+    if B == 0:
+        return s
+    mc_set, ratios = mc_set.contiguous(), ratios.contiguous()
+    L = _lib.lib()
+
+    def run():
+        with torch.cuda.device(dev):
+            h = eng.handle(dev)
+            nb = ctypes.c_size_t()
+            _lib.check(L.rgfm_sample_cond_workspace_bytes(h, B, N, ctypes.byref(nb)))
+            ws = _sampler_ws.get(nb.value, dev)
+            _lib.check(L.rgfm_sample_cond(h, _ptr(s), _ptr(mc_set), _ptr(ratios), N, B, int(num_steps), float(gamma),
+                                          int(step_begin), int(step_end), _ptr(ws), nb.value, _stream(dev)))
+        return s
+    return _range_guarded(dev, [s], run, [eng])
+
+
+def guidance_apply_cond(s, v, mc_set, ratios, t, gamma, want_weights=False):
+    """One evaluation of the one-sided guidance block (parity hook): overwrites v; returns weights or None."""
+    _require_hip(s, v, mc_set, ratios)
+    B, N, dev = s.shape[0], mc_set.shape[0], s.device
+    w = torch.empty(B, N, device=dev) if want_weights else None
+    L = _lib.lib()
+    with torch.cuda.device(dev):
+        nb = ctypes.c_size_t()
+        _lib.check(L.rgfm_guidance_workspace_bytes(B, N, ctypes.byref(nb)))
+        ws = _sampler_ws.get(nb.value, dev)
+        _lib.check(L.rgfm_guidance_apply_cond(_ptr(s.contiguous()), _ptr(v), _ptr(mc_set.contiguous()),
+                                              _ptr(ratios.contiguous()), B, N, s[0].numel(), float(t), float(gamma),
+                                              _ptr(w), _ptr(ws), nb.value, _stream(dev)))
     return w
 
 

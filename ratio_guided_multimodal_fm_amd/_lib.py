@@ -67,6 +67,9 @@ SIGNATURES = {
     "rgfm_ratio_workspace_bytes": (c_int, [c_void_p, c_int, P(c_size_t)]),
     "rgfm_ratio_eval": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_void_p,
                                 c_size_t, c_void_p]),
+    "rgfm_ratio_cross_workspace_bytes": (c_int, [c_void_p, c_int, c_int, P(c_size_t)]),
+    "rgfm_ratio_eval_cross": (c_int, [c_void_p, c_void_p, c_int, c_void_p, c_int, c_void_p, c_int, c_void_p,
+                                      c_size_t, c_void_p]),
     "rgfm_ratio_grad_workspace_bytes": (c_int, [c_void_p, c_int, P(c_size_t)]),
     "rgfm_ratio_grad_log_ratio": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int,
                                           c_void_p, c_size_t, c_void_p]),
@@ -84,6 +87,11 @@ SIGNATURES = {
     "rgfm_sample_single_workspace_bytes": (c_int, [c_void_p, c_int, P(c_size_t)]),
     "rgfm_sample_single": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_void_p,
                                    c_size_t, c_void_p]),
+    "rgfm_sample_cond_workspace_bytes": (c_int, [c_void_p, c_int, c_int, P(c_size_t)]),
+    "rgfm_sample_cond": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_double, c_int, c_int,
+                                 c_void_p, c_size_t, c_void_p]),
+    "rgfm_guidance_apply_cond": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_double,
+                                         c_double, c_void_p, c_void_p, c_size_t, c_void_p]),
     "rgfm_sample_pair_workspace_bytes": (c_int, [c_void_p, c_void_p, c_int, c_int, P(c_size_t)]),
     "rgfm_sample_pair": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
                                  c_void_p, c_int, c_int, c_int, c_double, c_int, c_int, c_void_p,

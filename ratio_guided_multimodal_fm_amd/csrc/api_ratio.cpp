@@ -73,6 +73,7 @@ size_t plan_ratio(const rgfm_ratio_desc& d, const rgfm_ratio_flex_desc& geom, rg
     h->ex = ex, h->ey = ey, h->hidden = hidden, h->headw = headw, h->headb = headb, h->head_in = dims.back();
     static_cast<WeightLayout&>(*h) = P.layout();
     h->n_bn = bn.off;
+    h->w1x = gw.take((size_t)Hd * F), h->w1y = gw.take((size_t)Hd * F);
     h->g_zeros = gw.take(1024);
     h->n_gradw = gw.off;
     h->max_c = 0, h->n_wtmp = 1;
@@ -147,6 +148,12 @@ int pack_ratio(rgfm_ratio* h, hipStream_t s) {
     launch_transpose2d(h->params + e->fcw, h->gradw + e->fcw_t, h->d.feature_dim, e->fc_in, s);
   }
   for (const auto& dn : h->hidden) launch_transpose2d(h->params + dn.w, h->gradw + dn.w_t, dn.out, dn.in, s);
+  {  // the cross path's column slices W[:, :F] and W[:, F:] of the first score Linear, each made contiguous
+    const size_t F = (size_t)h->d.feature_dim, Hd = (size_t)h->hidden[0].out;
+    const float* w1 = h->params + h->hidden[0].w;
+    HIP_TRY(hipMemcpy2DAsync(h->gradw + h->w1x, F * 4, w1, 2 * F * 4, F * 4, Hd, hipMemcpyDeviceToDevice, s));
+    HIP_TRY(hipMemcpy2DAsync(h->gradw + h->w1y, F * 4, w1 + F, 2 * F * 4, F * 4, Hd, hipMemcpyDeviceToDevice, s));
+  }
   launch_fill(h->gradw + h->g_zeros, 0.f, 1024, s);
   std::vector<HxImage*> images;
   for (auto* e : {&h->ex, &h->ey})
@@ -166,8 +173,8 @@ struct RatioRun {
   hipStream_t s;
   bool dry;
 
-  // one encoder: image NCHW -> features written at feat[:, col0 : col0+F] (row stride 2F)
-  void encode(const rgfm_ratio::Encoder& e, const float* img, float* feat, int col0) {
+  // one encoder: image NCHW -> features written at feat[:, col0 : col0+F] (row stride `stride`)
+  void encode(const rgfm_ratio::Encoder& e, const float* img, float* feat, int col0, int stride) {
     const bool gn = h->gn_encoders();
     const int F = h->d.feature_dim;
     int S = e.size;
@@ -229,15 +236,15 @@ struct RatioRun {
     if (!dry) {
       ProfScope p(RGFM_KCLASS_OTHER, 0, s);
       launch_avgpool(cur.data, ab, pooled, n, S * S, cur.C, s);
-      launch_linear_mfma(pooled, h->params + e.fcw, h->params + e.fcb, feat + col0, n, cur.C, F, cur.C, 2 * F, s);
+      launch_linear_mfma(pooled, h->params + e.fcw, h->params + e.fcb, feat + col0, n, cur.C, F, cur.C, stride, s);
     }
   }
 
   void run(const float* x, const float* y, float* out, int what) {
     const int F = h->d.feature_dim;
     float* feat = ws->f((size_t)n * 2 * F);
-    encode(h->ex, x, feat, 0);
-    encode(h->ey, y, feat, F);
+    encode(h->ex, x, feat, 0, 2 * F);
+    encode(h->ey, y, feat, F, 2 * F);
     float* cur = feat;
     for (const auto& dn : h->hidden) {
       float* nxt = ws->f((size_t)n * dn.out);
@@ -251,6 +258,63 @@ struct RatioRun {
     if (!dry) {
       ProfScope p(RGFM_KCLASS_OTHER, 0, s);
       launch_ratio_head(cur, h->params + h->headw, h->params + h->headb, out, n, h->head_in, h->d.loss_type, what, s);
+    }
+  }
+};
+
+// Cross evaluation: `what` of every pair (x_i, y_j), out[nx][ny].  Each encoder runs once over its own images; the
+// first score Linear is factorised over the concatenation (cross_ln_silu_kernel) and the rest of the MLP runs over the
+// nx * ny pairs in chunks of `chunk` pair indices, so the scratch does not grow with the matrix.
+constexpr long long RGFM_CROSS_ROWS_DEFAULT = 16384;  // pairs per chunk: 32 MB of first-layer activations at hidden_dim 512
+inline long long cross_rows() {  // RGFM_CROSS_ROWS: test hook, read on entry of the two cross entry points
+  const char* e = getenv("RGFM_CROSS_ROWS");
+  const long long v = e ? atoll(e) : 0;
+  return v >= 1 && v <= (1 << 20) ? v : RGFM_CROSS_ROWS_DEFAULT;
+}
+
+struct RatioCrossRun {
+  rgfm_ratio* h;
+  int nx, ny;
+  Bump* ws;
+  hipStream_t s;
+  bool dry;
+  long long chunk;
+
+  void run(const float* x, const float* y, float* out, int what) {
+    const int F = h->d.feature_dim;
+    const auto& d0 = h->hidden[0];
+    float* fx = ws->f((size_t)nx * F);
+    float* fy = ws->f((size_t)ny * F);
+    float* ux = ws->f((size_t)nx * d0.out);
+    float* uy = ws->f((size_t)ny * d0.out);
+    // the encoders' scratch is dead once the features are written: the two walks and the MLP chunk share one region
+    const size_t mark = ws->off;
+    size_t peak = mark;
+    RatioRun rx{h, nx, ws, s, dry};
+    rx.encode(h->ex, x, fx, 0, F);
+    peak = std::max(peak, ws->off), ws->off = mark;
+    RatioRun ry{h, ny, ws, s, dry};
+    ry.encode(h->ey, y, fy, 0, F);
+    peak = std::max(peak, ws->off), ws->off = mark;
+    const long long total = (long long)nx * ny;
+    const int rows_max = (int)std::min(total, chunk);
+    std::vector<float*> act;
+    for (const auto& dn : h->hidden) act.push_back(ws->f((size_t)rows_max * dn.out));
+    peak = std::max(peak, ws->off), ws->off = peak;
+    if (dry) return;
+    ProfScope p(RGFM_KCLASS_OTHER, 0, s);
+    const float* zeros = h->gradw + h->g_zeros;
+    launch_linear_mfma(fx, h->gradw + h->w1x, zeros, ux, nx, F, d0.out, F, d0.out, s);
+    launch_linear_mfma(fy, h->gradw + h->w1y, zeros, uy, ny, F, d0.out, F, d0.out, s);
+    for (long long r0 = 0; r0 < total; r0 += chunk) {
+      const int rows = (int)std::min(chunk, total - r0);
+      launch_cross_ln_silu(ux, uy, h->params + d0.b, h->params + d0.lw, h->params + d0.lb, act[0], r0, rows, ny, d0.out, s);
+      for (size_t l = 1; l < h->hidden.size(); ++l) {
+        const auto& dn = h->hidden[l];
+        launch_linear_mfma(act[l - 1], h->params + dn.w, h->params + dn.b, act[l], rows, dn.in, dn.out, dn.in, dn.out, s);
+        launch_layernorm_silu(act[l], h->params + dn.lw, h->params + dn.lb, rows, dn.out, s);
+      }
+      launch_ratio_head(act.back(), h->params + h->headw, h->params + h->headb, out + r0, rows, h->head_in, h->d.loss_type, what, s);
     }
   }
 };
@@ -353,6 +417,32 @@ extern "C" int rgfm_ratio_eval(rgfm_ratio* h, const float* x, const float* y, fl
   Bump b;
   b.base = (char*)ws, b.cap = ws_bytes, b.dry = false;
   RatioRun r{h, n, &b, (hipStream_t)stream, false};
+  r.run(x, y, out, what);
+  HIP_TRY(hipGetLastError());
+  return RGFM_OK;
+}
+
+extern "C" int rgfm_ratio_cross_workspace_bytes(const rgfm_ratio* h, int nx, int ny, size_t* bytes) {
+  if (!h || !bytes || nx < 1 || ny < 1) return fail(RGFM_EINVAL, "bad argument");
+  Bump b;
+  RatioCrossRun r{const_cast<rgfm_ratio*>(h), nx, ny, &b, nullptr, true, cross_rows()};
+  r.run(nullptr, nullptr, nullptr, 0);
+  *bytes = b.off;
+  return RGFM_OK;
+}
+
+extern "C" int rgfm_ratio_eval_cross(rgfm_ratio* h, const float* x, int nx, const float* y, int ny, float* out, int what,
+                                     void* ws, size_t ws_bytes, rgfm_stream_t stream) {
+  refresh_modes();
+  if (!h || !x || !y || !out || !ws) return fail(RGFM_EINVAL, "null argument");
+  if (what < 0 || what > 2) return fail(RGFM_EINVAL, "bad output selector");
+  size_t need = 0;
+  int rc = rgfm_ratio_cross_workspace_bytes(h, nx, ny, &need);
+  if (rc) return rc;
+  if (need > ws_bytes) return fail(RGFM_ENOMEM, "workspace too small: %zu < %zu", ws_bytes, need);
+  Bump b;
+  b.base = (char*)ws, b.cap = ws_bytes, b.dry = false;
+  RatioCrossRun r{h, nx, ny, &b, (hipStream_t)stream, false, cross_rows()};
   r.run(x, y, out, what);
   HIP_TRY(hipGetLastError());
   return RGFM_OK;

@@ -64,6 +64,81 @@ extern "C" int rgfm_guidance_apply(const float* x, const float* y, float* vx, fl
   return RGFM_OK;
 }
 
+// The one-sided block: the paired block with dy = 0 and a ratio row per sample (guidance_launch).
+extern "C" int rgfm_guidance_apply_cond(const float* s, float* v, const float* mc_set, const float* ratios, int batch, int n_mc,
+                                        int dim, double t, double gamma, float* weights_out, void* ws, size_t ws_bytes,
+                                        rgfm_stream_t stream) {
+  if (!s || !v || !mc_set || !ratios || !ws) return fail(RGFM_EINVAL, "null argument");
+  if (dim < 1) return fail(RGFM_EINVAL, "bad argument");
+  size_t need = 0;
+  int rc = rgfm_guidance_workspace_bytes(batch, n_mc, &need);
+  if (rc) return rc;
+  if (need > ws_bytes) return fail(RGFM_ENOMEM, "workspace too small: %zu < %zu", ws_bytes, need);
+  if ((rc = ensure_init())) return rc;
+  rc = guidance_launch(s, nullptr, v, nullptr, mc_set, nullptr, ratios, batch, n_mc, dim, 0, t, gamma, (float*)ws, weights_out,
+                       nullptr, nullptr, 0.f, (hipStream_t)stream, nullptr, nullptr, 0, n_mc);
+  if (rc) return rc;
+  HIP_TRY(hipGetLastError());
+  return RGFM_OK;
+}
+
+extern "C" int rgfm_sample_cond_workspace_bytes(const rgfm_unet* h, int batch, int n_mc, size_t* bytes) {
+  if (!h || !bytes || batch < 1 || n_mc < 1) return fail(RGFM_EINVAL, "bad argument");
+  const size_t d = (size_t)h->d.in_channels * h->d.img_size * h->d.img_size;
+  *bytes = unet_eval_bytes(const_cast<rgfm_unet*>(h), batch) + table_bytes(h, 4096) + counter_bytes(batch) +
+           ((batch * d * 4 + 255) & ~(size_t)255) + guid_scratch_bytes(batch, n_mc);
+  return RGFM_OK;
+}
+
+// One net, guided by the one-sided block: kernel by kernel on the caller's stream (nothing to overlap, no graph).
+extern "C" int rgfm_sample_cond(rgfm_unet* h, float* s_inout, const float* mc_set, const float* ratios, int n_mc, int batch,
+                                int num_steps, double gamma, int step_begin, int step_end, void* ws, size_t ws_bytes,
+                                rgfm_stream_t stream) {
+  refresh_modes();
+  if (!h || !s_inout || !mc_set || !ratios || !ws) return fail(RGFM_EINVAL, "null argument");
+  if (n_mc < 1) return fail(RGFM_EINVAL, "conditional sampling needs an MC set (n_mc >= 1)");
+  if (batch < 1 || num_steps < 1 || step_begin < 0 || step_end > num_steps || step_begin > step_end)
+    return fail(RGFM_EINVAL, "bad step range [%d,%d) of %d", step_begin, step_end, num_steps);
+  const int ns = step_end - step_begin;
+  if (ns > 4096) return fail(RGFM_EINVAL, "at most 4096 steps per call");
+  const int d = h->d.in_channels * h->d.img_size * h->d.img_size;
+  if (d % 4) return fail(RGFM_EINVAL, "flattened image sizes must be multiples of 4");
+  if (n_mc > 4096) return fail(RGFM_EINVAL, "n_mc too large (max 4096)");
+  size_t need = 0;
+  int rc = rgfm_sample_cond_workspace_bytes(h, batch, n_mc, &need);
+  if (rc) return rc;
+  if (need > ws_bytes) return fail(RGFM_ENOMEM, "workspace too small: %zu < %zu", ws_bytes, need);
+  if (ns == 0) return RGFM_OK;
+  hipStream_t s = (hipStream_t)stream;
+  Bump b;
+  b.base = (char*)ws, b.cap = ws_bytes, b.dry = false;
+  float* table = b.f((size_t)4096 * h->temb_total);
+  unsigned* cnt = reinterpret_cast<unsigned*>(b.f(batch));
+  float* v = b.f((size_t)batch * d);
+  float* scratch = b.f(guid_scratch_bytes(batch, n_mc) / sizeof(float));
+  HIP_TRY(hipMemsetAsync(cnt, 0, (size_t)batch * sizeof(unsigned), s));
+  launch_time_table(h, nullptr, num_steps, step_begin, ns, table, s);
+  const size_t mark = b.off;
+  const double dtd = 1.0 / (double)num_steps;
+  const float dt = (float)dtd;
+  for (int i = 0; i < ns; ++i) {
+    const double t = (double)(step_begin + i) * dtd;
+    const bool guided = t > 1e-3;  // `t > eps` test of the reference (:124)
+    b.off = mark;
+    UNetRun r{h, batch, &b, s, table + (size_t)i * h->temb_total, 0, false};
+    r.fin_counter = cnt;
+    // unguided: the fused Euler epilogue; guided: the raw velocity, and the guidance block moves the state
+    if ((rc = guided ? r.run(s_inout, v, nullptr, dt) : r.run(s_inout, nullptr, s_inout, dt))) return rc;
+    if (guided) {
+      rc = guidance_launch(s_inout, nullptr, v, nullptr, mc_set, nullptr, ratios, batch, n_mc, d, 0, t, gamma, scratch, nullptr,
+                           s_inout, nullptr, dt, s, nullptr, nullptr, 0, n_mc);
+      if (rc) return rc;
+    }
+  }
+  HIP_TRY(hipGetLastError());
+  return RGFM_OK;
+}
+
 extern "C" int rgfm_sample_pair_workspace_bytes(const rgfm_unet* hx, const rgfm_unet* hy, int batch, int n_mc,
                                                 size_t* bytes) {
   if (!hx || !hy || !bytes || batch < 1 || n_mc < 0) return fail(RGFM_EINVAL, "bad argument");

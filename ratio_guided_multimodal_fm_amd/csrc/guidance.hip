@@ -171,6 +171,7 @@ __global__ __launch_bounds__(256) void guid_weights_kernel(const GuidanceArgs a_
   const int b = blockIdx.x * 4 + wave;
   if (b >= a.B) return;
   float* swr = sw + (size_t)wave * N;
+  const float* ratios = a.mc_ratios + (size_t)b * a.ratio_stride;  // (the shared vector, or this row's own)
   float mx = -INFINITY;
   for (int i = lane; i < N; i += 64) {
     const float l = logp_of(a, b, i);
@@ -183,7 +184,7 @@ __global__ __launch_bounds__(256) void guid_weights_kernel(const GuidanceArgs a_
     const float p = expf(swr[i] - mx);
     swr[i] = p;
     ps += p;
-    zs += __fmul_rn(a.mc_ratios[i], p);
+    zs += __fmul_rn(ratios[i], p);
   }
   ps = wave_sum_g(ps);
   zs = wave_sum_g(zs);
@@ -191,7 +192,7 @@ __global__ __launch_bounds__(256) void guid_weights_kernel(const GuidanceArgs a_
   const float zbar = __fadd_rn(zs / (float)N, 1e-10f);
   float ws = 0.f;
   for (int i = lane; i < N; i += 64) {
-    const float w = __fmul_rn(a.mc_ratios[i] / zbar, swr[i] / pbar);
+    const float w = __fmul_rn(ratios[i] / zbar, swr[i] / pbar);
     swr[i] = w;
     ws += w;
   }

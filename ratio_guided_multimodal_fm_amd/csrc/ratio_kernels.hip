@@ -245,6 +245,65 @@ void launch_layernorm_silu(float* x, const float* w, const float* b, int rows, i
   hipLaunchKernelGGL(layernorm_silu_kernel, dim3((rows + 3) / 4), dim3(256), 0, s, x, w, b, rows, n);
 }
 
+// The first hidden layer of the score MLP for every pair (x_i, y_j) of a cross evaluation.  Its Linear acts on the
+// concatenation [f_x | f_y], so W [f_x | f_y] + b = W[:, :F] f_x + W[:, F:] f_y + b: the two products are computed once
+// per IMAGE (ux [nx][n], uy [ny][n], launch_linear_mfma on the two column slices of W) and this kernel forms a pair's
+// pre-activation as their sum, then LayerNorm + SiLU as layernorm_silu_kernel does -- in one pass, the row held in
+// registers (n <= 1024: four float4 per lane).  Wave per pair; the pair index r = row0 + row runs over the row-major
+// [nx][ny] matrix, so a chunk of rows may begin and end inside a matrix row.  The reductions are lane partials in
+// element order, then the xor butterfly: a fixed order, the same for a pair whichever chunk it falls into.
+__global__ __launch_bounds__(256) void cross_ln_silu_kernel(const float* ux, const float* uy, const float* bias, const float* w,
+                                                           const float* b, float* out, long long row0, int rows, int ny, int n) {
+  const int lane = threadIdx.x & 63;
+  const int row = blockIdx.x * 4 + (threadIdx.x >> 6);
+  if (row >= rows) return;
+  const long long r = row0 + row;
+  const f32x4* px = reinterpret_cast<const f32x4*>(ux + (size_t)(r / ny) * n);
+  const f32x4* py = reinterpret_cast<const f32x4*>(uy + (size_t)(r % ny) * n);
+  const f32x4* pb = reinterpret_cast<const f32x4*>(bias);
+  const int n4 = n >> 2;
+  f32x4 v[4];
+  float s = 0.f;
+#pragma unroll
+  for (int k = 0; k < 4; ++k) {
+    const int c = lane + 64 * k;
+    v[k] = f32x4{0.f, 0.f, 0.f, 0.f};
+    if (c < n4) {
+      const f32x4 a = px[c], y = py[c], bi = pb[c];
+      v[k].x = a.x + y.x + bi.x, v[k].y = a.y + y.y + bi.y, v[k].z = a.z + y.z + bi.z, v[k].w = a.w + y.w + bi.w;
+      s += (v[k].x + v[k].y) + (v[k].z + v[k].w);
+    }
+  }
+  const float mean = wsum(s) / (float)n;
+  float m2 = 0.f;
+#pragma unroll
+  for (int k = 0; k < 4; ++k)
+    if (lane + 64 * k < n4) {
+      const float d0 = v[k].x - mean, d1 = v[k].y - mean, d2 = v[k].z - mean, d3 = v[k].w - mean;
+      m2 += (d0 * d0 + d1 * d1) + (d2 * d2 + d3 * d3);
+    }
+  const float rstd = 1.0f / sqrtf(wsum(m2) / (float)n + 1e-5f);
+  f32x4* po = reinterpret_cast<f32x4*>(out + (size_t)row * n);
+#pragma unroll
+  for (int k = 0; k < 4; ++k) {
+    const int c = lane + 64 * k;
+    if (c < n4) {
+      const f32x4 g = reinterpret_cast<const f32x4*>(w)[c], be = reinterpret_cast<const f32x4*>(b)[c];
+      f32x4 o;
+      o.x = silu_f((v[k].x - mean) * rstd * g.x + be.x);
+      o.y = silu_f((v[k].y - mean) * rstd * g.y + be.y);
+      o.z = silu_f((v[k].z - mean) * rstd * g.z + be.z);
+      o.w = silu_f((v[k].w - mean) * rstd * g.w + be.w);
+      po[c] = o;
+    }
+  }
+}
+
+void launch_cross_ln_silu(const float* ux, const float* uy, const float* bias, const float* w, const float* b, float* out,
+                          long long row0, int rows, int ny, int n, hipStream_t s) {
+  hipLaunchKernelGGL(cross_ln_silu_kernel, dim3((rows + 3) / 4), dim3(256), 0, s, ux, uy, bias, w, b, out, row0, rows, ny, n);
+}
+
 __device__ __forceinline__ float logsigmoid_f(float x) { return fminf(x, 0.f) - log1pf(expf(-fabsf(x))); }
 
 // final Linear(n -> 1) + log_ratio (ratio_flexible.py:366-385) / exp (sample_mnist_svhn.py:111)

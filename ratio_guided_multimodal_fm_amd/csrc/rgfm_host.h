@@ -983,15 +983,19 @@ inline void guidance_scalars(double t, float* tf, float* s2, float* cden) {
 inline int guidance_launch(const float* x, const float* y, float* vx, float* vy, const float* mx, const float* my,
                     const float* r, int B, int N, int dx, int dy, double t, double gamma, float* logp,
                     float* weights_out, float* xs, float* ys, float dt, hipStream_t s, const float* sched = nullptr,
-                    const int* step_ptr = nullptr, int phase = 0) {
+                    const int* step_ptr = nullptr, int phase = 0, int ratio_stride = 0) {
   // phase 0: the whole block; 1: distances + importance weights only -- they need the step's (x_t, y_t) and the MC set,
   // not the velocities; 2: the rest (needs v)
+  // One-sided block (conditional sampling): dy = 0 with y, vy, my, ys null, and ratio_stride = N -- r is then [B][N],
+  // a ratio row per sample.  The kernels take the second modality's slices and column blocks from dy, so none is
+  // launched; the observed side's Gaussian factor is constant in the MC index and cancels in the normalised weights.
   if (dx % 4 || dy % 4) return fail(RGFM_EINVAL, "flattened image sizes must be multiples of 4");
   if ((size_t)4 * N * sizeof(float) > 64 * 1024) return fail(RGFM_EINVAL, "n_mc too large (max 4096)");
   // Python-double scalar arithmetic of the reference (sample_mnist_svhn.py:115,127,135,159,170),
   // rounded to fp32 where a tensor op consumes it.
   GuidanceArgs a{};
   a.x = x, a.y = y, a.vx = vx, a.vy = vy, a.mc_x1 = mx, a.mc_y1 = my, a.mc_ratios = r;
+  a.ratio_stride = ratio_stride;
   a.B = B, a.N = N, a.dx = dx, a.dy = dy;
   guidance_scalars(t, &a.tf, &a.s2, &a.cden);
   a.sched = sched, a.step_ptr = sched ? step_ptr : nullptr;
@@ -1192,6 +1196,9 @@ struct rgfm_ratio : WeightStore {
   std::vector<Dense> hidden;
   size_t headw = 0, headb = 0;
   int head_in = 0;
+  // cross evaluation (rgfm_ratio_eval_cross): the first Linear's weight [Hd][2F] as its two column slices, each a
+  // contiguous [Hd][F] matrix (offsets into gradw; copied by pack_ratio, so rgfm_ratio_update_params refreshes them)
+  size_t w1x = 0, w1y = 0;
 };
 
 

@@ -378,6 +378,10 @@ void launch_linear_mfma(const float* x, const float* w, const float* b, float* y
 void launch_linear_mfma_splitk(const float* x, const float* ab, int C, const float* w, const float* b, float* y,
                                float* part, int splits, int rows, int in, int out, int y_stride, hipStream_t s);
 void launch_layernorm_silu(float* x, const float* w, const float* b, int rows, int n, hipStream_t s);
+// Cross evaluation, first hidden layer: out[r - row0][n] = silu(LayerNorm(ux[r / ny] + uy[r % ny] + bias)) for the `rows`
+// pair indices r = row0 .. row0 + rows - 1 of the row-major [nx][ny] matrix (n % 4 == 0, n <= 1024)
+void launch_cross_ln_silu(const float* ux, const float* uy, const float* bias, const float* w, const float* b, float* out,
+                          long long row0, int rows, int ny, int n, hipStream_t s);
 void launch_ratio_head(const float* x, const float* w, const float* b, float* out, int rows, int n,
                        int loss, int what, hipStream_t s);
 void launch_bn_fold(const float* w, const float* b, const float* rm, const float* rv, float* scale,
@@ -416,7 +420,8 @@ struct GuidanceArgs {
   const float* mc_x1;
   const float* mc_y1;
   const float* mc_ratios;
-  int B, N, dx, dy;
+  int ratio_stride;  // row b reads mc_ratios[b * ratio_stride + i]: 0 = one vector shared by every row (the paired block), N = a ratio row per sample (the one-sided block)
+  int B, N, dx, dy;  // dy = 0 (with nsy = 0; y, vy, mc_y1 unused): a block with one modality
   float tf, s2, cden, g1, g2;
   double* dist;        // [nsx + nsy][B][N] scratch: sliced squared distances (guid_logp -> guid_apply)
   int slice_len, nsx, nsy;  // D-slices per modality (<= RGFM_GUID_SLICES in all)

@@ -41,6 +41,18 @@ def evaluate_coherence(samples_mnist, samples_svhn, mnist_classifier, svhn_class
     return {'coherence_acc': float(acc), 'num_samples': len(samples_mnist)}
 
 
+def evaluate_conditional_coherence(condition, samples, given, mnist_classifier, svhn_classifier, device):
+    """Share of rows where the classifier of the condition's modality and the classifier of the generated modality
+    agree: `condition` [B, ...] are the images `samples` [B, ...] were generated for (``sample_conditional``), `given`
+    ('mnist' or 'svhn') names the condition's modality."""
+    if given not in ('mnist', 'svhn'):
+        raise ValueError(f"given must be 'mnist' or 'svhn', got {given!r}")
+    if len(condition) != len(samples):
+        raise ValueError(f"{len(condition)} condition images for {len(samples)} samples")
+    mnist, svhn = (condition, samples) if given == 'mnist' else (samples, condition)
+    return evaluate_coherence(mnist, svhn, mnist_classifier, svhn_classifier, device)['coherence_acc']
+
+
 def run_sweep(fm_mnist, fm_svhn, make_ratio, mnist_classifier, svhn_classifier, methods, strengths,
               num_samples, num_steps, device, mc_batch_size, sampler=sample_bimodal_guided_mnist_svhn):
     """The reference's nested loop (:130-183). `make_ratio()` returns a fresh ratio estimator or None."""

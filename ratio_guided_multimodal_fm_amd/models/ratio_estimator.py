@@ -59,6 +59,17 @@ class RatioEstimator(nn.Module):
             raise ValueError(f"Unknown loss_type: {self.loss_type}")
         return self._engine.eval(x, y, "log_ratio")
 
+    def forward_cross(self, x, y):
+        """Scores of every pair: x [nx, ...], y [ny, ...] -> [nx, ny] with entry (i, j) = forward(x_i, y_j).  Each
+        encoder runs once per image, not once per pair (``rgfm_ratio_eval_cross``); eval mode only."""
+        return self._engine.eval_cross(x, y, "score")
+
+    def cross_log_ratio(self, x, y):
+        """log r(x_i, y_j) of every pair -> [nx, ny]: the matrix conditional sampling weighs its MC set with."""
+        if self.loss_type not in ("disc", "rulsif"):
+            raise ValueError(f"Unknown loss_type: {self.loss_type}")
+        return self._engine.eval_cross(x, y, "log_ratio")
+
     def grad_log_ratio(self, x, y):
         """(d log_ratio/dx, d log_ratio/dy): what ``torch.autograd.grad(self.log_ratio(x, y).sum(), (x, y))`` returns for
         the reference module in eval mode (reference ``ratio_estimator.py:137-191``; the quantity of the README's

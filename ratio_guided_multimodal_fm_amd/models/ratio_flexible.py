@@ -16,7 +16,7 @@ class FlexibleRatioEstimator(nn.Module):
     channels and sizes 8..64 (reference ``:69-154``).  The parameters do not depend on the image sizes (the encoders
     end in a global average pool); the sizes are read from the inputs of each call and the engine keeps one device
     handle per (Sx, Sy) pair seen.  ``forward`` / ``forward_train`` / ``log_ratio`` / ``grad_log_ratio`` /
-    ``dropout_p`` as for ``RatioEstimator``, whose architecture at 1x28x28 + 1x28x28 this is."""
+    ``forward_cross`` / ``cross_log_ratio`` / ``dropout_p`` as for ``RatioEstimator``, whose architecture at 1x28x28 + 1x28x28 this is."""
     _engine = engine_property(lambda m: FlexibleRatioEngine(m))
 
     def __init__(self, x_channels=1, y_channels=1, feature_dim=256, hidden_dim=512, loss_type='disc'):
@@ -40,6 +40,8 @@ class FlexibleRatioEstimator(nn.Module):
     dropout_p = RatioEstimator.dropout_p
     log_ratio = RatioEstimator.log_ratio
     grad_log_ratio = RatioEstimator.grad_log_ratio
+    forward_cross = RatioEstimator.forward_cross
+    cross_log_ratio = RatioEstimator.cross_log_ratio
 
 
 class RatioEstimatorMNIST(FlexibleRatioEstimator):
@@ -122,6 +124,17 @@ class RatioEstimatorMNISTSVHN(nn.Module):
         if self.loss_type not in ("disc", "rulsif"):
             raise ValueError(f"Unknown loss_type: {self.loss_type}")
         return self._engine.eval(x, y, "log_ratio")
+
+    def forward_cross(self, x, y):
+        """Scores of every pair: x [nx,1,32,32], y [ny,3,32,32] -> [nx, ny] with entry (i, j) = forward(x_i, y_j).
+        Each encoder runs once per image, not once per pair (``rgfm_ratio_eval_cross``); eval mode only."""
+        return self._engine.eval_cross(x, y, "score")
+
+    def cross_log_ratio(self, x, y):
+        """log r(x_i, y_j) of every pair -> [nx, ny]: the matrix conditional sampling weighs its MC set with."""
+        if self.loss_type not in ("disc", "rulsif"):
+            raise ValueError(f"Unknown loss_type: {self.loss_type}")
+        return self._engine.eval_cross(x, y, "log_ratio")
 
     def grad_log_ratio(self, x, y):
         """(d log_ratio/dx, d log_ratio/dy): what ``torch.autograd.grad(self.log_ratio(x, y).sum(), (x, y))``

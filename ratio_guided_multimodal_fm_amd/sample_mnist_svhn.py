@@ -13,7 +13,7 @@ import torch
 from .models.ratio_flexible import RatioEstimatorMNISTSVHN
 from .models.unet_flexible import FlowMatchingUNetMNIST, FlowMatchingUNetSVHN
 from .utils import load_checkpoint, set_seed
-from .utils.flow_utils import paired_sampler
+from .utils.flow_utils import paired_sampler, sample_conditional
 
 
 def sample_bimodal_guided_mnist_svhn(fm_mnist, fm_svhn, ratio_estimator=None, guidance_method='none',
@@ -22,6 +22,16 @@ def sample_bimodal_guided_mnist_svhn(fm_mnist, fm_svhn, ratio_estimator=None, gu
     """Returns ``(samples_mnist [n,1,32,32], samples_svhn [n,3,32,32])`` on `device`."""
     return paired_sampler(fm_mnist, fm_svhn, ratio_estimator, guidance_method, guidance_strength,
                           num_samples, num_steps, device, mc_batch_size, (1, 32, 32), (3, 32, 32))
+
+
+def load_condition(path, shape):
+    """Condition images [B, *shape] from a ``.npy`` array or a ``.pt`` tensor."""
+    import numpy as np
+    t = torch.from_numpy(np.load(path)) if path.endswith('.npy') else torch.load(path, map_location='cpu')
+    t = torch.as_tensor(t, dtype=torch.float32)
+    if t.dim() != 4 or tuple(t.shape[1:]) != shape:
+        raise ValueError(f"--condition: expected images of shape [B,{shape[0]},{shape[1]},{shape[2]}], got {tuple(t.shape)}")
+    return t
 
 
 def main(argv=None):
@@ -41,7 +51,16 @@ def main(argv=None):
                    help='rows sharded over the ranks of a torch.distributed.run launch (one process per GPU, RCCL); '
                         'e.g. BASELINE configs[3]: --nproc-per-node 8 ... --sharded --num_samples 4096 '
                         '--guidance_method mc_feng --guidance_strength 1.0')
+    p.add_argument('--given', type=str, default=None, choices=['mnist', 'svhn'],
+                   help="conditional sampling (this build's extension): the modality of --condition; the other one is "
+                        "generated, one sample per condition image (MC guidance, --guidance_strength, --mc_batch_size)")
+    p.add_argument('--condition', type=str, default=None, metavar='FILE.npy|.pt',
+                   help='condition images [B,1,32,32] (--given mnist) or [B,3,32,32] (--given svhn)')
     args = p.parse_args(argv)
+    if (args.given is None) != (args.condition is None):
+        p.error('--given and --condition go together')
+    if args.given and args.sharded:
+        p.error('conditional sampling has no --sharded form')
 
     set_seed(args.seed)  # (every rank alike: the sharded sampler slices ONE noise set)
     print(f"Random seed: {args.seed}")
@@ -69,7 +88,7 @@ def main(argv=None):
         print(f"  Loaded {path}")
 
     ratio = None
-    if args.guidance_method != 'none':
+    if args.guidance_method != 'none' or args.given:
         ratio = RatioEstimatorMNISTSVHN(loss_type=args.loss_type).to(device)
         path = f'checkpoints/ratio_{args.loss_type}_mnist_svhn_best.pth'
         if not os.path.exists(path):
@@ -77,6 +96,19 @@ def main(argv=None):
             return 1
         ratio.load_state_dict(torch.load(path, map_location=device))
         print(f"  Loaded ratio estimator from: {path}")
+
+    if args.given:
+        shape = (1, 32, 32) if args.given == 'mnist' else (3, 32, 32)
+        condition = load_condition(args.condition, shape)
+        target, name = (fm_svhn, 'svhn') if args.given == 'mnist' else (fm_mnist, 'mnist')
+        print(f"\nSampling {len(condition)} {name} images given {args.given}...")
+        out_t = sample_conditional(target, ratio, condition.to(device), 'x' if args.given == 'mnist' else 'y',
+                                   args.num_steps, args.guidance_strength, args.mc_batch_size, device=device)
+        os.makedirs('outputs/mnist_svhn', exist_ok=True)
+        out = f"outputs/mnist_svhn/samples_given_{args.given}_gamma{args.guidance_strength}.pt"
+        torch.save({args.given: condition, name: out_t.cpu()}, out)
+        print(f"Saved samples: {out}")
+        return 0
 
     print(f"\nSampling {args.num_samples} pairs...")
     xs, ys = sampler(fm_mnist, fm_svhn, ratio, args.guidance_method, args.guidance_strength, args.num_samples,

@@ -3,7 +3,8 @@
 ``CFMSchedule.sample`` (``:69-100``) and ``sample_bimodal_guided``
 (``:178-375``) keep the reference signatures and return values; the Euler
 loops, the U-Net evaluations, the ratio estimator and the MC guidance all run
-inside librgfm_hip.so (one C-ABI call per phase).  ``CFMSchedule.add_noise``
+inside librgfm_hip.so (one C-ABI call per phase).  ``sample_conditional`` (new: the reference
+has no conditional sampler) integrates one net given images of the other modality.  ``CFMSchedule.add_noise``
 (``:40-67``) and ``train_flow_matching_epoch`` (``:103-156``) train a
 ``FlexibleUNet`` through its HIP backward (``FlexibleUNet.forward_train``).
 """
@@ -134,6 +135,46 @@ def paired_sampler(fm_x, fm_y, ratio_estimator, guidance_method, guidance_streng
         return x_t, y_t
     _engine.sample_pair(fm_x, fm_y, x_t, y_t, mc_x1, mc_y1, mc_ratios, num_steps, guidance_strength)
     return x_t, y_t
+
+
+def sample_conditional(fm_target, ratio_estimator, condition, given='x', num_steps=100, guidance_strength=1.0,
+                       mc_batch_size=256, mc_samples=None, device=None):
+    """Partners for `condition` in the other modality: one sample of `fm_target`'s modality per condition image.
+
+    ``given='x'``: `condition` is the estimator's x argument and the target is its y; ``given='y'`` the other way
+    round.  The MC guidance of the paired sampler (reference ``src/sample_mnist_svhn.py:124-171``) with one side
+    observed: the MC set is `fm_target`'s own unguided samples, sample b weighs MC sample j by
+    r(condition_b, mc_j) times its own Gaussian factor (``rgfm_sample_cond``), and only the target net is integrated.
+
+    Draw order (global generator of the device): the MC noise ``[mc_batch_size, C, H, W]`` first, then the start
+    noise ``[len(condition), C, H, W]``.  With `mc_samples` (terminal MC samples of an earlier call) no MC noise is
+    drawn and no pre-phase runs.  Returns the samples ``[len(condition), C, H, W]`` on the device.  U-Net targets
+    only; gradient log-ratio guidance and ``--sharded`` launches have no conditional form yet.
+    """
+    from .._lib import RgfmError
+    if given not in ('x', 'y'):
+        raise ValueError(f"given must be 'x' or 'y', got {given!r}")
+    if not isinstance(fm_target._engine, _engine.UNetEngine):
+        raise RgfmError(f"sample_conditional needs a U-Net target (FlexibleUNet and its presets); "
+                        f"{type(fm_target).__name__} has no conditional sampler")
+    fm_target.eval()
+    ratio_estimator.eval()
+    if ratio_estimator.loss_type not in ("disc", "rulsif"):
+        raise ValueError(f"Unknown loss_type: {ratio_estimator.loss_type}")
+    dev = _device(condition.device if device is None else device)
+    condition = condition.to(dev, torch.float32).contiguous()
+    shape = (fm_target.in_channels, fm_target.img_size, fm_target.img_size)
+    if mc_samples is None:
+        mc = torch.randn(mc_batch_size, *shape, device=dev)
+        _engine.sample_single(fm_target, mc, num_steps)
+    else:
+        mc = mc_samples.to(dev, torch.float32).contiguous()
+    s_t = torch.randn(condition.shape[0], *shape, device=dev)
+    if given == 'x':
+        ratios = ratio_estimator.cross_log_ratio(condition, mc).exp()
+    else:
+        ratios = ratio_estimator.cross_log_ratio(mc, condition).exp().T.contiguous()
+    return _engine.sample_cond(fm_target, s_t, mc, ratios, num_steps, guidance_strength)
 
 
 def sample_bimodal_guided(fm_x, fm_y, ratio_estimator=None, guidance_method='none',
