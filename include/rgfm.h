@@ -252,6 +252,27 @@ int rgfm_ratio_grad_workspace_bytes(const rgfm_ratio* h, int n, size_t* bytes);
 int rgfm_ratio_grad_log_ratio(rgfm_ratio* h, const float* x, const float* y, float* gx, float* gy,
                               float* log_ratio_out, int n, void* ws, size_t ws_bytes, rgfm_stream_t stream);
 
+/* The same gradient for ONE side with the other side held fixed (conditional sampling: the observed image never
+ * moves).  `given` = 0: the condition is the estimator's x and the target its y; 1: the other way round.  Every kind.
+ *
+ * rgfm_ratio_cond_prepare: ctx_out[n][hidden_dim] = W1[:, given slice] f_given(cond) + b1 -- the given side's encoder,
+ * once, and its half of the first score Linear (W1 acts on the concatenation [f_x | f_y]; the factorisation of
+ * rgfm_ratio_eval_cross), bias folded in.  A context belongs to the parameters it was prepared with: prepare again
+ * after rgfm_ratio_update_params.
+ *
+ * rgfm_ratio_grad_log_ratio_cond: g_target = d log_ratio(x, y) / d target, row b pairing ctx[b] with target[b]
+ * (target and g_target in the target side's image shape, log_ratio_out optional [n]).  Only the target's encoder runs,
+ * forward and reverse; the first hidden layer is LayerNorm + SiLU of ctx + W1[:, target slice] f_target, and its input
+ * gradient is taken for the target's feature columns alone.  The sum ctx + W1[:, target slice] f_target associates
+ * differently from the 2 feature_dim long dot products of rgfm_ratio_grad_log_ratio, so the two agree to fp32 rounding,
+ * not bitwise.  Every reduction has a fixed order: two calls on the same inputs give identical bits.  Exact fp32 convs. */
+int rgfm_ratio_cond_prepare_workspace_bytes(const rgfm_ratio* h, int given, int n, size_t* bytes);
+int rgfm_ratio_cond_prepare(rgfm_ratio* h, const float* cond, int given, int n, float* ctx_out, void* ws,
+                            size_t ws_bytes, rgfm_stream_t stream);
+int rgfm_ratio_grad_cond_workspace_bytes(const rgfm_ratio* h, int given, int n, size_t* bytes);
+int rgfm_ratio_grad_log_ratio_cond(rgfm_ratio* h, const float* ctx, int given, const float* target, float* g_target,
+                                   float* log_ratio_out, int n, void* ws, size_t ws_bytes, rgfm_stream_t stream);
+
 /* Training pass of the ratio estimators (exact fp32 arithmetic on v_mfma_f32_32x32x2_f32, NCHW fp32 tensors,
  * stream-ordered, caller-owned workspace, nothing allocated or synchronised inside a call; every kind).
  *
@@ -345,6 +366,20 @@ int rgfm_sample_cond(rgfm_unet* h, float* s_inout, const float* mc_set, const fl
 int rgfm_sample_pair_grad_workspace_bytes(const rgfm_unet* hx, const rgfm_unet* hy, const rgfm_ratio* hr,
                                           int batch, size_t* bytes);
 int rgfm_sample_pair_grad(rgfm_unet* hx, rgfm_unet* hy, rgfm_ratio* hr, float* x_inout, float* y_inout,
+                          int batch, int num_steps, double gamma, int step_begin, int step_end, void* ws,
+                          size_t ws_bytes, rgfm_stream_t stream);
+
+/* Conditional sampling with GRADIENT LOG-RATIO guidance: the one-sided reading of rgfm_sample_pair_grad.  Euler loop
+ * of ONE net, in place on s_inout[B,C,H,W]; every step
+ *     s <- s + (v(s, t) + gamma * d log r / d s) dt
+ * with the observed side entering through ctx[B][hidden_dim] (rgfm_ratio_cond_prepare, once per condition batch) and
+ * the gradient that of rgfm_ratio_grad_log_ratio_cond.  No MC set, no pre-phase.  The target U-Net must have the
+ * estimator's shape for the side that is NOT given.  Conventions of rgfm_sample_cond: in place, stream-ordered, nothing
+ * allocated or synchronised, at most 4096 steps per call, every launch on `stream` (no side stream, no graph).  The
+ * estimator's convs follow the target net's conv arithmetic and raise its range flag, as in rgfm_sample_pair_grad. */
+int rgfm_sample_cond_grad_workspace_bytes(const rgfm_unet* h_unet, const rgfm_ratio* h_ratio, int given, int batch,
+                                          size_t* bytes);
+int rgfm_sample_cond_grad(rgfm_unet* h_unet, rgfm_ratio* h_ratio, float* s_inout, const float* ctx, int given,
                           int batch, int num_steps, double gamma, int step_begin, int step_end, void* ws,
                           size_t ws_bytes, rgfm_stream_t stream);
 

@@ -690,6 +690,88 @@ class RatioEngine(_EngineBase):
         return gx, gy, lr
 
 
+    # ---- one side given (conditional sampling) ------------------------
+    def _bind_given(self, given, cond, target_shape):
+        """Select the handle for a condition batch and a target of shape (C, S, S); returns (given as 0 / 1, the
+        estimator's image shapes as (condition's, target's))."""
+        if given not in ('x', 'y'):
+            raise ValueError(f"given must be 'x' or 'y', got {given!r}")
+        gi = 0 if given == 'x' else 1
+        if cond.dim() != 4:
+            raise _lib.RgfmError(f"expected condition images [B,C,S,S], got {tuple(cond.shape)}")
+        if target_shape is None:
+            target_shape = self._default_target_shape(gi)
+        probe = torch.empty(0, *target_shape, device='meta')
+        self.bind(*((cond, probe) if gi == 0 else (probe, cond)))
+        shapes = self.image_shapes()
+        sc, st = shapes[gi], shapes[1 - gi]
+        if tuple(cond.shape[1:]) != sc or tuple(target_shape) != st:
+            raise _lib.RgfmError(f"given={given!r}: expected the condition of shape [B,{sc[0]},{sc[1]},{sc[2]}] and the target of "
+                                 f"shape [B,{st[0]},{st[1]},{st[2]}], got {tuple(cond.shape)} and [B,{','.join(map(str, target_shape))}]")
+        return gi, (sc, st)
+
+    def _default_target_shape(self, gi):
+        return self.image_shapes()[1 - gi]
+
+    def cond_prepare(self, cond, given, target_shape=None):
+        """ctx [B, hidden_dim] = W1[:, given slice] f_given(cond) + b1 (rgfm_ratio_cond_prepare): the condition's encoder
+        and its half of the first score Linear, once.  `target_shape` (C, S, S) selects the handle of the flexible kind
+        (default: the sizes bound by the latest call); the context itself does not depend on it."""
+        m = self._module()
+        self._check_eval(m)
+        _require_hip(cond)
+        gi, _ = self._bind_given(given, cond, target_shape)
+        n, dev = cond.shape[0], cond.device
+        cond = cond.to(torch.float32).contiguous()
+        ctx = torch.empty(n, m.hidden_dim, device=dev, dtype=torch.float32)
+        if n == 0:
+            return ctx
+        L = _lib.lib()
+        with torch.cuda.device(dev):
+            h = self.handle(dev)
+            nb = ctypes.c_size_t()
+            _lib.check(L.rgfm_ratio_cond_prepare_workspace_bytes(h, gi, n, ctypes.byref(nb)))
+            ws = self._ws.get(nb.value, dev)
+            _lib.check(L.rgfm_ratio_cond_prepare(h, _ptr(cond), gi, n, _ptr(ctx), _ptr(ws), nb.value, _stream(dev)))
+        return ctx
+
+    def grad_log_ratio_cond(self, ctx, given, target):
+        """(d log_ratio/d target, log_ratio) with row b pairing ctx[b] (cond_prepare) and target[b]
+        (rgfm_ratio_grad_log_ratio_cond): only the target's encoder runs."""
+        m = self._module()
+        self._check_eval(m)
+        _require_hip(ctx, target)
+        if given not in ('x', 'y'):
+            raise ValueError(f"given must be 'x' or 'y', got {given!r}")
+        gi = 0 if given == 'x' else 1
+        if target.dim() != 4:
+            raise _lib.RgfmError(f"expected target images [B,C,S,S], got {tuple(target.shape)}")
+        self._bind_target(gi, target)
+        st = self.image_shapes()[1 - gi]
+        n = target.shape[0]
+        if tuple(target.shape[1:]) != st or tuple(ctx.shape) != (n, m.hidden_dim):
+            raise _lib.RgfmError(f"given={given!r}: expected the target of shape [B,{st[0]},{st[1]},{st[2]}] and ctx of shape "
+                                 f"[B,{m.hidden_dim}], got {tuple(target.shape)} and {tuple(ctx.shape)}")
+        target, ctx = target.contiguous(), ctx.contiguous()
+        g = torch.empty_like(target)
+        lr = torch.empty(n, device=target.device, dtype=torch.float32)
+        if n == 0:
+            return g, lr
+        dev = target.device
+        L = _lib.lib()
+        with torch.cuda.device(dev):
+            h = self.handle(dev)
+            nb = ctypes.c_size_t()
+            _lib.check(L.rgfm_ratio_grad_cond_workspace_bytes(h, gi, n, ctypes.byref(nb)))
+            ws = self._ws.get(nb.value, dev)
+            _lib.check(L.rgfm_ratio_grad_log_ratio_cond(h, _ptr(ctx), gi, _ptr(target), _ptr(g), _ptr(lr), n, _ptr(ws),
+                                                        nb.value, _stream(dev)))
+        return g, lr
+
+    def _bind_target(self, gi, target):
+        """Select the handle that serves a target batch (one geometry per fixed kind: nothing to select)."""
+
+
 class FlexibleRatioEngine(RatioEngine):
     """RatioEngine of FlexibleRatioEstimator.  The module is size-agnostic, a device handle is not (its rasters, tilings
     and workspaces follow from the image sizes): bind() reads (x_size, y_size) from the inputs of a call and handle()
@@ -713,6 +795,22 @@ class FlexibleRatioEngine(RatioEngine):
             self._handle, self._key, self._blob = self._cache.pop(sizes, (None, None, None))
             self._sizes = sizes
         return sizes
+
+    def _default_target_shape(self, gi):
+        if self._sizes is None:
+            raise _lib.RgfmError("FlexibleRatioEstimator: pass target_shape (C, S, S); no image sizes are bound yet")
+        m = self._module()
+        c, sz = ((m.y_channels, self._sizes[1]) if gi == 0 else (m.x_channels, self._sizes[0]))
+        return (c, sz, sz)
+
+    def _bind_target(self, gi, target):
+        # the context carries no image size: the given side keeps the size bound by cond_prepare
+        if self._sizes is None:
+            raise _lib.RgfmError("FlexibleRatioEstimator: call cond_prepare first (it binds the condition's image size)")
+        m = self._module()
+        sg = self._sizes[gi]
+        probe = torch.empty(0, m.x_channels if gi == 0 else m.y_channels, sg, sg, device='meta')
+        self.bind(*((probe, target) if gi == 0 else (target, probe)))
 
     def desc(self):
         if self._sizes is None:
@@ -1002,6 +1100,45 @@ def sample_cond(model, s, mc_set, ratios, num_steps, gamma, step_begin=0, step_e
             ws = _sampler_ws.get(nb.value, dev)
             _lib.check(L.rgfm_sample_cond(h, _ptr(s), _ptr(mc_set), _ptr(ratios), N, B, int(num_steps), float(gamma),
                                           int(step_begin), int(step_end), _ptr(ws), nb.value, _stream(dev)))
+        return s
+    return _range_guarded(dev, [s], run, [eng])
+
+
+def sample_cond_grad(model, ratio_estimator, s, ctx, given, num_steps, gamma, step_begin=0, step_end=None):
+    """In-place Euler loop of one U-Net with one-sided gradient log-ratio guidance (rgfm_sample_cond_grad): s [B, C, H, W],
+    ctx [B, hidden_dim] from ratio_estimator._engine.cond_prepare(condition, given)."""
+    eng, re = model._engine, ratio_estimator._engine
+    eng._check_eval(model)
+    re._check_eval(ratio_estimator)
+    if not isinstance(eng, UNetEngine):
+        raise _lib.RgfmError(f"conditional sampling needs a U-Net target (FlexibleUNet and its presets), got "
+                             f"{type(model).__name__}")
+    if given not in ('x', 'y'):
+        raise ValueError(f"given must be 'x' or 'y', got {given!r}")
+    gi = 0 if given == 'x' else 1
+    _require_hip(s, ctx)
+    if not s.is_contiguous():
+        raise _lib.RgfmError("s must be contiguous (it is updated in place)")
+    eng._check_input(model, s)
+    re._bind_target(gi, s)
+    B, dev = s.shape[0], s.device
+    if tuple(ctx.shape) != (B, ratio_estimator.hidden_dim):
+        raise _lib.RgfmError(f"expected ctx of shape [{B},{ratio_estimator.hidden_dim}] (a row per sample), got {tuple(ctx.shape)}")
+    if step_end is None:
+        step_end = num_steps
+    if B == 0:
+        return s
+    ctx = ctx.contiguous()
+    L = _lib.lib()
+
+    def run():
+        with torch.cuda.device(dev):
+            h, hr = eng.handle(dev), re.handle(dev)
+            nb = ctypes.c_size_t()
+            _lib.check(L.rgfm_sample_cond_grad_workspace_bytes(h, hr, gi, B, ctypes.byref(nb)))
+            ws = _sampler_ws.get(nb.value, dev)
+            _lib.check(L.rgfm_sample_cond_grad(h, hr, _ptr(s), _ptr(ctx), gi, B, int(num_steps), float(gamma),
+                                               int(step_begin), int(step_end), _ptr(ws), nb.value, _stream(dev)))
         return s
     return _range_guarded(dev, [s], run, [eng])
 

@@ -73,6 +73,11 @@ SIGNATURES = {
     "rgfm_ratio_grad_workspace_bytes": (c_int, [c_void_p, c_int, P(c_size_t)]),
     "rgfm_ratio_grad_log_ratio": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int,
                                           c_void_p, c_size_t, c_void_p]),
+    "rgfm_ratio_cond_prepare_workspace_bytes": (c_int, [c_void_p, c_int, c_int, P(c_size_t)]),
+    "rgfm_ratio_cond_prepare": (c_int, [c_void_p, c_void_p, c_int, c_int, c_void_p, c_void_p, c_size_t, c_void_p]),
+    "rgfm_ratio_grad_cond_workspace_bytes": (c_int, [c_void_p, c_int, c_int, P(c_size_t)]),
+    "rgfm_ratio_grad_log_ratio_cond": (c_int, [c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_int, c_void_p,
+                                               c_size_t, c_void_p]),
     "rgfm_ratio_train_workspace_bytes": (c_int, [c_void_p, c_int, P(c_size_t)]),
     "rgfm_ratio_forward_train": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_float, c_uint64,
                                          c_void_p, c_void_p, c_size_t, c_void_p]),
@@ -90,6 +95,9 @@ SIGNATURES = {
     "rgfm_sample_cond_workspace_bytes": (c_int, [c_void_p, c_int, c_int, P(c_size_t)]),
     "rgfm_sample_cond": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_double, c_int, c_int,
                                  c_void_p, c_size_t, c_void_p]),
+    "rgfm_sample_cond_grad_workspace_bytes": (c_int, [c_void_p, c_void_p, c_int, c_int, P(c_size_t)]),
+    "rgfm_sample_cond_grad": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_double, c_int, c_int,
+                                      c_void_p, c_size_t, c_void_p]),
     "rgfm_guidance_apply_cond": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_double,
                                          c_double, c_void_p, c_void_p, c_size_t, c_void_p]),
     "rgfm_sample_pair_workspace_bytes": (c_int, [c_void_p, c_void_p, c_int, c_int, P(c_size_t)]),

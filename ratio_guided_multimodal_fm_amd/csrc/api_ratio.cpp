@@ -468,6 +468,8 @@ struct RatioGradRun {
   float* ab1 = nullptr;  // [n][max_c][2] identity scale/shift: "SiLU on load"
   unsigned* amax = nullptr;  // one word per reverse conv: bits of max |gradient| of its input (ConvArgs::in_amax); zeroed per call
   int amax_used = 0;
+  int fs = 0;  // row stride of the feature / feature-gradient matrices: 0 = 2F (both sides, [f_x | f_y]); F in the one-sided run
+  int fstride() const { return fs ? fs : 2 * h->d.feature_dim; }
 
   struct Kept {
     float* z;
@@ -528,7 +530,7 @@ struct RatioGradRun {
     float* pooled = ws->f((size_t)n * curC);
     if (!dry) {
       launch_avgpool(cur, last.pooled ? nullptr : last.ab, pooled, n, S * S, curC, s);
-      launch_linear_mfma(pooled, h->params + e.fcw, h->params + e.fcb, feat + col0, n, curC, F, curC, 2 * F, s);
+      launch_linear_mfma(pooled, h->params + e.fcw, h->params + e.fcb, feat + col0, n, curC, F, curC, fstride(), s);
     }
   }
 
@@ -579,18 +581,18 @@ struct RatioGradRun {
     float* pooled = ws->f((size_t)n * curC);
     if (!dry) {
       launch_avgpool(cur, cur_is_z ? ab1 : nullptr, pooled, n, S * S, curC, s);
-      launch_linear_mfma(pooled, h->params + e.fcw, h->params + e.fcb, feat + col0, n, curC, F, curC, 2 * F, s);
+      launch_linear_mfma(pooled, h->params + e.fcw, h->params + e.fcb, feat + col0, n, curC, F, curC, fstride(), s);
     }
     return pooled;
   }
 
-  // reverse pass of one encoder: gfeat [n][2F] (columns col0 .. col0+F) -> gimg NCHW
+  // reverse pass of one encoder: gfeat [n][fstride()] (columns col0 .. col0+F) -> gimg NCHW
   void encode_bwd(const rgfm_ratio::Encoder& e, const std::vector<Kept>& kept, const float* gfeat, int col0, float* gimg) {
     const int F = h->d.feature_dim;
     const float* zeros = h->gradw + h->g_zeros;
     const Kept& last = kept.back();
     float* g = ws->f((size_t)n * last.C);  // gradient of the average-pooled vector
-    if (!dry) launch_linear_mfma(gfeat + col0, h->gradw + e.fcw_t, zeros, g, n, F, last.C, 2 * F, last.C, s);
+    if (!dry) launch_linear_mfma(gfeat + col0, h->gradw + e.fcw_t, zeros, g, n, F, last.C, fstride(), last.C, s);
     int mode = 2;  // first step: g is [n][C] behind the global average pool
     for (int i = (int)kept.size() - 1; i >= 0; --i) {
       const Kept& k = kept[i];
@@ -638,8 +640,7 @@ struct RatioGradRun {
     }
   }
 
-  void run(const float* x, const float* y, float* gx, float* gy, float* log_ratio) {
-    const int F = h->d.feature_dim;
+  void begin() {
     ab1 = ws->f((size_t)n * h->max_c * 2);
     amax = reinterpret_cast<unsigned*>(ws->f(64));
     amax_used = 0;
@@ -647,6 +648,11 @@ struct RatioGradRun {
       launch_fill_ab_identity(ab1, (size_t)n * h->max_c, s);
       (void)hipMemsetAsync(amax, 0, 64 * sizeof(unsigned), s);
     }
+  }
+
+  void run(const float* x, const float* y, float* gx, float* gy, float* log_ratio) {
+    const int F = h->d.feature_dim;
+    begin();
     float* feat = ws->f((size_t)n * 2 * F);
     std::vector<Kept> kx, ky;
     if (h->gn_encoders()) {
@@ -689,7 +695,90 @@ struct RatioGradRun {
     encode_bwd(h->ex, kx, g, 0, gx);
     encode_bwd(h->ey, ky, g, F, gy);
   }
+
+  // One side only (conditional sampling): d log_ratio / d target with the other side's share of the first score Linear,
+  // ctx [n][Hd] = W[:, given slice] f_given + b (RatioCondPrepare), held fixed.  Only the target's encoder runs, forward
+  // and reverse; the first hidden layer is u = ctx + W[:, target slice] f_target (cond_ln_silu_kernel), and its input
+  // gradient is taken for the target's F columns alone -- rows of the transposed weight, which are contiguous.
+  void run_cond(const float* ctx, int given, const float* target, float* g_target, float* log_ratio) {
+    const int F = h->d.feature_dim;
+    fs = F;
+    begin();
+    const rgfm_ratio::Encoder& e = given ? h->ex : h->ey;
+    const float* zeros = h->gradw + h->g_zeros;
+    float* feat = ws->f((size_t)n * F);
+    std::vector<Kept> kt;
+    if (h->gn_encoders()) encode_gn(e, target, feat, 0, kt);
+    else encode(e, target, feat, 0, kt);
+    std::vector<float*> us;
+    float* cur = nullptr;
+    for (size_t l = 0; l < h->hidden.size(); ++l) {
+      const auto& dn = h->hidden[l];
+      float* u = ws->f((size_t)n * dn.out);
+      float* a = ws->f((size_t)n * dn.out);
+      if (l == 0) {
+        float* ut = ws->f((size_t)n * dn.out);
+        if (!dry) {
+          launch_linear_mfma(feat, h->gradw + (given ? h->w1x : h->w1y), zeros, ut, n, F, dn.out, F, dn.out, s);
+          launch_cond_ln_silu(ctx, ut, h->params + dn.lw, h->params + dn.lb, u, a, n, dn.out, s);
+        }
+      } else if (!dry) {
+        launch_linear_mfma(cur, h->params + dn.w, h->params + dn.b, u, n, dn.in, dn.out, dn.in, dn.out, s);
+        (void)hipMemcpyAsync(a, u, (size_t)n * dn.out * sizeof(float), hipMemcpyDeviceToDevice, s);
+        launch_layernorm_silu(a, h->params + dn.lw, h->params + dn.lb, n, dn.out, s);
+      }
+      us.push_back(u);
+      cur = a;
+    }
+    float* score = ws->f(n);
+    float* g = ws->f((size_t)n * h->head_in);
+    if (!dry) {
+      launch_ratio_head(cur, h->params + h->headw, h->params + h->headb, score, n, h->head_in, h->d.loss_type, 0, s);
+      launch_ratio_head_bwd(score, h->params + h->headw, g, log_ratio, n, h->head_in, h->d.loss_type, s);
+    }
+    for (int l = (int)h->hidden.size() - 1; l >= 0; --l) {
+      const auto& dn = h->hidden[l];
+      const int in = l ? dn.in : F;  // layer 0: the target's columns of the concatenation only
+      const float* wt = h->gradw + dn.w_t + (l || given ? 0 : (size_t)F * dn.out);
+      float* gu = ws->f((size_t)n * dn.out);
+      float* gi = ws->f((size_t)n * in);
+      if (!dry) {
+        launch_layernorm_silu_bwd(us[l], g, h->params + dn.lw, h->params + dn.lb, gu, n, dn.out, s);
+        launch_linear_mfma(gu, wt, zeros, gi, n, dn.out, in, dn.out, in, s);
+      }
+      g = gi;
+    }
+    encode_bwd(e, kt, g, 0, g_target);
+  }
 };
+
+// ctx [n][Hd] = W[:, given slice] f_given(cond) + b of the first score Linear: the given side's encoder once (RatioRun::
+// encode, as the cross path runs it) and one linear_mfma on the contiguous column slice pack_ratio keeps.
+struct RatioCondPrepare {
+  rgfm_ratio* h;
+  int n;
+  Bump* ws;
+  hipStream_t s;
+  bool dry;
+
+  void run(const float* cond, int given, float* ctx) {
+    const int F = h->d.feature_dim;
+    const auto& d0 = h->hidden[0];
+    float* feat = ws->f((size_t)n * F);
+    RatioRun r{h, n, ws, s, dry};
+    r.encode(given ? h->ey : h->ex, cond, feat, 0, F);
+    if (dry) return;
+    ProfScope p(RGFM_KCLASS_OTHER, 0, s);
+    launch_linear_mfma(feat, h->gradw + (given ? h->w1y : h->w1x), h->params + d0.b, ctx, n, F, d0.out, F, d0.out, s);
+  }
+};
+
+size_t ratio_cond_grad_bytes(rgfm_ratio* h, int given, int n) {
+  Bump b;
+  RatioGradRun r{h, n, &b, nullptr, true};
+  r.run_cond(nullptr, given, nullptr, nullptr, nullptr);
+  return b.off;
+}
 
 size_t ratio_grad_bytes(rgfm_ratio* h, int n) {
   Bump b;
@@ -823,6 +912,138 @@ extern "C" int rgfm_sample_pair_grad(rgfm_unet* hx, rgfm_unet* hy, rgfm_ratio* h
     if (overlap) HIP_TRY(hipStreamWaitEvent(s, ds->join, 0));
     launch_euler_grad(x_inout, vx, gx, (size_t)batch * dx, gf, dt, s);
     launch_euler_grad(y_inout, vy, gy, (size_t)batch * dy, gf, dt, s);
+  }
+  HIP_TRY(hipGetLastError());
+  return RGFM_OK;
+}
+
+// ------------------------------------------------------------------ one-sided gradient: conditional sampling
+namespace {
+
+// (channels, size) of the estimator's x (side 0) or y (side 1) images
+void ratio_side_shape(const rgfm_ratio* hr, int side, int* c, int* sz) {
+  if (hr->d.kind == RGFM_RATIO_FLEXIBLE) *c = side ? hr->geom.y_channels : hr->geom.x_channels, *sz = side ? hr->geom.y_size : hr->geom.x_size;
+  else if (hr->d.kind == RGFM_RATIO_MNIST_SVHN) *c = side ? 3 : 1, *sz = 32;
+  else *c = 1, *sz = 28;
+}
+
+// check_grad_pair for one side: the target U-Net must be the estimator's shape for the side that is NOT given
+int check_grad_side(const rgfm_unet* hu, const rgfm_ratio* hr, int given) {
+  int c = 0, sz = 0;
+  ratio_side_shape(hr, given ? 0 : 1, &c, &sz);
+  if (hu->d.in_channels != c || hu->d.img_size != sz)
+    return fail(RGFM_EINVAL, "conditional gradient guidance: given the estimator's %s, its %s is %dx%dx%d; the target U-Net is %dx%dx%d",
+                given ? "y" : "x", given ? "x" : "y", c, sz, sz, hu->d.in_channels, hu->d.img_size, hu->d.img_size);
+  return RGFM_OK;
+}
+
+int check_given(int given) { return given == 0 || given == 1 ? RGFM_OK : fail(RGFM_EINVAL, "given must be 0 (the condition is x) or 1 (y)"); }
+
+}  // namespace
+
+extern "C" int rgfm_ratio_cond_prepare_workspace_bytes(const rgfm_ratio* h, int given, int n, size_t* bytes) {
+  if (!h || !bytes || n < 1) return fail(RGFM_EINVAL, "bad argument");
+  if (int rc = check_given(given)) return rc;
+  Bump b;
+  RatioCondPrepare r{const_cast<rgfm_ratio*>(h), n, &b, nullptr, true};
+  r.run(nullptr, given, nullptr);
+  *bytes = b.off;
+  return RGFM_OK;
+}
+
+extern "C" int rgfm_ratio_cond_prepare(rgfm_ratio* h, const float* cond, int given, int n, float* ctx_out, void* ws,
+                                       size_t ws_bytes, rgfm_stream_t stream) {
+  refresh_modes();
+  if (!h || !cond || !ctx_out || !ws) return fail(RGFM_EINVAL, "null argument");
+  size_t need = 0;
+  int rc = rgfm_ratio_cond_prepare_workspace_bytes(h, given, n, &need);
+  if (rc) return rc;
+  if (need > ws_bytes) return fail(RGFM_ENOMEM, "workspace too small: %zu < %zu", ws_bytes, need);
+  Bump b;
+  b.base = (char*)ws, b.cap = ws_bytes, b.dry = false;
+  RatioCondPrepare r{h, n, &b, (hipStream_t)stream, false};
+  r.run(cond, given, ctx_out);
+  HIP_TRY(hipGetLastError());
+  return RGFM_OK;
+}
+
+extern "C" int rgfm_ratio_grad_cond_workspace_bytes(const rgfm_ratio* h, int given, int n, size_t* bytes) {
+  if (!h || !bytes || n < 1) return fail(RGFM_EINVAL, "bad argument");
+  if (int rc = check_given(given)) return rc;
+  *bytes = ratio_cond_grad_bytes(const_cast<rgfm_ratio*>(h), given, n);
+  return RGFM_OK;
+}
+
+extern "C" int rgfm_ratio_grad_log_ratio_cond(rgfm_ratio* h, const float* ctx, int given, const float* target, float* g_target,
+                                              float* log_ratio_out, int n, void* ws, size_t ws_bytes, rgfm_stream_t stream) {
+  if (!h || !ctx || !target || !g_target || !ws) return fail(RGFM_EINVAL, "null argument");
+  size_t need = 0;
+  int rc = rgfm_ratio_grad_cond_workspace_bytes(h, given, n, &need);
+  if (rc) return rc;
+  if (need > ws_bytes) return fail(RGFM_ENOMEM, "workspace too small: %zu < %zu", ws_bytes, need);
+  refresh_modes();
+  Bump b;
+  b.base = (char*)ws, b.cap = ws_bytes, b.dry = false;
+  RatioGradRun r{h, n, &b, (hipStream_t)stream, false};
+  r.run_cond(ctx, given, target, g_target, log_ratio_out);
+  HIP_TRY(hipGetLastError());
+  return RGFM_OK;
+}
+
+// One net with gradient log-ratio guidance, the other side observed: s <- s + (v(s, t) + gamma dlogr/ds) dt, every step.
+// The velocity net and the estimator's one-sided pass run one after the other on `stream` and share one scratch region.
+extern "C" int rgfm_sample_cond_grad_workspace_bytes(const rgfm_unet* h, const rgfm_ratio* hr, int given, int batch, size_t* bytes) {
+  if (!h || !hr || !bytes || batch < 1) return fail(RGFM_EINVAL, "bad argument");
+  int rc = check_given(given);
+  if (rc || (rc = check_grad_side(h, hr, given))) return rc;
+  const size_t d = (size_t)h->d.in_channels * h->d.img_size * h->d.img_size;
+  *bytes = table_bytes(h, 4096) + counter_bytes(batch) + 2 * ((batch * d * 4 + 255) & ~(size_t)255) +
+           std::max(unet_eval_bytes(const_cast<rgfm_unet*>(h), batch), ratio_cond_grad_bytes(const_cast<rgfm_ratio*>(hr), given, batch));
+  return RGFM_OK;
+}
+
+extern "C" int rgfm_sample_cond_grad(rgfm_unet* h, rgfm_ratio* hr, float* s_inout, const float* ctx, int given, int batch,
+                                     int num_steps, double gamma, int step_begin, int step_end, void* ws, size_t ws_bytes,
+                                     rgfm_stream_t stream) {
+  refresh_modes();
+  if (!h || !hr || !s_inout || !ctx || !ws) return fail(RGFM_EINVAL, "null argument");
+  int rc = check_given(given);
+  if (rc || (rc = check_grad_side(h, hr, given))) return rc;
+  if (batch < 1 || num_steps < 1 || step_begin < 0 || step_end > num_steps || step_begin > step_end)
+    return fail(RGFM_EINVAL, "bad step range [%d,%d) of %d", step_begin, step_end, num_steps);
+  const int ns = step_end - step_begin;
+  if (ns > 4096) return fail(RGFM_EINVAL, "at most 4096 steps per call");
+  size_t need = 0;
+  if ((rc = rgfm_sample_cond_grad_workspace_bytes(h, hr, given, batch, &need))) return rc;
+  if (need > ws_bytes) return fail(RGFM_ENOMEM, "workspace too small: %zu < %zu", ws_bytes, need);
+  if (ns == 0) return RGFM_OK;
+  hipStream_t s = (hipStream_t)stream;
+  const size_t d = (size_t)h->d.in_channels * h->d.img_size * h->d.img_size;
+  Bump b;
+  b.base = (char*)ws, b.cap = ws_bytes, b.dry = false;
+  float* table = b.f((size_t)4096 * h->temb_total);
+  unsigned* cnt = reinterpret_cast<unsigned*>(b.f(batch));
+  float* v = b.f((size_t)batch * d);
+  float* g = b.f((size_t)batch * d);
+  HIP_TRY(hipMemsetAsync(cnt, 0, (size_t)batch * sizeof(unsigned), s));
+  launch_time_table(h, nullptr, num_steps, step_begin, ns, table, s);
+  const size_t mark = b.off;
+  const float dt = (float)(1.0 / (double)num_steps), gf = (float)gamma;
+  for (int i = 0; i < ns; ++i) {
+    {
+      b.off = mark;
+      UNetRun r{h, batch, &b, s, table + (size_t)i * h->temb_total, 0, false};
+      r.fin_counter = cnt;
+      if ((rc = r.run(s_inout, v, nullptr, 0.f))) return rc;
+    }
+    {
+      b.off = mark;
+      RatioGradRun r{hr, batch, &b, s, false};
+      r.flag = h->range_flag;
+      ModeScope ratio_mode(h->conv_mode);  // (the estimator's convs follow the target net's handle)
+      r.run_cond(ctx, given, s_inout, g, nullptr);
+    }
+    launch_euler_grad(s_inout, v, g, (size_t)batch * d, gf, dt, s);
   }
   HIP_TRY(hipGetLastError());
   return RGFM_OK;

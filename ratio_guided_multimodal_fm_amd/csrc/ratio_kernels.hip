@@ -304,6 +304,65 @@ void launch_cross_ln_silu(const float* ux, const float* uy, const float* bias, c
   hipLaunchKernelGGL(cross_ln_silu_kernel, dim3((rows + 3) / 4), dim3(256), 0, s, ux, uy, bias, w, b, out, row0, rows, ny, n);
 }
 
+// The first hidden layer of the score MLP for MATCHED rows with one side precomputed (the one-sided gradient of
+// conditional sampling): u[r] = ctx[r] + ut[r], where ctx = W[:, given slice] f_given + b was prepared once
+// (rgfm_ratio_cond_prepare) and ut = W[:, target slice] f_target comes from this step's linear_mfma (bias zero).  Stores
+// the pre-activation u, which layernorm_silu_bwd_kernel reads, and a = silu(LayerNorm(u)) in one pass -- in place of
+// the copy and the in-place layernorm_silu_kernel of the two-sided path.  Shape of cross_ln_silu_kernel: wave per row,
+// the row in registers (n <= 1024: four float4 per lane), lane partials in element order, then the xor butterfly.
+__global__ __launch_bounds__(256) void cond_ln_silu_kernel(const float* __restrict__ ctx, const float* __restrict__ ut,
+                                                          const float* __restrict__ w, const float* __restrict__ b,
+                                                          float* __restrict__ u, float* __restrict__ a, int rows, int n) {
+  const int lane = threadIdx.x & 63;
+  const int row = blockIdx.x * 4 + (threadIdx.x >> 6);
+  if (row >= rows) return;
+  const f32x4* pc = reinterpret_cast<const f32x4*>(ctx + (size_t)row * n);
+  const f32x4* pt = reinterpret_cast<const f32x4*>(ut + (size_t)row * n);
+  f32x4* pu = reinterpret_cast<f32x4*>(u + (size_t)row * n);
+  f32x4* pa = reinterpret_cast<f32x4*>(a + (size_t)row * n);
+  const int n4 = n >> 2;
+  f32x4 v[4];
+  float s = 0.f;
+#pragma unroll
+  for (int k = 0; k < 4; ++k) {
+    const int c = lane + 64 * k;
+    v[k] = f32x4{0.f, 0.f, 0.f, 0.f};
+    if (c < n4) {
+      const f32x4 p = pc[c], q = pt[c];
+      v[k].x = p.x + q.x, v[k].y = p.y + q.y, v[k].z = p.z + q.z, v[k].w = p.w + q.w;
+      pu[c] = v[k];
+      s += (v[k].x + v[k].y) + (v[k].z + v[k].w);
+    }
+  }
+  const float mean = wsum(s) / (float)n;
+  float m2 = 0.f;
+#pragma unroll
+  for (int k = 0; k < 4; ++k)
+    if (lane + 64 * k < n4) {
+      const float d0 = v[k].x - mean, d1 = v[k].y - mean, d2 = v[k].z - mean, d3 = v[k].w - mean;
+      m2 += (d0 * d0 + d1 * d1) + (d2 * d2 + d3 * d3);
+    }
+  const float rstd = 1.0f / sqrtf(wsum(m2) / (float)n + 1e-5f);
+#pragma unroll
+  for (int k = 0; k < 4; ++k) {
+    const int c = lane + 64 * k;
+    if (c < n4) {
+      const f32x4 g = reinterpret_cast<const f32x4*>(w)[c], be = reinterpret_cast<const f32x4*>(b)[c];
+      f32x4 o;
+      o.x = silu_f((v[k].x - mean) * rstd * g.x + be.x);
+      o.y = silu_f((v[k].y - mean) * rstd * g.y + be.y);
+      o.z = silu_f((v[k].z - mean) * rstd * g.z + be.z);
+      o.w = silu_f((v[k].w - mean) * rstd * g.w + be.w);
+      pa[c] = o;
+    }
+  }
+}
+
+void launch_cond_ln_silu(const float* ctx, const float* ut, const float* w, const float* b, float* u, float* a, int rows, int n,
+                         hipStream_t s) {
+  hipLaunchKernelGGL(cond_ln_silu_kernel, dim3((rows + 3) / 4), dim3(256), 0, s, ctx, ut, w, b, u, a, rows, n);
+}
+
 __device__ __forceinline__ float logsigmoid_f(float x) { return fminf(x, 0.f) - log1pf(expf(-fabsf(x))); }
 
 // final Linear(n -> 1) + log_ratio (ratio_flexible.py:366-385) / exp (sample_mnist_svhn.py:111)

@@ -382,6 +382,10 @@ void launch_layernorm_silu(float* x, const float* w, const float* b, int rows, i
 // pair indices r = row0 .. row0 + rows - 1 of the row-major [nx][ny] matrix (n % 4 == 0, n <= 1024)
 void launch_cross_ln_silu(const float* ux, const float* uy, const float* bias, const float* w, const float* b, float* out,
                           long long row0, int rows, int ny, int n, hipStream_t s);
+// One-sided gradient, first hidden layer for matched rows: u[r] = ctx[r] + ut[r] (stored: layernorm_silu_bwd reads it) and
+// a[r] = silu(LayerNorm(u[r])) in one pass (n % 4 == 0, n <= 1024); ctx, ut, u, a are [rows][n], u and a distinct from the inputs
+void launch_cond_ln_silu(const float* ctx, const float* ut, const float* w, const float* b, float* u, float* a, int rows, int n,
+                         hipStream_t s);
 void launch_ratio_head(const float* x, const float* w, const float* b, float* out, int rows, int n,
                        int loss, int what, hipStream_t s);
 void launch_bn_fold(const float* w, const float* b, const float* rm, const float* rv, float* scale,

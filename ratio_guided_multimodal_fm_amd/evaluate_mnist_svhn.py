@@ -41,12 +41,21 @@ def evaluate_coherence(samples_mnist, samples_svhn, mnist_classifier, svhn_class
     return {'coherence_acc': float(acc), 'num_samples': len(samples_mnist)}
 
 
-def evaluate_conditional_coherence(condition, samples, given, mnist_classifier, svhn_classifier, device):
+def evaluate_conditional_coherence(condition, samples, given, mnist_classifier, svhn_classifier, device,
+                                   fm_target=None, ratio_estimator=None, guidance_method='mc_feng', **sampler_kwargs):
     """Share of rows where the classifier of the condition's modality and the classifier of the generated modality
     agree: `condition` [B, ...] are the images `samples` [B, ...] were generated for (``sample_conditional``), `given`
-    ('mnist' or 'svhn') names the condition's modality."""
+    ('mnist' or 'svhn') names the condition's modality.  With ``samples=None`` they are generated here:
+    ``sample_conditional(fm_target, ratio_estimator, condition, given, guidance_method=guidance_method,
+    **sampler_kwargs)`` ('mc_feng' or 'grad_log_ratio'; num_steps, guidance_strength, mc_batch_size as keywords)."""
     if given not in ('mnist', 'svhn'):
         raise ValueError(f"given must be 'mnist' or 'svhn', got {given!r}")
+    if samples is None:
+        if fm_target is None or ratio_estimator is None:
+            raise ValueError("samples=None needs fm_target and ratio_estimator to generate them")
+        from .utils.flow_utils import sample_conditional
+        samples = sample_conditional(fm_target, ratio_estimator, condition, 'x' if given == 'mnist' else 'y',
+                                     guidance_method=guidance_method, device=device, **sampler_kwargs)
     if len(condition) != len(samples):
         raise ValueError(f"{len(condition)} condition images for {len(samples)} samples")
     mnist, svhn = (condition, samples) if given == 'mnist' else (samples, condition)

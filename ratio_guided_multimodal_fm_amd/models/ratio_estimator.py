@@ -79,3 +79,20 @@ class RatioEstimator(nn.Module):
             raise ValueError(f"Unknown loss_type: {self.loss_type}")
         gx, gy, _ = self._engine.grad_log_ratio(x, y)
         return gx, gy
+
+    def grad_log_ratio_given(self, condition, target, given='x'):
+        """d log_ratio / d target with the other argument observed: ``given='x'`` -- `condition` is x, `target` is y and
+        the result is what ``grad_log_ratio(condition, target)[1]`` returns (to fp32 rounding); ``given='y'`` -- the
+        other way round.  Row b pairs ``condition[b]`` with ``target[b]``.  The condition's encoder and its half of the
+        first score Linear run once (``rgfm_ratio_cond_prepare``), then only the target's encoder runs, forward and
+        reverse (``rgfm_ratio_grad_log_ratio_cond``): the step of conditional sampling with
+        ``guidance_method='grad_log_ratio'``, which prepares the context once for the whole loop."""
+        if self.loss_type not in ("disc", "rulsif"):
+            raise ValueError(f"Unknown loss_type: {self.loss_type}")
+        if given not in ('x', 'y'):
+            raise ValueError(f"given must be 'x' or 'y', got {given!r}")
+        if condition.shape[0] != target.shape[0]:
+            from .._lib import RgfmError
+            raise RgfmError("condition and target must have the same batch size")
+        ctx = self._engine.cond_prepare(condition, given, tuple(target.shape[1:]))
+        return self._engine.grad_log_ratio_cond(ctx, given, target)[0]

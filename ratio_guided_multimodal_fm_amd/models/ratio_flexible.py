@@ -16,7 +16,7 @@ class FlexibleRatioEstimator(nn.Module):
     channels and sizes 8..64 (reference ``:69-154``).  The parameters do not depend on the image sizes (the encoders
     end in a global average pool); the sizes are read from the inputs of each call and the engine keeps one device
     handle per (Sx, Sy) pair seen.  ``forward`` / ``forward_train`` / ``log_ratio`` / ``grad_log_ratio`` /
-    ``forward_cross`` / ``cross_log_ratio`` / ``dropout_p`` as for ``RatioEstimator``, whose architecture at 1x28x28 + 1x28x28 this is."""
+    ``grad_log_ratio_given`` / ``forward_cross`` / ``cross_log_ratio`` / ``dropout_p`` as for ``RatioEstimator``, whose architecture at 1x28x28 + 1x28x28 this is."""
     _engine = engine_property(lambda m: FlexibleRatioEngine(m))
 
     def __init__(self, x_channels=1, y_channels=1, feature_dim=256, hidden_dim=512, loss_type='disc'):
@@ -40,6 +40,7 @@ class FlexibleRatioEstimator(nn.Module):
     dropout_p = RatioEstimator.dropout_p
     log_ratio = RatioEstimator.log_ratio
     grad_log_ratio = RatioEstimator.grad_log_ratio
+    grad_log_ratio_given = RatioEstimator.grad_log_ratio_given
     forward_cross = RatioEstimator.forward_cross
     cross_log_ratio = RatioEstimator.cross_log_ratio
 
@@ -145,3 +146,6 @@ class RatioEstimatorMNISTSVHN(nn.Module):
             raise ValueError(f"Unknown loss_type: {self.loss_type}")
         gx, gy, _ = self._engine.grad_log_ratio(x, y)
         return gx, gy
+
+    # (one side observed: the same surface as RatioEstimator)
+    grad_log_ratio_given = RatioEstimator.grad_log_ratio_given

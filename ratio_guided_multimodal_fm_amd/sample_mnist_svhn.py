@@ -53,7 +53,8 @@ def main(argv=None):
                         '--guidance_method mc_feng --guidance_strength 1.0')
     p.add_argument('--given', type=str, default=None, choices=['mnist', 'svhn'],
                    help="conditional sampling (this build's extension): the modality of --condition; the other one is "
-                        "generated, one sample per condition image (MC guidance, --guidance_strength, --mc_batch_size)")
+                        "generated, one sample per condition image (MC guidance with --guidance_strength and "
+                        "--mc_batch_size; with --guidance_method grad_log_ratio the one-sided gradient guidance, no MC set)")
     p.add_argument('--condition', type=str, default=None, metavar='FILE.npy|.pt',
                    help='condition images [B,1,32,32] (--given mnist) or [B,3,32,32] (--given svhn)')
     args = p.parse_args(argv)
@@ -102,10 +103,14 @@ def main(argv=None):
         condition = load_condition(args.condition, shape)
         target, name = (fm_svhn, 'svhn') if args.given == 'mnist' else (fm_mnist, 'mnist')
         print(f"\nSampling {len(condition)} {name} images given {args.given}...")
+        # ('none' and 'mc_feng' both mean the MC guidance here: a conditional sampler without guidance ignores --condition)
+        method = 'grad_log_ratio' if args.guidance_method == 'grad_log_ratio' else 'mc_feng'
         out_t = sample_conditional(target, ratio, condition.to(device), 'x' if args.given == 'mnist' else 'y',
-                                   args.num_steps, args.guidance_strength, args.mc_batch_size, device=device)
+                                   args.num_steps, args.guidance_strength, args.mc_batch_size, device=device,
+                                   guidance_method=method)
         os.makedirs('outputs/mnist_svhn', exist_ok=True)
-        out = f"outputs/mnist_svhn/samples_given_{args.given}_gamma{args.guidance_strength}.pt"
+        tag = '_grad_log_ratio' if method == 'grad_log_ratio' else ''
+        out = f"outputs/mnist_svhn/samples_given_{args.given}{tag}_gamma{args.guidance_strength}.pt"
         torch.save({args.given: condition, name: out_t.cpu()}, out)
         print(f"Saved samples: {out}")
         return 0

@@ -138,22 +138,33 @@ def paired_sampler(fm_x, fm_y, ratio_estimator, guidance_method, guidance_streng
 
 
 def sample_conditional(fm_target, ratio_estimator, condition, given='x', num_steps=100, guidance_strength=1.0,
-                       mc_batch_size=256, mc_samples=None, device=None):
+                       mc_batch_size=256, mc_samples=None, device=None, guidance_method='mc_feng'):
     """Partners for `condition` in the other modality: one sample of `fm_target`'s modality per condition image.
 
     ``given='x'``: `condition` is the estimator's x argument and the target is its y; ``given='y'`` the other way
-    round.  The MC guidance of the paired sampler (reference ``src/sample_mnist_svhn.py:124-171``) with one side
-    observed: the MC set is `fm_target`'s own unguided samples, sample b weighs MC sample j by
-    r(condition_b, mc_j) times its own Gaussian factor (``rgfm_sample_cond``), and only the target net is integrated.
+    round.  Only the target net is integrated.
 
+    ``guidance_method='mc_feng'`` (default): the MC guidance of the paired sampler (reference
+    ``src/sample_mnist_svhn.py:124-171``) with one side observed: the MC set is `fm_target`'s own unguided samples,
+    sample b weighs MC sample j by r(condition_b, mc_j) times its own Gaussian factor (``rgfm_sample_cond``).
     Draw order (global generator of the device): the MC noise ``[mc_batch_size, C, H, W]`` first, then the start
     noise ``[len(condition), C, H, W]``.  With `mc_samples` (terminal MC samples of an earlier call) no MC noise is
-    drawn and no pre-phase runs.  Returns the samples ``[len(condition), C, H, W]`` on the device.  U-Net targets
-    only; gradient log-ratio guidance and ``--sharded`` launches have no conditional form yet.
+    drawn and no pre-phase runs.
+
+    ``guidance_method='grad_log_ratio'``: the one-sided reading of the paired gradient log-ratio sampler, every step
+    ``s += (v(s, t) + guidance_strength * d log r / d s) dt`` (``rgfm_sample_cond_grad``).  Only the start noise
+    ``[len(condition), C, H, W]`` is drawn; there is no MC set and no pre-phase (`mc_batch_size` and `mc_samples` are
+    ignored).  The condition's encoder and its half of the first score Linear run once, before the loop
+    (``rgfm_ratio_cond_prepare``); each step runs the target's encoder alone, forward and reverse.
+
+    Returns the samples ``[len(condition), C, H, W]`` on the device.  U-Net targets only; ``--sharded`` launches have
+    no conditional form yet.
     """
     from .._lib import RgfmError
     if given not in ('x', 'y'):
         raise ValueError(f"given must be 'x' or 'y', got {given!r}")
+    if guidance_method not in ('mc_feng', 'grad_log_ratio'):
+        raise ValueError(f"guidance_method must be 'mc_feng' or 'grad_log_ratio', got {guidance_method!r}")
     if not isinstance(fm_target._engine, _engine.UNetEngine):
         raise RgfmError(f"sample_conditional needs a U-Net target (FlexibleUNet and its presets); "
                         f"{type(fm_target).__name__} has no conditional sampler")
@@ -164,6 +175,10 @@ def sample_conditional(fm_target, ratio_estimator, condition, given='x', num_ste
     dev = _device(condition.device if device is None else device)
     condition = condition.to(dev, torch.float32).contiguous()
     shape = (fm_target.in_channels, fm_target.img_size, fm_target.img_size)
+    if guidance_method == 'grad_log_ratio':
+        s_t = torch.randn(condition.shape[0], *shape, device=dev)
+        ctx = ratio_estimator._engine.cond_prepare(condition, given, shape)
+        return _engine.sample_cond_grad(fm_target, ratio_estimator, s_t, ctx, given, num_steps, guidance_strength)
     if mc_samples is None:
         mc = torch.randn(mc_batch_size, *shape, device=dev)
         _engine.sample_single(fm_target, mc, num_steps)
