@@ -383,6 +383,64 @@ int rgfm_sample_cond_grad(rgfm_unet* h_unet, rgfm_ratio* h_ratio, float* s_inout
                           int batch, int num_steps, double gamma, int step_begin, int step_end, void* ws,
                           size_t ws_bytes, rgfm_stream_t stream);
 
+/* ------------------------------------------------------------------------
+ * Choice of ODE solver for the U-Net sampler loops.  Added functions only: the ABI version is unchanged.
+ *
+ * Each rgfm_sample_*_ode is its Euler namesake above with `int solver` in front of `ws`; each workspace query takes
+ * `solver` in front of `bytes`.  RGFM_SOLVER_EULER runs the very loop of the old entry point (same launches, same
+ * workspace size, same bits); the old entry points are that case.
+ *
+ * RGFM_SOLVER_MIDPOINT (explicit midpoint rule, second order): step i of num_steps, dt = 1.0 / num_steps,
+ *     t1 = i dt          k1 = F(s, t1)       s_mid = s + (dt / 2) k1
+ *     t2 = (i + 0.5) dt  k2 = F(s_mid, t2)   s     = s + dt k2
+ * with F the loop's WHOLE guided velocity at the stage's own state and time, scalars in double and rounded to fp32
+ * where a tensor op consumes them (as in the Euler loops):
+ *   - single, and pair with n_mc = 0: F is the network output;
+ *   - MC guidance (pair, cond): F = (1 - gamma) v + gamma g with the distances, importance weights, sigma_t and
+ *     1 - t + eps all taken at the stage's state and time; a stage is guided iff ITS OWN time is > 1e-3 (stage 1 of
+ *     step 0 never is; stage 2 of step 0 is whenever 0.5 / num_steps > 1e-3);
+ *   - gradient guidance (pair_grad, cond_grad): F = v + gamma grad log r at the stage's state; in the paired loops both
+ *     modalities advance stage by stage, stage 2 sees (x_mid, y_mid).
+ * No stage is ever evaluated at t = 1 (where the MC guidance's 1 / (1 - t + eps) is 1000).  Two network evaluations
+ * per step.  The update epilogues (out-conv, guid_apply, euler_grad) read the stage's start state from one buffer and
+ * write another: no copies on the step path.
+ *
+ * Conventions of the Euler loops: in place on the caller's state, [step_begin, step_end) counts WHOLE steps (running
+ * [0, k) then [k, n) gives the bits of [0, n)), stream-ordered, nothing allocated or synchronised, a row's result
+ * depends on its own row only.  The paired loops fork and join the side stream once per STAGE.
+ * Workspace: the Euler workspace plus one mid-state buffer per modality (a workspace sized by the Euler query is
+ * RGFM_ENOMEM for a midpoint call).
+ * Step cap: the time table of a call holds 4096 rows and a midpoint step takes two (t1 and t2: the table of the
+ * 2 num_steps half-steps), so a midpoint call covers at most 2048 steps -- RGFM_EINVAL beyond that; split the range.
+ * RGFM_GRAPH=1: a midpoint call runs kernel by kernel, nothing is captured or replayed (graph replay is Euler only).
+ * An unknown `solver` is RGFM_EINVAL before anything is enqueued: the state is untouched.
+ * The FlowMatchingModel loops (rgfm_fmnet_sample_*) are Euler only.
+ * ---------------------------------------------------------------------- */
+#define RGFM_SOLVER_EULER 0
+#define RGFM_SOLVER_MIDPOINT 1
+int rgfm_sample_single_ode_workspace_bytes(const rgfm_unet* h, int batch, int solver, size_t* bytes);
+int rgfm_sample_single_ode(rgfm_unet* h, float* x_inout, int batch, int num_steps, int step_begin, int step_end,
+                           int solver, void* ws, size_t ws_bytes, rgfm_stream_t stream);
+int rgfm_sample_pair_ode_workspace_bytes(const rgfm_unet* hx, const rgfm_unet* hy, int batch, int n_mc, int solver,
+                                         size_t* bytes);
+int rgfm_sample_pair_ode(rgfm_unet* hx, rgfm_unet* hy, float* x_inout, float* y_inout, const float* mc_x1,
+                         const float* mc_y1, const float* mc_ratios, int n_mc, int batch, int num_steps, double gamma,
+                         int step_begin, int step_end, int solver, void* ws, size_t ws_bytes, rgfm_stream_t stream);
+int rgfm_sample_cond_ode_workspace_bytes(const rgfm_unet* h, int batch, int n_mc, int solver, size_t* bytes);
+int rgfm_sample_cond_ode(rgfm_unet* h, float* s_inout, const float* mc_set, const float* ratios, int n_mc, int batch,
+                         int num_steps, double gamma, int step_begin, int step_end, int solver, void* ws,
+                         size_t ws_bytes, rgfm_stream_t stream);
+int rgfm_sample_pair_grad_ode_workspace_bytes(const rgfm_unet* hx, const rgfm_unet* hy, const rgfm_ratio* hr,
+                                              int batch, int solver, size_t* bytes);
+int rgfm_sample_pair_grad_ode(rgfm_unet* hx, rgfm_unet* hy, rgfm_ratio* hr, float* x_inout, float* y_inout,
+                              int batch, int num_steps, double gamma, int step_begin, int step_end, int solver,
+                              void* ws, size_t ws_bytes, rgfm_stream_t stream);
+int rgfm_sample_cond_grad_ode_workspace_bytes(const rgfm_unet* h_unet, const rgfm_ratio* h_ratio, int given,
+                                              int batch, int solver, size_t* bytes);
+int rgfm_sample_cond_grad_ode(rgfm_unet* h_unet, rgfm_ratio* h_ratio, float* s_inout, const float* ctx, int given,
+                              int batch, int num_steps, double gamma, int step_begin, int step_end, int solver,
+                              void* ws, size_t ws_bytes, rgfm_stream_t stream);
+
 /* ------------------------------------------------------------------ FlowMatchingModel ("--model original")
  * The reference's encoder-decoder velocity net (src/models/flow_matching.py:127-173;
  * built by src/sample.py:152-154 and src/evaluate.py:144-146) for 1x28x28 images:

@@ -925,15 +925,29 @@ class _RatioTrainFn(torch.autograd.Function):
 _sampler_ws = _Workspace()
 
 
-def sample_single(model, x, num_steps, step_begin=0, step_end=None):
-    """In-place unguided Euler integration of `x` (rgfm_sample_single)."""
+def _solver(solver, *models):
+    """RGFM_SOLVER_* of `solver` ('euler' | 'midpoint'; anything else: ValueError before any device work).  The
+    midpoint loops exist for U-Net nets only: a FlowMatchingModel net with 'midpoint' raises RgfmError."""
+    sid = _lib.solver_id(solver)
+    if sid:
+        for m in models:
+            if not isinstance(m._engine, UNetEngine):
+                raise _lib.RgfmError(f"solver={solver!r} needs U-Net velocity nets (FlexibleUNet and its presets); "
+                                     f"{type(m).__name__} has the Euler loop only")
+    return sid
+
+
+def sample_single(model, x, num_steps, step_begin=0, step_end=None, solver='euler'):
+    """In-place unguided integration of `x` (rgfm_sample_single; solver='midpoint': rgfm_sample_single_ode)."""
+    _solver(solver, model)
     if x.is_cuda and x.shape[0]:
-        return _range_guarded(x.device, [x], lambda: _sample_single(model, x, num_steps, step_begin, step_end),
+        return _range_guarded(x.device, [x], lambda: _sample_single(model, x, num_steps, step_begin, step_end, solver),
                               [model._engine])
-    return _sample_single(model, x, num_steps, step_begin, step_end)
+    return _sample_single(model, x, num_steps, step_begin, step_end, solver)
 
 
-def _sample_single(model, x, num_steps, step_begin=0, step_end=None):
+def _sample_single(model, x, num_steps, step_begin=0, step_end=None, solver='euler'):
+    sid = _solver(solver, model)
     eng = model._engine
     eng._check_eval(model)
     _require_hip(x)
@@ -946,6 +960,14 @@ def _sample_single(model, x, num_steps, step_begin=0, step_end=None):
         return x
     with torch.cuda.device(dev):
         h = eng.handle(dev)
+        if sid:
+            L = _lib.lib()
+            n = ctypes.c_size_t()
+            _lib.check(L.rgfm_sample_single_ode_workspace_bytes(h, B, sid, ctypes.byref(n)))
+            ws = eng._ws.get(n.value, dev)
+            _lib.check(L.rgfm_sample_single_ode(h, _ptr(x), B, int(num_steps), int(step_begin), int(step_end), sid,
+                                                _ptr(ws), n.value, _stream(dev)))
+            return x
         ws, nb = eng.workspace(eng.SINGLE_WS, B, dev)
         _lib.check(getattr(_lib.lib(), eng.SINGLE)(h, _ptr(x), B, int(num_steps), int(step_begin),
                                                    int(step_end), _ptr(ws), nb, _stream(dev)))
@@ -955,20 +977,21 @@ def _sample_single(model, x, num_steps, step_begin=0, step_end=None):
 _side_streams = {}
 
 
-def sample_two_streams(fm_x, x, fm_y, y, num_steps):
+def sample_two_streams(fm_x, x, fm_y, y, num_steps, solver='euler'):
     """Two independent unguided integrations (the MC pre-phase) on two HIP streams.
 
     Same arithmetic as two sample_single calls; the second net runs on a side stream that
     forks from / joins back into the current stream, so callers keep stream-ordered semantics.
     """
     dev = x.device
+    _solver(solver, fm_x, fm_y)
 
     def run():
         # one module passed for both modalities (legal in the reference) has ONE engine workspace:
         # its two integrations must not run concurrently
         if os.environ.get("RGFM_OVERLAP", "1") == "0" or fm_x._engine is fm_y._engine:
-            _sample_single(fm_x, x, num_steps)
-            _sample_single(fm_y, y, num_steps)
+            _sample_single(fm_x, x, num_steps, solver=solver)
+            _sample_single(fm_y, y, num_steps, solver=solver)
             return x, y
         cur = torch.cuda.current_stream(dev)
         side = _side_streams.get(dev)
@@ -976,8 +999,8 @@ def sample_two_streams(fm_x, x, fm_y, y, num_steps):
             side = _side_streams[dev] = torch.cuda.Stream(dev)
         side.wait_stream(cur)
         with torch.cuda.stream(side):
-            _sample_single(fm_y, y, num_steps)
-        _sample_single(fm_x, x, num_steps)
+            _sample_single(fm_y, y, num_steps, solver=solver)
+        _sample_single(fm_x, x, num_steps, solver=solver)
         cur.wait_stream(side)
         return x, y
     if x.is_cuda and y.is_cuda:
@@ -986,8 +1009,9 @@ def sample_two_streams(fm_x, x, fm_y, y, num_steps):
 
 
 def sample_pair(fm_x, fm_y, x, y, mc_x1, mc_y1, mc_ratios, num_steps, gamma, step_begin=0,
-                step_end=None):
-    """In-place paired Euler loop with optional MC guidance (rgfm_sample_pair)."""
+                step_end=None, solver='euler'):
+    """In-place paired loop with optional MC guidance (rgfm_sample_pair; solver='midpoint': rgfm_sample_pair_ode)."""
+    sid = _solver(solver, fm_x, fm_y)
     for m in (fm_x, fm_y):
         m._engine._check_eval(m)
     ex = fm_x._engine
@@ -1011,6 +1035,14 @@ def sample_pair(fm_x, fm_y, x, y, mc_x1, mc_y1, mc_ratios, num_steps, gamma, ste
         with torch.cuda.device(dev):
             hx, hy = fm_x._engine.handle(dev), fm_y._engine.handle(dev)
             nb = ctypes.c_size_t()
+            if sid:
+                _lib.check(L.rgfm_sample_pair_ode_workspace_bytes(hx, hy, B, n_mc, sid, ctypes.byref(nb)))
+                ws = _sampler_ws.get(nb.value, dev)
+                _lib.check(L.rgfm_sample_pair_ode(hx, hy, _ptr(x), _ptr(y), _ptr(mc_x1 if n_mc else None),
+                                                  _ptr(mc_y1 if n_mc else None), _ptr(mc_ratios if n_mc else None), n_mc,
+                                                  B, int(num_steps), float(gamma), int(step_begin), int(step_end), sid,
+                                                  _ptr(ws), nb.value, _stream(dev)))
+                return x, y
             _lib.check(getattr(L, ex.PAIR_WS)(hx, hy, B, n_mc, ctypes.byref(nb)))
             ws = _sampler_ws.get(nb.value, dev)
             _lib.check(getattr(L, ex.PAIR)(hx, hy, _ptr(x), _ptr(y), _ptr(mc_x1 if n_mc else None),
@@ -1022,8 +1054,10 @@ def sample_pair(fm_x, fm_y, x, y, mc_x1, mc_y1, mc_ratios, num_steps, gamma, ste
     return _range_guarded(dev, [x, y], run, [fm_x._engine, fm_y._engine])
 
 
-def sample_pair_grad(fm_x, fm_y, ratio_estimator, x, y, num_steps, gamma, step_begin=0, step_end=None):
-    """In-place paired Euler loop with gradient log-ratio guidance (rgfm_sample_pair_grad)."""
+def sample_pair_grad(fm_x, fm_y, ratio_estimator, x, y, num_steps, gamma, step_begin=0, step_end=None, solver='euler'):
+    """In-place paired loop with gradient log-ratio guidance (rgfm_sample_pair_grad; solver='midpoint':
+    rgfm_sample_pair_grad_ode)."""
+    sid = _lib.solver_id(solver)
     for m in (fm_x, fm_y, ratio_estimator):
         m._engine._check_eval(m)
     if not (isinstance(fm_x._engine, UNetEngine) and isinstance(fm_y._engine, UNetEngine)):
@@ -1043,6 +1077,12 @@ def sample_pair_grad(fm_x, fm_y, ratio_estimator, x, y, num_steps, gamma, step_b
         with torch.cuda.device(dev):
             hx, hy, hr = fm_x._engine.handle(dev), fm_y._engine.handle(dev), ratio_estimator._engine.handle(dev)
             nb = ctypes.c_size_t()
+            if sid:
+                _lib.check(L.rgfm_sample_pair_grad_ode_workspace_bytes(hx, hy, hr, B, sid, ctypes.byref(nb)))
+                ws = _sampler_ws.get(nb.value, dev)
+                _lib.check(L.rgfm_sample_pair_grad_ode(hx, hy, hr, _ptr(x), _ptr(y), B, int(num_steps), float(gamma),
+                                                       int(step_begin), int(step_end), sid, _ptr(ws), nb.value, _stream(dev)))
+                return x, y
             _lib.check(L.rgfm_sample_pair_grad_workspace_bytes(hx, hy, hr, B, ctypes.byref(nb)))
             ws = _sampler_ws.get(nb.value, dev)
             _lib.check(L.rgfm_sample_pair_grad(hx, hy, hr, _ptr(x), _ptr(y), B, int(num_steps), float(gamma),
@@ -1069,9 +1109,10 @@ def guidance_apply(x, y, vx, vy, mc_x1, mc_y1, mc_ratios, t, gamma, want_weights
     return w
 
 
-def sample_cond(model, s, mc_set, ratios, num_steps, gamma, step_begin=0, step_end=None):
-    """In-place Euler loop of one U-Net with one-sided MC guidance (rgfm_sample_cond): s [B, C, H, W], mc_set
-    [N, C, H, W], ratios [B, N]."""
+def sample_cond(model, s, mc_set, ratios, num_steps, gamma, step_begin=0, step_end=None, solver='euler'):
+    """In-place loop of one U-Net with one-sided MC guidance (rgfm_sample_cond; solver='midpoint':
+    rgfm_sample_cond_ode): s [B, C, H, W], mc_set [N, C, H, W], ratios [B, N]."""
+    sid = _lib.solver_id(solver)
     eng = model._engine
     eng._check_eval(model)
     if not isinstance(eng, UNetEngine):
@@ -1096,6 +1137,12 @@ def sample_cond(model, s, mc_set, ratios, num_steps, gamma, step_begin=0, step_e
         with torch.cuda.device(dev):
             h = eng.handle(dev)
             nb = ctypes.c_size_t()
+            if sid:
+                _lib.check(L.rgfm_sample_cond_ode_workspace_bytes(h, B, N, sid, ctypes.byref(nb)))
+                ws = _sampler_ws.get(nb.value, dev)
+                _lib.check(L.rgfm_sample_cond_ode(h, _ptr(s), _ptr(mc_set), _ptr(ratios), N, B, int(num_steps), float(gamma),
+                                                  int(step_begin), int(step_end), sid, _ptr(ws), nb.value, _stream(dev)))
+                return s
             _lib.check(L.rgfm_sample_cond_workspace_bytes(h, B, N, ctypes.byref(nb)))
             ws = _sampler_ws.get(nb.value, dev)
             _lib.check(L.rgfm_sample_cond(h, _ptr(s), _ptr(mc_set), _ptr(ratios), N, B, int(num_steps), float(gamma),
@@ -1104,9 +1151,11 @@ def sample_cond(model, s, mc_set, ratios, num_steps, gamma, step_begin=0, step_e
     return _range_guarded(dev, [s], run, [eng])
 
 
-def sample_cond_grad(model, ratio_estimator, s, ctx, given, num_steps, gamma, step_begin=0, step_end=None):
-    """In-place Euler loop of one U-Net with one-sided gradient log-ratio guidance (rgfm_sample_cond_grad): s [B, C, H, W],
-    ctx [B, hidden_dim] from ratio_estimator._engine.cond_prepare(condition, given)."""
+def sample_cond_grad(model, ratio_estimator, s, ctx, given, num_steps, gamma, step_begin=0, step_end=None, solver='euler'):
+    """In-place loop of one U-Net with one-sided gradient log-ratio guidance (rgfm_sample_cond_grad; solver='midpoint':
+    rgfm_sample_cond_grad_ode): s [B, C, H, W], ctx [B, hidden_dim] from ratio_estimator._engine.cond_prepare(condition,
+    given)."""
+    sid = _lib.solver_id(solver)
     eng, re = model._engine, ratio_estimator._engine
     eng._check_eval(model)
     re._check_eval(ratio_estimator)
@@ -1135,6 +1184,12 @@ def sample_cond_grad(model, ratio_estimator, s, ctx, given, num_steps, gamma, st
         with torch.cuda.device(dev):
             h, hr = eng.handle(dev), re.handle(dev)
             nb = ctypes.c_size_t()
+            if sid:
+                _lib.check(L.rgfm_sample_cond_grad_ode_workspace_bytes(h, hr, gi, B, sid, ctypes.byref(nb)))
+                ws = _sampler_ws.get(nb.value, dev)
+                _lib.check(L.rgfm_sample_cond_grad_ode(h, hr, _ptr(s), _ptr(ctx), gi, B, int(num_steps), float(gamma),
+                                                       int(step_begin), int(step_end), sid, _ptr(ws), nb.value, _stream(dev)))
+                return s
             _lib.check(L.rgfm_sample_cond_grad_workspace_bytes(h, hr, gi, B, ctypes.byref(nb)))
             ws = _sampler_ws.get(nb.value, dev)
             _lib.check(L.rgfm_sample_cond_grad(h, hr, _ptr(s), _ptr(ctx), gi, B, int(num_steps), float(gamma),

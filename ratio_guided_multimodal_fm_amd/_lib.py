@@ -104,6 +104,22 @@ SIGNATURES = {
     "rgfm_sample_pair": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
                                  c_void_p, c_int, c_int, c_int, c_double, c_int, c_int, c_void_p,
                                  c_size_t, c_void_p]),
+    # the sampler loops with a choice of solver (SOLVER_*): the Euler signatures with `solver` in front of ws / bytes
+    "rgfm_sample_single_ode_workspace_bytes": (c_int, [c_void_p, c_int, c_int, P(c_size_t)]),
+    "rgfm_sample_single_ode": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int, c_void_p, c_size_t,
+                                       c_void_p]),
+    "rgfm_sample_pair_ode_workspace_bytes": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, P(c_size_t)]),
+    "rgfm_sample_pair_ode": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int,
+                                     c_int, c_double, c_int, c_int, c_int, c_void_p, c_size_t, c_void_p]),
+    "rgfm_sample_cond_ode_workspace_bytes": (c_int, [c_void_p, c_int, c_int, c_int, P(c_size_t)]),
+    "rgfm_sample_cond_ode": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_double, c_int, c_int,
+                                     c_int, c_void_p, c_size_t, c_void_p]),
+    "rgfm_sample_pair_grad_ode_workspace_bytes": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_int, P(c_size_t)]),
+    "rgfm_sample_pair_grad_ode": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_double,
+                                          c_int, c_int, c_int, c_void_p, c_size_t, c_void_p]),
+    "rgfm_sample_cond_grad_ode_workspace_bytes": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, P(c_size_t)]),
+    "rgfm_sample_cond_grad_ode": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_double, c_int,
+                                          c_int, c_int, c_void_p, c_size_t, c_void_p]),
     "rgfm_fmnet_param_floats": (c_int, [P(FmNetDesc), P(c_size_t)]),
     "rgfm_fmnet_create": (c_int, [P(FmNetDesc), c_void_p, c_size_t, c_void_p, P(c_void_p)]),
     "rgfm_fmnet_destroy": (None, [c_void_p]),
@@ -138,6 +154,17 @@ SIGNATURES = {
     "rgfm_abi_version": (c_int, []),
     "rgfm_last_error": (ctypes.c_char_p, []),
 }
+
+
+# RGFM_SOLVER_* of include/rgfm.h by the name the Python samplers and the CLIs take
+SOLVERS = {"euler": 0, "midpoint": 1}
+
+
+def solver_id(solver):
+    """RGFM_SOLVER_* of a solver name; any other value is a ValueError (raised before any device work)."""
+    if not isinstance(solver, str) or solver not in SOLVERS:
+        raise ValueError(f"solver must be 'euler' or 'midpoint', got {solver!r}")
+    return SOLVERS[solver]
 
 
 # RGFM_ROUTE_* of include/rgfm.h, in index order (rgfm_unet_conv_routes); slot ROUTE_T2 counts the CONV_T2 launches

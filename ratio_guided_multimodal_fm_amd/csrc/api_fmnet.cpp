@@ -367,17 +367,18 @@ extern "C" int rgfm_fmnet_sample_pair(rgfm_fmnet* hx, rgfm_fmnet* hy, float* x_i
   HIP_TRY(hipMemsetAsync(cnt_y, 0, (size_t)batch * sizeof(unsigned), s));
   const size_t mark_x = b.off;
   const size_t mark_y = mark_x + fm_eval_bytes(hx, batch);
-  auto eval_x = [&](int i, hipStream_t st, float* v_out, float* x_state, float dt, const int*) {
+  // (Euler only: the state a stage reads, writes and starts from is the one buffer)
+  auto eval_x = [&](int i, hipStream_t st, const float* in, float* v_out, float* x_state, const float*, float dt, const int*) {
     b.off = mark_x;
     FmRun r{hx, batch, &b, st, false, nullptr, 1, num_steps, step_begin + i};
     r.fin_counter = cnt_x;
-    return r.run(x_inout, v_out, x_state, dt);
+    return r.run(in, v_out, x_state, dt);
   };
-  auto eval_y = [&](int i, hipStream_t st, float* v_out, float* y_state, float dt, const int*) {
+  auto eval_y = [&](int i, hipStream_t st, const float* in, float* v_out, float* y_state, const float*, float dt, const int*) {
     b.off = mark_y;
     FmRun r{hy, batch, &b, st, false, nullptr, 1, num_steps, step_begin + i};
     r.fin_counter = cnt_y;
-    return r.run(y_inout, v_out, y_state, dt);
+    return r.run(in, v_out, y_state, dt);
   };
   return pair_loop(eval_x, eval_y, x_inout, y_inout, mc_x1, mc_y1, mc_ratios, n_mc, batch, num_steps, gamma, step_begin,
                    ns, d, d, vx, vy, logp, s);

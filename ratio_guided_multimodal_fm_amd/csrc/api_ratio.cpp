@@ -829,10 +829,17 @@ static int check_grad_pair(const rgfm_unet* hx, const rgfm_unet* hy, const rgfm_
   return RGFM_OK;
 }
 
-// Paired Euler loop with gradient log-ratio guidance (reference README.md:159-164: v_guided = v_ind + gamma *
-// grad log r(x_t, y_t); the reference ships no code for it): x <- x + (v_x + gamma dlogr/dx) dt, every step.
-extern "C" int rgfm_sample_pair_grad_workspace_bytes(const rgfm_unet* hx, const rgfm_unet* hy, const rgfm_ratio* hr, int batch,
-                                                     size_t* bytes) {
+// Paired loop with gradient log-ratio guidance (reference README.md:159-164: v_guided = v_ind + gamma *
+// grad log r(x_t, y_t); the reference ships no code for it): x <- x + (v_x + gamma dlogr/dx) dt, every Euler step.
+// Midpoint: both modalities advance stage by stage -- (x_mid, y_mid) = (x, y) + (dt / 2) F(x, y, t1), then
+// (x, y) += dt F(x_mid, y_mid, t1 + dt / 2), the gradient taken at the stage's state.
+namespace {
+
+int solver_id_ok(int solver) {
+  return solver == SOLVER_EULER || solver == SOLVER_MIDPOINT ? RGFM_OK : fail(RGFM_EINVAL, "unknown solver %d (RGFM_SOLVER_EULER, RGFM_SOLVER_MIDPOINT)", solver);
+}
+
+int pair_grad_bytes(const rgfm_unet* hx, const rgfm_unet* hy, const rgfm_ratio* hr, int batch, int solver, size_t* bytes) {
   if (!hx || !hy || !hr || !bytes || batch < 1) return fail(RGFM_EINVAL, "bad argument");
   size_t base = 0, rg = 0;
   int rc = hr->d.kind == RGFM_RATIO_FLEXIBLE ? check_grad_pair(hx, hy, hr) : RGFM_OK;  // (the fixed kinds: checked by the sampler call)
@@ -841,22 +848,23 @@ extern "C" int rgfm_sample_pair_grad_workspace_bytes(const rgfm_unet* hx, const 
   if ((rc = rgfm_ratio_grad_workspace_bytes(hr, batch, &rg))) return rc;
   const size_t dx = (size_t)hx->d.in_channels * hx->d.img_size * hx->d.img_size;
   const size_t dy = (size_t)hy->d.in_channels * hy->d.img_size * hy->d.img_size;
-  *bytes = base + rg + ((batch * dx * 4 + 255) & ~(size_t)255) + ((batch * dy * 4 + 255) & ~(size_t)255);
+  *bytes = base + rg + ((batch * dx * 4 + 255) & ~(size_t)255) + ((batch * dy * 4 + 255) & ~(size_t)255) +
+           (solver == SOLVER_MIDPOINT ? state_bytes(batch, dx) + state_bytes(batch, dy) : 0);
   return RGFM_OK;
 }
 
-extern "C" int rgfm_sample_pair_grad(rgfm_unet* hx, rgfm_unet* hy, rgfm_ratio* hr, float* x_inout, float* y_inout, int batch,
-                                     int num_steps, double gamma, int step_begin, int step_end, void* ws, size_t ws_bytes,
-                                     rgfm_stream_t stream) {
+int pair_grad_loop(rgfm_unet* hx, rgfm_unet* hy, rgfm_ratio* hr, float* x_inout, float* y_inout, int batch, int num_steps,
+                   double gamma, int step_begin, int step_end, int solver, void* ws, size_t ws_bytes, rgfm_stream_t stream) {
   refresh_modes();
+  if (int rc = solver_id_ok(solver)) return rc;
   if (!hx || !hy || !hr || !x_inout || !y_inout || !ws) return fail(RGFM_EINVAL, "null argument");
   if (int rc = check_grad_pair(hx, hy, hr)) return rc;
   if (batch < 1 || num_steps < 1 || step_begin < 0 || step_end > num_steps || step_begin > step_end)
     return fail(RGFM_EINVAL, "bad step range [%d,%d) of %d", step_begin, step_end, num_steps);
   const int ns = step_end - step_begin;
-  if (ns > 4096) return fail(RGFM_EINVAL, "at most 4096 steps per call");
+  if (int rc = check_solver(solver, ns, num_steps)) return rc;
   size_t need = 0;
-  int rc = rgfm_sample_pair_grad_workspace_bytes(hx, hy, hr, batch, &need);
+  int rc = pair_grad_bytes(hx, hy, hr, batch, solver, &need);
   if (rc) return rc;
   if (need > ws_bytes) return fail(RGFM_ENOMEM, "workspace too small: %zu < %zu", ws_bytes, need);
   if (ns == 0) return RGFM_OK;
@@ -874,16 +882,20 @@ extern "C" int rgfm_sample_pair_grad(rgfm_unet* hx, rgfm_unet* hy, rgfm_ratio* h
   float* gy = b.f((size_t)batch * dy);
   unsigned* cnt_x = reinterpret_cast<unsigned*>(b.f(batch));
   unsigned* cnt_y = reinterpret_cast<unsigned*>(b.f(batch));
+  float* x_mid = solver == SOLVER_MIDPOINT ? b.f((size_t)batch * dx) : nullptr;
+  float* y_mid = solver == SOLVER_MIDPOINT ? b.f((size_t)batch * dy) : nullptr;
   HIP_TRY(hipMemsetAsync(cnt_x, 0, (size_t)batch * sizeof(unsigned), s));
   HIP_TRY(hipMemsetAsync(cnt_y, 0, (size_t)batch * sizeof(unsigned), s));
-  launch_time_table(hx, nullptr, num_steps, step_begin, ns, tx, s);
-  launch_time_table(hy, nullptr, num_steps, step_begin, ns, ty, s);
+  launch_stage_table(hx, solver, num_steps, step_begin, ns, tx, s);
+  launch_stage_table(hy, solver, num_steps, step_begin, ns, ty, s);
   const size_t mark_x = b.off;
   const size_t mark_y = mark_x + unet_eval_bytes(hx, batch);
   const size_t mark_r = mark_y + unet_eval_bytes(hy, batch);
-  const float dt = (float)(1.0 / (double)num_steps), gf = (float)gamma;
+  const double dtd = 1.0 / (double)num_steps;
+  const float dt = (float)dtd, dth = (float)(0.5 * dtd), gf = (float)gamma;
   const bool overlap = g_modes.overlap;
-  for (int i = 0; i < ns; ++i) {
+  // one stage: (xout, yout) = (xb, yb) + (v(in, row's t) + gamma grad log r(xin, yin)) dts; xb / yb null: in place
+  auto stage = [&](int row, float* xin, float* yin, float* xout, float* yout, const float* xb, const float* yb, float dts) -> int {
     hipStream_t sy = overlap ? ds->side : s;
     if (overlap) {
       HIP_TRY(hipEventRecord(ds->fork, s));
@@ -891,30 +903,63 @@ extern "C" int rgfm_sample_pair_grad(rgfm_unet* hx, rgfm_unet* hy, rgfm_ratio* h
     }
     {
       b.off = mark_y;
-      UNetRun r{hy, batch, &b, sy, ty + (size_t)i * hy->temb_total, 0, false};
+      UNetRun r{hy, batch, &b, sy, ty + (size_t)row * hy->temb_total, 0, false};
       r.fin_counter = cnt_y;
-      if ((rc = r.run(y_inout, vy, nullptr, 0.f))) return rc;
+      if (int rc = r.run(yin, vy, nullptr, 0.f)) return rc;
     }
     if (overlap) HIP_TRY(hipEventRecord(ds->join, ds->side));
     {
       b.off = mark_x;
-      UNetRun r{hx, batch, &b, s, tx + (size_t)i * hx->temb_total, 0, false};
+      UNetRun r{hx, batch, &b, s, tx + (size_t)row * hx->temb_total, 0, false};
       r.fin_counter = cnt_x;
-      if ((rc = r.run(x_inout, vx, nullptr, 0.f))) return rc;
+      if (int rc = r.run(xin, vx, nullptr, 0.f)) return rc;
     }
     {
       b.off = mark_r;
       RatioGradRun r{hr, batch, &b, s, false};
       r.flag = hx->range_flag;
       ModeScope ratio_mode(hx->conv_mode);  // (the estimator's forward convs follow the x net's handle)
-      r.run(x_inout, y_inout, gx, gy, nullptr);
+      r.run(xin, yin, gx, gy, nullptr);
     }
     if (overlap) HIP_TRY(hipStreamWaitEvent(s, ds->join, 0));
-    launch_euler_grad(x_inout, vx, gx, (size_t)batch * dx, gf, dt, s);
-    launch_euler_grad(y_inout, vy, gy, (size_t)batch * dy, gf, dt, s);
+    launch_euler_grad(xout, vx, gx, (size_t)batch * dx, gf, dts, s, xb);
+    launch_euler_grad(yout, vy, gy, (size_t)batch * dy, gf, dts, s, yb);
+    return RGFM_OK;
+  };
+  for (int i = 0; i < ns; ++i) {
+    if (solver == SOLVER_MIDPOINT) {
+      if ((rc = stage(2 * i, x_inout, y_inout, x_mid, y_mid, x_inout, y_inout, dth))) return rc;
+      rc = stage(2 * i + 1, x_mid, y_mid, x_inout, y_inout, nullptr, nullptr, dt);
+    } else {
+      rc = stage(i, x_inout, y_inout, x_inout, y_inout, nullptr, nullptr, dt);
+    }
+    if (rc) return rc;
   }
   HIP_TRY(hipGetLastError());
   return RGFM_OK;
+}
+
+}  // namespace
+
+extern "C" int rgfm_sample_pair_grad_workspace_bytes(const rgfm_unet* hx, const rgfm_unet* hy, const rgfm_ratio* hr, int batch,
+                                                     size_t* bytes) {
+  return pair_grad_bytes(hx, hy, hr, batch, SOLVER_EULER, bytes);
+}
+extern "C" int rgfm_sample_pair_grad_ode_workspace_bytes(const rgfm_unet* hx, const rgfm_unet* hy, const rgfm_ratio* hr,
+                                                         int batch, int solver, size_t* bytes) {
+  if (int rc = solver_id_ok(solver)) return rc;
+  return pair_grad_bytes(hx, hy, hr, batch, solver, bytes);
+}
+extern "C" int rgfm_sample_pair_grad(rgfm_unet* hx, rgfm_unet* hy, rgfm_ratio* hr, float* x_inout, float* y_inout, int batch,
+                                     int num_steps, double gamma, int step_begin, int step_end, void* ws, size_t ws_bytes,
+                                     rgfm_stream_t stream) {
+  return pair_grad_loop(hx, hy, hr, x_inout, y_inout, batch, num_steps, gamma, step_begin, step_end, SOLVER_EULER, ws, ws_bytes,
+                        stream);
+}
+extern "C" int rgfm_sample_pair_grad_ode(rgfm_unet* hx, rgfm_unet* hy, rgfm_ratio* hr, float* x_inout, float* y_inout,
+                                         int batch, int num_steps, double gamma, int step_begin, int step_end, int solver,
+                                         void* ws, size_t ws_bytes, rgfm_stream_t stream) {
+  return pair_grad_loop(hx, hy, hr, x_inout, y_inout, batch, num_steps, gamma, step_begin, step_end, solver, ws, ws_bytes, stream);
 }
 
 // ------------------------------------------------------------------ one-sided gradient: conditional sampling
@@ -990,31 +1035,35 @@ extern "C" int rgfm_ratio_grad_log_ratio_cond(rgfm_ratio* h, const float* ctx, i
   return RGFM_OK;
 }
 
-// One net with gradient log-ratio guidance, the other side observed: s <- s + (v(s, t) + gamma dlogr/ds) dt, every step.
+// One net with gradient log-ratio guidance, the other side observed: s <- s + (v(s, t) + gamma dlogr/ds) dt, every step
+// (midpoint: s_mid = s + (dt / 2) F(s, t1), s += dt F(s_mid, t1 + dt / 2)).
 // The velocity net and the estimator's one-sided pass run one after the other on `stream` and share one scratch region.
-extern "C" int rgfm_sample_cond_grad_workspace_bytes(const rgfm_unet* h, const rgfm_ratio* hr, int given, int batch, size_t* bytes) {
+namespace {
+
+int cond_grad_bytes(const rgfm_unet* h, const rgfm_ratio* hr, int given, int batch, int solver, size_t* bytes) {
   if (!h || !hr || !bytes || batch < 1) return fail(RGFM_EINVAL, "bad argument");
   int rc = check_given(given);
   if (rc || (rc = check_grad_side(h, hr, given))) return rc;
   const size_t d = (size_t)h->d.in_channels * h->d.img_size * h->d.img_size;
   *bytes = table_bytes(h, 4096) + counter_bytes(batch) + 2 * ((batch * d * 4 + 255) & ~(size_t)255) +
-           std::max(unet_eval_bytes(const_cast<rgfm_unet*>(h), batch), ratio_cond_grad_bytes(const_cast<rgfm_ratio*>(hr), given, batch));
+           std::max(unet_eval_bytes(const_cast<rgfm_unet*>(h), batch), ratio_cond_grad_bytes(const_cast<rgfm_ratio*>(hr), given, batch)) +
+           (solver == SOLVER_MIDPOINT ? state_bytes(batch, d) : 0);
   return RGFM_OK;
 }
 
-extern "C" int rgfm_sample_cond_grad(rgfm_unet* h, rgfm_ratio* hr, float* s_inout, const float* ctx, int given, int batch,
-                                     int num_steps, double gamma, int step_begin, int step_end, void* ws, size_t ws_bytes,
-                                     rgfm_stream_t stream) {
+int cond_grad_loop(rgfm_unet* h, rgfm_ratio* hr, float* s_inout, const float* ctx, int given, int batch, int num_steps,
+                   double gamma, int step_begin, int step_end, int solver, void* ws, size_t ws_bytes, rgfm_stream_t stream) {
   refresh_modes();
+  if (int rc = solver_id_ok(solver)) return rc;
   if (!h || !hr || !s_inout || !ctx || !ws) return fail(RGFM_EINVAL, "null argument");
   int rc = check_given(given);
   if (rc || (rc = check_grad_side(h, hr, given))) return rc;
   if (batch < 1 || num_steps < 1 || step_begin < 0 || step_end > num_steps || step_begin > step_end)
     return fail(RGFM_EINVAL, "bad step range [%d,%d) of %d", step_begin, step_end, num_steps);
   const int ns = step_end - step_begin;
-  if (ns > 4096) return fail(RGFM_EINVAL, "at most 4096 steps per call");
+  if ((rc = check_solver(solver, ns, num_steps))) return rc;
   size_t need = 0;
-  if ((rc = rgfm_sample_cond_grad_workspace_bytes(h, hr, given, batch, &need))) return rc;
+  if ((rc = cond_grad_bytes(h, hr, given, batch, solver, &need))) return rc;
   if (need > ws_bytes) return fail(RGFM_ENOMEM, "workspace too small: %zu < %zu", ws_bytes, need);
   if (ns == 0) return RGFM_OK;
   hipStream_t s = (hipStream_t)stream;
@@ -1025,26 +1074,60 @@ extern "C" int rgfm_sample_cond_grad(rgfm_unet* h, rgfm_ratio* hr, float* s_inou
   unsigned* cnt = reinterpret_cast<unsigned*>(b.f(batch));
   float* v = b.f((size_t)batch * d);
   float* g = b.f((size_t)batch * d);
+  float* mid = solver == SOLVER_MIDPOINT ? b.f((size_t)batch * d) : nullptr;
   HIP_TRY(hipMemsetAsync(cnt, 0, (size_t)batch * sizeof(unsigned), s));
-  launch_time_table(h, nullptr, num_steps, step_begin, ns, table, s);
+  launch_stage_table(h, solver, num_steps, step_begin, ns, table, s);
   const size_t mark = b.off;
-  const float dt = (float)(1.0 / (double)num_steps), gf = (float)gamma;
-  for (int i = 0; i < ns; ++i) {
+  const double dtd = 1.0 / (double)num_steps;
+  const float dt = (float)dtd, dth = (float)(0.5 * dtd), gf = (float)gamma;
+  // one stage: out = base + (v(in, row's t) + gamma grad log r(in)) dts; base null: in place on out
+  auto stage = [&](int row, float* in, float* out, const float* base, float dts) -> int {
     {
       b.off = mark;
-      UNetRun r{h, batch, &b, s, table + (size_t)i * h->temb_total, 0, false};
+      UNetRun r{h, batch, &b, s, table + (size_t)row * h->temb_total, 0, false};
       r.fin_counter = cnt;
-      if ((rc = r.run(s_inout, v, nullptr, 0.f))) return rc;
+      if (int rc = r.run(in, v, nullptr, 0.f)) return rc;
     }
     {
       b.off = mark;
       RatioGradRun r{hr, batch, &b, s, false};
       r.flag = h->range_flag;
       ModeScope ratio_mode(h->conv_mode);  // (the estimator's convs follow the target net's handle)
-      r.run_cond(ctx, given, s_inout, g, nullptr);
+      r.run_cond(ctx, given, in, g, nullptr);
     }
-    launch_euler_grad(s_inout, v, g, (size_t)batch * d, gf, dt, s);
+    launch_euler_grad(out, v, g, (size_t)batch * d, gf, dts, s, base);
+    return RGFM_OK;
+  };
+  for (int i = 0; i < ns; ++i) {
+    if (solver == SOLVER_MIDPOINT) {
+      if ((rc = stage(2 * i, s_inout, mid, s_inout, dth))) return rc;
+      rc = stage(2 * i + 1, mid, s_inout, nullptr, dt);
+    } else {
+      rc = stage(i, s_inout, s_inout, nullptr, dt);
+    }
+    if (rc) return rc;
   }
   HIP_TRY(hipGetLastError());
   return RGFM_OK;
+}
+
+}  // namespace
+
+extern "C" int rgfm_sample_cond_grad_workspace_bytes(const rgfm_unet* h, const rgfm_ratio* hr, int given, int batch, size_t* bytes) {
+  return cond_grad_bytes(h, hr, given, batch, SOLVER_EULER, bytes);
+}
+extern "C" int rgfm_sample_cond_grad_ode_workspace_bytes(const rgfm_unet* h, const rgfm_ratio* hr, int given, int batch, int solver,
+                                                         size_t* bytes) {
+  if (int rc = solver_id_ok(solver)) return rc;
+  return cond_grad_bytes(h, hr, given, batch, solver, bytes);
+}
+extern "C" int rgfm_sample_cond_grad(rgfm_unet* h, rgfm_ratio* hr, float* s_inout, const float* ctx, int given, int batch,
+                                     int num_steps, double gamma, int step_begin, int step_end, void* ws, size_t ws_bytes,
+                                     rgfm_stream_t stream) {
+  return cond_grad_loop(h, hr, s_inout, ctx, given, batch, num_steps, gamma, step_begin, step_end, SOLVER_EULER, ws, ws_bytes, stream);
+}
+extern "C" int rgfm_sample_cond_grad_ode(rgfm_unet* h, rgfm_ratio* hr, float* s_inout, const float* ctx, int given, int batch,
+                                         int num_steps, double gamma, int step_begin, int step_end, int solver, void* ws,
+                                         size_t ws_bytes, rgfm_stream_t stream) {
+  return cond_grad_loop(h, hr, s_inout, ctx, given, batch, num_steps, gamma, step_begin, step_end, solver, ws, ws_bytes, stream);
 }

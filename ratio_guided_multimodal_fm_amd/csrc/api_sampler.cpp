@@ -1,24 +1,40 @@
-// api_sampler.cpp -- the Euler samplers over U-Net handles and the stand-alone guidance block (C ABI: include/rgfm.h).
+// api_sampler.cpp -- the Euler / midpoint samplers over U-Net handles and the stand-alone guidance block (C ABI: include/rgfm.h).
 #include "rgfm_host.h"
 
 // ================================================================== samplers
-extern "C" int rgfm_sample_single_workspace_bytes(const rgfm_unet* h, int batch, size_t* bytes) {
+// Every loop below is shared by its Euler entry point (the `solver` = RGFM_SOLVER_EULER case: the launches, arguments and
+// workspace layout of before) and its *_ode twin.  Midpoint: a mid-state buffer per modality behind the Euler layout's
+// fixed part, two time-table rows per step (launch_stage_table), two stages per step.
+namespace {
+
+int check_range(int batch, int num_steps, int step_begin, int step_end) {
+  if (batch < 1 || num_steps < 1 || step_begin < 0 || step_end > num_steps || step_begin > step_end)
+    return fail(RGFM_EINVAL, "bad step range [%d,%d) of %d", step_begin, step_end, num_steps);
+  return RGFM_OK;
+}
+int check_solver_id(int solver) {
+  return solver == SOLVER_EULER || solver == SOLVER_MIDPOINT ? RGFM_OK : fail(RGFM_EINVAL, "unknown solver %d (RGFM_SOLVER_EULER, RGFM_SOLVER_MIDPOINT)", solver);
+}
+size_t image_floats(const rgfm_unet* h) { return (size_t)h->d.in_channels * h->d.img_size * h->d.img_size; }
+
+int single_bytes(const rgfm_unet* h, int batch, int solver, size_t* bytes) {
   if (!h || !bytes || batch < 1) return fail(RGFM_EINVAL, "bad argument");
-  // the time table is sized for up to 4096 steps per call
-  *bytes = unet_eval_bytes(const_cast<rgfm_unet*>(h), batch) + table_bytes(h, 4096) + counter_bytes(batch);
+  // the time table is sized for up to 4096 rows per call
+  *bytes = unet_eval_bytes(const_cast<rgfm_unet*>(h), batch) + table_bytes(h, 4096) + counter_bytes(batch) +
+           (solver == SOLVER_MIDPOINT ? state_bytes(batch, image_floats(h)) : 0);
   return RGFM_OK;
 }
 
-extern "C" int rgfm_sample_single(rgfm_unet* h, float* x_inout, int batch, int num_steps, int step_begin,
-                                  int step_end, void* ws, size_t ws_bytes, rgfm_stream_t stream) {
+int single_loop(rgfm_unet* h, float* x_inout, int batch, int num_steps, int step_begin, int step_end, int solver, void* ws,
+                size_t ws_bytes, rgfm_stream_t stream) {
   refresh_modes();
+  if (int rc = check_solver_id(solver)) return rc;
   if (!h || !x_inout || !ws) return fail(RGFM_EINVAL, "null argument");
-  if (batch < 1 || num_steps < 1 || step_begin < 0 || step_end > num_steps || step_begin > step_end)
-    return fail(RGFM_EINVAL, "bad step range [%d,%d) of %d", step_begin, step_end, num_steps);
+  if (int rc = check_range(batch, num_steps, step_begin, step_end)) return rc;
   const int ns = step_end - step_begin;
-  if (ns > 4096) return fail(RGFM_EINVAL, "at most 4096 steps per call");
+  if (int rc = check_solver(solver, ns, num_steps)) return rc;
   size_t need = 0;
-  rgfm_sample_single_workspace_bytes(h, batch, &need);
+  single_bytes(h, batch, solver, &need);
   if (need > ws_bytes) return fail(RGFM_ENOMEM, "workspace too small: %zu < %zu", ws_bytes, need);
   if (ns == 0) return RGFM_OK;
   hipStream_t s = (hipStream_t)stream;
@@ -26,19 +42,49 @@ extern "C" int rgfm_sample_single(rgfm_unet* h, float* x_inout, int batch, int n
   b.base = (char*)ws, b.cap = ws_bytes, b.dry = false;
   float* table = b.f((size_t)4096 * h->temb_total);
   unsigned* cnt = reinterpret_cast<unsigned*>(b.f(batch));
+  float* mid = solver == SOLVER_MIDPOINT ? b.f((size_t)batch * image_floats(h)) : nullptr;
   HIP_TRY(hipMemsetAsync(cnt, 0, (size_t)batch * sizeof(unsigned), s));
-  launch_time_table(h, nullptr, num_steps, step_begin, ns, table, s);
+  launch_stage_table(h, solver, num_steps, step_begin, ns, table, s);
   const size_t mark = b.off;
-  const float dt = (float)(1.0 / (double)num_steps);
-  for (int i = 0; i < ns; ++i) {
+  const double dtd = 1.0 / (double)num_steps;
+  const float dt = (float)dtd, dth = (float)(0.5 * dtd);
+  // one stage: out = base + v(in, row's t) dts, fused into the out-conv
+  auto stage = [&](int row, const float* in, float* out, const float* base, float dts) {
     b.off = mark;
-    UNetRun r{h, batch, &b, s, table + (size_t)i * h->temb_total, 0, false};
+    UNetRun r{h, batch, &b, s, table + (size_t)row * h->temb_total, 0, false};
     r.fin_counter = cnt;
-    int rc = r.run(x_inout, nullptr, x_inout, dt);
+    return r.run(in, nullptr, out, dts, base);
+  };
+  for (int i = 0; i < ns; ++i) {
+    int rc;
+    if (solver == SOLVER_MIDPOINT) {
+      if ((rc = stage(2 * i, x_inout, mid, x_inout, dth))) return rc;
+      rc = stage(2 * i + 1, mid, x_inout, x_inout, dt);
+    } else {
+      rc = stage(i, x_inout, x_inout, x_inout, dt);
+    }
     if (rc) return rc;
   }
   HIP_TRY(hipGetLastError());
   return RGFM_OK;
+}
+
+}  // namespace
+
+extern "C" int rgfm_sample_single_workspace_bytes(const rgfm_unet* h, int batch, size_t* bytes) {
+  return single_bytes(h, batch, SOLVER_EULER, bytes);
+}
+extern "C" int rgfm_sample_single_ode_workspace_bytes(const rgfm_unet* h, int batch, int solver, size_t* bytes) {
+  if (int rc = check_solver_id(solver)) return rc;
+  return single_bytes(h, batch, solver, bytes);
+}
+extern "C" int rgfm_sample_single(rgfm_unet* h, float* x_inout, int batch, int num_steps, int step_begin,
+                                  int step_end, void* ws, size_t ws_bytes, rgfm_stream_t stream) {
+  return single_loop(h, x_inout, batch, num_steps, step_begin, step_end, SOLVER_EULER, ws, ws_bytes, stream);
+}
+extern "C" int rgfm_sample_single_ode(rgfm_unet* h, float* x_inout, int batch, int num_steps, int step_begin, int step_end,
+                                      int solver, void* ws, size_t ws_bytes, rgfm_stream_t stream) {
+  return single_loop(h, x_inout, batch, num_steps, step_begin, step_end, solver, ws, ws_bytes, stream);
 }
 
 extern "C" int rgfm_guidance_workspace_bytes(int batch, int n_mc, size_t* bytes) {
@@ -82,30 +128,32 @@ extern "C" int rgfm_guidance_apply_cond(const float* s, float* v, const float* m
   return RGFM_OK;
 }
 
-extern "C" int rgfm_sample_cond_workspace_bytes(const rgfm_unet* h, int batch, int n_mc, size_t* bytes) {
+namespace {
+
+int cond_bytes(const rgfm_unet* h, int batch, int n_mc, int solver, size_t* bytes) {
   if (!h || !bytes || batch < 1 || n_mc < 1) return fail(RGFM_EINVAL, "bad argument");
-  const size_t d = (size_t)h->d.in_channels * h->d.img_size * h->d.img_size;
+  const size_t d = image_floats(h);
   *bytes = unet_eval_bytes(const_cast<rgfm_unet*>(h), batch) + table_bytes(h, 4096) + counter_bytes(batch) +
-           ((batch * d * 4 + 255) & ~(size_t)255) + guid_scratch_bytes(batch, n_mc);
+           ((batch * d * 4 + 255) & ~(size_t)255) + guid_scratch_bytes(batch, n_mc) +
+           (solver == SOLVER_MIDPOINT ? state_bytes(batch, d) : 0);
   return RGFM_OK;
 }
 
 // One net, guided by the one-sided block: kernel by kernel on the caller's stream (nothing to overlap, no graph).
-extern "C" int rgfm_sample_cond(rgfm_unet* h, float* s_inout, const float* mc_set, const float* ratios, int n_mc, int batch,
-                                int num_steps, double gamma, int step_begin, int step_end, void* ws, size_t ws_bytes,
-                                rgfm_stream_t stream) {
+int cond_loop(rgfm_unet* h, float* s_inout, const float* mc_set, const float* ratios, int n_mc, int batch, int num_steps,
+              double gamma, int step_begin, int step_end, int solver, void* ws, size_t ws_bytes, rgfm_stream_t stream) {
   refresh_modes();
+  if (int rc = check_solver_id(solver)) return rc;
   if (!h || !s_inout || !mc_set || !ratios || !ws) return fail(RGFM_EINVAL, "null argument");
   if (n_mc < 1) return fail(RGFM_EINVAL, "conditional sampling needs an MC set (n_mc >= 1)");
-  if (batch < 1 || num_steps < 1 || step_begin < 0 || step_end > num_steps || step_begin > step_end)
-    return fail(RGFM_EINVAL, "bad step range [%d,%d) of %d", step_begin, step_end, num_steps);
+  if (int rc = check_range(batch, num_steps, step_begin, step_end)) return rc;
   const int ns = step_end - step_begin;
-  if (ns > 4096) return fail(RGFM_EINVAL, "at most 4096 steps per call");
+  if (int rc = check_solver(solver, ns, num_steps)) return rc;
   const int d = h->d.in_channels * h->d.img_size * h->d.img_size;
   if (d % 4) return fail(RGFM_EINVAL, "flattened image sizes must be multiples of 4");
   if (n_mc > 4096) return fail(RGFM_EINVAL, "n_mc too large (max 4096)");
   size_t need = 0;
-  int rc = rgfm_sample_cond_workspace_bytes(h, batch, n_mc, &need);
+  int rc = cond_bytes(h, batch, n_mc, solver, &need);
   if (rc) return rc;
   if (need > ws_bytes) return fail(RGFM_ENOMEM, "workspace too small: %zu < %zu", ws_bytes, need);
   if (ns == 0) return RGFM_OK;
@@ -116,57 +164,64 @@ extern "C" int rgfm_sample_cond(rgfm_unet* h, float* s_inout, const float* mc_se
   unsigned* cnt = reinterpret_cast<unsigned*>(b.f(batch));
   float* v = b.f((size_t)batch * d);
   float* scratch = b.f(guid_scratch_bytes(batch, n_mc) / sizeof(float));
+  float* mid = solver == SOLVER_MIDPOINT ? b.f((size_t)batch * d) : nullptr;
   HIP_TRY(hipMemsetAsync(cnt, 0, (size_t)batch * sizeof(unsigned), s));
-  launch_time_table(h, nullptr, num_steps, step_begin, ns, table, s);
+  launch_stage_table(h, solver, num_steps, step_begin, ns, table, s);
   const size_t mark = b.off;
   const double dtd = 1.0 / (double)num_steps;
-  const float dt = (float)dtd;
-  for (int i = 0; i < ns; ++i) {
-    const double t = (double)(step_begin + i) * dtd;
-    const bool guided = t > 1e-3;  // `t > eps` test of the reference (:124)
+  const float dt = (float)dtd, dth = (float)(0.5 * dtd);
+  // one stage: out = base + F(in, t) dts; guided iff the stage's own t > eps (`t > eps` test of the reference, :124)
+  auto stage = [&](int row, double t, float* in, float* out, const float* base, float dts) -> int {
+    const bool guided = t > 1e-3;
     b.off = mark;
-    UNetRun r{h, batch, &b, s, table + (size_t)i * h->temb_total, 0, false};
+    UNetRun r{h, batch, &b, s, table + (size_t)row * h->temb_total, 0, false};
     r.fin_counter = cnt;
     // unguided: the fused Euler epilogue; guided: the raw velocity, and the guidance block moves the state
-    if ((rc = guided ? r.run(s_inout, v, nullptr, dt) : r.run(s_inout, nullptr, s_inout, dt))) return rc;
-    if (guided) {
-      rc = guidance_launch(s_inout, nullptr, v, nullptr, mc_set, nullptr, ratios, batch, n_mc, d, 0, t, gamma, scratch, nullptr,
-                           s_inout, nullptr, dt, s, nullptr, nullptr, 0, n_mc);
-      if (rc) return rc;
+    if (int rc = guided ? r.run(in, v, nullptr, dts) : r.run(in, nullptr, out, dts, base)) return rc;
+    if (!guided) return RGFM_OK;
+    return guidance_launch(in, nullptr, v, nullptr, mc_set, nullptr, ratios, batch, n_mc, d, 0, t, gamma, scratch, nullptr,
+                           out, nullptr, dts, s, nullptr, nullptr, 0, n_mc, base, nullptr);
+  };
+  for (int i = 0; i < ns; ++i) {
+    const double t = (double)(step_begin + i) * dtd;
+    if (solver == SOLVER_MIDPOINT) {
+      if ((rc = stage(2 * i, t, s_inout, mid, s_inout, dth))) return rc;
+      rc = stage(2 * i + 1, ((double)(step_begin + i) + 0.5) * dtd, mid, s_inout, s_inout, dt);
+    } else {
+      rc = stage(i, t, s_inout, s_inout, s_inout, dt);
     }
+    if (rc) return rc;
   }
   HIP_TRY(hipGetLastError());
   return RGFM_OK;
 }
 
-extern "C" int rgfm_sample_pair_workspace_bytes(const rgfm_unet* hx, const rgfm_unet* hy, int batch, int n_mc,
-                                                size_t* bytes) {
+int pair_bytes(const rgfm_unet* hx, const rgfm_unet* hy, int batch, int n_mc, int solver, size_t* bytes) {
   if (!hx || !hy || !bytes || batch < 1 || n_mc < 0) return fail(RGFM_EINVAL, "bad argument");
   const size_t ex = unet_eval_bytes(const_cast<rgfm_unet*>(hx), batch);
   const size_t ey = unet_eval_bytes(const_cast<rgfm_unet*>(hy), batch);
-  const size_t dx = (size_t)hx->d.in_channels * hx->d.img_size * hx->d.img_size;
-  const size_t dy = (size_t)hy->d.in_channels * hy->d.img_size * hy->d.img_size;
+  const size_t dx = image_floats(hx), dy = image_floats(hy);
   size_t total = table_bytes(hx, 4096) + table_bytes(hy, 4096) + ex + ey + 2 * counter_bytes(batch);  // the two nets run concurrently
   total += ((batch * dx * 4 + 255) & ~(size_t)255) + ((batch * dy * 4 + 255) & ~(size_t)255);
   total += guid_scratch_bytes(batch, n_mc);
   total += 256 + (size_t)4096 * 4 * sizeof(float);  // step counter + per-step guidance scalars (graph replay)
+  if (solver == SOLVER_MIDPOINT) total += state_bytes(batch, dx) + state_bytes(batch, dy);
   *bytes = total;
   return RGFM_OK;
 }
 
-extern "C" int rgfm_sample_pair(rgfm_unet* hx, rgfm_unet* hy, float* x_inout, float* y_inout, const float* mc_x1,
-                                const float* mc_y1, const float* mc_ratios, int n_mc, int batch, int num_steps,
-                                double gamma, int step_begin, int step_end, void* ws, size_t ws_bytes,
-                                rgfm_stream_t stream) {
+int pair_sample(rgfm_unet* hx, rgfm_unet* hy, float* x_inout, float* y_inout, const float* mc_x1, const float* mc_y1,
+                const float* mc_ratios, int n_mc, int batch, int num_steps, double gamma, int step_begin, int step_end,
+                int solver, void* ws, size_t ws_bytes, rgfm_stream_t stream) {
   refresh_modes();
+  if (int rc = check_solver_id(solver)) return rc;
   if (!hx || !hy || !x_inout || !y_inout || !ws) return fail(RGFM_EINVAL, "null argument");
   if (n_mc < 0 || (n_mc > 0 && (!mc_x1 || !mc_y1 || !mc_ratios))) return fail(RGFM_EINVAL, "MC set missing");
-  if (batch < 1 || num_steps < 1 || step_begin < 0 || step_end > num_steps || step_begin > step_end)
-    return fail(RGFM_EINVAL, "bad step range [%d,%d) of %d", step_begin, step_end, num_steps);
+  if (int rc = check_range(batch, num_steps, step_begin, step_end)) return rc;
   const int ns = step_end - step_begin;
-  if (ns > 4096) return fail(RGFM_EINVAL, "at most 4096 steps per call");
+  if (int rc = check_solver(solver, ns, num_steps)) return rc;
   size_t need = 0;
-  rgfm_sample_pair_workspace_bytes(hx, hy, batch, n_mc, &need);
+  pair_bytes(hx, hy, batch, n_mc, solver, &need);
   if (need > ws_bytes) return fail(RGFM_ENOMEM, "workspace too small: %zu < %zu", ws_bytes, need);
   if (ns == 0) return RGFM_OK;
   hipStream_t s = (hipStream_t)stream;
@@ -182,25 +237,74 @@ extern "C" int rgfm_sample_pair(rgfm_unet* hx, rgfm_unet* hy, float* x_inout, fl
   unsigned* cnt_x = reinterpret_cast<unsigned*>(b.f(batch));
   unsigned* cnt_y = reinterpret_cast<unsigned*>(b.f(batch));
   float* gstate = b.f(64 + (size_t)4096 * 4);
+  float* x_mid = solver == SOLVER_MIDPOINT ? b.f((size_t)batch * dx) : nullptr;
+  float* y_mid = solver == SOLVER_MIDPOINT ? b.f((size_t)batch * dy) : nullptr;
   HIP_TRY(hipMemsetAsync(cnt_x, 0, (size_t)batch * sizeof(unsigned), s));
   HIP_TRY(hipMemsetAsync(cnt_y, 0, (size_t)batch * sizeof(unsigned), s));
-  launch_time_table(hx, nullptr, num_steps, step_begin, ns, tx, s);
-  launch_time_table(hy, nullptr, num_steps, step_begin, ns, ty, s);
+  launch_stage_table(hx, solver, num_steps, step_begin, ns, tx, s);
+  launch_stage_table(hy, solver, num_steps, step_begin, ns, ty, s);
   const size_t mark_x = b.off;
   const size_t mark_y = mark_x + unet_eval_bytes(hx, batch);
   // (step: the device-side step counter of the graph-replay path -- the time-table row is then chosen on the device)
-  auto eval_x = [&](int i, hipStream_t st, float* v_out, float* x_state, float dt, const int* step) {
+  auto eval_x = [&](int row, hipStream_t st, const float* in, float* v_out, float* x_state, const float* base, float dt,
+                    const int* step) {
     b.off = mark_x;
-    UNetRun r{hx, batch, &b, st, step ? tx : tx + (size_t)i * hx->temb_total, 0, false};
+    UNetRun r{hx, batch, &b, st, step ? tx : tx + (size_t)row * hx->temb_total, 0, false};
     r.fin_counter = cnt_x, r.step_ptr = step;
-    return r.run(x_inout, v_out, x_state, dt);
+    return r.run(in, v_out, x_state, dt, base);
   };
-  auto eval_y = [&](int i, hipStream_t st, float* v_out, float* y_state, float dt, const int* step) {
+  auto eval_y = [&](int row, hipStream_t st, const float* in, float* v_out, float* y_state, const float* base, float dt,
+                    const int* step) {
     b.off = mark_y;
-    UNetRun r{hy, batch, &b, st, step ? ty : ty + (size_t)i * hy->temb_total, 0, false};
+    UNetRun r{hy, batch, &b, st, step ? ty : ty + (size_t)row * hy->temb_total, 0, false};
     r.fin_counter = cnt_y, r.step_ptr = step;
-    return r.run(y_inout, v_out, y_state, dt);
+    return r.run(in, v_out, y_state, dt, base);
   };
   return pair_loop(eval_x, eval_y, x_inout, y_inout, mc_x1, mc_y1, mc_ratios, n_mc, batch, num_steps, gamma,
-                   step_begin, ns, dx, dy, vx, vy, logp, s, gstate);
+                   step_begin, ns, dx, dy, vx, vy, logp, s, gstate, solver, x_mid, y_mid);
+}
+
+}  // namespace
+
+extern "C" int rgfm_sample_cond_workspace_bytes(const rgfm_unet* h, int batch, int n_mc, size_t* bytes) {
+  return cond_bytes(h, batch, n_mc, SOLVER_EULER, bytes);
+}
+extern "C" int rgfm_sample_cond_ode_workspace_bytes(const rgfm_unet* h, int batch, int n_mc, int solver, size_t* bytes) {
+  if (int rc = check_solver_id(solver)) return rc;
+  return cond_bytes(h, batch, n_mc, solver, bytes);
+}
+extern "C" int rgfm_sample_cond(rgfm_unet* h, float* s_inout, const float* mc_set, const float* ratios, int n_mc, int batch,
+                                int num_steps, double gamma, int step_begin, int step_end, void* ws, size_t ws_bytes,
+                                rgfm_stream_t stream) {
+  return cond_loop(h, s_inout, mc_set, ratios, n_mc, batch, num_steps, gamma, step_begin, step_end, SOLVER_EULER, ws, ws_bytes,
+                   stream);
+}
+extern "C" int rgfm_sample_cond_ode(rgfm_unet* h, float* s_inout, const float* mc_set, const float* ratios, int n_mc, int batch,
+                                    int num_steps, double gamma, int step_begin, int step_end, int solver, void* ws,
+                                    size_t ws_bytes, rgfm_stream_t stream) {
+  return cond_loop(h, s_inout, mc_set, ratios, n_mc, batch, num_steps, gamma, step_begin, step_end, solver, ws, ws_bytes, stream);
+}
+
+extern "C" int rgfm_sample_pair_workspace_bytes(const rgfm_unet* hx, const rgfm_unet* hy, int batch, int n_mc,
+                                                size_t* bytes) {
+  return pair_bytes(hx, hy, batch, n_mc, SOLVER_EULER, bytes);
+}
+extern "C" int rgfm_sample_pair_ode_workspace_bytes(const rgfm_unet* hx, const rgfm_unet* hy, int batch, int n_mc, int solver,
+                                                    size_t* bytes) {
+  if (int rc = check_solver_id(solver)) return rc;
+  return pair_bytes(hx, hy, batch, n_mc, solver, bytes);
+}
+extern "C" int rgfm_sample_pair(rgfm_unet* hx, rgfm_unet* hy, float* x_inout, float* y_inout, const float* mc_x1,
+                                const float* mc_y1, const float* mc_ratios, int n_mc, int batch, int num_steps,
+                                double gamma, int step_begin, int step_end, void* ws, size_t ws_bytes,
+                                rgfm_stream_t stream) {
+  return pair_sample(hx, hy, x_inout, y_inout, mc_x1, mc_y1, mc_ratios, n_mc, batch, num_steps, gamma, step_begin, step_end,
+                     SOLVER_EULER, ws, ws_bytes, stream);
+}
+extern "C" int rgfm_sample_pair_ode(rgfm_unet* hx, rgfm_unet* hy, float* x_inout, float* y_inout, const float* mc_x1,
+                                    const float* mc_y1, const float* mc_ratios, int n_mc, int batch, int num_steps,
+                                    double gamma, int step_begin, int step_end, int solver, void* ws, size_t ws_bytes,
+                                    rgfm_stream_t stream) {
+  return pair_sample(hx, hy, x_inout, y_inout, mc_x1, mc_y1, mc_ratios, n_mc, batch, num_steps, gamma, step_begin, step_end,
+                     solver, ws, ws_bytes, stream);
 }

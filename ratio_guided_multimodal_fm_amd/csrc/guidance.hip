@@ -234,6 +234,7 @@ __global__ __launch_bounds__(256, 2) void guid_apply_mfma_kernel(const GuidanceA
   const float* M = part ? a.mc_y1 : a.mc_x1;
   float* V = part ? a.vy : a.vx;
   float* XS = part ? a.y_state : a.x_state;
+  const float* XB = part ? a.y_base : a.x_base;  // (null: the update starts from X)
   const int D = part ? a.dy : a.dx;
   const int b0 = blockIdx.x * 32;
   const int d = ((int)blockIdx.y - (part ? nbx : 0)) * 128 + 4 * l31;
@@ -336,7 +337,7 @@ __global__ __launch_bounds__(256, 2) void guid_apply_mfma_kernel(const GuidanceA
     nv.z = __fadd_rn(__fmul_rn(a.g1, v.z), __fmul_rn(a.g2, g.z));
     nv.w = __fadd_rn(__fmul_rn(a.g1, v.w), __fmul_rn(a.g2, g.w));
     if (XS) {
-      f32x4 xs = xv;
+      f32x4 xs = XB ? *reinterpret_cast<const f32x4*>(XB + o) : xv;
       xs.x = __fadd_rn(xs.x, __fmul_rn(nv.x, a.dt));
       xs.y = __fadd_rn(xs.y, __fmul_rn(nv.y, a.dt));
       xs.z = __fadd_rn(xs.z, __fmul_rn(nv.z, a.dt));

@@ -364,13 +364,15 @@ void launch_ratio_head_bwd(const float* score, const float* w, float* gh, float*
                      rows, n, loss);
 }
 
-__global__ void euler_grad_kernel(float* x, const float* v, const float* g, size_t n, float gamma, float dt) {
+// x = base + (v + gamma g) dt; base null: in place on x (base, when given, is another buffer than x: a midpoint stage)
+__global__ void euler_grad_kernel(float* x, const float* base, const float* v, const float* g, size_t n, float gamma, float dt) {
+  const float* b = base ? base : x;
   for (size_t i = blockIdx.x * (size_t)blockDim.x + threadIdx.x; i < n; i += (size_t)gridDim.x * blockDim.x)
-    x[i] = __fadd_rn(x[i], __fmul_rn(fmaf(gamma, g[i], v[i]), dt));
+    x[i] = __fadd_rn(b[i], __fmul_rn(fmaf(gamma, g[i], v[i]), dt));
 }
-void launch_euler_grad(float* x, const float* v, const float* g, size_t n, float gamma, float dt, hipStream_t s) {
+void launch_euler_grad(float* x, const float* v, const float* g, size_t n, float gamma, float dt, hipStream_t s, const float* base) {
   const int blocks = (int)((n + 255) / 256 < 2048 ? (n + 255) / 256 : 2048);
-  hipLaunchKernelGGL(euler_grad_kernel, dim3(blocks), dim3(256), 0, s, x, v, g, n, gamma, dt);
+  hipLaunchKernelGGL(euler_grad_kernel, dim3(blocks), dim3(256), 0, s, x, base, v, g, n, gamma, dt);
 }
 
 }  // namespace rgfm

@@ -866,7 +866,9 @@ struct UNetRun {
 
   // FlexibleUNet.forward (unet_flexible.py:203-261).  Exactly one of v_out / x_state
   // may be non-null... both allowed: v_out receives the velocity, x_state the Euler update.
-  int run(const float* x, float* v_out, float* x_state, float dt) {
+  // x_base (with x_state): x_state = x_base + v dt, a midpoint stage that starts from another buffer than it writes;
+  // null or x_state itself: the in-place update.
+  int run(const float* x, float* v_out, float* x_state, float dt, const float* x_base = nullptr) {
     const rgfm_unet_desc& d = h->d;
     ModeScope mode_scope(h->conv_mode);
     if (!dry && h->trace) h->acts.clear();
@@ -918,6 +920,7 @@ struct UNetRun {
       ConvOutArgs co{};
       co.in = cur.data, co.ab = ab, co.w = h->packed + h->ocw_pk, co.bias = h->params + h->ocb;
       co.v_out = v_out, co.x_state = x_state, co.dt = dt, co.B = B, co.Cin = cur.C;
+      co.x_base = x_base == x_state ? nullptr : x_base;
       co.g = make_geom(cur.S, cur.S);
       co.halo_px = co.g.spt * (co.g.th + 2) * (co.g.W + 2);
       // algorithmic bytes: the NHWC map + its scale/shift in, the NCHW velocity out (fused Euler: state in and out)
@@ -983,12 +986,15 @@ inline void guidance_scalars(double t, float* tf, float* s2, float* cden) {
 inline int guidance_launch(const float* x, const float* y, float* vx, float* vy, const float* mx, const float* my,
                     const float* r, int B, int N, int dx, int dy, double t, double gamma, float* logp,
                     float* weights_out, float* xs, float* ys, float dt, hipStream_t s, const float* sched = nullptr,
-                    const int* step_ptr = nullptr, int phase = 0, int ratio_stride = 0) {
+                    const int* step_ptr = nullptr, int phase = 0, int ratio_stride = 0, const float* xb = nullptr,
+                    const float* yb = nullptr) {
   // phase 0: the whole block; 1: distances + importance weights only -- they need the step's (x_t, y_t) and the MC set,
   // not the velocities; 2: the rest (needs v)
   // One-sided block (conditional sampling): dy = 0 with y, vy, my, ys null, and ratio_stride = N -- r is then [B][N],
   // a ratio row per sample.  The kernels take the second modality's slices and column blocks from dy, so none is
   // launched; the observed side's Gaussian factor is constant in the MC index and cancels in the normalised weights.
+  // xb / yb (with xs / ys): the state the update starts from, xs = xb + dt * blended, while the block is evaluated at
+  // x / y (second stage of a midpoint step); null or x / y themselves: xs = x + dt * blended.
   if (dx % 4 || dy % 4) return fail(RGFM_EINVAL, "flattened image sizes must be multiples of 4");
   if ((size_t)4 * N * sizeof(float) > 64 * 1024) return fail(RGFM_EINVAL, "n_mc too large (max 4096)");
   // Python-double scalar arithmetic of the reference (sample_mnist_svhn.py:115,127,135,159,170),
@@ -1001,6 +1007,7 @@ inline int guidance_launch(const float* x, const float* y, float* vx, float* vy,
   a.sched = sched, a.step_ptr = sched ? step_ptr : nullptr;
   a.g1 = (float)(1.0 - gamma), a.g2 = (float)gamma;
   a.dist = reinterpret_cast<double*>(logp), a.weights_out = weights_out, a.x_state = xs, a.y_state = ys, a.dt = dt;
+  a.x_base = xb == x ? nullptr : xb, a.y_base = yb == y ? nullptr : yb;
   a.wbuf = reinterpret_cast<float*>(reinterpret_cast<char*>(logp) + guid_dist_bytes(B, N));
   a.wsum = reinterpret_cast<float*>(reinterpret_cast<char*>(a.wbuf) + guid_wbuf_bytes(B, N));
   a.slice_len = 512;  // 512-element slices (8 x 16 x 4 = 512 workgroups at the benchmark shape) unless that needs more than RGFM_GUID_SLICES of them
@@ -1022,11 +1029,36 @@ inline int guidance_launch(const float* x, const float* y, float* vx, float* vy,
 }
 
 
-// Shared Euler loop of paired_sampler (src/utils/flow_utils.py:186-278 with the guidance of
+// solvers of the sampler loops (include/rgfm.h: RGFM_SOLVER_*)
+constexpr int SOLVER_EULER = 0, SOLVER_MIDPOINT = 1;
+constexpr int MAX_STEPS_EULER = 4096, MAX_STEPS_MIDPOINT = 2048;  // the time tables hold 4096 rows: one / two per step
+inline int check_solver(int solver, int ns, int num_steps) {
+  if (solver != SOLVER_EULER && solver != SOLVER_MIDPOINT) return fail(RGFM_EINVAL, "unknown solver %d (RGFM_SOLVER_EULER, RGFM_SOLVER_MIDPOINT)", solver);
+  if (solver == SOLVER_EULER && ns > MAX_STEPS_EULER) return fail(RGFM_EINVAL, "at most 4096 steps per call");
+  if (solver == SOLVER_MIDPOINT && ns > MAX_STEPS_MIDPOINT) return fail(RGFM_EINVAL, "midpoint: at most 2048 steps per call (two time-table rows per step)");
+  if (solver == SOLVER_MIDPOINT && num_steps > (1 << 30)) return fail(RGFM_EINVAL, "midpoint: num_steps too large");
+  return RGFM_OK;
+}
+inline size_t state_bytes(int batch, size_t d) { return ((size_t)batch * d * 4 + 255) & ~(size_t)255; }
+// Time-table rows of a loop's stages.  Euler: row i is t = (step_begin + i) / num_steps.  Midpoint: row 2i is the step's
+// t1 = (step_begin + i) dt and row 2i + 1 its t2 = (step_begin + i + 0.5) dt -- the table of the 2 num_steps half-steps:
+// (2k + j) * (1.0 / (2 N)) and (k + j / 2) * (1.0 / N) are the same double (a factor two moves no rounding).
+inline int launch_stage_table(rgfm_unet* h, int solver, int num_steps, int step_begin, int ns, float* table, hipStream_t s) {
+  if (solver == SOLVER_MIDPOINT) return launch_time_table(h, nullptr, 2 * num_steps, 2 * step_begin, 2 * ns, table, s);
+  return launch_time_table(h, nullptr, num_steps, step_begin, ns, table, s);
+}
+
+// Shared loop of paired_sampler (src/utils/flow_utils.py:186-278 with the guidance of
 // src/sample_mnist_svhn.py:117-175): eval_x / eval_y enqueue one velocity-net evaluation of step i
 // on the given stream, writing the raw velocity (guided steps) or the fused Euler update.
+// eval(row, stream, in, v_out, state_out, base, dt, step): the net at `in` with time-table row `row`; state_out = base + v dt.
+// solver SOLVER_MIDPOINT (x_mid / y_mid: one mid-state buffer per modality): every step is two such stages,
+//   (x_mid, y_mid) = (x, y) + (dt / 2) F(x, y, t1),   (x, y) = (x, y) + dt F(x_mid, y_mid, t2),   t2 = t1 + dt / 2,
+// F the whole guided velocity at the stage's own state and time; a stage is guided iff its own t > 1e-3.  Each stage
+// forks and joins the side stream as an Euler step does.
 // Graph replay (U-Net pairs, RGFM_GRAPH=1; never with active kernel timers): every guided step enqueues the
-// same ~135 launches with the same arguments except the time-table row and three guidance scalars.  Those are read
+// same ~135 launches with the same arguments except the time-table row and three guidance scalars.  Euler only: a midpoint
+// call runs kernel by kernel.  Those are read
 // on the device through a step counter (`gstate`: [0] the counter, [64..] the per-step scalars), so the first guided
 // step is captured once -- both streams, fork and join included -- into a hipGraph and every guided step is one
 // hipGraphLaunch.  Results are bit-identical to the kernel-by-kernel path (same kernels, same arguments).
@@ -1034,7 +1066,7 @@ template <class EvalX, class EvalY>
 int pair_loop(EvalX&& eval_x, EvalY&& eval_y, float* x_inout, float* y_inout, const float* mc_x1,
               const float* mc_y1, const float* mc_ratios, int n_mc, int batch, int num_steps, double gamma,
               int step_begin, int ns, int dx, int dy, float* vx, float* vy, float* logp, hipStream_t caller,
-              float* gstate = nullptr) {
+              float* gstate = nullptr, int solver = SOLVER_EULER, float* x_mid = nullptr, float* y_mid = nullptr) {
   const double dtd = 1.0 / (double)num_steps;
   const float dt = (float)dtd;
   // The two velocity nets of a step are independent (reference :119-121): the second one runs on a
@@ -1046,7 +1078,7 @@ int pair_loop(EvalX&& eval_x, EvalY&& eval_y, float* x_inout, float* y_inout, co
   const bool overlap = g_modes.overlap;
   hipStream_t side = ds->side;
   hipEvent_t ev_fork = ds->fork, ev_join = ds->join;
-  const bool use_graph = gstate && g_modes.graph && !g_prof.on && n_mc > 0 && ns >= 4;
+  const bool use_graph = gstate && g_modes.graph && !g_prof.on && n_mc > 0 && ns >= 4 && solver == SOLVER_EULER;
   hipStream_t s = caller;
   if (use_graph && caller == nullptr) {  // (see DevState::main)
     s = ds->main;
@@ -1066,34 +1098,38 @@ int pair_loop(EvalX&& eval_x, EvalY&& eval_y, float* x_inout, float* y_inout, co
     HIP_TRY(hipMemsetAsync(step_dev, 0, 256, s));
     launch_guid_schedule(sched_dev, step_begin, ns, num_steps, s);
   }
-  auto one_step = [&](int i, bool guided) -> int {
+  // one stage: (xout, yout) = (xb, yb) + dts * F(xin, yin, t), the nets reading time-table row `row`
+  auto one_stage = [&](int row, double t, bool guided, float* xin, float* yin, float* xout, float* yout, const float* xb,
+                       const float* yb, float dts) -> int {
     hipStream_t sy = overlap ? side : s;
     if (overlap) {
       HIP_TRY(hipEventRecord(ev_fork, s));
       HIP_TRY(hipStreamWaitEvent(side, ev_fork, 0));
     }
-    int rc = eval_y(i, sy, guided ? vy : nullptr, guided ? nullptr : y_inout, dt, step_dev);
+    int rc = eval_y(row, sy, yin, guided ? vy : nullptr, guided ? nullptr : yout, yb, dts, step_dev);
     if (rc) return rc;
     if (overlap) HIP_TRY(hipEventRecord(ev_join, side));
-    rc = eval_x(i, s, guided ? vx : nullptr, guided ? nullptr : x_inout, dt, step_dev);
+    rc = eval_x(row, s, xin, guided ? vx : nullptr, guided ? nullptr : xout, xb, dts, step_dev);
     if (rc) return rc;
-    const double t = (double)(step_begin + i) * dtd;
     // The distances to the MC set and the importance weights depend on (x_t, y_t) only (sample_mnist_svhn.py:130-156; a
     // guided step's nets write velocities, the state moves in guid_apply): they go on this stream BEFORE it waits for the
     // other net -- the x net of a pair is the quicker one, so they run in its shadow instead of on the step's critical path
     if (guided && overlap) {
-      rc = guidance_launch(x_inout, y_inout, vx, vy, mc_x1, mc_y1, mc_ratios, batch, n_mc, dx, dy, t, gamma, logp,
-                           nullptr, x_inout, y_inout, dt, s, sched_dev, step_dev, 1);
+      rc = guidance_launch(xin, yin, vx, vy, mc_x1, mc_y1, mc_ratios, batch, n_mc, dx, dy, t, gamma, logp,
+                           nullptr, xout, yout, dts, s, sched_dev, step_dev, 1, 0, xb, yb);
       if (rc) return rc;
     }
     if (overlap) HIP_TRY(hipStreamWaitEvent(s, ev_join, 0));
     if (guided) {
-      rc = guidance_launch(x_inout, y_inout, vx, vy, mc_x1, mc_y1, mc_ratios, batch, n_mc, dx, dy, t, gamma, logp,
-                           nullptr, x_inout, y_inout, dt, s, sched_dev, step_dev, overlap ? 2 : 0);
+      rc = guidance_launch(xin, yin, vx, vy, mc_x1, mc_y1, mc_ratios, batch, n_mc, dx, dy, t, gamma, logp,
+                           nullptr, xout, yout, dts, s, sched_dev, step_dev, overlap ? 2 : 0, 0, xb, yb);
       if (rc) return rc;
     }
     if (step_dev) launch_step_inc(step_dev, s);
     return RGFM_OK;
+  };
+  auto one_step = [&](int i, bool guided) -> int {  // an Euler step: one stage, in place
+    return one_stage(i, (double)(step_begin + i) * dtd, guided, x_inout, y_inout, x_inout, y_inout, x_inout, y_inout, dt);
   };
   hipGraphExec_t exec = nullptr;
   // On EVERY exit path -- also the error returns inside the loop -- the work already enqueued must stay ordered: the
@@ -1119,6 +1155,15 @@ int pair_loop(EvalX&& eval_x, EvalY&& eval_y, float* x_inout, float* y_inout, co
   for (int i = 0; i < ns; ++i) {
     const double t = (double)(step_begin + i) * dtd;
     const bool guided = n_mc > 0 && t > 1e-3;  // `t > eps` test of the reference (:124)
+    if (solver == SOLVER_MIDPOINT) {
+      const double t2 = ((double)(step_begin + i) + 0.5) * dtd;
+      const float dth = (float)(0.5 * dtd);
+      int rc = one_stage(2 * i, t, guided, x_inout, y_inout, x_mid, y_mid, x_inout, y_inout, dth);
+      if (rc) return rc;
+      rc = one_stage(2 * i + 1, t2, n_mc > 0 && t2 > 1e-3, x_mid, y_mid, x_inout, y_inout, x_inout, y_inout, dt);
+      if (rc) return rc;
+      continue;
+    }
     if (use_graph && guided) {
       if (!exec) {
         hipGraph_t graph = nullptr;

@@ -194,6 +194,7 @@ struct ConvOutArgs {  // out_conv(silu(out_norm(h))) -> NCHW velocity, optional 
   const float* bias;
   float* v_out;       // NCHW velocity or null
   float* x_state;     // NCHW state for the fused Euler update or null
+  const float* x_base;  // x_state = x_base + v dt (out of place: a midpoint stage); null: x_state += v dt
   float dt;
   int B, Cin;
   TileGeom g;
@@ -412,8 +413,9 @@ void launch_conv_bwd_img(const float* gz, const float* w, float* gimg, int B, in
 void launch_layernorm_silu_bwd(const float* u, const float* gy, const float* w, const float* b, float* gu, int rows, int n, hipStream_t s);
 // gh[row][k] = d log_ratio / d score (score[row]) * w[k]; log_ratio (optional) [rows]
 void launch_ratio_head_bwd(const float* score, const float* w, float* gh, float* log_ratio, int rows, int n, int loss, hipStream_t s);
-// x <- x + (v + gamma g) dt
-void launch_euler_grad(float* x, const float* v, const float* g, size_t n, float gamma, float dt, hipStream_t s);
+// x <- base + (v + gamma g) dt; base null: x <- x + (v + gamma g) dt
+void launch_euler_grad(float* x, const float* v, const float* g, size_t n, float gamma, float dt, hipStream_t s,
+                       const float* base = nullptr);
 
 // ---- guidance / Euler
 struct GuidanceArgs {
@@ -437,6 +439,10 @@ struct GuidanceArgs {
   float* wsum;         // [B] their row sums (scratch: behind wbuf)
   float* x_state;      // optional fused Euler: x_state += dt * blended
   float* y_state;
+  // optional: x_state = x_base + dt * blended, with x still the point the guidance is evaluated at (the second stage of
+  // a midpoint step evaluates at the mid state and moves the step's start state); null: the base is x
+  const float* x_base;
+  const float* y_base;
   float dt;
 };
 constexpr int RGFM_GUID_SLICES = 8;

@@ -438,7 +438,8 @@ __global__ __launch_bounds__(256) void conv_out_kernel(const ConvOutArgs a) {
     const float v = (acc[co].x + acc[co].y) + a.bias[co];
     const size_t idx = ((size_t)b * CIMG + co) * HW + pixl;
     if (a.v_out) a.v_out[idx] = v;
-    if (a.x_state) a.x_state[idx] = __fadd_rn(a.x_state[idx], __fmul_rn(v, a.dt));
+    // (x_base: the state the update starts from when it is not the one written -- a midpoint stage; null: in place)
+    if (a.x_state) a.x_state[idx] = __fadd_rn((a.x_base ? a.x_base : a.x_state)[idx], __fmul_rn(v, a.dt));
   }
 }
 

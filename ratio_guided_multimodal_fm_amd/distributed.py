@@ -38,24 +38,24 @@ def shard_bounds(n, world, rank):
 class HipBackend:
     """Compute calls routed to librgfm_hip.so (the product path)."""
 
-    def sample_single(self, model, x, num_steps):
+    def sample_single(self, model, x, num_steps, solver='euler'):
         from . import _engine
-        return _engine.sample_single(model, x, num_steps)
+        return _engine.sample_single(model, x, num_steps, solver=solver)
 
-    def sample_two(self, fm_x, x, fm_y, y, num_steps):
+    def sample_two(self, fm_x, x, fm_y, y, num_steps, solver='euler'):
         from . import _engine
-        return _engine.sample_two_streams(fm_x, x, fm_y, y, num_steps)
+        return _engine.sample_two_streams(fm_x, x, fm_y, y, num_steps, solver=solver)
 
     def ratios(self, ratio_estimator, mc_x1, mc_y1):
         return ratio_estimator._engine.eval(mc_x1, mc_y1, "ratio")
 
-    def sample_pair(self, fm_x, fm_y, x, y, mc_x1, mc_y1, mc_ratios, num_steps, gamma):
+    def sample_pair(self, fm_x, fm_y, x, y, mc_x1, mc_y1, mc_ratios, num_steps, gamma, solver='euler'):
         from . import _engine
-        return _engine.sample_pair(fm_x, fm_y, x, y, mc_x1, mc_y1, mc_ratios, num_steps, gamma)
+        return _engine.sample_pair(fm_x, fm_y, x, y, mc_x1, mc_y1, mc_ratios, num_steps, gamma, solver=solver)
 
-    def sample_pair_grad(self, fm_x, fm_y, ratio_estimator, x, y, num_steps, gamma):
+    def sample_pair_grad(self, fm_x, fm_y, ratio_estimator, x, y, num_steps, gamma, solver='euler'):
         from . import _engine
-        return _engine.sample_pair_grad(fm_x, fm_y, ratio_estimator, x, y, num_steps, gamma)
+        return _engine.sample_pair_grad(fm_x, fm_y, ratio_estimator, x, y, num_steps, gamma, solver=solver)
 
 
 def _via_host(t, group):
@@ -86,7 +86,7 @@ def _all_gather_rows(t, counts, group):
 
 
 def sharded_paired_sampler(fm_x, fm_y, ratio_estimator, guidance_method, guidance_strength, num_steps,
-                           noise, device, backend=None, group=None, gather="rank0", keep=None):
+                           noise, device, backend=None, group=None, gather="rank0", keep=None, solver='euler'):
     """Sharded equivalent of ``paired_sampler`` on explicit host noise.
 
     noise = (x0, y0, mc_x0, mc_y0): the FULL tensors, identical on every rank
@@ -95,7 +95,12 @@ def sharded_paired_sampler(fm_x, fm_y, ratio_estimator, guidance_method, guidanc
     only (None, None elsewhere) for gather="rank0".
     keep: optional dict that receives references to the gathered MC set the guided loop ran on
     (``mc_x1``, ``mc_y1``, ``mc_ratios``) -- bench.py's parity gate follows rows of the timed call from it.
+    solver: 'euler' | 'midpoint', as in ``paired_sampler``; passed to the backend's calls as a keyword when it is
+    not the default.
     """
+    from ._lib import solver_id
+    solver_id(solver)
+    kw = {'solver': solver} if solver != 'euler' else {}
     backend = backend or HipBackend()
     world = dist.get_world_size(group) if dist.is_initialized() else 1
     rank = dist.get_rank(group) if dist.is_initialized() else 0
@@ -120,10 +125,10 @@ def sharded_paired_sampler(fm_x, fm_y, ratio_estimator, guidance_method, guidanc
         sy = mc_y0[lo:hi].to(device, copy=True).contiguous()
         if hi > lo:
             if hasattr(backend, "sample_two"):
-                backend.sample_two(fm_x, sx, fm_y, sy, num_steps)
+                backend.sample_two(fm_x, sx, fm_y, sy, num_steps, **kw)
             else:
-                backend.sample_single(fm_x, sx, num_steps)
-                backend.sample_single(fm_y, sy, num_steps)
+                backend.sample_single(fm_x, sx, num_steps, **kw)
+                backend.sample_single(fm_y, sy, num_steps, **kw)
             sr = backend.ratios(ratio_estimator, sx, sy)
         else:
             sr = torch.empty(0, device=device)
@@ -139,9 +144,9 @@ def sharded_paired_sampler(fm_x, fm_y, ratio_estimator, guidance_method, guidanc
     y = y0[lo:hi].to(device, copy=True).contiguous()
     if hi > lo:
         if grad_guided:
-            backend.sample_pair_grad(fm_x, fm_y, ratio_estimator, x, y, num_steps, guidance_strength)
+            backend.sample_pair_grad(fm_x, fm_y, ratio_estimator, x, y, num_steps, guidance_strength, **kw)
         else:
-            backend.sample_pair(fm_x, fm_y, x, y, mc_x1, mc_y1, mc_r, num_steps, guidance_strength)
+            backend.sample_pair(fm_x, fm_y, x, y, mc_x1, mc_y1, mc_r, num_steps, guidance_strength, **kw)
     if not dist.is_initialized():
         return x, y
     counts = [shard_bounds(B, world, r)[1] - shard_bounds(B, world, r)[0] for r in range(world)]
@@ -198,12 +203,13 @@ def make_sharded_sampler(shape_x, shape_y, backend=None, group=None, gather="all
     launchers do -- and ``sharded_paired_sampler`` slices its rows: consecutive calls consume one generator
     stream exactly like the reference's sweep (evaluate_mnist_svhn.py:80: one seeding, no re-seed)."""
     def sampler(fm_x, fm_y, ratio_estimator=None, guidance_method='none', guidance_strength=0.0, num_samples=16,
-                num_steps=100, device='cuda', mc_batch_size=64):
+                num_steps=100, device='cuda', mc_batch_size=64, solver='euler'):
         guided = guidance_method == 'mc_feng' and ratio_estimator is not None
         x0 = torch.randn(num_samples, *shape_x)
         y0 = torch.randn(num_samples, *shape_y)
         mx = torch.randn(mc_batch_size, *shape_x) if guided else None
         my = torch.randn(mc_batch_size, *shape_y) if guided else None
         return sharded_paired_sampler(fm_x, fm_y, ratio_estimator, guidance_method, guidance_strength, num_steps,
-                                      (x0, y0, mx, my), torch.device(device), backend=backend, group=group, gather=gather)
+                                      (x0, y0, mx, my), torch.device(device), backend=backend, group=group, gather=gather,
+                                      solver=solver)
     return sampler

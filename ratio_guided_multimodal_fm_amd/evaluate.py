@@ -49,8 +49,12 @@ def evaluate_coherence(samples_x, samples_y, classifier, device, transform_type=
 
 
 def run_sweep(fm_x, fm_y, make_ratio, classifier, methods, strengths, num_samples, num_steps, device,
-              mc_batch_size, transform_type, sampler=sample_bimodal_guided):
-    """The reference's nested loop (:165-222). `make_ratio()` returns a fresh ratio estimator or None."""
+              mc_batch_size, transform_type, sampler=sample_bimodal_guided, solver='euler'):
+    """The reference's nested loop (:165-222). `make_ratio()` returns a fresh ratio estimator or None.
+    `solver` ('euler' | 'midpoint') goes to `sampler` as a keyword when it is not the default."""
+    from ._lib import solver_id
+    solver_id(solver)
+    kw = {'solver': solver} if solver != 'euler' else {}
     results = []
     for method in methods:
         for strength in strengths:
@@ -59,7 +63,7 @@ def run_sweep(fm_x, fm_y, make_ratio, classifier, methods, strengths, num_sample
             ratio = make_ratio() if method != 'none' else None
             if method != 'none' and ratio is None:
                 continue
-            xs, ys = sampler(fm_x, fm_y, ratio, method, strength, num_samples, num_steps, device, mc_batch_size)
+            xs, ys = sampler(fm_x, fm_y, ratio, method, strength, num_samples, num_steps, device, mc_batch_size, **kw)
             metrics = evaluate_coherence(xs, ys, classifier, device, transform_type)
             results.append({'method': method, 'guidance_strength': strength, 'transform_type': transform_type,
                             **metrics})
@@ -103,7 +107,7 @@ def main(argv=None):
         return r
 
     results = run_sweep(fm_x, fm_y, make_ratio, classifier, args.guidance_methods, args.guidance_strengths,
-                        args.num_samples, args.num_steps, device, args.mc_batch_size, args.transform_type)
+                        args.num_samples, args.num_steps, device, args.mc_batch_size, args.transform_type, solver=args.solver)
     os.makedirs('outputs', exist_ok=True)
     out = 'outputs/evaluation_results.json'
     with open(out, 'w') as f:

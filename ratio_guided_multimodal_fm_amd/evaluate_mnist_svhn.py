@@ -47,7 +47,9 @@ def evaluate_conditional_coherence(condition, samples, given, mnist_classifier, 
     agree: `condition` [B, ...] are the images `samples` [B, ...] were generated for (``sample_conditional``), `given`
     ('mnist' or 'svhn') names the condition's modality.  With ``samples=None`` they are generated here:
     ``sample_conditional(fm_target, ratio_estimator, condition, given, guidance_method=guidance_method,
-    **sampler_kwargs)`` ('mc_feng' or 'grad_log_ratio'; num_steps, guidance_strength, mc_batch_size as keywords)."""
+    **sampler_kwargs)`` ('mc_feng' or 'grad_log_ratio'; num_steps, guidance_strength, mc_batch_size, solver as keywords)."""
+    from ._lib import solver_id
+    solver_id(sampler_kwargs.get('solver', 'euler'))
     if given not in ('mnist', 'svhn'):
         raise ValueError(f"given must be 'mnist' or 'svhn', got {given!r}")
     if samples is None:
@@ -63,8 +65,12 @@ def evaluate_conditional_coherence(condition, samples, given, mnist_classifier, 
 
 
 def run_sweep(fm_mnist, fm_svhn, make_ratio, mnist_classifier, svhn_classifier, methods, strengths,
-              num_samples, num_steps, device, mc_batch_size, sampler=sample_bimodal_guided_mnist_svhn):
-    """The reference's nested loop (:130-183). `make_ratio()` returns a fresh ratio estimator or None."""
+              num_samples, num_steps, device, mc_batch_size, sampler=sample_bimodal_guided_mnist_svhn, solver='euler'):
+    """The reference's nested loop (:130-183). `make_ratio()` returns a fresh ratio estimator or None.
+    `solver` ('euler' | 'midpoint') goes to `sampler` as a keyword when it is not the default."""
+    from ._lib import solver_id
+    solver_id(solver)
+    kw = {'solver': solver} if solver != 'euler' else {}
     results = []
     for method in methods:
         for strength in strengths:
@@ -74,7 +80,7 @@ def run_sweep(fm_mnist, fm_svhn, make_ratio, mnist_classifier, svhn_classifier, 
             if method != 'none' and ratio is None:
                 continue
             xs, ys = sampler(fm_mnist, fm_svhn, ratio, method, strength, num_samples, num_steps, device,
-                             mc_batch_size)
+                             mc_batch_size, **kw)
             metrics = evaluate_coherence(xs, ys, mnist_classifier, svhn_classifier, device)
             results.append({'method': method, 'guidance_strength': strength, 'experiment': 'mnist_svhn',
                             **metrics})
@@ -93,6 +99,8 @@ def main(argv=None):
     p.add_argument('--num_steps', type=int, default=100)
     p.add_argument('--device', type=str, default='cuda')
     p.add_argument('--seed', type=int, default=42)
+    p.add_argument('--solver', type=str, default='euler', choices=['euler', 'midpoint'],
+                   help="ODE solver of every sampler loop: 'midpoint' (explicit midpoint rule, second order) takes two network evaluations per step")
     p.add_argument('--sharded', action='store_true',
                    help='rows sharded over the ranks of a torch.distributed.run launch (one process per GPU, RCCL)')
     args = p.parse_args(argv)
@@ -135,7 +143,7 @@ def main(argv=None):
 
     results = run_sweep(fm_mnist, fm_svhn, make_ratio, mnist_clf, svhn_clf, args.guidance_methods,
                         args.guidance_strengths, args.num_samples, args.num_steps, device, args.mc_batch_size,
-                        sampler=sampler)
+                        sampler=sampler, solver=args.solver)
     if args.sharded:
         import torch.distributed as dist
         if dist.is_initialized():

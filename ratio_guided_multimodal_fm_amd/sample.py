@@ -36,6 +36,8 @@ def add_common_args(p, mc_default):
     p.add_argument('--device', type=str, default='cuda')
     p.add_argument('--model', type=str, default='unet', choices=['unet', 'original'])
     p.add_argument('--seed', type=int, default=42)
+    p.add_argument('--solver', type=str, default='euler', choices=['euler', 'midpoint'],
+                   help="ODE solver of every sampler loop: 'midpoint' (explicit midpoint rule, second order) takes two network evaluations per step (U-Net nets: not with --model original)")
 
 
 def main(argv=None):
@@ -78,7 +80,7 @@ def main(argv=None):
 
     print(f"\nSampling {args.num_samples} pairs...")
     xs, ys = sample_bimodal_guided(fm_x, fm_y, ratio, args.guidance_method, args.guidance_strength,
-                                   args.num_samples, args.num_steps, device, args.mc_batch_size)
+                                   args.num_samples, args.num_steps, device, args.mc_batch_size, solver=args.solver)
     os.makedirs('outputs', exist_ok=True)
     out = f"outputs/samples_{args.guidance_method}_gamma{args.guidance_strength}_{args.transform_type}.pt"
     torch.save({'x': xs.cpu(), 'y': ys.cpu()}, out)

@@ -18,10 +18,10 @@ from .utils.flow_utils import paired_sampler, sample_conditional
 
 def sample_bimodal_guided_mnist_svhn(fm_mnist, fm_svhn, ratio_estimator=None, guidance_method='none',
                                      guidance_strength=0.0, num_samples=16, num_steps=100,
-                                     device='cuda', mc_batch_size=64):
+                                     device='cuda', mc_batch_size=64, solver='euler'):
     """Returns ``(samples_mnist [n,1,32,32], samples_svhn [n,3,32,32])`` on `device`."""
     return paired_sampler(fm_mnist, fm_svhn, ratio_estimator, guidance_method, guidance_strength,
-                          num_samples, num_steps, device, mc_batch_size, (1, 32, 32), (3, 32, 32))
+                          num_samples, num_steps, device, mc_batch_size, (1, 32, 32), (3, 32, 32), solver=solver)
 
 
 def load_condition(path, shape):
@@ -47,6 +47,8 @@ def main(argv=None):
     p.add_argument('--num_steps', type=int, default=100)
     p.add_argument('--device', type=str, default='cuda')
     p.add_argument('--seed', type=int, default=42)
+    p.add_argument('--solver', type=str, default='euler', choices=['euler', 'midpoint'],
+                   help="ODE solver of every sampler loop: 'midpoint' (explicit midpoint rule, second order) takes two network evaluations per step")
     p.add_argument('--sharded', action='store_true',
                    help='rows sharded over the ranks of a torch.distributed.run launch (one process per GPU, RCCL); '
                         'e.g. BASELINE configs[3]: --nproc-per-node 8 ... --sharded --num_samples 4096 '
@@ -107,7 +109,7 @@ def main(argv=None):
         method = 'grad_log_ratio' if args.guidance_method == 'grad_log_ratio' else 'mc_feng'
         out_t = sample_conditional(target, ratio, condition.to(device), 'x' if args.given == 'mnist' else 'y',
                                    args.num_steps, args.guidance_strength, args.mc_batch_size, device=device,
-                                   guidance_method=method)
+                                   guidance_method=method, solver=args.solver)
         os.makedirs('outputs/mnist_svhn', exist_ok=True)
         tag = '_grad_log_ratio' if method == 'grad_log_ratio' else ''
         out = f"outputs/mnist_svhn/samples_given_{args.given}{tag}_gamma{args.guidance_strength}.pt"
@@ -117,7 +119,7 @@ def main(argv=None):
 
     print(f"\nSampling {args.num_samples} pairs...")
     xs, ys = sampler(fm_mnist, fm_svhn, ratio, args.guidance_method, args.guidance_strength, args.num_samples,
-                     args.num_steps, device, args.mc_batch_size)
+                     args.num_steps, device, args.mc_batch_size, **({'solver': args.solver} if args.solver != 'euler' else {}))
     if args.sharded:
         import torch.distributed as dist
         if dist.is_initialized():

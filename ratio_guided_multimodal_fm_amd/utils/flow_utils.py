@@ -12,6 +12,7 @@ import torch
 import torch.nn.functional as F
 
 from .. import _engine
+from .._lib import solver_id as _solver_id
 
 
 def _device(device):
@@ -44,12 +45,14 @@ class CFMSchedule:
         t = t.view(x_1.shape[0], *([1] * (x_1.dim() - 1)))
         return (1 - t) * x_0 + t * x_1, x_1 - x_0
 
-    def sample(self, model, num_samples, num_steps=100, device='cuda'):
-        """x0 ~ N(0, I) [n,1,28,28]; num_steps explicit Euler steps (reference :69-100)."""
+    def sample(self, model, num_samples, num_steps=100, device='cuda', solver='euler'):
+        """x0 ~ N(0, I) [n,1,28,28]; num_steps explicit Euler steps (reference :69-100), or midpoint steps with
+        solver='midpoint' (two network evaluations each, second order; U-Net nets)."""
+        _engine._solver(solver, model)
         model.eval()
         dev = _device(device)
         x_t = torch.randn(num_samples, 1, 28, 28, device=dev)
-        return _engine.sample_single(model, x_t, num_steps)
+        return _engine.sample_single(model, x_t, num_steps, solver=solver)
 
 
 def _velocity_train(model, x_t, t):
@@ -83,12 +86,16 @@ def train_flow_matching_epoch(model, dataloader, optimizer, schedule, device, mo
 
 
 def paired_sampler(fm_x, fm_y, ratio_estimator, guidance_method, guidance_strength, num_samples,
-                   num_steps, device, mc_batch_size, shape_x, shape_y, noise=None, verbose=True):
+                   num_steps, device, mc_batch_size, shape_x, shape_y, noise=None, verbose=True, solver='euler'):
     """Shared body of both paired samplers.
 
     `noise` = (x0, y0, mc_x0, mc_y0) overrides the generator draws (parity
     tests upload CPU-generated noise); tensors are copied, never modified.
+
+    `solver` = 'euler' | 'midpoint' integrates EVERY loop of the call (the MC pre-phase and the main loop) with that
+    solver, `num_steps` steps each; the noise draws and their order do not depend on it.  'midpoint' needs U-Net nets.
     """
+    _engine._solver(solver, fm_x, fm_y)
     fm_x.eval()
     fm_y.eval()
     if ratio_estimator is not None:
@@ -116,7 +123,7 @@ def paired_sampler(fm_x, fm_y, ratio_estimator, guidance_method, guidance_streng
         else:
             mc_x1 = noise[2].to(dev, copy=True).contiguous()
             mc_y1 = noise[3].to(dev, copy=True).contiguous()
-        _engine.sample_two_streams(fm_x, mc_x1, fm_y, mc_y1, num_steps)
+        _engine.sample_two_streams(fm_x, mc_x1, fm_y, mc_y1, num_steps, solver=solver)
         if verbose:
             print(f"  Generated MC samples: x shape={mc_x1.shape}, y shape={mc_y1.shape}")
         if ratio_estimator.loss_type not in ("disc", "rulsif"):
@@ -131,14 +138,14 @@ def paired_sampler(fm_x, fm_y, ratio_estimator, guidance_method, guidance_streng
         # reference accepts only 'none' / 'mc_feng' and has no code for this mode; see rgfm_sample_pair_grad.
         if ratio_estimator.loss_type not in ("disc", "rulsif"):
             raise ValueError(f"Unknown loss_type: {ratio_estimator.loss_type}")
-        _engine.sample_pair_grad(fm_x, fm_y, ratio_estimator, x_t, y_t, num_steps, guidance_strength)
+        _engine.sample_pair_grad(fm_x, fm_y, ratio_estimator, x_t, y_t, num_steps, guidance_strength, solver=solver)
         return x_t, y_t
-    _engine.sample_pair(fm_x, fm_y, x_t, y_t, mc_x1, mc_y1, mc_ratios, num_steps, guidance_strength)
+    _engine.sample_pair(fm_x, fm_y, x_t, y_t, mc_x1, mc_y1, mc_ratios, num_steps, guidance_strength, solver=solver)
     return x_t, y_t
 
 
 def sample_conditional(fm_target, ratio_estimator, condition, given='x', num_steps=100, guidance_strength=1.0,
-                       mc_batch_size=256, mc_samples=None, device=None, guidance_method='mc_feng'):
+                       mc_batch_size=256, mc_samples=None, device=None, guidance_method='mc_feng', solver='euler'):
     """Partners for `condition` in the other modality: one sample of `fm_target`'s modality per condition image.
 
     ``given='x'``: `condition` is the estimator's x argument and the target is its y; ``given='y'`` the other way
@@ -157,10 +164,14 @@ def sample_conditional(fm_target, ratio_estimator, condition, given='x', num_ste
     ignored).  The condition's encoder and its half of the first score Linear run once, before the loop
     (``rgfm_ratio_cond_prepare``); each step runs the target's encoder alone, forward and reverse.
 
+    ``solver='midpoint'`` integrates every loop of the call (the MC pre-phase too) with the explicit midpoint rule
+    (``rgfm_sample_*_ode``); the draws and their order are those of ``'euler'``.
+
     Returns the samples ``[len(condition), C, H, W]`` on the device.  U-Net targets only; ``--sharded`` launches have
     no conditional form yet.
     """
     from .._lib import RgfmError
+    _solver_id(solver)
     if given not in ('x', 'y'):
         raise ValueError(f"given must be 'x' or 'y', got {given!r}")
     if guidance_method not in ('mc_feng', 'grad_log_ratio'):
@@ -178,10 +189,10 @@ def sample_conditional(fm_target, ratio_estimator, condition, given='x', num_ste
     if guidance_method == 'grad_log_ratio':
         s_t = torch.randn(condition.shape[0], *shape, device=dev)
         ctx = ratio_estimator._engine.cond_prepare(condition, given, shape)
-        return _engine.sample_cond_grad(fm_target, ratio_estimator, s_t, ctx, given, num_steps, guidance_strength)
+        return _engine.sample_cond_grad(fm_target, ratio_estimator, s_t, ctx, given, num_steps, guidance_strength, solver=solver)
     if mc_samples is None:
         mc = torch.randn(mc_batch_size, *shape, device=dev)
-        _engine.sample_single(fm_target, mc, num_steps)
+        _engine.sample_single(fm_target, mc, num_steps, solver=solver)
     else:
         mc = mc_samples.to(dev, torch.float32).contiguous()
     s_t = torch.randn(condition.shape[0], *shape, device=dev)
@@ -189,12 +200,12 @@ def sample_conditional(fm_target, ratio_estimator, condition, given='x', num_ste
         ratios = ratio_estimator.cross_log_ratio(condition, mc).exp()
     else:
         ratios = ratio_estimator.cross_log_ratio(mc, condition).exp().T.contiguous()
-    return _engine.sample_cond(fm_target, s_t, mc, ratios, num_steps, guidance_strength)
+    return _engine.sample_cond(fm_target, s_t, mc, ratios, num_steps, guidance_strength, solver=solver)
 
 
 def sample_bimodal_guided(fm_x, fm_y, ratio_estimator=None, guidance_method='none',
                           guidance_strength=0.0, num_samples=16, num_steps=100, device='cuda',
-                          mc_batch_size=64):
+                          mc_batch_size=64, solver='euler'):
     """Pairs of 1x28x28 images, optional mc_feng guidance (reference :178-375).
 
     Returns ``(samples_x [n,1,28,28], samples_y [n,1,28,28])`` on `device`.
@@ -204,4 +215,4 @@ def sample_bimodal_guided(fm_x, fm_y, ratio_estimator=None, guidance_method='non
     reproduced.
     """
     return paired_sampler(fm_x, fm_y, ratio_estimator, guidance_method, guidance_strength,
-                          num_samples, num_steps, device, mc_batch_size, (1, 28, 28), (1, 28, 28))
+                          num_samples, num_steps, device, mc_batch_size, (1, 28, 28), (1, 28, 28), solver=solver)
