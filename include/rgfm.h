@@ -169,6 +169,46 @@ int rgfm_unet_dropout_mask(rgfm_unet* h, int block, uint64_t seed, float p_drop,
 int rgfm_unet_update_params(rgfm_unet* h, const float* params_dev, size_t n_floats, rgfm_stream_t stream);
 
 /* ------------------------------------------------------------------------
+ * Exact log-likelihood of images under the velocity U-Net.  Added functions only: the ABI
+ * version is unchanged.  All of it runs on the exact-fp32 training forward (p_drop = 0) and on the DATA-ONLY reverse
+ * walk; the two-plane eval arithmetic is not used.  Stream-ordered, nothing allocated or synchronised, nothing
+ * graph-captured, every reduction in a fixed order (two calls on the same inputs give the same bits, a row's result
+ * depends on its own row only).
+ *
+ * rgfm_unet_vjp: dx_out = J^T u, J = dv/dx of the forward whose state rgfm_unet_forward_train left in `ws` (same ws,
+ * same size query).  It is rgfm_unet_backward's walk restricted to what reaches x: no weight-gradient GEMMs and split-K
+ * reductions, no bias / norm-parameter / time-path gradients, no dparams memset.  dx_out has the bits of
+ * rgfm_unet_backward's dx_out for dv = u.  The saved state is left untouched: the call may be repeated on it.
+ *
+ * rgfm_unet_divergence: one forward v = model(x, t) (t_count in {1, batch}) and n_probes reverse walks;
+ *     div_out[b] = (1 / K) sum_k <eps_k[b], J^T eps_k[b]>,   eps[K][B][C][H][W] supplied by the caller
+ * (Hutchinson's estimate of the trace of J per row; the d probes sqrt(d) e_i give the exact trace).  v_out is optional
+ * (may be null).  n_probes = 0 is a plain exact-fp32 forward: div_out is untouched (and may be null, as eps).
+ *
+ * rgfm_unet_log_prob: data x at t = 1 is integrated BACKWARDS to z = x(0) along dx/dt = v(x, t), and
+ *     logp_out[b] = log N(z_b; 0, I) - A[b],   A = integral over [0, 1] of div v(x(t), t) dt.
+ * dt = 1 / num_steps; for i = num_steps - 1 ... 0, t_hi = (i + 1) dt, scalars in double and rounded to fp32 where a
+ * tensor op consumes them:
+ *     RGFM_SOLVER_EULER:     k = v(x, t_hi), D = div(x, t_hi);                                x -= dt k,  A += dt D
+ *     RGFM_SOLVER_MIDPOINT:  k1 = v(x, t_hi), x_mid = x - (dt / 2) k1, t_m = t_hi - dt / 2,
+ *                            k2 = v(x_mid, t_m), D = div(x_mid, t_m);                         x -= dt k2, A += dt D
+ * (midpoint: the divergence is taken at the second stage only; stage 1 is a forward without a reverse walk).  Velocity
+ * and divergence of a stage come from ONE forward; the probes are fixed for the whole call; the library draws nothing.
+ * x [B,C,H,W] is read-only, z_out [B,C,H,W] and logp_out [B] are written.  n_probes = 0 makes the call an encoder:
+ * only z_out is written (the same bits as with probes), logp_out and eps may be null.  At most 4096 Euler steps or
+ * 2048 midpoint steps per call.  Argument errors are reported before anything is enqueued, outputs untouched: null
+ * pointers, unknown solver, n_probes < 0, num_steps < 1 or above the cap, batch < 1 -> RGFM_EINVAL; a short workspace
+ * -> RGFM_ENOMEM. */
+int rgfm_unet_vjp(rgfm_unet* h, const float* u, float* dx_out, int batch, void* ws, size_t ws_bytes,
+                  rgfm_stream_t stream);
+int rgfm_unet_divergence_workspace_bytes(const rgfm_unet* h, int batch, size_t* bytes);
+int rgfm_unet_divergence(rgfm_unet* h, const float* x, const float* t_dev, int t_count, const float* eps, int n_probes,
+                         float* v_out, float* div_out, int batch, void* ws, size_t ws_bytes, rgfm_stream_t stream);
+int rgfm_unet_log_prob_workspace_bytes(const rgfm_unet* h, int batch, int solver, int n_probes, size_t* bytes);
+int rgfm_unet_log_prob(rgfm_unet* h, const float* x, const float* eps, int n_probes, int num_steps, int solver,
+                       float* z_out, float* logp_out, int batch, void* ws, size_t ws_bytes, rgfm_stream_t stream);
+
+/* ------------------------------------------------------------------------
  * Density-ratio estimators.  Replaces RatioEstimatorMNISTSVHN
  * (src/models/ratio_flexible.py:305-385), RatioEstimator
  * (src/models/ratio_estimator.py:96-191) and FlexibleRatioEstimator

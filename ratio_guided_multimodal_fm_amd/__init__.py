@@ -10,13 +10,16 @@ every ``forward`` / ``sample*`` call goes through the C-ABI library
 library is missing, or a tensor is not on a HIP device, the call raises.
 """
 from . import models, utils  # noqa: F401
-from .utils.flow_utils import CFMSchedule, sample_bimodal_guided, sample_conditional  # noqa: F401
+from .utils.flow_utils import (CFMSchedule, bits_per_dim, joint_log_prob, sample_bimodal_guided,  # noqa: F401
+                               sample_conditional)
 from .sample_mnist_svhn import sample_bimodal_guided_mnist_svhn  # noqa: F401
 
 __all__ = [
     "models",
     "utils",
     "CFMSchedule",
+    "bits_per_dim",
+    "joint_log_prob",
     "sample_bimodal_guided",
     "sample_bimodal_guided_mnist_svhn",
     "sample_conditional",

@@ -321,6 +321,73 @@ class UNetEngine(_VelocityEngine):
         p = m.dropout_p() if m.training else 0.0
         return _UNetTrainFn.apply(self, x, t, float(p), *m.parameters())
 
+    # ---- likelihood: J^T u, divergence, log p(x) -------------------------
+    def _check_xt(self, x, t):
+        m = self._module()
+        _require_hip(x, t)
+        self._check_input(m, x)
+        t = t.reshape(-1)
+        if t.numel() not in (1, x.shape[0]):
+            raise _lib.RgfmError(f"t must have 1 or {x.shape[0]} elements, got {t.numel()}")
+        return x.contiguous(), t.contiguous()
+
+    def _check_probes(self, x, eps):
+        _require_hip(eps)
+        if eps.dim() != 5 or tuple(eps.shape[1:]) != tuple(x.shape) or eps.device != x.device:
+            raise _lib.RgfmError(f"probes of shape [K,{','.join(map(str, x.shape))}] on {x.device} expected, got "
+                                 f"{tuple(eps.shape)} on {eps.device}")
+        return eps.contiguous()
+
+    def linearize(self, x, t):
+        """One exact-fp32 forward (no dropout, whatever the module's mode) that keeps its state: an object with `.v`
+        = model(x, t) and `.vjp(u)` = J^T u, J = dv/dx, as often as wanted (rgfm_unet_forward_train / rgfm_unet_vjp)."""
+        x, t = self._check_xt(x, t)
+        return _Linearization(self, x, t)
+
+    def divergence(self, x, t, eps, div_out=None):
+        """(v, div): v = model(x, t) on the exact-fp32 forward and div[b] = mean_k <eps_k[b], J^T eps_k[b]> for the probes
+        eps [K, B, C, H, W] (rgfm_unet_divergence).  K = 0: a plain forward, div (or the given `div_out`) untouched."""
+        x, t = self._check_xt(x, t)
+        eps = self._check_probes(x, eps)
+        B, K, dev = x.shape[0], eps.shape[0], x.device
+        v = torch.empty_like(x)
+        div = torch.zeros(B, device=dev) if div_out is None else div_out
+        if B == 0:
+            return v, div
+        L = _lib.lib()
+        with torch.cuda.device(dev):
+            h = self.handle(dev)
+            ws, nb = self.workspace("rgfm_unet_divergence_workspace_bytes", B, dev)
+            _lib.check(L.rgfm_unet_divergence(h, _ptr(x), _ptr(t), t.numel(), _ptr(eps), K, _ptr(v), _ptr(div), B,
+                                              _ptr(ws), nb, _stream(dev)))
+        return v, div
+
+    def log_prob(self, x, eps, num_steps, solver):
+        """(logp [B], z [B, C, H, W]) of rgfm_unet_log_prob for data x and probes eps [K, B, C, H, W]; eps None or K = 0:
+        the encoder, (None, z)."""
+        sid = _lib.solver_id(solver)
+        m = self._module()
+        _require_hip(x)
+        self._check_input(m, x)
+        x = x.contiguous()
+        B, dev = x.shape[0], x.device
+        K = 0 if eps is None else eps.shape[0]
+        if K:
+            eps = self._check_probes(x, eps)
+        z = torch.empty_like(x)
+        logp = torch.empty(B, device=dev) if K else None
+        if B == 0:
+            return logp, z
+        L = _lib.lib()
+        with torch.cuda.device(dev):
+            h = self.handle(dev)
+            n = ctypes.c_size_t()
+            _lib.check(L.rgfm_unet_log_prob_workspace_bytes(h, B, sid, K, ctypes.byref(n)))
+            ws = self._ws.get(n.value, dev)
+            _lib.check(L.rgfm_unet_log_prob(h, _ptr(x), _ptr(eps if K else None), K, int(num_steps), sid, _ptr(z),
+                                            _ptr(logp), B, _ptr(ws), n.value, _stream(dev)))
+        return logp, z
+
     def dropout_mask(self, block, seed, p, batch, device):
         """Keep decisions (1 / 0) of ResBlock `block` for `batch` rows: [batch, cout, H, W] (rgfm_unet_dropout_mask)."""
         m = self._module()
@@ -390,6 +457,45 @@ class UNetEngine(_VelocityEngine):
             finally:
                 _lib.check(L.rgfm_unet_set_trace(h, 0))
         return out, acts
+
+
+class _Linearization:
+    """The saved state of one exact-fp32 U-Net forward at (x, t) (UNetEngine.linearize).  It owns its workspace and
+    belongs to the parameters of its forward: take a new one after the module's parameters change."""
+
+    def __init__(self, engine, x, t):
+        dev = x.device
+        self.engine, self.shape, self.B = engine, x.shape, x.shape[0]
+        self.v = torch.empty_like(x)
+        self.ws, self.nbytes = None, 0
+        if self.B == 0:
+            return
+        L = _lib.lib()
+        with torch.cuda.device(dev):
+            h = engine.handle(dev)
+            n = ctypes.c_size_t()
+            _lib.check(L.rgfm_unet_train_workspace_bytes(h, self.B, ctypes.byref(n)))
+            self.ws, self.nbytes = torch.empty(n.value, dtype=torch.uint8, device=dev), n.value
+            _lib.check(L.rgfm_unet_forward_train(h, _ptr(x), _ptr(t), t.numel(), _ptr(self.v), self.B, 0.0, 0,
+                                                 _ptr(self.ws), n.value, _stream(dev)))
+        self.handle = h.value
+
+    def vjp(self, u):
+        """J^T u [B, C, H, W]: the data-only reverse walk (rgfm_unet_vjp)."""
+        _require_hip(u)
+        if tuple(u.shape) != tuple(self.shape) or u.device != self.v.device:
+            raise _lib.RgfmError(f"u of shape {tuple(self.shape)} on {self.v.device} expected, got {tuple(u.shape)} on {u.device}")
+        u = u.contiguous()
+        g = torch.empty_like(u)
+        if self.B == 0:
+            return g
+        dev = u.device
+        with torch.cuda.device(dev):
+            h = self.engine.handle(dev)
+            if h.value != self.handle:
+                raise _lib.RgfmError("the module was rebuilt since this forward; call linearize again")
+            _lib.check(_lib.lib().rgfm_unet_vjp(h, _ptr(u), _ptr(g), self.B, _ptr(self.ws), self.nbytes, _stream(dev)))
+        return g
 
 
 class _UNetTrainFn(torch.autograd.Function):

@@ -57,6 +57,13 @@ SIGNATURES = {
     "rgfm_unet_forward_train": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_void_p, c_int, c_float, c_uint64,
                                         c_void_p, c_size_t, c_void_p]),
     "rgfm_unet_backward": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_void_p, c_size_t, c_void_p]),
+    "rgfm_unet_vjp": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_void_p, c_size_t, c_void_p]),
+    "rgfm_unet_divergence_workspace_bytes": (c_int, [c_void_p, c_int, P(c_size_t)]),
+    "rgfm_unet_divergence": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_void_p, c_int, c_void_p, c_void_p, c_int,
+                                     c_void_p, c_size_t, c_void_p]),
+    "rgfm_unet_log_prob_workspace_bytes": (c_int, [c_void_p, c_int, c_int, c_int, P(c_size_t)]),
+    "rgfm_unet_log_prob": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_void_p, c_void_p, c_int,
+                                   c_void_p, c_size_t, c_void_p]),
     "rgfm_unet_dropout_mask": (c_int, [c_void_p, c_int, c_uint64, c_float, c_int, c_void_p]),
     "rgfm_unet_update_params": (c_int, [c_void_p, c_void_p, c_size_t, c_void_p]),
     "rgfm_ratio_param_floats": (c_int, [P(RatioDesc), P(c_size_t)]),

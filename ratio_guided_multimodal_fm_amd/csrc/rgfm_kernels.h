@@ -511,6 +511,15 @@ void launch_ug_split_add(const float* src, float* d0, float* d1, int B, int C0, 
 void launch_ug_mask(float* out, size_t n, uint64_t seed, int block, float p, hipStream_t s);
 void launch_ug_header(unsigned* hdr, float p, uint64_t seed, hipStream_t s);
 
+// ---- likelihood path of the U-Net (unet_logp.hip; fixed-order reductions, one workgroup per row)
+// acc[b] = (accumulate ? acc[b] : 0) + scale <a[b, :], g[b, :]>, rows of d floats
+void launch_ul_rowdot(const float* a, const float* g, int B, int d, float scale, int accumulate, float* acc,
+                      hipStream_t s);
+void launch_ul_step(const float* src, const float* k, float c, size_t n, float* dst, hipStream_t s);  // dst = src - c k
+// stage times of the reverse loop in the order it takes them: Euler tt[j] = (N - j) / N, midpoint also tt[2j + 1] = t_hi - dt / 2
+void launch_ul_times(float* tt, int num_steps, int midpoint, hipStream_t s);
+void launch_ul_gauss_logp(const float* z, const float* A, int B, int d, float* logp, hipStream_t s);  // log N(z_b; 0, I) - A[b]
+
 // ---- training pass of the ratio estimators (ratio_train.hip; NCHW fp32)
 // A norm in front of a SiLU: z [B][C][H][W] and its (mean, rstd) pairs -- groups == 0: BatchNorm, mr[C][2];
 // groups > 0: GroupNorm, mr[B][groups][2].

@@ -253,7 +253,8 @@ void launch_ug_gn_act(const UgAct& a, hipStream_t s) {
 
 // Backward of out = drop(silu(gamma xhat + beta)): a.out is dL/d(out) (read), the input gradient goes to d0 / d1 (the
 // channel ranges of the two sources; acc0 / acc1: add instead of overwrite), and pg / pb [B][C] receive the per-sample
-// dgamma / dbeta partials (summed over b by ug_colsum_kernel).  One workgroup per (b, g).
+// dgamma / dbeta partials (summed over b by ug_colsum_kernel; pg null: not wanted, the data-only walk of rgfm_unet_vjp).
+// One workgroup per (b, g).
 __global__ __launch_bounds__(256) void ug_gn_act_bwd_kernel(UgAct a, const float* dout, float* d0, float* d1, int acc0,
                                                             int acc1, float* pg, float* pb) {
   __shared__ float red[256];
@@ -284,7 +285,7 @@ __global__ __launch_bounds__(256) void ug_gn_act_bwd_kernel(UgAct a, const float
     }
     sg = ug_block_sum(sg, red);
     sb = ug_block_sum(sb, red);
-    if (threadIdx.x == 0) pg[(size_t)b * C + c] = sg, pb[(size_t)b * C + c] = sb;
+    if (threadIdx.x == 0 && pg) pg[(size_t)b * C + c] = sg, pb[(size_t)b * C + c] = sb;
     s1 += a.gamma[c] * sb;  // sum of dy gamma
     s2 += a.gamma[c] * sg;  // sum of dy gamma xhat
   }

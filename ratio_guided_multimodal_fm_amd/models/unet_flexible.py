@@ -121,6 +121,22 @@ class FlexibleUNet(nn.Module):
         HIP backward (rgfm_unet_forward_train / rgfm_unet_backward).  Dropout applies while ``self.training``."""
         return self._engine.forward_train(x, t)
 
+    def linearize(self, x, t):
+        """One exact-fp32 forward at (x, t) that keeps its state: ``.v`` = v(x, t) and ``.vjp(u)`` = J^T u with
+        J = dv/dx, as often as wanted (rgfm_unet_forward_train with no dropout / rgfm_unet_vjp)."""
+        return self._engine.linearize(x, t)
+
+    def vjp(self, x, t, u):
+        """J^T u for J = dv/dx at (x, t): the HIP reverse walk restricted to the path to x (no parameter gradients).
+        What ``torch.autograd.grad(model.forward_train(x, t), x, u)`` returns in eval mode, to the bit."""
+        return self._engine.linearize(x, t).vjp(u)
+
+    def divergence(self, x, t, eps):
+        """``(v, div)``: v(x, t) and the Hutchinson estimate ``div[b] = mean_k <eps_k[b], J^T eps_k[b]>`` of the
+        divergence of v at x for the probes ``eps [K, B, C, H, W]`` (rgfm_unet_divergence; one forward, K reverse
+        walks).  The K = d probes ``sqrt(d) e_i`` give the exact trace."""
+        return self._engine.divergence(x, t, eps)
+
     def _resblocks(self):
         return list(self.encoder_blocks) + [self.middle_block1, self.middle_block2] + list(self.decoder_blocks)
 

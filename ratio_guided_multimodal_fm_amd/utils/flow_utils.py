@@ -6,8 +6,12 @@ loops, the U-Net evaluations, the ratio estimator and the MC guidance all run
 inside librgfm_hip.so (one C-ABI call per phase).  ``sample_conditional`` (new: the reference
 has no conditional sampler) integrates one net given images of the other modality.  ``CFMSchedule.add_noise``
 (``:40-67``) and ``train_flow_matching_epoch`` (``:103-156``) train a
-``FlexibleUNet`` through its HIP backward (``FlexibleUNet.forward_train``).
+``FlexibleUNet`` through its HIP backward (``FlexibleUNet.forward_train``).  ``CFMSchedule.log_prob`` / ``encode``,
+``bits_per_dim`` and ``joint_log_prob`` (new: the reference has no likelihood) integrate the flow backwards with the
+divergence of v accumulated along the path (``rgfm_unet_log_prob``).
 """
+import math
+
 import torch
 import torch.nn.functional as F
 
@@ -53,6 +57,83 @@ class CFMSchedule:
         dev = _device(device)
         x_t = torch.randn(num_samples, 1, 28, 28, device=dev)
         return _engine.sample_single(model, x_t, num_steps, solver=solver)
+
+
+    def log_prob(self, model, x, num_steps=100, solver='midpoint', n_probes=1, generator=None, batch_size=128):
+        """``(logp [B], z [B, C, H, W])``: the log-density of the images `x` under the flow of `model`, and their
+        latents.  `x` (data, t = 1) is integrated backwards to ``z = x(0)`` in `num_steps` steps of `solver` while the
+        divergence of v is accumulated: ``logp = log N(z; 0, I) - int_0^1 div v dt`` (``rgfm_unet_log_prob``; exact
+        fp32 arithmetic, no dropout whatever the module's mode).  The divergence is Hutchinson's estimate over
+        `n_probes` Rademacher probes per image, drawn ONCE for the whole of `x` from `generator` (default: the
+        device's torch generator) and fixed along the path; the images are then processed in chunks of `batch_size`,
+        so the result does not depend on `batch_size`.  U-Net nets only."""
+        _check_likelihood_args(model, x, num_steps, solver, batch_size)
+        if not isinstance(n_probes, int) or n_probes < 1:
+            raise ValueError(f"n_probes must be an integer >= 1, got {n_probes!r} (encode() integrates without probes)")
+        dev = _device(x.device)
+        x = x.to(dev, torch.float32).contiguous()
+        gdev = dev if generator is None else generator.device
+        eps = torch.randint(0, 2, (n_probes, *x.shape), generator=generator, device=gdev).to(dev, torch.float32) * 2 - 1
+        logp, z = torch.empty(x.shape[0], device=dev), torch.empty_like(x)
+        for b in range(0, x.shape[0], batch_size):
+            e = min(b + batch_size, x.shape[0])
+            logp[b:e], z[b:e] = model._engine.log_prob(x[b:e], eps[:, b:e].contiguous(), num_steps, solver)
+        return logp, z
+
+    def encode(self, model, x, num_steps=100, solver='midpoint', batch_size=128):
+        """The latents ``z = x(0)`` of the images `x`: the backward integration of ``log_prob`` without probes (the
+        same bits as its `z`)."""
+        _check_likelihood_args(model, x, num_steps, solver, batch_size)
+        dev = _device(x.device)
+        x = x.to(dev, torch.float32).contiguous()
+        z = torch.empty_like(x)
+        for b in range(0, x.shape[0], batch_size):
+            e = min(b + batch_size, x.shape[0])
+            z[b:e] = model._engine.log_prob(x[b:e], None, num_steps, solver)[1]
+        return z
+
+
+def _check_likelihood_args(model, x, num_steps, solver, batch_size):
+    """Argument checks of log_prob / encode; all of them run before any device call."""
+    from .._lib import RgfmError
+    sid = _solver_id(solver)
+    cap = 2048 if sid else 4096
+    if not isinstance(num_steps, int) or not 1 <= num_steps <= cap:
+        raise ValueError(f"num_steps must be an integer in [1, {cap}] for solver={solver!r}, got {num_steps!r}")
+    if not isinstance(batch_size, int) or batch_size < 1:
+        raise ValueError(f"batch_size must be an integer >= 1, got {batch_size!r}")
+    if not isinstance(model._engine, _engine.UNetEngine):
+        raise RgfmError(f"the likelihood needs a U-Net velocity net (FlexibleUNet and its presets); "
+                        f"{type(model).__name__} has no HIP reverse walk to x alone")
+    shape = (model.in_channels, model.img_size, model.img_size)
+    if x.dim() != 4 or tuple(x.shape[1:]) != shape:
+        raise ValueError(f"x of shape [B,{','.join(map(str, shape))}] expected, got {tuple(x.shape)}")
+
+
+def bits_per_dim(logp, dims, data_range=2.0, levels=256):
+    """Bits per dimension of log-densities `logp` (nats, of data scaled to an interval of length `data_range` and
+    quantised to `levels` levels): ``-logp / (dims ln 2) + log2(levels / data_range)`` -- the change of variables back
+    to the integer grid; +7 bits for 8-bit images scaled to [-1, 1].  `logp`: tensor or number."""
+    if dims < 1 or data_range <= 0 or levels < 1:
+        raise ValueError(f"dims >= 1, data_range > 0 and levels >= 1 expected, got {dims!r}, {data_range!r}, {levels!r}")
+    return -logp / (dims * math.log(2.0)) + math.log2(levels / data_range)
+
+
+def joint_log_prob(fm_x, fm_y, ratio_estimator, x, y, num_steps=100, solver='midpoint', n_probes=1, generator=None,
+                   batch_size=128):
+    """``(joint, logp_x, logp_y, log_r)``, each ``[B]``: the log-density of the pairs ``(x_b, y_b)`` under the
+    ratio-corrected joint model ``p(x) p(y) r(x, y)``, ``joint = logp_x + logp_y + log_r`` with the marginal terms from
+    ``CFMSchedule.log_prob`` (x first, then y, both drawing from `generator`) and
+    ``log_r = ratio_estimator.log_ratio(x, y)``.  The ratio estimator is not normalised, so neither is the joint."""
+    if x.shape[0] != y.shape[0]:
+        raise ValueError(f"x and y must pair up: {x.shape[0]} and {y.shape[0]} images")
+    sched = CFMSchedule()
+    logp_x = sched.log_prob(fm_x, x, num_steps, solver, n_probes, generator, batch_size)[0]
+    logp_y = sched.log_prob(fm_y, y, num_steps, solver, n_probes, generator, batch_size)[0]
+    ratio_estimator.eval()
+    log_r = ratio_estimator.log_ratio(x.to(logp_x.device, torch.float32).contiguous(),
+                                      y.to(logp_x.device, torch.float32).contiguous()).reshape(-1)
+    return logp_x + logp_y + log_r, logp_x, logp_y, log_r
 
 
 def _velocity_train(model, x_t, t):
