@@ -467,6 +467,17 @@ int rgfm_sample_pair_ode(rgfm_unet* hx, rgfm_unet* hy, float* x_inout, float* y_
                          const float* mc_y1, const float* mc_ratios, int n_mc, int batch, int num_steps, double gamma,
                          int step_begin, int step_end, int solver, void* ws, size_t ws_bytes, rgfm_stream_t stream);
 int rgfm_sample_cond_ode_workspace_bytes(const rgfm_unet* h, int batch, int n_mc, int solver, size_t* bytes);
+/* Two independent unguided integrations in one call (the MC pre-phase of the paired sampler): x under hx and y under hy,
+ * each with its own row count, with the bits of two rgfm_sample_single_ode calls.  The two chains run side by side, x
+ * on `stream` and y on the device state's side stream (forked from and joined back into `stream`), enqueued step by
+ * step; the chain with less conv work per step (by the descriptors and row counts, not by argument position) is never
+ * more than one step ahead of the other (RGFM_PREPHASE_PRIO=0: one chain enqueued after the other, unpaced).  hx == hy
+ * is allowed.
+ * Added functions only: the ABI version is unchanged. */
+int rgfm_sample_two_workspace_bytes(const rgfm_unet* hx, const rgfm_unet* hy, int batch_x, int batch_y, int solver,
+                                    size_t* bytes);
+int rgfm_sample_two(rgfm_unet* hx, rgfm_unet* hy, float* x_inout, float* y_inout, int batch_x, int batch_y, int num_steps,
+                    int step_begin, int step_end, int solver, void* ws, size_t ws_bytes, rgfm_stream_t stream);
 int rgfm_sample_cond_ode(rgfm_unet* h, float* s_inout, const float* mc_set, const float* ratios, int n_mc, int batch,
                          int num_steps, double gamma, int step_begin, int step_end, int solver, void* ws,
                          size_t ws_bytes, rgfm_stream_t stream);
@@ -584,6 +595,10 @@ int rgfm_profile_reset(void);
  *   sum_ms   = plain sum of the launch durations (== busy_ms when nothing overlaps);
  *   launches, flops = launch count and the class's algorithmic work (FLOPs or bytes, see RGFM_KCLASS_*). */
 int rgfm_profile_read(int kclass, double* busy_ms, double* sum_ms, int64_t* launches, double* flops);
+/* Start of the class's first timed launch and end of its last one, in ms since the first timed launch after the latest
+ * reset (both 0 when the class has none).  The in- and out-conv classes are per modality (1 / 3 channels), so their
+ * spans tell when each net of a two-net call started and ended.  Added function only: the ABI version is unchanged. */
+int rgfm_profile_span(int kclass, double* first_start_ms, double* last_end_ms);
 
 /* Pre-creates the hipEvents of `launches` timed launches, so that none is created inside a timed region. */
 int rgfm_profile_reserve(int64_t launches);

@@ -1083,6 +1083,25 @@ def _sample_single(model, x, num_steps, step_begin=0, step_end=None, solver='eul
 _side_streams = {}
 
 
+def _sample_two(fm_x, x, fm_y, y, num_steps, solver):
+    sid = _solver(solver, fm_x, fm_y)
+    for m in (fm_x, fm_y):
+        m._engine._check_eval(m)
+    _require_hip(x, y)
+    if not (x.is_contiguous() and y.is_contiguous()):
+        raise _lib.RgfmError("x and y must be contiguous (they are updated in place)")
+    dev = x.device
+    L = _lib.lib()
+    with torch.cuda.device(dev):
+        hx, hy = fm_x._engine.handle(dev), fm_y._engine.handle(dev)
+        nb = ctypes.c_size_t()
+        _lib.check(L.rgfm_sample_two_workspace_bytes(hx, hy, x.shape[0], y.shape[0], sid, ctypes.byref(nb)))
+        ws = _sampler_ws.get(nb.value, dev)
+        _lib.check(L.rgfm_sample_two(hx, hy, _ptr(x), _ptr(y), x.shape[0], y.shape[0], int(num_steps), 0, int(num_steps), sid,
+                                     _ptr(ws), nb.value, _stream(dev)))
+    return x, y
+
+
 def sample_two_streams(fm_x, x, fm_y, y, num_steps, solver='euler'):
     """Two independent unguided integrations (the MC pre-phase) on two HIP streams.
 
@@ -1093,6 +1112,10 @@ def sample_two_streams(fm_x, x, fm_y, y, num_steps, solver='euler'):
     _solver(solver, fm_x, fm_y)
 
     def run():
+        # two U-Nets: one native call that schedules both chains (rgfm_sample_two; RGFM_OVERLAP, RGFM_PREPHASE_PRIO)
+        if isinstance(fm_x._engine, UNetEngine) and isinstance(fm_y._engine, UNetEngine) and x.is_cuda and y.is_cuda \
+                and x.shape[0] and y.shape[0] and x.data_ptr() != y.data_ptr():
+            return _sample_two(fm_x, x, fm_y, y, num_steps, solver)
         # one module passed for both modalities (legal in the reference) has ONE engine workspace:
         # its two integrations must not run concurrently
         if os.environ.get("RGFM_OVERLAP", "1") == "0" or fm_x._engine is fm_y._engine:
@@ -1336,3 +1359,10 @@ def profile_read(kclass):
     _lib.check(_lib.lib().rgfm_profile_read(kclass, ctypes.byref(busy), ctypes.byref(tot), ctypes.byref(n),
                                             ctypes.byref(fl)))
     return busy.value, tot.value, n.value, fl.value
+
+
+def profile_span(kclass):
+    """(start of the first launch, end of the last launch) of a kernel class, ms since the first timed launch."""
+    lo, hi = ctypes.c_double(), ctypes.c_double()
+    _lib.check(_lib.lib().rgfm_profile_span(kclass, ctypes.byref(lo), ctypes.byref(hi)))
+    return lo.value, hi.value

@@ -118,6 +118,9 @@ SIGNATURES = {
     "rgfm_sample_pair_ode_workspace_bytes": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, P(c_size_t)]),
     "rgfm_sample_pair_ode": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int,
                                      c_int, c_double, c_int, c_int, c_int, c_void_p, c_size_t, c_void_p]),
+    "rgfm_sample_two_workspace_bytes": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, P(c_size_t)]),
+    "rgfm_sample_two": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int, c_int, c_void_p,
+                                c_size_t, c_void_p]),
     "rgfm_sample_cond_ode_workspace_bytes": (c_int, [c_void_p, c_int, c_int, c_int, P(c_size_t)]),
     "rgfm_sample_cond_ode": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_double, c_int, c_int,
                                      c_int, c_void_p, c_size_t, c_void_p]),
@@ -147,6 +150,7 @@ SIGNATURES = {
     "rgfm_profile_reset": (c_int, []),
     "rgfm_profile_read": (c_int, [c_int, P(c_double), P(c_double), P(c_int64), P(c_double)]),
     "rgfm_profile_reserve": (c_int, [c_int64]),
+    "rgfm_profile_span": (c_int, [c_int, P(c_double), P(c_double)]),
     "rgfm_ubench_mfma_f16": (c_int, [P(c_double)]),
     "rgfm_fmnet_train_workspace_bytes": (c_int, [c_void_p, c_int, P(c_size_t)]),
     "rgfm_fmnet_forward_train": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_void_p, c_int, c_void_p, c_size_t,

@@ -27,6 +27,21 @@ extern "C" int rgfm_profile_read(int kclass, double* busy_ms, double* sum_ms, in
   if (flops) *flops = g_prof.flops[kclass];
   return RGFM_OK;
 }
+// when the class's first launch started and its last launch ended, in ms since the first timed launch after the reset
+extern "C" int rgfm_profile_span(int kclass, double* first_start_ms, double* last_end_ms) {
+  if (kclass < 0 || kclass >= RGFM_KCLASS_COUNT) return fail(RGFM_EINVAL, "bad kernel class %d", kclass);
+  int rc = prof_collect();
+  if (rc) return rc;
+  double lo = 0.0, hi = 0.0;
+  bool any = false;
+  for (const auto& p : g_prof.iv[kclass]) {
+    lo = any ? std::min(lo, p.first) : p.first, hi = any ? std::max(hi, p.second) : p.second;
+    any = true;
+  }
+  if (first_start_ms) *first_start_ms = lo;
+  if (last_end_ms) *last_end_ms = hi;
+  return RGFM_OK;
+}
 
 extern "C" int rgfm_profile_reserve(int64_t launches) {
   if (launches < 0) return fail(RGFM_EINVAL, "negative launch count");

@@ -69,7 +69,149 @@ int single_loop(rgfm_unet* h, float* x_inout, int batch, int num_steps, int step
   return RGFM_OK;
 }
 
+// ---- two unguided integrations at once (the MC pre-phase of the paired sampler)
+// One net's chain of launches as single_loop runs it, cut into steps so that two chains can be enqueued side by side.
+struct Chain {
+  rgfm_unet* h;
+  float* x;
+  int batch, solver;
+  hipStream_t s;
+  Bump b;
+  float *table = nullptr, *mid = nullptr;
+  unsigned* cnt = nullptr;
+  size_t mark = 0;
+  float dt = 0.f, dth = 0.f;
+
+  int begin(void* ws, size_t bytes, int num_steps, int step_begin, int ns) {
+    b.base = (char*)ws, b.cap = bytes, b.dry = false;
+    table = b.f((size_t)4096 * h->temb_total);
+    cnt = reinterpret_cast<unsigned*>(b.f(batch));
+    mid = solver == SOLVER_MIDPOINT ? b.f((size_t)batch * image_floats(h)) : nullptr;
+    HIP_TRY(hipMemsetAsync(cnt, 0, (size_t)batch * sizeof(unsigned), s));
+    launch_stage_table(h, solver, num_steps, step_begin, ns, table, s);
+    mark = b.off;
+    const double dtd = 1.0 / (double)num_steps;
+    dt = (float)dtd, dth = (float)(0.5 * dtd);
+    return RGFM_OK;
+  }
+  int stage(int row, const float* in, float* out, const float* base, float dts) {
+    b.off = mark;
+    UNetRun r{h, batch, &b, s, table + (size_t)row * h->temb_total, 0, false};
+    r.fin_counter = cnt;
+    return r.run(in, nullptr, out, dts, base);
+  }
+  int step(int i) {
+    if (solver != SOLVER_MIDPOINT) return stage(i, x, x, x, dt);
+    if (int rc = stage(2 * i, x, mid, x, dth)) return rc;
+    return stage(2 * i + 1, mid, x, x, dt);
+  }
+};
+
+// Conv FLOPs of one evaluation of one row, from the descriptor's layer list (the walk of UNetRun::run).
+double row_flops(const rgfm_unet* h) {
+  const rgfm_unet_desc& d = h->d;
+  auto res = [](const ResW& r, int S) {
+    return 2.0 * S * S * r.cout * (9.0 * r.cin + 9.0 * r.cout + (r.has_skip ? r.cin : 0));
+  };
+  int S = d.img_size;
+  double f = 2.0 * S * S * 9.0 * d.in_channels * (h->mc + h->final_ch);
+  size_t e = 0, di = 0;
+  for (int l = 0; l < d.num_levels; ++l) {
+    for (int r = 0; r < d.num_res_blocks; ++r) f += res(h->enc[e++], S);
+    if (l < d.num_levels - 1) S /= 2, f += 2.0 * S * S * 9.0 * h->down[l].cin * h->down[l].cout;
+  }
+  f += res(h->mid[0], S) + res(h->mid[1], S);
+  for (int l = d.num_levels - 1; l >= 0; --l) {
+    for (int i = 0; i < d.num_res_blocks + 1; ++i) f += res(h->dec[di++], S);
+    if (l > 0) S *= 2, f += 2.0 * S * S * 9.0 * h->up[d.num_levels - 1 - l].cin * h->up[d.num_levels - 1 - l].cout;
+  }
+  return f;
+}
+
+int two_bytes(const rgfm_unet* hx, const rgfm_unet* hy, int batch_x, int batch_y, int solver, size_t* bytes) {
+  size_t nx = 0, ny = 0;
+  if (int rc = single_bytes(hx, batch_x, solver, &nx)) return rc;
+  if (int rc = single_bytes(hy, batch_y, solver, &ny)) return rc;
+  *bytes = nx + ny;
+  return RGFM_OK;
+}
+
+// The two chains are independent and carry unequal work (the benchmark's pair: 1 : 2.8).  x runs on the caller's stream,
+// y on the device's side stream, forked from and joined back into the caller's.  Enqueued one whole chain after the
+// other, the second chain starts only when the host has got through the first one's launches, and from then on the two
+// drift: whichever ends first leaves the other alone on the chip, with nothing to cover its launch heads and tails and
+// its small grids.  So ("MC pre-phase") the chains are enqueued step by step, and step i + 1 of the lighter
+// chain -- by conv FLOPs per step x rows, from the descriptors -- waits for step i of the heavier one (hipStreamWaitEvent,
+// no host synchronisation): every step of the heavier chain has the lighter chain's step beside it, as a step of the
+// guided loop has, and both end within a step of each other.  Chains of equal work are not paced.
+// RGFM_PREPHASE_PRIO=0: the earlier schedule.  Same launches and arguments per chain either way: a row's bits do not
+// depend on the schedule.
+int two_loop(rgfm_unet* hx, rgfm_unet* hy, float* x_inout, float* y_inout, int batch_x, int batch_y, int num_steps,
+             int step_begin, int step_end, int solver, void* ws, size_t ws_bytes, rgfm_stream_t stream) {
+  refresh_modes();
+  if (int rc = check_solver_id(solver)) return rc;
+  if (!hx || !hy || !x_inout || !y_inout || !ws) return fail(RGFM_EINVAL, "null argument");
+  if (x_inout == y_inout) return fail(RGFM_EINVAL, "the two states must be different buffers");
+  if (int rc = check_range(batch_x, num_steps, step_begin, step_end)) return rc;
+  if (batch_y < 1) return fail(RGFM_EINVAL, "bad argument");
+  const int ns = step_end - step_begin;
+  if (int rc = check_solver(solver, ns, num_steps)) return rc;
+  size_t nx = 0, ny = 0;
+  single_bytes(hx, batch_x, solver, &nx);
+  single_bytes(hy, batch_y, solver, &ny);
+  if (nx + ny > ws_bytes) return fail(RGFM_ENOMEM, "workspace too small: %zu < %zu", ws_bytes, nx + ny);
+  if (ns == 0) return RGFM_OK;
+  DevState* ds = cur_dev();
+  if (!ds) return fail(RGFM_EINVAL, "no handle has been created on the current device");
+  hipStream_t caller = (hipStream_t)stream;
+  const bool overlap = g_modes.overlap;  // (RGFM_OVERLAP=0: both chains on the caller's stream)
+  const double wx = row_flops(hx) * batch_x, wy = row_flops(hy) * batch_y;
+  Chain cx{hx, x_inout, batch_x, solver, caller}, cy{hy, y_inout, batch_y, solver, overlap ? ds->side : caller};
+  Chain &lng = wx > wy ? cx : cy, &sht = wx > wy ? cy : cx;
+  // Whatever has been enqueued on the side stream must be joined into the caller's on every exit path.
+  struct Join {
+    DevState* ds;
+    hipStream_t caller, side;
+    ~Join() {
+      if (side != caller) (void)hipEventRecord(ds->join, side), (void)hipStreamWaitEvent(caller, ds->join, 0);
+    }
+  } join{ds, caller, cy.s};
+  if (overlap) {
+    HIP_TRY(hipEventRecord(ds->fork, caller));
+    HIP_TRY(hipStreamWaitEvent(cy.s, ds->fork, 0));
+  }
+  if (int rc = cx.begin(ws, nx, num_steps, step_begin, ns)) return rc;
+  if (int rc = cy.begin((char*)ws + nx, ny, num_steps, step_begin, ns)) return rc;
+  if (!overlap || !g_modes.prephase) {  // the earlier order: the second net's whole chain, then the first's
+    for (Chain* c : {&cy, &cx})
+      for (int i = 0; i < ns; ++i)
+        if (int rc = c->step(i)) return rc;
+  } else {
+    const bool pace = wx != wy;
+    for (int i = 0; i < ns; ++i) {
+      if (int rc = lng.step(i)) return rc;
+      if (pace && i + 1 < ns) HIP_TRY(hipEventRecord(ds->pre_pace, lng.s));
+      if (int rc = sht.step(i)) return rc;
+      if (pace && i + 1 < ns) HIP_TRY(hipStreamWaitEvent(sht.s, ds->pre_pace, 0));
+    }
+  }
+  HIP_TRY(hipGetLastError());
+  return RGFM_OK;
+}
+
 }  // namespace
+
+extern "C" int rgfm_sample_two_workspace_bytes(const rgfm_unet* hx, const rgfm_unet* hy, int batch_x, int batch_y, int solver,
+                                               size_t* bytes) {
+  if (int rc = check_solver_id(solver)) return rc;
+  if (!hx || !hy || !bytes || batch_x < 1 || batch_y < 1) return fail(RGFM_EINVAL, "bad argument");
+  return two_bytes(hx, hy, batch_x, batch_y, solver, bytes);
+}
+extern "C" int rgfm_sample_two(rgfm_unet* hx, rgfm_unet* hy, float* x_inout, float* y_inout, int batch_x, int batch_y,
+                               int num_steps, int step_begin, int step_end, int solver, void* ws, size_t ws_bytes,
+                               rgfm_stream_t stream) {
+  return two_loop(hx, hy, x_inout, y_inout, batch_x, batch_y, num_steps, step_begin, step_end, solver, ws, ws_bytes, stream);
+}
 
 extern "C" int rgfm_sample_single_workspace_bytes(const rgfm_unet* h, int batch, size_t* bytes) {
   return single_bytes(h, batch, SOLVER_EULER, bytes);

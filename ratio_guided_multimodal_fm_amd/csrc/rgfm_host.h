@@ -266,6 +266,8 @@ struct Modes {
                           // layer in isolation at 32x32, slower on the whole bench
   bool up_t2 = true;      // RGFM_UP_T2=0: the Upsample convs as nine taps over the upsampled raster instead of four parity classes (A/B switch)
   bool rev_hx2 = true;    // RGFM_REV_HX2=0: the reverse convs of the gradient-guided sampler on the exact fp32 MFMA (A/B switch)
+  bool prephase = true;   // RGFM_PREPHASE_PRIO=0: the two-net unguided entry (rgfm_sample_two) with its earlier schedule -- one chain
+                          // enqueued after the other, unpaced -- instead of step by step with the lighter chain paced (A/B switch)
   bool graph = false;     // RGFM_GRAPH=1: the guided steps of the paired U-Net loop replayed from one captured hipGraph
                           // (bit-identical; measured 0.995-1.002x of the kernel-by-kernel path: the host is not the bottleneck)
 };
@@ -300,6 +302,8 @@ inline void refresh_modes() {
   m.rev_hx2 = !(e && e[0] == '0');
   e = getenv("RGFM_GRAPH");
   m.graph = e && e[0] == '1';
+  e = getenv("RGFM_PREPHASE_PRIO");
+  m.prephase = !(e && e[0] == '0');
   g_modes = m;
   e = getenv("RGFM_WINO_W32");
   g_conv_tuning.wino_w32 = e ? atoi(e) : 0;
@@ -327,6 +331,7 @@ struct DevState {
   hipStream_t side = nullptr;
   void* zeros = nullptr;  // 256 zero bytes: the source of the padding records of conv_mfma_hx2d_kernel's halo DMA
   hipEvent_t fork = nullptr, join = nullptr;
+  hipEvent_t pre_pace = nullptr;  // the two-net unguided entry (two_loop, api_sampler.cpp): paces the lighter chain
   // the legacy default stream cannot be captured: a caller on it has its graph-replayed loop run on `main`,
   // forked from / joined back into the default stream with these events
   hipStream_t main = nullptr;
@@ -367,6 +372,7 @@ inline int ensure_init() {
     HIP_TRY(hipStreamCreateWithFlags(&d.main, hipStreamNonBlocking));
     HIP_TRY(hipEventCreateWithFlags(&d.main_fork, hipEventDisableTiming));
     HIP_TRY(hipEventCreateWithFlags(&d.main_join, hipEventDisableTiming));
+    HIP_TRY(hipEventCreateWithFlags(&d.pre_pace, hipEventDisableTiming));
     d.init = true;
   }
   return RGFM_OK;

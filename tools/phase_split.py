@@ -49,6 +49,16 @@ tm = t(lambda: _engine.sample_pair(fm, fs, x0.clone(), y0.clone(), mx1, my1, r, 
 print(f"pre-phase ({N} rows x 2 nets, {S} steps): {1e3 * tp:.1f} ms = {N * S * PAIR_FLOP / tp / 1e12:.1f} TFLOP/s; "
       f"main loop ({B} rows): {1e3 * tm:.1f} ms = {B * S * PAIR_FLOP / tm / 1e12:.1f} TFLOP/s")
 out["prephase_ms"], out["mainloop_ms"] = 1e3 * tp, 1e3 * tm
+# when each chain of the pre-phase starts and ends: one extra call under the library's per-launch event timers (the
+# in- / out-conv classes are per modality), outside every timed region above and below
+_engine.profile(enable=True, reset=True)
+_engine.sample_two_streams(fm, mx0.clone(), fs, my0.clone(), S)
+torch.cuda.synchronize()
+sx, sy = (_engine.profile_span(2)[0], _engine.profile_span(4)[1]), (_engine.profile_span(3)[0], _engine.profile_span(5)[1])
+_engine.profile(enable=False, reset=True)
+print(f"  pre-phase chains under the launch timers: MNIST32 {sx[0]:.1f} -> {sx[1]:.1f} ms, SVHN {sy[0]:.1f} -> {sy[1]:.1f} ms; "
+      f"they end {abs(sx[1] - sy[1]):.1f} ms apart = {100 * abs(sx[1] - sy[1]) / max(sx[1], sy[1]):.1f} % of the pre-phase")
+out["prephase_chain_span_ms"] = {"mnist32": sx, "svhn": sy}
 rows = {}
 for nb in (32, 64, 128, 256, 384, 512, 768):
     xx, yy = torch.randn(nb, 1, 32, 32, device=dev), torch.randn(nb, 3, 32, 32, device=dev)
