@@ -557,6 +557,66 @@ int rgfm_fmnet_backward(rgfm_fmnet* h, const float* dv, float* dx_out, float* dp
                         size_t ws_bytes, rgfm_stream_t stream);
 int rgfm_fmnet_update_params(rgfm_fmnet* h, const float* params_dev, size_t n_floats, rgfm_stream_t stream);
 
+/* ------------------------------------------------------------------ evaluation classifiers (training pass)
+ * The three digit classifiers of the coherence metric (reference src/models/classifier.py:9-52: MNISTClassifier,
+ * 1x28x28; src/models/svhn_classifier.py:74-116: MNISTClassifier32, 1x32x32; :11-71: SVHNClassifier, 3x32x32 with
+ * BatchNorm2d behind every conv): conv3x3 (+ BatchNorm) + ReLU blocks, a 2x2 max-pool behind the first two, fc1 + ReLU
+ * + Dropout, fc2 -> 10 logits.  Replaces the autograd of src/train_classifier.py and
+ * src/train_classifiers_mnist_svhn.py.  Same conventions as the ratio estimators' training pass: blob = state_dict()
+ * order INCLUDING the BatchNorm buffers, exact fp32 arithmetic on v_mfma_f32_32x32x2_f32 (convs, fc1), NCHW fp32
+ * tensors, stream-ordered, caller-owned 16-byte aligned workspace, nothing allocated or synchronised inside a call.
+ * Added functions only: the ABI version is unchanged.
+ *
+ * rgfm_clf_forward_train writes logits_out[n][10] = forward(x) and leaves in `ws` what rgfm_clf_backward needs; `ws`
+ * (rgfm_clf_train_workspace_bytes(h, n)) must stay untouched between the two calls.
+ *   training != 0: BatchNorm normalises with the batch mean and the biased batch variance (eps 1e-5); Dropout behind
+ *     fc1's ReLU keeps element i of [n][hidden] by the counter hash documented for rgfm_unet_dropout_mask (Dropout
+ *     layer 0), scales kept values by 1 / (1 - p_drop), and the backward regenerates the mask.  bn_stats_out (may be
+ *     null; unused by the two MNIST nets) receives per BatchNorm layer, in state_dict order, [C][2] = (batch mean,
+ *     UNBIASED batch variance): what the running-statistics update needs.
+ *   training == 0: running statistics, no dropout, still differentiable.
+ * The ReLU gate is `value > 0` (a value of exactly 0 gets no gradient) and a max-pool takes the first maximal element
+ * of its window in row-major order, both as in PyTorch.
+ * rgfm_clf_backward: given dlogits = dL/dlogits_out, writes dL/dx (optional) and dL/dparams -- one blob in state_dict
+ * order, overwritten; the slots of running_mean, running_var and num_batches_tracked are zero.  Every reduction has a
+ * fixed order: two calls on the same inputs give bitwise-identical results.
+ * rgfm_clf_xent: softmax cross-entropy of logits[n][classes] (classes <= 32) against int32 labels, every row shifted
+ * by its own maximum: loss_rows_out[n] (DOUBLES: at logits of magnitude 10^2 an fp32 row loss could not hold the
+ * accuracy of the softmax itself), dlogits_out[n][classes] = (softmax - onehot) * scale (optional) and pred_out[n] =
+ * argmax, the first index on a tie (optional).  No reduction across rows: the mean is the caller's scale = 1 / n and
+ * its own sum of the rows.  Needs no handle.
+ * Test hooks (null stream), for the forward that filled `ws`: rgfm_clf_pool_choice -- the window element (0..3,
+ * row-major) the max-pool behind conv block `layer` (0-based) took, as out[n][C][Ho][Wo] floats; rgfm_clf_gate -- 1.0
+ * where the ReLU of `layer` passed, else 0.0: for a conv block on the block's OUTPUT raster (behind a pool: the gate
+ * of the element taken), for layer == number of conv blocks fc1's ReLU, out[n][hidden], before the dropout;
+ * rgfm_clf_dropout_mask -- the keep decisions (1.0 / 0.0) of the Dropout layer, out[n][hidden].
+ * Errors touch no state: n < 1, a null pointer or an unknown kind -> RGFM_EINVAL; a workspace one byte short ->
+ * RGFM_ENOMEM; no gfx950 device -> RGFM_ENODEVICE (create, xent). */
+#define RGFM_CLF_MNIST28 0
+#define RGFM_CLF_MNIST32 1
+#define RGFM_CLF_SVHN 2
+typedef struct rgfm_clf_desc {
+  int32_t kind; /* RGFM_CLF_* */
+} rgfm_clf_desc;
+
+typedef struct rgfm_clf rgfm_clf;
+
+int rgfm_clf_param_floats(const rgfm_clf_desc* desc, size_t* n_floats);
+int rgfm_clf_create(const rgfm_clf_desc* desc, const float* params_dev, size_t n_floats, rgfm_stream_t stream,
+                    rgfm_clf** out);
+void rgfm_clf_destroy(rgfm_clf* h);
+int rgfm_clf_update_params(rgfm_clf* h, const float* params_dev, size_t n_floats, rgfm_stream_t stream);
+int rgfm_clf_train_workspace_bytes(const rgfm_clf* h, int n, size_t* bytes);
+int rgfm_clf_forward_train(rgfm_clf* h, const float* x, float* logits_out, int n, int training, uint64_t seed,
+                           float p_drop, float* bn_stats_out, void* ws, size_t ws_bytes, rgfm_stream_t stream);
+int rgfm_clf_backward(rgfm_clf* h, const float* dlogits, float* dx_out, float* dparams_out, int n, void* ws,
+                      size_t ws_bytes, rgfm_stream_t stream);
+int rgfm_clf_xent(const float* logits, const int32_t* labels, int n, int classes, float scale, double* loss_rows_out,
+                  float* dlogits_out, int32_t* pred_out, rgfm_stream_t stream);
+int rgfm_clf_pool_choice(rgfm_clf* h, const void* ws, int layer, int n, float* out);
+int rgfm_clf_gate(rgfm_clf* h, const void* ws, int layer, int n, float* out);
+int rgfm_clf_dropout_mask(rgfm_clf* h, uint64_t seed, float p_drop, int n, float* out);
+
 /* One guidance evaluation on its own (parity hook for sample_mnist_svhn.py:124-171):
  * vx/vy are overwritten with (1-gamma)*v + gamma*g at time t; weights_out[B,N]
  * (optional, may be null) receives the normalised importance weights. */

@@ -1026,6 +1026,236 @@ class _RatioTrainFn(torch.autograd.Function):
         return (None, dx, dy, None, *grads)
 
 
+_CLF_KIND = {"mnist28": 0, "mnist32": 1, "svhn": 2}
+# kind: (image shape, per conv block (channels, output size, max-pool behind it), fc1 width)
+_CLF_GEOMETRY = {
+    "mnist28": ((1, 28, 28), [(32, 14, True), (64, 7, True)], 128),
+    "mnist32": ((1, 32, 32), [(32, 16, True), (64, 8, True), (64, 8, False)], 128),
+    "svhn": ((3, 32, 32), [(32, 16, True), (64, 8, True), (128, 8, False), (128, 8, False)], 256),
+}
+
+
+class ClassifierEngine(_EngineBase):
+    """Training pass of the evaluation classifiers (rgfm_clf_*): one handle per module, re-packed in place when
+    only the values of its parameters moved."""
+
+    def __init__(self, module, kind):
+        super().__init__(module)
+        self.kind = kind
+        self._last_train = None
+
+    def desc(self):
+        d = _lib.ClfDesc()
+        d.kind = _CLF_KIND[self.kind]
+        return d
+
+    def handle(self, device):
+        sd = self._module().state_dict()
+        key = self._state_key(sd)
+        if self._handle is not None and key == self._key:
+            return self._handle
+        L = _lib.lib()
+        blob = self._blob_from(sd, device)
+        if self._handle is not None and _same_tensors(key, self._key):
+            # only the values moved (an optimizer step, the running statistics): refresh the same handle
+            with torch.cuda.device(device):
+                _lib.check(L.rgfm_clf_update_params(self._handle, _ptr(blob), blob.numel(), _stream(device)))
+            self._key, self._blob = key, blob
+            return self._handle
+        if self._handle is not None:
+            self._destroy()
+        d = self.desc()
+        n = ctypes.c_size_t()
+        _lib.check(L.rgfm_clf_param_floats(ctypes.byref(d), ctypes.byref(n)))
+        if blob.numel() != n.value:
+            raise _lib.RgfmError(f"parameter blob has {blob.numel()} floats, library expects {n.value}")
+        h = ctypes.c_void_p()
+        with torch.cuda.device(device):
+            _lib.check(L.rgfm_clf_create(ctypes.byref(d), _ptr(blob), blob.numel(), _stream(device), ctypes.byref(h)))
+        self._handle, self._key, self._blob = h, key, blob
+        return h
+
+    def _destroy(self):
+        _lib.lib().rgfm_clf_destroy(self._handle)
+        self._handle = None
+
+    def owns(self, handle):
+        """Is `handle` (as handle() returned it) still alive in this engine?"""
+        return self._handle is handle
+
+    def image_shape(self):
+        return _CLF_GEOMETRY[self.kind][0]
+
+    def layer_shapes(self):
+        """Per layer with a ReLU, in forward order: the shape (without the batch) of its gate -- the conv blocks on
+        their output raster, then fc1 -- and whether a max-pool sits behind it."""
+        _, blocks, hidden = _CLF_GEOMETRY[self.kind]
+        return [((c, s, s), pool) for c, s, pool in blocks] + [((hidden,), False)]
+
+    def forward_train(self, x):
+        """logits = model(x) in the module's current mode, differentiable w.r.t. x and the parameters (_ClfTrainFn).
+        In training mode: batch statistics, dropout, and the BatchNorm buffers are updated."""
+        m = self._module()
+        _require_hip(x)
+        c, s, _ = self.image_shape()
+        if x.dim() != 4 or tuple(x.shape[1:]) != (c, s, s):
+            raise _lib.RgfmError(f"expected images of shape [B,{c},{s},{s}], got {tuple(x.shape)}")
+        p = m.dropout_p() if m.training else 0.0
+        return _ClfTrainFn.apply(self, x, float(p), *m.parameters())
+
+    def _saved(self):
+        ws = self._last_train[0]() if self._last_train else None
+        if ws is None:
+            raise _lib.RgfmError("no saved state: call this between forward_train and its backward")
+        n, h = self._last_train[1], self._last_train[2]
+        if not self.owns(h):
+            raise _lib.RgfmError("the module's handle was re-created since that forward_train")
+        return ws, n, h
+
+    def pool_choices(self):
+        """The window elements (0..3, row-major) the max-pools of the latest forward_train chose: per conv block a
+        [B, C, Ho, Wo] tensor, or None where no pool follows (rgfm_clf_pool_choice).  Valid until that call's backward."""
+        ws, n, h = self._saved()
+        out = []
+        with torch.cuda.device(ws.device):
+            for i, (shape, pool) in enumerate(self.layer_shapes()[:-1]):
+                t = torch.empty(n, *shape, device=ws.device) if pool else None
+                if pool:
+                    _lib.check(_lib.lib().rgfm_clf_pool_choice(h, _ptr(ws), i, n, _ptr(t)))
+                out.append(t)
+        return out
+
+    def gates(self):
+        """1.0 where the ReLU of the latest forward_train passed: per conv block on its output raster (behind a pool:
+        the gate of the element taken), then fc1's [B, hidden] before the dropout (rgfm_clf_gate)."""
+        ws, n, h = self._saved()
+        out = []
+        with torch.cuda.device(ws.device):
+            for i, (shape, _) in enumerate(self.layer_shapes()):
+                t = torch.empty(n, *shape, device=ws.device)
+                _lib.check(_lib.lib().rgfm_clf_gate(h, _ptr(ws), i, n, _ptr(t)))
+                out.append(t)
+        return out
+
+    def last_dropout(self):
+        """(seed, p) of the latest forward_train's dropout."""
+        if not self._last_train:
+            raise _lib.RgfmError("no forward_train call yet")
+        return self._last_train[3]
+
+    def dropout_mask(self, seed, p, batch, device):
+        """Keep decisions (1 / 0) of the Dropout layer behind fc1: [batch, hidden] (rgfm_clf_dropout_mask)."""
+        out = torch.empty(batch, _CLF_GEOMETRY[self.kind][2], device=device)
+        with torch.cuda.device(device):
+            _lib.check(_lib.lib().rgfm_clf_dropout_mask(self.handle(device), int(seed), float(p), int(batch), _ptr(out)))
+        return out
+
+
+class _ClfTrainFn(torch.autograd.Function):
+    """Training forward / backward of the classifiers through rgfm_clf_forward_train / rgfm_clf_backward.
+
+    Inputs: the engine, x, p_drop and the module's parameters, so that autograd hands back dL/dx and every dL/dparam.
+    Each call owns its saved-state buffer; the dropout seed is drawn from the device's torch generator.  While the
+    module trains, the BatchNorm buffers are updated from the batch statistics the library reports."""
+
+    @staticmethod
+    def forward(ctx, engine, x, p_drop, *params):
+        m = engine._module()
+        dev = x.device
+        x = x.contiguous()
+        n = x.shape[0]
+        out = torch.empty(n, 10, device=dev)
+        ctx.engine, ctx.n, ctx.ws, ctx.nbytes, ctx.h = engine, n, None, 0, None
+        ctx.save_for_backward(*params)
+        ctx.shape = x.shape
+        if n == 0:
+            return out
+        training = bool(m.training)
+        seed = int(torch.randint(0, 2 ** 62, (1,), device=dev).item()) if p_drop > 0 else 0
+        bns = [b for b in m.modules() if isinstance(b, torch.nn.BatchNorm2d)] if training else []
+        stats = torch.empty(2 * sum(b.num_features for b in bns), device=dev) if bns else None
+        named = {id(q) for q in m.parameters()}
+        ctx.layout = [(v.numel(), id(v) in named) for v in m.state_dict(keep_vars=True).values()]
+        L = _lib.lib()
+        with torch.cuda.device(dev):
+            h = engine.handle(dev)
+            nb = ctypes.c_size_t()
+            _lib.check(L.rgfm_clf_train_workspace_bytes(h, n, ctypes.byref(nb)))
+            ws = torch.empty(nb.value, dtype=torch.uint8, device=dev)
+            _lib.check(L.rgfm_clf_forward_train(h, _ptr(x), _ptr(out), n, 1 if training else 0, seed, p_drop,
+                                                _ptr(stats), _ptr(ws), nb.value, _stream(dev)))
+        off = 0
+        for b in bns:  # nn.BatchNorm2d's update: momentum 0.1, unbiased batch variance
+            st = stats[off:off + 2 * b.num_features].view(-1, 2)
+            off += 2 * b.num_features
+            mom = b.momentum
+            b.running_mean.mul_(1 - mom).add_(st[:, 0], alpha=mom)
+            b.running_var.mul_(1 - mom).add_(st[:, 1], alpha=mom)
+            b.num_batches_tracked.add_(1)
+        ctx.ws, ctx.nbytes, ctx.h = ws, nb.value, h
+        engine._last_train = (weakref.ref(ws), n, h, (seed, p_drop))
+        return out
+
+    @staticmethod
+    def backward(ctx, dlogits):
+        params = ctx.saved_tensors
+        dev = dlogits.device
+        need_x = ctx.needs_input_grad[1]
+        if ctx.n == 0:
+            return (None, torch.zeros(ctx.shape, device=dev) if need_x else None, None, *[torch.zeros_like(q) for q in params])
+        if ctx.ws is None:
+            raise _lib.RgfmError("the saved state of this forward_train call is gone (backward ran twice?)")
+        if not ctx.engine.owns(ctx.h):
+            raise _lib.RgfmError("the module's handle was re-created between forward_train and backward")
+        dlogits = dlogits.to(torch.float32).contiguous()
+        dparams = torch.empty(sum(k for k, _ in ctx.layout), device=dev)
+        dx = torch.empty(ctx.shape, device=dev) if need_x else None
+        with torch.cuda.device(dev):
+            _lib.check(_lib.lib().rgfm_clf_backward(ctx.h, _ptr(dlogits), _ptr(dx), _ptr(dparams), ctx.n, _ptr(ctx.ws),
+                                                    ctx.nbytes, _stream(dev)))
+        ctx.ws = None
+        chunks = torch.split(dparams, [k for k, _ in ctx.layout])
+        grads = [g.view(q.shape) for g, q in zip([c for c, (_, is_p) in zip(chunks, ctx.layout) if is_p], params)]
+        return (None, dx, None, *grads)
+
+
+class _XentFn(torch.autograd.Function):
+    """Mean softmax cross-entropy through rgfm_clf_xent: the forward computes dlogits = (softmax - onehot) / n with
+    the loss rows, the backward scales it by the incoming gradient."""
+
+    @staticmethod
+    def forward(ctx, logits, labels):
+        _require_hip(logits)
+        if logits.dim() != 2 or not 1 <= logits.shape[1] <= 32:
+            raise _lib.RgfmError(f"expected logits of shape [B, classes <= 32], got {tuple(logits.shape)}")
+        if labels.shape != logits.shape[:1]:
+            raise _lib.RgfmError(f"expected {logits.shape[0]} labels, got {tuple(labels.shape)}")
+        dev = logits.device
+        n, classes = logits.shape
+        if n == 0:
+            raise _lib.RgfmError("cross_entropy of an empty batch")
+        logits = logits.contiguous()
+        labels = labels.to(device=dev, dtype=torch.int32).contiguous()
+        rows = torch.empty(n, dtype=torch.float64, device=dev)
+        pred = torch.empty(n, dtype=torch.int32, device=dev)
+        dlogits = torch.empty_like(logits) if ctx.needs_input_grad[0] else None
+        with torch.cuda.device(dev):
+            _lib.check(_lib.lib().rgfm_clf_xent(_ptr(logits), _ptr(labels), n, classes, 1.0 / n, _ptr(rows), _ptr(dlogits),
+                                                _ptr(pred), _stream(dev)))
+        ctx.dlogits = dlogits
+        ctx.mark_non_differentiable(rows)
+        return (rows.sum() / n).to(torch.float32), pred.long(), rows
+
+    @staticmethod
+    def backward(ctx, dloss, _dpred, _drows):
+        return ctx.dlogits * dloss, None
+
+
+def cross_entropy(logits, labels):
+    """(mean loss, predicted classes [B], per-row losses [B] in fp64) of the fused softmax cross-entropy kernel."""
+    return _XentFn.apply(logits, labels)
+
+
 # ---- sampler entry points ------------------------------------------------
 
 _sampler_ws = _Workspace()

@@ -37,6 +37,10 @@ class FmNetDesc(ctypes.Structure):
     _fields_ = [("img_channels", c_int32), ("feature_dim", c_int32), ("time_emb_dim", c_int32)]
 
 
+class ClfDesc(ctypes.Structure):
+    _fields_ = [("kind", c_int32)]
+
+
 # name -> (restype, argtypes); every symbol include/rgfm.h declares.
 SIGNATURES = {
     "rgfm_unet_param_floats": (c_int, [P(UNetDesc), P(c_size_t)]),
@@ -157,6 +161,18 @@ SIGNATURES = {
                                          c_void_p]),
     "rgfm_fmnet_backward": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_void_p, c_size_t, c_void_p]),
     "rgfm_fmnet_update_params": (c_int, [c_void_p, c_void_p, c_size_t, c_void_p]),
+    "rgfm_clf_param_floats": (c_int, [P(ClfDesc), P(c_size_t)]),
+    "rgfm_clf_create": (c_int, [P(ClfDesc), c_void_p, c_size_t, c_void_p, P(c_void_p)]),
+    "rgfm_clf_destroy": (None, [c_void_p]),
+    "rgfm_clf_update_params": (c_int, [c_void_p, c_void_p, c_size_t, c_void_p]),
+    "rgfm_clf_train_workspace_bytes": (c_int, [c_void_p, c_int, P(c_size_t)]),
+    "rgfm_clf_forward_train": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_int, c_uint64, c_float, c_void_p,
+                                       c_void_p, c_size_t, c_void_p]),
+    "rgfm_clf_backward": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_void_p, c_size_t, c_void_p]),
+    "rgfm_clf_xent": (c_int, [c_void_p, c_void_p, c_int, c_int, c_float, c_void_p, c_void_p, c_void_p, c_void_p]),
+    "rgfm_clf_pool_choice": (c_int, [c_void_p, c_void_p, c_int, c_int, c_void_p]),
+    "rgfm_clf_gate": (c_int, [c_void_p, c_void_p, c_int, c_int, c_void_p]),
+    "rgfm_clf_dropout_mask": (c_int, [c_void_p, c_uint64, c_float, c_int, c_void_p]),
     "rgfm_ubench_hbm_copy": (c_int, [c_size_t, P(c_double)]),
     "rgfm_unet_set_conv_mode": (c_int, [c_void_p, c_int]),
     "rgfm_fmnet_set_conv_mode": (c_int, [c_void_p, c_int]),

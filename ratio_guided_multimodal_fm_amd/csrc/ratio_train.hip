@@ -186,6 +186,11 @@ __global__ void rt_bn_bwd_finalize_kernel(const float* part, int C, int slices, 
   dgamma[c] = (float)sg, dbeta[c] = (float)sb;
   m12[2 * c] = training ? (float)sb * inv_n : 0.f, m12[2 * c + 1] = training ? (float)sg * inv_n : 0.f;
 }
+void launch_rt_bn_bwd_finalize(const float* part, int C, int slices, float inv_n, const unsigned* training, float* dgamma,
+                               float* dbeta, float* m12, hipStream_t s) {
+  hipLaunchKernelGGL(rt_bn_bwd_finalize_kernel, dim3((C + 63) / 64), dim3(64), 0, s, part, C, slices, inv_n, training,
+                     dgamma, dbeta, m12);
+}
 // pass 2, in place: dout <- dz
 __global__ void rt_bn_bwd_apply_kernel(RtNorm a, float* dout, const float* m12) {
   const size_t total = (size_t)a.B * a.C * a.H * a.W;
@@ -203,8 +208,7 @@ void launch_rt_bn_bwd(const RtNorm& a, float* dout, const unsigned* training, fl
   const int bper = (a.B + RT_BN_SLICES - 1) / RT_BN_SLICES, slices = (a.B + bper - 1) / bper;
   const size_t total = (size_t)a.B * a.C * a.H * a.W;
   hipLaunchKernelGGL(rt_bn_bwd_part_kernel, dim3(a.C, slices), dim3(256), 0, s, a, dout, bper, part);
-  hipLaunchKernelGGL(rt_bn_bwd_finalize_kernel, dim3((a.C + 63) / 64), dim3(64), 0, s, part, a.C, slices,
-                     1.0f / (float)((size_t)a.B * a.H * a.W), training, dgamma, dbeta, m12);
+  launch_rt_bn_bwd_finalize(part, a.C, slices, 1.0f / (float)((size_t)a.B * a.H * a.W), training, dgamma, dbeta, m12, s);
   hipLaunchKernelGGL(rt_bn_bwd_apply_kernel, dim3((unsigned)std::min<size_t>((total + 255) / 256, 4096)), dim3(256), 0,
                      s, a, dout, m12);
 }

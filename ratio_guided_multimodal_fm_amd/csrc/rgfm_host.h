@@ -13,6 +13,7 @@
 //   api_ratio_train.cpp  rgfm_ratio_forward_train / _backward (ratio estimators' training pass)
 //   api_fmnet.cpp    rgfm_fmnet_*           (FlowMatchingModel)
 //   api_fmnet_train.cpp  rgfm_fmnet_forward_train / _backward / _update_params (FlowMatchingModel's training pass)
+//   api_clf.cpp      rgfm_clf_*             (the evaluation classifiers: handle, training pass, cross-entropy)
 //
 // No PyTorch types, no allocation and no synchronisation inside forward / sample calls (everything is carved from the
 // caller's workspace, stream-ordered).

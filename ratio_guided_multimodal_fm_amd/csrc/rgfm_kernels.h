@@ -542,6 +542,9 @@ void launch_rt_choice(const unsigned char* choice, size_t n, float* out, hipStre
 // device word, non-zero = batch statistics (their dependence on z is differentiated), zero = constants
 void launch_rt_bn_bwd(const RtNorm& a, float* dout, const unsigned* training, float* part, float* m12, float* dgamma, float* dbeta,
                       hipStream_t s);
+// the step between the two passes of a BatchNorm backward (also clf_train.hip's): slices added in order; part: [C][slices][2]
+void launch_rt_bn_bwd_finalize(const float* part, int C, int slices, float inv_n, const unsigned* training, float* dgamma,
+                               float* dbeta, float* m12, hipStream_t s);
 void launch_rt_avgpool(const float* in, int rows, int n, float* out, hipStream_t s);
 void launch_rt_avgpool_bwd(const float* g, int rows, int n, float* din, hipStream_t s);
 void launch_rt_ln_act(const float* u, const float* gamma, const float* beta, int rows, int width, const unsigned* hdr,
@@ -565,5 +568,34 @@ struct FgGemm {
   int veca, vecb;     // a row-major operand may be read 16 bytes at a time (set by launch_fg_gemm)
 };
 void launch_fg_gemm(FgGemm g, bool a_kmajor, bool b_kmajor, hipStream_t s);
+
+// ---- training pass of the evaluation classifiers (clf_train.hip; NCHW fp32)
+// A conv output z [B][C][H][W] in front of a ReLU, with BatchNorm in between when mr (per channel (mean, rstd)) is set:
+// y = gamma (z - mean) rstd + beta, else y = z.
+struct CtAct {
+  const float* z;
+  const float* mr;  // [C][2] or null
+  const float* gamma;
+  const float* beta;
+  int B, C, H, W;
+};
+constexpr int CT_MAX_CLASSES = 32;
+void launch_ct_act(const CtAct& a, float* out, hipStream_t s);                              // out = relu(y)
+void launch_ct_act_pool(const CtAct& a, float* out, unsigned char* choice, hipStream_t s);  // + 2x2 max-pool, element taken
+// full (the conv's raster) = g (pooled raster) at the chosen element where the pooled activation `act` > 0, else 0
+void launch_ct_unpool_gate(const float* g, const unsigned char* choice, const float* act, float* full, int BC, int H,
+                           int W, hipStream_t s);
+void launch_ct_gate(float* g, const float* act, size_t n, hipStream_t s);          // in place: g where act > 0, else 0
+void launch_ct_gate_out(const float* act, size_t n, float* out, hipStream_t s);    // out = act > 0 ? 1 : 0
+// dout (gradient of relu(y) on the full raster; `act` = relu(y), or null when dout is the gradient of y already) is
+// replaced by dz; part: [C][RT_BN_SLICES][2], m12: [C][2]; training: as launch_rt_bn_bwd
+void launch_ct_bn_bwd(const CtAct& a, float* dout, const float* act, const unsigned* training, float* part, float* m12,
+                      float* dgamma, float* dbeta, hipStream_t s);
+// out = drop(relu(u)) / in place g <- drop(g) where u > 0: Dropout layer 0 of the header hdr (launch_ug_header)
+void launch_ct_relu_drop(const float* u, size_t n, const unsigned* hdr, float* out, hipStream_t s);
+void launch_ct_relu_drop_bwd(const float* u, float* g, size_t n, const unsigned* hdr, hipStream_t s);
+// rows of logits[n][classes <= CT_MAX_CLASSES]: loss[n] (fp64), optional dlogits = (softmax - onehot) scale, optional pred
+void launch_ct_xent(const float* logits, const int* labels, int n, int classes, float scale, double* loss,
+                    float* dlogits, int* pred, hipStream_t s);
 
 }  // namespace rgfm

@@ -1,4 +1,4 @@
-// train_device.h -- device helpers shared by the training kernels (unet_grad.hip, ratio_train.hip, fmnet_grad.hip).
+// train_device.h -- device helpers shared by the training kernels (unet_grad.hip, ratio_train.hip, fmnet_grad.hip, clf_train.hip).
 #pragma once
 #include <cstdint>
 

@@ -1,16 +1,25 @@
 """Evaluation classifiers of the MNIST-SVHN experiment (reference
 ``src/models/svhn_classifier.py``: ``SVHNClassifier`` ``:11-71``, ``MNISTClassifier32`` ``:74-116``).
 
-They run ONCE on the final samples (< 0.01 % of a sampling call's work), so they are
-ordinary PyTorch modules executed by PyTorch-ROCm: not part of the accelerated hot path.  Same
+They run ONCE on the final samples (< 0.01 % of a sampling call's work), so ``forward`` is
+ordinary PyTorch executed by PyTorch-ROCm: not part of the accelerated hot path.  Same
 ``state_dict`` keys and shapes as the reference, so its trained classifier checkpoints load.
+``forward_train`` is the differentiable forward that trains them: exact fp32 on the matrix cores with a
+hand-written HIP backward (``rgfm_clf_forward_train`` / ``rgfm_clf_backward``).
 """
 import torch.nn as nn
 import torch.nn.functional as F
 
+from .._engine import ClassifierEngine, engine_property
+from .classifier import MNISTClassifier
+
 
 class SVHNClassifier(nn.Module):
     """3x32x32 -> 10 logits: 4 x (conv3x3 + BatchNorm + ReLU), max-pool after the first two."""
+
+    _engine = engine_property(lambda m: ClassifierEngine(m, kind="svhn"))
+    forward_train = MNISTClassifier.forward_train
+    dropout_p = MNISTClassifier.dropout_p
 
     def __init__(self):
         super().__init__()
@@ -33,6 +42,10 @@ class SVHNClassifier(nn.Module):
 
 class MNISTClassifier32(nn.Module):
     """1x32x32 -> 10 logits: 3 x (conv3x3 + ReLU), max-pool after the first two."""
+
+    _engine = engine_property(lambda m: ClassifierEngine(m, kind="mnist32"))
+    forward_train = MNISTClassifier.forward_train
+    dropout_p = MNISTClassifier.dropout_p
 
     def __init__(self):
         super().__init__()

@@ -2,6 +2,8 @@
 
 Each loss maps (scores of real pairs, scores of fake pairs) to ``(loss, metrics)``.  They run in torch on the [B] score
 vector that ``forward_train`` returns: B floats, whose gradient enters the HIP backward as ``dscore``.
+
+``cross_entropy`` is the classifiers' loss: the fused softmax cross-entropy kernel (``rgfm_clf_xent``).
 """
 import torch
 import torch.nn as nn
@@ -45,6 +47,15 @@ class RuLSIFLoss(DensityRatioLoss):
             metrics = {'loss': loss.item(), 'mean_w_real': w_real.mean().item(), 'mean_w_fake': w_fake.mean().item(),
                        'constraint_term': constraint.item()}
         return loss, metrics
+
+
+def cross_entropy(logits, labels):
+    """``(loss, pred)``: the mean softmax cross-entropy of logits [B, classes <= 32] against integer labels [B], and
+    the predicted classes [B] (argmax, the first index on a tie), from one launch of the fused HIP kernel.  The loss
+    is differentiable w.r.t. the logits: the kernel computes (softmax - onehot) / B with it.  HIP tensors only."""
+    from .._engine import cross_entropy as fused
+    loss, pred, _ = fused(logits, labels)
+    return loss, pred
 
 
 def get_ratio_loss(loss_type='disc', **kwargs):
