@@ -127,12 +127,23 @@ def _range_guarded(device, state, fn, engines):
     return out
 
 
+def _same_tensors(key, old):
+    """Two _state_key tuples that differ at most in the tensors' version counters."""
+    return [(k, p, d) for k, p, _, d in key] == [(k, p, d) for k, p, _, d in old]
+
+
 class _EngineBase:
+    """Per-module cache of the device handle; subclasses name the ABI family and describe the architecture."""
+    PREFIX = None       # rgfm_<family>_{update_params,destroy,...}
+    DESC_PREFIX = None  # rgfm_<family>_{param_floats,create}, where the descriptor has a family of its own
+
     def __init__(self, module):
         self._module = weakref.ref(module)
         self._handle = None
         self._key = None
         self._blob = None
+        self._layout = None      # per state_dict entry: (numel, is it a parameter?), as of the latest create
+        self._last_train = None  # (weakref of the workspace, batch, handle, family's extra) of the latest forward_train
         self._ws = _Workspace()
 
     # engines are per-module caches: never copied or pickled with the module (engine_property rebuilds them)
@@ -142,11 +153,66 @@ class _EngineBase:
     def __reduce__(self):
         return (type(None), ())
 
+    def _fn(self, name, prefix=None):
+        return getattr(_lib.lib(), f"{prefix or self.PREFIX}_{name}")
+
+    def desc(self):
+        raise NotImplementedError
+
+    def _key_extra(self):
+        """What the handle depends on besides the module's tensors."""
+        return None
+
     def _state_key(self, sd):
         return tuple((k, v.data_ptr(), v._version, str(v.device)) for k, v in sd.items())
 
+    def handle(self, device):
+        """The module's device handle: the cached one while nothing moved, the same one re-packed in place when only
+        the values of the same tensors moved (an optimizer step, the running statistics), a new one otherwise."""
+        m = self._module()
+        sd = m.state_dict()
+        key, extra = self._state_key(sd), self._key_extra()
+        if self._handle is not None and (key, extra) == self._key:
+            return self._handle
+        blob = self._blob_from(sd, device)
+        if self._handle is not None and extra == self._key[1] and _same_tensors(key, self._key[0]):
+            with torch.cuda.device(device):
+                _lib.check(self._fn("update_params")(self._handle, _ptr(blob), blob.numel(), _stream(device)))
+            self._key, self._blob = (key, extra), blob
+            return self._handle
+        if self._handle is not None:
+            self._destroy()
+        d = self.desc()
+        n = ctypes.c_size_t()
+        _lib.check(self._fn("param_floats", self.DESC_PREFIX)(ctypes.byref(d), ctypes.byref(n)))
+        if blob.numel() != n.value:
+            raise _lib.RgfmError(f"parameter blob has {blob.numel()} floats, library expects {n.value}")
+        h = ctypes.c_void_p()
+        with torch.cuda.device(device):
+            _lib.check(self._fn("create", self.DESC_PREFIX)(ctypes.byref(d), _ptr(blob), blob.numel(), _stream(device),
+                                                            ctypes.byref(h)))
+        self._handle, self._key, self._blob = h, (key, extra), blob
+        named = {id(q) for q in m.parameters()}
+        self._layout = [(v.numel(), id(v) in named) for v in m.state_dict(keep_vars=True).values()]
+        return h
+
     def _destroy(self):
-        raise NotImplementedError
+        self._fn("destroy")(self._handle)
+        self._handle = None
+
+    def owns(self, handle):
+        """Is `handle` (as handle() returned it) still alive in this engine?"""
+        return self._handle is handle
+
+    def _saved(self):
+        """(workspace, batch, handle, the family's extra) of the latest forward_train, until its backward has run."""
+        ws = self._last_train[0]() if self._last_train else None
+        if ws is None:
+            raise _lib.RgfmError("no saved state: call this between forward_train and its backward")
+        _, n, h, extra = self._last_train
+        if not self.owns(h):
+            raise _lib.RgfmError("the module's handle was re-created since that forward_train")
+        return ws, n, h, extra
 
     def __del__(self):
         try:
@@ -166,57 +232,108 @@ class _EngineBase:
                 "semantics only (Dropout = identity, BatchNorm = running statistics). Call .eval().")
 
 
-def _same_tensors(key, old):
-    """Two _state_key tuples that differ at most in the tensors' version counters."""
-    return old is not None and [(k, p, d) for k, p, _, d in key] == [(k, p, d) for k, p, _, d in old]
+class _TrainSpec:
+    """What one family contributes to _TrainFn: how many tensors are inputs and how many of them (the leading ones) can
+    get a gradient, the output shape, the arguments of rgfm_<family>_forward_train between the handle and the
+    workspace, whether the pass has dropout, whether it takes the `training` flag and reports BatchNorm statistics,
+    and what it leaves in engine._last_train."""
+
+    def __init__(self, inputs, grads, out_shape, args, dropout=False, batchnorm=False, last=None):
+        self.inputs, self.grads, self.out_shape, self.args = inputs, grads, out_shape, args
+        self.dropout, self.batchnorm, self.last = dropout, batchnorm, last
+
+
+class _TrainFn(torch.autograd.Function):
+    """Training forward / backward of every family through rgfm_<family>_forward_train / rgfm_<family>_backward.
+
+    Inputs: the family's _TrainSpec, the engine, p_drop, the input tensors and the module's parameters (state_dict
+    order), so that autograd hands back the input gradients and every dL/dparam.  Each call owns its saved-state buffer
+    and runs its backward on the handle of its forward; the dropout seed is drawn from the device's torch generator.
+    While a module with BatchNorm trains, its buffers are updated from the batch statistics the library reports."""
+
+    @staticmethod
+    def forward(ctx, spec, engine, p_drop, *tensors):
+        m = engine._module()
+        inputs = [v.contiguous() for v in tensors[:spec.inputs]]
+        dev, n = inputs[0].device, inputs[0].shape[0]
+        out = torch.empty(spec.out_shape(*inputs), device=dev)
+        ctx.spec, ctx.engine, ctx.n, ctx.ws, ctx.nbytes, ctx.h = spec, engine, n, None, 0, None
+        ctx.save_for_backward(*tensors[spec.inputs:])
+        ctx.shapes = [v.shape for v in inputs[:spec.grads]]
+        if n == 0:
+            return out
+        training = spec.batchnorm and bool(m.training)
+        seed = int(torch.randint(0, 2 ** 62, (1,), device=dev).item()) if p_drop > 0 else 0
+        bns = [b for b in m.modules() if isinstance(b, torch.nn.BatchNorm2d)] if training else []
+        stats = torch.empty(2 * sum(b.num_features for b in bns), device=dev) if bns else None
+        with torch.cuda.device(dev):
+            h = engine.handle(dev)
+            nb = ctypes.c_size_t()
+            _lib.check(engine._fn("train_workspace_bytes")(h, n, ctypes.byref(nb)))
+            ws = torch.empty(nb.value, dtype=torch.uint8, device=dev)
+            _lib.check(engine._fn("forward_train")(
+                h, *spec.args(*inputs, out, n, 1 if training else 0, p_drop, seed, _ptr(stats)), _ptr(ws), nb.value,
+                _stream(dev)))
+        off = 0
+        for b in bns:  # nn.BatchNorm2d's update: momentum 0.1, unbiased batch variance
+            st = stats[off:off + 2 * b.num_features].view(-1, 2)
+            off += 2 * b.num_features
+            mom = b.momentum
+            b.running_mean.mul_(1 - mom).add_(st[:, 0], alpha=mom)
+            b.running_var.mul_(1 - mom).add_(st[:, 1], alpha=mom)
+            b.num_batches_tracked.add_(1)
+        ctx.ws, ctx.nbytes, ctx.h, ctx.layout = ws, nb.value, h, engine._layout
+        engine._last_train = (weakref.ref(ws), n, h, spec.last(engine, seed, p_drop) if spec.last else None)
+        return out
+
+    @staticmethod
+    def backward(ctx, dout):
+        spec, params, dev = ctx.spec, ctx.saved_tensors, dout.device
+        need = ctx.needs_input_grad[3:3 + spec.grads]
+        rest = (None,) * (spec.inputs - spec.grads)
+        if ctx.n == 0:
+            dins = [torch.zeros(sh, device=dev) if nd else None for sh, nd in zip(ctx.shapes, need)]
+            return (None, None, None, *dins, *rest, *[torch.zeros_like(q) for q in params])
+        if ctx.ws is None:
+            raise _lib.RgfmError("the saved state of this forward_train call is gone (backward ran twice?)")
+        if not ctx.engine.owns(ctx.h):
+            raise _lib.RgfmError("the module's handle was re-created between forward_train and backward")
+        dout = dout.to(torch.float32).contiguous()
+        dparams = torch.empty(sum(k for k, _ in ctx.layout), device=dev)
+        dins = [torch.empty(sh, device=dev) if nd else None for sh, nd in zip(ctx.shapes, need)]
+        with torch.cuda.device(dev):
+            _lib.check(ctx.engine._fn("backward")(ctx.h, _ptr(dout), *map(_ptr, dins), _ptr(dparams), ctx.n, _ptr(ctx.ws),
+                                                  ctx.nbytes, _stream(dev)))
+        ctx.ws = None
+        chunks = torch.split(dparams, [k for k, _ in ctx.layout])  # the buffers' slots are dropped
+        grads = [g.view(q.shape) for g, q in zip([c for c, (_, is_p) in zip(chunks, ctx.layout) if is_p], params)]
+        return (None, None, None, *dins, *rest, *grads)
 
 
 class _VelocityEngine(_EngineBase):
     """Shared handle cache / forward of the velocity nets; subclasses name the ABI family."""
-    PREFIX = None          # rgfm_<family>_{param_floats,create,destroy,workspace_bytes,forward}
     SINGLE = SINGLE_WS = PAIR = PAIR_WS = None
-    UPDATE = False         # the family has rgfm_<family>_update_params (in-place repack of the same handle)
-
-    def desc(self):
-        raise NotImplementedError
+    TRAIN = None  # the family's _TrainSpec
 
     def _check_input(self, m, x):
         raise NotImplementedError
 
-    def _fn(self, name):
-        return getattr(_lib.lib(), f"{self.PREFIX}_{name}")
+    def _check_xt(self, x, t):
+        """x checked against the module, t flattened to its 1 or B elements; both contiguous."""
+        _require_hip(x, t)
+        self._check_input(self._module(), x)
+        t = t.reshape(-1)
+        if t.numel() not in (1, x.shape[0]):
+            raise _lib.RgfmError(f"t must have 1 or {x.shape[0]} elements, got {t.numel()}")
+        return x.contiguous(), t.contiguous()
 
-    def handle(self, device):
+    def forward_train(self, x, t):
+        """v = model(x, t) on the exact-fp32 training path, differentiable w.r.t. x and the parameters (_TrainFn).  A
+        net with Dropout applies it while the module trains; neither net has batch statistics."""
         m = self._module()
-        sd = m.state_dict()
-        key = self._state_key(sd)
-        if self._handle is not None and key == self._key:
-            return self._handle
-        if self._handle is not None and self.UPDATE and _same_tensors(key, self._key):
-            # only the values moved (an optimizer step, an in-place edit): repack the same handle
-            blob = self._blob_from(sd, device)
-            with torch.cuda.device(device):
-                _lib.check(self._fn("update_params")(self._handle, _ptr(blob), blob.numel(), _stream(device)))
-            self._key, self._blob = key, blob
-            return self._handle
-        if self._handle is not None:
-            self._destroy()
-        d = self.desc()
-        n = ctypes.c_size_t()
-        _lib.check(self._fn("param_floats")(ctypes.byref(d), ctypes.byref(n)))
-        blob = self._blob_from(sd, device)
-        if blob.numel() != n.value:
-            raise _lib.RgfmError(f"parameter blob has {blob.numel()} floats, library expects {n.value}")
-        h = ctypes.c_void_p()
-        with torch.cuda.device(device):
-            _lib.check(self._fn("create")(ctypes.byref(d), _ptr(blob), blob.numel(), _stream(device),
-                                          ctypes.byref(h)))
-        self._handle, self._key, self._blob = h, key, blob
-        return h
-
-    def _destroy(self):
-        self._fn("destroy")(self._handle)
-        self._handle = None
+        x, t = self._check_xt(x, t)
+        p = m.dropout_p() if self.TRAIN.dropout and m.training else 0.0
+        return _TrainFn.apply(self.TRAIN, self, float(p), x, t, *m.parameters())
 
     def workspace(self, fn_name, batch, device):
         L = _lib.lib()
@@ -235,16 +352,9 @@ class _VelocityEngine(_EngineBase):
         _lib.check(self._fn("set_conv_mode")(self.handle(device), int(mode)))
 
     def forward(self, x, t):
-        m = self._module()
-        self._check_eval(m)
-        _require_hip(x, t)
-        self._check_input(m, x)
+        self._check_eval(self._module())
+        x, t = self._check_xt(x, t)
         B = x.shape[0]
-        t = t.reshape(-1)
-        if t.numel() not in (1, B):
-            raise _lib.RgfmError(f"t must have 1 or {B} elements, got {t.numel()}")
-        x = x.contiguous()
-        t = t.contiguous()
         out = torch.empty_like(x)
         if B == 0:
             return out
@@ -265,25 +375,14 @@ class FmNetEngine(_VelocityEngine):
     PREFIX = "rgfm_fmnet"
     SINGLE, SINGLE_WS = "rgfm_fmnet_sample_single", "rgfm_fmnet_workspace_bytes"
     PAIR, PAIR_WS = "rgfm_fmnet_sample_pair", "rgfm_fmnet_sample_pair_workspace_bytes"
-    UPDATE = True
+    TRAIN = _TrainSpec(inputs=2, grads=1, out_shape=lambda x, t: x.shape,
+                       args=lambda x, t, out, n, training, p, seed, stats: (_ptr(x), _ptr(t), t.numel(), _ptr(out), n))
 
     def _check_eval(self, module):
         if module.training:
             raise _lib.RgfmError(
                 f"{type(module).__name__} is in training mode; model(x, t) and the samplers are the eval path. Train "
                 "through model.forward_train(x, t) (HIP backward), or call .eval() to evaluate / sample.")
-
-    # ---- training -----------------------------------------------------
-    def forward_train(self, x, t):
-        """v = model(x, t) on the exact-fp32 training path, differentiable w.r.t. x and the parameters
-        (_FmNetTrainFn).  The net has no Dropout and no batch statistics: the module's mode does not matter."""
-        m = self._module()
-        _require_hip(x, t)
-        self._check_input(m, x)
-        t = t.reshape(-1)
-        if t.numel() not in (1, x.shape[0]):
-            raise _lib.RgfmError(f"t must have 1 or {x.shape[0]} elements, got {t.numel()}")
-        return _FmNetTrainFn.apply(self, x, t, *m.parameters())
 
     def desc(self):
         m = self._module()
@@ -300,7 +399,8 @@ class UNetEngine(_VelocityEngine):
     PREFIX = "rgfm_unet"
     SINGLE, SINGLE_WS = "rgfm_sample_single", "rgfm_sample_single_workspace_bytes"
     PAIR, PAIR_WS = "rgfm_sample_pair", "rgfm_sample_pair_workspace_bytes"
-    UPDATE = True
+    TRAIN = _TrainSpec(inputs=2, grads=1, out_shape=lambda x, t: x.shape, dropout=True,
+                       args=lambda x, t, out, n, training, p, seed, stats: (_ptr(x), _ptr(t), t.numel(), _ptr(out), n, p, seed))
 
     def _check_eval(self, module):
         if module.training:
@@ -309,28 +409,7 @@ class UNetEngine(_VelocityEngine):
                 "(Dropout = identity). Train through model.forward_train(x, t) (HIP backward, dropout), or call "
                 ".eval() to evaluate / sample.")
 
-    # ---- training -----------------------------------------------------
-    def forward_train(self, x, t):
-        """v = model(x, t) in training semantics, differentiable w.r.t. x and the parameters (_UNetTrainFn)."""
-        m = self._module()
-        _require_hip(x, t)
-        self._check_input(m, x)
-        t = t.reshape(-1)
-        if t.numel() not in (1, x.shape[0]):
-            raise _lib.RgfmError(f"t must have 1 or {x.shape[0]} elements, got {t.numel()}")
-        p = m.dropout_p() if m.training else 0.0
-        return _UNetTrainFn.apply(self, x, t, float(p), *m.parameters())
-
     # ---- likelihood: J^T u, divergence, log p(x) -------------------------
-    def _check_xt(self, x, t):
-        m = self._module()
-        _require_hip(x, t)
-        self._check_input(m, x)
-        t = t.reshape(-1)
-        if t.numel() not in (1, x.shape[0]):
-            raise _lib.RgfmError(f"t must have 1 or {x.shape[0]} elements, got {t.numel()}")
-        return x.contiguous(), t.contiguous()
-
     def _check_probes(self, x, eps):
         _require_hip(eps)
         if eps.dim() != 5 or tuple(eps.shape[1:]) != tuple(x.shape) or eps.device != x.device:
@@ -498,109 +577,12 @@ class _Linearization:
         return g
 
 
-class _UNetTrainFn(torch.autograd.Function):
-    """Training forward / backward of FlexibleUNet through rgfm_unet_forward_train / rgfm_unet_backward.
-
-    Inputs: the engine, x, t, p_drop and the module's parameters (state_dict order), so that autograd hands back
-    dL/dx and every dL/dparam.  Each call owns its saved-state buffer; the dropout seed is drawn from the device's
-    torch generator."""
-
-    @staticmethod
-    def forward(ctx, engine, x, t, p_drop, *params):
-        dev = x.device
-        x, t = x.contiguous(), t.contiguous()
-        B = x.shape[0]
-        out = torch.empty_like(x)
-        ctx.engine, ctx.B, ctx.ws, ctx.nbytes = engine, B, None, 0
-        ctx.save_for_backward(*params)
-        if B == 0:
-            return out
-        seed = int(torch.randint(0, 2 ** 62, (1,), device=dev).item()) if p_drop > 0 else 0
-        L = _lib.lib()
-        with torch.cuda.device(dev):
-            h = engine.handle(dev)
-            n = ctypes.c_size_t()
-            _lib.check(L.rgfm_unet_train_workspace_bytes(h, B, ctypes.byref(n)))
-            ws = torch.empty(n.value, dtype=torch.uint8, device=dev)
-            _lib.check(L.rgfm_unet_forward_train(h, _ptr(x), _ptr(t), t.numel(), _ptr(out), B, p_drop, seed, _ptr(ws),
-                                                 n.value, _stream(dev)))
-        ctx.ws, ctx.nbytes = ws, n.value
-        ctx.x_shape = x.shape
-        return out
-
-    @staticmethod
-    def backward(ctx, dv):
-        params = ctx.saved_tensors
-        dev = dv.device
-        grads = [torch.zeros_like(q) for q in params]
-        if ctx.B == 0:
-            return (None, torch.zeros(0, *dv.shape[1:], device=dev) if ctx.needs_input_grad[1] else None, None, None,
-                    *grads)
-        dv = dv.to(torch.float32).contiguous()
-        dparams = torch.empty(sum(q.numel() for q in params), device=dev)
-        dx = torch.empty(ctx.x_shape, device=dev) if ctx.needs_input_grad[1] else None
-        with torch.cuda.device(dev):
-            h = ctx.engine.handle(dev)
-            _lib.check(_lib.lib().rgfm_unet_backward(h, _ptr(dv), _ptr(dx), _ptr(dparams), ctx.B, _ptr(ctx.ws),
-                                                     ctx.nbytes, _stream(dev)))
-        ctx.ws = None
-        grads = [g.view(q.shape) for g, q in zip(torch.split(dparams, [q.numel() for q in params]), params)]
-        return (None, dx, None, None, *grads)
-
-
-class _FmNetTrainFn(torch.autograd.Function):
-    """Training forward / backward of FlowMatchingModel through rgfm_fmnet_forward_train / rgfm_fmnet_backward.
-
-    Inputs: the engine, x, t and the module's parameters (state_dict order), so that autograd hands back dL/dx and
-    every dL/dparam.  Each call owns its saved-state buffer; dL/dx is computed only when x requires it."""
-
-    @staticmethod
-    def forward(ctx, engine, x, t, *params):
-        dev = x.device
-        x, t = x.contiguous(), t.contiguous()
-        B = x.shape[0]
-        out = torch.empty_like(x)
-        ctx.engine, ctx.B, ctx.ws, ctx.nbytes, ctx.h = engine, B, None, 0, None
-        ctx.save_for_backward(*params)
-        ctx.x_shape = x.shape
-        if B == 0:
-            return out
-        L = _lib.lib()
-        with torch.cuda.device(dev):
-            h = engine.handle(dev)
-            n = ctypes.c_size_t()
-            _lib.check(L.rgfm_fmnet_train_workspace_bytes(h, B, ctypes.byref(n)))
-            ws = torch.empty(n.value, dtype=torch.uint8, device=dev)
-            _lib.check(L.rgfm_fmnet_forward_train(h, _ptr(x), _ptr(t), t.numel(), _ptr(out), B, _ptr(ws), n.value,
-                                                  _stream(dev)))
-        ctx.ws, ctx.nbytes, ctx.h = ws, n.value, h
-        return out
-
-    @staticmethod
-    def backward(ctx, dv):
-        params = ctx.saved_tensors
-        dev = dv.device
-        need_x = ctx.needs_input_grad[1]
-        if ctx.B == 0:
-            return (None, torch.zeros(ctx.x_shape, device=dev) if need_x else None, None,
-                    *[torch.zeros_like(q) for q in params])
-        if ctx.ws is None:
-            raise _lib.RgfmError("the saved state of this forward_train call is gone (backward ran twice?)")
-        if ctx.engine._handle is not ctx.h:
-            raise _lib.RgfmError("the module's handle was re-created between forward_train and backward")
-        dv = dv.to(torch.float32).contiguous()
-        dparams = torch.empty(sum(q.numel() for q in params), device=dev)
-        dx = torch.empty(ctx.x_shape, device=dev) if need_x else None
-        with torch.cuda.device(dev):
-            _lib.check(_lib.lib().rgfm_fmnet_backward(ctx.h, _ptr(dv), _ptr(dx), _ptr(dparams), ctx.B, _ptr(ctx.ws),
-                                                      ctx.nbytes, _stream(dev)))
-        ctx.ws = None
-        grads = [g.view(q.shape) for g, q in zip(torch.split(dparams, [q.numel() for q in params]), params)]
-        return (None, dx, None, *grads)
-
-
 class RatioEngine(_EngineBase):
-    PARAM_FLOATS, CREATE = "rgfm_ratio_param_floats", "rgfm_ratio_create"
+    PREFIX = "rgfm_ratio"
+    TRAIN = _TrainSpec(inputs=2, grads=2, out_shape=lambda x, y: x.shape[:1], dropout=True, batchnorm=True,
+                       args=lambda x, y, out, n, training, p, seed, stats: (_ptr(x), _ptr(y), _ptr(out), n, training, p,
+                                                                            seed, stats),
+                       last=lambda engine, seed, p: engine.pool_geometry())
 
     def __init__(self, module, kind):
         super().__init__(module)
@@ -621,45 +603,11 @@ class RatioEngine(_EngineBase):
                 "eval-mode semantics only (Dropout = identity, BatchNorm = running statistics). Train through "
                 "model.forward_train(x, y) (HIP backward, batch statistics, dropout), or call .eval().")
 
-    def handle(self, device):
-        m = self._module()
-        sd = m.state_dict()
-        key = self._state_key(sd) + (m.loss_type,)
-        if self._handle is not None and key == self._key:
-            return self._handle
-        L = _lib.lib()
-        if self._handle is not None and key[-1] == self._key[-1] and _same_tensors(key[:-1], self._key[:-1]):
-            # only the values moved (an optimizer step, the running statistics): repack the same handle
-            blob = self._blob_from(sd, device)
-            with torch.cuda.device(device):
-                _lib.check(L.rgfm_ratio_update_params(self._handle, _ptr(blob), blob.numel(), _stream(device)))
-            self._key, self._blob = key, blob
-            return self._handle
-        if self._handle is not None:
-            self._destroy()
-        d = self.desc()
-        n = ctypes.c_size_t()
-        _lib.check(getattr(L, self.PARAM_FLOATS)(ctypes.byref(d), ctypes.byref(n)))
-        blob = self._blob_from(sd, device)
-        if blob.numel() != n.value:
-            raise _lib.RgfmError(f"parameter blob has {blob.numel()} floats, library expects {n.value}")
-        h = ctypes.c_void_p()
-        with torch.cuda.device(device):
-            _lib.check(getattr(L, self.CREATE)(ctypes.byref(d), _ptr(blob), blob.numel(), _stream(device),
-                                               ctypes.byref(h)))
-        self._handle, self._key, self._blob = h, key, blob
-        return h
-
-    def _destroy(self):
-        _lib.lib().rgfm_ratio_destroy(self._handle)
-        self._handle = None
+    def _key_extra(self):
+        return self._module().loss_type
 
     def bind(self, x, y):
         """Select the handle that serves this pair of inputs (one geometry per fixed kind: nothing to select)."""
-
-    def owns(self, handle):
-        """Is `handle` (as handle() returned it) still alive in this engine?"""
-        return self._handle is handle
 
     # ---- training -----------------------------------------------------
     def image_shapes(self):
@@ -681,11 +629,11 @@ class RatioEngine(_EngineBase):
 
     def forward_train(self, x, y):
         """scores = model(x, y) in the module's current mode, differentiable w.r.t. x, y and the parameters
-        (_RatioTrainFn).  In training mode: batch statistics, dropout, and the BatchNorm buffers are updated."""
+        (_TrainFn).  In training mode: batch statistics, dropout, and the BatchNorm buffers are updated."""
         m = self._module()
         self._check_pair(x, y)
         p = m.dropout_p() if m.training else 0.0
-        return _RatioTrainFn.apply(self, x, y, float(p), *m.parameters())
+        return _TrainFn.apply(self.TRAIN, self, float(p), x, y, *m.parameters())
 
     def dropout_mask(self, block, seed, p, batch, device):
         """Keep decisions (1 / 0) of Dropout layer `block` of the score MLP: [batch, width] (rgfm_ratio_dropout_mask)."""
@@ -700,12 +648,7 @@ class RatioEngine(_EngineBase):
     def pool_choices(self):
         """The window elements (0..3, row-major) the max-pools of the latest forward_train chose, per encoder (x, y) a
         list of [B, C, Ho, Wo] tensors (rgfm_ratio_pool_choice).  Valid until that call's backward has run."""
-        ws, n = (self._last_train[0](), self._last_train[1]) if getattr(self, "_last_train", None) else (None, 0)
-        if ws is None:
-            raise _lib.RgfmError("no saved state: call pool_choices() between forward_train and its backward")
-        h, geometry = self._last_train[2], self._last_train[3]
-        if not self.owns(h):
-            raise _lib.RgfmError("the module's handle was re-created since that forward_train")
+        ws, n, h, geometry = self._saved()
         dev = ws.device
         out = []
         with torch.cuda.device(dev):
@@ -882,7 +825,7 @@ class FlexibleRatioEngine(RatioEngine):
     """RatioEngine of FlexibleRatioEstimator.  The module is size-agnostic, a device handle is not (its rasters, tilings
     and workspaces follow from the image sizes): bind() reads (x_size, y_size) from the inputs of a call and handle()
     serves the handle of the bound pair, keeping one per pair seen -- alternating between sizes re-creates nothing."""
-    PARAM_FLOATS, CREATE = "rgfm_ratio_flex_param_floats", "rgfm_ratio_flex_create"
+    DESC_PREFIX = "rgfm_ratio_flex"
 
     def __init__(self, module):
         super().__init__(module, "flexible")
@@ -956,76 +899,6 @@ class FlexibleRatioEngine(RatioEngine):
         return tuple([(32, s // 2), (64, s // 4), (128, s // 8)] for s in (sx, sy))
 
 
-class _RatioTrainFn(torch.autograd.Function):
-    """Training forward / backward of the ratio estimators through rgfm_ratio_forward_train / rgfm_ratio_backward.
-
-    Inputs: the engine, x, y, p_drop and the module's parameters, so that autograd hands back dL/dx, dL/dy and every
-    dL/dparam.  Each call owns its saved-state buffer; the dropout seed is drawn from the device's torch generator.
-    While the module trains, the BatchNorm buffers are updated from the batch statistics the library reports."""
-
-    @staticmethod
-    def forward(ctx, engine, x, y, p_drop, *params):
-        m = engine._module()
-        dev = x.device
-        x, y = x.contiguous(), y.contiguous()
-        n = x.shape[0]
-        out = torch.empty(n, device=dev)
-        ctx.engine, ctx.n, ctx.ws, ctx.nbytes, ctx.h = engine, n, None, 0, None
-        ctx.save_for_backward(*params)
-        ctx.shapes = (x.shape, y.shape)
-        if n == 0:
-            return out
-        training = bool(m.training)
-        seed = int(torch.randint(0, 2 ** 62, (1,), device=dev).item()) if p_drop > 0 else 0
-        bns = [b for b in m.modules() if isinstance(b, torch.nn.BatchNorm2d)] if training else []
-        stats = torch.empty(2 * sum(b.num_features for b in bns), device=dev) if bns else None
-        named = {id(q) for q in m.parameters()}
-        ctx.layout = [(v.numel(), id(v) in named) for v in m.state_dict(keep_vars=True).values()]
-        L = _lib.lib()
-        with torch.cuda.device(dev):
-            h = engine.handle(dev)
-            nb = ctypes.c_size_t()
-            _lib.check(L.rgfm_ratio_train_workspace_bytes(h, n, ctypes.byref(nb)))
-            ws = torch.empty(nb.value, dtype=torch.uint8, device=dev)
-            _lib.check(L.rgfm_ratio_forward_train(h, _ptr(x), _ptr(y), _ptr(out), n, 1 if training else 0, p_drop, seed,
-                                                  _ptr(stats), _ptr(ws), nb.value, _stream(dev)))
-        off = 0
-        for b in bns:  # nn.BatchNorm2d's update: momentum 0.1, unbiased batch variance
-            st = stats[off:off + 2 * b.num_features].view(-1, 2)
-            off += 2 * b.num_features
-            mom = b.momentum
-            b.running_mean.mul_(1 - mom).add_(st[:, 0], alpha=mom)
-            b.running_var.mul_(1 - mom).add_(st[:, 1], alpha=mom)
-            b.num_batches_tracked.add_(1)
-        ctx.ws, ctx.nbytes, ctx.h = ws, nb.value, h
-        engine._last_train = (weakref.ref(ws), n, h, engine.pool_geometry())
-        return out
-
-    @staticmethod
-    def backward(ctx, dscore):
-        params = ctx.saved_tensors
-        dev = dscore.device
-        need_x, need_y = ctx.needs_input_grad[1], ctx.needs_input_grad[2]
-        if ctx.n == 0:
-            return (None, torch.zeros(ctx.shapes[0], device=dev) if need_x else None,
-                    torch.zeros(ctx.shapes[1], device=dev) if need_y else None, None, *[torch.zeros_like(q) for q in params])
-        if ctx.ws is None:
-            raise _lib.RgfmError("the saved state of this forward_train call is gone (backward ran twice?)")
-        if not ctx.engine.owns(ctx.h):
-            raise _lib.RgfmError("the module's handle was re-created between forward_train and backward")
-        dscore = dscore.to(torch.float32).contiguous()
-        dparams = torch.empty(sum(k for k, _ in ctx.layout), device=dev)
-        dx = torch.empty(ctx.shapes[0], device=dev) if need_x else None
-        dy = torch.empty(ctx.shapes[1], device=dev) if need_y else None
-        with torch.cuda.device(dev):
-            _lib.check(_lib.lib().rgfm_ratio_backward(ctx.h, _ptr(dscore), _ptr(dx), _ptr(dy), _ptr(dparams), ctx.n,
-                                                      _ptr(ctx.ws), ctx.nbytes, _stream(dev)))
-        ctx.ws = None
-        chunks = torch.split(dparams, [k for k, _ in ctx.layout])
-        grads = [g.view(q.shape) for g, q in zip([c for c, (_, is_p) in zip(chunks, ctx.layout) if is_p], params)]
-        return (None, dx, dy, None, *grads)
-
-
 _CLF_KIND = {"mnist28": 0, "mnist32": 1, "svhn": 2}
 # kind: (image shape, per conv block (channels, output size, max-pool behind it), fc1 width)
 _CLF_GEOMETRY = {
@@ -1039,49 +912,19 @@ class ClassifierEngine(_EngineBase):
     """Training pass of the evaluation classifiers (rgfm_clf_*): one handle per module, re-packed in place when
     only the values of its parameters moved."""
 
+    PREFIX = "rgfm_clf"
+    TRAIN = _TrainSpec(inputs=1, grads=1, out_shape=lambda x: (x.shape[0], 10), dropout=True, batchnorm=True,
+                       args=lambda x, out, n, training, p, seed, stats: (_ptr(x), _ptr(out), n, training, seed, p, stats),
+                       last=lambda engine, seed, p: (seed, p))
+
     def __init__(self, module, kind):
         super().__init__(module)
         self.kind = kind
-        self._last_train = None
 
     def desc(self):
         d = _lib.ClfDesc()
         d.kind = _CLF_KIND[self.kind]
         return d
-
-    def handle(self, device):
-        sd = self._module().state_dict()
-        key = self._state_key(sd)
-        if self._handle is not None and key == self._key:
-            return self._handle
-        L = _lib.lib()
-        blob = self._blob_from(sd, device)
-        if self._handle is not None and _same_tensors(key, self._key):
-            # only the values moved (an optimizer step, the running statistics): refresh the same handle
-            with torch.cuda.device(device):
-                _lib.check(L.rgfm_clf_update_params(self._handle, _ptr(blob), blob.numel(), _stream(device)))
-            self._key, self._blob = key, blob
-            return self._handle
-        if self._handle is not None:
-            self._destroy()
-        d = self.desc()
-        n = ctypes.c_size_t()
-        _lib.check(L.rgfm_clf_param_floats(ctypes.byref(d), ctypes.byref(n)))
-        if blob.numel() != n.value:
-            raise _lib.RgfmError(f"parameter blob has {blob.numel()} floats, library expects {n.value}")
-        h = ctypes.c_void_p()
-        with torch.cuda.device(device):
-            _lib.check(L.rgfm_clf_create(ctypes.byref(d), _ptr(blob), blob.numel(), _stream(device), ctypes.byref(h)))
-        self._handle, self._key, self._blob = h, key, blob
-        return h
-
-    def _destroy(self):
-        _lib.lib().rgfm_clf_destroy(self._handle)
-        self._handle = None
-
-    def owns(self, handle):
-        """Is `handle` (as handle() returned it) still alive in this engine?"""
-        return self._handle is handle
 
     def image_shape(self):
         return _CLF_GEOMETRY[self.kind][0]
@@ -1093,7 +936,7 @@ class ClassifierEngine(_EngineBase):
         return [((c, s, s), pool) for c, s, pool in blocks] + [((hidden,), False)]
 
     def forward_train(self, x):
-        """logits = model(x) in the module's current mode, differentiable w.r.t. x and the parameters (_ClfTrainFn).
+        """logits = model(x) in the module's current mode, differentiable w.r.t. x and the parameters (_TrainFn).
         In training mode: batch statistics, dropout, and the BatchNorm buffers are updated."""
         m = self._module()
         _require_hip(x)
@@ -1101,21 +944,12 @@ class ClassifierEngine(_EngineBase):
         if x.dim() != 4 or tuple(x.shape[1:]) != (c, s, s):
             raise _lib.RgfmError(f"expected images of shape [B,{c},{s},{s}], got {tuple(x.shape)}")
         p = m.dropout_p() if m.training else 0.0
-        return _ClfTrainFn.apply(self, x, float(p), *m.parameters())
-
-    def _saved(self):
-        ws = self._last_train[0]() if self._last_train else None
-        if ws is None:
-            raise _lib.RgfmError("no saved state: call this between forward_train and its backward")
-        n, h = self._last_train[1], self._last_train[2]
-        if not self.owns(h):
-            raise _lib.RgfmError("the module's handle was re-created since that forward_train")
-        return ws, n, h
+        return _TrainFn.apply(self.TRAIN, self, float(p), x, *m.parameters())
 
     def pool_choices(self):
         """The window elements (0..3, row-major) the max-pools of the latest forward_train chose: per conv block a
         [B, C, Ho, Wo] tensor, or None where no pool follows (rgfm_clf_pool_choice).  Valid until that call's backward."""
-        ws, n, h = self._saved()
+        ws, n, h, _ = self._saved()
         out = []
         with torch.cuda.device(ws.device):
             for i, (shape, pool) in enumerate(self.layer_shapes()[:-1]):
@@ -1128,7 +962,7 @@ class ClassifierEngine(_EngineBase):
     def gates(self):
         """1.0 where the ReLU of the latest forward_train passed: per conv block on its output raster (behind a pool:
         the gate of the element taken), then fc1's [B, hidden] before the dropout (rgfm_clf_gate)."""
-        ws, n, h = self._saved()
+        ws, n, h, _ = self._saved()
         out = []
         with torch.cuda.device(ws.device):
             for i, (shape, _) in enumerate(self.layer_shapes()):
@@ -1149,74 +983,6 @@ class ClassifierEngine(_EngineBase):
         with torch.cuda.device(device):
             _lib.check(_lib.lib().rgfm_clf_dropout_mask(self.handle(device), int(seed), float(p), int(batch), _ptr(out)))
         return out
-
-
-class _ClfTrainFn(torch.autograd.Function):
-    """Training forward / backward of the classifiers through rgfm_clf_forward_train / rgfm_clf_backward.
-
-    Inputs: the engine, x, p_drop and the module's parameters, so that autograd hands back dL/dx and every dL/dparam.
-    Each call owns its saved-state buffer; the dropout seed is drawn from the device's torch generator.  While the
-    module trains, the BatchNorm buffers are updated from the batch statistics the library reports."""
-
-    @staticmethod
-    def forward(ctx, engine, x, p_drop, *params):
-        m = engine._module()
-        dev = x.device
-        x = x.contiguous()
-        n = x.shape[0]
-        out = torch.empty(n, 10, device=dev)
-        ctx.engine, ctx.n, ctx.ws, ctx.nbytes, ctx.h = engine, n, None, 0, None
-        ctx.save_for_backward(*params)
-        ctx.shape = x.shape
-        if n == 0:
-            return out
-        training = bool(m.training)
-        seed = int(torch.randint(0, 2 ** 62, (1,), device=dev).item()) if p_drop > 0 else 0
-        bns = [b for b in m.modules() if isinstance(b, torch.nn.BatchNorm2d)] if training else []
-        stats = torch.empty(2 * sum(b.num_features for b in bns), device=dev) if bns else None
-        named = {id(q) for q in m.parameters()}
-        ctx.layout = [(v.numel(), id(v) in named) for v in m.state_dict(keep_vars=True).values()]
-        L = _lib.lib()
-        with torch.cuda.device(dev):
-            h = engine.handle(dev)
-            nb = ctypes.c_size_t()
-            _lib.check(L.rgfm_clf_train_workspace_bytes(h, n, ctypes.byref(nb)))
-            ws = torch.empty(nb.value, dtype=torch.uint8, device=dev)
-            _lib.check(L.rgfm_clf_forward_train(h, _ptr(x), _ptr(out), n, 1 if training else 0, seed, p_drop,
-                                                _ptr(stats), _ptr(ws), nb.value, _stream(dev)))
-        off = 0
-        for b in bns:  # nn.BatchNorm2d's update: momentum 0.1, unbiased batch variance
-            st = stats[off:off + 2 * b.num_features].view(-1, 2)
-            off += 2 * b.num_features
-            mom = b.momentum
-            b.running_mean.mul_(1 - mom).add_(st[:, 0], alpha=mom)
-            b.running_var.mul_(1 - mom).add_(st[:, 1], alpha=mom)
-            b.num_batches_tracked.add_(1)
-        ctx.ws, ctx.nbytes, ctx.h = ws, nb.value, h
-        engine._last_train = (weakref.ref(ws), n, h, (seed, p_drop))
-        return out
-
-    @staticmethod
-    def backward(ctx, dlogits):
-        params = ctx.saved_tensors
-        dev = dlogits.device
-        need_x = ctx.needs_input_grad[1]
-        if ctx.n == 0:
-            return (None, torch.zeros(ctx.shape, device=dev) if need_x else None, None, *[torch.zeros_like(q) for q in params])
-        if ctx.ws is None:
-            raise _lib.RgfmError("the saved state of this forward_train call is gone (backward ran twice?)")
-        if not ctx.engine.owns(ctx.h):
-            raise _lib.RgfmError("the module's handle was re-created between forward_train and backward")
-        dlogits = dlogits.to(torch.float32).contiguous()
-        dparams = torch.empty(sum(k for k, _ in ctx.layout), device=dev)
-        dx = torch.empty(ctx.shape, device=dev) if need_x else None
-        with torch.cuda.device(dev):
-            _lib.check(_lib.lib().rgfm_clf_backward(ctx.h, _ptr(dlogits), _ptr(dx), _ptr(dparams), ctx.n, _ptr(ctx.ws),
-                                                    ctx.nbytes, _stream(dev)))
-        ctx.ws = None
-        chunks = torch.split(dparams, [k for k, _ in ctx.layout])
-        grads = [g.view(q.shape) for g, q in zip([c for c, (_, is_p) in zip(chunks, ctx.layout) if is_p], params)]
-        return (None, dx, None, *grads)
 
 
 class _XentFn(torch.autograd.Function):

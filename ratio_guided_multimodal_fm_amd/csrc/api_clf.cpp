@@ -10,7 +10,7 @@
 // (mean, rstd) pairs where it has a BatchNorm, the activated (and pooled) map with the pool's choices, fc1's output u
 // and its activated, dropped-out map), then the SCRATCH of the backward (the forward keeps a conv output that no
 // BatchNorm needs again there too).  The flatten is NCHW order, so fc1 consumes the last map in place.
-#include "rgfm_host.h"
+#include "train_host.h"
 
 struct rgfm_clf {
   rgfm_clf_desc d;
@@ -74,99 +74,56 @@ size_t plan_clf(const rgfm_clf_desc& d, rgfm_clf* h) {
   return c.off;
 }
 
-struct CConv {
-  const rgfm_clf::Conv* cv;
-  int Cin, C, S, So;  // So: raster of the block's output (S / 2 behind a pool)
-  size_t in, z, mr, a, choice;
-  size_t stats;  // floats before this layer's pairs in bn_stats_out
-};
 struct CPlan {
-  std::vector<CConv> convs;
+  std::vector<TrainBlock> convs;
   size_t hdr, img, u, a1, saved;
   size_t G0, G1, part, bnpart, m12, dA;
   size_t total;  // floats
 };
 
-UgConv conv_of(const rgfm_clf* h, const CConv& r, int n) {
-  UgConv c{};
-  c.w = h->params + r.cv->w, c.bias = h->params + r.cv->b;
-  c.B = n, c.Cin = r.Cin, c.Cout = r.C, c.taps = 9, c.stride = 1, c.up = 0;
-  c.Hs = c.Ws = c.Hc = c.Wc = c.Ho = c.Wo = r.S;
-  c.C0 = r.Cin;
-  c.splits = 1;
-  return c;
-}
-
-// the three GEMMs of fc1 (fmnet_grad.hip); pointers are filled in by the caller
-FgGemm clf_gemm(int M, int N, int K, int lda, int ldb, int ldc, bool split) {
-  FgGemm g{};
-  g.M = M, g.N = N, g.K = K, g.lda = lda, g.ldb = ldb, g.ldc = ldc;
-  g.splits = 1, g.kps = (K + 15) / 16 * 16;
-  if (split) fg_split(g);
-  return g;
-}
-FgGemm fc1_fwd(const rgfm_clf* h, int n) { return clf_gemm(n, h->hidden, h->flat, h->flat, h->flat, h->hidden, true); }
-FgGemm fc1_dgrad(const rgfm_clf* h, int n) { return clf_gemm(n, h->flat, h->hidden, h->hidden, h->flat, h->flat, false); }
-FgGemm fc1_wgrad(const rgfm_clf* h, int n) { return clf_gemm(h->hidden, h->flat, n, h->hidden, h->flat, h->flat, false); }
+// the three GEMMs of fc1
+FgGemm fc1_fwd(const rgfm_clf* h, int n) { return fg_gemm_of(n, h->hidden, h->flat, h->flat, h->flat, h->hidden, true); }
+FgGemm fc1_dgrad(const rgfm_clf* h, int n) { return fg_gemm_of(n, h->flat, h->hidden, h->hidden, h->flat, h->flat, false); }
+FgGemm fc1_wgrad(const rgfm_clf* h, int n) { return fg_gemm_of(h->hidden, h->flat, n, h->hidden, h->flat, h->flat, false); }
 
 // every region starts on a 16-byte boundary of the workspace (the 16-byte accesses of clf_train.hip and fg_gemm_kernel)
 CPlan plan_ct(const rgfm_clf* h, int n) {
   CPlan p;
   Cursor c;
   auto take = [&](size_t k) { return c.take((k + 3) & ~(size_t)3); };
-  size_t mx = 1, mxC = 1, mx_part = 1, stats = 0;
+  TrainBlockMax m;
   p.hdr = take(64);
   p.img = take((size_t)n * h->in_ch * h->size * h->size);
-  size_t in = p.img;
-  int Cin = h->in_ch, S = h->size;
   for (const rgfm_clf::Conv& cv : h->convs) {
-    CConv r{};
-    r.cv = &cv, r.Cin = Cin, r.C = cv.cout, r.S = S, r.So = cv.pool_after ? S / 2 : S;
-    r.in = in;
-    if (h->bn) r.z = take((size_t)n * r.C * S * S), r.mr = take((size_t)r.C * 2);
-    r.a = take((size_t)n * r.C * r.So * r.So);
-    r.choice = cv.pool_after ? take(((size_t)n * r.C * r.So * r.So + 3) / 4) : 0;
-    r.stats = stats;
-    stats += (size_t)r.C * 2;
-    mx = std::max(mx, (size_t)n * r.C * S * S);
-    mxC = std::max(mxC, (size_t)r.C);
-    UgConv u = conv_of(h, r, n);
-    wgrad_split(u);
-    mx_part = std::max(mx_part, (size_t)u.splits * r.C * Cin * 9);
+    TrainBlock r{};
+    r.w = cv.w, r.b = cv.b, r.nw = cv.nw, r.nb = cv.nb, r.rm = cv.rm, r.rv = cv.rv, r.C = cv.cout, r.pool = cv.pool_after;
     p.convs.push_back(r);
-    in = r.a, Cin = r.C, S = r.So;
   }
+  p.convs[0].Cin = h->in_ch, p.convs[0].S = h->size, p.convs[0].in = p.img;
+  plan_blocks(p.convs, n, take, h->bn ? NORM_BATCH : NORM_NONE, m);
   p.u = take((size_t)n * h->hidden), p.a1 = take((size_t)n * h->hidden);
   p.saved = c.off;
-  p.G0 = take(mx), p.G1 = take(mx);
+  p.G0 = take(m.mx), p.G1 = take(m.mx);
   const FgGemm g = fc1_fwd(h, n);
-  mx_part = std::max(mx_part, (size_t)g.splits * g.M * g.N);
-  p.part = take(mx_part);
-  p.bnpart = take(mxC * RT_BN_SLICES * 3);
-  p.m12 = take(mxC * 2);
+  p.part = take(std::max(m.mx_part, (size_t)g.splits * g.M * g.N));
+  p.bnpart = take(m.mxC * RT_BN_SLICES * 3);
+  p.m12 = take(m.mxC * 2);
   p.dA = take((size_t)n * h->hidden);
   p.total = c.off;
   return p;
 }
 
-CtAct act_of(const rgfm_clf* h, const CConv& r, int n, const float* z, const float* W) {
+CtAct act_of(const rgfm_clf* h, const TrainBlock& r, int n, const float* z, const float* W) {
   CtAct a{};
   a.z = z, a.B = n, a.C = r.C, a.H = a.W = r.S;
-  if (h->bn) a.mr = W + r.mr, a.gamma = h->params + r.cv->nw, a.beta = h->params + r.cv->nb;
+  if (h->bn) a.mr = W + r.mr, a.gamma = h->params + r.nw, a.beta = h->params + r.nb;
   return a;
 }
 
 int check_ct(const rgfm_clf* h, int n, const void* ws, size_t ws_bytes) {
   if (!h || n < 1) return fail(RGFM_EINVAL, "bad argument");
-  const size_t need = plan_ct(h, n).total * sizeof(float);
-  if (!ws) return fail(RGFM_EINVAL, "null workspace");
-  if (ws_bytes < need) return fail(RGFM_ENOMEM, "training workspace too small: %zu < %zu bytes", ws_bytes, need);
-  if (reinterpret_cast<uintptr_t>(ws) % 16 != 0) return fail(RGFM_EINVAL, "the training workspace must be 16-byte aligned");
-  return RGFM_OK;
+  return check_train_ws(plan_ct(h, n).total * sizeof(float), ws, ws_bytes, 16);
 }
-
-// header words: {p_drop bits, seed lo, seed hi, 0, training}
-constexpr int HDR_TRAINING = 4;
 
 }  // namespace
 
@@ -223,23 +180,22 @@ extern "C" int rgfm_clf_forward_train(rgfm_clf* h, const float* x, float* logits
                                       float p_drop, float* bn_stats_out, void* ws, size_t ws_bytes, rgfm_stream_t stream) {
   if (int rc = check_ct(h, n, ws, ws_bytes)) return rc;
   if (!x || !logits_out) return fail(RGFM_EINVAL, "bad argument");
-  if (!(p_drop >= 0.f && p_drop < 1.f)) return fail(RGFM_EINVAL, "p_drop must be in [0, 1)");
+  if (int rc = check_p_drop(p_drop)) return rc;
   hipStream_t s = (hipStream_t)stream;
   const CPlan p = plan_ct(h, n);
   float* W = (float*)ws;
   const float* P = h->params;
   unsigned* hdr = (unsigned*)(W + p.hdr);
-  launch_ug_header(hdr, training ? p_drop : 0.f, seed, s);
-  HIP_TRY(hipMemsetD32Async((hipDeviceptr_t)(hdr + HDR_TRAINING), training ? 1 : 0, 1, s));
+  if (int rc = write_train_header(hdr, training, p_drop, seed, s)) return rc;
   HIP_TRY(hipMemcpyAsync(W + p.img, x, (size_t)n * h->in_ch * h->size * h->size * sizeof(float), hipMemcpyDeviceToDevice, s));
-  for (const CConv& r : p.convs) {
+  for (const TrainBlock& r : p.convs) {
     float* z = W + (h->bn ? r.z : p.G0);
-    run_fwd(conv_of(h, r, n), W + r.in, z, nullptr, nullptr, s);
+    run_fwd(conv_of(P, r, n), W + r.in, z, nullptr, nullptr, s);
     if (h->bn && training)
       launch_rt_bn_stats(z, n, r.C, r.S * r.S, W + p.bnpart, W + r.mr, bn_stats_out ? bn_stats_out + r.stats : nullptr, s);
-    else if (h->bn) launch_rt_bn_running(P + r.cv->rm, P + r.cv->rv, r.C, W + r.mr, s);
+    else if (h->bn) launch_rt_bn_running(P + r.rm, P + r.rv, r.C, W + r.mr, s);
     const CtAct a = act_of(h, r, n, z, W);
-    if (r.cv->pool_after) launch_ct_act_pool(a, W + r.a, (unsigned char*)(W + r.choice), s);
+    if (r.pool) launch_ct_act_pool(a, W + r.a, (unsigned char*)(W + r.choice), s);
     else launch_ct_act(a, W + r.a, s);
   }
   FgGemm g = fc1_fwd(h, n);
@@ -277,9 +233,9 @@ extern "C" int rgfm_clf_backward(rgfm_clf* h, const float* dlogits, float* dx_ou
   launch_fg_gemm(g, false, true, s);
   // the conv blocks, backwards.  cur: gradient of the block's output
   for (int i = (int)p.convs.size() - 1; i >= 0; --i) {
-    const CConv& r = p.convs[i];
+    const TrainBlock& r = p.convs[i];
     const float* gate = W + r.a;  // the gate the BatchNorm backward still has to apply, or null
-    if (r.cv->pool_after) {
+    if (r.pool) {
       launch_ct_unpool_gate(cur, (const unsigned char*)(W + r.choice), W + r.a, other, n * r.C, r.S, r.S, s);
       std::swap(cur, other);
       gate = nullptr;
@@ -287,16 +243,9 @@ extern "C" int rgfm_clf_backward(rgfm_clf* h, const float* dlogits, float* dx_ou
       launch_ct_gate(cur, W + r.a, (size_t)n * r.C * r.S * r.S, s);
     }
     if (h->bn)
-      launch_ct_bn_bwd(act_of(h, r, n, W + r.z, W), cur, gate, hdr + HDR_TRAINING, W + p.bnpart, W + p.m12, D + r.cv->nw,
-                       D + r.cv->nb, s);
-    const UgConv c = conv_of(h, r, n);
-    run_wgrad(c, cur, W + r.in, W + p.part, D + r.cv->w, D + r.cv->b, s);
-    if (i > 0) {
-      run_dgrad(c, cur, other, nullptr, r.Cin, 0, s);
-      std::swap(cur, other);
-    } else if (dx_out) {
-      run_dgrad(c, cur, dx_out, nullptr, r.Cin, 0, s);
-    }
+      launch_ct_bn_bwd(act_of(h, r, n, W + r.z, W), cur, gate, hdr + HDR_TRAINING, W + p.bnpart, W + p.m12, D + r.nw,
+                       D + r.nb, s);
+    block_grads(conv_of(P, r, n), r, W, p.part, D, cur, other, i > 0 ? other : dx_out, s);
   }
   HIP_TRY(hipGetLastError());
   return RGFM_OK;
@@ -318,7 +267,7 @@ extern "C" int rgfm_clf_pool_choice(rgfm_clf* h, const void* ws, int layer, int 
   if (layer < 0 || layer >= (int)h->convs.size() || !h->convs[layer].pool_after)
     return fail(RGFM_EINVAL, "conv block %d has no max-pool", layer);
   const CPlan p = plan_ct(h, n);
-  const CConv& r = p.convs[layer];
+  const TrainBlock& r = p.convs[layer];
   launch_rt_choice((const unsigned char*)((const float*)ws + r.choice), (size_t)n * r.C * r.So * r.So, out, nullptr);
   HIP_TRY(hipGetLastError());
   return RGFM_OK;
@@ -338,7 +287,7 @@ extern "C" int rgfm_clf_gate(rgfm_clf* h, const void* ws, int layer, int n, floa
 
 extern "C" int rgfm_clf_dropout_mask(rgfm_clf* h, uint64_t seed, float p_drop, int n, float* out) {
   if (!h || !out || n < 1) return fail(RGFM_EINVAL, "bad argument");
-  if (!(p_drop >= 0.f && p_drop < 1.f)) return fail(RGFM_EINVAL, "p_drop must be in [0, 1)");
+  if (int rc = check_p_drop(p_drop)) return rc;
   launch_ug_mask(out, (size_t)n * h->hidden, seed, 0, p_drop, nullptr);
   HIP_TRY(hipGetLastError());
   return RGFM_OK;

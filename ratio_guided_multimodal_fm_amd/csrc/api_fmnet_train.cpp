@@ -12,7 +12,7 @@
 // E: [Cout][2S][2S] -> [Cin][S][S] whose weight [E.Cout = Cin][E.Cin = Cout][16] is the same array.  So on
 // ug_igemm_kernel: its forward is E's op 1 (fed the layer's input as `dy`, plus the bias), its data gradient E's op 0
 // (fed the output gradient as `x`), its weight gradient E's op 2 with the two exchanged.
-#include "rgfm_host.h"
+#include "train_host.h"
 
 namespace {
 
@@ -59,22 +59,15 @@ FmConvs fm_convs(const rgfm_fmnet* h, int B) {
   return v;
 }
 
-// the six GEMMs of the two Linears (fmnet_grad.hip); pointers are filled in by the caller
-FgGemm fm_gemm(int M, int N, int K, int lda, int ldb, int ldc, bool split) {
-  FgGemm g{};
-  g.M = M, g.N = N, g.K = K, g.lda = lda, g.ldb = ldb, g.ldc = ldc;
-  g.splits = 1, g.kps = (K + 15) / 16 * 16;
-  if (split) fg_split(g);
-  return g;
-}
+// the six GEMMs of the two Linears
 constexpr int FM_FLAT = FM_CF * FM_P;  // 12544
-FgGemm fc_fwd(int B, int F, int T) { return fm_gemm(B, F, FM_FLAT, FM_FLAT, FM_FLAT, F + T, true); }
-FgGemm fc_dgrad(int B, int F) { return fm_gemm(B, FM_FLAT, F, F, FM_FLAT, FM_FLAT, false); }
-FgGemm fc_wgrad(int B, int F) { return fm_gemm(F, FM_FLAT, B, F, FM_FLAT, FM_FLAT, false); }
-FgGemm fc1_fwd(int B, int F, int T) { return fm_gemm(B, FM_FLAT, F + T, F + T, F + T, FM_FLAT, false); }
+FgGemm fc_fwd(int B, int F, int T) { return fg_gemm_of(B, F, FM_FLAT, FM_FLAT, FM_FLAT, F + T, true); }
+FgGemm fc_dgrad(int B, int F) { return fg_gemm_of(B, FM_FLAT, F, F, FM_FLAT, FM_FLAT, false); }
+FgGemm fc_wgrad(int B, int F) { return fg_gemm_of(F, FM_FLAT, B, F, FM_FLAT, FM_FLAT, false); }
+FgGemm fc1_fwd(int B, int F, int T) { return fg_gemm_of(B, FM_FLAT, F + T, F + T, F + T, FM_FLAT, false); }
 // (only the first F columns of the concat's gradient exist: t has none)
-FgGemm fc1_dgrad(int B, int F, int T) { return fm_gemm(B, F, FM_FLAT, FM_FLAT, F + T, F, true); }
-FgGemm fc1_wgrad(int B, int F, int T) { return fm_gemm(FM_FLAT, F + T, B, FM_FLAT, F + T, F + T, false); }
+FgGemm fc1_dgrad(int B, int F, int T) { return fg_gemm_of(B, F, FM_FLAT, FM_FLAT, F + T, F, true); }
+FgGemm fc1_wgrad(int B, int F, int T) { return fg_gemm_of(FM_FLAT, F + T, B, FM_FLAT, F + T, F + T, false); }
 
 FmTrainPlan plan_train(const rgfm_fmnet* h, int B) {
   FmTrainPlan p;
@@ -113,9 +106,7 @@ UgAct act_of(const float* z, int C, int B, int HW, const float* mr, const float*
 
 int check_train(const rgfm_fmnet* h, int batch, void* ws, size_t ws_bytes) {
   if (!h || batch < 1) return fail(RGFM_EINVAL, "bad argument");
-  const size_t need = plan_train(h, batch).total * sizeof(float);
-  if (!ws || ws_bytes < need) return fail(RGFM_ENOMEM, "training workspace too small: %zu < %zu bytes", ws_bytes, need);
-  return RGFM_OK;
+  return check_train_ws(plan_train(h, batch).total * sizeof(float), ws, ws_bytes);
 }
 
 // weight gradient of a transposed conv: E's op 2 with the layer's input as `dy` and the output gradient as `x`; the

@@ -8,19 +8,13 @@
 // by plan_rt: first the SAVED state (header, both images, per conv its input, its output z, the norm's (mean, rstd)
 // pairs, the activated (and pooled) map with the pool's choices, the score MLP's pre-norm tensors and row statistics),
 // then the backward's SCRATCH.
-#include "rgfm_host.h"
+#include "train_host.h"
 
 namespace {
 
-struct RConv {
-  const rgfm_ratio::Conv* cv;
-  int Cin, C, S, So;  // So: raster of the block's output (S / 2 behind a pool)
-  size_t in, z, mr, a, choice;
-  size_t stats;  // floats before this layer's pairs in bn_stats_out
-};
 struct REnc {
   const rgfm_ratio::Encoder* e;
-  std::vector<RConv> convs;
+  std::vector<TrainBlock> convs;
   size_t img, pooled, feat;
   int C, S;  // of the last block's output
 };
@@ -39,48 +33,27 @@ struct RPlan {
 
 bool is_bn(const rgfm_ratio* h) { return !h->gn_encoders(); }
 
-UgConv conv_of(const rgfm_ratio* h, const RConv& r, int n) {
-  UgConv c{};
-  c.w = h->params + r.cv->w.w_raw, c.bias = h->params + r.cv->w.b;
-  c.B = n, c.Cin = r.Cin, c.Cout = r.C, c.taps = 9, c.stride = 1, c.up = 0;
-  c.Hs = c.Ws = c.Hc = c.Wc = c.Ho = c.Wo = r.S;
-  c.C0 = r.Cin;
-  c.splits = 1;
-  return c;
-}
-
 RPlan plan_rt(const rgfm_ratio* h, int n) {
   RPlan p;
   Cursor c;
   const int F = h->d.feature_dim;
-  size_t mx = 1, mxC = 1, mx_part = 1, stats = 0;
+  auto take = [&](size_t k) { return c.take(k); };
+  TrainBlockMax m;
   p.hdr = c.take(64);
   const rgfm_ratio::Encoder* encs[2] = {&h->ex, &h->ey};
   for (int k = 0; k < 2; ++k) {
     REnc& e = p.enc[k];
     e.e = encs[k];
-    int S = e.e->size, Cin = e.e->in_ch;
-    e.img = c.take((size_t)n * Cin * S * S);
-    size_t in = e.img;
+    e.img = c.take((size_t)n * e.e->in_ch * e.e->size * e.e->size);
     for (const rgfm_ratio::Conv& cv : e.e->convs) {
-      RConv r{};
-      r.cv = &cv, r.Cin = Cin, r.C = cv.w.cout, r.S = S, r.So = cv.pool_after ? S / 2 : S;
-      r.in = in;
-      r.z = c.take((size_t)n * r.C * S * S);
-      r.mr = c.take(is_bn(h) ? (size_t)r.C * 2 : (size_t)n * 8 * 2);
-      r.a = c.take((size_t)n * r.C * r.So * r.So);
-      r.choice = cv.pool_after ? c.take(((size_t)n * r.C * r.So * r.So + 3) / 4) : 0;
-      r.stats = stats;
-      stats += (size_t)r.C * 2;
-      mx = std::max(mx, (size_t)n * r.C * S * S);
-      mxC = std::max(mxC, (size_t)r.C);
-      UgConv u = conv_of(h, r, n);
-      wgrad_split(u);
-      mx_part = std::max(mx_part, (size_t)u.splits * r.C * Cin * 9);
+      TrainBlock r{};
+      r.w = cv.w.w_raw, r.b = cv.w.b, r.nw = cv.nw, r.nb = cv.nb, r.rm = cv.rm, r.rv = cv.rv, r.C = cv.w.cout;
+      r.pool = cv.pool_after;
       e.convs.push_back(r);
-      in = r.a, Cin = r.C, S = r.So;
     }
-    e.C = Cin, e.S = S;
+    e.convs[0].Cin = e.e->in_ch, e.convs[0].S = e.e->size, e.convs[0].in = e.img;
+    plan_blocks(e.convs, n, take, is_bn(h) ? NORM_BATCH : 8, m);
+    e.C = e.convs.back().C, e.S = e.convs.back().So;
     e.pooled = c.take((size_t)n * e.C);
     e.feat = c.take((size_t)n * F);
   }
@@ -97,8 +70,9 @@ RPlan plan_rt(const rgfm_ratio* h, int n) {
     in = dn.a;
   }
   p.saved = c.off;
-  p.G0 = c.take(mx), p.G1 = c.take(mx);
-  p.part = c.take(mx_part);
+  const size_t mxC = m.mxC;
+  p.G0 = c.take(m.mx), p.G1 = c.take(m.mx);
+  p.part = c.take(m.mx_part);
   p.bnpart = c.take(mxC * RT_BN_SLICES * 3);
   p.m12 = c.take(mxC * 2);
   p.pg = c.take((size_t)n * std::max(mxC, width)), p.pb = c.take((size_t)n * std::max(mxC, width));
@@ -110,22 +84,17 @@ RPlan plan_rt(const rgfm_ratio* h, int n) {
   return p;
 }
 
-RtNorm norm_of(const rgfm_ratio* h, const RConv& r, int n, const float* W) {
+RtNorm norm_of(const rgfm_ratio* h, const TrainBlock& r, int n, const float* W) {
   RtNorm a{};
-  a.z = W + r.z, a.mr = W + r.mr, a.gamma = h->params + r.cv->nw, a.beta = h->params + r.cv->nb;
+  a.z = W + r.z, a.mr = W + r.mr, a.gamma = h->params + r.nw, a.beta = h->params + r.nb;
   a.B = n, a.C = r.C, a.H = a.W = r.S, a.groups = is_bn(h) ? 0 : 8;
   return a;
 }
 
 int check_rt(const rgfm_ratio* h, int n, void* ws, size_t ws_bytes) {
   if (!h || n < 1) return fail(RGFM_EINVAL, "bad argument");
-  const size_t need = plan_rt(h, n).total * sizeof(float);
-  if (!ws || ws_bytes < need) return fail(RGFM_ENOMEM, "training workspace too small: %zu < %zu bytes", ws_bytes, need);
-  return RGFM_OK;
+  return check_train_ws(plan_rt(h, n).total * sizeof(float), ws, ws_bytes);
 }
-
-// header words: {p_drop bits, seed lo, seed hi, 0, training}
-constexpr int HDR_TRAINING = 4;
 
 }  // namespace
 
@@ -140,28 +109,27 @@ extern "C" int rgfm_ratio_forward_train(rgfm_ratio* h, const float* x, const flo
                                         size_t ws_bytes, rgfm_stream_t stream) {
   if (int rc = check_rt(h, n, ws, ws_bytes)) return rc;
   if (!x || !y || !score_out) return fail(RGFM_EINVAL, "bad argument");
-  if (!(p_drop >= 0.f && p_drop < 1.f)) return fail(RGFM_EINVAL, "p_drop must be in [0, 1)");
+  if (int rc = check_p_drop(p_drop)) return rc;
   hipStream_t s = (hipStream_t)stream;
   const RPlan p = plan_rt(h, n);
   const int F = h->d.feature_dim;
   float* W = (float*)ws;
   const float* P = h->params;
   unsigned* hdr = (unsigned*)(W + p.hdr);
-  launch_ug_header(hdr, training ? p_drop : 0.f, seed, s);
-  HIP_TRY(hipMemsetD32Async((hipDeviceptr_t)(hdr + HDR_TRAINING), training ? 1 : 0, 1, s));
+  if (int rc = write_train_header(hdr, training, p_drop, seed, s)) return rc;
   const float* img[2] = {x, y};
   for (int k = 0; k < 2; ++k) {
     const REnc& e = p.enc[k];
     HIP_TRY(hipMemcpyAsync(W + e.img, img[k], (size_t)n * e.e->in_ch * e.e->size * e.e->size * sizeof(float),
                            hipMemcpyDeviceToDevice, s));
-    for (const RConv& r : e.convs) {
-      run_fwd(conv_of(h, r, n), W + r.in, W + r.z, nullptr, nullptr, s);
+    for (const TrainBlock& r : e.convs) {
+      run_fwd(conv_of(P, r, n), W + r.in, W + r.z, nullptr, nullptr, s);
       if (!is_bn(h)) launch_ug_gn_stats(W + r.z, nullptr, r.C, 0, n, r.S * r.S, 8, W + r.mr, s);
       else if (training)
         launch_rt_bn_stats(W + r.z, n, r.C, r.S * r.S, W + p.bnpart, W + r.mr, bn_stats_out ? bn_stats_out + r.stats : nullptr, s);
-      else launch_rt_bn_running(P + r.cv->rm, P + r.cv->rv, r.C, W + r.mr, s);
+      else launch_rt_bn_running(P + r.rm, P + r.rv, r.C, W + r.mr, s);
       const RtNorm a = norm_of(h, r, n, W);
-      if (r.cv->pool_after) launch_rt_norm_act_pool(a, W + r.a, (unsigned char*)(W + r.choice), s);
+      if (r.pool) launch_rt_norm_act_pool(a, W + r.a, (unsigned char*)(W + r.choice), s);
       else launch_rt_norm_act(a, W + r.a, s);
     }
     launch_rt_avgpool(W + e.convs.back().a, n * e.C, e.S * e.S, W + e.pooled, s);
@@ -218,32 +186,25 @@ extern "C" int rgfm_ratio_backward(rgfm_ratio* h, const float* dscore, float* dx
     float *cur = W + p.G0, *other = W + p.G1;
     launch_rt_avgpool_bwd(W + p.gpool, n * e.C, e.S * e.S, cur, s);
     for (int i = (int)e.convs.size() - 1; i >= 0; --i) {
-      const RConv& r = e.convs[i];
-      if (r.cv->pool_after) {
+      const TrainBlock& r = e.convs[i];
+      if (r.pool) {
         launch_rt_unpool(cur, (const unsigned char*)(W + r.choice), other, n * r.C, r.S, r.S, s);
         std::swap(cur, other);
       }
       // cur: gradient of silu(norm(z)) on the conv's raster -> gradient of z
       const RtNorm a = norm_of(h, r, n, W);
       if (is_bn(h)) {
-        launch_rt_bn_bwd(a, cur, hdr + HDR_TRAINING, W + p.bnpart, W + p.m12, D + r.cv->nw, D + r.cv->nb, s);
+        launch_rt_bn_bwd(a, cur, hdr + HDR_TRAINING, W + p.bnpart, W + p.m12, D + r.nw, D + r.nb, s);
       } else {
         UgAct g{};
         g.s0 = a.z, g.C0 = r.C, g.B = n, g.HW = r.S * r.S, g.groups = 8, g.mr = a.mr, g.gamma = a.gamma, g.beta = a.beta;
         g.block = -1;
         launch_ug_gn_act_bwd(g, cur, other, nullptr, 0, 0, W + p.pg, W + p.pb, s);
-        launch_ug_colsum(W + p.pg, n, r.C, D + r.cv->nw, s);
-        launch_ug_colsum(W + p.pb, n, r.C, D + r.cv->nb, s);
+        launch_ug_colsum(W + p.pg, n, r.C, D + r.nw, s);
+        launch_ug_colsum(W + p.pb, n, r.C, D + r.nb, s);
         std::swap(cur, other);
       }
-      const UgConv c = conv_of(h, r, n);
-      run_wgrad(c, cur, W + r.in, W + p.part, D + r.cv->w.w_raw, D + r.cv->w.b, s);
-      if (i > 0) {
-        run_dgrad(c, cur, other, nullptr, r.Cin, 0, s);
-        std::swap(cur, other);
-      } else if (dimg[k]) {
-        run_dgrad(c, cur, dimg[k], nullptr, r.Cin, 0, s);
-      }
+      block_grads(conv_of(P, r, n), r, W, p.part, D, cur, other, i > 0 ? other : dimg[k], s);
     }
   }
   HIP_TRY(hipGetLastError());
@@ -254,8 +215,8 @@ extern "C" int rgfm_ratio_pool_choice(rgfm_ratio* h, const void* ws, int encoder
   if (!h || !ws || !out || n < 1 || encoder < 0 || encoder > 1 || pool < 0) return fail(RGFM_EINVAL, "bad argument");
   const RPlan p = plan_rt(h, n);
   int seen = 0;
-  for (const RConv& r : p.enc[encoder].convs)
-    if (r.cv->pool_after && seen++ == pool) {
+  for (const TrainBlock& r : p.enc[encoder].convs)
+    if (r.pool && seen++ == pool) {
       launch_rt_choice((const unsigned char*)((const float*)ws + r.choice), (size_t)n * r.C * r.So * r.So, out, nullptr);
       HIP_TRY(hipGetLastError());
       return RGFM_OK;
@@ -265,7 +226,7 @@ extern "C" int rgfm_ratio_pool_choice(rgfm_ratio* h, const void* ws, int encoder
 
 extern "C" int rgfm_ratio_dropout_mask(rgfm_ratio* h, int block, uint64_t seed, float p_drop, int n, float* out) {
   if (!h || !out || n < 1) return fail(RGFM_EINVAL, "bad argument");
-  if (!(p_drop >= 0.f && p_drop < 1.f)) return fail(RGFM_EINVAL, "p_drop must be in [0, 1)");
+  if (int rc = check_p_drop(p_drop)) return rc;
   if (block < 0 || block > 1) return fail(RGFM_EINVAL, "block %d out of range (the score MLP has 2 Dropout layers)", block);
   launch_ug_mask(out, (size_t)n * h->hidden[block].out, seed, block, p_drop, nullptr);
   HIP_TRY(hipGetLastError());

@@ -7,7 +7,7 @@
 // caller's workspace, laid out by plan_train: first the SAVED state (dropout header, x, the time path, every tensor
 // the walk produces, and per ResBlock the group statistics of both norms, the time projection and conv1's output),
 // then the backward's SCRATCH (one gradient buffer per produced tensor and a few transient maps).
-#include "rgfm_host.h"
+#include "train_host.h"
 
 namespace {
 
@@ -162,11 +162,9 @@ UgAct act_of(const float* s0, const float* s1, int C0, int C1, int B, int HW, co
   return a;
 }
 
-int check_train(const rgfm_unet* h, int batch, void* ws, size_t ws_bytes, size_t* need) {
+int check_train(const rgfm_unet* h, int batch, void* ws, size_t ws_bytes) {
   if (!h || batch < 1) return fail(RGFM_EINVAL, "bad argument");
-  *need = plan_train(h, batch).total * sizeof(float);
-  if (!ws || ws_bytes < *need) return fail(RGFM_ENOMEM, "training workspace too small: %zu < %zu bytes", ws_bytes, *need);
-  return RGFM_OK;
+  return check_train_ws(plan_train(h, batch).total * sizeof(float), ws, ws_bytes);
 }
 
 // The training forward over the planned workspace W.  keep_x: copy x into the saved state (the weight gradient of the
@@ -419,26 +417,23 @@ extern "C" int rgfm_unet_train_workspace_bytes(const rgfm_unet* h, int batch, si
 extern "C" int rgfm_unet_forward_train(rgfm_unet* h, const float* x, const float* t_dev, int t_count, float* v_out,
                                        int batch, float p_drop, uint64_t seed, void* ws, size_t ws_bytes,
                                        rgfm_stream_t stream) {
-  size_t need = 0;
-  if (int rc = check_train(h, batch, ws, ws_bytes, &need)) return rc;
+  if (int rc = check_train(h, batch, ws, ws_bytes)) return rc;
   if (!x || !t_dev || !v_out || (t_count != 1 && t_count != batch)) return fail(RGFM_EINVAL, "bad argument");
-  if (!(p_drop >= 0.f && p_drop < 1.f)) return fail(RGFM_EINVAL, "p_drop must be in [0, 1)");
+  if (int rc = check_p_drop(p_drop)) return rc;
   return forward_walk(h, x, true, t_dev, t_count, v_out, batch, p_drop, seed, (float*)ws, plan_train(h, batch),
                       (hipStream_t)stream);
 }
 
 extern "C" int rgfm_unet_backward(rgfm_unet* h, const float* dv, float* dx_out, float* dparams_out, int batch,
                                   void* ws, size_t ws_bytes, rgfm_stream_t stream) {
-  size_t need = 0;
-  if (int rc = check_train(h, batch, ws, ws_bytes, &need)) return rc;
+  if (int rc = check_train(h, batch, ws, ws_bytes)) return rc;
   if (!dv || !dparams_out) return fail(RGFM_EINVAL, "bad argument");
   return backward_walk(h, dv, dx_out, dparams_out, batch, (float*)ws, plan_train(h, batch), (hipStream_t)stream);
 }
 
 extern "C" int rgfm_unet_vjp(rgfm_unet* h, const float* u, float* dx_out, int batch, void* ws, size_t ws_bytes,
                              rgfm_stream_t stream) {
-  size_t need = 0;
-  if (int rc = check_train(h, batch, ws, ws_bytes, &need)) return rc;
+  if (int rc = check_train(h, batch, ws, ws_bytes)) return rc;
   if (!u || !dx_out) return fail(RGFM_EINVAL, "bad argument");
   return backward_walk(h, u, dx_out, nullptr, batch, (float*)ws, plan_train(h, batch), (hipStream_t)stream);
 }
@@ -520,7 +515,7 @@ extern "C" int rgfm_unet_log_prob(rgfm_unet* h, const float* x, const float* eps
 
 extern "C" int rgfm_unet_dropout_mask(rgfm_unet* h, int block, uint64_t seed, float p_drop, int batch, float* out) {
   if (!h || !out || batch < 1) return fail(RGFM_EINVAL, "bad argument");
-  if (!(p_drop >= 0.f && p_drop < 1.f)) return fail(RGFM_EINVAL, "p_drop must be in [0, 1)");
+  if (int rc = check_p_drop(p_drop)) return rc;
   const TrainPlan p = plan_train(h, batch);
   for (const TOp& o : p.ops)
     if (o.kind == OP_RES && o.block == block) {

@@ -85,7 +85,7 @@ def test_training_exports_reject_bad_arguments():
 def test_module_and_engine_offer_the_training_path():
     m = make_module("fm_original")
     assert callable(m.forward_train)
-    assert type(m._engine).UPDATE is True
+    assert callable(m._engine._fn("update_params"))  # (an optimizer step repacks the same handle)
     with pytest.raises(_lib.RgfmError, match="HIP device"):
         m.forward_train(torch.zeros(2, 1, 28, 28), torch.zeros(2))
 
