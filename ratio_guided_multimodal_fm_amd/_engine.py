@@ -397,8 +397,9 @@ class FmNetEngine(_VelocityEngine):
 
 class UNetEngine(_VelocityEngine):
     PREFIX = "rgfm_unet"
-    SINGLE, SINGLE_WS = "rgfm_sample_single", "rgfm_sample_single_workspace_bytes"
-    PAIR, PAIR_WS = "rgfm_sample_pair", "rgfm_sample_pair_workspace_bytes"
+    # (the *_ode entry points take the solver id; with RGFM_SOLVER_EULER they are the Euler loops, bit for bit)
+    SINGLE, SINGLE_WS = "rgfm_sample_single_ode", "rgfm_sample_single_ode_workspace_bytes"
+    PAIR, PAIR_WS = "rgfm_sample_pair_ode", "rgfm_sample_pair_ode_workspace_bytes"
     TRAIN = _TrainSpec(inputs=2, grads=1, out_shape=lambda x, t: x.shape, dropout=True,
                        args=lambda x, t, out, n, training, p, seed, stats: (_ptr(x), _ptr(t), t.numel(), _ptr(out), n, p, seed))
 
@@ -1039,6 +1040,22 @@ def _solver(solver, *models):
     return sid
 
 
+def _run_loop(fn, ws_fn, ws_args, args, steps, sid, dev, ws=None):
+    """One native sampler loop: the size query `ws_fn`(*ws_args[, sid]), the workspace (`ws`: a _Workspace; default the
+    samplers' shared one), then `fn`(*args, *steps[, sid], workspace, stream).  `steps`: (step_begin, step_end).  sid
+    None: entry points without a solver argument (the FlowMatchingModel loops)."""
+    L = _lib.lib()
+    tail = () if sid is None else (sid,)
+    nb = ctypes.c_size_t()
+    _lib.check(getattr(L, ws_fn)(*ws_args, *tail, ctypes.byref(nb)))
+    buf = (ws or _sampler_ws).get(nb.value, dev)
+    _lib.check(getattr(L, fn)(*args, int(steps[0]), int(steps[1]), *tail, _ptr(buf), nb.value, _stream(dev)))
+
+
+def _solver_arg(engine, sid):
+    return sid if isinstance(engine, UNetEngine) else None
+
+
 def sample_single(model, x, num_steps, step_begin=0, step_end=None, solver='euler'):
     """In-place unguided integration of `x` (rgfm_sample_single; solver='midpoint': rgfm_sample_single_ode)."""
     _solver(solver, model)
@@ -1062,17 +1079,8 @@ def _sample_single(model, x, num_steps, step_begin=0, step_end=None, solver='eul
         return x
     with torch.cuda.device(dev):
         h = eng.handle(dev)
-        if sid:
-            L = _lib.lib()
-            n = ctypes.c_size_t()
-            _lib.check(L.rgfm_sample_single_ode_workspace_bytes(h, B, sid, ctypes.byref(n)))
-            ws = eng._ws.get(n.value, dev)
-            _lib.check(L.rgfm_sample_single_ode(h, _ptr(x), B, int(num_steps), int(step_begin), int(step_end), sid,
-                                                _ptr(ws), n.value, _stream(dev)))
-            return x
-        ws, nb = eng.workspace(eng.SINGLE_WS, B, dev)
-        _lib.check(getattr(_lib.lib(), eng.SINGLE)(h, _ptr(x), B, int(num_steps), int(step_begin),
-                                                   int(step_end), _ptr(ws), nb, _stream(dev)))
+        _run_loop(eng.SINGLE, eng.SINGLE_WS, (h, B), (h, _ptr(x), B, int(num_steps)), (step_begin, step_end),
+                  _solver_arg(eng, sid), dev, ws=eng._ws)
     return x
 
 
@@ -1087,14 +1095,10 @@ def _sample_two(fm_x, x, fm_y, y, num_steps, solver):
     if not (x.is_contiguous() and y.is_contiguous()):
         raise _lib.RgfmError("x and y must be contiguous (they are updated in place)")
     dev = x.device
-    L = _lib.lib()
     with torch.cuda.device(dev):
         hx, hy = fm_x._engine.handle(dev), fm_y._engine.handle(dev)
-        nb = ctypes.c_size_t()
-        _lib.check(L.rgfm_sample_two_workspace_bytes(hx, hy, x.shape[0], y.shape[0], sid, ctypes.byref(nb)))
-        ws = _sampler_ws.get(nb.value, dev)
-        _lib.check(L.rgfm_sample_two(hx, hy, _ptr(x), _ptr(y), x.shape[0], y.shape[0], int(num_steps), 0, int(num_steps), sid,
-                                     _ptr(ws), nb.value, _stream(dev)))
+        _run_loop("rgfm_sample_two", "rgfm_sample_two_workspace_bytes", (hx, hy, x.shape[0], y.shape[0]),
+                  (hx, hy, _ptr(x), _ptr(y), x.shape[0], y.shape[0], int(num_steps)), (0, num_steps), sid, dev)
     return x, y
 
 
@@ -1154,27 +1158,14 @@ def sample_pair(fm_x, fm_y, x, y, mc_x1, mc_y1, mc_ratios, num_steps, gamma, ste
     n_mc = 0 if mc_x1 is None else mc_x1.shape[0]
     if n_mc:
         mc_x1, mc_y1, mc_ratios = mc_x1.contiguous(), mc_y1.contiguous(), mc_ratios.contiguous()
-    L = _lib.lib()
 
     def run():
         with torch.cuda.device(dev):
             hx, hy = fm_x._engine.handle(dev), fm_y._engine.handle(dev)
-            nb = ctypes.c_size_t()
-            if sid:
-                _lib.check(L.rgfm_sample_pair_ode_workspace_bytes(hx, hy, B, n_mc, sid, ctypes.byref(nb)))
-                ws = _sampler_ws.get(nb.value, dev)
-                _lib.check(L.rgfm_sample_pair_ode(hx, hy, _ptr(x), _ptr(y), _ptr(mc_x1 if n_mc else None),
-                                                  _ptr(mc_y1 if n_mc else None), _ptr(mc_ratios if n_mc else None), n_mc,
-                                                  B, int(num_steps), float(gamma), int(step_begin), int(step_end), sid,
-                                                  _ptr(ws), nb.value, _stream(dev)))
-                return x, y
-            _lib.check(getattr(L, ex.PAIR_WS)(hx, hy, B, n_mc, ctypes.byref(nb)))
-            ws = _sampler_ws.get(nb.value, dev)
-            _lib.check(getattr(L, ex.PAIR)(hx, hy, _ptr(x), _ptr(y), _ptr(mc_x1 if n_mc else None),
-                                          _ptr(mc_y1 if n_mc else None),
-                                          _ptr(mc_ratios if n_mc else None), n_mc, B, int(num_steps),
-                                          float(gamma), int(step_begin), int(step_end), _ptr(ws),
-                                          nb.value, _stream(dev)))
+            _run_loop(ex.PAIR, ex.PAIR_WS, (hx, hy, B, n_mc),
+                      (hx, hy, _ptr(x), _ptr(y), _ptr(mc_x1 if n_mc else None), _ptr(mc_y1 if n_mc else None),
+                       _ptr(mc_ratios if n_mc else None), n_mc, B, int(num_steps), float(gamma)),
+                      (step_begin, step_end), _solver_arg(ex, sid), dev)
         return x, y
     return _range_guarded(dev, [x, y], run, [fm_x._engine, fm_y._engine])
 
@@ -1196,22 +1187,12 @@ def sample_pair_grad(fm_x, fm_y, ratio_estimator, x, y, num_steps, gamma, step_b
     B, dev = x.shape[0], x.device
     if B == 0:
         return x, y
-    L = _lib.lib()
 
     def run():
         with torch.cuda.device(dev):
             hx, hy, hr = fm_x._engine.handle(dev), fm_y._engine.handle(dev), ratio_estimator._engine.handle(dev)
-            nb = ctypes.c_size_t()
-            if sid:
-                _lib.check(L.rgfm_sample_pair_grad_ode_workspace_bytes(hx, hy, hr, B, sid, ctypes.byref(nb)))
-                ws = _sampler_ws.get(nb.value, dev)
-                _lib.check(L.rgfm_sample_pair_grad_ode(hx, hy, hr, _ptr(x), _ptr(y), B, int(num_steps), float(gamma),
-                                                       int(step_begin), int(step_end), sid, _ptr(ws), nb.value, _stream(dev)))
-                return x, y
-            _lib.check(L.rgfm_sample_pair_grad_workspace_bytes(hx, hy, hr, B, ctypes.byref(nb)))
-            ws = _sampler_ws.get(nb.value, dev)
-            _lib.check(L.rgfm_sample_pair_grad(hx, hy, hr, _ptr(x), _ptr(y), B, int(num_steps), float(gamma),
-                                               int(step_begin), int(step_end), _ptr(ws), nb.value, _stream(dev)))
+            _run_loop("rgfm_sample_pair_grad_ode", "rgfm_sample_pair_grad_ode_workspace_bytes", (hx, hy, hr, B),
+                      (hx, hy, hr, _ptr(x), _ptr(y), B, int(num_steps), float(gamma)), (step_begin, step_end), sid, dev)
         return x, y
     return _range_guarded(dev, [x, y], run, [fm_x._engine, fm_y._engine])
 
@@ -1256,22 +1237,13 @@ def sample_cond(model, s, mc_set, ratios, num_steps, gamma, step_begin=0, step_e
     if B == 0:
         return s
     mc_set, ratios = mc_set.contiguous(), ratios.contiguous()
-    L = _lib.lib()
 
     def run():
         with torch.cuda.device(dev):
             h = eng.handle(dev)
-            nb = ctypes.c_size_t()
-            if sid:
-                _lib.check(L.rgfm_sample_cond_ode_workspace_bytes(h, B, N, sid, ctypes.byref(nb)))
-                ws = _sampler_ws.get(nb.value, dev)
-                _lib.check(L.rgfm_sample_cond_ode(h, _ptr(s), _ptr(mc_set), _ptr(ratios), N, B, int(num_steps), float(gamma),
-                                                  int(step_begin), int(step_end), sid, _ptr(ws), nb.value, _stream(dev)))
-                return s
-            _lib.check(L.rgfm_sample_cond_workspace_bytes(h, B, N, ctypes.byref(nb)))
-            ws = _sampler_ws.get(nb.value, dev)
-            _lib.check(L.rgfm_sample_cond(h, _ptr(s), _ptr(mc_set), _ptr(ratios), N, B, int(num_steps), float(gamma),
-                                          int(step_begin), int(step_end), _ptr(ws), nb.value, _stream(dev)))
+            _run_loop("rgfm_sample_cond_ode", "rgfm_sample_cond_ode_workspace_bytes", (h, B, N),
+                      (h, _ptr(s), _ptr(mc_set), _ptr(ratios), N, B, int(num_steps), float(gamma)),
+                      (step_begin, step_end), sid, dev)
         return s
     return _range_guarded(dev, [s], run, [eng])
 
@@ -1303,22 +1275,12 @@ def sample_cond_grad(model, ratio_estimator, s, ctx, given, num_steps, gamma, st
     if B == 0:
         return s
     ctx = ctx.contiguous()
-    L = _lib.lib()
 
     def run():
         with torch.cuda.device(dev):
             h, hr = eng.handle(dev), re.handle(dev)
-            nb = ctypes.c_size_t()
-            if sid:
-                _lib.check(L.rgfm_sample_cond_grad_ode_workspace_bytes(h, hr, gi, B, sid, ctypes.byref(nb)))
-                ws = _sampler_ws.get(nb.value, dev)
-                _lib.check(L.rgfm_sample_cond_grad_ode(h, hr, _ptr(s), _ptr(ctx), gi, B, int(num_steps), float(gamma),
-                                                       int(step_begin), int(step_end), sid, _ptr(ws), nb.value, _stream(dev)))
-                return s
-            _lib.check(L.rgfm_sample_cond_grad_workspace_bytes(h, hr, gi, B, ctypes.byref(nb)))
-            ws = _sampler_ws.get(nb.value, dev)
-            _lib.check(L.rgfm_sample_cond_grad(h, hr, _ptr(s), _ptr(ctx), gi, B, int(num_steps), float(gamma),
-                                               int(step_begin), int(step_end), _ptr(ws), nb.value, _stream(dev)))
+            _run_loop("rgfm_sample_cond_grad_ode", "rgfm_sample_cond_grad_ode_workspace_bytes", (h, hr, gi, B),
+                      (h, hr, _ptr(s), _ptr(ctx), gi, B, int(num_steps), float(gamma)), (step_begin, step_end), sid, dev)
         return s
     return _range_guarded(dev, [s], run, [eng])
 

@@ -1,6 +1,6 @@
 // api_fmnet.cpp -- FlowMatchingModel ("--model original"): handle, weight packing, forward, samplers (C ABI:
 // include/rgfm.h).  The training pass: api_fmnet_train.cpp.
-#include "rgfm_host.h"
+#include "sampler_host.h"
 
 // ================================================================== FlowMatchingModel ("--model original")
 // Encoder-decoder velocity net of src/models/flow_matching.py:34-173, 1x28x28 images.
@@ -174,11 +174,34 @@ struct FmRun {
   }
 };
 
-size_t fm_eval_bytes(rgfm_fmnet* h, int B) {
-  Bump b;
+// one evaluation's activations, from the Bump's current offset (the walk of FmRun, run dry)
+void fm_carve_eval(Bump& b, rgfm_fmnet* h, int B) {
   FmRun r{h, B, &b, nullptr, true, nullptr, 1, 1, 0};
   r.run(nullptr, nullptr, nullptr, 0.f);
-  return b.off;
+}
+
+// workspace of one net (forward, single loop): its arrival counters, then the evaluation region from *mark
+unsigned* fm_carve(Bump& b, rgfm_fmnet* h, int B, size_t* mark) {
+  unsigned* cnt = b.u(B);
+  *mark = b.off;
+  fm_carve_eval(b, h, B);
+  return cnt;
+}
+
+struct FmPairWs {
+  float *vx, *vy, *logp;
+  unsigned *cnt_x, *cnt_y;
+  size_t mark_x, mark_y;
+};
+FmPairWs fm_carve_pair(Bump& b, rgfm_fmnet* hx, rgfm_fmnet* hy, int batch, int n_mc) {
+  FmPairWs w{};
+  w.vx = b.f((size_t)batch * FM_S * FM_S);
+  w.vy = b.f((size_t)batch * FM_S * FM_S);
+  w.logp = b.f(guid_scratch_bytes(batch, n_mc) / sizeof(float));
+  w.cnt_x = b.u(batch), w.cnt_y = b.u(batch);
+  w.mark_x = b.off, fm_carve_eval(b, hx, batch);  // the two nets run concurrently: disjoint regions
+  w.mark_y = b.off, fm_carve_eval(b, hy, batch);
+  return w;
 }
 
 }  // namespace
@@ -279,7 +302,10 @@ extern "C" int rgfm_fmnet_range_flag(rgfm_fmnet* h, int* flagged, int reset, rgf
 
 extern "C" int rgfm_fmnet_workspace_bytes(const rgfm_fmnet* h, int batch, size_t* bytes) {
   if (!h || !bytes || batch < 1) return fail(RGFM_EINVAL, "bad argument");
-  *bytes = fm_eval_bytes(const_cast<rgfm_fmnet*>(h), batch) + counter_bytes(batch);
+  Bump b;
+  size_t mark;
+  fm_carve(b, const_cast<rgfm_fmnet*>(h), batch, &mark);
+  *bytes = b.off;
   return RGFM_OK;
 }
 
@@ -288,11 +314,11 @@ extern "C" int rgfm_fmnet_forward(rgfm_fmnet* h, const float* x, const float* t_
   refresh_modes();
   if (!h || !x || !t_dev || !v_out || !ws) return fail(RGFM_EINVAL, "null argument");
   if (batch < 1 || (t_count != 1 && t_count != batch)) return fail(RGFM_EINVAL, "t_count must be 1 or batch");
-  const size_t need = fm_eval_bytes(h, batch) + counter_bytes(batch);
-  if (need > ws_bytes) return fail(RGFM_ENOMEM, "workspace too small: %zu < %zu", ws_bytes, need);
-  Bump b;
-  b.base = (char*)ws, b.cap = ws_bytes, b.dry = false;
-  unsigned* cnt = reinterpret_cast<unsigned*>(b.f(batch));
+  Bump b(ws, ws_bytes);
+  size_t mark;
+  unsigned* cnt = fm_carve(b, h, batch, &mark);
+  if (int rc = check_workspace(b, ws_bytes)) return rc;
+  b.off = mark;
   HIP_TRY(hipMemsetAsync(cnt, 0, (size_t)batch * sizeof(unsigned), (hipStream_t)stream));
   FmRun r{h, batch, &b, (hipStream_t)stream, false, t_dev, t_count, 1, 0};
   r.fin_counter = cnt;
@@ -302,28 +328,26 @@ extern "C" int rgfm_fmnet_forward(rgfm_fmnet* h, const float* x, const float* t_
   return RGFM_OK;
 }
 
+// The FlowMatchingModel loops: Euler only, the time embedded per evaluation (no table: the stage's row is its step).
 extern "C" int rgfm_fmnet_sample_single(rgfm_fmnet* h, float* x_inout, int batch, int num_steps, int step_begin,
                                         int step_end, void* ws, size_t ws_bytes, rgfm_stream_t stream) {
   refresh_modes();
-  if (!h || !x_inout || !ws) return fail(RGFM_EINVAL, "null argument");
-  if (batch < 1 || num_steps < 1 || step_begin < 0 || step_end > num_steps || step_begin > step_end)
-    return fail(RGFM_EINVAL, "bad step range [%d,%d) of %d", step_begin, step_end, num_steps);
-  const size_t need = fm_eval_bytes(h, batch) + counter_bytes(batch);
-  if (need > ws_bytes) return fail(RGFM_ENOMEM, "workspace too small: %zu < %zu", ws_bytes, need);
-  const float dt = (float)(1.0 / (double)num_steps);
-  unsigned* cnt = nullptr;
-  for (int st = step_begin; st < step_end; ++st) {
-    Bump b;
-    b.base = (char*)ws, b.cap = ws_bytes, b.dry = false;
-    unsigned* c0 = reinterpret_cast<unsigned*>(b.f(batch));
-    if (!cnt) {
-      cnt = c0;
-      HIP_TRY(hipMemsetAsync(cnt, 0, (size_t)batch * sizeof(unsigned), (hipStream_t)stream));
-    }
-    FmRun r{h, batch, &b, (hipStream_t)stream, false, nullptr, 1, num_steps, st};
+  int ns = 0;
+  if (int rc = check_loop(SOLVER_EULER, h && x_inout && ws, batch, num_steps, step_begin, step_end, &ns, false))
+    return rc;
+  Bump b(ws, ws_bytes);
+  size_t mark;
+  unsigned* cnt = fm_carve(b, h, batch, &mark);
+  if (int rc = check_workspace(b, ws_bytes)) return rc;
+  if (ns == 0) return RGFM_OK;
+  HIP_TRY(hipMemsetAsync(cnt, 0, (size_t)batch * sizeof(unsigned), (hipStream_t)stream));
+  for (int i = 0; i < ns; ++i) {
+    Stage st[2];
+    step_stages(SOLVER_EULER, num_steps, step_begin, i, st);
+    b.off = mark;
+    FmRun r{h, batch, &b, (hipStream_t)stream, false, nullptr, 1, num_steps, step_begin + st[0].row};
     r.fin_counter = cnt;
-    int rc = r.run(x_inout, nullptr, x_inout, dt);
-    if (rc) return rc;
+    if (int rc = r.run(x_inout, nullptr, x_inout, st[0].dts)) return rc;
   }
   HIP_TRY(hipGetLastError());
   return RGFM_OK;
@@ -332,11 +356,9 @@ extern "C" int rgfm_fmnet_sample_single(rgfm_fmnet* h, float* x_inout, int batch
 extern "C" int rgfm_fmnet_sample_pair_workspace_bytes(const rgfm_fmnet* hx, const rgfm_fmnet* hy, int batch, int n_mc,
                                                       size_t* bytes) {
   if (!hx || !hy || !bytes || batch < 1 || n_mc < 0) return fail(RGFM_EINVAL, "bad argument");
-  const size_t d = (size_t)FM_S * FM_S;
-  size_t total = fm_eval_bytes(const_cast<rgfm_fmnet*>(hx), batch) + fm_eval_bytes(const_cast<rgfm_fmnet*>(hy), batch);
-  total += 2 * ((batch * d * 4 + 255) & ~(size_t)255) + 2 * counter_bytes(batch);
-  total += guid_scratch_bytes(batch, n_mc);
-  *bytes = total;
+  Bump b;
+  fm_carve_pair(b, const_cast<rgfm_fmnet*>(hx), const_cast<rgfm_fmnet*>(hy), batch, n_mc);
+  *bytes = b.off;
   return RGFM_OK;
 }
 
@@ -345,41 +367,28 @@ extern "C" int rgfm_fmnet_sample_pair(rgfm_fmnet* hx, rgfm_fmnet* hy, float* x_i
                                       int batch, int num_steps, double gamma, int step_begin, int step_end, void* ws,
                                       size_t ws_bytes, rgfm_stream_t stream) {
   refresh_modes();
-  if (!hx || !hy || !x_inout || !y_inout || !ws) return fail(RGFM_EINVAL, "null argument");
+  int ns = 0;
+  if (int rc = check_loop(SOLVER_EULER, hx && hy && x_inout && y_inout && ws, batch, num_steps, step_begin, step_end, &ns,
+                          false))
+    return rc;
   if (n_mc < 0 || (n_mc > 0 && (!mc_x1 || !mc_y1 || !mc_ratios))) return fail(RGFM_EINVAL, "MC set missing");
-  if (batch < 1 || num_steps < 1 || step_begin < 0 || step_end > num_steps || step_begin > step_end)
-    return fail(RGFM_EINVAL, "bad step range [%d,%d) of %d", step_begin, step_end, num_steps);
-  size_t need = 0;
-  rgfm_fmnet_sample_pair_workspace_bytes(hx, hy, batch, n_mc, &need);
-  if (need > ws_bytes) return fail(RGFM_ENOMEM, "workspace too small: %zu < %zu", ws_bytes, need);
-  const int ns = step_end - step_begin;
+  Bump b(ws, ws_bytes);
+  FmPairWs w = fm_carve_pair(b, hx, hy, batch, n_mc);
+  if (int rc = check_workspace(b, ws_bytes)) return rc;
   if (ns == 0) return RGFM_OK;
   hipStream_t s = (hipStream_t)stream;
   const int d = FM_S * FM_S;
-  Bump b;
-  b.base = (char*)ws, b.cap = ws_bytes, b.dry = false;
-  float* vx = b.f((size_t)batch * d);
-  float* vy = b.f((size_t)batch * d);
-  float* logp = b.f(guid_scratch_bytes(batch, n_mc) / sizeof(float));
-  unsigned* cnt_x = reinterpret_cast<unsigned*>(b.f(batch));
-  unsigned* cnt_y = reinterpret_cast<unsigned*>(b.f(batch));
-  HIP_TRY(hipMemsetAsync(cnt_x, 0, (size_t)batch * sizeof(unsigned), s));
-  HIP_TRY(hipMemsetAsync(cnt_y, 0, (size_t)batch * sizeof(unsigned), s));
-  const size_t mark_x = b.off;
-  const size_t mark_y = mark_x + fm_eval_bytes(hx, batch);
+  HIP_TRY(hipMemsetAsync(w.cnt_x, 0, (size_t)batch * sizeof(unsigned), s));
+  HIP_TRY(hipMemsetAsync(w.cnt_y, 0, (size_t)batch * sizeof(unsigned), s));
   // (Euler only: the state a stage reads, writes and starts from is the one buffer)
-  auto eval_x = [&](int i, hipStream_t st, const float* in, float* v_out, float* x_state, const float*, float dt, const int*) {
-    b.off = mark_x;
-    FmRun r{hx, batch, &b, st, false, nullptr, 1, num_steps, step_begin + i};
-    r.fin_counter = cnt_x;
-    return r.run(in, v_out, x_state, dt);
+  auto net = [&](rgfm_fmnet* h, unsigned* cnt, size_t mark) {
+    return [=, &b](int i, hipStream_t st, const float* in, float* v_out, float* state, const float*, float dt, const int*) {
+      b.off = mark;
+      FmRun r{h, batch, &b, st, false, nullptr, 1, num_steps, step_begin + i};
+      r.fin_counter = cnt;
+      return r.run(in, v_out, state, dt);
+    };
   };
-  auto eval_y = [&](int i, hipStream_t st, const float* in, float* v_out, float* y_state, const float*, float dt, const int*) {
-    b.off = mark_y;
-    FmRun r{hy, batch, &b, st, false, nullptr, 1, num_steps, step_begin + i};
-    r.fin_counter = cnt_y;
-    return r.run(in, v_out, y_state, dt);
-  };
-  return pair_loop(eval_x, eval_y, x_inout, y_inout, mc_x1, mc_y1, mc_ratios, n_mc, batch, num_steps, gamma, step_begin,
-                   ns, d, d, vx, vy, logp, s);
+  return pair_loop(net(hx, w.cnt_x, w.mark_x), net(hy, w.cnt_y, w.mark_y), x_inout, y_inout, mc_x1, mc_y1, mc_ratios, n_mc,
+                   batch, num_steps, gamma, step_begin, ns, d, d, w.vx, w.vy, w.logp, s);
 }

@@ -1,5 +1,5 @@
 // api_ratio.cpp -- ratio estimators: evaluation, gradient of log r, and the gradient-guided paired sampler (C ABI: include/rgfm.h).
-#include "rgfm_host.h"
+#include "sampler_host.h"
 
 namespace {
 
@@ -414,8 +414,7 @@ extern "C" int rgfm_ratio_eval(rgfm_ratio* h, const float* x, const float* y, fl
   int rc = rgfm_ratio_workspace_bytes(h, n, &need);
   if (rc) return rc;
   if (need > ws_bytes) return fail(RGFM_ENOMEM, "workspace too small: %zu < %zu", ws_bytes, need);
-  Bump b;
-  b.base = (char*)ws, b.cap = ws_bytes, b.dry = false;
+  Bump b(ws, ws_bytes);
   RatioRun r{h, n, &b, (hipStream_t)stream, false};
   r.run(x, y, out, what);
   HIP_TRY(hipGetLastError());
@@ -440,8 +439,7 @@ extern "C" int rgfm_ratio_eval_cross(rgfm_ratio* h, const float* x, int nx, cons
   int rc = rgfm_ratio_cross_workspace_bytes(h, nx, ny, &need);
   if (rc) return rc;
   if (need > ws_bytes) return fail(RGFM_ENOMEM, "workspace too small: %zu < %zu", ws_bytes, need);
-  Bump b;
-  b.base = (char*)ws, b.cap = ws_bytes, b.dry = false;
+  Bump b(ws, ws_bytes);
   RatioCrossRun r{h, nx, ny, &b, (hipStream_t)stream, false, cross_rows()};
   r.run(x, y, out, what);
   HIP_TRY(hipGetLastError());
@@ -642,7 +640,7 @@ struct RatioGradRun {
 
   void begin() {
     ab1 = ws->f((size_t)n * h->max_c * 2);
-    amax = reinterpret_cast<unsigned*>(ws->f(64));
+    amax = ws->u(64);
     amax_used = 0;
     if (!dry) {
       launch_fill_ab_identity(ab1, (size_t)n * h->max_c, s);
@@ -803,8 +801,7 @@ extern "C" int rgfm_ratio_grad_log_ratio(rgfm_ratio* h, const float* x, const fl
   if (rc) return rc;
   if (need > ws_bytes) return fail(RGFM_ENOMEM, "workspace too small: %zu < %zu", ws_bytes, need);
   refresh_modes();
-  Bump b;
-  b.base = (char*)ws, b.cap = ws_bytes, b.dry = false;
+  Bump b(ws, ws_bytes);
   RatioGradRun r{h, n, &b, (hipStream_t)stream, false};
   r.run(x, y, gx, gy, log_ratio_out);
   HIP_TRY(hipGetLastError());
@@ -835,105 +832,87 @@ static int check_grad_pair(const rgfm_unet* hx, const rgfm_unet* hy, const rgfm_
 // (x, y) += dt F(x_mid, y_mid, t1 + dt / 2), the gradient taken at the stage's state.
 namespace {
 
-int solver_id_ok(int solver) {
-  return solver == SOLVER_EULER || solver == SOLVER_MIDPOINT ? RGFM_OK : fail(RGFM_EINVAL, "unknown solver %d (RGFM_SOLVER_EULER, RGFM_SOLVER_MIDPOINT)", solver);
+// the loop's workspace, in order: the two chains, the velocities, the gradients, then one region per concurrent pass
+struct PairGradWs {
+  NetChain cx, cy;
+  float *vx, *vy, *gx, *gy;
+  size_t mark_r;
+};
+void carve_pair_grad(Bump& b, PairGradWs& w, rgfm_ratio* hr) {
+  const int batch = w.cx.batch;
+  w.cx.carve(b), w.cy.carve(b);
+  w.vx = b.f((size_t)batch * w.cx.image_floats());
+  w.vy = b.f((size_t)batch * w.cy.image_floats());
+  w.gx = b.f((size_t)batch * w.cx.image_floats());
+  w.gy = b.f((size_t)batch * w.cy.image_floats());
+  w.cx.carve_eval(), w.cy.carve_eval();
+  w.mark_r = b.off;
+  RatioGradRun r{hr, batch, &b, nullptr, true};
+  r.run(nullptr, nullptr, nullptr, nullptr, nullptr);
 }
 
 int pair_grad_bytes(const rgfm_unet* hx, const rgfm_unet* hy, const rgfm_ratio* hr, int batch, int solver, size_t* bytes) {
+  if (int rc = check_solver_id(solver)) return rc;
   if (!hx || !hy || !hr || !bytes || batch < 1) return fail(RGFM_EINVAL, "bad argument");
-  size_t base = 0, rg = 0;
-  int rc = hr->d.kind == RGFM_RATIO_FLEXIBLE ? check_grad_pair(hx, hy, hr) : RGFM_OK;  // (the fixed kinds: checked by the sampler call)
-  if (rc) return rc;
-  if ((rc = rgfm_sample_pair_workspace_bytes(hx, hy, batch, 0, &base))) return rc;
-  if ((rc = rgfm_ratio_grad_workspace_bytes(hr, batch, &rg))) return rc;
-  const size_t dx = (size_t)hx->d.in_channels * hx->d.img_size * hx->d.img_size;
-  const size_t dy = (size_t)hy->d.in_channels * hy->d.img_size * hy->d.img_size;
-  *bytes = base + rg + ((batch * dx * 4 + 255) & ~(size_t)255) + ((batch * dy * 4 + 255) & ~(size_t)255) +
-           (solver == SOLVER_MIDPOINT ? state_bytes(batch, dx) + state_bytes(batch, dy) : 0);
+  if (hr->d.kind == RGFM_RATIO_FLEXIBLE)  // (the fixed kinds: checked by the sampler call)
+    if (int rc = check_grad_pair(hx, hy, hr)) return rc;
+  Bump b;
+  PairGradWs w{{const_cast<rgfm_unet*>(hx), batch, solver}, {const_cast<rgfm_unet*>(hy), batch, solver}};
+  carve_pair_grad(b, w, const_cast<rgfm_ratio*>(hr));
+  *bytes = b.off;
   return RGFM_OK;
 }
 
 int pair_grad_loop(rgfm_unet* hx, rgfm_unet* hy, rgfm_ratio* hr, float* x_inout, float* y_inout, int batch, int num_steps,
                    double gamma, int step_begin, int step_end, int solver, void* ws, size_t ws_bytes, rgfm_stream_t stream) {
   refresh_modes();
-  if (int rc = solver_id_ok(solver)) return rc;
-  if (!hx || !hy || !hr || !x_inout || !y_inout || !ws) return fail(RGFM_EINVAL, "null argument");
+  int ns = 0;
+  if (int rc = check_loop(solver, hx && hy && hr && x_inout && y_inout && ws, batch, num_steps, step_begin, step_end, &ns))
+    return rc;
   if (int rc = check_grad_pair(hx, hy, hr)) return rc;
-  if (batch < 1 || num_steps < 1 || step_begin < 0 || step_end > num_steps || step_begin > step_end)
-    return fail(RGFM_EINVAL, "bad step range [%d,%d) of %d", step_begin, step_end, num_steps);
-  const int ns = step_end - step_begin;
-  if (int rc = check_solver(solver, ns, num_steps)) return rc;
-  size_t need = 0;
-  int rc = pair_grad_bytes(hx, hy, hr, batch, solver, &need);
-  if (rc) return rc;
-  if (need > ws_bytes) return fail(RGFM_ENOMEM, "workspace too small: %zu < %zu", ws_bytes, need);
+  Bump b(ws, ws_bytes);
+  PairGradWs w{{hx, batch, solver}, {hy, batch, solver}};
+  carve_pair_grad(b, w, hr);
+  if (int rc = check_workspace(b, ws_bytes)) return rc;
   if (ns == 0) return RGFM_OK;
   DevState* ds = cur_dev();
   if (!ds) return fail(RGFM_EINVAL, "no handle has been created on the current device");
   hipStream_t s = (hipStream_t)stream;
-  const int dx = hx->d.in_channels * hx->d.img_size * hx->d.img_size, dy = hy->d.in_channels * hy->d.img_size * hy->d.img_size;
-  Bump b;
-  b.base = (char*)ws, b.cap = ws_bytes, b.dry = false;
-  float* tx = b.f((size_t)4096 * hx->temb_total);
-  float* ty = b.f((size_t)4096 * hy->temb_total);
-  float* vx = b.f((size_t)batch * dx);
-  float* vy = b.f((size_t)batch * dy);
-  float* gx = b.f((size_t)batch * dx);
-  float* gy = b.f((size_t)batch * dy);
-  unsigned* cnt_x = reinterpret_cast<unsigned*>(b.f(batch));
-  unsigned* cnt_y = reinterpret_cast<unsigned*>(b.f(batch));
-  float* x_mid = solver == SOLVER_MIDPOINT ? b.f((size_t)batch * dx) : nullptr;
-  float* y_mid = solver == SOLVER_MIDPOINT ? b.f((size_t)batch * dy) : nullptr;
-  HIP_TRY(hipMemsetAsync(cnt_x, 0, (size_t)batch * sizeof(unsigned), s));
-  HIP_TRY(hipMemsetAsync(cnt_y, 0, (size_t)batch * sizeof(unsigned), s));
-  launch_stage_table(hx, solver, num_steps, step_begin, ns, tx, s);
-  launch_stage_table(hy, solver, num_steps, step_begin, ns, ty, s);
-  const size_t mark_x = b.off;
-  const size_t mark_y = mark_x + unet_eval_bytes(hx, batch);
-  const size_t mark_r = mark_y + unet_eval_bytes(hy, batch);
-  const double dtd = 1.0 / (double)num_steps;
-  const float dt = (float)dtd, dth = (float)(0.5 * dtd), gf = (float)gamma;
+  const size_t dx = w.cx.image_floats(), dy = w.cy.image_floats();
+  if (int rc = w.cx.begin(s, num_steps, step_begin, ns)) return rc;
+  if (int rc = w.cy.begin(s, num_steps, step_begin, ns)) return rc;
+  const float gf = (float)gamma;
   const bool overlap = g_modes.overlap;
   // one stage: (xout, yout) = (xb, yb) + (v(in, row's t) + gamma grad log r(xin, yin)) dts; xb / yb null: in place
-  auto stage = [&](int row, float* xin, float* yin, float* xout, float* yout, const float* xb, const float* yb, float dts) -> int {
+  auto stage = [&](const Stage& g) -> int {
+    float *xin = g.reads_mid ? w.cx.mid : x_inout, *yin = g.reads_mid ? w.cy.mid : y_inout;
+    float *xout = g.writes_mid ? w.cx.mid : x_inout, *yout = g.writes_mid ? w.cy.mid : y_inout;
+    const float *xb = g.writes_mid ? x_inout : nullptr, *yb = g.writes_mid ? y_inout : nullptr;
     hipStream_t sy = overlap ? ds->side : s;
     if (overlap) {
       HIP_TRY(hipEventRecord(ds->fork, s));
       HIP_TRY(hipStreamWaitEvent(ds->side, ds->fork, 0));
     }
-    {
-      b.off = mark_y;
-      UNetRun r{hy, batch, &b, sy, ty + (size_t)row * hy->temb_total, 0, false};
-      r.fin_counter = cnt_y;
-      if (int rc = r.run(yin, vy, nullptr, 0.f)) return rc;
-    }
+    if (int rc = w.cy.eval(g.row, sy, yin, w.vy, nullptr, nullptr, 0.f)) return rc;
     if (overlap) HIP_TRY(hipEventRecord(ds->join, ds->side));
+    if (int rc = w.cx.eval(g.row, s, xin, w.vx, nullptr, nullptr, 0.f)) return rc;
     {
-      b.off = mark_x;
-      UNetRun r{hx, batch, &b, s, tx + (size_t)row * hx->temb_total, 0, false};
-      r.fin_counter = cnt_x;
-      if (int rc = r.run(xin, vx, nullptr, 0.f)) return rc;
-    }
-    {
-      b.off = mark_r;
+      b.off = w.mark_r;
       RatioGradRun r{hr, batch, &b, s, false};
       r.flag = hx->range_flag;
       ModeScope ratio_mode(hx->conv_mode);  // (the estimator's forward convs follow the x net's handle)
-      r.run(xin, yin, gx, gy, nullptr);
+      r.run(xin, yin, w.gx, w.gy, nullptr);
     }
     if (overlap) HIP_TRY(hipStreamWaitEvent(s, ds->join, 0));
-    launch_euler_grad(xout, vx, gx, (size_t)batch * dx, gf, dts, s, xb);
-    launch_euler_grad(yout, vy, gy, (size_t)batch * dy, gf, dts, s, yb);
+    launch_euler_grad(xout, w.vx, w.gx, (size_t)batch * dx, gf, g.dts, s, xb);
+    launch_euler_grad(yout, w.vy, w.gy, (size_t)batch * dy, gf, g.dts, s, yb);
     return RGFM_OK;
   };
   for (int i = 0; i < ns; ++i) {
-    if (solver == SOLVER_MIDPOINT) {
-      if ((rc = stage(2 * i, x_inout, y_inout, x_mid, y_mid, x_inout, y_inout, dth))) return rc;
-      rc = stage(2 * i + 1, x_mid, y_mid, x_inout, y_inout, nullptr, nullptr, dt);
-    } else {
-      rc = stage(i, x_inout, y_inout, x_inout, y_inout, nullptr, nullptr, dt);
-    }
-    if (rc) return rc;
+    Stage st[2];
+    const int n = w.cx.stages(i, st);
+    for (int k = 0; k < n; ++k)
+      if (int rc = stage(st[k])) return rc;
   }
   HIP_TRY(hipGetLastError());
   return RGFM_OK;
@@ -947,7 +926,6 @@ extern "C" int rgfm_sample_pair_grad_workspace_bytes(const rgfm_unet* hx, const 
 }
 extern "C" int rgfm_sample_pair_grad_ode_workspace_bytes(const rgfm_unet* hx, const rgfm_unet* hy, const rgfm_ratio* hr,
                                                          int batch, int solver, size_t* bytes) {
-  if (int rc = solver_id_ok(solver)) return rc;
   return pair_grad_bytes(hx, hy, hr, batch, solver, bytes);
 }
 extern "C" int rgfm_sample_pair_grad(rgfm_unet* hx, rgfm_unet* hy, rgfm_ratio* hr, float* x_inout, float* y_inout, int batch,
@@ -1004,8 +982,7 @@ extern "C" int rgfm_ratio_cond_prepare(rgfm_ratio* h, const float* cond, int giv
   int rc = rgfm_ratio_cond_prepare_workspace_bytes(h, given, n, &need);
   if (rc) return rc;
   if (need > ws_bytes) return fail(RGFM_ENOMEM, "workspace too small: %zu < %zu", ws_bytes, need);
-  Bump b;
-  b.base = (char*)ws, b.cap = ws_bytes, b.dry = false;
+  Bump b(ws, ws_bytes);
   RatioCondPrepare r{h, n, &b, (hipStream_t)stream, false};
   r.run(cond, given, ctx_out);
   HIP_TRY(hipGetLastError());
@@ -1027,8 +1004,7 @@ extern "C" int rgfm_ratio_grad_log_ratio_cond(rgfm_ratio* h, const float* ctx, i
   if (rc) return rc;
   if (need > ws_bytes) return fail(RGFM_ENOMEM, "workspace too small: %zu < %zu", ws_bytes, need);
   refresh_modes();
-  Bump b;
-  b.base = (char*)ws, b.cap = ws_bytes, b.dry = false;
+  Bump b(ws, ws_bytes);
   RatioGradRun r{h, n, &b, (hipStream_t)stream, false};
   r.run_cond(ctx, given, target, g_target, log_ratio_out);
   HIP_TRY(hipGetLastError());
@@ -1040,72 +1016,69 @@ extern "C" int rgfm_ratio_grad_log_ratio_cond(rgfm_ratio* h, const float* ctx, i
 // The velocity net and the estimator's one-sided pass run one after the other on `stream` and share one scratch region.
 namespace {
 
+// the loop's workspace, in order: the chain, the velocity, the gradient, then ONE region for the net and the ratio pass
+struct CondGradWs {
+  NetChain c;
+  float *v, *g;
+};
+CondGradWs carve_cond_grad(Bump& b, rgfm_unet* h, rgfm_ratio* hr, int given, int batch, int solver) {
+  CondGradWs w{{h, batch, solver}, nullptr, nullptr};
+  w.c.carve(b);
+  w.v = b.f((size_t)batch * w.c.image_floats());
+  w.g = b.f((size_t)batch * w.c.image_floats());
+  w.c.carve_eval();
+  const size_t net_end = b.off;
+  b.off = w.c.mark;
+  RatioGradRun r{hr, batch, &b, nullptr, true};
+  r.run_cond(nullptr, given, nullptr, nullptr, nullptr);
+  b.off = std::max(b.off, net_end);
+  return w;
+}
+
 int cond_grad_bytes(const rgfm_unet* h, const rgfm_ratio* hr, int given, int batch, int solver, size_t* bytes) {
+  if (int rc = check_solver_id(solver)) return rc;
   if (!h || !hr || !bytes || batch < 1) return fail(RGFM_EINVAL, "bad argument");
   int rc = check_given(given);
   if (rc || (rc = check_grad_side(h, hr, given))) return rc;
-  const size_t d = (size_t)h->d.in_channels * h->d.img_size * h->d.img_size;
-  *bytes = table_bytes(h, 4096) + counter_bytes(batch) + 2 * ((batch * d * 4 + 255) & ~(size_t)255) +
-           std::max(unet_eval_bytes(const_cast<rgfm_unet*>(h), batch), ratio_cond_grad_bytes(const_cast<rgfm_ratio*>(hr), given, batch)) +
-           (solver == SOLVER_MIDPOINT ? state_bytes(batch, d) : 0);
+  Bump b;
+  carve_cond_grad(b, const_cast<rgfm_unet*>(h), const_cast<rgfm_ratio*>(hr), given, batch, solver);
+  *bytes = b.off;
   return RGFM_OK;
 }
 
 int cond_grad_loop(rgfm_unet* h, rgfm_ratio* hr, float* s_inout, const float* ctx, int given, int batch, int num_steps,
                    double gamma, int step_begin, int step_end, int solver, void* ws, size_t ws_bytes, rgfm_stream_t stream) {
   refresh_modes();
-  if (int rc = solver_id_ok(solver)) return rc;
-  if (!h || !hr || !s_inout || !ctx || !ws) return fail(RGFM_EINVAL, "null argument");
+  int ns = 0;
+  if (int rc = check_loop(solver, h && hr && s_inout && ctx && ws, batch, num_steps, step_begin, step_end, &ns))
+    return rc;
   int rc = check_given(given);
   if (rc || (rc = check_grad_side(h, hr, given))) return rc;
-  if (batch < 1 || num_steps < 1 || step_begin < 0 || step_end > num_steps || step_begin > step_end)
-    return fail(RGFM_EINVAL, "bad step range [%d,%d) of %d", step_begin, step_end, num_steps);
-  const int ns = step_end - step_begin;
-  if ((rc = check_solver(solver, ns, num_steps))) return rc;
-  size_t need = 0;
-  if ((rc = cond_grad_bytes(h, hr, given, batch, solver, &need))) return rc;
-  if (need > ws_bytes) return fail(RGFM_ENOMEM, "workspace too small: %zu < %zu", ws_bytes, need);
+  Bump b(ws, ws_bytes);
+  CondGradWs w = carve_cond_grad(b, h, hr, given, batch, solver);
+  if ((rc = check_workspace(b, ws_bytes))) return rc;
   if (ns == 0) return RGFM_OK;
   hipStream_t s = (hipStream_t)stream;
-  const size_t d = (size_t)h->d.in_channels * h->d.img_size * h->d.img_size;
-  Bump b;
-  b.base = (char*)ws, b.cap = ws_bytes, b.dry = false;
-  float* table = b.f((size_t)4096 * h->temb_total);
-  unsigned* cnt = reinterpret_cast<unsigned*>(b.f(batch));
-  float* v = b.f((size_t)batch * d);
-  float* g = b.f((size_t)batch * d);
-  float* mid = solver == SOLVER_MIDPOINT ? b.f((size_t)batch * d) : nullptr;
-  HIP_TRY(hipMemsetAsync(cnt, 0, (size_t)batch * sizeof(unsigned), s));
-  launch_stage_table(h, solver, num_steps, step_begin, ns, table, s);
-  const size_t mark = b.off;
-  const double dtd = 1.0 / (double)num_steps;
-  const float dt = (float)dtd, dth = (float)(0.5 * dtd), gf = (float)gamma;
-  // one stage: out = base + (v(in, row's t) + gamma grad log r(in)) dts; base null: in place on out
-  auto stage = [&](int row, float* in, float* out, const float* base, float dts) -> int {
-    {
-      b.off = mark;
-      UNetRun r{h, batch, &b, s, table + (size_t)row * h->temb_total, 0, false};
-      r.fin_counter = cnt;
-      if (int rc = r.run(in, v, nullptr, 0.f)) return rc;
-    }
-    {
-      b.off = mark;
-      RatioGradRun r{hr, batch, &b, s, false};
-      r.flag = h->range_flag;
-      ModeScope ratio_mode(h->conv_mode);  // (the estimator's convs follow the target net's handle)
-      r.run_cond(ctx, given, in, g, nullptr);
-    }
-    launch_euler_grad(out, v, g, (size_t)batch * d, gf, dts, s, base);
-    return RGFM_OK;
-  };
+  const size_t d = w.c.image_floats();
+  if ((rc = w.c.begin(s, num_steps, step_begin, ns))) return rc;
+  const float gf = (float)gamma;
   for (int i = 0; i < ns; ++i) {
-    if (solver == SOLVER_MIDPOINT) {
-      if ((rc = stage(2 * i, s_inout, mid, s_inout, dth))) return rc;
-      rc = stage(2 * i + 1, mid, s_inout, nullptr, dt);
-    } else {
-      rc = stage(i, s_inout, s_inout, nullptr, dt);
+    Stage st[2];
+    const int n = w.c.stages(i, st);
+    for (int k = 0; k < n; ++k) {
+      // one stage: out = base + (v(in, row's t) + gamma grad log r(in)) dts; base null: in place on out
+      const Stage& g = st[k];
+      float *in = g.reads_mid ? w.c.mid : s_inout, *out = g.writes_mid ? w.c.mid : s_inout;
+      if ((rc = w.c.eval(g.row, s, in, w.v, nullptr, nullptr, 0.f))) return rc;
+      {
+        b.off = w.c.mark;
+        RatioGradRun r{hr, batch, &b, s, false};
+        r.flag = h->range_flag;
+        ModeScope ratio_mode(h->conv_mode);  // (the estimator's convs follow the target net's handle)
+        r.run_cond(ctx, given, in, w.g, nullptr);
+      }
+      launch_euler_grad(out, w.v, w.g, (size_t)batch * d, gf, g.dts, s, g.writes_mid ? s_inout : nullptr);
     }
-    if (rc) return rc;
   }
   HIP_TRY(hipGetLastError());
   return RGFM_OK;
@@ -1118,7 +1091,6 @@ extern "C" int rgfm_sample_cond_grad_workspace_bytes(const rgfm_unet* h, const r
 }
 extern "C" int rgfm_sample_cond_grad_ode_workspace_bytes(const rgfm_unet* h, const rgfm_ratio* hr, int given, int batch, int solver,
                                                          size_t* bytes) {
-  if (int rc = solver_id_ok(solver)) return rc;
   return cond_grad_bytes(h, hr, given, batch, solver, bytes);
 }
 extern "C" int rgfm_sample_cond_grad(rgfm_unet* h, rgfm_ratio* hr, float* s_inout, const float* ctx, int given, int batch,

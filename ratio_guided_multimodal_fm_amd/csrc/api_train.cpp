@@ -7,6 +7,7 @@
 // caller's workspace, laid out by plan_train: first the SAVED state (dropout header, x, the time path, every tensor
 // the walk produces, and per ResBlock the group statistics of both norms, the time projection and conv1's output),
 // then the backward's SCRATCH (one gradient buffer per produced tensor and a few transient maps).
+#include "sampler_host.h"
 #include "train_host.h"
 
 namespace {

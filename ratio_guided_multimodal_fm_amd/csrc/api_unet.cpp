@@ -141,13 +141,12 @@ extern "C" int rgfm_unet_forward(rgfm_unet* h, const float* x, const float* t_de
   if (!h || !x || !t_dev || !v_out || !ws) return fail(RGFM_EINVAL, "null argument");
   if (batch < 1 || (t_count != 1 && t_count != batch)) return fail(RGFM_EINVAL, "t_count must be 1 or batch");
   hipStream_t s = (hipStream_t)stream;
-  Bump b;
-  b.base = (char*)ws, b.cap = ws_bytes, b.dry = false;
+  Bump b(ws, ws_bytes);
   size_t need = 0;
   rgfm_unet_workspace_bytes(h, batch, &need);
   if (need > ws_bytes) return fail(RGFM_ENOMEM, "workspace too small: %zu < %zu", ws_bytes, need);
   float* table = b.f((size_t)t_count * h->temb_total);
-  unsigned* cnt = reinterpret_cast<unsigned*>(b.f(batch));
+  unsigned* cnt = b.u(batch);
   HIP_TRY(hipMemsetAsync(cnt, 0, (size_t)batch * sizeof(unsigned), s));
   launch_time_table(h, t_dev, 1, 0, t_count, table, s);
   UNetRun r{h, batch, &b, s, table, t_count == batch ? 1 : 0, false};

@@ -1,9 +1,9 @@
 // rgfm_host.h -- host-side internals shared by the translation units of the C ABI (api_*.cpp): error text, the
 // hipEvent kernel-class timers, workspace carving, the per-thread run-time switches (Modes; with the process-wide
 // ConvTuning of rgfm_kernels.h the only two places that can change conv routing), per-device state, conv dispatch,
-// the U-Net handle and its network walk (used by the samplers and the gradient-guided loop too), the guidance launch and
-// the shared paired Euler loop.  Not part of the public ABI (that is include/rgfm.h); everything here is `inline` /
-// C++17 inline variables, so every unit sees ONE definition.
+// the U-Net handle and its network walk (used by the samplers and the gradient-guided loop too) and the guidance launch.
+// (What only the sampler loops share is in sampler_host.h.)  Not part of the public ABI (that is include/rgfm.h);
+// everything here is `inline` / C++17 inline variables, so every unit sees ONE definition.
 //
 //   api_core.cpp     rgfm_last_error, rgfm_abi_version, rgfm_profile_*
 //   api_unet.cpp     rgfm_unet_*            (create / forward / trace hooks)
@@ -141,6 +141,9 @@ struct Bump {  // workspace carving; dry = size-only pass
   size_t cap = 0;
   bool dry = true;
   bool overflow = false;
+  Bump() = default;
+  Bump(void* ws, size_t ws_bytes) : base((char*)ws), cap(ws_bytes), dry(false) {}  // the live pass over a caller's workspace
+  unsigned* u(size_t n) { return reinterpret_cast<unsigned*>(f(n)); }  // n 32-bit words (arrival counters)
   float* f(size_t nfloats) {
     const size_t bytes = (nfloats * sizeof(float) + 255) & ~(size_t)255;
     const size_t o = off;
@@ -1032,176 +1035,6 @@ inline int guidance_launch(const float* x, const float* y, float* vx, float* vy,
     ProfScope p(RGFM_KCLASS_GUID_APPLY, 4.0 * B * N + 4.0 * N * D + 4.0 * B * D * 3.0, s);
     launch_guid_apply(a, s);
   }
-  return RGFM_OK;
-}
-
-
-// solvers of the sampler loops (include/rgfm.h: RGFM_SOLVER_*)
-constexpr int SOLVER_EULER = 0, SOLVER_MIDPOINT = 1;
-constexpr int MAX_STEPS_EULER = 4096, MAX_STEPS_MIDPOINT = 2048;  // the time tables hold 4096 rows: one / two per step
-inline int check_solver(int solver, int ns, int num_steps) {
-  if (solver != SOLVER_EULER && solver != SOLVER_MIDPOINT) return fail(RGFM_EINVAL, "unknown solver %d (RGFM_SOLVER_EULER, RGFM_SOLVER_MIDPOINT)", solver);
-  if (solver == SOLVER_EULER && ns > MAX_STEPS_EULER) return fail(RGFM_EINVAL, "at most 4096 steps per call");
-  if (solver == SOLVER_MIDPOINT && ns > MAX_STEPS_MIDPOINT) return fail(RGFM_EINVAL, "midpoint: at most 2048 steps per call (two time-table rows per step)");
-  if (solver == SOLVER_MIDPOINT && num_steps > (1 << 30)) return fail(RGFM_EINVAL, "midpoint: num_steps too large");
-  return RGFM_OK;
-}
-inline size_t state_bytes(int batch, size_t d) { return ((size_t)batch * d * 4 + 255) & ~(size_t)255; }
-// Time-table rows of a loop's stages.  Euler: row i is t = (step_begin + i) / num_steps.  Midpoint: row 2i is the step's
-// t1 = (step_begin + i) dt and row 2i + 1 its t2 = (step_begin + i + 0.5) dt -- the table of the 2 num_steps half-steps:
-// (2k + j) * (1.0 / (2 N)) and (k + j / 2) * (1.0 / N) are the same double (a factor two moves no rounding).
-inline int launch_stage_table(rgfm_unet* h, int solver, int num_steps, int step_begin, int ns, float* table, hipStream_t s) {
-  if (solver == SOLVER_MIDPOINT) return launch_time_table(h, nullptr, 2 * num_steps, 2 * step_begin, 2 * ns, table, s);
-  return launch_time_table(h, nullptr, num_steps, step_begin, ns, table, s);
-}
-
-// Shared loop of paired_sampler (src/utils/flow_utils.py:186-278 with the guidance of
-// src/sample_mnist_svhn.py:117-175): eval_x / eval_y enqueue one velocity-net evaluation of step i
-// on the given stream, writing the raw velocity (guided steps) or the fused Euler update.
-// eval(row, stream, in, v_out, state_out, base, dt, step): the net at `in` with time-table row `row`; state_out = base + v dt.
-// solver SOLVER_MIDPOINT (x_mid / y_mid: one mid-state buffer per modality): every step is two such stages,
-//   (x_mid, y_mid) = (x, y) + (dt / 2) F(x, y, t1),   (x, y) = (x, y) + dt F(x_mid, y_mid, t2),   t2 = t1 + dt / 2,
-// F the whole guided velocity at the stage's own state and time; a stage is guided iff its own t > 1e-3.  Each stage
-// forks and joins the side stream as an Euler step does.
-// Graph replay (U-Net pairs, RGFM_GRAPH=1; never with active kernel timers): every guided step enqueues the
-// same ~135 launches with the same arguments except the time-table row and three guidance scalars.  Euler only: a midpoint
-// call runs kernel by kernel.  Those are read
-// on the device through a step counter (`gstate`: [0] the counter, [64..] the per-step scalars), so the first guided
-// step is captured once -- both streams, fork and join included -- into a hipGraph and every guided step is one
-// hipGraphLaunch.  Results are bit-identical to the kernel-by-kernel path (same kernels, same arguments).
-template <class EvalX, class EvalY>
-int pair_loop(EvalX&& eval_x, EvalY&& eval_y, float* x_inout, float* y_inout, const float* mc_x1,
-              const float* mc_y1, const float* mc_ratios, int n_mc, int batch, int num_steps, double gamma,
-              int step_begin, int ns, int dx, int dy, float* vx, float* vy, float* logp, hipStream_t caller,
-              float* gstate = nullptr, int solver = SOLVER_EULER, float* x_mid = nullptr, float* y_mid = nullptr) {
-  const double dtd = 1.0 / (double)num_steps;
-  const float dt = (float)dtd;
-  // The two velocity nets of a step are independent (reference :119-121): the second one runs on a
-  // side stream forked from / joined back into the caller's stream every step, which fills the CUs
-  // that one net's small-grid launches (8x8 level, kernel tails) leave idle.
-  // (the stream and its fork/join events belong to the device's DevState, created with the first handle)
-  DevState* ds = cur_dev();
-  if (!ds) return fail(RGFM_EINVAL, "no handle has been created on the current device");
-  const bool overlap = g_modes.overlap;
-  hipStream_t side = ds->side;
-  hipEvent_t ev_fork = ds->fork, ev_join = ds->join;
-  const bool use_graph = gstate && g_modes.graph && !g_prof.on && n_mc > 0 && ns >= 4 && solver == SOLVER_EULER;
-  hipStream_t s = caller;
-  if (use_graph && caller == nullptr) {  // (see DevState::main)
-    s = ds->main;
-    HIP_TRY(hipEventRecord(ds->main_fork, caller));
-    HIP_TRY(hipStreamWaitEvent(s, ds->main_fork, 0));
-  }
-  int* step_dev = nullptr;
-  float* sched_dev = nullptr;
-  if (use_graph) {
-    // graphs of earlier calls: release them once the device is past their last replay
-    if (!ds->graphs.empty() && hipEventQuery(ds->graph_done) == hipSuccess) {
-      for (auto& g : ds->graphs) (void)hipGraphExecDestroy(g.first), (void)hipGraphDestroy(g.second);
-      ds->graphs.clear();
-    }
-    step_dev = reinterpret_cast<int*>(gstate);
-    sched_dev = gstate + 64;
-    HIP_TRY(hipMemsetAsync(step_dev, 0, 256, s));
-    launch_guid_schedule(sched_dev, step_begin, ns, num_steps, s);
-  }
-  // one stage: (xout, yout) = (xb, yb) + dts * F(xin, yin, t), the nets reading time-table row `row`
-  auto one_stage = [&](int row, double t, bool guided, float* xin, float* yin, float* xout, float* yout, const float* xb,
-                       const float* yb, float dts) -> int {
-    hipStream_t sy = overlap ? side : s;
-    if (overlap) {
-      HIP_TRY(hipEventRecord(ev_fork, s));
-      HIP_TRY(hipStreamWaitEvent(side, ev_fork, 0));
-    }
-    int rc = eval_y(row, sy, yin, guided ? vy : nullptr, guided ? nullptr : yout, yb, dts, step_dev);
-    if (rc) return rc;
-    if (overlap) HIP_TRY(hipEventRecord(ev_join, side));
-    rc = eval_x(row, s, xin, guided ? vx : nullptr, guided ? nullptr : xout, xb, dts, step_dev);
-    if (rc) return rc;
-    // The distances to the MC set and the importance weights depend on (x_t, y_t) only (sample_mnist_svhn.py:130-156; a
-    // guided step's nets write velocities, the state moves in guid_apply): they go on this stream BEFORE it waits for the
-    // other net -- the x net of a pair is the quicker one, so they run in its shadow instead of on the step's critical path
-    if (guided && overlap) {
-      rc = guidance_launch(xin, yin, vx, vy, mc_x1, mc_y1, mc_ratios, batch, n_mc, dx, dy, t, gamma, logp,
-                           nullptr, xout, yout, dts, s, sched_dev, step_dev, 1, 0, xb, yb);
-      if (rc) return rc;
-    }
-    if (overlap) HIP_TRY(hipStreamWaitEvent(s, ev_join, 0));
-    if (guided) {
-      rc = guidance_launch(xin, yin, vx, vy, mc_x1, mc_y1, mc_ratios, batch, n_mc, dx, dy, t, gamma, logp,
-                           nullptr, xout, yout, dts, s, sched_dev, step_dev, overlap ? 2 : 0, 0, xb, yb);
-      if (rc) return rc;
-    }
-    if (step_dev) launch_step_inc(step_dev, s);
-    return RGFM_OK;
-  };
-  auto one_step = [&](int i, bool guided) -> int {  // an Euler step: one stage, in place
-    return one_stage(i, (double)(step_begin + i) * dtd, guided, x_inout, y_inout, x_inout, y_inout, x_inout, y_inout, dt);
-  };
-  hipGraphExec_t exec = nullptr;
-  // On EVERY exit path -- also the error returns inside the loop -- the work already enqueued must stay ordered: the
-  // event that guards the destruction of this call's graph is recorded behind its last launch, and the caller's
-  // stream is joined behind whatever ran on the device's `main` stream (a stale graph_done could let the
-  // next call destroy a graph that is still executing).
-  struct ExitGuard {
-    DevState* ds;
-    hipStream_t s, caller;
-    hipGraphExec_t* exec;
-    ~ExitGuard() {
-      if (*exec) (void)hipEventRecord(ds->graph_done, s);
-      if (s != caller) {
-        (void)hipEventRecord(ds->main_join, s);
-        (void)hipStreamWaitEvent(caller, ds->main_join, 0);
-      }
-    }
-  } exit_guard{ds, s, caller, &exec};
-  // (Measured and rejected in round 4, profiles/r04_ab_decoupled_loop.txt: the loop WITHOUT the per-step join -- each
-  // modality a chain net -> its half of the guided update on its own stream, coupled only through two events per step
-  // around the importance weights, the x net up to one evaluation ahead -- is bit-identical and 0.5 - 0.9 % SLOWER
-  // (469 - 471 vs 473 paired images/s, same box, alternating): the join costs nothing the chains could use.)
-  for (int i = 0; i < ns; ++i) {
-    const double t = (double)(step_begin + i) * dtd;
-    const bool guided = n_mc > 0 && t > 1e-3;  // `t > eps` test of the reference (:124)
-    if (solver == SOLVER_MIDPOINT) {
-      const double t2 = ((double)(step_begin + i) + 0.5) * dtd;
-      const float dth = (float)(0.5 * dtd);
-      int rc = one_stage(2 * i, t, guided, x_inout, y_inout, x_mid, y_mid, x_inout, y_inout, dth);
-      if (rc) return rc;
-      rc = one_stage(2 * i + 1, t2, n_mc > 0 && t2 > 1e-3, x_mid, y_mid, x_inout, y_inout, x_inout, y_inout, dt);
-      if (rc) return rc;
-      continue;
-    }
-    if (use_graph && guided) {
-      if (!exec) {
-        hipGraph_t graph = nullptr;
-        HIP_TRY(hipStreamBeginCapture(s, hipStreamCaptureModeRelaxed));
-        const int rc = one_step(i, true);
-        const hipError_t ce = hipStreamEndCapture(s, &graph);
-        if (rc) {  // (a captured graph that will never run: nothing refers to it)
-          if (graph) (void)hipGraphDestroy(graph);
-          return rc;
-        }
-        if (ce != hipSuccess || !graph) {
-          if (graph) (void)hipGraphDestroy(graph);
-          return fail(RGFM_EHIP, "hipStreamEndCapture: %s", hipGetErrorString(ce));
-        }
-        const hipError_t ie = hipGraphInstantiate(&exec, graph, nullptr, nullptr, 0);
-        if (ie != hipSuccess) {
-          exec = nullptr;
-          (void)hipGraphDestroy(graph);
-          return fail(RGFM_EHIP, "hipGraphInstantiate: %s", hipGetErrorString(ie));
-        }
-        ds->graphs.push_back({exec, graph});
-      }
-      HIP_TRY(hipGraphLaunch(exec, s));
-      continue;
-    }
-    const int rc = one_step(i, guided);
-    if (rc) return rc;
-  }
-  // (the guard's destructor records graph_done and joins `main` into the caller's stream -- on this path too, so that a
-  // failing record cannot skip the join)
-  HIP_TRY(hipGetLastError());
   return RGFM_OK;
 }
 

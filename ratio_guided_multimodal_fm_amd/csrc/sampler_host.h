@@ -1,0 +1,234 @@
+// sampler_host.h -- what the sampler loops share (api_sampler.cpp, api_ratio.cpp, api_fmnet.cpp; api_train.cpp for the
+// solver checks): the argument prelude, the stage list (sampler_stages.h), one U-Net's integration state (NetChain) and
+// the paired guided loop.  A loop's workspace is described once, by a carve over a Bump: the *_workspace_bytes query is
+// that carve's end offset, the call checks the same figure against ws_bytes before it launches anything.
+#pragma once
+#include "rgfm_host.h"
+#include "sampler_stages.h"
+
+constexpr int TABLE_ROWS = 4096;  // rows of a call's time table: one per Euler step, two per midpoint step
+constexpr int MAX_STEPS_EULER = TABLE_ROWS, MAX_STEPS_MIDPOINT = TABLE_ROWS / 2;
+inline int check_solver(int solver, int ns, int num_steps) {
+  if (solver != SOLVER_EULER && solver != SOLVER_MIDPOINT) return fail(RGFM_EINVAL, "unknown solver %d (RGFM_SOLVER_EULER, RGFM_SOLVER_MIDPOINT)", solver);
+  if (solver == SOLVER_EULER && ns > MAX_STEPS_EULER) return fail(RGFM_EINVAL, "at most 4096 steps per call");
+  if (solver == SOLVER_MIDPOINT && ns > MAX_STEPS_MIDPOINT) return fail(RGFM_EINVAL, "midpoint: at most 2048 steps per call (two time-table rows per step)");
+  if (solver == SOLVER_MIDPOINT && num_steps > (1 << 30)) return fail(RGFM_EINVAL, "midpoint: num_steps too large");
+  return RGFM_OK;
+}
+inline int check_solver_id(int solver) { return check_solver(solver, 0, 0); }  // (what a *_workspace_bytes query can check)
+
+// The prelude of every loop, in this order: solver id, null arguments (`have_args`: the loop's own pointers), step range,
+// step caps.  `time_table` = false (the FlowMatchingModel loops embed t per evaluation): no cap on the steps of a call.
+inline int check_loop(int solver, bool have_args, int batch, int num_steps, int step_begin, int step_end, int* ns,
+                      bool time_table = true) {
+  if (int rc = check_solver_id(solver)) return rc;
+  if (!have_args) return fail(RGFM_EINVAL, "null argument");
+  if (batch < 1 || num_steps < 1 || step_begin < 0 || step_end > num_steps || step_begin > step_end)
+    return fail(RGFM_EINVAL, "bad step range [%d,%d) of %d", step_begin, step_end, num_steps);
+  *ns = step_end - step_begin;
+  return time_table ? check_solver(solver, *ns, num_steps) : RGFM_OK;
+}
+// ... and its last line: the carve's end against what the caller brought
+inline int check_workspace(const Bump& carved, size_t ws_bytes) {
+  return carved.off > ws_bytes ? fail(RGFM_ENOMEM, "workspace too small: %zu < %zu", ws_bytes, carved.off) : RGFM_OK;
+}
+
+// Time-table rows of a loop's stages.  Euler: row i is t = (step_begin + i) / num_steps.  Midpoint: row 2i is the step's
+// t1 = (step_begin + i) dt and row 2i + 1 its t2 = (step_begin + i + 0.5) dt -- the table of the 2 num_steps half-steps:
+// (2k + j) * (1.0 / (2 N)) and (k + j / 2) * (1.0 / N) are the same double (a factor two moves no rounding).
+inline int launch_stage_table(rgfm_unet* h, int solver, int num_steps, int step_begin, int ns, float* table, hipStream_t s) {
+  if (solver == SOLVER_MIDPOINT) return launch_time_table(h, nullptr, 2 * num_steps, 2 * step_begin, 2 * ns, table, s);
+  return launch_time_table(h, nullptr, num_steps, step_begin, ns, table, s);
+}
+
+// One U-Net's integration state inside a loop's workspace: the time table, the [batch] arrival counters of the
+// producer-side GroupNorm finalize, the mid state of the midpoint solver and the region its evaluations carve their
+// activations from.  The Bump is the loop's: nets that run concurrently carve disjoint regions of it (carve_eval one
+// after the other), a pass that runs after the net on the same stream may reuse the region from `mark`.
+struct NetChain {
+  rgfm_unet* h = nullptr;
+  int batch = 0, solver = SOLVER_EULER;
+  float* x = nullptr;  // the state `step` advances (the unguided loops; the guided loops pass their own pointers to eval)
+  hipStream_t s = nullptr;  // ... and its stream, from begin
+  Bump* b = nullptr;
+  float *table = nullptr, *mid = nullptr;
+  unsigned* cnt = nullptr;
+  size_t mark = 0;
+  int num_steps = 1, step_begin = 0;
+
+  size_t image_floats() const { return (size_t)h->d.in_channels * h->d.img_size * h->d.img_size; }
+  void carve(Bump& bump) {
+    b = &bump;
+    table = bump.f((size_t)TABLE_ROWS * h->temb_total);
+    cnt = bump.u(batch);
+    mid = solver == SOLVER_MIDPOINT ? bump.f((size_t)batch * image_floats()) : nullptr;
+  }
+  void carve_eval() {  // one evaluation's activations, from the Bump's current offset (the walk of UNetRun, run dry)
+    mark = b->off;
+    UNetRun r{h, batch, b, nullptr, nullptr, 0, true};
+    r.run(nullptr, nullptr, nullptr, 0.f);
+  }
+  int begin(hipStream_t stream, int num_steps_, int step_begin_, int ns) {
+    s = stream, num_steps = num_steps_, step_begin = step_begin_;
+    HIP_TRY(hipMemsetAsync(cnt, 0, (size_t)batch * sizeof(unsigned), s));
+    return launch_stage_table(h, solver, num_steps, step_begin, ns, table, s);
+  }
+  int stages(int i, Stage st[2]) const { return step_stages(solver, num_steps, step_begin, i, st); }
+  // The net at `in` with time-table row `row` on `s`: v_out receives the raw velocity, state_out = base + v dts (the fused
+  // epilogue of the out-conv).  step_ptr: the device-side step counter of the graph-replay path, which picks the row.
+  int eval(int row, hipStream_t s, const float* in, float* v_out, float* state_out, const float* base, float dts,
+           const int* step_ptr = nullptr) {
+    b->off = mark;
+    UNetRun r{h, batch, b, s, step_ptr ? table : table + (size_t)row * h->temb_total, 0, false};
+    r.fin_counter = cnt, r.step_ptr = step_ptr;
+    return r.run(in, v_out, state_out, dts, base);
+  }
+  // one unguided step of `x` on `s`: every stage's update fused into the out-conv
+  int step(int i) {
+    Stage st[2];
+    const int n = stages(i, st);
+    for (int k = 0; k < n; ++k)
+      if (int rc = eval(st[k].row, s, st[k].reads_mid ? mid : x, nullptr, st[k].writes_mid ? mid : x, x, st[k].dts)) return rc;
+    return RGFM_OK;
+  }
+};
+
+// Shared loop of paired_sampler (src/utils/flow_utils.py:186-278 with the guidance of
+// src/sample_mnist_svhn.py:117-175): eval_x / eval_y enqueue one velocity-net evaluation of a stage
+// on the given stream, writing the raw velocity (guided stages) or the fused Euler update.
+// eval(row, stream, in, v_out, state_out, base, dt, step): the net at `in` with time-table row `row`; state_out = base + v dt.
+// The stages of a step come from step_stages.  Midpoint (x_mid / y_mid: one mid-state buffer per modality):
+//   (x_mid, y_mid) = (x, y) + (dt / 2) F(x, y, t1),   (x, y) = (x, y) + dt F(x_mid, y_mid, t2),   t2 = t1 + dt / 2,
+// F the whole guided velocity at the stage's own state and time; a stage is guided iff its own t > 1e-3.  Each stage
+// forks and joins the side stream as an Euler step does.
+// Graph replay (U-Net pairs, RGFM_GRAPH=1; never with active kernel timers): every guided step enqueues the
+// same ~135 launches with the same arguments except the time-table row and three guidance scalars.  Euler only: a midpoint
+// call runs kernel by kernel.  Those are read
+// on the device through a step counter (`gstate`: [0] the counter, [64..] the per-step scalars), so the first guided
+// step is captured once -- both streams, fork and join included -- into a hipGraph and every guided step is one
+// hipGraphLaunch.  Results are bit-identical to the kernel-by-kernel path (same kernels, same arguments).
+template <class EvalX, class EvalY>
+int pair_loop(EvalX&& eval_x, EvalY&& eval_y, float* x_inout, float* y_inout, const float* mc_x1,
+              const float* mc_y1, const float* mc_ratios, int n_mc, int batch, int num_steps, double gamma,
+              int step_begin, int ns, int dx, int dy, float* vx, float* vy, float* logp, hipStream_t caller,
+              float* gstate = nullptr, int solver = SOLVER_EULER, float* x_mid = nullptr, float* y_mid = nullptr) {
+  // The two velocity nets of a step are independent (reference :119-121): the second one runs on a
+  // side stream forked from / joined back into the caller's stream every step, which fills the CUs
+  // that one net's small-grid launches (8x8 level, kernel tails) leave idle.
+  // (the stream and its fork/join events belong to the device's DevState, created with the first handle)
+  DevState* ds = cur_dev();
+  if (!ds) return fail(RGFM_EINVAL, "no handle has been created on the current device");
+  const bool overlap = g_modes.overlap;
+  hipStream_t side = ds->side;
+  hipEvent_t ev_fork = ds->fork, ev_join = ds->join;
+  const bool use_graph = gstate && g_modes.graph && !g_prof.on && n_mc > 0 && ns >= 4 && solver == SOLVER_EULER;
+  hipStream_t s = caller;
+  if (use_graph && caller == nullptr) {  // (see DevState::main)
+    s = ds->main;
+    HIP_TRY(hipEventRecord(ds->main_fork, caller));
+    HIP_TRY(hipStreamWaitEvent(s, ds->main_fork, 0));
+  }
+  int* step_dev = nullptr;
+  float* sched_dev = nullptr;
+  if (use_graph) {
+    // graphs of earlier calls: release them once the device is past their last replay
+    if (!ds->graphs.empty() && hipEventQuery(ds->graph_done) == hipSuccess) {
+      for (auto& g : ds->graphs) (void)hipGraphExecDestroy(g.first), (void)hipGraphDestroy(g.second);
+      ds->graphs.clear();
+    }
+    step_dev = reinterpret_cast<int*>(gstate);
+    sched_dev = gstate + 64;
+    HIP_TRY(hipMemsetAsync(step_dev, 0, 256, s));
+    launch_guid_schedule(sched_dev, step_begin, ns, num_steps, s);
+  }
+  // one stage: (xout, yout) = (x, y) + dts * F(xin, yin, t), the nets reading time-table row `row`
+  auto one_stage = [&](const Stage& g, bool guided) -> int {
+    float *xin = g.reads_mid ? x_mid : x_inout, *yin = g.reads_mid ? y_mid : y_inout;
+    float *xout = g.writes_mid ? x_mid : x_inout, *yout = g.writes_mid ? y_mid : y_inout;
+    const float *xb = x_inout, *yb = y_inout;
+    hipStream_t sy = overlap ? side : s;
+    if (overlap) {
+      HIP_TRY(hipEventRecord(ev_fork, s));
+      HIP_TRY(hipStreamWaitEvent(side, ev_fork, 0));
+    }
+    int rc = eval_y(g.row, sy, yin, guided ? vy : nullptr, guided ? nullptr : yout, yb, g.dts, step_dev);
+    if (rc) return rc;
+    if (overlap) HIP_TRY(hipEventRecord(ev_join, side));
+    rc = eval_x(g.row, s, xin, guided ? vx : nullptr, guided ? nullptr : xout, xb, g.dts, step_dev);
+    if (rc) return rc;
+    // The distances to the MC set and the importance weights depend on (x_t, y_t) only (sample_mnist_svhn.py:130-156; a
+    // guided step's nets write velocities, the state moves in guid_apply): they go on this stream BEFORE it waits for the
+    // other net -- the x net of a pair is the quicker one, so they run in its shadow instead of on the step's critical path
+    if (guided && overlap) {
+      rc = guidance_launch(xin, yin, vx, vy, mc_x1, mc_y1, mc_ratios, batch, n_mc, dx, dy, g.t, gamma, logp,
+                           nullptr, xout, yout, g.dts, s, sched_dev, step_dev, 1, 0, xb, yb);
+      if (rc) return rc;
+    }
+    if (overlap) HIP_TRY(hipStreamWaitEvent(s, ev_join, 0));
+    if (guided) {
+      rc = guidance_launch(xin, yin, vx, vy, mc_x1, mc_y1, mc_ratios, batch, n_mc, dx, dy, g.t, gamma, logp,
+                           nullptr, xout, yout, g.dts, s, sched_dev, step_dev, overlap ? 2 : 0, 0, xb, yb);
+      if (rc) return rc;
+    }
+    if (step_dev) launch_step_inc(step_dev, s);
+    return RGFM_OK;
+  };
+  hipGraphExec_t exec = nullptr;
+  // On EVERY exit path -- also the error returns inside the loop -- the work already enqueued must stay ordered: the
+  // event that guards the destruction of this call's graph is recorded behind its last launch, and the caller's
+  // stream is joined behind whatever ran on the device's `main` stream (a stale graph_done could let the
+  // next call destroy a graph that is still executing).
+  struct ExitGuard {
+    DevState* ds;
+    hipStream_t s, caller;
+    hipGraphExec_t* exec;
+    ~ExitGuard() {
+      if (*exec) (void)hipEventRecord(ds->graph_done, s);
+      if (s != caller) {
+        (void)hipEventRecord(ds->main_join, s);
+        (void)hipStreamWaitEvent(caller, ds->main_join, 0);
+      }
+    }
+  } exit_guard{ds, s, caller, &exec};
+  // (Measured and rejected in round 4, profiles/r04_ab_decoupled_loop.txt: the loop WITHOUT the per-step join -- each
+  // modality a chain net -> its half of the guided update on its own stream, coupled only through two events per step
+  // around the importance weights, the x net up to one evaluation ahead -- is bit-identical and 0.5 - 0.9 % SLOWER
+  // (469 - 471 vs 473 paired images/s, same box, alternating): the join costs nothing the chains could use.)
+  for (int i = 0; i < ns; ++i) {
+    Stage st[2];
+    const int n = step_stages(solver, num_steps, step_begin, i, st);
+    for (int k = 0; k < n; ++k) {
+      const bool guided = n_mc > 0 && st[k].t > 1e-3;  // `t > eps` test of the reference (:124)
+      if (use_graph && guided) {  // (Euler: the step's one stage)
+        if (!exec) {
+          hipGraph_t graph = nullptr;
+          HIP_TRY(hipStreamBeginCapture(s, hipStreamCaptureModeRelaxed));
+          const int rc = one_stage(st[k], true);
+          const hipError_t ce = hipStreamEndCapture(s, &graph);
+          if (rc) {  // (a captured graph that will never run: nothing refers to it)
+            if (graph) (void)hipGraphDestroy(graph);
+            return rc;
+          }
+          if (ce != hipSuccess || !graph) {
+            if (graph) (void)hipGraphDestroy(graph);
+            return fail(RGFM_EHIP, "hipStreamEndCapture: %s", hipGetErrorString(ce));
+          }
+          const hipError_t ie = hipGraphInstantiate(&exec, graph, nullptr, nullptr, 0);
+          if (ie != hipSuccess) {
+            exec = nullptr;
+            (void)hipGraphDestroy(graph);
+            return fail(RGFM_EHIP, "hipGraphInstantiate: %s", hipGetErrorString(ie));
+          }
+          ds->graphs.push_back({exec, graph});
+        }
+        HIP_TRY(hipGraphLaunch(exec, s));
+        continue;
+      }
+      if (int rc = one_stage(st[k], guided)) return rc;
+    }
+  }
+  // (the guard's destructor records graph_done and joins `main` into the caller's stream -- on this path too, so that a
+  // failing record cannot skip the join)
+  HIP_TRY(hipGetLastError());
+  return RGFM_OK;
+}
