@@ -265,7 +265,8 @@ struct RatioRun {
 // Cross evaluation: `what` of every pair (x_i, y_j), out[nx][ny].  Each encoder runs once over its own images; the
 // first score Linear is factorised over the concatenation (cross_ln_silu_kernel) and the rest of the MLP runs over the
 // nx * ny pairs in chunks of `chunk` pair indices, so the scratch does not grow with the matrix.
-constexpr long long RGFM_CROSS_ROWS_DEFAULT = 16384;  // pairs per chunk: 32 MB of first-layer activations at hidden_dim 512
+// pairs per chunk: 32 MB of first-layer activations at hidden_dim 512, 64 MB at the largest, 1024
+constexpr long long RGFM_CROSS_ROWS_DEFAULT = 16384;
 inline long long cross_rows() {  // RGFM_CROSS_ROWS: test hook, read on entry of the two cross entry points
   const char* e = getenv("RGFM_CROSS_ROWS");
   const long long v = e ? atoll(e) : 0;

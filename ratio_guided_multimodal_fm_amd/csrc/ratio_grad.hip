@@ -190,7 +190,8 @@ void launch_grad_act_gn(const float* g, const float* z, const float* ab, float* 
 // nn.GroupNorm backward, in place on gu (d/du, u = gamma xhat + beta) -> d/dz, one workgroup per (sample, group):
 //   d xhat = d u gamma,  d z = rstd (d xhat - mean(d xhat) - xhat mean(d xhat xhat)),  xhat = (z - mean) rstd
 // with (mean, rstd) of the group from gn_finalize (GnFinalizeArgs::mr).  A group is cpg channels x S x S values
-// (3136 at most in the 28x28 encoders): two passes over data that stays in L2.
+// (3136 in the 28x28 encoders, 16384 at most: the flexible kind's first level at 64x64): two passes over data that
+// stays in L2.
 __global__ __launch_bounds__(256) void gn_bwd_kernel(float* __restrict__ gu, const float* __restrict__ z,
                                                      const float* __restrict__ gamma, const float* __restrict__ mr, int HW, int C,
                                                      int groups) {

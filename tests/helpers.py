@@ -141,6 +141,88 @@ def make_sweep_unet(tag, batch, device=None):
     return (m.to(device) if device is not None else m), x, t
 
 
+# Ratio-estimator cases chosen to reach the raster- and width-dependent branches of the ratio kernel chains that the
+# presets and the flexible tests (sizes 8..32, widths (64, 128) and (256, 512)) leave out.  tag -> (x_channels, x_size,
+# y_channels, y_size, feature_dim, hidden_dim, batch, data_seed).  A tag that begins with "ms_" is a
+# RatioEstimatorMNISTSVHN, one that begins with "r28_" a RatioEstimator (their geometry is fixed; it is repeated here);
+# every other tag is a FlexibleRatioEstimator.  Fixed: nothing is drawn at run time.  The data seeds keep every
+# max-pool window away from a tie; tests/ratio_sweep_seeds.py states the rule, holds the search and prints the
+# measured table, tests/test_ratio_sweep_cpu.py checks every entry.
+RATIO_SWEEP = {
+    # --- geometry: one large side, one small side (rasters per level: S, S/2, S/4, S/8)
+    # x: 64 (16 tiles of 4 rows, 64 GroupNorm statistics parts, gn_bwd groups of 16384 values), 32 (multi-tile level
+    # 2), 16 (level 3, one-sample tiles, 64 -> 128 channels), 8 (conv4 and the reverse conv, four samples per tile on
+    # 64 pixels); three input channels.  y: 9x9 = 81 pixels as a single one-sample tile, 9 -> 4 -> 2 -> 1
+    "s64": (3, 64, 1, 9, 192, 384, 2, 2910),
+    # x: odd at every level with ragged tiles, 63 (last tile 3 rows) -> 31 -> 15 -> 7: every pool drops a row and a
+    # column (grad_act_kernel<true> with its memset, pool2 / rt_norm_act_pool / rt_unpool on odd maps).  y: 33 (5 tiles
+    # of 7 rows, the last with 5) -> 16 -> 8 -> 4; four input channels
+    "s63": (2, 63, 4, 33, 320, 640, 2, 2918),
+    # x: 48 (last tile 3 rows), 24 (3 tiles), 12, 6.  y: 40 (last tile 4 rows), 20, 10 (100-pixel one-sample tile), 5
+    "s48": (1, 48, 3, 40, 64, 128, 2, 2320),
+    # x: 56 (14 tiles), 28, 14, 7; four input channels.  y: 17 (two tiles of 9 and 8 rows) -> 8x8 at level 2 in
+    # four-samples-per-tile form -> 4 -> 2
+    "s56": (4, 56, 1, 17, 512, 128, 2, 2509),
+    # x: 36, 18, 9, 4.  y: 25 (tiles of 9, 9, 7 rows), 12, 6, 3
+    "s36": (1, 36, 2, 25, 64, 1024, 2, 2422),
+    # the large raster on the y encoder with four input channels (conv_bwd_img_kernel at 64x64 x 4), at the widest MLP;
+    # x: 15 (odd, two tiles), 7, 3, 1
+    "y64": (1, 15, 4, 64, 512, 1024, 2, 3215),
+    # --- widths, at 1x8 + 1x8 (8, 4, 2, 1), batch 5 (two four-sample tiles, the second with one sample)
+    # linear_mfma_kernel with 3 column blocks (hidden 384), cross_ln_silu / layernorm_silu / rt_ln_act rows of 384 and
+    # 192 (96 and 48 float4: a half-filled second and a partly filled first group of 64 lanes)
+    "w192": (1, 8, 1, 8, 192, 384, 5, 2600),
+    # 5 column blocks (hidden 640) and rows of 640 and 320
+    "w320": (1, 8, 1, 8, 320, 640, 5, 2700),
+    # both at their maximum: 8 column blocks, cross_ln_silu's four float4 per lane exactly full, and the input gradient
+    # of the first score Linear reading all 2 F = 1024 zeros of the bias-free reverse Linears
+    "w512": (1, 8, 1, 8, 512, 1024, 5, 2803),
+    # the narrowest features under the widest hidden layer (K = 128 into 1024 columns)
+    "w64h": (1, 8, 1, 8, 64, 1024, 5, 2900),
+    # the widest features under the narrowest hidden layer (K = 1024 into 128 columns; the reverse Linear 128 -> 1024)
+    "w512n": (1, 8, 1, 8, 512, 128, 5, 3000),
+    # --- the fixed kinds away from (256, 512): RatioEstimatorMNISTSVHN's three-layer MLP (H, H, H / 2) at the
+    # narrowest, a middle and the widest setting; RatioEstimator at the widest.  The BatchNorm estimator has 44 032
+    # windows per sample: of 1000 candidates none reaches the rule's floor in eval mode at batch 2 (best 3.6), so its
+    # eval-mode batch is 1 (RATIO_SWEEP_TRAIN has the training-mode batch)
+    "ms_64": (1, 32, 3, 32, 64, 128, 1, 3197),
+    "ms_192": (1, 32, 3, 32, 192, 640, 1, 3197),
+    "ms_512": (1, 32, 3, 32, 512, 1024, 1, 3197),
+    "r28_512": (1, 28, 1, 28, 512, 1024, 5, 3828),
+}
+# BatchNorm normalises with batch statistics in training mode, so the maps in front of the pools are others than in eval
+# mode and the rule is applied to them on their own: tag -> (batch, data_seed) of the training-mode pass of the "ms_"
+# entries.  Two rows, so that the batch statistics couple them.
+RATIO_SWEEP_TRAIN = {"ms_64": (2, 3939), "ms_192": (2, 3939), "ms_512": (2, 3939)}
+RATIO_SWEEP_W_SEED = {"flexible": 31, "mnist_svhn": SEED_W["ratio_ms"], "mnist28": SEED_W["ratio28"]}
+
+
+def sweep_ratio_kind(tag):
+    return "mnist_svhn" if tag.startswith("ms_") else "mnist28" if tag.startswith("r28_") else "flexible"
+
+
+def make_sweep_ratio(tag, device=None, loss_type="disc"):
+    """The estimator of RATIO_SWEEP[tag] under its kind's synthetic-weight seed, in eval mode."""
+    xc, _, yc, _, feat, hid, _, _ = RATIO_SWEEP[tag]
+    kind = sweep_ratio_kind(tag)
+    ctor = {"flexible": lambda: M.FlexibleRatioEstimator(xc, yc, feat, hid, loss_type),
+            "mnist_svhn": lambda: M.RatioEstimatorMNISTSVHN(feat, hid, loss_type),
+            "mnist28": lambda: M.RatioEstimator(feat, hid, loss_type)}[kind]
+    m = load_synth(ctor(), RATIO_SWEEP_W_SEED[kind]).eval()
+    return m.to(device) if device is not None else m
+
+
+def sweep_ratio_inputs(tag, batch=None, seed=None):
+    """(x, y, cross_x, cross_y) of an entry from its data seed alone: the `batch` pairs the seed was searched for, then
+    3 more x images and 2 more y images for the cross matrix (a max-pool is continuous, so evaluation needs no searched
+    seed; the gradients, whose routing is not, run on the pairs only)."""
+    xc, xs, yc, ys, _, _, b, s = RATIO_SWEEP[tag]
+    batch = b if batch is None else batch
+    g = torch.Generator().manual_seed(s if seed is None else seed)
+    x, y = torch.randn(batch, xc, xs, xs, generator=g), torch.randn(batch, yc, ys, ys, generator=g)
+    return x, y, torch.randn(3, xc, xs, xs, generator=g), torch.randn(2, yc, ys, ys, generator=g)
+
+
 # ------------------------------------------------------------------ conv routing fixture (tests/golden/conv_routes.json)
 # Small descriptors whose per-route conv launch counts (rgfm_unet_conv_routes) are recorded by
 # tests/golden/make_conv_routes.py on the commit BEFORE a change of the conv dispatch and compared by
