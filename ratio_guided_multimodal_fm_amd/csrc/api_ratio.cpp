@@ -622,9 +622,12 @@ struct RatioGradRun {
           c.g = make_geom(k.S, k.S);
           c.halo_px = c.g.spt * (c.g.th + 2) * (c.g.W + 2);
           // Inside the gradient-guided sampler (flag set): the data gradient on the two-plane fp16 arithmetic.  Gradients
-          // are 1e-3 ... 1e-6 in magnitude -- below the raw staging window -- so the conv stages them x 2^-e for the
-          // tensor's measured maximum f 2^e (grad_act wrote its bits) and scales its outputs back; the staged values are
-          // then <= 16 and the x net's range flag covers the rest.  Otherwise (stand-alone gradient, fallback modes,
+          // are far from 1 in magnitude -- typically 1e-3 ... 1e-6, below the raw staging window -- so the conv stages
+          // them x 2^-e for the tensor's measured maximum f 2^e (grad_act wrote its bits) and scales its outputs back;
+          // the staged values are then <= 16 and the x net's range flag covers the rest.  The pre-scale is a power of
+          // two, so the result scales exactly with the gradient: tests/test_gpu_grad_loop.py holds the in-loop
+          // gradient to 1e-4 of its maximum against float64 for image gradients of 6.5e-10 ... 17 in magnitude (the same
+          // relative error at every magnitude).  Otherwise (stand-alone gradient, fallback modes,
           // weights outside the fp16 window): the exact fp32 matrix-core conv.
           bool hx = false;
           if (am) {

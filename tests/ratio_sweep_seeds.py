@@ -2,6 +2,7 @@
 
     python tests/ratio_sweep_seeds.py                 # the table of the committed seeds
     python tests/ratio_sweep_seeds.py --search [tag]  # run the search again (every entry, or one)
+    python tests/ratio_sweep_seeds.py --collect tag N # the first N single-row seeds of an entry (helpers.RATIO_ROW_SEEDS)
 
 A max-pool whose two largest window elements nearly tie may route differently in another fp32 arithmetic or in float64:
 a discontinuity of the function's gradient, not an arithmetic error (tests/test_gpu_ratio_flex.py,
@@ -129,6 +130,27 @@ def search(tag, batch, training=False):
     return best[0], best[1], "best_ratio"
 
 
+def collect(tag, count, training=False):
+    """[(seed, measurement, rule)]: the first `count` candidates of BASE[tag] .. BASE[tag] + 999 that satisfy the rule at
+    batch 1 (agree and gap >= 10 dev), in candidate order; where fewer do, filled up with the agreeing candidates of the
+    largest gap / dev that reach FLOOR ('best_ratio'), so the list may stay shorter than `count`.  The rows of an
+    eval-mode RatioEstimatorMNISTSVHN are independent, so a batch stacked from such single-row seeds
+    (helpers.RATIO_ROW_SEEDS, helpers.stacked_ratio_inputs) keeps every row's margin."""
+    ten, rest = [], []
+    for seed in range(BASE[tag], BASE[tag] + CANDIDATES):
+        r = measure(tag, seed, 1, training)
+        if not r["agree"]:
+            continue
+        if r["ratio"] >= TEN:
+            ten.append((seed, r, "ten_times"))
+            if len(ten) == count:
+                return ten
+        elif r["ratio"] >= FLOOR:
+            rest.append((seed, r, "best_ratio"))
+    rest.sort(key=lambda c: -c[1]["ratio"])
+    return ten + rest[:count - len(ten)]
+
+
 def row(tag, seed, batch, r, note=""):
     return (f"{tag:18s} seed {seed} batch {batch} windows {r['windows']:7d} gap {r['gap']:.3e} dev {r['dev']:.3e} "
             f"ratio {r['ratio']:5.1f} agree {r['agree']} {note}")
@@ -149,6 +171,10 @@ def main(argv):
                     break
                 print(f"{name:18s} batch {batch}: no candidate reaches {FLOOR} (best {r['ratio'] if r else float('nan'):.1f})", flush=True)
                 batch -= 1
+        return 0
+    if argv and argv[0] == "--collect":
+        for seed, r, rule in collect(argv[1], int(argv[2])):
+            print(row(argv[1], seed, 1, r, rule), flush=True)
         return 0
     for tag, e in RATIO_SWEEP.items():
         print(row(tag, e[7], e[6], measure(tag)))
