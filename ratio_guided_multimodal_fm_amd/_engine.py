@@ -620,13 +620,45 @@ class RatioEngine(_EngineBase):
             return [(32, 16), (64, 8), (128, 4)], [(64, 16), (128, 8), (256, 4), (256, 2)]
         return [(32, 14), (64, 7), (128, 3)], [(32, 14), (64, 7), (128, 3)]
 
+    def _check_shapes(self, x, y, rows=("B", "B"), paired=False):
+        """x and y are batches of the bound handle's images (`paired`: of one size); `rows` names their row counts."""
+        sx, sy = self.image_shapes()
+        if (x.dim() != 4 or y.dim() != 4 or tuple(x.shape[1:]) != sx or tuple(y.shape[1:]) != sy
+                or (paired and x.shape[0] != y.shape[0])):
+            raise _lib.RgfmError(f"expected x of shape [{rows[0]},{sx[0]},{sx[1]},{sx[2]}] and y of shape "
+                                 f"[{rows[1]},{sy[0]},{sy[1]},{sy[2]}], got {tuple(x.shape)} and {tuple(y.shape)}")
+
     def _check_pair(self, x, y):
         _require_hip(x, y)
         self.bind(x, y)
-        sx, sy = self.image_shapes()
-        if x.dim() != 4 or y.dim() != 4 or tuple(x.shape[1:]) != sx or tuple(y.shape[1:]) != sy or x.shape[0] != y.shape[0]:
-            raise _lib.RgfmError(f"expected x of shape [B,{sx[0]},{sx[1]},{sx[2]}] and y of shape [B,{sy[0]},{sy[1]},{sy[2]}], got "
-                                 f"{tuple(x.shape)} and {tuple(y.shape)}")
+        self._check_shapes(x, y, paired=True)
+
+    def _checked(self, *tensors):
+        """What every eval-mode call starts with; returns the module."""
+        m = self._module()
+        self._check_eval(m)
+        _require_hip(*tensors)
+        return m
+
+    def _check_xy(self, x, y, rows=None, paired=True):
+        """_checked, equal batch sizes (`paired`), the handle bound, and with `rows` the image shapes."""
+        self._checked(x, y)
+        if paired and x.shape[0] != y.shape[0]:
+            raise _lib.RgfmError("x and y must have the same batch size")
+        self.bind(x, y)
+        if rows:
+            self._check_shapes(x, y, rows)
+
+    def _call(self, dev, ws_fn, ws_args, fn, *args):
+        """One native call in exactly the workspace it asks for: the size query `ws_fn`(handle, *ws_args), then
+        `fn`(handle, *args, workspace, its size, stream)."""
+        L = _lib.lib()
+        with torch.cuda.device(dev):
+            h = self.handle(dev)
+            nb = ctypes.c_size_t()
+            _lib.check(getattr(L, ws_fn)(h, *ws_args, ctypes.byref(nb)))
+            ws = self._ws.get(nb.value, dev)
+            _lib.check(getattr(L, fn)(h, *args, _ptr(ws), nb.value, _stream(dev)))
 
     def forward_train(self, x, y):
         """scores = model(x, y) in the module's current mode, differentiable w.r.t. x, y and the parameters
@@ -662,91 +694,49 @@ class RatioEngine(_EngineBase):
         return out
 
     def eval(self, x, y, what):
-        m = self._module()
-        self._check_eval(m)
-        _require_hip(x, y)
-        if x.shape[0] != y.shape[0]:
-            raise _lib.RgfmError("x and y must have the same batch size")
-        self.bind(x, y)
+        self._check_xy(x, y)
         n = x.shape[0]
         x, y = x.contiguous(), y.contiguous()
         out = torch.empty(n, device=x.device, dtype=torch.float32)
-        if n == 0:
-            return out
-        dev = x.device
-        L = _lib.lib()
-        with torch.cuda.device(dev):
-            h = self.handle(dev)
-            nb = ctypes.c_size_t()
-            _lib.check(L.rgfm_ratio_workspace_bytes(h, n, ctypes.byref(nb)))
-            ws = self._ws.get(nb.value, dev)
-            _lib.check(L.rgfm_ratio_eval(h, _ptr(x), _ptr(y), _ptr(out), n, _RATIO_OUT[what],
-                                         _ptr(ws), nb.value, _stream(dev)))
+        if n:
+            self._call(x.device, "rgfm_ratio_workspace_bytes", (n,),
+                       "rgfm_ratio_eval", _ptr(x), _ptr(y), _ptr(out), n, _RATIO_OUT[what])
         return out
 
     def eval_cross(self, x, y, what):
         """[nx, ny]: `what` of every pair (x_i, y_j) (rgfm_ratio_eval_cross): each encoder runs once per image."""
-        m = self._module()
-        self._check_eval(m)
-        _require_hip(x, y)
-        self.bind(x, y)
-        sx, sy = self.image_shapes()
-        if x.dim() != 4 or y.dim() != 4 or tuple(x.shape[1:]) != sx or tuple(y.shape[1:]) != sy:
-            raise _lib.RgfmError(f"expected x of shape [nx,{sx[0]},{sx[1]},{sx[2]}] and y of shape [ny,{sy[0]},{sy[1]},{sy[2]}], got "
-                                 f"{tuple(x.shape)} and {tuple(y.shape)}")
+        self._check_xy(x, y, rows=("nx", "ny"), paired=False)
         nx, ny = x.shape[0], y.shape[0]
         x, y = x.contiguous(), y.contiguous()
         out = torch.empty(nx, ny, device=x.device, dtype=torch.float32)
-        if nx == 0 or ny == 0:
-            return out
-        dev = x.device
-        L = _lib.lib()
-        with torch.cuda.device(dev):
-            h = self.handle(dev)
-            nb = ctypes.c_size_t()
-            _lib.check(L.rgfm_ratio_cross_workspace_bytes(h, nx, ny, ctypes.byref(nb)))
-            ws = self._ws.get(nb.value, dev)
-            _lib.check(L.rgfm_ratio_eval_cross(h, _ptr(x), nx, _ptr(y), ny, _ptr(out), _RATIO_OUT[what], _ptr(ws),
-                                               nb.value, _stream(dev)))
+        if nx and ny:
+            self._call(x.device, "rgfm_ratio_cross_workspace_bytes", (nx, ny),
+                       "rgfm_ratio_eval_cross", _ptr(x), nx, _ptr(y), ny, _ptr(out), _RATIO_OUT[what])
         return out
 
     def grad_log_ratio(self, x, y):
         """(d log_ratio/dx, d log_ratio/dy, log_ratio): rgfm_ratio_grad_log_ratio (either estimator)."""
-        m = self._module()
-        self._check_eval(m)
-        _require_hip(x, y)
-        if x.shape[0] != y.shape[0]:
-            raise _lib.RgfmError("x and y must have the same batch size")
-        self.bind(x, y)
-        sx, sy = self.image_shapes()
-        if x.dim() != 4 or y.dim() != 4 or tuple(x.shape[1:]) != sx or tuple(y.shape[1:]) != sy:
-            raise _lib.RgfmError(f"expected x of shape [B,{sx[0]},{sx[1]},{sx[2]}] and y of shape [B,{sy[0]},{sy[1]},{sy[2]}], got "
-                                 f"{tuple(x.shape)} and {tuple(y.shape)}")
+        self._check_xy(x, y, rows=("B", "B"))
         n = x.shape[0]
         x, y = x.contiguous(), y.contiguous()
         gx, gy = torch.empty_like(x), torch.empty_like(y)
         lr = torch.empty(n, device=x.device, dtype=torch.float32)
-        if n == 0:
-            return gx, gy, lr
-        dev = x.device
-        L = _lib.lib()
-        with torch.cuda.device(dev):
-            h = self.handle(dev)
-            nb = ctypes.c_size_t()
-            _lib.check(L.rgfm_ratio_grad_workspace_bytes(h, n, ctypes.byref(nb)))
-            ws = self._ws.get(nb.value, dev)
-            _lib.check(L.rgfm_ratio_grad_log_ratio(h, _ptr(x), _ptr(y), _ptr(gx), _ptr(gy), _ptr(lr), n, _ptr(ws),
-                                                   nb.value, _stream(dev)))
+        if n:
+            self._call(x.device, "rgfm_ratio_grad_workspace_bytes", (n,),
+                       "rgfm_ratio_grad_log_ratio", _ptr(x), _ptr(y), _ptr(gx), _ptr(gy), _ptr(lr), n)
         return gx, gy, lr
 
-
     # ---- one side given (conditional sampling) ------------------------
+    @staticmethod
+    def _given_index(given):
+        if given not in ('x', 'y'):
+            raise ValueError(f"given must be 'x' or 'y', got {given!r}")
+        return 0 if given == 'x' else 1
+
     def _bind_given(self, given, cond, target_shape):
         """Select the handle for a condition batch and a target of shape (C, S, S); returns (given as 0 / 1, the
         estimator's image shapes as (condition's, target's))."""
-        if given not in ('x', 'y'):
-            raise ValueError(f"given must be 'x' or 'y', got {given!r}")
-        gi = 0 if given == 'x' else 1
+        gi = self._given_index(given)
         if cond.dim() != 4:
             raise _lib.RgfmError(f"expected condition images [B,C,S,S], got {tuple(cond.shape)}")
         if target_shape is None:
@@ -767,33 +757,21 @@ class RatioEngine(_EngineBase):
         """ctx [B, hidden_dim] = W1[:, given slice] f_given(cond) + b1 (rgfm_ratio_cond_prepare): the condition's encoder
         and its half of the first score Linear, once.  `target_shape` (C, S, S) selects the handle of the flexible kind
         (default: the sizes bound by the latest call); the context itself does not depend on it."""
-        m = self._module()
-        self._check_eval(m)
-        _require_hip(cond)
+        m = self._checked(cond)
         gi, _ = self._bind_given(given, cond, target_shape)
         n, dev = cond.shape[0], cond.device
         cond = cond.to(torch.float32).contiguous()
         ctx = torch.empty(n, m.hidden_dim, device=dev, dtype=torch.float32)
-        if n == 0:
-            return ctx
-        L = _lib.lib()
-        with torch.cuda.device(dev):
-            h = self.handle(dev)
-            nb = ctypes.c_size_t()
-            _lib.check(L.rgfm_ratio_cond_prepare_workspace_bytes(h, gi, n, ctypes.byref(nb)))
-            ws = self._ws.get(nb.value, dev)
-            _lib.check(L.rgfm_ratio_cond_prepare(h, _ptr(cond), gi, n, _ptr(ctx), _ptr(ws), nb.value, _stream(dev)))
+        if n:
+            self._call(dev, "rgfm_ratio_cond_prepare_workspace_bytes", (gi, n),
+                       "rgfm_ratio_cond_prepare", _ptr(cond), gi, n, _ptr(ctx))
         return ctx
 
     def grad_log_ratio_cond(self, ctx, given, target):
         """(d log_ratio/d target, log_ratio) with row b pairing ctx[b] (cond_prepare) and target[b]
         (rgfm_ratio_grad_log_ratio_cond): only the target's encoder runs."""
-        m = self._module()
-        self._check_eval(m)
-        _require_hip(ctx, target)
-        if given not in ('x', 'y'):
-            raise ValueError(f"given must be 'x' or 'y', got {given!r}")
-        gi = 0 if given == 'x' else 1
+        m = self._checked(ctx, target)
+        gi = self._given_index(given)
         if target.dim() != 4:
             raise _lib.RgfmError(f"expected target images [B,C,S,S], got {tuple(target.shape)}")
         self._bind_target(gi, target)
@@ -805,17 +783,9 @@ class RatioEngine(_EngineBase):
         target, ctx = target.contiguous(), ctx.contiguous()
         g = torch.empty_like(target)
         lr = torch.empty(n, device=target.device, dtype=torch.float32)
-        if n == 0:
-            return g, lr
-        dev = target.device
-        L = _lib.lib()
-        with torch.cuda.device(dev):
-            h = self.handle(dev)
-            nb = ctypes.c_size_t()
-            _lib.check(L.rgfm_ratio_grad_cond_workspace_bytes(h, gi, n, ctypes.byref(nb)))
-            ws = self._ws.get(nb.value, dev)
-            _lib.check(L.rgfm_ratio_grad_log_ratio_cond(h, _ptr(ctx), gi, _ptr(target), _ptr(g), _ptr(lr), n, _ptr(ws),
-                                                        nb.value, _stream(dev)))
+        if n:
+            self._call(target.device, "rgfm_ratio_grad_cond_workspace_bytes", (gi, n),
+                       "rgfm_ratio_grad_log_ratio_cond", _ptr(ctx), gi, _ptr(target), _ptr(g), _ptr(lr), n)
         return g, lr
 
     def _bind_target(self, gi, target):

@@ -1,4 +1,6 @@
 // api_ratio.cpp -- ratio estimators: evaluation, gradient of log r, and the gradient-guided paired sampler (C ABI: include/rgfm.h).
+#include <optional>
+
 #include "sampler_host.h"
 
 namespace {
@@ -166,106 +168,7 @@ int pack_ratio(rgfm_ratio* h, hipStream_t s) {
   return read_hx_flags(*h, images, s);
 }
 
-struct RatioRun {
-  rgfm_ratio* h;
-  int n;
-  Bump* ws;
-  hipStream_t s;
-  bool dry;
-
-  // one encoder: image NCHW -> features written at feat[:, col0 : col0+F] (row stride `stride`)
-  void encode(const rgfm_ratio::Encoder& e, const float* img, float* feat, int col0, int stride) {
-    const bool gn = h->gn_encoders();
-    const int F = h->d.feature_dim;
-    int S = e.size;
-    Tensor cur;
-    float* ab = nullptr;  // pending GroupNorm scale/shift of `cur` (mnist28)
-    for (size_t i = 0; i < e.convs.size(); ++i) {
-      const rgfm_ratio::Conv& cv = e.convs[i];
-      const TileGeom g = make_geom(S, S);
-      Tensor o;
-      o.C = cv.w.cout, o.S = S;
-      o.data = ws->f((size_t)n * S * S * o.C);
-      o.stats = gn ? ws->f((size_t)n * g.nparts * o.C * 2) : nullptr;
-      if (!dry) {
-        const float* es = gn ? nullptr : h->bn + cv.bn_scale;
-        const float* eh = gn ? nullptr : h->bn + cv.bn_shift;
-        if (i == 0) {
-          ConvInArgs ci{};
-          ci.x = img, ci.w = h->params + cv.w.w_raw, ci.bias = h->params + cv.w.b;
-          ci.ep_scale = es, ci.ep_shift = eh;
-          ci.out = o.data, ci.stats_out = o.stats, ci.B = n, ci.C0 = o.C, ci.g = g;
-          ProfScope p(RGFM_KCLASS_OTHER, 0, s);
-          launch_conv_in(ci, e.in_ch, s);
-        } else {
-          ConvArgs c{};
-          c.in0 = cur.data, c.C0 = cur.C, c.Hin = c.Win = S;
-          c.wpk = h->packed + cv.w.w_pk, c.bias = h->params + cv.w.b;
-          c.ep_scale = es, c.ep_shift = eh;
-          c.out = o.data, c.stats_out = o.stats, c.B = n, c.Cout = o.C, c.g = g;
-          c.halo_px = g.spt * (g.th + 2) * (g.W + 2);
-          ProfScope p(RGFM_KCLASS_CONV_MFMA, conv_flops(n, S * S, o.C, 9 * cur.C), s);
-          launch_conv(c, CONV_S1, s);
-        }
-      }
-      cur = o;
-      if (gn) {
-        ab = ws->f((size_t)n * o.C * 2);
-        if (!dry) {
-          GnFinalizeArgs f{};
-          f.stats0 = o.stats, f.C0 = o.C, f.groups = 8;
-          f.gamma = h->params + cv.nw, f.beta = h->params + cv.nb, f.ab = ab, f.B = n, f.g = g;
-          ProfScope p(RGFM_KCLASS_OTHER, 0, s);
-          launch_gn_finalize(f, s);
-        }
-      }
-      if (cv.pool_after) {
-        Tensor pl;
-        pl.C = cur.C, pl.S = S / 2;
-        pl.data = ws->f((size_t)n * pl.S * pl.S * pl.C);
-        if (!dry) {
-          ProfScope p(RGFM_KCLASS_OTHER, 0, s);
-          launch_pool2(cur.data, gn ? ab : nullptr, pl.data, n, S, S, cur.C, s);
-        }
-        cur = pl;
-        S /= 2;
-        ab = nullptr;
-      }
-    }
-    float* pooled = ws->f((size_t)n * cur.C);
-    if (!dry) {
-      ProfScope p(RGFM_KCLASS_OTHER, 0, s);
-      launch_avgpool(cur.data, ab, pooled, n, S * S, cur.C, s);
-      launch_linear_mfma(pooled, h->params + e.fcw, h->params + e.fcb, feat + col0, n, cur.C, F, cur.C, stride, s);
-    }
-  }
-
-  void run(const float* x, const float* y, float* out, int what) {
-    const int F = h->d.feature_dim;
-    float* feat = ws->f((size_t)n * 2 * F);
-    encode(h->ex, x, feat, 0, 2 * F);
-    encode(h->ey, y, feat, F, 2 * F);
-    float* cur = feat;
-    for (const auto& dn : h->hidden) {
-      float* nxt = ws->f((size_t)n * dn.out);
-      if (!dry) {
-        ProfScope p(RGFM_KCLASS_OTHER, 0, s);
-        launch_linear_mfma(cur, h->params + dn.w, h->params + dn.b, nxt, n, dn.in, dn.out, dn.in, dn.out, s);
-        launch_layernorm_silu(nxt, h->params + dn.lw, h->params + dn.lb, n, dn.out, s);
-      }
-      cur = nxt;
-    }
-    if (!dry) {
-      ProfScope p(RGFM_KCLASS_OTHER, 0, s);
-      launch_ratio_head(cur, h->params + h->headw, h->params + h->headb, out, n, h->head_in, h->d.loss_type, what, s);
-    }
-  }
-};
-
-// Cross evaluation: `what` of every pair (x_i, y_j), out[nx][ny].  Each encoder runs once over its own images; the
-// first score Linear is factorised over the concatenation (cross_ln_silu_kernel) and the rest of the MLP runs over the
-// nx * ny pairs in chunks of `chunk` pair indices, so the scratch does not grow with the matrix.
-// pairs per chunk: 32 MB of first-layer activations at hidden_dim 512, 64 MB at the largest, 1024
+// pairs per chunk of the cross evaluation: 32 MB of first-layer activations at hidden_dim 512, 64 MB at the largest, 1024
 constexpr long long RGFM_CROSS_ROWS_DEFAULT = 16384;
 inline long long cross_rows() {  // RGFM_CROSS_ROWS: test hook, read on entry of the two cross entry points
   const char* e = getenv("RGFM_CROSS_ROWS");
@@ -273,15 +176,238 @@ inline long long cross_rows() {  // RGFM_CROSS_ROWS: test hook, read on entry of
   return v >= 1 && v <= (1 << 20) ? v : RGFM_CROSS_ROWS_DEFAULT;
 }
 
-struct RatioCrossRun {
+// what a conv of the encoder walk leaves for the reverse pass
+struct Kept {
+  float* z;  // its pre-activation (GroupNorm kinds: the conv output; BatchNorm kind: the BatchNorm output)
+  int C, S;
+  bool pooled;
+  float* ab = nullptr;  // GroupNorm encoders: the samples' scale/shift pairs [n][C][2] ...
+  float* mr = nullptr;  // ... and (mean, rstd) of every group [n][8][2]
+};
+
+// One pass over an estimator handle: n rows, buffers carved from `ws`, launches on `s`; dry = carve only.  Every entry
+// point is a member, run dry for its *_workspace_bytes figure and live for the call (ratio_call below, and the carves
+// of the two gradient-guided loops).
+struct RatioPass {
   rgfm_ratio* h;
-  int nx, ny;
+  int n;
   Bump* ws;
   hipStream_t s;
   bool dry;
-  long long chunk;
+  // the range-flag word of the U-Net handle whose sampler loop this pass belongs to, or null (stand-alone gradient:
+  // exact fp32 convs).  With it the encoders' forward convs follow that handle's conv arithmetic (g_modes, set by the
+  // caller's ModeScope) and raise ITS flag, so that the sampler's range guard and fallback cover them.
+  unsigned* flag = nullptr;
+  float* ab1 = nullptr;  // [n][max_c][2] identity scale/shift: "SiLU on load"
+  unsigned* amax = nullptr;  // one word per reverse conv: bits of max |gradient| of its input (ConvArgs::in_amax); zeroed per call
+  int amax_used = 0;
 
-  void run(const float* x, const float* y, float* out, int what) {
+  RatioPass rows(int m) const {  // the same pass over m rows
+    RatioPass p = *this;
+    p.n = m;
+    return p;
+  }
+
+  // One encoder forward (the ImageEncoder of ratio_estimator.py:67-93 / ratio_flexible.py:42-66 and the two BatchNorm
+  // encoders of RatioEstimatorMNISTSVHN): image NCHW -> features written at feat[:, col0 : col0+F] (row stride `stride`).
+  // kept == null, inference: a GroupNorm conv writes its partial statistics, gn_finalize turns them into the scale/shift
+  // pairs that the max-pool / average pool behind it applies with SiLU; a BatchNorm conv applies the folded scale/shift
+  // and SiLU in its epilogue.
+  // kept != null, the forward of a gradient pass: the same launches with every pre-activation kept, one Kept per conv.
+  // GroupNorm: the finalize also writes (mean, rstd).  BatchNorm: the epilogue stores z instead of silu(z) (ep_nosilu)
+  // and whoever reads z applies SiLU on load through the identity pairs ab1 (begin_grad); inside a sampler loop (`flag`)
+  // these convs are offered the two-plane fp16 image of their weights.
+  void encode(const rgfm_ratio::Encoder& e, const float* img, float* feat, int col0, int stride, std::vector<Kept>* kept) {
+    const bool gn = h->gn_encoders(), keep_z = kept && !gn;
+    const int F = h->d.feature_dim;
+    int S = e.size, curC = e.in_ch;
+    const float* cur = nullptr;  // input of the next conv
+    const float* act = nullptr;  // ... and the scale/shift pairs its reader applies with SiLU, or null: `cur` is final
+    for (size_t i = 0; i < e.convs.size(); ++i) {
+      const rgfm_ratio::Conv& cv = e.convs[i];
+      const TileGeom g = make_geom(S, S);
+      const int C = cv.w.cout;
+      float* z = ws->f((size_t)n * S * S * C);
+      float* stats = gn ? ws->f((size_t)n * g.nparts * C * 2) : nullptr;
+      float* ab = gn ? ws->f((size_t)n * C * 2) : nullptr;
+      float* mr = gn && kept ? ws->f((size_t)n * 8 * 2) : nullptr;
+      if (!dry) {
+        const float* es = gn ? nullptr : h->bn + cv.bn_scale;
+        const float* eh = gn ? nullptr : h->bn + cv.bn_shift;
+        if (i == 0) {
+          ConvInArgs ci{};
+          ci.x = img, ci.w = h->params + cv.w.w_raw, ci.bias = h->params + cv.w.b;
+          ci.ep_scale = es, ci.ep_shift = eh, ci.ep_nosilu = keep_z;
+          ci.out = z, ci.stats_out = stats, ci.B = n, ci.C0 = C, ci.g = g;
+          ProfScope p(RGFM_KCLASS_OTHER, 0, s);
+          launch_conv_in(ci, e.in_ch, s);
+        } else {
+          ConvArgs c{};
+          c.in0 = cur, c.C0 = curC, c.Hin = c.Win = S, c.ab = act;
+          c.wpk = h->packed + cv.w.w_pk, c.bias = h->params + cv.w.b;
+          c.ep_scale = es, c.ep_shift = eh, c.ep_nosilu = keep_z;
+          c.out = z, c.stats_out = stats, c.B = n, c.Cout = C, c.g = g;
+          c.halo_px = g.spt * (g.th + 2) * (g.W + 2);
+          // (fp16 two-plane conv with the BatchNorm epilogue, any of its pipelined forms; without the image conv_route
+          // ends at the fp32 MFMA kernel)
+          if (keep_z && flag && g_modes.conv == CONV_ARITH_HX2 && cv.w.hx.ok)
+            c.wpkh = h->packedh + cv.w.hx.off, c.hq = h->hq + 4 * cv.w.hx.hq, c.range_flag = flag;
+          ProfScope p(RGFM_KCLASS_CONV_MFMA, conv_flops(n, S * S, C, 9 * curC), s);
+          launch_conv(c, CONV_S1, s);
+        }
+        if (gn) {
+          GnFinalizeArgs f{};
+          f.stats0 = stats, f.C0 = C, f.groups = 8;
+          f.gamma = h->params + cv.nw, f.beta = h->params + cv.nb, f.ab = ab, f.mr = mr, f.B = n, f.g = g;
+          ProfScope p(RGFM_KCLASS_OTHER, 0, s);
+          launch_gn_finalize(f, s);
+        }
+      }
+      if (kept) kept->push_back({z, C, S, cv.pool_after, ab, mr});
+      cur = z, curC = C, act = gn ? ab : keep_z ? ab1 : nullptr;
+      if (cv.pool_after) {
+        float* pl = ws->f((size_t)n * (S / 2) * (S / 2) * C);
+        if (!dry) {
+          ProfScope p(RGFM_KCLASS_OTHER, 0, s);
+          launch_pool2(z, act, pl, n, S, S, C, s);
+        }
+        cur = pl, act = nullptr, S /= 2;
+      }
+    }
+    float* pooled = ws->f((size_t)n * curC);
+    if (!dry) {
+      ProfScope p(RGFM_KCLASS_OTHER, 0, s);
+      launch_avgpool(cur, act, pooled, n, S * S, curC, s);
+      launch_linear_mfma(pooled, h->params + e.fcw, h->params + e.fcb, feat + col0, n, curC, F, curC, stride, s);
+    }
+  }
+
+  // reverse pass of one encoder: gfeat [n][stride] (columns col0 .. col0+F) -> gimg NCHW
+  void encode_bwd(const rgfm_ratio::Encoder& e, const std::vector<Kept>& kept, const float* gfeat, int col0, int stride, float* gimg) {
+    const int F = h->d.feature_dim;
+    const float* zeros = h->gradw + h->g_zeros;
+    const Kept& last = kept.back();
+    float* g = ws->f((size_t)n * last.C);  // gradient of the average-pooled vector
+    if (!dry) launch_linear_mfma(gfeat + col0, h->gradw + e.fcw_t, zeros, g, n, F, last.C, stride, last.C, s);
+    int mode = 2;  // first step: g is [n][C] behind the global average pool
+    for (int i = (int)kept.size() - 1; i >= 0; --i) {
+      const Kept& k = kept[i];
+      const rgfm_ratio::Conv& cv = e.convs[i];
+      if (i != (int)kept.size() - 1) mode = k.pooled ? 1 : 0;
+      else mode = k.pooled ? 3 : 2;  // (SVHN encoder: a max-pool sits between the last conv and the average pool)
+      float* gz = ws->f((size_t)n * k.S * k.S * k.C);
+      unsigned* am = nullptr;
+      if (!dry) {
+        if (k.ab) {  // GroupNorm encoder: SiLU' (and the max-pool routing) at u = a z + b, then the norm's backward in place
+          launch_grad_act_gn(g, k.z, k.ab, gz, n, k.S, k.C, mode, s);
+          launch_gn_bwd(gz, k.z, h->params + cv.nw, k.mr, n, k.S * k.S, k.C, 8, s);
+        } else {
+          // (inside the sampler the next conv runs on the two-plane arithmetic: it needs the tensor's magnitude)
+          am = (flag && i > 0 && amax && g_modes.conv == CONV_ARITH_HX2 && g_modes.rev_hx2 && cv.wt_h.ok) ? amax + amax_used++ : nullptr;
+          launch_grad_act(g, k.z, h->bn + cv.bn_scale, gz, n, k.S, k.C, mode, s, am);
+        }
+      }
+      if (i == 0) {
+        if (!dry) launch_conv_bwd_img(gz, h->params + cv.w.w_raw, gimg, n, k.S, k.C, e.in_ch, s);
+      } else {
+        float* gin = ws->f((size_t)n * k.S * k.S * cv.w.cin);
+        if (!dry) {
+          ConvArgs c{};
+          c.in0 = gz, c.C0 = k.C, c.Hin = c.Win = k.S;
+          c.wpk = h->gradw + cv.wt_pk, c.bias = zeros;
+          c.out = gin, c.stats_out = nullptr, c.B = n, c.Cout = cv.w.cin;
+          c.g = make_geom(k.S, k.S);
+          c.halo_px = c.g.spt * (c.g.th + 2) * (c.g.W + 2);
+          // Inside the gradient-guided sampler (flag set): the data gradient on the two-plane fp16 arithmetic.  Gradients
+          // are far from 1 in magnitude -- typically 1e-3 ... 1e-6, below the raw staging window -- so the conv stages
+          // them x 2^-e for the tensor's measured maximum f 2^e (grad_act wrote its bits) and scales its outputs back;
+          // the staged values are then <= 16 and the x net's range flag covers the rest.  The pre-scale is a power of
+          // two, so the result scales exactly with the gradient: tests/test_gpu_grad_loop.py holds the in-loop
+          // gradient to 1e-4 of its maximum against float64 for image gradients of 6.5e-10 ... 17 in magnitude (the same
+          // relative error at every magnitude; DESIGN.md section 11).  Otherwise (stand-alone gradient, fallback modes,
+          // weights outside the fp16 window): the exact fp32 matrix-core conv.
+          bool hx = false;
+          if (am) {
+            c.wpkh = h->packedh + cv.wt_h.off, c.hq = h->hq + 4 * cv.wt_h.hq, c.range_flag = flag, c.in_amax = am;
+            hx = conv_hx2_supported(c, CONV_S1);
+          }
+          if (hx) launch_conv_hx2(c, CONV_S1, s);
+          else launch_conv_mfma(c, CONV_S1, s);
+        }
+        g = gin;
+      }
+    }
+  }
+
+  // Hidden layers first .. last of the score MLP forward from `cur`: buffers of n rows, launches over rows <= n of them.
+  // us == null: Linear, then LayerNorm + SiLU in place (`scoped`: under the launch timers, one scope per layer).
+  // us != null, the forward of a gradient pass: each Linear's output u is kept (appended to *us) and a copy normalised.
+  // Returns the last activation.
+  float* mlp_fwd(size_t first, float* cur, int rows, std::vector<float*>* us, bool scoped = false) {
+    for (size_t l = first; l < h->hidden.size(); ++l) {
+      const auto& dn = h->hidden[l];
+      float* u = ws->f((size_t)n * dn.out);
+      float* a = us ? ws->f((size_t)n * dn.out) : u;
+      if (!dry) {
+        std::optional<ProfScope> p;
+        if (scoped) p.emplace(RGFM_KCLASS_OTHER, 0, s);
+        launch_linear_mfma(cur, h->params + dn.w, h->params + dn.b, u, rows, dn.in, dn.out, dn.in, dn.out, s);
+        if (us) (void)hipMemcpyAsync(a, u, (size_t)rows * dn.out * sizeof(float), hipMemcpyDeviceToDevice, s);
+        launch_layernorm_silu(a, h->params + dn.lw, h->params + dn.lb, rows, dn.out, s);
+      }
+      if (us) us->push_back(u);
+      cur = a;
+    }
+    return cur;
+  }
+
+  void head(const float* a, float* out, int rows, int what) {
+    launch_ratio_head(a, h->params + h->headw, h->params + h->headb, out, rows, h->head_in, h->d.loss_type, what, s);
+  }
+
+  // The head on the last activation `a`, its backward (writes log_ratio when asked) and the hidden layers in reverse
+  // over their kept outputs `us`.  Layer 0 gives the gradient of `in0` of its input columns, those whose rows of the
+  // transposed weight start at row `row0` (rows of W^T are contiguous): all 2F from 0, or one side's F.  Returns it, [n][in0].
+  float* mlp_bwd(const float* a, const std::vector<float*>& us, int in0, int row0, float* log_ratio) {
+    const float* zeros = h->gradw + h->g_zeros;
+    float* score = ws->f(n);
+    float* g = ws->f((size_t)n * h->head_in);
+    if (!dry) {
+      head(a, score, n, 0);
+      launch_ratio_head_bwd(score, h->params + h->headw, g, log_ratio, n, h->head_in, h->d.loss_type, s);
+    }
+    for (int l = (int)h->hidden.size() - 1; l >= 0; --l) {
+      const auto& dn = h->hidden[l];
+      const int in = l ? dn.in : in0;
+      const float* wt = h->gradw + dn.w_t + (l ? 0 : (size_t)row0 * dn.out);
+      float* gu = ws->f((size_t)n * dn.out);
+      float* gi = ws->f((size_t)n * in);
+      if (!dry) {
+        launch_layernorm_silu_bwd(us[l], g, h->params + dn.lw, h->params + dn.lb, gu, n, dn.out, s);
+        launch_linear_mfma(gu, wt, zeros, gi, n, dn.out, in, dn.out, in, s);
+      }
+      g = gi;
+    }
+    return g;
+  }
+
+  // ---- the entry points
+  void eval(const float* x, const float* y, float* out, int what) {
+    const int F = h->d.feature_dim;
+    float* feat = ws->f((size_t)n * 2 * F);
+    encode(h->ex, x, feat, 0, 2 * F, nullptr);
+    encode(h->ey, y, feat, F, 2 * F, nullptr);
+    const float* a = mlp_fwd(0, feat, n, nullptr, true);
+    if (!dry) {
+      ProfScope p(RGFM_KCLASS_OTHER, 0, s);
+      head(a, out, n, what);
+    }
+  }
+
+  // Cross evaluation: `what` of every pair (x_i, y_j), out[nx][ny].  Each encoder runs once over its own images; the
+  // first score Linear is factorised over the concatenation (cross_ln_silu_kernel) and the rest of the MLP runs over the
+  // nx * ny pairs in chunks of `chunk` pair indices, so the scratch does not grow with the matrix.
+  void cross(const float* x, int nx, const float* y, int ny, float* out, int what, long long chunk) {
     const int F = h->d.feature_dim;
     const auto& d0 = h->hidden[0];
     float* fx = ws->f((size_t)nx * F);
@@ -291,34 +417,117 @@ struct RatioCrossRun {
     // the encoders' scratch is dead once the features are written: the two walks and the MLP chunk share one region
     const size_t mark = ws->off;
     size_t peak = mark;
-    RatioRun rx{h, nx, ws, s, dry};
-    rx.encode(h->ex, x, fx, 0, F);
+    rows(nx).encode(h->ex, x, fx, 0, F, nullptr);
     peak = std::max(peak, ws->off), ws->off = mark;
-    RatioRun ry{h, ny, ws, s, dry};
-    ry.encode(h->ey, y, fy, 0, F);
+    rows(ny).encode(h->ey, y, fy, 0, F, nullptr);
     peak = std::max(peak, ws->off), ws->off = mark;
     const long long total = (long long)nx * ny;
-    const int rows_max = (int)std::min(total, chunk);
-    std::vector<float*> act;
-    for (const auto& dn : h->hidden) act.push_back(ws->f((size_t)rows_max * dn.out));
-    peak = std::max(peak, ws->off), ws->off = peak;
+    RatioPass mlp = rows((int)std::min(total, chunk));
+    std::optional<ProfScope> p;
+    if (!dry) {
+      p.emplace(RGFM_KCLASS_OTHER, 0, s);
+      const float* zeros = h->gradw + h->g_zeros;
+      launch_linear_mfma(fx, h->gradw + h->w1x, zeros, ux, nx, F, d0.out, F, d0.out, s);
+      launch_linear_mfma(fy, h->gradw + h->w1y, zeros, uy, ny, F, d0.out, F, d0.out, s);
+    }
+    for (long long r0 = 0; r0 < total; r0 += chunk) {
+      const int m = (int)std::min(chunk, total - r0);
+      ws->off = mark;  // (every chunk in the buffers of the first, the largest)
+      float* a0 = ws->f((size_t)mlp.n * d0.out);
+      if (!dry) launch_cross_ln_silu(ux, uy, h->params + d0.b, h->params + d0.lw, h->params + d0.lb, a0, r0, m, ny, d0.out, s);
+      const float* a = mlp.mlp_fwd(1, a0, m, nullptr);
+      if (dry) break;
+      head(a, out + r0, m, what);
+    }
+    ws->off = std::max(peak, ws->off);
+  }
+
+  // ctx [n][Hd] = W[:, given slice] f_given(cond) + b of the first score Linear: the given side's encoder once (as the
+  // cross path runs it) and one linear_mfma on the contiguous column slice pack_ratio keeps.
+  void cond_prepare(const float* cond, int given, float* ctx) {
+    const int F = h->d.feature_dim;
+    const auto& d0 = h->hidden[0];
+    float* feat = ws->f((size_t)n * F);
+    encode(given ? h->ey : h->ex, cond, feat, 0, F, nullptr);
     if (dry) return;
     ProfScope p(RGFM_KCLASS_OTHER, 0, s);
-    const float* zeros = h->gradw + h->g_zeros;
-    launch_linear_mfma(fx, h->gradw + h->w1x, zeros, ux, nx, F, d0.out, F, d0.out, s);
-    launch_linear_mfma(fy, h->gradw + h->w1y, zeros, uy, ny, F, d0.out, F, d0.out, s);
-    for (long long r0 = 0; r0 < total; r0 += chunk) {
-      const int rows = (int)std::min(chunk, total - r0);
-      launch_cross_ln_silu(ux, uy, h->params + d0.b, h->params + d0.lw, h->params + d0.lb, act[0], r0, rows, ny, d0.out, s);
-      for (size_t l = 1; l < h->hidden.size(); ++l) {
-        const auto& dn = h->hidden[l];
-        launch_linear_mfma(act[l - 1], h->params + dn.w, h->params + dn.b, act[l], rows, dn.in, dn.out, dn.in, dn.out, s);
-        launch_layernorm_silu(act[l], h->params + dn.lw, h->params + dn.lb, rows, dn.out, s);
-      }
-      launch_ratio_head(act.back(), h->params + h->headw, h->params + h->headb, out + r0, rows, h->head_in, h->d.loss_type, what, s);
+    launch_linear_mfma(feat, h->gradw + (given ? h->w1y : h->w1x), h->params + d0.b, ctx, n, F, d0.out, F, d0.out, s);
+  }
+
+  // ---- gradient of log r.  The forward with every pre-activation kept (encode with `kept`, mlp_fwd
+  // with `us`: same kernels as inference), then the reverse pass down to the images: ratio_grad.hip, linear_mfma with
+  // W^T, conv_mfma with the transposed weights (dL/d(in) of a 3x3 conv: pack_ratio).
+  void begin_grad() {
+    ab1 = ws->f((size_t)n * h->max_c * 2);
+    amax = ws->u(64);
+    amax_used = 0;
+    if (!dry) {
+      launch_fill_ab_identity(ab1, (size_t)n * h->max_c, s);
+      (void)hipMemsetAsync(amax, 0, 64 * sizeof(unsigned), s);
     }
   }
+
+  void grad(const float* x, const float* y, float* gx, float* gy, float* log_ratio) {
+    const int F = h->d.feature_dim;
+    begin_grad();
+    float* feat = ws->f((size_t)n * 2 * F);
+    std::vector<Kept> kx, ky;
+    encode(h->ex, x, feat, 0, 2 * F, &kx);
+    encode(h->ey, y, feat, F, 2 * F, &ky);
+    std::vector<float*> us;
+    const float* a = mlp_fwd(0, feat, n, &us);
+    const float* g = mlp_bwd(a, us, 2 * F, 0, log_ratio);
+    encode_bwd(h->ex, kx, g, 0, 2 * F, gx);
+    encode_bwd(h->ey, ky, g, F, 2 * F, gy);
+  }
+
+  // One side only (conditional sampling): d log_ratio / d target with the other side's share of the first score Linear,
+  // ctx [n][Hd] = W[:, given slice] f_given + b (cond_prepare), held fixed.  Only the target's encoder runs, forward
+  // and reverse; the first hidden layer is u = ctx + W[:, target slice] f_target (cond_ln_silu_kernel), and its input
+  // gradient is taken for the target's F columns alone.
+  void grad_cond(const float* ctx, int given, const float* target, float* g_target, float* log_ratio) {
+    const int F = h->d.feature_dim;
+    const auto& d0 = h->hidden[0];
+    begin_grad();
+    const rgfm_ratio::Encoder& e = given ? h->ex : h->ey;
+    float* feat = ws->f((size_t)n * F);
+    std::vector<Kept> kt;
+    encode(e, target, feat, 0, F, &kt);
+    float* u = ws->f((size_t)n * d0.out);
+    float* a0 = ws->f((size_t)n * d0.out);
+    float* ut = ws->f((size_t)n * d0.out);
+    if (!dry) {
+      launch_linear_mfma(feat, h->gradw + (given ? h->w1x : h->w1y), h->gradw + h->g_zeros, ut, n, F, d0.out, F, d0.out, s);
+      launch_cond_ln_silu(ctx, ut, h->params + d0.lw, h->params + d0.lb, u, a0, n, d0.out, s);
+    }
+    std::vector<float*> us{u};
+    const float* a = mlp_fwd(1, a0, n, &us);
+    const float* g = mlp_bwd(a, us, F, given ? 0 : F, log_ratio);
+    encode_bwd(e, kt, g, 0, F, g_target);
+  }
 };
+
+// A stand-alone entry point is its own argument checks and one of these around its body, a member call on the pass.
+// Run dry over an empty Bump, the body's end offset is the *_workspace_bytes figure; the call computes the same figure,
+// refuses a smaller workspace before anything is launched, and runs the same body over the caller's workspace.
+template <class Body>
+size_t ratio_bytes(const rgfm_ratio* h, int n, Body&& body) {
+  Bump b;
+  RatioPass p{const_cast<rgfm_ratio*>(h), n, &b, nullptr, true};
+  body(p);
+  return b.off;
+}
+template <class Body>
+int ratio_call(rgfm_ratio* h, int n, void* ws, size_t ws_bytes, rgfm_stream_t stream, Body&& body) {
+  const size_t need = ratio_bytes(h, n, body);
+  if (need > ws_bytes) return fail(RGFM_ENOMEM, "workspace too small: %zu < %zu", ws_bytes, need);
+  refresh_modes();
+  Bump b(ws, ws_bytes);
+  RatioPass p{h, n, &b, (hipStream_t)stream, false};
+  body(p);
+  HIP_TRY(hipGetLastError());
+  return RGFM_OK;
+}
 
 }  // namespace
 
@@ -397,438 +606,117 @@ extern "C" int rgfm_ratio_update_params(rgfm_ratio* h, const float* params_dev, 
   return pack_ratio(h, s);
 }
 
+namespace {
+int bad_unless(bool ok) { return ok ? RGFM_OK : fail(RGFM_EINVAL, "bad argument"); }
+int check_what(int what) { return what >= 0 && what <= 2 ? RGFM_OK : fail(RGFM_EINVAL, "bad output selector"); }
+int check_given(int given) { return given == 0 || given == 1 ? RGFM_OK : fail(RGFM_EINVAL, "given must be 0 (the condition is x) or 1 (y)"); }
+}  // namespace
+
 extern "C" int rgfm_ratio_workspace_bytes(const rgfm_ratio* h, int n, size_t* bytes) {
-  if (!h || !bytes || n < 1) return fail(RGFM_EINVAL, "bad argument");
-  Bump b;
-  RatioRun r{const_cast<rgfm_ratio*>(h), n, &b, nullptr, true};
-  r.run(nullptr, nullptr, nullptr, 0);
-  *bytes = b.off;
+  if (int rc = bad_unless(h && bytes && n >= 1)) return rc;
+  *bytes = ratio_bytes(h, n, [](RatioPass& p) { p.eval(nullptr, nullptr, nullptr, 0); });
   return RGFM_OK;
 }
 
 extern "C" int rgfm_ratio_eval(rgfm_ratio* h, const float* x, const float* y, float* out, int n, int what,
                                void* ws, size_t ws_bytes, rgfm_stream_t stream) {
-  refresh_modes();
   if (!h || !x || !y || !out || !ws) return fail(RGFM_EINVAL, "null argument");
-  if (what < 0 || what > 2) return fail(RGFM_EINVAL, "bad output selector");
-  size_t need = 0;
-  int rc = rgfm_ratio_workspace_bytes(h, n, &need);
-  if (rc) return rc;
-  if (need > ws_bytes) return fail(RGFM_ENOMEM, "workspace too small: %zu < %zu", ws_bytes, need);
-  Bump b(ws, ws_bytes);
-  RatioRun r{h, n, &b, (hipStream_t)stream, false};
-  r.run(x, y, out, what);
-  HIP_TRY(hipGetLastError());
-  return RGFM_OK;
+  int rc = check_what(what);
+  if (rc || (rc = bad_unless(n >= 1))) return rc;
+  return ratio_call(h, n, ws, ws_bytes, stream, [&](RatioPass& p) { p.eval(x, y, out, what); });
 }
 
 extern "C" int rgfm_ratio_cross_workspace_bytes(const rgfm_ratio* h, int nx, int ny, size_t* bytes) {
-  if (!h || !bytes || nx < 1 || ny < 1) return fail(RGFM_EINVAL, "bad argument");
-  Bump b;
-  RatioCrossRun r{const_cast<rgfm_ratio*>(h), nx, ny, &b, nullptr, true, cross_rows()};
-  r.run(nullptr, nullptr, nullptr, 0);
-  *bytes = b.off;
+  const long long chunk = cross_rows();
+  if (int rc = bad_unless(h && bytes && nx >= 1 && ny >= 1)) return rc;
+  *bytes = ratio_bytes(h, 0, [&](RatioPass& p) { p.cross(nullptr, nx, nullptr, ny, nullptr, 0, chunk); });
   return RGFM_OK;
 }
 
 extern "C" int rgfm_ratio_eval_cross(rgfm_ratio* h, const float* x, int nx, const float* y, int ny, float* out, int what,
                                      void* ws, size_t ws_bytes, rgfm_stream_t stream) {
-  refresh_modes();
+  const long long chunk = cross_rows();
   if (!h || !x || !y || !out || !ws) return fail(RGFM_EINVAL, "null argument");
-  if (what < 0 || what > 2) return fail(RGFM_EINVAL, "bad output selector");
-  size_t need = 0;
-  int rc = rgfm_ratio_cross_workspace_bytes(h, nx, ny, &need);
-  if (rc) return rc;
-  if (need > ws_bytes) return fail(RGFM_ENOMEM, "workspace too small: %zu < %zu", ws_bytes, need);
-  Bump b(ws, ws_bytes);
-  RatioCrossRun r{h, nx, ny, &b, (hipStream_t)stream, false, cross_rows()};
-  r.run(x, y, out, what);
-  HIP_TRY(hipGetLastError());
-  return RGFM_OK;
+  int rc = check_what(what);
+  if (rc || (rc = bad_unless(nx >= 1 && ny >= 1))) return rc;
+  return ratio_call(h, 0, ws, ws_bytes, stream, [&](RatioPass& p) { p.cross(x, nx, y, ny, out, what, chunk); });
 }
-
-// ------------------------------------------------------------------ gradient of log r
-namespace {
-
-// Forward of RatioEstimatorMNISTSVHN with every pre-activation kept (BatchNorm output z of each conv, Linear output
-// u of each score_net layer), then the reverse pass down to the two images.  Same kernels as RatioRun for the
-// forward (the conv epilogue stores z instead of silu(z); SiLU is applied by the consumer through an identity
-// scale/shift array), conv_mfma with transposed weights / linear_mfma with W^T / ratio_grad.hip for the reverse.
-struct RatioGradRun {
-  rgfm_ratio* h;
-  int n;
-  Bump* ws;
-  hipStream_t s;
-  bool dry;
-  // the range-flag word of the U-Net handle whose sampler loop this pass belongs to, or null (stand-alone gradient:
-  // exact fp32 convs).  With it the encoders' forward convs follow that handle's conv arithmetic (g_modes, set by the
-  // caller's ModeScope) and raise ITS flag, so that the sampler's range guard and fallback cover them.
-  unsigned* flag = nullptr;
-  float* ab1 = nullptr;  // [n][max_c][2] identity scale/shift: "SiLU on load"
-  unsigned* amax = nullptr;  // one word per reverse conv: bits of max |gradient| of its input (ConvArgs::in_amax); zeroed per call
-  int amax_used = 0;
-  int fs = 0;  // row stride of the feature / feature-gradient matrices: 0 = 2F (both sides, [f_x | f_y]); F in the one-sided run
-  int fstride() const { return fs ? fs : 2 * h->d.feature_dim; }
-
-  struct Kept {
-    float* z;
-    int C, S;
-    bool pooled;
-    float* ab = nullptr;  // GroupNorm encoders: the samples' scale/shift pairs [n][C][2] ...
-    float* mr = nullptr;  // ... and (mean, rstd) of every group [n][8][2]
-  };
-
-  // The GroupNorm ImageEncoder (ratio_estimator.py:67-93, ratio_flexible.py:42-66) with the conv outputs and their
-  // norms' statistics kept
-  void encode_gn(const rgfm_ratio::Encoder& e, const float* img, float* feat, int col0, std::vector<Kept>& kept) {
-    const int F = h->d.feature_dim;
-    int S = e.size;
-    const float* cur = nullptr;
-    int curC = e.in_ch;
-    for (size_t i = 0; i < e.convs.size(); ++i) {
-      const rgfm_ratio::Conv& cv = e.convs[i];
-      const TileGeom g = make_geom(S, S);
-      const int C = cv.w.cout;
-      float* z = ws->f((size_t)n * S * S * C);
-      float* stats = ws->f((size_t)n * g.nparts * C * 2);
-      float* ab = ws->f((size_t)n * C * 2);
-      float* mr = ws->f((size_t)n * 8 * 2);
-      if (!dry) {
-        if (i == 0) {
-          ConvInArgs ci{};
-          ci.x = img, ci.w = h->params + cv.w.w_raw, ci.bias = h->params + cv.w.b;
-          ci.out = z, ci.stats_out = stats, ci.B = n, ci.C0 = C, ci.g = g;
-          launch_conv_in(ci, e.in_ch, s);
-        } else {
-          ConvArgs c{};
-          c.in0 = cur, c.C0 = curC, c.Hin = c.Win = S;
-          c.wpk = h->packed + cv.w.w_pk, c.bias = h->params + cv.w.b;
-          c.out = z, c.stats_out = stats, c.B = n, c.Cout = C, c.g = g;
-          c.halo_px = g.spt * (g.th + 2) * (g.W + 2);
-          launch_conv_mfma(c, CONV_S1, s);
-        }
-        GnFinalizeArgs f{};
-        f.stats0 = stats, f.C0 = C, f.groups = 8;
-        f.gamma = h->params + cv.nw, f.beta = h->params + cv.nb, f.ab = ab, f.mr = mr, f.B = n, f.g = g;
-        launch_gn_finalize(f, s);
-      }
-      Kept k{z, C, S, cv.pool_after};
-      k.ab = ab, k.mr = mr;
-      kept.push_back(k);
-      curC = C;
-      if (cv.pool_after) {
-        float* pl = ws->f((size_t)n * (S / 2) * (S / 2) * C);
-        if (!dry) launch_pool2(z, ab, pl, n, S, S, C, s);
-        cur = pl;
-        S /= 2;
-      } else {
-        cur = z;  // (only the last conv: the average pool applies its norm and SiLU)
-      }
-    }
-    const Kept& last = kept.back();
-    float* pooled = ws->f((size_t)n * curC);
-    if (!dry) {
-      launch_avgpool(cur, last.pooled ? nullptr : last.ab, pooled, n, S * S, curC, s);
-      launch_linear_mfma(pooled, h->params + e.fcw, h->params + e.fcb, feat + col0, n, curC, F, curC, fstride(), s);
-    }
-  }
-
-  float* encode(const rgfm_ratio::Encoder& e, const float* img, float* feat, int col0, std::vector<Kept>& kept) {
-    const int F = h->d.feature_dim;
-    int S = e.size;
-    const float* cur = nullptr;  // input of the next conv
-    bool cur_is_z = false;       // ... is a kept pre-activation (SiLU on load) rather than a pooled map
-    int curC = e.in_ch;
-    for (size_t i = 0; i < e.convs.size(); ++i) {
-      const rgfm_ratio::Conv& cv = e.convs[i];
-      const TileGeom g = make_geom(S, S);
-      float* z = ws->f((size_t)n * S * S * cv.w.cout);
-      if (!dry) {
-        if (i == 0) {
-          ConvInArgs ci{};
-          ci.x = img, ci.w = h->params + cv.w.w_raw, ci.bias = h->params + cv.w.b;
-          ci.ep_scale = h->bn + cv.bn_scale, ci.ep_shift = h->bn + cv.bn_shift, ci.ep_nosilu = 1;
-          ci.out = z, ci.stats_out = nullptr, ci.B = n, ci.C0 = cv.w.cout, ci.g = g;
-          launch_conv_in(ci, e.in_ch, s);
-        } else {
-          ConvArgs c{};
-          c.in0 = cur, c.C0 = curC, c.Hin = c.Win = S;
-          c.ab = cur_is_z ? ab1 : nullptr;
-          c.wpk = h->packed + cv.w.w_pk, c.bias = h->params + cv.w.b;
-          c.ep_scale = h->bn + cv.bn_scale, c.ep_shift = h->bn + cv.bn_shift, c.ep_nosilu = 1;
-          c.out = z, c.stats_out = nullptr, c.B = n, c.Cout = cv.w.cout, c.g = g;
-          c.halo_px = g.spt * (g.th + 2) * (g.W + 2);
-          if (flag && g_modes.conv == CONV_ARITH_HX2 && cv.w.hx.ok) {
-            c.wpkh = h->packedh + cv.w.hx.off, c.hq = h->hq + 4 * cv.w.hx.hq, c.range_flag = flag;
-            launch_conv(c, CONV_S1, s);  // (fp16 two-plane conv with the BatchNorm epilogue; fp32 MFMA when unsupported)
-          } else {
-            launch_conv_mfma(c, CONV_S1, s);
-          }
-        }
-      }
-      kept.push_back({z, cv.w.cout, S, cv.pool_after});
-      curC = cv.w.cout;
-      if (cv.pool_after) {
-        float* pl = ws->f((size_t)n * (S / 2) * (S / 2) * curC);
-        if (!dry) launch_pool2(z, ab1, pl, n, S, S, curC, s);
-        cur = pl, cur_is_z = false;
-        S /= 2;
-      } else {
-        cur = z, cur_is_z = true;
-      }
-    }
-    float* pooled = ws->f((size_t)n * curC);
-    if (!dry) {
-      launch_avgpool(cur, cur_is_z ? ab1 : nullptr, pooled, n, S * S, curC, s);
-      launch_linear_mfma(pooled, h->params + e.fcw, h->params + e.fcb, feat + col0, n, curC, F, curC, fstride(), s);
-    }
-    return pooled;
-  }
-
-  // reverse pass of one encoder: gfeat [n][fstride()] (columns col0 .. col0+F) -> gimg NCHW
-  void encode_bwd(const rgfm_ratio::Encoder& e, const std::vector<Kept>& kept, const float* gfeat, int col0, float* gimg) {
-    const int F = h->d.feature_dim;
-    const float* zeros = h->gradw + h->g_zeros;
-    const Kept& last = kept.back();
-    float* g = ws->f((size_t)n * last.C);  // gradient of the average-pooled vector
-    if (!dry) launch_linear_mfma(gfeat + col0, h->gradw + e.fcw_t, zeros, g, n, F, last.C, fstride(), last.C, s);
-    int mode = 2;  // first step: g is [n][C] behind the global average pool
-    for (int i = (int)kept.size() - 1; i >= 0; --i) {
-      const Kept& k = kept[i];
-      const rgfm_ratio::Conv& cv = e.convs[i];
-      if (i != (int)kept.size() - 1) mode = k.pooled ? 1 : 0;
-      else mode = k.pooled ? 3 : 2;  // (SVHN encoder: a max-pool sits between the last conv and the average pool)
-      float* gz = ws->f((size_t)n * k.S * k.S * k.C);
-      unsigned* am = nullptr;
-      if (!dry) {
-        if (k.ab) {  // GroupNorm encoder: SiLU' (and the max-pool routing) at u = a z + b, then the norm's backward in place
-          launch_grad_act_gn(g, k.z, k.ab, gz, n, k.S, k.C, mode, s);
-          launch_gn_bwd(gz, k.z, h->params + cv.nw, k.mr, n, k.S * k.S, k.C, 8, s);
-        } else {
-          // (inside the sampler the next conv runs on the two-plane arithmetic: it needs the tensor's magnitude)
-          am = (flag && i > 0 && amax && g_modes.conv == CONV_ARITH_HX2 && g_modes.rev_hx2 && cv.wt_h.ok) ? amax + amax_used++ : nullptr;
-          launch_grad_act(g, k.z, h->bn + cv.bn_scale, gz, n, k.S, k.C, mode, s, am);
-        }
-      }
-      if (i == 0) {
-        if (!dry) launch_conv_bwd_img(gz, h->params + cv.w.w_raw, gimg, n, k.S, k.C, e.in_ch, s);
-      } else {
-        float* gin = ws->f((size_t)n * k.S * k.S * cv.w.cin);
-        if (!dry) {
-          ConvArgs c{};
-          c.in0 = gz, c.C0 = k.C, c.Hin = c.Win = k.S;
-          c.wpk = h->gradw + cv.wt_pk, c.bias = zeros;
-          c.out = gin, c.stats_out = nullptr, c.B = n, c.Cout = cv.w.cin;
-          c.g = make_geom(k.S, k.S);
-          c.halo_px = c.g.spt * (c.g.th + 2) * (c.g.W + 2);
-          // Inside the gradient-guided sampler (flag set): the data gradient on the two-plane fp16 arithmetic.  Gradients
-          // are far from 1 in magnitude -- typically 1e-3 ... 1e-6, below the raw staging window -- so the conv stages
-          // them x 2^-e for the tensor's measured maximum f 2^e (grad_act wrote its bits) and scales its outputs back;
-          // the staged values are then <= 16 and the x net's range flag covers the rest.  The pre-scale is a power of
-          // two, so the result scales exactly with the gradient: tests/test_gpu_grad_loop.py holds the in-loop
-          // gradient to 1e-4 of its maximum against float64 for image gradients of 6.5e-10 ... 17 in magnitude (the same
-          // relative error at every magnitude; DESIGN.md section 11).  Otherwise (stand-alone gradient, fallback modes,
-          // weights outside the fp16 window): the exact fp32 matrix-core conv.
-          bool hx = false;
-          if (am) {
-            c.wpkh = h->packedh + cv.wt_h.off, c.hq = h->hq + 4 * cv.wt_h.hq, c.range_flag = flag, c.in_amax = am;
-            hx = conv_hx2_supported(c, CONV_S1);
-          }
-          if (hx) launch_conv_hx2(c, CONV_S1, s);
-          else launch_conv_mfma(c, CONV_S1, s);
-        }
-        g = gin;
-      }
-    }
-  }
-
-  void begin() {
-    ab1 = ws->f((size_t)n * h->max_c * 2);
-    amax = ws->u(64);
-    amax_used = 0;
-    if (!dry) {
-      launch_fill_ab_identity(ab1, (size_t)n * h->max_c, s);
-      (void)hipMemsetAsync(amax, 0, 64 * sizeof(unsigned), s);
-    }
-  }
-
-  void run(const float* x, const float* y, float* gx, float* gy, float* log_ratio) {
-    const int F = h->d.feature_dim;
-    begin();
-    float* feat = ws->f((size_t)n * 2 * F);
-    std::vector<Kept> kx, ky;
-    if (h->gn_encoders()) {
-      encode_gn(h->ex, x, feat, 0, kx);
-      encode_gn(h->ey, y, feat, F, ky);
-    } else {
-      encode(h->ex, x, feat, 0, kx);
-      encode(h->ey, y, feat, F, ky);
-    }
-    std::vector<float*> us, ins{feat};
-    float* cur = feat;
-    for (const auto& dn : h->hidden) {
-      float* u = ws->f((size_t)n * dn.out);
-      float* a = ws->f((size_t)n * dn.out);
-      if (!dry) {
-        launch_linear_mfma(cur, h->params + dn.w, h->params + dn.b, u, n, dn.in, dn.out, dn.in, dn.out, s);
-        (void)hipMemcpyAsync(a, u, (size_t)n * dn.out * sizeof(float), hipMemcpyDeviceToDevice, s);
-        launch_layernorm_silu(a, h->params + dn.lw, h->params + dn.lb, n, dn.out, s);
-      }
-      us.push_back(u);
-      cur = a;
-    }
-    float* score = ws->f(n);
-    float* g = ws->f((size_t)n * h->head_in);
-    if (!dry) {
-      launch_ratio_head(cur, h->params + h->headw, h->params + h->headb, score, n, h->head_in, h->d.loss_type, 0, s);
-      launch_ratio_head_bwd(score, h->params + h->headw, g, log_ratio, n, h->head_in, h->d.loss_type, s);
-    }
-    const float* zeros = h->gradw + h->g_zeros;
-    for (int l = (int)h->hidden.size() - 1; l >= 0; --l) {
-      const auto& dn = h->hidden[l];
-      float* gu = ws->f((size_t)n * dn.out);
-      float* gi = ws->f((size_t)n * dn.in);
-      if (!dry) {
-        launch_layernorm_silu_bwd(us[l], g, h->params + dn.lw, h->params + dn.lb, gu, n, dn.out, s);
-        launch_linear_mfma(gu, h->gradw + dn.w_t, zeros, gi, n, dn.out, dn.in, dn.out, dn.in, s);
-      }
-      g = gi;
-    }
-    encode_bwd(h->ex, kx, g, 0, gx);
-    encode_bwd(h->ey, ky, g, F, gy);
-  }
-
-  // One side only (conditional sampling): d log_ratio / d target with the other side's share of the first score Linear,
-  // ctx [n][Hd] = W[:, given slice] f_given + b (RatioCondPrepare), held fixed.  Only the target's encoder runs, forward
-  // and reverse; the first hidden layer is u = ctx + W[:, target slice] f_target (cond_ln_silu_kernel), and its input
-  // gradient is taken for the target's F columns alone -- rows of the transposed weight, which are contiguous.
-  void run_cond(const float* ctx, int given, const float* target, float* g_target, float* log_ratio) {
-    const int F = h->d.feature_dim;
-    fs = F;
-    begin();
-    const rgfm_ratio::Encoder& e = given ? h->ex : h->ey;
-    const float* zeros = h->gradw + h->g_zeros;
-    float* feat = ws->f((size_t)n * F);
-    std::vector<Kept> kt;
-    if (h->gn_encoders()) encode_gn(e, target, feat, 0, kt);
-    else encode(e, target, feat, 0, kt);
-    std::vector<float*> us;
-    float* cur = nullptr;
-    for (size_t l = 0; l < h->hidden.size(); ++l) {
-      const auto& dn = h->hidden[l];
-      float* u = ws->f((size_t)n * dn.out);
-      float* a = ws->f((size_t)n * dn.out);
-      if (l == 0) {
-        float* ut = ws->f((size_t)n * dn.out);
-        if (!dry) {
-          launch_linear_mfma(feat, h->gradw + (given ? h->w1x : h->w1y), zeros, ut, n, F, dn.out, F, dn.out, s);
-          launch_cond_ln_silu(ctx, ut, h->params + dn.lw, h->params + dn.lb, u, a, n, dn.out, s);
-        }
-      } else if (!dry) {
-        launch_linear_mfma(cur, h->params + dn.w, h->params + dn.b, u, n, dn.in, dn.out, dn.in, dn.out, s);
-        (void)hipMemcpyAsync(a, u, (size_t)n * dn.out * sizeof(float), hipMemcpyDeviceToDevice, s);
-        launch_layernorm_silu(a, h->params + dn.lw, h->params + dn.lb, n, dn.out, s);
-      }
-      us.push_back(u);
-      cur = a;
-    }
-    float* score = ws->f(n);
-    float* g = ws->f((size_t)n * h->head_in);
-    if (!dry) {
-      launch_ratio_head(cur, h->params + h->headw, h->params + h->headb, score, n, h->head_in, h->d.loss_type, 0, s);
-      launch_ratio_head_bwd(score, h->params + h->headw, g, log_ratio, n, h->head_in, h->d.loss_type, s);
-    }
-    for (int l = (int)h->hidden.size() - 1; l >= 0; --l) {
-      const auto& dn = h->hidden[l];
-      const int in = l ? dn.in : F;  // layer 0: the target's columns of the concatenation only
-      const float* wt = h->gradw + dn.w_t + (l || given ? 0 : (size_t)F * dn.out);
-      float* gu = ws->f((size_t)n * dn.out);
-      float* gi = ws->f((size_t)n * in);
-      if (!dry) {
-        launch_layernorm_silu_bwd(us[l], g, h->params + dn.lw, h->params + dn.lb, gu, n, dn.out, s);
-        launch_linear_mfma(gu, wt, zeros, gi, n, dn.out, in, dn.out, in, s);
-      }
-      g = gi;
-    }
-    encode_bwd(e, kt, g, 0, g_target);
-  }
-};
-
-// ctx [n][Hd] = W[:, given slice] f_given(cond) + b of the first score Linear: the given side's encoder once (RatioRun::
-// encode, as the cross path runs it) and one linear_mfma on the contiguous column slice pack_ratio keeps.
-struct RatioCondPrepare {
-  rgfm_ratio* h;
-  int n;
-  Bump* ws;
-  hipStream_t s;
-  bool dry;
-
-  void run(const float* cond, int given, float* ctx) {
-    const int F = h->d.feature_dim;
-    const auto& d0 = h->hidden[0];
-    float* feat = ws->f((size_t)n * F);
-    RatioRun r{h, n, ws, s, dry};
-    r.encode(given ? h->ey : h->ex, cond, feat, 0, F);
-    if (dry) return;
-    ProfScope p(RGFM_KCLASS_OTHER, 0, s);
-    launch_linear_mfma(feat, h->gradw + (given ? h->w1y : h->w1x), h->params + d0.b, ctx, n, F, d0.out, F, d0.out, s);
-  }
-};
-
-size_t ratio_cond_grad_bytes(rgfm_ratio* h, int given, int n) {
-  Bump b;
-  RatioGradRun r{h, n, &b, nullptr, true};
-  r.run_cond(nullptr, given, nullptr, nullptr, nullptr);
-  return b.off;
-}
-
-size_t ratio_grad_bytes(rgfm_ratio* h, int n) {
-  Bump b;
-  RatioGradRun r{h, n, &b, nullptr, true};
-  r.run(nullptr, nullptr, nullptr, nullptr, nullptr);
-  return b.off;
-}
-
-}  // namespace
 
 extern "C" int rgfm_ratio_grad_workspace_bytes(const rgfm_ratio* h, int n, size_t* bytes) {
-  if (!h || !bytes || n < 1) return fail(RGFM_EINVAL, "bad argument");
-  *bytes = ratio_grad_bytes(const_cast<rgfm_ratio*>(h), n);
+  if (int rc = bad_unless(h && bytes && n >= 1)) return rc;
+  *bytes = ratio_bytes(h, n, [](RatioPass& p) { p.grad(nullptr, nullptr, nullptr, nullptr, nullptr); });
   return RGFM_OK;
 }
 
 extern "C" int rgfm_ratio_grad_log_ratio(rgfm_ratio* h, const float* x, const float* y, float* gx, float* gy,
                                          float* log_ratio_out, int n, void* ws, size_t ws_bytes, rgfm_stream_t stream) {
   if (!h || !x || !y || !gx || !gy || !ws) return fail(RGFM_EINVAL, "null argument");
-  size_t need = 0;
-  int rc = rgfm_ratio_grad_workspace_bytes(h, n, &need);
-  if (rc) return rc;
-  if (need > ws_bytes) return fail(RGFM_ENOMEM, "workspace too small: %zu < %zu", ws_bytes, need);
-  refresh_modes();
-  Bump b(ws, ws_bytes);
-  RatioGradRun r{h, n, &b, (hipStream_t)stream, false};
-  r.run(x, y, gx, gy, log_ratio_out);
-  HIP_TRY(hipGetLastError());
+  if (int rc = bad_unless(n >= 1)) return rc;
+  return ratio_call(h, n, ws, ws_bytes, stream, [&](RatioPass& p) { p.grad(x, y, gx, gy, log_ratio_out); });
+}
+
+// the one-sided forms (conditional sampling): the given side's context once, then the gradient for the other side
+extern "C" int rgfm_ratio_cond_prepare_workspace_bytes(const rgfm_ratio* h, int given, int n, size_t* bytes) {
+  int rc = bad_unless(h && bytes && n >= 1);
+  if (rc || (rc = check_given(given))) return rc;
+  *bytes = ratio_bytes(h, n, [&](RatioPass& p) { p.cond_prepare(nullptr, given, nullptr); });
   return RGFM_OK;
 }
 
-// the U-Net pair must be the one the estimator handle was built for
-static int check_grad_pair(const rgfm_unet* hx, const rgfm_unet* hy, const rgfm_ratio* hr) {
-  if (hr->d.kind == RGFM_RATIO_FLEXIBLE) {
-    const rgfm_ratio_flex_desc& f = hr->geom;
-    if (hx->d.in_channels != f.x_channels || hx->d.img_size != f.x_size || hy->d.in_channels != f.y_channels ||
-        hy->d.img_size != f.y_size)
-      return fail(RGFM_EINVAL, "gradient guidance: the FlexibleRatioEstimator handle is built for %dx%dx%d + %dx%dx%d, the U-Nets are %dx%dx%d + %dx%dx%d",
-                  f.x_channels, f.x_size, f.x_size, f.y_channels, f.y_size, f.y_size, hx->d.in_channels, hx->d.img_size,
-                  hx->d.img_size, hy->d.in_channels, hy->d.img_size, hy->d.img_size);
-  } else if (hr->d.kind == RGFM_RATIO_MNIST_SVHN) {
-    if (hx->d.in_channels != 1 || hx->d.img_size != 32 || hy->d.in_channels != 3 || hy->d.img_size != 32)
-      return fail(RGFM_EINVAL, "gradient guidance with RatioEstimatorMNISTSVHN needs the 1x32x32 + 3x32x32 pair");
-  } else if (hx->d.in_channels != 1 || hx->d.img_size != 28 || hy->d.in_channels != 1 || hy->d.img_size != 28) {
-    return fail(RGFM_EINVAL, "gradient guidance with RatioEstimator needs the 1x28x28 + 1x28x28 pair");
-  }
+extern "C" int rgfm_ratio_cond_prepare(rgfm_ratio* h, const float* cond, int given, int n, float* ctx_out, void* ws,
+                                       size_t ws_bytes, rgfm_stream_t stream) {
+  if (!h || !cond || !ctx_out || !ws) return fail(RGFM_EINVAL, "null argument");
+  int rc = bad_unless(n >= 1);
+  if (rc || (rc = check_given(given))) return rc;
+  return ratio_call(h, n, ws, ws_bytes, stream, [&](RatioPass& p) { p.cond_prepare(cond, given, ctx_out); });
+}
+
+extern "C" int rgfm_ratio_grad_cond_workspace_bytes(const rgfm_ratio* h, int given, int n, size_t* bytes) {
+  int rc = bad_unless(h && bytes && n >= 1);
+  if (rc || (rc = check_given(given))) return rc;
+  *bytes = ratio_bytes(h, n, [&](RatioPass& p) { p.grad_cond(nullptr, given, nullptr, nullptr, nullptr); });
   return RGFM_OK;
 }
+
+extern "C" int rgfm_ratio_grad_log_ratio_cond(rgfm_ratio* h, const float* ctx, int given, const float* target, float* g_target,
+                                              float* log_ratio_out, int n, void* ws, size_t ws_bytes, rgfm_stream_t stream) {
+  if (!h || !ctx || !target || !g_target || !ws) return fail(RGFM_EINVAL, "null argument");
+  int rc = bad_unless(n >= 1);
+  if (rc || (rc = check_given(given))) return rc;
+  return ratio_call(h, n, ws, ws_bytes, stream, [&](RatioPass& p) { p.grad_cond(ctx, given, target, g_target, log_ratio_out); });
+}
+
+namespace {
+
+// (channels, size) of the estimator's x (side 0) or y (side 1) images
+void ratio_side_shape(const rgfm_ratio* hr, int side, int* c, int* sz) {
+  if (hr->d.kind == RGFM_RATIO_FLEXIBLE) *c = side ? hr->geom.y_channels : hr->geom.x_channels, *sz = side ? hr->geom.y_size : hr->geom.x_size;
+  else if (hr->d.kind == RGFM_RATIO_MNIST_SVHN) *c = side ? 3 : 1, *sz = 32;
+  else *c = 1, *sz = 28;
+}
+bool is_side(const rgfm_unet* hu, const rgfm_ratio* hr, int side, int* c, int* sz) {
+  ratio_side_shape(hr, side, c, sz);
+  return hu->d.in_channels == *c && hu->d.img_size == *sz;
+}
+
+// the U-Net pair must be the one the estimator handle was built for
+int check_grad_pair(const rgfm_unet* hx, const rgfm_unet* hy, const rgfm_ratio* hr) {
+  int cx = 0, sx = 0, cy = 0, sy = 0;
+  const bool okx = is_side(hx, hr, 0, &cx, &sx), oky = is_side(hy, hr, 1, &cy, &sy);
+  if (okx && oky) return RGFM_OK;
+  return fail(RGFM_EINVAL, "gradient guidance: the estimator handle is built for %dx%dx%d + %dx%dx%d, the U-Nets are %dx%dx%d + %dx%dx%d",
+              cx, sx, sx, cy, sy, sy, hx->d.in_channels, hx->d.img_size, hx->d.img_size, hy->d.in_channels, hy->d.img_size, hy->d.img_size);
+}
+
+// ... and for one side: the target U-Net must be the estimator's shape for the side that is NOT given
+int check_grad_side(const rgfm_unet* hu, const rgfm_ratio* hr, int given) {
+  int c = 0, sz = 0;
+  if (is_side(hu, hr, given ? 0 : 1, &c, &sz)) return RGFM_OK;
+  return fail(RGFM_EINVAL, "conditional gradient guidance: given the estimator's %s, its %s is %dx%dx%d; the target U-Net is %dx%dx%d",
+              given ? "y" : "x", given ? "x" : "y", c, sz, sz, hu->d.in_channels, hu->d.img_size, hu->d.img_size);
+}
+
+}  // namespace
 
 // Paired loop with gradient log-ratio guidance (reference README.md:159-164: v_guided = v_ind + gamma *
 // grad log r(x_t, y_t); the reference ships no code for it): x <- x + (v_x + gamma dlogr/dx) dt, every Euler step.
@@ -851,8 +739,7 @@ void carve_pair_grad(Bump& b, PairGradWs& w, rgfm_ratio* hr) {
   w.gy = b.f((size_t)batch * w.cy.image_floats());
   w.cx.carve_eval(), w.cy.carve_eval();
   w.mark_r = b.off;
-  RatioGradRun r{hr, batch, &b, nullptr, true};
-  r.run(nullptr, nullptr, nullptr, nullptr, nullptr);
+  RatioPass{hr, batch, &b, nullptr, true}.grad(nullptr, nullptr, nullptr, nullptr, nullptr);
 }
 
 int pair_grad_bytes(const rgfm_unet* hx, const rgfm_unet* hy, const rgfm_ratio* hr, int batch, int solver, size_t* bytes) {
@@ -902,10 +789,9 @@ int pair_grad_loop(rgfm_unet* hx, rgfm_unet* hy, rgfm_ratio* hr, float* x_inout,
     if (int rc = w.cx.eval(g.row, s, xin, w.vx, nullptr, nullptr, 0.f)) return rc;
     {
       b.off = w.mark_r;
-      RatioGradRun r{hr, batch, &b, s, false};
-      r.flag = hx->range_flag;
+      RatioPass r{hr, batch, &b, s, false, hx->range_flag};
       ModeScope ratio_mode(hx->conv_mode);  // (the estimator's forward convs follow the x net's handle)
-      r.run(xin, yin, w.gx, w.gy, nullptr);
+      r.grad(xin, yin, w.gx, w.gy, nullptr);
     }
     if (overlap) HIP_TRY(hipStreamWaitEvent(s, ds->join, 0));
     launch_euler_grad(xout, w.vx, w.gx, (size_t)batch * dx, gf, g.dts, s, xb);
@@ -944,77 +830,6 @@ extern "C" int rgfm_sample_pair_grad_ode(rgfm_unet* hx, rgfm_unet* hy, rgfm_rati
   return pair_grad_loop(hx, hy, hr, x_inout, y_inout, batch, num_steps, gamma, step_begin, step_end, solver, ws, ws_bytes, stream);
 }
 
-// ------------------------------------------------------------------ one-sided gradient: conditional sampling
-namespace {
-
-// (channels, size) of the estimator's x (side 0) or y (side 1) images
-void ratio_side_shape(const rgfm_ratio* hr, int side, int* c, int* sz) {
-  if (hr->d.kind == RGFM_RATIO_FLEXIBLE) *c = side ? hr->geom.y_channels : hr->geom.x_channels, *sz = side ? hr->geom.y_size : hr->geom.x_size;
-  else if (hr->d.kind == RGFM_RATIO_MNIST_SVHN) *c = side ? 3 : 1, *sz = 32;
-  else *c = 1, *sz = 28;
-}
-
-// check_grad_pair for one side: the target U-Net must be the estimator's shape for the side that is NOT given
-int check_grad_side(const rgfm_unet* hu, const rgfm_ratio* hr, int given) {
-  int c = 0, sz = 0;
-  ratio_side_shape(hr, given ? 0 : 1, &c, &sz);
-  if (hu->d.in_channels != c || hu->d.img_size != sz)
-    return fail(RGFM_EINVAL, "conditional gradient guidance: given the estimator's %s, its %s is %dx%dx%d; the target U-Net is %dx%dx%d",
-                given ? "y" : "x", given ? "x" : "y", c, sz, sz, hu->d.in_channels, hu->d.img_size, hu->d.img_size);
-  return RGFM_OK;
-}
-
-int check_given(int given) { return given == 0 || given == 1 ? RGFM_OK : fail(RGFM_EINVAL, "given must be 0 (the condition is x) or 1 (y)"); }
-
-}  // namespace
-
-extern "C" int rgfm_ratio_cond_prepare_workspace_bytes(const rgfm_ratio* h, int given, int n, size_t* bytes) {
-  if (!h || !bytes || n < 1) return fail(RGFM_EINVAL, "bad argument");
-  if (int rc = check_given(given)) return rc;
-  Bump b;
-  RatioCondPrepare r{const_cast<rgfm_ratio*>(h), n, &b, nullptr, true};
-  r.run(nullptr, given, nullptr);
-  *bytes = b.off;
-  return RGFM_OK;
-}
-
-extern "C" int rgfm_ratio_cond_prepare(rgfm_ratio* h, const float* cond, int given, int n, float* ctx_out, void* ws,
-                                       size_t ws_bytes, rgfm_stream_t stream) {
-  refresh_modes();
-  if (!h || !cond || !ctx_out || !ws) return fail(RGFM_EINVAL, "null argument");
-  size_t need = 0;
-  int rc = rgfm_ratio_cond_prepare_workspace_bytes(h, given, n, &need);
-  if (rc) return rc;
-  if (need > ws_bytes) return fail(RGFM_ENOMEM, "workspace too small: %zu < %zu", ws_bytes, need);
-  Bump b(ws, ws_bytes);
-  RatioCondPrepare r{h, n, &b, (hipStream_t)stream, false};
-  r.run(cond, given, ctx_out);
-  HIP_TRY(hipGetLastError());
-  return RGFM_OK;
-}
-
-extern "C" int rgfm_ratio_grad_cond_workspace_bytes(const rgfm_ratio* h, int given, int n, size_t* bytes) {
-  if (!h || !bytes || n < 1) return fail(RGFM_EINVAL, "bad argument");
-  if (int rc = check_given(given)) return rc;
-  *bytes = ratio_cond_grad_bytes(const_cast<rgfm_ratio*>(h), given, n);
-  return RGFM_OK;
-}
-
-extern "C" int rgfm_ratio_grad_log_ratio_cond(rgfm_ratio* h, const float* ctx, int given, const float* target, float* g_target,
-                                              float* log_ratio_out, int n, void* ws, size_t ws_bytes, rgfm_stream_t stream) {
-  if (!h || !ctx || !target || !g_target || !ws) return fail(RGFM_EINVAL, "null argument");
-  size_t need = 0;
-  int rc = rgfm_ratio_grad_cond_workspace_bytes(h, given, n, &need);
-  if (rc) return rc;
-  if (need > ws_bytes) return fail(RGFM_ENOMEM, "workspace too small: %zu < %zu", ws_bytes, need);
-  refresh_modes();
-  Bump b(ws, ws_bytes);
-  RatioGradRun r{h, n, &b, (hipStream_t)stream, false};
-  r.run_cond(ctx, given, target, g_target, log_ratio_out);
-  HIP_TRY(hipGetLastError());
-  return RGFM_OK;
-}
-
 // One net with gradient log-ratio guidance, the other side observed: s <- s + (v(s, t) + gamma dlogr/ds) dt, every step
 // (midpoint: s_mid = s + (dt / 2) F(s, t1), s += dt F(s_mid, t1 + dt / 2)).
 // The velocity net and the estimator's one-sided pass run one after the other on `stream` and share one scratch region.
@@ -1033,8 +848,7 @@ CondGradWs carve_cond_grad(Bump& b, rgfm_unet* h, rgfm_ratio* hr, int given, int
   w.c.carve_eval();
   const size_t net_end = b.off;
   b.off = w.c.mark;
-  RatioGradRun r{hr, batch, &b, nullptr, true};
-  r.run_cond(nullptr, given, nullptr, nullptr, nullptr);
+  RatioPass{hr, batch, &b, nullptr, true}.grad_cond(nullptr, given, nullptr, nullptr, nullptr);
   b.off = std::max(b.off, net_end);
   return w;
 }
@@ -1076,10 +890,9 @@ int cond_grad_loop(rgfm_unet* h, rgfm_ratio* hr, float* s_inout, const float* ct
       if ((rc = w.c.eval(g.row, s, in, w.v, nullptr, nullptr, 0.f))) return rc;
       {
         b.off = w.c.mark;
-        RatioGradRun r{hr, batch, &b, s, false};
-        r.flag = h->range_flag;
+        RatioPass r{hr, batch, &b, s, false, h->range_flag};
         ModeScope ratio_mode(h->conv_mode);  // (the estimator's convs follow the target net's handle)
-        r.run_cond(ctx, given, in, w.g, nullptr);
+        r.grad_cond(ctx, given, in, w.g, nullptr);
       }
       launch_euler_grad(out, w.v, w.g, (size_t)batch * d, gf, g.dts, s, g.writes_mid ? s_inout : nullptr);
     }
