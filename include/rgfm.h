@@ -634,6 +634,78 @@ int rgfm_guidance_apply_cond(const float* s, float* v, const float* mc_set, cons
                              size_t ws_bytes, rgfm_stream_t stream);
 
 /* ------------------------------------------------------------------------
+ * Guidance diagnostics (opt-in).  Added functions only: the ABI version is unchanged.
+ *
+ * One record of RGFM_DIAG_FLOATS fp32 values per (stage, sample), written on the device, stage-major
+ * [n_stages][batch][RGFM_DIAG_FLOATS]; n_stages = step_end - step_begin for RGFM_SOLVER_EULER and twice that for
+ * RGFM_SOLVER_MIDPOINT (stage 1 then stage 2 of each step).  What the reference prints once per run
+ * (src/utils/flow_utils.py:349-363), as per-sample curves:
+ *   RGFM_DIAG_ESS      MC guidance: (sum_i w_i)^2 / sum_i w_i^2 of the row's normalised importance weights, 1 .. n_mc;
+ *                      0 marks "this stage was not MC-guided" (t <= 1e-3, n_mc = 0, or a gradient-guided loop)
+ *   RGFM_DIAG_W_MAX / RGFM_DIAG_W_MIN    max_i w_i, min_i w_i of the row
+ *   RGFM_DIAG_Z_BAR    the row's Z_bar = mean_i r_i p_i + 1e-10 (reference :315)
+ *   RGFM_DIAG_V_NORM_X / _Y    L2 norm of the net's velocity at the stage, before any blend
+ *   RGFM_DIAG_G_NORM_X / _Y    MC guidance: L2 norm of the pure guided velocity g = sum_i w_i (m_i - x) / (1 - t + eps)
+ *                      (reference :340-341); gradient guidance: L2 norm of d log r / dx, d log r / dy, before gamma
+ * One-sided loops and blocks leave the _Y entries 0.  A stage that runs unguided is an all-zero record.
+ * Gradient-guided loops fill the four norms and leave the first four entries 0.
+ *
+ * Block level: the inputs of the guidance block's parity hooks without gamma; v is read, nothing but diag_out
+ * [batch][RGFM_DIAG_FLOATS] and the workspace is written.
+ * Loop level: each *_diag loop is its *_ode namesake (the FlowMatchingModel pair: its Euler entry point) with
+ * `float* diag_out, size_t diag_records` in front of `ws`; the state it computes has the bits of that entry point.
+ * diag_out null with diag_records 0: exactly the existing entry point.  Otherwise both must be given and diag_records
+ * (a capacity, in records) must be at least n_stages * batch: RGFM_EINVAL before anything is enqueued.  No host
+ * synchronisation is added; the records are complete when the stream reaches the end of the call.  With diagnostics on
+ * the paired MC loop runs kernel by kernel (no hipGraph replay: same kernels, same arguments, same bits) and each
+ * guided stage adds the weight statistics (one launch), a row norm per velocity and modality (four launches, two in a
+ * one-sided loop) and one more pass of the guided-velocity GEMM into a scratch velocity; the workspace grows by that
+ * scratch (the *_diag_workspace_bytes queries).  The gradient-guided loops add the row norms only and need no scratch.
+ * ---------------------------------------------------------------------- */
+#define RGFM_DIAG_FLOATS 8
+#define RGFM_DIAG_ESS 0
+#define RGFM_DIAG_W_MAX 1
+#define RGFM_DIAG_W_MIN 2
+#define RGFM_DIAG_Z_BAR 3
+#define RGFM_DIAG_V_NORM_X 4
+#define RGFM_DIAG_V_NORM_Y 5
+#define RGFM_DIAG_G_NORM_X 6
+#define RGFM_DIAG_G_NORM_Y 7
+int rgfm_guidance_diag_workspace_bytes(int batch, int n_mc, int dim_x, int dim_y, size_t* bytes);
+int rgfm_guidance_diag(const float* x, const float* y, const float* vx, const float* vy, const float* mc_x1,
+                       const float* mc_y1, const float* mc_ratios, int batch, int n_mc, int dim_x, int dim_y, double t,
+                       float* diag_out, void* ws, size_t ws_bytes, rgfm_stream_t stream);
+/* (the one-sided block: dim_y = 0 in the workspace query) */
+int rgfm_guidance_diag_cond(const float* s, const float* v, const float* mc_set, const float* ratios, int batch, int n_mc,
+                            int dim, double t, float* diag_out, void* ws, size_t ws_bytes, rgfm_stream_t stream);
+int rgfm_sample_pair_diag_workspace_bytes(const rgfm_unet* hx, const rgfm_unet* hy, int batch, int n_mc, int solver,
+                                          size_t* bytes);
+int rgfm_sample_pair_diag(rgfm_unet* hx, rgfm_unet* hy, float* x_inout, float* y_inout, const float* mc_x1,
+                          const float* mc_y1, const float* mc_ratios, int n_mc, int batch, int num_steps, double gamma,
+                          int step_begin, int step_end, int solver, float* diag_out, size_t diag_records, void* ws,
+                          size_t ws_bytes, rgfm_stream_t stream);
+int rgfm_sample_cond_diag_workspace_bytes(const rgfm_unet* h, int batch, int n_mc, int solver, size_t* bytes);
+int rgfm_sample_cond_diag(rgfm_unet* h, float* s_inout, const float* mc_set, const float* ratios, int n_mc, int batch,
+                          int num_steps, double gamma, int step_begin, int step_end, int solver, float* diag_out,
+                          size_t diag_records, void* ws, size_t ws_bytes, rgfm_stream_t stream);
+int rgfm_sample_pair_grad_diag_workspace_bytes(const rgfm_unet* hx, const rgfm_unet* hy, const rgfm_ratio* hr,
+                                               int batch, int solver, size_t* bytes);
+int rgfm_sample_pair_grad_diag(rgfm_unet* hx, rgfm_unet* hy, rgfm_ratio* hr, float* x_inout, float* y_inout,
+                               int batch, int num_steps, double gamma, int step_begin, int step_end, int solver,
+                               float* diag_out, size_t diag_records, void* ws, size_t ws_bytes, rgfm_stream_t stream);
+int rgfm_sample_cond_grad_diag_workspace_bytes(const rgfm_unet* h_unet, const rgfm_ratio* h_ratio, int given,
+                                               int batch, int solver, size_t* bytes);
+int rgfm_sample_cond_grad_diag(rgfm_unet* h_unet, rgfm_ratio* h_ratio, float* s_inout, const float* ctx, int given,
+                               int batch, int num_steps, double gamma, int step_begin, int step_end, int solver,
+                               float* diag_out, size_t diag_records, void* ws, size_t ws_bytes, rgfm_stream_t stream);
+int rgfm_fmnet_sample_pair_diag_workspace_bytes(const rgfm_fmnet* hx, const rgfm_fmnet* hy, int batch, int n_mc,
+                                                size_t* bytes);
+int rgfm_fmnet_sample_pair_diag(rgfm_fmnet* hx, rgfm_fmnet* hy, float* x_inout, float* y_inout, const float* mc_x1,
+                                const float* mc_y1, const float* mc_ratios, int n_mc, int batch, int num_steps,
+                                double gamma, int step_begin, int step_end, float* diag_out, size_t diag_records,
+                                void* ws, size_t ws_bytes, rgfm_stream_t stream);
+
+/* ------------------------------------------------------------------------
  * Bench support: per-kernel-class device time measured with hipEvents on the
  * launch stream (bench.py's roofline line).  Timing is off by default.
  * ---------------------------------------------------------------------- */

@@ -1010,16 +1010,32 @@ def _solver(solver, *models):
     return sid
 
 
-def _run_loop(fn, ws_fn, ws_args, args, steps, sid, dev, ws=None):
+def _diag_fn(name):
+    """The *_diag twin of a guided loop's entry point or workspace query (rgfm_sample_pair_ode -> rgfm_sample_pair_diag)."""
+    tail = "_workspace_bytes" if name.endswith("_workspace_bytes") else ""
+    stem = name[:len(name) - len(tail)]
+    return (stem[:-4] if stem.endswith("_ode") else stem) + "_diag" + tail
+
+
+def _run_loop(fn, ws_fn, ws_args, args, steps, sid, dev, ws=None, diag=None):
     """One native sampler loop: the size query `ws_fn`(*ws_args[, sid]), the workspace (`ws`: a _Workspace; default the
     samplers' shared one), then `fn`(*args, *steps[, sid], workspace, stream).  `steps`: (step_begin, step_end).  sid
-    None: entry points without a solver argument (the FlowMatchingModel loops)."""
+    None: entry points without a solver argument (the FlowMatchingModel loops).  `diag`: a records tensor
+    [n_stages, B, RGFM_DIAG_FLOATS] -- the loop's *_diag twin runs and fills it (guided loops only)."""
     L = _lib.lib()
     tail = () if sid is None else (sid,)
+    sink = ()
+    if diag is not None:
+        if not (diag.is_cuda and diag.dtype == torch.float32 and diag.is_contiguous() and diag.dim() == 3
+                and diag.shape[2] == _lib.DIAG_FLOATS):
+            raise _lib.RgfmError(f"diagnostics records: a contiguous fp32 device tensor [n_stages, B, {_lib.DIAG_FLOATS}] "
+                                 f"expected, got {tuple(diag.shape)} {diag.dtype} on {diag.device}")
+        fn, ws_fn = _diag_fn(fn), _diag_fn(ws_fn)
+        sink = (_ptr(diag), diag.shape[0] * diag.shape[1])
     nb = ctypes.c_size_t()
     _lib.check(getattr(L, ws_fn)(*ws_args, *tail, ctypes.byref(nb)))
     buf = (ws or _sampler_ws).get(nb.value, dev)
-    _lib.check(getattr(L, fn)(*args, int(steps[0]), int(steps[1]), *tail, _ptr(buf), nb.value, _stream(dev)))
+    _lib.check(getattr(L, fn)(*args, int(steps[0]), int(steps[1]), *tail, *sink, _ptr(buf), nb.value, _stream(dev)))
 
 
 def _solver_arg(engine, sid):
@@ -1108,8 +1124,10 @@ def sample_two_streams(fm_x, x, fm_y, y, num_steps, solver='euler'):
 
 
 def sample_pair(fm_x, fm_y, x, y, mc_x1, mc_y1, mc_ratios, num_steps, gamma, step_begin=0,
-                step_end=None, solver='euler'):
-    """In-place paired loop with optional MC guidance (rgfm_sample_pair; solver='midpoint': rgfm_sample_pair_ode)."""
+                step_end=None, solver='euler', diag=None):
+    """In-place paired loop with optional MC guidance (rgfm_sample_pair; solver='midpoint': rgfm_sample_pair_ode).
+    `diag`: a records tensor [n_stages, B, 8] to fill (rgfm_sample_pair_diag / rgfm_fmnet_sample_pair_diag; the state
+    keeps its bits); the other guided loops below take it the same way."""
     sid = _solver(solver, fm_x, fm_y)
     for m in (fm_x, fm_y):
         m._engine._check_eval(m)
@@ -1135,12 +1153,13 @@ def sample_pair(fm_x, fm_y, x, y, mc_x1, mc_y1, mc_ratios, num_steps, gamma, ste
             _run_loop(ex.PAIR, ex.PAIR_WS, (hx, hy, B, n_mc),
                       (hx, hy, _ptr(x), _ptr(y), _ptr(mc_x1 if n_mc else None), _ptr(mc_y1 if n_mc else None),
                        _ptr(mc_ratios if n_mc else None), n_mc, B, int(num_steps), float(gamma)),
-                      (step_begin, step_end), _solver_arg(ex, sid), dev)
+                      (step_begin, step_end), _solver_arg(ex, sid), dev, diag=diag)
         return x, y
     return _range_guarded(dev, [x, y], run, [fm_x._engine, fm_y._engine])
 
 
-def sample_pair_grad(fm_x, fm_y, ratio_estimator, x, y, num_steps, gamma, step_begin=0, step_end=None, solver='euler'):
+def sample_pair_grad(fm_x, fm_y, ratio_estimator, x, y, num_steps, gamma, step_begin=0, step_end=None, solver='euler',
+                     diag=None):
     """In-place paired loop with gradient log-ratio guidance (rgfm_sample_pair_grad; solver='midpoint':
     rgfm_sample_pair_grad_ode)."""
     sid = _lib.solver_id(solver)
@@ -1162,7 +1181,8 @@ def sample_pair_grad(fm_x, fm_y, ratio_estimator, x, y, num_steps, gamma, step_b
         with torch.cuda.device(dev):
             hx, hy, hr = fm_x._engine.handle(dev), fm_y._engine.handle(dev), ratio_estimator._engine.handle(dev)
             _run_loop("rgfm_sample_pair_grad_ode", "rgfm_sample_pair_grad_ode_workspace_bytes", (hx, hy, hr, B),
-                      (hx, hy, hr, _ptr(x), _ptr(y), B, int(num_steps), float(gamma)), (step_begin, step_end), sid, dev)
+                      (hx, hy, hr, _ptr(x), _ptr(y), B, int(num_steps), float(gamma)), (step_begin, step_end), sid, dev,
+                      diag=diag)
         return x, y
     return _range_guarded(dev, [x, y], run, [fm_x._engine, fm_y._engine])
 
@@ -1185,7 +1205,43 @@ def guidance_apply(x, y, vx, vy, mc_x1, mc_y1, mc_ratios, t, gamma, want_weights
     return w
 
 
-def sample_cond(model, s, mc_set, ratios, num_steps, gamma, step_begin=0, step_end=None, solver='euler'):
+def guidance_diag(x, y, vx, vy, mc_x1, mc_y1, mc_ratios, t):
+    """Diagnostics of one evaluation of the paired guidance block (rgfm_guidance_diag): records [B, 8]
+    (utils.diagnostics.FIELDS); nothing else is written."""
+    _require_hip(x, y, vx, vy, mc_x1, mc_y1, mc_ratios)
+    B, N, dev = x.shape[0], mc_x1.shape[0], x.device
+    dx, dy = x[0].numel(), y[0].numel()
+    out = torch.empty(B, _lib.DIAG_FLOATS, device=dev)
+    L = _lib.lib()
+    with torch.cuda.device(dev):
+        nb = ctypes.c_size_t()
+        _lib.check(L.rgfm_guidance_diag_workspace_bytes(B, N, dx, dy, ctypes.byref(nb)))
+        ws = _sampler_ws.get(nb.value, dev)
+        _lib.check(L.rgfm_guidance_diag(_ptr(x.contiguous()), _ptr(y.contiguous()), _ptr(vx.contiguous()),
+                                        _ptr(vy.contiguous()), _ptr(mc_x1.contiguous()), _ptr(mc_y1.contiguous()),
+                                        _ptr(mc_ratios.contiguous()), B, N, dx, dy, float(t), _ptr(out), _ptr(ws),
+                                        nb.value, _stream(dev)))
+    return out
+
+
+def guidance_diag_cond(s, v, mc_set, ratios, t):
+    """Diagnostics of one evaluation of the one-sided guidance block (rgfm_guidance_diag_cond): records [B, 8], the _y
+    fields 0."""
+    _require_hip(s, v, mc_set, ratios)
+    B, N, dev = s.shape[0], mc_set.shape[0], s.device
+    out = torch.empty(B, _lib.DIAG_FLOATS, device=dev)
+    L = _lib.lib()
+    with torch.cuda.device(dev):
+        nb = ctypes.c_size_t()
+        _lib.check(L.rgfm_guidance_diag_workspace_bytes(B, N, s[0].numel(), 0, ctypes.byref(nb)))
+        ws = _sampler_ws.get(nb.value, dev)
+        _lib.check(L.rgfm_guidance_diag_cond(_ptr(s.contiguous()), _ptr(v.contiguous()), _ptr(mc_set.contiguous()),
+                                             _ptr(ratios.contiguous()), B, N, s[0].numel(), float(t), _ptr(out), _ptr(ws),
+                                             nb.value, _stream(dev)))
+    return out
+
+
+def sample_cond(model, s, mc_set, ratios, num_steps, gamma, step_begin=0, step_end=None, solver='euler', diag=None):
     """In-place loop of one U-Net with one-sided MC guidance (rgfm_sample_cond; solver='midpoint':
     rgfm_sample_cond_ode): s [B, C, H, W], mc_set [N, C, H, W], ratios [B, N]."""
     sid = _lib.solver_id(solver)
@@ -1213,12 +1269,13 @@ def sample_cond(model, s, mc_set, ratios, num_steps, gamma, step_begin=0, step_e
             h = eng.handle(dev)
             _run_loop("rgfm_sample_cond_ode", "rgfm_sample_cond_ode_workspace_bytes", (h, B, N),
                       (h, _ptr(s), _ptr(mc_set), _ptr(ratios), N, B, int(num_steps), float(gamma)),
-                      (step_begin, step_end), sid, dev)
+                      (step_begin, step_end), sid, dev, diag=diag)
         return s
     return _range_guarded(dev, [s], run, [eng])
 
 
-def sample_cond_grad(model, ratio_estimator, s, ctx, given, num_steps, gamma, step_begin=0, step_end=None, solver='euler'):
+def sample_cond_grad(model, ratio_estimator, s, ctx, given, num_steps, gamma, step_begin=0, step_end=None, solver='euler',
+                     diag=None):
     """In-place loop of one U-Net with one-sided gradient log-ratio guidance (rgfm_sample_cond_grad; solver='midpoint':
     rgfm_sample_cond_grad_ode): s [B, C, H, W], ctx [B, hidden_dim] from ratio_estimator._engine.cond_prepare(condition,
     given)."""
@@ -1250,7 +1307,8 @@ def sample_cond_grad(model, ratio_estimator, s, ctx, given, num_steps, gamma, st
         with torch.cuda.device(dev):
             h, hr = eng.handle(dev), re.handle(dev)
             _run_loop("rgfm_sample_cond_grad_ode", "rgfm_sample_cond_grad_ode_workspace_bytes", (h, hr, gi, B),
-                      (h, hr, _ptr(s), _ptr(ctx), gi, B, int(num_steps), float(gamma)), (step_begin, step_end), sid, dev)
+                      (h, hr, _ptr(s), _ptr(ctx), gi, B, int(num_steps), float(gamma)), (step_begin, step_end), sid, dev,
+                      diag=diag)
         return s
     return _range_guarded(dev, [s], run, [eng])
 

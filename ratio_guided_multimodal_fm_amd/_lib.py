@@ -150,6 +150,30 @@ SIGNATURES = {
     "rgfm_guidance_apply": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
                                     c_void_p, c_int, c_int, c_int, c_int, c_double, c_double,
                                     c_void_p, c_void_p, c_size_t, c_void_p]),
+    # guidance diagnostics: the block's inputs without gamma + diag_out; the *_ode loops (the FlowMatchingModel pair: its
+    # Euler loop) with (diag_out, diag_records) in front of ws
+    "rgfm_guidance_diag_workspace_bytes": (c_int, [c_int, c_int, c_int, c_int, P(c_size_t)]),
+    "rgfm_guidance_diag": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int,
+                                   c_int, c_int, c_double, c_void_p, c_void_p, c_size_t, c_void_p]),
+    "rgfm_guidance_diag_cond": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_double, c_void_p,
+                                        c_void_p, c_size_t, c_void_p]),
+    "rgfm_sample_pair_diag_workspace_bytes": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, P(c_size_t)]),
+    "rgfm_sample_pair_diag": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int,
+                                      c_int, c_double, c_int, c_int, c_int, c_void_p, c_size_t, c_void_p, c_size_t,
+                                      c_void_p]),
+    "rgfm_sample_cond_diag_workspace_bytes": (c_int, [c_void_p, c_int, c_int, c_int, P(c_size_t)]),
+    "rgfm_sample_cond_diag": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_double, c_int, c_int,
+                                      c_int, c_void_p, c_size_t, c_void_p, c_size_t, c_void_p]),
+    "rgfm_sample_pair_grad_diag_workspace_bytes": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_int, P(c_size_t)]),
+    "rgfm_sample_pair_grad_diag": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_double,
+                                           c_int, c_int, c_int, c_void_p, c_size_t, c_void_p, c_size_t, c_void_p]),
+    "rgfm_sample_cond_grad_diag_workspace_bytes": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, P(c_size_t)]),
+    "rgfm_sample_cond_grad_diag": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_double, c_int,
+                                           c_int, c_int, c_void_p, c_size_t, c_void_p, c_size_t, c_void_p]),
+    "rgfm_fmnet_sample_pair_diag_workspace_bytes": (c_int, [c_void_p, c_void_p, c_int, c_int, P(c_size_t)]),
+    "rgfm_fmnet_sample_pair_diag": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int,
+                                            c_int, c_int, c_double, c_int, c_int, c_void_p, c_size_t, c_void_p, c_size_t,
+                                            c_void_p]),
     "rgfm_profile_enable": (c_int, [c_int]),
     "rgfm_profile_reset": (c_int, []),
     "rgfm_profile_read": (c_int, [c_int, P(c_double), P(c_double), P(c_int64), P(c_double)]),
@@ -182,6 +206,9 @@ SIGNATURES = {
     "rgfm_last_error": (ctypes.c_char_p, []),
 }
 
+
+# RGFM_DIAG_FLOATS of include/rgfm.h: fp32 values of one guidance-diagnostics record (utils/diagnostics.py names them)
+DIAG_FLOATS = 8
 
 # RGFM_SOLVER_* of include/rgfm.h by the name the Python samplers and the CLIs take
 SOLVERS = {"euler": 0, "midpoint": 1}

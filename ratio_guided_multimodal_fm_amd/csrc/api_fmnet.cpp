@@ -362,22 +362,28 @@ extern "C" int rgfm_fmnet_sample_pair_workspace_bytes(const rgfm_fmnet* hx, cons
   return RGFM_OK;
 }
 
-extern "C" int rgfm_fmnet_sample_pair(rgfm_fmnet* hx, rgfm_fmnet* hy, float* x_inout, float* y_inout,
-                                      const float* mc_x1, const float* mc_y1, const float* mc_ratios, int n_mc,
-                                      int batch, int num_steps, double gamma, int step_begin, int step_end, void* ws,
-                                      size_t ws_bytes, rgfm_stream_t stream) {
+namespace {
+int fm_pair_loop(rgfm_fmnet* hx, rgfm_fmnet* hy, float* x_inout, float* y_inout, const float* mc_x1, const float* mc_y1,
+                 const float* mc_ratios, int n_mc, int batch, int num_steps, double gamma, int step_begin, int step_end,
+                 void* ws, size_t ws_bytes, rgfm_stream_t stream, float* diag_out, size_t diag_records) {
   refresh_modes();
   int ns = 0;
   if (int rc = check_loop(SOLVER_EULER, hx && hy && x_inout && y_inout && ws, batch, num_steps, step_begin, step_end, &ns,
                           false))
     return rc;
   if (n_mc < 0 || (n_mc > 0 && (!mc_x1 || !mc_y1 || !mc_ratios))) return fail(RGFM_EINVAL, "MC set missing");
+  DiagSink sink;
+  if (int rc = sink.check(diag_out, diag_records, batch, ns, SOLVER_EULER)) return rc;
+  const int d = FM_S * FM_S;
   Bump b(ws, ws_bytes);
   FmPairWs w = fm_carve_pair(b, hx, hy, batch, n_mc);
+  // (the nets' evaluations rewind the Bump to their marks: the sink's scratch lies behind every region)
+  if (sink.on()) sink.carve(b, d, d);
   if (int rc = check_workspace(b, ws_bytes)) return rc;
   if (ns == 0) return RGFM_OK;
   hipStream_t s = (hipStream_t)stream;
-  const int d = FM_S * FM_S;
+  if (sink.on())
+    if (int rc = sink.begin(s, d, d)) return rc;
   HIP_TRY(hipMemsetAsync(w.cnt_x, 0, (size_t)batch * sizeof(unsigned), s));
   HIP_TRY(hipMemsetAsync(w.cnt_y, 0, (size_t)batch * sizeof(unsigned), s));
   // (Euler only: the state a stage reads, writes and starts from is the one buffer)
@@ -390,5 +396,29 @@ extern "C" int rgfm_fmnet_sample_pair(rgfm_fmnet* hx, rgfm_fmnet* hy, float* x_i
     };
   };
   return pair_loop(net(hx, w.cnt_x, w.mark_x), net(hy, w.cnt_y, w.mark_y), x_inout, y_inout, mc_x1, mc_y1, mc_ratios, n_mc,
-                   batch, num_steps, gamma, step_begin, ns, d, d, w.vx, w.vy, w.logp, s);
+                   batch, num_steps, gamma, step_begin, ns, d, d, w.vx, w.vy, w.logp, s, nullptr, SOLVER_EULER, nullptr, nullptr,
+                   sink.on() ? &sink : nullptr);
+}
+}  // namespace
+
+extern "C" int rgfm_fmnet_sample_pair(rgfm_fmnet* hx, rgfm_fmnet* hy, float* x_inout, float* y_inout,
+                                      const float* mc_x1, const float* mc_y1, const float* mc_ratios, int n_mc,
+                                      int batch, int num_steps, double gamma, int step_begin, int step_end, void* ws,
+                                      size_t ws_bytes, rgfm_stream_t stream) {
+  return fm_pair_loop(hx, hy, x_inout, y_inout, mc_x1, mc_y1, mc_ratios, n_mc, batch, num_steps, gamma, step_begin, step_end, ws,
+                      ws_bytes, stream, nullptr, 0);
+}
+// ... with the diagnostics sink (include/rgfm.h, "Guidance diagnostics")
+extern "C" int rgfm_fmnet_sample_pair_diag_workspace_bytes(const rgfm_fmnet* hx, const rgfm_fmnet* hy, int batch, int n_mc,
+                                                           size_t* bytes) {
+  if (int rc = rgfm_fmnet_sample_pair_workspace_bytes(hx, hy, batch, n_mc, bytes)) return rc;
+  *bytes += diag_scratch_bytes(batch, FM_S * FM_S, FM_S * FM_S);
+  return RGFM_OK;
+}
+extern "C" int rgfm_fmnet_sample_pair_diag(rgfm_fmnet* hx, rgfm_fmnet* hy, float* x_inout, float* y_inout, const float* mc_x1,
+                                           const float* mc_y1, const float* mc_ratios, int n_mc, int batch, int num_steps,
+                                           double gamma, int step_begin, int step_end, float* diag_out, size_t diag_records,
+                                           void* ws, size_t ws_bytes, rgfm_stream_t stream) {
+  return fm_pair_loop(hx, hy, x_inout, y_inout, mc_x1, mc_y1, mc_ratios, n_mc, batch, num_steps, gamma, step_begin, step_end, ws,
+                      ws_bytes, stream, diag_out, diag_records);
 }

@@ -755,12 +755,15 @@ int pair_grad_bytes(const rgfm_unet* hx, const rgfm_unet* hy, const rgfm_ratio* 
 }
 
 int pair_grad_loop(rgfm_unet* hx, rgfm_unet* hy, rgfm_ratio* hr, float* x_inout, float* y_inout, int batch, int num_steps,
-                   double gamma, int step_begin, int step_end, int solver, void* ws, size_t ws_bytes, rgfm_stream_t stream) {
+                   double gamma, int step_begin, int step_end, int solver, void* ws, size_t ws_bytes, rgfm_stream_t stream,
+                   float* diag_out = nullptr, size_t diag_records = 0) {
   refresh_modes();
   int ns = 0;
   if (int rc = check_loop(solver, hx && hy && hr && x_inout && y_inout && ws, batch, num_steps, step_begin, step_end, &ns))
     return rc;
   if (int rc = check_grad_pair(hx, hy, hr)) return rc;
+  DiagSink sink;  // (the gradient loops need no scratch: v and grad log r are both in the workspace already)
+  if (int rc = sink.check(diag_out, diag_records, batch, ns, solver)) return rc;
   Bump b(ws, ws_bytes);
   PairGradWs w{{hx, batch, solver}, {hy, batch, solver}};
   carve_pair_grad(b, w, hr);
@@ -772,6 +775,8 @@ int pair_grad_loop(rgfm_unet* hx, rgfm_unet* hy, rgfm_ratio* hr, float* x_inout,
   const size_t dx = w.cx.image_floats(), dy = w.cy.image_floats();
   if (int rc = w.cx.begin(s, num_steps, step_begin, ns)) return rc;
   if (int rc = w.cy.begin(s, num_steps, step_begin, ns)) return rc;
+  if (sink.on())
+    if (int rc = sink.begin(s, 0, 0)) return rc;
   const float gf = (float)gamma;
   const bool overlap = g_modes.overlap;
   // one stage: (xout, yout) = (xb, yb) + (v(in, row's t) + gamma grad log r(xin, yin)) dts; xb / yb null: in place
@@ -794,6 +799,13 @@ int pair_grad_loop(rgfm_unet* hx, rgfm_unet* hy, rgfm_ratio* hr, float* x_inout,
       r.grad(xin, yin, w.gx, w.gy, nullptr);
     }
     if (overlap) HIP_TRY(hipStreamWaitEvent(s, ds->join, 0));
+    if (sink.on()) {  // |v| and |grad log r| (before gamma) per row and modality
+      float* rec = sink.next();
+      launch_diag_rownorm(w.vx, batch, (int)dx, rec, RGFM_DIAG_V_NORM_X, s);
+      launch_diag_rownorm(w.vy, batch, (int)dy, rec, RGFM_DIAG_V_NORM_Y, s);
+      launch_diag_rownorm(w.gx, batch, (int)dx, rec, RGFM_DIAG_G_NORM_X, s);
+      launch_diag_rownorm(w.gy, batch, (int)dy, rec, RGFM_DIAG_G_NORM_Y, s);
+    }
     launch_euler_grad(xout, w.vx, w.gx, (size_t)batch * dx, gf, g.dts, s, xb);
     launch_euler_grad(yout, w.vy, w.gy, (size_t)batch * dy, gf, g.dts, s, yb);
     return RGFM_OK;
@@ -865,13 +877,16 @@ int cond_grad_bytes(const rgfm_unet* h, const rgfm_ratio* hr, int given, int bat
 }
 
 int cond_grad_loop(rgfm_unet* h, rgfm_ratio* hr, float* s_inout, const float* ctx, int given, int batch, int num_steps,
-                   double gamma, int step_begin, int step_end, int solver, void* ws, size_t ws_bytes, rgfm_stream_t stream) {
+                   double gamma, int step_begin, int step_end, int solver, void* ws, size_t ws_bytes, rgfm_stream_t stream,
+                   float* diag_out = nullptr, size_t diag_records = 0) {
   refresh_modes();
   int ns = 0;
   if (int rc = check_loop(solver, h && hr && s_inout && ctx && ws, batch, num_steps, step_begin, step_end, &ns))
     return rc;
   int rc = check_given(given);
   if (rc || (rc = check_grad_side(h, hr, given))) return rc;
+  DiagSink sink;
+  if ((rc = sink.check(diag_out, diag_records, batch, ns, solver))) return rc;
   Bump b(ws, ws_bytes);
   CondGradWs w = carve_cond_grad(b, h, hr, given, batch, solver);
   if ((rc = check_workspace(b, ws_bytes))) return rc;
@@ -879,6 +894,7 @@ int cond_grad_loop(rgfm_unet* h, rgfm_ratio* hr, float* s_inout, const float* ct
   hipStream_t s = (hipStream_t)stream;
   const size_t d = w.c.image_floats();
   if ((rc = w.c.begin(s, num_steps, step_begin, ns))) return rc;
+  if (sink.on() && (rc = sink.begin(s, 0, 0))) return rc;
   const float gf = (float)gamma;
   for (int i = 0; i < ns; ++i) {
     Stage st[2];
@@ -893,6 +909,11 @@ int cond_grad_loop(rgfm_unet* h, rgfm_ratio* hr, float* s_inout, const float* ct
         RatioPass r{hr, batch, &b, s, false, h->range_flag};
         ModeScope ratio_mode(h->conv_mode);  // (the estimator's convs follow the target net's handle)
         r.grad_cond(ctx, given, in, w.g, nullptr);
+      }
+      if (sink.on()) {  // (one-sided: the target's norms in the x entries, whichever side of the estimator it is)
+        float* rec = sink.next();
+        launch_diag_rownorm(w.v, batch, (int)d, rec, RGFM_DIAG_V_NORM_X, s);
+        launch_diag_rownorm(w.g, batch, (int)d, rec, RGFM_DIAG_G_NORM_X, s);
       }
       launch_euler_grad(out, w.v, w.g, (size_t)batch * d, gf, g.dts, s, g.writes_mid ? s_inout : nullptr);
     }
@@ -919,4 +940,28 @@ extern "C" int rgfm_sample_cond_grad_ode(rgfm_unet* h, rgfm_ratio* hr, float* s_
                                          int num_steps, double gamma, int step_begin, int step_end, int solver, void* ws,
                                          size_t ws_bytes, rgfm_stream_t stream) {
   return cond_grad_loop(h, hr, s_inout, ctx, given, batch, num_steps, gamma, step_begin, step_end, solver, ws, ws_bytes, stream);
+}
+
+// ---- the gradient-guided loops with the diagnostics sink (include/rgfm.h, "Guidance diagnostics"): no extra workspace
+extern "C" int rgfm_sample_pair_grad_diag_workspace_bytes(const rgfm_unet* hx, const rgfm_unet* hy, const rgfm_ratio* hr,
+                                                          int batch, int solver, size_t* bytes) {
+  return pair_grad_bytes(hx, hy, hr, batch, solver, bytes);
+}
+extern "C" int rgfm_sample_pair_grad_diag(rgfm_unet* hx, rgfm_unet* hy, rgfm_ratio* hr, float* x_inout, float* y_inout,
+                                          int batch, int num_steps, double gamma, int step_begin, int step_end, int solver,
+                                          float* diag_out, size_t diag_records, void* ws, size_t ws_bytes,
+                                          rgfm_stream_t stream) {
+  return pair_grad_loop(hx, hy, hr, x_inout, y_inout, batch, num_steps, gamma, step_begin, step_end, solver, ws, ws_bytes, stream,
+                        diag_out, diag_records);
+}
+extern "C" int rgfm_sample_cond_grad_diag_workspace_bytes(const rgfm_unet* h, const rgfm_ratio* hr, int given, int batch,
+                                                          int solver, size_t* bytes) {
+  return cond_grad_bytes(h, hr, given, batch, solver, bytes);
+}
+extern "C" int rgfm_sample_cond_grad_diag(rgfm_unet* h, rgfm_ratio* hr, float* s_inout, const float* ctx, int given, int batch,
+                                          int num_steps, double gamma, int step_begin, int step_end, int solver,
+                                          float* diag_out, size_t diag_records, void* ws, size_t ws_bytes,
+                                          rgfm_stream_t stream) {
+  return cond_grad_loop(h, hr, s_inout, ctx, given, batch, num_steps, gamma, step_begin, step_end, solver, ws, ws_bytes, stream,
+                        diag_out, diag_records);
 }

@@ -226,34 +226,90 @@ extern "C" int rgfm_guidance_apply_cond(const float* s, float* v, const float* m
   return RGFM_OK;
 }
 
+// ---- diagnostics of one evaluation of the block (include/rgfm.h, "Guidance diagnostics")
+// workspace: the block's, then the two scratch velocities of GuidDiag
+namespace {
+int guidance_diag(const float* x, const float* y, const float* vx, const float* vy, const float* mx, const float* my,
+                  const float* r, int batch, int n_mc, int dx, int dy, double t, int ratio_stride, float* diag_out, void* ws,
+                  size_t ws_bytes, rgfm_stream_t stream) {
+  size_t need = 0;
+  int rc = rgfm_guidance_diag_workspace_bytes(batch, n_mc, dx, dy, &need);
+  if (rc) return rc;
+  if (n_mc > 4096) return fail(RGFM_EINVAL, "n_mc too large (max 4096)");
+  if (need > ws_bytes) return fail(RGFM_ENOMEM, "workspace too small: %zu < %zu", ws_bytes, need);
+  if ((rc = ensure_init())) return rc;
+  hipStream_t s = (hipStream_t)stream;
+  Bump b(ws, ws_bytes);
+  float* scratch = b.f(guid_scratch_bytes(batch, n_mc) / sizeof(float));
+  DiagSink sink;
+  if ((rc = sink.check(diag_out, (size_t)batch, batch, 1, SOLVER_EULER))) return rc;
+  sink.carve(b, dx, dy);
+  if ((rc = sink.begin(s, dx, dy))) return rc;
+  const GuidDiag gd{sink.next(), sink.gx, sink.gy};
+  // (phase 3 reads v and writes none of the block's outputs: the casts drop a const that is kept)
+  rc = guidance_launch(x, y, const_cast<float*>(vx), const_cast<float*>(vy), mx, my, r, batch, n_mc, dx, dy, t, 0.0, scratch,
+                       nullptr, nullptr, nullptr, 0.f, s, nullptr, nullptr, 3, ratio_stride, nullptr, nullptr, &gd);
+  if (rc) return rc;
+  HIP_TRY(hipGetLastError());
+  return RGFM_OK;
+}
+}  // namespace
+
+extern "C" int rgfm_guidance_diag_workspace_bytes(int batch, int n_mc, int dim_x, int dim_y, size_t* bytes) {
+  if (!bytes || batch < 1 || n_mc < 1 || dim_x < 1 || dim_y < 0) return fail(RGFM_EINVAL, "bad argument");
+  if (dim_x % 4 || dim_y % 4) return fail(RGFM_EINVAL, "flattened image sizes must be multiples of 4");
+  *bytes = guid_scratch_bytes(batch, n_mc) + diag_scratch_bytes(batch, dim_x, dim_y);
+  return RGFM_OK;
+}
+extern "C" int rgfm_guidance_diag(const float* x, const float* y, const float* vx, const float* vy, const float* mc_x1,
+                                  const float* mc_y1, const float* mc_ratios, int batch, int n_mc, int dim_x, int dim_y,
+                                  double t, float* diag_out, void* ws, size_t ws_bytes, rgfm_stream_t stream) {
+  if (!x || !y || !vx || !vy || !mc_x1 || !mc_y1 || !mc_ratios || !diag_out || !ws) return fail(RGFM_EINVAL, "null argument");
+  if (dim_y < 1) return fail(RGFM_EINVAL, "bad argument");
+  return guidance_diag(x, y, vx, vy, mc_x1, mc_y1, mc_ratios, batch, n_mc, dim_x, dim_y, t, 0, diag_out, ws, ws_bytes, stream);
+}
+extern "C" int rgfm_guidance_diag_cond(const float* s, const float* v, const float* mc_set, const float* ratios, int batch,
+                                       int n_mc, int dim, double t, float* diag_out, void* ws, size_t ws_bytes,
+                                       rgfm_stream_t stream) {
+  if (!s || !v || !mc_set || !ratios || !diag_out || !ws) return fail(RGFM_EINVAL, "null argument");
+  return guidance_diag(s, nullptr, v, nullptr, mc_set, nullptr, ratios, batch, n_mc, dim, 0, t, n_mc, diag_out, ws, ws_bytes,
+                       stream);
+}
+
 namespace {
 
-int cond_bytes(const rgfm_unet* h, int batch, int n_mc, int solver, size_t* bytes) {
+int cond_bytes(const rgfm_unet* h, int batch, int n_mc, int solver, size_t* bytes, bool diag = false) {
   if (int rc = check_solver_id(solver)) return rc;
   if (!h || !bytes || batch < 1 || n_mc < 1) return fail(RGFM_EINVAL, "bad argument");
   Bump b;
-  carve_cond(b, const_cast<rgfm_unet*>(h), batch, n_mc, solver);
-  *bytes = b.off;
+  const CondWs w = carve_cond(b, const_cast<rgfm_unet*>(h), batch, n_mc, solver);
+  *bytes = b.off + (diag ? diag_scratch_bytes(batch, w.c.image_floats(), 0) : 0);
   return RGFM_OK;
 }
 
 // One net, guided by the one-sided block: kernel by kernel on the caller's stream (nothing to overlap, no graph).
 int cond_loop(rgfm_unet* h, float* s_inout, const float* mc_set, const float* ratios, int n_mc, int batch, int num_steps,
-              double gamma, int step_begin, int step_end, int solver, void* ws, size_t ws_bytes, rgfm_stream_t stream) {
+              double gamma, int step_begin, int step_end, int solver, void* ws, size_t ws_bytes, rgfm_stream_t stream,
+              float* diag_out = nullptr, size_t diag_records = 0) {
   refresh_modes();
   int ns = 0;
   if (int rc = check_loop(solver, h && s_inout && mc_set && ratios && ws, batch, num_steps, step_begin, step_end, &ns))
     return rc;
+  DiagSink sink;
+  if (int rc = sink.check(diag_out, diag_records, batch, ns, solver)) return rc;
   if (n_mc < 1) return fail(RGFM_EINVAL, "conditional sampling needs an MC set (n_mc >= 1)");
   const int d = h->d.in_channels * h->d.img_size * h->d.img_size;
   if (d % 4) return fail(RGFM_EINVAL, "flattened image sizes must be multiples of 4");
   if (n_mc > 4096) return fail(RGFM_EINVAL, "n_mc too large (max 4096)");
   Bump b(ws, ws_bytes);
   CondWs w = carve_cond(b, h, batch, n_mc, solver);
+  if (sink.on()) sink.carve(b, d, 0);
   if (int rc = check_workspace(b, ws_bytes)) return rc;
   if (ns == 0) return RGFM_OK;
   hipStream_t s = (hipStream_t)stream;
   if (int rc = w.c.begin(s, num_steps, step_begin, ns)) return rc;
+  if (sink.on())
+    if (int rc = sink.begin(s, d, 0)) return rc;
   for (int i = 0; i < ns; ++i) {
     Stage st[2];
     const int n = w.c.stages(i, st);
@@ -262,13 +318,15 @@ int cond_loop(rgfm_unet* h, float* s_inout, const float* mc_set, const float* ra
       const Stage& g = st[k];
       float *in = g.reads_mid ? w.c.mid : s_inout, *out = g.writes_mid ? w.c.mid : s_inout;
       const bool guided = g.t > 1e-3;
+      GuidDiag gd{};
+      if (sink.on()) gd = {sink.next(), sink.gx, sink.gy};
       // unguided: the fused Euler epilogue; guided: the raw velocity, and the guidance block moves the state
       if (int rc = guided ? w.c.eval(g.row, s, in, w.v, nullptr, nullptr, g.dts)
                           : w.c.eval(g.row, s, in, nullptr, out, s_inout, g.dts))
         return rc;
       if (!guided) continue;
       if (int rc = guidance_launch(in, nullptr, w.v, nullptr, mc_set, nullptr, ratios, batch, n_mc, d, 0, g.t, gamma, w.scratch,
-                                   nullptr, out, nullptr, g.dts, s, nullptr, nullptr, 0, n_mc, s_inout, nullptr))
+                                   nullptr, out, nullptr, g.dts, s, nullptr, nullptr, 0, n_mc, s_inout, nullptr, sink.on() ? &gd : nullptr))
         return rc;
     }
   }
@@ -276,36 +334,41 @@ int cond_loop(rgfm_unet* h, float* s_inout, const float* mc_set, const float* ra
   return RGFM_OK;
 }
 
-int pair_bytes(const rgfm_unet* hx, const rgfm_unet* hy, int batch, int n_mc, int solver, size_t* bytes) {
+int pair_bytes(const rgfm_unet* hx, const rgfm_unet* hy, int batch, int n_mc, int solver, size_t* bytes, bool diag = false) {
   if (int rc = check_solver_id(solver)) return rc;
   if (!hx || !hy || !bytes || batch < 1 || n_mc < 0) return fail(RGFM_EINVAL, "bad argument");
   Bump b;
   PairWs w{{const_cast<rgfm_unet*>(hx), batch, solver}, {const_cast<rgfm_unet*>(hy), batch, solver}};
   carve_pair(b, w, n_mc);
-  *bytes = b.off;
+  *bytes = b.off + (diag ? diag_scratch_bytes(batch, w.cx.image_floats(), w.cy.image_floats()) : 0);
   return RGFM_OK;
 }
 
 int pair_sample(rgfm_unet* hx, rgfm_unet* hy, float* x_inout, float* y_inout, const float* mc_x1, const float* mc_y1,
                 const float* mc_ratios, int n_mc, int batch, int num_steps, double gamma, int step_begin, int step_end,
-                int solver, void* ws, size_t ws_bytes, rgfm_stream_t stream) {
+                int solver, void* ws, size_t ws_bytes, rgfm_stream_t stream, float* diag_out = nullptr, size_t diag_records = 0) {
   refresh_modes();
   int ns = 0;
   if (int rc = check_loop(solver, hx && hy && x_inout && y_inout && ws, batch, num_steps, step_begin, step_end, &ns))
     return rc;
   if (n_mc < 0 || (n_mc > 0 && (!mc_x1 || !mc_y1 || !mc_ratios))) return fail(RGFM_EINVAL, "MC set missing");
+  DiagSink sink;
+  if (int rc = sink.check(diag_out, diag_records, batch, ns, solver)) return rc;
   Bump b(ws, ws_bytes);
   PairWs w{{hx, batch, solver}, {hy, batch, solver}};
   carve_pair(b, w, n_mc);
+  if (sink.on()) sink.carve(b, w.cx.image_floats(), w.cy.image_floats());
   if (int rc = check_workspace(b, ws_bytes)) return rc;
   if (ns == 0) return RGFM_OK;
   hipStream_t s = (hipStream_t)stream;
   if (int rc = w.cx.begin(s, num_steps, step_begin, ns)) return rc;
   if (int rc = w.cy.begin(s, num_steps, step_begin, ns)) return rc;
+  if (sink.on())
+    if (int rc = sink.begin(s, w.cx.image_floats(), w.cy.image_floats())) return rc;
   auto net = [](NetChain& c) { return [&c](auto... a) { return c.eval(a...); }; };  // pair_loop's eval: NetChain::eval
   return pair_loop(net(w.cx), net(w.cy), x_inout, y_inout, mc_x1, mc_y1, mc_ratios, n_mc, batch, num_steps, gamma, step_begin, ns,
                    (int)w.cx.image_floats(), (int)w.cy.image_floats(), w.vx, w.vy, w.logp, s, w.gstate, solver, w.cx.mid,
-                   w.cy.mid);
+                   w.cy.mid, sink.on() ? &sink : nullptr);
 }
 
 }  // namespace
@@ -349,4 +412,26 @@ extern "C" int rgfm_sample_pair_ode(rgfm_unet* hx, rgfm_unet* hy, float* x_inout
                                     rgfm_stream_t stream) {
   return pair_sample(hx, hy, x_inout, y_inout, mc_x1, mc_y1, mc_ratios, n_mc, batch, num_steps, gamma, step_begin, step_end,
                      solver, ws, ws_bytes, stream);
+}
+
+// ---- the same loops with the diagnostics sink (include/rgfm.h, "Guidance diagnostics")
+extern "C" int rgfm_sample_cond_diag_workspace_bytes(const rgfm_unet* h, int batch, int n_mc, int solver, size_t* bytes) {
+  return cond_bytes(h, batch, n_mc, solver, bytes, true);
+}
+extern "C" int rgfm_sample_cond_diag(rgfm_unet* h, float* s_inout, const float* mc_set, const float* ratios, int n_mc, int batch,
+                                     int num_steps, double gamma, int step_begin, int step_end, int solver, float* diag_out,
+                                     size_t diag_records, void* ws, size_t ws_bytes, rgfm_stream_t stream) {
+  return cond_loop(h, s_inout, mc_set, ratios, n_mc, batch, num_steps, gamma, step_begin, step_end, solver, ws, ws_bytes, stream,
+                   diag_out, diag_records);
+}
+extern "C" int rgfm_sample_pair_diag_workspace_bytes(const rgfm_unet* hx, const rgfm_unet* hy, int batch, int n_mc, int solver,
+                                                     size_t* bytes) {
+  return pair_bytes(hx, hy, batch, n_mc, solver, bytes, true);
+}
+extern "C" int rgfm_sample_pair_diag(rgfm_unet* hx, rgfm_unet* hy, float* x_inout, float* y_inout, const float* mc_x1,
+                                     const float* mc_y1, const float* mc_ratios, int n_mc, int batch, int num_steps,
+                                     double gamma, int step_begin, int step_end, int solver, float* diag_out,
+                                     size_t diag_records, void* ws, size_t ws_bytes, rgfm_stream_t stream) {
+  return pair_sample(hx, hy, x_inout, y_inout, mc_x1, mc_y1, mc_ratios, n_mc, batch, num_steps, gamma, step_begin, step_end,
+                     solver, ws, ws_bytes, stream, diag_out, diag_records);
 }

@@ -190,6 +190,7 @@ __global__ __launch_bounds__(256) void guid_weights_kernel(const GuidanceArgs a_
   zs = wave_sum_g(zs);
   const float pbar = __fadd_rn(ps / (float)N, 1e-10f);
   const float zbar = __fadd_rn(zs / (float)N, 1e-10f);
+  if (a.diag_rec && lane == 0) a.diag_rec[(size_t)b * RGFM_DIAG_FLOATS + RGFM_DIAG_Z_BAR] = zbar;
   float ws = 0.f;
   for (int i = lane; i < N; i += 64) {
     const float w = __fmul_rn(ratios[i] / zbar, swr[i] / pbar);
@@ -347,6 +348,62 @@ __global__ __launch_bounds__(256, 2) void guid_apply_mfma_kernel(const GuidanceA
       *reinterpret_cast<f32x4*>(V + o) = nv;
     }
   }
+}
+
+// ---- diagnostics (opt-in: launched only for a caller that passes a record buffer; include/rgfm.h, RGFM_DIAG_*)
+__device__ __forceinline__ float wave_min_g(float v) {
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) v = fminf(v, __shfl_xor(v, o));
+  return v;
+}
+
+// Row statistics of the step's importance weights w [B][N] (GuidanceArgs::wbuf), one wave per row as guid_weights_kernel:
+// lane l adds samples l, l + 64, ... in index order, the 64 partials meet in the xor butterfly -- an order fixed by N
+// alone, the same on every lane.  ess = (sum w)^2 / sum w^2; a row whose weights are all zero (every ratio zero) has
+// ess 0.  N < 64: the idle lanes hold the identities (0, -inf, +inf).
+__global__ __launch_bounds__(256) void guid_diag_wstats_kernel(const float* __restrict__ w, int B, int N, float* __restrict__ rec) {
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  const int b = blockIdx.x * 4 + wave;
+  if (b >= B) return;
+  const float* wr = w + (size_t)b * N;
+  float s = 0.f, q = 0.f, mx = -INFINITY, mn = INFINITY;
+  for (int i = lane; i < N; i += 64) {
+    const float v = wr[i];
+    s += v;
+    q = fmaf(v, v, q);
+    mx = fmaxf(mx, v);
+    mn = fminf(mn, v);
+  }
+  s = wave_sum_g(s), q = wave_sum_g(q), mx = wave_max_g(mx), mn = wave_min_g(mn);
+  if (lane == 0) {
+    float* r = rec + (size_t)b * RGFM_DIAG_FLOATS;
+    r[RGFM_DIAG_ESS] = q > 0.f ? s * s / q : 0.f;
+    r[RGFM_DIAG_W_MAX] = mx;
+    r[RGFM_DIAG_W_MIN] = mn;
+  }
+}
+
+// rec[b][slot] = |v_b|_2 for v [B][D], D % 4 == 0: one wave per row, lane l squares float4s l, l + 64, ... into four
+// running sums (one per component), adds them pairwise and the 64 partials in the xor butterfly: an order fixed by D.
+__global__ __launch_bounds__(256) void guid_diag_rownorm_kernel(const float* __restrict__ v, int B, int D, float* __restrict__ rec, int slot) {
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  const int b = blockIdx.x * 4 + wave;
+  if (b >= B) return;
+  const f32x4* r = reinterpret_cast<const f32x4*>(v + (size_t)b * D);
+  float s0 = 0.f, s1 = 0.f, s2 = 0.f, s3 = 0.f;
+  for (int i = lane; i < (D >> 2); i += 64) {
+    const f32x4 a = r[i];
+    s0 = fmaf(a.x, a.x, s0), s1 = fmaf(a.y, a.y, s1), s2 = fmaf(a.z, a.z, s2), s3 = fmaf(a.w, a.w, s3);
+  }
+  const float s = wave_sum_g((s0 + s1) + (s2 + s3));
+  if (lane == 0) rec[(size_t)b * RGFM_DIAG_FLOATS + slot] = sqrtf(s);
+}
+
+void launch_diag_wstats(const float* w, int B, int N, float* rec, hipStream_t s) {
+  hipLaunchKernelGGL(guid_diag_wstats_kernel, dim3((B + 3) / 4), dim3(256), 0, s, w, B, N, rec);
+}
+void launch_diag_rownorm(const float* v, int B, int D, float* rec, int slot, hipStream_t s) {
+  hipLaunchKernelGGL(guid_diag_rownorm_kernel, dim3((B + 3) / 4), dim3(256), 0, s, v, B, D, rec, slot);
 }
 
 void launch_guid_logp(const GuidanceArgs& a, hipStream_t s) {

@@ -993,13 +993,21 @@ inline void guidance_scalars(double t, float* tf, float* s2, float* cden) {
   *tf = (float)t, *s2 = (float)(sigma_t * sigma_t), *cden = (float)(1.0 - t + eps);
 }
 
+// Diagnostics of one evaluation of the block (include/rgfm.h, RGFM_DIAG_*).  rec: its [B][RGFM_DIAG_FLOATS] records,
+// zeroed by the caller (the entries of a modality that is not there stay 0).  gx / gy: scratch velocities [B][dx] /
+// [B][dy] holding finite values (zeroed once by the caller): they receive the pure guided velocity g -- one more
+// launch_guid_apply with the blend (1 - gamma, gamma) = (0, 1) and no state update, the bits of the g inside the real one.
+struct GuidDiag {
+  float *rec, *gx, *gy;
+};
+
 inline int guidance_launch(const float* x, const float* y, float* vx, float* vy, const float* mx, const float* my,
                     const float* r, int B, int N, int dx, int dy, double t, double gamma, float* logp,
                     float* weights_out, float* xs, float* ys, float dt, hipStream_t s, const float* sched = nullptr,
                     const int* step_ptr = nullptr, int phase = 0, int ratio_stride = 0, const float* xb = nullptr,
-                    const float* yb = nullptr) {
+                    const float* yb = nullptr, const GuidDiag* diag = nullptr) {
   // phase 0: the whole block; 1: distances + importance weights only -- they need the step's (x_t, y_t) and the MC set,
-  // not the velocities; 2: the rest (needs v)
+  // not the velocities; 2: the rest (needs v); 3 (with diag): the weights and the diagnostics, v is only read
   // One-sided block (conditional sampling): dy = 0 with y, vy, my, ys null, and ratio_stride = N -- r is then [B][N],
   // a ratio row per sample.  The kernels take the second modality's slices and column blocks from dy, so none is
   // launched; the observed side's Gaussian factor is constant in the MC index and cancels in the normalised weights.
@@ -1017,6 +1025,7 @@ inline int guidance_launch(const float* x, const float* y, float* vx, float* vy,
   a.sched = sched, a.step_ptr = sched ? step_ptr : nullptr;
   a.g1 = (float)(1.0 - gamma), a.g2 = (float)gamma;
   a.dist = reinterpret_cast<double*>(logp), a.weights_out = weights_out, a.x_state = xs, a.y_state = ys, a.dt = dt;
+  a.diag_rec = diag ? diag->rec : nullptr;
   a.x_base = xb == x ? nullptr : xb, a.y_base = yb == y ? nullptr : yb;
   a.wbuf = reinterpret_cast<float*>(reinterpret_cast<char*>(logp) + guid_dist_bytes(B, N));
   a.wsum = reinterpret_cast<float*>(reinterpret_cast<char*>(a.wbuf) + guid_wbuf_bytes(B, N));
@@ -1026,12 +1035,23 @@ inline int guidance_launch(const float* x, const float* y, float* vx, float* vy,
   // algorithmic bytes.  logp: rows of x, y and the MC set in, the sliced fp64 distances out.  apply: the
   // distances, x, y, v and the MC set in, the new state (or velocity) out.
   const double D = (double)dx + dy, dist_b = 8.0 * (a.nsx + a.nsy) * (double)B * N;
-  if (phase < 2) {  // (timer class "guid_logp": the distances AND the importance weights made of them)
+  if (phase != 2) {  // (timer class "guid_logp": the distances AND the importance weights made of them)
     ProfScope p(RGFM_KCLASS_GUID_LOGP, 4.0 * (B + N) * D + dist_b, s);
     launch_guid_logp(a, s);
     launch_guid_weights(a, s);
   }
-  if (phase != 1) {
+  if (phase != 2 && diag) launch_diag_wstats(a.wbuf, B, N, diag->rec, s);
+  if (phase != 1 && diag) {  // before the real apply: in a loop that one moves the state g is taken at
+    launch_diag_rownorm(vx, B, dx, diag->rec, RGFM_DIAG_V_NORM_X, s);
+    if (dy) launch_diag_rownorm(vy, B, dy, diag->rec, RGFM_DIAG_V_NORM_Y, s);
+    GuidanceArgs d = a;
+    d.vx = diag->gx, d.vy = diag->gy, d.g1 = 0.f, d.g2 = 1.f;
+    d.x_state = d.y_state = nullptr, d.x_base = d.y_base = nullptr, d.weights_out = nullptr;
+    launch_guid_apply(d, s);
+    launch_diag_rownorm(diag->gx, B, dx, diag->rec, RGFM_DIAG_G_NORM_X, s);
+    if (dy) launch_diag_rownorm(diag->gy, B, dy, diag->rec, RGFM_DIAG_G_NORM_Y, s);
+  }
+  if (phase != 1 && phase != 3) {
     ProfScope p(RGFM_KCLASS_GUID_APPLY, 4.0 * B * N + 4.0 * N * D + 4.0 * B * D * 3.0, s);
     launch_guid_apply(a, s);
   }

@@ -437,6 +437,7 @@ struct GuidanceArgs {
   float* weights_out;  // optional [B][N]
   float* wbuf;         // [B][N] importance weights of the step (scratch: behind the distance slices)
   float* wsum;         // [B] their row sums (scratch: behind wbuf)
+  float* diag_rec;     // optional [B][RGFM_DIAG_FLOATS] diagnostics records: guid_weights writes each row's Z_bar into its slot
   float* x_state;      // optional fused Euler: x_state += dt * blended
   float* y_state;
   // optional: x_state = x_base + dt * blended, with x still the point the guidance is evaluated at (the second stage of
@@ -453,6 +454,9 @@ int guid_apply_init();                                         // (once per proc
 void launch_euler(float* x, const float* v, size_t n, float dt, hipStream_t s);
 void launch_step_inc(int* step, hipStream_t s);  // *step += 1
 void launch_guid_schedule(float* sched, int step_begin, int ns, int num_steps, hipStream_t s);  // [ns][4] = {tf, s2, cden, 0}
+// diagnostics (opt-in; rec: [B][RGFM_DIAG_FLOATS] records, include/rgfm.h)
+void launch_diag_wstats(const float* w, int B, int N, float* rec, hipStream_t s);  // ess, w_max, w_min of the rows of w [B][N]
+void launch_diag_rownorm(const float* v, int B, int D, float* rec, int slot, hipStream_t s);  // rec[b][slot] = |v[b]|_2, v [B][D], D % 4 == 0
 
 // ---- training pass of the U-Net (unet_grad.hip; all tensors NCHW fp32)
 // One conv for ug_igemm_kernel.  op 0: out = conv(x) + bias (+ temb[b][co]) (+ res), op 1: data gradient of the conv's

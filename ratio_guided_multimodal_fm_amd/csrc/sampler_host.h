@@ -33,6 +33,43 @@ inline int check_workspace(const Bump& carved, size_t ws_bytes) {
   return carved.off > ws_bytes ? fail(RGFM_ENOMEM, "workspace too small: %zu < %zu", ws_bytes, carved.off) : RGFM_OK;
 }
 
+// The diagnostics sink of a loop (include/rgfm.h, "Guidance diagnostics"): null `out` = off, and every loop then enqueues
+// what it enqueues without one.  On: one [batch][RGFM_DIAG_FLOATS] block of `out` per stage, in the order of step_stages;
+// `begin` zeroes all of them (an unguided stage's record, and the entries a loop does not fill, stay 0), the guided
+// stages' kernels fill theirs.  gx / gy: the MC loops' scratch velocities for the pure guided velocity (GuidDiag),
+// carved behind the loop's own workspace.
+struct DiagSink {
+  float* out = nullptr;
+  size_t records = 0;
+  int batch = 0, n_stages = 0, stage = 0;
+  float *gx = nullptr, *gy = nullptr;
+  bool on() const { return out != nullptr; }
+  // the argument check of every *_diag entry point, before anything is carved or enqueued
+  int check(float* diag_out, size_t diag_records, int batch_, int ns, int solver) {
+    if (!diag_out && !diag_records) return RGFM_OK;
+    if (!diag_out || !diag_records) return fail(RGFM_EINVAL, "diag_out and diag_records go together (both, or null and 0)");
+    out = diag_out, records = diag_records, batch = batch_, n_stages = ns * (solver == SOLVER_MIDPOINT ? 2 : 1);
+    if (records < (size_t)n_stages * batch)
+      return fail(RGFM_EINVAL, "diag_records %zu < %d stages x %d samples", records, n_stages, batch);
+    return RGFM_OK;
+  }
+  void carve(Bump& b, size_t dx, size_t dy) { gx = b.f((size_t)batch * dx), gy = b.f((size_t)batch * dy); }
+  int begin(hipStream_t s, size_t dx, size_t dy) {
+    HIP_TRY(hipMemsetAsync(out, 0, (size_t)n_stages * batch * RGFM_DIAG_FLOATS * sizeof(float), s));
+    if (gx && dx) HIP_TRY(hipMemsetAsync(gx, 0, (size_t)batch * dx * sizeof(float), s));
+    if (gy && dy) HIP_TRY(hipMemsetAsync(gy, 0, (size_t)batch * dy * sizeof(float), s));
+    return RGFM_OK;
+  }
+  float* next() { return out + (size_t)(stage++) * batch * RGFM_DIAG_FLOATS; }  // the next stage's records
+};
+// bytes a loop's workspace grows by with diagnostics on (the *_diag_workspace_bytes queries): DiagSink::carve
+inline size_t diag_scratch_bytes(int batch, size_t dx, size_t dy) {
+  Bump b;
+  DiagSink d;
+  d.batch = batch, d.carve(b, dx, dy);
+  return b.off;
+}
+
 // Time-table rows of a loop's stages.  Euler: row i is t = (step_begin + i) / num_steps.  Midpoint: row 2i is the step's
 // t1 = (step_begin + i) dt and row 2i + 1 its t2 = (step_begin + i + 0.5) dt -- the table of the 2 num_steps half-steps:
 // (2k + j) * (1.0 / (2 N)) and (k + j / 2) * (1.0 / N) are the same double (a factor two moves no rounding).
@@ -111,7 +148,8 @@ template <class EvalX, class EvalY>
 int pair_loop(EvalX&& eval_x, EvalY&& eval_y, float* x_inout, float* y_inout, const float* mc_x1,
               const float* mc_y1, const float* mc_ratios, int n_mc, int batch, int num_steps, double gamma,
               int step_begin, int ns, int dx, int dy, float* vx, float* vy, float* logp, hipStream_t caller,
-              float* gstate = nullptr, int solver = SOLVER_EULER, float* x_mid = nullptr, float* y_mid = nullptr) {
+              float* gstate = nullptr, int solver = SOLVER_EULER, float* x_mid = nullptr, float* y_mid = nullptr,
+              DiagSink* diag = nullptr) {
   // The two velocity nets of a step are independent (reference :119-121): the second one runs on a
   // side stream forked from / joined back into the caller's stream every step, which fills the CUs
   // that one net's small-grid launches (8x8 level, kernel tails) leave idle.
@@ -121,7 +159,8 @@ int pair_loop(EvalX&& eval_x, EvalY&& eval_y, float* x_inout, float* y_inout, co
   const bool overlap = g_modes.overlap;
   hipStream_t side = ds->side;
   hipEvent_t ev_fork = ds->fork, ev_join = ds->join;
-  const bool use_graph = gstate && g_modes.graph && !g_prof.on && n_mc > 0 && ns >= 4 && solver == SOLVER_EULER;
+  // (diagnostics: kernel by kernel -- each stage writes its own records, a replayed graph would write one stage's)
+  const bool use_graph = gstate && g_modes.graph && !g_prof.on && n_mc > 0 && ns >= 4 && solver == SOLVER_EULER && !diag;
   hipStream_t s = caller;
   if (use_graph && caller == nullptr) {  // (see DevState::main)
     s = ds->main;
@@ -147,6 +186,9 @@ int pair_loop(EvalX&& eval_x, EvalY&& eval_y, float* x_inout, float* y_inout, co
     float *xout = g.writes_mid ? x_mid : x_inout, *yout = g.writes_mid ? y_mid : y_inout;
     const float *xb = x_inout, *yb = y_inout;
     hipStream_t sy = overlap ? side : s;
+    GuidDiag gd{};
+    if (diag) gd = {diag->next(), diag->gx, diag->gy};
+    const GuidDiag* dg = diag && guided ? &gd : nullptr;
     if (overlap) {
       HIP_TRY(hipEventRecord(ev_fork, s));
       HIP_TRY(hipStreamWaitEvent(side, ev_fork, 0));
@@ -161,13 +203,13 @@ int pair_loop(EvalX&& eval_x, EvalY&& eval_y, float* x_inout, float* y_inout, co
     // other net -- the x net of a pair is the quicker one, so they run in its shadow instead of on the step's critical path
     if (guided && overlap) {
       rc = guidance_launch(xin, yin, vx, vy, mc_x1, mc_y1, mc_ratios, batch, n_mc, dx, dy, g.t, gamma, logp,
-                           nullptr, xout, yout, g.dts, s, sched_dev, step_dev, 1, 0, xb, yb);
+                           nullptr, xout, yout, g.dts, s, sched_dev, step_dev, 1, 0, xb, yb, dg);
       if (rc) return rc;
     }
     if (overlap) HIP_TRY(hipStreamWaitEvent(s, ev_join, 0));
     if (guided) {
       rc = guidance_launch(xin, yin, vx, vy, mc_x1, mc_y1, mc_ratios, batch, n_mc, dx, dy, g.t, gamma, logp,
-                           nullptr, xout, yout, g.dts, s, sched_dev, step_dev, overlap ? 2 : 0, 0, xb, yb);
+                           nullptr, xout, yout, g.dts, s, sched_dev, step_dev, overlap ? 2 : 0, 0, xb, yb, dg);
       if (rc) return rc;
     }
     if (step_dev) launch_step_inc(step_dev, s);

@@ -16,6 +16,8 @@ depend only on the row and the SHARED Monte-Carlo set
 No collective sits inside the Euler loop.  `backend` abstracts the three compute
 calls so that the sharding logic can be exercised with gloo on CPU ranks (the
 tests inject the CPU oracle there); the default backend is the HIP library.
+
+Guidance diagnostics (utils/diagnostics.py) are out of scope here: the sharded samplers take no ``diagnostics=``.
 """
 import os
 

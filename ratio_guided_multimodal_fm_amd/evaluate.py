@@ -20,6 +20,7 @@ from .models.classifier import MNISTClassifier
 from .models.ratio_estimator import RatioEstimator
 from .sample import add_common_args, build_flow_models
 from .utils import load_checkpoint, set_seed
+from .utils.diagnostics import GuidanceDiagnostics, add_cli_args as add_diagnostics_args, row_metrics
 from .utils.flow_utils import sample_bimodal_guided
 from .utils.path_utils import get_checkpoint_path
 
@@ -49,9 +50,11 @@ def evaluate_coherence(samples_x, samples_y, classifier, device, transform_type=
 
 
 def run_sweep(fm_x, fm_y, make_ratio, classifier, methods, strengths, num_samples, num_steps, device,
-              mc_batch_size, transform_type, sampler=sample_bimodal_guided, solver='euler'):
+              mc_batch_size, transform_type, sampler=sample_bimodal_guided, solver='euler', diagnostics=False):
     """The reference's nested loop (:165-222). `make_ratio()` returns a fresh ratio estimator or None.
-    `solver` ('euler' | 'midpoint') goes to `sampler` as a keyword when it is not the default."""
+    `solver` ('euler' | 'midpoint') goes to `sampler` as a keyword when it is not the default.
+    `diagnostics`: every guided row also gets ess_mean, ess_min and w_max of the importance weights at step
+    int(0.3 * num_steps) (utils/diagnostics.py); without it the rows keep exactly their keys."""
     from ._lib import solver_id
     solver_id(solver)
     kw = {'solver': solver} if solver != 'euler' else {}
@@ -63,8 +66,12 @@ def run_sweep(fm_x, fm_y, make_ratio, classifier, methods, strengths, num_sample
             ratio = make_ratio() if method != 'none' else None
             if method != 'none' and ratio is None:
                 continue
-            xs, ys = sampler(fm_x, fm_y, ratio, method, strength, num_samples, num_steps, device, mc_batch_size, **kw)
+            diag = GuidanceDiagnostics() if diagnostics and method != 'none' else None
+            xs, ys = sampler(fm_x, fm_y, ratio, method, strength, num_samples, num_steps, device, mc_batch_size, **kw,
+                             **({'diagnostics': diag} if diag is not None else {}))
             metrics = evaluate_coherence(xs, ys, classifier, device, transform_type)
+            if diag is not None and diag.records is not None:
+                metrics = {**metrics, **row_metrics(diag, num_steps)}
             results.append({'method': method, 'guidance_strength': strength, 'transform_type': transform_type,
                             **metrics})
             print(f"  method={method} gamma={strength} -> coherence accuracy {metrics['coherence_acc']:.3f}")
@@ -77,6 +84,7 @@ def main(argv=None):
     p.add_argument('--guidance_strengths', nargs='+', type=float, default=[0.0, 0.5, 1.0])
     p.add_argument('--num_samples', type=int, default=500)
     add_common_args(p, mc_default=256)
+    add_diagnostics_args(p, sampling=False)
     args = p.parse_args(argv)
 
     set_seed(args.seed)
@@ -107,7 +115,8 @@ def main(argv=None):
         return r
 
     results = run_sweep(fm_x, fm_y, make_ratio, classifier, args.guidance_methods, args.guidance_strengths,
-                        args.num_samples, args.num_steps, device, args.mc_batch_size, args.transform_type, solver=args.solver)
+                        args.num_samples, args.num_steps, device, args.mc_batch_size, args.transform_type, solver=args.solver,
+                        diagnostics=args.diagnostics)
     os.makedirs('outputs', exist_ok=True)
     out = 'outputs/evaluation_results.json'
     with open(out, 'w') as f:

@@ -28,6 +28,7 @@ from .models.svhn_classifier import MNISTClassifier32, SVHNClassifier
 from .models.unet_flexible import FlowMatchingUNetMNIST, FlowMatchingUNetSVHN
 from .sample_mnist_svhn import sample_bimodal_guided_mnist_svhn
 from .utils import load_checkpoint, set_seed
+from .utils.diagnostics import GuidanceDiagnostics, add_cli_args as add_diagnostics_args, row_metrics
 
 
 def evaluate_coherence(samples_mnist, samples_svhn, mnist_classifier, svhn_classifier, device):
@@ -65,9 +66,11 @@ def evaluate_conditional_coherence(condition, samples, given, mnist_classifier, 
 
 
 def run_sweep(fm_mnist, fm_svhn, make_ratio, mnist_classifier, svhn_classifier, methods, strengths,
-              num_samples, num_steps, device, mc_batch_size, sampler=sample_bimodal_guided_mnist_svhn, solver='euler'):
+              num_samples, num_steps, device, mc_batch_size, sampler=sample_bimodal_guided_mnist_svhn, solver='euler', diagnostics=False):
     """The reference's nested loop (:130-183). `make_ratio()` returns a fresh ratio estimator or None.
-    `solver` ('euler' | 'midpoint') goes to `sampler` as a keyword when it is not the default."""
+    `solver` ('euler' | 'midpoint') goes to `sampler` as a keyword when it is not the default.
+    `diagnostics`: every guided row also gets ess_mean, ess_min and w_max of the importance weights at step
+    int(0.3 * num_steps) (utils/diagnostics.py); without it the rows keep exactly their keys."""
     from ._lib import solver_id
     solver_id(solver)
     kw = {'solver': solver} if solver != 'euler' else {}
@@ -79,9 +82,12 @@ def run_sweep(fm_mnist, fm_svhn, make_ratio, mnist_classifier, svhn_classifier, 
             ratio = make_ratio() if method != 'none' else None
             if method != 'none' and ratio is None:
                 continue
+            diag = GuidanceDiagnostics() if diagnostics and method != 'none' else None
             xs, ys = sampler(fm_mnist, fm_svhn, ratio, method, strength, num_samples, num_steps, device,
-                             mc_batch_size, **kw)
+                             mc_batch_size, **kw, **({'diagnostics': diag} if diag is not None else {}))
             metrics = evaluate_coherence(xs, ys, mnist_classifier, svhn_classifier, device)
+            if diag is not None and diag.records is not None:
+                metrics = {**metrics, **row_metrics(diag, num_steps)}
             results.append({'method': method, 'guidance_strength': strength, 'experiment': 'mnist_svhn',
                             **metrics})
             print(f"  method={method} gamma={strength} -> coherence accuracy {metrics['coherence_acc']:.3f}")
@@ -103,7 +109,10 @@ def main(argv=None):
                    help="ODE solver of every sampler loop: 'midpoint' (explicit midpoint rule, second order) takes two network evaluations per step")
     p.add_argument('--sharded', action='store_true',
                    help='rows sharded over the ranks of a torch.distributed.run launch (one process per GPU, RCCL)')
+    add_diagnostics_args(p, sampling=False)
     args = p.parse_args(argv)
+    if args.diagnostics and args.sharded:
+        p.error('--diagnostics has no --sharded form')
 
     set_seed(args.seed)  # (every rank alike: the sharded sampler slices ONE noise set)
     if not torch.cuda.is_available():
@@ -143,7 +152,7 @@ def main(argv=None):
 
     results = run_sweep(fm_mnist, fm_svhn, make_ratio, mnist_clf, svhn_clf, args.guidance_methods,
                         args.guidance_strengths, args.num_samples, args.num_steps, device, args.mc_batch_size,
-                        sampler=sampler, solver=args.solver)
+                        sampler=sampler, solver=args.solver, diagnostics=args.diagnostics)
     if args.sharded:
         import torch.distributed as dist
         if dist.is_initialized():

@@ -15,6 +15,7 @@ from .models.flow_matching import FlowMatchingModel
 from .models.ratio_estimator import RatioEstimator
 from .models.unet import FlowMatchingUNet
 from .utils import load_checkpoint, set_seed
+from .utils.diagnostics import GuidanceDiagnostics, add_cli_args as add_diagnostics_args, report_diagnostics
 from .utils.flow_utils import sample_bimodal_guided
 from .utils.path_utils import get_checkpoint_path
 
@@ -46,7 +47,9 @@ def main(argv=None):
     p.add_argument('--guidance_strength', type=float, default=0.5)
     p.add_argument('--num_samples', type=int, default=64)
     add_common_args(p, mc_default=128)
+    add_diagnostics_args(p)
     args = p.parse_args(argv)
+    diag = GuidanceDiagnostics() if args.diagnostics or args.diagnostics_out else None
 
     set_seed(args.seed)
     print(f"Random seed: {args.seed}")
@@ -80,7 +83,9 @@ def main(argv=None):
 
     print(f"\nSampling {args.num_samples} pairs...")
     xs, ys = sample_bimodal_guided(fm_x, fm_y, ratio, args.guidance_method, args.guidance_strength,
-                                   args.num_samples, args.num_steps, device, args.mc_batch_size, solver=args.solver)
+                                   args.num_samples, args.num_steps, device, args.mc_batch_size, solver=args.solver,
+                                   diagnostics=diag)
+    report_diagnostics(diag, args.num_steps, args.diagnostics, args.diagnostics_out)
     os.makedirs('outputs', exist_ok=True)
     out = f"outputs/samples_{args.guidance_method}_gamma{args.guidance_strength}_{args.transform_type}.pt"
     torch.save({'x': xs.cpu(), 'y': ys.cpu()}, out)

@@ -13,15 +13,18 @@ import torch
 from .models.ratio_flexible import RatioEstimatorMNISTSVHN
 from .models.unet_flexible import FlowMatchingUNetMNIST, FlowMatchingUNetSVHN
 from .utils import load_checkpoint, set_seed
+from .utils.diagnostics import GuidanceDiagnostics, add_cli_args as add_diagnostics_args, report_diagnostics
 from .utils.flow_utils import paired_sampler, sample_conditional
 
 
 def sample_bimodal_guided_mnist_svhn(fm_mnist, fm_svhn, ratio_estimator=None, guidance_method='none',
                                      guidance_strength=0.0, num_samples=16, num_steps=100,
-                                     device='cuda', mc_batch_size=64, solver='euler'):
-    """Returns ``(samples_mnist [n,1,32,32], samples_svhn [n,3,32,32])`` on `device`."""
+                                     device='cuda', mc_batch_size=64, solver='euler', diagnostics=None):
+    """Returns ``(samples_mnist [n,1,32,32], samples_svhn [n,3,32,32])`` on `device`.  `diagnostics`: a
+    ``utils.diagnostics.GuidanceDiagnostics`` to fill (``paired_sampler``)."""
     return paired_sampler(fm_mnist, fm_svhn, ratio_estimator, guidance_method, guidance_strength,
-                          num_samples, num_steps, device, mc_batch_size, (1, 32, 32), (3, 32, 32), solver=solver)
+                          num_samples, num_steps, device, mc_batch_size, (1, 32, 32), (3, 32, 32), solver=solver,
+                          diagnostics=diagnostics)
 
 
 def load_condition(path, shape):
@@ -59,7 +62,11 @@ def main(argv=None):
                         "--mc_batch_size; with --guidance_method grad_log_ratio the one-sided gradient guidance, no MC set)")
     p.add_argument('--condition', type=str, default=None, metavar='FILE.npy|.pt',
                    help='condition images [B,1,32,32] (--given mnist) or [B,3,32,32] (--given svhn)')
+    add_diagnostics_args(p)
     args = p.parse_args(argv)
+    if (args.diagnostics or args.diagnostics_out) and args.sharded:
+        p.error('--diagnostics / --diagnostics_out have no --sharded form')
+    diag = GuidanceDiagnostics() if args.diagnostics or args.diagnostics_out else None
     if (args.given is None) != (args.condition is None):
         p.error('--given and --condition go together')
     if args.given and args.sharded:
@@ -109,7 +116,8 @@ def main(argv=None):
         method = 'grad_log_ratio' if args.guidance_method == 'grad_log_ratio' else 'mc_feng'
         out_t = sample_conditional(target, ratio, condition.to(device), 'x' if args.given == 'mnist' else 'y',
                                    args.num_steps, args.guidance_strength, args.mc_batch_size, device=device,
-                                   guidance_method=method, solver=args.solver)
+                                   guidance_method=method, solver=args.solver, diagnostics=diag)
+        report_diagnostics(diag, args.num_steps, args.diagnostics, args.diagnostics_out)
         os.makedirs('outputs/mnist_svhn', exist_ok=True)
         tag = '_grad_log_ratio' if method == 'grad_log_ratio' else ''
         out = f"outputs/mnist_svhn/samples_given_{args.given}{tag}_gamma{args.guidance_strength}.pt"
@@ -119,7 +127,9 @@ def main(argv=None):
 
     print(f"\nSampling {args.num_samples} pairs...")
     xs, ys = sampler(fm_mnist, fm_svhn, ratio, args.guidance_method, args.guidance_strength, args.num_samples,
-                     args.num_steps, device, args.mc_batch_size, **({'solver': args.solver} if args.solver != 'euler' else {}))
+                     args.num_steps, device, args.mc_batch_size, **({'solver': args.solver} if args.solver != 'euler' else {}),
+                     **({'diagnostics': diag} if diag is not None else {}))
+    report_diagnostics(diag, args.num_steps, args.diagnostics, args.diagnostics_out)
     if args.sharded:
         import torch.distributed as dist
         if dist.is_initialized():

@@ -17,6 +17,7 @@ import torch.nn.functional as F
 
 from .. import _engine
 from .._lib import solver_id as _solver_id
+from .diagnostics import check as _check_diagnostics
 
 
 def _device(device):
@@ -167,7 +168,8 @@ def train_flow_matching_epoch(model, dataloader, optimizer, schedule, device, mo
 
 
 def paired_sampler(fm_x, fm_y, ratio_estimator, guidance_method, guidance_strength, num_samples,
-                   num_steps, device, mc_batch_size, shape_x, shape_y, noise=None, verbose=True, solver='euler'):
+                   num_steps, device, mc_batch_size, shape_x, shape_y, noise=None, verbose=True, solver='euler',
+                   diagnostics=None):
     """Shared body of both paired samplers.
 
     `noise` = (x0, y0, mc_x0, mc_y0) overrides the generator draws (parity
@@ -175,7 +177,12 @@ def paired_sampler(fm_x, fm_y, ratio_estimator, guidance_method, guidance_streng
 
     `solver` = 'euler' | 'midpoint' integrates EVERY loop of the call (the MC pre-phase and the main loop) with that
     solver, `num_steps` steps each; the noise draws and their order do not depend on it.  'midpoint' needs U-Net nets.
+
+    `diagnostics` = a ``utils.diagnostics.GuidanceDiagnostics``: the main loop fills it with per-stage, per-sample
+    records (effective sample size, weight range, Z_bar, velocity and guidance norms), written on the device with no
+    host synchronisation.  The returned samples keep their bits.  Sharded launches (``distributed.py``) take none.
     """
+    _check_diagnostics(diagnostics)
     _engine._solver(solver, fm_x, fm_y)
     fm_x.eval()
     fm_y.eval()
@@ -219,14 +226,21 @@ def paired_sampler(fm_x, fm_y, ratio_estimator, guidance_method, guidance_streng
         # reference accepts only 'none' / 'mc_feng' and has no code for this mode; see rgfm_sample_pair_grad.
         if ratio_estimator.loss_type not in ("disc", "rulsif"):
             raise ValueError(f"Unknown loss_type: {ratio_estimator.loss_type}")
-        _engine.sample_pair_grad(fm_x, fm_y, ratio_estimator, x_t, y_t, num_steps, guidance_strength, solver=solver)
+        diag = None
+        if diagnostics is not None and num_samples:
+            diag = diagnostics._begin('grad_log_ratio', solver, num_steps, num_samples, dev)
+        _engine.sample_pair_grad(fm_x, fm_y, ratio_estimator, x_t, y_t, num_steps, guidance_strength, solver=solver, diag=diag)
         return x_t, y_t
-    _engine.sample_pair(fm_x, fm_y, x_t, y_t, mc_x1, mc_y1, mc_ratios, num_steps, guidance_strength, solver=solver)
+    diag = None
+    if diagnostics is not None and num_samples:
+        diag = diagnostics._begin('mc_feng' if guided else 'none', solver, num_steps, num_samples, dev)
+    _engine.sample_pair(fm_x, fm_y, x_t, y_t, mc_x1, mc_y1, mc_ratios, num_steps, guidance_strength, solver=solver, diag=diag)
     return x_t, y_t
 
 
 def sample_conditional(fm_target, ratio_estimator, condition, given='x', num_steps=100, guidance_strength=1.0,
-                       mc_batch_size=256, mc_samples=None, device=None, guidance_method='mc_feng', solver='euler'):
+                       mc_batch_size=256, mc_samples=None, device=None, guidance_method='mc_feng', solver='euler',
+                       diagnostics=None):
     """Partners for `condition` in the other modality: one sample of `fm_target`'s modality per condition image.
 
     ``given='x'``: `condition` is the estimator's x argument and the target is its y; ``given='y'`` the other way
@@ -248,10 +262,14 @@ def sample_conditional(fm_target, ratio_estimator, condition, given='x', num_ste
     ``solver='midpoint'`` integrates every loop of the call (the MC pre-phase too) with the explicit midpoint rule
     (``rgfm_sample_*_ode``); the draws and their order are those of ``'euler'``.
 
+    `diagnostics` = a ``utils.diagnostics.GuidanceDiagnostics``: filled by the guided loop (the target's fields in the
+    ``_x`` entries, the ``_y`` entries 0); the samples keep their bits.
+
     Returns the samples ``[len(condition), C, H, W]`` on the device.  U-Net targets only; ``--sharded`` launches have
     no conditional form yet.
     """
     from .._lib import RgfmError
+    _check_diagnostics(diagnostics)
     _solver_id(solver)
     if given not in ('x', 'y'):
         raise ValueError(f"given must be 'x' or 'y', got {given!r}")
@@ -270,7 +288,11 @@ def sample_conditional(fm_target, ratio_estimator, condition, given='x', num_ste
     if guidance_method == 'grad_log_ratio':
         s_t = torch.randn(condition.shape[0], *shape, device=dev)
         ctx = ratio_estimator._engine.cond_prepare(condition, given, shape)
-        return _engine.sample_cond_grad(fm_target, ratio_estimator, s_t, ctx, given, num_steps, guidance_strength, solver=solver)
+        diag = None
+        if diagnostics is not None and s_t.shape[0]:
+            diag = diagnostics._begin('grad_log_ratio', solver, num_steps, s_t.shape[0], dev)
+        return _engine.sample_cond_grad(fm_target, ratio_estimator, s_t, ctx, given, num_steps, guidance_strength, solver=solver,
+                                        diag=diag)
     if mc_samples is None:
         mc = torch.randn(mc_batch_size, *shape, device=dev)
         _engine.sample_single(fm_target, mc, num_steps, solver=solver)
@@ -281,19 +303,24 @@ def sample_conditional(fm_target, ratio_estimator, condition, given='x', num_ste
         ratios = ratio_estimator.cross_log_ratio(condition, mc).exp()
     else:
         ratios = ratio_estimator.cross_log_ratio(mc, condition).exp().T.contiguous()
-    return _engine.sample_cond(fm_target, s_t, mc, ratios, num_steps, guidance_strength, solver=solver)
+    diag = None
+    if diagnostics is not None and s_t.shape[0]:
+        diag = diagnostics._begin('mc_feng', solver, num_steps, s_t.shape[0], dev)
+    return _engine.sample_cond(fm_target, s_t, mc, ratios, num_steps, guidance_strength, solver=solver, diag=diag)
 
 
 def sample_bimodal_guided(fm_x, fm_y, ratio_estimator=None, guidance_method='none',
                           guidance_strength=0.0, num_samples=16, num_steps=100, device='cuda',
-                          mc_batch_size=64, solver='euler'):
+                          mc_batch_size=64, solver='euler', diagnostics=None):
     """Pairs of 1x28x28 images, optional mc_feng guidance (reference :178-375).
 
     Returns ``(samples_x [n,1,28,28], samples_y [n,1,28,28])`` on `device`.
     Guidance is silently off when `ratio_estimator` is None, skipped on step 0
     (t > 1e-3 test), and `guidance_strength` is not clamped -- all as in the
-    reference.  The reference's one-shot diagnostics print (:349-363) is not
-    reproduced.
+    reference.  The reference's one-shot diagnostics print (:349-363) is
+    available through `diagnostics`: pass a ``utils.diagnostics.GuidanceDiagnostics`` and read its
+    ``reference_block(int(0.3 * num_steps))`` (the same text) or its per-sample, per-stage records.
     """
     return paired_sampler(fm_x, fm_y, ratio_estimator, guidance_method, guidance_strength,
-                          num_samples, num_steps, device, mc_batch_size, (1, 28, 28), (1, 28, 28), solver=solver)
+                          num_samples, num_steps, device, mc_batch_size, (1, 28, 28), (1, 28, 28), solver=solver,
+                          diagnostics=diagnostics)
