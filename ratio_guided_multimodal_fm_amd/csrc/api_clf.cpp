@@ -1,8 +1,8 @@
 // api_clf.cpp -- the evaluation classifiers' handle and training pass: create / destroy / update_params, the forward
 // that keeps what the backward needs (BatchNorm on batch statistics, dropout behind fc1), the backward to the image and
 // to every parameter, the fused softmax cross-entropy and the three test hooks (C ABI: include/rgfm.h; kernels:
-// clf_train.hip, the convs and the 10-way head of unet_grad.hip, the BatchNorm statistics of ratio_train.hip and the
-// GEMM of fmnet_grad.hip for fc1).
+// block_train.hip behind the convs, clf_train.hip, the convs and the 10-way head of unet_grad.hip and the GEMM of
+// fmnet_grad.hip for fc1).
 //
 // The walk is the reference MNISTClassifier.forward (src/models/classifier.py:38-52), MNISTClassifier32.forward
 // (src/models/svhn_classifier.py:101-116) or SVHNClassifier.forward (:49-71) over NCHW tensors in the caller's
@@ -86,7 +86,9 @@ FgGemm fc1_fwd(const rgfm_clf* h, int n) { return fg_gemm_of(n, h->hidden, h->fl
 FgGemm fc1_dgrad(const rgfm_clf* h, int n) { return fg_gemm_of(n, h->flat, h->hidden, h->hidden, h->flat, h->flat, false); }
 FgGemm fc1_wgrad(const rgfm_clf* h, int n) { return fg_gemm_of(h->hidden, h->flat, n, h->hidden, h->flat, h->flat, false); }
 
-// every region starts on a 16-byte boundary of the workspace (the 16-byte accesses of clf_train.hip and fg_gemm_kernel)
+int norm_kind(const rgfm_clf* h) { return h->bn ? NORM_BATCH : NORM_NONE; }  // the conv blocks' norm (train_host.h)
+
+// every region starts on a 16-byte boundary of the workspace (the 16-byte accesses of block_train.hip, clf_train.hip and fg_gemm_kernel)
 CPlan plan_ct(const rgfm_clf* h, int n) {
   CPlan p;
   Cursor c;
@@ -100,24 +102,17 @@ CPlan plan_ct(const rgfm_clf* h, int n) {
     p.convs.push_back(r);
   }
   p.convs[0].Cin = h->in_ch, p.convs[0].S = h->size, p.convs[0].in = p.img;
-  plan_blocks(p.convs, n, take, h->bn ? NORM_BATCH : NORM_NONE, m);
+  plan_blocks(p.convs, n, take, norm_kind(h), m);
   p.u = take((size_t)n * h->hidden), p.a1 = take((size_t)n * h->hidden);
   p.saved = c.off;
   p.G0 = take(m.mx), p.G1 = take(m.mx);
   const FgGemm g = fc1_fwd(h, n);
   p.part = take(std::max(m.mx_part, (size_t)g.splits * g.M * g.N));
-  p.bnpart = take(m.mxC * RT_BN_SLICES * 3);
+  p.bnpart = take(m.mxC * BT_BN_SLICES * 3);
   p.m12 = take(m.mxC * 2);
   p.dA = take((size_t)n * h->hidden);
   p.total = c.off;
   return p;
-}
-
-CtAct act_of(const rgfm_clf* h, const TrainBlock& r, int n, const float* z, const float* W) {
-  CtAct a{};
-  a.z = z, a.B = n, a.C = r.C, a.H = a.W = r.S;
-  if (h->bn) a.mr = W + r.mr, a.gamma = h->params + r.nw, a.beta = h->params + r.nb;
-  return a;
 }
 
 int check_ct(const rgfm_clf* h, int n, const void* ws, size_t ws_bytes) {
@@ -191,12 +186,7 @@ extern "C" int rgfm_clf_forward_train(rgfm_clf* h, const float* x, float* logits
   for (const TrainBlock& r : p.convs) {
     float* z = W + (h->bn ? r.z : p.G0);
     run_fwd(conv_of(P, r, n), W + r.in, z, nullptr, nullptr, s);
-    if (h->bn && training)
-      launch_rt_bn_stats(z, n, r.C, r.S * r.S, W + p.bnpart, W + r.mr, bn_stats_out ? bn_stats_out + r.stats : nullptr, s);
-    else if (h->bn) launch_rt_bn_running(P + r.rm, P + r.rv, r.C, W + r.mr, s);
-    const CtAct a = act_of(h, r, n, z, W);
-    if (r.pool) launch_ct_act_pool(a, W + r.a, (unsigned char*)(W + r.choice), s);
-    else launch_ct_act(a, W + r.a, s);
+    block_tail(BT_RELU, r, norm_kind(h), n, training, z, P, W, p.bnpart, bn_stats_out, s);
   }
   FgGemm g = fc1_fwd(h, n);
   g.a = W + p.convs.back().a, g.b = P + h->f1w, g.bias = P + h->f1b, g.c = W + p.u, g.part = W + p.part;
@@ -236,15 +226,15 @@ extern "C" int rgfm_clf_backward(rgfm_clf* h, const float* dlogits, float* dx_ou
     const TrainBlock& r = p.convs[i];
     const float* gate = W + r.a;  // the gate the BatchNorm backward still has to apply, or null
     if (r.pool) {
-      launch_ct_unpool_gate(cur, (const unsigned char*)(W + r.choice), W + r.a, other, n * r.C, r.S, r.S, s);
+      launch_bt_unpool(BT_RELU, cur, (const unsigned char*)(W + r.choice), gate, other, n * r.C, r.S, r.S, s);
       std::swap(cur, other);
       gate = nullptr;
     } else if (!h->bn) {
       launch_ct_gate(cur, W + r.a, (size_t)n * r.C * r.S * r.S, s);
     }
     if (h->bn)
-      launch_ct_bn_bwd(act_of(h, r, n, W + r.z, W), cur, gate, hdr + HDR_TRAINING, W + p.bnpart, W + p.m12, D + r.nw,
-                       D + r.nb, s);
+      launch_bt_bn_bwd(BT_RELU, norm_act_of(r, NORM_BATCH, n, W + r.z, P, W), cur, gate, hdr + HDR_TRAINING, W + p.bnpart,
+                       W + p.m12, D + r.nw, D + r.nb, s);
     block_grads(conv_of(P, r, n), r, W, p.part, D, cur, other, i > 0 ? other : dx_out, s);
   }
   HIP_TRY(hipGetLastError());
@@ -268,7 +258,7 @@ extern "C" int rgfm_clf_pool_choice(rgfm_clf* h, const void* ws, int layer, int 
     return fail(RGFM_EINVAL, "conv block %d has no max-pool", layer);
   const CPlan p = plan_ct(h, n);
   const TrainBlock& r = p.convs[layer];
-  launch_rt_choice((const unsigned char*)((const float*)ws + r.choice), (size_t)n * r.C * r.So * r.So, out, nullptr);
+  launch_bt_choice((const unsigned char*)((const float*)ws + r.choice), (size_t)n * r.C * r.So * r.So, out, nullptr);
   HIP_TRY(hipGetLastError());
   return RGFM_OK;
 }

@@ -1,6 +1,7 @@
 // api_ratio_train.cpp -- training pass of the ratio-estimator handle: the forward that keeps what the backward needs
 // (BatchNorm on batch statistics, dropout in the score MLP), the backward to both images and to every parameter, and
-// the two test hooks (C ABI: include/rgfm.h; kernels: ratio_train.hip and the conv / Linear kernels of unet_grad.hip).
+// the two test hooks (C ABI: include/rgfm.h; kernels: block_train.hip behind the encoders' convs, ratio_train.hip, and
+// the conv / Linear kernels of unet_grad.hip).
 //
 // The walk is the reference RatioEstimatorMNISTSVHN.forward (src/models/ratio_flexible.py:211-364),
 // RatioEstimator.forward (src/models/ratio_estimator.py:67-135) or FlexibleRatioEstimator.forward
@@ -31,7 +32,7 @@ struct RPlan {
   size_t total;  // floats
 };
 
-bool is_bn(const rgfm_ratio* h) { return !h->gn_encoders(); }
+int norm_kind(const rgfm_ratio* h) { return h->gn_encoders() ? 8 : NORM_BATCH; }  // the encoders' norm (train_host.h)
 
 RPlan plan_rt(const rgfm_ratio* h, int n) {
   RPlan p;
@@ -52,7 +53,7 @@ RPlan plan_rt(const rgfm_ratio* h, int n) {
       e.convs.push_back(r);
     }
     e.convs[0].Cin = e.e->in_ch, e.convs[0].S = e.e->size, e.convs[0].in = e.img;
-    plan_blocks(e.convs, n, take, is_bn(h) ? NORM_BATCH : 8, m);
+    plan_blocks(e.convs, n, take, norm_kind(h), m);
     e.C = e.convs.back().C, e.S = e.convs.back().So;
     e.pooled = c.take((size_t)n * e.C);
     e.feat = c.take((size_t)n * F);
@@ -73,7 +74,7 @@ RPlan plan_rt(const rgfm_ratio* h, int n) {
   const size_t mxC = m.mxC;
   p.G0 = c.take(m.mx), p.G1 = c.take(m.mx);
   p.part = c.take(m.mx_part);
-  p.bnpart = c.take(mxC * RT_BN_SLICES * 3);
+  p.bnpart = c.take(mxC * BT_BN_SLICES * 3);
   p.m12 = c.take(mxC * 2);
   p.pg = c.take((size_t)n * std::max(mxC, width)), p.pb = c.take((size_t)n * std::max(mxC, width));
   p.dA = c.take((size_t)n * width), p.dU = c.take((size_t)n * width);
@@ -82,13 +83,6 @@ RPlan plan_rt(const rgfm_ratio* h, int n) {
   p.gpool = c.take((size_t)n * mxC);
   p.total = c.off;
   return p;
-}
-
-RtNorm norm_of(const rgfm_ratio* h, const TrainBlock& r, int n, const float* W) {
-  RtNorm a{};
-  a.z = W + r.z, a.mr = W + r.mr, a.gamma = h->params + r.nw, a.beta = h->params + r.nb;
-  a.B = n, a.C = r.C, a.H = a.W = r.S, a.groups = is_bn(h) ? 0 : 8;
-  return a;
 }
 
 int check_rt(const rgfm_ratio* h, int n, void* ws, size_t ws_bytes) {
@@ -124,13 +118,7 @@ extern "C" int rgfm_ratio_forward_train(rgfm_ratio* h, const float* x, const flo
                            hipMemcpyDeviceToDevice, s));
     for (const TrainBlock& r : e.convs) {
       run_fwd(conv_of(P, r, n), W + r.in, W + r.z, nullptr, nullptr, s);
-      if (!is_bn(h)) launch_ug_gn_stats(W + r.z, nullptr, r.C, 0, n, r.S * r.S, 8, W + r.mr, s);
-      else if (training)
-        launch_rt_bn_stats(W + r.z, n, r.C, r.S * r.S, W + p.bnpart, W + r.mr, bn_stats_out ? bn_stats_out + r.stats : nullptr, s);
-      else launch_rt_bn_running(P + r.rm, P + r.rv, r.C, W + r.mr, s);
-      const RtNorm a = norm_of(h, r, n, W);
-      if (r.pool) launch_rt_norm_act_pool(a, W + r.a, (unsigned char*)(W + r.choice), s);
-      else launch_rt_norm_act(a, W + r.a, s);
+      block_tail(BT_SILU, r, norm_kind(h), n, training, W + r.z, P, W, p.bnpart, bn_stats_out, s);
     }
     launch_rt_avgpool(W + e.convs.back().a, n * e.C, e.S * e.S, W + e.pooled, s);
     launch_ug_linear(W + e.pooled, P + e.e->fcw, P + e.e->fcb, W + e.feat, n, e.C, F, 0, s);
@@ -188,16 +176,16 @@ extern "C" int rgfm_ratio_backward(rgfm_ratio* h, const float* dscore, float* dx
     for (int i = (int)e.convs.size() - 1; i >= 0; --i) {
       const TrainBlock& r = e.convs[i];
       if (r.pool) {
-        launch_rt_unpool(cur, (const unsigned char*)(W + r.choice), other, n * r.C, r.S, r.S, s);
+        launch_bt_unpool(BT_SILU, cur, (const unsigned char*)(W + r.choice), nullptr, other, n * r.C, r.S, r.S, s);
         std::swap(cur, other);
       }
       // cur: gradient of silu(norm(z)) on the conv's raster -> gradient of z
-      const RtNorm a = norm_of(h, r, n, W);
-      if (is_bn(h)) {
-        launch_rt_bn_bwd(a, cur, hdr + HDR_TRAINING, W + p.bnpart, W + p.m12, D + r.nw, D + r.nb, s);
+      const BtBlock a = norm_act_of(r, norm_kind(h), n, W + r.z, P, W);
+      if (a.groups == 0) {
+        launch_bt_bn_bwd(BT_SILU, a, cur, nullptr, hdr + HDR_TRAINING, W + p.bnpart, W + p.m12, D + r.nw, D + r.nb, s);
       } else {
         UgAct g{};
-        g.s0 = a.z, g.C0 = r.C, g.B = n, g.HW = r.S * r.S, g.groups = 8, g.mr = a.mr, g.gamma = a.gamma, g.beta = a.beta;
+        g.s0 = a.z, g.C0 = r.C, g.B = n, g.HW = r.S * r.S, g.groups = a.groups, g.mr = a.mr, g.gamma = a.gamma, g.beta = a.beta;
         g.block = -1;
         launch_ug_gn_act_bwd(g, cur, other, nullptr, 0, 0, W + p.pg, W + p.pb, s);
         launch_ug_colsum(W + p.pg, n, r.C, D + r.nw, s);
@@ -217,7 +205,7 @@ extern "C" int rgfm_ratio_pool_choice(rgfm_ratio* h, const void* ws, int encoder
   int seen = 0;
   for (const TrainBlock& r : p.enc[encoder].convs)
     if (r.pool && seen++ == pool) {
-      launch_rt_choice((const unsigned char*)((const float*)ws + r.choice), (size_t)n * r.C * r.So * r.So, out, nullptr);
+      launch_bt_choice((const unsigned char*)((const float*)ws + r.choice), (size_t)n * r.C * r.So * r.So, out, nullptr);
       HIP_TRY(hipGetLastError());
       return RGFM_OK;
     }

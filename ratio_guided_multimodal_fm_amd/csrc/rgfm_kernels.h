@@ -524,31 +524,36 @@ void launch_ul_step(const float* src, const float* k, float c, size_t n, float* 
 void launch_ul_times(float* tt, int num_steps, int midpoint, hipStream_t s);
 void launch_ul_gauss_logp(const float* z, const float* A, int B, int d, float* logp, hipStream_t s);  // log N(z_b; 0, I) - A[b]
 
-// ---- training pass of the ratio estimators (ratio_train.hip; NCHW fp32)
-// A norm in front of a SiLU: z [B][C][H][W] and its (mean, rstd) pairs -- groups == 0: BatchNorm, mr[C][2];
-// groups > 0: GroupNorm, mr[B][groups][2].
-struct RtNorm {
+// ---- the tail of a training conv block (block_train.hip; NCHW fp32): norm, activation, optional 2x2 max-pool
+// A conv output z [B][C][H][W] in front of an activation, with a norm in between when mr, its (mean, rstd) pairs, is set:
+// y = gamma (z - mean) rstd + beta -- groups == 0: one pair per channel (BatchNorm), mr[C][2]; groups > 0: GroupNorm,
+// mr[B][groups][2] -- else y = z.
+struct BtBlock {
   const float* z;
-  const float* mr;
+  const float* mr;  // or null
   const float* gamma;
   const float* beta;
   int B, C, H, W, groups;
 };
-constexpr int RT_BN_SLICES = 16;  // batch slices of a per-channel BatchNorm reduction (partials per channel)
-// part: [C][RT_BN_SLICES][3] floats; stats (optional): [C][2] = (batch mean, unbiased batch variance)
-void launch_rt_bn_stats(const float* z, int B, int C, int HW, float* part, float* mr, float* stats, hipStream_t s);
-void launch_rt_bn_running(const float* rm, const float* rv, int C, float* mr, hipStream_t s);
-void launch_rt_norm_act(const RtNorm& a, float* out, hipStream_t s);
-void launch_rt_norm_act_pool(const RtNorm& a, float* out, unsigned char* choice, hipStream_t s);
-void launch_rt_unpool(const float* g, const unsigned char* choice, float* full, int BC, int H, int W, hipStream_t s);
-void launch_rt_choice(const unsigned char* choice, size_t n, float* out, hipStream_t s);
-// dout (gradient of silu(norm(z)), full raster) is replaced by dz; part: [C][RT_BN_SLICES][2], m12: [C][2]; training: a
-// device word, non-zero = batch statistics (their dependence on z is differentiated), zero = constants
-void launch_rt_bn_bwd(const RtNorm& a, float* dout, const unsigned* training, float* part, float* m12, float* dgamma, float* dbeta,
-                      hipStream_t s);
-// the step between the two passes of a BatchNorm backward (also clf_train.hip's): slices added in order; part: [C][slices][2]
-void launch_rt_bn_bwd_finalize(const float* part, int C, int slices, float inv_n, const unsigned* training, float* dgamma,
-                               float* dbeta, float* m12, hipStream_t s);
+enum BtActKind { BT_SILU, BT_RELU };  // the ratio estimators' encoders / the classifiers
+constexpr int BT_BN_SLICES = 16;  // batch slices of a per-channel BatchNorm reduction (partials per channel)
+// part: [C][BT_BN_SLICES][3] floats; stats (optional): [C][2] = (batch mean, unbiased batch variance)
+void launch_bt_bn_stats(const float* z, int B, int C, int HW, float* part, float* mr, float* stats, hipStream_t s);
+void launch_bt_bn_running(const float* rm, const float* rv, int C, float* mr, hipStream_t s);
+// out = act(y); with `choice` its 2x2 max-pool (floor division of odd rasters) and the window element taken per output
+void launch_bt_act(BtActKind act, const BtBlock& a, float* out, unsigned char* choice, hipStream_t s);
+// full (the conv's raster) = g (pooled raster) at the chosen element -- where `gate`, the pooled activation, is > 0 when
+// there is one -- else 0
+void launch_bt_unpool(BtActKind act, const float* g, const unsigned char* choice, const float* gate, float* full, int BC,
+                      int H, int W, hipStream_t s);
+void launch_bt_choice(const unsigned char* choice, size_t n, float* out, hipStream_t s);  // out = (float)choice
+// BatchNorm: dout (gradient of act(y) on the full raster; `saved` = the stored act(y) where the activation's gradient needs
+// it, null for SiLU and when dout is the gradient of y already) is replaced by dz; part: [C][BT_BN_SLICES][2], m12: [C][2];
+// training: a device word, non-zero = batch statistics (their dependence on z is differentiated), zero = constants
+void launch_bt_bn_bwd(BtActKind act, const BtBlock& a, float* dout, const float* saved, const unsigned* training, float* part,
+                      float* m12, float* dgamma, float* dbeta, hipStream_t s);
+
+// ---- training pass of the ratio estimators (ratio_train.hip; NCHW fp32): what block_train.hip does not cover
 void launch_rt_avgpool(const float* in, int rows, int n, float* out, hipStream_t s);
 void launch_rt_avgpool_bwd(const float* g, int rows, int n, float* din, hipStream_t s);
 void launch_rt_ln_act(const float* u, const float* gamma, const float* beta, int rows, int width, const unsigned* hdr,
@@ -573,28 +578,10 @@ struct FgGemm {
 };
 void launch_fg_gemm(FgGemm g, bool a_kmajor, bool b_kmajor, hipStream_t s);
 
-// ---- training pass of the evaluation classifiers (clf_train.hip; NCHW fp32)
-// A conv output z [B][C][H][W] in front of a ReLU, with BatchNorm in between when mr (per channel (mean, rstd)) is set:
-// y = gamma (z - mean) rstd + beta, else y = z.
-struct CtAct {
-  const float* z;
-  const float* mr;  // [C][2] or null
-  const float* gamma;
-  const float* beta;
-  int B, C, H, W;
-};
+// ---- training pass of the evaluation classifiers (clf_train.hip; NCHW fp32): what block_train.hip does not cover
 constexpr int CT_MAX_CLASSES = 32;
-void launch_ct_act(const CtAct& a, float* out, hipStream_t s);                              // out = relu(y)
-void launch_ct_act_pool(const CtAct& a, float* out, unsigned char* choice, hipStream_t s);  // + 2x2 max-pool, element taken
-// full (the conv's raster) = g (pooled raster) at the chosen element where the pooled activation `act` > 0, else 0
-void launch_ct_unpool_gate(const float* g, const unsigned char* choice, const float* act, float* full, int BC, int H,
-                           int W, hipStream_t s);
 void launch_ct_gate(float* g, const float* act, size_t n, hipStream_t s);          // in place: g where act > 0, else 0
 void launch_ct_gate_out(const float* act, size_t n, float* out, hipStream_t s);    // out = act > 0 ? 1 : 0
-// dout (gradient of relu(y) on the full raster; `act` = relu(y), or null when dout is the gradient of y already) is
-// replaced by dz; part: [C][RT_BN_SLICES][2], m12: [C][2]; training: as launch_rt_bn_bwd
-void launch_ct_bn_bwd(const CtAct& a, float* dout, const float* act, const unsigned* training, float* part, float* m12,
-                      float* dgamma, float* dbeta, hipStream_t s);
 // out = drop(relu(u)) / in place g <- drop(g) where u > 0: Dropout layer 0 of the header hdr (launch_ug_header)
 void launch_ct_relu_drop(const float* u, size_t n, const unsigned* hdr, float* out, hipStream_t s);
 void launch_ct_relu_drop_bwd(const float* u, float* g, size_t n, const unsigned* hdr, hipStream_t s);

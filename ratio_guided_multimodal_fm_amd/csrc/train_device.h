@@ -1,6 +1,9 @@
-// train_device.h -- device helpers shared by the training kernels (unet_grad.hip, ratio_train.hip, fmnet_grad.hip, clf_train.hip).
+// train_device.h -- helpers shared by the training kernels (unet_grad.hip, fmnet_grad.hip, block_train.hip,
+// ratio_train.hip, clf_train.hip): SiLU, the MFMA GEMM core, the dropout hash, the block sum, and the V = 1 / 4 access
+// of the memory-bound elementwise kernels with the host-side checks their launchers make.
 #pragma once
 #include <cstdint>
+#include <initializer_list>
 
 #include "rgfm_device.h"
 
@@ -68,5 +71,28 @@ __device__ __forceinline__ void ug_drop_params(const unsigned* hdr, float& p, ui
   p = 0.f, seed = 0;
   if (hdr) p = __uint_as_float(hdr[0]), seed = (uint64_t)hdr[1] | ((uint64_t)hdr[2] << 32);
 }
+
+// V consecutive floats per thread: one 16-byte access at V = 4
+template <int V>
+__device__ __forceinline__ void vec_load(const float* p, float (&v)[V]) {
+  if constexpr (V == 4) {
+    const f32x4 t = *reinterpret_cast<const f32x4*>(p);
+    v[0] = t.x, v[1] = t.y, v[2] = t.z, v[3] = t.w;
+  } else {
+    v[0] = *p;
+  }
+}
+template <int V>
+__device__ __forceinline__ void vec_store(float* p, const float (&v)[V]) {
+  if constexpr (V == 4) *reinterpret_cast<f32x4*>(p) = f32x4{v[0], v[1], v[2], v[3]};
+  else *p = v[0];
+}
+static bool vec_aligned(std::initializer_list<const void*> ps) {
+  for (const void* p : ps)
+    if (reinterpret_cast<uintptr_t>(p) % 16 != 0) return false;
+  return true;
+}
+// grid-stride launch of 256-thread workgroups over `groups` work items, capped at 4096 workgroups
+static dim3 vec_grid(size_t groups) { return dim3((unsigned)std::max<size_t>(1, std::min<size_t>((groups + 255) / 256, 4096))); }
 
 }  // namespace rgfm

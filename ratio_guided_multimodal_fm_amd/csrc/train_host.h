@@ -1,6 +1,7 @@
 // train_host.h -- host-side pieces the four training passes share (api_train.cpp, api_fmnet_train.cpp,
 // api_ratio_train.cpp, api_clf.cpp): the argument checks, the saved state's header, the dense-layer descriptor, and the
-// plan of a stack of conv blocks (conv -> norm -> activation -> optional 2x2 max-pool) with the tail of its backward.
+// plan of a stack of conv blocks (conv -> norm -> activation -> optional 2x2 max-pool) with the tail of a block's forward
+// (block_train.hip) and of its backward.
 #pragma once
 #include "rgfm_host.h"
 
@@ -82,6 +83,26 @@ void plan_blocks(std::vector<TrainBlock>& blocks, int n, Take take, int norm, Tr
     wgrad_split(u);
     m.mx_part = std::max(m.mx_part, (size_t)u.splits * r.C * r.Cin * 9);
   }
+}
+
+// z (the conv's output) in front of the block's norm and activation
+inline BtBlock norm_act_of(const TrainBlock& r, int norm, int n, const float* z, const float* params, const float* W) {
+  BtBlock a{};
+  a.z = z, a.B = n, a.C = r.C, a.H = a.W = r.S, a.groups = std::max(norm, 0);
+  if (norm != NORM_NONE) a.mr = W + r.mr, a.gamma = params + r.nw, a.beta = params + r.nb;
+  return a;
+}
+
+// The tail of a block's forward behind the conv: the norm's (mean, rstd) pairs -- of the batch (BatchNorm in training
+// mode, through bnpart, with the pairs bn_stats_out asks for), of the running statistics, or per (sample, group) -- then
+// the activation, with the pool where the block has one.
+inline void block_tail(BtActKind act, const TrainBlock& r, int norm, int n, bool training, const float* z, const float* params,
+                       float* W, size_t bnpart, float* bn_stats_out, hipStream_t s) {
+  if (norm > 0) launch_ug_gn_stats(z, nullptr, r.C, 0, n, r.S * r.S, norm, W + r.mr, s);
+  else if (norm == NORM_BATCH && training)
+    launch_bt_bn_stats(z, n, r.C, r.S * r.S, W + bnpart, W + r.mr, bn_stats_out ? bn_stats_out + r.stats : nullptr, s);
+  else if (norm == NORM_BATCH) launch_bt_bn_running(params + r.rm, params + r.rv, r.C, W + r.mr, s);
+  launch_bt_act(act, norm_act_of(r, norm, n, z, params, W), W + r.a, r.pool ? (unsigned char*)(W + r.choice) : nullptr, s);
 }
 
 // The tail of a block's backward.  cur: the gradient of the conv's output.  The weight and bias gradients go into D; the

@@ -155,7 +155,7 @@ RATIO_SWEEP = {
     # 64 pixels); three input channels.  y: 9x9 = 81 pixels as a single one-sample tile, 9 -> 4 -> 2 -> 1
     "s64": (3, 64, 1, 9, 192, 384, 2, 2910),
     # x: odd at every level with ragged tiles, 63 (last tile 3 rows) -> 31 -> 15 -> 7: every pool drops a row and a
-    # column (grad_act_kernel<true> with its memset, pool2 / rt_norm_act_pool / rt_unpool on odd maps).  y: 33 (5 tiles
+    # column (grad_act_kernel<true> with its memset, pool2 / bt_act_pool / bt_unpool on odd maps).  y: 33 (5 tiles
     # of 7 rows, the last with 5) -> 16 -> 8 -> 4; four input channels
     "s63": (2, 63, 4, 33, 320, 640, 2, 2918),
     # x: 48 (last tile 3 rows), 24 (3 tiles), 12, 6.  y: 40 (last tile 4 rows), 20, 10 (100-pixel one-sample tile), 5
