@@ -68,27 +68,6 @@ int single_loop(rgfm_unet* h, float* x_inout, int batch, int num_steps, int step
 }
 
 // ---- two unguided integrations at once (the MC pre-phase of the paired sampler)
-// Conv FLOPs of one evaluation of one row, from the descriptor's layer list (the walk of UNetRun::run).
-double row_flops(const rgfm_unet* h) {
-  const rgfm_unet_desc& d = h->d;
-  auto res = [](const ResW& r, int S) {
-    return 2.0 * S * S * r.cout * (9.0 * r.cin + 9.0 * r.cout + (r.has_skip ? r.cin : 0));
-  };
-  int S = d.img_size;
-  double f = 2.0 * S * S * 9.0 * d.in_channels * (h->mc + h->final_ch);
-  size_t e = 0, di = 0;
-  for (int l = 0; l < d.num_levels; ++l) {
-    for (int r = 0; r < d.num_res_blocks; ++r) f += res(h->enc[e++], S);
-    if (l < d.num_levels - 1) S /= 2, f += 2.0 * S * S * 9.0 * h->down[l].cin * h->down[l].cout;
-  }
-  f += res(h->mid[0], S) + res(h->mid[1], S);
-  for (int l = d.num_levels - 1; l >= 0; --l) {
-    for (int i = 0; i < d.num_res_blocks + 1; ++i) f += res(h->dec[di++], S);
-    if (l > 0) S *= 2, f += 2.0 * S * S * 9.0 * h->up[d.num_levels - 1 - l].cin * h->up[d.num_levels - 1 - l].cout;
-  }
-  return f;
-}
-
 // The workspace: the first net's single-loop layout, then the second's (its size: the sum of the two single sizes).
 // The two chains are independent and carry unequal work (the benchmark's pair: 1 : 2.8).  x runs on the caller's stream,
 // y on the device's side stream, forked from and joined back into the caller's.  Enqueued one whole chain after the
@@ -118,7 +97,8 @@ int two_loop(rgfm_unet* hx, rgfm_unet* hy, float* x_inout, float* y_inout, int b
   if (!ds) return fail(RGFM_EINVAL, "no handle has been created on the current device");
   hipStream_t caller = (hipStream_t)stream;
   const bool overlap = g_modes.overlap;  // (RGFM_OVERLAP=0: both chains on the caller's stream)
-  const double wx = row_flops(hx) * batch_x, wy = row_flops(hy) * batch_y;
+  // (conv FLOPs of one evaluation of one row, from each plan's op list: unet_plan.h)
+  const double wx = unet_row_flops(*hx) * batch_x, wy = unet_row_flops(*hy) * batch_y;
   hipStream_t sy = overlap ? ds->side : caller;
   NetChain &lng = wx > wy ? cx : cy, &sht = wx > wy ? cy : cx;
   // Whatever has been enqueued on the side stream must be joined into the caller's on every exit path.

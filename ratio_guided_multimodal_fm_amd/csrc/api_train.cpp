@@ -3,8 +3,9 @@
 // same two walks, the likelihood path: J^T u by the data-only reverse walk (rgfm_unet_vjp), the Hutchinson divergence
 // (rgfm_unet_divergence) and the reverse-time augmented ODE loop (rgfm_unet_log_prob; kernels: unet_logp.hip).
 //
-// The walk is the reference FlexibleUNet.forward (src/models/unet_flexible.py:203-261) over NCHW tensors in the
-// caller's workspace, laid out by plan_train: first the SAVED state (dropout header, x, the time path, every tensor
+// The walk is the op list of the handle's plan (unet_plan.h: the reference FlexibleUNet.forward,
+// src/models/unet_flexible.py:203-261) over NCHW tensors in the caller's workspace, laid out by plan_train, which adds
+// to each op only what the training pass owns: first the SAVED state (dropout header, x, the time path, every tensor
 // the walk produces, and per ResBlock the group statistics of both norms, the time projection and conv1's output),
 // then the backward's SCRATCH (one gradient buffer per produced tensor and a few transient maps).
 #include "sampler_host.h"
@@ -17,27 +18,19 @@ struct TTensor {  // a produced tensor: float offset into the workspace, channel
   int C, S;
 };
 
-enum { OP_IN, OP_RES, OP_DOWN, OP_UP, OP_OUT };
-
-struct TOp {
-  int kind;
-  const ResW* r = nullptr;
-  const ConvW* cw = nullptr;  // Downsample / Upsample conv (the input and output convs: TrainPlan)
-  int in0 = -1, in1 = -1, out = -1;
-  int S = 0;       // spatial size of the input
-  int block = -1;  // ResBlock index in walk order (the dropout mask's block id)
+struct TOp {  // an op of the plan + (ResBlocks) the workspace offsets of what the forward saves for the backward
+  const UOp* u;
   size_t mr1 = 0, temb = 0, h1 = 0, mr2 = 0;
 };
 
 struct TrainPlan {
-  std::vector<TTensor> T;
+  std::vector<TTensor> T;  // by the plan's tensor ids
   std::vector<TOp> ops;
   std::vector<size_t> dT;  // gradient buffer of T[i]
   size_t hdr, x0, emb0, e1, emb, mro, saved;
   size_t dT_begin, dT_end, A, R, G, DH, part, pg, pb, dtemb, dsemb, de1;
   size_t total;  // floats
   ConvW in_conv, out_conv;
-  int nblocks = 0;
 };
 
 int groups_of(int C) { return std::min(8, C); }
@@ -54,78 +47,39 @@ TrainPlan plan_train(const rgfm_unet* h, int B) {
   p.emb0 = c.take((size_t)B * mc);
   p.e1 = c.take((size_t)B * temb);
   p.emb = c.take((size_t)B * temb);
-  auto tensor = [&](int C, int S) {
-    p.T.push_back({c.take((size_t)B * C * S * S), C, S});
-    big(C, S);
-    return (int)p.T.size() - 1;
-  };
-  auto part_of = [&](int Cout, int Cin, int taps, int So) {
+  auto part_of = [&](const ConvW& w, int So) {
     UgConv u{};
-    u.Cout = Cout, u.Cin = Cin, u.taps = taps, u.B = B, u.Ho = u.Wo = So;
+    u.Cout = w.cout, u.Cin = w.cin, u.taps = w.taps, u.B = B, u.Ho = u.Wo = So;
     wgrad_split(u);
-    mx_part = std::max(mx_part, (size_t)u.splits * Cout * Cin * taps);
+    mx_part = std::max(mx_part, (size_t)u.splits * w.cout * w.cin * w.taps);
   };
   p.in_conv.w_raw = h->icw, p.in_conv.b = h->icb, p.in_conv.cin = d.in_channels, p.in_conv.cout = mc;
   p.out_conv.w_raw = h->ocw, p.out_conv.b = h->ocb, p.out_conv.cin = h->final_ch, p.out_conv.cout = d.in_channels;
-  int S = S0;
-  TOp in{OP_IN};
-  in.S = S, in.out = tensor(mc, S);
-  p.ops.push_back(in);
-  part_of(mc, d.in_channels, 9, S);
-  int cur = in.out;
-  std::vector<int> skips{cur};
-  auto res = [&](const ResW& r, int a, int b) {
-    TOp o{OP_RES};
-    o.r = &r, o.in0 = a, o.in1 = b, o.S = S, o.block = p.nblocks++;
-    const int cin = r.cin, cout = r.cout;
-    o.mr1 = c.take((size_t)B * groups_of(cin) * 2);
-    o.temb = c.take((size_t)B * cout);
-    o.h1 = c.take((size_t)B * cout * S * S);
-    o.mr2 = c.take((size_t)B * groups_of(cout) * 2);
-    o.out = tensor(cout, S);
-    big(cin, S);
-    mxC = std::max(mxC, (size_t)cin);
-    part_of(cout, cin, 9, S);
-    part_of(cout, cout, 9, S);
-    if (r.has_skip) part_of(cout, cin, 1, S);
+  for (const UOp& u : h->ops) {
+    TOp o{&u};
+    const int S = u.S;
+    if (u.kind == UOP_RES) {
+      const ResW& r = h->res[u.idx];
+      o.mr1 = c.take((size_t)B * groups_of(r.cin) * 2);
+      o.temb = c.take((size_t)B * r.cout);
+      o.h1 = c.take((size_t)B * r.cout * S * S);
+      o.mr2 = c.take((size_t)B * groups_of(r.cout) * 2);
+      big(r.cin, S);
+      mxC = std::max(mxC, (size_t)r.cin);
+      part_of(r.c1, S), part_of(r.c2, S);
+      if (r.has_skip) part_of(r.sk, S);
+    }
+    if (u.out >= 0) {  // (the ops produce the plan's tensors in id order)
+      const UTensor& t = h->tensors[u.out];
+      p.T.push_back({c.take((size_t)B * t.C * t.S * t.S), t.C, t.S});
+      big(t.C, t.S);
+    }
+    if (u.kind == UOP_IN) part_of(p.in_conv, S);
+    if (u.kind == UOP_DOWN) part_of(h->down[u.idx], S / 2);
+    if (u.kind == UOP_UP) part_of(h->up[u.idx], 2 * S);
+    if (u.kind == UOP_OUT) part_of(p.out_conv, S);
     p.ops.push_back(o);
-    return o.out;
-  };
-  size_t ei = 0, di = 0, ui = 0;
-  for (int l = 0; l < d.num_levels; ++l) {
-    for (int i = 0; i < d.num_res_blocks; ++i) {
-      cur = res(h->enc[ei++], cur, -1);
-      skips.push_back(cur);
-    }
-    if (l < d.num_levels - 1) {
-      TOp o{OP_DOWN};
-      o.cw = &h->down[l], o.in0 = cur, o.S = S, o.out = tensor(o.cw->cout, S / 2);
-      part_of(o.cw->cout, o.cw->cin, 9, S / 2);
-      p.ops.push_back(o);
-      cur = o.out, S /= 2;
-      skips.push_back(cur);
-    }
   }
-  cur = res(h->mid[0], cur, -1);
-  cur = res(h->mid[1], cur, -1);
-  for (int l = d.num_levels - 1; l >= 0; --l) {
-    for (int i = 0; i < d.num_res_blocks + 1; ++i) {
-      cur = res(h->dec[di++], cur, skips.back());
-      skips.pop_back();
-    }
-    if (l > 0) {
-      TOp o{OP_UP};
-      o.cw = &h->up[ui++], o.in0 = cur, o.S = S, o.out = tensor(o.cw->cout, 2 * S);
-      big(o.cw->cout, 2 * S);
-      part_of(o.cw->cout, o.cw->cin, 9, 2 * S);
-      p.ops.push_back(o);
-      cur = o.out, S *= 2;
-    }
-  }
-  TOp out{OP_OUT};
-  out.in0 = cur, out.S = S;
-  p.ops.push_back(out);
-  part_of(d.in_channels, h->final_ch, 9, S);
   mxC = std::max(mxC, (size_t)h->final_ch);
   p.mro = c.take((size_t)B * groups_of(h->final_ch) * 2);
   p.saved = c.off;
@@ -186,37 +140,38 @@ int forward_walk(rgfm_unet* h, const float* x, bool keep_x, const float* t_dev, 
   launch_ug_linear(W + p.emb0, P + h->te0w, P + h->te0b, W + p.e1, B, mc, temb, 0, s);
   launch_ug_linear(W + p.e1, P + h->te2w, P + h->te2b, W + p.emb, B, temb, temb, 1, s);
   for (const TOp& o : p.ops) {
-    const int S = o.S, HW = S * S;
-    switch (o.kind) {
-      case OP_IN:
-        run_fwd(conv_of(h, p.in_conv, B, S, 0), x_in, W + p.T[o.out].off, nullptr, nullptr, s);
+    const UOp& u = *o.u;
+    const int S = u.S, HW = S * S;
+    switch (u.kind) {
+      case UOP_IN:
+        run_fwd(conv_of(h, p.in_conv, B, S, 0), x_in, W + p.T[u.out].off, nullptr, nullptr, s);
         break;
-      case OP_DOWN:
-        run_fwd(conv_of(h, *o.cw, B, S, 1), W + p.T[o.in0].off, W + p.T[o.out].off, nullptr, nullptr, s);
+      case UOP_DOWN:
+        run_fwd(conv_of(h, h->down[u.idx], B, S, 1), W + p.T[u.in0].off, W + p.T[u.out].off, nullptr, nullptr, s);
         break;
-      case OP_UP:
-        run_fwd(conv_of(h, *o.cw, B, S, 2), W + p.T[o.in0].off, W + p.T[o.out].off, nullptr, nullptr, s);
+      case UOP_UP:
+        run_fwd(conv_of(h, h->up[u.idx], B, S, 2), W + p.T[u.in0].off, W + p.T[u.out].off, nullptr, nullptr, s);
         break;
-      case OP_OUT: {
-        const TTensor& t = p.T[o.in0];
+      case UOP_OUT: {
+        const TTensor& t = p.T[u.in0];
         launch_ug_gn_stats(W + t.off, nullptr, t.C, 0, B, HW, groups_of(t.C), W + p.mro, s);
         launch_ug_gn_act(act_of(W + t.off, nullptr, t.C, 0, B, HW, W + p.mro, P + h->onw, P + h->onb, nullptr, -1,
                                 W + p.A), s);
         run_fwd(conv_of(h, p.out_conv, B, S, 0), W + p.A, v_out, nullptr, nullptr, s);
         break;
       }
-      case OP_RES: {
-        const ResW& r = *o.r;
-        const float* s0 = W + p.T[o.in0].off;
-        const float* s1 = o.in1 >= 0 ? W + p.T[o.in1].off : nullptr;
-        const int C0 = p.T[o.in0].C, C1 = o.in1 >= 0 ? p.T[o.in1].C : 0;
-        float* out = W + p.T[o.out].off;
+      case UOP_RES: {
+        const ResW& r = h->res[u.idx];
+        const float* s0 = W + p.T[u.in0].off;
+        const float* s1 = u.in1 >= 0 ? W + p.T[u.in1].off : nullptr;
+        const int C0 = p.T[u.in0].C, C1 = u.in1 >= 0 ? p.T[u.in1].C : 0;
+        float* out = W + p.T[u.out].off;
         launch_ug_gn_stats(s0, s1, C0, C1, B, HW, groups_of(r.cin), W + o.mr1, s);
-        launch_ug_gn_act(act_of(s0, s1, C0, C1, B, HW, W + o.mr1, P + r.n1w, P + r.n1b, nullptr, o.block, W + p.A), s);
+        launch_ug_gn_act(act_of(s0, s1, C0, C1, B, HW, W + o.mr1, P + r.n1w, P + r.n1b, nullptr, u.block, W + p.A), s);
         launch_ug_linear(W + p.emb, P + r.tw, P + r.tb, W + o.temb, B, temb, r.cout, 1, s);
         run_fwd(conv_of(h, r.c1, B, S, 0), W + p.A, W + o.h1, W + o.temb, nullptr, s);
         launch_ug_gn_stats(W + o.h1, nullptr, r.cout, 0, B, HW, groups_of(r.cout), W + o.mr2, s);
-        launch_ug_gn_act(act_of(W + o.h1, nullptr, r.cout, 0, B, HW, W + o.mr2, P + r.n2w, P + r.n2b, hdr, o.block,
+        launch_ug_gn_act(act_of(W + o.h1, nullptr, r.cout, 0, B, HW, W + o.mr2, P + r.n2w, P + r.n2b, hdr, u.block,
                                 W + p.A), s);
         const float* xr = s0;  // the block input as the skip path sees it (raw)
         if (C1) {
@@ -269,52 +224,55 @@ int backward_walk(rgfm_unet* h, const float* dv, float* dx_out, float* D, int ba
   };
   for (auto it = p.ops.rbegin(); it != p.ops.rend(); ++it) {
     const TOp& o = *it;
-    const int S = o.S, HW = S * S;
-    switch (o.kind) {
-      case OP_OUT: {
-        const TTensor& t = p.T[o.in0];
+    const UOp& u = *o.u;
+    const int S = u.S, HW = S * S;
+    switch (u.kind) {
+      case UOP_OUT: {
+        const TTensor& t = p.T[u.in0];
         const UgAct a = act_of(W + t.off, nullptr, t.C, 0, B, HW, W + p.mro, P + h->onw, P + h->onb, nullptr, -1,
                                W + p.A);
         recompute(a);
         const UgConv c = conv_of(h, p.out_conv, B, S, 0);
         wgrad(c, dv, W + p.A, h->ocw, h->ocb);
         run_dgrad(c, dv, W + p.G, nullptr, t.C, 0, s);
-        launch_ug_gn_act_bwd(a, W + p.G, W + p.dT[o.in0], nullptr, 1, 0, pg, pb, s);
+        launch_ug_gn_act_bwd(a, W + p.G, W + p.dT[u.in0], nullptr, 1, 0, pg, pb, s);
         norm_grads(t.C, h->onw, h->onb);
         break;
       }
-      case OP_UP: {
-        const UgConv c = conv_of(h, *o.cw, B, S, 2);
-        const float* dy = W + p.dT[o.out];
-        wgrad(c, dy, W + p.T[o.in0].off, o.cw->w_raw, o.cw->b);
+      case UOP_UP: {
+        const ConvW& w = h->up[u.idx];
+        const UgConv c = conv_of(h, w, B, S, 2);
+        const float* dy = W + p.dT[u.out];
+        wgrad(c, dy, W + p.T[u.in0].off, w.w_raw, w.b);
         run_dgrad(c, dy, W + p.G, nullptr, c.Cin, 0, s);  // gradient of the upsampled map (2S x 2S)
-        launch_ug_pool2_add(W + p.G, W + p.dT[o.in0], B * c.Cin, S, S, s);
+        launch_ug_pool2_add(W + p.G, W + p.dT[u.in0], B * c.Cin, S, S, s);
         break;
       }
-      case OP_DOWN: {
-        const UgConv c = conv_of(h, *o.cw, B, S, 1);
-        const float* dy = W + p.dT[o.out];
-        wgrad(c, dy, W + p.T[o.in0].off, o.cw->w_raw, o.cw->b);
-        run_dgrad(c, dy, W + p.dT[o.in0], nullptr, c.Cin, 1, s);
+      case UOP_DOWN: {
+        const ConvW& w = h->down[u.idx];
+        const UgConv c = conv_of(h, w, B, S, 1);
+        const float* dy = W + p.dT[u.out];
+        wgrad(c, dy, W + p.T[u.in0].off, w.w_raw, w.b);
+        run_dgrad(c, dy, W + p.dT[u.in0], nullptr, c.Cin, 1, s);
         break;
       }
-      case OP_IN: {
+      case UOP_IN: {
         const UgConv c = conv_of(h, p.in_conv, B, S, 0);
-        const float* dy = W + p.dT[o.out];
+        const float* dy = W + p.dT[u.out];
         wgrad(c, dy, W + p.x0, h->icw, h->icb);
         if (dx_out) run_dgrad(c, dy, dx_out, nullptr, c.Cin, 0, s);
         break;
       }
-      case OP_RES: {
-        const ResW& r = *o.r;
-        const float* s0 = W + p.T[o.in0].off;
-        const float* s1 = o.in1 >= 0 ? W + p.T[o.in1].off : nullptr;
-        float* d0 = W + p.dT[o.in0];
-        float* d1 = o.in1 >= 0 ? W + p.dT[o.in1] : nullptr;
-        const int C0 = p.T[o.in0].C, C1 = o.in1 >= 0 ? p.T[o.in1].C : 0;
-        const float* dout = W + p.dT[o.out];
+      case UOP_RES: {
+        const ResW& r = h->res[u.idx];
+        const float* s0 = W + p.T[u.in0].off;
+        const float* s1 = u.in1 >= 0 ? W + p.T[u.in1].off : nullptr;
+        float* d0 = W + p.dT[u.in0];
+        float* d1 = u.in1 >= 0 ? W + p.dT[u.in1] : nullptr;
+        const int C0 = p.T[u.in0].C, C1 = u.in1 >= 0 ? p.T[u.in1].C : 0;
+        const float* dout = W + p.dT[u.out];
         // conv2 and norm2 (+ dropout)
-        const UgAct a2 = act_of(W + o.h1, nullptr, r.cout, 0, B, HW, W + o.mr2, P + r.n2w, P + r.n2b, hdr, o.block,
+        const UgAct a2 = act_of(W + o.h1, nullptr, r.cout, 0, B, HW, W + o.mr2, P + r.n2w, P + r.n2b, hdr, u.block,
                                 W + p.A);
         recompute(a2);
         const UgConv c2 = conv_of(h, r.c2, B, S, 0);
@@ -328,7 +286,7 @@ int backward_walk(rgfm_unet* h, const float* dv, float* dx_out, float* D, int ba
           launch_ug_linear_dgrad(W + p.dtemb, P + r.tw, B, temb, r.cout, W + p.dsemb, 1, s);
         }
         // conv1 and norm1
-        const UgAct a1 = act_of(s0, s1, C0, C1, B, HW, W + o.mr1, P + r.n1w, P + r.n1b, nullptr, o.block, W + p.A);
+        const UgAct a1 = act_of(s0, s1, C0, C1, B, HW, W + o.mr1, P + r.n1w, P + r.n1b, nullptr, u.block, W + p.A);
         recompute(a1);
         const UgConv c1 = conv_of(h, r.c1, B, S, 0);
         wgrad(c1, W + p.DH, W + p.A, r.c1.w_raw, r.c1.b);
@@ -517,12 +475,11 @@ extern "C" int rgfm_unet_log_prob(rgfm_unet* h, const float* x, const float* eps
 extern "C" int rgfm_unet_dropout_mask(rgfm_unet* h, int block, uint64_t seed, float p_drop, int batch, float* out) {
   if (!h || !out || batch < 1) return fail(RGFM_EINVAL, "bad argument");
   if (int rc = check_p_drop(p_drop)) return rc;
-  const TrainPlan p = plan_train(h, batch);
-  for (const TOp& o : p.ops)
-    if (o.kind == OP_RES && o.block == block) {
-      launch_ug_mask(out, (size_t)batch * o.r->cout * o.S * o.S, seed, block, p_drop, nullptr);
+  for (const UOp& o : h->ops)
+    if (o.kind == UOP_RES && o.block == block) {
+      launch_ug_mask(out, (size_t)batch * h->res[o.idx].cout * o.S * o.S, seed, block, p_drop, nullptr);
       HIP_TRY(hipGetLastError());
       return RGFM_OK;
     }
-  return fail(RGFM_EINVAL, "block %d out of range (the net has %d ResBlocks)", block, p.nblocks);
+  return fail(RGFM_EINVAL, "block %d out of range (the net has %d ResBlocks)", block, (int)h->res.size());
 }

@@ -1,11 +1,12 @@
-// api_unet.cpp -- the U-Net handle: parameter ingestion / packing, forward, trace hooks (the walk itself: rgfm_host.h, UNetRun) (C ABI: include/rgfm.h).
+// api_unet.cpp -- the U-Net handle: parameter ingestion / packing, forward, trace hooks (C ABI: include/rgfm.h).  The
+// network's topology is the op list of unet_plan.h (plan_unet); the inference walk over it is UNetRun (rgfm_host.h).
 #include "rgfm_host.h"
 
 extern "C" int rgfm_unet_param_floats(const rgfm_unet_desc* desc, size_t* n_floats) {
   int rc = check_desc(desc);
   if (rc) return rc;
   if (!n_floats) return fail(RGFM_EINVAL, "null output");
-  *n_floats = plan_unet(*desc, nullptr);
+  *n_floats = plan_unet(*desc).layout.n_params;
   return RGFM_OK;
 }
 
@@ -16,12 +17,11 @@ static int pack_weights(rgfm_unet* h, hipStream_t s) {
   std::vector<HxImage*> images;
   std::vector<NormGate> gates;
   std::vector<ConvW*> res_convs;
-  for (auto* v : {&h->enc, &h->mid, &h->dec})
-    for (ResW& r : *v) {
-      res_convs.push_back(&r.c1), res_convs.push_back(&r.c2);
-      if (r.has_skip) res_convs.push_back(&r.sk);
-      gates.push_back({r.n1w, r.n1b, r.cin, &r.c1.hx}), gates.push_back({r.n2w, r.n2b, r.cout, &r.c2.hx});
-    }
+  for (ResW& r : h->res) {
+    res_convs.push_back(&r.c1), res_convs.push_back(&r.c2);
+    if (r.has_skip) res_convs.push_back(&r.sk);
+    gates.push_back({r.n1w, r.n1b, r.cin, &r.c1.hx}), gates.push_back({r.n2w, r.n2b, r.cout, &r.c2.hx});
+  }
   for (ConvW* w : res_convs) pack_one(h, *w, CONV_S1, s), images.push_back(&w->hx);
   for (ConvW& w : h->down) {  // stride-2 convs: phase-ordered weights, and once more in plain tap order
     pack_one(h, w, CONV_S2, s), images.push_back(&w.hx);
@@ -55,17 +55,17 @@ extern "C" int rgfm_unet_create(const rgfm_unet_desc* desc, const float* params_
   hipStream_t s = (hipStream_t)stream;
   rgfm_unet* h = new rgfm_unet();
   h->d = *desc;
-  if (plan_unet(*desc, h) != n_floats) {
+  static_cast<UNetPlan&>(*h) = plan_unet(*desc);
+  static_cast<WeightLayout&>(*h) = h->layout;
+  if (h->n_params != n_floats) {
     const size_t want = h->n_params;
     delete h;
     return fail(RGFM_EINVAL, "parameter blob has %zu floats, architecture needs %zu", n_floats, want);
   }
-  for (const auto* v : {&h->enc, &h->mid, &h->dec})
-    for (const ResW& r : *v) {
-      if (r.cin % KC || r.cout % 32) {
-        delete h;
-        return fail(RGFM_EINVAL, "channel counts must be multiples of 16 (in) / 32 (out)");
-      }
+  for (const ResW& r : h->res)
+    if (r.cin % KC || r.cout % 32) {
+      delete h;
+      return fail(RGFM_EINVAL, "channel counts must be multiples of 16 (in) / 32 (out)");
     }
   auto bail = [&](int code, const char* what) {
     rgfm_unet_destroy(h);
@@ -75,11 +75,10 @@ extern "C" int rgfm_unet_create(const rgfm_unet_desc* desc, const float* params_
   {
     size_t mx = 0;
     for (const ConvW& w : h->up) mx = std::max(mx, (size_t)w.cin * w.cout * 16);
-    for (const auto* v : {&h->enc, &h->mid, &h->dec})
-      for (const ResW& r : *v) {
-        if (r.c1.wino.present) mx = std::max(mx, (size_t)r.c1.cin * r.c1.cout * 16);
-        if (r.c2.wino.present) mx = std::max(mx, (size_t)r.c2.cin * r.c2.cout * 16);
-      }
+    for (const ResW& r : h->res) {
+      if (r.c1.wino.present) mx = std::max(mx, (size_t)r.c1.cin * r.c1.cout * 16);
+      if (r.c2.wino.present) mx = std::max(mx, (size_t)r.c2.cin * r.c2.cout * 16);
+    }
     if (mx && hipMalloc(&h->wtmp, mx * sizeof(float)) != hipSuccess) return bail(RGFM_ENOMEM, "hipMalloc(upsample weights)");
   }
   if ((rc = pack_weights(h, s))) return bail(rc, "packing the weights failed");
@@ -89,8 +88,7 @@ extern "C" int rgfm_unet_create(const rgfm_unet_desc* desc, const float* params_
   const float neg_log = (float)(-std::log(10000.0));
   for (int i = 0; i < half; ++i) fr[i] = std::exp(((float)i * neg_log) / (float)half);
   std::vector<TimeLinear> lin;
-  for (const auto* v : {&h->enc, &h->mid, &h->dec})
-    for (const ResW& r : *v) lin.push_back({(int)r.tw, (int)r.tb, r.cout, r.temb_off});
+  for (const ResW& r : h->res) lin.push_back({(int)r.tw, (int)r.tb, r.cout, r.temb_off});
   h->nlin = (int)lin.size();
   if (hipMalloc(&h->freqs, half * sizeof(float)) != hipSuccess) return bail(RGFM_ENOMEM, "hipMalloc(freqs)");
   if (hipMalloc(&h->lin_dev, lin.size() * sizeof(TimeLinear)) != hipSuccess) return bail(RGFM_ENOMEM, "hipMalloc(lin)");
@@ -175,40 +173,6 @@ extern "C" int rgfm_unet_set_trace(rgfm_unet* h, int enable) {
   return RGFM_OK;
 }
 
-namespace {
-void act_table(const rgfm_unet* h, std::vector<std::pair<int, int>>& t) {
-  const rgfm_unet_desc& d = h->d;
-  int S = d.img_size, ch = h->mc;
-  t.push_back({ch, S});
-  for (int l = 0; l < d.num_levels; ++l) {
-    const int oc = h->mc * d.channel_mult[l];
-    for (int r = 0; r < d.num_res_blocks; ++r) {
-      t.push_back({oc, S});
-      t.push_back({oc, S});
-      ch = oc;
-    }
-    if (l < d.num_levels - 1) {
-      S /= 2;
-      t.push_back({ch, S});
-    }
-  }
-  for (int i = 0; i < 4; ++i) t.push_back({ch, S});
-  for (int l = d.num_levels - 1; l >= 0; --l) {
-    const int oc = h->mc * d.channel_mult[l];
-    for (int i = 0; i < d.num_res_blocks + 1; ++i) {
-      t.push_back({oc, S});
-      t.push_back({oc, S});
-      ch = oc;
-    }
-    if (l > 0) {
-      S *= 2;
-      t.push_back({ch, S});
-    }
-  }
-  t.push_back({d.in_channels, S});
-}
-}  // namespace
-
 extern "C" int rgfm_unet_p_handovers(const rgfm_unet* h, int* blocks) {
   if (!h || !blocks) return fail(RGFM_EINVAL, "null argument");
   *blocks = h->p_handovers;
@@ -227,19 +191,16 @@ extern "C" int rgfm_unet_conv_routes(const rgfm_unet* h, int* counts, int n) {
 
 extern "C" int rgfm_unet_num_activations(const rgfm_unet* h, int* n) {
   if (!h || !n) return fail(RGFM_EINVAL, "null argument");
-  std::vector<std::pair<int, int>> t;
-  act_table(h, t);
-  *n = (int)t.size();
+  *n = (int)unet_trace_table(*h).size();
   return RGFM_OK;
 }
 
 extern "C" int rgfm_unet_activation_shape(const rgfm_unet* h, int index, int* channels, int* height, int* width) {
   if (!h) return fail(RGFM_EINVAL, "null handle");
-  std::vector<std::pair<int, int>> t;
-  act_table(h, t);
+  const std::vector<UTensor> t = unet_trace_table(*h);
   if (index < 0 || index >= (int)t.size()) return fail(RGFM_EINVAL, "activation index out of range");
-  *channels = t[index].first;
-  *height = *width = t[index].second;
+  *channels = t[index].C;
+  *height = *width = t[index].S;
   return RGFM_OK;
 }
 

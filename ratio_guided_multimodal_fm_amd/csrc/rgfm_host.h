@@ -1,7 +1,8 @@
 // rgfm_host.h -- host-side internals shared by the translation units of the C ABI (api_*.cpp): error text, the
 // hipEvent kernel-class timers, workspace carving, the per-thread run-time switches (Modes; with the process-wide
 // ConvTuning of rgfm_kernels.h the only two places that can change conv routing), per-device state, conv dispatch,
-// the U-Net handle and its network walk (used by the samplers and the gradient-guided loop too) and the guidance launch.
+// the U-Net handle and its inference walk over the plan's op list (unet_plan.h: the one place that knows the network's
+// topology; the walk is used by the samplers and the gradient-guided loop too) and the guidance launch.
 // (What only the sampler loops share is in sampler_host.h.)  Not part of the public ABI (that is include/rgfm.h);
 // everything here is `inline` / C++17 inline variables, so every unit sees ONE definition.
 //
@@ -32,8 +33,11 @@
 #include <vector>
 
 #include "rgfm_kernels.h"
+#include "unet_plan.h"  // the weight-plan types (Cursor .. ResW) and the U-Net's plan: parameter offsets + op list
 
 using namespace rgfm;
+
+static_assert(UNET_KC == KC, "unet_plan.h states the conv kernels' K chunk for the Winograd-image condition");
 
 // ------------------------------------------------------------------ errors
 inline thread_local std::string g_err;
@@ -163,74 +167,6 @@ struct Tensor {  // NHWC activation + its GroupNorm partial statistics
   int C = 0, S = 0;
   void* p = nullptr;     // the same map in P format (ConvArgs::pout / pin0), when its producer wrote it
   bool p_valid = false;
-};
-
-struct Cursor {
-  size_t off = 0;
-  size_t take(size_t n) {
-    const size_t r = off;
-    off += n;
-    return r;
-  }
-};
-
-// One two-plane fp16 weight image (conv_mfma_hx2*.hip) of a conv.
-struct HxImage {
-  size_t off = 0;        // offset (fp16 elements) into the packedh buffer
-  int hq = 0;            // index of its scale record {q, 1/q, s_w, eligible} in the hq array
-  bool present = false;  // the plan carved it
-  bool ok = false;       // weights inside the fp16 path's range (read_hx_flags, after packing)
-  bool usable() const { return present && ok; }
-};
-
-struct ConvW {  // one packed conv
-  size_t w_raw = 0, b = 0;  // offsets into the params blob
-  size_t w_pk = 0;          // offset into the packed buffer
-  size_t w_bx3 = 0;         // offset (bf16 elements) into the 3-plane bf16 buffer of conv_mfma_bx3.hip
-  int cin = 0, cout = 0, taps = 9;
-  HxImage hx;    // the image every conv has, in the order of its mode (stride-2 convs: phase-major)
-  HxImage hx9;   // stride-2 convs once more in plain nine-tap order (conv_mfma_hx2s.hip): same weights, hx's scale record
-  HxImage wino;  // ResBlock convs with Cout % 64 == 0 once more as Winograd F(2x2, 3x3) images (conv_mfma_hx2w.hip)
-  // Upsample convs (nearest x 2, then 3x3: unet_flexible.py:107-108) once more as the EQUIVALENT ConvTranspose2d(4, 2, 1)
-  // -- four 2x2-tap parity classes over the INPUT raster, 16 instead of 36 tap products per input pixel (launch_up2_as_deconv)
-  HxImage t2;
-};
-
-// What a plan hands to the weight store: element counts of the buffers every handle owns.
-struct WeightLayout {
-  size_t n_params = 0, n_packed = 0, n_packed3 = 0, n_packedh = 0;
-  int n_hq = 0;
-};
-
-// The cursors of one plan: the state_dict-order blob, the fp32-packed, bf16 and fp16 buffers and the scale records.
-struct Planner {
-  Cursor raw, pk, p3, ph;
-  int nhq = 0;
-  // a two-plane image of n_fp16 elements; `same_scale`: an image of the same weights, whose scale record this one shares
-  HxImage image(size_t n_fp16, const HxImage* same_scale = nullptr) {
-    HxImage i;
-    i.off = ph.take(n_fp16), i.hq = same_scale ? same_scale->hq : nhq++, i.present = true;
-    return i;
-  }
-  ConvW conv(int cin, int cout, int taps) {
-    ConvW w;
-    w.cin = cin, w.cout = cout, w.taps = taps;
-    w.w_raw = raw.take((size_t)cout * cin * taps);
-    w.b = raw.take(cout);
-    w.w_pk = pk.take((size_t)cout * cin * taps);
-    w.w_bx3 = p3.take((size_t)cout * cin * taps * 3);
-    w.hx = image((size_t)cout * cin * taps * 2);
-    return w;
-  }
-  WeightLayout layout() const { return {raw.off, pk.off, p3.off, ph.off, nhq}; }
-};
-
-struct ResW {
-  int cin = 0, cout = 0;
-  size_t n1w, n1b, n2w, n2b, tw, tb;
-  ConvW c1, c2, sk;
-  bool has_skip = false;
-  int temb_off = 0;
 };
 
 inline int nt32_of(int cout) { return (cout % 64 == 0) ? 2 : 1; }
@@ -535,17 +471,12 @@ inline int demote_by_norms(const WeightStore& st, const std::vector<NormGate>& g
 
 
 // ================================================================== U-Net
-struct rgfm_unet : WeightStore {
+struct rgfm_unet : WeightStore, UNetPlan {  // (the plan: unet_plan.h; its `layout` is also the store's WeightLayout)
   rgfm_unet_desc d;
   float* freqs = nullptr;
   TimeLinear* lin_dev = nullptr;
   float* wtmp = nullptr;  // scratch of the Upsample / Winograd weight images (kept for rgfm_unet_update_params)
-  int mc = 0, temb = 0, nlin = 0, temb_total = 0;
-  size_t te0w, te0b, te2w, te2b, icw, icb, onw, onb, ocw, ocb;
-  size_t ocw_pk = 0;  // out_conv weights re-laid out for conv_out_kernel (offset into `packed`)
-  std::vector<ResW> enc, mid, dec;
-  std::vector<ConvW> down, up;
-  int final_ch = 0;
+  int nlin = 0;
   bool trace = false;
   int wino_convs = 0;   // convs of the latest walk described for the Winograd kernel (rgfm_unet_wino_convs)
   int p_handovers = 0;  // ResBlocks of the latest walk whose conv1 -> conv2 hand-over took the P format (rgfm_unet_p_handovers)
@@ -558,87 +489,6 @@ struct rgfm_unet : WeightStore {
   std::vector<Act> acts;  // filled by the last (non-dry) run in trace mode
 };
 
-
-// Walks the parameter registration order of FlexibleUNet.__init__
-// (reference src/models/unet_flexible.py:146-201; UNetMNIST, src/models/unet.py:155-214,
-// is identical) and records blob offsets.  Returns the total float count.
-inline size_t plan_unet(const rgfm_unet_desc& d, rgfm_unet* h) {
-  Planner P;
-  Cursor& c = P.raw;
-  const int mc = d.model_channels, temb = 4 * mc;
-  std::vector<ResW> enc, mid, dec;
-  std::vector<ConvW> down, up;
-  int temb_off = 0;
-  auto res = [&](int cin, int cout) {
-    ResW r;
-    r.cin = cin, r.cout = cout;
-    r.n1w = c.take(cin), r.n1b = c.take(cin);
-    r.c1 = P.conv(cin, cout, 9);
-    r.tw = c.take((size_t)cout * temb), r.tb = c.take(cout);
-    r.n2w = c.take(cout), r.n2b = c.take(cout);
-    r.c2 = P.conv(cout, cout, 9);
-    if (cout % 64 == 0 && cin % KC == 0) {  // the Winograd images (16 positions instead of 9 taps)
-      r.c1.wino = P.image((size_t)cout * cin * 16 * 2);
-      r.c2.wino = P.image((size_t)cout * cout * 16 * 2);
-    }
-    r.has_skip = cin != cout;
-    if (r.has_skip) r.sk = P.conv(cin, cout, 1);
-    r.temb_off = temb_off;
-    temb_off += cout;
-    return r;
-  };
-  const size_t te0w = c.take((size_t)temb * mc), te0b = c.take(temb);
-  const size_t te2w = c.take((size_t)temb * temb), te2b = c.take(temb);
-  const size_t icw = c.take((size_t)mc * d.in_channels * 9), icb = c.take(mc);
-  int ch = mc;
-  std::vector<int> skips{ch}, down_ch, up_ch;
-  for (int l = 0; l < d.num_levels; ++l) {
-    const int oc = mc * d.channel_mult[l];
-    for (int r = 0; r < d.num_res_blocks; ++r) {
-      enc.push_back(res(ch, oc));
-      ch = oc;
-      skips.push_back(ch);
-    }
-    if (l < d.num_levels - 1) {
-      down_ch.push_back(ch);
-      skips.push_back(ch);
-    }
-  }
-  for (int dc : down_ch) {
-    ConvW w = P.conv(dc, dc, 9);
-    w.hx9 = P.image((size_t)dc * dc * 9 * 2, &w.hx);  // (the Downsample convs twice: phase-major and plain)
-    down.push_back(w);
-  }
-  mid.push_back(res(ch, ch));
-  mid.push_back(res(ch, ch));
-  for (int l = d.num_levels - 1; l >= 0; --l) {
-    const int oc = mc * d.channel_mult[l];
-    for (int i = 0; i < d.num_res_blocks + 1; ++i) {
-      dec.push_back(res(ch + skips.back(), oc));
-      skips.pop_back();
-      ch = oc;
-    }
-    if (l > 0) up_ch.push_back(ch);
-  }
-  for (int uc : up_ch) {
-    ConvW w = P.conv(uc, uc, 9);
-    w.t2 = P.image((size_t)uc * uc * 16 * 2);  // (the Upsample convs twice: nine taps, and the parity-class form)
-    up.push_back(w);
-  }
-  const size_t onw = c.take(ch), onb = c.take(ch);
-  const size_t ocw = c.take((size_t)d.in_channels * ch * 9), ocb = c.take(d.in_channels);
-  const size_t ocw_pk = P.pk.take((size_t)d.in_channels * ch * 9);
-  if (h) {
-    h->mc = mc, h->temb = temb;
-    h->te0w = te0w, h->te0b = te0b, h->te2w = te2w, h->te2b = te2b;
-    h->icw = icw, h->icb = icb, h->onw = onw, h->onb = onb, h->ocw = ocw, h->ocb = ocb, h->ocw_pk = ocw_pk;
-    h->enc = enc, h->mid = mid, h->dec = dec, h->down = down, h->up = up;
-    h->final_ch = ch;
-    h->temb_total = temb_off;
-    static_cast<WeightLayout&>(*h) = P.layout();
-  }
-  return c.off;
-}
 
 inline int check_desc(const rgfm_unet_desc* d) {
   if (!d) return fail(RGFM_EINVAL, "null descriptor");
@@ -874,7 +724,7 @@ struct UNetRun {
     return o;
   }
 
-  // FlexibleUNet.forward (unet_flexible.py:203-261).  Exactly one of v_out / x_state
+  // FlexibleUNet.forward (unet_flexible.py:203-261), op by op of the handle's plan.  Exactly one of v_out / x_state
   // may be non-null... both allowed: v_out receives the velocity, x_state the Euler update.
   // x_base (with x_state): x_state = x_base + v dt, a midpoint stage that starts from another buffer than it writes;
   // null or x_state itself: the in-place update.
@@ -883,62 +733,57 @@ struct UNetRun {
     ModeScope mode_scope(h->conv_mode);
     if (!dry && h->trace) h->acts.clear();
     if (!dry) h->p_handovers = 0, h->wino_convs = 0, std::fill(h->routes, h->routes + RGFM_ROUTE_SLOTS, 0);
-    int S = d.img_size;
-    Tensor cur = new_tensor(h->mc, S);
-    if (!dry) {
-      ConvInArgs ci{};
-      ci.x = x, ci.w = h->params + h->icw, ci.bias = h->params + h->icb;
-      ci.out = cur.data, ci.stats_out = cur.stats, ci.B = B, ci.C0 = h->mc, ci.g = make_geom(S, S);
-      ci.range_flag = h->range_flag, ci.small_check = g_modes.conv == CONV_ARITH_HX2 ? 1 : 0;  // (the last decoder block's skip reads it raw)
-      // algorithmic bytes: the NCHW image in, the NHWC map (+ its statistics) out
-      const TileGeom g0 = make_geom(S, S);
-      ProfScope p(d.in_channels == 1 ? RGFM_KCLASS_CONV_IN1 : RGFM_KCLASS_CONV_IN3,
-                  4.0 * B * ((double)S * S * (d.in_channels + h->mc) + 2.0 * g0.nparts * h->mc), s);
-      launch_conv_in(ci, d.in_channels, s);
-    }
-    record(cur);
-    std::vector<Tensor> skips{cur};
-    size_t e = 0;
-    for (int l = 0; l < d.num_levels; ++l) {
-      for (int r = 0; r < d.num_res_blocks; ++r) {
-        cur = resblock(h->enc[e++], cur, nullptr);
-        skips.push_back(cur);
+    std::vector<Tensor> T(h->tensors.size());  // the maps of this run, by the plan's tensor ids
+    for (const UOp& o : h->ops) {
+      switch (o.kind) {
+        case UOP_IN: {
+          const int S = o.S;
+          const Tensor& cur = T[o.out] = new_tensor(h->mc, S);
+          if (!dry) {
+            ConvInArgs ci{};
+            ci.x = x, ci.w = h->params + h->icw, ci.bias = h->params + h->icb;
+            ci.out = cur.data, ci.stats_out = cur.stats, ci.B = B, ci.C0 = h->mc, ci.g = make_geom(S, S);
+            ci.range_flag = h->range_flag, ci.small_check = g_modes.conv == CONV_ARITH_HX2 ? 1 : 0;  // (the last decoder block's skip reads it raw)
+            // algorithmic bytes: the NCHW image in, the NHWC map (+ its statistics) out
+            const TileGeom g0 = make_geom(S, S);
+            ProfScope p(d.in_channels == 1 ? RGFM_KCLASS_CONV_IN1 : RGFM_KCLASS_CONV_IN3,
+                        4.0 * B * ((double)S * S * (d.in_channels + h->mc) + 2.0 * g0.nparts * h->mc), s);
+            launch_conv_in(ci, d.in_channels, s);
+          }
+          record(cur);
+          break;
+        }
+        case UOP_RES:
+          T[o.out] = resblock(h->res[o.idx], T[o.in0], o.in1 >= 0 ? &T[o.in1] : nullptr);
+          break;
+        case UOP_DOWN:
+          T[o.out] = conv(T[o.in0], nullptr, nullptr, h->down[o.idx], CONV_S2, nullptr, 0, nullptr, nullptr, nullptr, true);
+          record(T[o.out]);
+          break;
+        case UOP_UP:
+          T[o.out] = conv(T[o.in0], nullptr, nullptr, h->up[o.idx], CONV_UP2, nullptr, 0, nullptr, nullptr, nullptr, true);
+          record(T[o.out]);
+          break;
+        case UOP_OUT: {
+          const Tensor& cur = T[o.in0];
+          float* ab = finalize(cur, nullptr, h->onw, h->onb);
+          if (dry) break;
+          flush_conv(pend, s, h->routes);
+          ConvOutArgs co{};
+          co.in = cur.data, co.ab = ab, co.w = h->packed + h->ocw_pk, co.bias = h->params + h->ocb;
+          co.v_out = v_out, co.x_state = x_state, co.dt = dt, co.B = B, co.Cin = cur.C;
+          co.x_base = x_base == x_state ? nullptr : x_base;
+          co.g = make_geom(cur.S, cur.S);
+          co.halo_px = co.g.spt * (co.g.th + 2) * (co.g.W + 2);
+          // algorithmic bytes: the NHWC map + its scale/shift in, the NCHW velocity out (fused Euler: state in and out)
+          const double px = (double)B * cur.S * cur.S;
+          ProfScope p(d.in_channels == 1 ? RGFM_KCLASS_CONV_OUT1 : RGFM_KCLASS_CONV_OUT3,
+                      4.0 * (px * cur.C + 2.0 * B * cur.C + px * d.in_channels * ((v_out ? 1 : 0) + (x_state ? 2 : 0))), s);
+          launch_conv_out(co, d.in_channels, s);
+          if (h->trace && v_out) h->acts.push_back({v_out, d.in_channels, cur.S, true});
+          break;
+        }
       }
-      if (l < d.num_levels - 1) {
-        cur = conv(cur, nullptr, nullptr, h->down[l], CONV_S2, nullptr, 0, nullptr, nullptr, nullptr, true);
-        record(cur);
-        skips.push_back(cur);
-      }
-    }
-    cur = resblock(h->mid[0], cur, nullptr);
-    cur = resblock(h->mid[1], cur, nullptr);
-    size_t di = 0, ui = 0;
-    for (int l = d.num_levels - 1; l >= 0; --l) {
-      for (int i = 0; i < d.num_res_blocks + 1; ++i) {
-        Tensor sk = skips.back();
-        skips.pop_back();
-        cur = resblock(h->dec[di++], cur, &sk);
-      }
-      if (l > 0) {
-        cur = conv(cur, nullptr, nullptr, h->up[ui++], CONV_UP2, nullptr, 0, nullptr, nullptr, nullptr, true);
-        record(cur);
-      }
-    }
-    float* ab = finalize(cur, nullptr, h->onw, h->onb);
-    if (!dry) {
-      flush_conv(pend, s, h->routes);
-      ConvOutArgs co{};
-      co.in = cur.data, co.ab = ab, co.w = h->packed + h->ocw_pk, co.bias = h->params + h->ocb;
-      co.v_out = v_out, co.x_state = x_state, co.dt = dt, co.B = B, co.Cin = cur.C;
-      co.x_base = x_base == x_state ? nullptr : x_base;
-      co.g = make_geom(cur.S, cur.S);
-      co.halo_px = co.g.spt * (co.g.th + 2) * (co.g.W + 2);
-      // algorithmic bytes: the NHWC map + its scale/shift in, the NCHW velocity out (fused Euler: state in and out)
-      const double px = (double)B * cur.S * cur.S;
-      ProfScope p(d.in_channels == 1 ? RGFM_KCLASS_CONV_OUT1 : RGFM_KCLASS_CONV_OUT3,
-                  4.0 * (px * cur.C + 2.0 * B * cur.C + px * d.in_channels * ((v_out ? 1 : 0) + (x_state ? 2 : 0))), s);
-      launch_conv_out(co, d.in_channels, s);
-      if (h->trace && v_out) h->acts.push_back({v_out, d.in_channels, cur.S, true});
     }
     return RGFM_OK;
   }
