@@ -617,6 +617,73 @@ int rgfm_clf_pool_choice(rgfm_clf* h, const void* ws, int layer, int n, float* o
 int rgfm_clf_gate(rgfm_clf* h, const void* ws, int layer, int n, float* out);
 int rgfm_clf_dropout_mask(rgfm_clf* h, uint64_t seed, float p_drop, int n, float* out);
 
+/* ------------------------------------------------------------------ optimizer step (Adam / AdamW, clip, weight EMA)
+ * The step around the four training passes: torch.optim.Adam(amsgrad=False, maximize=False) -- AdamW when `decoupled`
+ * -- with torch.nn.utils.clip_grad_norm_'s global-norm clip in front and an exponential moving average of the weights
+ * behind, as two launches over a table of tensors.  Needs no handle.  Added functions only: the ABI version is unchanged.
+ *
+ * State.  The caller owns three flat fp32 device buffers, 16-byte aligned: exp_avg, exp_avg_sq and (optional) ema.
+ * Tensor e owns floats [offset, offset + numel) of each; every offset is a multiple of 4 and slots do not overlap (so
+ * a slot is padded to whole quads of 4 floats; the padding is read and written back unchanged: keep it inside the
+ * buffers).
+ *
+ * Table.  `table_dev` is a DEVICE array of n_entries rgfm_adam_entry, sorted by strictly increasing offset.  param and
+ * grad are contiguous fp32 device tensors of numel floats at ANY 4-byte alignment (gradients are typically views into
+ * one blob): 16-byte accesses are issued only for a quad whose tensor has both base pointers 16-byte aligned, dword
+ * accesses otherwise.  bc1 = 1 - beta1^t and bc2 = 1 - beta2^t are THIS tensor's bias corrections for its own step
+ * count t >= 1, computed by the caller in double (a parameter without a gradient is left out of the table and keeps
+ * its count).  span_begin / span_end (multiples of 4, span_begin <= the first offset, span_end >= the end of the last
+ * slot) name the flat range the table covers, which the host cannot read from the device table.
+ * Stream ordering: the calls READ THE TABLE ON THE STREAM, not on entry -- the caller keeps table_dev alive and
+ * unmodified until the work enqueued by the call has run (a table uploaded by an asynchronous copy on the same stream
+ * is fine; so is overwriting it by a later copy on that stream).
+ *
+ * rgfm_adam_grad_norm: leaves in `ws` (rgfm_adam_workspace_bytes; 16-byte aligned) the partial sums of g^2 over every
+ * tensor of the table: squares and sums in float64, one partial per workgroup, a fixed chunk-to-workgroup assignment,
+ * no atomics -- the same bits on every run.  Called ONCE over the union of all parameter groups' tensors.
+ * rgfm_adam_step: then per group (each with its own lr / weight_decay; the table of a group is a sub-range of the
+ * union's).  With norm = sqrt(sum of the partials) (every workgroup adds them in the same order) and
+ *   coef = max_grad_norm > 0 ? min(1, max_grad_norm / (norm + 1e-6)) : 1        (clip_grad_norm_'s formula)
+ * it does per element, in one pass (36 bytes per element with the EMA, 28 without):
+ *   g = coef g;   coupled: g += weight_decay p;   decoupled: p *= 1 - lr weight_decay;
+ *   m = beta1 m + (1 - beta1) g;   v = beta2 v + (1 - beta2) g^2;
+ *   p -= (lr / bc1) m / (sqrt(v) / sqrt(bc2) + eps);
+ *   ema = ema_decay ema + (1 - ema_decay) p                                      (ema_decay >= 0)
+ * Products and sums in float64, each stored value rounded to fp32 once; the square root and the quotient in fp32.  The
+ * gradients are NOT modified (clip_grad_norm_ scales them in place).  `ws` is read when max_grad_norm > 0 or
+ * grad_norm_out is given (the norm call must then precede on the stream) and may be null otherwise; grad_norm_out
+ * (optional device float) receives the norm before clipping.  max_grad_norm = infinity reports the norm without
+ * clipping.  `ema` must be given exactly when ema_decay >= 0.
+ * Errors touch no state: a null descriptor, table, state buffer or needed workspace, n_entries < 1, a span that is
+ * empty or not a multiple of 4, a misaligned state buffer or workspace, lr < 0, betas outside [0, 1), eps < 0,
+ * weight_decay < 0, ema_decay > 1 or ema / ema_decay given one without the other -> RGFM_EINVAL; a workspace too small
+ * -> RGFM_ENOMEM; no gfx950 device -> RGFM_ENODEVICE. */
+typedef struct rgfm_adam_entry { /* 48 bytes */
+  float* param;
+  const float* grad;
+  uint64_t offset; /* first float of the tensor's slot in exp_avg / exp_avg_sq / ema; a multiple of 4 */
+  uint64_t numel;
+  double bc1, bc2; /* 1 - beta1^t, 1 - beta2^t for this tensor's step count t */
+} rgfm_adam_entry;
+
+typedef struct rgfm_adam_desc {
+  double lr;
+  double betas[2];
+  double eps;
+  double weight_decay;
+  double max_grad_norm; /* <= 0: no clipping */
+  double ema_decay;     /* < 0: no EMA */
+  int32_t decoupled;    /* 0: g += weight_decay p (Adam);  1: p *= 1 - lr weight_decay (AdamW) */
+  int32_t reserved;     /* 0 */
+} rgfm_adam_desc;
+
+int rgfm_adam_workspace_bytes(size_t* bytes);
+int rgfm_adam_grad_norm(const rgfm_adam_entry* table_dev, int n_entries, uint64_t span_begin, uint64_t span_end, void* ws,
+                        size_t ws_bytes, rgfm_stream_t stream);
+int rgfm_adam_step(const rgfm_adam_desc* desc, const rgfm_adam_entry* table_dev, int n_entries, uint64_t span_begin,
+                   uint64_t span_end, float* exp_avg, float* exp_avg_sq, float* ema, float* grad_norm_out, void* ws,
+                   size_t ws_bytes, rgfm_stream_t stream);
+
 /* One guidance evaluation on its own (parity hook for sample_mnist_svhn.py:124-171):
  * vx/vy are overwritten with (1-gamma)*v + gamma*g at time t; weights_out[B,N]
  * (optional, may be null) receives the normalised importance weights. */

@@ -41,6 +41,16 @@ class ClfDesc(ctypes.Structure):
     _fields_ = [("kind", c_int32)]
 
 
+class AdamEntry(ctypes.Structure):  # rgfm_adam_entry: one tensor of the optimizer step's device table (48 bytes)
+    _fields_ = [("param", c_uint64), ("grad", c_uint64), ("offset", c_uint64), ("numel", c_uint64),
+                ("bc1", c_double), ("bc2", c_double)]
+
+
+class AdamDesc(ctypes.Structure):
+    _fields_ = [("lr", c_double), ("betas", c_double * 2), ("eps", c_double), ("weight_decay", c_double),
+                ("max_grad_norm", c_double), ("ema_decay", c_double), ("decoupled", c_int32), ("reserved", c_int32)]
+
+
 # name -> (restype, argtypes); every symbol include/rgfm.h declares.
 SIGNATURES = {
     "rgfm_unet_param_floats": (c_int, [P(UNetDesc), P(c_size_t)]),
@@ -197,6 +207,10 @@ SIGNATURES = {
     "rgfm_clf_pool_choice": (c_int, [c_void_p, c_void_p, c_int, c_int, c_void_p]),
     "rgfm_clf_gate": (c_int, [c_void_p, c_void_p, c_int, c_int, c_void_p]),
     "rgfm_clf_dropout_mask": (c_int, [c_void_p, c_uint64, c_float, c_int, c_void_p]),
+    "rgfm_adam_workspace_bytes": (c_int, [P(c_size_t)]),
+    "rgfm_adam_grad_norm": (c_int, [c_void_p, c_int, c_uint64, c_uint64, c_void_p, c_size_t, c_void_p]),
+    "rgfm_adam_step": (c_int, [P(AdamDesc), c_void_p, c_int, c_uint64, c_uint64, c_void_p, c_void_p, c_void_p, c_void_p,
+                               c_void_p, c_size_t, c_void_p]),
     "rgfm_ubench_hbm_copy": (c_int, [c_size_t, P(c_double)]),
     "rgfm_unet_set_conv_mode": (c_int, [c_void_p, c_int]),
     "rgfm_fmnet_set_conv_mode": (c_int, [c_void_p, c_int]),

@@ -15,6 +15,7 @@
 //   api_fmnet.cpp    rgfm_fmnet_*           (FlowMatchingModel)
 //   api_fmnet_train.cpp  rgfm_fmnet_forward_train / _backward / _update_params (FlowMatchingModel's training pass)
 //   api_clf.cpp      rgfm_clf_*             (the evaluation classifiers: handle, training pass, cross-entropy)
+//   api_optim.cpp    rgfm_adam_*            (the optimizer step: gradient norm, clip, Adam / AdamW, weight EMA)
 //
 // No PyTorch types, no allocation and no synchronisation inside forward / sample calls (everything is carved from the
 // caller's workspace, stream-ordered).

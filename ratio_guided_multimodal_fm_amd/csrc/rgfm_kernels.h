@@ -589,4 +589,23 @@ void launch_ct_relu_drop_bwd(const float* u, float* g, size_t n, const unsigned*
 void launch_ct_xent(const float* logits, const int* labels, int n, int classes, float scale, double* loss,
                     float* dlogits, int* pred, hipStream_t s);
 
+// ---- optimizer step (optim.hip): gradient norm, clip, Adam / AdamW, weight EMA over a table of rgfm_adam_entry
+constexpr int ADAM_CHUNK = 1024;     // floats of the flat state range per chunk (a quad per lane of a 256-thread workgroup)
+constexpr int ADAM_PARTIALS = 1024;  // float64 partial sums of g^2: the norm launch's grid cap; the step sums all of them
+constexpr int ADAM_MAX_GRID = 2048;  // the step launch's grid cap (beyond it a workgroup walks a run of consecutive chunks)
+struct AdamStepArgs {
+  const rgfm_adam_entry* tab;  // device table, sorted by offset
+  int n;
+  uint64_t span_begin, n_chunks;  // first float of the flat range the table covers; its chunks (set by launch_adam_step)
+  float *exp_avg, *exp_avg_sq, *ema;  // ema null: no average kept
+  const double* partials;             // [ADAM_PARTIALS] of launch_adam_norm, or null: no norm, coef = 1
+  float* grad_norm_out;               // optional
+  double lr, beta1, one_minus_beta1, beta2, one_minus_beta2, wd, decay_mul, max_norm, ema_decay, one_minus_ema_decay;
+  float eps;
+  int decoupled;
+};
+void launch_adam_norm(const rgfm_adam_entry* tab, int n, uint64_t span_begin, uint64_t span_end, double* partials,
+                      hipStream_t s);
+void launch_adam_step(AdamStepArgs a, uint64_t span_end, hipStream_t s);
+
 }  // namespace rgfm

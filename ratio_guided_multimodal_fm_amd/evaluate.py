@@ -102,8 +102,8 @@ def main(argv=None):
     classifier = MNISTClassifier().to(device)
     classifier.load_state_dict(torch.load(clf_path, map_location=device))
     fm_x, fm_y = build_flow_models(args.model, device)
-    load_checkpoint(fm_x, path_x, device)
-    load_checkpoint(fm_y, path_y, device)
+    load_checkpoint(fm_x, path_x, device, ema=args.ema)
+    load_checkpoint(fm_y, path_y, device, ema=args.ema)
 
     def make_ratio():
         path = get_checkpoint_path('ratio', args.loss_type, args.transform_type, 'best')

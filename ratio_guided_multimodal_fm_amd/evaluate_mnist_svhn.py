@@ -105,6 +105,7 @@ def main(argv=None):
     p.add_argument('--num_steps', type=int, default=100)
     p.add_argument('--device', type=str, default='cuda')
     p.add_argument('--seed', type=int, default=42)
+    p.add_argument('--ema', action='store_true', help="load the averaged weights ('ema_state_dict') of the flow checkpoints (train_flow --optimizer hip --ema_decay ...)")
     p.add_argument('--solver', type=str, default='euler', choices=['euler', 'midpoint'],
                    help="ODE solver of every sampler loop: 'midpoint' (explicit midpoint rule, second order) takes two network evaluations per step")
     p.add_argument('--sharded', action='store_true',
@@ -138,8 +139,8 @@ def main(argv=None):
     svhn_clf.load_state_dict(torch.load(paths['svhn_clf'], map_location=device))
     fm_mnist = FlowMatchingUNetMNIST(img_size=32).to(device)
     fm_svhn = FlowMatchingUNetSVHN().to(device)
-    load_checkpoint(fm_mnist, paths['fm_mnist'], device)
-    load_checkpoint(fm_svhn, paths['fm_svhn'], device)
+    load_checkpoint(fm_mnist, paths['fm_mnist'], device, ema=args.ema)
+    load_checkpoint(fm_svhn, paths['fm_svhn'], device, ema=args.ema)
 
     def make_ratio():
         path = f'checkpoints/ratio_{args.loss_type}_mnist_svhn_best.pth'

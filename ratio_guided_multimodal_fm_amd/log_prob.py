@@ -41,6 +41,7 @@ def parse_args(argv=None):
     p.add_argument('--data', required=True, help='.npy / .pt tensor [N, C, H, W]')
     p.add_argument('--num_steps', type=int, default=100)
     p.add_argument('--solver', choices=['euler', 'midpoint'], default='midpoint')
+    p.add_argument('--ema', action='store_true', help="load the averaged weights ('ema_state_dict') of the flow checkpoints (train_flow --optimizer hip --ema_decay ...)")
     p.add_argument('--n_probes', type=int, default=1, help='Hutchinson probes per image')
     p.add_argument('--seed', type=int, default=42, help='seed of the probe generator')
     p.add_argument('--batch_size', type=int, default=128)
@@ -62,9 +63,9 @@ def parse_args(argv=None):
     return args
 
 
-def load_net(preset, path, device):
+def load_net(preset, path, device, ema=False):
     model = PRESETS[preset][0]().to(device)
-    load_checkpoint(model, path, device)
+    load_checkpoint(model, path, device, ema=ema)
     return model.eval()
 
 
@@ -86,18 +87,20 @@ def main(argv=None):
     device = torch.device(args.device)
     shape = PRESETS[args.preset][1]
     x = load_data(args.data, shape).to(device)
-    model = load_net(args.preset, args.checkpoint, device)
+    model = load_net(args.preset, args.checkpoint, device, args.ema)
     gen = torch.Generator(device=device).manual_seed(args.seed)
     kw = dict(num_steps=args.num_steps, solver=args.solver, n_probes=args.n_probes, generator=gen,
               batch_size=args.batch_size)
     settings = {k: getattr(args, k) for k in ('preset', 'checkpoint', 'data', 'num_steps', 'solver', 'n_probes', 'seed',
                                               'batch_size', 'data_range', 'levels')}
+    if args.ema:
+        settings['ema'] = True
     dims = shape[0] * shape[1] * shape[2]
     result = {'num_images': int(x.shape[0]), 'dims': dims, 'settings': settings}
     if args.joint:
         shape_y = PRESETS[args.preset_y][1]
         y = load_data(args.data_y, shape_y).to(device)
-        model_y = load_net(args.preset_y, args.checkpoint_y, device)
+        model_y = load_net(args.preset_y, args.checkpoint_y, device, args.ema)
         ratio = RATIO_OF[(args.preset, args.preset_y)](loss_type=args.loss_type).to(device)
         load_checkpoint(ratio, args.ratio_checkpoint, device)
         joint, logp, logp_y, log_r = joint_log_prob(model, model_y, ratio.eval(), x, y, **kw)

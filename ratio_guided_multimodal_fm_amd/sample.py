@@ -37,6 +37,7 @@ def add_common_args(p, mc_default):
     p.add_argument('--device', type=str, default='cuda')
     p.add_argument('--model', type=str, default='unet', choices=['unet', 'original'])
     p.add_argument('--seed', type=int, default=42)
+    p.add_argument('--ema', action='store_true', help="load the averaged weights ('ema_state_dict') of the flow checkpoints (train_flow --optimizer hip --ema_decay ...)")
     p.add_argument('--solver', type=str, default='euler', choices=['euler', 'midpoint'],
                    help="ODE solver of every sampler loop: 'midpoint' (explicit midpoint rule, second order) takes two network evaluations per step (U-Net nets: not with --model original)")
 
@@ -67,8 +68,8 @@ def main(argv=None):
             print(f"ERROR: FM checkpoint not found: {path} (train it: python -m ratio_guided_multimodal_fm_amd.train_flow "
                   f"--preset {preset} {flags} --data <images.npy>)")
             return 1
-    load_checkpoint(fm_x, path_x, device)
-    load_checkpoint(fm_y, path_y, device)
+    load_checkpoint(fm_x, path_x, device, ema=args.ema)
+    load_checkpoint(fm_y, path_y, device, ema=args.ema)
     print(f"  Loaded FM_x from: {path_x}\n  Loaded FM_y from: {path_y}")
 
     ratio = None

@@ -50,6 +50,7 @@ def main(argv=None):
     p.add_argument('--num_steps', type=int, default=100)
     p.add_argument('--device', type=str, default='cuda')
     p.add_argument('--seed', type=int, default=42)
+    p.add_argument('--ema', action='store_true', help="load the averaged weights ('ema_state_dict') of the flow checkpoints (train_flow --optimizer hip --ema_decay ...)")
     p.add_argument('--solver', type=str, default='euler', choices=['euler', 'midpoint'],
                    help="ODE solver of every sampler loop: 'midpoint' (explicit midpoint rule, second order) takes two network evaluations per step")
     p.add_argument('--sharded', action='store_true',
@@ -94,7 +95,7 @@ def main(argv=None):
             print(f"ERROR: checkpoint not found: {path}")
             print(f"Please train first with the reference: python src/{hint}")
             return 1
-        load_checkpoint(model, path, device)
+        load_checkpoint(model, path, device, ema=args.ema)
         print(f"  Loaded {path}")
 
     ratio = None

@@ -20,6 +20,7 @@ import torch
 from .models.classifier import MNISTClassifier
 from .models.svhn_classifier import MNISTClassifier32, SVHNClassifier
 from .utils import set_seed
+from .utils.optim import add_optimizer_args, build_optimizer, check_optimizer_args, ema_path
 from .utils.trainer import ClassifierTrainer
 
 KINDS = {
@@ -41,7 +42,9 @@ def parse_args(argv=None):
     p.add_argument('--lr', type=float, default=1e-3)
     p.add_argument('--device', type=str, default='cuda')
     p.add_argument('--seed', type=int, default=42)
+    add_optimizer_args(p)
     args = p.parse_args(argv)
+    check_optimizer_args(p, args)
     if args.epochs is None:
         args.epochs = KINDS[args.kind][2]
     return args
@@ -86,10 +89,13 @@ def checkpoint_path(kind):
     return KINDS[kind][3]
 
 
-def save_checkpoint(model, kind):
+def save_checkpoint(model, kind, optimizer=None):
+    """The plain state_dict; with an optimizer that keeps an EMA of the weights also the sibling <name>_ema.pth."""
     path = checkpoint_path(kind)
     os.makedirs(os.path.dirname(path), exist_ok=True)
     torch.save(model.state_dict(), path)
+    if getattr(optimizer, 'ema_decay', None) is not None:
+        torch.save(optimizer.ema_state_dict(model), ema_path(path))
     return path
 
 
@@ -106,7 +112,8 @@ def main(argv=None):
     print(f"train: {train[0].shape[0]} images, test: {test[0].shape[0]} images")
     model = ctor().to(device)
     print(f"Model parameters: {sum(p.numel() for p in model.parameters()):,}")
-    trainer = ClassifierTrainer(model, torch.optim.Adam(model.parameters(), lr=args.lr), device)
+    optimizer = build_optimizer(args, model.parameters())
+    trainer = ClassifierTrainer(model, optimizer, device)
     gen = torch.Generator().manual_seed(args.seed)
     best_acc = 0.0
     for epoch in range(args.epochs):
@@ -117,9 +124,9 @@ def main(argv=None):
         if test_acc > best_acc:
             best_acc = test_acc
             if save_best:
-                print(f"  -> Saved best model: {save_checkpoint(model, args.kind)} (test_acc={test_acc:.4f})")
+                print(f"  -> Saved best model: {save_checkpoint(model, args.kind, optimizer)} (test_acc={test_acc:.4f})")
     if not save_best:
-        print(f"Saved classifier: {save_checkpoint(model, args.kind)} (best acc: {best_acc:.4f})")
+        print(f"Saved classifier: {save_checkpoint(model, args.kind, optimizer)} (best acc: {best_acc:.4f})")
     print(f"\nTraining complete! Best test accuracy: {best_acc:.4f}")
     return best_acc
 

@@ -4,7 +4,8 @@
     python -m ratio_guided_multimodal_fm_amd.train_flow --preset original --modality x --data mnist_x.npy
 
 Mirrors the reference trainers (src/train_flow_svhn.py, src/train_flow_mnist32.py, src/train_flow.py): same
-arguments and defaults, Adam, best / every-N checkpoints {'epoch', 'model_state_dict', 'optimizer_state_dict',
+arguments and defaults, Adam (--optimizer hip: the fused HIP step of utils/optim.py, with --ema_decay,
+--max_grad_norm, --weight_decay), best / every-N checkpoints {'epoch', 'model_state_dict', 'optimizer_state_dict',
 'best_loss'} under the reference's names, early stopping.  The data is one tensor [N, C, H, W] in a .npy or .pt
 file, already in the reference's value range (no dataset download here).
 
@@ -22,6 +23,7 @@ import torch
 from .models import FlowMatchingModel, FlowMatchingUNet, FlowMatchingUNetMNIST, FlowMatchingUNetSVHN
 from .utils import set_seed
 from .utils.flow_utils import CFMSchedule, train_flow_matching_epoch
+from .utils.optim import add_optimizer_args, build_optimizer, check_optimizer_args
 
 PRESETS = {
     # preset: (constructor, image shape, checkpoint stem) -- the stems sample_mnist_svhn.py / sample.py load
@@ -57,7 +59,9 @@ def parse_args(argv=None):
     p.add_argument('--modality', type=str, default=None, choices=['x', 'y'],
                    help='28x28 presets: which modality the data is (selects the checkpoint name)')
     p.add_argument('--transform_type', type=str, default='rotate90', help='names the y checkpoint')
+    add_optimizer_args(p)
     args = p.parse_args(argv)
+    check_optimizer_args(p, args)
     if args.modality is not None and args.preset not in MODALITY_PRESETS:
         p.error(f"--modality applies to the presets {', '.join(MODALITY_PRESETS)}")
     if args.preset == 'original' and args.modality is None:
@@ -82,8 +86,13 @@ def batches(data, batch_size, gen):
 
 
 def checkpoint(epoch, model, optimizer, best_loss):
-    return {'epoch': epoch, 'model_state_dict': model.state_dict(), 'optimizer_state_dict': optimizer.state_dict(),
-            'best_loss': best_loss}
+    """The reference's checkpoint dict; with an optimizer that keeps an EMA of the weights (--optimizer hip --ema_decay)
+    also 'ema_state_dict', the averaged weights under the model's keys (load_checkpoint(..., ema=True))."""
+    ck = {'epoch': epoch, 'model_state_dict': model.state_dict(), 'optimizer_state_dict': optimizer.state_dict(),
+          'best_loss': best_loss}
+    if getattr(optimizer, 'ema_decay', None) is not None:
+        ck['ema_state_dict'] = optimizer.ema_state_dict(model)
+    return ck
 
 
 def main(argv=None):
@@ -94,7 +103,7 @@ def main(argv=None):
     device = torch.device(args.device)
     data = load_data(args.data, shape)
     model = ctor().to(device)
-    optimizer = torch.optim.Adam(model.parameters(), lr=args.lr)
+    optimizer = build_optimizer(args, model.parameters())
     schedule = CFMSchedule()
     start_epoch, best_loss = 0, float('inf')
     if args.resume:

@@ -26,6 +26,7 @@ from .models.ratio_estimator import RatioEstimator
 from .models.ratio_flexible import FlexibleRatioEstimator, RatioEstimatorMNISTSVHN
 from .utils import set_seed
 from .utils.losses import get_ratio_loss
+from .utils.optim import add_optimizer_args, build_optimizer, check_optimizer_args, ema_path
 from .utils.path_utils import get_checkpoint_path
 from .utils.trainer import RatioTrainer
 
@@ -54,7 +55,10 @@ def parse_args(argv=None):
     p.add_argument('--rulsif_alpha', type=float, default=0.2)
     p.add_argument('--lambda_penalty', type=float, default=0.1)
     p.add_argument('--seed', type=int, default=42)
-    return p.parse_args(argv)
+    add_optimizer_args(p)
+    args = p.parse_args(argv)
+    check_optimizer_args(p, args)
+    return args
 
 
 def load_pairs(path, shape_x, shape_y):
@@ -138,8 +142,12 @@ def checkpoint_path(args, tag):
     return get_checkpoint_path('ratio', args.loss_type, args.transform_type, tag)
 
 
-def save_checkpoint(model, args, path, epoch, best_loss):
-    """Plain state_dict for the fixed kinds (as the reference trainers write); the flexible kind adds what rebuilds it."""
+def save_checkpoint(model, args, path, epoch, best_loss, optimizer=None):
+    """Plain state_dict for the fixed kinds (as the reference trainers write); the flexible kind adds what rebuilds it.
+    With an optimizer that keeps an EMA of the weights, the averaged weights go to the sibling <name>_ema.pth as a
+    plain state_dict."""
+    if getattr(optimizer, 'ema_decay', None) is not None:
+        torch.save(optimizer.ema_state_dict(model), ema_path(path))
     if args.kind != 'flexible':
         torch.save(model.state_dict(), path)
         return
@@ -166,7 +174,8 @@ def main(argv=None):
         loss_fn = get_ratio_loss(loss_type=args.loss_type)
     else:
         loss_fn = get_ratio_loss(loss_type=args.loss_type, alpha=args.rulsif_alpha, lambda_penalty=args.lambda_penalty)
-    optimizer = torch.optim.Adam(model.parameters(), lr=args.lr)
+    # (--optimizer hip clips at the reference's max_norm = 1.0 by default, inside the step; RatioTrainer then skips its own)
+    optimizer = build_optimizer(args, model.parameters(), default_max_grad_norm=1.0)
     trainer = RatioTrainer(model, loss_fn, optimizer, device)
     gen = torch.Generator().manual_seed(args.seed)
     best_loss, patience_counter = float('inf'), 0
@@ -180,13 +189,13 @@ def main(argv=None):
         if metrics['loss'] < best_loss:
             best_loss, patience_counter = metrics['loss'], 0
             path = checkpoint_path(args, 'best')
-            save_checkpoint(model, args, path, epoch + 1, best_loss)
+            save_checkpoint(model, args, path, epoch + 1, best_loss, optimizer)
             print(f"  -> Saved best model: {path}")
         else:
             patience_counter += 1
         if (epoch + 1) % SAVE_EVERY == 0:
             path = checkpoint_path(args, f'epoch{epoch + 1}')
-            save_checkpoint(model, args, path, epoch + 1, best_loss)
+            save_checkpoint(model, args, path, epoch + 1, best_loss, optimizer)
             print(f"  -> Saved checkpoint: {path}")
         if patience_counter >= PATIENCE:
             print(f"\nEarly stopping after {epoch + 1} epochs (patience={PATIENCE})")

@@ -19,15 +19,24 @@ def set_seed(seed: int = 42):
         torch.cuda.manual_seed_all(seed)
 
 
-def load_checkpoint(model, path, device='cpu'):
+def load_checkpoint(model, path, device='cpu', ema=False):
     """Load either checkpoint format the reference writes (reference :25-51).
 
     ``{'model_state_dict': ..., 'epoch': ..., 'best_loss': ...}`` dicts
     (train_flow_mnist32.py / train_flow_svhn.py) or a raw ``state_dict``
     (train_flow.py, ratio and classifier trainers).  Returns
     ``{'epoch', 'best_loss'}`` for the dict format, ``{}`` otherwise.
+
+    ``ema=True`` loads the averaged weights instead: the ``'ema_state_dict'`` a dict checkpoint of
+    ``train_flow --optimizer hip --ema_decay ...`` carries; a file without one is an error.
     """
     ckpt = torch.load(path, map_location=device)
+    if ema:
+        if not (isinstance(ckpt, dict) and 'ema_state_dict' in ckpt):
+            raise KeyError(f"{path} has no 'ema_state_dict': it was not trained with --optimizer hip --ema_decay "
+                           "(the ratio and classifier trainers write the averaged weights to <name>_ema.pth instead)")
+        model.load_state_dict(ckpt['ema_state_dict'])
+        return {'epoch': ckpt.get('epoch', 0), 'best_loss': ckpt.get('best_loss', float('inf'))}
     if isinstance(ckpt, dict) and 'model_state_dict' in ckpt:
         model.load_state_dict(ckpt['model_state_dict'])
         return {'epoch': ckpt.get('epoch', 0), 'best_loss': ckpt.get('best_loss', float('inf'))}

@@ -35,7 +35,8 @@ class RatioTrainer:
         loss, metrics = self.loss_fn(*self._scores(batch))
         self.optimizer.zero_grad()
         loss.backward()
-        torch.nn.utils.clip_grad_norm_(self.model.parameters(), max_norm=1.0)
+        if getattr(self.optimizer, 'max_grad_norm', None) is None:  # (utils.optim.Adam clips inside its step)
+            torch.nn.utils.clip_grad_norm_(self.model.parameters(), max_norm=1.0)
         self.optimizer.step()
         return metrics
 
