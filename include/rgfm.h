@@ -773,6 +773,46 @@ int rgfm_fmnet_sample_pair_diag(rgfm_fmnet* hx, rgfm_fmnet* hy, float* x_inout, 
                                 void* ws, size_t ws_bytes, rgfm_stream_t stream);
 
 /* ------------------------------------------------------------------------
+ * Cross pairing of the MC set (U-Net pairs).  Added functions only: the ABI version is unchanged.
+ *
+ * The paired MC guidance uses the n_mc pairs (mc_x1[i], mc_y1[i]).  Every (mc_x1[i], mc_y1[j]) is as valid a draw
+ * from the product of the marginals, so the same MC set yields n_mc^2 importance pairs.  Cross pairing is the
+ * reference block (src/utils/flow_utils.py:273-369, src/sample_mnist_svhn.py:124-171) on that list of n_mc^2 pairs
+ * with ratios ratio_matrix[i][j] = r(mc_x1[i], mc_y1[j]) ([n_mc][n_mc] row-major, x index first:
+ * rgfm_ratio_eval_cross).  The Gaussian factor of pair (i, j) is a_i b_j, so only the marginals of the weights are
+ * ever formed:
+ *   a_i = exp(lx_i - max lx), b_j = exp(ly_j - max ly),  u = R b,  s = R^T a,
+ *   p_bar = (sum a)(sum b) / n_mc^2 + 1e-10,  Z_bar = a^T R b / n_mc^2 + 1e-10,
+ *   wx_i = sum_j w_ij ~ a_i u_i,  wy_j = sum_i w_ij ~ b_j s_j,  each summing to 1,
+ *   g_x = sum_i wx_i (mc_x1[i] - x) / (1 - t + 1e-3),  g_y = sum_j wy_j (mc_y1[j] - y) / (1 - t + 1e-3).
+ * 1 <= n_mc <= 1024; dim_x, dim_y multiples of 4.  wx_out / wy_out [batch][n_mc]: optional (may be null).
+ *
+ * Diagnostics records of a cross call: RGFM_DIAG_ESS is the JOINT effective sample size
+ * (sum_ij w_ij)^2 / sum_ij w_ij^2, 1 .. n_mc^2; RGFM_DIAG_W_MAX / _W_MIN the max and min over the 2 n_mc marginal
+ * weights wx, wy; RGFM_DIAG_Z_BAR the Z_bar above; the four norms as before, g from the marginal weights.
+ *
+ * rgfm_sample_pair_cross is rgfm_sample_pair_diag with the ratio matrix in the ratio vector's place: one entry point
+ * for both solvers; diag_out null with diag_records 0 = no diagnostics; n_mc = 0 = unguided.  A cross call runs
+ * kernel by kernel (no hipGraph replay).  All argument errors (null pointers, n_mc above 1024, flattened sizes that
+ * are no multiples of 4, a short workspace, short diag_records) are returned before anything is enqueued.
+ * ---------------------------------------------------------------------- */
+int rgfm_guidance_cross_workspace_bytes(int batch, int n_mc, int dim_x, int dim_y, size_t* bytes);
+int rgfm_guidance_apply_cross(const float* x, const float* y, float* vx, float* vy, const float* mc_x1,
+                              const float* mc_y1, const float* ratio_matrix, int batch, int n_mc, int dim_x, int dim_y,
+                              double t, double gamma, float* wx_out, float* wy_out, void* ws, size_t ws_bytes,
+                              rgfm_stream_t stream);
+/* (v is read; nothing but diag_out [batch][RGFM_DIAG_FLOATS] and the workspace is written) */
+int rgfm_guidance_diag_cross(const float* x, const float* y, const float* vx, const float* vy, const float* mc_x1,
+                             const float* mc_y1, const float* ratio_matrix, int batch, int n_mc, int dim_x, int dim_y,
+                             double t, float* diag_out, void* ws, size_t ws_bytes, rgfm_stream_t stream);
+int rgfm_sample_pair_cross_workspace_bytes(const rgfm_unet* hx, const rgfm_unet* hy, int batch, int n_mc, int solver,
+                                           size_t* bytes);
+int rgfm_sample_pair_cross(rgfm_unet* hx, rgfm_unet* hy, float* x_inout, float* y_inout, const float* mc_x1,
+                           const float* mc_y1, const float* ratio_matrix, int n_mc, int batch, int num_steps,
+                           double gamma, int step_begin, int step_end, int solver, float* diag_out,
+                           size_t diag_records, void* ws, size_t ws_bytes, rgfm_stream_t stream);
+
+/* ------------------------------------------------------------------------
  * Bench support: per-kernel-class device time measured with hipEvents on the
  * launch stream (bench.py's roofline line).  Timing is off by default.
  * ---------------------------------------------------------------------- */

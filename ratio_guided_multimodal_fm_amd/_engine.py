@@ -1017,11 +1017,12 @@ def _diag_fn(name):
     return (stem[:-4] if stem.endswith("_ode") else stem) + "_diag" + tail
 
 
-def _run_loop(fn, ws_fn, ws_args, args, steps, sid, dev, ws=None, diag=None):
+def _run_loop(fn, ws_fn, ws_args, args, steps, sid, dev, ws=None, diag=None, cross=False):
     """One native sampler loop: the size query `ws_fn`(*ws_args[, sid]), the workspace (`ws`: a _Workspace; default the
     samplers' shared one), then `fn`(*args, *steps[, sid], workspace, stream).  `steps`: (step_begin, step_end).  sid
     None: entry points without a solver argument (the FlowMatchingModel loops).  `diag`: a records tensor
-    [n_stages, B, RGFM_DIAG_FLOATS] -- the loop's *_diag twin runs and fills it (guided loops only)."""
+    [n_stages, B, RGFM_DIAG_FLOATS] -- the loop's *_diag twin runs and fills it (guided loops only).  `cross`: the
+    U-Net pair loop over all pairs of the MC set (rgfm_sample_pair_cross: one entry point with and without records)."""
     L = _lib.lib()
     tail = () if sid is None else (sid,)
     sink = ()
@@ -1032,6 +1033,9 @@ def _run_loop(fn, ws_fn, ws_args, args, steps, sid, dev, ws=None, diag=None):
                                  f"expected, got {tuple(diag.shape)} {diag.dtype} on {diag.device}")
         fn, ws_fn = _diag_fn(fn), _diag_fn(ws_fn)
         sink = (_ptr(diag), diag.shape[0] * diag.shape[1])
+    if cross:
+        fn, ws_fn = "rgfm_sample_pair_cross", "rgfm_sample_pair_cross_workspace_bytes"
+        sink = sink or (None, 0)
     nb = ctypes.c_size_t()
     _lib.check(getattr(L, ws_fn)(*ws_args, *tail, ctypes.byref(nb)))
     buf = (ws or _sampler_ws).get(nb.value, dev)
@@ -1127,7 +1131,11 @@ def sample_pair(fm_x, fm_y, x, y, mc_x1, mc_y1, mc_ratios, num_steps, gamma, ste
                 step_end=None, solver='euler', diag=None):
     """In-place paired loop with optional MC guidance (rgfm_sample_pair; solver='midpoint': rgfm_sample_pair_ode).
     `diag`: a records tensor [n_stages, B, 8] to fill (rgfm_sample_pair_diag / rgfm_fmnet_sample_pair_diag; the state
-    keeps its bits); the other guided loops below take it the same way."""
+    keeps its bits); the other guided loops below take it the same way.
+
+    `mc_ratios` [N]: the ratios of the N pairs (mc_x1[i], mc_y1[i]).  `mc_ratios` [N, N] (x index first, what
+    RatioEngine.eval_cross returns): cross pairing, the guidance over all N x N pairs (mc_x1[i], mc_y1[j])
+    (rgfm_sample_pair_cross; U-Net nets, N <= 1024)."""
     sid = _solver(solver, fm_x, fm_y)
     for m in (fm_x, fm_y):
         m._engine._check_eval(m)
@@ -1144,6 +1152,9 @@ def sample_pair(fm_x, fm_y, x, y, mc_x1, mc_y1, mc_ratios, num_steps, gamma, ste
     if B == 0:
         return x, y
     n_mc = 0 if mc_x1 is None else mc_x1.shape[0]
+    cross = bool(n_mc) and mc_ratios.dim() == 2
+    if cross:
+        _check_cross(mc_ratios.shape, n_mc, mc_y1.shape[0], fm_x, fm_y)
     if n_mc:
         mc_x1, mc_y1, mc_ratios = mc_x1.contiguous(), mc_y1.contiguous(), mc_ratios.contiguous()
 
@@ -1153,7 +1164,7 @@ def sample_pair(fm_x, fm_y, x, y, mc_x1, mc_y1, mc_ratios, num_steps, gamma, ste
             _run_loop(ex.PAIR, ex.PAIR_WS, (hx, hy, B, n_mc),
                       (hx, hy, _ptr(x), _ptr(y), _ptr(mc_x1 if n_mc else None), _ptr(mc_y1 if n_mc else None),
                        _ptr(mc_ratios if n_mc else None), n_mc, B, int(num_steps), float(gamma)),
-                      (step_begin, step_end), _solver_arg(ex, sid), dev, diag=diag)
+                      (step_begin, step_end), _solver_arg(ex, sid), dev, diag=diag, cross=cross)
         return x, y
     return _range_guarded(dev, [x, y], run, [fm_x._engine, fm_y._engine])
 
@@ -1203,6 +1214,62 @@ def guidance_apply(x, y, vx, vy, mc_x1, mc_y1, mc_ratios, t, gamma, want_weights
                                          _ptr(mc_ratios.contiguous()), B, N, dx, dy, float(t),
                                          float(gamma), _ptr(w), _ptr(ws), nb.value, _stream(dev)))
     return w
+
+
+CROSS_MAX_N = 1024  # GUID_CROSS_MAX_N of csrc/rgfm_host.h
+
+
+def _check_cross(shape, n_x, n_y, *models):
+    """Argument checks of a cross-pairing call, before any device work."""
+    for m in models:
+        if not isinstance(m._engine, UNetEngine):
+            raise _lib.RgfmError("cross pairing (a ratio matrix over all pairs of the MC set) needs U-Net velocity nets "
+                                 f"(FlexibleUNet and its presets); {type(m).__name__} has the paired loop only")
+    if n_x != n_y or tuple(shape) != (n_x, n_x):
+        raise _lib.RgfmError(f"cross pairing needs equal MC counts and a ratio matrix [N, N] (x index first); got "
+                             f"{n_x} x samples, {n_y} y samples and ratios of shape {tuple(shape)}")
+    if not 1 <= n_x <= CROSS_MAX_N:
+        raise _lib.RgfmError(f"cross pairing takes 1 <= N <= {CROSS_MAX_N} MC samples per modality, got {n_x}")
+
+
+def guidance_apply_cross(x, y, vx, vy, mc_x1, mc_y1, ratio_matrix, t, gamma, want_weights=False):
+    """One guidance evaluation over all N x N pairs of the MC set (rgfm_guidance_apply_cross; parity hook): overwrites
+    vx, vy; returns the marginal weights (wx [B, N], wy [B, N]) or None.  ratio_matrix [N, N]: r(mc_x1[i], mc_y1[j])."""
+    _require_hip(x, y, vx, vy, mc_x1, mc_y1, ratio_matrix)
+    B, N, dev = x.shape[0], mc_x1.shape[0], x.device
+    _check_cross(ratio_matrix.shape, N, mc_y1.shape[0])
+    dx, dy = x[0].numel(), y[0].numel()
+    wx, wy = (torch.empty(B, N, device=dev), torch.empty(B, N, device=dev)) if want_weights else (None, None)
+    L = _lib.lib()
+    with torch.cuda.device(dev):
+        nb = ctypes.c_size_t()
+        _lib.check(L.rgfm_guidance_cross_workspace_bytes(B, N, dx, dy, ctypes.byref(nb)))
+        ws = _sampler_ws.get(nb.value, dev)
+        _lib.check(L.rgfm_guidance_apply_cross(_ptr(x.contiguous()), _ptr(y.contiguous()), _ptr(vx), _ptr(vy),
+                                               _ptr(mc_x1.contiguous()), _ptr(mc_y1.contiguous()),
+                                               _ptr(ratio_matrix.contiguous()), B, N, dx, dy, float(t), float(gamma),
+                                               _ptr(wx), _ptr(wy), _ptr(ws), nb.value, _stream(dev)))
+    return (wx, wy) if want_weights else None
+
+
+def guidance_diag_cross(x, y, vx, vy, mc_x1, mc_y1, ratio_matrix, t):
+    """Diagnostics of one evaluation of the cross-pairing block (rgfm_guidance_diag_cross): records [B, 8] -- the joint
+    ESS (1 .. N^2), the range over the 2N marginal weights, Z_bar, the four norms; nothing else is written."""
+    _require_hip(x, y, vx, vy, mc_x1, mc_y1, ratio_matrix)
+    B, N, dev = x.shape[0], mc_x1.shape[0], x.device
+    _check_cross(ratio_matrix.shape, N, mc_y1.shape[0])
+    dx, dy = x[0].numel(), y[0].numel()
+    out = torch.empty(B, _lib.DIAG_FLOATS, device=dev)
+    L = _lib.lib()
+    with torch.cuda.device(dev):
+        nb = ctypes.c_size_t()
+        _lib.check(L.rgfm_guidance_cross_workspace_bytes(B, N, dx, dy, ctypes.byref(nb)))
+        ws = _sampler_ws.get(nb.value, dev)
+        _lib.check(L.rgfm_guidance_diag_cross(_ptr(x.contiguous()), _ptr(y.contiguous()), _ptr(vx.contiguous()),
+                                              _ptr(vy.contiguous()), _ptr(mc_x1.contiguous()), _ptr(mc_y1.contiguous()),
+                                              _ptr(ratio_matrix.contiguous()), B, N, dx, dy, float(t), _ptr(out), _ptr(ws),
+                                              nb.value, _stream(dev)))
+    return out
 
 
 def guidance_diag(x, y, vx, vy, mc_x1, mc_y1, mc_ratios, t):

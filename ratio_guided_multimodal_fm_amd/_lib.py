@@ -184,6 +184,16 @@ SIGNATURES = {
     "rgfm_fmnet_sample_pair_diag": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int,
                                             c_int, c_int, c_double, c_int, c_int, c_void_p, c_size_t, c_void_p, c_size_t,
                                             c_void_p]),
+    # cross pairing of the MC set: the ratio matrix [n_mc][n_mc] in the ratio vector's place; two optional weight outputs
+    "rgfm_guidance_cross_workspace_bytes": (c_int, [c_int, c_int, c_int, c_int, P(c_size_t)]),
+    "rgfm_guidance_apply_cross": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int,
+                                          c_int, c_int, c_double, c_double, c_void_p, c_void_p, c_void_p, c_size_t, c_void_p]),
+    "rgfm_guidance_diag_cross": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int,
+                                         c_int, c_int, c_double, c_void_p, c_void_p, c_size_t, c_void_p]),
+    "rgfm_sample_pair_cross_workspace_bytes": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, P(c_size_t)]),
+    "rgfm_sample_pair_cross": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int,
+                                       c_int, c_double, c_int, c_int, c_int, c_void_p, c_size_t, c_void_p, c_size_t,
+                                       c_void_p]),
     "rgfm_profile_enable": (c_int, [c_int]),
     "rgfm_profile_reset": (c_int, []),
     "rgfm_profile_read": (c_int, [c_int, P(c_double), P(c_double), P(c_int64), P(c_double)]),

@@ -30,12 +30,12 @@ struct PairWs {
   NetChain cx, cy;
   float *vx, *vy, *logp, *gstate;
 };
-void carve_pair(Bump& b, PairWs& w, int n_mc) {
+void carve_pair(Bump& b, PairWs& w, int n_mc, int pairing = PAIRING_PAIRED) {
   const int batch = w.cx.batch;
   w.cx.carve(b), w.cy.carve(b);
   w.vx = b.f((size_t)batch * w.cx.image_floats());
   w.vy = b.f((size_t)batch * w.cy.image_floats());
-  w.logp = b.f(guid_scratch_bytes(batch, n_mc) / sizeof(float));
+  w.logp = b.f(guid_scratch_bytes(batch, n_mc, pairing) / sizeof(float));
   w.gstate = b.f(64 + (size_t)TABLE_ROWS * 4);  // step counter + per-step guidance scalars (graph replay)
   w.cx.carve_eval(), w.cy.carve_eval();         // the two nets run concurrently: disjoint regions
 }
@@ -211,16 +211,17 @@ extern "C" int rgfm_guidance_apply_cond(const float* s, float* v, const float* m
 namespace {
 int guidance_diag(const float* x, const float* y, const float* vx, const float* vy, const float* mx, const float* my,
                   const float* r, int batch, int n_mc, int dx, int dy, double t, int ratio_stride, float* diag_out, void* ws,
-                  size_t ws_bytes, rgfm_stream_t stream) {
+                  size_t ws_bytes, rgfm_stream_t stream, int pairing = PAIRING_PAIRED) {
   size_t need = 0;
-  int rc = rgfm_guidance_diag_workspace_bytes(batch, n_mc, dx, dy, &need);
+  int rc = pairing == PAIRING_CROSS ? rgfm_guidance_cross_workspace_bytes(batch, n_mc, dx, dy, &need)
+                                    : rgfm_guidance_diag_workspace_bytes(batch, n_mc, dx, dy, &need);
   if (rc) return rc;
   if (n_mc > 4096) return fail(RGFM_EINVAL, "n_mc too large (max 4096)");
   if (need > ws_bytes) return fail(RGFM_ENOMEM, "workspace too small: %zu < %zu", ws_bytes, need);
   if ((rc = ensure_init())) return rc;
   hipStream_t s = (hipStream_t)stream;
   Bump b(ws, ws_bytes);
-  float* scratch = b.f(guid_scratch_bytes(batch, n_mc) / sizeof(float));
+  float* scratch = b.f(guid_scratch_bytes(batch, n_mc, pairing) / sizeof(float));
   DiagSink sink;
   if ((rc = sink.check(diag_out, (size_t)batch, batch, 1, SOLVER_EULER))) return rc;
   sink.carve(b, dx, dy);
@@ -228,7 +229,7 @@ int guidance_diag(const float* x, const float* y, const float* vx, const float* 
   const GuidDiag gd{sink.next(), sink.gx, sink.gy};
   // (phase 3 reads v and writes none of the block's outputs: the casts drop a const that is kept)
   rc = guidance_launch(x, y, const_cast<float*>(vx), const_cast<float*>(vy), mx, my, r, batch, n_mc, dx, dy, t, 0.0, scratch,
-                       nullptr, nullptr, nullptr, 0.f, s, nullptr, nullptr, 3, ratio_stride, nullptr, nullptr, &gd);
+                       nullptr, nullptr, nullptr, 0.f, s, nullptr, nullptr, 3, ratio_stride, nullptr, nullptr, &gd, pairing);
   if (rc) return rc;
   HIP_TRY(hipGetLastError());
   return RGFM_OK;
@@ -314,30 +315,39 @@ int cond_loop(rgfm_unet* h, float* s_inout, const float* mc_set, const float* ra
   return RGFM_OK;
 }
 
-int pair_bytes(const rgfm_unet* hx, const rgfm_unet* hy, int batch, int n_mc, int solver, size_t* bytes, bool diag = false) {
+int pair_bytes(const rgfm_unet* hx, const rgfm_unet* hy, int batch, int n_mc, int solver, size_t* bytes, bool diag = false,
+               int pairing = PAIRING_PAIRED) {
   if (int rc = check_solver_id(solver)) return rc;
   if (!hx || !hy || !bytes || batch < 1 || n_mc < 0) return fail(RGFM_EINVAL, "bad argument");
   Bump b;
   PairWs w{{const_cast<rgfm_unet*>(hx), batch, solver}, {const_cast<rgfm_unet*>(hy), batch, solver}};
-  carve_pair(b, w, n_mc);
+  carve_pair(b, w, n_mc, pairing);
   *bytes = b.off + (diag ? diag_scratch_bytes(batch, w.cx.image_floats(), w.cy.image_floats()) : 0);
   return RGFM_OK;
 }
 
 int pair_sample(rgfm_unet* hx, rgfm_unet* hy, float* x_inout, float* y_inout, const float* mc_x1, const float* mc_y1,
                 const float* mc_ratios, int n_mc, int batch, int num_steps, double gamma, int step_begin, int step_end,
-                int solver, void* ws, size_t ws_bytes, rgfm_stream_t stream, float* diag_out = nullptr, size_t diag_records = 0) {
+                int solver, void* ws, size_t ws_bytes, rgfm_stream_t stream, float* diag_out = nullptr, size_t diag_records = 0,
+                int pairing = PAIRING_PAIRED) {
   refresh_modes();
   int ns = 0;
   if (int rc = check_loop(solver, hx && hy && x_inout && y_inout && ws, batch, num_steps, step_begin, step_end, &ns))
     return rc;
   if (n_mc < 0 || (n_mc > 0 && (!mc_x1 || !mc_y1 || !mc_ratios))) return fail(RGFM_EINVAL, "MC set missing");
+  if (pairing == PAIRING_CROSS) {  // (what guidance_launch would refuse at the first guided stage, before anything is enqueued)
+    if (n_mc > GUID_CROSS_MAX_N) return fail(RGFM_EINVAL, "cross pairing: n_mc %d too large (max %d)", n_mc, GUID_CROSS_MAX_N);
+    for (const rgfm_unet* h : {hx, hy})
+      if ((h->d.in_channels * h->d.img_size * h->d.img_size) % 4) return fail(RGFM_EINVAL, "flattened image sizes must be multiples of 4");
+  }
   DiagSink sink;
   if (int rc = sink.check(diag_out, diag_records, batch, ns, solver)) return rc;
   Bump b(ws, ws_bytes);
   PairWs w{{hx, batch, solver}, {hy, batch, solver}};
-  carve_pair(b, w, n_mc);
+  carve_pair(b, w, n_mc, pairing);
   if (sink.on()) sink.carve(b, w.cx.image_floats(), w.cy.image_floats());
+  else if (pairing == PAIRING_CROSS)  // (one workspace query for calls with and without records: the same carve)
+    (void)b.f((size_t)batch * w.cx.image_floats()), (void)b.f((size_t)batch * w.cy.image_floats());
   if (int rc = check_workspace(b, ws_bytes)) return rc;
   if (ns == 0) return RGFM_OK;
   hipStream_t s = (hipStream_t)stream;
@@ -348,7 +358,7 @@ int pair_sample(rgfm_unet* hx, rgfm_unet* hy, float* x_inout, float* y_inout, co
   auto net = [](NetChain& c) { return [&c](auto... a) { return c.eval(a...); }; };  // pair_loop's eval: NetChain::eval
   return pair_loop(net(w.cx), net(w.cy), x_inout, y_inout, mc_x1, mc_y1, mc_ratios, n_mc, batch, num_steps, gamma, step_begin, ns,
                    (int)w.cx.image_floats(), (int)w.cy.image_floats(), w.vx, w.vy, w.logp, s, w.gstate, solver, w.cx.mid,
-                   w.cy.mid, sink.on() ? &sink : nullptr);
+                   w.cy.mid, sink.on() ? &sink : nullptr, pairing);
 }
 
 }  // namespace
@@ -414,4 +424,51 @@ extern "C" int rgfm_sample_pair_diag(rgfm_unet* hx, rgfm_unet* hy, float* x_inou
                                      size_t diag_records, void* ws, size_t ws_bytes, rgfm_stream_t stream) {
   return pair_sample(hx, hy, x_inout, y_inout, mc_x1, mc_y1, mc_ratios, n_mc, batch, num_steps, gamma, step_begin, step_end,
                      solver, ws, ws_bytes, stream, diag_out, diag_records);
+}
+
+// ---- cross pairing: all n_mc x n_mc pairs of the MC set (include/rgfm.h, "Cross pairing of the MC set")
+// workspace of the block: the cross scratch (rgfm_host.h), then the two scratch velocities of the diagnostics call
+extern "C" int rgfm_guidance_cross_workspace_bytes(int batch, int n_mc, int dim_x, int dim_y, size_t* bytes) {
+  if (!bytes || batch < 1 || dim_x < 1 || dim_y < 1) return fail(RGFM_EINVAL, "bad argument");
+  if (n_mc < 1 || n_mc > GUID_CROSS_MAX_N) return fail(RGFM_EINVAL, "cross pairing: 1 <= n_mc <= %d (got %d)", GUID_CROSS_MAX_N, n_mc);
+  if (dim_x % 4 || dim_y % 4) return fail(RGFM_EINVAL, "flattened image sizes must be multiples of 4");
+  *bytes = guid_cross_scratch_bytes(batch, n_mc) + diag_scratch_bytes(batch, dim_x, dim_y);
+  return RGFM_OK;
+}
+extern "C" int rgfm_guidance_apply_cross(const float* x, const float* y, float* vx, float* vy, const float* mc_x1,
+                                         const float* mc_y1, const float* ratio_matrix, int batch, int n_mc, int dim_x,
+                                         int dim_y, double t, double gamma, float* wx_out, float* wy_out, void* ws,
+                                         size_t ws_bytes, rgfm_stream_t stream) {
+  if (!x || !y || !vx || !vy || !mc_x1 || !mc_y1 || !ratio_matrix || !ws) return fail(RGFM_EINVAL, "null argument");
+  size_t need = 0;
+  int rc = rgfm_guidance_cross_workspace_bytes(batch, n_mc, dim_x, dim_y, &need);
+  if (rc) return rc;
+  if (need > ws_bytes) return fail(RGFM_ENOMEM, "workspace too small: %zu < %zu", ws_bytes, need);
+  if ((rc = ensure_init())) return rc;
+  rc = guidance_launch(x, y, vx, vy, mc_x1, mc_y1, ratio_matrix, batch, n_mc, dim_x, dim_y, t, gamma, (float*)ws, wx_out,
+                       nullptr, nullptr, 0.f, (hipStream_t)stream, nullptr, nullptr, 0, 0, nullptr, nullptr, nullptr,
+                       PAIRING_CROSS, wy_out);
+  if (rc) return rc;
+  HIP_TRY(hipGetLastError());
+  return RGFM_OK;
+}
+extern "C" int rgfm_guidance_diag_cross(const float* x, const float* y, const float* vx, const float* vy, const float* mc_x1,
+                                        const float* mc_y1, const float* ratio_matrix, int batch, int n_mc, int dim_x,
+                                        int dim_y, double t, float* diag_out, void* ws, size_t ws_bytes, rgfm_stream_t stream) {
+  if (!x || !y || !vx || !vy || !mc_x1 || !mc_y1 || !ratio_matrix || !diag_out || !ws) return fail(RGFM_EINVAL, "null argument");
+  return guidance_diag(x, y, vx, vy, mc_x1, mc_y1, ratio_matrix, batch, n_mc, dim_x, dim_y, t, 0, diag_out, ws, ws_bytes, stream,
+                       PAIRING_CROSS);
+}
+// (one query for calls with and without diagnostics: the scratch velocities are always counted)
+extern "C" int rgfm_sample_pair_cross_workspace_bytes(const rgfm_unet* hx, const rgfm_unet* hy, int batch, int n_mc, int solver,
+                                                      size_t* bytes) {
+  if (n_mc > GUID_CROSS_MAX_N) return fail(RGFM_EINVAL, "cross pairing: n_mc %d too large (max %d)", n_mc, GUID_CROSS_MAX_N);
+  return pair_bytes(hx, hy, batch, n_mc, solver, bytes, true, PAIRING_CROSS);
+}
+extern "C" int rgfm_sample_pair_cross(rgfm_unet* hx, rgfm_unet* hy, float* x_inout, float* y_inout, const float* mc_x1,
+                                      const float* mc_y1, const float* ratio_matrix, int n_mc, int batch, int num_steps,
+                                      double gamma, int step_begin, int step_end, int solver, float* diag_out,
+                                      size_t diag_records, void* ws, size_t ws_bytes, rgfm_stream_t stream) {
+  return pair_sample(hx, hy, x_inout, y_inout, mc_x1, mc_y1, ratio_matrix, n_mc, batch, num_steps, gamma, step_begin, step_end,
+                     solver, ws, ws_bytes, stream, diag_out, diag_records, PAIRING_CROSS);
 }

@@ -11,6 +11,8 @@
 //               sequence), g = sum_i w_i (m_i - x)/(1 - t + eps) as an fp32-MFMA
 //               GEMM [B,N] x [N,D], blend (1-gamma) v + gamma g, and optionally the
 //               Euler update.
+//   guid_cross_*: with cross pairing (all N x N pairs of the MC set) the weights stage between the two: one marginal
+//               weight row per modality from the distance slices and the ratio matrix (below, "cross pairing")
 // guid_logp is a VALU-bound elementwise reduction, guid_apply a small fp32 GEMM; the MC set
 // (N x D) stays L2-resident.
 #include "rgfm_device.h"
@@ -243,7 +245,9 @@ __global__ __launch_bounds__(256, 2) void guid_apply_mfma_kernel(const GuidanceA
   const int KH = (N + 7) >> 3;              // samples per (wave, lane half)
   const int k0 = (wave * 2 + hf) * KH;
   const bool rowok = b0 + l31 < B;
-  const float* wrow = a.wbuf + (size_t)(rowok ? b0 + l31 : 0) * N;
+  const float* wb = part && a.wbuf_y ? a.wbuf_y : a.wbuf;  // (cross pairing: the y column blocks have weights of their own)
+  const float* wsm = part && a.wbuf_y ? a.wsum_y : a.wsum;
+  const float* wrow = wb + (size_t)(rowok ? b0 + l31 : 0) * N;
   const float* mcol = M + (dok ? d : 0);
   constexpr int U = 16;  // samples per group: two groups of registers, one being multiplied (64 MFMAs, 1.7 us) while the other loads
   struct Grp {
@@ -303,7 +307,7 @@ __global__ __launch_bounds__(256, 2) void guid_apply_mfma_kernel(const GuidanceA
     const size_t o = (size_t)(b < B ? b : 0) * D + (dok ? d : 0);
     ex[rr] = *reinterpret_cast<const f32x4*>(X + o);
     ev[rr] = *reinterpret_cast<const f32x4*>(V + o);
-    esw[rr] = a.wsum[b < B ? b : 0];
+    esw[rr] = wsm[b < B ? b : 0];
   }
   // partial tiles -> LDS; wave w then owns accumulator rows r = 4w .. 4w + 3: output rows b0 + 8w + 4 (lane / 32) + (r & 3)
 #pragma unroll
@@ -348,6 +352,165 @@ __global__ __launch_bounds__(256, 2) void guid_apply_mfma_kernel(const GuidanceA
       *reinterpret_cast<f32x4*>(V + o) = nv;
     }
   }
+}
+
+// ---- cross pairing: the importance weights over all N x N pairs (x1_i, y1_j) of the MC set, R_ij = r(x1_i, y1_j)
+// (GuidanceArgs::mc_ratios is then the matrix [N][N], x index first).  The Gaussian factor of pair (i, j) is a_i b_j,
+//   a_i = exp(lx_i - max lx),  b_j = exp(ly_j - max ly),  lx / ly: the two terms of logp_of, each rounded as there,
+// so the reference block on the list of N^2 pairs (p_bar = mean a_i b_j + 1e-10, Z_bar = mean R_ij a_i b_j + 1e-10,
+// w_ij = (R_ij / Z_bar)(a_i b_j / p_bar) normalised by its sum + 1e-10) needs only the weights' marginals
+//   wx_i = sum_j w_ij ~ a_i u_i,  u = R b        wy_j = sum_i w_ij ~ b_j s_j,  s = R^T a
+// and nothing of size N^2 per row.  Three launches: guid_cross_ab_kernel (a, b), guid_cross_prod_kernel (the two
+// [B, N] x [N, N] products; a third, q = (R o R) b^2, for the joint ESS when diagnostics are on) and guid_cross_fin_kernel
+// (the marginals wx -> wbuf / wsum, wy -> wbuf_y / wsum_y, which guid_apply_mfma_kernel reads per modality).
+__global__ __launch_bounds__(256) void guid_cross_ab_kernel(const GuidanceArgs a_in) {
+  const GuidanceArgs a = with_schedule(a_in);
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  const int N = a.N;
+  const int b = blockIdx.x * 4 + wave;
+  if (b >= a.B) return;
+  float* pa = a.ca + (size_t)b * N;
+  float* pb = a.cb + (size_t)b * N;
+  float mxa = -INFINITY, mxb = -INFINITY;
+  for (int i = lane; i < N; i += 64) {  // (each lane reads back only what it wrote itself)
+    double sx = 0.0, sy = 0.0;
+    for (int z = 0; z < a.nsx; ++z) sx += a.dist[((size_t)z * a.B + b) * N + i];
+    for (int z = a.nsx; z < a.nsx + a.nsy; ++z) sy += a.dist[((size_t)z * a.B + b) * N + i];
+    const float lx = __fadd_rn(0.f, __fmul_rn(-0.5f, (float)sx) / a.s2);
+    const float ly = __fadd_rn(0.f, __fmul_rn(-0.5f, (float)sy) / a.s2);
+    pa[i] = lx, pb[i] = ly;
+    mxa = fmaxf(mxa, lx), mxb = fmaxf(mxb, ly);
+  }
+  mxa = wave_max_g(mxa), mxb = wave_max_g(mxb);
+  for (int i = lane; i < N; i += 64) pa[i] = expf(pa[i] - mxa), pb[i] = expf(pb[i] - mxb);
+}
+
+// out[b][c] = sum_k A[b][k] M[k][c] on v_mfma_f32_32x32x2_f32 (exact fp32 products, fp32 accumulation; every term is
+// non-negative), blockIdx.z picking the product:
+//   0: s = a R      (M[k][c] = R[k][c])        1: u = b R^T      (M[k][c] = R[c][k])
+//   2: q = b^2 (R o R)^T  (M[k][c] = R[c][k]^2; diagnostics only)
+// Workgroup = 32 rows x 128 columns, wave w the 32 x 32 tile of columns 32 w ..; k in chunks of 32 staged through LDS
+// (R does not fit: 4 MB at N = 1024), where the transposed products turn R's rows into columns -- both global reads
+// run along R's rows.  Rows, columns and k past the end are staged as zeros: any 1 <= N <= 1024, any B.  A row's sum
+// runs over k in index order, two terms per MFMA: fixed by N, the same in every batch.
+constexpr int XK = 32, XAS = XK + 1, XBS = 128 + 1;
+__global__ __launch_bounds__(256) void guid_cross_prod_kernel(const GuidanceArgs a) {
+  __shared__ float sA[32 * XAS];
+  __shared__ float sB[XK * XBS];
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const int l31 = lane & 31, hf = lane >> 5;
+  const int N = a.N, B = a.B;
+  const int z = blockIdx.z;
+  const int b0 = blockIdx.x * 32, c0 = blockIdx.y * 128;
+  const float* A = z == 0 ? a.ca : a.cb;
+  const float* R = a.mc_ratios;
+  float* out = z == 0 ? a.cs : z == 1 ? a.cu : a.cq;
+  f32x16 acc;
+#pragma unroll
+  for (int r = 0; r < 16; ++r) acc[r] = 0.f;
+  for (int k0 = 0; k0 < N; k0 += XK) {
+    __syncthreads();
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+      const int e = tid + 256 * j, k = e & 31, row = e >> 5;
+      const bool ok = b0 + row < B && k0 + k < N;
+      float v = A[ok ? (size_t)(b0 + row) * N + k0 + k : 0];
+      v = ok ? v : 0.f;
+      sA[row * XAS + k] = z == 2 ? v * v : v;
+    }
+#pragma unroll
+    for (int j = 0; j < 16; ++j) {
+      const int e = tid + 256 * j;
+      const int k = z == 0 ? e >> 7 : e & 31, c = z == 0 ? e & 127 : e >> 5;
+      const bool ok = k0 + k < N && c0 + c < N;
+      const size_t g = z == 0 ? (size_t)(k0 + k) * N + c0 + c : (size_t)(c0 + c) * N + k0 + k;
+      float v = R[ok ? g : 0];
+      v = ok ? v : 0.f;
+      sB[k * XBS + c] = z == 2 ? v * v : v;
+    }
+    __syncthreads();
+#pragma unroll
+    for (int kk = 0; kk < XK / 2; ++kk) {
+      const int k = 2 * kk + hf;
+      acc = __builtin_amdgcn_mfma_f32_32x32x2f32(sA[l31 * XAS + k], sB[k * XBS + wave * 32 + l31], acc, 0, 0, 0);
+    }
+  }
+  const int c = c0 + wave * 32 + l31;
+#pragma unroll
+  for (int r = 0; r < 16; ++r) {  // accumulator r of a lane: row 8 (r / 4) + 4 (lane / 32) + r % 4, column lane % 32
+    const int b = b0 + 8 * (r >> 2) + 4 * hf + (r & 3);
+    if (b < B && c < N) out[(size_t)b * N + c] = acc[r];
+  }
+}
+
+// The marginal weights of one row per wave, from a, b, u, s: with E = a.u (= b.s up to rounding)
+//   p_bar = (sum a)(sum b) / N^2 + 1e-10,  Z_bar = E / N^2 + 1e-10,
+//   wx_i = (u_i / Z_bar)(a_i / p_bar) / (their sum + 1e-10),  wy_j = (s_j / Z_bar)(b_j / p_bar) / (their sum + 1e-10)
+// -- the operation order of guid_weights_kernel with u / s in the ratio's place; each marginal is normalised by its own
+// sum (the two sums are the same number, sum_ij w_ij, up to rounding).  A zero row (column) of R gives u_i (s_j) = 0 and
+// a weight of exactly 0.  Diagnostics: Z_bar, the range over the 2N marginal weights and the joint effective sample
+// size (sum_ij w_ij)^2 / sum_ij w_ij^2 = (a.u)^2 / (a^2 . q), formed from u / Z_bar and q / Z_bar^2 so that the
+// scale of R cancels before anything is squared.
+__global__ __launch_bounds__(256) void guid_cross_fin_kernel(const GuidanceArgs a) {
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  const int N = a.N;
+  const int b = blockIdx.x * 4 + wave;
+  if (b >= a.B) return;
+  const size_t o = (size_t)b * N;
+  const float *pa = a.ca + o, *pb = a.cb + o, *pu = a.cu + o, *ps = a.cs + o;
+  float *wx = a.wbuf + o, *wy = a.wbuf_y + o;
+  float sa = 0.f, sb = 0.f, e = 0.f;
+  for (int i = lane; i < N; i += 64) {
+    sa += pa[i], sb += pb[i];
+    e += __fmul_rn(pa[i], pu[i]);
+  }
+  sa = wave_sum_g(sa), sb = wave_sum_g(sb), e = wave_sum_g(e);
+  const float nn = (float)N * (float)N;
+  const float pbar = __fadd_rn(__fmul_rn(sa, sb) / nn, 1e-10f);
+  const float zbar = __fadd_rn(e / nn, 1e-10f);
+  float tx = 0.f, ty = 0.f;
+  for (int i = lane; i < N; i += 64) {
+    const float vx = __fmul_rn(pu[i] / zbar, pa[i] / pbar), vy = __fmul_rn(ps[i] / zbar, pb[i] / pbar);
+    wx[i] = vx, wy[i] = vy;
+    tx += vx, ty += vy;
+  }
+  tx = __fadd_rn(wave_sum_g(tx), 1e-10f), ty = __fadd_rn(wave_sum_g(ty), 1e-10f);
+  float rx = 0.f, ry = 0.f, mx = -INFINITY, mn = INFINITY;
+  for (int i = lane; i < N; i += 64) {
+    const float vx = wx[i] / tx, vy = wy[i] / ty;
+    wx[i] = vx, wy[i] = vy;
+    if (a.weights_out) a.weights_out[o + i] = vx;
+    if (a.weights_out_y) a.weights_out_y[o + i] = vy;
+    rx += vx, ry += vy;
+    mx = fmaxf(mx, fmaxf(vx, vy)), mn = fminf(mn, fminf(vx, vy));
+  }
+  rx = wave_sum_g(rx), ry = wave_sum_g(ry);
+  if (lane == 0) a.wsum[b] = rx, a.wsum_y[b] = ry;
+  if (!a.diag_rec) return;
+  const float* pq = a.cq + o;
+  float es = 0.f, fs = 0.f;
+  for (int i = lane; i < N; i += 64) {
+    es += __fmul_rn(pa[i], pu[i] / zbar);
+    fs += __fmul_rn(__fmul_rn(pa[i], pa[i]), (pq[i] / zbar) / zbar);
+  }
+  es = wave_sum_g(es), fs = wave_sum_g(fs);
+  mx = wave_max_g(mx);
+#pragma unroll
+  for (int s = 32; s > 0; s >>= 1) mn = fminf(mn, __shfl_xor(mn, s));
+  if (lane == 0) {
+    float* r = a.diag_rec + (size_t)b * RGFM_DIAG_FLOATS;
+    r[RGFM_DIAG_ESS] = fs > 0.f ? es * es / fs : 0.f;
+    r[RGFM_DIAG_W_MAX] = mx;
+    r[RGFM_DIAG_W_MIN] = mn;
+    r[RGFM_DIAG_Z_BAR] = zbar;
+  }
+}
+
+void launch_guid_cross_weights(const GuidanceArgs& a, hipStream_t s) {  // (needs the distances only: no velocity)
+  const dim3 rows((a.B + 3) / 4);
+  hipLaunchKernelGGL(guid_cross_ab_kernel, rows, dim3(256), 0, s, a);
+  hipLaunchKernelGGL(guid_cross_prod_kernel, dim3((a.B + 31) / 32, (a.N + 127) / 128, a.diag_rec ? 3 : 2), dim3(256), 0, s, a);
+  hipLaunchKernelGGL(guid_cross_fin_kernel, rows, dim3(256), 0, s, a);
 }
 
 // ---- diagnostics (opt-in: launched only for a caller that passes a record buffer; include/rgfm.h, RGFM_DIAG_*)

@@ -826,8 +826,19 @@ inline size_t guid_dist_bytes(int batch, int n_mc) {  // sliced fp64 distances, 
 inline size_t guid_wbuf_bytes(int batch, int n_mc) {  // the step's importance weights [B][N]
   return (((size_t)batch * (n_mc > 0 ? n_mc : 1) * sizeof(float)) + 255) & ~(size_t)255;
 }
+inline size_t guid_wsum_bytes(int batch) { return ((size_t)batch * sizeof(float) + 255) & ~(size_t)255; }
 inline size_t guid_scratch_bytes(int batch, int n_mc) {  // + the weights and their row sums [B]
-  return guid_dist_bytes(batch, n_mc) + guid_wbuf_bytes(batch, n_mc) + (((size_t)batch * sizeof(float) + 255) & ~(size_t)255);
+  return guid_dist_bytes(batch, n_mc) + guid_wbuf_bytes(batch, n_mc) + guid_wsum_bytes(batch);
+}
+// Cross pairing (PAIRING_CROSS: all N x N pairs of the MC set): the paired block's scratch -- its weight rows are the x
+// marginals -- then the y marginals and their row sums, then five [B][N] rows of the weights stage (a, b, u, s, q).
+constexpr int PAIRING_PAIRED = 0, PAIRING_CROSS = 1;
+constexpr int GUID_CROSS_MAX_N = 1024;
+inline size_t guid_cross_scratch_bytes(int batch, int n_mc) {
+  return guid_scratch_bytes(batch, n_mc) + guid_wbuf_bytes(batch, n_mc) + guid_wsum_bytes(batch) + 5 * guid_wbuf_bytes(batch, n_mc);
+}
+inline size_t guid_scratch_bytes(int batch, int n_mc, int pairing) {
+  return pairing == PAIRING_CROSS ? guid_cross_scratch_bytes(batch, n_mc) : guid_scratch_bytes(batch, n_mc);
 }
 
 
@@ -851,16 +862,22 @@ inline int guidance_launch(const float* x, const float* y, float* vx, float* vy,
                     const float* r, int B, int N, int dx, int dy, double t, double gamma, float* logp,
                     float* weights_out, float* xs, float* ys, float dt, hipStream_t s, const float* sched = nullptr,
                     const int* step_ptr = nullptr, int phase = 0, int ratio_stride = 0, const float* xb = nullptr,
-                    const float* yb = nullptr, const GuidDiag* diag = nullptr) {
+                    const float* yb = nullptr, const GuidDiag* diag = nullptr, int pairing = PAIRING_PAIRED,
+                    float* weights_out_y = nullptr) {
   // phase 0: the whole block; 1: distances + importance weights only -- they need the step's (x_t, y_t) and the MC set,
   // not the velocities; 2: the rest (needs v); 3 (with diag): the weights and the diagnostics, v is only read
   // One-sided block (conditional sampling): dy = 0 with y, vy, my, ys null, and ratio_stride = N -- r is then [B][N],
   // a ratio row per sample.  The kernels take the second modality's slices and column blocks from dy, so none is
   // launched; the observed side's Gaussian factor is constant in the MC index and cancels in the normalised weights.
+  // pairing = PAIRING_CROSS: r is the ratio matrix [N][N] (x index first) of all pairs (x1_i, y1_j); the weights stage
+  // writes one marginal weight row per modality (weights_out: x, weights_out_y: y) and logp is guid_cross_scratch_bytes.
   // xb / yb (with xs / ys): the state the update starts from, xs = xb + dt * blended, while the block is evaluated at
   // x / y (second stage of a midpoint step); null or x / y themselves: xs = x + dt * blended.
   if (dx % 4 || dy % 4) return fail(RGFM_EINVAL, "flattened image sizes must be multiples of 4");
   if ((size_t)4 * N * sizeof(float) > 64 * 1024) return fail(RGFM_EINVAL, "n_mc too large (max 4096)");
+  const bool cross = pairing == PAIRING_CROSS;
+  if (cross && (N < 1 || N > GUID_CROSS_MAX_N || dy < 1))
+    return fail(RGFM_EINVAL, "cross pairing needs two modalities and 1 <= n_mc <= %d (got %d)", GUID_CROSS_MAX_N, N);
   // Python-double scalar arithmetic of the reference (sample_mnist_svhn.py:115,127,135,159,170),
   // rounded to fp32 where a tensor op consumes it.
   GuidanceArgs a{};
@@ -875,6 +892,13 @@ inline int guidance_launch(const float* x, const float* y, float* vx, float* vy,
   a.x_base = xb == x ? nullptr : xb, a.y_base = yb == y ? nullptr : yb;
   a.wbuf = reinterpret_cast<float*>(reinterpret_cast<char*>(logp) + guid_dist_bytes(B, N));
   a.wsum = reinterpret_cast<float*>(reinterpret_cast<char*>(a.wbuf) + guid_wbuf_bytes(B, N));
+  if (cross) {
+    float* p = reinterpret_cast<float*>(reinterpret_cast<char*>(logp) + guid_scratch_bytes(B, N));
+    const size_t row = guid_wbuf_bytes(B, N) / sizeof(float), sum = guid_wsum_bytes(B) / sizeof(float);
+    a.wbuf_y = p, a.wsum_y = p + row, p += row + sum;
+    a.ca = p, a.cb = p + row, a.cu = p + 2 * row, a.cs = p + 3 * row, a.cq = p + 4 * row;
+    a.weights_out_y = weights_out_y;
+  }
   a.slice_len = 512;  // 512-element slices (8 x 16 x 4 = 512 workgroups at the benchmark shape) unless that needs more than RGFM_GUID_SLICES of them
   while ((dx + a.slice_len - 1) / a.slice_len + (dy + a.slice_len - 1) / a.slice_len > RGFM_GUID_SLICES) a.slice_len *= 2;
   a.nsx = (dx + a.slice_len - 1) / a.slice_len, a.nsy = (dy + a.slice_len - 1) / a.slice_len;
@@ -884,9 +908,10 @@ inline int guidance_launch(const float* x, const float* y, float* vx, float* vy,
   if (phase != 2) {  // (timer class "guid_logp": the distances AND the importance weights made of them)
     ProfScope p(RGFM_KCLASS_GUID_LOGP, 4.0 * (B + N) * D + dist_b, s);
     launch_guid_logp(a, s);
-    launch_guid_weights(a, s);
+    if (cross) launch_guid_cross_weights(a, s);  // (with diag: the joint ESS, the marginals' range and Z_bar too)
+    else launch_guid_weights(a, s);
   }
-  if (phase != 2 && diag) launch_diag_wstats(a.wbuf, B, N, diag->rec, s);
+  if (phase != 2 && diag && !cross) launch_diag_wstats(a.wbuf, B, N, diag->rec, s);
   if (phase != 1 && diag) {  // before the real apply: in a loop that one moves the state g is taken at
     launch_diag_rownorm(vx, B, dx, diag->rec, RGFM_DIAG_V_NORM_X, s);
     if (dy) launch_diag_rownorm(vy, B, dy, diag->rec, RGFM_DIAG_V_NORM_Y, s);

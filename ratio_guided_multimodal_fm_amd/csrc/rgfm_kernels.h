@@ -437,6 +437,13 @@ struct GuidanceArgs {
   float* weights_out;  // optional [B][N]
   float* wbuf;         // [B][N] importance weights of the step (scratch: behind the distance slices)
   float* wsum;         // [B] their row sums (scratch: behind wbuf)
+  // cross pairing (all N x N pairs of the MC set; mc_ratios is then the matrix R [N][N], x index first; ratio_stride
+  // unused): wbuf / wsum hold the x marginal weights, wbuf_y / wsum_y the y ones, which guid_apply's y column blocks read.
+  // Null wbuf_y: one weight row for both modalities.
+  float* wbuf_y;
+  float* wsum_y;
+  float* weights_out_y;  // optional [B][N] (weights_out: the x marginals)
+  float *ca, *cb, *cu, *cs, *cq;  // scratch [B][N] each: a, b, u = R b, s = R^T a, q = (R o R) b^2 (read with diag_rec only)
   float* diag_rec;     // optional [B][RGFM_DIAG_FLOATS] diagnostics records: guid_weights writes each row's Z_bar into its slot
   float* x_state;      // optional fused Euler: x_state += dt * blended
   float* y_state;
@@ -449,6 +456,7 @@ struct GuidanceArgs {
 constexpr int RGFM_GUID_SLICES = 8;
 void launch_guid_logp(const GuidanceArgs& a, hipStream_t s);   // distances -> GuidanceArgs::dist
 void launch_guid_weights(const GuidanceArgs& a, hipStream_t s);  // distances + ratios -> importance weights (GuidanceArgs::wbuf, wsum)
+void launch_guid_cross_weights(const GuidanceArgs& a, hipStream_t s);  // cross pairing: distances + R -> marginal weights (wbuf, wbuf_y and their sums; the diagnostics' weight entries)
 void launch_guid_apply(const GuidanceArgs& a, hipStream_t s);  // guided velocity (the [B,N] x [N,D] GEMM), blend (+ Euler)
 int guid_apply_init();                                         // (once per process: the GEMM kernel's LDS size)
 void launch_euler(float* x, const float* v, size_t n, float dt, hipStream_t s);

@@ -149,7 +149,8 @@ int pair_loop(EvalX&& eval_x, EvalY&& eval_y, float* x_inout, float* y_inout, co
               const float* mc_y1, const float* mc_ratios, int n_mc, int batch, int num_steps, double gamma,
               int step_begin, int ns, int dx, int dy, float* vx, float* vy, float* logp, hipStream_t caller,
               float* gstate = nullptr, int solver = SOLVER_EULER, float* x_mid = nullptr, float* y_mid = nullptr,
-              DiagSink* diag = nullptr) {
+              DiagSink* diag = nullptr, int pairing = PAIRING_PAIRED) {
+  // pairing = PAIRING_CROSS: mc_ratios is the [n_mc][n_mc] ratio matrix and logp guid_cross_scratch_bytes (guidance_launch)
   // The two velocity nets of a step are independent (reference :119-121): the second one runs on a
   // side stream forked from / joined back into the caller's stream every step, which fills the CUs
   // that one net's small-grid launches (8x8 level, kernel tails) leave idle.
@@ -160,7 +161,8 @@ int pair_loop(EvalX&& eval_x, EvalY&& eval_y, float* x_inout, float* y_inout, co
   hipStream_t side = ds->side;
   hipEvent_t ev_fork = ds->fork, ev_join = ds->join;
   // (diagnostics: kernel by kernel -- each stage writes its own records, a replayed graph would write one stage's)
-  const bool use_graph = gstate && g_modes.graph && !g_prof.on && n_mc > 0 && ns >= 4 && solver == SOLVER_EULER && !diag;
+  // (cross pairing: kernel by kernel as well)
+  const bool use_graph = gstate && g_modes.graph && !g_prof.on && n_mc > 0 && ns >= 4 && solver == SOLVER_EULER && !diag && pairing == PAIRING_PAIRED;
   hipStream_t s = caller;
   if (use_graph && caller == nullptr) {  // (see DevState::main)
     s = ds->main;
@@ -203,13 +205,13 @@ int pair_loop(EvalX&& eval_x, EvalY&& eval_y, float* x_inout, float* y_inout, co
     // other net -- the x net of a pair is the quicker one, so they run in its shadow instead of on the step's critical path
     if (guided && overlap) {
       rc = guidance_launch(xin, yin, vx, vy, mc_x1, mc_y1, mc_ratios, batch, n_mc, dx, dy, g.t, gamma, logp,
-                           nullptr, xout, yout, g.dts, s, sched_dev, step_dev, 1, 0, xb, yb, dg);
+                           nullptr, xout, yout, g.dts, s, sched_dev, step_dev, 1, 0, xb, yb, dg, pairing);
       if (rc) return rc;
     }
     if (overlap) HIP_TRY(hipStreamWaitEvent(s, ev_join, 0));
     if (guided) {
       rc = guidance_launch(xin, yin, vx, vy, mc_x1, mc_y1, mc_ratios, batch, n_mc, dx, dy, g.t, gamma, logp,
-                           nullptr, xout, yout, g.dts, s, sched_dev, step_dev, overlap ? 2 : 0, 0, xb, yb, dg);
+                           nullptr, xout, yout, g.dts, s, sched_dev, step_dev, overlap ? 2 : 0, 0, xb, yb, dg, pairing);
       if (rc) return rc;
     }
     if (step_dev) launch_step_inc(step_dev, s);

@@ -88,7 +88,8 @@ def _all_gather_rows(t, counts, group):
 
 
 def sharded_paired_sampler(fm_x, fm_y, ratio_estimator, guidance_method, guidance_strength, num_steps,
-                           noise, device, backend=None, group=None, gather="rank0", keep=None, solver='euler'):
+                           noise, device, backend=None, group=None, gather="rank0", keep=None, solver='euler',
+                           mc_pairing='paired'):
     """Sharded equivalent of ``paired_sampler`` on explicit host noise.
 
     noise = (x0, y0, mc_x0, mc_y0): the FULL tensors, identical on every rank
@@ -99,9 +100,14 @@ def sharded_paired_sampler(fm_x, fm_y, ratio_estimator, guidance_method, guidanc
     (``mc_x1``, ``mc_y1``, ``mc_ratios``) -- bench.py's parity gate follows rows of the timed call from it.
     solver: 'euler' | 'midpoint', as in ``paired_sampler``; passed to the backend's calls as a keyword when it is
     not the default.
+    mc_pairing: 'paired' only -- cross pairing (``paired_sampler``) has no sharded form: RgfmError.
     """
-    from ._lib import solver_id
+    from ._lib import RgfmError, solver_id
+    from .utils.flow_utils import check_pairing
     solver_id(solver)
+    if check_pairing(mc_pairing, guidance_method) == 'cross':
+        raise RgfmError("mc_pairing='cross' has no sharded form: the ratio matrix couples every MC sample of one modality "
+                        "with every one of the other; run it on one device")
     kw = {'solver': solver} if solver != 'euler' else {}
     backend = backend or HipBackend()
     world = dist.get_world_size(group) if dist.is_initialized() else 1
@@ -205,7 +211,7 @@ def make_sharded_sampler(shape_x, shape_y, backend=None, group=None, gather="all
     launchers do -- and ``sharded_paired_sampler`` slices its rows: consecutive calls consume one generator
     stream exactly like the reference's sweep (evaluate_mnist_svhn.py:80: one seeding, no re-seed)."""
     def sampler(fm_x, fm_y, ratio_estimator=None, guidance_method='none', guidance_strength=0.0, num_samples=16,
-                num_steps=100, device='cuda', mc_batch_size=64, solver='euler'):
+                num_steps=100, device='cuda', mc_batch_size=64, solver='euler', mc_pairing='paired'):
         guided = guidance_method == 'mc_feng' and ratio_estimator is not None
         x0 = torch.randn(num_samples, *shape_x)
         y0 = torch.randn(num_samples, *shape_y)
@@ -213,5 +219,5 @@ def make_sharded_sampler(shape_x, shape_y, backend=None, group=None, gather="all
         my = torch.randn(mc_batch_size, *shape_y) if guided else None
         return sharded_paired_sampler(fm_x, fm_y, ratio_estimator, guidance_method, guidance_strength, num_steps,
                                       (x0, y0, mx, my), torch.device(device), backend=backend, group=group, gather=gather,
-                                      solver=solver)
+                                      solver=solver, mc_pairing=mc_pairing)
     return sampler

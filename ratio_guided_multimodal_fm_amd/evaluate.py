@@ -21,7 +21,7 @@ from .models.ratio_estimator import RatioEstimator
 from .sample import add_common_args, build_flow_models
 from .utils import load_checkpoint, set_seed
 from .utils.diagnostics import GuidanceDiagnostics, add_cli_args as add_diagnostics_args, row_metrics
-from .utils.flow_utils import sample_bimodal_guided
+from .utils.flow_utils import add_pairing_arg, sample_bimodal_guided
 from .utils.path_utils import get_checkpoint_path
 
 
@@ -50,13 +50,18 @@ def evaluate_coherence(samples_x, samples_y, classifier, device, transform_type=
 
 
 def run_sweep(fm_x, fm_y, make_ratio, classifier, methods, strengths, num_samples, num_steps, device,
-              mc_batch_size, transform_type, sampler=sample_bimodal_guided, solver='euler', diagnostics=False):
+              mc_batch_size, transform_type, sampler=sample_bimodal_guided, solver='euler', diagnostics=False,
+              mc_pairing='paired'):
     """The reference's nested loop (:165-222). `make_ratio()` returns a fresh ratio estimator or None.
     `solver` ('euler' | 'midpoint') goes to `sampler` as a keyword when it is not the default.
     `diagnostics`: every guided row also gets ess_mean, ess_min and w_max of the importance weights at step
-    int(0.3 * num_steps) (utils/diagnostics.py); without it the rows keep exactly their keys."""
+    int(0.3 * num_steps) (utils/diagnostics.py); without it the rows keep exactly their keys.
+    `mc_pairing` = 'cross': the 'mc_feng' configurations guide over all mc_batch_size ** 2 pairs of the MC set (the
+    sampler's `mc_pairing` keyword) and their rows record ``"mc_pairing": "cross"``; 'paired' rows keep their keys."""
     from ._lib import solver_id
+    from .utils.flow_utils import check_pairing
     solver_id(solver)
+    check_pairing(mc_pairing)
     kw = {'solver': solver} if solver != 'euler' else {}
     results = []
     for method in methods:
@@ -67,13 +72,14 @@ def run_sweep(fm_x, fm_y, make_ratio, classifier, methods, strengths, num_sample
             if method != 'none' and ratio is None:
                 continue
             diag = GuidanceDiagnostics() if diagnostics and method != 'none' else None
+            cross = {'mc_pairing': 'cross'} if mc_pairing == 'cross' and method == 'mc_feng' else {}
             xs, ys = sampler(fm_x, fm_y, ratio, method, strength, num_samples, num_steps, device, mc_batch_size, **kw,
-                             **({'diagnostics': diag} if diag is not None else {}))
+                             **({'diagnostics': diag} if diag is not None else {}), **cross)
             metrics = evaluate_coherence(xs, ys, classifier, device, transform_type)
             if diag is not None and diag.records is not None:
                 metrics = {**metrics, **row_metrics(diag, num_steps)}
             results.append({'method': method, 'guidance_strength': strength, 'transform_type': transform_type,
-                            **metrics})
+                            **metrics, **cross})
             print(f"  method={method} gamma={strength} -> coherence accuracy {metrics['coherence_acc']:.3f}")
     return results
 
@@ -85,6 +91,7 @@ def main(argv=None):
     p.add_argument('--num_samples', type=int, default=500)
     add_common_args(p, mc_default=256)
     add_diagnostics_args(p, sampling=False)
+    add_pairing_arg(p)
     args = p.parse_args(argv)
 
     set_seed(args.seed)
@@ -116,7 +123,7 @@ def main(argv=None):
 
     results = run_sweep(fm_x, fm_y, make_ratio, classifier, args.guidance_methods, args.guidance_strengths,
                         args.num_samples, args.num_steps, device, args.mc_batch_size, args.transform_type, solver=args.solver,
-                        diagnostics=args.diagnostics)
+                        diagnostics=args.diagnostics, mc_pairing=args.mc_pairing)
     os.makedirs('outputs', exist_ok=True)
     out = 'outputs/evaluation_results.json'
     with open(out, 'w') as f:

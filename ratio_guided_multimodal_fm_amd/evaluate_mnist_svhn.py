@@ -29,6 +29,7 @@ from .models.unet_flexible import FlowMatchingUNetMNIST, FlowMatchingUNetSVHN
 from .sample_mnist_svhn import sample_bimodal_guided_mnist_svhn
 from .utils import load_checkpoint, set_seed
 from .utils.diagnostics import GuidanceDiagnostics, add_cli_args as add_diagnostics_args, row_metrics
+from .utils.flow_utils import add_pairing_arg
 
 
 def evaluate_coherence(samples_mnist, samples_svhn, mnist_classifier, svhn_classifier, device):
@@ -66,13 +67,18 @@ def evaluate_conditional_coherence(condition, samples, given, mnist_classifier, 
 
 
 def run_sweep(fm_mnist, fm_svhn, make_ratio, mnist_classifier, svhn_classifier, methods, strengths,
-              num_samples, num_steps, device, mc_batch_size, sampler=sample_bimodal_guided_mnist_svhn, solver='euler', diagnostics=False):
+              num_samples, num_steps, device, mc_batch_size, sampler=sample_bimodal_guided_mnist_svhn, solver='euler', diagnostics=False,
+              mc_pairing='paired'):
     """The reference's nested loop (:130-183). `make_ratio()` returns a fresh ratio estimator or None.
     `solver` ('euler' | 'midpoint') goes to `sampler` as a keyword when it is not the default.
     `diagnostics`: every guided row also gets ess_mean, ess_min and w_max of the importance weights at step
-    int(0.3 * num_steps) (utils/diagnostics.py); without it the rows keep exactly their keys."""
+    int(0.3 * num_steps) (utils/diagnostics.py); without it the rows keep exactly their keys.
+    `mc_pairing` = 'cross': the 'mc_feng' configurations guide over all mc_batch_size ** 2 pairs of the MC set (the
+    sampler's `mc_pairing` keyword) and their rows record ``"mc_pairing": "cross"``; 'paired' rows keep their keys."""
     from ._lib import solver_id
+    from .utils.flow_utils import check_pairing
     solver_id(solver)
+    check_pairing(mc_pairing)
     kw = {'solver': solver} if solver != 'euler' else {}
     results = []
     for method in methods:
@@ -83,13 +89,14 @@ def run_sweep(fm_mnist, fm_svhn, make_ratio, mnist_classifier, svhn_classifier, 
             if method != 'none' and ratio is None:
                 continue
             diag = GuidanceDiagnostics() if diagnostics and method != 'none' else None
+            cross = {'mc_pairing': 'cross'} if mc_pairing == 'cross' and method == 'mc_feng' else {}
             xs, ys = sampler(fm_mnist, fm_svhn, ratio, method, strength, num_samples, num_steps, device,
-                             mc_batch_size, **kw, **({'diagnostics': diag} if diag is not None else {}))
+                             mc_batch_size, **kw, **({'diagnostics': diag} if diag is not None else {}), **cross)
             metrics = evaluate_coherence(xs, ys, mnist_classifier, svhn_classifier, device)
             if diag is not None and diag.records is not None:
                 metrics = {**metrics, **row_metrics(diag, num_steps)}
             results.append({'method': method, 'guidance_strength': strength, 'experiment': 'mnist_svhn',
-                            **metrics})
+                            **metrics, **cross})
             print(f"  method={method} gamma={strength} -> coherence accuracy {metrics['coherence_acc']:.3f}")
     return results
 
@@ -111,9 +118,12 @@ def main(argv=None):
     p.add_argument('--sharded', action='store_true',
                    help='rows sharded over the ranks of a torch.distributed.run launch (one process per GPU, RCCL)')
     add_diagnostics_args(p, sampling=False)
+    add_pairing_arg(p)
     args = p.parse_args(argv)
     if args.diagnostics and args.sharded:
         p.error('--diagnostics has no --sharded form')
+    if args.mc_pairing == 'cross' and args.sharded:
+        p.error('--mc_pairing cross has no --sharded form')
 
     set_seed(args.seed)  # (every rank alike: the sharded sampler slices ONE noise set)
     if not torch.cuda.is_available():
@@ -153,7 +163,7 @@ def main(argv=None):
 
     results = run_sweep(fm_mnist, fm_svhn, make_ratio, mnist_clf, svhn_clf, args.guidance_methods,
                         args.guidance_strengths, args.num_samples, args.num_steps, device, args.mc_batch_size,
-                        sampler=sampler, solver=args.solver, diagnostics=args.diagnostics)
+                        sampler=sampler, solver=args.solver, diagnostics=args.diagnostics, mc_pairing=args.mc_pairing)
     if args.sharded:
         import torch.distributed as dist
         if dist.is_initialized():

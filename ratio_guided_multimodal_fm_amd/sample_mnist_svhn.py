@@ -14,17 +14,18 @@ from .models.ratio_flexible import RatioEstimatorMNISTSVHN
 from .models.unet_flexible import FlowMatchingUNetMNIST, FlowMatchingUNetSVHN
 from .utils import load_checkpoint, set_seed
 from .utils.diagnostics import GuidanceDiagnostics, add_cli_args as add_diagnostics_args, report_diagnostics
-from .utils.flow_utils import paired_sampler, sample_conditional
+from .utils.flow_utils import add_pairing_arg, paired_sampler, sample_conditional
 
 
 def sample_bimodal_guided_mnist_svhn(fm_mnist, fm_svhn, ratio_estimator=None, guidance_method='none',
                                      guidance_strength=0.0, num_samples=16, num_steps=100,
-                                     device='cuda', mc_batch_size=64, solver='euler', diagnostics=None):
+                                     device='cuda', mc_batch_size=64, solver='euler', diagnostics=None,
+                                     mc_pairing='paired'):
     """Returns ``(samples_mnist [n,1,32,32], samples_svhn [n,3,32,32])`` on `device`.  `diagnostics`: a
-    ``utils.diagnostics.GuidanceDiagnostics`` to fill (``paired_sampler``)."""
+    ``utils.diagnostics.GuidanceDiagnostics`` to fill; `mc_pairing`: 'paired' | 'cross' (``paired_sampler``)."""
     return paired_sampler(fm_mnist, fm_svhn, ratio_estimator, guidance_method, guidance_strength,
                           num_samples, num_steps, device, mc_batch_size, (1, 32, 32), (3, 32, 32), solver=solver,
-                          diagnostics=diagnostics)
+                          diagnostics=diagnostics, mc_pairing=mc_pairing)
 
 
 def load_condition(path, shape):
@@ -64,7 +65,10 @@ def main(argv=None):
     p.add_argument('--condition', type=str, default=None, metavar='FILE.npy|.pt',
                    help='condition images [B,1,32,32] (--given mnist) or [B,3,32,32] (--given svhn)')
     add_diagnostics_args(p)
+    add_pairing_arg(p)
     args = p.parse_args(argv)
+    if args.mc_pairing == 'cross' and (args.guidance_method != 'mc_feng' or args.given or args.sharded):
+        p.error('--mc_pairing cross goes with --guidance_method mc_feng; it has no --given and no --sharded form')
     if (args.diagnostics or args.diagnostics_out) and args.sharded:
         p.error('--diagnostics / --diagnostics_out have no --sharded form')
     diag = GuidanceDiagnostics() if args.diagnostics or args.diagnostics_out else None
@@ -129,7 +133,8 @@ def main(argv=None):
     print(f"\nSampling {args.num_samples} pairs...")
     xs, ys = sampler(fm_mnist, fm_svhn, ratio, args.guidance_method, args.guidance_strength, args.num_samples,
                      args.num_steps, device, args.mc_batch_size, **({'solver': args.solver} if args.solver != 'euler' else {}),
-                     **({'diagnostics': diag} if diag is not None else {}))
+                     **({'diagnostics': diag} if diag is not None else {}),
+                     **({'mc_pairing': args.mc_pairing} if args.mc_pairing != 'paired' else {}))
     report_diagnostics(diag, args.num_steps, args.diagnostics, args.diagnostics_out)
     if args.sharded:
         import torch.distributed as dist

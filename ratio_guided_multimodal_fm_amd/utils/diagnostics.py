@@ -17,6 +17,13 @@ MC guidance fills every field; an effective sample size near 1 means one MC samp
 MC sample").  Gradient log-ratio guidance fills the four norms (``g`` is ``grad log r`` before gamma) and leaves
 ess / w_max / w_min / z_bar at 0.  One-sided (conditional) sampling leaves the ``_y`` fields at 0.
 
+Cross pairing (``mc_pairing='cross'``: the guidance over all N x N pairs of the MC set, N = mc_batch_size): the records
+describe the N^2 joint weights w_ij through what the loop forms of them.  ``ess`` is the JOINT effective sample size
+(sum_ij w_ij)^2 / sum_ij w_ij^2, 1 .. N^2 (compare it with N^2, not N); ``w_max`` / ``w_min`` are the max and min over
+the 2N marginal weights wx_i = sum_j w_ij, wy_j = sum_i w_ij (each marginal sums to 1, as a paired row does);
+``z_bar`` is mean_ij R_ij a_i b_j + 1e-10; the four norms are as before, g formed from the marginal weights.
+``reference_block`` and ``row_metrics`` read such records unchanged.
+
 Sharded launches (``distributed.py``) are out of scope: they take no ``diagnostics=``.
 """
 import torch

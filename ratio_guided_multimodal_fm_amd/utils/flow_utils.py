@@ -167,9 +167,34 @@ def train_flow_matching_epoch(model, dataloader, optimizer, schedule, device, mo
     return total_loss / num_batches
 
 
+PAIRINGS = ('paired', 'cross')
+
+
+def check_pairing(mc_pairing, guidance_method='mc_feng'):
+    """'paired' | 'cross' (anything else: ValueError); 'cross' is a pairing of the MC guidance and goes with
+    guidance_method='mc_feng' only.  Raised before any device work."""
+    if not isinstance(mc_pairing, str) or mc_pairing not in PAIRINGS:
+        raise ValueError(f"mc_pairing must be 'paired' or 'cross', got {mc_pairing!r}")
+    if mc_pairing == 'cross' and guidance_method != 'mc_feng':
+        raise ValueError(f"mc_pairing='cross' pairs up the MC set of guidance_method='mc_feng'; got guidance_method={guidance_method!r}")
+    return mc_pairing
+
+
+def add_pairing_arg(p):
+    """--mc_pairing of the command-line tools."""
+    p.add_argument('--mc_pairing', type=str, default='paired', choices=list(PAIRINGS),
+                   help="MC guidance (mc_feng): 'paired' uses the mc_batch_size pairs (x1_i, y1_i) of the MC set; 'cross' "
+                        "all mc_batch_size^2 pairs (x1_i, y1_j) of the same set (U-Net nets, mc_batch_size <= 1024; not "
+                        "with --sharded)")
+
+
+def _stats(name, t):
+    return f"{name}: min={t.min():.4f}, max={t.max():.4f}, mean={t.mean():.4f}"
+
+
 def paired_sampler(fm_x, fm_y, ratio_estimator, guidance_method, guidance_strength, num_samples,
                    num_steps, device, mc_batch_size, shape_x, shape_y, noise=None, verbose=True, solver='euler',
-                   diagnostics=None):
+                   diagnostics=None, mc_pairing='paired'):
     """Shared body of both paired samplers.
 
     `noise` = (x0, y0, mc_x0, mc_y0) overrides the generator draws (parity
@@ -181,8 +206,18 @@ def paired_sampler(fm_x, fm_y, ratio_estimator, guidance_method, guidance_streng
     `diagnostics` = a ``utils.diagnostics.GuidanceDiagnostics``: the main loop fills it with per-stage, per-sample
     records (effective sample size, weight range, Z_bar, velocity and guidance norms), written on the device with no
     host synchronisation.  The returned samples keep their bits.  Sharded launches (``distributed.py``) take none.
+
+    `mc_pairing` = 'paired' (default) guides with the `mc_batch_size` pairs ``(mc_x1[i], mc_y1[i])``.  'cross'
+    (``guidance_method='mc_feng'``, U-Net nets, ``mc_batch_size <= 1024``) guides with all ``mc_batch_size ** 2`` pairs
+    ``(mc_x1[i], mc_y1[j])``: every one of them is a draw from the product of the marginals, so the same pre-phase
+    yields that many importance pairs.  The noise draws and the pre-phase are unchanged; the ratios are the matrix
+    ``ratio_estimator._engine.eval_cross(mc_x1, mc_y1, "ratio")`` and the loop is ``rgfm_sample_pair_cross``.  With
+    `diagnostics` the effective sample size is the joint one (1 .. mc_batch_size ** 2; utils/diagnostics.py).
     """
     _check_diagnostics(diagnostics)
+    check_pairing(mc_pairing, guidance_method)
+    if mc_pairing == 'cross' and ratio_estimator is not None:
+        _engine._check_cross((mc_batch_size, mc_batch_size), mc_batch_size, mc_batch_size, fm_x, fm_y)
     _engine._solver(solver, fm_x, fm_y)
     fm_x.eval()
     fm_y.eval()
@@ -216,10 +251,16 @@ def paired_sampler(fm_x, fm_y, ratio_estimator, guidance_method, guidance_streng
             print(f"  Generated MC samples: x shape={mc_x1.shape}, y shape={mc_y1.shape}")
         if ratio_estimator.loss_type not in ("disc", "rulsif"):
             raise ValueError(f"Unknown loss_type: {ratio_estimator.loss_type}")
-        mc_ratios = ratio_estimator._engine.eval(mc_x1, mc_y1, "ratio")
-        if verbose:
-            print(f"  MC ratios: min={mc_ratios.min():.4f}, max={mc_ratios.max():.4f}, "
-                  f"mean={mc_ratios.mean():.4f}")
+        if mc_pairing == 'cross':
+            mc_ratios = ratio_estimator._engine.eval_cross(mc_x1, mc_y1, "ratio")
+            if verbose:
+                print("  " + _stats(f"MC ratio matrix [{mc_batch_size} x {mc_batch_size}]", mc_ratios))
+                print("  " + _stats("  its diagonal (the paired ratios)", mc_ratios.diagonal()))
+        else:
+            mc_ratios = ratio_estimator._engine.eval(mc_x1, mc_y1, "ratio")
+            if verbose:
+                print(f"  MC ratios: min={mc_ratios.min():.4f}, max={mc_ratios.max():.4f}, "
+                      f"mean={mc_ratios.mean():.4f}")
 
     if grad_guided:
         # "Gradient Log-Ratio" of the reference README (:159-164): v + gamma * grad log r(x_t, y_t) every step.  The
@@ -311,7 +352,7 @@ def sample_conditional(fm_target, ratio_estimator, condition, given='x', num_ste
 
 def sample_bimodal_guided(fm_x, fm_y, ratio_estimator=None, guidance_method='none',
                           guidance_strength=0.0, num_samples=16, num_steps=100, device='cuda',
-                          mc_batch_size=64, solver='euler', diagnostics=None):
+                          mc_batch_size=64, solver='euler', diagnostics=None, mc_pairing='paired'):
     """Pairs of 1x28x28 images, optional mc_feng guidance (reference :178-375).
 
     Returns ``(samples_x [n,1,28,28], samples_y [n,1,28,28])`` on `device`.
@@ -320,7 +361,8 @@ def sample_bimodal_guided(fm_x, fm_y, ratio_estimator=None, guidance_method='non
     reference.  The reference's one-shot diagnostics print (:349-363) is
     available through `diagnostics`: pass a ``utils.diagnostics.GuidanceDiagnostics`` and read its
     ``reference_block(int(0.3 * num_steps))`` (the same text) or its per-sample, per-stage records.
+    ``mc_pairing='cross'``: the guidance over all ``mc_batch_size ** 2`` pairs of the MC set (``paired_sampler``).
     """
     return paired_sampler(fm_x, fm_y, ratio_estimator, guidance_method, guidance_strength,
                           num_samples, num_steps, device, mc_batch_size, (1, 28, 28), (1, 28, 28), solver=solver,
-                          diagnostics=diagnostics)
+                          diagnostics=diagnostics, mc_pairing=mc_pairing)
