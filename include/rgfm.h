@@ -813,6 +813,70 @@ int rgfm_sample_pair_cross(rgfm_unet* hx, rgfm_unet* hy, float* x_inout, float* 
                            size_t diag_records, void* ws, size_t ws_bytes, rgfm_stream_t stream);
 
 /* ------------------------------------------------------------------------
+ * Guidance strength per sample and per stage (U-Net nets).  Added functions only: the ABI version is unchanged.
+ *
+ * For row b and stage k of a call the effective strength is gamma[b,k] = (double)gamma_b * s_k, formed in double.
+ *   k        counts the call's own stages in the order of the diagnostics records: step_end - step_begin stages for
+ *            RGFM_SOLVER_EULER, twice that for RGFM_SOLVER_MIDPOINT (stage 1 then stage 2 of each step).
+ *   gamma_b  gamma_rows[batch], a DEVICE vector of fp32 owned by the caller; null: the call's `double gamma` for every row.
+ *   s_k      stage_scale[n_stage_scale], a HOST array of doubles, read before the call returns and not retained;
+ *            null (with n_stage_scale 0): 1 for every stage.
+ * The MC blends (paired, cross, one-sided) use g1 = (float)(1.0 - gamma[b,k]) and g2 = (float)gamma[b,k] in
+ * g1 v + g2 g; the gradient loops use (float)gamma[b,k] in x = base + fma(gamma, grad log r, v) dt -- the rules of the
+ * scalar entry points.  So with s_k = 1 row b has the bits of the scalar call with gamma = (double)gamma_rows[b].
+ * Values are not clamped: negative strengths and strengths above 1 are allowed.
+ * A stage is guided iff it is guided in the scalar call (the MC loops: n_mc > 0 and the stage's own t > 1e-3; the
+ * gradient loops: always) AND s_k != 0.  A stage with s_k == 0 runs as the loop's unguided stage: the nets with the
+ * fused Euler epilogue and no guidance, ratio-estimator or update launch.  Its state has the bits of the unguided loops
+ * over that range (rgfm_sample_pair_ode with n_mc = 0, rgfm_sample_single_ode) and its diagnostics record is all zero.
+ * The diagnostics' norms and weights do not depend on gamma.
+ * A call with gamma_rows or stage_scale runs kernel by kernel (no hipGraph replay).  With both null each *_gs loop is
+ * exactly its namesake: same launches, arguments and replay.
+ *
+ * Loops: each *_gs entry point is its *_diag namesake (rgfm_sample_pair_cross_gs: rgfm_sample_pair_cross) with
+ * `const float* gamma_rows, const double* stage_scale, int n_stage_scale` behind `gamma`; workspace: the namesake's
+ * query (rgfm_sample_pair_diag_workspace_bytes with records, rgfm_sample_pair_ode_workspace_bytes without, ...).
+ * Blocks: each *_rows entry point is the existing block with `const float* gamma_rows` (not null) in place of
+ * `double gamma`; workspace: the existing block queries.
+ * Errors are returned before anything is enqueued and touch no state: the namesake's own, and RGFM_EINVAL for
+ * n_stage_scale != the call's stage count, a stage_scale entry that is not finite, or stage_scale null with
+ * n_stage_scale != 0.
+ * ---------------------------------------------------------------------- */
+int rgfm_sample_pair_gs(rgfm_unet* hx, rgfm_unet* hy, float* x_inout, float* y_inout, const float* mc_x1,
+                        const float* mc_y1, const float* mc_ratios, int n_mc, int batch, int num_steps, double gamma,
+                        const float* gamma_rows, const double* stage_scale, int n_stage_scale, int step_begin,
+                        int step_end, int solver, float* diag_out, size_t diag_records, void* ws, size_t ws_bytes,
+                        rgfm_stream_t stream);
+int rgfm_sample_pair_cross_gs(rgfm_unet* hx, rgfm_unet* hy, float* x_inout, float* y_inout, const float* mc_x1,
+                              const float* mc_y1, const float* ratio_matrix, int n_mc, int batch, int num_steps,
+                              double gamma, const float* gamma_rows, const double* stage_scale, int n_stage_scale,
+                              int step_begin, int step_end, int solver, float* diag_out, size_t diag_records, void* ws,
+                              size_t ws_bytes, rgfm_stream_t stream);
+int rgfm_sample_cond_gs(rgfm_unet* h, float* s_inout, const float* mc_set, const float* ratios, int n_mc, int batch,
+                        int num_steps, double gamma, const float* gamma_rows, const double* stage_scale,
+                        int n_stage_scale, int step_begin, int step_end, int solver, float* diag_out,
+                        size_t diag_records, void* ws, size_t ws_bytes, rgfm_stream_t stream);
+int rgfm_sample_pair_grad_gs(rgfm_unet* hx, rgfm_unet* hy, rgfm_ratio* hr, float* x_inout, float* y_inout, int batch,
+                             int num_steps, double gamma, const float* gamma_rows, const double* stage_scale,
+                             int n_stage_scale, int step_begin, int step_end, int solver, float* diag_out,
+                             size_t diag_records, void* ws, size_t ws_bytes, rgfm_stream_t stream);
+int rgfm_sample_cond_grad_gs(rgfm_unet* h_unet, rgfm_ratio* h_ratio, float* s_inout, const float* ctx, int given,
+                             int batch, int num_steps, double gamma, const float* gamma_rows,
+                             const double* stage_scale, int n_stage_scale, int step_begin, int step_end, int solver,
+                             float* diag_out, size_t diag_records, void* ws, size_t ws_bytes, rgfm_stream_t stream);
+int rgfm_guidance_apply_rows(const float* x, const float* y, float* vx, float* vy, const float* mc_x1,
+                             const float* mc_y1, const float* mc_ratios, int batch, int n_mc, int dim_x, int dim_y,
+                             double t, const float* gamma_rows, float* weights_out, void* ws, size_t ws_bytes,
+                             rgfm_stream_t stream);
+int rgfm_guidance_apply_cond_rows(const float* s, float* v, const float* mc_set, const float* ratios, int batch,
+                                  int n_mc, int dim, double t, const float* gamma_rows, float* weights_out, void* ws,
+                                  size_t ws_bytes, rgfm_stream_t stream);
+int rgfm_guidance_apply_cross_rows(const float* x, const float* y, float* vx, float* vy, const float* mc_x1,
+                                   const float* mc_y1, const float* ratio_matrix, int batch, int n_mc, int dim_x,
+                                   int dim_y, double t, const float* gamma_rows, float* wx_out, float* wy_out, void* ws,
+                                   size_t ws_bytes, rgfm_stream_t stream);
+
+/* ------------------------------------------------------------------------
  * Bench support: per-kernel-class device time measured with hipEvents on the
  * launch stream (bench.py's roofline line).  Timing is off by default.
  * ---------------------------------------------------------------------- */

@@ -1017,15 +1017,50 @@ def _diag_fn(name):
     return (stem[:-4] if stem.endswith("_ode") else stem) + "_diag" + tail
 
 
-def _run_loop(fn, ws_fn, ws_args, args, steps, sid, dev, ws=None, diag=None, cross=False):
+def _gs_fn(name):
+    """The *_gs twin of a guided U-Net loop's entry point (rgfm_sample_pair_ode -> rgfm_sample_pair_gs)."""
+    return (name[:-4] if name.endswith("_ode") else name) + "_gs"
+
+
+def _check_strength(gamma_rows, stage_scale, batch, num_steps, steps, sid, models):
+    """Argument checks of a call with a strength per row (`gamma_rows`: fp32 device tensor [batch]) and / or a scale per
+    stage (`stage_scale`: floats, one per stage of the call), before any device work.  Returns what _run_loop takes as
+    `strength`: None when both are None (the call is then today's), else (gamma_rows, ctypes double array or None)."""
+    if gamma_rows is None and stage_scale is None:
+        return None
+    for m in models:
+        if not isinstance(m._engine, UNetEngine):
+            raise _lib.RgfmError("a guidance strength per sample or per stage needs U-Net velocity nets (FlexibleUNet and "
+                                 f"its presets); {type(m).__name__} takes a scalar strength only")
+    if gamma_rows is not None:
+        if not isinstance(gamma_rows, torch.Tensor) or gamma_rows.dim() != 1 or gamma_rows.shape[0] != batch:
+            shape = tuple(gamma_rows.shape) if isinstance(gamma_rows, torch.Tensor) else type(gamma_rows).__name__
+            raise ValueError(f"gamma_rows: a 1-D tensor with one strength per row ([{batch}]) expected, got {shape}")
+        if gamma_rows.dtype != torch.float32:
+            raise ValueError(f"gamma_rows must be float32, got {gamma_rows.dtype}")
+    arr = None
+    if stage_scale is not None:
+        n = (int(steps[1]) - int(steps[0])) * (2 if sid else 1)
+        vals = [float(v) for v in stage_scale]
+        if len(vals) != n:
+            raise ValueError(f"stage_scale holds {len(vals)} values, the call has {n} stages")
+        arr = (ctypes.c_double * max(n, 1))(*vals)
+        arr.n = n
+    return gamma_rows, arr
+
+
+def _run_loop(fn, ws_fn, ws_args, args, steps, sid, dev, ws=None, diag=None, cross=False, strength=None):
     """One native sampler loop: the size query `ws_fn`(*ws_args[, sid]), the workspace (`ws`: a _Workspace; default the
     samplers' shared one), then `fn`(*args, *steps[, sid], workspace, stream).  `steps`: (step_begin, step_end).  sid
     None: entry points without a solver argument (the FlowMatchingModel loops).  `diag`: a records tensor
     [n_stages, B, RGFM_DIAG_FLOATS] -- the loop's *_diag twin runs and fills it (guided loops only).  `cross`: the
-    U-Net pair loop over all pairs of the MC set (rgfm_sample_pair_cross: one entry point with and without records)."""
+    U-Net pair loop over all pairs of the MC set (rgfm_sample_pair_cross: one entry point with and without records).
+    `strength`: what _check_strength returns -- not None: the loop's *_gs twin runs (U-Net loops), the namesake's
+    arguments with (gamma_rows, stage_scale, n_stage_scale) behind gamma and its workspace query."""
     L = _lib.lib()
     tail = () if sid is None else (sid,)
     sink = ()
+    base_fn = fn
     if diag is not None:
         if not (diag.is_cuda and diag.dtype == torch.float32 and diag.is_contiguous() and diag.dim() == 3
                 and diag.shape[2] == _lib.DIAG_FLOATS):
@@ -1035,6 +1070,13 @@ def _run_loop(fn, ws_fn, ws_args, args, steps, sid, dev, ws=None, diag=None, cro
         sink = (_ptr(diag), diag.shape[0] * diag.shape[1])
     if cross:
         fn, ws_fn = "rgfm_sample_pair_cross", "rgfm_sample_pair_cross_workspace_bytes"
+        sink = sink or (None, 0)
+    if strength is not None:
+        rows, scale = strength
+        if rows is not None and not (rows.is_cuda and rows.is_contiguous() and rows.device == dev):
+            raise _lib.RgfmError(f"gamma_rows must be a contiguous tensor on {dev}, got one on {rows.device}")
+        fn = "rgfm_sample_pair_cross_gs" if cross else _gs_fn(base_fn)
+        args = (*args, _ptr(rows), scale, scale.n if scale is not None else 0)
         sink = sink or (None, 0)
     nb = ctypes.c_size_t()
     _lib.check(getattr(L, ws_fn)(*ws_args, *tail, ctypes.byref(nb)))
@@ -1128,15 +1170,22 @@ def sample_two_streams(fm_x, x, fm_y, y, num_steps, solver='euler'):
 
 
 def sample_pair(fm_x, fm_y, x, y, mc_x1, mc_y1, mc_ratios, num_steps, gamma, step_begin=0,
-                step_end=None, solver='euler', diag=None):
+                step_end=None, solver='euler', diag=None, gamma_rows=None, stage_scale=None):
     """In-place paired loop with optional MC guidance (rgfm_sample_pair; solver='midpoint': rgfm_sample_pair_ode).
     `diag`: a records tensor [n_stages, B, 8] to fill (rgfm_sample_pair_diag / rgfm_fmnet_sample_pair_diag; the state
     keeps its bits); the other guided loops below take it the same way.
 
     `mc_ratios` [N]: the ratios of the N pairs (mc_x1[i], mc_y1[i]).  `mc_ratios` [N, N] (x index first, what
     RatioEngine.eval_cross returns): cross pairing, the guidance over all N x N pairs (mc_x1[i], mc_y1[j])
-    (rgfm_sample_pair_cross; U-Net nets, N <= 1024)."""
+    (rgfm_sample_pair_cross; U-Net nets, N <= 1024).
+
+    `gamma_rows` (fp32 device tensor [B]: a strength per row, in `gamma`'s place) and `stage_scale` (floats, one per
+    stage of the call: a scale of the strength per stage; 0 = the stage runs unguided): rgfm_sample_pair_gs /
+    rgfm_sample_pair_cross_gs (U-Net nets).  Both None: the call above, unchanged.  The other guided loops below take
+    them the same way."""
     sid = _solver(solver, fm_x, fm_y)
+    strength = _check_strength(gamma_rows, stage_scale, x.shape[0], num_steps,
+                               (step_begin, num_steps if step_end is None else step_end), sid, (fm_x, fm_y))
     for m in (fm_x, fm_y):
         m._engine._check_eval(m)
     ex = fm_x._engine
@@ -1164,16 +1213,19 @@ def sample_pair(fm_x, fm_y, x, y, mc_x1, mc_y1, mc_ratios, num_steps, gamma, ste
             _run_loop(ex.PAIR, ex.PAIR_WS, (hx, hy, B, n_mc),
                       (hx, hy, _ptr(x), _ptr(y), _ptr(mc_x1 if n_mc else None), _ptr(mc_y1 if n_mc else None),
                        _ptr(mc_ratios if n_mc else None), n_mc, B, int(num_steps), float(gamma)),
-                      (step_begin, step_end), _solver_arg(ex, sid), dev, diag=diag, cross=cross)
+                      (step_begin, step_end), _solver_arg(ex, sid), dev, diag=diag, cross=cross,
+                      **({} if strength is None else {"strength": strength}))
         return x, y
     return _range_guarded(dev, [x, y], run, [fm_x._engine, fm_y._engine])
 
 
 def sample_pair_grad(fm_x, fm_y, ratio_estimator, x, y, num_steps, gamma, step_begin=0, step_end=None, solver='euler',
-                     diag=None):
+                     diag=None, gamma_rows=None, stage_scale=None):
     """In-place paired loop with gradient log-ratio guidance (rgfm_sample_pair_grad; solver='midpoint':
     rgfm_sample_pair_grad_ode)."""
     sid = _lib.solver_id(solver)
+    strength = _check_strength(gamma_rows, stage_scale, x.shape[0], num_steps,
+                               (step_begin, num_steps if step_end is None else step_end), sid, (fm_x, fm_y))
     for m in (fm_x, fm_y, ratio_estimator):
         m._engine._check_eval(m)
     if not (isinstance(fm_x._engine, UNetEngine) and isinstance(fm_y._engine, UNetEngine)):
@@ -1193,13 +1245,27 @@ def sample_pair_grad(fm_x, fm_y, ratio_estimator, x, y, num_steps, gamma, step_b
             hx, hy, hr = fm_x._engine.handle(dev), fm_y._engine.handle(dev), ratio_estimator._engine.handle(dev)
             _run_loop("rgfm_sample_pair_grad_ode", "rgfm_sample_pair_grad_ode_workspace_bytes", (hx, hy, hr, B),
                       (hx, hy, hr, _ptr(x), _ptr(y), B, int(num_steps), float(gamma)), (step_begin, step_end), sid, dev,
-                      diag=diag)
+                      diag=diag, **({} if strength is None else {"strength": strength}))
         return x, y
     return _range_guarded(dev, [x, y], run, [fm_x._engine, fm_y._engine])
 
 
+def _block_gamma(gamma, batch, dev, name):
+    """(entry point, its gamma argument) of a guidance block: a number is the scalar block `name`; an fp32 device tensor
+    [batch] -- a strength per row -- its *_rows twin."""
+    if not isinstance(gamma, torch.Tensor):
+        return name, float(gamma)
+    if gamma.dim() != 1 or gamma.shape[0] != batch or gamma.dtype != torch.float32:
+        raise ValueError(f"gamma: a number or a float32 tensor [{batch}] (a strength per row) expected, got "
+                         f"{tuple(gamma.shape)} {gamma.dtype}")
+    if not (gamma.is_cuda and gamma.device == dev and gamma.is_contiguous()):
+        raise _lib.RgfmError(f"gamma must be a contiguous tensor on {dev}")
+    return name + "_rows", _ptr(gamma)
+
+
 def guidance_apply(x, y, vx, vy, mc_x1, mc_y1, mc_ratios, t, gamma, want_weights=False):
-    """One guidance evaluation (parity hook): overwrites vx, vy; returns weights or None."""
+    """One guidance evaluation (parity hook): overwrites vx, vy; returns weights or None.  `gamma`: a number, or an
+    fp32 device tensor [B] with a strength per row (rgfm_guidance_apply_rows); the other blocks take it the same way."""
     _require_hip(x, y, vx, vy, mc_x1, mc_y1, mc_ratios)
     B, N, dev = x.shape[0], mc_x1.shape[0], x.device
     dx, dy = x[0].numel(), y[0].numel()
@@ -1209,10 +1275,11 @@ def guidance_apply(x, y, vx, vy, mc_x1, mc_y1, mc_ratios, t, gamma, want_weights
         nb = ctypes.c_size_t()
         _lib.check(L.rgfm_guidance_workspace_bytes(B, N, ctypes.byref(nb)))
         ws = _sampler_ws.get(nb.value, dev)
-        _lib.check(L.rgfm_guidance_apply(_ptr(x.contiguous()), _ptr(y.contiguous()), _ptr(vx), _ptr(vy),
-                                         _ptr(mc_x1.contiguous()), _ptr(mc_y1.contiguous()),
-                                         _ptr(mc_ratios.contiguous()), B, N, dx, dy, float(t),
-                                         float(gamma), _ptr(w), _ptr(ws), nb.value, _stream(dev)))
+        fn, g = _block_gamma(gamma, B, dev, "rgfm_guidance_apply")
+        _lib.check(getattr(L, fn)(_ptr(x.contiguous()), _ptr(y.contiguous()), _ptr(vx), _ptr(vy),
+                                  _ptr(mc_x1.contiguous()), _ptr(mc_y1.contiguous()),
+                                  _ptr(mc_ratios.contiguous()), B, N, dx, dy, float(t),
+                                  g, _ptr(w), _ptr(ws), nb.value, _stream(dev)))
     return w
 
 
@@ -1245,10 +1312,11 @@ def guidance_apply_cross(x, y, vx, vy, mc_x1, mc_y1, ratio_matrix, t, gamma, wan
         nb = ctypes.c_size_t()
         _lib.check(L.rgfm_guidance_cross_workspace_bytes(B, N, dx, dy, ctypes.byref(nb)))
         ws = _sampler_ws.get(nb.value, dev)
-        _lib.check(L.rgfm_guidance_apply_cross(_ptr(x.contiguous()), _ptr(y.contiguous()), _ptr(vx), _ptr(vy),
-                                               _ptr(mc_x1.contiguous()), _ptr(mc_y1.contiguous()),
-                                               _ptr(ratio_matrix.contiguous()), B, N, dx, dy, float(t), float(gamma),
-                                               _ptr(wx), _ptr(wy), _ptr(ws), nb.value, _stream(dev)))
+        fn, g = _block_gamma(gamma, B, dev, "rgfm_guidance_apply_cross")
+        _lib.check(getattr(L, fn)(_ptr(x.contiguous()), _ptr(y.contiguous()), _ptr(vx), _ptr(vy),
+                                  _ptr(mc_x1.contiguous()), _ptr(mc_y1.contiguous()),
+                                  _ptr(ratio_matrix.contiguous()), B, N, dx, dy, float(t), g,
+                                  _ptr(wx), _ptr(wy), _ptr(ws), nb.value, _stream(dev)))
     return (wx, wy) if want_weights else None
 
 
@@ -1308,10 +1376,13 @@ def guidance_diag_cond(s, v, mc_set, ratios, t):
     return out
 
 
-def sample_cond(model, s, mc_set, ratios, num_steps, gamma, step_begin=0, step_end=None, solver='euler', diag=None):
+def sample_cond(model, s, mc_set, ratios, num_steps, gamma, step_begin=0, step_end=None, solver='euler', diag=None,
+                gamma_rows=None, stage_scale=None):
     """In-place loop of one U-Net with one-sided MC guidance (rgfm_sample_cond; solver='midpoint':
     rgfm_sample_cond_ode): s [B, C, H, W], mc_set [N, C, H, W], ratios [B, N]."""
     sid = _lib.solver_id(solver)
+    strength = _check_strength(gamma_rows, stage_scale, s.shape[0], num_steps,
+                               (step_begin, num_steps if step_end is None else step_end), sid, (model,))
     eng = model._engine
     eng._check_eval(model)
     if not isinstance(eng, UNetEngine):
@@ -1336,17 +1407,19 @@ def sample_cond(model, s, mc_set, ratios, num_steps, gamma, step_begin=0, step_e
             h = eng.handle(dev)
             _run_loop("rgfm_sample_cond_ode", "rgfm_sample_cond_ode_workspace_bytes", (h, B, N),
                       (h, _ptr(s), _ptr(mc_set), _ptr(ratios), N, B, int(num_steps), float(gamma)),
-                      (step_begin, step_end), sid, dev, diag=diag)
+                      (step_begin, step_end), sid, dev, diag=diag, **({} if strength is None else {"strength": strength}))
         return s
     return _range_guarded(dev, [s], run, [eng])
 
 
 def sample_cond_grad(model, ratio_estimator, s, ctx, given, num_steps, gamma, step_begin=0, step_end=None, solver='euler',
-                     diag=None):
+                     diag=None, gamma_rows=None, stage_scale=None):
     """In-place loop of one U-Net with one-sided gradient log-ratio guidance (rgfm_sample_cond_grad; solver='midpoint':
     rgfm_sample_cond_grad_ode): s [B, C, H, W], ctx [B, hidden_dim] from ratio_estimator._engine.cond_prepare(condition,
     given)."""
     sid = _lib.solver_id(solver)
+    strength = _check_strength(gamma_rows, stage_scale, s.shape[0], num_steps,
+                               (step_begin, num_steps if step_end is None else step_end), sid, (model,))
     eng, re = model._engine, ratio_estimator._engine
     eng._check_eval(model)
     re._check_eval(ratio_estimator)
@@ -1375,7 +1448,7 @@ def sample_cond_grad(model, ratio_estimator, s, ctx, given, num_steps, gamma, st
             h, hr = eng.handle(dev), re.handle(dev)
             _run_loop("rgfm_sample_cond_grad_ode", "rgfm_sample_cond_grad_ode_workspace_bytes", (h, hr, gi, B),
                       (h, hr, _ptr(s), _ptr(ctx), gi, B, int(num_steps), float(gamma)), (step_begin, step_end), sid, dev,
-                      diag=diag)
+                      diag=diag, **({} if strength is None else {"strength": strength}))
         return s
     return _range_guarded(dev, [s], run, [eng])
 
@@ -1390,9 +1463,10 @@ def guidance_apply_cond(s, v, mc_set, ratios, t, gamma, want_weights=False):
         nb = ctypes.c_size_t()
         _lib.check(L.rgfm_guidance_workspace_bytes(B, N, ctypes.byref(nb)))
         ws = _sampler_ws.get(nb.value, dev)
-        _lib.check(L.rgfm_guidance_apply_cond(_ptr(s.contiguous()), _ptr(v), _ptr(mc_set.contiguous()),
-                                              _ptr(ratios.contiguous()), B, N, s[0].numel(), float(t), float(gamma),
-                                              _ptr(w), _ptr(ws), nb.value, _stream(dev)))
+        fn, g = _block_gamma(gamma, B, dev, "rgfm_guidance_apply_cond")
+        _lib.check(getattr(L, fn)(_ptr(s.contiguous()), _ptr(v), _ptr(mc_set.contiguous()),
+                                  _ptr(ratios.contiguous()), B, N, s[0].numel(), float(t), g,
+                                  _ptr(w), _ptr(ws), nb.value, _stream(dev)))
     return w
 
 

@@ -194,6 +194,30 @@ SIGNATURES = {
     "rgfm_sample_pair_cross": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int,
                                        c_int, c_double, c_int, c_int, c_int, c_void_p, c_size_t, c_void_p, c_size_t,
                                        c_void_p]),
+    # guidance strength as data: the *_diag loops (cross: rgfm_sample_pair_cross) with (gamma_rows [device fp32],
+    # stage_scale [host doubles], n_stage_scale) behind gamma; the blocks with gamma_rows in gamma's place
+    "rgfm_sample_pair_gs": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int,
+                                    c_int, c_double, c_void_p, P(c_double), c_int, c_int, c_int, c_int, c_void_p, c_size_t,
+                                    c_void_p, c_size_t, c_void_p]),
+    "rgfm_sample_pair_cross_gs": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int,
+                                          c_int, c_double, c_void_p, P(c_double), c_int, c_int, c_int, c_int, c_void_p,
+                                          c_size_t, c_void_p, c_size_t, c_void_p]),
+    "rgfm_sample_cond_gs": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_double, c_void_p,
+                                    P(c_double), c_int, c_int, c_int, c_int, c_void_p, c_size_t, c_void_p, c_size_t,
+                                    c_void_p]),
+    "rgfm_sample_pair_grad_gs": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_double, c_void_p,
+                                         P(c_double), c_int, c_int, c_int, c_int, c_void_p, c_size_t, c_void_p, c_size_t,
+                                         c_void_p]),
+    "rgfm_sample_cond_grad_gs": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_double, c_void_p,
+                                         P(c_double), c_int, c_int, c_int, c_int, c_void_p, c_size_t, c_void_p, c_size_t,
+                                         c_void_p]),
+    "rgfm_guidance_apply_rows": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int,
+                                         c_int, c_int, c_double, c_void_p, c_void_p, c_void_p, c_size_t, c_void_p]),
+    "rgfm_guidance_apply_cond_rows": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_double,
+                                              c_void_p, c_void_p, c_void_p, c_size_t, c_void_p]),
+    "rgfm_guidance_apply_cross_rows": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int,
+                                               c_int, c_int, c_int, c_double, c_void_p, c_void_p, c_void_p, c_void_p,
+                                               c_size_t, c_void_p]),
     "rgfm_profile_enable": (c_int, [c_int]),
     "rgfm_profile_reset": (c_int, []),
     "rgfm_profile_read": (c_int, [c_int, P(c_double), P(c_double), P(c_int64), P(c_double)]),

@@ -754,8 +754,15 @@ int pair_grad_bytes(const rgfm_unet* hx, const rgfm_unet* hy, const rgfm_ratio* 
   return RGFM_OK;
 }
 
+// x = base + (v + gamma g) dt over [batch][dim] with the stage's strength: the scalar kernel, or the per-row one
+void euler_grad_update(float* x, const float* v, const float* g, int batch, size_t dim, const StageStrength& gamma, float dt,
+                       hipStream_t s, const float* base) {
+  if (gamma.rows) launch_euler_grad_rows(x, v, g, (size_t)batch * dim, (int)dim, gamma.rows, gamma.scale, dt, s, base);
+  else launch_euler_grad(x, v, g, (size_t)batch * dim, (float)gamma.gamma, dt, s, base);
+}
+
 int pair_grad_loop(rgfm_unet* hx, rgfm_unet* hy, rgfm_ratio* hr, float* x_inout, float* y_inout, int batch, int num_steps,
-                   double gamma, int step_begin, int step_end, int solver, void* ws, size_t ws_bytes, rgfm_stream_t stream,
+                   const Strength& strength, int step_begin, int step_end, int solver, void* ws, size_t ws_bytes, rgfm_stream_t stream,
                    float* diag_out = nullptr, size_t diag_records = 0) {
   refresh_modes();
   int ns = 0;
@@ -764,6 +771,7 @@ int pair_grad_loop(rgfm_unet* hx, rgfm_unet* hy, rgfm_ratio* hr, float* x_inout,
   if (int rc = check_grad_pair(hx, hy, hr)) return rc;
   DiagSink sink;  // (the gradient loops need no scratch: v and grad log r are both in the workspace already)
   if (int rc = sink.check(diag_out, diag_records, batch, ns, solver)) return rc;
+  if (int rc = strength.check(loop_stages(solver, ns))) return rc;
   Bump b(ws, ws_bytes);
   PairGradWs w{{hx, batch, solver}, {hy, batch, solver}};
   carve_pair_grad(b, w, hr);
@@ -777,10 +785,11 @@ int pair_grad_loop(rgfm_unet* hx, rgfm_unet* hy, rgfm_ratio* hr, float* x_inout,
   if (int rc = w.cy.begin(s, num_steps, step_begin, ns)) return rc;
   if (sink.on())
     if (int rc = sink.begin(s, 0, 0)) return rc;
-  const float gf = (float)gamma;
   const bool overlap = g_modes.overlap;
   // one stage: (xout, yout) = (xb, yb) + (v(in, row's t) + gamma grad log r(xin, yin)) dts; xb / yb null: in place
-  auto stage = [&](const Stage& g) -> int {
+  // A stage whose scale is 0 runs unguided -- both nets with the fused Euler epilogue on the two streams, as pair_loop's
+  // unguided stage, and no ratio pass; its diagnostics record stays zero.
+  auto stage = [&](const Stage& g, const StageStrength& gamma, bool guided) -> int {
     float *xin = g.reads_mid ? w.cx.mid : x_inout, *yin = g.reads_mid ? w.cy.mid : y_inout;
     float *xout = g.writes_mid ? w.cx.mid : x_inout, *yout = g.writes_mid ? w.cy.mid : y_inout;
     const float *xb = g.writes_mid ? x_inout : nullptr, *yb = g.writes_mid ? y_inout : nullptr;
@@ -788,6 +797,14 @@ int pair_grad_loop(rgfm_unet* hx, rgfm_unet* hy, rgfm_ratio* hr, float* x_inout,
     if (overlap) {
       HIP_TRY(hipEventRecord(ds->fork, s));
       HIP_TRY(hipStreamWaitEvent(ds->side, ds->fork, 0));
+    }
+    if (!guided) {
+      if (sink.on()) (void)sink.next();
+      if (int rc = w.cy.eval(g.row, sy, yin, nullptr, yout, y_inout, g.dts)) return rc;
+      if (overlap) HIP_TRY(hipEventRecord(ds->join, ds->side));
+      if (int rc = w.cx.eval(g.row, s, xin, nullptr, xout, x_inout, g.dts)) return rc;
+      if (overlap) HIP_TRY(hipStreamWaitEvent(s, ds->join, 0));
+      return RGFM_OK;
     }
     if (int rc = w.cy.eval(g.row, sy, yin, w.vy, nullptr, nullptr, 0.f)) return rc;
     if (overlap) HIP_TRY(hipEventRecord(ds->join, ds->side));
@@ -806,15 +823,16 @@ int pair_grad_loop(rgfm_unet* hx, rgfm_unet* hy, rgfm_ratio* hr, float* x_inout,
       launch_diag_rownorm(w.gx, batch, (int)dx, rec, RGFM_DIAG_G_NORM_X, s);
       launch_diag_rownorm(w.gy, batch, (int)dy, rec, RGFM_DIAG_G_NORM_Y, s);
     }
-    launch_euler_grad(xout, w.vx, w.gx, (size_t)batch * dx, gf, g.dts, s, xb);
-    launch_euler_grad(yout, w.vy, w.gy, (size_t)batch * dy, gf, g.dts, s, yb);
+    euler_grad_update(xout, w.vx, w.gx, batch, dx, gamma, g.dts, s, xb);
+    euler_grad_update(yout, w.vy, w.gy, batch, dy, gamma, g.dts, s, yb);
     return RGFM_OK;
   };
+  int stage_no = 0;  // (the index into the strength's per-stage scale)
   for (int i = 0; i < ns; ++i) {
     Stage st[2];
     const int n = w.cx.stages(i, st);
-    for (int k = 0; k < n; ++k)
-      if (int rc = stage(st[k])) return rc;
+    for (int k = 0; k < n; ++k, ++stage_no)
+      if (int rc = stage(st[k], strength.stage(stage_no), !strength.off(stage_no))) return rc;
   }
   HIP_TRY(hipGetLastError());
   return RGFM_OK;
@@ -877,7 +895,7 @@ int cond_grad_bytes(const rgfm_unet* h, const rgfm_ratio* hr, int given, int bat
 }
 
 int cond_grad_loop(rgfm_unet* h, rgfm_ratio* hr, float* s_inout, const float* ctx, int given, int batch, int num_steps,
-                   double gamma, int step_begin, int step_end, int solver, void* ws, size_t ws_bytes, rgfm_stream_t stream,
+                   const Strength& strength, int step_begin, int step_end, int solver, void* ws, size_t ws_bytes, rgfm_stream_t stream,
                    float* diag_out = nullptr, size_t diag_records = 0) {
   refresh_modes();
   int ns = 0;
@@ -887,6 +905,7 @@ int cond_grad_loop(rgfm_unet* h, rgfm_ratio* hr, float* s_inout, const float* ct
   if (rc || (rc = check_grad_side(h, hr, given))) return rc;
   DiagSink sink;
   if ((rc = sink.check(diag_out, diag_records, batch, ns, solver))) return rc;
+  if ((rc = strength.check(loop_stages(solver, ns)))) return rc;
   Bump b(ws, ws_bytes);
   CondGradWs w = carve_cond_grad(b, h, hr, given, batch, solver);
   if ((rc = check_workspace(b, ws_bytes))) return rc;
@@ -895,14 +914,19 @@ int cond_grad_loop(rgfm_unet* h, rgfm_ratio* hr, float* s_inout, const float* ct
   const size_t d = w.c.image_floats();
   if ((rc = w.c.begin(s, num_steps, step_begin, ns))) return rc;
   if (sink.on() && (rc = sink.begin(s, 0, 0))) return rc;
-  const float gf = (float)gamma;
+  int stage_no = 0;  // (the index into the strength's per-stage scale)
   for (int i = 0; i < ns; ++i) {
     Stage st[2];
     const int n = w.c.stages(i, st);
-    for (int k = 0; k < n; ++k) {
+    for (int k = 0; k < n; ++k, ++stage_no) {
       // one stage: out = base + (v(in, row's t) + gamma grad log r(in)) dts; base null: in place on out
       const Stage& g = st[k];
       float *in = g.reads_mid ? w.c.mid : s_inout, *out = g.writes_mid ? w.c.mid : s_inout;
+      if (strength.off(stage_no)) {  // scale 0: the unguided stage (NetChain::step's evaluation), no ratio pass, a zero record
+        if (sink.on()) (void)sink.next();
+        if ((rc = w.c.eval(g.row, s, in, nullptr, out, s_inout, g.dts))) return rc;
+        continue;
+      }
       if ((rc = w.c.eval(g.row, s, in, w.v, nullptr, nullptr, 0.f))) return rc;
       {
         b.off = w.c.mark;
@@ -915,7 +939,7 @@ int cond_grad_loop(rgfm_unet* h, rgfm_ratio* hr, float* s_inout, const float* ct
         launch_diag_rownorm(w.v, batch, (int)d, rec, RGFM_DIAG_V_NORM_X, s);
         launch_diag_rownorm(w.g, batch, (int)d, rec, RGFM_DIAG_G_NORM_X, s);
       }
-      launch_euler_grad(out, w.v, w.g, (size_t)batch * d, gf, g.dts, s, g.writes_mid ? s_inout : nullptr);
+      euler_grad_update(out, w.v, w.g, batch, d, strength.stage(stage_no), g.dts, s, g.writes_mid ? s_inout : nullptr);
     }
   }
   HIP_TRY(hipGetLastError());
@@ -964,4 +988,21 @@ extern "C" int rgfm_sample_cond_grad_diag(rgfm_unet* h, rgfm_ratio* hr, float* s
                                           rgfm_stream_t stream) {
   return cond_grad_loop(h, hr, s_inout, ctx, given, batch, num_steps, gamma, step_begin, step_end, solver, ws, ws_bytes, stream,
                         diag_out, diag_records);
+}
+
+// ---- guidance strength as data (include/rgfm.h, "Guidance strength per sample and per stage"): each loop is its *_diag
+// namesake with (gamma_rows, stage_scale, n_stage_scale) behind gamma
+extern "C" int rgfm_sample_pair_grad_gs(rgfm_unet* hx, rgfm_unet* hy, rgfm_ratio* hr, float* x_inout, float* y_inout, int batch,
+                                        int num_steps, double gamma, const float* gamma_rows, const double* stage_scale,
+                                        int n_stage_scale, int step_begin, int step_end, int solver, float* diag_out,
+                                        size_t diag_records, void* ws, size_t ws_bytes, rgfm_stream_t stream) {
+  return pair_grad_loop(hx, hy, hr, x_inout, y_inout, batch, num_steps, Strength(gamma, gamma_rows, stage_scale, n_stage_scale),
+                        step_begin, step_end, solver, ws, ws_bytes, stream, diag_out, diag_records);
+}
+extern "C" int rgfm_sample_cond_grad_gs(rgfm_unet* h, rgfm_ratio* hr, float* s_inout, const float* ctx, int given, int batch,
+                                        int num_steps, double gamma, const float* gamma_rows, const double* stage_scale,
+                                        int n_stage_scale, int step_begin, int step_end, int solver, float* diag_out,
+                                        size_t diag_records, void* ws, size_t ws_bytes, rgfm_stream_t stream) {
+  return cond_grad_loop(h, hr, s_inout, ctx, given, batch, num_steps, Strength(gamma, gamma_rows, stage_scale, n_stage_scale),
+                        step_begin, step_end, solver, ws, ws_bytes, stream, diag_out, diag_records);
 }

@@ -171,10 +171,11 @@ extern "C" int rgfm_guidance_workspace_bytes(int batch, int n_mc, size_t* bytes)
   return RGFM_OK;
 }
 
-extern "C" int rgfm_guidance_apply(const float* x, const float* y, float* vx, float* vy, const float* mc_x1,
-                                   const float* mc_y1, const float* mc_ratios, int batch, int n_mc, int dim_x,
-                                   int dim_y, double t, double gamma, float* weights_out, void* ws,
-                                   size_t ws_bytes, rgfm_stream_t stream) {
+// (the blocks below: `gamma` is the scalar of the existing entry points, or the per-row vector of their *_rows twins)
+namespace {
+int guidance_block(const float* x, const float* y, float* vx, float* vy, const float* mc_x1, const float* mc_y1,
+                   const float* mc_ratios, int batch, int n_mc, int dim_x, int dim_y, double t, const StageStrength& gamma,
+                   float* weights_out, void* ws, size_t ws_bytes, rgfm_stream_t stream) {
   if (!x || !y || !vx || !vy || !mc_x1 || !mc_y1 || !mc_ratios || !ws) return fail(RGFM_EINVAL, "null argument");
   size_t need = 0;
   int rc = rgfm_guidance_workspace_bytes(batch, n_mc, &need);
@@ -189,9 +190,9 @@ extern "C" int rgfm_guidance_apply(const float* x, const float* y, float* vx, fl
 }
 
 // The one-sided block: the paired block with dy = 0 and a ratio row per sample (guidance_launch).
-extern "C" int rgfm_guidance_apply_cond(const float* s, float* v, const float* mc_set, const float* ratios, int batch, int n_mc,
-                                        int dim, double t, double gamma, float* weights_out, void* ws, size_t ws_bytes,
-                                        rgfm_stream_t stream) {
+int guidance_block_cond(const float* s, float* v, const float* mc_set, const float* ratios, int batch, int n_mc, int dim,
+                        double t, const StageStrength& gamma, float* weights_out, void* ws, size_t ws_bytes,
+                        rgfm_stream_t stream) {
   if (!s || !v || !mc_set || !ratios || !ws) return fail(RGFM_EINVAL, "null argument");
   if (dim < 1) return fail(RGFM_EINVAL, "bad argument");
   size_t need = 0;
@@ -204,6 +205,36 @@ extern "C" int rgfm_guidance_apply_cond(const float* s, float* v, const float* m
   if (rc) return rc;
   HIP_TRY(hipGetLastError());
   return RGFM_OK;
+}
+}  // namespace
+
+extern "C" int rgfm_guidance_apply(const float* x, const float* y, float* vx, float* vy, const float* mc_x1,
+                                   const float* mc_y1, const float* mc_ratios, int batch, int n_mc, int dim_x,
+                                   int dim_y, double t, double gamma, float* weights_out, void* ws,
+                                   size_t ws_bytes, rgfm_stream_t stream) {
+  return guidance_block(x, y, vx, vy, mc_x1, mc_y1, mc_ratios, batch, n_mc, dim_x, dim_y, t, gamma, weights_out, ws, ws_bytes,
+                        stream);
+}
+extern "C" int rgfm_guidance_apply_cond(const float* s, float* v, const float* mc_set, const float* ratios, int batch, int n_mc,
+                                        int dim, double t, double gamma, float* weights_out, void* ws, size_t ws_bytes,
+                                        rgfm_stream_t stream) {
+  return guidance_block_cond(s, v, mc_set, ratios, batch, n_mc, dim, t, gamma, weights_out, ws, ws_bytes, stream);
+}
+// ... with a strength per row (include/rgfm.h, "Guidance strength per sample and per stage")
+extern "C" int rgfm_guidance_apply_rows(const float* x, const float* y, float* vx, float* vy, const float* mc_x1,
+                                        const float* mc_y1, const float* mc_ratios, int batch, int n_mc, int dim_x, int dim_y,
+                                        double t, const float* gamma_rows, float* weights_out, void* ws, size_t ws_bytes,
+                                        rgfm_stream_t stream) {
+  if (!gamma_rows) return fail(RGFM_EINVAL, "null argument");
+  return guidance_block(x, y, vx, vy, mc_x1, mc_y1, mc_ratios, batch, n_mc, dim_x, dim_y, t, StageStrength(0.0, gamma_rows, 1.0),
+                        weights_out, ws, ws_bytes, stream);
+}
+extern "C" int rgfm_guidance_apply_cond_rows(const float* s, float* v, const float* mc_set, const float* ratios, int batch,
+                                             int n_mc, int dim, double t, const float* gamma_rows, float* weights_out, void* ws,
+                                             size_t ws_bytes, rgfm_stream_t stream) {
+  if (!gamma_rows) return fail(RGFM_EINVAL, "null argument");
+  return guidance_block_cond(s, v, mc_set, ratios, batch, n_mc, dim, t, StageStrength(0.0, gamma_rows, 1.0), weights_out, ws,
+                             ws_bytes, stream);
 }
 
 // ---- diagnostics of one evaluation of the block (include/rgfm.h, "Guidance diagnostics")
@@ -270,7 +301,7 @@ int cond_bytes(const rgfm_unet* h, int batch, int n_mc, int solver, size_t* byte
 
 // One net, guided by the one-sided block: kernel by kernel on the caller's stream (nothing to overlap, no graph).
 int cond_loop(rgfm_unet* h, float* s_inout, const float* mc_set, const float* ratios, int n_mc, int batch, int num_steps,
-              double gamma, int step_begin, int step_end, int solver, void* ws, size_t ws_bytes, rgfm_stream_t stream,
+              const Strength& strength, int step_begin, int step_end, int solver, void* ws, size_t ws_bytes, rgfm_stream_t stream,
               float* diag_out = nullptr, size_t diag_records = 0) {
   refresh_modes();
   int ns = 0;
@@ -278,6 +309,7 @@ int cond_loop(rgfm_unet* h, float* s_inout, const float* mc_set, const float* ra
     return rc;
   DiagSink sink;
   if (int rc = sink.check(diag_out, diag_records, batch, ns, solver)) return rc;
+  if (int rc = strength.check(loop_stages(solver, ns))) return rc;
   if (n_mc < 1) return fail(RGFM_EINVAL, "conditional sampling needs an MC set (n_mc >= 1)");
   const int d = h->d.in_channels * h->d.img_size * h->d.img_size;
   if (d % 4) return fail(RGFM_EINVAL, "flattened image sizes must be multiples of 4");
@@ -291,14 +323,16 @@ int cond_loop(rgfm_unet* h, float* s_inout, const float* mc_set, const float* ra
   if (int rc = w.c.begin(s, num_steps, step_begin, ns)) return rc;
   if (sink.on())
     if (int rc = sink.begin(s, d, 0)) return rc;
+  int stage_no = 0;  // (the index into the strength's per-stage scale)
   for (int i = 0; i < ns; ++i) {
     Stage st[2];
     const int n = w.c.stages(i, st);
-    for (int k = 0; k < n; ++k) {
+    for (int k = 0; k < n; ++k, ++stage_no) {
       // one stage: out = s + F(in, t) dts; guided iff the stage's own t > eps (`t > eps` test of the reference, :124)
+      // and its scale is not 0
       const Stage& g = st[k];
       float *in = g.reads_mid ? w.c.mid : s_inout, *out = g.writes_mid ? w.c.mid : s_inout;
-      const bool guided = g.t > 1e-3;
+      const bool guided = g.t > 1e-3 && !strength.off(stage_no);
       GuidDiag gd{};
       if (sink.on()) gd = {sink.next(), sink.gx, sink.gy};
       // unguided: the fused Euler epilogue; guided: the raw velocity, and the guidance block moves the state
@@ -306,7 +340,7 @@ int cond_loop(rgfm_unet* h, float* s_inout, const float* mc_set, const float* ra
                           : w.c.eval(g.row, s, in, nullptr, out, s_inout, g.dts))
         return rc;
       if (!guided) continue;
-      if (int rc = guidance_launch(in, nullptr, w.v, nullptr, mc_set, nullptr, ratios, batch, n_mc, d, 0, g.t, gamma, w.scratch,
+      if (int rc = guidance_launch(in, nullptr, w.v, nullptr, mc_set, nullptr, ratios, batch, n_mc, d, 0, g.t, strength.stage(stage_no), w.scratch,
                                    nullptr, out, nullptr, g.dts, s, nullptr, nullptr, 0, n_mc, s_inout, nullptr, sink.on() ? &gd : nullptr))
         return rc;
     }
@@ -327,7 +361,7 @@ int pair_bytes(const rgfm_unet* hx, const rgfm_unet* hy, int batch, int n_mc, in
 }
 
 int pair_sample(rgfm_unet* hx, rgfm_unet* hy, float* x_inout, float* y_inout, const float* mc_x1, const float* mc_y1,
-                const float* mc_ratios, int n_mc, int batch, int num_steps, double gamma, int step_begin, int step_end,
+                const float* mc_ratios, int n_mc, int batch, int num_steps, const Strength& strength, int step_begin, int step_end,
                 int solver, void* ws, size_t ws_bytes, rgfm_stream_t stream, float* diag_out = nullptr, size_t diag_records = 0,
                 int pairing = PAIRING_PAIRED) {
   refresh_modes();
@@ -342,6 +376,7 @@ int pair_sample(rgfm_unet* hx, rgfm_unet* hy, float* x_inout, float* y_inout, co
   }
   DiagSink sink;
   if (int rc = sink.check(diag_out, diag_records, batch, ns, solver)) return rc;
+  if (int rc = strength.check(loop_stages(solver, ns))) return rc;
   Bump b(ws, ws_bytes);
   PairWs w{{hx, batch, solver}, {hy, batch, solver}};
   carve_pair(b, w, n_mc, pairing);
@@ -356,7 +391,7 @@ int pair_sample(rgfm_unet* hx, rgfm_unet* hy, float* x_inout, float* y_inout, co
   if (sink.on())
     if (int rc = sink.begin(s, w.cx.image_floats(), w.cy.image_floats())) return rc;
   auto net = [](NetChain& c) { return [&c](auto... a) { return c.eval(a...); }; };  // pair_loop's eval: NetChain::eval
-  return pair_loop(net(w.cx), net(w.cy), x_inout, y_inout, mc_x1, mc_y1, mc_ratios, n_mc, batch, num_steps, gamma, step_begin, ns,
+  return pair_loop(net(w.cx), net(w.cy), x_inout, y_inout, mc_x1, mc_y1, mc_ratios, n_mc, batch, num_steps, strength, step_begin, ns,
                    (int)w.cx.image_floats(), (int)w.cy.image_floats(), w.vx, w.vy, w.logp, s, w.gstate, solver, w.cx.mid,
                    w.cy.mid, sink.on() ? &sink : nullptr, pairing);
 }
@@ -435,10 +470,11 @@ extern "C" int rgfm_guidance_cross_workspace_bytes(int batch, int n_mc, int dim_
   *bytes = guid_cross_scratch_bytes(batch, n_mc) + diag_scratch_bytes(batch, dim_x, dim_y);
   return RGFM_OK;
 }
-extern "C" int rgfm_guidance_apply_cross(const float* x, const float* y, float* vx, float* vy, const float* mc_x1,
-                                         const float* mc_y1, const float* ratio_matrix, int batch, int n_mc, int dim_x,
-                                         int dim_y, double t, double gamma, float* wx_out, float* wy_out, void* ws,
-                                         size_t ws_bytes, rgfm_stream_t stream) {
+namespace {
+int guidance_block_cross(const float* x, const float* y, float* vx, float* vy, const float* mc_x1, const float* mc_y1,
+                         const float* ratio_matrix, int batch, int n_mc, int dim_x, int dim_y, double t,
+                         const StageStrength& gamma, float* wx_out, float* wy_out, void* ws, size_t ws_bytes,
+                         rgfm_stream_t stream) {
   if (!x || !y || !vx || !vy || !mc_x1 || !mc_y1 || !ratio_matrix || !ws) return fail(RGFM_EINVAL, "null argument");
   size_t need = 0;
   int rc = rgfm_guidance_cross_workspace_bytes(batch, n_mc, dim_x, dim_y, &need);
@@ -451,6 +487,22 @@ extern "C" int rgfm_guidance_apply_cross(const float* x, const float* y, float* 
   if (rc) return rc;
   HIP_TRY(hipGetLastError());
   return RGFM_OK;
+}
+}  // namespace
+extern "C" int rgfm_guidance_apply_cross(const float* x, const float* y, float* vx, float* vy, const float* mc_x1,
+                                         const float* mc_y1, const float* ratio_matrix, int batch, int n_mc, int dim_x,
+                                         int dim_y, double t, double gamma, float* wx_out, float* wy_out, void* ws,
+                                         size_t ws_bytes, rgfm_stream_t stream) {
+  return guidance_block_cross(x, y, vx, vy, mc_x1, mc_y1, ratio_matrix, batch, n_mc, dim_x, dim_y, t, gamma, wx_out, wy_out, ws,
+                              ws_bytes, stream);
+}
+extern "C" int rgfm_guidance_apply_cross_rows(const float* x, const float* y, float* vx, float* vy, const float* mc_x1,
+                                              const float* mc_y1, const float* ratio_matrix, int batch, int n_mc, int dim_x,
+                                              int dim_y, double t, const float* gamma_rows, float* wx_out, float* wy_out,
+                                              void* ws, size_t ws_bytes, rgfm_stream_t stream) {
+  if (!gamma_rows) return fail(RGFM_EINVAL, "null argument");
+  return guidance_block_cross(x, y, vx, vy, mc_x1, mc_y1, ratio_matrix, batch, n_mc, dim_x, dim_y, t,
+                              StageStrength(0.0, gamma_rows, 1.0), wx_out, wy_out, ws, ws_bytes, stream);
 }
 extern "C" int rgfm_guidance_diag_cross(const float* x, const float* y, const float* vx, const float* vy, const float* mc_x1,
                                         const float* mc_y1, const float* ratio_matrix, int batch, int n_mc, int dim_x,
@@ -471,4 +523,32 @@ extern "C" int rgfm_sample_pair_cross(rgfm_unet* hx, rgfm_unet* hy, float* x_ino
                                       size_t diag_records, void* ws, size_t ws_bytes, rgfm_stream_t stream) {
   return pair_sample(hx, hy, x_inout, y_inout, mc_x1, mc_y1, ratio_matrix, n_mc, batch, num_steps, gamma, step_begin, step_end,
                      solver, ws, ws_bytes, stream, diag_out, diag_records, PAIRING_CROSS);
+}
+
+// ---- guidance strength as data (include/rgfm.h, "Guidance strength per sample and per stage"): each loop is its
+// *_diag / *_cross namesake with (gamma_rows, stage_scale, n_stage_scale) behind gamma
+extern "C" int rgfm_sample_pair_gs(rgfm_unet* hx, rgfm_unet* hy, float* x_inout, float* y_inout, const float* mc_x1,
+                                   const float* mc_y1, const float* mc_ratios, int n_mc, int batch, int num_steps, double gamma,
+                                   const float* gamma_rows, const double* stage_scale, int n_stage_scale, int step_begin,
+                                   int step_end, int solver, float* diag_out, size_t diag_records, void* ws, size_t ws_bytes,
+                                   rgfm_stream_t stream) {
+  return pair_sample(hx, hy, x_inout, y_inout, mc_x1, mc_y1, mc_ratios, n_mc, batch, num_steps,
+                     Strength(gamma, gamma_rows, stage_scale, n_stage_scale), step_begin, step_end, solver, ws, ws_bytes, stream,
+                     diag_out, diag_records);
+}
+extern "C" int rgfm_sample_pair_cross_gs(rgfm_unet* hx, rgfm_unet* hy, float* x_inout, float* y_inout, const float* mc_x1,
+                                         const float* mc_y1, const float* ratio_matrix, int n_mc, int batch, int num_steps,
+                                         double gamma, const float* gamma_rows, const double* stage_scale, int n_stage_scale,
+                                         int step_begin, int step_end, int solver, float* diag_out, size_t diag_records,
+                                         void* ws, size_t ws_bytes, rgfm_stream_t stream) {
+  return pair_sample(hx, hy, x_inout, y_inout, mc_x1, mc_y1, ratio_matrix, n_mc, batch, num_steps,
+                     Strength(gamma, gamma_rows, stage_scale, n_stage_scale), step_begin, step_end, solver, ws, ws_bytes, stream,
+                     diag_out, diag_records, PAIRING_CROSS);
+}
+extern "C" int rgfm_sample_cond_gs(rgfm_unet* h, float* s_inout, const float* mc_set, const float* ratios, int n_mc, int batch,
+                                   int num_steps, double gamma, const float* gamma_rows, const double* stage_scale,
+                                   int n_stage_scale, int step_begin, int step_end, int solver, float* diag_out,
+                                   size_t diag_records, void* ws, size_t ws_bytes, rgfm_stream_t stream) {
+  return cond_loop(h, s_inout, mc_set, ratios, n_mc, batch, num_steps, Strength(gamma, gamma_rows, stage_scale, n_stage_scale),
+                   step_begin, step_end, solver, ws, ws_bytes, stream, diag_out, diag_records);
 }

@@ -224,7 +224,18 @@ __global__ __launch_bounds__(256) void guid_weights_kernel(const GuidanceArgs a_
 // the A element and M[k][d0 + 4 (l % 32) + j] as the B element of column tile j: one float4 of the MC set feeds four
 // MFMAs and the lane ends up with four consecutive columns of a row (float4 loads and stores in the epilogue).  A
 // row's result depends on its own weights and the MC set only, in an order fixed by N: independent of the batch it is in.
-template <bool W4>  // N % 32 == 0: a lane's run of samples starts at a multiple of four and its weights arrive as float4
+// The blend coefficients of a row with its own strength: gamma = (double)gamma_b * scale, each operation rounded on its
+// own (no contraction into 1 - gamma_b scale): the host's rule for GuidanceArgs::g1 / g2 (rgfm_host.h).
+__device__ __forceinline__ void row_blend(float gamma_b, double scale, float& g1, float& g2) {
+#pragma clang fp contract(off)
+  const double gm = (double)gamma_b * scale;
+  g1 = (float)(1.0 - gm), g2 = (float)gm;
+}
+
+// ROWS: the blend coefficients of a row come from GuidanceArgs::gamma_rows (a strength per sample) instead of g1 / g2;
+// the row's entry is fetched in the final epilogue loop, when the accumulators have left the registers for LDS, so the
+// main loop and the prefetch block are those of the scalar instantiation.
+template <bool W4, bool ROWS>  // W4: N % 32 == 0, a lane's run of samples starts at a multiple of four and its weights arrive as float4
 __global__ __launch_bounds__(256, 2) void guid_apply_mfma_kernel(const GuidanceArgs a_in) {
   const GuidanceArgs a = with_schedule(a_in);
   const int nbx = (a.dx + 127) >> 7;  // column blocks of modality x; those of y behind them
@@ -332,15 +343,19 @@ __global__ __launch_bounds__(256, 2) void guid_apply_mfma_kernel(const GuidanceA
     const size_t o = (size_t)b * D + d;
     const f32x4 xv = ex[rr], v = ev[rr];
     const float sw = esw[rr];
+    float g1 = a.g1, g2 = a.g2;
+    if constexpr (ROWS) row_blend(a.gamma_rows[b], a.gamma_scale, g1, g2);  // (b < B here: the load is in bounds)
+    // (the blend g1 v + g2 g is written as the fma the compiler contracts it to in the scalar kernel -- fma(g1, v, g2 g)
+    // -- so that the per-row instantiations cannot associate it the other way: a row's bits are those of the scalar call)
     f32x4 g, nv;
     g.x = __fmul_rn(__fsub_rn(c[0], __fmul_rn(xv.x, sw)), rcden);
     g.y = __fmul_rn(__fsub_rn(c[1], __fmul_rn(xv.y, sw)), rcden);
     g.z = __fmul_rn(__fsub_rn(c[2], __fmul_rn(xv.z, sw)), rcden);
     g.w = __fmul_rn(__fsub_rn(c[3], __fmul_rn(xv.w, sw)), rcden);
-    nv.x = __fadd_rn(__fmul_rn(a.g1, v.x), __fmul_rn(a.g2, g.x));
-    nv.y = __fadd_rn(__fmul_rn(a.g1, v.y), __fmul_rn(a.g2, g.y));
-    nv.z = __fadd_rn(__fmul_rn(a.g1, v.z), __fmul_rn(a.g2, g.z));
-    nv.w = __fadd_rn(__fmul_rn(a.g1, v.w), __fmul_rn(a.g2, g.w));
+    nv.x = fmaf(g1, v.x, __fmul_rn(g2, g.x));
+    nv.y = fmaf(g1, v.y, __fmul_rn(g2, g.y));
+    nv.z = fmaf(g1, v.z, __fmul_rn(g2, g.z));
+    nv.w = fmaf(g1, v.w, __fmul_rn(g2, g.w));
     if (XS) {
       f32x4 xs = XB ? *reinterpret_cast<const f32x4*>(XB + o) : xv;
       xs.x = __fadd_rn(xs.x, __fmul_rn(nv.x, a.dt));
@@ -575,8 +590,11 @@ void launch_guid_logp(const GuidanceArgs& a, hipStream_t s) {
 }
 
 int guid_apply_init() {  // (64 KB of dynamic LDS)
-  return (int)hipFuncSetAttribute(reinterpret_cast<const void*>(&guid_apply_mfma_kernel<true>), hipFuncAttributeMaxDynamicSharedMemorySize, 64 * 1024) |
-         (int)hipFuncSetAttribute(reinterpret_cast<const void*>(&guid_apply_mfma_kernel<false>), hipFuncAttributeMaxDynamicSharedMemorySize, 64 * 1024);
+  int rc = 0;
+  for (const void* k : {reinterpret_cast<const void*>(&guid_apply_mfma_kernel<true, false>), reinterpret_cast<const void*>(&guid_apply_mfma_kernel<false, false>),
+                        reinterpret_cast<const void*>(&guid_apply_mfma_kernel<true, true>), reinterpret_cast<const void*>(&guid_apply_mfma_kernel<false, true>)})
+    rc |= (int)hipFuncSetAttribute(k, hipFuncAttributeMaxDynamicSharedMemorySize, 64 * 1024);
+  return rc;
 }
 
 void launch_guid_weights(const GuidanceArgs& a, hipStream_t s) {  // (needs the distances only: no velocity)
@@ -586,8 +604,13 @@ void launch_guid_weights(const GuidanceArgs& a, hipStream_t s) {  // (needs the 
 void launch_guid_apply(const GuidanceArgs& a, hipStream_t s) {
   const size_t lds = (size_t)4 * 64 * 64 * sizeof(float);
   const dim3 grid((a.B + 31) / 32, (a.dx + 127) / 128 + (a.dy + 127) / 128);
-  if (a.N % 32 == 0) hipLaunchKernelGGL(guid_apply_mfma_kernel<true>, grid, dim3(256), lds, s, a);
-  else hipLaunchKernelGGL(guid_apply_mfma_kernel<false>, grid, dim3(256), lds, s, a);
+  if (a.gamma_rows) {  // (a strength per row: the ROWS instantiations)
+    if (a.N % 32 == 0) hipLaunchKernelGGL((guid_apply_mfma_kernel<true, true>), grid, dim3(256), lds, s, a);
+    else hipLaunchKernelGGL((guid_apply_mfma_kernel<false, true>), grid, dim3(256), lds, s, a);
+    return;
+  }
+  if (a.N % 32 == 0) hipLaunchKernelGGL((guid_apply_mfma_kernel<true, false>), grid, dim3(256), lds, s, a);
+  else hipLaunchKernelGGL((guid_apply_mfma_kernel<false, false>), grid, dim3(256), lds, s, a);
 }
 
 // x <- x + v * dt (mul, then add: two roundings like the reference's x_t + v * dt)

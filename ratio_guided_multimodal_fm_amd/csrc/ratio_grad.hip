@@ -365,15 +365,38 @@ void launch_ratio_head_bwd(const float* score, const float* w, float* gh, float*
                      rows, n, loss);
 }
 
+// One element of the update, b + (v + gamma g) dt, as the two fmas the compiler contracts the scalar kernel's
+// x = b + fma(gamma, g, v) * dt to: written out so that the per-row kernel below rounds the same way.
+__device__ __forceinline__ float euler_grad_elem(float b, float v, float g, float gamma, float dt) {
+  return fmaf(fmaf(gamma, g, v), dt, b);
+}
+
 // x = base + (v + gamma g) dt; base null: in place on x (base, when given, is another buffer than x: a midpoint stage)
 __global__ void euler_grad_kernel(float* x, const float* base, const float* v, const float* g, size_t n, float gamma, float dt) {
   const float* b = base ? base : x;
   for (size_t i = blockIdx.x * (size_t)blockDim.x + threadIdx.x; i < n; i += (size_t)gridDim.x * blockDim.x)
-    x[i] = __fadd_rn(b[i], __fmul_rn(fmaf(gamma, g[i], v[i]), dt));
+    x[i] = euler_grad_elem(b[i], v[i], g[i], gamma, dt);
 }
 void launch_euler_grad(float* x, const float* v, const float* g, size_t n, float gamma, float dt, hipStream_t s, const float* base) {
   const int blocks = (int)((n + 255) / 256 < 2048 ? (n + 255) / 256 : 2048);
   hipLaunchKernelGGL(euler_grad_kernel, dim3(blocks), dim3(256), 0, s, x, base, v, g, n, gamma, dt);
+}
+
+// The same update with a strength per row (row = i / dim; dim need not be a power of two): gamma of a row is formed in
+// double from its fp32 entry and the stage's scale, then rounded once -- with scale 1 the bits of the scalar kernel
+// called with (float)(double)gamma_rows[row].
+__global__ void euler_grad_rows_kernel(float* x, const float* base, const float* v, const float* g, size_t n, unsigned dim,
+                                       const float* __restrict__ gamma_rows, double scale, float dt) {
+  const float* b = base ? base : x;
+  for (size_t i = blockIdx.x * (size_t)blockDim.x + threadIdx.x; i < n; i += (size_t)gridDim.x * blockDim.x) {
+    const float gamma = (float)((double)gamma_rows[i / dim] * scale);
+    x[i] = euler_grad_elem(b[i], v[i], g[i], gamma, dt);
+  }
+}
+void launch_euler_grad_rows(float* x, const float* v, const float* g, size_t n, int dim, const float* gamma_rows, double scale,
+                            float dt, hipStream_t s, const float* base) {
+  const int blocks = (int)((n + 255) / 256 < 2048 ? (n + 255) / 256 : 2048);
+  hipLaunchKernelGGL(euler_grad_rows_kernel, dim3(blocks), dim3(256), 0, s, x, base, v, g, n, (unsigned)dim, gamma_rows, scale, dt);
 }
 
 }  // namespace rgfm

@@ -858,8 +858,43 @@ struct GuidDiag {
   float *rec, *gx, *gy;
 };
 
+// Guidance strength as data (include/rgfm.h, "Guidance strength per sample and per stage").
+// Strength: what a loop is called with -- the scalar gamma, optionally a device vector of per-row strengths (fp32
+// [batch]; null: gamma for every row) and a HOST array of per-stage scales (null: 1 for every stage), read while the
+// call enqueues and not kept.  A plain double converts to the scalar-only strength, which is every existing entry point.
+// StageStrength: one stage of it, what guidance_launch and the gradient loops' update take -- with `rows` null the blend
+// is the scalar rule on `gamma` (already multiplied by the stage's scale, in double), otherwise row b has
+// (double)rows[b] * scale, formed on the device.
+struct StageStrength {
+  double gamma = 0.0;
+  const float* rows = nullptr;
+  double scale = 1.0;
+  StageStrength(double g) : gamma(g) {}
+  StageStrength(double g, const float* r, double s) : gamma(g), rows(r), scale(s) {}
+};
+struct Strength {
+  double gamma = 0.0;
+  const float* rows = nullptr;
+  const double* scale = nullptr;
+  int n_scale = 0;
+  Strength(double g) : gamma(g) {}
+  Strength(double g, const float* r, const double* s, int n) : gamma(g), rows(r), scale(s), n_scale(n) {}
+  bool is_data() const { return rows || scale; }  // (a call with either runs kernel by kernel: no graph replay)
+  // before anything is enqueued: the scale array's length against the call's stage count, and finite entries
+  int check(int n_stages) const {
+    if (!scale) return n_scale == 0 ? RGFM_OK : fail(RGFM_EINVAL, "stage_scale null with n_stage_scale %d (null goes with 0)", n_scale);
+    if (n_scale != n_stages) return fail(RGFM_EINVAL, "n_stage_scale %d != %d stages of the call", n_scale, n_stages);
+    for (int k = 0; k < n_scale; ++k)
+      if (!std::isfinite(scale[k])) return fail(RGFM_EINVAL, "stage_scale[%d] is not finite", k);
+    return RGFM_OK;
+  }
+  double s(int k) const { return scale ? scale[k] : 1.0; }
+  bool off(int k) const { return scale && scale[k] == 0.0; }  // the stage runs unguided
+  StageStrength stage(int k) const { return rows ? StageStrength(gamma, rows, s(k)) : StageStrength(scale ? gamma * scale[k] : gamma); }
+};
+
 inline int guidance_launch(const float* x, const float* y, float* vx, float* vy, const float* mx, const float* my,
-                    const float* r, int B, int N, int dx, int dy, double t, double gamma, float* logp,
+                    const float* r, int B, int N, int dx, int dy, double t, const StageStrength& strength, float* logp,
                     float* weights_out, float* xs, float* ys, float dt, hipStream_t s, const float* sched = nullptr,
                     const int* step_ptr = nullptr, int phase = 0, int ratio_stride = 0, const float* xb = nullptr,
                     const float* yb = nullptr, const GuidDiag* diag = nullptr, int pairing = PAIRING_PAIRED,
@@ -886,7 +921,8 @@ inline int guidance_launch(const float* x, const float* y, float* vx, float* vy,
   a.B = B, a.N = N, a.dx = dx, a.dy = dy;
   guidance_scalars(t, &a.tf, &a.s2, &a.cden);
   a.sched = sched, a.step_ptr = sched ? step_ptr : nullptr;
-  a.g1 = (float)(1.0 - gamma), a.g2 = (float)gamma;
+  a.g1 = (float)(1.0 - strength.gamma), a.g2 = (float)strength.gamma;
+  a.gamma_rows = strength.rows, a.gamma_scale = strength.scale;
   a.dist = reinterpret_cast<double*>(logp), a.weights_out = weights_out, a.x_state = xs, a.y_state = ys, a.dt = dt;
   a.diag_rec = diag ? diag->rec : nullptr;
   a.x_base = xb == x ? nullptr : xb, a.y_base = yb == y ? nullptr : yb;
@@ -916,7 +952,7 @@ inline int guidance_launch(const float* x, const float* y, float* vx, float* vy,
     launch_diag_rownorm(vx, B, dx, diag->rec, RGFM_DIAG_V_NORM_X, s);
     if (dy) launch_diag_rownorm(vy, B, dy, diag->rec, RGFM_DIAG_V_NORM_Y, s);
     GuidanceArgs d = a;
-    d.vx = diag->gx, d.vy = diag->gy, d.g1 = 0.f, d.g2 = 1.f;
+    d.vx = diag->gx, d.vy = diag->gy, d.g1 = 0.f, d.g2 = 1.f, d.gamma_rows = nullptr;
     d.x_state = d.y_state = nullptr, d.x_base = d.y_base = nullptr, d.weights_out = nullptr;
     launch_guid_apply(d, s);
     launch_diag_rownorm(diag->gx, B, dx, diag->rec, RGFM_DIAG_G_NORM_X, s);

@@ -416,6 +416,9 @@ void launch_ratio_head_bwd(const float* score, const float* w, float* gh, float*
 // x <- base + (v + gamma g) dt; base null: x <- x + (v + gamma g) dt
 void launch_euler_grad(float* x, const float* v, const float* g, size_t n, float gamma, float dt, hipStream_t s,
                        const float* base = nullptr);
+// ... with a strength per row: element i takes (float)((double)gamma_rows[i / dim] * scale) as its gamma (n = rows x dim)
+void launch_euler_grad_rows(float* x, const float* v, const float* g, size_t n, int dim, const float* gamma_rows, double scale,
+                            float dt, hipStream_t s, const float* base = nullptr);
 
 // ---- guidance / Euler
 struct GuidanceArgs {
@@ -452,6 +455,11 @@ struct GuidanceArgs {
   const float* x_base;
   const float* y_base;
   float dt;
+  // optional per-row strength (include/rgfm.h, "Guidance strength per sample and per stage"): row b blends with
+  // gamma = (double)gamma_rows[b] * gamma_scale, g1 = (float)(1 - gamma), g2 = (float)gamma -- the host's rule for the
+  // scalar fields, per row; null: g1 / g2 above for every row
+  const float* gamma_rows;
+  double gamma_scale;
 };
 constexpr int RGFM_GUID_SLICES = 8;
 void launch_guid_logp(const GuidanceArgs& a, hipStream_t s);   // distances -> GuidanceArgs::dist

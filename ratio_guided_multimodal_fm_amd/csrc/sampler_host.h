@@ -16,6 +16,8 @@ inline int check_solver(int solver, int ns, int num_steps) {
   return RGFM_OK;
 }
 inline int check_solver_id(int solver) { return check_solver(solver, 0, 0); }  // (what a *_workspace_bytes query can check)
+// stages of a call over `ns` steps, in the order of step_stages: what the diagnostics records and a Strength's scale count
+inline int loop_stages(int solver, int ns) { return ns * (solver == SOLVER_MIDPOINT ? 2 : 1); }
 
 // The prelude of every loop, in this order: solver id, null arguments (`have_args`: the loop's own pointers), step range,
 // step caps.  `time_table` = false (the FlowMatchingModel loops embed t per evaluation): no cap on the steps of a call.
@@ -146,7 +148,7 @@ struct NetChain {
 // hipGraphLaunch.  Results are bit-identical to the kernel-by-kernel path (same kernels, same arguments).
 template <class EvalX, class EvalY>
 int pair_loop(EvalX&& eval_x, EvalY&& eval_y, float* x_inout, float* y_inout, const float* mc_x1,
-              const float* mc_y1, const float* mc_ratios, int n_mc, int batch, int num_steps, double gamma,
+              const float* mc_y1, const float* mc_ratios, int n_mc, int batch, int num_steps, const Strength& strength,
               int step_begin, int ns, int dx, int dy, float* vx, float* vy, float* logp, hipStream_t caller,
               float* gstate = nullptr, int solver = SOLVER_EULER, float* x_mid = nullptr, float* y_mid = nullptr,
               DiagSink* diag = nullptr, int pairing = PAIRING_PAIRED) {
@@ -162,7 +164,8 @@ int pair_loop(EvalX&& eval_x, EvalY&& eval_y, float* x_inout, float* y_inout, co
   hipEvent_t ev_fork = ds->fork, ev_join = ds->join;
   // (diagnostics: kernel by kernel -- each stage writes its own records, a replayed graph would write one stage's)
   // (cross pairing: kernel by kernel as well)
-  const bool use_graph = gstate && g_modes.graph && !g_prof.on && n_mc > 0 && ns >= 4 && solver == SOLVER_EULER && !diag && pairing == PAIRING_PAIRED;
+  const bool use_graph = gstate && g_modes.graph && !g_prof.on && n_mc > 0 && ns >= 4 && solver == SOLVER_EULER && !diag && pairing == PAIRING_PAIRED && !strength.is_data();
+  // (a strength that is data -- per row or per stage -- runs kernel by kernel: the replayed graph holds one stage's scalars)
   hipStream_t s = caller;
   if (use_graph && caller == nullptr) {  // (see DevState::main)
     s = ds->main;
@@ -183,7 +186,7 @@ int pair_loop(EvalX&& eval_x, EvalY&& eval_y, float* x_inout, float* y_inout, co
     launch_guid_schedule(sched_dev, step_begin, ns, num_steps, s);
   }
   // one stage: (xout, yout) = (x, y) + dts * F(xin, yin, t), the nets reading time-table row `row`
-  auto one_stage = [&](const Stage& g, bool guided) -> int {
+  auto one_stage = [&](const Stage& g, bool guided, const StageStrength& gamma) -> int {
     float *xin = g.reads_mid ? x_mid : x_inout, *yin = g.reads_mid ? y_mid : y_inout;
     float *xout = g.writes_mid ? x_mid : x_inout, *yout = g.writes_mid ? y_mid : y_inout;
     const float *xb = x_inout, *yb = y_inout;
@@ -238,16 +241,19 @@ int pair_loop(EvalX&& eval_x, EvalY&& eval_y, float* x_inout, float* y_inout, co
   // modality a chain net -> its half of the guided update on its own stream, coupled only through two events per step
   // around the importance weights, the x net up to one evaluation ahead -- is bit-identical and 0.5 - 0.9 % SLOWER
   // (469 - 471 vs 473 paired images/s, same box, alternating): the join costs nothing the chains could use.)
+  int stage_no = 0;  // the call's own stage count: the index into the strength's per-stage scale
   for (int i = 0; i < ns; ++i) {
     Stage st[2];
     const int n = step_stages(solver, num_steps, step_begin, i, st);
-    for (int k = 0; k < n; ++k) {
-      const bool guided = n_mc > 0 && st[k].t > 1e-3;  // `t > eps` test of the reference (:124)
+    for (int k = 0; k < n; ++k, ++stage_no) {
+      // `t > eps` test of the reference (:124); a stage whose scale is 0 runs as the unguided stage
+      const bool guided = n_mc > 0 && st[k].t > 1e-3 && !strength.off(stage_no);
+      const StageStrength gamma = strength.stage(stage_no);
       if (use_graph && guided) {  // (Euler: the step's one stage)
         if (!exec) {
           hipGraph_t graph = nullptr;
           HIP_TRY(hipStreamBeginCapture(s, hipStreamCaptureModeRelaxed));
-          const int rc = one_stage(st[k], true);
+          const int rc = one_stage(st[k], true, gamma);
           const hipError_t ce = hipStreamEndCapture(s, &graph);
           if (rc) {  // (a captured graph that will never run: nothing refers to it)
             if (graph) (void)hipGraphDestroy(graph);
@@ -268,7 +274,7 @@ int pair_loop(EvalX&& eval_x, EvalY&& eval_y, float* x_inout, float* y_inout, co
         HIP_TRY(hipGraphLaunch(exec, s));
         continue;
       }
-      if (int rc = one_stage(st[k], guided)) return rc;
+      if (int rc = one_stage(st[k], guided, gamma)) return rc;
     }
   }
   // (the guard's destructor records graph_done and joins `main` into the caller's stream -- on this path too, so that a

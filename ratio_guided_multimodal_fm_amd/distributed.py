@@ -89,7 +89,7 @@ def _all_gather_rows(t, counts, group):
 
 def sharded_paired_sampler(fm_x, fm_y, ratio_estimator, guidance_method, guidance_strength, num_steps,
                            noise, device, backend=None, group=None, gather="rank0", keep=None, solver='euler',
-                           mc_pairing='paired'):
+                           mc_pairing='paired', guidance_schedule=None):
     """Sharded equivalent of ``paired_sampler`` on explicit host noise.
 
     noise = (x0, y0, mc_x0, mc_y0): the FULL tensors, identical on every rank
@@ -101,10 +101,13 @@ def sharded_paired_sampler(fm_x, fm_y, ratio_estimator, guidance_method, guidanc
     solver: 'euler' | 'midpoint', as in ``paired_sampler``; passed to the backend's calls as a keyword when it is
     not the default.
     mc_pairing: 'paired' only -- cross pairing (``paired_sampler``) has no sharded form: RgfmError.
+    guidance_schedule / a guidance_strength per sample (``paired_sampler``): no sharded form either: RgfmError.
     """
     from ._lib import RgfmError, solver_id
     from .utils.flow_utils import check_pairing
     solver_id(solver)
+    if guidance_schedule is not None or isinstance(guidance_strength, (torch.Tensor, list, tuple)):
+        raise RgfmError("a guidance_schedule and a guidance strength per sample have no sharded form: run them on one device")
     if check_pairing(mc_pairing, guidance_method) == 'cross':
         raise RgfmError("mc_pairing='cross' has no sharded form: the ratio matrix couples every MC sample of one modality "
                         "with every one of the other; run it on one device")
@@ -211,7 +214,8 @@ def make_sharded_sampler(shape_x, shape_y, backend=None, group=None, gather="all
     launchers do -- and ``sharded_paired_sampler`` slices its rows: consecutive calls consume one generator
     stream exactly like the reference's sweep (evaluate_mnist_svhn.py:80: one seeding, no re-seed)."""
     def sampler(fm_x, fm_y, ratio_estimator=None, guidance_method='none', guidance_strength=0.0, num_samples=16,
-                num_steps=100, device='cuda', mc_batch_size=64, solver='euler', mc_pairing='paired'):
+                num_steps=100, device='cuda', mc_batch_size=64, solver='euler', mc_pairing='paired',
+                guidance_schedule=None):
         guided = guidance_method == 'mc_feng' and ratio_estimator is not None
         x0 = torch.randn(num_samples, *shape_x)
         y0 = torch.randn(num_samples, *shape_y)
@@ -219,5 +223,5 @@ def make_sharded_sampler(shape_x, shape_y, backend=None, group=None, gather="all
         my = torch.randn(mc_batch_size, *shape_y) if guided else None
         return sharded_paired_sampler(fm_x, fm_y, ratio_estimator, guidance_method, guidance_strength, num_steps,
                                       (x0, y0, mx, my), torch.device(device), backend=backend, group=group, gather=gather,
-                                      solver=solver, mc_pairing=mc_pairing)
+                                      solver=solver, mc_pairing=mc_pairing, guidance_schedule=guidance_schedule)
     return sampler

@@ -29,7 +29,8 @@ from .models.unet_flexible import FlowMatchingUNetMNIST, FlowMatchingUNetSVHN
 from .sample_mnist_svhn import sample_bimodal_guided_mnist_svhn
 from .utils import load_checkpoint, set_seed
 from .utils.diagnostics import GuidanceDiagnostics, add_cli_args as add_diagnostics_args, row_metrics
-from .utils.flow_utils import add_pairing_arg
+from .utils.flow_utils import add_pairing_arg, shared_mc_sweep
+from .utils.guidance_schedule import add_cli_args as add_schedule_args, from_cli as schedule_from_cli
 
 
 def evaluate_coherence(samples_mnist, samples_svhn, mnist_classifier, svhn_classifier, device):
@@ -68,20 +69,48 @@ def evaluate_conditional_coherence(condition, samples, given, mnist_classifier, 
 
 def run_sweep(fm_mnist, fm_svhn, make_ratio, mnist_classifier, svhn_classifier, methods, strengths,
               num_samples, num_steps, device, mc_batch_size, sampler=sample_bimodal_guided_mnist_svhn, solver='euler', diagnostics=False,
-              mc_pairing='paired'):
+              mc_pairing='paired', shared_mc=False, guidance_schedule=None):
     """The reference's nested loop (:130-183). `make_ratio()` returns a fresh ratio estimator or None.
     `solver` ('euler' | 'midpoint') goes to `sampler` as a keyword when it is not the default.
     `diagnostics`: every guided row also gets ess_mean, ess_min and w_max of the importance weights at step
     int(0.3 * num_steps) (utils/diagnostics.py); without it the rows keep exactly their keys.
     `mc_pairing` = 'cross': the 'mc_feng' configurations guide over all mc_batch_size ** 2 pairs of the MC set (the
-    sampler's `mc_pairing` keyword) and their rows record ``"mc_pairing": "cross"``; 'paired' rows keep their keys."""
+    sampler's `mc_pairing` keyword) and their rows record ``"mc_pairing": "cross"``; 'paired' rows keep their keys.
+    `guidance_schedule` (utils/guidance_schedule.py) goes to `sampler` as a keyword when it is given.
+    `shared_mc`: all strengths of a guided method run as ONE sampler call of ``len(strengths) * num_samples`` rows,
+    row block j carrying strength j, over one MC set, one pre-phase and one start-noise set repeated per block
+    (``utils.flow_utils.shared_mc_sweep``): the strengths' numbers then differ by the strength alone.  Every row of
+    the result gains ``"shared_mc": true``.  The default sampler only (no sharded form)."""
     from ._lib import solver_id
     from .utils.flow_utils import check_pairing
     solver_id(solver)
     check_pairing(mc_pairing)
     kw = {'solver': solver} if solver != 'euler' else {}
+    if guidance_schedule is not None:
+        kw['guidance_schedule'] = guidance_schedule
+    if shared_mc and sampler is not sample_bimodal_guided_mnist_svhn:
+        raise ValueError("shared_mc runs the default sampler: it has no sharded form")
     results = []
     for method in methods:
+        if shared_mc and method != 'none':
+            ratio = make_ratio()
+            if ratio is None:
+                continue
+            diag = GuidanceDiagnostics() if diagnostics else None
+            cross = {'mc_pairing': 'cross'} if mc_pairing == 'cross' and method == 'mc_feng' else {}
+            blocks = shared_mc_sweep(fm_mnist, fm_svhn, ratio, method, strengths, num_samples, num_steps, device,
+                                     mc_batch_size, (1, 32, 32), (3, 32, 32), solver=solver, diagnostics=diag,
+                                     guidance_schedule=guidance_schedule, **cross)
+            for j, (strength, (xs, ys)) in enumerate(zip(strengths, blocks)):
+                metrics = evaluate_coherence(xs, ys, mnist_classifier, svhn_classifier, device)
+                if diag is not None and diag.records is not None:
+                    part = GuidanceDiagnostics.from_records(diag.records[:, j * num_samples:(j + 1) * num_samples], method,
+                                                            solver, num_steps)
+                    metrics = {**metrics, **row_metrics(part, num_steps)}
+                results.append({'method': method, 'guidance_strength': strength, 'experiment': 'mnist_svhn',
+                                **metrics, **cross, 'shared_mc': True})
+                print(f"  method={method} gamma={strength} -> coherence accuracy {metrics['coherence_acc']:.3f}")
+            continue
         for strength in strengths:
             if method == 'none' and strength > 0:
                 continue
@@ -95,6 +124,8 @@ def run_sweep(fm_mnist, fm_svhn, make_ratio, mnist_classifier, svhn_classifier, 
             metrics = evaluate_coherence(xs, ys, mnist_classifier, svhn_classifier, device)
             if diag is not None and diag.records is not None:
                 metrics = {**metrics, **row_metrics(diag, num_steps)}
+            if shared_mc:
+                metrics = {**metrics, 'shared_mc': True}
             results.append({'method': method, 'guidance_strength': strength, 'experiment': 'mnist_svhn',
                             **metrics, **cross})
             print(f"  method={method} gamma={strength} -> coherence accuracy {metrics['coherence_acc']:.3f}")
@@ -119,7 +150,17 @@ def main(argv=None):
                    help='rows sharded over the ranks of a torch.distributed.run launch (one process per GPU, RCCL)')
     add_diagnostics_args(p, sampling=False)
     add_pairing_arg(p)
+    add_schedule_args(p)
+    p.add_argument('--shared_mc', action='store_true',
+                   help='run all strengths of a guided method as one sampler call over one MC set, one pre-phase and one '
+                        'start-noise set (a strength per row): the strengths then differ by the strength alone; not with '
+                        '--sharded')
     args = p.parse_args(argv)
+    schedule = schedule_from_cli(args)
+    if args.shared_mc and args.sharded:
+        p.error('--shared_mc has no --sharded form')
+    if schedule is not None and args.sharded:
+        p.error('--guidance_schedule / --guidance_window have no --sharded form')
     if args.diagnostics and args.sharded:
         p.error('--diagnostics has no --sharded form')
     if args.mc_pairing == 'cross' and args.sharded:
@@ -163,7 +204,8 @@ def main(argv=None):
 
     results = run_sweep(fm_mnist, fm_svhn, make_ratio, mnist_clf, svhn_clf, args.guidance_methods,
                         args.guidance_strengths, args.num_samples, args.num_steps, device, args.mc_batch_size,
-                        sampler=sampler, solver=args.solver, diagnostics=args.diagnostics, mc_pairing=args.mc_pairing)
+                        sampler=sampler, solver=args.solver, diagnostics=args.diagnostics, mc_pairing=args.mc_pairing,
+                        shared_mc=args.shared_mc, guidance_schedule=schedule)
     if args.sharded:
         import torch.distributed as dist
         if dist.is_initialized():

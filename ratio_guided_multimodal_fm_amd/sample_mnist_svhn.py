@@ -15,17 +15,19 @@ from .models.unet_flexible import FlowMatchingUNetMNIST, FlowMatchingUNetSVHN
 from .utils import load_checkpoint, set_seed
 from .utils.diagnostics import GuidanceDiagnostics, add_cli_args as add_diagnostics_args, report_diagnostics
 from .utils.flow_utils import add_pairing_arg, paired_sampler, sample_conditional
+from .utils.guidance_schedule import add_cli_args as add_schedule_args, from_cli as schedule_from_cli
 
 
 def sample_bimodal_guided_mnist_svhn(fm_mnist, fm_svhn, ratio_estimator=None, guidance_method='none',
                                      guidance_strength=0.0, num_samples=16, num_steps=100,
                                      device='cuda', mc_batch_size=64, solver='euler', diagnostics=None,
-                                     mc_pairing='paired'):
+                                     mc_pairing='paired', guidance_schedule=None):
     """Returns ``(samples_mnist [n,1,32,32], samples_svhn [n,3,32,32])`` on `device`.  `diagnostics`: a
-    ``utils.diagnostics.GuidanceDiagnostics`` to fill; `mc_pairing`: 'paired' | 'cross' (``paired_sampler``)."""
+    ``utils.diagnostics.GuidanceDiagnostics`` to fill; `mc_pairing`: 'paired' | 'cross'; `guidance_strength`: a float or
+    one strength per sample; `guidance_schedule`: a scale of it per stage (all: ``paired_sampler``)."""
     return paired_sampler(fm_mnist, fm_svhn, ratio_estimator, guidance_method, guidance_strength,
                           num_samples, num_steps, device, mc_batch_size, (1, 32, 32), (3, 32, 32), solver=solver,
-                          diagnostics=diagnostics, mc_pairing=mc_pairing)
+                          diagnostics=diagnostics, mc_pairing=mc_pairing, guidance_schedule=guidance_schedule)
 
 
 def load_condition(path, shape):
@@ -66,7 +68,11 @@ def main(argv=None):
                    help='condition images [B,1,32,32] (--given mnist) or [B,3,32,32] (--given svhn)')
     add_diagnostics_args(p)
     add_pairing_arg(p)
+    add_schedule_args(p)
     args = p.parse_args(argv)
+    schedule = schedule_from_cli(args)
+    if schedule is not None and args.sharded:
+        p.error('--guidance_schedule / --guidance_window have no --sharded form')
     if args.mc_pairing == 'cross' and (args.guidance_method != 'mc_feng' or args.given or args.sharded):
         p.error('--mc_pairing cross goes with --guidance_method mc_feng; it has no --given and no --sharded form')
     if (args.diagnostics or args.diagnostics_out) and args.sharded:
@@ -121,7 +127,8 @@ def main(argv=None):
         method = 'grad_log_ratio' if args.guidance_method == 'grad_log_ratio' else 'mc_feng'
         out_t = sample_conditional(target, ratio, condition.to(device), 'x' if args.given == 'mnist' else 'y',
                                    args.num_steps, args.guidance_strength, args.mc_batch_size, device=device,
-                                   guidance_method=method, solver=args.solver, diagnostics=diag)
+                                   guidance_method=method, solver=args.solver, diagnostics=diag,
+                                   **({'guidance_schedule': schedule} if schedule is not None else {}))
         report_diagnostics(diag, args.num_steps, args.diagnostics, args.diagnostics_out)
         os.makedirs('outputs/mnist_svhn', exist_ok=True)
         tag = '_grad_log_ratio' if method == 'grad_log_ratio' else ''
@@ -134,7 +141,8 @@ def main(argv=None):
     xs, ys = sampler(fm_mnist, fm_svhn, ratio, args.guidance_method, args.guidance_strength, args.num_samples,
                      args.num_steps, device, args.mc_batch_size, **({'solver': args.solver} if args.solver != 'euler' else {}),
                      **({'diagnostics': diag} if diag is not None else {}),
-                     **({'mc_pairing': args.mc_pairing} if args.mc_pairing != 'paired' else {}))
+                     **({'mc_pairing': args.mc_pairing} if args.mc_pairing != 'paired' else {}),
+                     **({'guidance_schedule': schedule} if schedule is not None else {}))
     report_diagnostics(diag, args.num_steps, args.diagnostics, args.diagnostics_out)
     if args.sharded:
         import torch.distributed as dist

@@ -83,9 +83,12 @@ class GuidanceDiagnostics:
             self.guided = torch.full((len(ts),), method == "grad_log_ratio", dtype=torch.bool)
         return len(ts)
 
-    def _begin(self, method, solver, num_steps, batch, device, step_begin=0, step_end=None, has_mc=True):
-        """Sets the schedule and returns a fresh records tensor [n_stages, batch, 8] on `device` for the loop."""
+    def _begin(self, method, solver, num_steps, batch, device, step_begin=0, step_end=None, has_mc=True, stage_scale=None):
+        """Sets the schedule and returns a fresh records tensor [n_stages, batch, 8] on `device` for the loop.
+        `stage_scale` (a guidance schedule's per-stage values): a stage whose scale is 0 runs unguided."""
         n = self._schedule(method, solver, num_steps, step_begin, step_end, has_mc)
+        if stage_scale is not None:
+            self.guided = self.guided & torch.tensor([float(v) != 0.0 for v in stage_scale], dtype=torch.bool)
         self.records = torch.zeros(n, batch, DIAG_FLOATS, dtype=torch.float32, device=device)
         return self.records
 

@@ -18,6 +18,7 @@ import torch.nn.functional as F
 from .. import _engine
 from .._lib import solver_id as _solver_id
 from .diagnostics import check as _check_diagnostics
+from .guidance_schedule import resolve as _resolve_strength
 
 
 def _device(device):
@@ -188,14 +189,41 @@ def add_pairing_arg(p):
                         "with --sharded)")
 
 
+def _strength_kwargs(guidance_strength, guidance_schedule, rows, num_steps, solver, dev_of, models, what='num_samples'):
+    """(gamma, keywords) of the main loop's _engine call for a strength that may be a vector and a schedule that may be
+    given: all checks run here, before any device work.  A scalar strength without a schedule gives (the strength as
+    passed, {}): the call goes out as it always did.  `dev_of()`: the device, asked for only when a vector goes there."""
+    from .._lib import RgfmError
+    gamma, vec, scale = _resolve_strength(guidance_strength, guidance_schedule, rows, num_steps, solver, what)
+    if vec is None and scale is None:
+        return gamma, {}
+    for m in models:
+        if not isinstance(m._engine, _engine.UNetEngine):
+            raise RgfmError("a guidance strength per sample and a guidance_schedule need U-Net velocity nets (FlexibleUNet "
+                            f"and its presets); {type(m).__name__} takes a scalar strength only")
+    kw = {}
+    if vec is not None:
+        kw['gamma_rows'] = vec.to(dev_of()).contiguous()
+    if scale is not None:
+        kw['stage_scale'] = scale
+    return gamma, kw
+
+
 def _stats(name, t):
     return f"{name}: min={t.min():.4f}, max={t.max():.4f}, mean={t.mean():.4f}"
 
 
 def paired_sampler(fm_x, fm_y, ratio_estimator, guidance_method, guidance_strength, num_samples,
                    num_steps, device, mc_batch_size, shape_x, shape_y, noise=None, verbose=True, solver='euler',
-                   diagnostics=None, mc_pairing='paired'):
+                   diagnostics=None, mc_pairing='paired', guidance_schedule=None):
     """Shared body of both paired samplers.
+
+    `guidance_strength`: a float, or a 1-D tensor / sequence of `num_samples` strengths (one per pair).
+    `guidance_schedule` = None | ``utils.guidance_schedule.GuidanceSchedule`` | callable s(t) | sequence of per-stage
+    values: scales the strength per stage of the main loop; a stage whose scale is 0 runs unguided and skips the
+    guidance work (``GuidanceSchedule.window``).  Row b, stage k: ``float64(strength_b) * s_k``.  Both guidance
+    methods, both solvers, both pairings, with and without `diagnostics`; U-Net nets.  With a float strength and no
+    schedule the call is what it was.
 
     `noise` = (x0, y0, mc_x0, mc_y0) overrides the generator draws (parity
     tests upload CPU-generated noise); tensors are copied, never modified.
@@ -219,6 +247,8 @@ def paired_sampler(fm_x, fm_y, ratio_estimator, guidance_method, guidance_streng
     if mc_pairing == 'cross' and ratio_estimator is not None:
         _engine._check_cross((mc_batch_size, mc_batch_size), mc_batch_size, mc_batch_size, fm_x, fm_y)
     _engine._solver(solver, fm_x, fm_y)
+    guidance_strength, gs_kw = _strength_kwargs(guidance_strength, guidance_schedule, num_samples, num_steps, solver,
+                                                lambda: _device(device), (fm_x, fm_y))
     fm_x.eval()
     fm_y.eval()
     if ratio_estimator is not None:
@@ -269,19 +299,52 @@ def paired_sampler(fm_x, fm_y, ratio_estimator, guidance_method, guidance_streng
             raise ValueError(f"Unknown loss_type: {ratio_estimator.loss_type}")
         diag = None
         if diagnostics is not None and num_samples:
-            diag = diagnostics._begin('grad_log_ratio', solver, num_steps, num_samples, dev)
-        _engine.sample_pair_grad(fm_x, fm_y, ratio_estimator, x_t, y_t, num_steps, guidance_strength, solver=solver, diag=diag)
+            diag = diagnostics._begin('grad_log_ratio', solver, num_steps, num_samples, dev, stage_scale=gs_kw.get('stage_scale'))
+        _engine.sample_pair_grad(fm_x, fm_y, ratio_estimator, x_t, y_t, num_steps, guidance_strength, solver=solver, diag=diag,
+                                 **gs_kw)
         return x_t, y_t
     diag = None
     if diagnostics is not None and num_samples:
-        diag = diagnostics._begin('mc_feng' if guided else 'none', solver, num_steps, num_samples, dev)
-    _engine.sample_pair(fm_x, fm_y, x_t, y_t, mc_x1, mc_y1, mc_ratios, num_steps, guidance_strength, solver=solver, diag=diag)
+        diag = diagnostics._begin('mc_feng' if guided else 'none', solver, num_steps, num_samples, dev, stage_scale=gs_kw.get('stage_scale'))
+    _engine.sample_pair(fm_x, fm_y, x_t, y_t, mc_x1, mc_y1, mc_ratios, num_steps, guidance_strength, solver=solver, diag=diag,
+                        **gs_kw)
     return x_t, y_t
+
+
+def shared_mc_sweep(fm_x, fm_y, ratio_estimator, guidance_method, strengths, num_samples, num_steps, device,
+                    mc_batch_size, shape_x, shape_y, solver='euler', diagnostics=None, mc_pairing='paired',
+                    guidance_schedule=None):
+    """All `strengths` of one guided method as ONE ``paired_sampler`` call of ``len(strengths) * num_samples`` rows: row
+    block j carries ``strengths[j]`` (a strength per row), over one MC set, one pre-phase and one start-noise set
+    ``[num_samples]`` repeated per block (common random numbers: the blocks differ by the strength alone).  The noise is
+    drawn once, in the order of one ordinary call (x0, y0, then mc_x0, mc_y0 for 'mc_feng').  Rows do not depend on the
+    batch they run in, so block j has the bits of a call with that strength on the same noise and MC set.
+    Returns ``[(samples_x, samples_y), ...]``, one pair ``[num_samples, ...]`` per strength; `diagnostics` (optional)
+    holds the records of all rows, block after block."""
+    if guidance_method not in ('mc_feng', 'grad_log_ratio') or ratio_estimator is None:
+        raise ValueError(f"a shared-MC sweep runs a guided method with its ratio estimator, got {guidance_method!r}")
+    strengths = [float(g) for g in strengths]
+    if not strengths:
+        return []
+    dev = _device(device)
+    x0 = torch.randn(num_samples, *shape_x, device=dev)
+    y0 = torch.randn(num_samples, *shape_y, device=dev)
+    mc_x0 = mc_y0 = None
+    if guidance_method == 'mc_feng':
+        mc_x0 = torch.randn(mc_batch_size, *shape_x, device=dev)
+        mc_y0 = torch.randn(mc_batch_size, *shape_y, device=dev)
+    k = len(strengths)
+    rows = torch.tensor(strengths, dtype=torch.float32).repeat_interleave(num_samples)
+    noise = (x0.repeat(k, 1, 1, 1), y0.repeat(k, 1, 1, 1), mc_x0, mc_y0)
+    xs, ys = paired_sampler(fm_x, fm_y, ratio_estimator, guidance_method, rows, k * num_samples, num_steps, dev,
+                            mc_batch_size, shape_x, shape_y, noise=noise, verbose=False, solver=solver,
+                            diagnostics=diagnostics, mc_pairing=mc_pairing, guidance_schedule=guidance_schedule)
+    return [(xs[j * num_samples:(j + 1) * num_samples], ys[j * num_samples:(j + 1) * num_samples]) for j in range(k)]
 
 
 def sample_conditional(fm_target, ratio_estimator, condition, given='x', num_steps=100, guidance_strength=1.0,
                        mc_batch_size=256, mc_samples=None, device=None, guidance_method='mc_feng', solver='euler',
-                       diagnostics=None):
+                       diagnostics=None, guidance_schedule=None):
     """Partners for `condition` in the other modality: one sample of `fm_target`'s modality per condition image.
 
     ``given='x'``: `condition` is the estimator's x argument and the target is its y; ``given='y'`` the other way
@@ -306,6 +369,9 @@ def sample_conditional(fm_target, ratio_estimator, condition, given='x', num_ste
     `diagnostics` = a ``utils.diagnostics.GuidanceDiagnostics``: filled by the guided loop (the target's fields in the
     ``_x`` entries, the ``_y`` entries 0); the samples keep their bits.
 
+    `guidance_strength` may be a 1-D tensor / sequence of ``len(condition)`` strengths and `guidance_schedule` scales
+    it per stage, as in ``paired_sampler``.
+
     Returns the samples ``[len(condition), C, H, W]`` on the device.  U-Net targets only; ``--sharded`` launches have
     no conditional form yet.
     """
@@ -323,6 +389,9 @@ def sample_conditional(fm_target, ratio_estimator, condition, given='x', num_ste
     ratio_estimator.eval()
     if ratio_estimator.loss_type not in ("disc", "rulsif"):
         raise ValueError(f"Unknown loss_type: {ratio_estimator.loss_type}")
+    guidance_strength, gs_kw = _strength_kwargs(guidance_strength, guidance_schedule, len(condition), num_steps, solver,
+                                                lambda: _device(condition.device if device is None else device),
+                                                (fm_target,), what='len(condition)')
     dev = _device(condition.device if device is None else device)
     condition = condition.to(dev, torch.float32).contiguous()
     shape = (fm_target.in_channels, fm_target.img_size, fm_target.img_size)
@@ -331,9 +400,9 @@ def sample_conditional(fm_target, ratio_estimator, condition, given='x', num_ste
         ctx = ratio_estimator._engine.cond_prepare(condition, given, shape)
         diag = None
         if diagnostics is not None and s_t.shape[0]:
-            diag = diagnostics._begin('grad_log_ratio', solver, num_steps, s_t.shape[0], dev)
+            diag = diagnostics._begin('grad_log_ratio', solver, num_steps, s_t.shape[0], dev, stage_scale=gs_kw.get('stage_scale'))
         return _engine.sample_cond_grad(fm_target, ratio_estimator, s_t, ctx, given, num_steps, guidance_strength, solver=solver,
-                                        diag=diag)
+                                        diag=diag, **gs_kw)
     if mc_samples is None:
         mc = torch.randn(mc_batch_size, *shape, device=dev)
         _engine.sample_single(fm_target, mc, num_steps, solver=solver)
@@ -346,13 +415,13 @@ def sample_conditional(fm_target, ratio_estimator, condition, given='x', num_ste
         ratios = ratio_estimator.cross_log_ratio(mc, condition).exp().T.contiguous()
     diag = None
     if diagnostics is not None and s_t.shape[0]:
-        diag = diagnostics._begin('mc_feng', solver, num_steps, s_t.shape[0], dev)
-    return _engine.sample_cond(fm_target, s_t, mc, ratios, num_steps, guidance_strength, solver=solver, diag=diag)
+        diag = diagnostics._begin('mc_feng', solver, num_steps, s_t.shape[0], dev, stage_scale=gs_kw.get('stage_scale'))
+    return _engine.sample_cond(fm_target, s_t, mc, ratios, num_steps, guidance_strength, solver=solver, diag=diag, **gs_kw)
 
 
 def sample_bimodal_guided(fm_x, fm_y, ratio_estimator=None, guidance_method='none',
                           guidance_strength=0.0, num_samples=16, num_steps=100, device='cuda',
-                          mc_batch_size=64, solver='euler', diagnostics=None, mc_pairing='paired'):
+                          mc_batch_size=64, solver='euler', diagnostics=None, mc_pairing='paired', guidance_schedule=None):
     """Pairs of 1x28x28 images, optional mc_feng guidance (reference :178-375).
 
     Returns ``(samples_x [n,1,28,28], samples_y [n,1,28,28])`` on `device`.
@@ -362,7 +431,9 @@ def sample_bimodal_guided(fm_x, fm_y, ratio_estimator=None, guidance_method='non
     available through `diagnostics`: pass a ``utils.diagnostics.GuidanceDiagnostics`` and read its
     ``reference_block(int(0.3 * num_steps))`` (the same text) or its per-sample, per-stage records.
     ``mc_pairing='cross'``: the guidance over all ``mc_batch_size ** 2`` pairs of the MC set (``paired_sampler``).
+    `guidance_strength` may also hold one strength per sample and `guidance_schedule` scales it per stage
+    (``paired_sampler``, ``utils/guidance_schedule.py``).
     """
     return paired_sampler(fm_x, fm_y, ratio_estimator, guidance_method, guidance_strength,
                           num_samples, num_steps, device, mc_batch_size, (1, 28, 28), (1, 28, 28), solver=solver,
-                          diagnostics=diagnostics, mc_pairing=mc_pairing)
+                          diagnostics=diagnostics, mc_pairing=mc_pairing, guidance_schedule=guidance_schedule)
