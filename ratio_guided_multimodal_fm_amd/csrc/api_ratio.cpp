@@ -127,6 +127,38 @@ int check_ratio_flex_desc(const rgfm_ratio_flex_desc* f, rgfm_ratio_desc* d) {
   return RGFM_OK;
 }
 
+// BatchNorm encoders inside a gradient-guided sampler loop: conv i stages S_A silu(z) of layer i - 1 raw on the two fp16
+// planes (RatioPass::encode), z = gamma (c - mean) / sqrt(var + eps) + beta.  The staging path covers the high side (the
+// x net's range flag), but nothing on this path looks at the low side: the producer's epilogue is the BatchNorm, not a
+// ConvArgs::small_check.  So, as norm_params_ok does for a GroupNorm in front of a U-Net conv: a layer whose gamma AND
+// beta are all below 2^-6 -- its output would sit under the two-plane floor -- takes its reader off the fp16 path here,
+// at create / update_params (after read_hx_flags, which recomputes every verdict); that conv then runs the exact fp32
+// kernel in the loops.  Only the low side: a large layer is left to the range flag, whose fallback covers the whole call.
+// One stream-ordered read of the norm parameters (weight and bias are adjacent in the blob), nothing per launch.
+int demote_by_batchnorms(rgfm_ratio* h, hipStream_t s) {
+  std::vector<std::vector<float>> host;
+  std::vector<HxImage*> readers;
+  for (auto* e : {&h->ex, &h->ey})
+    for (size_t i = 1; i < e->convs.size(); ++i) {
+      const auto& prev = e->convs[i - 1];
+      if (prev.nb != prev.nw + (size_t)prev.w.cout) return fail(RGFM_EINVAL, "BatchNorm weight and bias are not adjacent");
+      host.emplace_back((size_t)2 * prev.w.cout);
+      readers.push_back(&e->convs[i].w.hx);
+    }
+  size_t k = 0;
+  for (auto* e : {&h->ex, &h->ey})
+    for (size_t i = 1; i < e->convs.size(); ++i, ++k)
+      if (hipMemcpyAsync(host[k].data(), h->params + e->convs[i - 1].nw, host[k].size() * sizeof(float), hipMemcpyDeviceToHost, s) != hipSuccess)
+        return fail(RGFM_EHIP, "reading the BatchNorm parameters back failed");
+  if (hipStreamSynchronize(s) != hipSuccess) return fail(RGFM_EHIP, "reading the BatchNorm parameters back failed");
+  for (k = 0; k < host.size(); ++k) {
+    float lo = 0.f;
+    for (float v : host[k]) lo = std::max(lo, std::fabs(v));
+    if (!(lo >= 0.015625f)) readers[k]->ok = false;  // (NaN parameters too)
+  }
+  return RGFM_OK;
+}
+
 // Every derived image of the handle from h->params: the fp32-packed and two-plane conv weights, the folded BatchNorm
 // scale/shift, and the transposed weights of the gradient path (dL/d(in) of a 3x3 conv is the conv of dL/d(out) with
 // the weights transposed and the taps flipped; of a Linear, the Linear with W^T); then which convs may run on the fp16
@@ -165,7 +197,8 @@ int pack_ratio(rgfm_ratio* h, hipStream_t s) {
       images.push_back(&w.hx);
       images.push_back(&e->convs[i].wt_h);
     }
-  return read_hx_flags(*h, images, s);
+  if (int rc = read_hx_flags(*h, images, s)) return rc;
+  return h->gn_encoders() ? RGFM_OK : demote_by_batchnorms(h, s);
 }
 
 // pairs per chunk of the cross evaluation: 32 MB of first-layer activations at hidden_dim 512, 64 MB at the largest, 1024
