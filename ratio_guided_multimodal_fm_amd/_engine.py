@@ -38,14 +38,27 @@ def _require_hip(*tensors):
 
 
 class _Workspace:
-    """Grow-only byte buffer per device."""
+    """Grow-only byte buffer per device, shared by every call that goes through it.
+
+    The calls are ordered by the stream they run on.  When the current stream is not the one that took the buffer
+    last, it is made to wait for the streams that used the buffer since the last such hand-over -- a call on another
+    stream then starts behind the work that is still pending in the scratch (also when it grows the buffer: one rule).
+    A caller that stays on one stream enqueues nothing."""
 
     def __init__(self):
         self.buf = None
         self.streams = set()
+        self.last = None  # the stream of the latest get
 
     def get(self, nbytes, device):
         cur = torch.cuda.current_stream(device)
+        waited = False
+        if self.last is not None and cur != self.last and self.buf is not None and self.buf.device == device:
+            for st in self.streams:
+                if st != cur:
+                    cur.wait_stream(st)
+            waited = True
+        self.last = cur
         if self.buf is None or self.buf.numel() < nbytes or self.buf.device != device:
             old = self.buf
             self.buf = torch.empty(max(int(nbytes), 16), dtype=torch.uint8, device=device)
@@ -54,6 +67,9 @@ class _Workspace:
                 # caching allocator from handing its memory out before those streams get there
                 for st in self.streams:
                     old.record_stream(st)
+            self.streams = set()
+        elif waited:
+            # everything those streams enqueued now precedes `cur`: from here on `cur` stands for them
             self.streams = set()
         self.streams.add(cur)
         return self.buf
