@@ -4,6 +4,7 @@ PyTorch is used for what it is good at here: owning device memory (parameter
 blob, workspace, I/O tensors) and naming the stream.  All arithmetic happens
 inside librgfm_hip.so.
 """
+import collections
 import ctypes
 import os
 import weakref
@@ -326,9 +327,30 @@ class _TrainFn(torch.autograd.Function):
         return (None, None, None, *dins, *rest, *grads)
 
 
+# The exports of a sampler loop, one row each: the entry point and its workspace query, their *_diag pair, the *_gs entry
+# point (a strength per row / per stage; no query of its own), and for the U-Net pair the cross-pairing entry points (one
+# query for calls with and without records).  None: the loop has no such export.  _run_loop picks from the row.
+_Loop = collections.namedtuple("_Loop", "fn ws diag diag_ws gs cross cross_ws cross_gs", defaults=(None,) * 6)
+_SINGLE = _Loop("rgfm_sample_single_ode", "rgfm_sample_single_ode_workspace_bytes")
+_TWO = _Loop("rgfm_sample_two", "rgfm_sample_two_workspace_bytes")
+_PAIR = _Loop("rgfm_sample_pair_ode", "rgfm_sample_pair_ode_workspace_bytes",
+              "rgfm_sample_pair_diag", "rgfm_sample_pair_diag_workspace_bytes", "rgfm_sample_pair_gs",
+              "rgfm_sample_pair_cross", "rgfm_sample_pair_cross_workspace_bytes", "rgfm_sample_pair_cross_gs")
+_PAIR_GRAD = _Loop("rgfm_sample_pair_grad_ode", "rgfm_sample_pair_grad_ode_workspace_bytes",
+                   "rgfm_sample_pair_grad_diag", "rgfm_sample_pair_grad_diag_workspace_bytes", "rgfm_sample_pair_grad_gs")
+_COND = _Loop("rgfm_sample_cond_ode", "rgfm_sample_cond_ode_workspace_bytes",
+              "rgfm_sample_cond_diag", "rgfm_sample_cond_diag_workspace_bytes", "rgfm_sample_cond_gs")
+_COND_GRAD = _Loop("rgfm_sample_cond_grad_ode", "rgfm_sample_cond_grad_ode_workspace_bytes",
+                   "rgfm_sample_cond_grad_diag", "rgfm_sample_cond_grad_diag_workspace_bytes", "rgfm_sample_cond_grad_gs")
+_FM_SINGLE = _Loop("rgfm_fmnet_sample_single", "rgfm_fmnet_workspace_bytes")
+_FM_PAIR = _Loop("rgfm_fmnet_sample_pair", "rgfm_fmnet_sample_pair_workspace_bytes",
+                 "rgfm_fmnet_sample_pair_diag", "rgfm_fmnet_sample_pair_diag_workspace_bytes")
+_GUIDED_LOOPS = (_PAIR, _PAIR_GRAD, _COND, _COND_GRAD, _FM_PAIR)
+
+
 class _VelocityEngine(_EngineBase):
     """Shared handle cache / forward of the velocity nets; subclasses name the ABI family."""
-    SINGLE = SINGLE_WS = PAIR = PAIR_WS = None
+    SINGLE = PAIR = None  # the family's _Loop rows
     TRAIN = None  # the family's _TrainSpec
 
     def _check_input(self, m, x):
@@ -389,8 +411,7 @@ class _VelocityEngine(_EngineBase):
 class FmNetEngine(_VelocityEngine):
     """FlowMatchingModel ('--model original', reference src/models/flow_matching.py:127-173)."""
     PREFIX = "rgfm_fmnet"
-    SINGLE, SINGLE_WS = "rgfm_fmnet_sample_single", "rgfm_fmnet_workspace_bytes"
-    PAIR, PAIR_WS = "rgfm_fmnet_sample_pair", "rgfm_fmnet_sample_pair_workspace_bytes"
+    SINGLE, PAIR = _FM_SINGLE, _FM_PAIR
     TRAIN = _TrainSpec(inputs=2, grads=1, out_shape=lambda x, t: x.shape,
                        args=lambda x, t, out, n, training, p, seed, stats: (_ptr(x), _ptr(t), t.numel(), _ptr(out), n))
 
@@ -414,8 +435,7 @@ class FmNetEngine(_VelocityEngine):
 class UNetEngine(_VelocityEngine):
     PREFIX = "rgfm_unet"
     # (the *_ode entry points take the solver id; with RGFM_SOLVER_EULER they are the Euler loops, bit for bit)
-    SINGLE, SINGLE_WS = "rgfm_sample_single_ode", "rgfm_sample_single_ode_workspace_bytes"
-    PAIR, PAIR_WS = "rgfm_sample_pair_ode", "rgfm_sample_pair_ode_workspace_bytes"
+    SINGLE, PAIR = _SINGLE, _PAIR
     TRAIN = _TrainSpec(inputs=2, grads=1, out_shape=lambda x, t: x.shape, dropout=True,
                        args=lambda x, t, out, n, training, p, seed, stats: (_ptr(x), _ptr(t), t.numel(), _ptr(out), n, p, seed))
 
@@ -1026,18 +1046,6 @@ def _solver(solver, *models):
     return sid
 
 
-def _diag_fn(name):
-    """The *_diag twin of a guided loop's entry point or workspace query (rgfm_sample_pair_ode -> rgfm_sample_pair_diag)."""
-    tail = "_workspace_bytes" if name.endswith("_workspace_bytes") else ""
-    stem = name[:len(name) - len(tail)]
-    return (stem[:-4] if stem.endswith("_ode") else stem) + "_diag" + tail
-
-
-def _gs_fn(name):
-    """The *_gs twin of a guided U-Net loop's entry point (rgfm_sample_pair_ode -> rgfm_sample_pair_gs)."""
-    return (name[:-4] if name.endswith("_ode") else name) + "_gs"
-
-
 def _check_strength(gamma_rows, stage_scale, batch, num_steps, steps, sid, models):
     """Argument checks of a call with a strength per row (`gamma_rows`: fp32 device tensor [batch]) and / or a scale per
     stage (`stage_scale`: floats, one per stage of the call), before any device work.  Returns what _run_loop takes as
@@ -1065,34 +1073,33 @@ def _check_strength(gamma_rows, stage_scale, batch, num_steps, steps, sid, model
     return gamma_rows, arr
 
 
-def _run_loop(fn, ws_fn, ws_args, args, steps, sid, dev, ws=None, diag=None, cross=False, strength=None):
-    """One native sampler loop: the size query `ws_fn`(*ws_args[, sid]), the workspace (`ws`: a _Workspace; default the
-    samplers' shared one), then `fn`(*args, *steps[, sid], workspace, stream).  `steps`: (step_begin, step_end).  sid
-    None: entry points without a solver argument (the FlowMatchingModel loops).  `diag`: a records tensor
-    [n_stages, B, RGFM_DIAG_FLOATS] -- the loop's *_diag twin runs and fills it (guided loops only).  `cross`: the
-    U-Net pair loop over all pairs of the MC set (rgfm_sample_pair_cross: one entry point with and without records).
-    `strength`: what _check_strength returns -- not None: the loop's *_gs twin runs (U-Net loops), the namesake's
-    arguments with (gamma_rows, stage_scale, n_stage_scale) behind gamma and its workspace query."""
+def _run_loop(loop, ws_args, args, steps, sid, dev, ws=None, diag=None, cross=False, strength=None):
+    """One native sampler loop (`loop`: its _Loop row): the size query (*ws_args[, sid]), the workspace (`ws`: a
+    _Workspace; default the samplers' shared one), then the entry point (*args, *steps[, sid], workspace, stream).
+    `steps`: (step_begin, step_end).  sid None: entry points without a solver argument (the FlowMatchingModel loops).
+    `diag`: a records tensor [n_stages, B, RGFM_DIAG_FLOATS] -- the loop's *_diag pair runs and fills it (guided loops
+    only).  `cross`: the U-Net pair loop over all pairs of the MC set (one entry point with and without records).
+    `strength`: what _check_strength returns -- not None: the loop's *_gs entry point runs (U-Net loops), the *_diag
+    arguments with (gamma_rows, stage_scale, n_stage_scale) behind gamma, in the workspace chosen above."""
     L = _lib.lib()
     tail = () if sid is None else (sid,)
-    sink = ()
-    base_fn = fn
+    fn, ws_fn, sink = loop.fn, loop.ws, ()
     if diag is not None:
         if not (diag.is_cuda and diag.dtype == torch.float32 and diag.is_contiguous() and diag.dim() == 3
                 and diag.shape[2] == _lib.DIAG_FLOATS):
             raise _lib.RgfmError(f"diagnostics records: a contiguous fp32 device tensor [n_stages, B, {_lib.DIAG_FLOATS}] "
                                  f"expected, got {tuple(diag.shape)} {diag.dtype} on {diag.device}")
-        fn, ws_fn = _diag_fn(fn), _diag_fn(ws_fn)
+        fn, ws_fn = loop.diag, loop.diag_ws
         sink = (_ptr(diag), diag.shape[0] * diag.shape[1])
     if cross:
-        fn, ws_fn = "rgfm_sample_pair_cross", "rgfm_sample_pair_cross_workspace_bytes"
-        sink = sink or (None, 0)
+        fn, ws_fn = loop.cross, loop.cross_ws
     if strength is not None:
         rows, scale = strength
         if rows is not None and not (rows.is_cuda and rows.is_contiguous() and rows.device == dev):
             raise _lib.RgfmError(f"gamma_rows must be a contiguous tensor on {dev}, got one on {rows.device}")
-        fn = "rgfm_sample_pair_cross_gs" if cross else _gs_fn(base_fn)
+        fn = loop.cross_gs if cross else loop.gs
         args = (*args, _ptr(rows), scale, scale.n if scale is not None else 0)
+    if cross or strength is not None:  # (these entry points always take the sink's two arguments)
         sink = sink or (None, 0)
     nb = ctypes.c_size_t()
     _lib.check(getattr(L, ws_fn)(*ws_args, *tail, ctypes.byref(nb)))
@@ -1127,7 +1134,7 @@ def _sample_single(model, x, num_steps, step_begin=0, step_end=None, solver='eul
         return x
     with torch.cuda.device(dev):
         h = eng.handle(dev)
-        _run_loop(eng.SINGLE, eng.SINGLE_WS, (h, B), (h, _ptr(x), B, int(num_steps)), (step_begin, step_end),
+        _run_loop(eng.SINGLE, (h, B), (h, _ptr(x), B, int(num_steps)), (step_begin, step_end),
                   _solver_arg(eng, sid), dev, ws=eng._ws)
     return x
 
@@ -1145,7 +1152,7 @@ def _sample_two(fm_x, x, fm_y, y, num_steps, solver):
     dev = x.device
     with torch.cuda.device(dev):
         hx, hy = fm_x._engine.handle(dev), fm_y._engine.handle(dev)
-        _run_loop("rgfm_sample_two", "rgfm_sample_two_workspace_bytes", (hx, hy, x.shape[0], y.shape[0]),
+        _run_loop(_TWO, (hx, hy, x.shape[0], y.shape[0]),
                   (hx, hy, _ptr(x), _ptr(y), x.shape[0], y.shape[0], int(num_steps)), (0, num_steps), sid, dev)
     return x, y
 
@@ -1226,11 +1233,10 @@ def sample_pair(fm_x, fm_y, x, y, mc_x1, mc_y1, mc_ratios, num_steps, gamma, ste
     def run():
         with torch.cuda.device(dev):
             hx, hy = fm_x._engine.handle(dev), fm_y._engine.handle(dev)
-            _run_loop(ex.PAIR, ex.PAIR_WS, (hx, hy, B, n_mc),
+            _run_loop(ex.PAIR, (hx, hy, B, n_mc),
                       (hx, hy, _ptr(x), _ptr(y), _ptr(mc_x1 if n_mc else None), _ptr(mc_y1 if n_mc else None),
                        _ptr(mc_ratios if n_mc else None), n_mc, B, int(num_steps), float(gamma)),
-                      (step_begin, step_end), _solver_arg(ex, sid), dev, diag=diag, cross=cross,
-                      **({} if strength is None else {"strength": strength}))
+                      (step_begin, step_end), _solver_arg(ex, sid), dev, diag=diag, cross=cross, strength=strength)
         return x, y
     return _range_guarded(dev, [x, y], run, [fm_x._engine, fm_y._engine])
 
@@ -1259,9 +1265,9 @@ def sample_pair_grad(fm_x, fm_y, ratio_estimator, x, y, num_steps, gamma, step_b
     def run():
         with torch.cuda.device(dev):
             hx, hy, hr = fm_x._engine.handle(dev), fm_y._engine.handle(dev), ratio_estimator._engine.handle(dev)
-            _run_loop("rgfm_sample_pair_grad_ode", "rgfm_sample_pair_grad_ode_workspace_bytes", (hx, hy, hr, B),
+            _run_loop(_PAIR_GRAD, (hx, hy, hr, B),
                       (hx, hy, hr, _ptr(x), _ptr(y), B, int(num_steps), float(gamma)), (step_begin, step_end), sid, dev,
-                      diag=diag, **({} if strength is None else {"strength": strength}))
+                      diag=diag, strength=strength)
         return x, y
     return _range_guarded(dev, [x, y], run, [fm_x._engine, fm_y._engine])
 
@@ -1279,6 +1285,19 @@ def _block_gamma(gamma, batch, dev, name):
     return name + "_rows", _ptr(gamma)
 
 
+def _block(dev, ws_fn, ws_args, fn, *args):
+    """One guidance-block call: the size query `ws_fn`(*ws_args), a buffer of the samplers' workspace, then
+    `fn`(*args, workspace, stream).  A tensor among `args` is an input: it is passed contiguous.  What the block writes
+    comes as the pointer of the caller's own tensor."""
+    L = _lib.lib()
+    with torch.cuda.device(dev):
+        nb = ctypes.c_size_t()
+        _lib.check(getattr(L, ws_fn)(*ws_args, ctypes.byref(nb)))
+        ws = _sampler_ws.get(nb.value, dev)
+        args = [_ptr(a.contiguous()) if isinstance(a, torch.Tensor) else a for a in args]
+        _lib.check(getattr(L, fn)(*args, _ptr(ws), nb.value, _stream(dev)))
+
+
 def guidance_apply(x, y, vx, vy, mc_x1, mc_y1, mc_ratios, t, gamma, want_weights=False):
     """One guidance evaluation (parity hook): overwrites vx, vy; returns weights or None.  `gamma`: a number, or an
     fp32 device tensor [B] with a strength per row (rgfm_guidance_apply_rows); the other blocks take it the same way."""
@@ -1286,16 +1305,9 @@ def guidance_apply(x, y, vx, vy, mc_x1, mc_y1, mc_ratios, t, gamma, want_weights
     B, N, dev = x.shape[0], mc_x1.shape[0], x.device
     dx, dy = x[0].numel(), y[0].numel()
     w = torch.empty(B, N, device=dev) if want_weights else None
-    L = _lib.lib()
-    with torch.cuda.device(dev):
-        nb = ctypes.c_size_t()
-        _lib.check(L.rgfm_guidance_workspace_bytes(B, N, ctypes.byref(nb)))
-        ws = _sampler_ws.get(nb.value, dev)
-        fn, g = _block_gamma(gamma, B, dev, "rgfm_guidance_apply")
-        _lib.check(getattr(L, fn)(_ptr(x.contiguous()), _ptr(y.contiguous()), _ptr(vx), _ptr(vy),
-                                  _ptr(mc_x1.contiguous()), _ptr(mc_y1.contiguous()),
-                                  _ptr(mc_ratios.contiguous()), B, N, dx, dy, float(t),
-                                  g, _ptr(w), _ptr(ws), nb.value, _stream(dev)))
+    fn, g = _block_gamma(gamma, B, dev, "rgfm_guidance_apply")
+    _block(dev, "rgfm_guidance_workspace_bytes", (B, N), fn, x, y, _ptr(vx), _ptr(vy), mc_x1, mc_y1, mc_ratios, B, N, dx, dy,
+           float(t), g, _ptr(w))
     return w
 
 
@@ -1323,16 +1335,9 @@ def guidance_apply_cross(x, y, vx, vy, mc_x1, mc_y1, ratio_matrix, t, gamma, wan
     _check_cross(ratio_matrix.shape, N, mc_y1.shape[0])
     dx, dy = x[0].numel(), y[0].numel()
     wx, wy = (torch.empty(B, N, device=dev), torch.empty(B, N, device=dev)) if want_weights else (None, None)
-    L = _lib.lib()
-    with torch.cuda.device(dev):
-        nb = ctypes.c_size_t()
-        _lib.check(L.rgfm_guidance_cross_workspace_bytes(B, N, dx, dy, ctypes.byref(nb)))
-        ws = _sampler_ws.get(nb.value, dev)
-        fn, g = _block_gamma(gamma, B, dev, "rgfm_guidance_apply_cross")
-        _lib.check(getattr(L, fn)(_ptr(x.contiguous()), _ptr(y.contiguous()), _ptr(vx), _ptr(vy),
-                                  _ptr(mc_x1.contiguous()), _ptr(mc_y1.contiguous()),
-                                  _ptr(ratio_matrix.contiguous()), B, N, dx, dy, float(t), g,
-                                  _ptr(wx), _ptr(wy), _ptr(ws), nb.value, _stream(dev)))
+    fn, g = _block_gamma(gamma, B, dev, "rgfm_guidance_apply_cross")
+    _block(dev, "rgfm_guidance_cross_workspace_bytes", (B, N, dx, dy), fn, x, y, _ptr(vx), _ptr(vy), mc_x1, mc_y1,
+           ratio_matrix, B, N, dx, dy, float(t), g, _ptr(wx), _ptr(wy))
     return (wx, wy) if want_weights else None
 
 
@@ -1344,15 +1349,8 @@ def guidance_diag_cross(x, y, vx, vy, mc_x1, mc_y1, ratio_matrix, t):
     _check_cross(ratio_matrix.shape, N, mc_y1.shape[0])
     dx, dy = x[0].numel(), y[0].numel()
     out = torch.empty(B, _lib.DIAG_FLOATS, device=dev)
-    L = _lib.lib()
-    with torch.cuda.device(dev):
-        nb = ctypes.c_size_t()
-        _lib.check(L.rgfm_guidance_cross_workspace_bytes(B, N, dx, dy, ctypes.byref(nb)))
-        ws = _sampler_ws.get(nb.value, dev)
-        _lib.check(L.rgfm_guidance_diag_cross(_ptr(x.contiguous()), _ptr(y.contiguous()), _ptr(vx.contiguous()),
-                                              _ptr(vy.contiguous()), _ptr(mc_x1.contiguous()), _ptr(mc_y1.contiguous()),
-                                              _ptr(ratio_matrix.contiguous()), B, N, dx, dy, float(t), _ptr(out), _ptr(ws),
-                                              nb.value, _stream(dev)))
+    _block(dev, "rgfm_guidance_cross_workspace_bytes", (B, N, dx, dy), "rgfm_guidance_diag_cross", x, y, vx, vy, mc_x1,
+           mc_y1, ratio_matrix, B, N, dx, dy, float(t), _ptr(out))
     return out
 
 
@@ -1363,15 +1361,8 @@ def guidance_diag(x, y, vx, vy, mc_x1, mc_y1, mc_ratios, t):
     B, N, dev = x.shape[0], mc_x1.shape[0], x.device
     dx, dy = x[0].numel(), y[0].numel()
     out = torch.empty(B, _lib.DIAG_FLOATS, device=dev)
-    L = _lib.lib()
-    with torch.cuda.device(dev):
-        nb = ctypes.c_size_t()
-        _lib.check(L.rgfm_guidance_diag_workspace_bytes(B, N, dx, dy, ctypes.byref(nb)))
-        ws = _sampler_ws.get(nb.value, dev)
-        _lib.check(L.rgfm_guidance_diag(_ptr(x.contiguous()), _ptr(y.contiguous()), _ptr(vx.contiguous()),
-                                        _ptr(vy.contiguous()), _ptr(mc_x1.contiguous()), _ptr(mc_y1.contiguous()),
-                                        _ptr(mc_ratios.contiguous()), B, N, dx, dy, float(t), _ptr(out), _ptr(ws),
-                                        nb.value, _stream(dev)))
+    _block(dev, "rgfm_guidance_diag_workspace_bytes", (B, N, dx, dy), "rgfm_guidance_diag", x, y, vx, vy, mc_x1, mc_y1,
+           mc_ratios, B, N, dx, dy, float(t), _ptr(out))
     return out
 
 
@@ -1381,14 +1372,8 @@ def guidance_diag_cond(s, v, mc_set, ratios, t):
     _require_hip(s, v, mc_set, ratios)
     B, N, dev = s.shape[0], mc_set.shape[0], s.device
     out = torch.empty(B, _lib.DIAG_FLOATS, device=dev)
-    L = _lib.lib()
-    with torch.cuda.device(dev):
-        nb = ctypes.c_size_t()
-        _lib.check(L.rgfm_guidance_diag_workspace_bytes(B, N, s[0].numel(), 0, ctypes.byref(nb)))
-        ws = _sampler_ws.get(nb.value, dev)
-        _lib.check(L.rgfm_guidance_diag_cond(_ptr(s.contiguous()), _ptr(v.contiguous()), _ptr(mc_set.contiguous()),
-                                             _ptr(ratios.contiguous()), B, N, s[0].numel(), float(t), _ptr(out), _ptr(ws),
-                                             nb.value, _stream(dev)))
+    _block(dev, "rgfm_guidance_diag_workspace_bytes", (B, N, s[0].numel(), 0), "rgfm_guidance_diag_cond", s, v, mc_set,
+           ratios, B, N, s[0].numel(), float(t), _ptr(out))
     return out
 
 
@@ -1421,9 +1406,9 @@ def sample_cond(model, s, mc_set, ratios, num_steps, gamma, step_begin=0, step_e
     def run():
         with torch.cuda.device(dev):
             h = eng.handle(dev)
-            _run_loop("rgfm_sample_cond_ode", "rgfm_sample_cond_ode_workspace_bytes", (h, B, N),
+            _run_loop(_COND, (h, B, N),
                       (h, _ptr(s), _ptr(mc_set), _ptr(ratios), N, B, int(num_steps), float(gamma)),
-                      (step_begin, step_end), sid, dev, diag=diag, **({} if strength is None else {"strength": strength}))
+                      (step_begin, step_end), sid, dev, diag=diag, strength=strength)
         return s
     return _range_guarded(dev, [s], run, [eng])
 
@@ -1462,9 +1447,9 @@ def sample_cond_grad(model, ratio_estimator, s, ctx, given, num_steps, gamma, st
     def run():
         with torch.cuda.device(dev):
             h, hr = eng.handle(dev), re.handle(dev)
-            _run_loop("rgfm_sample_cond_grad_ode", "rgfm_sample_cond_grad_ode_workspace_bytes", (h, hr, gi, B),
+            _run_loop(_COND_GRAD, (h, hr, gi, B),
                       (h, hr, _ptr(s), _ptr(ctx), gi, B, int(num_steps), float(gamma)), (step_begin, step_end), sid, dev,
-                      diag=diag, **({} if strength is None else {"strength": strength}))
+                      diag=diag, strength=strength)
         return s
     return _range_guarded(dev, [s], run, [eng])
 
@@ -1474,15 +1459,9 @@ def guidance_apply_cond(s, v, mc_set, ratios, t, gamma, want_weights=False):
     _require_hip(s, v, mc_set, ratios)
     B, N, dev = s.shape[0], mc_set.shape[0], s.device
     w = torch.empty(B, N, device=dev) if want_weights else None
-    L = _lib.lib()
-    with torch.cuda.device(dev):
-        nb = ctypes.c_size_t()
-        _lib.check(L.rgfm_guidance_workspace_bytes(B, N, ctypes.byref(nb)))
-        ws = _sampler_ws.get(nb.value, dev)
-        fn, g = _block_gamma(gamma, B, dev, "rgfm_guidance_apply_cond")
-        _lib.check(getattr(L, fn)(_ptr(s.contiguous()), _ptr(v), _ptr(mc_set.contiguous()),
-                                  _ptr(ratios.contiguous()), B, N, s[0].numel(), float(t), g,
-                                  _ptr(w), _ptr(ws), nb.value, _stream(dev)))
+    fn, g = _block_gamma(gamma, B, dev, "rgfm_guidance_apply_cond")
+    _block(dev, "rgfm_guidance_workspace_bytes", (B, N), fn, s, _ptr(v), mc_set, ratios, B, N, s[0].numel(),
+           float(t), g, _ptr(w))
     return w
 
 

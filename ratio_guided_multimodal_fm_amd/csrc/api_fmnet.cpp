@@ -189,7 +189,7 @@ unsigned* fm_carve(Bump& b, rgfm_fmnet* h, int B, size_t* mark) {
 }
 
 struct FmPairWs {
-  float *vx, *vy, *logp;
+  float *vx, *vy, *scratch;
   unsigned *cnt_x, *cnt_y;
   size_t mark_x, mark_y;
 };
@@ -197,7 +197,7 @@ FmPairWs fm_carve_pair(Bump& b, rgfm_fmnet* hx, rgfm_fmnet* hy, int batch, int n
   FmPairWs w{};
   w.vx = b.f((size_t)batch * FM_S * FM_S);
   w.vy = b.f((size_t)batch * FM_S * FM_S);
-  w.logp = b.f(guid_scratch_bytes(batch, n_mc) / sizeof(float));
+  w.scratch = b.f(guid_scratch_bytes(batch, n_mc) / sizeof(float));
   w.cnt_x = b.u(batch), w.cnt_y = b.u(batch);
   w.mark_x = b.off, fm_carve_eval(b, hx, batch);  // the two nets run concurrently: disjoint regions
   w.mark_y = b.off, fm_carve_eval(b, hy, batch);
@@ -341,14 +341,13 @@ extern "C" int rgfm_fmnet_sample_single(rgfm_fmnet* h, float* x_inout, int batch
   if (int rc = check_workspace(b, ws_bytes)) return rc;
   if (ns == 0) return RGFM_OK;
   HIP_TRY(hipMemsetAsync(cnt, 0, (size_t)batch * sizeof(unsigned), (hipStream_t)stream));
-  for (int i = 0; i < ns; ++i) {
-    Stage st[2];
-    step_stages(SOLVER_EULER, num_steps, step_begin, i, st);
+  auto stage = [&](const Stage& g) -> int {
     b.off = mark;
-    FmRun r{h, batch, &b, (hipStream_t)stream, false, nullptr, 1, num_steps, step_begin + st[0].row};
+    FmRun r{h, batch, &b, (hipStream_t)stream, false, nullptr, 1, num_steps, step_begin + g.row};
     r.fin_counter = cnt;
-    if (int rc = r.run(x_inout, nullptr, x_inout, st[0].dts)) return rc;
-  }
+    return r.run(x_inout, nullptr, x_inout, g.dts);
+  };
+  if (int rc = for_each_stage(SOLVER_EULER, num_steps, step_begin, ns, stage)) return rc;
   HIP_TRY(hipGetLastError());
   return RGFM_OK;
 }
@@ -364,24 +363,21 @@ extern "C" int rgfm_fmnet_sample_pair_workspace_bytes(const rgfm_fmnet* hx, cons
 
 namespace {
 int fm_pair_loop(rgfm_fmnet* hx, rgfm_fmnet* hy, float* x_inout, float* y_inout, const float* mc_x1, const float* mc_y1,
-                 const float* mc_ratios, int n_mc, int batch, int num_steps, double gamma, int step_begin, int step_end,
-                 void* ws, size_t ws_bytes, rgfm_stream_t stream, float* diag_out, size_t diag_records) {
-  refresh_modes();
+                 const float* mc_ratios, int n_mc, const LoopCall& c) {
+  const int batch = c.batch, num_steps = c.num_steps, step_begin = c.step_begin;
   int ns = 0;
-  if (int rc = check_loop(SOLVER_EULER, hx && hy && x_inout && y_inout && ws, batch, num_steps, step_begin, step_end, &ns,
-                          false))
-    return rc;
-  if (n_mc < 0 || (n_mc > 0 && (!mc_x1 || !mc_y1 || !mc_ratios))) return fail(RGFM_EINVAL, "MC set missing");
   DiagSink sink;
-  if (int rc = sink.check(diag_out, diag_records, batch, ns, SOLVER_EULER)) return rc;
+  const bool time_table = false;  // (the time is embedded per evaluation: no cap on the steps of a call)
+  if (int rc = open_loop(c, hx && hy && x_inout && y_inout, &ns, &sink, time_table)) return rc;
+  if (n_mc < 0 || (n_mc > 0 && (!mc_x1 || !mc_y1 || !mc_ratios))) return fail(RGFM_EINVAL, "MC set missing");
   const int d = FM_S * FM_S;
-  Bump b(ws, ws_bytes);
+  Bump b(c.ws, c.ws_bytes);
   FmPairWs w = fm_carve_pair(b, hx, hy, batch, n_mc);
   // (the nets' evaluations rewind the Bump to their marks: the sink's scratch lies behind every region)
   if (sink.on()) sink.carve(b, d, d);
-  if (int rc = check_workspace(b, ws_bytes)) return rc;
+  if (int rc = check_workspace(b, c.ws_bytes)) return rc;
   if (ns == 0) return RGFM_OK;
-  hipStream_t s = (hipStream_t)stream;
+  hipStream_t s = (hipStream_t)c.stream;
   if (sink.on())
     if (int rc = sink.begin(s, d, d)) return rc;
   HIP_TRY(hipMemsetAsync(w.cnt_x, 0, (size_t)batch * sizeof(unsigned), s));
@@ -395,9 +391,11 @@ int fm_pair_loop(rgfm_fmnet* hx, rgfm_fmnet* hy, float* x_inout, float* y_inout,
       return r.run(in, v_out, state, dt);
     };
   };
-  return pair_loop(net(hx, w.cnt_x, w.mark_x), net(hy, w.cnt_y, w.mark_y), x_inout, y_inout, mc_x1, mc_y1, mc_ratios, n_mc,
-                   batch, num_steps, gamma, step_begin, ns, d, d, w.vx, w.vy, w.logp, s, nullptr, SOLVER_EULER, nullptr, nullptr,
-                   sink.on() ? &sink : nullptr);
+  // (no gstate: never graph replay; no mid states: Euler only)
+  return pair_loop(net(hx, w.cnt_x, w.mark_x), net(hy, w.cnt_y, w.mark_y),
+                   {.x = x_inout, .y = y_inout, .mc_x1 = mc_x1, .mc_y1 = mc_y1, .mc_ratios = mc_ratios, .n_mc = n_mc, .dx = d,
+                    .dy = d, .vx = w.vx, .vy = w.vy, .scratch = w.scratch},
+                   c, ns, sink);
 }
 }  // namespace
 
@@ -405,8 +403,9 @@ extern "C" int rgfm_fmnet_sample_pair(rgfm_fmnet* hx, rgfm_fmnet* hy, float* x_i
                                       const float* mc_x1, const float* mc_y1, const float* mc_ratios, int n_mc,
                                       int batch, int num_steps, double gamma, int step_begin, int step_end, void* ws,
                                       size_t ws_bytes, rgfm_stream_t stream) {
-  return fm_pair_loop(hx, hy, x_inout, y_inout, mc_x1, mc_y1, mc_ratios, n_mc, batch, num_steps, gamma, step_begin, step_end, ws,
-                      ws_bytes, stream, nullptr, 0);
+  return fm_pair_loop(hx, hy, x_inout, y_inout, mc_x1, mc_y1, mc_ratios, n_mc,
+                      {.batch = batch, .num_steps = num_steps, .step_begin = step_begin, .step_end = step_end,
+                       .strength = gamma, .ws = ws, .ws_bytes = ws_bytes, .stream = stream});
 }
 // ... with the diagnostics sink (include/rgfm.h, "Guidance diagnostics")
 extern "C" int rgfm_fmnet_sample_pair_diag_workspace_bytes(const rgfm_fmnet* hx, const rgfm_fmnet* hy, int batch, int n_mc,
@@ -419,6 +418,8 @@ extern "C" int rgfm_fmnet_sample_pair_diag(rgfm_fmnet* hx, rgfm_fmnet* hy, float
                                            const float* mc_y1, const float* mc_ratios, int n_mc, int batch, int num_steps,
                                            double gamma, int step_begin, int step_end, float* diag_out, size_t diag_records,
                                            void* ws, size_t ws_bytes, rgfm_stream_t stream) {
-  return fm_pair_loop(hx, hy, x_inout, y_inout, mc_x1, mc_y1, mc_ratios, n_mc, batch, num_steps, gamma, step_begin, step_end, ws,
-                      ws_bytes, stream, diag_out, diag_records);
+  return fm_pair_loop(hx, hy, x_inout, y_inout, mc_x1, mc_y1, mc_ratios, n_mc,
+                      {.batch = batch, .num_steps = num_steps, .step_begin = step_begin, .step_end = step_end,
+                       .strength = gamma, .diag_out = diag_out, .diag_records = diag_records, .ws = ws, .ws_bytes = ws_bytes,
+                       .stream = stream});
 }

@@ -794,35 +794,30 @@ void euler_grad_update(float* x, const float* v, const float* g, int batch, size
   else launch_euler_grad(x, v, g, (size_t)batch * dim, (float)gamma.gamma, dt, s, base);
 }
 
-int pair_grad_loop(rgfm_unet* hx, rgfm_unet* hy, rgfm_ratio* hr, float* x_inout, float* y_inout, int batch, int num_steps,
-                   const Strength& strength, int step_begin, int step_end, int solver, void* ws, size_t ws_bytes, rgfm_stream_t stream,
-                   float* diag_out = nullptr, size_t diag_records = 0) {
-  refresh_modes();
+int pair_grad_loop(rgfm_unet* hx, rgfm_unet* hy, rgfm_ratio* hr, float* x_inout, float* y_inout, const LoopCall& c) {
+  const int batch = c.batch;
   int ns = 0;
-  if (int rc = check_loop(solver, hx && hy && hr && x_inout && y_inout && ws, batch, num_steps, step_begin, step_end, &ns))
-    return rc;
-  if (int rc = check_grad_pair(hx, hy, hr)) return rc;
   DiagSink sink;  // (the gradient loops need no scratch: v and grad log r are both in the workspace already)
-  if (int rc = sink.check(diag_out, diag_records, batch, ns, solver)) return rc;
-  if (int rc = strength.check(loop_stages(solver, ns))) return rc;
-  Bump b(ws, ws_bytes);
-  PairGradWs w{{hx, batch, solver}, {hy, batch, solver}};
+  if (int rc = open_loop(c, hx && hy && hr && x_inout && y_inout, &ns, &sink)) return rc;
+  if (int rc = check_grad_pair(hx, hy, hr)) return rc;
+  Bump b(c.ws, c.ws_bytes);
+  PairGradWs w{{hx, batch, c.solver}, {hy, batch, c.solver}};
   carve_pair_grad(b, w, hr);
-  if (int rc = check_workspace(b, ws_bytes)) return rc;
+  if (int rc = check_workspace(b, c.ws_bytes)) return rc;
   if (ns == 0) return RGFM_OK;
   DevState* ds = cur_dev();
   if (!ds) return fail(RGFM_EINVAL, "no handle has been created on the current device");
-  hipStream_t s = (hipStream_t)stream;
+  hipStream_t s = (hipStream_t)c.stream;
   const size_t dx = w.cx.image_floats(), dy = w.cy.image_floats();
-  if (int rc = w.cx.begin(s, num_steps, step_begin, ns)) return rc;
-  if (int rc = w.cy.begin(s, num_steps, step_begin, ns)) return rc;
+  if (int rc = w.cx.begin(s, c.num_steps, c.step_begin, ns)) return rc;
+  if (int rc = w.cy.begin(s, c.num_steps, c.step_begin, ns)) return rc;
   if (sink.on())
     if (int rc = sink.begin(s, 0, 0)) return rc;
   const bool overlap = g_modes.overlap;
   // one stage: (xout, yout) = (xb, yb) + (v(in, row's t) + gamma grad log r(xin, yin)) dts; xb / yb null: in place
   // A stage whose scale is 0 runs unguided -- both nets with the fused Euler epilogue on the two streams, as pair_loop's
   // unguided stage, and no ratio pass; its diagnostics record stays zero.
-  auto stage = [&](const Stage& g, const StageStrength& gamma, bool guided) -> int {
+  auto stage = [&](const Stage& g) -> int {
     float *xin = g.reads_mid ? w.cx.mid : x_inout, *yin = g.reads_mid ? w.cy.mid : y_inout;
     float *xout = g.writes_mid ? w.cx.mid : x_inout, *yout = g.writes_mid ? w.cy.mid : y_inout;
     const float *xb = g.writes_mid ? x_inout : nullptr, *yb = g.writes_mid ? y_inout : nullptr;
@@ -831,8 +826,7 @@ int pair_grad_loop(rgfm_unet* hx, rgfm_unet* hy, rgfm_ratio* hr, float* x_inout,
       HIP_TRY(hipEventRecord(ds->fork, s));
       HIP_TRY(hipStreamWaitEvent(ds->side, ds->fork, 0));
     }
-    if (!guided) {
-      if (sink.on()) (void)sink.next();
+    if (c.strength.off(g.row)) {
       if (int rc = w.cy.eval(g.row, sy, yin, nullptr, yout, y_inout, g.dts)) return rc;
       if (overlap) HIP_TRY(hipEventRecord(ds->join, ds->side));
       if (int rc = w.cx.eval(g.row, s, xin, nullptr, xout, x_inout, g.dts)) return rc;
@@ -850,23 +844,18 @@ int pair_grad_loop(rgfm_unet* hx, rgfm_unet* hy, rgfm_ratio* hr, float* x_inout,
     }
     if (overlap) HIP_TRY(hipStreamWaitEvent(s, ds->join, 0));
     if (sink.on()) {  // |v| and |grad log r| (before gamma) per row and modality
-      float* rec = sink.next();
+      float* rec = sink.at(g.row).rec;
       launch_diag_rownorm(w.vx, batch, (int)dx, rec, RGFM_DIAG_V_NORM_X, s);
       launch_diag_rownorm(w.vy, batch, (int)dy, rec, RGFM_DIAG_V_NORM_Y, s);
       launch_diag_rownorm(w.gx, batch, (int)dx, rec, RGFM_DIAG_G_NORM_X, s);
       launch_diag_rownorm(w.gy, batch, (int)dy, rec, RGFM_DIAG_G_NORM_Y, s);
     }
+    const StageStrength gamma = c.strength.stage(g.row);
     euler_grad_update(xout, w.vx, w.gx, batch, dx, gamma, g.dts, s, xb);
     euler_grad_update(yout, w.vy, w.gy, batch, dy, gamma, g.dts, s, yb);
     return RGFM_OK;
   };
-  int stage_no = 0;  // (the index into the strength's per-stage scale)
-  for (int i = 0; i < ns; ++i) {
-    Stage st[2];
-    const int n = w.cx.stages(i, st);
-    for (int k = 0; k < n; ++k, ++stage_no)
-      if (int rc = stage(st[k], strength.stage(stage_no), !strength.off(stage_no))) return rc;
-  }
+  if (int rc = for_each_stage(c.solver, c.num_steps, c.step_begin, ns, stage)) return rc;
   HIP_TRY(hipGetLastError());
   return RGFM_OK;
 }
@@ -884,13 +873,16 @@ extern "C" int rgfm_sample_pair_grad_ode_workspace_bytes(const rgfm_unet* hx, co
 extern "C" int rgfm_sample_pair_grad(rgfm_unet* hx, rgfm_unet* hy, rgfm_ratio* hr, float* x_inout, float* y_inout, int batch,
                                      int num_steps, double gamma, int step_begin, int step_end, void* ws, size_t ws_bytes,
                                      rgfm_stream_t stream) {
-  return pair_grad_loop(hx, hy, hr, x_inout, y_inout, batch, num_steps, gamma, step_begin, step_end, SOLVER_EULER, ws, ws_bytes,
-                        stream);
+  return pair_grad_loop(hx, hy, hr, x_inout, y_inout,
+                        {.batch = batch, .num_steps = num_steps, .step_begin = step_begin, .step_end = step_end,
+                         .strength = gamma, .ws = ws, .ws_bytes = ws_bytes, .stream = stream});
 }
 extern "C" int rgfm_sample_pair_grad_ode(rgfm_unet* hx, rgfm_unet* hy, rgfm_ratio* hr, float* x_inout, float* y_inout,
                                          int batch, int num_steps, double gamma, int step_begin, int step_end, int solver,
                                          void* ws, size_t ws_bytes, rgfm_stream_t stream) {
-  return pair_grad_loop(hx, hy, hr, x_inout, y_inout, batch, num_steps, gamma, step_begin, step_end, solver, ws, ws_bytes, stream);
+  return pair_grad_loop(hx, hy, hr, x_inout, y_inout,
+                        {.batch = batch, .num_steps = num_steps, .step_begin = step_begin, .step_end = step_end,
+                         .solver = solver, .strength = gamma, .ws = ws, .ws_bytes = ws_bytes, .stream = stream});
 }
 
 // One net with gradient log-ratio guidance, the other side observed: s <- s + (v(s, t) + gamma dlogr/ds) dt, every step
@@ -927,54 +919,41 @@ int cond_grad_bytes(const rgfm_unet* h, const rgfm_ratio* hr, int given, int bat
   return RGFM_OK;
 }
 
-int cond_grad_loop(rgfm_unet* h, rgfm_ratio* hr, float* s_inout, const float* ctx, int given, int batch, int num_steps,
-                   const Strength& strength, int step_begin, int step_end, int solver, void* ws, size_t ws_bytes, rgfm_stream_t stream,
-                   float* diag_out = nullptr, size_t diag_records = 0) {
-  refresh_modes();
+int cond_grad_loop(rgfm_unet* h, rgfm_ratio* hr, float* s_inout, const float* ctx, int given, const LoopCall& c) {
+  const int batch = c.batch;
   int ns = 0;
-  if (int rc = check_loop(solver, h && hr && s_inout && ctx && ws, batch, num_steps, step_begin, step_end, &ns))
-    return rc;
-  int rc = check_given(given);
-  if (rc || (rc = check_grad_side(h, hr, given))) return rc;
   DiagSink sink;
-  if ((rc = sink.check(diag_out, diag_records, batch, ns, solver))) return rc;
-  if ((rc = strength.check(loop_stages(solver, ns)))) return rc;
-  Bump b(ws, ws_bytes);
-  CondGradWs w = carve_cond_grad(b, h, hr, given, batch, solver);
-  if ((rc = check_workspace(b, ws_bytes))) return rc;
+  int rc = open_loop(c, h && hr && s_inout && ctx, &ns, &sink);
+  if (rc || (rc = check_given(given)) || (rc = check_grad_side(h, hr, given))) return rc;
+  Bump b(c.ws, c.ws_bytes);
+  CondGradWs w = carve_cond_grad(b, h, hr, given, batch, c.solver);
+  if ((rc = check_workspace(b, c.ws_bytes))) return rc;
   if (ns == 0) return RGFM_OK;
-  hipStream_t s = (hipStream_t)stream;
+  hipStream_t s = (hipStream_t)c.stream;
   const size_t d = w.c.image_floats();
-  if ((rc = w.c.begin(s, num_steps, step_begin, ns))) return rc;
+  if ((rc = w.c.begin(s, c.num_steps, c.step_begin, ns))) return rc;
   if (sink.on() && (rc = sink.begin(s, 0, 0))) return rc;
-  int stage_no = 0;  // (the index into the strength's per-stage scale)
-  for (int i = 0; i < ns; ++i) {
-    Stage st[2];
-    const int n = w.c.stages(i, st);
-    for (int k = 0; k < n; ++k, ++stage_no) {
-      // one stage: out = base + (v(in, row's t) + gamma grad log r(in)) dts; base null: in place on out
-      const Stage& g = st[k];
-      float *in = g.reads_mid ? w.c.mid : s_inout, *out = g.writes_mid ? w.c.mid : s_inout;
-      if (strength.off(stage_no)) {  // scale 0: the unguided stage (NetChain::step's evaluation), no ratio pass, a zero record
-        if (sink.on()) (void)sink.next();
-        if ((rc = w.c.eval(g.row, s, in, nullptr, out, s_inout, g.dts))) return rc;
-        continue;
-      }
-      if ((rc = w.c.eval(g.row, s, in, w.v, nullptr, nullptr, 0.f))) return rc;
-      {
-        b.off = w.c.mark;
-        RatioPass r{hr, batch, &b, s, false, h->range_flag};
-        ModeScope ratio_mode(h->conv_mode);  // (the estimator's convs follow the target net's handle)
-        r.grad_cond(ctx, given, in, w.g, nullptr);
-      }
-      if (sink.on()) {  // (one-sided: the target's norms in the x entries, whichever side of the estimator it is)
-        float* rec = sink.next();
-        launch_diag_rownorm(w.v, batch, (int)d, rec, RGFM_DIAG_V_NORM_X, s);
-        launch_diag_rownorm(w.g, batch, (int)d, rec, RGFM_DIAG_G_NORM_X, s);
-      }
-      euler_grad_update(out, w.v, w.g, batch, d, strength.stage(stage_no), g.dts, s, g.writes_mid ? s_inout : nullptr);
+  // one stage: out = base + (v(in, row's t) + gamma grad log r(in)) dts; base null: in place on out
+  auto stage = [&](const Stage& g) -> int {
+    float *in = g.reads_mid ? w.c.mid : s_inout, *out = g.writes_mid ? w.c.mid : s_inout;
+    // scale 0: the unguided stage (NetChain::step's evaluation), no ratio pass, a zero record
+    if (c.strength.off(g.row)) return w.c.eval(g.row, s, in, nullptr, out, s_inout, g.dts);
+    if (int rc = w.c.eval(g.row, s, in, w.v, nullptr, nullptr, 0.f)) return rc;
+    {
+      b.off = w.c.mark;
+      RatioPass r{hr, batch, &b, s, false, h->range_flag};
+      ModeScope ratio_mode(h->conv_mode);  // (the estimator's convs follow the target net's handle)
+      r.grad_cond(ctx, given, in, w.g, nullptr);
     }
-  }
+    if (sink.on()) {  // (one-sided: the target's norms in the x entries, whichever side of the estimator it is)
+      float* rec = sink.at(g.row).rec;
+      launch_diag_rownorm(w.v, batch, (int)d, rec, RGFM_DIAG_V_NORM_X, s);
+      launch_diag_rownorm(w.g, batch, (int)d, rec, RGFM_DIAG_G_NORM_X, s);
+    }
+    euler_grad_update(out, w.v, w.g, batch, d, c.strength.stage(g.row), g.dts, s, g.writes_mid ? s_inout : nullptr);
+    return RGFM_OK;
+  };
+  if ((rc = for_each_stage(c.solver, c.num_steps, c.step_begin, ns, stage))) return rc;
   HIP_TRY(hipGetLastError());
   return RGFM_OK;
 }
@@ -991,12 +970,16 @@ extern "C" int rgfm_sample_cond_grad_ode_workspace_bytes(const rgfm_unet* h, con
 extern "C" int rgfm_sample_cond_grad(rgfm_unet* h, rgfm_ratio* hr, float* s_inout, const float* ctx, int given, int batch,
                                      int num_steps, double gamma, int step_begin, int step_end, void* ws, size_t ws_bytes,
                                      rgfm_stream_t stream) {
-  return cond_grad_loop(h, hr, s_inout, ctx, given, batch, num_steps, gamma, step_begin, step_end, SOLVER_EULER, ws, ws_bytes, stream);
+  return cond_grad_loop(h, hr, s_inout, ctx, given,
+                        {.batch = batch, .num_steps = num_steps, .step_begin = step_begin, .step_end = step_end,
+                         .strength = gamma, .ws = ws, .ws_bytes = ws_bytes, .stream = stream});
 }
 extern "C" int rgfm_sample_cond_grad_ode(rgfm_unet* h, rgfm_ratio* hr, float* s_inout, const float* ctx, int given, int batch,
                                          int num_steps, double gamma, int step_begin, int step_end, int solver, void* ws,
                                          size_t ws_bytes, rgfm_stream_t stream) {
-  return cond_grad_loop(h, hr, s_inout, ctx, given, batch, num_steps, gamma, step_begin, step_end, solver, ws, ws_bytes, stream);
+  return cond_grad_loop(h, hr, s_inout, ctx, given,
+                        {.batch = batch, .num_steps = num_steps, .step_begin = step_begin, .step_end = step_end,
+                         .solver = solver, .strength = gamma, .ws = ws, .ws_bytes = ws_bytes, .stream = stream});
 }
 
 // ---- the gradient-guided loops with the diagnostics sink (include/rgfm.h, "Guidance diagnostics"): no extra workspace
@@ -1008,8 +991,10 @@ extern "C" int rgfm_sample_pair_grad_diag(rgfm_unet* hx, rgfm_unet* hy, rgfm_rat
                                           int batch, int num_steps, double gamma, int step_begin, int step_end, int solver,
                                           float* diag_out, size_t diag_records, void* ws, size_t ws_bytes,
                                           rgfm_stream_t stream) {
-  return pair_grad_loop(hx, hy, hr, x_inout, y_inout, batch, num_steps, gamma, step_begin, step_end, solver, ws, ws_bytes, stream,
-                        diag_out, diag_records);
+  return pair_grad_loop(hx, hy, hr, x_inout, y_inout,
+                        {.batch = batch, .num_steps = num_steps, .step_begin = step_begin, .step_end = step_end,
+                         .solver = solver, .strength = gamma, .diag_out = diag_out, .diag_records = diag_records, .ws = ws,
+                         .ws_bytes = ws_bytes, .stream = stream});
 }
 extern "C" int rgfm_sample_cond_grad_diag_workspace_bytes(const rgfm_unet* h, const rgfm_ratio* hr, int given, int batch,
                                                           int solver, size_t* bytes) {
@@ -1019,8 +1004,10 @@ extern "C" int rgfm_sample_cond_grad_diag(rgfm_unet* h, rgfm_ratio* hr, float* s
                                           int num_steps, double gamma, int step_begin, int step_end, int solver,
                                           float* diag_out, size_t diag_records, void* ws, size_t ws_bytes,
                                           rgfm_stream_t stream) {
-  return cond_grad_loop(h, hr, s_inout, ctx, given, batch, num_steps, gamma, step_begin, step_end, solver, ws, ws_bytes, stream,
-                        diag_out, diag_records);
+  return cond_grad_loop(h, hr, s_inout, ctx, given,
+                        {.batch = batch, .num_steps = num_steps, .step_begin = step_begin, .step_end = step_end,
+                         .solver = solver, .strength = gamma, .diag_out = diag_out, .diag_records = diag_records, .ws = ws,
+                         .ws_bytes = ws_bytes, .stream = stream});
 }
 
 // ---- guidance strength as data (include/rgfm.h, "Guidance strength per sample and per stage"): each loop is its *_diag
@@ -1029,13 +1016,17 @@ extern "C" int rgfm_sample_pair_grad_gs(rgfm_unet* hx, rgfm_unet* hy, rgfm_ratio
                                         int num_steps, double gamma, const float* gamma_rows, const double* stage_scale,
                                         int n_stage_scale, int step_begin, int step_end, int solver, float* diag_out,
                                         size_t diag_records, void* ws, size_t ws_bytes, rgfm_stream_t stream) {
-  return pair_grad_loop(hx, hy, hr, x_inout, y_inout, batch, num_steps, Strength(gamma, gamma_rows, stage_scale, n_stage_scale),
-                        step_begin, step_end, solver, ws, ws_bytes, stream, diag_out, diag_records);
+  return pair_grad_loop(hx, hy, hr, x_inout, y_inout,
+                        {.batch = batch, .num_steps = num_steps, .step_begin = step_begin, .step_end = step_end,
+                         .solver = solver, .strength = Strength(gamma, gamma_rows, stage_scale, n_stage_scale),
+                         .diag_out = diag_out, .diag_records = diag_records, .ws = ws, .ws_bytes = ws_bytes, .stream = stream});
 }
 extern "C" int rgfm_sample_cond_grad_gs(rgfm_unet* h, rgfm_ratio* hr, float* s_inout, const float* ctx, int given, int batch,
                                         int num_steps, double gamma, const float* gamma_rows, const double* stage_scale,
                                         int n_stage_scale, int step_begin, int step_end, int solver, float* diag_out,
                                         size_t diag_records, void* ws, size_t ws_bytes, rgfm_stream_t stream) {
-  return cond_grad_loop(h, hr, s_inout, ctx, given, batch, num_steps, Strength(gamma, gamma_rows, stage_scale, n_stage_scale),
-                        step_begin, step_end, solver, ws, ws_bytes, stream, diag_out, diag_records);
+  return cond_grad_loop(h, hr, s_inout, ctx, given,
+                        {.batch = batch, .num_steps = num_steps, .step_begin = step_begin, .step_end = step_end,
+                         .solver = solver, .strength = Strength(gamma, gamma_rows, stage_scale, n_stage_scale),
+                         .diag_out = diag_out, .diag_records = diag_records, .ws = ws, .ws_bytes = ws_bytes, .stream = stream});
 }

@@ -4,7 +4,8 @@
 // ================================================================== samplers
 // Every loop below is shared by its Euler entry point (the `solver` = RGFM_SOLVER_EULER case) and its *_ode twin.  A loop
 // is: check_loop, its carve over the caller's workspace (the same function, run dry, is its *_workspace_bytes), a
-// NetChain per U-Net, and the stages of each step from step_stages (sampler_host.h).
+// NetChain per U-Net, and the stages of the call from for_each_stage (sampler_stages.h).  A guided loop takes its own
+// operands and the call's LoopCall record, which its extern "C" wrapper fills by field name.
 namespace {
 
 // ---- carves: each loop's buffers, in the order they lie in its workspace
@@ -28,14 +29,14 @@ CondWs carve_cond(Bump& b, rgfm_unet* h, int batch, int n_mc, int solver) {
 
 struct PairWs {
   NetChain cx, cy;
-  float *vx, *vy, *logp, *gstate;
+  float *vx, *vy, *scratch, *gstate;
 };
-void carve_pair(Bump& b, PairWs& w, int n_mc, int pairing = PAIRING_PAIRED) {
+void carve_pair(Bump& b, PairWs& w, int n_mc, int pairing) {
   const int batch = w.cx.batch;
   w.cx.carve(b), w.cy.carve(b);
   w.vx = b.f((size_t)batch * w.cx.image_floats());
   w.vy = b.f((size_t)batch * w.cy.image_floats());
-  w.logp = b.f(guid_scratch_bytes(batch, n_mc, pairing) / sizeof(float));
+  w.scratch = b.f(guid_scratch_bytes(batch, n_mc, pairing) / sizeof(float));
   w.gstate = b.f(64 + (size_t)TABLE_ROWS * 4);  // step counter + per-step guidance scalars (graph replay)
   w.cx.carve_eval(), w.cy.carve_eval();         // the two nets run concurrently: disjoint regions
 }
@@ -182,14 +183,15 @@ int guidance_block(const float* x, const float* y, float* vx, float* vy, const f
   if (rc) return rc;
   if (need > ws_bytes) return fail(RGFM_ENOMEM, "workspace too small: %zu < %zu", ws_bytes, need);
   if ((rc = ensure_init())) return rc;
-  rc = guidance_launch(x, y, vx, vy, mc_x1, mc_y1, mc_ratios, batch, n_mc, dim_x, dim_y, t, gamma, (float*)ws,
-                       weights_out, nullptr, nullptr, 0.f, (hipStream_t)stream);
+  rc = guidance_launch({.x = x, .y = y, .vx = vx, .vy = vy, .mx = mc_x1, .my = mc_y1, .r = mc_ratios, .B = batch, .N = n_mc,
+                        .dx = dim_x, .dy = dim_y, .t = t, .strength = gamma, .scratch = (float*)ws,
+                        .weights_out = weights_out, .stream = (hipStream_t)stream});
   if (rc) return rc;
   HIP_TRY(hipGetLastError());
   return RGFM_OK;
 }
 
-// The one-sided block: the paired block with dy = 0 and a ratio row per sample (guidance_launch).
+// The one-sided block: the paired block with dy = 0 and a ratio row per sample (GuidanceCall).
 int guidance_block_cond(const float* s, float* v, const float* mc_set, const float* ratios, int batch, int n_mc, int dim,
                         double t, const StageStrength& gamma, float* weights_out, void* ws, size_t ws_bytes,
                         rgfm_stream_t stream) {
@@ -200,8 +202,9 @@ int guidance_block_cond(const float* s, float* v, const float* mc_set, const flo
   if (rc) return rc;
   if (need > ws_bytes) return fail(RGFM_ENOMEM, "workspace too small: %zu < %zu", ws_bytes, need);
   if ((rc = ensure_init())) return rc;
-  rc = guidance_launch(s, nullptr, v, nullptr, mc_set, nullptr, ratios, batch, n_mc, dim, 0, t, gamma, (float*)ws, weights_out,
-                       nullptr, nullptr, 0.f, (hipStream_t)stream, nullptr, nullptr, 0, n_mc);
+  rc = guidance_launch({.x = s, .vx = v, .mx = mc_set, .r = ratios, .ratio_stride = n_mc, .B = batch, .N = n_mc, .dx = dim,
+                        .t = t, .strength = gamma, .scratch = (float*)ws, .weights_out = weights_out,
+                        .stream = (hipStream_t)stream});
   if (rc) return rc;
   HIP_TRY(hipGetLastError());
   return RGFM_OK;
@@ -240,28 +243,25 @@ extern "C" int rgfm_guidance_apply_cond_rows(const float* s, float* v, const flo
 // ---- diagnostics of one evaluation of the block (include/rgfm.h, "Guidance diagnostics")
 // workspace: the block's, then the two scratch velocities of GuidDiag
 namespace {
-int guidance_diag(const float* x, const float* y, const float* vx, const float* vy, const float* mx, const float* my,
-                  const float* r, int batch, int n_mc, int dx, int dy, double t, int ratio_stride, float* diag_out, void* ws,
-                  size_t ws_bytes, rgfm_stream_t stream, int pairing = PAIRING_PAIRED) {
+// `c`: the block's inputs by name (state, MC set, ratios, shape, t, stream, pairing); v is only read
+int guidance_diag(GuidanceCall c, const float* vx, const float* vy, float* diag_out, void* ws, size_t ws_bytes) {
   size_t need = 0;
-  int rc = pairing == PAIRING_CROSS ? rgfm_guidance_cross_workspace_bytes(batch, n_mc, dx, dy, &need)
-                                    : rgfm_guidance_diag_workspace_bytes(batch, n_mc, dx, dy, &need);
+  int rc = c.pairing == PAIRING_CROSS ? rgfm_guidance_cross_workspace_bytes(c.B, c.N, c.dx, c.dy, &need)
+                                      : rgfm_guidance_diag_workspace_bytes(c.B, c.N, c.dx, c.dy, &need);
   if (rc) return rc;
-  if (n_mc > 4096) return fail(RGFM_EINVAL, "n_mc too large (max 4096)");
+  if (c.N > 4096) return fail(RGFM_EINVAL, "n_mc too large (max 4096)");
   if (need > ws_bytes) return fail(RGFM_ENOMEM, "workspace too small: %zu < %zu", ws_bytes, need);
   if ((rc = ensure_init())) return rc;
-  hipStream_t s = (hipStream_t)stream;
   Bump b(ws, ws_bytes);
-  float* scratch = b.f(guid_scratch_bytes(batch, n_mc, pairing) / sizeof(float));
+  c.scratch = b.f(guid_scratch_bytes(c.B, c.N, c.pairing) / sizeof(float));
   DiagSink sink;
-  if ((rc = sink.check(diag_out, (size_t)batch, batch, 1, SOLVER_EULER))) return rc;
-  sink.carve(b, dx, dy);
-  if ((rc = sink.begin(s, dx, dy))) return rc;
-  const GuidDiag gd{sink.next(), sink.gx, sink.gy};
-  // (phase 3 reads v and writes none of the block's outputs: the casts drop a const that is kept)
-  rc = guidance_launch(x, y, const_cast<float*>(vx), const_cast<float*>(vy), mx, my, r, batch, n_mc, dx, dy, t, 0.0, scratch,
-                       nullptr, nullptr, nullptr, 0.f, s, nullptr, nullptr, 3, ratio_stride, nullptr, nullptr, &gd, pairing);
-  if (rc) return rc;
+  if ((rc = sink.check(diag_out, (size_t)c.B, c.B, 1, SOLVER_EULER))) return rc;
+  sink.carve(b, c.dx, c.dy);
+  if ((rc = sink.begin(c.stream, c.dx, c.dy))) return rc;
+  // (WeightsDiag reads v and writes none of the block's outputs: the casts drop a const that is kept)
+  c.vx = const_cast<float*>(vx), c.vy = const_cast<float*>(vy);
+  c.diag = sink.at(0), c.phase = GuidPhase::WeightsDiag;  // (one evaluation, one record)
+  if ((rc = guidance_launch(c))) return rc;
   HIP_TRY(hipGetLastError());
   return RGFM_OK;
 }
@@ -278,14 +278,18 @@ extern "C" int rgfm_guidance_diag(const float* x, const float* y, const float* v
                                   double t, float* diag_out, void* ws, size_t ws_bytes, rgfm_stream_t stream) {
   if (!x || !y || !vx || !vy || !mc_x1 || !mc_y1 || !mc_ratios || !diag_out || !ws) return fail(RGFM_EINVAL, "null argument");
   if (dim_y < 1) return fail(RGFM_EINVAL, "bad argument");
-  return guidance_diag(x, y, vx, vy, mc_x1, mc_y1, mc_ratios, batch, n_mc, dim_x, dim_y, t, 0, diag_out, ws, ws_bytes, stream);
+  return guidance_diag({.x = x, .y = y, .mx = mc_x1, .my = mc_y1, .r = mc_ratios, .B = batch, .N = n_mc, .dx = dim_x, .dy = dim_y,
+                        .t = t, .stream = (hipStream_t)stream},
+                       vx, vy, diag_out, ws, ws_bytes);
 }
 extern "C" int rgfm_guidance_diag_cond(const float* s, const float* v, const float* mc_set, const float* ratios, int batch,
                                        int n_mc, int dim, double t, float* diag_out, void* ws, size_t ws_bytes,
                                        rgfm_stream_t stream) {
   if (!s || !v || !mc_set || !ratios || !diag_out || !ws) return fail(RGFM_EINVAL, "null argument");
-  return guidance_diag(s, nullptr, v, nullptr, mc_set, nullptr, ratios, batch, n_mc, dim, 0, t, n_mc, diag_out, ws, ws_bytes,
-                       stream);
+  const float* no_vy = nullptr;  // (the one-sided block: GuidanceCall)
+  return guidance_diag({.x = s, .mx = mc_set, .r = ratios, .ratio_stride = n_mc, .B = batch, .N = n_mc, .dx = dim, .t = t,
+                        .stream = (hipStream_t)stream},
+                       v, no_vy, diag_out, ws, ws_bytes);
 }
 
 namespace {
@@ -300,51 +304,36 @@ int cond_bytes(const rgfm_unet* h, int batch, int n_mc, int solver, size_t* byte
 }
 
 // One net, guided by the one-sided block: kernel by kernel on the caller's stream (nothing to overlap, no graph).
-int cond_loop(rgfm_unet* h, float* s_inout, const float* mc_set, const float* ratios, int n_mc, int batch, int num_steps,
-              const Strength& strength, int step_begin, int step_end, int solver, void* ws, size_t ws_bytes, rgfm_stream_t stream,
-              float* diag_out = nullptr, size_t diag_records = 0) {
-  refresh_modes();
+int cond_loop(rgfm_unet* h, float* s_inout, const float* mc_set, const float* ratios, int n_mc, const LoopCall& c) {
   int ns = 0;
-  if (int rc = check_loop(solver, h && s_inout && mc_set && ratios && ws, batch, num_steps, step_begin, step_end, &ns))
-    return rc;
   DiagSink sink;
-  if (int rc = sink.check(diag_out, diag_records, batch, ns, solver)) return rc;
-  if (int rc = strength.check(loop_stages(solver, ns))) return rc;
+  if (int rc = open_loop(c, h && s_inout && mc_set && ratios, &ns, &sink)) return rc;
   if (n_mc < 1) return fail(RGFM_EINVAL, "conditional sampling needs an MC set (n_mc >= 1)");
   const int d = h->d.in_channels * h->d.img_size * h->d.img_size;
   if (d % 4) return fail(RGFM_EINVAL, "flattened image sizes must be multiples of 4");
   if (n_mc > 4096) return fail(RGFM_EINVAL, "n_mc too large (max 4096)");
-  Bump b(ws, ws_bytes);
-  CondWs w = carve_cond(b, h, batch, n_mc, solver);
+  Bump b(c.ws, c.ws_bytes);
+  CondWs w = carve_cond(b, h, c.batch, n_mc, c.solver);
   if (sink.on()) sink.carve(b, d, 0);
-  if (int rc = check_workspace(b, ws_bytes)) return rc;
+  if (int rc = check_workspace(b, c.ws_bytes)) return rc;
   if (ns == 0) return RGFM_OK;
-  hipStream_t s = (hipStream_t)stream;
-  if (int rc = w.c.begin(s, num_steps, step_begin, ns)) return rc;
+  hipStream_t s = (hipStream_t)c.stream;
+  if (int rc = w.c.begin(s, c.num_steps, c.step_begin, ns)) return rc;
   if (sink.on())
     if (int rc = sink.begin(s, d, 0)) return rc;
-  int stage_no = 0;  // (the index into the strength's per-stage scale)
-  for (int i = 0; i < ns; ++i) {
-    Stage st[2];
-    const int n = w.c.stages(i, st);
-    for (int k = 0; k < n; ++k, ++stage_no) {
-      // one stage: out = s + F(in, t) dts; guided iff the stage's own t > eps (`t > eps` test of the reference, :124)
-      // and its scale is not 0
-      const Stage& g = st[k];
-      float *in = g.reads_mid ? w.c.mid : s_inout, *out = g.writes_mid ? w.c.mid : s_inout;
-      const bool guided = g.t > 1e-3 && !strength.off(stage_no);
-      GuidDiag gd{};
-      if (sink.on()) gd = {sink.next(), sink.gx, sink.gy};
-      // unguided: the fused Euler epilogue; guided: the raw velocity, and the guidance block moves the state
-      if (int rc = guided ? w.c.eval(g.row, s, in, w.v, nullptr, nullptr, g.dts)
-                          : w.c.eval(g.row, s, in, nullptr, out, s_inout, g.dts))
-        return rc;
-      if (!guided) continue;
-      if (int rc = guidance_launch(in, nullptr, w.v, nullptr, mc_set, nullptr, ratios, batch, n_mc, d, 0, g.t, strength.stage(stage_no), w.scratch,
-                                   nullptr, out, nullptr, g.dts, s, nullptr, nullptr, 0, n_mc, s_inout, nullptr, sink.on() ? &gd : nullptr))
-        return rc;
-    }
-  }
+  // one stage: out = s + F(in, t) dts; guided iff the stage's own t > eps (`t > eps` test of the reference, :124)
+  // and its scale is not 0
+  auto stage = [&](const Stage& g) -> int {
+    float *in = g.reads_mid ? w.c.mid : s_inout, *out = g.writes_mid ? w.c.mid : s_inout;
+    // unguided: the fused Euler epilogue
+    if (g.t <= 1e-3 || c.strength.off(g.row)) return w.c.eval(g.row, s, in, nullptr, out, s_inout, g.dts);
+    // guided: the raw velocity, and the (one-sided) guidance block moves the state
+    if (int rc = w.c.eval(g.row, s, in, w.v, nullptr, nullptr, g.dts)) return rc;
+    return guidance_launch({.x = in, .vx = w.v, .mx = mc_set, .r = ratios, .ratio_stride = n_mc, .B = c.batch, .N = n_mc,
+                            .dx = d, .t = g.t, .strength = c.strength.stage(g.row), .scratch = w.scratch, .xs = out,
+                            .xb = s_inout, .dt = g.dts, .stream = s, .diag = sink.at(g.row)});
+  };
+  if (int rc = for_each_stage(c.solver, c.num_steps, c.step_begin, ns, stage)) return rc;
   HIP_TRY(hipGetLastError());
   return RGFM_OK;
 }
@@ -361,39 +350,35 @@ int pair_bytes(const rgfm_unet* hx, const rgfm_unet* hy, int batch, int n_mc, in
 }
 
 int pair_sample(rgfm_unet* hx, rgfm_unet* hy, float* x_inout, float* y_inout, const float* mc_x1, const float* mc_y1,
-                const float* mc_ratios, int n_mc, int batch, int num_steps, const Strength& strength, int step_begin, int step_end,
-                int solver, void* ws, size_t ws_bytes, rgfm_stream_t stream, float* diag_out = nullptr, size_t diag_records = 0,
-                int pairing = PAIRING_PAIRED) {
-  refresh_modes();
+                const float* mc_ratios, int n_mc, const LoopCall& c) {
   int ns = 0;
-  if (int rc = check_loop(solver, hx && hy && x_inout && y_inout && ws, batch, num_steps, step_begin, step_end, &ns))
-    return rc;
+  DiagSink sink;
+  if (int rc = open_loop(c, hx && hy && x_inout && y_inout, &ns, &sink)) return rc;
   if (n_mc < 0 || (n_mc > 0 && (!mc_x1 || !mc_y1 || !mc_ratios))) return fail(RGFM_EINVAL, "MC set missing");
-  if (pairing == PAIRING_CROSS) {  // (what guidance_launch would refuse at the first guided stage, before anything is enqueued)
+  if (c.pairing == PAIRING_CROSS) {  // (what guidance_launch would refuse at the first guided stage, before anything is enqueued)
     if (n_mc > GUID_CROSS_MAX_N) return fail(RGFM_EINVAL, "cross pairing: n_mc %d too large (max %d)", n_mc, GUID_CROSS_MAX_N);
     for (const rgfm_unet* h : {hx, hy})
       if ((h->d.in_channels * h->d.img_size * h->d.img_size) % 4) return fail(RGFM_EINVAL, "flattened image sizes must be multiples of 4");
   }
-  DiagSink sink;
-  if (int rc = sink.check(diag_out, diag_records, batch, ns, solver)) return rc;
-  if (int rc = strength.check(loop_stages(solver, ns))) return rc;
-  Bump b(ws, ws_bytes);
-  PairWs w{{hx, batch, solver}, {hy, batch, solver}};
-  carve_pair(b, w, n_mc, pairing);
+  Bump b(c.ws, c.ws_bytes);
+  PairWs w{{hx, c.batch, c.solver}, {hy, c.batch, c.solver}};
+  carve_pair(b, w, n_mc, c.pairing);
   if (sink.on()) sink.carve(b, w.cx.image_floats(), w.cy.image_floats());
-  else if (pairing == PAIRING_CROSS)  // (one workspace query for calls with and without records: the same carve)
-    (void)b.f((size_t)batch * w.cx.image_floats()), (void)b.f((size_t)batch * w.cy.image_floats());
-  if (int rc = check_workspace(b, ws_bytes)) return rc;
+  else if (c.pairing == PAIRING_CROSS)  // (one workspace query for calls with and without records: the same carve)
+    (void)b.f((size_t)c.batch * w.cx.image_floats()), (void)b.f((size_t)c.batch * w.cy.image_floats());
+  if (int rc = check_workspace(b, c.ws_bytes)) return rc;
   if (ns == 0) return RGFM_OK;
-  hipStream_t s = (hipStream_t)stream;
-  if (int rc = w.cx.begin(s, num_steps, step_begin, ns)) return rc;
-  if (int rc = w.cy.begin(s, num_steps, step_begin, ns)) return rc;
+  hipStream_t s = (hipStream_t)c.stream;
+  if (int rc = w.cx.begin(s, c.num_steps, c.step_begin, ns)) return rc;
+  if (int rc = w.cy.begin(s, c.num_steps, c.step_begin, ns)) return rc;
   if (sink.on())
     if (int rc = sink.begin(s, w.cx.image_floats(), w.cy.image_floats())) return rc;
-  auto net = [](NetChain& c) { return [&c](auto... a) { return c.eval(a...); }; };  // pair_loop's eval: NetChain::eval
-  return pair_loop(net(w.cx), net(w.cy), x_inout, y_inout, mc_x1, mc_y1, mc_ratios, n_mc, batch, num_steps, strength, step_begin, ns,
-                   (int)w.cx.image_floats(), (int)w.cy.image_floats(), w.vx, w.vy, w.logp, s, w.gstate, solver, w.cx.mid,
-                   w.cy.mid, sink.on() ? &sink : nullptr, pairing);
+  auto net = [](NetChain& n) { return [&n](auto... a) { return n.eval(a...); }; };  // pair_loop's eval: NetChain::eval
+  return pair_loop(net(w.cx), net(w.cy),
+                   {.x = x_inout, .y = y_inout, .mc_x1 = mc_x1, .mc_y1 = mc_y1, .mc_ratios = mc_ratios, .n_mc = n_mc,
+                    .dx = (int)w.cx.image_floats(), .dy = (int)w.cy.image_floats(), .vx = w.vx, .vy = w.vy, .scratch = w.scratch,
+                    .gstate = w.gstate, .x_mid = w.cx.mid, .y_mid = w.cy.mid},
+                   c, ns, sink);
 }
 
 }  // namespace
@@ -407,13 +392,16 @@ extern "C" int rgfm_sample_cond_ode_workspace_bytes(const rgfm_unet* h, int batc
 extern "C" int rgfm_sample_cond(rgfm_unet* h, float* s_inout, const float* mc_set, const float* ratios, int n_mc, int batch,
                                 int num_steps, double gamma, int step_begin, int step_end, void* ws, size_t ws_bytes,
                                 rgfm_stream_t stream) {
-  return cond_loop(h, s_inout, mc_set, ratios, n_mc, batch, num_steps, gamma, step_begin, step_end, SOLVER_EULER, ws, ws_bytes,
-                   stream);
+  return cond_loop(h, s_inout, mc_set, ratios, n_mc,
+                   {.batch = batch, .num_steps = num_steps, .step_begin = step_begin, .step_end = step_end, .strength = gamma,
+                    .ws = ws, .ws_bytes = ws_bytes, .stream = stream});
 }
 extern "C" int rgfm_sample_cond_ode(rgfm_unet* h, float* s_inout, const float* mc_set, const float* ratios, int n_mc, int batch,
                                     int num_steps, double gamma, int step_begin, int step_end, int solver, void* ws,
                                     size_t ws_bytes, rgfm_stream_t stream) {
-  return cond_loop(h, s_inout, mc_set, ratios, n_mc, batch, num_steps, gamma, step_begin, step_end, solver, ws, ws_bytes, stream);
+  return cond_loop(h, s_inout, mc_set, ratios, n_mc,
+                   {.batch = batch, .num_steps = num_steps, .step_begin = step_begin, .step_end = step_end, .solver = solver,
+                    .strength = gamma, .ws = ws, .ws_bytes = ws_bytes, .stream = stream});
 }
 
 extern "C" int rgfm_sample_pair_workspace_bytes(const rgfm_unet* hx, const rgfm_unet* hy, int batch, int n_mc,
@@ -428,15 +416,17 @@ extern "C" int rgfm_sample_pair(rgfm_unet* hx, rgfm_unet* hy, float* x_inout, fl
                                 const float* mc_y1, const float* mc_ratios, int n_mc, int batch, int num_steps,
                                 double gamma, int step_begin, int step_end, void* ws, size_t ws_bytes,
                                 rgfm_stream_t stream) {
-  return pair_sample(hx, hy, x_inout, y_inout, mc_x1, mc_y1, mc_ratios, n_mc, batch, num_steps, gamma, step_begin, step_end,
-                     SOLVER_EULER, ws, ws_bytes, stream);
+  return pair_sample(hx, hy, x_inout, y_inout, mc_x1, mc_y1, mc_ratios, n_mc,
+                     {.batch = batch, .num_steps = num_steps, .step_begin = step_begin, .step_end = step_end, .strength = gamma,
+                      .ws = ws, .ws_bytes = ws_bytes, .stream = stream});
 }
 extern "C" int rgfm_sample_pair_ode(rgfm_unet* hx, rgfm_unet* hy, float* x_inout, float* y_inout, const float* mc_x1,
                                     const float* mc_y1, const float* mc_ratios, int n_mc, int batch, int num_steps,
                                     double gamma, int step_begin, int step_end, int solver, void* ws, size_t ws_bytes,
                                     rgfm_stream_t stream) {
-  return pair_sample(hx, hy, x_inout, y_inout, mc_x1, mc_y1, mc_ratios, n_mc, batch, num_steps, gamma, step_begin, step_end,
-                     solver, ws, ws_bytes, stream);
+  return pair_sample(hx, hy, x_inout, y_inout, mc_x1, mc_y1, mc_ratios, n_mc,
+                     {.batch = batch, .num_steps = num_steps, .step_begin = step_begin, .step_end = step_end, .solver = solver,
+                      .strength = gamma, .ws = ws, .ws_bytes = ws_bytes, .stream = stream});
 }
 
 // ---- the same loops with the diagnostics sink (include/rgfm.h, "Guidance diagnostics")
@@ -446,8 +436,10 @@ extern "C" int rgfm_sample_cond_diag_workspace_bytes(const rgfm_unet* h, int bat
 extern "C" int rgfm_sample_cond_diag(rgfm_unet* h, float* s_inout, const float* mc_set, const float* ratios, int n_mc, int batch,
                                      int num_steps, double gamma, int step_begin, int step_end, int solver, float* diag_out,
                                      size_t diag_records, void* ws, size_t ws_bytes, rgfm_stream_t stream) {
-  return cond_loop(h, s_inout, mc_set, ratios, n_mc, batch, num_steps, gamma, step_begin, step_end, solver, ws, ws_bytes, stream,
-                   diag_out, diag_records);
+  return cond_loop(h, s_inout, mc_set, ratios, n_mc,
+                   {.batch = batch, .num_steps = num_steps, .step_begin = step_begin, .step_end = step_end, .solver = solver,
+                    .strength = gamma, .diag_out = diag_out, .diag_records = diag_records, .ws = ws, .ws_bytes = ws_bytes,
+                    .stream = stream});
 }
 extern "C" int rgfm_sample_pair_diag_workspace_bytes(const rgfm_unet* hx, const rgfm_unet* hy, int batch, int n_mc, int solver,
                                                      size_t* bytes) {
@@ -457,8 +449,10 @@ extern "C" int rgfm_sample_pair_diag(rgfm_unet* hx, rgfm_unet* hy, float* x_inou
                                      const float* mc_y1, const float* mc_ratios, int n_mc, int batch, int num_steps,
                                      double gamma, int step_begin, int step_end, int solver, float* diag_out,
                                      size_t diag_records, void* ws, size_t ws_bytes, rgfm_stream_t stream) {
-  return pair_sample(hx, hy, x_inout, y_inout, mc_x1, mc_y1, mc_ratios, n_mc, batch, num_steps, gamma, step_begin, step_end,
-                     solver, ws, ws_bytes, stream, diag_out, diag_records);
+  return pair_sample(hx, hy, x_inout, y_inout, mc_x1, mc_y1, mc_ratios, n_mc,
+                     {.batch = batch, .num_steps = num_steps, .step_begin = step_begin, .step_end = step_end, .solver = solver,
+                      .strength = gamma, .diag_out = diag_out, .diag_records = diag_records, .ws = ws, .ws_bytes = ws_bytes,
+                      .stream = stream});
 }
 
 // ---- cross pairing: all n_mc x n_mc pairs of the MC set (include/rgfm.h, "Cross pairing of the MC set")
@@ -481,9 +475,9 @@ int guidance_block_cross(const float* x, const float* y, float* vx, float* vy, c
   if (rc) return rc;
   if (need > ws_bytes) return fail(RGFM_ENOMEM, "workspace too small: %zu < %zu", ws_bytes, need);
   if ((rc = ensure_init())) return rc;
-  rc = guidance_launch(x, y, vx, vy, mc_x1, mc_y1, ratio_matrix, batch, n_mc, dim_x, dim_y, t, gamma, (float*)ws, wx_out,
-                       nullptr, nullptr, 0.f, (hipStream_t)stream, nullptr, nullptr, 0, 0, nullptr, nullptr, nullptr,
-                       PAIRING_CROSS, wy_out);
+  rc = guidance_launch({.x = x, .y = y, .vx = vx, .vy = vy, .mx = mc_x1, .my = mc_y1, .r = ratio_matrix, .B = batch, .N = n_mc,
+                        .dx = dim_x, .dy = dim_y, .t = t, .strength = gamma, .scratch = (float*)ws, .weights_out = wx_out,
+                        .weights_out_y = wy_out, .stream = (hipStream_t)stream, .pairing = PAIRING_CROSS});
   if (rc) return rc;
   HIP_TRY(hipGetLastError());
   return RGFM_OK;
@@ -508,8 +502,9 @@ extern "C" int rgfm_guidance_diag_cross(const float* x, const float* y, const fl
                                         const float* mc_y1, const float* ratio_matrix, int batch, int n_mc, int dim_x,
                                         int dim_y, double t, float* diag_out, void* ws, size_t ws_bytes, rgfm_stream_t stream) {
   if (!x || !y || !vx || !vy || !mc_x1 || !mc_y1 || !ratio_matrix || !diag_out || !ws) return fail(RGFM_EINVAL, "null argument");
-  return guidance_diag(x, y, vx, vy, mc_x1, mc_y1, ratio_matrix, batch, n_mc, dim_x, dim_y, t, 0, diag_out, ws, ws_bytes, stream,
-                       PAIRING_CROSS);
+  return guidance_diag({.x = x, .y = y, .mx = mc_x1, .my = mc_y1, .r = ratio_matrix, .B = batch, .N = n_mc, .dx = dim_x,
+                        .dy = dim_y, .t = t, .stream = (hipStream_t)stream, .pairing = PAIRING_CROSS},
+                       vx, vy, diag_out, ws, ws_bytes);
 }
 // (one query for calls with and without diagnostics: the scratch velocities are always counted)
 extern "C" int rgfm_sample_pair_cross_workspace_bytes(const rgfm_unet* hx, const rgfm_unet* hy, int batch, int n_mc, int solver,
@@ -521,8 +516,10 @@ extern "C" int rgfm_sample_pair_cross(rgfm_unet* hx, rgfm_unet* hy, float* x_ino
                                       const float* mc_y1, const float* ratio_matrix, int n_mc, int batch, int num_steps,
                                       double gamma, int step_begin, int step_end, int solver, float* diag_out,
                                       size_t diag_records, void* ws, size_t ws_bytes, rgfm_stream_t stream) {
-  return pair_sample(hx, hy, x_inout, y_inout, mc_x1, mc_y1, ratio_matrix, n_mc, batch, num_steps, gamma, step_begin, step_end,
-                     solver, ws, ws_bytes, stream, diag_out, diag_records, PAIRING_CROSS);
+  return pair_sample(hx, hy, x_inout, y_inout, mc_x1, mc_y1, ratio_matrix, n_mc,
+                     {.batch = batch, .num_steps = num_steps, .step_begin = step_begin, .step_end = step_end, .solver = solver,
+                      .strength = gamma, .diag_out = diag_out, .diag_records = diag_records, .ws = ws, .ws_bytes = ws_bytes,
+                      .stream = stream, .pairing = PAIRING_CROSS});
 }
 
 // ---- guidance strength as data (include/rgfm.h, "Guidance strength per sample and per stage"): each loop is its
@@ -532,23 +529,28 @@ extern "C" int rgfm_sample_pair_gs(rgfm_unet* hx, rgfm_unet* hy, float* x_inout,
                                    const float* gamma_rows, const double* stage_scale, int n_stage_scale, int step_begin,
                                    int step_end, int solver, float* diag_out, size_t diag_records, void* ws, size_t ws_bytes,
                                    rgfm_stream_t stream) {
-  return pair_sample(hx, hy, x_inout, y_inout, mc_x1, mc_y1, mc_ratios, n_mc, batch, num_steps,
-                     Strength(gamma, gamma_rows, stage_scale, n_stage_scale), step_begin, step_end, solver, ws, ws_bytes, stream,
-                     diag_out, diag_records);
+  return pair_sample(hx, hy, x_inout, y_inout, mc_x1, mc_y1, mc_ratios, n_mc,
+                     {.batch = batch, .num_steps = num_steps, .step_begin = step_begin, .step_end = step_end, .solver = solver,
+                      .strength = Strength(gamma, gamma_rows, stage_scale, n_stage_scale), .diag_out = diag_out,
+                      .diag_records = diag_records, .ws = ws, .ws_bytes = ws_bytes, .stream = stream});
 }
 extern "C" int rgfm_sample_pair_cross_gs(rgfm_unet* hx, rgfm_unet* hy, float* x_inout, float* y_inout, const float* mc_x1,
                                          const float* mc_y1, const float* ratio_matrix, int n_mc, int batch, int num_steps,
                                          double gamma, const float* gamma_rows, const double* stage_scale, int n_stage_scale,
                                          int step_begin, int step_end, int solver, float* diag_out, size_t diag_records,
                                          void* ws, size_t ws_bytes, rgfm_stream_t stream) {
-  return pair_sample(hx, hy, x_inout, y_inout, mc_x1, mc_y1, ratio_matrix, n_mc, batch, num_steps,
-                     Strength(gamma, gamma_rows, stage_scale, n_stage_scale), step_begin, step_end, solver, ws, ws_bytes, stream,
-                     diag_out, diag_records, PAIRING_CROSS);
+  return pair_sample(hx, hy, x_inout, y_inout, mc_x1, mc_y1, ratio_matrix, n_mc,
+                     {.batch = batch, .num_steps = num_steps, .step_begin = step_begin, .step_end = step_end, .solver = solver,
+                      .strength = Strength(gamma, gamma_rows, stage_scale, n_stage_scale), .diag_out = diag_out,
+                      .diag_records = diag_records, .ws = ws, .ws_bytes = ws_bytes, .stream = stream,
+                      .pairing = PAIRING_CROSS});
 }
 extern "C" int rgfm_sample_cond_gs(rgfm_unet* h, float* s_inout, const float* mc_set, const float* ratios, int n_mc, int batch,
                                    int num_steps, double gamma, const float* gamma_rows, const double* stage_scale,
                                    int n_stage_scale, int step_begin, int step_end, int solver, float* diag_out,
                                    size_t diag_records, void* ws, size_t ws_bytes, rgfm_stream_t stream) {
-  return cond_loop(h, s_inout, mc_set, ratios, n_mc, batch, num_steps, Strength(gamma, gamma_rows, stage_scale, n_stage_scale),
-                   step_begin, step_end, solver, ws, ws_bytes, stream, diag_out, diag_records);
+  return cond_loop(h, s_inout, mc_set, ratios, n_mc,
+                   {.batch = batch, .num_steps = num_steps, .step_begin = step_begin, .step_end = step_end, .solver = solver,
+                    .strength = Strength(gamma, gamma_rows, stage_scale, n_stage_scale), .diag_out = diag_out,
+                    .diag_records = diag_records, .ws = ws, .ws_bytes = ws_bytes, .stream = stream});
 }

@@ -862,7 +862,7 @@ struct GuidDiag {
 // Strength: what a loop is called with -- the scalar gamma, optionally a device vector of per-row strengths (fp32
 // [batch]; null: gamma for every row) and a HOST array of per-stage scales (null: 1 for every stage), read while the
 // call enqueues and not kept.  A plain double converts to the scalar-only strength, which is every existing entry point.
-// StageStrength: one stage of it, what guidance_launch and the gradient loops' update take -- with `rows` null the blend
+// StageStrength: one stage of it, what a GuidanceCall and the gradient loops' update take -- with `rows` null the blend
 // is the scalar rule on `gamma` (already multiplied by the stage's scale, in double), otherwise row b has
 // (double)rows[b] * scale, formed on the device.
 struct StageStrength {
@@ -893,47 +893,81 @@ struct Strength {
   StageStrength stage(int k) const { return rows ? StageStrength(gamma, rows, s(k)) : StageStrength(scale ? gamma * scale[k] : gamma); }
 };
 
-inline int guidance_launch(const float* x, const float* y, float* vx, float* vy, const float* mx, const float* my,
-                    const float* r, int B, int N, int dx, int dy, double t, const StageStrength& strength, float* logp,
-                    float* weights_out, float* xs, float* ys, float dt, hipStream_t s, const float* sched = nullptr,
-                    const int* step_ptr = nullptr, int phase = 0, int ratio_stride = 0, const float* xb = nullptr,
-                    const float* yb = nullptr, const GuidDiag* diag = nullptr, int pairing = PAIRING_PAIRED,
-                    float* weights_out_y = nullptr) {
-  // phase 0: the whole block; 1: distances + importance weights only -- they need the step's (x_t, y_t) and the MC set,
-  // not the velocities; 2: the rest (needs v); 3 (with diag): the weights and the diagnostics, v is only read
-  // One-sided block (conditional sampling): dy = 0 with y, vy, my, ys null, and ratio_stride = N -- r is then [B][N],
-  // a ratio row per sample.  The kernels take the second modality's slices and column blocks from dy, so none is
-  // launched; the observed side's Gaussian factor is constant in the MC index and cancels in the normalised weights.
-  // pairing = PAIRING_CROSS: r is the ratio matrix [N][N] (x index first) of all pairs (x1_i, y1_j); the weights stage
-  // writes one marginal weight row per modality (weights_out: x, weights_out_y: y) and logp is guid_cross_scratch_bytes.
-  // xb / yb (with xs / ys): the state the update starts from, xs = xb + dt * blended, while the block is evaluated at
-  // x / y (second stage of a midpoint step); null or x / y themselves: xs = x + dt * blended.
+// What of the block a call of guidance_launch enqueues.
+enum class GuidPhase {
+  All,          // the whole block
+  Weights,      // distances + importance weights only: they need the step's (x_t, y_t) and the MC set, not the velocities
+  Apply,        // the rest (needs v, and the weights of an earlier Weights call in the scratch)
+  WeightsDiag,  // (with diag) the weights and the diagnostics, no apply: v is only read
+};
+// One call of the MC guidance block, by field name; what a caller leaves out is off.
+struct GuidanceCall {
+  // the state the block is evaluated at, [B][dx] / [B][dy], and the velocities it reads and overwrites.
+  // One-sided block (conditional sampling): dy = 0 with y, vy, my, ys null and ratio_stride = N.  The kernels take the
+  // second modality's slices and column blocks from dy, so none is launched; the observed side's Gaussian factor is
+  // constant in the MC index and cancels in the normalised weights.
+  const float *x = nullptr, *y = nullptr;
+  float *vx = nullptr, *vy = nullptr;
+  const float *mx = nullptr, *my = nullptr;  // the MC set, [N][dx] / [N][dy]
+  // ratios of the MC set.  ratio_stride 0: r is [N], one ratio per MC pair; ratio_stride = N (the one-sided block): r is
+  // [B][N], a ratio row per sample.  pairing = PAIRING_CROSS: r is the ratio matrix [N][N] (x index first) of all pairs
+  // (x1_i, y1_j), the weights stage writes one marginal weight row per modality (weights_out: x, weights_out_y: y) and
+  // `scratch` is guid_cross_scratch_bytes.
+  const float* r = nullptr;
+  int ratio_stride = 0;
+  int B = 0, N = 0, dx = 0, dy = 0;
+  double t = 0.0;
+  StageStrength strength{0.0};
+  float* scratch = nullptr;  // the block's whole scratch: guid_scratch_bytes(B, N, pairing)
+  float *weights_out = nullptr, *weights_out_y = nullptr;  // [B][N] copies of the normalised weights, or null
+  // xs / ys: the state the apply stage moves, xs = xb + dt * blended; null: the blended velocity goes to vx / vy only.
+  // xb / yb: the state the update starts from while the block is evaluated at x / y (second stage of a midpoint
+  // step); null or x / y themselves: xs = x + dt * blended.
+  float *xs = nullptr, *ys = nullptr;
+  const float *xb = nullptr, *yb = nullptr;
+  float dt = 0.f;
+  hipStream_t stream = nullptr;
+  // graph replay: the per-step scalars and the device-side step counter that picks them (pair_loop)
+  const float* sched = nullptr;
+  const int* step_ptr = nullptr;
+  GuidDiag diag{};  // rec null: no diagnostics
+  int pairing = PAIRING_PAIRED;
+  GuidPhase phase = GuidPhase::All;
+};
+
+inline int guidance_launch(const GuidanceCall& c) {
+  const float *x = c.x, *y = c.y, *xb = c.xb, *yb = c.yb;
+  float *vx = c.vx, *vy = c.vy, *scratch = c.scratch;
+  const int B = c.B, N = c.N, dx = c.dx, dy = c.dy;
+  const GuidPhase phase = c.phase;
+  const GuidDiag& diag = c.diag;
+  hipStream_t s = c.stream;
   if (dx % 4 || dy % 4) return fail(RGFM_EINVAL, "flattened image sizes must be multiples of 4");
   if ((size_t)4 * N * sizeof(float) > 64 * 1024) return fail(RGFM_EINVAL, "n_mc too large (max 4096)");
-  const bool cross = pairing == PAIRING_CROSS;
+  const bool cross = c.pairing == PAIRING_CROSS;
   if (cross && (N < 1 || N > GUID_CROSS_MAX_N || dy < 1))
     return fail(RGFM_EINVAL, "cross pairing needs two modalities and 1 <= n_mc <= %d (got %d)", GUID_CROSS_MAX_N, N);
   // Python-double scalar arithmetic of the reference (sample_mnist_svhn.py:115,127,135,159,170),
   // rounded to fp32 where a tensor op consumes it.
   GuidanceArgs a{};
-  a.x = x, a.y = y, a.vx = vx, a.vy = vy, a.mc_x1 = mx, a.mc_y1 = my, a.mc_ratios = r;
-  a.ratio_stride = ratio_stride;
+  a.x = x, a.y = y, a.vx = vx, a.vy = vy, a.mc_x1 = c.mx, a.mc_y1 = c.my, a.mc_ratios = c.r;
+  a.ratio_stride = c.ratio_stride;
   a.B = B, a.N = N, a.dx = dx, a.dy = dy;
-  guidance_scalars(t, &a.tf, &a.s2, &a.cden);
-  a.sched = sched, a.step_ptr = sched ? step_ptr : nullptr;
-  a.g1 = (float)(1.0 - strength.gamma), a.g2 = (float)strength.gamma;
-  a.gamma_rows = strength.rows, a.gamma_scale = strength.scale;
-  a.dist = reinterpret_cast<double*>(logp), a.weights_out = weights_out, a.x_state = xs, a.y_state = ys, a.dt = dt;
-  a.diag_rec = diag ? diag->rec : nullptr;
+  guidance_scalars(c.t, &a.tf, &a.s2, &a.cden);
+  a.sched = c.sched, a.step_ptr = c.sched ? c.step_ptr : nullptr;
+  a.g1 = (float)(1.0 - c.strength.gamma), a.g2 = (float)c.strength.gamma;
+  a.gamma_rows = c.strength.rows, a.gamma_scale = c.strength.scale;
+  a.dist = reinterpret_cast<double*>(scratch), a.weights_out = c.weights_out, a.x_state = c.xs, a.y_state = c.ys, a.dt = c.dt;
+  a.diag_rec = diag.rec;
   a.x_base = xb == x ? nullptr : xb, a.y_base = yb == y ? nullptr : yb;
-  a.wbuf = reinterpret_cast<float*>(reinterpret_cast<char*>(logp) + guid_dist_bytes(B, N));
+  a.wbuf = reinterpret_cast<float*>(reinterpret_cast<char*>(scratch) + guid_dist_bytes(B, N));
   a.wsum = reinterpret_cast<float*>(reinterpret_cast<char*>(a.wbuf) + guid_wbuf_bytes(B, N));
   if (cross) {
-    float* p = reinterpret_cast<float*>(reinterpret_cast<char*>(logp) + guid_scratch_bytes(B, N));
+    float* p = reinterpret_cast<float*>(reinterpret_cast<char*>(scratch) + guid_scratch_bytes(B, N));
     const size_t row = guid_wbuf_bytes(B, N) / sizeof(float), sum = guid_wsum_bytes(B) / sizeof(float);
     a.wbuf_y = p, a.wsum_y = p + row, p += row + sum;
     a.ca = p, a.cb = p + row, a.cu = p + 2 * row, a.cs = p + 3 * row, a.cq = p + 4 * row;
-    a.weights_out_y = weights_out_y;
+    a.weights_out_y = c.weights_out_y;
   }
   a.slice_len = 512;  // 512-element slices (8 x 16 x 4 = 512 workgroups at the benchmark shape) unless that needs more than RGFM_GUID_SLICES of them
   while ((dx + a.slice_len - 1) / a.slice_len + (dy + a.slice_len - 1) / a.slice_len > RGFM_GUID_SLICES) a.slice_len *= 2;
@@ -941,24 +975,24 @@ inline int guidance_launch(const float* x, const float* y, float* vx, float* vy,
   // algorithmic bytes.  logp: rows of x, y and the MC set in, the sliced fp64 distances out.  apply: the
   // distances, x, y, v and the MC set in, the new state (or velocity) out.
   const double D = (double)dx + dy, dist_b = 8.0 * (a.nsx + a.nsy) * (double)B * N;
-  if (phase != 2) {  // (timer class "guid_logp": the distances AND the importance weights made of them)
+  if (phase != GuidPhase::Apply) {  // (timer class "guid_logp": the distances AND the importance weights made of them)
     ProfScope p(RGFM_KCLASS_GUID_LOGP, 4.0 * (B + N) * D + dist_b, s);
     launch_guid_logp(a, s);
     if (cross) launch_guid_cross_weights(a, s);  // (with diag: the joint ESS, the marginals' range and Z_bar too)
     else launch_guid_weights(a, s);
   }
-  if (phase != 2 && diag && !cross) launch_diag_wstats(a.wbuf, B, N, diag->rec, s);
-  if (phase != 1 && diag) {  // before the real apply: in a loop that one moves the state g is taken at
-    launch_diag_rownorm(vx, B, dx, diag->rec, RGFM_DIAG_V_NORM_X, s);
-    if (dy) launch_diag_rownorm(vy, B, dy, diag->rec, RGFM_DIAG_V_NORM_Y, s);
+  if (phase != GuidPhase::Apply && diag.rec && !cross) launch_diag_wstats(a.wbuf, B, N, diag.rec, s);
+  if (phase != GuidPhase::Weights && diag.rec) {  // before the real apply: in a loop that one moves the state g is taken at
+    launch_diag_rownorm(vx, B, dx, diag.rec, RGFM_DIAG_V_NORM_X, s);
+    if (dy) launch_diag_rownorm(vy, B, dy, diag.rec, RGFM_DIAG_V_NORM_Y, s);
     GuidanceArgs d = a;
-    d.vx = diag->gx, d.vy = diag->gy, d.g1 = 0.f, d.g2 = 1.f, d.gamma_rows = nullptr;
+    d.vx = diag.gx, d.vy = diag.gy, d.g1 = 0.f, d.g2 = 1.f, d.gamma_rows = nullptr;
     d.x_state = d.y_state = nullptr, d.x_base = d.y_base = nullptr, d.weights_out = nullptr;
     launch_guid_apply(d, s);
-    launch_diag_rownorm(diag->gx, B, dx, diag->rec, RGFM_DIAG_G_NORM_X, s);
-    if (dy) launch_diag_rownorm(diag->gy, B, dy, diag->rec, RGFM_DIAG_G_NORM_Y, s);
+    launch_diag_rownorm(diag.gx, B, dx, diag.rec, RGFM_DIAG_G_NORM_X, s);
+    if (dy) launch_diag_rownorm(diag.gy, B, dy, diag.rec, RGFM_DIAG_G_NORM_Y, s);
   }
-  if (phase != 1 && phase != 3) {
+  if (phase == GuidPhase::All || phase == GuidPhase::Apply) {
     ProfScope p(RGFM_KCLASS_GUID_APPLY, 4.0 * B * N + 4.0 * N * D + 4.0 * B * D * 3.0, s);
     launch_guid_apply(a, s);
   }

@@ -16,8 +16,6 @@ inline int check_solver(int solver, int ns, int num_steps) {
   return RGFM_OK;
 }
 inline int check_solver_id(int solver) { return check_solver(solver, 0, 0); }  // (what a *_workspace_bytes query can check)
-// stages of a call over `ns` steps, in the order of step_stages: what the diagnostics records and a Strength's scale count
-inline int loop_stages(int solver, int ns) { return ns * (solver == SOLVER_MIDPOINT ? 2 : 1); }
 
 // The prelude of every loop, in this order: solver id, null arguments (`have_args`: the loop's own pointers), step range,
 // step caps.  `time_table` = false (the FlowMatchingModel loops embed t per evaluation): no cap on the steps of a call.
@@ -36,21 +34,21 @@ inline int check_workspace(const Bump& carved, size_t ws_bytes) {
 }
 
 // The diagnostics sink of a loop (include/rgfm.h, "Guidance diagnostics"): null `out` = off, and every loop then enqueues
-// what it enqueues without one.  On: one [batch][RGFM_DIAG_FLOATS] block of `out` per stage, in the order of step_stages;
-// `begin` zeroes all of them (an unguided stage's record, and the entries a loop does not fill, stay 0), the guided
-// stages' kernels fill theirs.  gx / gy: the MC loops' scratch velocities for the pure guided velocity (GuidDiag),
-// carved behind the loop's own workspace.
+// what it enqueues without one.  On: one [batch][RGFM_DIAG_FLOATS] block of `out` per stage, block Stage::row the
+// stage's; `begin` zeroes all of them (an unguided stage's record, and the entries a loop does not fill, stay 0), the
+// guided stages' kernels fill theirs.  gx / gy: the MC loops' scratch velocities for the pure guided velocity
+// (GuidDiag), carved behind the loop's own workspace.
 struct DiagSink {
   float* out = nullptr;
   size_t records = 0;
-  int batch = 0, n_stages = 0, stage = 0;
+  int batch = 0, n_stages = 0;
   float *gx = nullptr, *gy = nullptr;
   bool on() const { return out != nullptr; }
   // the argument check of every *_diag entry point, before anything is carved or enqueued
   int check(float* diag_out, size_t diag_records, int batch_, int ns, int solver) {
     if (!diag_out && !diag_records) return RGFM_OK;
     if (!diag_out || !diag_records) return fail(RGFM_EINVAL, "diag_out and diag_records go together (both, or null and 0)");
-    out = diag_out, records = diag_records, batch = batch_, n_stages = ns * (solver == SOLVER_MIDPOINT ? 2 : 1);
+    out = diag_out, records = diag_records, batch = batch_, n_stages = loop_stages(solver, ns);
     if (records < (size_t)n_stages * batch)
       return fail(RGFM_EINVAL, "diag_records %zu < %d stages x %d samples", records, n_stages, batch);
     return RGFM_OK;
@@ -62,7 +60,8 @@ struct DiagSink {
     if (gy && dy) HIP_TRY(hipMemsetAsync(gy, 0, (size_t)batch * dy * sizeof(float), s));
     return RGFM_OK;
   }
-  float* next() { return out + (size_t)(stage++) * batch * RGFM_DIAG_FLOATS; }  // the next stage's records
+  // the records of stage `row` (Stage::row; the one evaluation of a block: 0), for a GuidanceCall; off: none
+  GuidDiag at(int row) const { return on() ? GuidDiag{out + (size_t)row * batch * RGFM_DIAG_FLOATS, gx, gy} : GuidDiag{}; }
 };
 // bytes a loop's workspace grows by with diagnostics on (the *_diag_workspace_bytes queries): DiagSink::carve
 inline size_t diag_scratch_bytes(int batch, size_t dx, size_t dy) {
@@ -70,6 +69,27 @@ inline size_t diag_scratch_bytes(int batch, size_t dx, size_t dy) {
   DiagSink d;
   d.batch = batch, d.carve(b, dx, dy);
   return b.off;
+}
+
+// The call-level arguments of a sampler loop, filled by field name in its extern "C" wrapper; the loop's own operands
+// (handles, states, MC set) travel beside it.  What an entry point has no argument for keeps its default.
+struct LoopCall {
+  int batch = 0, num_steps = 0, step_begin = 0, step_end = 0, solver = SOLVER_EULER;
+  Strength strength{0.0};
+  float* diag_out = nullptr;  // the diagnostics sink (DiagSink): both, or null and 0
+  size_t diag_records = 0;
+  void* ws = nullptr;
+  size_t ws_bytes = 0;
+  rgfm_stream_t stream = nullptr;
+  int pairing = PAIRING_PAIRED;  // (the U-Net pair loop)
+};
+// The head of every guided loop, in this order: the switches, check_loop (`have_args`: the loop's own pointers), the
+// sink's arguments, the strength's.  The loop's own argument checks follow it, then its carve and check_workspace.
+inline int open_loop(const LoopCall& c, bool have_args, int* ns, DiagSink* sink, bool time_table = true) {
+  refresh_modes();
+  if (int rc = check_loop(c.solver, have_args && c.ws, c.batch, c.num_steps, c.step_begin, c.step_end, ns, time_table)) return rc;
+  if (int rc = sink->check(c.diag_out, c.diag_records, c.batch, *ns, c.solver)) return rc;
+  return c.strength.check(loop_stages(c.solver, *ns));
 }
 
 // Time-table rows of a loop's stages.  Euler: row i is t = (step_begin + i) / num_steps.  Midpoint: row 2i is the step's
@@ -112,7 +132,6 @@ struct NetChain {
     HIP_TRY(hipMemsetAsync(cnt, 0, (size_t)batch * sizeof(unsigned), s));
     return launch_stage_table(h, solver, num_steps, step_begin, ns, table, s);
   }
-  int stages(int i, Stage st[2]) const { return step_stages(solver, num_steps, step_begin, i, st); }
   // The net at `in` with time-table row `row` on `s`: v_out receives the raw velocity, state_out = base + v dts (the fused
   // epilogue of the out-conv).  step_ptr: the device-side step counter of the graph-replay path, which picks the row.
   int eval(int row, hipStream_t s, const float* in, float* v_out, float* state_out, const float* base, float dts,
@@ -125,18 +144,30 @@ struct NetChain {
   // one unguided step of `x` on `s`: every stage's update fused into the out-conv
   int step(int i) {
     Stage st[2];
-    const int n = stages(i, st);
+    const int n = step_stages(solver, num_steps, step_begin, i, st);
     for (int k = 0; k < n; ++k)
       if (int rc = eval(st[k].row, s, st[k].reads_mid ? mid : x, nullptr, st[k].writes_mid ? mid : x, x, st[k].dts)) return rc;
     return RGFM_OK;
   }
 };
 
+// what pair_loop works on beside the call record: the two states, the MC set, and its buffers in the caller's workspace
+struct PairOperands {
+  float *x = nullptr, *y = nullptr;  // the states, advanced in place
+  // the MC set; pairing = PAIRING_CROSS: mc_ratios is the [n_mc][n_mc] ratio matrix and `scratch` guid_cross_scratch_bytes
+  const float *mc_x1 = nullptr, *mc_y1 = nullptr, *mc_ratios = nullptr;
+  int n_mc = 0, dx = 0, dy = 0;
+  float *vx = nullptr, *vy = nullptr;  // the guided stages' raw velocities
+  float* scratch = nullptr;            // the guidance block's (GuidanceCall::scratch)
+  float* gstate = nullptr;             // graph-replay state, or null: never replay
+  float *x_mid = nullptr, *y_mid = nullptr;  // midpoint: one mid-state buffer per modality
+};
+
 // Shared loop of paired_sampler (src/utils/flow_utils.py:186-278 with the guidance of
 // src/sample_mnist_svhn.py:117-175): eval_x / eval_y enqueue one velocity-net evaluation of a stage
 // on the given stream, writing the raw velocity (guided stages) or the fused Euler update.
 // eval(row, stream, in, v_out, state_out, base, dt, step): the net at `in` with time-table row `row`; state_out = base + v dt.
-// The stages of a step come from step_stages.  Midpoint (x_mid / y_mid: one mid-state buffer per modality):
+// The stages come from for_each_stage.  Midpoint (x_mid / y_mid: one mid-state buffer per modality):
 //   (x_mid, y_mid) = (x, y) + (dt / 2) F(x, y, t1),   (x, y) = (x, y) + dt F(x_mid, y_mid, t2),   t2 = t1 + dt / 2,
 // F the whole guided velocity at the stage's own state and time; a stage is guided iff its own t > 1e-3.  Each stage
 // forks and joins the side stream as an Euler step does.
@@ -147,12 +178,9 @@ struct NetChain {
 // step is captured once -- both streams, fork and join included -- into a hipGraph and every guided step is one
 // hipGraphLaunch.  Results are bit-identical to the kernel-by-kernel path (same kernels, same arguments).
 template <class EvalX, class EvalY>
-int pair_loop(EvalX&& eval_x, EvalY&& eval_y, float* x_inout, float* y_inout, const float* mc_x1,
-              const float* mc_y1, const float* mc_ratios, int n_mc, int batch, int num_steps, const Strength& strength,
-              int step_begin, int ns, int dx, int dy, float* vx, float* vy, float* logp, hipStream_t caller,
-              float* gstate = nullptr, int solver = SOLVER_EULER, float* x_mid = nullptr, float* y_mid = nullptr,
-              DiagSink* diag = nullptr, int pairing = PAIRING_PAIRED) {
-  // pairing = PAIRING_CROSS: mc_ratios is the [n_mc][n_mc] ratio matrix and logp guid_cross_scratch_bytes (guidance_launch)
+int pair_loop(EvalX&& eval_x, EvalY&& eval_y, const PairOperands& p, const LoopCall& c, int ns, const DiagSink& sink) {
+  const int n_mc = p.n_mc, num_steps = c.num_steps, step_begin = c.step_begin, solver = c.solver;
+  const Strength& strength = c.strength;
   // The two velocity nets of a step are independent (reference :119-121): the second one runs on a
   // side stream forked from / joined back into the caller's stream every step, which fills the CUs
   // that one net's small-grid launches (8x8 level, kernel tails) leave idle.
@@ -164,8 +192,9 @@ int pair_loop(EvalX&& eval_x, EvalY&& eval_y, float* x_inout, float* y_inout, co
   hipEvent_t ev_fork = ds->fork, ev_join = ds->join;
   // (diagnostics: kernel by kernel -- each stage writes its own records, a replayed graph would write one stage's)
   // (cross pairing: kernel by kernel as well)
-  const bool use_graph = gstate && g_modes.graph && !g_prof.on && n_mc > 0 && ns >= 4 && solver == SOLVER_EULER && !diag && pairing == PAIRING_PAIRED && !strength.is_data();
+  const bool use_graph = p.gstate && g_modes.graph && !g_prof.on && n_mc > 0 && ns >= 4 && solver == SOLVER_EULER && !sink.on() && c.pairing == PAIRING_PAIRED && !strength.is_data();
   // (a strength that is data -- per row or per stage -- runs kernel by kernel: the replayed graph holds one stage's scalars)
+  const hipStream_t caller = (hipStream_t)c.stream;
   hipStream_t s = caller;
   if (use_graph && caller == nullptr) {  // (see DevState::main)
     s = ds->main;
@@ -180,20 +209,22 @@ int pair_loop(EvalX&& eval_x, EvalY&& eval_y, float* x_inout, float* y_inout, co
       for (auto& g : ds->graphs) (void)hipGraphExecDestroy(g.first), (void)hipGraphDestroy(g.second);
       ds->graphs.clear();
     }
-    step_dev = reinterpret_cast<int*>(gstate);
-    sched_dev = gstate + 64;
+    step_dev = reinterpret_cast<int*>(p.gstate);
+    sched_dev = p.gstate + 64;
     HIP_TRY(hipMemsetAsync(step_dev, 0, 256, s));
     launch_guid_schedule(sched_dev, step_begin, ns, num_steps, s);
   }
   // one stage: (xout, yout) = (x, y) + dts * F(xin, yin, t), the nets reading time-table row `row`
-  auto one_stage = [&](const Stage& g, bool guided, const StageStrength& gamma) -> int {
-    float *xin = g.reads_mid ? x_mid : x_inout, *yin = g.reads_mid ? y_mid : y_inout;
-    float *xout = g.writes_mid ? x_mid : x_inout, *yout = g.writes_mid ? y_mid : y_inout;
-    const float *xb = x_inout, *yb = y_inout;
+  auto one_stage = [&](const Stage& g, bool guided) -> int {
+    float *xin = g.reads_mid ? p.x_mid : p.x, *yin = g.reads_mid ? p.y_mid : p.y;
+    float *xout = g.writes_mid ? p.x_mid : p.x, *yout = g.writes_mid ? p.y_mid : p.y;
+    float *vx = p.vx, *vy = p.vy;
+    const float *xb = p.x, *yb = p.y;
     hipStream_t sy = overlap ? side : s;
-    GuidDiag gd{};
-    if (diag) gd = {diag->next(), diag->gx, diag->gy};
-    const GuidDiag* dg = diag && guided ? &gd : nullptr;
+    GuidanceCall gc{.x = xin, .y = yin, .vx = vx, .vy = vy, .mx = p.mc_x1, .my = p.mc_y1, .r = p.mc_ratios,
+                    .B = c.batch, .N = n_mc, .dx = p.dx, .dy = p.dy, .t = g.t, .strength = strength.stage(g.row),
+                    .scratch = p.scratch, .xs = xout, .ys = yout, .xb = xb, .yb = yb, .dt = g.dts, .stream = s,
+                    .sched = sched_dev, .step_ptr = step_dev, .diag = sink.at(g.row), .pairing = c.pairing};
     if (overlap) {
       HIP_TRY(hipEventRecord(ev_fork, s));
       HIP_TRY(hipStreamWaitEvent(side, ev_fork, 0));
@@ -207,15 +238,13 @@ int pair_loop(EvalX&& eval_x, EvalY&& eval_y, float* x_inout, float* y_inout, co
     // guided step's nets write velocities, the state moves in guid_apply): they go on this stream BEFORE it waits for the
     // other net -- the x net of a pair is the quicker one, so they run in its shadow instead of on the step's critical path
     if (guided && overlap) {
-      rc = guidance_launch(xin, yin, vx, vy, mc_x1, mc_y1, mc_ratios, batch, n_mc, dx, dy, g.t, gamma, logp,
-                           nullptr, xout, yout, g.dts, s, sched_dev, step_dev, 1, 0, xb, yb, dg, pairing);
-      if (rc) return rc;
+      gc.phase = GuidPhase::Weights;
+      if ((rc = guidance_launch(gc))) return rc;
     }
     if (overlap) HIP_TRY(hipStreamWaitEvent(s, ev_join, 0));
     if (guided) {
-      rc = guidance_launch(xin, yin, vx, vy, mc_x1, mc_y1, mc_ratios, batch, n_mc, dx, dy, g.t, gamma, logp,
-                           nullptr, xout, yout, g.dts, s, sched_dev, step_dev, overlap ? 2 : 0, 0, xb, yb, dg, pairing);
-      if (rc) return rc;
+      gc.phase = overlap ? GuidPhase::Apply : GuidPhase::All;
+      if ((rc = guidance_launch(gc))) return rc;
     }
     if (step_dev) launch_step_inc(step_dev, s);
     return RGFM_OK;
@@ -241,42 +270,35 @@ int pair_loop(EvalX&& eval_x, EvalY&& eval_y, float* x_inout, float* y_inout, co
   // modality a chain net -> its half of the guided update on its own stream, coupled only through two events per step
   // around the importance weights, the x net up to one evaluation ahead -- is bit-identical and 0.5 - 0.9 % SLOWER
   // (469 - 471 vs 473 paired images/s, same box, alternating): the join costs nothing the chains could use.)
-  int stage_no = 0;  // the call's own stage count: the index into the strength's per-stage scale
-  for (int i = 0; i < ns; ++i) {
-    Stage st[2];
-    const int n = step_stages(solver, num_steps, step_begin, i, st);
-    for (int k = 0; k < n; ++k, ++stage_no) {
-      // `t > eps` test of the reference (:124); a stage whose scale is 0 runs as the unguided stage
-      const bool guided = n_mc > 0 && st[k].t > 1e-3 && !strength.off(stage_no);
-      const StageStrength gamma = strength.stage(stage_no);
-      if (use_graph && guided) {  // (Euler: the step's one stage)
-        if (!exec) {
-          hipGraph_t graph = nullptr;
-          HIP_TRY(hipStreamBeginCapture(s, hipStreamCaptureModeRelaxed));
-          const int rc = one_stage(st[k], true, gamma);
-          const hipError_t ce = hipStreamEndCapture(s, &graph);
-          if (rc) {  // (a captured graph that will never run: nothing refers to it)
-            if (graph) (void)hipGraphDestroy(graph);
-            return rc;
-          }
-          if (ce != hipSuccess || !graph) {
-            if (graph) (void)hipGraphDestroy(graph);
-            return fail(RGFM_EHIP, "hipStreamEndCapture: %s", hipGetErrorString(ce));
-          }
-          const hipError_t ie = hipGraphInstantiate(&exec, graph, nullptr, nullptr, 0);
-          if (ie != hipSuccess) {
-            exec = nullptr;
-            (void)hipGraphDestroy(graph);
-            return fail(RGFM_EHIP, "hipGraphInstantiate: %s", hipGetErrorString(ie));
-          }
-          ds->graphs.push_back({exec, graph});
-        }
-        HIP_TRY(hipGraphLaunch(exec, s));
-        continue;
+  const int rc = for_each_stage(solver, num_steps, step_begin, ns, [&](const Stage& st) -> int {
+    // `t > eps` test of the reference (:124); a stage whose scale is 0 runs as the unguided stage
+    const bool guided = n_mc > 0 && st.t > 1e-3 && !strength.off(st.row);
+    if (!(use_graph && guided)) return one_stage(st, guided);
+    if (!exec) {  // (Euler: the step's one stage)
+      hipGraph_t graph = nullptr;
+      HIP_TRY(hipStreamBeginCapture(s, hipStreamCaptureModeRelaxed));
+      const int rc = one_stage(st, true);
+      const hipError_t ce = hipStreamEndCapture(s, &graph);
+      if (rc) {  // (a captured graph that will never run: nothing refers to it)
+        if (graph) (void)hipGraphDestroy(graph);
+        return rc;
       }
-      if (int rc = one_stage(st[k], guided, gamma)) return rc;
+      if (ce != hipSuccess || !graph) {
+        if (graph) (void)hipGraphDestroy(graph);
+        return fail(RGFM_EHIP, "hipStreamEndCapture: %s", hipGetErrorString(ce));
+      }
+      const hipError_t ie = hipGraphInstantiate(&exec, graph, nullptr, nullptr, 0);
+      if (ie != hipSuccess) {
+        exec = nullptr;
+        (void)hipGraphDestroy(graph);
+        return fail(RGFM_EHIP, "hipGraphInstantiate: %s", hipGetErrorString(ie));
+      }
+      ds->graphs.push_back({exec, graph});
     }
-  }
+    HIP_TRY(hipGraphLaunch(exec, s));
+    return RGFM_OK;
+  });
+  if (rc) return rc;
   // (the guard's destructor records graph_done and joins `main` into the caller's stream -- on this path too, so that a
   // failing record cannot skip the join)
   HIP_TRY(hipGetLastError());

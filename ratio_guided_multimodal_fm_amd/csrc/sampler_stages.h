@@ -1,17 +1,23 @@
 // sampler_stages.h -- the stage list of the sampler loops' ODE solvers: which time-table row, which time and which step
-// size each stage of step i takes.  The only place that knows the row convention and the two time formulas.  Plain C++
-// (no HIP types): tests/test_sampler_stages_cpu.py compiles it alone into a host program.
+// size each stage of step i takes, and the one walk over the stages of a call.  The only place that knows the row
+// convention and the two time formulas.  Plain C++ (no HIP types): tests/test_sampler_stages_cpu.py compiles it alone
+// into a host program.
 #pragma once
 
 // solvers of the sampler loops (include/rgfm.h: RGFM_SOLVER_*)
 constexpr int SOLVER_EULER = 0, SOLVER_MIDPOINT = 1;
 
 struct Stage {
-  int row;     // time-table row of the stage (launch_stage_table)
+  // The stage's index within the call, 0 .. loop_stages - 1 in the order the stages run: its time-table row
+  // (launch_stage_table), its diagnostics record (DiagSink::at) and its entry of a Strength's per-stage scale.
+  int row;
   double t;    // the stage's own time: a stage is guided iff t > 1e-3
   float dts;   // out = base + dts * F(in, t); base is always the step's state
   bool reads_mid, writes_mid;  // in / out is the loop's mid-state buffer instead of the state
 };
+
+// stages of a call over `ns` steps
+inline int loop_stages(int solver, int ns) { return ns * (solver == SOLVER_MIDPOINT ? 2 : 1); }
 
 // The stages of step i of a call over [step_begin, ...) of num_steps.  Returns their number.
 //   Euler:    one stage, row i, t = (step_begin + i) dt, in place.
@@ -26,4 +32,17 @@ inline int step_stages(int solver, int num_steps, int step_begin, int i, Stage o
   out[0] = {2 * i, t1, (float)(0.5 * dtd), false, true};
   out[1] = {2 * i + 1, ((double)(step_begin + i) + 0.5) * dtd, (float)dtd, true, false};
   return 2;
+}
+
+// The walk of every loop: f(const Stage&) -> int for the loop_stages(solver, ns) stages of a call over `ns` steps from
+// step_begin, in order.  Stops at the first nonzero return and returns it; 0 after the last stage.
+template <class F>
+inline int for_each_stage(int solver, int num_steps, int step_begin, int ns, F&& f) {
+  for (int i = 0; i < ns; ++i) {
+    Stage st[2];
+    const int n = step_stages(solver, num_steps, step_begin, i, st);
+    for (int k = 0; k < n; ++k)
+      if (int rc = f(st[k])) return rc;
+  }
+  return 0;
 }

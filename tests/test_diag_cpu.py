@@ -270,10 +270,12 @@ def test_header_bindings_and_library_list_the_diag_entry_points():
     old, got = _lib.SIGNATURES["rgfm_guidance_apply_cond"][1], _lib.SIGNATURES["rgfm_guidance_diag_cond"][1]
     assert got == old[:8] + [ctypes.c_void_p] + old[-3:]
     from ratio_guided_multimodal_fm_amd import _engine
-    assert _engine._diag_fn("rgfm_sample_pair_ode") == "rgfm_sample_pair_diag"
-    assert _engine._diag_fn("rgfm_sample_cond_grad_ode_workspace_bytes") == "rgfm_sample_cond_grad_diag_workspace_bytes"
-    assert _engine._diag_fn("rgfm_fmnet_sample_pair") == "rgfm_fmnet_sample_pair_diag"
-    assert _engine._diag_fn("rgfm_fmnet_sample_pair_workspace_bytes") == "rgfm_fmnet_sample_pair_diag_workspace_bytes"
+    # the Python layer's export table: every guided loop has a row, which names the twin, its query and their *_diag pair
+    rows = {row.fn: row for row in _engine._GUIDED_LOOPS}
+    assert len(rows) == len(LOOPS)
+    for stem in LOOPS:
+        twin = stem if "fmnet" in stem else stem + "_ode"
+        assert rows[twin][:4] == (twin, twin + "_workspace_bytes", stem + "_diag", stem + "_diag_workspace_bytes"), stem
 
 
 def test_block_level_argument_errors_need_no_device():

@@ -1,11 +1,15 @@
-"""The stage list of the sampler loops (csrc/sampler_stages.h: step_stages) on the CPU: compiled with the host compiler
-and -fsanitize=address,undefined into a stand-alone program (tests/sampler_stages_main.cpp), run for both solvers, and
-compared EXACTLY with the same quantities computed here:
+"""The stage list of the sampler loops (csrc/sampler_stages.h: step_stages, and the loops' one walk over it,
+for_each_stage) on the CPU: compiled with the host compiler and -fsanitize=address,undefined into a stand-alone program
+(tests/sampler_stages_main.cpp), run for both solvers, and compared EXACTLY with the same quantities computed here:
 
   Euler:    row i,           t = (step_begin + i) / num_steps,        dts = float(1 / num_steps)
   Midpoint: rows 2i, 2i + 1, t = t1 and (step_begin + i + 0.5) / num_steps, dts = float(0.5 / num_steps), float(1 / num_steps)
 
 num_steps in {1, 3, 2048}, step_begin in {0, 1, num_steps - 1}, every i of the range.
+
+The walk visits exactly those stages in that order, a stage's row is its index in the walk -- 0, 1, ..., loop_stages - 1
+-- and loop_stages is their count; a walk whose callback returns nonzero at its third stage returns that value having
+visited exactly three.
 
 A quotient k / num_steps above is formed the way every loop has always formed it, k * (1.0 / num_steps) in float64: that
 product is what the guidance scalars and the `t > 1e-3` test are made of, so it is what "exact" has to mean here.  The
@@ -37,13 +41,27 @@ def stage_lines(tmp_path_factory):
     args = [str(v) for case in CASES for v in case]
     out = subprocess.run([exe] + args, check=True, capture_output=True, text=True)
     assert "Sanitizer" not in out.stderr and "runtime error" not in out.stderr, out.stderr
-    table = {}
+    table, walks, counts, early = {}, {}, {}, []
+
+    def stage(f):
+        return (int(f[0]), float.fromhex(f[1]), float.fromhex(f[2]), int(f[3]), int(f[4]))
     for line in out.stdout.splitlines():
-        f = line.split()
-        key = tuple(int(v) for v in f[:5])
-        assert key not in table
-        table[key] = (int(f[5]), float.fromhex(f[6]), float.fromhex(f[7]), int(f[8]), int(f[9]))
-    return table
+        kind, *f = line.split()
+        if kind == "S":  # step_stages: (solver, n, b, i, k) -> stage
+            key = tuple(int(v) for v in f[:5])
+            assert key not in table
+            table[key] = stage(f[5:])
+        elif kind == "W":  # for_each_stage: (solver, n, b) -> its visits, in order
+            visits = walks.setdefault(tuple(int(v) for v in f[:3]), [])
+            assert int(f[3]) == len(visits)
+            visits.append(stage(f[4:]))
+        elif kind == "C":  # (solver, n, b) -> (visits, loop_stages, return value)
+            counts[tuple(int(v) for v in f[:3])] = tuple(int(v) for v in f[3:])
+        else:
+            assert kind == "E", line
+            early.append(tuple(int(v) for v in f))
+    assert early == [(3, 7)]  # stopped at the third of six stages, and returned what the callback returned
+    return table, walks, counts
 
 
 def f32(v):
@@ -62,5 +80,11 @@ def test_stage_list_is_the_loops_formulas_exactly(stage_lines, solver, n, b):
         else:
             want[(solver, n, b, i, 0)] = (2 * i, t1, f32(0.5 / n), 0, 1)
             want[(solver, n, b, i, 1)] = (2 * i + 1, t2, f32(1 / n), 1, 0)
-    got = {k: v for k, v in stage_lines.items() if k[:3] == (solver, n, b)}
+    table, walks, counts = stage_lines
+    got = {k: v for k, v in table.items() if k[:3] == (solver, n, b)}
     assert len(want) == (1 + solver) * len(steps) and got == want
+    # the walk: the same stages in (i, k) order, row = index, loop_stages = their count, 0 returned at the end
+    walk = walks.get((solver, n, b), [])
+    assert walk == [want[k] for k in sorted(want)]
+    assert [g[0] for g in walk] == list(range(len(walk)))
+    assert counts[(solver, n, b)] == (len(walk), len(walk), 0)
