@@ -141,7 +141,7 @@ struct ConvArgs {
   int ep_nosilu;     // 1: store ep_scale * acc + ep_shift itself (the gradient path keeps the pre-activation)
   float* out;        // NHWC [B][H][W][Cout]
   float* stats_out;  // [B][nparts][Cout][2] or null
-  // Producer-side GroupNorm finalize (conv_mfma_bx3.hip): when fin_ab is set, the LAST wave to deliver
+  // Producer-side GroupNorm finalize (rgfm_device.h: fin_arrive): when fin_ab is set, the LAST wave to deliver
   // statistics of a sample (arrival counter) computes the scale/shift of the norm that consumes this
   // output -- cat(this output, fin_stats1's tensor) -- instead of a separate gn_finalize launch.
   float* fin_ab;             // [B][Cout + fin_C1][2] or null
@@ -166,6 +166,12 @@ inline int conv_halo_px(const ConvArgs& a) { return a.g.spt * (a.g.th + 2) * (a.
 // output channels per block of the packed split-plane weight images (bf16x3 and two-plane fp16 alike) = channels one
 // workgroup covers: 128 when Cout % 128 == 0 (two 64-channel groups), else 64 or 32
 inline int conv_block_channels(int Cout) { return Cout % 128 == 0 ? 128 : (Cout % 64 == 0 ? 64 : 32); }
+// ConvArgs::fin_expected: waves that arrive per sample in the producer-side finalize (rgfm_device.h: fin_arrive), the
+// same for every conv_mfma* kernel -- one per 64-pixel segment and 4-wave channel group (and CONV_T2 parity class)
+inline int conv_fin_expected(const ConvArgs& a, int mode) {
+  const int groups = a.Cout / (32 * ((a.Cout % 64 == 0) ? 2 : 1));  // 4-wave groups along the channels
+  return (a.g.spt == 1 ? 4 * a.g.tps : 1) * groups * (mode == CONV_T2 ? 4 : 1);
+}
 // raises a kernel's dynamic-LDS limit (the default is 64 KB); returns the hipError_t as an int, 0 = success
 template <class Kernel>
 inline int raise_lds_limit(Kernel* kernel, int bytes) {
@@ -263,8 +269,6 @@ struct ConvTuning {
   bool f32_simple = false; // RGFM_CONV_SIMPLE set: conv_mfma.hip's non-prefetching kernel wherever it exists (debug)
 };
 inline ConvTuning g_conv_tuning;
-
-int conv_fin_expected(const ConvArgs& a, int mode);  // arrivals per sample for ConvArgs::fin_expected (all conv_mfma* kernels)
 
 // conv_mfma.hip: exact fp32 MFMA, every shape
 int conv_mfma_init();
