@@ -114,6 +114,10 @@ int rgfm_unet_p_handovers(const rgfm_unet* h, int* blocks);
 /* Debug / test hook: how many convs of the handle's LATEST network walk were described for the Winograd F(2x2, 3x3) kernel
  * (conv_mfma_hx2w.hip; opt-in: RGFM_WINO=1). */
 int rgfm_unet_wino_convs(const rgfm_unet* h, int* convs);
+/* Debug / test hook: how many convs of the handle's LATEST network walk ran on the Upsample kernel that computes all four
+ * parity classes from one staged input tile (conv_mfma_hx2u.hip; RGFM_HX2U=0 switches it off).  They count under route
+ * RGFM_ROUTE_HX2P and in slot RGFM_ROUTE_T2 of rgfm_unet_conv_routes, as the launches they replace. */
+int rgfm_unet_up_merged(const rgfm_unet* h, int* convs);
 /* Debug / test hook: conv launches of the handle's LATEST network walk per kernel route (the dispatch of
  * launch_conv, csrc/rgfm_host.h), plus the launches that ran as the four parity classes of an Upsample (CONV_T2,
  * whichever route took them).  counts[i] for i < min(n, RGFM_ROUTE_SLOTS); the input / output convs are not counted. */

@@ -549,6 +549,12 @@ class UNetEngine(_VelocityEngine):
         _lib.check(_lib.lib().rgfm_unet_conv_routes(self.handle(device), counts, len(counts)))
         return dict(zip(_lib.ROUTES + ("t2",), counts))
 
+    def up_merged(self, device):
+        """Convs of the handle's latest walk that ran on the merged-parity-class Upsample kernel (rgfm_unet_up_merged)."""
+        n = ctypes.c_int(0)
+        _lib.check(_lib.lib().rgfm_unet_up_merged(self.handle(device), ctypes.byref(n)))
+        return n.value
+
     def forward_trace(self, x, t):
         """Forward in trace mode; returns (out, [activation tensors, NCHW])."""
         dev = x.device

@@ -62,6 +62,7 @@ SIGNATURES = {
     "rgfm_unet_set_trace": (c_int, [c_void_p, c_int]),
     "rgfm_unet_p_handovers": (c_int, [c_void_p, P(c_int)]),
     "rgfm_unet_wino_convs": (c_int, [c_void_p, P(c_int)]),
+    "rgfm_unet_up_merged": (c_int, [c_void_p, P(c_int)]),
     "rgfm_unet_conv_routes": (c_int, [c_void_p, P(c_int), c_int]),
     "rgfm_unet_time_embedding": (c_int, [c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_size_t, c_void_p]),
     "rgfm_unet_num_activations": (c_int, [c_void_p, P(c_int)]),

@@ -183,6 +183,11 @@ extern "C" int rgfm_unet_wino_convs(const rgfm_unet* h, int* convs) {
   *convs = h->wino_convs;
   return RGFM_OK;
 }
+extern "C" int rgfm_unet_up_merged(const rgfm_unet* h, int* convs) {
+  if (!h || !convs) return fail(RGFM_EINVAL, "null argument");
+  *convs = h->up_merged;
+  return RGFM_OK;
+}
 extern "C" int rgfm_unet_conv_routes(const rgfm_unet* h, int* counts, int n) {
   if (!h || !counts || n < 0) return fail(RGFM_EINVAL, "null argument or negative count");
   for (int i = 0; i < n && i < RGFM_ROUTE_SLOTS; ++i) counts[i] = h->routes[i];

@@ -193,7 +193,8 @@ inline bool on_gfx950() {
 //   RGFM_GN=table    every GroupNorm finalized into a scale/shift array instead of the consumer-side prologue;
 //   RGFM_HX2P=0, RGFM_HX2Q=0, RGFM_HX2S=0, RGFM_HX2C=0, RGFM_HX2D=0, RGFM_GRAPH=1: A/B switches of the pipelined fp16
 //               kernel, its four-waves-per-SIMD version, the stride-2 kernel, the 8x8-level kernel, the P-format hand-over
-//               between a ResBlock's two convs (conv_mfma_hx2d.hip) and the hipGraph replay.
+//               between a ResBlock's two convs (conv_mfma_hx2d.hip) and the hipGraph replay;
+//   RGFM_HX2U=0      the Upsample convs on conv_mfma_hx2p_kernel<*, CONV_T2, *>, a workgroup per parity class (A/B switch, bit-identical).
 enum { CONV_ARITH_HX2 = 0, CONV_ARITH_BX3 = 1, CONV_ARITH_F32 = 2 };
 struct Modes {
   int conv = CONV_ARITH_HX2;
@@ -206,6 +207,7 @@ struct Modes {
   bool wino = false;      // RGFM_WINO=1: the Winograd form of the long-K stride-1 convs (conv_mfma_hx2w.hip) -- opt-in: faster per
                           // layer in isolation at 32x32, slower on the whole bench
   bool up_t2 = true;      // RGFM_UP_T2=0: the Upsample convs as nine taps over the upsampled raster instead of four parity classes (A/B switch)
+  bool up_merged = true;  // RGFM_HX2U=0: the parity-class Upsample convs on conv_mfma_hx2p_kernel instead of conv_mfma_hx2u_kernel (A/B switch, bit-identical)
   bool rev_hx2 = true;    // RGFM_REV_HX2=0: the reverse convs of the gradient-guided sampler on the exact fp32 MFMA (A/B switch)
   bool prephase = true;   // RGFM_PREPHASE_PRIO=0: the two-net unguided entry (rgfm_sample_two) with its earlier schedule -- one chain
                           // enqueued after the other, unpaced -- instead of step by step with the lighter chain paced (A/B switch)
@@ -239,6 +241,8 @@ inline void refresh_modes() {
   m.wino = e && e[0] == '1';
   e = getenv("RGFM_UP_T2");
   m.up_t2 = !(e && e[0] == '0');
+  e = getenv("RGFM_HX2U");
+  m.up_merged = !(e && e[0] == '0');
   e = getenv("RGFM_REV_HX2");
   m.rev_hx2 = !(e && e[0] == '0');
   e = getenv("RGFM_GRAPH");
@@ -248,6 +252,8 @@ inline void refresh_modes() {
   g_modes = m;
   e = getenv("RGFM_WINO_W32");
   g_conv_tuning.wino_w32 = e ? atoi(e) : 0;
+  e = getenv("RGFM_HX2U_WGS");
+  g_conv_tuning.hx2u_wgs_env = e ? atoi(e) : 0;
   g_conv_tuning.s2_f32 = getenv("RGFM_S2_F32") != nullptr;
   g_conv_tuning.f32_simple = getenv("RGFM_CONV_SIMPLE") != nullptr;
 }
@@ -299,11 +305,13 @@ inline int ensure_init() {
   if (!d.init) {
     int rc = guid_apply_init();
     for (const ConvKernel& k : CONV_KERNELS) rc |= k.init();
+    rc |= conv_hx2u_init();  // (a cut of route hx2p: launch_conv)
     if (rc != 0) return fail(RGFM_EHIP, "hipFuncSetAttribute(MaxDynamicSharedMemorySize) failed");
     hipDeviceProp_t p;
     if (hipGetDeviceProperties(&p, dev) == hipSuccess) d.num_cus = p.multiProcessorCount;
     const char* e = getenv("RGFM_HX2P_HALF");
     g_conv_tuning.hx2p_half = e ? atoi(e) : d.num_cus;  // launches with fewer 128-channel workgroups than CUs take 64-channel workgroups
+    g_conv_tuning.hx2u_wgs = d.num_cus;                 // a tile-walking workgroup per CU (conv_mfma_hx2u.hip)
     HIP_TRY(hipStreamCreateWithFlags(&d.side, hipStreamNonBlocking));
     HIP_TRY(hipMalloc(&d.zeros, 256));
     HIP_TRY(hipMemset(d.zeros, 0, 256));
@@ -360,11 +368,18 @@ inline bool launch_conv_on(int route, const ConvArgs& c, int mode, hipStream_t s
 }
 
 // routes: the handle's per-route launch counts (RGFM_ROUTE_SLOTS entries), or null
-inline void launch_conv(const ConvArgs& c, int mode, hipStream_t s, int* routes = nullptr) {
+// up_merged: the handle's count of launches that took conv_mfma_hx2u_kernel, or null.  That kernel is a cut of route hx2p
+// (an Upsample's parity classes from one staged halo), chosen by layer shape only: it counts as hx2p in `routes`.
+inline void launch_conv(const ConvArgs& c, int mode, hipStream_t s, int* routes = nullptr, int* up_merged = nullptr) {
   const int route = conv_route(c, mode);
   if (routes) {
     routes[route] += 1;
     if (mode == CONV_T2) routes[RGFM_ROUTE_T2] += 1;
+  }
+  if (route == RGFM_ROUTE_HX2P && g_modes.up_merged && conv_hx2u_supported(c, mode)) {
+    if (up_merged) *up_merged += 1;
+    if (!launch_conv_hx2u(c, mode, s)) fail(RGFM_EINVAL, "no hx2u instantiation for a %d x %d raster", c.g.H, c.g.W);
+    return;
   }
   launch_conv_on(route, c, mode, s);
 }
@@ -480,6 +495,7 @@ struct rgfm_unet : WeightStore, UNetPlan {  // (the plan: unet_plan.h; its `layo
   int nlin = 0;
   bool trace = false;
   int wino_convs = 0;   // convs of the latest walk described for the Winograd kernel (rgfm_unet_wino_convs)
+  int up_merged = 0;    // convs of the latest walk that ran on conv_mfma_hx2u_kernel (rgfm_unet_up_merged)
   int p_handovers = 0;  // ResBlocks of the latest walk whose conv1 -> conv2 hand-over took the P format (rgfm_unet_p_handovers)
   int routes[RGFM_ROUTE_SLOTS] = {};  // conv launches of the latest walk per route, + CONV_T2 launches (rgfm_unet_conv_routes)
   struct Act {
@@ -550,11 +566,11 @@ struct PendingConv {
   double flops = 0.0;
 };
 
-inline void flush_conv(PendingConv& p, hipStream_t s, int* routes = nullptr) {
+inline void flush_conv(PendingConv& p, hipStream_t s, int* routes = nullptr, int* up_merged = nullptr) {
   if (!p.valid) return;
   p.valid = false;
   ProfScope ps(RGFM_KCLASS_CONV_MFMA, p.flops, s);
-  launch_conv(p.c, p.mode, s, routes);
+  launch_conv(p.c, p.mode, s, routes, up_merged);
 }
 
 // true when `p` can take the finalize of cat(its output, partner) itself
@@ -617,7 +633,7 @@ struct UNetRun {
     if (dry) return ab;
     const bool fused = try_fuse_finalize(pend, a.data, b ? b->stats : nullptr, b ? b->C : 0, h->params + gamma,
                                          h->params + beta, ab, fin_counter);
-    flush_conv(pend, s, h->routes);
+    flush_conv(pend, s, h->routes, &h->up_merged);
     if (fused) return ab;
     GnFinalizeArgs f{};
     f.stats0 = a.stats, f.stats1 = b ? b->stats : nullptr;
@@ -692,7 +708,7 @@ struct UNetRun {
                            h->params + norm->beta))
         c.ab = finalize(a, b, norm->gamma, norm->beta, ab_buf);  // (may attach itself to the pending producer)
     }
-    flush_conv(pend, s, h->routes);
+    flush_conv(pend, s, h->routes, &h->up_merged);
     if (conv_route(c, mode) == RGFM_ROUTE_HX2W) h->wino_convs += 1;  // (as described: a finalize or pout attached later moves it)
     pend.valid = true, pend.c = c, pend.mode = mode;
     pend.flops = conv_flops(B, So * So, w.cout, kprod);
@@ -733,7 +749,7 @@ struct UNetRun {
     const rgfm_unet_desc& d = h->d;
     ModeScope mode_scope(h->conv_mode);
     if (!dry && h->trace) h->acts.clear();
-    if (!dry) h->p_handovers = 0, h->wino_convs = 0, std::fill(h->routes, h->routes + RGFM_ROUTE_SLOTS, 0);
+    if (!dry) h->p_handovers = 0, h->wino_convs = 0, h->up_merged = 0, std::fill(h->routes, h->routes + RGFM_ROUTE_SLOTS, 0);
     std::vector<Tensor> T(h->tensors.size());  // the maps of this run, by the plan's tensor ids
     for (const UOp& o : h->ops) {
       switch (o.kind) {
@@ -769,7 +785,7 @@ struct UNetRun {
           const Tensor& cur = T[o.in0];
           float* ab = finalize(cur, nullptr, h->onw, h->onb);
           if (dry) break;
-          flush_conv(pend, s, h->routes);
+          flush_conv(pend, s, h->routes, &h->up_merged);
           ConvOutArgs co{};
           co.in = cur.data, co.ab = ab, co.w = h->packed + h->ocw_pk, co.bias = h->params + h->ocb;
           co.v_out = v_out, co.x_state = x_state, co.dt = dt, co.B = B, co.Cin = cur.C;

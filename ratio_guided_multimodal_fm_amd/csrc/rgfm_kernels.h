@@ -260,6 +260,9 @@ struct ConvTuning {
   int hx2q_cut = 0;        // kbench: force the workgroup cut, 10 NG + NT (0: hx2q_cut)
   int hx2q_all = 0;        // kbench: 1 = every supported shape, not only those where it is the faster kernel
   int hx2s_on = 1;         // conv_mfma_hx2s.hip: 0 = never (Modes::s2 is the per-call switch)
+  int hx2u_wgs = 256;      // conv_mfma_hx2u.hip: workgroups a launch is cut into at most, each walking its share of the tiles: the
+                           // device's CU count (one workgroup fills a CU)
+  int hx2u_wgs_env = 0;    // RGFM_HX2U_WGS=n: that number instead (> 0; A/B of the tile walk, and how a test reaches it with few rows)
   int hx2c_on = 1;         // conv_mfma_hx2c.hip: 0 = never (Modes::c8 is the per-call switch)
   int hx2c_all = 0;        // kbench: 1 = every supported shape, also the fused-skip layers where hx2p is faster
   int hx2d_cut = 3;        // conv_mfma_hx2d.hip: 0 off, 1 the eight-wave kernel everywhere, 2 the four-wave kernel everywhere,
@@ -312,6 +315,12 @@ bool launch_conv_hx2q(const ConvArgs& a, int mode, hipStream_t s);
 bool conv_hx2s_supported(const ConvArgs& a, int mode);
 int conv_hx2s_init();
 bool launch_conv_hx2s(const ConvArgs& a, int mode, hipStream_t s);
+
+// conv_mfma_hx2u.hip: the Upsample convs (CONV_T2 over a 16x16 / 8x8 raster, raw input) with one staged halo for all four
+// parity classes -- a cut of route RGFM_ROUTE_HX2P (launch_conv, rgfm_host.h), not a route of its own; bit-identical results
+bool conv_hx2u_supported(const ConvArgs& a, int mode);
+int conv_hx2u_init();
+bool launch_conv_hx2u(const ConvArgs& a, int mode, hipStream_t s);
 
 // conv_mfma_hx2c.hip: the stride-1 convs of the 8x8 level, one barrier per chunk (cut for the workgroup's serial chain)
 bool conv_hx2c_supported(const ConvArgs& a, int mode);

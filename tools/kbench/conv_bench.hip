@@ -1,6 +1,8 @@
 // Single-layer benchmark of the conv kernels (development tool; not part of the library).
-//   conv_bench <S> <Cin> <Cout> [mode 0|1|2] [res 0|1|2] [B] [which: bx3|f32|hx2|hx2p|hx2q|hx2s|hx2c]
+//   conv_bench <S> <Cin> <Cout> [mode 0|1|2|3] [res 0|1|2] [B] [which: bx3|f32|hx2|hx2p|hx2q|hx2s|hx2c|hx2u]
 //   (mode 1: the stride-2 conv of a Downsample -- S is the OUTPUT size, the input is raw: hx2 or hx2s)
+//   (mode 3: an Upsample conv as ConvTranspose2d(4, 2, 1) parity classes -- S is the OUTPUT size, the input is raw: f32, hx2,
+//    hx2p or hx2u; hx2u also compares its output and statistics with hx2p's bit for bit)
 // Every run also checks the selected kernel against the exact-fp32 MFMA kernel on the same data.
 // Builds one ConvArgs with random NHWC input / packed weights, launches it 20x, prints us and
 // fp32-equivalent TFLOP/s; with -DRGFM_BX3_PROF also the per-phase cycle counts of the bx3w kernel.
@@ -24,6 +26,7 @@
 #include "../../ratio_guided_multimodal_fm_amd/csrc/conv_mfma_hx2q.hip"
 #endif
 #include "../../ratio_guided_multimodal_fm_amd/csrc/conv_mfma_hx2s.hip"
+#include "../../ratio_guided_multimodal_fm_amd/csrc/conv_mfma_hx2u.hip"
 #include "../../ratio_guided_multimodal_fm_amd/csrc/conv_mfma_hx2c.hip"
 #include "../../ratio_guided_multimodal_fm_amd/csrc/conv_mfma_hx2d.hip"
 #include "../../ratio_guided_multimodal_fm_amd/csrc/conv_mfma_hx2w.hip"
@@ -76,11 +79,14 @@ int main(int argc, char** argv) {
   const bool hx2c = argc > 7 && strcmp(argv[7], "hx2c") == 0;
   const bool hx2d = argc > 7 && strcmp(argv[7], "hx2d") == 0;
   const bool hx2w = argc > 7 && strcmp(argv[7], "hx2w") == 0;  // Winograd F(2x2, 3x3) on the two-plane arithmetic
-  const int Sin = mode == CONV_UP2 ? S / 2 : (mode == CONV_S2 ? 2 * S : S);
+  const bool hx2u = argc > 7 && strcmp(argv[7], "hx2u") == 0;  // an Upsample's four parity classes from one staged halo
+  const bool t2 = mode == CONV_T2;
+  const int Sin = (mode == CONV_UP2 || t2) ? S / 2 : (mode == CONV_S2 ? 2 * S : S);
   const int nt = Cout % 64 == 0 ? 2 : 1;
   CK(hipSetDevice(0));
   for (const ConvKernel& k : CONV_KERNELS)
     if (k.init() != 0) { printf("%s: raising the LDS limit failed\n", k.name); return 1; }
+  if (conv_hx2u_init() != 0) { printf("hx2u: raising the LDS limit failed\n"); return 1; }
   ConvTuning& tune = g_conv_tuning;  // (the library's defaults, then this tool's environment)
   if (getenv("RGFM_HX2D")) tune.hx2d_cut = atoi(getenv("RGFM_HX2D"));  // 1: eight waves, 2: four waves x two workgroups per CU
   tune.hx2c_all = 1;
@@ -90,6 +96,7 @@ int main(int argc, char** argv) {
   if (getenv("RGFM_HX2Q_CUT")) tune.hx2q_cut = atoi(getenv("RGFM_HX2Q_CUT"));
   if (getenv("RGFM_HX2P_W4")) tune.hx2p_w4 = atoi(getenv("RGFM_HX2P_W4"));
   if (getenv("RGFM_HX2P_HALF")) tune.hx2p_half = atoi(getenv("RGFM_HX2P_HALF"));
+  if (getenv("RGFM_HX2U_WGS")) tune.hx2u_wgs_env = atoi(getenv("RGFM_HX2U_WGS"));  // hx2u: workgroups along the tiles (>= the tiles: one tile each)
   tune.f32_simple = getenv("RGFM_CONV_SIMPLE") != nullptr;
 #ifdef RGFM_KB_SCAFFOLD
   if (getenv("RGFM_HX2P_CHUNK")) conv_hx2p_set_chunk(atoi(getenv("RGFM_HX2P_CHUNK")));
@@ -128,20 +135,24 @@ int main(int argc, char** argv) {
     launch_gn_finalize(f, 0);
   }
   a.ab = abbuf;
-  float* w = dev_rand((size_t)Cout * Cin * 9, 0.05f, 3);
+  const int wtaps = t2 ? 16 : 9;  // (CONV_T2: w is the ConvTranspose2d weight [Cin][Cout][4][4])
+  float* w = dev_rand((size_t)Cout * Cin * wtaps, 0.05f, 3);
   float* wp;
-  hipMalloc(&wp, (size_t)Cout * Cin * 9 * 4);
-  pack_plain<<<256, 256>>>(w, wp, Cout, Cin, 9, 32 * nt);
+  hipMalloc(&wp, (size_t)Cout * Cin * wtaps * 4);
+  if (t2) launch_pack_deconv(w, wp, Cin, Cout, nt, 0);
+  else pack_plain<<<256, 256>>>(w, wp, Cout, Cin, 9, 32 * nt);
   void* w3;
-  hipMalloc(&w3, (size_t)Cout * Cin * 9 * 6);
-  launch_pack_conv_bx3(w, w3, Cout, Cin, 9, 0);
+  hipMalloc(&w3, (size_t)Cout * Cin * wtaps * 6);
+  if (t2) launch_pack_deconv_bx3(w, w3, Cin, Cout, 0);
+  else launch_pack_conv_bx3(w, w3, Cout, Cin, 9, 0);
   a.wpk = wp, a.wpk3 = w3;
   void* wh;
-  hipMalloc(&wh, (size_t)Cout * Cin * 9 * 4);
+  hipMalloc(&wh, (size_t)Cout * Cin * wtaps * 4);
   float* hq;
   hipMalloc(&hq, 8 * sizeof(float));
-  launch_pack_conv_hx2(w, wh, hq, Cout, Cin, 9, mode == CONV_S2 ? CONV_S2 : CONV_S1, 0);
+  launch_pack_conv_hx2(w, wh, hq, Cout, Cin, wtaps, t2 ? CONV_T2 : (mode == CONV_S2 ? CONV_S2 : CONV_S1), 0);
   a.wpkh = wh, a.hq = hq;
+  if (t2) a.ab = nullptr;  // (an Upsample has no norm in front: raw input)
   if (mode == CONV_S2) {  // the plain nine-tap image once more (conv_mfma_hx2s.hip)
     void* wh9;
     hipMalloc(&wh9, (size_t)Cout * Cin * 9 * 4);
@@ -155,7 +166,7 @@ int main(int argc, char** argv) {
   a.range_flag = flag;
   a.bias = dev_rand(Cout, 0.1f, 4);
   a.temb = dev_rand(Cout, 0.1f, 5), a.temb_stride = Cout;
-  if (mode == CONV_S2) a.temb = nullptr;  // (a Downsample has no time term)
+  if (mode == CONV_S2 || t2) a.temb = nullptr;  // (a Downsample / Upsample has no time term)
   a.res_mode = res;
   if (getenv("RGFM_KB_SC")) a.small_check = atoi(getenv("RGFM_KB_SC"));  // the output's low-range check (ConvArgs::small_check)
   int skipk = 0;
@@ -180,15 +191,17 @@ int main(int argc, char** argv) {
   float* out;
   hipMalloc(&out, (size_t)B * S * S * Cout * 4);
   a.out = out;
-  a.g = make_geom(S, S);
+  a.g = t2 ? make_geom(Sin, Sin) : make_geom(S, S);  // (CONV_T2: the tiles walk the INPUT raster)
+  const int nparts_out = (t2 ? 4 : 1) * a.g.nparts;  // (CONV_T2: four parity classes x the input raster's parts)
   float* st;
-  hipMalloc(&st, (size_t)B * a.g.nparts * Cout * 2 * 4);
+  hipMalloc(&st, (size_t)B * nparts_out * Cout * 2 * 4);
   a.stats_out = st;
   a.B = B, a.Cout = Cout;
   a.halo_px = a.g.spt * (a.g.th + 2) * (a.g.W + 2);
-  const double flops = 2.0 * B * S * S * (double)Cout * (9 * Cin + skipk);
+  const double flops = 2.0 * B * S * S * (double)Cout * ((t2 ? 4 : 9) * Cin + skipk);  // (executed products)
   ConvArgs ap = a;  // the pipelined kernel takes the norm itself
   ap.ab = nullptr, ap.gn_stats0 = gstats, ap.gn_gamma = ggamma, ap.gn_beta = gbeta, ap.gn_nparts0 = gin.nparts, ap.gn_g = gin;
+  if (t2) ap = a;  // (raw input)
   ConvArgs ad = a;  // conv_mfma_hx2d_kernel: the same input, normalised + activated + split beforehand (P format)
   if (hx2d) {
     void* pbuf;
@@ -224,6 +237,7 @@ int main(int argc, char** argv) {
   if (hx2p && !conv_hx2p_supported(ap, mode)) { printf("hx2p: unsupported shape\n"); return 1; }
   if (hx2q && !conv_hx2q_supported(ap, mode)) { printf("hx2q: unsupported shape\n"); return 1; }
   if (hx2s && !conv_hx2s_supported(a, mode)) { printf("hx2s: unsupported shape\n"); return 1; }
+  if (hx2u && !conv_hx2u_supported(a, mode)) { printf("hx2u: unsupported shape\n"); return 1; }
   if (hx2c && !conv_hx2c_supported(ap, mode)) { printf("hx2c: unsupported shape\n"); return 1; }
   auto launch = [&]() {
     bool ok;
@@ -232,6 +246,7 @@ int main(int argc, char** argv) {
     else if (hx2p) ok = launch_conv_hx2p(ap, mode, 0);
     else if (hx2q) ok = launch_conv_hx2q(ap, mode, 0);
     else if (hx2s) ok = launch_conv_hx2s(a, mode, 0);
+    else if (hx2u) ok = launch_conv_hx2u(a, mode, 0);
     else if (hx2c) ok = launch_conv_hx2c(ap, mode, 0);
     else if (hx2d) ok = launch_conv_hx2d(ad, mode, 0);
 #ifdef RGFM_KB_HX2W4
@@ -242,7 +257,7 @@ int main(int argc, char** argv) {
     if (!ok) printf("no instantiation of the selected kernel for this shape / mode / cut: nothing was launched\n"), exit(1);
   };
   {  // reference: the exact-fp32 MFMA kernel on the same data
-    const size_t no = (size_t)B * S * S * Cout, ns = (size_t)B * a.g.nparts * Cout * 2;
+    const size_t no = (size_t)B * S * S * Cout, ns = (size_t)B * nparts_out * Cout * 2;
     std::vector<float> ref(no), got(no), sref(ns), sgot(ns);
     if (mode == CONV_S2) launch_conv_hx2(a, mode, 0);  // (stride 2: the reference is conv_mfma_hx2_kernel, itself pinned by the library's parity tests)
     else launch_conv_mfma(a, mode, 0);
@@ -269,6 +284,19 @@ int main(int argc, char** argv) {
     unsigned fl = 0;
     hipMemcpy(&fl, flag, 4, hipMemcpyDeviceToHost);
     printf("check vs f32 kernel: max|diff| %.3e (max|ref| %.3f), stats rel diff %.3e, range flag %u\n", emax, vmax, smax, fl);
+    if (hx2u) {  // the kernel it replaces: same bits
+      if (!conv_hx2p_supported(a, mode)) { printf("hx2p: unsupported shape\n"); return 1; }
+      hipMemset(out, 0, no * 4);
+      hipMemset(st, 0, ns * 4);
+      launch_conv_hx2p(a, mode, 0);
+      CK(hipDeviceSynchronize());
+      CK(hipGetLastError());
+      hipMemcpy(ref.data(), out, no * 4, hipMemcpyDeviceToHost);
+      hipMemcpy(sref.data(), st, ns * 4, hipMemcpyDeviceToHost);
+      const bool same = memcmp(ref.data(), got.data(), no * 4) == 0 && memcmp(sref.data(), sgot.data(), ns * 4) == 0;
+      printf("bitwise vs hx2p (output and statistics): %s\n", same ? "equal" : "DIFFERENT");
+      if (!same) return 1;
+    }
   }
 #ifdef RGFM_HX2Q_PROF
   {
@@ -299,7 +327,7 @@ int main(int argc, char** argv) {
   float ms;
   hipEventElapsedTime(&ms, e0, e1);
   const double us = ms * 1e3 / reps;
-  printf("%s S=%d Cin=%d Cout=%d mode=%d res=%d B=%d: %8.1f us  %6.1f TFLOP/s (fp32-equivalent)\n", f32 ? "f32" : (hx2 ? "hx2" : (hx2p ? "hx2p" : (hx2q ? "hx2q" : (hx2s ? "hx2s" : (hx2c ? "hx2c" : (hx2d ? "hx2d" : (hx2w ? "hx2w" : "bx3"))))))), S, Cin,
+  printf("%s S=%d Cin=%d Cout=%d mode=%d res=%d B=%d: %8.1f us  %6.1f TFLOP/s (fp32-equivalent)\n", f32 ? "f32" : (hx2 ? "hx2" : (hx2p ? "hx2p" : (hx2q ? "hx2q" : (hx2s ? "hx2s" : (hx2c ? "hx2c" : (hx2d ? "hx2d" : (hx2w ? "hx2w" : (hx2u ? "hx2u" : "bx3")))))))), S, Cin,
          Cout, mode, res, B, us, flops / us / 1e6);
 #ifdef RGFM_HX2Q_PROF
   if (hx2q) {

@@ -78,9 +78,10 @@ def main():
         by = 4.0 * B * (s_in * s_in * cin + S * S * cout)
         if name.endswith(".conv2"):
             by += 4.0 * B * S * S * (sk if sk else cout)  # 1x1-skip source, or the identity residual
-        # an Upsample conv launched as four parity classes (grid z = 4) EXECUTES 4 / 9 of its algorithmic products: the
-        # TF/s column stays algorithmic, its matrix roofline is that of the executed work (name marked *)
-        t2 = mode == 2 and gz == 4
+        # an Upsample conv launched as four parity classes (grid z = 4, or conv_mfma_hx2u_kernel: all four in one workgroup)
+        # EXECUTES 4 / 9 of its algorithmic products: the TF/s column stays algorithmic, its matrix roofline is
+        # that of the executed work (name marked *)
+        t2 = mode == 2 and (gz == 4 or "conv_mfma_hx2u" in kn)
         if t2:
             name += "*"
         t_m, t_h = fl * (4.0 / 9.0 if t2 else 1.0) / (mf * 1e6), by / (bw * 1e6)
