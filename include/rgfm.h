@@ -881,6 +881,76 @@ int rgfm_guidance_apply_cross_rows(const float* x, const float* y, float* vx, fl
                                    size_t ws_bytes, rgfm_stream_t stream);
 
 /* ------------------------------------------------------------------------
+ * Stochastic sampling: Euler-Maruyama steps in every U-Net sampler loop (added functions only: the ABI version is
+ * unchanged).  For the Gaussian path x_t = (1 - t) x_0 + t x_1, x_0 ~ N(0, I), the score follows from the velocity,
+ * grad log p_t(x) = (t v - x) / (1 - t), and with g(t)^2 = 2 eta (1 - t) the SDE of the ODE's marginals is
+ *     dx = [F + eta (t F - x)] dt + sqrt(2 eta (1 - t)) dW          (no singularity at either end; eta = 0: the ODE)
+ * with F the loop's whole velocity at the stage: the net's (unguided), the MC blend (MC loops), v + gamma grad log r
+ * (gradient loops).
+ *
+ * 1. The step.  Step i of num_steps: dt = 1 / num_steps and t = i dt in double, k = i the GLOBAL step index (not the
+ *    index within the call):
+ *        base = (1 - eta dt) x + sigma_k xi_k          sigma_k = sqrt(2 eta (1 - t) dt)
+ *        x    = base + ((1 + eta t) dt) F(x, t)
+ *    The second line is the loop's fused update as it is: it reads the old state, its base is the new buffer, and
+ *    dts = (float)((1 + eta t) dt), formed in double.  The first line is one kernel over the [batch][D] state of each
+ *    modality, which generates xi itself, with a = (float)(1 - eta dt) and sigma = (float)sigma_k:
+ *    base[e] = fma(a, x[e], sigma xi[e]).  Whether a stage is guided, and t, are unchanged.
+ *
+ * 2. The noise, bit-defined up to logf, sqrtf and sincospif.  xi_k of stream m (0: the loop's first or only state,
+ *    1: the second) is a function of (seed, m, k, e) alone, e the flat element index in [batch][D].  Elements come in
+ *    pairs p = e / 2; with fin the splitmix64 finaliser documented for rgfm_unet_dropout_mask, arithmetic mod 2^64:
+ *        key = fin(seed + 0x9E3779B97F4A7C15 * ((((uint64)m << 32) | k) + 1))
+ *        z   = fin(key  + 0x9E3779B97F4A7C15 * (p + 1))
+ *        u1  = ((z >> 40) + 1) * 2^-24            in (0, 1]
+ *        u2  = ((z >> 8) & 0xFFFFFF) * 2^-24      in [0, 1)
+ *        r   = sqrt(-2 ln u1),   xi[2p] = r cos(2 pi u2),   xi[2p + 1] = r sin(2 pi u2)
+ *    in fp32 (u1, u2 and the argument 2 u2 of sincospif are exact).  So |xi| <= sqrt(48 ln 2) = 5.77; an odd
+ *    batch * D ends on a cosine; a row's noise does not depend on the batch size; and split calls reproduce the bits of
+ *    one call: steps [0, a) then [a, N) equal [0, N).  rgfm_sde_noise (test hook) writes xi[0..n) of (seed,
+ *    stream_id in {0, 1}, k >= 0) to out, stream-ordered.
+ *
+ * 3. Entry points.  rgfm_sample_single_sde is rgfm_sample_single_ode, and rgfm_sample_{pair, pair_cross, cond,
+ *    pair_grad, cond_grad}_sde is its *_gs namesake, with `const rgfm_sde* sde` directly in front of ws.
+ *    sde == NULL or eta == 0: the call IS its namesake -- same launches, same arguments, same graph replay, same
+ *    bits, same workspace.  eta > 0: the workspace is the namesake's query plus rgfm_sde_scratch_bytes (batch, D of the
+ *    first state, D of the second or 0): one [batch][D] buffer per modality, carved behind the loop's own buffers;
+ *    the call runs kernel by kernel (no hipGraph replay).  rgfm_sample_two (the MC pre-phase) has no stochastic twin.
+ *    Errors are returned before anything is enqueued and touch no state: the namesake's own; RGFM_EINVAL for eta < 0 or
+ *    not finite, and for solver == RGFM_SOLVER_MIDPOINT with eta > 0 (a stochastic midpoint rule is out of scope);
+ *    RGFM_ENOMEM for a workspace short of the sum above.
+ * ---------------------------------------------------------------------- */
+typedef struct rgfm_sde { double eta; uint64_t seed; } rgfm_sde;
+int rgfm_sde_scratch_bytes(int batch, int dim_x, int dim_y, size_t* bytes);
+int rgfm_sde_noise(uint64_t seed, int stream_id, int k, size_t n, float* out, rgfm_stream_t stream);
+int rgfm_sample_single_sde(rgfm_unet* h, float* x_inout, int batch, int num_steps, int step_begin, int step_end,
+                           int solver, const rgfm_sde* sde, void* ws, size_t ws_bytes, rgfm_stream_t stream);
+int rgfm_sample_pair_sde(rgfm_unet* hx, rgfm_unet* hy, float* x_inout, float* y_inout, const float* mc_x1,
+                         const float* mc_y1, const float* mc_ratios, int n_mc, int batch, int num_steps, double gamma,
+                         const float* gamma_rows, const double* stage_scale, int n_stage_scale, int step_begin,
+                         int step_end, int solver, float* diag_out, size_t diag_records, const rgfm_sde* sde, void* ws,
+                         size_t ws_bytes, rgfm_stream_t stream);
+int rgfm_sample_pair_cross_sde(rgfm_unet* hx, rgfm_unet* hy, float* x_inout, float* y_inout, const float* mc_x1,
+                               const float* mc_y1, const float* ratio_matrix, int n_mc, int batch, int num_steps,
+                               double gamma, const float* gamma_rows, const double* stage_scale, int n_stage_scale,
+                               int step_begin, int step_end, int solver, float* diag_out, size_t diag_records,
+                               const rgfm_sde* sde, void* ws, size_t ws_bytes, rgfm_stream_t stream);
+int rgfm_sample_cond_sde(rgfm_unet* h, float* s_inout, const float* mc_set, const float* ratios, int n_mc, int batch,
+                         int num_steps, double gamma, const float* gamma_rows, const double* stage_scale,
+                         int n_stage_scale, int step_begin, int step_end, int solver, float* diag_out,
+                         size_t diag_records, const rgfm_sde* sde, void* ws, size_t ws_bytes, rgfm_stream_t stream);
+int rgfm_sample_pair_grad_sde(rgfm_unet* hx, rgfm_unet* hy, rgfm_ratio* hr, float* x_inout, float* y_inout, int batch,
+                              int num_steps, double gamma, const float* gamma_rows, const double* stage_scale,
+                              int n_stage_scale, int step_begin, int step_end, int solver, float* diag_out,
+                              size_t diag_records, const rgfm_sde* sde, void* ws, size_t ws_bytes,
+                              rgfm_stream_t stream);
+int rgfm_sample_cond_grad_sde(rgfm_unet* h_unet, rgfm_ratio* h_ratio, float* s_inout, const float* ctx, int given,
+                              int batch, int num_steps, double gamma, const float* gamma_rows,
+                              const double* stage_scale, int n_stage_scale, int step_begin, int step_end, int solver,
+                              float* diag_out, size_t diag_records, const rgfm_sde* sde, void* ws, size_t ws_bytes,
+                              rgfm_stream_t stream);
+
+/* ------------------------------------------------------------------------
  * Bench support: per-kernel-class device time measured with hipEvents on the
  * launch stream (bench.py's roofline line).  Timing is off by default.
  * ---------------------------------------------------------------------- */
@@ -917,6 +987,10 @@ int rgfm_profile_reserve(int64_t launches);
  *   rgfm_ubench_hbm_copy: float4 copy of `bytes` (>= 256 MiB recommended) in GB/s of read + written bytes. */
 int rgfm_ubench_mfma_f16(double* tflops);
 int rgfm_ubench_hbm_copy(size_t bytes, double* gbps);
+/* The stochastic step's pre-update kernel ("Stochastic sampling", 1.) alone over n floats, 200 launches back to back
+ * between two device events on the null stream (synchronises): GB/s of the 8 bytes per element it moves, and the time
+ * of one launch in microseconds.  Added function only. */
+int rgfm_ubench_sde_pre(size_t n, double* gbps, double* us_per_launch);
 
 /* Conv arithmetic of ONE handle (see "arithmetic" above); RGFM_CONV_DEFAULT follows the RGFM_CONV environment
  * variable (hx2 | bx3 | f32, read once per API call; unset = hx2).  A handle setting, not process state: two host

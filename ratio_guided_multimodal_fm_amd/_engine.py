@@ -6,6 +6,7 @@ inside librgfm_hip.so.
 """
 import collections
 import ctypes
+import math
 import os
 import weakref
 
@@ -329,19 +330,24 @@ class _TrainFn(torch.autograd.Function):
 
 # The exports of a sampler loop, one row each: the entry point and its workspace query, their *_diag pair, the *_gs entry
 # point (a strength per row / per stage; no query of its own), and for the U-Net pair the cross-pairing entry points (one
-# query for calls with and without records).  None: the loop has no such export.  _run_loop picks from the row.
-_Loop = collections.namedtuple("_Loop", "fn ws diag diag_ws gs cross cross_ws cross_gs", defaults=(None,) * 6)
-_SINGLE = _Loop("rgfm_sample_single_ode", "rgfm_sample_single_ode_workspace_bytes")
+# query for calls with and without records), and the *_sde entry points (the stochastic step; workspace: the query the
+# call would use without it plus rgfm_sde_scratch_bytes).  None: the loop has no such export.  _run_loop picks from the row.
+_Loop = collections.namedtuple("_Loop", "fn ws diag diag_ws gs cross cross_ws cross_gs sde cross_sde", defaults=(None,) * 8)
+_SINGLE = _Loop("rgfm_sample_single_ode", "rgfm_sample_single_ode_workspace_bytes", sde="rgfm_sample_single_sde")
 _TWO = _Loop("rgfm_sample_two", "rgfm_sample_two_workspace_bytes")
 _PAIR = _Loop("rgfm_sample_pair_ode", "rgfm_sample_pair_ode_workspace_bytes",
               "rgfm_sample_pair_diag", "rgfm_sample_pair_diag_workspace_bytes", "rgfm_sample_pair_gs",
-              "rgfm_sample_pair_cross", "rgfm_sample_pair_cross_workspace_bytes", "rgfm_sample_pair_cross_gs")
+              "rgfm_sample_pair_cross", "rgfm_sample_pair_cross_workspace_bytes", "rgfm_sample_pair_cross_gs",
+              "rgfm_sample_pair_sde", "rgfm_sample_pair_cross_sde")
 _PAIR_GRAD = _Loop("rgfm_sample_pair_grad_ode", "rgfm_sample_pair_grad_ode_workspace_bytes",
-                   "rgfm_sample_pair_grad_diag", "rgfm_sample_pair_grad_diag_workspace_bytes", "rgfm_sample_pair_grad_gs")
+                   "rgfm_sample_pair_grad_diag", "rgfm_sample_pair_grad_diag_workspace_bytes", "rgfm_sample_pair_grad_gs",
+                   sde="rgfm_sample_pair_grad_sde")
 _COND = _Loop("rgfm_sample_cond_ode", "rgfm_sample_cond_ode_workspace_bytes",
-              "rgfm_sample_cond_diag", "rgfm_sample_cond_diag_workspace_bytes", "rgfm_sample_cond_gs")
+              "rgfm_sample_cond_diag", "rgfm_sample_cond_diag_workspace_bytes", "rgfm_sample_cond_gs",
+              sde="rgfm_sample_cond_sde")
 _COND_GRAD = _Loop("rgfm_sample_cond_grad_ode", "rgfm_sample_cond_grad_ode_workspace_bytes",
-                   "rgfm_sample_cond_grad_diag", "rgfm_sample_cond_grad_diag_workspace_bytes", "rgfm_sample_cond_grad_gs")
+                   "rgfm_sample_cond_grad_diag", "rgfm_sample_cond_grad_diag_workspace_bytes", "rgfm_sample_cond_grad_gs",
+                   sde="rgfm_sample_cond_grad_sde")
 _FM_SINGLE = _Loop("rgfm_fmnet_sample_single", "rgfm_fmnet_workspace_bytes")
 _FM_PAIR = _Loop("rgfm_fmnet_sample_pair", "rgfm_fmnet_sample_pair_workspace_bytes",
                  "rgfm_fmnet_sample_pair_diag", "rgfm_fmnet_sample_pair_diag_workspace_bytes")
@@ -1079,14 +1085,53 @@ def _check_strength(gamma_rows, stage_scale, batch, num_steps, steps, sid, model
     return gamma_rows, arr
 
 
-def _run_loop(loop, ws_args, args, steps, sid, dev, ws=None, diag=None, cross=False, strength=None):
+def draw_sde_seed():
+    """The noise seed of a stochastic sampler call that names none: one 62-bit integer from torch's CPU default
+    generator (torch.manual_seed fixes it; no device read-back)."""
+    return int(torch.randint(0, 1 << 62, (1,), dtype=torch.int64).item())
+
+
+def check_sde(sde_eta, solver, models):
+    """Argument checks of a stochastic sampler call, before any draw and any device work; returns sde_eta as a float
+    (0.0: off).  sde_eta must be finite and >= 0 (ValueError); sde_eta > 0 needs solver='euler' and U-Net velocity nets
+    (RgfmError)."""
+    eta = float(sde_eta)
+    if not (eta >= 0.0 and math.isfinite(eta)):
+        raise ValueError(f"sde_eta must be finite and >= 0, got {sde_eta!r}")
+    if eta == 0.0:
+        return eta
+    if _lib.solver_id(solver):
+        raise _lib.RgfmError("sde_eta > 0 needs solver='euler': there is no stochastic midpoint rule")
+    for m in models:
+        if not isinstance(m._engine, UNetEngine):
+            raise _lib.RgfmError("stochastic sampling (sde_eta > 0) needs U-Net velocity nets (FlexibleUNet and its "
+                                 f"presets); {type(m).__name__} has the deterministic Euler loop only")
+    return eta
+
+
+def _sde(sde_eta, sde_seed, sid, models, *states):
+    """The stochastic step of a loop call (include/rgfm.h, "Stochastic sampling"), before any device work: None for
+    sde_eta = 0 (the call is then today's), else what _run_loop takes as `sde`.  The checks: check_sde; sde_seed None:
+    draw_sde_seed().  `states`: the loop's state tensors."""
+    eta = check_sde(sde_eta, 'midpoint' if sid else 'euler', models)
+    if eta == 0.0:
+        return None
+    seed = draw_sde_seed() if sde_seed is None else int(sde_seed) % (1 << 64)
+    B = states[0].shape[0]
+    dims = [int(t[0].numel()) if B else 0 for t in states] + [0]
+    return _lib.Sde(eta, seed), B, dims[0], dims[1]
+
+
+def _run_loop(loop, ws_args, args, steps, sid, dev, ws=None, diag=None, cross=False, strength=None, sde=None):
     """One native sampler loop (`loop`: its _Loop row): the size query (*ws_args[, sid]), the workspace (`ws`: a
     _Workspace; default the samplers' shared one), then the entry point (*args, *steps[, sid], workspace, stream).
     `steps`: (step_begin, step_end).  sid None: entry points without a solver argument (the FlowMatchingModel loops).
     `diag`: a records tensor [n_stages, B, RGFM_DIAG_FLOATS] -- the loop's *_diag pair runs and fills it (guided loops
     only).  `cross`: the U-Net pair loop over all pairs of the MC set (one entry point with and without records).
     `strength`: what _check_strength returns -- not None: the loop's *_gs entry point runs (U-Net loops), the *_diag
-    arguments with (gamma_rows, stage_scale, n_stage_scale) behind gamma, in the workspace chosen above."""
+    arguments with (gamma_rows, stage_scale, n_stage_scale) behind gamma, in the workspace chosen above.
+    `sde`: what _sde returns -- not None: the loop's *_sde entry point runs (the *_gs arguments, or the single loop's own,
+    with the rgfm_sde in front of the workspace), in the workspace chosen above plus rgfm_sde_scratch_bytes."""
     L = _lib.lib()
     tail = () if sid is None else (sid,)
     fn, ws_fn, sink = loop.fn, loop.ws, ()
@@ -1107,26 +1152,41 @@ def _run_loop(loop, ws_args, args, steps, sid, dev, ws=None, diag=None, cross=Fa
         args = (*args, _ptr(rows), scale, scale.n if scale is not None else 0)
     if cross or strength is not None:  # (these entry points always take the sink's two arguments)
         sink = sink or (None, 0)
-    nb = ctypes.c_size_t()
+    nb, more = ctypes.c_size_t(), ()
     _lib.check(getattr(L, ws_fn)(*ws_args, *tail, ctypes.byref(nb)))
-    buf = (ws or _sampler_ws).get(nb.value, dev)
-    _lib.check(getattr(L, fn)(*args, int(steps[0]), int(steps[1]), *tail, *sink, _ptr(buf), nb.value, _stream(dev)))
+    nbytes = nb.value
+    if sde is not None:
+        rec, batch, dim_x, dim_y = sde
+        fn = loop.cross_sde if cross else loop.sde
+        if fn is None:
+            raise _lib.RgfmError("this sampler loop has no stochastic step")
+        if loop.gs is not None:  # (the guided loops: the *_gs arguments)
+            if strength is None:
+                args = (*args, None, None, 0)
+            sink = sink or (None, 0)
+        _lib.check(L.rgfm_sde_scratch_bytes(batch, dim_x, dim_y, ctypes.byref(nb)))
+        nbytes, more = nbytes + nb.value, (ctypes.byref(rec),)
+    buf = (ws or _sampler_ws).get(nbytes, dev)
+    _lib.check(getattr(L, fn)(*args, int(steps[0]), int(steps[1]), *tail, *sink, *more, _ptr(buf), nbytes, _stream(dev)))
 
 
 def _solver_arg(engine, sid):
     return sid if isinstance(engine, UNetEngine) else None
 
 
-def sample_single(model, x, num_steps, step_begin=0, step_end=None, solver='euler'):
-    """In-place unguided integration of `x` (rgfm_sample_single; solver='midpoint': rgfm_sample_single_ode)."""
-    _solver(solver, model)
+def sample_single(model, x, num_steps, step_begin=0, step_end=None, solver='euler', sde_eta=0.0, sde_seed=None):
+    """In-place unguided integration of `x` (rgfm_sample_single; solver='midpoint': rgfm_sample_single_ode).
+    `sde_eta` > 0: Euler-Maruyama steps of that strength (rgfm_sample_single_sde; U-Net nets, solver='euler'), the
+    noise seeded by `sde_seed` (None: draw_sde_seed()); 0: the call above, unchanged.  The loops below take the two the
+    same way."""
+    sde = _sde(sde_eta, sde_seed, _solver(solver, model), (model,), x)
     if x.is_cuda and x.shape[0]:
-        return _range_guarded(x.device, [x], lambda: _sample_single(model, x, num_steps, step_begin, step_end, solver),
+        return _range_guarded(x.device, [x], lambda: _sample_single(model, x, num_steps, step_begin, step_end, solver, sde),
                               [model._engine])
-    return _sample_single(model, x, num_steps, step_begin, step_end, solver)
+    return _sample_single(model, x, num_steps, step_begin, step_end, solver, sde)
 
 
-def _sample_single(model, x, num_steps, step_begin=0, step_end=None, solver='euler'):
+def _sample_single(model, x, num_steps, step_begin=0, step_end=None, solver='euler', sde=None):
     sid = _solver(solver, model)
     eng = model._engine
     eng._check_eval(model)
@@ -1141,7 +1201,7 @@ def _sample_single(model, x, num_steps, step_begin=0, step_end=None, solver='eul
     with torch.cuda.device(dev):
         h = eng.handle(dev)
         _run_loop(eng.SINGLE, (h, B), (h, _ptr(x), B, int(num_steps)), (step_begin, step_end),
-                  _solver_arg(eng, sid), dev, ws=eng._ws)
+                  _solver_arg(eng, sid), dev, ws=eng._ws, sde=sde)
     return x
 
 
@@ -1199,7 +1259,7 @@ def sample_two_streams(fm_x, x, fm_y, y, num_steps, solver='euler'):
 
 
 def sample_pair(fm_x, fm_y, x, y, mc_x1, mc_y1, mc_ratios, num_steps, gamma, step_begin=0,
-                step_end=None, solver='euler', diag=None, gamma_rows=None, stage_scale=None):
+                step_end=None, solver='euler', diag=None, gamma_rows=None, stage_scale=None, sde_eta=0.0, sde_seed=None):
     """In-place paired loop with optional MC guidance (rgfm_sample_pair; solver='midpoint': rgfm_sample_pair_ode).
     `diag`: a records tensor [n_stages, B, 8] to fill (rgfm_sample_pair_diag / rgfm_fmnet_sample_pair_diag; the state
     keeps its bits); the other guided loops below take it the same way.
@@ -1215,6 +1275,7 @@ def sample_pair(fm_x, fm_y, x, y, mc_x1, mc_y1, mc_ratios, num_steps, gamma, ste
     sid = _solver(solver, fm_x, fm_y)
     strength = _check_strength(gamma_rows, stage_scale, x.shape[0], num_steps,
                                (step_begin, num_steps if step_end is None else step_end), sid, (fm_x, fm_y))
+    sde = _sde(sde_eta, sde_seed, sid, (fm_x, fm_y), x, y)
     for m in (fm_x, fm_y):
         m._engine._check_eval(m)
     ex = fm_x._engine
@@ -1242,13 +1303,14 @@ def sample_pair(fm_x, fm_y, x, y, mc_x1, mc_y1, mc_ratios, num_steps, gamma, ste
             _run_loop(ex.PAIR, (hx, hy, B, n_mc),
                       (hx, hy, _ptr(x), _ptr(y), _ptr(mc_x1 if n_mc else None), _ptr(mc_y1 if n_mc else None),
                        _ptr(mc_ratios if n_mc else None), n_mc, B, int(num_steps), float(gamma)),
-                      (step_begin, step_end), _solver_arg(ex, sid), dev, diag=diag, cross=cross, strength=strength)
+                      (step_begin, step_end), _solver_arg(ex, sid), dev, diag=diag, cross=cross, strength=strength,
+                      sde=sde)
         return x, y
     return _range_guarded(dev, [x, y], run, [fm_x._engine, fm_y._engine])
 
 
 def sample_pair_grad(fm_x, fm_y, ratio_estimator, x, y, num_steps, gamma, step_begin=0, step_end=None, solver='euler',
-                     diag=None, gamma_rows=None, stage_scale=None):
+                     diag=None, gamma_rows=None, stage_scale=None, sde_eta=0.0, sde_seed=None):
     """In-place paired loop with gradient log-ratio guidance (rgfm_sample_pair_grad; solver='midpoint':
     rgfm_sample_pair_grad_ode)."""
     sid = _lib.solver_id(solver)
@@ -1258,6 +1320,7 @@ def sample_pair_grad(fm_x, fm_y, ratio_estimator, x, y, num_steps, gamma, step_b
         m._engine._check_eval(m)
     if not (isinstance(fm_x._engine, UNetEngine) and isinstance(fm_y._engine, UNetEngine)):
         raise _lib.RgfmError("gradient log-ratio guidance needs two U-Net velocity nets")
+    sde = _sde(sde_eta, sde_seed, sid, (fm_x, fm_y), x, y)
     _require_hip(x, y)
     ratio_estimator._engine.bind(x, y)
     if not (x.is_contiguous() and y.is_contiguous()):
@@ -1273,7 +1336,7 @@ def sample_pair_grad(fm_x, fm_y, ratio_estimator, x, y, num_steps, gamma, step_b
             hx, hy, hr = fm_x._engine.handle(dev), fm_y._engine.handle(dev), ratio_estimator._engine.handle(dev)
             _run_loop(_PAIR_GRAD, (hx, hy, hr, B),
                       (hx, hy, hr, _ptr(x), _ptr(y), B, int(num_steps), float(gamma)), (step_begin, step_end), sid, dev,
-                      diag=diag, strength=strength)
+                      diag=diag, strength=strength, sde=sde)
         return x, y
     return _range_guarded(dev, [x, y], run, [fm_x._engine, fm_y._engine])
 
@@ -1384,7 +1447,7 @@ def guidance_diag_cond(s, v, mc_set, ratios, t):
 
 
 def sample_cond(model, s, mc_set, ratios, num_steps, gamma, step_begin=0, step_end=None, solver='euler', diag=None,
-                gamma_rows=None, stage_scale=None):
+                gamma_rows=None, stage_scale=None, sde_eta=0.0, sde_seed=None):
     """In-place loop of one U-Net with one-sided MC guidance (rgfm_sample_cond; solver='midpoint':
     rgfm_sample_cond_ode): s [B, C, H, W], mc_set [N, C, H, W], ratios [B, N]."""
     sid = _lib.solver_id(solver)
@@ -1395,6 +1458,7 @@ def sample_cond(model, s, mc_set, ratios, num_steps, gamma, step_begin=0, step_e
     if not isinstance(eng, UNetEngine):
         raise _lib.RgfmError(f"conditional sampling needs a U-Net target (FlexibleUNet and its presets), got "
                              f"{type(model).__name__}")
+    sde = _sde(sde_eta, sde_seed, sid, (model,), s)
     _require_hip(s, mc_set, ratios)
     if not s.is_contiguous():
         raise _lib.RgfmError("s must be contiguous (it is updated in place)")
@@ -1414,13 +1478,13 @@ def sample_cond(model, s, mc_set, ratios, num_steps, gamma, step_begin=0, step_e
             h = eng.handle(dev)
             _run_loop(_COND, (h, B, N),
                       (h, _ptr(s), _ptr(mc_set), _ptr(ratios), N, B, int(num_steps), float(gamma)),
-                      (step_begin, step_end), sid, dev, diag=diag, strength=strength)
+                      (step_begin, step_end), sid, dev, diag=diag, strength=strength, sde=sde)
         return s
     return _range_guarded(dev, [s], run, [eng])
 
 
 def sample_cond_grad(model, ratio_estimator, s, ctx, given, num_steps, gamma, step_begin=0, step_end=None, solver='euler',
-                     diag=None, gamma_rows=None, stage_scale=None):
+                     diag=None, gamma_rows=None, stage_scale=None, sde_eta=0.0, sde_seed=None):
     """In-place loop of one U-Net with one-sided gradient log-ratio guidance (rgfm_sample_cond_grad; solver='midpoint':
     rgfm_sample_cond_grad_ode): s [B, C, H, W], ctx [B, hidden_dim] from ratio_estimator._engine.cond_prepare(condition,
     given)."""
@@ -1436,6 +1500,7 @@ def sample_cond_grad(model, ratio_estimator, s, ctx, given, num_steps, gamma, st
     if given not in ('x', 'y'):
         raise ValueError(f"given must be 'x' or 'y', got {given!r}")
     gi = 0 if given == 'x' else 1
+    sde = _sde(sde_eta, sde_seed, sid, (model,), s)
     _require_hip(s, ctx)
     if not s.is_contiguous():
         raise _lib.RgfmError("s must be contiguous (it is updated in place)")
@@ -1455,7 +1520,7 @@ def sample_cond_grad(model, ratio_estimator, s, ctx, given, num_steps, gamma, st
             h, hr = eng.handle(dev), re.handle(dev)
             _run_loop(_COND_GRAD, (h, hr, gi, B),
                       (h, hr, _ptr(s), _ptr(ctx), gi, B, int(num_steps), float(gamma)), (step_begin, step_end), sid, dev,
-                      diag=diag, strength=strength)
+                      diag=diag, strength=strength, sde=sde)
         return s
     return _range_guarded(dev, [s], run, [eng])
 

@@ -51,6 +51,10 @@ class AdamDesc(ctypes.Structure):
                 ("max_grad_norm", c_double), ("ema_decay", c_double), ("decoupled", c_int32), ("reserved", c_int32)]
 
 
+class Sde(ctypes.Structure):  # rgfm_sde: the stochastic step's strength and noise seed
+    _fields_ = [("eta", c_double), ("seed", c_uint64)]
+
+
 # name -> (restype, argtypes); every symbol include/rgfm.h declares.
 SIGNATURES = {
     "rgfm_unet_param_floats": (c_int, [P(UNetDesc), P(c_size_t)]),
@@ -219,6 +223,26 @@ SIGNATURES = {
     "rgfm_guidance_apply_cross_rows": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int,
                                                c_int, c_int, c_int, c_double, c_void_p, c_void_p, c_void_p, c_void_p,
                                                c_size_t, c_void_p]),
+    # the stochastic step: rgfm_sample_single_ode / the *_gs loops with `const rgfm_sde*` in front of ws
+    "rgfm_sde_scratch_bytes": (c_int, [c_int, c_int, c_int, P(c_size_t)]),
+    "rgfm_sde_noise": (c_int, [c_uint64, c_int, c_int, c_size_t, c_void_p, c_void_p]),
+    "rgfm_sample_single_sde": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int, P(Sde), c_void_p, c_size_t,
+                                       c_void_p]),
+    "rgfm_sample_pair_sde": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int,
+                                     c_int, c_double, c_void_p, P(c_double), c_int, c_int, c_int, c_int, c_void_p, c_size_t,
+                                     P(Sde), c_void_p, c_size_t, c_void_p]),
+    "rgfm_sample_pair_cross_sde": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int,
+                                           c_int, c_double, c_void_p, P(c_double), c_int, c_int, c_int, c_int, c_void_p,
+                                           c_size_t, P(Sde), c_void_p, c_size_t, c_void_p]),
+    "rgfm_sample_cond_sde": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_double, c_void_p,
+                                     P(c_double), c_int, c_int, c_int, c_int, c_void_p, c_size_t, P(Sde), c_void_p, c_size_t,
+                                     c_void_p]),
+    "rgfm_sample_pair_grad_sde": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_double, c_void_p,
+                                          P(c_double), c_int, c_int, c_int, c_int, c_void_p, c_size_t, P(Sde), c_void_p,
+                                          c_size_t, c_void_p]),
+    "rgfm_sample_cond_grad_sde": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_double, c_void_p,
+                                          P(c_double), c_int, c_int, c_int, c_int, c_void_p, c_size_t, P(Sde), c_void_p,
+                                          c_size_t, c_void_p]),
     "rgfm_profile_enable": (c_int, [c_int]),
     "rgfm_profile_reset": (c_int, []),
     "rgfm_profile_read": (c_int, [c_int, P(c_double), P(c_double), P(c_int64), P(c_double)]),
@@ -247,6 +271,7 @@ SIGNATURES = {
     "rgfm_adam_step": (c_int, [P(AdamDesc), c_void_p, c_int, c_uint64, c_uint64, c_void_p, c_void_p, c_void_p, c_void_p,
                                c_void_p, c_size_t, c_void_p]),
     "rgfm_ubench_hbm_copy": (c_int, [c_size_t, P(c_double)]),
+    "rgfm_ubench_sde_pre": (c_int, [c_size_t, P(c_double), P(c_double)]),
     "rgfm_unet_set_conv_mode": (c_int, [c_void_p, c_int]),
     "rgfm_fmnet_set_conv_mode": (c_int, [c_void_p, c_int]),
     "rgfm_unet_range_flag": (c_int, [c_void_p, P(c_int), c_int, c_void_p]),

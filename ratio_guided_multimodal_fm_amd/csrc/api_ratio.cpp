@@ -803,6 +803,8 @@ int pair_grad_loop(rgfm_unet* hx, rgfm_unet* hy, rgfm_ratio* hr, float* x_inout,
   Bump b(c.ws, c.ws_bytes);
   PairGradWs w{{hx, batch, c.solver}, {hy, batch, c.solver}};
   carve_pair_grad(b, w, hr);
+  Sde sde = c.sde;
+  if (sde.on()) sde.carve(b, batch, w.cx.image_floats(), w.cy.image_floats());
   if (int rc = check_workspace(b, c.ws_bytes)) return rc;
   if (ns == 0) return RGFM_OK;
   DevState* ds = cur_dev();
@@ -821,15 +823,19 @@ int pair_grad_loop(rgfm_unet* hx, rgfm_unet* hy, rgfm_ratio* hr, float* x_inout,
     float *xin = g.reads_mid ? w.cx.mid : x_inout, *yin = g.reads_mid ? w.cy.mid : y_inout;
     float *xout = g.writes_mid ? w.cx.mid : x_inout, *yout = g.writes_mid ? w.cy.mid : y_inout;
     const float *xb = g.writes_mid ? x_inout : nullptr, *yb = g.writes_mid ? y_inout : nullptr;
+    float dts = g.dts;
+    // (the stochastic step: both pre-updates on `s`, in front of the fork; then xb / yb are its buffers)
+    if (int rc = sde.stage(g, c.num_steps, 0, x_inout, (size_t)batch * dx, s, xb, &xb, &dts)) return rc;
+    if (int rc = sde.stage(g, c.num_steps, 1, y_inout, (size_t)batch * dy, s, yb, &yb, &dts)) return rc;
     hipStream_t sy = overlap ? ds->side : s;
     if (overlap) {
       HIP_TRY(hipEventRecord(ds->fork, s));
       HIP_TRY(hipStreamWaitEvent(ds->side, ds->fork, 0));
     }
     if (c.strength.off(g.row)) {
-      if (int rc = w.cy.eval(g.row, sy, yin, nullptr, yout, y_inout, g.dts)) return rc;
+      if (int rc = w.cy.eval(g.row, sy, yin, nullptr, yout, yb ? yb : y_inout, dts)) return rc;
       if (overlap) HIP_TRY(hipEventRecord(ds->join, ds->side));
-      if (int rc = w.cx.eval(g.row, s, xin, nullptr, xout, x_inout, g.dts)) return rc;
+      if (int rc = w.cx.eval(g.row, s, xin, nullptr, xout, xb ? xb : x_inout, dts)) return rc;
       if (overlap) HIP_TRY(hipStreamWaitEvent(s, ds->join, 0));
       return RGFM_OK;
     }
@@ -851,8 +857,8 @@ int pair_grad_loop(rgfm_unet* hx, rgfm_unet* hy, rgfm_ratio* hr, float* x_inout,
       launch_diag_rownorm(w.gy, batch, (int)dy, rec, RGFM_DIAG_G_NORM_Y, s);
     }
     const StageStrength gamma = c.strength.stage(g.row);
-    euler_grad_update(xout, w.vx, w.gx, batch, dx, gamma, g.dts, s, xb);
-    euler_grad_update(yout, w.vy, w.gy, batch, dy, gamma, g.dts, s, yb);
+    euler_grad_update(xout, w.vx, w.gx, batch, dx, gamma, dts, s, xb);
+    euler_grad_update(yout, w.vy, w.gy, batch, dy, gamma, dts, s, yb);
     return RGFM_OK;
   };
   if (int rc = for_each_stage(c.solver, c.num_steps, c.step_begin, ns, stage)) return rc;
@@ -927,6 +933,8 @@ int cond_grad_loop(rgfm_unet* h, rgfm_ratio* hr, float* s_inout, const float* ct
   if (rc || (rc = check_given(given)) || (rc = check_grad_side(h, hr, given))) return rc;
   Bump b(c.ws, c.ws_bytes);
   CondGradWs w = carve_cond_grad(b, h, hr, given, batch, c.solver);
+  Sde sde = c.sde;
+  if (sde.on()) sde.carve(b, batch, w.c.image_floats(), 0);
   if ((rc = check_workspace(b, c.ws_bytes))) return rc;
   if (ns == 0) return RGFM_OK;
   hipStream_t s = (hipStream_t)c.stream;
@@ -936,8 +944,11 @@ int cond_grad_loop(rgfm_unet* h, rgfm_ratio* hr, float* s_inout, const float* ct
   // one stage: out = base + (v(in, row's t) + gamma grad log r(in)) dts; base null: in place on out
   auto stage = [&](const Stage& g) -> int {
     float *in = g.reads_mid ? w.c.mid : s_inout, *out = g.writes_mid ? w.c.mid : s_inout;
+    const float* base = g.writes_mid ? s_inout : nullptr;
+    float dts = g.dts;
+    if (int rc = sde.stage(g, c.num_steps, 0, s_inout, (size_t)batch * d, s, base, &base, &dts)) return rc;
     // scale 0: the unguided stage (NetChain::step's evaluation), no ratio pass, a zero record
-    if (c.strength.off(g.row)) return w.c.eval(g.row, s, in, nullptr, out, s_inout, g.dts);
+    if (c.strength.off(g.row)) return w.c.eval(g.row, s, in, nullptr, out, base ? base : s_inout, dts);
     if (int rc = w.c.eval(g.row, s, in, w.v, nullptr, nullptr, 0.f)) return rc;
     {
       b.off = w.c.mark;
@@ -950,7 +961,7 @@ int cond_grad_loop(rgfm_unet* h, rgfm_ratio* hr, float* s_inout, const float* ct
       launch_diag_rownorm(w.v, batch, (int)d, rec, RGFM_DIAG_V_NORM_X, s);
       launch_diag_rownorm(w.g, batch, (int)d, rec, RGFM_DIAG_G_NORM_X, s);
     }
-    euler_grad_update(out, w.v, w.g, batch, d, c.strength.stage(g.row), g.dts, s, g.writes_mid ? s_inout : nullptr);
+    euler_grad_update(out, w.v, w.g, batch, d, c.strength.stage(g.row), dts, s, base);
     return RGFM_OK;
   };
   if ((rc = for_each_stage(c.solver, c.num_steps, c.step_begin, ns, stage))) return rc;
@@ -1029,4 +1040,28 @@ extern "C" int rgfm_sample_cond_grad_gs(rgfm_unet* h, rgfm_ratio* hr, float* s_i
                         {.batch = batch, .num_steps = num_steps, .step_begin = step_begin, .step_end = step_end,
                          .solver = solver, .strength = Strength(gamma, gamma_rows, stage_scale, n_stage_scale),
                          .diag_out = diag_out, .diag_records = diag_records, .ws = ws, .ws_bytes = ws_bytes, .stream = stream});
+}
+
+// ---- the stochastic step (include/rgfm.h, "Stochastic sampling"): the *_gs loops with `const rgfm_sde* sde` in front of ws
+extern "C" int rgfm_sample_pair_grad_sde(rgfm_unet* hx, rgfm_unet* hy, rgfm_ratio* hr, float* x_inout, float* y_inout, int batch,
+                                         int num_steps, double gamma, const float* gamma_rows, const double* stage_scale,
+                                         int n_stage_scale, int step_begin, int step_end, int solver, float* diag_out,
+                                         size_t diag_records, const rgfm_sde* sde, void* ws, size_t ws_bytes,
+                                         rgfm_stream_t stream) {
+  return pair_grad_loop(hx, hy, hr, x_inout, y_inout,
+                        {.batch = batch, .num_steps = num_steps, .step_begin = step_begin, .step_end = step_end,
+                         .solver = solver, .strength = Strength(gamma, gamma_rows, stage_scale, n_stage_scale),
+                         .diag_out = diag_out, .diag_records = diag_records, .ws = ws, .ws_bytes = ws_bytes, .stream = stream,
+                         .sde = sde});
+}
+extern "C" int rgfm_sample_cond_grad_sde(rgfm_unet* h, rgfm_ratio* hr, float* s_inout, const float* ctx, int given, int batch,
+                                         int num_steps, double gamma, const float* gamma_rows, const double* stage_scale,
+                                         int n_stage_scale, int step_begin, int step_end, int solver, float* diag_out,
+                                         size_t diag_records, const rgfm_sde* sde, void* ws, size_t ws_bytes,
+                                         rgfm_stream_t stream) {
+  return cond_grad_loop(h, hr, s_inout, ctx, given,
+                        {.batch = batch, .num_steps = num_steps, .step_begin = step_begin, .step_end = step_end,
+                         .solver = solver, .strength = Strength(gamma, gamma_rows, stage_scale, n_stage_scale),
+                         .diag_out = diag_out, .diag_records = diag_records, .ws = ws, .ws_bytes = ws_bytes, .stream = stream,
+                         .sde = sde});
 }

@@ -52,18 +52,20 @@ int single_bytes(const rgfm_unet* h, int batch, int solver, size_t* bytes) {
 }
 
 int single_loop(rgfm_unet* h, float* x_inout, int batch, int num_steps, int step_begin, int step_end, int solver, void* ws,
-                size_t ws_bytes, rgfm_stream_t stream) {
+                size_t ws_bytes, rgfm_stream_t stream, Sde sde = Sde()) {
   refresh_modes();
   int ns = 0;
   if (int rc = check_loop(solver, h && x_inout && ws, batch, num_steps, step_begin, step_end, &ns)) return rc;
+  if (int rc = sde.check(solver)) return rc;
   Bump b(ws, ws_bytes);
   NetChain c{h, batch, solver, x_inout};
   carve_single(b, c);
+  if (sde.on()) sde.carve(b, batch, c.image_floats(), 0);
   if (int rc = check_workspace(b, ws_bytes)) return rc;
   if (ns == 0) return RGFM_OK;
   if (int rc = c.begin((hipStream_t)stream, num_steps, step_begin, ns)) return rc;
   for (int i = 0; i < ns; ++i)
-    if (int rc = c.step(i)) return rc;
+    if (int rc = c.step(i, sde)) return rc;
   HIP_TRY(hipGetLastError());
   return RGFM_OK;
 }
@@ -315,6 +317,8 @@ int cond_loop(rgfm_unet* h, float* s_inout, const float* mc_set, const float* ra
   Bump b(c.ws, c.ws_bytes);
   CondWs w = carve_cond(b, h, c.batch, n_mc, c.solver);
   if (sink.on()) sink.carve(b, d, 0);
+  Sde sde = c.sde;
+  if (sde.on()) sde.carve(b, c.batch, d, 0);
   if (int rc = check_workspace(b, c.ws_bytes)) return rc;
   if (ns == 0) return RGFM_OK;
   hipStream_t s = (hipStream_t)c.stream;
@@ -325,13 +329,16 @@ int cond_loop(rgfm_unet* h, float* s_inout, const float* mc_set, const float* ra
   // and its scale is not 0
   auto stage = [&](const Stage& g) -> int {
     float *in = g.reads_mid ? w.c.mid : s_inout, *out = g.writes_mid ? w.c.mid : s_inout;
+    const float* base = nullptr;
+    float dts = 0.f;
+    if (int rc = sde.stage(g, c.num_steps, 0, s_inout, (size_t)c.batch * d, s, s_inout, &base, &dts)) return rc;
     // unguided: the fused Euler epilogue
-    if (g.t <= 1e-3 || c.strength.off(g.row)) return w.c.eval(g.row, s, in, nullptr, out, s_inout, g.dts);
+    if (g.t <= 1e-3 || c.strength.off(g.row)) return w.c.eval(g.row, s, in, nullptr, out, base, dts);
     // guided: the raw velocity, and the (one-sided) guidance block moves the state
-    if (int rc = w.c.eval(g.row, s, in, w.v, nullptr, nullptr, g.dts)) return rc;
+    if (int rc = w.c.eval(g.row, s, in, w.v, nullptr, nullptr, dts)) return rc;
     return guidance_launch({.x = in, .vx = w.v, .mx = mc_set, .r = ratios, .ratio_stride = n_mc, .B = c.batch, .N = n_mc,
                             .dx = d, .t = g.t, .strength = c.strength.stage(g.row), .scratch = w.scratch, .xs = out,
-                            .xb = s_inout, .dt = g.dts, .stream = s, .diag = sink.at(g.row)});
+                            .xb = base, .dt = dts, .stream = s, .diag = sink.at(g.row)});
   };
   if (int rc = for_each_stage(c.solver, c.num_steps, c.step_begin, ns, stage)) return rc;
   HIP_TRY(hipGetLastError());
@@ -366,6 +373,8 @@ int pair_sample(rgfm_unet* hx, rgfm_unet* hy, float* x_inout, float* y_inout, co
   if (sink.on()) sink.carve(b, w.cx.image_floats(), w.cy.image_floats());
   else if (c.pairing == PAIRING_CROSS)  // (one workspace query for calls with and without records: the same carve)
     (void)b.f((size_t)c.batch * w.cx.image_floats()), (void)b.f((size_t)c.batch * w.cy.image_floats());
+  LoopCall cc = c;  // (the call with the stochastic step's buffers carved)
+  if (cc.sde.on()) cc.sde.carve(b, c.batch, w.cx.image_floats(), w.cy.image_floats());
   if (int rc = check_workspace(b, c.ws_bytes)) return rc;
   if (ns == 0) return RGFM_OK;
   hipStream_t s = (hipStream_t)c.stream;
@@ -378,7 +387,7 @@ int pair_sample(rgfm_unet* hx, rgfm_unet* hy, float* x_inout, float* y_inout, co
                    {.x = x_inout, .y = y_inout, .mc_x1 = mc_x1, .mc_y1 = mc_y1, .mc_ratios = mc_ratios, .n_mc = n_mc,
                     .dx = (int)w.cx.image_floats(), .dy = (int)w.cy.image_floats(), .vx = w.vx, .vy = w.vy, .scratch = w.scratch,
                     .gstate = w.gstate, .x_mid = w.cx.mid, .y_mid = w.cy.mid},
-                   c, ns, sink);
+                   cc, ns, sink);
 }
 
 }  // namespace
@@ -553,4 +562,53 @@ extern "C" int rgfm_sample_cond_gs(rgfm_unet* h, float* s_inout, const float* mc
                    {.batch = batch, .num_steps = num_steps, .step_begin = step_begin, .step_end = step_end, .solver = solver,
                     .strength = Strength(gamma, gamma_rows, stage_scale, n_stage_scale), .diag_out = diag_out,
                     .diag_records = diag_records, .ws = ws, .ws_bytes = ws_bytes, .stream = stream});
+}
+
+// ---- the stochastic step (include/rgfm.h, "Stochastic sampling"): each loop is its *_ode / *_gs namesake with
+// `const rgfm_sde* sde` in front of ws; null or eta = 0: the namesake
+extern "C" int rgfm_sde_scratch_bytes(int batch, int dim_x, int dim_y, size_t* bytes) {
+  if (!bytes || batch < 1 || dim_x < 1 || dim_y < 0) return fail(RGFM_EINVAL, "bad argument");
+  *bytes = sde_scratch_bytes(batch, (size_t)dim_x, (size_t)dim_y);
+  return RGFM_OK;
+}
+extern "C" int rgfm_sde_noise(uint64_t seed, int stream_id, int k, size_t n, float* out, rgfm_stream_t stream) {
+  if (!out || stream_id < 0 || stream_id > 1 || k < 0) return fail(RGFM_EINVAL, "bad argument");
+  if (int rc = ensure_init()) return rc;
+  launch_sde_noise(out, n, sde_key(seed, stream_id, k), (hipStream_t)stream);
+  HIP_TRY(hipGetLastError());
+  return RGFM_OK;
+}
+extern "C" int rgfm_sample_single_sde(rgfm_unet* h, float* x_inout, int batch, int num_steps, int step_begin, int step_end,
+                                      int solver, const rgfm_sde* sde, void* ws, size_t ws_bytes, rgfm_stream_t stream) {
+  return single_loop(h, x_inout, batch, num_steps, step_begin, step_end, solver, ws, ws_bytes, stream, sde);
+}
+extern "C" int rgfm_sample_pair_sde(rgfm_unet* hx, rgfm_unet* hy, float* x_inout, float* y_inout, const float* mc_x1,
+                                    const float* mc_y1, const float* mc_ratios, int n_mc, int batch, int num_steps, double gamma,
+                                    const float* gamma_rows, const double* stage_scale, int n_stage_scale, int step_begin,
+                                    int step_end, int solver, float* diag_out, size_t diag_records, const rgfm_sde* sde, void* ws,
+                                    size_t ws_bytes, rgfm_stream_t stream) {
+  return pair_sample(hx, hy, x_inout, y_inout, mc_x1, mc_y1, mc_ratios, n_mc,
+                     {.batch = batch, .num_steps = num_steps, .step_begin = step_begin, .step_end = step_end, .solver = solver,
+                      .strength = Strength(gamma, gamma_rows, stage_scale, n_stage_scale), .diag_out = diag_out,
+                      .diag_records = diag_records, .ws = ws, .ws_bytes = ws_bytes, .stream = stream, .sde = sde});
+}
+extern "C" int rgfm_sample_pair_cross_sde(rgfm_unet* hx, rgfm_unet* hy, float* x_inout, float* y_inout, const float* mc_x1,
+                                          const float* mc_y1, const float* ratio_matrix, int n_mc, int batch, int num_steps,
+                                          double gamma, const float* gamma_rows, const double* stage_scale, int n_stage_scale,
+                                          int step_begin, int step_end, int solver, float* diag_out, size_t diag_records,
+                                          const rgfm_sde* sde, void* ws, size_t ws_bytes, rgfm_stream_t stream) {
+  return pair_sample(hx, hy, x_inout, y_inout, mc_x1, mc_y1, ratio_matrix, n_mc,
+                     {.batch = batch, .num_steps = num_steps, .step_begin = step_begin, .step_end = step_end, .solver = solver,
+                      .strength = Strength(gamma, gamma_rows, stage_scale, n_stage_scale), .diag_out = diag_out,
+                      .diag_records = diag_records, .ws = ws, .ws_bytes = ws_bytes, .stream = stream,
+                      .pairing = PAIRING_CROSS, .sde = sde});
+}
+extern "C" int rgfm_sample_cond_sde(rgfm_unet* h, float* s_inout, const float* mc_set, const float* ratios, int n_mc, int batch,
+                                    int num_steps, double gamma, const float* gamma_rows, const double* stage_scale,
+                                    int n_stage_scale, int step_begin, int step_end, int solver, float* diag_out,
+                                    size_t diag_records, const rgfm_sde* sde, void* ws, size_t ws_bytes, rgfm_stream_t stream) {
+  return cond_loop(h, s_inout, mc_set, ratios, n_mc,
+                   {.batch = batch, .num_steps = num_steps, .step_begin = step_begin, .step_end = step_end, .solver = solver,
+                    .strength = Strength(gamma, gamma_rows, stage_scale, n_stage_scale), .diag_out = diag_out,
+                    .diag_records = diag_records, .ws = ws, .ws_bytes = ws_bytes, .stream = stream, .sde = sde});
 }

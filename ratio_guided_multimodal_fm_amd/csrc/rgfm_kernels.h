@@ -482,6 +482,10 @@ void launch_guid_apply(const GuidanceArgs& a, hipStream_t s);  // guided velocit
 int guid_apply_init();                                         // (once per process: the GEMM kernel's LDS size)
 void launch_euler(float* x, const float* v, size_t n, float dt, hipStream_t s);
 void launch_step_inc(int* step, hipStream_t s);  // *step += 1
+// the stochastic step's pre-update (sde.hip): base = a x + sigma xi over n floats, xi the Gaussian noise of `key`
+// (sde_key, sampler_host.h); launch_sde_noise writes xi alone
+void launch_sde_pre(const float* x, float* base, size_t n, uint64_t key, float a, float sigma, hipStream_t s);
+void launch_sde_noise(float* out, size_t n, uint64_t key, hipStream_t s);
 void launch_guid_schedule(float* sched, int step_begin, int ns, int num_steps, hipStream_t s);  // [ns][4] = {tf, s2, cden, 0}
 // diagnostics (opt-in; rec: [B][RGFM_DIAG_FLOATS] records, include/rgfm.h)
 void launch_diag_wstats(const float* w, int B, int N, float* rec, hipStream_t s);  // ess, w_max, w_min of the rows of w [B][N]

@@ -71,6 +71,59 @@ inline size_t diag_scratch_bytes(int batch, size_t dx, size_t dy) {
   return b.off;
 }
 
+// The stochastic step of a loop (include/rgfm.h, "Stochastic sampling"; Euler-Maruyama): eta = 0 -- or no rgfm_sde -- is
+// off, and every loop then enqueues what it enqueues without the argument.  On, step k of num_steps is
+//   base = (1 - eta dt) state + sigma_k xi_k,   sigma_k = sqrt(2 eta (1 - t) dt),   state = base + ((1 + eta t) dt) F(state, t):
+// `stage` enqueues the first line into the loop's extra [batch][D] buffer of the modality (carved behind the loop's
+// own buffers, as the diagnostics' scratch) and hands back the second line's base and dts for the loop's fused update,
+// which reads the old state and stays as it is.  The noise of stream m (0: the loop's first or only state, 1: the
+// second) at step k depends on (seed, m, k, element) alone: sde_key, and sde.hip.
+inline uint64_t sde_fin(uint64_t z) {  // (the splitmix64 finaliser of the dropout masks)
+  z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9ull;
+  z = (z ^ (z >> 27)) * 0x94D049BB133111EBull;
+  return z ^ (z >> 31);
+}
+inline uint64_t sde_key(uint64_t seed, int stream_id, int k) {
+  return sde_fin(seed + 0x9E3779B97F4A7C15ull * ((((uint64_t)(uint32_t)stream_id << 32) | (uint32_t)k) + 1ull));
+}
+struct Sde {
+  double eta = 0.0;
+  uint64_t seed = 0;
+  float* buf[2] = {nullptr, nullptr};  // the pre-updated state of stream 0 / 1
+  Sde() = default;
+  Sde(const rgfm_sde* a) {  // (null: off)
+    if (a) eta = a->eta, seed = a->seed;
+  }
+  bool on() const { return eta > 0.0; }
+  // the argument check of every *_sde entry point, before anything is carved or enqueued
+  int check(int solver) const {
+    if (!(eta >= 0.0) || !std::isfinite(eta)) return fail(RGFM_EINVAL, "sde: eta must be finite and >= 0 (got %g)", eta);
+    if (on() && solver == SOLVER_MIDPOINT) return fail(RGFM_EINVAL, "sde: eta > 0 needs RGFM_SOLVER_EULER (no stochastic midpoint rule)");
+    return RGFM_OK;
+  }
+  void carve(Bump& b, int batch, size_t dx, size_t dy) {
+    buf[0] = b.f((size_t)batch * dx);
+    if (dy) buf[1] = b.f((size_t)batch * dy);
+  }
+  // Stage g of a loop over num_steps, state `x` ([batch][D] = n floats) of stream m, on s: enqueues the pre-update and
+  // returns the stage's base and dts.  Off: nothing is enqueued, and (base_off, g.dts) -- the loop's own -- come back.
+  int stage(const Stage& g, int num_steps, int m, const float* x, size_t n, hipStream_t s, const float* base_off, const float** base,
+            float* dts) const {
+    *base = base_off, *dts = g.dts;
+    if (!on()) return RGFM_OK;
+    const double dt = 1.0 / (double)num_steps;
+    launch_sde_pre(x, buf[m], n, sde_key(seed, m, g.step), (float)(1.0 - eta * dt), (float)std::sqrt(2.0 * eta * (1.0 - g.t) * dt), s);
+    *base = buf[m], *dts = (float)((1.0 + eta * g.t) * dt);
+    return RGFM_OK;
+  }
+};
+// bytes a loop's workspace grows by with eta > 0 (rgfm_sde_scratch_bytes): Sde::carve
+inline size_t sde_scratch_bytes(int batch, size_t dx, size_t dy) {
+  Bump b;
+  Sde().carve(b, batch, dx, dy);
+  return b.off;
+}
+
 // The call-level arguments of a sampler loop, filled by field name in its extern "C" wrapper; the loop's own operands
 // (handles, states, MC set) travel beside it.  What an entry point has no argument for keeps its default.
 struct LoopCall {
@@ -82,12 +135,14 @@ struct LoopCall {
   size_t ws_bytes = 0;
   rgfm_stream_t stream = nullptr;
   int pairing = PAIRING_PAIRED;  // (the U-Net pair loop)
+  Sde sde;                       // (the *_sde entry points)
 };
 // The head of every guided loop, in this order: the switches, check_loop (`have_args`: the loop's own pointers), the
-// sink's arguments, the strength's.  The loop's own argument checks follow it, then its carve and check_workspace.
+// stochastic step's arguments, the sink's, the strength's.  The loop's own argument checks follow it, then its carve and check_workspace.
 inline int open_loop(const LoopCall& c, bool have_args, int* ns, DiagSink* sink, bool time_table = true) {
   refresh_modes();
   if (int rc = check_loop(c.solver, have_args && c.ws, c.batch, c.num_steps, c.step_begin, c.step_end, ns, time_table)) return rc;
+  if (int rc = c.sde.check(c.solver)) return rc;
   if (int rc = sink->check(c.diag_out, c.diag_records, c.batch, *ns, c.solver)) return rc;
   return c.strength.check(loop_stages(c.solver, *ns));
 }
@@ -141,12 +196,16 @@ struct NetChain {
     r.fin_counter = cnt, r.step_ptr = step_ptr;
     return r.run(in, v_out, state_out, dts, base);
   }
-  // one unguided step of `x` on `s`: every stage's update fused into the out-conv
-  int step(int i) {
+  // one unguided step of `x` on `s`: every stage's update fused into the out-conv; `sde`: the stochastic step (stream 0)
+  int step(int i, const Sde& sde = Sde()) {
     Stage st[2];
     const int n = step_stages(solver, num_steps, step_begin, i, st);
-    for (int k = 0; k < n; ++k)
-      if (int rc = eval(st[k].row, s, st[k].reads_mid ? mid : x, nullptr, st[k].writes_mid ? mid : x, x, st[k].dts)) return rc;
+    for (int k = 0; k < n; ++k) {
+      const float* base = nullptr;
+      float dts = 0.f;
+      if (int rc = sde.stage(st[k], num_steps, 0, x, (size_t)batch * image_floats(), s, x, &base, &dts)) return rc;
+      if (int rc = eval(st[k].row, s, st[k].reads_mid ? mid : x, nullptr, st[k].writes_mid ? mid : x, base, dts)) return rc;
+    }
     return RGFM_OK;
   }
 };
@@ -192,8 +251,9 @@ int pair_loop(EvalX&& eval_x, EvalY&& eval_y, const PairOperands& p, const LoopC
   hipEvent_t ev_fork = ds->fork, ev_join = ds->join;
   // (diagnostics: kernel by kernel -- each stage writes its own records, a replayed graph would write one stage's)
   // (cross pairing: kernel by kernel as well)
-  const bool use_graph = p.gstate && g_modes.graph && !g_prof.on && n_mc > 0 && ns >= 4 && solver == SOLVER_EULER && !sink.on() && c.pairing == PAIRING_PAIRED && !strength.is_data();
+  const bool use_graph = p.gstate && g_modes.graph && !g_prof.on && n_mc > 0 && ns >= 4 && solver == SOLVER_EULER && !sink.on() && c.pairing == PAIRING_PAIRED && !strength.is_data() && !c.sde.on();
   // (a strength that is data -- per row or per stage -- runs kernel by kernel: the replayed graph holds one stage's scalars)
+  // (the stochastic step: kernel by kernel as well -- its noise key and scalars are launch arguments of the step)
   const hipStream_t caller = (hipStream_t)c.stream;
   hipStream_t s = caller;
   if (use_graph && caller == nullptr) {  // (see DevState::main)
@@ -220,19 +280,23 @@ int pair_loop(EvalX&& eval_x, EvalY&& eval_y, const PairOperands& p, const LoopC
     float *xout = g.writes_mid ? p.x_mid : p.x, *yout = g.writes_mid ? p.y_mid : p.y;
     float *vx = p.vx, *vy = p.vy;
     const float *xb = p.x, *yb = p.y;
+    float dts = g.dts;
+    // (the stochastic step: both pre-updates on `s`, in front of the fork)
+    if (int rc = c.sde.stage(g, num_steps, 0, p.x, (size_t)c.batch * p.dx, s, p.x, &xb, &dts)) return rc;
+    if (int rc = c.sde.stage(g, num_steps, 1, p.y, (size_t)c.batch * p.dy, s, p.y, &yb, &dts)) return rc;
     hipStream_t sy = overlap ? side : s;
     GuidanceCall gc{.x = xin, .y = yin, .vx = vx, .vy = vy, .mx = p.mc_x1, .my = p.mc_y1, .r = p.mc_ratios,
                     .B = c.batch, .N = n_mc, .dx = p.dx, .dy = p.dy, .t = g.t, .strength = strength.stage(g.row),
-                    .scratch = p.scratch, .xs = xout, .ys = yout, .xb = xb, .yb = yb, .dt = g.dts, .stream = s,
+                    .scratch = p.scratch, .xs = xout, .ys = yout, .xb = xb, .yb = yb, .dt = dts, .stream = s,
                     .sched = sched_dev, .step_ptr = step_dev, .diag = sink.at(g.row), .pairing = c.pairing};
     if (overlap) {
       HIP_TRY(hipEventRecord(ev_fork, s));
       HIP_TRY(hipStreamWaitEvent(side, ev_fork, 0));
     }
-    int rc = eval_y(g.row, sy, yin, guided ? vy : nullptr, guided ? nullptr : yout, yb, g.dts, step_dev);
+    int rc = eval_y(g.row, sy, yin, guided ? vy : nullptr, guided ? nullptr : yout, yb, dts, step_dev);
     if (rc) return rc;
     if (overlap) HIP_TRY(hipEventRecord(ev_join, side));
-    rc = eval_x(g.row, s, xin, guided ? vx : nullptr, guided ? nullptr : xout, xb, g.dts, step_dev);
+    rc = eval_x(g.row, s, xin, guided ? vx : nullptr, guided ? nullptr : xout, xb, dts, step_dev);
     if (rc) return rc;
     // The distances to the MC set and the importance weights depend on (x_t, y_t) only (sample_mnist_svhn.py:130-156; a
     // guided step's nets write velocities, the state moves in guid_apply): they go on this stream BEFORE it waits for the

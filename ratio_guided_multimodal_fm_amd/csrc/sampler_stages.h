@@ -14,6 +14,7 @@ struct Stage {
   double t;    // the stage's own time: a stage is guided iff t > 1e-3
   float dts;   // out = base + dts * F(in, t); base is always the step's state
   bool reads_mid, writes_mid;  // in / out is the loop's mid-state buffer instead of the state
+  int step;    // the global step index step_begin + i: what the stochastic step's noise is keyed by (sampler_host.h, Sde)
 };
 
 // stages of a call over `ns` steps
@@ -26,11 +27,11 @@ inline int step_stages(int solver, int num_steps, int step_begin, int i, Stage o
   const double dtd = 1.0 / (double)num_steps;
   const double t1 = (double)(step_begin + i) * dtd;
   if (solver != SOLVER_MIDPOINT) {
-    out[0] = {i, t1, (float)dtd, false, false};
+    out[0] = {i, t1, (float)dtd, false, false, step_begin + i};
     return 1;
   }
-  out[0] = {2 * i, t1, (float)(0.5 * dtd), false, true};
-  out[1] = {2 * i + 1, ((double)(step_begin + i) + 0.5) * dtd, (float)dtd, true, false};
+  out[0] = {2 * i, t1, (float)(0.5 * dtd), false, true, step_begin + i};
+  out[1] = {2 * i + 1, ((double)(step_begin + i) + 0.5) * dtd, (float)dtd, true, false, step_begin + i};
   return 2;
 }
 

@@ -1,10 +1,15 @@
 // ubench.hip -- measured ceilings for bench.py's roofline line (bench support, not on the product path):
-// the sustained f16 MFMA rate of the device under DVFS and its HBM copy bandwidth.
+// the sustained f16 MFMA rate of the device under DVFS and its HBM copy bandwidth; and the stochastic step's pre-update
+// kernel (sde.hip) timed alone, for tools/bench_sde.py.
 #include <hip/hip_runtime.h>
 
 #include <cstdio>
 
 #include "../../include/rgfm.h"
+
+namespace rgfm {  // (rgfm_kernels.h, sde.hip)
+void launch_sde_pre(const float* x, float* base, size_t n, uint64_t key, float a, float sigma, hipStream_t s);
+}
 
 namespace {
 
@@ -156,5 +161,37 @@ extern "C" int rgfm_ubench_hbm_copy(size_t bytes, double* gbps) {
   (void)hipEventDestroy(e1);
   (void)hipFree(in);
   (void)hipFree(out);
+  return RGFM_OK;
+}
+
+// base = a x + sigma xi over n floats (launch_sde_pre, the loops' own launch), timed with device events: GB/s of the
+// 8 bytes per element the kernel moves, and the time of one launch
+extern "C" int rgfm_ubench_sde_pre(size_t n, double* gbps, double* us_per_launch) {
+  if (!gbps || !us_per_launch || n < 1) return RGFM_EINVAL;
+  float *x = nullptr, *base = nullptr;
+  if (hipMalloc(&x, n * sizeof(float)) != hipSuccess) return RGFM_ENOMEM;
+  if (hipMalloc(&base, n * sizeof(float)) != hipSuccess) {
+    (void)hipFree(x);
+    return RGFM_ENOMEM;
+  }
+  UB_TRY(hipMemset(x, 0, n * sizeof(float)));
+  hipEvent_t e0, e1;
+  UB_TRY(hipEventCreate(&e0));
+  UB_TRY(hipEventCreate(&e1));
+  const int reps = 200;
+  for (int pass = 0; pass < 2; ++pass) {  // (the first pass warms up)
+    UB_TRY(hipEventRecord(e0, 0));
+    for (int r = 0; r < reps; ++r) rgfm::launch_sde_pre(x, base, n, 0x0123456789ABCDEFull + r, 0.99f, 0.14f, 0);
+    UB_TRY(hipEventRecord(e1, 0));
+    UB_TRY(hipEventSynchronize(e1));
+  }
+  float ms = 0.f;
+  UB_TRY(hipEventElapsedTime(&ms, e0, e1));
+  *us_per_launch = (double)ms * 1e3 / reps;
+  *gbps = 8.0 * (double)n * reps / (ms * 1e-3) / 1e9;
+  (void)hipEventDestroy(e0);
+  (void)hipEventDestroy(e1);
+  (void)hipFree(x);
+  (void)hipFree(base);
   return RGFM_OK;
 }

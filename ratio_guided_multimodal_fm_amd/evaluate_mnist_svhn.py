@@ -29,7 +29,7 @@ from .models.unet_flexible import FlowMatchingUNetMNIST, FlowMatchingUNetSVHN
 from .sample_mnist_svhn import sample_bimodal_guided_mnist_svhn
 from .utils import load_checkpoint, set_seed
 from .utils.diagnostics import GuidanceDiagnostics, add_cli_args as add_diagnostics_args, row_metrics
-from .utils.flow_utils import add_pairing_arg, shared_mc_sweep
+from .utils.flow_utils import add_sde_args, sde_from_cli, add_pairing_arg, shared_mc_sweep
 from .utils.guidance_schedule import add_cli_args as add_schedule_args, from_cli as schedule_from_cli
 
 
@@ -69,7 +69,7 @@ def evaluate_conditional_coherence(condition, samples, given, mnist_classifier, 
 
 def run_sweep(fm_mnist, fm_svhn, make_ratio, mnist_classifier, svhn_classifier, methods, strengths,
               num_samples, num_steps, device, mc_batch_size, sampler=sample_bimodal_guided_mnist_svhn, solver='euler', diagnostics=False,
-              mc_pairing='paired', shared_mc=False, guidance_schedule=None):
+              mc_pairing='paired', shared_mc=False, guidance_schedule=None, sde_eta=0.0, sde_seed=None):
     """The reference's nested loop (:130-183). `make_ratio()` returns a fresh ratio estimator or None.
     `solver` ('euler' | 'midpoint') goes to `sampler` as a keyword when it is not the default.
     `diagnostics`: every guided row also gets ess_mean, ess_min and w_max of the importance weights at step
@@ -80,7 +80,9 @@ def run_sweep(fm_mnist, fm_svhn, make_ratio, mnist_classifier, svhn_classifier, 
     `shared_mc`: all strengths of a guided method run as ONE sampler call of ``len(strengths) * num_samples`` rows,
     row block j carrying strength j, over one MC set, one pre-phase and one start-noise set repeated per block
     (``utils.flow_utils.shared_mc_sweep``): the strengths' numbers then differ by the strength alone.  Every row of
-    the result gains ``"shared_mc": true``.  The default sampler only (no sharded form)."""
+    the result gains ``"shared_mc": true``.  The default sampler only (no sharded form).
+    `sde_eta` > 0: every sampler call takes Euler-Maruyama steps (``paired_sampler``; `sde_seed` None: each call draws its
+    own seed after its other draws); the keywords go to `sampler` only then, and every row gains ``"sde_eta"``."""
     from ._lib import solver_id
     from .utils.flow_utils import check_pairing
     solver_id(solver)
@@ -88,6 +90,9 @@ def run_sweep(fm_mnist, fm_svhn, make_ratio, mnist_classifier, svhn_classifier, 
     kw = {'solver': solver} if solver != 'euler' else {}
     if guidance_schedule is not None:
         kw['guidance_schedule'] = guidance_schedule
+    sde = {'sde_eta': float(sde_eta), 'sde_seed': sde_seed} if sde_eta else {}
+    sde_row = {'sde_eta': float(sde_eta)} if sde_eta else {}
+    kw.update(sde)
     if shared_mc and sampler is not sample_bimodal_guided_mnist_svhn:
         raise ValueError("shared_mc runs the default sampler: it has no sharded form")
     results = []
@@ -100,7 +105,7 @@ def run_sweep(fm_mnist, fm_svhn, make_ratio, mnist_classifier, svhn_classifier, 
             cross = {'mc_pairing': 'cross'} if mc_pairing == 'cross' and method == 'mc_feng' else {}
             blocks = shared_mc_sweep(fm_mnist, fm_svhn, ratio, method, strengths, num_samples, num_steps, device,
                                      mc_batch_size, (1, 32, 32), (3, 32, 32), solver=solver, diagnostics=diag,
-                                     guidance_schedule=guidance_schedule, **cross)
+                                     guidance_schedule=guidance_schedule, **cross, **sde)
             for j, (strength, (xs, ys)) in enumerate(zip(strengths, blocks)):
                 metrics = evaluate_coherence(xs, ys, mnist_classifier, svhn_classifier, device)
                 if diag is not None and diag.records is not None:
@@ -108,7 +113,7 @@ def run_sweep(fm_mnist, fm_svhn, make_ratio, mnist_classifier, svhn_classifier, 
                                                             solver, num_steps)
                     metrics = {**metrics, **row_metrics(part, num_steps)}
                 results.append({'method': method, 'guidance_strength': strength, 'experiment': 'mnist_svhn',
-                                **metrics, **cross, 'shared_mc': True})
+                                **metrics, **cross, **sde_row, 'shared_mc': True})
                 print(f"  method={method} gamma={strength} -> coherence accuracy {metrics['coherence_acc']:.3f}")
             continue
         for strength in strengths:
@@ -127,7 +132,7 @@ def run_sweep(fm_mnist, fm_svhn, make_ratio, mnist_classifier, svhn_classifier, 
             if shared_mc:
                 metrics = {**metrics, 'shared_mc': True}
             results.append({'method': method, 'guidance_strength': strength, 'experiment': 'mnist_svhn',
-                            **metrics, **cross})
+                            **metrics, **cross, **sde_row})
             print(f"  method={method} gamma={strength} -> coherence accuracy {metrics['coherence_acc']:.3f}")
     return results
 
@@ -151,12 +156,14 @@ def main(argv=None):
     add_diagnostics_args(p, sampling=False)
     add_pairing_arg(p)
     add_schedule_args(p)
+    add_sde_args(p)
     p.add_argument('--shared_mc', action='store_true',
                    help='run all strengths of a guided method as one sampler call over one MC set, one pre-phase and one '
                         'start-noise set (a strength per row): the strengths then differ by the strength alone; not with '
                         '--sharded')
     args = p.parse_args(argv)
     schedule = schedule_from_cli(args)
+    sde_kw = sde_from_cli(args, args.sharded)
     if args.shared_mc and args.sharded:
         p.error('--shared_mc has no --sharded form')
     if schedule is not None and args.sharded:
@@ -205,7 +212,7 @@ def main(argv=None):
     results = run_sweep(fm_mnist, fm_svhn, make_ratio, mnist_clf, svhn_clf, args.guidance_methods,
                         args.guidance_strengths, args.num_samples, args.num_steps, device, args.mc_batch_size,
                         sampler=sampler, solver=args.solver, diagnostics=args.diagnostics, mc_pairing=args.mc_pairing,
-                        shared_mc=args.shared_mc, guidance_schedule=schedule)
+                        shared_mc=args.shared_mc, guidance_schedule=schedule, **sde_kw)
     if args.sharded:
         import torch.distributed as dist
         if dist.is_initialized():

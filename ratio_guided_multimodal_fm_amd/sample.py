@@ -16,7 +16,7 @@ from .models.ratio_estimator import RatioEstimator
 from .models.unet import FlowMatchingUNet
 from .utils import load_checkpoint, set_seed
 from .utils.diagnostics import GuidanceDiagnostics, add_cli_args as add_diagnostics_args, report_diagnostics
-from .utils.flow_utils import add_pairing_arg, sample_bimodal_guided
+from .utils.flow_utils import add_pairing_arg, add_sde_args, sample_bimodal_guided, sde_from_cli
 from .utils.guidance_schedule import add_cli_args as add_schedule_args, from_cli as schedule_from_cli
 from .utils.path_utils import get_checkpoint_path
 
@@ -52,8 +52,10 @@ def main(argv=None):
     add_diagnostics_args(p)
     add_pairing_arg(p)
     add_schedule_args(p)
+    add_sde_args(p)
     args = p.parse_args(argv)
     schedule = schedule_from_cli(args)
+    sde_kw = sde_from_cli(args)
     if schedule is not None and args.model != 'unet':
         p.error('--guidance_schedule / --guidance_window go with --model unet')
     if args.mc_pairing == 'cross' and (args.guidance_method != 'mc_feng' or args.model != 'unet'):
@@ -94,7 +96,7 @@ def main(argv=None):
     xs, ys = sample_bimodal_guided(fm_x, fm_y, ratio, args.guidance_method, args.guidance_strength,
                                    args.num_samples, args.num_steps, device, args.mc_batch_size, solver=args.solver,
                                    diagnostics=diag, mc_pairing=args.mc_pairing,
-                                   **({'guidance_schedule': schedule} if schedule is not None else {}))
+                                   **({'guidance_schedule': schedule} if schedule is not None else {}), **sde_kw)
     report_diagnostics(diag, args.num_steps, args.diagnostics, args.diagnostics_out)
     os.makedirs('outputs', exist_ok=True)
     out = f"outputs/samples_{args.guidance_method}_gamma{args.guidance_strength}_{args.transform_type}.pt"

@@ -14,20 +14,22 @@ from .models.ratio_flexible import RatioEstimatorMNISTSVHN
 from .models.unet_flexible import FlowMatchingUNetMNIST, FlowMatchingUNetSVHN
 from .utils import load_checkpoint, set_seed
 from .utils.diagnostics import GuidanceDiagnostics, add_cli_args as add_diagnostics_args, report_diagnostics
-from .utils.flow_utils import add_pairing_arg, paired_sampler, sample_conditional
+from .utils.flow_utils import add_pairing_arg, add_sde_args, paired_sampler, sample_conditional, sde_from_cli
 from .utils.guidance_schedule import add_cli_args as add_schedule_args, from_cli as schedule_from_cli
 
 
 def sample_bimodal_guided_mnist_svhn(fm_mnist, fm_svhn, ratio_estimator=None, guidance_method='none',
                                      guidance_strength=0.0, num_samples=16, num_steps=100,
                                      device='cuda', mc_batch_size=64, solver='euler', diagnostics=None,
-                                     mc_pairing='paired', guidance_schedule=None):
+                                     mc_pairing='paired', guidance_schedule=None, sde_eta=0.0, sde_seed=None):
     """Returns ``(samples_mnist [n,1,32,32], samples_svhn [n,3,32,32])`` on `device`.  `diagnostics`: a
     ``utils.diagnostics.GuidanceDiagnostics`` to fill; `mc_pairing`: 'paired' | 'cross'; `guidance_strength`: a float or
-    one strength per sample; `guidance_schedule`: a scale of it per stage (all: ``paired_sampler``)."""
+    one strength per sample; `guidance_schedule`: a scale of it per stage; `sde_eta`, `sde_seed`: the stochastic sampler
+    (all: ``paired_sampler``)."""
     return paired_sampler(fm_mnist, fm_svhn, ratio_estimator, guidance_method, guidance_strength,
                           num_samples, num_steps, device, mc_batch_size, (1, 32, 32), (3, 32, 32), solver=solver,
-                          diagnostics=diagnostics, mc_pairing=mc_pairing, guidance_schedule=guidance_schedule)
+                          diagnostics=diagnostics, mc_pairing=mc_pairing, guidance_schedule=guidance_schedule,
+                          sde_eta=sde_eta, sde_seed=sde_seed)
 
 
 def load_condition(path, shape):
@@ -69,8 +71,10 @@ def main(argv=None):
     add_diagnostics_args(p)
     add_pairing_arg(p)
     add_schedule_args(p)
+    add_sde_args(p)
     args = p.parse_args(argv)
     schedule = schedule_from_cli(args)
+    sde_kw = sde_from_cli(args, args.sharded)
     if schedule is not None and args.sharded:
         p.error('--guidance_schedule / --guidance_window have no --sharded form')
     if args.mc_pairing == 'cross' and (args.guidance_method != 'mc_feng' or args.given or args.sharded):
@@ -128,7 +132,7 @@ def main(argv=None):
         out_t = sample_conditional(target, ratio, condition.to(device), 'x' if args.given == 'mnist' else 'y',
                                    args.num_steps, args.guidance_strength, args.mc_batch_size, device=device,
                                    guidance_method=method, solver=args.solver, diagnostics=diag,
-                                   **({'guidance_schedule': schedule} if schedule is not None else {}))
+                                   **({'guidance_schedule': schedule} if schedule is not None else {}), **sde_kw)
         report_diagnostics(diag, args.num_steps, args.diagnostics, args.diagnostics_out)
         os.makedirs('outputs/mnist_svhn', exist_ok=True)
         tag = '_grad_log_ratio' if method == 'grad_log_ratio' else ''
@@ -142,7 +146,7 @@ def main(argv=None):
                      args.num_steps, device, args.mc_batch_size, **({'solver': args.solver} if args.solver != 'euler' else {}),
                      **({'diagnostics': diag} if diag is not None else {}),
                      **({'mc_pairing': args.mc_pairing} if args.mc_pairing != 'paired' else {}),
-                     **({'guidance_schedule': schedule} if schedule is not None else {}))
+                     **({'guidance_schedule': schedule} if schedule is not None else {}), **sde_kw)
     report_diagnostics(diag, args.num_steps, args.diagnostics, args.diagnostics_out)
     if args.sharded:
         import torch.distributed as dist

@@ -21,6 +21,16 @@ from .diagnostics import check as _check_diagnostics
 from .guidance_schedule import resolve as _resolve_strength
 
 
+def _sde_kwargs(eta, sde_seed):
+    """Keywords of the main loop's _engine call for a stochastic sampler: `eta` is what _engine.check_sde returned at the
+    head of the call; 0: {} -- the call goes out as it always did.  Called AFTER every other draw of the call: a seed
+    that is None is drawn here (one 62-bit integer from torch's CPU default generator), so the start noise and the MC
+    set are those of the sde_eta = 0 call and torch.manual_seed fixes the whole call."""
+    if eta == 0.0:
+        return {}
+    return {'sde_eta': eta, 'sde_seed': _engine.draw_sde_seed() if sde_seed is None else int(sde_seed)}
+
+
 def _device(device):
     dev = torch.device(device)
     if dev.type != 'cuda':
@@ -51,14 +61,17 @@ class CFMSchedule:
         t = t.view(x_1.shape[0], *([1] * (x_1.dim() - 1)))
         return (1 - t) * x_0 + t * x_1, x_1 - x_0
 
-    def sample(self, model, num_samples, num_steps=100, device='cuda', solver='euler'):
+    def sample(self, model, num_samples, num_steps=100, device='cuda', solver='euler', sde_eta=0.0, sde_seed=None):
         """x0 ~ N(0, I) [n,1,28,28]; num_steps explicit Euler steps (reference :69-100), or midpoint steps with
-        solver='midpoint' (two network evaluations each, second order; U-Net nets)."""
+        solver='midpoint' (two network evaluations each, second order; U-Net nets).  `sde_eta` > 0: Euler-Maruyama
+        steps of the SDE with the same marginals (``paired_sampler``; U-Net nets, solver='euler'), the noise seeded by
+        `sde_seed` (None: drawn from torch's CPU generator after the start noise)."""
         _engine._solver(solver, model)
+        eta = _engine.check_sde(sde_eta, solver, (model,))
         model.eval()
         dev = _device(device)
         x_t = torch.randn(num_samples, 1, 28, 28, device=dev)
-        return _engine.sample_single(model, x_t, num_steps, solver=solver)
+        return _engine.sample_single(model, x_t, num_steps, solver=solver, **_sde_kwargs(eta, sde_seed))
 
 
     def log_prob(self, model, x, num_steps=100, solver='midpoint', n_probes=1, generator=None, batch_size=128):
@@ -189,6 +202,25 @@ def add_pairing_arg(p):
                         "with --sharded)")
 
 
+def add_sde_args(p):
+    """--sde_eta / --sde_seed of the command-line tools."""
+    p.add_argument('--sde_eta', type=float, default=0.0,
+                   help="stochastic sampler: Euler-Maruyama steps of the SDE with the ODE's marginals in the main loop, "
+                        "noise strength eta (0 = the ODE; U-Net nets, --solver euler; not with --sharded)")
+    p.add_argument('--sde_seed', type=int, default=None,
+                   help='seed of the per-step noise of --sde_eta (default: drawn from the generator that --seed seeds)')
+
+
+def sde_from_cli(args, sharded=False):
+    """Sampler keywords of --sde_eta / --sde_seed: {} without them, so that the call goes out as it always did."""
+    from .._lib import RgfmError
+    if not args.sde_eta:
+        return {}
+    if sharded:
+        raise RgfmError("--sde_eta has no --sharded form: run the stochastic sampler on one device")
+    return {'sde_eta': args.sde_eta, 'sde_seed': args.sde_seed}
+
+
 def _strength_kwargs(guidance_strength, guidance_schedule, rows, num_steps, solver, dev_of, models, what='num_samples'):
     """(gamma, keywords) of the main loop's _engine call for a strength that may be a vector and a schedule that may be
     given: all checks run here, before any device work.  A scalar strength without a schedule gives (the strength as
@@ -215,8 +247,17 @@ def _stats(name, t):
 
 def paired_sampler(fm_x, fm_y, ratio_estimator, guidance_method, guidance_strength, num_samples,
                    num_steps, device, mc_batch_size, shape_x, shape_y, noise=None, verbose=True, solver='euler',
-                   diagnostics=None, mc_pairing='paired', guidance_schedule=None):
+                   diagnostics=None, mc_pairing='paired', guidance_schedule=None, sde_eta=0.0, sde_seed=None):
     """Shared body of both paired samplers.
+
+    `sde_eta` > 0: the main loop takes Euler-Maruyama steps of ``dx = [F + eta (t F - x)] dt + sqrt(2 eta (1 - t)) dW``,
+    the SDE that shares the marginals of the ODE ``dx = F dt`` on the path ``x_t = (1 - t) x_0 + t x_1`` (F: the loop's
+    whole guided velocity; ``rgfm_sample_*_sde``, DESIGN.md "Stochastic sampling").  The per-step noise is generated on
+    the device from `sde_seed` (counter-based: a function of seed, modality, step and element).  ``sde_seed=None``
+    draws the seed from torch's CPU default generator after every other draw of the call, so the start noise and the
+    MC set are those of the ``sde_eta=0`` call and ``torch.manual_seed`` fixes the whole call.  The MC pre-phase stays
+    deterministic.  Both guidance methods, both pairings, with `diagnostics`, strength rows and schedules; U-Net nets
+    and ``solver='euler'`` only (``RgfmError`` otherwise).  ``sde_eta=0`` (default): the call is what it was.
 
     `guidance_strength`: a float, or a 1-D tensor / sequence of `num_samples` strengths (one per pair).
     `guidance_schedule` = None | ``utils.guidance_schedule.GuidanceSchedule`` | callable s(t) | sequence of per-stage
@@ -247,6 +288,7 @@ def paired_sampler(fm_x, fm_y, ratio_estimator, guidance_method, guidance_streng
     if mc_pairing == 'cross' and ratio_estimator is not None:
         _engine._check_cross((mc_batch_size, mc_batch_size), mc_batch_size, mc_batch_size, fm_x, fm_y)
     _engine._solver(solver, fm_x, fm_y)
+    eta = _engine.check_sde(sde_eta, solver, (fm_x, fm_y))
     guidance_strength, gs_kw = _strength_kwargs(guidance_strength, guidance_schedule, num_samples, num_steps, solver,
                                                 lambda: _device(device), (fm_x, fm_y))
     fm_x.eval()
@@ -301,31 +343,35 @@ def paired_sampler(fm_x, fm_y, ratio_estimator, guidance_method, guidance_streng
         if diagnostics is not None and num_samples:
             diag = diagnostics._begin('grad_log_ratio', solver, num_steps, num_samples, dev, stage_scale=gs_kw.get('stage_scale'))
         _engine.sample_pair_grad(fm_x, fm_y, ratio_estimator, x_t, y_t, num_steps, guidance_strength, solver=solver, diag=diag,
-                                 **gs_kw)
+                                 **gs_kw, **_sde_kwargs(eta, sde_seed))
         return x_t, y_t
     diag = None
     if diagnostics is not None and num_samples:
         diag = diagnostics._begin('mc_feng' if guided else 'none', solver, num_steps, num_samples, dev, stage_scale=gs_kw.get('stage_scale'))
     _engine.sample_pair(fm_x, fm_y, x_t, y_t, mc_x1, mc_y1, mc_ratios, num_steps, guidance_strength, solver=solver, diag=diag,
-                        **gs_kw)
+                        **gs_kw, **_sde_kwargs(eta, sde_seed))
     return x_t, y_t
 
 
 def shared_mc_sweep(fm_x, fm_y, ratio_estimator, guidance_method, strengths, num_samples, num_steps, device,
                     mc_batch_size, shape_x, shape_y, solver='euler', diagnostics=None, mc_pairing='paired',
-                    guidance_schedule=None):
+                    guidance_schedule=None, sde_eta=0.0, sde_seed=None):
     """All `strengths` of one guided method as ONE ``paired_sampler`` call of ``len(strengths) * num_samples`` rows: row
     block j carries ``strengths[j]`` (a strength per row), over one MC set, one pre-phase and one start-noise set
     ``[num_samples]`` repeated per block (common random numbers: the blocks differ by the strength alone).  The noise is
     drawn once, in the order of one ordinary call (x0, y0, then mc_x0, mc_y0 for 'mc_feng').  Rows do not depend on the
     batch they run in, so block j has the bits of a call with that strength on the same noise and MC set.
     Returns ``[(samples_x, samples_y), ...]``, one pair ``[num_samples, ...]`` per strength; `diagnostics` (optional)
-    holds the records of all rows, block after block."""
+    holds the records of all rows, block after block.
+    `sde_eta` > 0 (``paired_sampler``): one noise seed for the whole call (`sde_seed`; None: drawn after the noise above).
+    The per-step noise is a function of the element's place in the batch, so the blocks then share the start noise and
+    the MC set but not the path noise."""
     if guidance_method not in ('mc_feng', 'grad_log_ratio') or ratio_estimator is None:
         raise ValueError(f"a shared-MC sweep runs a guided method with its ratio estimator, got {guidance_method!r}")
     strengths = [float(g) for g in strengths]
     if not strengths:
         return []
+    eta = _engine.check_sde(sde_eta, solver, (fm_x, fm_y))
     dev = _device(device)
     x0 = torch.randn(num_samples, *shape_x, device=dev)
     y0 = torch.randn(num_samples, *shape_y, device=dev)
@@ -338,13 +384,14 @@ def shared_mc_sweep(fm_x, fm_y, ratio_estimator, guidance_method, strengths, num
     noise = (x0.repeat(k, 1, 1, 1), y0.repeat(k, 1, 1, 1), mc_x0, mc_y0)
     xs, ys = paired_sampler(fm_x, fm_y, ratio_estimator, guidance_method, rows, k * num_samples, num_steps, dev,
                             mc_batch_size, shape_x, shape_y, noise=noise, verbose=False, solver=solver,
-                            diagnostics=diagnostics, mc_pairing=mc_pairing, guidance_schedule=guidance_schedule)
+                            diagnostics=diagnostics, mc_pairing=mc_pairing, guidance_schedule=guidance_schedule,
+                            **_sde_kwargs(eta, sde_seed))
     return [(xs[j * num_samples:(j + 1) * num_samples], ys[j * num_samples:(j + 1) * num_samples]) for j in range(k)]
 
 
 def sample_conditional(fm_target, ratio_estimator, condition, given='x', num_steps=100, guidance_strength=1.0,
                        mc_batch_size=256, mc_samples=None, device=None, guidance_method='mc_feng', solver='euler',
-                       diagnostics=None, guidance_schedule=None):
+                       diagnostics=None, guidance_schedule=None, sde_eta=0.0, sde_seed=None):
     """Partners for `condition` in the other modality: one sample of `fm_target`'s modality per condition image.
 
     ``given='x'``: `condition` is the estimator's x argument and the target is its y; ``given='y'`` the other way
@@ -372,6 +419,10 @@ def sample_conditional(fm_target, ratio_estimator, condition, given='x', num_ste
     `guidance_strength` may be a 1-D tensor / sequence of ``len(condition)`` strengths and `guidance_schedule` scales
     it per stage, as in ``paired_sampler``.
 
+    `sde_eta` > 0: Euler-Maruyama steps in the guided loop, as in ``paired_sampler`` (``rgfm_sample_cond_sde`` /
+    ``rgfm_sample_cond_grad_sde``; ``solver='euler'``).  The MC pre-phase stays deterministic; ``sde_seed=None`` is
+    drawn from torch's CPU generator after the draws above.
+
     Returns the samples ``[len(condition), C, H, W]`` on the device.  U-Net targets only; ``--sharded`` launches have
     no conditional form yet.
     """
@@ -389,6 +440,7 @@ def sample_conditional(fm_target, ratio_estimator, condition, given='x', num_ste
     ratio_estimator.eval()
     if ratio_estimator.loss_type not in ("disc", "rulsif"):
         raise ValueError(f"Unknown loss_type: {ratio_estimator.loss_type}")
+    eta = _engine.check_sde(sde_eta, solver, (fm_target,))
     guidance_strength, gs_kw = _strength_kwargs(guidance_strength, guidance_schedule, len(condition), num_steps, solver,
                                                 lambda: _device(condition.device if device is None else device),
                                                 (fm_target,), what='len(condition)')
@@ -402,7 +454,7 @@ def sample_conditional(fm_target, ratio_estimator, condition, given='x', num_ste
         if diagnostics is not None and s_t.shape[0]:
             diag = diagnostics._begin('grad_log_ratio', solver, num_steps, s_t.shape[0], dev, stage_scale=gs_kw.get('stage_scale'))
         return _engine.sample_cond_grad(fm_target, ratio_estimator, s_t, ctx, given, num_steps, guidance_strength, solver=solver,
-                                        diag=diag, **gs_kw)
+                                        diag=diag, **gs_kw, **_sde_kwargs(eta, sde_seed))
     if mc_samples is None:
         mc = torch.randn(mc_batch_size, *shape, device=dev)
         _engine.sample_single(fm_target, mc, num_steps, solver=solver)
@@ -416,12 +468,14 @@ def sample_conditional(fm_target, ratio_estimator, condition, given='x', num_ste
     diag = None
     if diagnostics is not None and s_t.shape[0]:
         diag = diagnostics._begin('mc_feng', solver, num_steps, s_t.shape[0], dev, stage_scale=gs_kw.get('stage_scale'))
-    return _engine.sample_cond(fm_target, s_t, mc, ratios, num_steps, guidance_strength, solver=solver, diag=diag, **gs_kw)
+    return _engine.sample_cond(fm_target, s_t, mc, ratios, num_steps, guidance_strength, solver=solver, diag=diag, **gs_kw,
+                               **_sde_kwargs(eta, sde_seed))
 
 
 def sample_bimodal_guided(fm_x, fm_y, ratio_estimator=None, guidance_method='none',
                           guidance_strength=0.0, num_samples=16, num_steps=100, device='cuda',
-                          mc_batch_size=64, solver='euler', diagnostics=None, mc_pairing='paired', guidance_schedule=None):
+                          mc_batch_size=64, solver='euler', diagnostics=None, mc_pairing='paired', guidance_schedule=None,
+                          sde_eta=0.0, sde_seed=None):
     """Pairs of 1x28x28 images, optional mc_feng guidance (reference :178-375).
 
     Returns ``(samples_x [n,1,28,28], samples_y [n,1,28,28])`` on `device`.
@@ -432,8 +486,10 @@ def sample_bimodal_guided(fm_x, fm_y, ratio_estimator=None, guidance_method='non
     ``reference_block(int(0.3 * num_steps))`` (the same text) or its per-sample, per-stage records.
     ``mc_pairing='cross'``: the guidance over all ``mc_batch_size ** 2`` pairs of the MC set (``paired_sampler``).
     `guidance_strength` may also hold one strength per sample and `guidance_schedule` scales it per stage
-    (``paired_sampler``, ``utils/guidance_schedule.py``).
+    (``paired_sampler``, ``utils/guidance_schedule.py``).  `sde_eta`, `sde_seed`: the stochastic sampler
+    (``paired_sampler``).
     """
     return paired_sampler(fm_x, fm_y, ratio_estimator, guidance_method, guidance_strength,
                           num_samples, num_steps, device, mc_batch_size, (1, 28, 28), (1, 28, 28), solver=solver,
-                          diagnostics=diagnostics, mc_pairing=mc_pairing, guidance_schedule=guidance_schedule)
+                          diagnostics=diagnostics, mc_pairing=mc_pairing, guidance_schedule=guidance_schedule,
+                          sde_eta=sde_eta, sde_seed=sde_seed)
