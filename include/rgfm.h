@@ -951,6 +951,69 @@ int rgfm_sample_cond_grad_sde(rgfm_unet* h_unet, rgfm_ratio* h_ratio, float* s_i
                               rgfm_stream_t stream);
 
 /* ------------------------------------------------------------------------
+ * Effective-sample-size floor: adaptive tempering of the MC importance weights (paired and one-sided MC loops of the
+ * U-Nets).  Added functions only: the ABI version is unchanged.
+ *
+ * Row b of a guided stage weighs the MC set by w_i ~ r_i N(x_t; t m_i, sigma_t^2), and as t -> 1 the weights collapse
+ * onto the nearest MC sample.  With a floor ess_min (a double, 1 <= ess_min <= n_mc) the row's weights are flattened by
+ * an exponent tau <= 1 of its own, just enough that their effective sample size reaches the floor; rows at or above it
+ * are not touched.
+ *
+ * 1. The rule.  l_i: the row's log-density term (the two modalities' -0.5 |.|^2 / sigma_t^2, each rounded to fp32, then
+ *    added); r_i: its ratio (the shared vector, or the row's own in the one-sided loop); w_i: the weights of the call
+ *    without a floor; ESS_1 = (sum w)^2 / sum w^2.
+ *      P = {i : r_i > 0}, n_pos = |P|.  Samples outside P have weight exactly 0 for every tau: they are masked,
+ *                 tau * (-inf) is never formed.
+ *      E* = min(ess_min, n_pos).  n_pos = 0: the all-zero row of the call without a floor (tau = 1).
+ *      ESS_1 >= E*, or E* <= 1 (an effective sample size is at least 1, whatever the rounding of ESS_1 says):
+ *                 tau = 1, and the row's weights, weight sum and weights_out are the BITS of the call without a
+ *                 floor -- the existing result is kept, the tempered formula is not evaluated at tau = 1.
+ *      otherwise  L_i = l_i + log r_i,  d_i = L_i - max_P L,  ESS(tau) = (sum_P e^{tau d_i})^2 / sum_P e^{2 tau d_i},
+ *                 non-increasing in tau with ESS(0) = n_pos >= E*.  Bisection from lo = 0, hi = 1, exactly 40 times
+ *                 mid = 0.5 (lo + hi); lo = mid if ESS(mid) >= E*, else hi = mid.  Then tau = lo and
+ *                 w_i = e^{tau d_i} / sum_P e^{tau d_j}.  No early exit and no epsilon: the largest term is 1.
+ *    All in fp32, e^{2 tau d} as the square of e^{tau d}; every sum runs lane l over samples l, l + 64, ... in index
+ *    order followed by the xor butterfly over the 64 lanes, so a row's result depends on its own data and n_mc only,
+ *    not on the batch.  The WHOLE weight r p is tempered, not the Gaussian factor alone: with r held fixed,
+ *    (sum r_i p_i^tau)^2 / sum r_i^2 p_i^{2 tau} is not monotone in tau and the target may be unreachable (at tau = 0 it
+ *    is the effective sample size of r itself).  Tempering biases the estimator: it trades the collapsed weights'
+ *    variance for a pull toward the ratio-free, flatter posterior mean.
+ *
+ * 2. Loops.  rgfm_sample_pair_ess / rgfm_sample_cond_ess: the *_sde namesake with `const rgfm_ess* ess` directly in
+ *    front of ws.  ess == NULL or ess_min <= 0: the call IS its namesake -- launches, graph replay, bits, workspace.
+ *    Otherwise the workspace is still the namesake's query (the kernel needs LDS only, no memory of the caller's), every
+ *    guided stage enqueues the tempering weights kernel in the place of the plain one and nothing else changes, and the
+ *    call runs kernel by kernel (no hipGraph replay).  tau_out: a DEVICE array [stages][batch] of fp32, or null; it
+ *    receives tau per row in the diagnostics records' stage order (tau_records >= stages x batch floats), 0 for an
+ *    unguided stage.  Composes with both solvers, gamma_rows / stage_scale, sde and diagnostics: RGFM_DIAG_ESS, _W_MAX
+ *    and _W_MIN are then those of the tempered weights, RGFM_DIAG_Z_BAR stays the untempered value.
+ *    Blocks: rgfm_guidance_apply_ess / rgfm_guidance_apply_cond_ess are the *_rows blocks with
+ *    `double ess_min, float* tau_out` (tau_out [batch] or null) behind weights_out; ess_min <= 0: the *_rows block.
+ *    n_mc: 1 .. 4096 as everywhere (two [4][n_mc] fp32 arrays in LDS: 128 KB of the CU's 160 at n_mc = 4096).
+ *    Errors are returned before anything is enqueued: the namesake's own, and RGFM_EINVAL for ess_min not finite, in
+ *    (0, 1) or above n_mc, and for tau_out with tau_records short of the call's stages x batch.  There is no cross
+ *    twin: a per-row exponent makes the ratio matrix row-dependent, and the two [B,N] x [N,N] products are gone.
+ * ---------------------------------------------------------------------- */
+typedef struct rgfm_ess { double ess_min; float* tau_out; size_t tau_records; } rgfm_ess;
+int rgfm_sample_pair_ess(rgfm_unet* hx, rgfm_unet* hy, float* x_inout, float* y_inout, const float* mc_x1,
+                         const float* mc_y1, const float* mc_ratios, int n_mc, int batch, int num_steps, double gamma,
+                         const float* gamma_rows, const double* stage_scale, int n_stage_scale, int step_begin,
+                         int step_end, int solver, float* diag_out, size_t diag_records, const rgfm_sde* sde,
+                         const rgfm_ess* ess, void* ws, size_t ws_bytes, rgfm_stream_t stream);
+int rgfm_sample_cond_ess(rgfm_unet* h, float* s_inout, const float* mc_set, const float* ratios, int n_mc, int batch,
+                         int num_steps, double gamma, const float* gamma_rows, const double* stage_scale,
+                         int n_stage_scale, int step_begin, int step_end, int solver, float* diag_out,
+                         size_t diag_records, const rgfm_sde* sde, const rgfm_ess* ess, void* ws, size_t ws_bytes,
+                         rgfm_stream_t stream);
+int rgfm_guidance_apply_ess(const float* x, const float* y, float* vx, float* vy, const float* mc_x1,
+                            const float* mc_y1, const float* mc_ratios, int batch, int n_mc, int dim_x, int dim_y,
+                            double t, const float* gamma_rows, float* weights_out, double ess_min, float* tau_out,
+                            void* ws, size_t ws_bytes, rgfm_stream_t stream);
+int rgfm_guidance_apply_cond_ess(const float* s, float* v, const float* mc_set, const float* ratios, int batch,
+                                 int n_mc, int dim, double t, const float* gamma_rows, float* weights_out,
+                                 double ess_min, float* tau_out, void* ws, size_t ws_bytes, rgfm_stream_t stream);
+
+/* ------------------------------------------------------------------------
  * Bench support: per-kernel-class device time measured with hipEvents on the
  * launch stream (bench.py's roofline line).  Timing is off by default.
  * ---------------------------------------------------------------------- */

@@ -331,20 +331,21 @@ class _TrainFn(torch.autograd.Function):
 # The exports of a sampler loop, one row each: the entry point and its workspace query, their *_diag pair, the *_gs entry
 # point (a strength per row / per stage; no query of its own), and for the U-Net pair the cross-pairing entry points (one
 # query for calls with and without records), and the *_sde entry points (the stochastic step; workspace: the query the
-# call would use without it plus rgfm_sde_scratch_bytes).  None: the loop has no such export.  _run_loop picks from the row.
-_Loop = collections.namedtuple("_Loop", "fn ws diag diag_ws gs cross cross_ws cross_gs sde cross_sde", defaults=(None,) * 8)
+# call would use without it plus rgfm_sde_scratch_bytes), and the *_ess entry point (the effective-sample-size floor of the
+# MC loops; no workspace of its own).  None: the loop has no such export.  _run_loop picks from the row.
+_Loop = collections.namedtuple("_Loop", "fn ws diag diag_ws gs cross cross_ws cross_gs sde cross_sde ess", defaults=(None,) * 9)
 _SINGLE = _Loop("rgfm_sample_single_ode", "rgfm_sample_single_ode_workspace_bytes", sde="rgfm_sample_single_sde")
 _TWO = _Loop("rgfm_sample_two", "rgfm_sample_two_workspace_bytes")
 _PAIR = _Loop("rgfm_sample_pair_ode", "rgfm_sample_pair_ode_workspace_bytes",
               "rgfm_sample_pair_diag", "rgfm_sample_pair_diag_workspace_bytes", "rgfm_sample_pair_gs",
               "rgfm_sample_pair_cross", "rgfm_sample_pair_cross_workspace_bytes", "rgfm_sample_pair_cross_gs",
-              "rgfm_sample_pair_sde", "rgfm_sample_pair_cross_sde")
+              "rgfm_sample_pair_sde", "rgfm_sample_pair_cross_sde", ess="rgfm_sample_pair_ess")
 _PAIR_GRAD = _Loop("rgfm_sample_pair_grad_ode", "rgfm_sample_pair_grad_ode_workspace_bytes",
                    "rgfm_sample_pair_grad_diag", "rgfm_sample_pair_grad_diag_workspace_bytes", "rgfm_sample_pair_grad_gs",
                    sde="rgfm_sample_pair_grad_sde")
 _COND = _Loop("rgfm_sample_cond_ode", "rgfm_sample_cond_ode_workspace_bytes",
               "rgfm_sample_cond_diag", "rgfm_sample_cond_diag_workspace_bytes", "rgfm_sample_cond_gs",
-              sde="rgfm_sample_cond_sde")
+              sde="rgfm_sample_cond_sde", ess="rgfm_sample_cond_ess")
 _COND_GRAD = _Loop("rgfm_sample_cond_grad_ode", "rgfm_sample_cond_grad_ode_workspace_bytes",
                    "rgfm_sample_cond_grad_diag", "rgfm_sample_cond_grad_diag_workspace_bytes", "rgfm_sample_cond_grad_gs",
                    sde="rgfm_sample_cond_grad_sde")
@@ -1122,7 +1123,42 @@ def _sde(sde_eta, sde_seed, sid, models, *states):
     return _lib.Sde(eta, seed), B, dims[0], dims[1]
 
 
-def _run_loop(loop, ws_args, args, steps, sid, dev, ws=None, diag=None, cross=False, strength=None, sde=None):
+def check_ess(ess_floor, n_mc, models, cross=False):
+    """Argument checks of an effective-sample-size floor (include/rgfm.h, "Effective-sample-size floor"), before any
+    draw and any device work; returns the floor as a float, or None for ess_floor=None (the call is then today's).
+    The floor must be finite with 1 <= ess_floor <= n_mc (ValueError); it needs U-Net velocity nets and the paired
+    (not the cross) pairing (RgfmError)."""
+    if ess_floor is None:
+        return None
+    floor = float(ess_floor)
+    if not math.isfinite(floor) or floor < 1.0:
+        raise ValueError(f"ess_floor must be finite and >= 1 (an effective sample size), got {ess_floor!r}")
+    if floor > n_mc:
+        raise ValueError(f"ess_floor {floor:g} is above the {n_mc} MC samples: no exponent can reach it")
+    if cross:
+        raise _lib.RgfmError("ess_floor does not go with mc_pairing='cross': an exponent per row makes the ratio matrix "
+                             "row-dependent, and the two [B,N] x [N,N] products of the cross weights no longer exist")
+    for m in models:
+        if not isinstance(m._engine, UNetEngine):
+            raise _lib.RgfmError("ess_floor needs U-Net velocity nets (FlexibleUNet and its presets); "
+                                 f"{type(m).__name__}'s loop has the plain importance weights only")
+    return floor
+
+
+def _ess(ess_floor, n_mc, models, cross, tau, n_stages, batch):
+    """The floor of a loop call, before any device work: None for ess_floor=None, else what _run_loop takes as `ess` --
+    the rgfm_ess record and the tensor it points into.  `tau`: a zeroed fp32 device tensor [n_stages, batch], or None."""
+    floor = check_ess(ess_floor, n_mc, models, cross)
+    if floor is None:
+        return None
+    if tau is not None and not (tau.is_cuda and tau.dtype == torch.float32 and tau.is_contiguous()
+                                and tuple(tau.shape) == (n_stages, batch)):
+        raise _lib.RgfmError(f"tau: a contiguous fp32 device tensor [{n_stages}, {batch}] expected, got "
+                             f"{tuple(tau.shape)} {tau.dtype} on {tau.device}")
+    return _lib.Ess(floor, _ptr(tau), 0 if tau is None else tau.numel()), tau
+
+
+def _run_loop(loop, ws_args, args, steps, sid, dev, ws=None, diag=None, cross=False, strength=None, sde=None, ess=None):
     """One native sampler loop (`loop`: its _Loop row): the size query (*ws_args[, sid]), the workspace (`ws`: a
     _Workspace; default the samplers' shared one), then the entry point (*args, *steps[, sid], workspace, stream).
     `steps`: (step_begin, step_end).  sid None: entry points without a solver argument (the FlowMatchingModel loops).
@@ -1131,7 +1167,9 @@ def _run_loop(loop, ws_args, args, steps, sid, dev, ws=None, diag=None, cross=Fa
     `strength`: what _check_strength returns -- not None: the loop's *_gs entry point runs (U-Net loops), the *_diag
     arguments with (gamma_rows, stage_scale, n_stage_scale) behind gamma, in the workspace chosen above.
     `sde`: what _sde returns -- not None: the loop's *_sde entry point runs (the *_gs arguments, or the single loop's own,
-    with the rgfm_sde in front of the workspace), in the workspace chosen above plus rgfm_sde_scratch_bytes."""
+    with the rgfm_sde in front of the workspace), in the workspace chosen above plus rgfm_sde_scratch_bytes.
+    `ess`: what _ess returns -- not None: the loop's *_ess entry point runs (the *_sde arguments with the rgfm_ess behind
+    the rgfm_sde, which is null without `sde`), in the workspace chosen above."""
     L = _lib.lib()
     tail = () if sid is None else (sid,)
     fn, ws_fn, sink = loop.fn, loop.ws, ()
@@ -1166,6 +1204,15 @@ def _run_loop(loop, ws_args, args, steps, sid, dev, ws=None, diag=None, cross=Fa
             sink = sink or (None, 0)
         _lib.check(L.rgfm_sde_scratch_bytes(batch, dim_x, dim_y, ctypes.byref(nb)))
         nbytes, more = nbytes + nb.value, (ctypes.byref(rec),)
+    if ess is not None:
+        if loop.ess is None or cross:
+            raise _lib.RgfmError("this sampler loop has no effective-sample-size floor")
+        fn = loop.ess
+        if sde is None:
+            if strength is None:
+                args = (*args, None, None, 0)
+            sink, more = sink or (None, 0), (None,)
+        more = (*more, ctypes.byref(ess[0]))
     buf = (ws or _sampler_ws).get(nbytes, dev)
     _lib.check(getattr(L, fn)(*args, int(steps[0]), int(steps[1]), *tail, *sink, *more, _ptr(buf), nbytes, _stream(dev)))
 
@@ -1259,7 +1306,8 @@ def sample_two_streams(fm_x, x, fm_y, y, num_steps, solver='euler'):
 
 
 def sample_pair(fm_x, fm_y, x, y, mc_x1, mc_y1, mc_ratios, num_steps, gamma, step_begin=0,
-                step_end=None, solver='euler', diag=None, gamma_rows=None, stage_scale=None, sde_eta=0.0, sde_seed=None):
+                step_end=None, solver='euler', diag=None, gamma_rows=None, stage_scale=None, sde_eta=0.0, sde_seed=None,
+                ess_floor=None, tau=None):
     """In-place paired loop with optional MC guidance (rgfm_sample_pair; solver='midpoint': rgfm_sample_pair_ode).
     `diag`: a records tensor [n_stages, B, 8] to fill (rgfm_sample_pair_diag / rgfm_fmnet_sample_pair_diag; the state
     keeps its bits); the other guided loops below take it the same way.
@@ -1271,7 +1319,11 @@ def sample_pair(fm_x, fm_y, x, y, mc_x1, mc_y1, mc_ratios, num_steps, gamma, ste
     `gamma_rows` (fp32 device tensor [B]: a strength per row, in `gamma`'s place) and `stage_scale` (floats, one per
     stage of the call: a scale of the strength per stage; 0 = the stage runs unguided): rgfm_sample_pair_gs /
     rgfm_sample_pair_cross_gs (U-Net nets).  Both None: the call above, unchanged.  The other guided loops below take
-    them the same way."""
+    them the same way.
+
+    `ess_floor` (a float in [1, N]): every guided stage tempers the rows whose effective sample size is below it
+    (rgfm_sample_pair_ess); `tau`: a zeroed fp32 device tensor [n_stages, B] that receives the rows' exponents.  None:
+    the call above, unchanged.  sample_cond takes them the same way."""
     sid = _solver(solver, fm_x, fm_y)
     strength = _check_strength(gamma_rows, stage_scale, x.shape[0], num_steps,
                                (step_begin, num_steps if step_end is None else step_end), sid, (fm_x, fm_y))
@@ -1294,6 +1346,7 @@ def sample_pair(fm_x, fm_y, x, y, mc_x1, mc_y1, mc_ratios, num_steps, gamma, ste
     cross = bool(n_mc) and mc_ratios.dim() == 2
     if cross:
         _check_cross(mc_ratios.shape, n_mc, mc_y1.shape[0], fm_x, fm_y)
+    ess = _ess(ess_floor, n_mc, (fm_x, fm_y), cross, tau, (step_end - step_begin) * (2 if sid else 1), B)
     if n_mc:
         mc_x1, mc_y1, mc_ratios = mc_x1.contiguous(), mc_y1.contiguous(), mc_ratios.contiguous()
 
@@ -1304,7 +1357,7 @@ def sample_pair(fm_x, fm_y, x, y, mc_x1, mc_y1, mc_ratios, num_steps, gamma, ste
                       (hx, hy, _ptr(x), _ptr(y), _ptr(mc_x1 if n_mc else None), _ptr(mc_y1 if n_mc else None),
                        _ptr(mc_ratios if n_mc else None), n_mc, B, int(num_steps), float(gamma)),
                       (step_begin, step_end), _solver_arg(ex, sid), dev, diag=diag, cross=cross, strength=strength,
-                      sde=sde)
+                      sde=sde, ess=ess)
         return x, y
     return _range_guarded(dev, [x, y], run, [fm_x._engine, fm_y._engine])
 
@@ -1447,7 +1500,7 @@ def guidance_diag_cond(s, v, mc_set, ratios, t):
 
 
 def sample_cond(model, s, mc_set, ratios, num_steps, gamma, step_begin=0, step_end=None, solver='euler', diag=None,
-                gamma_rows=None, stage_scale=None, sde_eta=0.0, sde_seed=None):
+                gamma_rows=None, stage_scale=None, sde_eta=0.0, sde_seed=None, ess_floor=None, tau=None):
     """In-place loop of one U-Net with one-sided MC guidance (rgfm_sample_cond; solver='midpoint':
     rgfm_sample_cond_ode): s [B, C, H, W], mc_set [N, C, H, W], ratios [B, N]."""
     sid = _lib.solver_id(solver)
@@ -1471,6 +1524,7 @@ def sample_cond(model, s, mc_set, ratios, num_steps, gamma, step_begin=0, step_e
         step_end = num_steps
     if B == 0:
         return s
+    ess = _ess(ess_floor, N, (model,), False, tau, (step_end - step_begin) * (2 if sid else 1), B)
     mc_set, ratios = mc_set.contiguous(), ratios.contiguous()
 
     def run():
@@ -1478,7 +1532,7 @@ def sample_cond(model, s, mc_set, ratios, num_steps, gamma, step_begin=0, step_e
             h = eng.handle(dev)
             _run_loop(_COND, (h, B, N),
                       (h, _ptr(s), _ptr(mc_set), _ptr(ratios), N, B, int(num_steps), float(gamma)),
-                      (step_begin, step_end), sid, dev, diag=diag, strength=strength, sde=sde)
+                      (step_begin, step_end), sid, dev, diag=diag, strength=strength, sde=sde, ess=ess)
         return s
     return _range_guarded(dev, [s], run, [eng])
 

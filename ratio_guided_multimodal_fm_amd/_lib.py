@@ -55,6 +55,10 @@ class Sde(ctypes.Structure):  # rgfm_sde: the stochastic step's strength and noi
     _fields_ = [("eta", c_double), ("seed", c_uint64)]
 
 
+class Ess(ctypes.Structure):  # rgfm_ess: the effective-sample-size floor and the per-row exponents' sink
+    _fields_ = [("ess_min", c_double), ("tau_out", c_void_p), ("tau_records", c_size_t)]
+
+
 # name -> (restype, argtypes); every symbol include/rgfm.h declares.
 SIGNATURES = {
     "rgfm_unet_param_floats": (c_int, [P(UNetDesc), P(c_size_t)]),
@@ -243,6 +247,19 @@ SIGNATURES = {
     "rgfm_sample_cond_grad_sde": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_double, c_void_p,
                                           P(c_double), c_int, c_int, c_int, c_int, c_void_p, c_size_t, P(Sde), c_void_p,
                                           c_size_t, c_void_p]),
+    # the effective-sample-size floor: the *_sde MC loops with `const rgfm_ess*` in front of ws; the *_rows blocks with
+    # (ess_min, tau_out) behind weights_out
+    "rgfm_sample_pair_ess": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int,
+                                     c_int, c_double, c_void_p, P(c_double), c_int, c_int, c_int, c_int, c_void_p, c_size_t,
+                                     P(Sde), P(Ess), c_void_p, c_size_t, c_void_p]),
+    "rgfm_sample_cond_ess": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_double, c_void_p,
+                                     P(c_double), c_int, c_int, c_int, c_int, c_void_p, c_size_t, P(Sde), P(Ess), c_void_p,
+                                     c_size_t, c_void_p]),
+    "rgfm_guidance_apply_ess": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int,
+                                        c_int, c_int, c_double, c_void_p, c_void_p, c_double, c_void_p, c_void_p, c_size_t,
+                                        c_void_p]),
+    "rgfm_guidance_apply_cond_ess": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_double,
+                                             c_void_p, c_void_p, c_double, c_void_p, c_void_p, c_size_t, c_void_p]),
     "rgfm_profile_enable": (c_int, [c_int]),
     "rgfm_profile_reset": (c_int, []),
     "rgfm_profile_read": (c_int, [c_int, P(c_double), P(c_double), P(c_int64), P(c_double)]),

@@ -178,16 +178,18 @@ extern "C" int rgfm_guidance_workspace_bytes(int batch, int n_mc, size_t* bytes)
 namespace {
 int guidance_block(const float* x, const float* y, float* vx, float* vy, const float* mc_x1, const float* mc_y1,
                    const float* mc_ratios, int batch, int n_mc, int dim_x, int dim_y, double t, const StageStrength& gamma,
-                   float* weights_out, void* ws, size_t ws_bytes, rgfm_stream_t stream) {
+                   float* weights_out, void* ws, size_t ws_bytes, rgfm_stream_t stream, double ess_min = 0.0,
+                   float* tau_out = nullptr) {
   if (!x || !y || !vx || !vy || !mc_x1 || !mc_y1 || !mc_ratios || !ws) return fail(RGFM_EINVAL, "null argument");
   size_t need = 0;
   int rc = rgfm_guidance_workspace_bytes(batch, n_mc, &need);
   if (rc) return rc;
+  if (!(ess_min <= 0.0) && (rc = Ess::check_min(ess_min, n_mc))) return rc;  // (<= 0: off, the *_rows block)
   if (need > ws_bytes) return fail(RGFM_ENOMEM, "workspace too small: %zu < %zu", ws_bytes, need);
   if ((rc = ensure_init())) return rc;
   rc = guidance_launch({.x = x, .y = y, .vx = vx, .vy = vy, .mx = mc_x1, .my = mc_y1, .r = mc_ratios, .B = batch, .N = n_mc,
                         .dx = dim_x, .dy = dim_y, .t = t, .strength = gamma, .scratch = (float*)ws,
-                        .weights_out = weights_out, .stream = (hipStream_t)stream});
+                        .weights_out = weights_out, .stream = (hipStream_t)stream, .ess_min = ess_min, .tau_out = tau_out});
   if (rc) return rc;
   HIP_TRY(hipGetLastError());
   return RGFM_OK;
@@ -196,17 +198,18 @@ int guidance_block(const float* x, const float* y, float* vx, float* vy, const f
 // The one-sided block: the paired block with dy = 0 and a ratio row per sample (GuidanceCall).
 int guidance_block_cond(const float* s, float* v, const float* mc_set, const float* ratios, int batch, int n_mc, int dim,
                         double t, const StageStrength& gamma, float* weights_out, void* ws, size_t ws_bytes,
-                        rgfm_stream_t stream) {
+                        rgfm_stream_t stream, double ess_min = 0.0, float* tau_out = nullptr) {
   if (!s || !v || !mc_set || !ratios || !ws) return fail(RGFM_EINVAL, "null argument");
   if (dim < 1) return fail(RGFM_EINVAL, "bad argument");
   size_t need = 0;
   int rc = rgfm_guidance_workspace_bytes(batch, n_mc, &need);
   if (rc) return rc;
+  if (!(ess_min <= 0.0) && (rc = Ess::check_min(ess_min, n_mc))) return rc;  // (<= 0: off, the *_rows block)
   if (need > ws_bytes) return fail(RGFM_ENOMEM, "workspace too small: %zu < %zu", ws_bytes, need);
   if ((rc = ensure_init())) return rc;
   rc = guidance_launch({.x = s, .vx = v, .mx = mc_set, .r = ratios, .ratio_stride = n_mc, .B = batch, .N = n_mc, .dx = dim,
                         .t = t, .strength = gamma, .scratch = (float*)ws, .weights_out = weights_out,
-                        .stream = (hipStream_t)stream});
+                        .stream = (hipStream_t)stream, .ess_min = ess_min, .tau_out = tau_out});
   if (rc) return rc;
   HIP_TRY(hipGetLastError());
   return RGFM_OK;
@@ -240,6 +243,23 @@ extern "C" int rgfm_guidance_apply_cond_rows(const float* s, float* v, const flo
   if (!gamma_rows) return fail(RGFM_EINVAL, "null argument");
   return guidance_block_cond(s, v, mc_set, ratios, batch, n_mc, dim, t, StageStrength(0.0, gamma_rows, 1.0), weights_out, ws,
                              ws_bytes, stream);
+}
+// ... held to an effective-sample-size floor (include/rgfm.h, "Effective-sample-size floor"): the *_rows blocks plus
+// (ess_min, tau_out); ess_min 0 is the *_rows block itself
+extern "C" int rgfm_guidance_apply_ess(const float* x, const float* y, float* vx, float* vy, const float* mc_x1,
+                                       const float* mc_y1, const float* mc_ratios, int batch, int n_mc, int dim_x, int dim_y,
+                                       double t, const float* gamma_rows, float* weights_out, double ess_min, float* tau_out,
+                                       void* ws, size_t ws_bytes, rgfm_stream_t stream) {
+  if (!gamma_rows) return fail(RGFM_EINVAL, "null argument");
+  return guidance_block(x, y, vx, vy, mc_x1, mc_y1, mc_ratios, batch, n_mc, dim_x, dim_y, t, StageStrength(0.0, gamma_rows, 1.0),
+                        weights_out, ws, ws_bytes, stream, ess_min, tau_out);
+}
+extern "C" int rgfm_guidance_apply_cond_ess(const float* s, float* v, const float* mc_set, const float* ratios, int batch,
+                                            int n_mc, int dim, double t, const float* gamma_rows, float* weights_out,
+                                            double ess_min, float* tau_out, void* ws, size_t ws_bytes, rgfm_stream_t stream) {
+  if (!gamma_rows) return fail(RGFM_EINVAL, "null argument");
+  return guidance_block_cond(s, v, mc_set, ratios, batch, n_mc, dim, t, StageStrength(0.0, gamma_rows, 1.0), weights_out, ws,
+                             ws_bytes, stream, ess_min, tau_out);
 }
 
 // ---- diagnostics of one evaluation of the block (include/rgfm.h, "Guidance diagnostics")
@@ -314,6 +334,7 @@ int cond_loop(rgfm_unet* h, float* s_inout, const float* mc_set, const float* ra
   const int d = h->d.in_channels * h->d.img_size * h->d.img_size;
   if (d % 4) return fail(RGFM_EINVAL, "flattened image sizes must be multiples of 4");
   if (n_mc > 4096) return fail(RGFM_EINVAL, "n_mc too large (max 4096)");
+  if (int rc = c.ess.check(n_mc, loop_stages(c.solver, ns), c.batch)) return rc;
   Bump b(c.ws, c.ws_bytes);
   CondWs w = carve_cond(b, h, c.batch, n_mc, c.solver);
   if (sink.on()) sink.carve(b, d, 0);
@@ -325,6 +346,7 @@ int cond_loop(rgfm_unet* h, float* s_inout, const float* mc_set, const float* ra
   if (int rc = w.c.begin(s, c.num_steps, c.step_begin, ns)) return rc;
   if (sink.on())
     if (int rc = sink.begin(s, d, 0)) return rc;
+  if (int rc = c.ess.begin(s, loop_stages(c.solver, ns), c.batch)) return rc;
   // one stage: out = s + F(in, t) dts; guided iff the stage's own t > eps (`t > eps` test of the reference, :124)
   // and its scale is not 0
   auto stage = [&](const Stage& g) -> int {
@@ -338,7 +360,8 @@ int cond_loop(rgfm_unet* h, float* s_inout, const float* mc_set, const float* ra
     if (int rc = w.c.eval(g.row, s, in, w.v, nullptr, nullptr, dts)) return rc;
     return guidance_launch({.x = in, .vx = w.v, .mx = mc_set, .r = ratios, .ratio_stride = n_mc, .B = c.batch, .N = n_mc,
                             .dx = d, .t = g.t, .strength = c.strength.stage(g.row), .scratch = w.scratch, .xs = out,
-                            .xb = base, .dt = dts, .stream = s, .diag = sink.at(g.row)});
+                            .xb = base, .dt = dts, .stream = s, .diag = sink.at(g.row), .ess_min = c.ess.floor(),
+                            .tau_out = c.ess.at(g.row, c.batch)});
   };
   if (int rc = for_each_stage(c.solver, c.num_steps, c.step_begin, ns, stage)) return rc;
   HIP_TRY(hipGetLastError());
@@ -362,6 +385,8 @@ int pair_sample(rgfm_unet* hx, rgfm_unet* hy, float* x_inout, float* y_inout, co
   DiagSink sink;
   if (int rc = open_loop(c, hx && hy && x_inout && y_inout, &ns, &sink)) return rc;
   if (n_mc < 0 || (n_mc > 0 && (!mc_x1 || !mc_y1 || !mc_ratios))) return fail(RGFM_EINVAL, "MC set missing");
+  if (c.ess.on() && c.pairing == PAIRING_CROSS) return fail(RGFM_EINVAL, "the effective-sample-size floor does not go with cross pairing");
+  if (int rc = c.ess.check(n_mc, loop_stages(c.solver, ns), c.batch)) return rc;
   if (c.pairing == PAIRING_CROSS) {  // (what guidance_launch would refuse at the first guided stage, before anything is enqueued)
     if (n_mc > GUID_CROSS_MAX_N) return fail(RGFM_EINVAL, "cross pairing: n_mc %d too large (max %d)", n_mc, GUID_CROSS_MAX_N);
     for (const rgfm_unet* h : {hx, hy})
@@ -382,6 +407,7 @@ int pair_sample(rgfm_unet* hx, rgfm_unet* hy, float* x_inout, float* y_inout, co
   if (int rc = w.cy.begin(s, c.num_steps, c.step_begin, ns)) return rc;
   if (sink.on())
     if (int rc = sink.begin(s, w.cx.image_floats(), w.cy.image_floats())) return rc;
+  if (int rc = c.ess.begin(s, loop_stages(c.solver, ns), c.batch)) return rc;
   auto net = [](NetChain& n) { return [&n](auto... a) { return n.eval(a...); }; };  // pair_loop's eval: NetChain::eval
   return pair_loop(net(w.cx), net(w.cy),
                    {.x = x_inout, .y = y_inout, .mc_x1 = mc_x1, .mc_y1 = mc_y1, .mc_ratios = mc_ratios, .n_mc = n_mc,
@@ -611,4 +637,27 @@ extern "C" int rgfm_sample_cond_sde(rgfm_unet* h, float* s_inout, const float* m
                    {.batch = batch, .num_steps = num_steps, .step_begin = step_begin, .step_end = step_end, .solver = solver,
                     .strength = Strength(gamma, gamma_rows, stage_scale, n_stage_scale), .diag_out = diag_out,
                     .diag_records = diag_records, .ws = ws, .ws_bytes = ws_bytes, .stream = stream, .sde = sde});
+}
+
+// ---- the effective-sample-size floor (include/rgfm.h, "Effective-sample-size floor"): each loop is its *_sde namesake
+// with `const rgfm_ess* ess` in front of ws; null or ess_min <= 0: the namesake
+extern "C" int rgfm_sample_pair_ess(rgfm_unet* hx, rgfm_unet* hy, float* x_inout, float* y_inout, const float* mc_x1,
+                                    const float* mc_y1, const float* mc_ratios, int n_mc, int batch, int num_steps, double gamma,
+                                    const float* gamma_rows, const double* stage_scale, int n_stage_scale, int step_begin,
+                                    int step_end, int solver, float* diag_out, size_t diag_records, const rgfm_sde* sde,
+                                    const rgfm_ess* ess, void* ws, size_t ws_bytes, rgfm_stream_t stream) {
+  return pair_sample(hx, hy, x_inout, y_inout, mc_x1, mc_y1, mc_ratios, n_mc,
+                     {.batch = batch, .num_steps = num_steps, .step_begin = step_begin, .step_end = step_end, .solver = solver,
+                      .strength = Strength(gamma, gamma_rows, stage_scale, n_stage_scale), .diag_out = diag_out,
+                      .diag_records = diag_records, .ws = ws, .ws_bytes = ws_bytes, .stream = stream, .sde = sde, .ess = ess});
+}
+extern "C" int rgfm_sample_cond_ess(rgfm_unet* h, float* s_inout, const float* mc_set, const float* ratios, int n_mc, int batch,
+                                    int num_steps, double gamma, const float* gamma_rows, const double* stage_scale,
+                                    int n_stage_scale, int step_begin, int step_end, int solver, float* diag_out,
+                                    size_t diag_records, const rgfm_sde* sde, const rgfm_ess* ess, void* ws, size_t ws_bytes,
+                                    rgfm_stream_t stream) {
+  return cond_loop(h, s_inout, mc_set, ratios, n_mc,
+                   {.batch = batch, .num_steps = num_steps, .step_begin = step_begin, .step_end = step_end, .solver = solver,
+                    .strength = Strength(gamma, gamma_rows, stage_scale, n_stage_scale), .diag_out = diag_out,
+                    .diag_records = diag_records, .ws = ws, .ws_bytes = ws_bytes, .stream = stream, .sde = sde, .ess = ess});
 }

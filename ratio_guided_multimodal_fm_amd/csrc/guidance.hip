@@ -211,6 +211,118 @@ __global__ __launch_bounds__(256) void guid_weights_kernel(const GuidanceArgs a_
   if (lane == 0) a.wsum[b] = rsum;
 }
 
+// The same weights, held to an effective-sample-size floor (include/rgfm.h, "Effective-sample-size floor").  The first
+// half is guid_weights_kernel statement by statement -- the row's weights w of today, its Z_bar, its sum -- with the
+// log-density terms kept beside them (LDS: sl [4][N] and sw [4][N]).  ESS_1 = (sum w)^2 / sum w^2 in
+// guid_diag_wstats_kernel's arithmetic, n_pos = #{r_i > 0}, E* = min(ess_min, n_pos).  A row with ESS_1 >= E* (or E* <= 1,
+// or no positive ratio) leaves as guid_weights_kernel writes it, tau = 1: the tempered formula is never evaluated there.
+// A collapsed row: d_i = L_i - max_P L, L_i = l_i + log r_i over P = {r_i > 0} (samples outside P carry the marker -inf
+// and enter every sum as an exact 0: tau * -inf is never formed), 40 bisection steps on tau in [0, 1] for
+// ESS(tau) = (sum e^{tau d})^2 / sum e^{2 tau d} >= E* (one expf per sample and step, no early exit, no epsilon: the
+// largest term is 1), tau = lo, w_i = e^{tau d_i} / sum.  Every sum: lane l over samples l, l + 64, ... in index order,
+// then the xor butterfly -- fixed by N, so a row's result is the same in every batch.  Each lane reads back only the LDS
+// entries it wrote itself: no barrier.
+constexpr int ESS_BISECT = 40;
+__global__ __launch_bounds__(256) void guid_weights_ess_kernel(const GuidanceArgs a_in) {
+  const GuidanceArgs a = with_schedule(a_in);
+  extern __shared__ __attribute__((aligned(16))) float sw[];  // [4][N] weights, then [4][N] log-weights
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const int N = a.N;
+  const int b = blockIdx.x * 4 + wave;
+  if (b >= a.B) return;
+  float* swr = sw + (size_t)wave * N;
+  float* slr = sw + (size_t)(4 + wave) * N;
+  const float* ratios = a.mc_ratios + (size_t)b * a.ratio_stride;
+  float mx = -INFINITY;
+  for (int i = lane; i < N; i += 64) {
+    const float l = logp_of(a, b, i);
+    swr[i] = l;
+    slr[i] = l;
+    mx = fmaxf(mx, l);
+  }
+  mx = wave_max_g(mx);
+  float ps = 0.f, zs = 0.f;
+  for (int i = lane; i < N; i += 64) {
+    const float p = expf(swr[i] - mx);
+    swr[i] = p;
+    ps += p;
+    zs += __fmul_rn(ratios[i], p);
+  }
+  ps = wave_sum_g(ps);
+  zs = wave_sum_g(zs);
+  const float pbar = __fadd_rn(ps / (float)N, 1e-10f);
+  const float zbar = __fadd_rn(zs / (float)N, 1e-10f);
+  if (a.diag_rec && lane == 0) a.diag_rec[(size_t)b * RGFM_DIAG_FLOATS + RGFM_DIAG_Z_BAR] = zbar;  // (the untempered value)
+  float ws = 0.f;
+  for (int i = lane; i < N; i += 64) {
+    const float w = __fmul_rn(ratios[i] / zbar, swr[i] / pbar);
+    swr[i] = w;
+    ws += w;
+  }
+  ws = __fadd_rn(wave_sum_g(ws), 1e-10f);
+  float rsum = 0.f, q = 0.f, npos = 0.f, lmax = -INFINITY;
+  for (int i = lane; i < N; i += 64) {
+    const float w = swr[i] / ws;
+    swr[i] = w;
+    rsum += w;
+    q = fmaf(w, w, q);
+    const float r = ratios[i];
+    const float L = r > 0.f ? __fadd_rn(slr[i], logf(r)) : -INFINITY;
+    slr[i] = L;
+    npos += r > 0.f ? 1.f : 0.f;
+    lmax = fmaxf(lmax, L);
+  }
+  rsum = wave_sum_g(rsum), q = wave_sum_g(q), npos = wave_sum_g(npos), lmax = wave_max_g(lmax);
+  const float ess1 = q > 0.f ? __fmul_rn(rsum, rsum) / q : 0.f;
+  const float target = fminf(a.ess_min, npos);
+  float tau = 1.f;
+  // (wave-uniform: every lane holds the same reduced values.  E* <= 1 is met by every row -- an effective sample size
+  // is at least 1 -- whatever the rounding of ess1 says)
+  if (npos > 0.f && target > 1.f && !(ess1 >= target)) {
+    float lo = 0.f, hi = 1.f;
+    for (int it = 0; it < ESS_BISECT; ++it) {
+      const float mid = __fmul_rn(0.5f, __fadd_rn(lo, hi));
+      float s1 = 0.f, s2 = 0.f;
+      for (int i = lane; i < N; i += 64) {
+        const float L = slr[i];
+        const float e = L == -INFINITY ? 0.f : expf(__fmul_rn(mid, __fsub_rn(L, lmax)));
+        s1 += e;
+        s2 = fmaf(e, e, s2);
+      }
+      s1 = wave_sum_g(s1), s2 = wave_sum_g(s2);
+      if (__fmul_rn(s1, s1) / s2 >= target) lo = mid;  // (s2 >= 1: the sample at the maximum)
+      else hi = mid;
+    }
+    // (lmax is finite here: some r_i > 0, and l_i is finite for finite inputs.  A row whose every l_i is -inf -- a
+    // distance that overflows fp32 -- would give d = nan, as it gives nan weights in the sibling)
+    tau = lo;
+    float s1 = 0.f;
+    for (int i = lane; i < N; i += 64) {
+      const float L = slr[i];
+      const float e = L == -INFINITY ? 0.f : expf(__fmul_rn(tau, __fsub_rn(L, lmax)));
+      swr[i] = e;
+      s1 += e;
+    }
+    s1 = wave_sum_g(s1);
+    rsum = 0.f;
+    for (int i = lane; i < N; i += 64) {
+      const float w = swr[i] / s1;
+      swr[i] = w;
+      rsum += w;
+    }
+    rsum = wave_sum_g(rsum);
+  }
+  for (int i = lane; i < N; i += 64) {
+    const float w = swr[i];
+    a.wbuf[(size_t)b * N + i] = w;
+    if (a.weights_out) a.weights_out[(size_t)b * N + i] = w;
+  }
+  if (lane == 0) {
+    a.wsum[b] = rsum;
+    if (a.tau_out) a.tau_out[b] = tau;
+  }
+}
+
 // The guided velocity g_b = sum_i w_bi (m_i - x_b) / c (sample_mnist_svhn.py:157-160) as the fp32 GEMM it is:
 //   g_b = (sum_i w_bi m_i  -  x_b sum_i w_bi) / c,   [B, N] x [N, D] on v_mfma_f32_32x32x2_f32 (exact fp32 products, fp32
 // accumulation: the arithmetic of an fmaf chain), then the blend (1 - gamma) v + gamma g and the optional Euler update in
@@ -594,11 +706,17 @@ int guid_apply_init() {  // (64 KB of dynamic LDS)
   for (const void* k : {reinterpret_cast<const void*>(&guid_apply_mfma_kernel<true, false>), reinterpret_cast<const void*>(&guid_apply_mfma_kernel<false, false>),
                         reinterpret_cast<const void*>(&guid_apply_mfma_kernel<true, true>), reinterpret_cast<const void*>(&guid_apply_mfma_kernel<false, true>)})
     rc |= (int)hipFuncSetAttribute(k, hipFuncAttributeMaxDynamicSharedMemorySize, 64 * 1024);
+  // (the floor's weights kernel: two [4][N] arrays, 128 KB of the CU's 160 at n_mc = 4096 -- no smaller cap than its sibling's)
+  rc |= (int)hipFuncSetAttribute(reinterpret_cast<const void*>(&guid_weights_ess_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, 128 * 1024);
   return rc;
 }
 
 void launch_guid_weights(const GuidanceArgs& a, hipStream_t s) {  // (needs the distances only: no velocity)
   hipLaunchKernelGGL(guid_weights_kernel, dim3((a.B + 3) / 4), dim3(256), (size_t)4 * a.N * sizeof(float), s, a);
+}
+
+void launch_guid_weights_ess(const GuidanceArgs& a, hipStream_t s) {
+  hipLaunchKernelGGL(guid_weights_ess_kernel, dim3((a.B + 3) / 4), dim3(256), (size_t)8 * a.N * sizeof(float), s, a);
 }
 
 void launch_guid_apply(const GuidanceArgs& a, hipStream_t s) {

@@ -949,6 +949,10 @@ struct GuidanceCall {
   GuidDiag diag{};  // rec null: no diagnostics
   int pairing = PAIRING_PAIRED;
   GuidPhase phase = GuidPhase::All;
+  // effective-sample-size floor (include/rgfm.h): ess_min > 0 swaps the weights kernel for its tempering sibling, which
+  // writes the rows' exponents to tau_out [B] (or nowhere: null); 0: off.  Paired and one-sided blocks only.
+  double ess_min = 0.0;
+  float* tau_out = nullptr;
 };
 
 inline int guidance_launch(const GuidanceCall& c) {
@@ -963,6 +967,7 @@ inline int guidance_launch(const GuidanceCall& c) {
   const bool cross = c.pairing == PAIRING_CROSS;
   if (cross && (N < 1 || N > GUID_CROSS_MAX_N || dy < 1))
     return fail(RGFM_EINVAL, "cross pairing needs two modalities and 1 <= n_mc <= %d (got %d)", GUID_CROSS_MAX_N, N);
+  if (cross && c.ess_min > 0.0) return fail(RGFM_EINVAL, "the effective-sample-size floor does not go with cross pairing");
   // Python-double scalar arithmetic of the reference (sample_mnist_svhn.py:115,127,135,159,170),
   // rounded to fp32 where a tensor op consumes it.
   GuidanceArgs a{};
@@ -975,6 +980,7 @@ inline int guidance_launch(const GuidanceCall& c) {
   a.gamma_rows = c.strength.rows, a.gamma_scale = c.strength.scale;
   a.dist = reinterpret_cast<double*>(scratch), a.weights_out = c.weights_out, a.x_state = c.xs, a.y_state = c.ys, a.dt = c.dt;
   a.diag_rec = diag.rec;
+  a.ess_min = (float)c.ess_min, a.tau_out = c.tau_out;
   a.x_base = xb == x ? nullptr : xb, a.y_base = yb == y ? nullptr : yb;
   a.wbuf = reinterpret_cast<float*>(reinterpret_cast<char*>(scratch) + guid_dist_bytes(B, N));
   a.wsum = reinterpret_cast<float*>(reinterpret_cast<char*>(a.wbuf) + guid_wbuf_bytes(B, N));
@@ -995,6 +1001,7 @@ inline int guidance_launch(const GuidanceCall& c) {
     ProfScope p(RGFM_KCLASS_GUID_LOGP, 4.0 * (B + N) * D + dist_b, s);
     launch_guid_logp(a, s);
     if (cross) launch_guid_cross_weights(a, s);  // (with diag: the joint ESS, the marginals' range and Z_bar too)
+    else if (c.ess_min > 0.0) launch_guid_weights_ess(a, s);
     else launch_guid_weights(a, s);
   }
   if (phase != GuidPhase::Apply && diag.rec && !cross) launch_diag_wstats(a.wbuf, B, N, diag.rec, s);

@@ -473,10 +473,16 @@ struct GuidanceArgs {
   // scalar fields, per row; null: g1 / g2 above for every row
   const float* gamma_rows;
   double gamma_scale;
+  // optional effective-sample-size floor (include/rgfm.h, "Effective-sample-size floor"; read by guid_weights_ess_kernel
+  // alone): ess_min >= 1 as fp32, and the row's exponent tau goes to tau_out[b] when that is not null
+  float ess_min;
+  float* tau_out;
 };
 constexpr int RGFM_GUID_SLICES = 8;
 void launch_guid_logp(const GuidanceArgs& a, hipStream_t s);   // distances -> GuidanceArgs::dist
 void launch_guid_weights(const GuidanceArgs& a, hipStream_t s);  // distances + ratios -> importance weights (GuidanceArgs::wbuf, wsum)
+// ... held to the floor GuidanceArgs::ess_min (a sibling kernel: twice the LDS, [4][N] log-weights beside the [4][N] weights)
+void launch_guid_weights_ess(const GuidanceArgs& a, hipStream_t s);
 void launch_guid_cross_weights(const GuidanceArgs& a, hipStream_t s);  // cross pairing: distances + R -> marginal weights (wbuf, wbuf_y and their sums; the diagnostics' weight entries)
 void launch_guid_apply(const GuidanceArgs& a, hipStream_t s);  // guided velocity (the [B,N] x [N,D] GEMM), blend (+ Euler)
 int guid_apply_init();                                         // (once per process: the GEMM kernel's LDS size)

@@ -124,6 +124,41 @@ inline size_t sde_scratch_bytes(int batch, size_t dx, size_t dy) {
   return b.off;
 }
 
+// The effective-sample-size floor of an MC loop (include/rgfm.h, "Effective-sample-size floor"): no rgfm_ess, or
+// ess_min <= 0, is off, and every loop then enqueues what it enqueues without the argument.  On, each guided stage's
+// weights kernel is guid_weights_ess_kernel, and block Stage::row of tau_out ([stages][batch], or null) receives the
+// rows' exponents; `begin` zeroes the blocks, so an unguided stage's stay 0.
+struct Ess {
+  double ess_min = 0.0;
+  float* tau_out = nullptr;
+  size_t tau_records = 0;
+  Ess() = default;
+  Ess(const rgfm_ess* a) {  // (null: off)
+    if (a) ess_min = a->ess_min, tau_out = a->tau_out, tau_records = a->tau_records;
+  }
+  bool on() const { return !(ess_min <= 0.0); }  // (NaN counts as on, and fails the check)
+  // the argument check of every *_ess entry point, before anything is carved or enqueued
+  static int check_min(double ess_min, int n_mc) {
+    if (!std::isfinite(ess_min)) return fail(RGFM_EINVAL, "ess: ess_min must be finite (got %g)", ess_min);
+    if (ess_min < 1.0) return fail(RGFM_EINVAL, "ess: ess_min %g in (0, 1): an effective sample size is at least 1", ess_min);
+    if (ess_min > (double)n_mc) return fail(RGFM_EINVAL, "ess: ess_min %g > n_mc %d", ess_min, n_mc);
+    return RGFM_OK;
+  }
+  int check(int n_mc, int n_stages, int batch) const {
+    if (!on()) return RGFM_OK;
+    if (int rc = check_min(ess_min, n_mc)) return rc;
+    if (tau_out && tau_records < (size_t)n_stages * batch)
+      return fail(RGFM_EINVAL, "ess: tau_records %zu < %d stages x %d samples", tau_records, n_stages, batch);
+    return RGFM_OK;
+  }
+  int begin(hipStream_t s, int n_stages, int batch) const {
+    if (on() && tau_out) HIP_TRY(hipMemsetAsync(tau_out, 0, (size_t)n_stages * batch * sizeof(float), s));
+    return RGFM_OK;
+  }
+  float* at(int row, int batch) const { return on() && tau_out ? tau_out + (size_t)row * batch : nullptr; }
+  double floor() const { return on() ? ess_min : 0.0; }
+};
+
 // The call-level arguments of a sampler loop, filled by field name in its extern "C" wrapper; the loop's own operands
 // (handles, states, MC set) travel beside it.  What an entry point has no argument for keeps its default.
 struct LoopCall {
@@ -136,6 +171,7 @@ struct LoopCall {
   rgfm_stream_t stream = nullptr;
   int pairing = PAIRING_PAIRED;  // (the U-Net pair loop)
   Sde sde;                       // (the *_sde entry points)
+  Ess ess;                       // (the *_ess entry points)
 };
 // The head of every guided loop, in this order: the switches, check_loop (`have_args`: the loop's own pointers), the
 // stochastic step's arguments, the sink's, the strength's.  The loop's own argument checks follow it, then its carve and check_workspace.
@@ -251,9 +287,10 @@ int pair_loop(EvalX&& eval_x, EvalY&& eval_y, const PairOperands& p, const LoopC
   hipEvent_t ev_fork = ds->fork, ev_join = ds->join;
   // (diagnostics: kernel by kernel -- each stage writes its own records, a replayed graph would write one stage's)
   // (cross pairing: kernel by kernel as well)
-  const bool use_graph = p.gstate && g_modes.graph && !g_prof.on && n_mc > 0 && ns >= 4 && solver == SOLVER_EULER && !sink.on() && c.pairing == PAIRING_PAIRED && !strength.is_data() && !c.sde.on();
+  const bool use_graph = p.gstate && g_modes.graph && !g_prof.on && n_mc > 0 && ns >= 4 && solver == SOLVER_EULER && !sink.on() && c.pairing == PAIRING_PAIRED && !strength.is_data() && !c.sde.on() && !c.ess.on();
   // (a strength that is data -- per row or per stage -- runs kernel by kernel: the replayed graph holds one stage's scalars)
   // (the stochastic step: kernel by kernel as well -- its noise key and scalars are launch arguments of the step)
+  // (the effective-sample-size floor: kernel by kernel as well -- each stage writes its own block of tau_out)
   const hipStream_t caller = (hipStream_t)c.stream;
   hipStream_t s = caller;
   if (use_graph && caller == nullptr) {  // (see DevState::main)
@@ -288,7 +325,8 @@ int pair_loop(EvalX&& eval_x, EvalY&& eval_y, const PairOperands& p, const LoopC
     GuidanceCall gc{.x = xin, .y = yin, .vx = vx, .vy = vy, .mx = p.mc_x1, .my = p.mc_y1, .r = p.mc_ratios,
                     .B = c.batch, .N = n_mc, .dx = p.dx, .dy = p.dy, .t = g.t, .strength = strength.stage(g.row),
                     .scratch = p.scratch, .xs = xout, .ys = yout, .xb = xb, .yb = yb, .dt = dts, .stream = s,
-                    .sched = sched_dev, .step_ptr = step_dev, .diag = sink.at(g.row), .pairing = c.pairing};
+                    .sched = sched_dev, .step_ptr = step_dev, .diag = sink.at(g.row), .pairing = c.pairing,
+                    .ess_min = c.ess.floor(), .tau_out = c.ess.at(g.row, c.batch)};
     if (overlap) {
       HIP_TRY(hipEventRecord(ev_fork, s));
       HIP_TRY(hipStreamWaitEvent(side, ev_fork, 0));

@@ -89,7 +89,7 @@ def _all_gather_rows(t, counts, group):
 
 def sharded_paired_sampler(fm_x, fm_y, ratio_estimator, guidance_method, guidance_strength, num_steps,
                            noise, device, backend=None, group=None, gather="rank0", keep=None, solver='euler',
-                           mc_pairing='paired', guidance_schedule=None, sde_eta=0.0, sde_seed=None):
+                           mc_pairing='paired', guidance_schedule=None, sde_eta=0.0, sde_seed=None, ess_floor=None):
     """Sharded equivalent of ``paired_sampler`` on explicit host noise.
 
     noise = (x0, y0, mc_x0, mc_y0): the FULL tensors, identical on every rank
@@ -104,12 +104,15 @@ def sharded_paired_sampler(fm_x, fm_y, ratio_estimator, guidance_method, guidanc
     guidance_schedule / a guidance_strength per sample (``paired_sampler``): no sharded form either: RgfmError.
     sde_eta > 0 (the stochastic sampler, ``paired_sampler``): no sharded form either -- the noise is keyed by the
     element's place in the whole batch, which a rank's loop does not know: RgfmError.
+    ess_floor (the effective-sample-size floor, ``paired_sampler``): no sharded form either: RgfmError.
     """
     from ._lib import RgfmError, solver_id
     from .utils.flow_utils import check_pairing
     solver_id(solver)
     if sde_eta:
         raise RgfmError("sde_eta > 0 (the stochastic sampler) has no sharded form: run it on one device")
+    if ess_floor is not None:
+        raise RgfmError("ess_floor (the effective-sample-size floor) has no sharded form: run it on one device")
     if guidance_schedule is not None or isinstance(guidance_strength, (torch.Tensor, list, tuple)):
         raise RgfmError("a guidance_schedule and a guidance strength per sample have no sharded form: run them on one device")
     if check_pairing(mc_pairing, guidance_method) == 'cross':
@@ -219,10 +222,13 @@ def make_sharded_sampler(shape_x, shape_y, backend=None, group=None, gather="all
     stream exactly like the reference's sweep (evaluate_mnist_svhn.py:80: one seeding, no re-seed)."""
     def sampler(fm_x, fm_y, ratio_estimator=None, guidance_method='none', guidance_strength=0.0, num_samples=16,
                 num_steps=100, device='cuda', mc_batch_size=64, solver='euler', mc_pairing='paired',
-                guidance_schedule=None, sde_eta=0.0, sde_seed=None):
+                guidance_schedule=None, sde_eta=0.0, sde_seed=None, ess_floor=None):
         if sde_eta:  # (before any draw)
             from ._lib import RgfmError
             raise RgfmError("sde_eta > 0 (the stochastic sampler) has no sharded form: run it on one device")
+        if ess_floor is not None:
+            from ._lib import RgfmError
+            raise RgfmError("ess_floor (the effective-sample-size floor) has no sharded form: run it on one device")
         guided = guidance_method == 'mc_feng' and ratio_estimator is not None
         x0 = torch.randn(num_samples, *shape_x)
         y0 = torch.randn(num_samples, *shape_y)

@@ -29,7 +29,7 @@ from .models.unet_flexible import FlowMatchingUNetMNIST, FlowMatchingUNetSVHN
 from .sample_mnist_svhn import sample_bimodal_guided_mnist_svhn
 from .utils import load_checkpoint, set_seed
 from .utils.diagnostics import GuidanceDiagnostics, add_cli_args as add_diagnostics_args, row_metrics
-from .utils.flow_utils import add_sde_args, sde_from_cli, add_pairing_arg, shared_mc_sweep
+from .utils.flow_utils import add_ess_arg, add_sde_args, ess_from_cli, sde_from_cli, add_pairing_arg, shared_mc_sweep
 from .utils.guidance_schedule import add_cli_args as add_schedule_args, from_cli as schedule_from_cli
 
 
@@ -69,7 +69,7 @@ def evaluate_conditional_coherence(condition, samples, given, mnist_classifier, 
 
 def run_sweep(fm_mnist, fm_svhn, make_ratio, mnist_classifier, svhn_classifier, methods, strengths,
               num_samples, num_steps, device, mc_batch_size, sampler=sample_bimodal_guided_mnist_svhn, solver='euler', diagnostics=False,
-              mc_pairing='paired', shared_mc=False, guidance_schedule=None, sde_eta=0.0, sde_seed=None):
+              mc_pairing='paired', shared_mc=False, guidance_schedule=None, sde_eta=0.0, sde_seed=None, ess_floor=None):
     """The reference's nested loop (:130-183). `make_ratio()` returns a fresh ratio estimator or None.
     `solver` ('euler' | 'midpoint') goes to `sampler` as a keyword when it is not the default.
     `diagnostics`: every guided row also gets ess_mean, ess_min and w_max of the importance weights at step
@@ -82,7 +82,10 @@ def run_sweep(fm_mnist, fm_svhn, make_ratio, mnist_classifier, svhn_classifier, 
     (``utils.flow_utils.shared_mc_sweep``): the strengths' numbers then differ by the strength alone.  Every row of
     the result gains ``"shared_mc": true``.  The default sampler only (no sharded form).
     `sde_eta` > 0: every sampler call takes Euler-Maruyama steps (``paired_sampler``; `sde_seed` None: each call draws its
-    own seed after its other draws); the keywords go to `sampler` only then, and every row gains ``"sde_eta"``."""
+    own seed after its other draws); the keywords go to `sampler` only then, and every row gains ``"sde_eta"``.
+    `ess_floor`: the 'mc_feng' configurations hold their importance weights to this effective sample size
+    (``paired_sampler``; the sampler's `ess_floor` keyword) and their rows record ``"ess_floor"``; it goes with no
+    gradient method among `methods` (they have no weights: ``RgfmError``) and has no sharded form.  None: nothing changes."""
     from ._lib import solver_id
     from .utils.flow_utils import check_pairing
     solver_id(solver)
@@ -93,19 +96,29 @@ def run_sweep(fm_mnist, fm_svhn, make_ratio, mnist_classifier, svhn_classifier, 
     sde = {'sde_eta': float(sde_eta), 'sde_seed': sde_seed} if sde_eta else {}
     sde_row = {'sde_eta': float(sde_eta)} if sde_eta else {}
     kw.update(sde)
+    if ess_floor is not None:
+        from ._lib import RgfmError
+        if any(m not in ('none', 'mc_feng') for m in methods):
+            raise RgfmError(f"ess_floor tempers the importance weights of 'mc_feng'; {list(methods)} holds a gradient method, "
+                            "which has no weights: sweep it in a run of its own")
+        if sampler is not sample_bimodal_guided_mnist_svhn:
+            raise RgfmError("ess_floor has no sharded form: run the tempered sampler on one device")
     if shared_mc and sampler is not sample_bimodal_guided_mnist_svhn:
         raise ValueError("shared_mc runs the default sampler: it has no sharded form")
     results = []
     for method in methods:
+        # `extra` (below): what an 'mc_feng' configuration adds, to the sampler's keywords and to its result rows alike
         if shared_mc and method != 'none':
             ratio = make_ratio()
             if ratio is None:
                 continue
             diag = GuidanceDiagnostics() if diagnostics else None
-            cross = {'mc_pairing': 'cross'} if mc_pairing == 'cross' and method == 'mc_feng' else {}
+            extra = {'mc_pairing': 'cross'} if mc_pairing == 'cross' and method == 'mc_feng' else {}
+            if ess_floor is not None and method == 'mc_feng':
+                extra['ess_floor'] = float(ess_floor)
             blocks = shared_mc_sweep(fm_mnist, fm_svhn, ratio, method, strengths, num_samples, num_steps, device,
                                      mc_batch_size, (1, 32, 32), (3, 32, 32), solver=solver, diagnostics=diag,
-                                     guidance_schedule=guidance_schedule, **cross, **sde)
+                                     guidance_schedule=guidance_schedule, **extra, **sde)
             for j, (strength, (xs, ys)) in enumerate(zip(strengths, blocks)):
                 metrics = evaluate_coherence(xs, ys, mnist_classifier, svhn_classifier, device)
                 if diag is not None and diag.records is not None:
@@ -113,7 +126,7 @@ def run_sweep(fm_mnist, fm_svhn, make_ratio, mnist_classifier, svhn_classifier, 
                                                             solver, num_steps)
                     metrics = {**metrics, **row_metrics(part, num_steps)}
                 results.append({'method': method, 'guidance_strength': strength, 'experiment': 'mnist_svhn',
-                                **metrics, **cross, **sde_row, 'shared_mc': True})
+                                **metrics, **extra, **sde_row, 'shared_mc': True})
                 print(f"  method={method} gamma={strength} -> coherence accuracy {metrics['coherence_acc']:.3f}")
             continue
         for strength in strengths:
@@ -123,16 +136,18 @@ def run_sweep(fm_mnist, fm_svhn, make_ratio, mnist_classifier, svhn_classifier, 
             if method != 'none' and ratio is None:
                 continue
             diag = GuidanceDiagnostics() if diagnostics and method != 'none' else None
-            cross = {'mc_pairing': 'cross'} if mc_pairing == 'cross' and method == 'mc_feng' else {}
+            extra = {'mc_pairing': 'cross'} if mc_pairing == 'cross' and method == 'mc_feng' else {}
+            if ess_floor is not None and method == 'mc_feng':
+                extra['ess_floor'] = float(ess_floor)
             xs, ys = sampler(fm_mnist, fm_svhn, ratio, method, strength, num_samples, num_steps, device,
-                             mc_batch_size, **kw, **({'diagnostics': diag} if diag is not None else {}), **cross)
+                             mc_batch_size, **kw, **({'diagnostics': diag} if diag is not None else {}), **extra)
             metrics = evaluate_coherence(xs, ys, mnist_classifier, svhn_classifier, device)
             if diag is not None and diag.records is not None:
                 metrics = {**metrics, **row_metrics(diag, num_steps)}
             if shared_mc:
                 metrics = {**metrics, 'shared_mc': True}
             results.append({'method': method, 'guidance_strength': strength, 'experiment': 'mnist_svhn',
-                            **metrics, **cross, **sde_row})
+                            **metrics, **extra, **sde_row})
             print(f"  method={method} gamma={strength} -> coherence accuracy {metrics['coherence_acc']:.3f}")
     return results
 
@@ -157,13 +172,14 @@ def main(argv=None):
     add_pairing_arg(p)
     add_schedule_args(p)
     add_sde_args(p)
+    add_ess_arg(p)
     p.add_argument('--shared_mc', action='store_true',
                    help='run all strengths of a guided method as one sampler call over one MC set, one pre-phase and one '
                         'start-noise set (a strength per row): the strengths then differ by the strength alone; not with '
                         '--sharded')
     args = p.parse_args(argv)
     schedule = schedule_from_cli(args)
-    sde_kw = sde_from_cli(args, args.sharded)
+    sde_kw = {**sde_from_cli(args, args.sharded), **ess_from_cli(args, args.sharded)}
     if args.shared_mc and args.sharded:
         p.error('--shared_mc has no --sharded form')
     if schedule is not None and args.sharded:

@@ -16,7 +16,7 @@ from .models.ratio_estimator import RatioEstimator
 from .models.unet import FlowMatchingUNet
 from .utils import load_checkpoint, set_seed
 from .utils.diagnostics import GuidanceDiagnostics, add_cli_args as add_diagnostics_args, report_diagnostics
-from .utils.flow_utils import add_pairing_arg, add_sde_args, sample_bimodal_guided, sde_from_cli
+from .utils.flow_utils import add_ess_arg, add_pairing_arg, add_sde_args, ess_from_cli, sample_bimodal_guided, sde_from_cli
 from .utils.guidance_schedule import add_cli_args as add_schedule_args, from_cli as schedule_from_cli
 from .utils.path_utils import get_checkpoint_path
 
@@ -53,9 +53,10 @@ def main(argv=None):
     add_pairing_arg(p)
     add_schedule_args(p)
     add_sde_args(p)
+    add_ess_arg(p)
     args = p.parse_args(argv)
     schedule = schedule_from_cli(args)
-    sde_kw = sde_from_cli(args)
+    sde_kw = {**sde_from_cli(args), **ess_from_cli(args)}
     if schedule is not None and args.model != 'unet':
         p.error('--guidance_schedule / --guidance_window go with --model unet')
     if args.mc_pairing == 'cross' and (args.guidance_method != 'mc_feng' or args.model != 'unet'):

@@ -14,22 +14,23 @@ from .models.ratio_flexible import RatioEstimatorMNISTSVHN
 from .models.unet_flexible import FlowMatchingUNetMNIST, FlowMatchingUNetSVHN
 from .utils import load_checkpoint, set_seed
 from .utils.diagnostics import GuidanceDiagnostics, add_cli_args as add_diagnostics_args, report_diagnostics
-from .utils.flow_utils import add_pairing_arg, add_sde_args, paired_sampler, sample_conditional, sde_from_cli
+from .utils.flow_utils import add_ess_arg, add_pairing_arg, add_sde_args, ess_from_cli, paired_sampler, sample_conditional, sde_from_cli
 from .utils.guidance_schedule import add_cli_args as add_schedule_args, from_cli as schedule_from_cli
 
 
 def sample_bimodal_guided_mnist_svhn(fm_mnist, fm_svhn, ratio_estimator=None, guidance_method='none',
                                      guidance_strength=0.0, num_samples=16, num_steps=100,
                                      device='cuda', mc_batch_size=64, solver='euler', diagnostics=None,
-                                     mc_pairing='paired', guidance_schedule=None, sde_eta=0.0, sde_seed=None):
+                                     mc_pairing='paired', guidance_schedule=None, sde_eta=0.0, sde_seed=None,
+                                     ess_floor=None):
     """Returns ``(samples_mnist [n,1,32,32], samples_svhn [n,3,32,32])`` on `device`.  `diagnostics`: a
     ``utils.diagnostics.GuidanceDiagnostics`` to fill; `mc_pairing`: 'paired' | 'cross'; `guidance_strength`: a float or
-    one strength per sample; `guidance_schedule`: a scale of it per stage; `sde_eta`, `sde_seed`: the stochastic sampler
-    (all: ``paired_sampler``)."""
+    one strength per sample; `guidance_schedule`: a scale of it per stage; `sde_eta`, `sde_seed`: the stochastic sampler;
+    `ess_floor`: the effective-sample-size floor of the importance weights (all: ``paired_sampler``)."""
     return paired_sampler(fm_mnist, fm_svhn, ratio_estimator, guidance_method, guidance_strength,
                           num_samples, num_steps, device, mc_batch_size, (1, 32, 32), (3, 32, 32), solver=solver,
                           diagnostics=diagnostics, mc_pairing=mc_pairing, guidance_schedule=guidance_schedule,
-                          sde_eta=sde_eta, sde_seed=sde_seed)
+                          sde_eta=sde_eta, sde_seed=sde_seed, ess_floor=ess_floor)
 
 
 def load_condition(path, shape):
@@ -72,9 +73,10 @@ def main(argv=None):
     add_pairing_arg(p)
     add_schedule_args(p)
     add_sde_args(p)
+    add_ess_arg(p)
     args = p.parse_args(argv)
     schedule = schedule_from_cli(args)
-    sde_kw = sde_from_cli(args, args.sharded)
+    sde_kw = {**sde_from_cli(args, args.sharded), **ess_from_cli(args, args.sharded)}
     if schedule is not None and args.sharded:
         p.error('--guidance_schedule / --guidance_window have no --sharded form')
     if args.mc_pairing == 'cross' and (args.guidance_method != 'mc_feng' or args.given or args.sharded):

@@ -12,6 +12,10 @@ return value and its bits do not change; after the call the object holds
     t, sigma_t   float64 CPU tensors [n_stages]: each stage's time by the loops' own formulas and 1 - t + 1e-3
     guided    bool CPU tensor [n_stages]: the stage ran with guidance ('mc_feng': t > 1e-3 and an MC set; the first
               stage of a run never is, and its records are all zero)
+    tau       with ``ess_floor=`` only (else None): device tensor [n_stages, B], the exponent each row's importance
+              weights were tempered by at the stage -- 1: the row was at or above the floor and kept its weights,
+              0: the stage ran unguided.  ess / w_max / w_min are then those of the tempered weights, z_bar stays the
+              untempered value
 
 MC guidance fills every field; an effective sample size near 1 means one MC sample carries the row ("copy the nearest
 MC sample").  Gradient log-ratio guidance fills the four norms (``g`` is ``grad log r`` before gamma) and leaves
@@ -66,6 +70,7 @@ class GuidanceDiagnostics:
 
     def __init__(self):
         self.records = self.t = self.sigma_t = self.guided = None
+        self.tau = None  # with ess_floor=: the rows' tempering exponents [n_stages, B] (1: untouched, 0: unguided stage)
         self.method = self.solver = None
         self.num_steps = self.step_begin = None
 
@@ -90,7 +95,13 @@ class GuidanceDiagnostics:
         if stage_scale is not None:
             self.guided = self.guided & torch.tensor([float(v) != 0.0 for v in stage_scale], dtype=torch.bool)
         self.records = torch.zeros(n, batch, DIAG_FLOATS, dtype=torch.float32, device=device)
+        self.tau = None
         return self.records
+
+    def _begin_tau(self):
+        """A fresh exponents tensor [n_stages, batch] beside the records of _begin, for a loop with an ess_floor."""
+        self.tau = torch.zeros(self.records.shape[:2], dtype=torch.float32, device=self.records.device)
+        return self.tau
 
     @classmethod
     def from_records(cls, records, method, solver, num_steps, step_begin=0, step_end=None, has_mc=True):

@@ -221,6 +221,43 @@ def sde_from_cli(args, sharded=False):
     return {'sde_eta': args.sde_eta, 'sde_seed': args.sde_seed}
 
 
+def add_ess_arg(p):
+    """--ess_floor of the command-line tools."""
+    p.add_argument('--ess_floor', type=float, default=None,
+                   help="MC guidance (mc_feng): hold every row's importance weights to this effective sample size by "
+                        "tempering them with an exponent tau <= 1 of the row's own (1 <= ess_floor <= mc_batch_size; "
+                        "U-Net nets, --mc_pairing paired; not with --sharded).  Default: the plain weights")
+
+
+def ess_from_cli(args, sharded=False):
+    """Sampler keywords of --ess_floor: {} without it, so that the call goes out as it always did."""
+    from .._lib import RgfmError
+    if getattr(args, 'ess_floor', None) is None:
+        return {}
+    if sharded:
+        raise RgfmError("--ess_floor has no --sharded form: run the tempered sampler on one device")
+    return {'ess_floor': args.ess_floor}
+
+
+def _ess_kwargs(ess_floor, guidance_method, guided, n_mc, models, cross, diagnostics, diag):
+    """Keywords of the MC loop's _engine call for an effective-sample-size floor; every check runs here or in
+    _engine.check_ess, before any device work.  None gives {}: the call goes out as it always did.  With records
+    (`diag`, what diagnostics._begin returned) the object's `tau` [n_stages, B] is allocated and handed to the loop."""
+    from .._lib import RgfmError
+    if ess_floor is None:
+        return {}
+    if guidance_method != 'mc_feng':
+        raise RgfmError(f"ess_floor holds the importance weights of guidance_method='mc_feng' to a floor; "
+                        f"{guidance_method!r} has no weights to temper")
+    floor = _engine.check_ess(ess_floor, n_mc, models, cross)
+    if not guided:  # (mc_feng without a ratio estimator runs unguided, as in the reference: nothing to temper)
+        return {}
+    kw = {'ess_floor': floor}
+    if diag is not None:
+        kw['tau'] = diagnostics._begin_tau()
+    return kw
+
+
 def _strength_kwargs(guidance_strength, guidance_schedule, rows, num_steps, solver, dev_of, models, what='num_samples'):
     """(gamma, keywords) of the main loop's _engine call for a strength that may be a vector and a schedule that may be
     given: all checks run here, before any device work.  A scalar strength without a schedule gives (the strength as
@@ -247,8 +284,18 @@ def _stats(name, t):
 
 def paired_sampler(fm_x, fm_y, ratio_estimator, guidance_method, guidance_strength, num_samples,
                    num_steps, device, mc_batch_size, shape_x, shape_y, noise=None, verbose=True, solver='euler',
-                   diagnostics=None, mc_pairing='paired', guidance_schedule=None, sde_eta=0.0, sde_seed=None):
+                   diagnostics=None, mc_pairing='paired', guidance_schedule=None, sde_eta=0.0, sde_seed=None,
+                   ess_floor=None):
     """Shared body of both paired samplers.
+
+    `ess_floor` (None, or a float with 1 <= ess_floor <= mc_batch_size): adaptive tempering of the MC importance
+    weights (``guidance_method='mc_feng'``, ``rgfm_sample_pair_ess``).  At every guided stage a
+    row whose effective sample size is below the floor has its weights flattened by an exponent tau <= 1 of its own,
+    found by bisection so that the effective sample size reaches the floor; rows at or above it keep their bits.  With
+    `diagnostics` the object gains ``tau`` [n_stages, B] (1: untouched, 0: the stage ran unguided) and its ess / w_max /
+    w_min are those of the tempered weights.  Tempering biases the estimator toward the flatter posterior mean.  Both
+    solvers, strength rows and schedules, `sde_eta`; not with ``mc_pairing='cross'``, the gradient method,
+    ``FlowMatchingModel`` nets or sharded launches (``RgfmError``).  None (default): the call is what it was.
 
     `sde_eta` > 0: the main loop takes Euler-Maruyama steps of ``dx = [F + eta (t F - x)] dt + sqrt(2 eta (1 - t)) dW``,
     the SDE that shares the marginals of the ODE ``dx = F dt`` on the path ``x_t = (1 - t) x_0 + t x_1`` (F: the loop's
@@ -291,6 +338,7 @@ def paired_sampler(fm_x, fm_y, ratio_estimator, guidance_method, guidance_streng
     eta = _engine.check_sde(sde_eta, solver, (fm_x, fm_y))
     guidance_strength, gs_kw = _strength_kwargs(guidance_strength, guidance_schedule, num_samples, num_steps, solver,
                                                 lambda: _device(device), (fm_x, fm_y))
+    _ess_kwargs(ess_floor, guidance_method, False, mc_batch_size, (fm_x, fm_y), mc_pairing == 'cross', None, None)
     fm_x.eval()
     fm_y.eval()
     if ratio_estimator is not None:
@@ -348,14 +396,16 @@ def paired_sampler(fm_x, fm_y, ratio_estimator, guidance_method, guidance_streng
     diag = None
     if diagnostics is not None and num_samples:
         diag = diagnostics._begin('mc_feng' if guided else 'none', solver, num_steps, num_samples, dev, stage_scale=gs_kw.get('stage_scale'))
+    ess_kw = _ess_kwargs(ess_floor, guidance_method, guided and num_samples > 0, mc_batch_size, (fm_x, fm_y), False,
+                         diagnostics, diag)
     _engine.sample_pair(fm_x, fm_y, x_t, y_t, mc_x1, mc_y1, mc_ratios, num_steps, guidance_strength, solver=solver, diag=diag,
-                        **gs_kw, **_sde_kwargs(eta, sde_seed))
+                        **gs_kw, **_sde_kwargs(eta, sde_seed), **ess_kw)
     return x_t, y_t
 
 
 def shared_mc_sweep(fm_x, fm_y, ratio_estimator, guidance_method, strengths, num_samples, num_steps, device,
                     mc_batch_size, shape_x, shape_y, solver='euler', diagnostics=None, mc_pairing='paired',
-                    guidance_schedule=None, sde_eta=0.0, sde_seed=None):
+                    guidance_schedule=None, sde_eta=0.0, sde_seed=None, ess_floor=None):
     """All `strengths` of one guided method as ONE ``paired_sampler`` call of ``len(strengths) * num_samples`` rows: row
     block j carries ``strengths[j]`` (a strength per row), over one MC set, one pre-phase and one start-noise set
     ``[num_samples]`` repeated per block (common random numbers: the blocks differ by the strength alone).  The noise is
@@ -365,13 +415,14 @@ def shared_mc_sweep(fm_x, fm_y, ratio_estimator, guidance_method, strengths, num
     holds the records of all rows, block after block.
     `sde_eta` > 0 (``paired_sampler``): one noise seed for the whole call (`sde_seed`; None: drawn after the noise above).
     The per-step noise is a function of the element's place in the batch, so the blocks then share the start noise and
-    the MC set but not the path noise."""
+    the MC set but not the path noise.  `ess_floor`: ``paired_sampler``'s, for every block."""
     if guidance_method not in ('mc_feng', 'grad_log_ratio') or ratio_estimator is None:
         raise ValueError(f"a shared-MC sweep runs a guided method with its ratio estimator, got {guidance_method!r}")
     strengths = [float(g) for g in strengths]
     if not strengths:
         return []
     eta = _engine.check_sde(sde_eta, solver, (fm_x, fm_y))
+    _ess_kwargs(ess_floor, guidance_method, False, mc_batch_size, (fm_x, fm_y), mc_pairing == 'cross', None, None)
     dev = _device(device)
     x0 = torch.randn(num_samples, *shape_x, device=dev)
     y0 = torch.randn(num_samples, *shape_y, device=dev)
@@ -385,13 +436,13 @@ def shared_mc_sweep(fm_x, fm_y, ratio_estimator, guidance_method, strengths, num
     xs, ys = paired_sampler(fm_x, fm_y, ratio_estimator, guidance_method, rows, k * num_samples, num_steps, dev,
                             mc_batch_size, shape_x, shape_y, noise=noise, verbose=False, solver=solver,
                             diagnostics=diagnostics, mc_pairing=mc_pairing, guidance_schedule=guidance_schedule,
-                            **_sde_kwargs(eta, sde_seed))
+                            ess_floor=ess_floor, **_sde_kwargs(eta, sde_seed))
     return [(xs[j * num_samples:(j + 1) * num_samples], ys[j * num_samples:(j + 1) * num_samples]) for j in range(k)]
 
 
 def sample_conditional(fm_target, ratio_estimator, condition, given='x', num_steps=100, guidance_strength=1.0,
                        mc_batch_size=256, mc_samples=None, device=None, guidance_method='mc_feng', solver='euler',
-                       diagnostics=None, guidance_schedule=None, sde_eta=0.0, sde_seed=None):
+                       diagnostics=None, guidance_schedule=None, sde_eta=0.0, sde_seed=None, ess_floor=None):
     """Partners for `condition` in the other modality: one sample of `fm_target`'s modality per condition image.
 
     ``given='x'``: `condition` is the estimator's x argument and the target is its y; ``given='y'`` the other way
@@ -423,6 +474,9 @@ def sample_conditional(fm_target, ratio_estimator, condition, given='x', num_ste
     ``rgfm_sample_cond_grad_sde``; ``solver='euler'``).  The MC pre-phase stays deterministic; ``sde_seed=None`` is
     drawn from torch's CPU generator after the draws above.
 
+    `ess_floor`: the effective-sample-size floor of ``paired_sampler`` on each row's one-sided weights
+    (``guidance_method='mc_feng'``, ``rgfm_sample_cond_ess``; ``1 <= ess_floor <=`` the size of the MC set).
+
     Returns the samples ``[len(condition), C, H, W]`` on the device.  U-Net targets only; ``--sharded`` launches have
     no conditional form yet.
     """
@@ -441,6 +495,8 @@ def sample_conditional(fm_target, ratio_estimator, condition, given='x', num_ste
     if ratio_estimator.loss_type not in ("disc", "rulsif"):
         raise ValueError(f"Unknown loss_type: {ratio_estimator.loss_type}")
     eta = _engine.check_sde(sde_eta, solver, (fm_target,))
+    n_mc = mc_batch_size if mc_samples is None else len(mc_samples)
+    _ess_kwargs(ess_floor, guidance_method, False, n_mc, (fm_target,), False, None, None)
     guidance_strength, gs_kw = _strength_kwargs(guidance_strength, guidance_schedule, len(condition), num_steps, solver,
                                                 lambda: _device(condition.device if device is None else device),
                                                 (fm_target,), what='len(condition)')
@@ -468,14 +524,15 @@ def sample_conditional(fm_target, ratio_estimator, condition, given='x', num_ste
     diag = None
     if diagnostics is not None and s_t.shape[0]:
         diag = diagnostics._begin('mc_feng', solver, num_steps, s_t.shape[0], dev, stage_scale=gs_kw.get('stage_scale'))
+    ess_kw = _ess_kwargs(ess_floor, guidance_method, s_t.shape[0] > 0, n_mc, (fm_target,), False, diagnostics, diag)
     return _engine.sample_cond(fm_target, s_t, mc, ratios, num_steps, guidance_strength, solver=solver, diag=diag, **gs_kw,
-                               **_sde_kwargs(eta, sde_seed))
+                               **_sde_kwargs(eta, sde_seed), **ess_kw)
 
 
 def sample_bimodal_guided(fm_x, fm_y, ratio_estimator=None, guidance_method='none',
                           guidance_strength=0.0, num_samples=16, num_steps=100, device='cuda',
                           mc_batch_size=64, solver='euler', diagnostics=None, mc_pairing='paired', guidance_schedule=None,
-                          sde_eta=0.0, sde_seed=None):
+                          sde_eta=0.0, sde_seed=None, ess_floor=None):
     """Pairs of 1x28x28 images, optional mc_feng guidance (reference :178-375).
 
     Returns ``(samples_x [n,1,28,28], samples_y [n,1,28,28])`` on `device`.
@@ -487,9 +544,9 @@ def sample_bimodal_guided(fm_x, fm_y, ratio_estimator=None, guidance_method='non
     ``mc_pairing='cross'``: the guidance over all ``mc_batch_size ** 2`` pairs of the MC set (``paired_sampler``).
     `guidance_strength` may also hold one strength per sample and `guidance_schedule` scales it per stage
     (``paired_sampler``, ``utils/guidance_schedule.py``).  `sde_eta`, `sde_seed`: the stochastic sampler
-    (``paired_sampler``).
+    (``paired_sampler``).  `ess_floor`: the effective-sample-size floor of the importance weights (``paired_sampler``).
     """
     return paired_sampler(fm_x, fm_y, ratio_estimator, guidance_method, guidance_strength,
                           num_samples, num_steps, device, mc_batch_size, (1, 28, 28), (1, 28, 28), solver=solver,
                           diagnostics=diagnostics, mc_pairing=mc_pairing, guidance_schedule=guidance_schedule,
-                          sde_eta=sde_eta, sde_seed=sde_seed)
+                          sde_eta=sde_eta, sde_seed=sde_seed, ess_floor=ess_floor)
