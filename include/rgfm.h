@@ -1014,6 +1014,60 @@ int rgfm_guidance_apply_cond_ess(const float* s, float* v, const float* mc_set, 
                                  double ess_min, float* tau_out, void* ws, size_t ws_bytes, rgfm_stream_t stream);
 
 /* ------------------------------------------------------------------------
+ * Class conditioning and classifier-free guidance (an extension: the reference's nets are unconditional).
+ * Added functions only: rgfm_unet_desc and RGFM_ABI_VERSION are unchanged.
+ *
+ * 1. The model.  A class-conditional U-Net with K = num_classes classes owns one more tensor, label_emb.weight
+ *    [K + 1][4 model_channels], the LAST entry of its blob: the unlabelled blob, then that table.  Row K is the null
+ *    label, the net's unconditional branch.  The function is the ADM form
+ *        emb = time_embed(timestep_embedding(t)) + label_emb[y],   then every ResBlock: Linear(SiLU(emb)) as before.
+ *    rgfm_unet_labeled_param_floats / rgfm_unet_labeled_create: the counterparts of rgfm_unet_param_floats / _create,
+ *    1 <= num_classes < 4096.  Every function that takes an rgfm_unet* takes such a handle: rgfm_unet_update_params
+ *    the longer blob, rgfm_unet_backward writes dparams_out with d label_emb.weight [K + 1][temb] at its end, and every
+ *    entry point WITHOUT a labels argument (forward, the sampler loops, the likelihood path, training) evaluates the
+ *    net with the null label in every row.
+ * 2. Labels are device int32, one per row, values 0 .. K.  A value outside that range is READ AS K on the device (an
+ *    index taken from user data never addresses outside the table); callers that want an error check on the host.
+ *    Labels on a handle without classes: RGFM_EINVAL.  A null labels pointer: the namesake without labels.
+ * 3. rgfm_unet_forward_labels / rgfm_unet_forward_train_labels: rgfm_unet_forward / rgfm_unet_forward_train with
+ *    labels_dev behind t_count; same workspaces.  The training forward saves the labels in ws;
+ *    dE[c] = sum of d emb[b] over the rows b with y_b == c, added in ascending b by one workgroup per class (no
+ *    atomics: two backward calls give the same bits), exact zeros for a class without a row.
+ * 4. rgfm_sample_single_cfg is rgfm_sample_single_sde, rgfm_sample_two_cfg is rgfm_sample_two, with labels and a
+ *    guidance scale w per net: every stage advances by  F = v_u + w (v_c - v_u),  v_c the net at the rows' labels, v_u
+ *    at the null label.  w == 1 evaluates v_c alone and w == 0 v_u alone (one evaluation per stage, the out-conv's fused
+ *    update; w == 0 has the bits of the call without labels); any other w evaluates both and one elementwise kernel
+ *    writes state = base + F dts with the stage's own (base, dts), so midpoint stages and the stochastic step compose.
+ *    A call builds its time table once, [stages][K + 1][temb_total], and hands each conditional evaluation the rows
+ *    gathered by label.  The table holds 4096 rows: stages x (K + 1) beyond that is RGFM_EINVAL -- split the call with
+ *    step_begin / step_end (split calls reproduce one call bit for bit).  Workspace: the *_cfg_workspace_bytes
+ *    queries (one size for every scale; rgfm_sample_single_cfg with eta > 0 adds rgfm_sde_scratch_bytes).
+ *    Errors are returned before anything is enqueued: the namesake's own, RGFM_EINVAL for labels on a handle without
+ *    classes or a cfg_scale that is not finite, RGFM_ENOMEM for a short workspace.
+ * ---------------------------------------------------------------------- */
+int rgfm_unet_labeled_param_floats(const rgfm_unet_desc* desc, int num_classes, size_t* n_floats);
+int rgfm_unet_labeled_create(const rgfm_unet_desc* desc, int num_classes, const float* params_dev, size_t n_floats,
+                             rgfm_stream_t stream, rgfm_unet** out);
+int rgfm_unet_forward_labels(rgfm_unet* h, const float* x, const float* t_dev, int t_count, const int32_t* labels_dev,
+                             float* v_out, int batch, void* ws, size_t ws_bytes, rgfm_stream_t stream);
+int rgfm_unet_forward_train_labels(rgfm_unet* h, const float* x, const float* t_dev, int t_count,
+                                   const int32_t* labels_dev, float* v_out, int batch, float p_drop, uint64_t seed,
+                                   void* ws, size_t ws_bytes, rgfm_stream_t stream);
+int rgfm_sample_single_cfg_workspace_bytes(const rgfm_unet* h, int batch, int solver, size_t* bytes);
+int rgfm_sample_single_cfg(rgfm_unet* h, float* x_inout, const int32_t* labels_dev, double cfg_scale, int batch,
+                           int num_steps, int step_begin, int step_end, int solver, const rgfm_sde* sde, void* ws,
+                           size_t ws_bytes, rgfm_stream_t stream);
+int rgfm_sample_two_cfg_workspace_bytes(const rgfm_unet* hx, const rgfm_unet* hy, int batch_x, int batch_y, int solver,
+                                        size_t* bytes);
+int rgfm_sample_two_cfg(rgfm_unet* hx, rgfm_unet* hy, float* x_inout, float* y_inout, const int32_t* labels_x,
+                        const int32_t* labels_y, double cfg_scale_x, double cfg_scale_y, int batch_x, int batch_y,
+                        int num_steps, int step_begin, int step_end, int solver, void* ws, size_t ws_bytes,
+                        rgfm_stream_t stream);
+/* The blend kernel of 4. alone over n floats, 200 launches back to back between two device events on the null stream
+ * (synchronises): GB/s of the 16 bytes per element it moves, and the time of one launch in microseconds. */
+int rgfm_ubench_cfg_blend(size_t n, double* gbps, double* us_per_launch);
+
+/* ------------------------------------------------------------------------
  * Bench support: per-kernel-class device time measured with hipEvents on the
  * launch stream (bench.py's roofline line).  Timing is off by default.
  * ---------------------------------------------------------------------- */

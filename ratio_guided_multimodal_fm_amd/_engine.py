@@ -181,6 +181,10 @@ class _EngineBase:
         """What the handle depends on besides the module's tensors."""
         return None
 
+    def _create_variant(self):
+        """(prefix of the param_floats / create entry points, their arguments behind the descriptor)."""
+        return self.DESC_PREFIX, ()
+
     def _state_key(self, sd):
         return tuple((k, v.data_ptr(), v._version, str(v.device)) for k, v in sd.items())
 
@@ -202,13 +206,14 @@ class _EngineBase:
             self._destroy()
         d = self.desc()
         n = ctypes.c_size_t()
-        _lib.check(self._fn("param_floats", self.DESC_PREFIX)(ctypes.byref(d), ctypes.byref(n)))
+        prefix, more = self._create_variant()
+        _lib.check(self._fn("param_floats", prefix)(ctypes.byref(d), *more, ctypes.byref(n)))
         if blob.numel() != n.value:
             raise _lib.RgfmError(f"parameter blob has {blob.numel()} floats, library expects {n.value}")
         h = ctypes.c_void_p()
         with torch.cuda.device(device):
-            _lib.check(self._fn("create", self.DESC_PREFIX)(ctypes.byref(d), _ptr(blob), blob.numel(), _stream(device),
-                                                            ctypes.byref(h)))
+            _lib.check(self._fn("create", prefix)(ctypes.byref(d), *more, _ptr(blob), blob.numel(), _stream(device),
+                                                  ctypes.byref(h)))
         self._handle, self._key, self._blob = h, (key, extra), blob
         named = {id(q) for q in m.parameters()}
         self._layout = [(v.numel(), id(v) in named) for v in m.state_dict(keep_vars=True).values()]
@@ -256,9 +261,10 @@ class _TrainSpec:
     workspace, whether the pass has dropout, whether it takes the `training` flag and reports BatchNorm statistics,
     and what it leaves in engine._last_train."""
 
-    def __init__(self, inputs, grads, out_shape, args, dropout=False, batchnorm=False, last=None):
+    def __init__(self, inputs, grads, out_shape, args, dropout=False, batchnorm=False, last=None, fn="forward_train"):
         self.inputs, self.grads, self.out_shape, self.args = inputs, grads, out_shape, args
         self.dropout, self.batchnorm, self.last = dropout, batchnorm, last
+        self.fn = fn  # the forward's entry point, rgfm_<family>_<fn>; the backward is the family's one
 
 
 class _TrainFn(torch.autograd.Function):
@@ -289,7 +295,7 @@ class _TrainFn(torch.autograd.Function):
             nb = ctypes.c_size_t()
             _lib.check(engine._fn("train_workspace_bytes")(h, n, ctypes.byref(nb)))
             ws = torch.empty(nb.value, dtype=torch.uint8, device=dev)
-            _lib.check(engine._fn("forward_train")(
+            _lib.check(engine._fn(spec.fn)(
                 h, *spec.args(*inputs, out, n, 1 if training else 0, p_drop, seed, _ptr(stats)), _ptr(ws), nb.value,
                 _stream(dev)))
         off = 0
@@ -372,12 +378,25 @@ class _VelocityEngine(_EngineBase):
             raise _lib.RgfmError(f"t must have 1 or {x.shape[0]} elements, got {t.numel()}")
         return x.contiguous(), t.contiguous()
 
-    def forward_train(self, x, t):
+    def check_labels(self, y, batch, device):
+        """The labels of a call as the library takes them: None for `y` None, else a contiguous int32 tensor [batch] on
+        `device`.  Every check runs here, before the library enqueues anything: the family has labels at all, the net
+        was built with num_classes, `y` is an integer tensor [batch] with values in 0..num_classes."""
+        if y is None:
+            return None
+        raise _lib.RgfmError(f"{type(self._module()).__name__} has no class labels (FlexibleUNet and its presets take "
+                             "num_classes)")
+
+    def forward_train(self, x, t, y=None):
         """v = model(x, t) on the exact-fp32 training path, differentiable w.r.t. x and the parameters (_TrainFn).  A
-        net with Dropout applies it while the module trains; neither net has batch statistics."""
+        net with Dropout applies it while the module trains; neither net has batch statistics.  `y`: labels
+        (check_labels; U-Nets built with num_classes)."""
         m = self._module()
         x, t = self._check_xt(x, t)
+        y = self.check_labels(y, x.shape[0], x.device)
         p = m.dropout_p() if self.TRAIN.dropout and m.training else 0.0
+        if y is not None:
+            return _TrainFn.apply(self.TRAIN_LABELS, self, float(p), x, t, y, *m.parameters())
         return _TrainFn.apply(self.TRAIN, self, float(p), x, t, *m.parameters())
 
     def workspace(self, fn_name, batch, device):
@@ -396,10 +415,11 @@ class _VelocityEngine(_EngineBase):
         """Conv arithmetic of this engine's handle: CONV_DEFAULT (RGFM_CONV), CONV_HX2, CONV_BX3, CONV_F32."""
         _lib.check(self._fn("set_conv_mode")(self.handle(device), int(mode)))
 
-    def forward(self, x, t):
+    def forward(self, x, t, y=None):
         self._check_eval(self._module())
         x, t = self._check_xt(x, t)
         B = x.shape[0]
+        y = self.check_labels(y, B, x.device)
         out = torch.empty_like(x)
         if B == 0:
             return out
@@ -409,6 +429,10 @@ class _VelocityEngine(_EngineBase):
             with torch.cuda.device(dev):
                 h = self.handle(dev)
                 ws, nb = self.workspace(f"{self.PREFIX}_workspace_bytes", B, dev)
+                if y is not None:
+                    _lib.check(self._fn("forward_labels")(h, _ptr(x), _ptr(t), t.numel(), _ptr(y), _ptr(out), B, _ptr(ws),
+                                                          nb, _stream(dev)))
+                    return out
                 _lib.check(self._fn("forward")(h, _ptr(x), _ptr(t), t.numel(), _ptr(out), B, _ptr(ws), nb,
                                                _stream(dev)))
             return out
@@ -445,6 +469,44 @@ class UNetEngine(_VelocityEngine):
     SINGLE, PAIR = _SINGLE, _PAIR
     TRAIN = _TrainSpec(inputs=2, grads=1, out_shape=lambda x, t: x.shape, dropout=True,
                        args=lambda x, t, out, n, training, p, seed, stats: (_ptr(x), _ptr(t), t.numel(), _ptr(out), n, p, seed))
+    # (with labels: rgfm_unet_forward_train_labels, the int32 labels a third input without a gradient)
+    TRAIN_LABELS = _TrainSpec(inputs=3, grads=1, out_shape=lambda x, t, y: x.shape, dropout=True, fn="forward_train_labels",
+                              args=lambda x, t, y, out, n, training, p, seed, stats: (_ptr(x), _ptr(t), t.numel(), _ptr(y),
+                                                                                      _ptr(out), n, p, seed))
+
+    def num_classes(self):
+        """K of a class-conditional net (label_emb.weight: [K + 1, 4 model_channels]), or 0."""
+        return int(getattr(self._module(), "num_classes", None) or 0)
+
+    def _key_extra(self):
+        return self.num_classes()
+
+    def _create_variant(self):
+        K = self.num_classes()
+        return ("rgfm_unet_labeled", (K,)) if K else (self.DESC_PREFIX, ())
+
+    def check_labels(self, y, batch, device):
+        if y is None:
+            return None
+        K = self.num_classes()
+        if not K:
+            raise _lib.RgfmError(f"labels on a {type(self._module()).__name__} built without num_classes: the net is unconditional")
+        if not isinstance(y, torch.Tensor) or y.dtype.is_floating_point or y.dtype in (torch.bool, torch.complex64, torch.complex128):
+            raise _lib.RgfmError(f"labels: an integer tensor [{batch}] expected, got {type(y).__name__}"
+                                 f"{' of ' + str(y.dtype) if isinstance(y, torch.Tensor) else ''}")
+        if y.dim() != 1 or y.shape[0] != batch:
+            raise _lib.RgfmError(f"labels: one label per row ([{batch}]) expected, got {tuple(y.shape)}")
+        if batch:
+            lo, hi = int(y.min()), int(y.max())
+            if lo < 0 or hi > K:
+                raise _lib.RgfmError(f"labels must lie in 0..{K} ({K} is the null label), got values in {lo}..{hi}")
+        return y.to(device=device, dtype=torch.int32).contiguous()
+
+    def no_labels(self, y, what):
+        """The refusal of the entry points that have no labelled form."""
+        if y is not None:
+            raise _lib.RgfmError(f"{what} has no labelled form; without labels a class-conditional net runs as its "
+                                 "unconditional branch (the null label in every row)")
 
     def _check_eval(self, module):
         if module.training:
@@ -1221,12 +1283,47 @@ def _solver_arg(engine, sid):
     return sid if isinstance(engine, UNetEngine) else None
 
 
-def sample_single(model, x, num_steps, step_begin=0, step_end=None, solver='euler', sde_eta=0.0, sde_seed=None):
+TABLE_ROWS = 4096  # (stage, class) rows of a labelled sampler call's time table (csrc/sampler_host.h)
+
+
+def check_cfg(labels, cfg_scale, batch, model, device=None):
+    """Argument checks of a labelled sampler call for one net, before any draw and any device work.  Returns None when
+    the call has neither labels nor a scale other than 1 (it is then today's), else (labels as int32 [batch] on
+    `device`, cfg_scale as a float).  A scale other than 1 needs labels: without them v_c and v_u are the same."""
+    w = float(cfg_scale)
+    if not math.isfinite(w):
+        raise ValueError(f"cfg_scale must be finite, got {cfg_scale!r}")
+    if labels is None:
+        if w != 1.0:
+            raise _lib.RgfmError("cfg_scale needs labels: without them the net's conditional and unconditional "
+                                 "velocities are the same")
+        return None
+    return model._engine.check_labels(labels, batch, device), w
+
+
+def _cfg_chunks(nets, sid, step_begin, step_end):
+    """The step ranges a labelled call is split into so that stages x (K + 1) of every labelled net fits TABLE_ROWS.
+    Split calls reproduce one call bit for bit."""
+    K = max(m._engine.num_classes() for m in nets)
+    cap = max(1, TABLE_ROWS // ((K + 1) * (2 if sid else 1)))
+    return [(b, min(b + cap, step_end)) for b in range(step_begin, step_end, cap)] or [(step_begin, step_end)]
+
+
+def sample_single(model, x, num_steps, step_begin=0, step_end=None, solver='euler', sde_eta=0.0, sde_seed=None,
+                  labels=None, cfg_scale=1.0):
     """In-place unguided integration of `x` (rgfm_sample_single; solver='midpoint': rgfm_sample_single_ode).
     `sde_eta` > 0: Euler-Maruyama steps of that strength (rgfm_sample_single_sde; U-Net nets, solver='euler'), the
     noise seeded by `sde_seed` (None: draw_sde_seed()); 0: the call above, unchanged.  The loops below take the two the
-    same way."""
+    same way.
+    `labels` (an integer tensor [B], values 0..K of a net built with num_classes=K) and `cfg_scale` = w: every stage
+    advances by v_u + w (v_c - v_u) (rgfm_sample_single_cfg); neither: the call above, unchanged."""
+    cfg = check_cfg(labels, cfg_scale, x.shape[0], model, x.device)
     sde = _sde(sde_eta, sde_seed, _solver(solver, model), (model,), x)
+    if cfg is not None:
+        if x.is_cuda and x.shape[0]:
+            return _range_guarded(x.device, [x], lambda: _sample_single_cfg(model, x, num_steps, step_begin, step_end, solver,
+                                                                            sde, cfg), [model._engine])
+        return _sample_single_cfg(model, x, num_steps, step_begin, step_end, solver, sde, cfg)
     if x.is_cuda and x.shape[0]:
         return _range_guarded(x.device, [x], lambda: _sample_single(model, x, num_steps, step_begin, step_end, solver, sde),
                               [model._engine])
@@ -1250,6 +1347,71 @@ def _sample_single(model, x, num_steps, step_begin=0, step_end=None, solver='eul
         _run_loop(eng.SINGLE, (h, B), (h, _ptr(x), B, int(num_steps)), (step_begin, step_end),
                   _solver_arg(eng, sid), dev, ws=eng._ws, sde=sde)
     return x
+
+
+def _sample_single_cfg(model, x, num_steps, step_begin, step_end, solver, sde, cfg):
+    """The labelled single loop: rgfm_sample_single_cfg over the chunks of _cfg_chunks, in the engine's workspace."""
+    sid = _solver(solver, model)
+    eng = model._engine
+    eng._check_eval(model)
+    _require_hip(x)
+    if not x.is_contiguous():
+        raise _lib.RgfmError("x must be contiguous (it is updated in place)")
+    if step_end is None:
+        step_end = num_steps
+    B, dev = x.shape[0], x.device
+    if B == 0:
+        return x
+    labels, w = cfg
+    L = _lib.lib()
+    with torch.cuda.device(dev):
+        h = eng.handle(dev)
+        nb = ctypes.c_size_t()
+        _lib.check(L.rgfm_sample_single_cfg_workspace_bytes(h, B, sid, ctypes.byref(nb)))
+        nbytes, rec = nb.value, None
+        if sde is not None:
+            rec, batch, dim_x, dim_y = sde
+            _lib.check(L.rgfm_sde_scratch_bytes(batch, dim_x, dim_y, ctypes.byref(nb)))
+            nbytes += nb.value
+        buf = eng._ws.get(nbytes, dev)
+        for b, e in _cfg_chunks((model,), sid, int(step_begin), int(step_end)):
+            _lib.check(L.rgfm_sample_single_cfg(h, _ptr(x), _ptr(labels), w, B, int(num_steps), b, e, sid,
+                                                ctypes.byref(rec) if rec is not None else None, _ptr(buf), nbytes,
+                                                _stream(dev)))
+    return x
+
+
+def sample_two_cfg(fm_x, x, fm_y, y, num_steps, solver='euler', labels_x=None, labels_y=None, cfg_scale_x=1.0, cfg_scale_y=1.0):
+    """Two independent labelled integrations at once, in place (rgfm_sample_two_cfg: rgfm_sample_two with labels and a
+    scale per net): the unguided pair of two class-conditional nets.  Either net may go without labels."""
+    cx = check_cfg(labels_x, cfg_scale_x, x.shape[0], fm_x, x.device) or (None, 1.0)
+    cy = check_cfg(labels_y, cfg_scale_y, y.shape[0], fm_y, y.device) or (None, 1.0)
+    sid = _solver(solver, fm_x, fm_y)
+    for m in (fm_x, fm_y):
+        if not isinstance(m._engine, UNetEngine):
+            raise _lib.RgfmError(f"labelled sampling needs U-Net velocity nets; {type(m).__name__} has no class labels")
+        m._engine._check_eval(m)
+    _require_hip(x, y)
+    if not (x.is_contiguous() and y.is_contiguous()):
+        raise _lib.RgfmError("x and y must be contiguous (they are updated in place)")
+    if x.data_ptr() == y.data_ptr() or fm_x._engine is fm_y._engine:
+        raise _lib.RgfmError("the labelled pair needs two nets and two state tensors")
+    dev = x.device
+    if x.shape[0] == 0 or y.shape[0] == 0:
+        return x, y
+    L = _lib.lib()
+
+    def run():
+        with torch.cuda.device(dev):
+            hx, hy = fm_x._engine.handle(dev), fm_y._engine.handle(dev)
+            nb = ctypes.c_size_t()
+            _lib.check(L.rgfm_sample_two_cfg_workspace_bytes(hx, hy, x.shape[0], y.shape[0], sid, ctypes.byref(nb)))
+            buf = _sampler_ws.get(nb.value, dev)
+            for b, e in _cfg_chunks((fm_x, fm_y), sid, 0, int(num_steps)):
+                _lib.check(L.rgfm_sample_two_cfg(hx, hy, _ptr(x), _ptr(y), _ptr(cx[0]), _ptr(cy[0]), cx[1], cy[1], x.shape[0],
+                                                 y.shape[0], int(num_steps), b, e, sid, _ptr(buf), nb.value, _stream(dev)))
+        return x, y
+    return _range_guarded(dev, [x, y], run, [fm_x._engine, fm_y._engine])
 
 
 _side_streams = {}

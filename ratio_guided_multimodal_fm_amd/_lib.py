@@ -260,6 +260,21 @@ SIGNATURES = {
                                         c_void_p]),
     "rgfm_guidance_apply_cond_ess": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_double,
                                              c_void_p, c_void_p, c_double, c_void_p, c_void_p, c_size_t, c_void_p]),
+    # class conditioning and classifier-free guidance: the namesakes with num_classes behind the descriptor, labels
+    # (device int32) behind t_count / the states, and a scale per net
+    "rgfm_unet_labeled_param_floats": (c_int, [P(UNetDesc), c_int, P(c_size_t)]),
+    "rgfm_unet_labeled_create": (c_int, [P(UNetDesc), c_int, c_void_p, c_size_t, c_void_p, P(c_void_p)]),
+    "rgfm_unet_forward_labels": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_int, c_void_p,
+                                         c_size_t, c_void_p]),
+    "rgfm_unet_forward_train_labels": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_int, c_float,
+                                               c_uint64, c_void_p, c_size_t, c_void_p]),
+    "rgfm_sample_single_cfg_workspace_bytes": (c_int, [c_void_p, c_int, c_int, P(c_size_t)]),
+    "rgfm_sample_single_cfg": (c_int, [c_void_p, c_void_p, c_void_p, c_double, c_int, c_int, c_int, c_int, c_int, P(Sde),
+                                       c_void_p, c_size_t, c_void_p]),
+    "rgfm_sample_two_cfg_workspace_bytes": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, P(c_size_t)]),
+    "rgfm_sample_two_cfg": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_double, c_double, c_int,
+                                    c_int, c_int, c_int, c_int, c_int, c_void_p, c_size_t, c_void_p]),
+    "rgfm_ubench_cfg_blend": (c_int, [c_size_t, P(c_double), P(c_double)]),
     "rgfm_profile_enable": (c_int, [c_int]),
     "rgfm_profile_reset": (c_int, []),
     "rgfm_profile_read": (c_int, [c_int, P(c_double), P(c_double), P(c_int64), P(c_double)]),

@@ -41,24 +41,34 @@ void carve_pair(Bump& b, PairWs& w, int n_mc, int pairing) {
   w.cx.carve_eval(), w.cy.carve_eval();         // the two nets run concurrently: disjoint regions
 }
 
-int single_bytes(const rgfm_unet* h, int batch, int solver, size_t* bytes) {
+int single_bytes(const rgfm_unet* h, int batch, int solver, size_t* bytes, bool cfg = false) {
   if (int rc = check_solver_id(solver)) return rc;
   if (!h || !bytes || batch < 1) return fail(RGFM_EINVAL, "bad argument");
   Bump b;
   NetChain c{const_cast<rgfm_unet*>(h), batch, solver};
+  c.cfg_ws = cfg;
   carve_single(b, c);
   *bytes = b.off;
   return RGFM_OK;
 }
 
+// The labels and scale of a *_cfg entry point (include/rgfm.h, "Class conditioning"); the other entry points pass none.
+struct Cfg {
+  bool on = false;
+  const int* labels = nullptr;
+  double scale = 1.0;
+};
+
 int single_loop(rgfm_unet* h, float* x_inout, int batch, int num_steps, int step_begin, int step_end, int solver, void* ws,
-                size_t ws_bytes, rgfm_stream_t stream, Sde sde = Sde()) {
+                size_t ws_bytes, rgfm_stream_t stream, Sde sde = Sde(), Cfg cfg = Cfg()) {
   refresh_modes();
   int ns = 0;
   if (int rc = check_loop(solver, h && x_inout && ws, batch, num_steps, step_begin, step_end, &ns)) return rc;
   if (int rc = sde.check(solver)) return rc;
   Bump b(ws, ws_bytes);
   NetChain c{h, batch, solver, x_inout};
+  if (cfg.on)
+    if (int rc = c.check_cfg(cfg.labels, cfg.scale, ns)) return rc;
   carve_single(b, c);
   if (sde.on()) sde.carve(b, batch, c.image_floats(), 0);
   if (int rc = check_workspace(b, ws_bytes)) return rc;
@@ -83,7 +93,8 @@ int single_loop(rgfm_unet* h, float* x_inout, int batch, int num_steps, int step
 // RGFM_PREPHASE_PRIO=0: the earlier schedule.  Same launches and arguments per chain either way: a row's bits do not
 // depend on the schedule.
 int two_loop(rgfm_unet* hx, rgfm_unet* hy, float* x_inout, float* y_inout, int batch_x, int batch_y, int num_steps,
-             int step_begin, int step_end, int solver, void* ws, size_t ws_bytes, rgfm_stream_t stream) {
+             int step_begin, int step_end, int solver, void* ws, size_t ws_bytes, rgfm_stream_t stream, Cfg cfg_x = Cfg(),
+             Cfg cfg_y = Cfg()) {
   refresh_modes();
   int ns = 0;
   if (int rc = check_loop(solver, hx && hy && x_inout && y_inout && ws, batch_x, num_steps, step_begin, step_end, &ns))
@@ -93,6 +104,10 @@ int two_loop(rgfm_unet* hx, rgfm_unet* hy, float* x_inout, float* y_inout, int b
   Bump b(ws, ws_bytes);
   // each net's chain is cut into steps so that the two can be enqueued side by side
   NetChain cx{hx, batch_x, solver, x_inout}, cy{hy, batch_y, solver, y_inout};
+  if (cfg_x.on)
+    if (int rc = cx.check_cfg(cfg_x.labels, cfg_x.scale, ns)) return rc;
+  if (cfg_y.on)
+    if (int rc = cy.check_cfg(cfg_y.labels, cfg_y.scale, ns)) return rc;
   carve_single(b, cx), carve_single(b, cy);
   if (int rc = check_workspace(b, ws_bytes)) return rc;
   if (ns == 0) return RGFM_OK;
@@ -608,6 +623,36 @@ extern "C" int rgfm_sample_single_sde(rgfm_unet* h, float* x_inout, int batch, i
                                       int solver, const rgfm_sde* sde, void* ws, size_t ws_bytes, rgfm_stream_t stream) {
   return single_loop(h, x_inout, batch, num_steps, step_begin, step_end, solver, ws, ws_bytes, stream, sde);
 }
+// ---- class labels and classifier-free guidance (include/rgfm.h, "Class conditioning"): rgfm_sample_single_sde and
+// rgfm_sample_two with labels and a scale per net; null labels: the namesake's launches in the *_cfg workspace
+extern "C" int rgfm_sample_single_cfg_workspace_bytes(const rgfm_unet* h, int batch, int solver, size_t* bytes) {
+  return single_bytes(h, batch, solver, bytes, true);
+}
+extern "C" int rgfm_sample_single_cfg(rgfm_unet* h, float* x_inout, const int32_t* labels_dev, double cfg_scale, int batch,
+                                      int num_steps, int step_begin, int step_end, int solver, const rgfm_sde* sde, void* ws,
+                                      size_t ws_bytes, rgfm_stream_t stream) {
+  return single_loop(h, x_inout, batch, num_steps, step_begin, step_end, solver, ws, ws_bytes, stream, sde,
+                     {true, labels_dev, cfg_scale});
+}
+extern "C" int rgfm_sample_two_cfg_workspace_bytes(const rgfm_unet* hx, const rgfm_unet* hy, int batch_x, int batch_y, int solver,
+                                                   size_t* bytes) {
+  if (int rc = check_solver_id(solver)) return rc;
+  if (!hx || !hy || !bytes || batch_x < 1 || batch_y < 1) return fail(RGFM_EINVAL, "bad argument");
+  Bump b;
+  NetChain cx{const_cast<rgfm_unet*>(hx), batch_x, solver}, cy{const_cast<rgfm_unet*>(hy), batch_y, solver};
+  cx.cfg_ws = cy.cfg_ws = true;
+  carve_single(b, cx), carve_single(b, cy);
+  *bytes = b.off;
+  return RGFM_OK;
+}
+extern "C" int rgfm_sample_two_cfg(rgfm_unet* hx, rgfm_unet* hy, float* x_inout, float* y_inout, const int32_t* labels_x,
+                                   const int32_t* labels_y, double cfg_scale_x, double cfg_scale_y, int batch_x, int batch_y,
+                                   int num_steps, int step_begin, int step_end, int solver, void* ws, size_t ws_bytes,
+                                   rgfm_stream_t stream) {
+  return two_loop(hx, hy, x_inout, y_inout, batch_x, batch_y, num_steps, step_begin, step_end, solver, ws, ws_bytes, stream,
+                  {true, labels_x, cfg_scale_x}, {true, labels_y, cfg_scale_y});
+}
+
 extern "C" int rgfm_sample_pair_sde(rgfm_unet* hx, rgfm_unet* hy, float* x_inout, float* y_inout, const float* mc_x1,
                                     const float* mc_y1, const float* mc_ratios, int n_mc, int batch, int num_steps, double gamma,
                                     const float* gamma_rows, const double* stage_scale, int n_stage_scale, int step_begin,

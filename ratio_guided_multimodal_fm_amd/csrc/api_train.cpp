@@ -28,6 +28,7 @@ struct TrainPlan {
   std::vector<TOp> ops;
   std::vector<size_t> dT;  // gradient buffer of T[i]
   size_t hdr, x0, emb0, e1, emb, mro, saved;
+  size_t labels = 0;  // class-conditional handles: the rows' labels as the forward used them (int32 [B])
   size_t dT_begin, dT_end, A, R, G, DH, part, pg, pb, dtemb, dsemb, de1;
   size_t total;  // floats
   ConvW in_conv, out_conv;
@@ -47,6 +48,7 @@ TrainPlan plan_train(const rgfm_unet* h, int B) {
   p.emb0 = c.take((size_t)B * mc);
   p.e1 = c.take((size_t)B * temb);
   p.emb = c.take((size_t)B * temb);
+  if (h->num_classes) p.labels = c.take((size_t)B);  // (an unlabelled handle's layout stays what it was)
   auto part_of = [&](const ConvW& w, int So) {
     UgConv u{};
     u.Cout = w.cout, u.Cin = w.cin, u.taps = w.taps, u.B = B, u.Ho = u.Wo = So;
@@ -124,8 +126,9 @@ int check_train(const rgfm_unet* h, int batch, void* ws, size_t ws_bytes) {
 
 // The training forward over the planned workspace W.  keep_x: copy x into the saved state (the weight gradient of the
 // input conv reads it); the data-only users pass false and the input conv reads the caller's x.
+// labels (device int32 [batch], class-conditional handles): emb[b] += label_emb[labels[b]]; null: every row the null label.
 int forward_walk(rgfm_unet* h, const float* x, bool keep_x, const float* t_dev, int t_count, float* v_out, int batch,
-                 float p_drop, uint64_t seed, float* W, const TrainPlan& p, hipStream_t s) {
+                 float p_drop, uint64_t seed, float* W, const TrainPlan& p, hipStream_t s, const int* labels = nullptr) {
   const int B = batch, mc = h->mc, temb = h->temb;
   const float* P = h->params;
   unsigned* hdr = (unsigned*)(W + p.hdr);
@@ -139,6 +142,7 @@ int forward_walk(rgfm_unet* h, const float* x, bool keep_x, const float* t_dev, 
   launch_ug_sincos(t_dev, t_count, h->freqs, B, mc, W + p.emb0, s);
   launch_ug_linear(W + p.emb0, P + h->te0w, P + h->te0b, W + p.e1, B, mc, temb, 0, s);
   launch_ug_linear(W + p.e1, P + h->te2w, P + h->te2b, W + p.emb, B, temb, temb, 1, s);
+  if (h->num_classes) launch_cfg_label_add(W + p.emb, P + h->lemb, labels, h->num_classes, B, temb, (int*)(W + p.labels), s);
   for (const TOp& o : p.ops) {
     const UOp& u = *o.u;
     const int S = u.S, HW = S * S;
@@ -313,6 +317,9 @@ int backward_walk(rgfm_unet* h, const float* dv, float* dx_out, float* D, int ba
   if (full) {
     // time_embed: Linear(mc, temb) -> SiLU -> Linear(temb, temb); every ResBlock's time_mlp starts with SiLU(emb)
     launch_ug_dsilu(W + p.dsemb, W + p.emb, B * temb, s);
+    // label_emb: emb[b] = time_embed(..)[b] + E[y_b], so dE[c] collects the rows of d emb whose label is c
+    if (h->num_classes)
+      launch_cfg_label_grad(W + p.dsemb, (const int*)(W + p.labels), h->num_classes, B, temb, D + h->lemb, s);
     launch_ug_linear_wgrad(W + p.dsemb, W + p.e1, B, temb, temb, 1, D + h->te2w, D + h->te2b, s);
     launch_ug_linear_dgrad(W + p.dsemb, P + h->te2w, B, temb, temb, W + p.de1, 0, s);
     launch_ug_dsilu(W + p.de1, W + p.e1, B * temb, s);
@@ -381,6 +388,17 @@ extern "C" int rgfm_unet_forward_train(rgfm_unet* h, const float* x, const float
   if (int rc = check_p_drop(p_drop)) return rc;
   return forward_walk(h, x, true, t_dev, t_count, v_out, batch, p_drop, seed, (float*)ws, plan_train(h, batch),
                       (hipStream_t)stream);
+}
+
+extern "C" int rgfm_unet_forward_train_labels(rgfm_unet* h, const float* x, const float* t_dev, int t_count,
+                                              const int32_t* labels_dev, float* v_out, int batch, float p_drop, uint64_t seed,
+                                              void* ws, size_t ws_bytes, rgfm_stream_t stream) {
+  if (int rc = check_train(h, batch, ws, ws_bytes)) return rc;
+  if (!x || !t_dev || !v_out || (t_count != 1 && t_count != batch)) return fail(RGFM_EINVAL, "bad argument");
+  if (labels_dev && !h->num_classes) return fail(RGFM_EINVAL, "labels on a handle without classes (rgfm_unet_labeled_create makes one)");
+  if (int rc = check_p_drop(p_drop)) return rc;
+  return forward_walk(h, x, true, t_dev, t_count, v_out, batch, p_drop, seed, (float*)ws, plan_train(h, batch),
+                      (hipStream_t)stream, labels_dev);
 }
 
 extern "C" int rgfm_unet_backward(rgfm_unet* h, const float* dv, float* dx_out, float* dparams_out, int batch,

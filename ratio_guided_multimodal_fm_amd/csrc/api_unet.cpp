@@ -46,8 +46,26 @@ static int pack_weights(rgfm_unet* h, hipStream_t s) {
   return demote_by_norms(*h, gates, s);
 }
 
-extern "C" int rgfm_unet_create(const rgfm_unet_desc* desc, const float* params_dev, size_t n_floats,
-                                rgfm_stream_t stream, rgfm_unet** out) {
+// label_emb.weight [K + 1][temb] of a class-conditional net, in floats (K = 0: none)
+static size_t label_floats(const rgfm_unet_desc& d, int num_classes) {
+  return num_classes ? (size_t)(num_classes + 1) * (size_t)(4 * d.model_channels) : 0;
+}
+static int check_classes(int num_classes) {
+  // (a sampler call's class table holds 4096 rows, sampler_host.h: one stage of K + 1 classes must fit)
+  if (num_classes < 1 || num_classes >= 4096) return fail(RGFM_EINVAL, "num_classes must be in [1, 4096), got %d", num_classes);
+  return RGFM_OK;
+}
+
+extern "C" int rgfm_unet_labeled_param_floats(const rgfm_unet_desc* desc, int num_classes, size_t* n_floats) {
+  if (int rc = rgfm_unet_param_floats(desc, n_floats)) return rc;
+  if (int rc = check_classes(num_classes)) return rc;
+  *n_floats += label_floats(*desc, num_classes);
+  return RGFM_OK;
+}
+
+// num_classes 0: the unlabelled handle of rgfm_unet_create
+static int create_unet(const rgfm_unet_desc* desc, int num_classes, const float* params_dev, size_t n_floats,
+                       rgfm_stream_t stream, rgfm_unet** out) {
   int rc = check_desc(desc);
   if (rc) return rc;
   if (!params_dev || !out) return fail(RGFM_EINVAL, "null argument");
@@ -57,6 +75,8 @@ extern "C" int rgfm_unet_create(const rgfm_unet_desc* desc, const float* params_
   h->d = *desc;
   static_cast<UNetPlan&>(*h) = plan_unet(*desc);
   static_cast<WeightLayout&>(*h) = h->layout;
+  h->num_classes = num_classes, h->lemb = h->n_params;
+  h->n_params += label_floats(*desc, num_classes);  // (the store's count: alloc, update_params and the backward's blob follow it)
   if (h->n_params != n_floats) {
     const size_t want = h->n_params;
     delete h;
@@ -99,6 +119,17 @@ extern "C" int rgfm_unet_create(const rgfm_unet_desc* desc, const float* params_
   return RGFM_OK;
 }
 
+extern "C" int rgfm_unet_create(const rgfm_unet_desc* desc, const float* params_dev, size_t n_floats,
+                                rgfm_stream_t stream, rgfm_unet** out) {
+  return create_unet(desc, 0, params_dev, n_floats, stream, out);
+}
+extern "C" int rgfm_unet_labeled_create(const rgfm_unet_desc* desc, int num_classes, const float* params_dev, size_t n_floats,
+                                        rgfm_stream_t stream, rgfm_unet** out) {
+  if (int rc = check_desc(desc)) return rc;
+  if (int rc = check_classes(num_classes)) return rc;
+  return create_unet(desc, num_classes, params_dev, n_floats, stream, out);
+}
+
 extern "C" void rgfm_unet_destroy(rgfm_unet* h) {
   if (!h) return;
   h->free();
@@ -133,26 +164,39 @@ extern "C" int rgfm_unet_workspace_bytes(const rgfm_unet* h, int batch, size_t* 
   return RGFM_OK;
 }
 
-extern "C" int rgfm_unet_forward(rgfm_unet* h, const float* x, const float* t_dev, int t_count, float* v_out,
-                                 int batch, void* ws, size_t ws_bytes, rgfm_stream_t stream) {
+// labels (device int32 [batch]) non-null: the labelled forward -- a [batch]-row time table, row b of (t_b, label_b)
+static int unet_forward(rgfm_unet* h, const float* x, const float* t_dev, int t_count, const int* labels, float* v_out,
+                        int batch, void* ws, size_t ws_bytes, rgfm_stream_t stream) {
   refresh_modes();
   if (!h || !x || !t_dev || !v_out || !ws) return fail(RGFM_EINVAL, "null argument");
   if (batch < 1 || (t_count != 1 && t_count != batch)) return fail(RGFM_EINVAL, "t_count must be 1 or batch");
+  if (labels && !h->num_classes) return fail(RGFM_EINVAL, "labels on a handle without classes (rgfm_unet_labeled_create makes one)");
   hipStream_t s = (hipStream_t)stream;
   Bump b(ws, ws_bytes);
   size_t need = 0;
   rgfm_unet_workspace_bytes(h, batch, &need);
   if (need > ws_bytes) return fail(RGFM_ENOMEM, "workspace too small: %zu < %zu", ws_bytes, need);
-  float* table = b.f((size_t)t_count * h->temb_total);
+  const int rows = labels ? batch : t_count;
+  float* table = b.f((size_t)rows * h->temb_total);
   unsigned* cnt = b.u(batch);
   HIP_TRY(hipMemsetAsync(cnt, 0, (size_t)batch * sizeof(unsigned), s));
-  launch_time_table(h, t_dev, 1, 0, t_count, table, s);
-  UNetRun r{h, batch, &b, s, table, t_count == batch ? 1 : 0, false};
+  if (labels) launch_class_table(h, t_dev, t_count == 1, labels, 1, 0, rows, table, s);
+  else launch_time_table(h, t_dev, 1, 0, t_count, table, s);
+  UNetRun r{h, batch, &b, s, table, rows == batch ? 1 : 0, false};
   r.fin_counter = cnt;
   int rc = r.run(x, v_out, nullptr, 0.f);
   if (rc) return rc;
   HIP_TRY(hipGetLastError());
   return RGFM_OK;
+}
+
+extern "C" int rgfm_unet_forward(rgfm_unet* h, const float* x, const float* t_dev, int t_count, float* v_out,
+                                 int batch, void* ws, size_t ws_bytes, rgfm_stream_t stream) {
+  return unet_forward(h, x, t_dev, t_count, nullptr, v_out, batch, ws, ws_bytes, stream);
+}
+extern "C" int rgfm_unet_forward_labels(rgfm_unet* h, const float* x, const float* t_dev, int t_count, const int32_t* labels_dev,
+                                        float* v_out, int batch, void* ws, size_t ws_bytes, rgfm_stream_t stream) {
+  return unet_forward(h, x, t_dev, t_count, labels_dev, v_out, batch, ws, ws_bytes, stream);
 }
 
 extern "C" int rgfm_unet_time_embedding(rgfm_unet* h, const float* t_dev, int t_count, float* emb_out, void* ws,

@@ -493,6 +493,10 @@ struct rgfm_unet : WeightStore, UNetPlan {  // (the plan: unet_plan.h; its `layo
   TimeLinear* lin_dev = nullptr;
   float* wtmp = nullptr;  // scratch of the Upsample / Winograd weight images (kept for rgfm_unet_update_params)
   int nlin = 0;
+  // class conditioning (rgfm_unet_labeled_create): K classes, label_emb.weight [K + 1][temb] at `lemb`, behind the
+  // unlabelled blob (n_params counts it); 0: an unlabelled net
+  int num_classes = 0;
+  size_t lemb = 0;
   bool trace = false;
   int wino_convs = 0;   // convs of the latest walk described for the Winograd kernel (rgfm_unet_wino_convs)
   int up_merged = 0;    // convs of the latest walk that ran on conv_mfma_hx2u_kernel (rgfm_unet_up_merged)
@@ -821,7 +825,20 @@ inline TimeEmbedArgs time_embed_args(const rgfm_unet* h, const float* t_dev, int
   a.te0w = (int)h->te0w, a.te0b = (int)h->te0b, a.te2w = (int)h->te2w, a.te2b = (int)h->te2b;
   a.lin = h->lin_dev, a.nlin = h->nlin, a.total = h->temb_total;
   a.t_dev = t_dev, a.num_steps = num_steps, a.step_begin = step_begin, a.table = table;
+  // a class-conditional net without labels is its own unconditional branch: every row takes the null label
+  if (h->num_classes) a.label_emb = h->params + h->lemb, a.num_classes = h->num_classes, a.ncls = 1;
   return a;
+}
+
+// The time table of a labelled evaluation.  `labels` (device, one per row): row i is (t_dev[i] or t_dev[0], labels[i]),
+// the forward's per-row table.  Null: rows (stage, class) of a sampler call, [nt / (K + 1)][K + 1][total].
+inline int launch_class_table(rgfm_unet* h, const float* t_dev, int t_shared, const int* labels, int num_steps, int step_begin,
+                              int nt, float* table, hipStream_t s) {
+  ProfScope p(RGFM_KCLASS_OTHER, 0, s);
+  TimeEmbedArgs a = time_embed_args(h, t_dev, num_steps, step_begin, table);
+  a.labels = labels, a.t_shared = t_shared, a.ncls = labels ? 1 : h->num_classes + 1;
+  launch_time_embed(a, nt, s);
+  return RGFM_OK;
 }
 
 inline int launch_time_table(rgfm_unet* h, const float* t_dev, int num_steps, int step_begin, int nt, float* table,

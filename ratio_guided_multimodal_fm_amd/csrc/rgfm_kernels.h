@@ -237,6 +237,12 @@ struct TimeEmbedArgs {
   int num_steps, step_begin;
   float* table;            // [nt][total]
   float* emb_out;          // optional [nt][mc]: the sinusoidal embedding itself (parity hook)
+  // class-conditional nets (time_embed_labels_kernel); label_emb null: an unlabelled net, nothing below is read
+  const float* label_emb;  // [num_classes + 1][temb]; row num_classes is the null label
+  const int* labels;       // optional [nt]: the class of each row (outside 0..num_classes: the null label)
+  int num_classes;
+  int ncls;                // rows per time value: 1, or num_classes + 1 (row i: time i / ncls, class i % ncls without labels)
+  int t_shared;            // 1: every row reads t_dev[0]
 };
 
 // ---- the conv kernels (conv_mfma*.hip), one group per kernel.  Each file lists its instantiations ONCE (*_FOR_ALL):
@@ -493,6 +499,15 @@ void launch_step_inc(int* step, hipStream_t s);  // *step += 1
 void launch_sde_pre(const float* x, float* base, size_t n, uint64_t key, float a, float sigma, hipStream_t s);
 void launch_sde_noise(float* out, size_t n, uint64_t key, hipStream_t s);
 void launch_guid_schedule(float* sched, int step_begin, int ns, int num_steps, hipStream_t s);  // [ns][4] = {tf, s2, cden, 0}
+// class conditioning and classifier-free guidance (cfg.hip); a label outside 0..K reads as K on every path
+// rows[b][:] = table[stage][label_b][:], table [stages][K + 1][total] (total % 4 == 0): the per-row time table of a stage
+void launch_cfg_gather(const float* table, const int* labels, int K, int stage, int B, int total, float* rows, hipStream_t s);
+// out = base + (vu + w (vc - vu)) dts over n floats (out may be base)
+void launch_cfg_blend(const float* base, const float* vc, const float* vu, float w, float dts, size_t n, float* out, hipStream_t s);
+// training: emb[b][:] += E[label_b][:] (labels null: every row K), saved[b] = the label as used
+void launch_cfg_label_add(float* emb, const float* E, const int* labels, int K, int B, int temb, int* saved, hipStream_t s);
+// training: dE[c][:] = sum over rows b with saved[b] == c of g[b][:], in ascending b (one workgroup per class, no atomics)
+void launch_cfg_label_grad(const float* g, const int* saved, int K, int B, int temb, float* dE, hipStream_t s);
 // diagnostics (opt-in; rec: [B][RGFM_DIAG_FLOATS] records, include/rgfm.h)
 void launch_diag_wstats(const float* w, int B, int N, float* rec, hipStream_t s);  // ess, w_max, w_min of the rows of w [B][N]
 void launch_diag_rownorm(const float* v, int B, int D, float* rec, int slot, hipStream_t s);  // rec[b][slot] = |v[b]|_2, v [B][D], D % 4 == 0

@@ -205,13 +205,37 @@ struct NetChain {
   unsigned* cnt = nullptr;
   size_t mark = 0;
   int num_steps = 1, step_begin = 0;
+  // Class labels and classifier-free guidance (the *_cfg entry points; include/rgfm.h, "Class conditioning").  `cfg_ws`:
+  // the carve holds the labelled call's buffers, so that one query serves every scale.  With `labels` (device int32
+  // [batch]) the table is [stages][K + 1][temb_total], a stage's conditional evaluation reads `rowtab`, its rows gathered
+  // by label, and its unconditional one the stage's null row -- today's launch.  Without: nothing below is touched.
+  bool cfg_ws = false;
+  const int* labels = nullptr;
+  float cfg_scale = 1.f;
+  float *rowtab = nullptr, *vc = nullptr, *vu = nullptr;
 
   size_t image_floats() const { return (size_t)h->d.in_channels * h->d.img_size * h->d.img_size; }
+  int classes() const { return labels ? h->num_classes + 1 : 1; }  // table rows per stage
   void carve(Bump& bump) {
     b = &bump;
     table = bump.f((size_t)TABLE_ROWS * h->temb_total);
     cnt = bump.u(batch);
     mid = solver == SOLVER_MIDPOINT ? bump.f((size_t)batch * image_floats()) : nullptr;
+    if (cfg_ws) {
+      rowtab = bump.f((size_t)batch * h->temb_total);
+      vc = bump.f((size_t)batch * image_floats()), vu = bump.f((size_t)batch * image_floats());
+    }
+  }
+  // the argument check of the *_cfg entry points, before anything is carved or enqueued (ns: the call's steps)
+  int check_cfg(const int* labels_dev, double scale, int ns) {
+    cfg_ws = true, labels = labels_dev, cfg_scale = (float)scale;
+    if (!std::isfinite(scale)) return fail(RGFM_EINVAL, "cfg_scale must be finite (got %g)", scale);
+    if (!labels) return RGFM_OK;
+    if (!h->num_classes) return fail(RGFM_EINVAL, "labels on a handle without classes (rgfm_unet_labeled_create makes one)");
+    if ((long long)loop_stages(solver, ns) * classes() > TABLE_ROWS)
+      return fail(RGFM_EINVAL, "a labelled call holds at most %d (stage, class) rows: %d stages x %d classes; split the steps", TABLE_ROWS,
+                  loop_stages(solver, ns), classes());
+    return RGFM_OK;
   }
   void carve_eval() {  // one evaluation's activations, from the Bump's current offset (the walk of UNetRun, run dry)
     mark = b->off;
@@ -221,6 +245,10 @@ struct NetChain {
   int begin(hipStream_t stream, int num_steps_, int step_begin_, int ns) {
     s = stream, num_steps = num_steps_, step_begin = step_begin_;
     HIP_TRY(hipMemsetAsync(cnt, 0, (size_t)batch * sizeof(unsigned), s));
+    if (labels) {  // the class table: one row per (stage, class), the stages' times as launch_stage_table lays them out
+      const int f = solver == SOLVER_MIDPOINT ? 2 : 1;
+      return launch_class_table(h, nullptr, 0, nullptr, f * num_steps, f * step_begin, f * ns * classes(), table, s);
+    }
     return launch_stage_table(h, solver, num_steps, step_begin, ns, table, s);
   }
   // The net at `in` with time-table row `row` on `s`: v_out receives the raw velocity, state_out = base + v dts (the fused
@@ -228,9 +256,31 @@ struct NetChain {
   int eval(int row, hipStream_t s, const float* in, float* v_out, float* state_out, const float* base, float dts,
            const int* step_ptr = nullptr) {
     b->off = mark;
-    UNetRun r{h, batch, b, s, step_ptr ? table : table + (size_t)row * h->temb_total, 0, false};
+    // (a labelled call: the stage's null row, last of its K + 1 -- the unconditional evaluation)
+    const size_t trow = labels ? (size_t)row * classes() + h->num_classes : (size_t)row;
+    UNetRun r{h, batch, b, s, step_ptr ? table : table + trow * h->temb_total, 0, false};
     r.fin_counter = cnt, r.step_ptr = step_ptr;
     return r.run(in, v_out, state_out, dts, base);
+  }
+  // The conditional evaluation of a labelled call's stage: the rows' time table gathered by label, then eval's walk with a
+  // row of the table per sample (ConvArgs::temb_per_row).
+  int eval_cond(int row, hipStream_t s, const float* in, float* v_out, float* state_out, const float* base, float dts) {
+    b->off = mark;
+    launch_cfg_gather(table, labels, h->num_classes, row, batch, h->temb_total, rowtab, s);
+    UNetRun r{h, batch, b, s, rowtab, 1, false};
+    r.fin_counter = cnt;
+    return r.run(in, v_out, state_out, dts, base);
+  }
+  // One stage of a *_cfg call: state_out = base + (v_u + w (v_c - v_u)) dts.  w = 1: the conditional evaluation alone
+  // and w = 0 (or no labels): the unconditional one alone, each with the out-conv's fused update; else both raw
+  // velocities and the blend kernel, which takes the same (base, dts).
+  int eval_cfg(int row, hipStream_t s, const float* in, float* state_out, const float* base, float dts) {
+    if (!labels || cfg_scale == 0.f) return eval(row, s, in, nullptr, state_out, base, dts);
+    if (cfg_scale == 1.f) return eval_cond(row, s, in, nullptr, state_out, base, dts);
+    if (int rc = eval_cond(row, s, in, vc, nullptr, nullptr, dts)) return rc;
+    if (int rc = eval(row, s, in, vu, nullptr, nullptr, dts)) return rc;
+    launch_cfg_blend(base, vc, vu, cfg_scale, dts, (size_t)batch * image_floats(), state_out, s);
+    return RGFM_OK;
   }
   // one unguided step of `x` on `s`: every stage's update fused into the out-conv; `sde`: the stochastic step (stream 0)
   int step(int i, const Sde& sde = Sde()) {
@@ -240,7 +290,7 @@ struct NetChain {
       const float* base = nullptr;
       float dts = 0.f;
       if (int rc = sde.stage(st[k], num_steps, 0, x, (size_t)batch * image_floats(), s, x, &base, &dts)) return rc;
-      if (int rc = eval(st[k].row, s, st[k].reads_mid ? mid : x, nullptr, st[k].writes_mid ? mid : x, base, dts)) return rc;
+      if (int rc = eval_cfg(st[k].row, s, st[k].reads_mid ? mid : x, st[k].writes_mid ? mid : x, base, dts)) return rc;
     }
     return RGFM_OK;
   }

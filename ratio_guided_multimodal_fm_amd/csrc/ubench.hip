@@ -7,8 +7,9 @@
 
 #include "../../include/rgfm.h"
 
-namespace rgfm {  // (rgfm_kernels.h, sde.hip)
+namespace rgfm {  // (rgfm_kernels.h, sde.hip, cfg.hip)
 void launch_sde_pre(const float* x, float* base, size_t n, uint64_t key, float a, float sigma, hipStream_t s);
+void launch_cfg_blend(const float* base, const float* vc, const float* vu, float w, float dts, size_t n, float* out, hipStream_t s);
 }
 
 namespace {
@@ -193,5 +194,32 @@ extern "C" int rgfm_ubench_sde_pre(size_t n, double* gbps, double* us_per_launch
   (void)hipEventDestroy(e1);
   (void)hipFree(x);
   (void)hipFree(base);
+  return RGFM_OK;
+}
+
+// state = base + (v_u + w (v_c - v_u)) dts over n floats (launch_cfg_blend, the loops' own launch), in place as the
+// Euler stage runs it: GB/s of the 16 bytes per element the kernel moves (three reads, one write), and the time of one launch
+extern "C" int rgfm_ubench_cfg_blend(size_t n, double* gbps, double* us_per_launch) {
+  if (!gbps || !us_per_launch || n < 1) return RGFM_EINVAL;
+  float* buf = nullptr;  // state, v_c, v_u
+  if (hipMalloc(&buf, 3 * n * sizeof(float)) != hipSuccess) return RGFM_ENOMEM;
+  UB_TRY(hipMemset(buf, 0, 3 * n * sizeof(float)));
+  hipEvent_t e0, e1;
+  UB_TRY(hipEventCreate(&e0));
+  UB_TRY(hipEventCreate(&e1));
+  const int reps = 200;
+  for (int pass = 0; pass < 2; ++pass) {  // (the first pass warms up)
+    UB_TRY(hipEventRecord(e0, 0));
+    for (int r = 0; r < reps; ++r) rgfm::launch_cfg_blend(buf, buf + n, buf + 2 * n, 3.f, 0.02f, n, buf, 0);
+    UB_TRY(hipEventRecord(e1, 0));
+    UB_TRY(hipEventSynchronize(e1));
+  }
+  float ms = 0.f;
+  UB_TRY(hipEventElapsedTime(&ms, e0, e1));
+  *us_per_launch = (double)ms * 1e3 / reps;
+  *gbps = 16.0 * (double)n * reps / (ms * 1e-3) / 1e9;
+  (void)hipEventDestroy(e0);
+  (void)hipEventDestroy(e1);
+  (void)hipFree(buf);
   return RGFM_OK;
 }

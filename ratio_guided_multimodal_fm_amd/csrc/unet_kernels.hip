@@ -554,13 +554,30 @@ __device__ __forceinline__ float wave_sum(float v) {
   return v;
 }
 
-__global__ __launch_bounds__(256) void time_embed_kernel(const TimeEmbedArgs a) {
+// LABELS (a class-conditional net, include/rgfm.h "Class conditioning"): row i is (time value i / ncls, class), the
+// class from labels[i] (any value outside 0..K reads as K, the null row: an index taken from user data never leaves
+// the table), else i % ncls for ncls = K + 1 (the [stages][K + 1] table of a labelled sampler call), else K; and
+// emb = time_embed(...) + label_emb[class] in front of every time_mlp's SiLU.  Same LDS, same loops: temb = 1024 fits.
+template <bool LABELS>
+__device__ __forceinline__ void time_embed_body(const TimeEmbedArgs& a) {
   __shared__ float s_emb[256], s_h[1024], s_st[1024];
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   const int i = blockIdx.x;
+  const int ti = LABELS ? (a.t_shared ? 0 : i / a.ncls) : i;
+  const float* E = nullptr;
+  if (LABELS) {
+    int c = a.num_classes;
+    if (a.labels) {
+      c = a.labels[i];
+      if ((unsigned)c > (unsigned)a.num_classes) c = a.num_classes;
+    } else if (a.ncls > 1) {
+      c = i % a.ncls;
+    }
+    E = a.label_emb + (size_t)c * a.temb;
+  }
   float t;
-  if (a.t_dev) t = a.t_dev[i];
-  else t = (float)((double)(a.step_begin + i) * (1.0 / (double)a.num_steps));
+  if (a.t_dev) t = a.t_dev[ti];
+  else t = (float)((double)(a.step_begin + ti) * (1.0 / (double)a.num_steps));
   const int half = a.mc / 2;
   if (tid < half) {
     const float arg = t * a.freqs[tid];
@@ -581,7 +598,7 @@ __global__ __launch_bounds__(256) void time_embed_kernel(const TimeEmbedArgs a) 
     float acc = 0.f;
     for (int k = lane; k < a.temb; k += 64) acc += P[a.te2w + (size_t)o * a.temb + k] * s_h[k];
     acc = wave_sum(acc);
-    if (lane == 0) s_st[o] = silu_f(acc + P[a.te2b + o]);  // SiLU of time_mlp
+    if (lane == 0) s_st[o] = silu_f(LABELS ? (acc + P[a.te2b + o]) + E[o] : acc + P[a.te2b + o]);  // SiLU of time_mlp
   }
   __syncthreads();
   for (int li = 0; li < a.nlin; ++li) {
@@ -595,8 +612,12 @@ __global__ __launch_bounds__(256) void time_embed_kernel(const TimeEmbedArgs a) 
   }
 }
 
+__global__ __launch_bounds__(256) void time_embed_kernel(const TimeEmbedArgs a) { time_embed_body<false>(a); }
+__global__ __launch_bounds__(256) void time_embed_labels_kernel(const TimeEmbedArgs a) { time_embed_body<true>(a); }
+
 void launch_time_embed(const TimeEmbedArgs& a, int nt, hipStream_t s) {
-  hipLaunchKernelGGL(time_embed_kernel, dim3(nt), dim3(256), 0, s, a);
+  if (a.label_emb) hipLaunchKernelGGL(time_embed_labels_kernel, dim3(nt), dim3(256), 0, s, a);
+  else hipLaunchKernelGGL(time_embed_kernel, dim3(nt), dim3(256), 0, s, a);
 }
 
 // ------------------------------------------------------------------ weight packing

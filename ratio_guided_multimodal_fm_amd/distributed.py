@@ -222,7 +222,11 @@ def make_sharded_sampler(shape_x, shape_y, backend=None, group=None, gather="all
     stream exactly like the reference's sweep (evaluate_mnist_svhn.py:80: one seeding, no re-seed)."""
     def sampler(fm_x, fm_y, ratio_estimator=None, guidance_method='none', guidance_strength=0.0, num_samples=16,
                 num_steps=100, device='cuda', mc_batch_size=64, solver='euler', mc_pairing='paired',
-                guidance_schedule=None, sde_eta=0.0, sde_seed=None, ess_floor=None):
+                guidance_schedule=None, sde_eta=0.0, sde_seed=None, ess_floor=None, labels=None, cfg_scale=1.0):
+        if labels is not None or cfg_scale != 1.0:  # (before any draw)
+            from ._lib import RgfmError
+            raise RgfmError("labels / cfg_scale (class-conditional nets) have no sharded form: run them on one device; "
+                            "without labels a class-conditional net runs as its unconditional branch")
         if sde_eta:  # (before any draw)
             from ._lib import RgfmError
             raise RgfmError("sde_eta > 0 (the stochastic sampler) has no sharded form: run it on one device")

@@ -21,7 +21,8 @@ from .models.ratio_estimator import RatioEstimator
 from .sample import add_common_args, build_flow_models
 from .utils import load_checkpoint, set_seed
 from .utils.diagnostics import GuidanceDiagnostics, add_cli_args as add_diagnostics_args, row_metrics
-from .utils.flow_utils import add_ess_arg, add_sde_args, ess_from_cli, sde_from_cli, add_pairing_arg, sample_bimodal_guided, shared_mc_sweep
+from .utils.flow_utils import (add_ess_arg, add_label_args, add_sde_args, ess_from_cli, labels_from_cli, sde_from_cli, add_pairing_arg,
+                               sample_bimodal_guided, shared_mc_sweep)
 from .utils.guidance_schedule import add_cli_args as add_schedule_args, from_cli as schedule_from_cli
 from .utils.path_utils import get_checkpoint_path
 
@@ -50,9 +51,21 @@ def evaluate_coherence(samples_x, samples_y, classifier, device, transform_type=
     return {'coherence_acc': float(acc), 'num_samples': len(samples_x)}
 
 
+def label_accuracy(samples, classifier, labels, device, num_classes=None):
+    """Share of the rows whose class the classifier predicts as the requested label; rows with the null label
+    (`num_classes`) are left out.  nan without rows."""
+    classifier.eval()
+    labels = torch.as_tensor(labels).to(device).reshape(-1)
+    with torch.no_grad():
+        pred = classifier(samples.to(device)).argmax(dim=1)
+    keep = labels != num_classes if num_classes is not None else torch.ones_like(labels, dtype=torch.bool)
+    return float((pred[keep] == labels[keep]).float().mean().item()) if int(keep.sum()) else float('nan')
+
+
 def run_sweep(fm_x, fm_y, make_ratio, classifier, methods, strengths, num_samples, num_steps, device,
               mc_batch_size, transform_type, sampler=sample_bimodal_guided, solver='euler', diagnostics=False,
-              mc_pairing='paired', shared_mc=False, guidance_schedule=None, sde_eta=0.0, sde_seed=None, ess_floor=None):
+              mc_pairing='paired', shared_mc=False, guidance_schedule=None, sde_eta=0.0, sde_seed=None, ess_floor=None,
+              labels=None, cfg_scale=1.0):
     """The reference's nested loop (:165-222). `make_ratio()` returns a fresh ratio estimator or None.
     `solver` ('euler' | 'midpoint') goes to `sampler` as a keyword when it is not the default.
     `diagnostics`: every guided row also gets ess_mean, ess_min and w_max of the importance weights at step
@@ -68,7 +81,12 @@ def run_sweep(fm_x, fm_y, make_ratio, classifier, methods, strengths, num_sample
     own seed after its other draws); the keywords go to `sampler` only then, and every row gains ``"sde_eta"``.
     `ess_floor`: the 'mc_feng' configurations hold their importance weights to this effective sample size
     (``paired_sampler``; the sampler's `ess_floor` keyword) and their rows record ``"ess_floor"``; it goes with no
-    gradient method among `methods` (they have no weights: ``RgfmError``) and has no sharded form.  None: nothing changes."""
+    gradient method among `methods` (they have no weights: ``RgfmError``) and has no sharded form.  None: nothing changes.
+    `labels` (an integer tensor [num_samples]) with `cfg_scale`: the class-conditional baseline.  The 'none' configuration
+    samples both nets with these labels (``paired_sampler``) and its row gains ``"labelled": true``, ``"cfg_scale"`` and
+    ``label_accuracy_x`` / ``label_accuracy_y`` -- the classifier's prediction on x and on the inverse-transformed y against the requested label (null-label
+    rows left out) -- beside the coherence.  It goes with no guided method among `methods` and has no sharded form
+    (``RgfmError``).  None: nothing changes."""
     from ._lib import solver_id
     from .utils.flow_utils import check_pairing
     solver_id(solver)
@@ -88,6 +106,14 @@ def run_sweep(fm_x, fm_y, make_ratio, classifier, methods, strengths, num_sample
             raise RgfmError("ess_floor has no sharded form: run the tempered sampler on one device")
     if shared_mc and sampler is not sample_bimodal_guided:
         raise ValueError("shared_mc runs the default sampler: it has no sharded form")
+    if labels is not None:
+        from ._lib import RgfmError
+        if any(m != 'none' for m in methods):
+            raise RgfmError(f"labels go with the 'none' method alone (the supervised baseline); {list(methods)} holds a guided "
+                            "method: sweep it without labels, in a run of its own")
+        if sampler is not sample_bimodal_guided:
+            raise RgfmError("labels have no sharded form: run the labelled sampler on one device")
+    lab_kw = {'labels': labels, 'cfg_scale': float(cfg_scale)} if labels is not None else {}
     results = []
     for method in methods:
         # `extra` (below): what an 'mc_feng' configuration adds, to the sampler's keywords and to its result rows alike
@@ -123,8 +149,14 @@ def run_sweep(fm_x, fm_y, make_ratio, classifier, methods, strengths, num_sample
             if ess_floor is not None and method == 'mc_feng':
                 extra['ess_floor'] = float(ess_floor)
             xs, ys = sampler(fm_x, fm_y, ratio, method, strength, num_samples, num_steps, device, mc_batch_size, **kw,
-                             **({'diagnostics': diag} if diag is not None else {}), **extra)
+                             **({'diagnostics': diag} if diag is not None else {}), **extra, **lab_kw)
             metrics = evaluate_coherence(xs, ys, classifier, device, transform_type)
+            if lab_kw:
+                K = getattr(fm_x, 'num_classes', None)
+                metrics = {**metrics, 'labelled': True, 'cfg_scale': float(cfg_scale),
+                           'label_accuracy_x': label_accuracy(xs, classifier, labels, device, K),
+                           'label_accuracy_y': label_accuracy(get_inverse_transform(transform_type)(ys), classifier, labels,
+                                                              device, K)}
             if diag is not None and diag.records is not None:
                 metrics = {**metrics, **row_metrics(diag, num_steps)}
             if shared_mc:
@@ -146,6 +178,7 @@ def main(argv=None):
     add_schedule_args(p)
     add_sde_args(p)
     add_ess_arg(p)
+    add_label_args(p)
     p.add_argument('--shared_mc', action='store_true',
                    help='run all strengths of a guided method as one sampler call over one MC set, one pre-phase and one '
                         'start-noise set (a strength per row): the strengths then differ by the strength alone; --model unet')
@@ -156,6 +189,8 @@ def main(argv=None):
         p.error('--guidance_schedule / --guidance_window / --shared_mc go with --model unet')
 
     set_seed(args.seed)
+    lab_kw = labels_from_cli(args, args.num_samples, guided=bool(args.labels) and any(m != 'none' for m in args.guidance_methods),
+                             unet=args.model == 'unet')
     if not torch.cuda.is_available():
         raise RuntimeError("no HIP device visible; the sampler has no CPU path")
     device = torch.device(args.device)
@@ -169,7 +204,7 @@ def main(argv=None):
             return 1
     classifier = MNISTClassifier().to(device)
     classifier.load_state_dict(torch.load(clf_path, map_location=device))
-    fm_x, fm_y = build_flow_models(args.model, device)
+    fm_x, fm_y = build_flow_models(args.model, device, args.num_classes)
     load_checkpoint(fm_x, path_x, device, ema=args.ema)
     load_checkpoint(fm_y, path_y, device, ema=args.ema)
 
@@ -185,7 +220,7 @@ def main(argv=None):
     results = run_sweep(fm_x, fm_y, make_ratio, classifier, args.guidance_methods, args.guidance_strengths,
                         args.num_samples, args.num_steps, device, args.mc_batch_size, args.transform_type, solver=args.solver,
                         diagnostics=args.diagnostics, mc_pairing=args.mc_pairing, shared_mc=args.shared_mc,
-                        guidance_schedule=schedule, **sde_kw)
+                        guidance_schedule=schedule, **sde_kw, **lab_kw)
     os.makedirs('outputs', exist_ok=True)
     out = 'outputs/evaluation_results.json'
     with open(out, 'w') as f:

@@ -29,7 +29,8 @@ from .models.unet_flexible import FlowMatchingUNetMNIST, FlowMatchingUNetSVHN
 from .sample_mnist_svhn import sample_bimodal_guided_mnist_svhn
 from .utils import load_checkpoint, set_seed
 from .utils.diagnostics import GuidanceDiagnostics, add_cli_args as add_diagnostics_args, row_metrics
-from .utils.flow_utils import add_ess_arg, add_sde_args, ess_from_cli, sde_from_cli, add_pairing_arg, shared_mc_sweep
+from .utils.flow_utils import (add_ess_arg, add_label_args, add_sde_args, ess_from_cli, labels_from_cli, sde_from_cli, add_pairing_arg,
+                               shared_mc_sweep)
 from .utils.guidance_schedule import add_cli_args as add_schedule_args, from_cli as schedule_from_cli
 
 
@@ -42,6 +43,17 @@ def evaluate_coherence(samples_mnist, samples_svhn, mnist_classifier, svhn_class
         pred_s = svhn_classifier(samples_svhn.to(device)).argmax(dim=1)
     acc = (pred_m == pred_s).float().mean().item() if len(samples_mnist) else float('nan')
     return {'coherence_acc': float(acc), 'num_samples': len(samples_mnist)}
+
+
+def label_accuracy(samples, classifier, labels, device, num_classes=None):
+    """Share of the rows whose class the classifier predicts as the requested label; rows with the null label
+    (`num_classes`) are left out.  nan without rows."""
+    classifier.eval()
+    labels = torch.as_tensor(labels).to(device).reshape(-1)
+    with torch.no_grad():
+        pred = classifier(samples.to(device)).argmax(dim=1)
+    keep = labels != num_classes if num_classes is not None else torch.ones_like(labels, dtype=torch.bool)
+    return float((pred[keep] == labels[keep]).float().mean().item()) if int(keep.sum()) else float('nan')
 
 
 def evaluate_conditional_coherence(condition, samples, given, mnist_classifier, svhn_classifier, device,
@@ -69,7 +81,8 @@ def evaluate_conditional_coherence(condition, samples, given, mnist_classifier, 
 
 def run_sweep(fm_mnist, fm_svhn, make_ratio, mnist_classifier, svhn_classifier, methods, strengths,
               num_samples, num_steps, device, mc_batch_size, sampler=sample_bimodal_guided_mnist_svhn, solver='euler', diagnostics=False,
-              mc_pairing='paired', shared_mc=False, guidance_schedule=None, sde_eta=0.0, sde_seed=None, ess_floor=None):
+              mc_pairing='paired', shared_mc=False, guidance_schedule=None, sde_eta=0.0, sde_seed=None, ess_floor=None,
+              labels=None, cfg_scale=1.0):
     """The reference's nested loop (:130-183). `make_ratio()` returns a fresh ratio estimator or None.
     `solver` ('euler' | 'midpoint') goes to `sampler` as a keyword when it is not the default.
     `diagnostics`: every guided row also gets ess_mean, ess_min and w_max of the importance weights at step
@@ -85,7 +98,12 @@ def run_sweep(fm_mnist, fm_svhn, make_ratio, mnist_classifier, svhn_classifier, 
     own seed after its other draws); the keywords go to `sampler` only then, and every row gains ``"sde_eta"``.
     `ess_floor`: the 'mc_feng' configurations hold their importance weights to this effective sample size
     (``paired_sampler``; the sampler's `ess_floor` keyword) and their rows record ``"ess_floor"``; it goes with no
-    gradient method among `methods` (they have no weights: ``RgfmError``) and has no sharded form.  None: nothing changes."""
+    gradient method among `methods` (they have no weights: ``RgfmError``) and has no sharded form.  None: nothing changes.
+    `labels` (an integer tensor [num_samples]) with `cfg_scale`: the class-conditional baseline.  The 'none' configuration
+    samples both nets with these labels (``paired_sampler``) and its row gains ``"labelled": true``, ``"cfg_scale"`` and
+    ``label_accuracy_x`` / ``label_accuracy_y`` -- each classifier's prediction against the requested label (null-label
+    rows left out) -- beside the coherence.  It goes with no guided method among `methods` and has no sharded form
+    (``RgfmError``).  None: nothing changes."""
     from ._lib import solver_id
     from .utils.flow_utils import check_pairing
     solver_id(solver)
@@ -105,6 +123,14 @@ def run_sweep(fm_mnist, fm_svhn, make_ratio, mnist_classifier, svhn_classifier, 
             raise RgfmError("ess_floor has no sharded form: run the tempered sampler on one device")
     if shared_mc and sampler is not sample_bimodal_guided_mnist_svhn:
         raise ValueError("shared_mc runs the default sampler: it has no sharded form")
+    if labels is not None:
+        from ._lib import RgfmError
+        if any(m != 'none' for m in methods):
+            raise RgfmError(f"labels go with the 'none' method alone (the supervised baseline); {list(methods)} holds a guided "
+                            "method: sweep it without labels, in a run of its own")
+        if sampler is not sample_bimodal_guided_mnist_svhn:
+            raise RgfmError("labels have no sharded form: run the labelled sampler on one device")
+    lab_kw = {'labels': labels, 'cfg_scale': float(cfg_scale)} if labels is not None else {}
     results = []
     for method in methods:
         # `extra` (below): what an 'mc_feng' configuration adds, to the sampler's keywords and to its result rows alike
@@ -140,8 +166,13 @@ def run_sweep(fm_mnist, fm_svhn, make_ratio, mnist_classifier, svhn_classifier, 
             if ess_floor is not None and method == 'mc_feng':
                 extra['ess_floor'] = float(ess_floor)
             xs, ys = sampler(fm_mnist, fm_svhn, ratio, method, strength, num_samples, num_steps, device,
-                             mc_batch_size, **kw, **({'diagnostics': diag} if diag is not None else {}), **extra)
+                             mc_batch_size, **kw, **({'diagnostics': diag} if diag is not None else {}), **extra, **lab_kw)
             metrics = evaluate_coherence(xs, ys, mnist_classifier, svhn_classifier, device)
+            if lab_kw:
+                K = getattr(fm_mnist, 'num_classes', None)
+                metrics = {**metrics, 'labelled': True, 'cfg_scale': float(cfg_scale),
+                           'label_accuracy_x': label_accuracy(xs, mnist_classifier, labels, device, K),
+                           'label_accuracy_y': label_accuracy(ys, svhn_classifier, labels, device, K)}
             if diag is not None and diag.records is not None:
                 metrics = {**metrics, **row_metrics(diag, num_steps)}
             if shared_mc:
@@ -173,6 +204,7 @@ def main(argv=None):
     add_schedule_args(p)
     add_sde_args(p)
     add_ess_arg(p)
+    add_label_args(p)
     p.add_argument('--shared_mc', action='store_true',
                    help='run all strengths of a guided method as one sampler call over one MC set, one pre-phase and one '
                         'start-noise set (a strength per row): the strengths then differ by the strength alone; not with '
@@ -190,6 +222,8 @@ def main(argv=None):
         p.error('--mc_pairing cross has no --sharded form')
 
     set_seed(args.seed)  # (every rank alike: the sharded sampler slices ONE noise set)
+    lab_kw = labels_from_cli(args, args.num_samples, sharded=args.sharded,
+                             guided=bool(args.labels) and any(m != 'none' for m in args.guidance_methods))
     if not torch.cuda.is_available():
         raise RuntimeError("no HIP device visible; the sampler has no CPU path")
     rank, sampler = 0, sample_bimodal_guided_mnist_svhn
@@ -211,8 +245,8 @@ def main(argv=None):
     svhn_clf = SVHNClassifier().to(device)
     mnist_clf.load_state_dict(torch.load(paths['mnist_clf'], map_location=device))
     svhn_clf.load_state_dict(torch.load(paths['svhn_clf'], map_location=device))
-    fm_mnist = FlowMatchingUNetMNIST(img_size=32).to(device)
-    fm_svhn = FlowMatchingUNetSVHN().to(device)
+    fm_mnist = FlowMatchingUNetMNIST(img_size=32, num_classes=args.num_classes).to(device)
+    fm_svhn = FlowMatchingUNetSVHN(num_classes=args.num_classes).to(device)
     load_checkpoint(fm_mnist, paths['fm_mnist'], device, ema=args.ema)
     load_checkpoint(fm_svhn, paths['fm_svhn'], device, ema=args.ema)
 
@@ -228,7 +262,7 @@ def main(argv=None):
     results = run_sweep(fm_mnist, fm_svhn, make_ratio, mnist_clf, svhn_clf, args.guidance_methods,
                         args.guidance_strengths, args.num_samples, args.num_steps, device, args.mc_batch_size,
                         sampler=sampler, solver=args.solver, diagnostics=args.diagnostics, mc_pairing=args.mc_pairing,
-                        shared_mc=args.shared_mc, guidance_schedule=schedule, **sde_kw)
+                        shared_mc=args.shared_mc, guidance_schedule=schedule, **sde_kw, **lab_kw)
     if args.sharded:
         import torch.distributed as dist
         if dist.is_initialized():

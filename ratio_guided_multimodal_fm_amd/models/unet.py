@@ -10,15 +10,15 @@ from .unet_flexible import FlexibleUNet, timestep_embedding  # noqa: F401
 
 class UNetMNIST(FlexibleUNet):
     def __init__(self, in_channels=1, model_channels=32, channel_mult=(1, 2, 2), num_res_blocks=2,
-                 dropout=0.0):
+                 dropout=0.0, num_classes=None):
         super().__init__(in_channels=in_channels, img_size=28, model_channels=model_channels,
-                         channel_mult=channel_mult, num_res_blocks=num_res_blocks, dropout=dropout)
+                         channel_mult=channel_mult, num_res_blocks=num_res_blocks, dropout=dropout, num_classes=num_classes)
 
 
 class FlowMatchingUNet(UNetMNIST):
     """Default velocity net of ``src/sample.py`` (``--model unet``)."""
 
     def __init__(self, img_channels=1, model_channels=32, channel_mult=(1, 2), num_res_blocks=2,
-                 dropout=0.1):
+                 dropout=0.1, num_classes=None):
         super().__init__(in_channels=img_channels, model_channels=model_channels,
-                         channel_mult=channel_mult, num_res_blocks=num_res_blocks, dropout=dropout)
+                         channel_mult=channel_mult, num_res_blocks=num_res_blocks, dropout=dropout, num_classes=num_classes)

@@ -66,8 +66,11 @@ class FlexibleUNet(nn.Module):
     _engine = engine_property(lambda m: UNetEngine(m))
 
     def __init__(self, in_channels=1, img_size=28, model_channels=32, channel_mult=(1, 2),
-                 num_res_blocks=2, dropout=0.1):
+                 num_res_blocks=2, dropout=0.1, num_classes=None):
         super().__init__()
+        if num_classes is not None and (not isinstance(num_classes, int) or isinstance(num_classes, bool) or num_classes < 1):
+            raise ValueError(f"num_classes must be None or an integer >= 1, got {num_classes!r}")
+        self.num_classes = num_classes
         self.in_channels = in_channels
         self.img_size = img_size
         self.model_channels = model_channels
@@ -110,31 +113,43 @@ class FlexibleUNet(nn.Module):
         # the reference zero-initialises the output conv (:200-201)
         nn.init.zeros_(self.out_conv.weight)
         nn.init.zeros_(self.out_conv.bias)
+        # Class conditioning (an extension: the reference's nets are unconditional).  Registered AFTER every module of
+        # the reference, so `label_emb.weight` is the last state_dict entry and every other blob offset stays put.
+        # emb = time_embed(timestep_embedding(t)) + label_emb[y]; row num_classes is the null label.
+        if num_classes is not None:
+            self.label_emb = nn.Embedding(num_classes + 1, temb)
 
+    def forward(self, x, t, y=None):
+        """x: [B,C,H,W] fp32 on a HIP device, t: [B] (or [1]) -> velocity [B,C,H,W] (eval mode only).  `y` (nets built
+        with ``num_classes=K``): an integer tensor [B] of labels in 0..K, K the null label; None: the null label in
+        every row, the net's unconditional branch."""
+        return self._engine.forward(x, t, y)
 
-    def forward(self, x, t):
-        """x: [B,C,H,W] fp32 on a HIP device, t: [B] (or [1]) -> velocity [B,C,H,W] (eval mode only)."""
-        return self._engine.forward(x, t)
-
-    def forward_train(self, x, t):
+    def forward_train(self, x, t, y=None):
         """Differentiable forward for training: ``loss.backward()`` fills ``p.grad`` and ``x.grad`` through the
-        HIP backward (rgfm_unet_forward_train / rgfm_unet_backward).  Dropout applies while ``self.training``."""
-        return self._engine.forward_train(x, t)
+        HIP backward (rgfm_unet_forward_train / rgfm_unet_backward).  Dropout applies while ``self.training``.
+        `y`: labels as in ``forward`` (``label_emb.weight.grad`` is filled like every other parameter's)."""
+        return self._engine.forward_train(x, t, y)
 
-    def linearize(self, x, t):
+    def linearize(self, x, t, y=None):
         """One exact-fp32 forward at (x, t) that keeps its state: ``.v`` = v(x, t) and ``.vjp(u)`` = J^T u with
-        J = dv/dx, as often as wanted (rgfm_unet_forward_train with no dropout / rgfm_unet_vjp)."""
+        J = dv/dx, as often as wanted (rgfm_unet_forward_train with no dropout / rgfm_unet_vjp).  The likelihood path
+        has no labelled form: `y` other than None raises ``RgfmError`` (here, in ``vjp`` and in ``divergence``); a
+        class-conditional net runs it as its unconditional branch."""
+        self._engine.no_labels(y, "linearize")
         return self._engine.linearize(x, t)
 
-    def vjp(self, x, t, u):
+    def vjp(self, x, t, u, y=None):
         """J^T u for J = dv/dx at (x, t): the HIP reverse walk restricted to the path to x (no parameter gradients).
         What ``torch.autograd.grad(model.forward_train(x, t), x, u)`` returns in eval mode, to the bit."""
+        self._engine.no_labels(y, "vjp")
         return self._engine.linearize(x, t).vjp(u)
 
-    def divergence(self, x, t, eps):
+    def divergence(self, x, t, eps, y=None):
         """``(v, div)``: v(x, t) and the Hutchinson estimate ``div[b] = mean_k <eps_k[b], J^T eps_k[b]>`` of the
         divergence of v at x for the probes ``eps [K, B, C, H, W]`` (rgfm_unet_divergence; one forward, K reverse
         walks).  The K = d probes ``sqrt(d) e_i`` give the exact trace."""
+        self._engine.no_labels(y, "divergence")
         return self._engine.divergence(x, t, eps)
 
     def _resblocks(self):
@@ -173,14 +188,14 @@ class FlexibleUNet(nn.Module):
 class FlowMatchingUNetMNIST(FlexibleUNet):
     """MNIST preset, 1x28x28 or 1x32x32 (reference :266-277)."""
 
-    def __init__(self, img_size=28):
+    def __init__(self, img_size=28, num_classes=None):
         super().__init__(in_channels=1, img_size=img_size, model_channels=32, channel_mult=(1, 2),
-                         num_res_blocks=2, dropout=0.1)
+                         num_res_blocks=2, dropout=0.1, num_classes=num_classes)
 
 
 class FlowMatchingUNetSVHN(FlexibleUNet):
     """SVHN preset, 3x32x32 (reference :280-291)."""
 
-    def __init__(self):
+    def __init__(self, num_classes=None):
         super().__init__(in_channels=3, img_size=32, model_channels=64, channel_mult=(1, 2, 2),
-                         num_res_blocks=2, dropout=0.1)
+                         num_res_blocks=2, dropout=0.1, num_classes=num_classes)

@@ -16,15 +16,18 @@ from .models.ratio_estimator import RatioEstimator
 from .models.unet import FlowMatchingUNet
 from .utils import load_checkpoint, set_seed
 from .utils.diagnostics import GuidanceDiagnostics, add_cli_args as add_diagnostics_args, report_diagnostics
-from .utils.flow_utils import add_ess_arg, add_pairing_arg, add_sde_args, ess_from_cli, sample_bimodal_guided, sde_from_cli
+from .utils.flow_utils import (add_ess_arg, add_label_args, add_pairing_arg, add_sde_args, ess_from_cli, labels_from_cli,
+                               sample_bimodal_guided, sde_from_cli)
 from .utils.guidance_schedule import add_cli_args as add_schedule_args, from_cli as schedule_from_cli
 from .utils.path_utils import get_checkpoint_path
 
 
-def build_flow_models(model, device):
-    """The reference's ``--model`` switch (:149-154)."""
+def build_flow_models(model, device, num_classes=None):
+    """The reference's ``--model`` switch (:149-154); `num_classes`: class-conditional U-Nets (--num_classes)."""
     if model == 'unet':
-        return FlowMatchingUNet().to(device), FlowMatchingUNet().to(device)
+        return FlowMatchingUNet(num_classes=num_classes).to(device), FlowMatchingUNet(num_classes=num_classes).to(device)
+    if num_classes is not None:
+        raise ValueError("--num_classes goes with --model unet")
     if model == 'original':
         return FlowMatchingModel().to(device), FlowMatchingModel().to(device)
     raise ValueError(f"unknown --model {model!r} (choices: unet, original)")
@@ -54,6 +57,7 @@ def main(argv=None):
     add_schedule_args(p)
     add_sde_args(p)
     add_ess_arg(p)
+    add_label_args(p)
     args = p.parse_args(argv)
     schedule = schedule_from_cli(args)
     sde_kw = {**sde_from_cli(args), **ess_from_cli(args)}
@@ -64,13 +68,14 @@ def main(argv=None):
     diag = GuidanceDiagnostics() if args.diagnostics or args.diagnostics_out else None
 
     set_seed(args.seed)
+    lab_kw = labels_from_cli(args, args.num_samples, guided=args.guidance_method != 'none', unet=args.model == 'unet')
     print(f"Random seed: {args.seed}")
     if not torch.cuda.is_available():
         raise RuntimeError("no HIP device visible; this sampler has no CPU path")
     device = torch.device(args.device)
     print(f"Using device: {device}")
 
-    fm_x, fm_y = build_flow_models(args.model, device)
+    fm_x, fm_y = build_flow_models(args.model, device, args.num_classes)
     path_x = get_checkpoint_path('flow', 'x', None, 'best')
     path_y = get_checkpoint_path('flow', 'y', args.transform_type, 'best')
     preset = 'original' if args.model == 'original' else 'unet28'
@@ -97,7 +102,7 @@ def main(argv=None):
     xs, ys = sample_bimodal_guided(fm_x, fm_y, ratio, args.guidance_method, args.guidance_strength,
                                    args.num_samples, args.num_steps, device, args.mc_batch_size, solver=args.solver,
                                    diagnostics=diag, mc_pairing=args.mc_pairing,
-                                   **({'guidance_schedule': schedule} if schedule is not None else {}), **sde_kw)
+                                   **({'guidance_schedule': schedule} if schedule is not None else {}), **sde_kw, **lab_kw)
     report_diagnostics(diag, args.num_steps, args.diagnostics, args.diagnostics_out)
     os.makedirs('outputs', exist_ok=True)
     out = f"outputs/samples_{args.guidance_method}_gamma{args.guidance_strength}_{args.transform_type}.pt"

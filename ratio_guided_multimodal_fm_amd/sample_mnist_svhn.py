@@ -14,7 +14,8 @@ from .models.ratio_flexible import RatioEstimatorMNISTSVHN
 from .models.unet_flexible import FlowMatchingUNetMNIST, FlowMatchingUNetSVHN
 from .utils import load_checkpoint, set_seed
 from .utils.diagnostics import GuidanceDiagnostics, add_cli_args as add_diagnostics_args, report_diagnostics
-from .utils.flow_utils import add_ess_arg, add_pairing_arg, add_sde_args, ess_from_cli, paired_sampler, sample_conditional, sde_from_cli
+from .utils.flow_utils import (add_ess_arg, add_label_args, add_pairing_arg, add_sde_args, ess_from_cli, labels_from_cli, paired_sampler,
+                               sample_conditional, sde_from_cli)
 from .utils.guidance_schedule import add_cli_args as add_schedule_args, from_cli as schedule_from_cli
 
 
@@ -22,15 +23,16 @@ def sample_bimodal_guided_mnist_svhn(fm_mnist, fm_svhn, ratio_estimator=None, gu
                                      guidance_strength=0.0, num_samples=16, num_steps=100,
                                      device='cuda', mc_batch_size=64, solver='euler', diagnostics=None,
                                      mc_pairing='paired', guidance_schedule=None, sde_eta=0.0, sde_seed=None,
-                                     ess_floor=None):
+                                     ess_floor=None, labels=None, cfg_scale=1.0):
     """Returns ``(samples_mnist [n,1,32,32], samples_svhn [n,3,32,32])`` on `device`.  `diagnostics`: a
     ``utils.diagnostics.GuidanceDiagnostics`` to fill; `mc_pairing`: 'paired' | 'cross'; `guidance_strength`: a float or
     one strength per sample; `guidance_schedule`: a scale of it per stage; `sde_eta`, `sde_seed`: the stochastic sampler;
-    `ess_floor`: the effective-sample-size floor of the importance weights (all: ``paired_sampler``)."""
+    `ess_floor`: the effective-sample-size floor of the importance weights; `labels`, `cfg_scale`
+    (``guidance_method='none'``): the class-conditional pair (all: ``paired_sampler``)."""
     return paired_sampler(fm_mnist, fm_svhn, ratio_estimator, guidance_method, guidance_strength,
                           num_samples, num_steps, device, mc_batch_size, (1, 32, 32), (3, 32, 32), solver=solver,
                           diagnostics=diagnostics, mc_pairing=mc_pairing, guidance_schedule=guidance_schedule,
-                          sde_eta=sde_eta, sde_seed=sde_seed, ess_floor=ess_floor)
+                          sde_eta=sde_eta, sde_seed=sde_seed, ess_floor=ess_floor, labels=labels, cfg_scale=cfg_scale)
 
 
 def load_condition(path, shape):
@@ -74,6 +76,7 @@ def main(argv=None):
     add_schedule_args(p)
     add_sde_args(p)
     add_ess_arg(p)
+    add_label_args(p)
     args = p.parse_args(argv)
     schedule = schedule_from_cli(args)
     sde_kw = {**sde_from_cli(args, args.sharded), **ess_from_cli(args, args.sharded)}
@@ -90,6 +93,8 @@ def main(argv=None):
         p.error('conditional sampling has no --sharded form')
 
     set_seed(args.seed)  # (every rank alike: the sharded sampler slices ONE noise set)
+    lab_kw = labels_from_cli(args, args.num_samples, sharded=args.sharded,
+                             guided=args.guidance_method != 'none' or bool(args.given))
     print(f"Random seed: {args.seed}")
     if not torch.cuda.is_available():
         raise RuntimeError("no HIP device visible; this sampler has no CPU path")
@@ -103,8 +108,8 @@ def main(argv=None):
         device = torch.device(args.device)
     print(f"Using device: {device}")
 
-    fm_mnist = FlowMatchingUNetMNIST(img_size=32).to(device)
-    fm_svhn = FlowMatchingUNetSVHN().to(device)
+    fm_mnist = FlowMatchingUNetMNIST(img_size=32, num_classes=args.num_classes).to(device)
+    fm_svhn = FlowMatchingUNetSVHN(num_classes=args.num_classes).to(device)
     for model, path, hint in ((fm_mnist, 'checkpoints/flow_mnist32_best.pth', 'train_flow_mnist32.py'),
                               (fm_svhn, 'checkpoints/flow_svhn_best.pth', 'train_flow_svhn.py')):
         if not os.path.exists(path):
@@ -148,7 +153,7 @@ def main(argv=None):
                      args.num_steps, device, args.mc_batch_size, **({'solver': args.solver} if args.solver != 'euler' else {}),
                      **({'diagnostics': diag} if diag is not None else {}),
                      **({'mc_pairing': args.mc_pairing} if args.mc_pairing != 'paired' else {}),
-                     **({'guidance_schedule': schedule} if schedule is not None else {}), **sde_kw)
+                     **({'guidance_schedule': schedule} if schedule is not None else {}), **sde_kw, **lab_kw)
     report_diagnostics(diag, args.num_steps, args.diagnostics, args.diagnostics_out)
     if args.sharded:
         import torch.distributed as dist

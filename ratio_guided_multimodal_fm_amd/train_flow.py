@@ -27,7 +27,8 @@ from .utils.optim import add_optimizer_args, build_optimizer, check_optimizer_ar
 
 PRESETS = {
     # preset: (constructor, image shape, checkpoint stem) -- the stems sample_mnist_svhn.py / sample.py load
-    'mnist32': (lambda: FlowMatchingUNetMNIST(32), (1, 32, 32), 'flow_mnist32'),
+    # (the U-Net constructors take num_classes: --num_classes)
+    'mnist32': (lambda **kw: FlowMatchingUNetMNIST(32, **kw), (1, 32, 32), 'flow_mnist32'),
     'svhn': (FlowMatchingUNetSVHN, (3, 32, 32), 'flow_svhn'),
     'unet28': (FlowMatchingUNet, (1, 28, 28), 'flow_unet28'),
     'original': (FlowMatchingModel, (1, 28, 28), None),  # (stem from --modality: checkpoint_stem)
@@ -59,9 +60,18 @@ def parse_args(argv=None):
     p.add_argument('--modality', type=str, default=None, choices=['x', 'y'],
                    help='28x28 presets: which modality the data is (selects the checkpoint name)')
     p.add_argument('--transform_type', type=str, default='rotate90', help='names the y checkpoint')
+    p.add_argument('--num_classes', type=int, default=None,
+                   help="train a class-conditional net (U-Net presets): --data is then a .npz / .pt with 'x' [N,C,H,W] and "
+                        "'label' [N] in 0..num_classes-1, as train_classifier reads; stored in the checkpoint")
+    p.add_argument('--p_uncond', type=float, default=0.1,
+                   help='--num_classes: probability that a label is replaced by the null label (classifier-free training)')
     add_optimizer_args(p)
     args = p.parse_args(argv)
     check_optimizer_args(p, args)
+    if args.num_classes is not None and (args.num_classes < 1 or args.preset == 'original'):
+        p.error("--num_classes: an integer >= 1, for the U-Net presets (mnist32, svhn, unet28)")
+    if not 0.0 <= args.p_uncond <= 1.0:
+        p.error("--p_uncond is a probability")
     if args.modality is not None and args.preset not in MODALITY_PRESETS:
         p.error(f"--modality applies to the presets {', '.join(MODALITY_PRESETS)}")
     if args.preset == 'original' and args.modality is None:
@@ -78,11 +88,31 @@ def load_data(path, shape):
     return data
 
 
-def batches(data, batch_size, gen):
-    """The reference loaders' shuffle=True, drop_last=False epoch order."""
+def load_labelled(path, shape, num_classes):
+    """(x, label) of a .npz / .pt data file with 'x' [N, C, H, W] and 'label' [N] in 0..num_classes-1."""
+    d = torch.load(path, map_location='cpu') if path.endswith('.pt') else np.load(path)
+    for key in ('x', 'label'):
+        if key not in d:
+            raise ValueError(f"{path}: --num_classes needs a file with 'x' and 'label' (missing {key!r})")
+    x = torch.as_tensor(np.asarray(d['x']), dtype=torch.float32).contiguous()
+    label = torch.as_tensor(np.asarray(d['label'])).long().reshape(-1)
+    if x.dim() != 4 or tuple(x.shape[1:]) != shape:
+        raise ValueError(f"{path}: expected x [N, {shape[0]}, {shape[1]}, {shape[2]}], got {tuple(x.shape)}")
+    if x.shape[0] != label.shape[0] or x.shape[0] == 0:
+        raise ValueError(f"{path}: x and label must have the same, non-zero length")
+    if int(label.min()) < 0 or int(label.max()) >= num_classes:
+        raise ValueError(f"{path}: labels must be in 0..{num_classes - 1}")
+    return x, label
+
+
+def batches(data, batch_size, gen, label=None):
+    """The reference loaders' shuffle=True, drop_last=False epoch order; with `label`, (x, label) batches."""
     perm = torch.randperm(data.shape[0], generator=gen)
     for i in range(0, data.shape[0], batch_size):
-        yield {'x': data[perm[i:i + batch_size]]}
+        if label is not None:
+            yield data[perm[i:i + batch_size]], label[perm[i:i + batch_size]]
+        else:
+            yield {'x': data[perm[i:i + batch_size]]}
 
 
 def checkpoint(epoch, model, optimizer, best_loss):
@@ -90,6 +120,8 @@ def checkpoint(epoch, model, optimizer, best_loss):
     also 'ema_state_dict', the averaged weights under the model's keys (load_checkpoint(..., ema=True))."""
     ck = {'epoch': epoch, 'model_state_dict': model.state_dict(), 'optimizer_state_dict': optimizer.state_dict(),
           'best_loss': best_loss}
+    if getattr(model, 'num_classes', None) is not None:  # (a class-conditional net: load_checkpoint checks it)
+        ck['num_classes'] = model.num_classes
     if getattr(optimizer, 'ema_decay', None) is not None:
         ck['ema_state_dict'] = optimizer.ema_state_dict(model)
     return ck
@@ -101,8 +133,13 @@ def main(argv=None):
     ctor, shape, _ = PRESETS[args.preset]
     stem = args.stem
     device = torch.device(args.device)
-    data = load_data(args.data, shape)
-    model = ctor().to(device)
+    label = None
+    if args.num_classes is not None:
+        data, label = load_labelled(args.data, shape, args.num_classes)
+        model = ctor(num_classes=args.num_classes).to(device)
+    else:
+        data = load_data(args.data, shape)
+        model = ctor().to(device)
     optimizer = build_optimizer(args, model.parameters())
     schedule = CFMSchedule()
     start_epoch, best_loss = 0, float('inf')
@@ -121,7 +158,8 @@ def main(argv=None):
     gen = torch.Generator().manual_seed(args.seed)
     patience_counter = 0
     for epoch in range(start_epoch, args.epochs):
-        avg_loss = train_flow_matching_epoch(model, batches(data, args.batch_size, gen), optimizer, schedule, device)
+        avg_loss = train_flow_matching_epoch(model, batches(data, args.batch_size, gen, label), optimizer, schedule, device,
+                                             p_uncond=args.p_uncond)
         print(f"Epoch {epoch + 1}/{args.epochs} - Loss: {avg_loss:.4f}")
         if avg_loss < best_loss:
             best_loss, patience_counter = avg_loss, 0

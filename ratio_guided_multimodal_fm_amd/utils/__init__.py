@@ -29,16 +29,25 @@ def load_checkpoint(model, path, device='cpu', ema=False):
 
     ``ema=True`` loads the averaged weights instead: the ``'ema_state_dict'`` a dict checkpoint of
     ``train_flow --optimizer hip --ema_decay ...`` carries; a file without one is an error.
+
+    A dict checkpoint of a class-conditional net (``train_flow --num_classes K``) carries ``'num_classes'``: it must be
+    the model's (``ValueError`` otherwise, before any tensor is loaded) and is returned with the other entries.
     """
     ckpt = torch.load(path, map_location=device)
+    extra = {}
+    if isinstance(ckpt, dict) and ckpt.get('num_classes') is not None:
+        if ckpt['num_classes'] != getattr(model, 'num_classes', None):
+            raise ValueError(f"{path} holds a net with num_classes={ckpt['num_classes']}, the model was built with "
+                             f"num_classes={getattr(model, 'num_classes', None)} (--num_classes)")
+        extra = {'num_classes': ckpt['num_classes']}
     if ema:
         if not (isinstance(ckpt, dict) and 'ema_state_dict' in ckpt):
             raise KeyError(f"{path} has no 'ema_state_dict': it was not trained with --optimizer hip --ema_decay "
                            "(the ratio and classifier trainers write the averaged weights to <name>_ema.pth instead)")
         model.load_state_dict(ckpt['ema_state_dict'])
-        return {'epoch': ckpt.get('epoch', 0), 'best_loss': ckpt.get('best_loss', float('inf'))}
+        return {'epoch': ckpt.get('epoch', 0), 'best_loss': ckpt.get('best_loss', float('inf')), **extra}
     if isinstance(ckpt, dict) and 'model_state_dict' in ckpt:
         model.load_state_dict(ckpt['model_state_dict'])
-        return {'epoch': ckpt.get('epoch', 0), 'best_loss': ckpt.get('best_loss', float('inf'))}
+        return {'epoch': ckpt.get('epoch', 0), 'best_loss': ckpt.get('best_loss', float('inf')), **extra}
     model.load_state_dict(ckpt)
     return {}

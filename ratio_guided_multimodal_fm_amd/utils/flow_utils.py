@@ -61,28 +61,41 @@ class CFMSchedule:
         t = t.view(x_1.shape[0], *([1] * (x_1.dim() - 1)))
         return (1 - t) * x_0 + t * x_1, x_1 - x_0
 
-    def sample(self, model, num_samples, num_steps=100, device='cuda', solver='euler', sde_eta=0.0, sde_seed=None):
+    def sample(self, model, num_samples, num_steps=100, device='cuda', solver='euler', sde_eta=0.0, sde_seed=None,
+               labels=None, cfg_scale=1.0):
         """x0 ~ N(0, I) [n,1,28,28]; num_steps explicit Euler steps (reference :69-100), or midpoint steps with
         solver='midpoint' (two network evaluations each, second order; U-Net nets).  `sde_eta` > 0: Euler-Maruyama
         steps of the SDE with the same marginals (``paired_sampler``; U-Net nets, solver='euler'), the noise seeded by
-        `sde_seed` (None: drawn from torch's CPU generator after the start noise)."""
+        `sde_seed` (None: drawn from torch's CPU generator after the start noise).
+        `labels` (an integer tensor [num_samples], values 0..K of a net built with ``num_classes=K``; K is the null
+        label) and `cfg_scale` = w: classifier-free guidance, every stage advances by ``v_u + w (v_c - v_u)``
+        (``rgfm_sample_single_cfg``; w = 1: the conditional net alone, one evaluation per stage; w = 0: the
+        unconditional branch, the bits of the call without labels).  The start noise then has the net's own image shape;
+        the draws are those of the call without labels.  Neither (default): the call is what it was."""
         _engine._solver(solver, model)
         eta = _engine.check_sde(sde_eta, solver, (model,))
+        cfg = _engine.check_cfg(labels, cfg_scale, num_samples, model)
         model.eval()
         dev = _device(device)
-        x_t = torch.randn(num_samples, 1, 28, 28, device=dev)
-        return _engine.sample_single(model, x_t, num_steps, solver=solver, **_sde_kwargs(eta, sde_seed))
+        if cfg is None:
+            x_t = torch.randn(num_samples, 1, 28, 28, device=dev)
+            return _engine.sample_single(model, x_t, num_steps, solver=solver, **_sde_kwargs(eta, sde_seed))
+        x_t = torch.randn(num_samples, model.in_channels, model.img_size, model.img_size, device=dev)
+        return _engine.sample_single(model, x_t, num_steps, solver=solver, labels=labels, cfg_scale=cfg[1],
+                                     **_sde_kwargs(eta, sde_seed))
 
 
-    def log_prob(self, model, x, num_steps=100, solver='midpoint', n_probes=1, generator=None, batch_size=128):
+    def log_prob(self, model, x, num_steps=100, solver='midpoint', n_probes=1, generator=None, batch_size=128, labels=None):
         """``(logp [B], z [B, C, H, W])``: the log-density of the images `x` under the flow of `model`, and their
         latents.  `x` (data, t = 1) is integrated backwards to ``z = x(0)`` in `num_steps` steps of `solver` while the
         divergence of v is accumulated: ``logp = log N(z; 0, I) - int_0^1 div v dt`` (``rgfm_unet_log_prob``; exact
         fp32 arithmetic, no dropout whatever the module's mode).  The divergence is Hutchinson's estimate over
         `n_probes` Rademacher probes per image, drawn ONCE for the whole of `x` from `generator` (default: the
         device's torch generator) and fixed along the path; the images are then processed in chunks of `batch_size`,
-        so the result does not depend on `batch_size`.  U-Net nets only."""
+        so the result does not depend on `batch_size`.  U-Net nets only.  There is no labelled likelihood: `labels`
+        other than None raises ``RgfmError``; a class-conditional net is scored as its unconditional branch."""
         _check_likelihood_args(model, x, num_steps, solver, batch_size)
+        model._engine.no_labels(labels, "log_prob")
         if not isinstance(n_probes, int) or n_probes < 1:
             raise ValueError(f"n_probes must be an integer >= 1, got {n_probes!r} (encode() integrates without probes)")
         dev = _device(x.device)
@@ -159,19 +172,45 @@ def _velocity_train(model, x_t, t):
     return fwd(x_t, t)
 
 
-def train_flow_matching_epoch(model, dataloader, optimizer, schedule, device, modality='x'):
+def drop_labels(labels, num_classes, p_uncond, generator=None):
+    """Label dropout of classifier-free training: each label becomes the null label `num_classes` with probability
+    `p_uncond`, the decisions drawn as ``torch.rand(len(labels))`` on the labels' device (`generator`: default that
+    device's).  ``p_uncond=0`` draws all the same, so the stream of random numbers does not depend on the value."""
+    if not 0.0 <= float(p_uncond) <= 1.0:
+        raise ValueError(f"p_uncond must be a probability, got {p_uncond!r}")
+    u = torch.rand(labels.shape[0], device=labels.device, generator=generator)
+    return torch.where(u < float(p_uncond), torch.full_like(labels, int(num_classes)), labels)
+
+
+def train_flow_matching_epoch(model, dataloader, optimizer, schedule, device, modality='x', p_uncond=0.1):
     """One CFM epoch (reference :103-156): per batch t ~ U(0, 1), (x_t, u_t) = schedule.add_noise(x_1, t),
     MSE(model(x_t, t), u_t), backward, optimizer step.  Batches are dicts (``batch[modality]``) as the reference's
-    loaders yield, or plain tensors.  Returns the mean batch loss."""
+    loaders yield, or plain tensors.  Returns the mean batch loss.
+    Labelled batches -- ``(x, label)`` tuples / lists, or (for a net with classes) dicts with a ``'label'`` entry --
+    train a net built with ``num_classes=K`` class-conditionally: each label is replaced by the null label K with probability `p_uncond`
+    (``drop_labels``, drawn from the device's generator AFTER the batch's t and noise draws).  Without labels nothing
+    is drawn for them: the epoch's draws are what they were."""
     model.train()
     dev = _device(device)
     total_loss = 0.0
     num_batches = 0
     for batch in dataloader:
+        labels = None
+        if isinstance(batch, (tuple, list)):
+            batch, labels = batch
+        elif isinstance(batch, dict) and getattr(model, 'num_classes', None):
+            labels = batch.get('label')
         x_1 = (batch[modality] if isinstance(batch, dict) else batch).to(dev)
         t = torch.rand(x_1.shape[0], device=dev)
         x_t, u_t_target = schedule.add_noise(x_1, t)
-        v_t = _velocity_train(model, x_t, t)
+        if labels is not None:
+            K = getattr(model, 'num_classes', None)
+            if not K:
+                raise TypeError(f"labelled batches need a net built with num_classes; {type(model).__name__} has none")
+            labels = drop_labels(torch.as_tensor(labels).to(dev).reshape(-1).long(), K, p_uncond)
+            v_t = model.forward_train(x_t, t, labels)
+        else:
+            v_t = _velocity_train(model, x_t, t)
         loss = F.mse_loss(v_t, u_t_target)
         optimizer.zero_grad()
         loss.backward()
@@ -219,6 +258,51 @@ def sde_from_cli(args, sharded=False):
     if sharded:
         raise RgfmError("--sde_eta has no --sharded form: run the stochastic sampler on one device")
     return {'sde_eta': args.sde_eta, 'sde_seed': args.sde_seed}
+
+
+def add_label_args(p):
+    """--num_classes / --labels / --cfg_scale of the command-line tools (class-conditional nets)."""
+    p.add_argument('--num_classes', type=int, default=None,
+                   help='the flow checkpoints are class-conditional nets with this many classes (train_flow --num_classes); '
+                        'without --labels they run as their unconditional branch')
+    p.add_argument('--labels', type=str, default=None, metavar='{c,random,cycle}',
+                   help="labels of the samples (needs --num_classes, --guidance_method none, U-Net nets; not with --sharded): "
+                        "an integer c for every sample, 'random' (uniform over the classes, from the generator that --seed "
+                        "seeds) or 'cycle' (0, 1, ..., K-1, 0, ...); both nets of a pair take the same labels")
+    p.add_argument('--cfg_scale', type=float, default=1.0,
+                   help='classifier-free guidance scale w of --labels: v_u + w (v_c - v_u); 1 = the conditional net alone')
+
+
+def labels_from_cli(args, num_samples, sharded=False, guided=False, unet=True):
+    """Sampler keywords of --labels / --cfg_scale: {} without --labels, so that the call goes out as it always did."""
+    from .._lib import RgfmError
+    spec = getattr(args, 'labels', None)
+    if spec is None:
+        if getattr(args, 'cfg_scale', 1.0) != 1.0:
+            raise RgfmError("--cfg_scale needs --labels")
+        return {}
+    K = getattr(args, 'num_classes', None)
+    if not K:
+        raise RgfmError("--labels needs --num_classes (the checkpoints must be class-conditional nets)")
+    if sharded:
+        raise RgfmError("--labels has no --sharded form: run the labelled sampler on one device")
+    if guided:
+        raise RgfmError("--labels goes with --guidance_method none: a label-conditioned guided loop is not defined here")
+    if not unet:
+        raise RgfmError("--labels needs U-Net velocity nets (not --model original)")
+    if spec == 'random':
+        labels = torch.randint(0, K, (num_samples,))
+    elif spec == 'cycle':
+        labels = torch.arange(num_samples) % K
+    else:
+        try:
+            c = int(spec)
+        except ValueError:
+            raise RgfmError(f"--labels: an integer, 'random' or 'cycle' expected, got {spec!r}") from None
+        if not 0 <= c <= K:
+            raise RgfmError(f"--labels {c}: labels lie in 0..{K} ({K} is the null label)")
+        labels = torch.full((num_samples,), c, dtype=torch.long)
+    return {'labels': labels, 'cfg_scale': float(args.cfg_scale)}
 
 
 def add_ess_arg(p):
@@ -278,6 +362,25 @@ def _strength_kwargs(guidance_strength, guidance_schedule, rows, num_steps, solv
     return gamma, kw
 
 
+def _pair_cfg(labels, cfg_scale, num_samples, fm_x, fm_y, guidance_method, diagnostics, eta):
+    """The labels and scales of a paired call, checked before any draw and any device work: None without them (the call
+    is then today's), else ((labels_x, w_x), (labels_y, w_y))."""
+    from .._lib import RgfmError
+    lx, ly = labels if isinstance(labels, (tuple, list)) else (labels, labels)
+    wx, wy = cfg_scale if isinstance(cfg_scale, (tuple, list)) else (cfg_scale, cfg_scale)
+    cx = _engine.check_cfg(lx, wx, num_samples, fm_x)
+    cy = _engine.check_cfg(ly, wy, num_samples, fm_y)
+    if cx is None and cy is None:
+        return None
+    if guidance_method != 'none':
+        raise RgfmError(f"labels go with guidance_method='none' (the supervised pair), got {guidance_method!r}: a "
+                        "label-conditioned guided loop is not defined here; without labels the nets run unconditionally")
+    if diagnostics is not None or eta != 0.0:
+        raise RgfmError("the labelled pair takes no diagnostics and no sde_eta (CFMSchedule.sample has the stochastic "
+                        "labelled loop for one net)")
+    return cx or (None, 1.0), cy or (None, 1.0)
+
+
 def _stats(name, t):
     return f"{name}: min={t.min():.4f}, max={t.max():.4f}, mean={t.mean():.4f}"
 
@@ -285,8 +388,16 @@ def _stats(name, t):
 def paired_sampler(fm_x, fm_y, ratio_estimator, guidance_method, guidance_strength, num_samples,
                    num_steps, device, mc_batch_size, shape_x, shape_y, noise=None, verbose=True, solver='euler',
                    diagnostics=None, mc_pairing='paired', guidance_schedule=None, sde_eta=0.0, sde_seed=None,
-                   ess_floor=None):
+                   ess_floor=None, labels=None, cfg_scale=1.0):
     """Shared body of both paired samplers.
+
+    `labels` (``guidance_method='none'``, nets built with ``num_classes``): one integer tensor [num_samples] used for
+    BOTH nets -- the supervised coherent pair, the baseline ratio guidance is measured against -- or a pair
+    ``(labels_x, labels_y)``, either of which may be None.  `cfg_scale`: a float, or a pair ``(w_x, w_y)``; each net's
+    stages advance by ``v_u + w (v_c - v_u)`` (``rgfm_sample_two_cfg``; ``CFMSchedule.sample``).  The noise draws are
+    those of the call without labels.  Labels together with a guided method, `diagnostics`, `sde_eta` or sharded
+    launches raise ``RgfmError``: what the MC set of a label-conditioned guided loop should be is a research question,
+    not plumbing.  In those calls a class-conditional net runs without labels, as its unconditional branch.
 
     `ess_floor` (None, or a float with 1 <= ess_floor <= mc_batch_size): adaptive tempering of the MC importance
     weights (``guidance_method='mc_feng'``, ``rgfm_sample_pair_ess``).  At every guided stage a
@@ -336,6 +447,7 @@ def paired_sampler(fm_x, fm_y, ratio_estimator, guidance_method, guidance_streng
         _engine._check_cross((mc_batch_size, mc_batch_size), mc_batch_size, mc_batch_size, fm_x, fm_y)
     _engine._solver(solver, fm_x, fm_y)
     eta = _engine.check_sde(sde_eta, solver, (fm_x, fm_y))
+    cfg = _pair_cfg(labels, cfg_scale, num_samples, fm_x, fm_y, guidance_method, diagnostics, eta)
     guidance_strength, gs_kw = _strength_kwargs(guidance_strength, guidance_schedule, num_samples, num_steps, solver,
                                                 lambda: _device(device), (fm_x, fm_y))
     _ess_kwargs(ess_floor, guidance_method, False, mc_batch_size, (fm_x, fm_y), mc_pairing == 'cross', None, None)
@@ -382,6 +494,11 @@ def paired_sampler(fm_x, fm_y, ratio_estimator, guidance_method, guidance_streng
                 print(f"  MC ratios: min={mc_ratios.min():.4f}, max={mc_ratios.max():.4f}, "
                       f"mean={mc_ratios.mean():.4f}")
 
+    if cfg is not None:
+        (lx, wx), (ly, wy) = cfg
+        _engine.sample_two_cfg(fm_x, x_t, fm_y, y_t, num_steps, solver=solver, labels_x=lx, labels_y=ly, cfg_scale_x=wx,
+                               cfg_scale_y=wy)
+        return x_t, y_t
     if grad_guided:
         # "Gradient Log-Ratio" of the reference README (:159-164): v + gamma * grad log r(x_t, y_t) every step.  The
         # reference accepts only 'none' / 'mc_feng' and has no code for this mode; see rgfm_sample_pair_grad.
@@ -442,8 +559,10 @@ def shared_mc_sweep(fm_x, fm_y, ratio_estimator, guidance_method, strengths, num
 
 def sample_conditional(fm_target, ratio_estimator, condition, given='x', num_steps=100, guidance_strength=1.0,
                        mc_batch_size=256, mc_samples=None, device=None, guidance_method='mc_feng', solver='euler',
-                       diagnostics=None, guidance_schedule=None, sde_eta=0.0, sde_seed=None, ess_floor=None):
+                       diagnostics=None, guidance_schedule=None, sde_eta=0.0, sde_seed=None, ess_floor=None, labels=None):
     """Partners for `condition` in the other modality: one sample of `fm_target`'s modality per condition image.
+    (`labels` other than None raises ``RgfmError``: conditional sampling has no labelled form; a class-conditional
+    target runs as its unconditional branch.)
 
     ``given='x'``: `condition` is the estimator's x argument and the target is its y; ``given='y'`` the other way
     round.  Only the target net is integrated.
@@ -487,6 +606,9 @@ def sample_conditional(fm_target, ratio_estimator, condition, given='x', num_ste
         raise ValueError(f"given must be 'x' or 'y', got {given!r}")
     if guidance_method not in ('mc_feng', 'grad_log_ratio'):
         raise ValueError(f"guidance_method must be 'mc_feng' or 'grad_log_ratio', got {guidance_method!r}")
+    if labels is not None:
+        raise RgfmError("sample_conditional has no labelled form; without labels a class-conditional target runs as its "
+                        "unconditional branch")
     if not isinstance(fm_target._engine, _engine.UNetEngine):
         raise RgfmError(f"sample_conditional needs a U-Net target (FlexibleUNet and its presets); "
                         f"{type(fm_target).__name__} has no conditional sampler")
@@ -532,8 +654,9 @@ def sample_conditional(fm_target, ratio_estimator, condition, given='x', num_ste
 def sample_bimodal_guided(fm_x, fm_y, ratio_estimator=None, guidance_method='none',
                           guidance_strength=0.0, num_samples=16, num_steps=100, device='cuda',
                           mc_batch_size=64, solver='euler', diagnostics=None, mc_pairing='paired', guidance_schedule=None,
-                          sde_eta=0.0, sde_seed=None, ess_floor=None):
+                          sde_eta=0.0, sde_seed=None, ess_floor=None, labels=None, cfg_scale=1.0):
     """Pairs of 1x28x28 images, optional mc_feng guidance (reference :178-375).
+    `labels`, `cfg_scale` (``guidance_method='none'``): the class-conditional pair (``paired_sampler``).
 
     Returns ``(samples_x [n,1,28,28], samples_y [n,1,28,28])`` on `device`.
     Guidance is silently off when `ratio_estimator` is None, skipped on step 0
@@ -549,4 +672,4 @@ def sample_bimodal_guided(fm_x, fm_y, ratio_estimator=None, guidance_method='non
     return paired_sampler(fm_x, fm_y, ratio_estimator, guidance_method, guidance_strength,
                           num_samples, num_steps, device, mc_batch_size, (1, 28, 28), (1, 28, 28), solver=solver,
                           diagnostics=diagnostics, mc_pairing=mc_pairing, guidance_schedule=guidance_schedule,
-                          sde_eta=sde_eta, sde_seed=sde_seed, ess_floor=ess_floor)
+                          sde_eta=sde_eta, sde_seed=sde_seed, ess_floor=ess_floor, labels=labels, cfg_scale=cfg_scale)
